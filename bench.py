@@ -10,7 +10,13 @@ per-GPU micro-batch 8, GA 1): forward + shifted CE + backward + (N>1: bucketed R
 overlapped with backward) + global-norm clip 0.5 + AdamW (bf16 parameters and moments: the recipe's precision), on synthetic unit-token batches already
 resident in HBM. Weak scaling (per-GPU work fixed). Prints ONE JSON line on rank 0.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` (wall time of the K steps / K),
+`config` with the per-step HIP-event median and minimum, the mean loss and the last step's exposed communication.
+  --dump-outputs DIR  after the timed steps, writes what the last of them computed (loss, gradient norm, a fixed seeded sample
+                      of the parameters and AdamW moments) as DIR/<name>.npy: two builds compare output for output.
+  --full              everything below as well, measured after the timed region (minutes; the headline is unchanged).
+
+Extra objects on the line (--full):
   roofline     - dominant kernel (the gate|up projection GEMM with fused SwiGLU, M=8192 N=9728 K=896, 256x256 8-phase kernel): algorithmic flops per
                  launch / mean launch time measured here with HIP events on the launch stream, against the
                  2.5 PFLOP/s dense bf16 MFMA peak (MI355X_MICROARCH.md). `step_frac` is the whole-step
@@ -639,6 +645,8 @@ def bench_qwen1p5b(a, world, rank, dev):
     fence()
     t0 = time.perf_counter()
     for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:
+            held = hold_loss(trainer)
         step(a.warmup + i)
     fence()
     dt = time.perf_counter() - t0
@@ -646,6 +654,8 @@ def bench_qwen1p5b(a, world, rank, dev):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, trainer, release_loss(trainer, held), world)
     if rank == 0:
         toks = sum(counts[(a.warmup + i) % nb] for i in range(a.steps))
         flops = sum(w4_flops_per_batch(made[(a.warmup + i) % nb][1]) for i in range(a.steps))
@@ -697,6 +707,8 @@ def bench_dpo(a, world, rank, dev):
     fence()
     t0 = time.perf_counter()
     for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:
+            held = hold_loss(tr)
         tr.optimizer_step([batches[(a.warmup + i) % 4]], 5e-5)
     fence()
     dt = time.perf_counter() - t0
@@ -704,6 +716,8 @@ def bench_dpo(a, world, rank, dev):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, tr, release_loss(tr, held), world)
     if rank == 0:
         done = sum(toks[(a.warmup + i) % 4] for i in range(a.steps))
         emit(({
@@ -719,13 +733,175 @@ def bench_dpo(a, world, rank, dev):
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 21  # sampled elements per buffer of --dump-outputs: 3 buffers x 8 MB in float32
+
+
+def hold_loss(trainer):
+    """--dump-outputs, before the last timed step: set the loss accumulated so far aside (a device copy, no host sync), so
+    that the accumulator holds the loss of that step alone. `release_loss` returns it and restores the running sum."""
+    held = trainer._loss_acc.clone()
+    trainer._loss_acc.zero_()
+    return held
+
+
+def release_loss(trainer, held):
+    last = trainer._loss_acc.clone()
+    trainer._loss_acc += held
+    return last
+
+
+def dump_outputs(d, model, trainer, last_loss, world):
+    """--dump-outputs DIR: what the last timed optimizer step hands back to its caller, as .npy files under DIR - its loss
+    (`loss`, float64, over all ranks), the gradient norm it clipped with (`grad_norm`, float64),
+    and the parameters and AdamW moments it left (`params`, `exp_avg`, `exp_avg_sq`, float32). Those three are sampled at
+    fixed positions: each tensor, in the model's parameter order, gives elements in proportion to its size, drawn with seed 0,
+    so that the same arguments read the same positions in every run and every build. Every rank calls this (N > 1 has
+    collectives in it); rank 0 writes."""
+    import math
+    import numpy as np
+    loss = last_loss.double()
+    if world > 1:  # over the ranks as SLAMTrainer._log reports it
+        dist.all_reduce(loss)
+        if not trainer.args.average_tokens_across_devices or trainer._loss_is_rank_mean:
+            loss /= world
+        trainer._gather_optimizer_state()  # rs_ag: the moments of the other ranks' shards
+    model.engine.join()
+    if world > 1 and dist.get_rank() != 0:
+        return
+    g = torch.Generator().manual_seed(0)
+    keys = list(model.key_map)
+    sizes = [math.prod(model.key_map[k][1]) for k in keys]
+    total = sum(sizes)
+    idx = [torch.randint(0, n, (max(1, DUMP_SAMPLE * n // total),), generator=g).sort().values.to(model.device) for n in sizes]
+    out = {"loss": loss.cpu().numpy(), "grad_norm": trainer.norm_out[:1].double().cpu().numpy()}
+    for name, buf in (("params", model.flat_params), ("exp_avg", trainer.exp_avg), ("exp_avg_sq", trainer.exp_avg_sq)):
+        out[name] = torch.cat([model._view(buf, k).reshape(-1)[i].float() for k, i in zip(keys, idx)]).cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(d, name + ".npy"), arr)
+    print(f"[bench] outputs of the last timed step in {d}: " + ", ".join(f"{k} {v.shape}" for k, v in out.items()),
+          file=sys.stderr, flush=True)
+
+
+def full_measurements(a, model, trainer, args, rank, world, dev, step, fence, dp_on, out):
+    """--full: everything beside the headline, measured after the timed region on EVERY rank (the kernel probes touch the
+    optimizer state identically on all ranks, the extra steps contain the data-parallel collectives); rank 0 adds it to `out`."""
+    # SURVEY.md §8d protocol (discard >= 10 steps, median of >= 50): whatever K the launcher asked for, 50 more optimizer steps
+    # follow the timed region, each between two HIP events; their median is `config.ms_per_step_median_50` (this rank)
+    n50 = int(os.environ.get("SLAM_BENCH_MEDIAN_STEPS", "50"))  # (the one-GPU gloo plumbing check sets a few: its steps take seconds)
+    marks50 = [torch.cuda.Event(enable_timing=True) for _ in range(n50 + 1)]
+    marks50[0].record()
+    for i in range(n50):
+        step(a.warmup + a.steps + i)
+        marks50[i + 1].record()
+    fence()
+    per50 = sorted(marks50[i].elapsed_time(marks50[i + 1]) for i in range(n50))
+    ms_median_50 = per50[n50 // 2]
+    base_i = a.warmup + a.steps + n50
+    # The dominant kernel where it runs: three more optimizer steps with timing events around every gate|up projection
+    # launch (slam_gateup_launch_ms) - 72 launches between their real neighbours, the launches rocprofv3 reports for the step.
+    # (A stand-alone loop of the same launch reads 137-162 us from run to run: 50 back-to-back launches of the
+    # hottest kernel move with the power state of the part, profiles/r3_experiments/README.md, profiles/r4_vendor_gemm.md.)
+    model.engine.set_option("time_gateup", 1)
+    model.engine.set_option("time_param_waits", 1)  # rs_ag: the stall of the forward behind the parameter all-gather
+    trainer.reducer.time_buckets = dp_on
+    in_step_ms = []
+    for i in range(3):
+        step(base_i + i)
+        in_step_ms += model.engine.gateup_launch_ms(24)
+    model.engine.set_option("time_gateup", 0)
+    # ... and three more with a timing-event pair around EVERY launch family, on the stream each launch goes to
+    # (slam_family_ms): the in-step duration of the dgrad chain and of the weight-gradient GEMMs on the side stream
+    model.engine.set_option("time_families", 1)
+    fam = {}
+    for i in range(3):
+        step(base_i + 3 + i)
+        for name, ms_ in model.engine.family_ms():
+            fam.setdefault(name, []).append(ms_)
+    model.engine.set_option("time_families", 0)
+    param_gather_ms = model.engine.param_wait_ms()
+    model.engine.set_option("time_param_waits", 0)
+    bucket_ms = trainer.reducer.bucket_ms() if dp_on else []  # this rank's collectives of the last of those steps
+    trainer.reducer.time_buckets = False
+    hbm = hbm_kernel_rates(model, trainer)
+    # the extras are single-GPU context for the headline (GA 16, host boundary, bf16 state); a multi-rank run measures `value` only
+    extras = None if (a.no_extras or world > 1) else extra_measurements(model, trainer, rank, dev, a)
+    if rank == 0:
+        trained_tokens = B * T * a.grad_accum
+        value = out["value"]
+        out["config"].update({
+            "ms_per_step_median_50": round(ms_median_50, 3), "median_50_steps": n50,  # 50 further steps after the timed region (SURVEY.md §8d: median of >= 50)
+            "tokens_per_s_median_50": round(trained_tokens / (ms_median_50 * 1e-3), 1),  # this rank
+            # [what, offset, elements, ms on the communication stream] per bucket, rank 0, one step after the timed region
+            "bucket_comm_ms": bucket_ms,
+            # rs_ag: stall of the forwards behind the parameter all-gather, summed over the 3 instrumented steps
+            "exposed_param_gather_ms_3_steps": round(param_gather_ms, 3)})
+        roof = dominant_kernel_roofline(model)
+        ms_in = sum(in_step_ms) / len(in_step_ms)
+        flops_gu = 2.0 * (B * T) * (2 * 4864) * 896
+        roof["standalone"] = {"ms_per_launch": roof["ms_per_launch"], "achieved": roof["achieved"], "frac": roof["frac"],
+                              "what": "50 back-to-back launches on probe buffers after the run"}
+        roof["ms_per_launch"] = round(ms_in, 4)
+        roof["achieved"] = round(flops_gu / (ms_in * 1e-3) / 1e12, 1)
+        roof["frac"] = round(flops_gu / (ms_in * 1e-3) / PEAK_BF16, 4)
+        roof["measured"] = (f"mean of {len(in_step_ms)} launches inside 3 optimizer steps after the timed region, HIP timing events "
+                            "around each launch on its stream (slam_gateup_launch_ms); min "
+                            f"{min(in_step_ms) * 1e3:.1f} us, max {max(in_step_ms) * 1e3:.1f} us")
+        roof["step_frac"] = round(value / world * FLOP_PER_TOKEN / PEAK_BF16, 4)
+        roof["step_tflops_per_gpu"] = round(value / world * FLOP_PER_TOKEN / 1e12, 1)
+        roof["kernels"] = kernel_rooflines(model)
+        roof["in_step"] = in_step_table(fam)
+        # the headline `frac` above is the gate|up projection (the kernel with the most flops and the best fraction); the kernel
+        # with the most LAUNCH TIME per step sits next to it, not three levels down (VERDICT r4 item 6)
+        big = roof["in_step"]["largest_kernel_by_time"] or {}
+        roof["dominant_by_time"] = {"kernel": big.get("kernel"), "ms_per_step": big.get("ms_per_step"), "frac": big.get("frac_of_peak_in_step"),
+                                    "what": "sum of in-step launch durations of this kernel (side-stream launches overlap the caller's stream); frac = its flops / that time / peak"}
+        out["roofline"] = roof
+        out["hbm_kernels"] = hbm
+        if extras is not None:
+            out["extras"] = extras
+            # the attention (and the other shape-dependent) kernels on the recipe's own data modes, next to the dense in-step table
+            roof["in_step"]["recipe_data_modes_us"] = {k: extras[k]["in_step_us"] for k in ("packed_ga16", "padded") if k in extras}
+            if "fp32_master_optimizer" in extras:  # like-for-like with rounds 1-3 (fp32 master + fp32 moments), first-class
+                out["value_fp32_master_optimizer"] = extras["fp32_master_optimizer"]["tokens_per_s"]
+    # N > 1 (or SLAM_DP_FORCE=1 on one rank): the exchange variants, LAST - the line above is complete without them. A variant
+    # that fails or hangs (none of these collectives has met a second GPU from the authoring side) must not cost the run its
+    # headline: errors are recorded per variant, and a watchdog emits the line as it stands after SLAM_BENCH_DP_VARIANT_BUDGET_S
+    if dp_on and os.environ.get("SLAM_BENCH_DP_VARIANTS", "1") == "1":
+        import threading
+        rows = []
+
+        def bail():
+            if rank == 0:
+                out.setdefault("extras", {})["dp_variants"] = rows + [{"error": "watchdog: the variant table did not finish in time"}]
+                emit(out)
+            os._exit(0)
+        dog = threading.Timer(float(os.environ.get("SLAM_BENCH_DP_VARIANT_BUDGET_S", "120")), bail)
+        dog.daemon = True
+        dog.start()
+        try:
+            dp_variant_table(model, trainer, args, rank, world, dev, rows)
+        except Exception as e:  # noqa: BLE001 - recorded on the line
+            rows.append({"error": f"{type(e).__name__}: {e}"[:300]})
+        dog.cancel()
+        if rank == 0:
+            out.setdefault("extras", {})["dp_variants"] = rows
+            out["extras"]["nccl_env"] = {k: os.environ.get(k) for k in ("NCCL_MAX_NCHANNELS", "NCCL_MIN_NCHANNELS", "NCCL_ALGO", "NCCL_PROTO", "GPU_MAX_HW_QUEUES")}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)   # SURVEY.md §8d protocol: discard >= 10 steps, median of >= 50
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the GA=16 and recipe-optimizer measurements after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beside the headline: 50 more steps for the median, in-step "
+                         "kernel times, rooflines, HBM rates, the extras, the N > 1 exchange variants and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, gradient norm, a fixed sample of the parameters and AdamW "
+                         "moments) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the GA=16 and recipe-optimizer measurements after the timed region")
     ap.add_argument("--grad-accum", type=int, default=1)
     ap.add_argument("--workload", default="slam358m", choices=["slam358m", "qwen1p5b", "dpo"],
                     help="slam358m = BASELINE.json configs[1] (the headline metric); qwen1p5b = configs[3]-shaped extra; dpo = configs[4] extra")
@@ -827,6 +1003,8 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:
+            held = hold_loss(trainer)
         step(a.warmup + i)
         marks[i + 1].record()
     fence()
@@ -835,6 +1013,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, trainer, release_loss(trainer, held), world)
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
     ms_median = per_step[len(per_step) // 2]
     loss = float(trainer._loss_acc) / max(1, trainer._loss_n)
@@ -847,50 +1027,7 @@ def main():
         t = torch.tensor([loss], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         loss = float(t)
-
-    # SURVEY.md §8d protocol (discard >= 10 steps, median of >= 50): whatever K the launcher asked for, 50 more optimizer steps
-    # follow the timed region, each between two HIP events; their median is `config.ms_per_step_median_50` (this rank)
-    n50 = int(os.environ.get("SLAM_BENCH_MEDIAN_STEPS", "50"))  # (the one-GPU gloo plumbing check sets a few: its steps take seconds)
-    marks50 = [torch.cuda.Event(enable_timing=True) for _ in range(n50 + 1)]
-    marks50[0].record()
-    for i in range(n50):
-        step(a.warmup + a.steps + i)
-        marks50[i + 1].record()
-    fence()
-    per50 = sorted(marks50[i].elapsed_time(marks50[i + 1]) for i in range(n50))
-    ms_median_50 = per50[n50 // 2]
-    base_i = a.warmup + a.steps + n50
-    # after the timed region, on EVERY rank: the kernel probes touch the optimizer state (identically on all ranks), the
-    # extra steps contain the data-parallel collectives
-    # The dominant kernel where it runs: three more optimizer steps with timing events around every gate|up projection
-    # launch (slam_gateup_launch_ms) - 72 launches between their real neighbours, the launches rocprofv3 reports for the step.
-    # (A stand-alone loop of the same launch reads 137-162 us from run to run: 50 back-to-back launches of the
-    # hottest kernel move with the power state of the part, profiles/r3_experiments/README.md, profiles/r4_vendor_gemm.md.)
-    model.engine.set_option("time_gateup", 1)
-    model.engine.set_option("time_param_waits", 1)  # rs_ag: the stall of the forward behind the parameter all-gather
     dp_on = world > 1 or trainer.reducer.force  # SLAM_DP_FORCE=1: the collective path on a 1-rank group (tools/dp1_bench.sh)
-    trainer.reducer.time_buckets = dp_on
-    in_step_ms = []
-    for i in range(3):
-        step(base_i + i)
-        in_step_ms += model.engine.gateup_launch_ms(24)
-    model.engine.set_option("time_gateup", 0)
-    # ... and three more with a timing-event pair around EVERY launch family, on the stream each launch goes to
-    # (slam_family_ms): the in-step duration of the dgrad chain and of the weight-gradient GEMMs on the side stream
-    model.engine.set_option("time_families", 1)
-    fam = {}
-    for i in range(3):
-        step(base_i + 3 + i)
-        for name, ms_ in model.engine.family_ms():
-            fam.setdefault(name, []).append(ms_)
-    model.engine.set_option("time_families", 0)
-    param_gather_ms = model.engine.param_wait_ms()
-    model.engine.set_option("time_param_waits", 0)
-    bucket_ms = trainer.reducer.bucket_ms() if dp_on else []  # this rank's collectives of the last of those steps
-    trainer.reducer.time_buckets = False
-    hbm = hbm_kernel_rates(model, trainer)
-    # the extras are single-GPU context for the headline (GA 16, host boundary, bf16 state); a multi-rank run measures `value` only
-    extras = None if (a.no_extras or world > 1) else extra_measurements(model, trainer, rank, dev, a)
     out = None
     if rank == 0:
         ms = dt / a.steps * 1e3
@@ -906,76 +1043,21 @@ def main():
                        "grad_accum": a.grad_accum, "parallelism": f"dp{world}",
                        "optimizer": ("AdamW fp32 master+moments" if args.optim_state_dtype == "float32" else
                                      "AdamW on bf16 parameters with bf16 moments - the recipe's own precision (reference config/model/slam.yaml:9); "
-                                     "fp32-master variant in extras") + ", clip 0.5",
+                                     "fp32-master variant in extras, --full") + ", clip 0.5",
                        "final_loss": round(loss, 4),
                        "optimizer_state_dtype": args.optim_state_dtype,
                        "ms_per_step_median": round(ms_median, 3), "ms_per_step_min": round(per_step[0], 3),
-                       "ms_per_step_median_50": round(ms_median_50, 3), "median_50_steps": n50,  # 50 further steps after the timed region (median of >= 50)
-                       "tokens_per_s_median_50": round(trained_tokens / (ms_median_50 * 1e-3), 1),  # this rank
                        "tokens_per_s_median_step": round(trained_tokens / (ms_median * 1e-3), 1),  # this rank
                        "ddp_algo": args.ddp_algo if dp_on else None,
-                       "exposed_comm_ms_last_step": round(exposed, 3),
-                       # [what, offset, elements, ms on the communication stream] per bucket, rank 0, one step after the timed region
-                       "bucket_comm_ms": bucket_ms,
-                       # rs_ag: stall of the forwards behind the parameter all-gather, summed over the 3 instrumented steps
-                       "exposed_param_gather_ms_3_steps": round(param_gather_ms, 3)},
+                       "exposed_comm_ms_last_step": round(exposed, 3)},
         }
-        roof = dominant_kernel_roofline(model)
-        ms_in = sum(in_step_ms) / len(in_step_ms)
-        flops_gu = 2.0 * (B * T) * (2 * 4864) * 896
-        roof["standalone"] = {"ms_per_launch": roof["ms_per_launch"], "achieved": roof["achieved"], "frac": roof["frac"],
-                              "what": "50 back-to-back launches on probe buffers after the run"}
-        roof["ms_per_launch"] = round(ms_in, 4)
-        roof["achieved"] = round(flops_gu / (ms_in * 1e-3) / 1e12, 1)
-        roof["frac"] = round(flops_gu / (ms_in * 1e-3) / PEAK_BF16, 4)
-        roof["measured"] = (f"mean of {len(in_step_ms)} launches inside 3 optimizer steps after the timed region, HIP timing events "
-                            "around each launch on its stream (slam_gateup_launch_ms); min "
-                            f"{min(in_step_ms) * 1e3:.1f} us, max {max(in_step_ms) * 1e3:.1f} us")
-        roof["step_frac"] = round(value / world * FLOP_PER_TOKEN / PEAK_BF16, 4)
-        roof["step_tflops_per_gpu"] = round(value / world * FLOP_PER_TOKEN / 1e12, 1)
-        roof["kernels"] = kernel_rooflines(model)
-        roof["in_step"] = in_step_table(fam)
-        # the headline `frac` above is the gate|up projection (the kernel with the most flops and the best fraction); the kernel
-        # with the most LAUNCH TIME per step sits next to it, not three levels down
-        big = roof["in_step"]["largest_kernel_by_time"] or {}
-        roof["dominant_by_time"] = {"kernel": big.get("kernel"), "ms_per_step": big.get("ms_per_step"), "frac": big.get("frac_of_peak_in_step"),
-                                    "what": "sum of in-step launch durations of this kernel (side-stream launches overlap the caller's stream); frac = its flops / that time / peak"}
-        out["roofline"] = roof
-        out["hbm_kernels"] = hbm
-        if extras is not None:
-            out["extras"] = extras
-            # the attention (and the other shape-dependent) kernels on the recipe's own data modes, next to the dense in-step table
-            roof["in_step"]["recipe_data_modes_us"] = {k: extras[k]["in_step_us"] for k in ("packed_ga16", "padded") if k in extras}
-            if "fp32_master_optimizer" in extras:  # like-for-like with rounds 1-3 (fp32 master + fp32 moments), first-class
-                out["value_fp32_master_optimizer"] = extras["fp32_master_optimizer"]["tokens_per_s"]
-    # N > 1 (or SLAM_DP_FORCE=1 on one rank): the exchange variants, LAST - the line above is complete without them. A variant
-    # that fails or hangs (none of these collectives has met a second GPU from the authoring side) must not cost the run its
-    # headline: errors are recorded per variant, and a watchdog emits the line as it stands after SLAM_BENCH_DP_VARIANT_BUDGET_S
-    if dp_on and os.environ.get("SLAM_BENCH_DP_VARIANTS", "1") == "1":
-        import threading
-        rows = []
-
-        def bail():
-            if rank == 0:
-                out.setdefault("extras", {})["dp_variants"] = rows + [{"error": "watchdog: the variant table did not finish in time"}]
-                emit(out)
-            os._exit(0)
-        dog = threading.Timer(float(os.environ.get("SLAM_BENCH_DP_VARIANT_BUDGET_S", "120")), bail)
-        dog.daemon = True
-        dog.start()
-        try:
-            dp_variant_table(model, trainer, args, rank, world, dev, rows)
-        except Exception as e:  # noqa: BLE001 - recorded on the line
-            rows.append({"error": f"{type(e).__name__}: {e}"[:300]})
-        dog.cancel()
-        if rank == 0:
-            out.setdefault("extras", {})["dp_variants"] = rows
-            out["extras"]["nccl_env"] = {k: os.environ.get(k) for k in ("NCCL_MAX_NCHANNELS", "NCCL_MIN_NCHANNELS", "NCCL_ALGO", "NCCL_PROTO", "GPU_MAX_HW_QUEUES")}
-    if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+    if a.full:
+        full_measurements(a, model, trainer, args, rank, world, dev, step, fence, dp_on, out)
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
             del trainer, model
             torch.cuda.empty_cache()
             out["cpu_baseline"] = cpu_baseline()
+    if rank == 0:
         emit(out)
     if dist.is_initialized():
         dist.barrier()

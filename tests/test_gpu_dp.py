@@ -65,6 +65,10 @@ if force:
     dist.destroy_process_group()
 '''
 
+# The data-parallel step refuses fewer than 8 hardware queues (slamkit_amd.check_hw_queues). The workers are fresh processes:
+# they get at least that many, whatever the launching environment pinned.
+HW_QUEUES = str(max(8, int(os.environ.get("GPU_MAX_HW_QUEUES", "8") or 8)))
+
 
 def _free_port():
     s = socket.socket()
@@ -79,7 +83,7 @@ def _run(tmp_path, name, force, comm="", algo="", osd="", **extra_env):
     out = str(tmp_path / f"{name}.pt")
     env = dict(os.environ, SLAM_ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), OUT=out,
                SLAM_DP_FORCE="1" if force else "0", COMM=comm, ALGO=algo, OSD=osd, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
-               HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), **extra_env)
+               HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), GPU_MAX_HW_QUEUES=HW_QUEUES, **extra_env)
     r = subprocess.run([sys.executable, "-c", WORKER], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     return torch.load(out)
@@ -205,7 +209,7 @@ def test_dpo_trainer_forced_single_rank_rccl_is_bit_identical(tmp_path, osd):
         out = str(tmp_path / f"{name}.pt")
         e = dict(os.environ, SLAM_ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), OUT=out, OSD=osd,
                  SLAM_DP_FORCE="1" if force else "0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
-                 HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), **env)
+                 HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"), GPU_MAX_HW_QUEUES=HW_QUEUES, **env)
         r = subprocess.run([sys.executable, "-c", DPO_WORKER], env=e, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         return torch.load(out)

@@ -19,7 +19,7 @@ for st in "$@"; do
     smoke) (timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3) > ${O}_smoke.log; tail -1 ${O}_smoke.log;;
     b|q) name=${rest%%:*}; envs=${rest#*:}; [ "$envs" = "$rest" ] && envs=""
        wl=""; [ "$kind" = q ] && wl="--workload qwen1p5b"
-       (env $(echo $envs | tr ',' ' ') timeout 500 python bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline ${BENCH_ARGS:---no-extras} $wl 2>${O}_bench_${name}.err | tail -1) > ${O}_bench_${name}.json
+       (env $(echo $envs | tr ',' ' ') timeout 500 python bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline ${BENCH_ARGS:---full --no-extras} $wl 2>${O}_bench_${name}.err | tail -1) > ${O}_bench_${name}.json
        python - <<P
 import json
 try:
@@ -44,9 +44,9 @@ P
        cd $R; python tools/probes/power_or_stall_summary.py ${O}_pmcx ${O}_pmcx_manifest.json ${O}_pmcx.md | tail -14;;
     dp2) # plumbing check of bench.py's N > 1 path on the one GPU: two ranks on device 0, exchange over gloo (NOT a measurement)
        (env SLAM_BENCH_BACKEND=gloo SLAM_BENCH_DEVICE=0 SLAM_BENCH_MEDIAN_STEPS=3 SLAM_BENCH_DP_VARIANT_STEPS=1 timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>${O}_dp2.err | tail -1) > ${O}_dp2.json
+          --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --full 2>${O}_dp2.err | tail -1) > ${O}_dp2.json
        python -c "import json;d=json.load(open('${O}_dp2.json'));print('dp2', d['n_gpus'], d['value'], d['config'].get('ms_per_step_median_50'), json.dumps(d.get('extras'))[:1500])" || tail -5 ${O}_dp2.err;;
-    prof) cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/${O}_prof -o r4 -- python $OLDPWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $OLDPWD/${O}_prof.log 2>&1; cd $OLDPWD; ls ${O}_prof | head;;
+    prof) cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/${O}_prof -o r4 -- python $OLDPWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --full > $OLDPWD/${O}_prof.log 2>&1; cd $OLDPWD; ls ${O}_prof | head;;
     *) echo "unknown stage $st";;
   esac
 done

@@ -6,7 +6,7 @@ import sys
 src, dst, title = sys.argv[1:4]
 import os
 CMD = os.environ.get("PROF_CMD", "`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline "
-                     "--no-extras` on 1x MI355X (7 optimizer steps of Slam-358M B=8 T=1024, plus the probes bench.py runs after the timed region - 90 "
+                     "--no-extras --full` on 1x MI355X (7 optimizer steps of Slam-358M B=8 T=1024, plus the probes bench.py runs after the timed region - 90 "
                      "gate|up GEMM launches of the roofline probe, the RMSNorm / AdamW / gradient-norm launches of `hbm_kernels` - and model init). "
                      "With the wgrad side stream the kernels of the two streams overlap: per-kernel times are launch durations, their sum is more "
                      "than the step.")

@@ -2,7 +2,7 @@
 python tools/trace_breakdown.py gpurun_out/fin_prof/r3_kernel_trace.csv profiles/NAME.md "title" [steps=5] [instrumented steps to skip=3]
 
 Optimizer steps are delimited by the AdamW launch; the steps of the timed region are the LAST `nsteps` steps before the
-probes bench.py runs afterwards (every step before them is identical work). For each step: wall time (first kernel start
+probes bench.py --full runs afterwards (every step before them is identical work). For each step: wall time (first kernel start
 to AdamW end), the same split into forward (to the loss kernel), backward (to the last gradient kernel) and optimizer,
 busy time per stream (union of launch intervals), and per launch family: stream, launches per step, average duration,
 milliseconds per step. Launch durations on two overlapping streams add up to more than the wall time; the per-stream busy
@@ -92,7 +92,7 @@ ns = len(steps)
 mean = lambda v: sum(v) / len(v)
 with open(dst, "w") as f:
     f.write(f"# {title}\n\n")
-    f.write(f"Source: `{src}` (rocprofv3 --kernel-trace of `bench.py --steps 5 --warmup 2`); the {ns} optimizer steps of the timed region (the {skip_last} instrumented steps and the probes that follow are left out).\n\n")
+    f.write(f"Source: `{src}` (rocprofv3 --kernel-trace of `bench.py --full --steps 5 --warmup 2`); the {ns} optimizer steps of the timed region (the {skip_last} instrumented steps and the probes that follow are left out).\n\n")
     f.write(f"Step wall time (first kernel start → AdamW end): **{mean(walls)/1e6:.2f} ms** = forward {mean(fw)/1e6:.2f} + backward {mean(bw)/1e6:.2f} + optimizer {mean(op)/1e6:.2f} ms"
             " (rocprofv3 serialises nothing but adds ≈2-3 % to the un-profiled step).\n\n")
     f.write("| stream (HSA queue) | busy ms / step (union of its launch intervals) |\n|---|---|\n")
