@@ -97,6 +97,24 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
                  const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
                  float* loss_out, void* logits_out, slam_stream_t stream);
 
+/* ---- KV-cached generation: HF GenerationMixin.generate with use_cache (the reference's speech_lm.py / metric_utils.py call
+ * model.generate(input_ids, attention_mask, bad_words_ids, temperature, top_k, max_new_tokens)) ---------------------------
+ * The cache is caller-owned like the workspace: bf16, per layer K[max_batch][n_kv_heads][capacity][head_dim] followed by V of
+ * the same shape (L x 2 x max_batch x n_kv_heads x capacity x head_dim x 2 bytes); K is stored after RoPE.
+ * slam_prefill: ids int64 [B][T] right-padded, lens int32 [B] device (1 <= lens[b] <= T). Runs the forward's layer loop over
+ *   the batch, copies each layer's K / V rows 0 .. lens[b]-1 into the cache and writes fp32 logits [B][vocab] of each row's
+ *   last prompt token (one head launch over B rows). Replaces the cache contents.
+ * slam_decode_step: ids int64 [B] device, one token per row at position lens[b]; appends its K / V, attends over rows
+ *   0 .. lens[b], writes fp32 logits [B][vocab] and increments lens ON THE DEVICE (no host synchronisation). B must be the
+ *   prefill's B and the workspace at least 2 B tokens. SLAM_ESTATE without a bound cache, without a prefill, or when the
+ *   step could pass `capacity` (the host bound: prefill T + steps so far).
+ * Both overwrite the forward activations (slam_backward then needs a new slam_forward). */
+size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity);
+int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity);
+int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
+                 slam_stream_t stream);
+int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B, float* logits_out, slam_stream_t stream);
+
 /* loss.backward(): accumulates d(loss*grad_scale)/dparam into the bound fp32 gradient buffer.
  * bucket_layers = decoder layers per gradient bucket for the callback (<=0: one bucket). */
 int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_bucket_cb cb, void* user,
@@ -285,6 +303,21 @@ int slam_op_gemm_tn(const void* dY, const void* X, float* dW, int accumulate, in
  * background != 0 selects the plans slam_backward uses on its weight-gradient stream */
 int slam_op_gemm_tn_image(const void* dY, const void* X, float* dW, void* dW_bf16, int accumulate, int M, int N, int K,
                           float* ws, int background, slam_stream_t s);
+/* decode-time projection Y[M,N] = X[M,K] W[N,K]^T (+bias[N]) (+resid[M,N]) for small M (the weight-streaming kernel of
+ * slam_decode_step): Y is fp32 when y_f32, else bf16; K a multiple of 8. ws: fp32 split-K partials,
+ * slam_op_gemm_skinny_workspace(M, N, K) bytes for the full split (less: fewer splits). Bit-identical run to run. */
+size_t slam_op_gemm_skinny_workspace(int M, int N, int K);
+int slam_op_gemm_skinny(const void* X, const void* W, void* Y, int y_f32, const void* bias, const void* resid, int M, int N, int K,
+                        float* ws, size_t ws_bytes, slam_stream_t s);
+/* one decode step of attention: qkv fp32 [B][(nH + 2 nKV) head_dim] projection without bias, bias bf16 [..] (nullable), lens
+ * int32 [B] device = the new token's position. Bias and RoPE are applied in fp32 (queries pre-scaled as in the forward), the
+ * new K / V rows are written to row lens[b] of k_cache / v_cache (bf16 [B][nKV][capacity][head_dim]) and o (bf16
+ * [B][nH head_dim]) attends over rows 0 .. lens[b]. kv_bound >= max(lens) + 1, <= capacity.
+ * ws: slam_op_attn_decode_workspace(B, nH, nKV, head_dim, kv_bound) bytes. */
+size_t slam_op_attn_decode_workspace(int B, int nH, int nKV, int head_dim, int kv_bound);
+int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens, void* k_cache, void* v_cache, void* o, void* ws,
+                        size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity, int kv_bound, float theta,
+                        slam_stream_t s);
 int slam_op_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int M, int H, float eps, slam_stream_t s);
 size_t slam_op_rmsnorm_bwd_workspace(int M, int H);
 int slam_op_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,

@@ -1,0 +1,430 @@
+// KV-cached generation kernels (slam_prefill / slam_decode_step, include/slam_engine.h):
+//  * gemm_skinny: Y[M][N] = X[M][K] W[N][K]^T for a handful of rows. A decode step reads every weight once, so the launch is
+//    a weight stream: each wave owns 16 W rows over a K range, loads them 16 B per lane straight into the B operand of
+//    v_mfma_f32_16x16x32_bf16 (X rows padded to 16 form the A operand), and splits K until the grid covers the chip. The
+//    split-K partials are summed in split order by a second launch: no atomics, the same bits every run.
+//  * attn_decode: bias + RoPE of the new token's q / k on the fp32 projection (one rounding, the forward's tables and query
+//    pre-scale), K / V appended to the cache, split-KV flash decoding with every query head of a KV group in one pass over the
+//    group's keys, partial (m, l, o) merged in the log2 domain by attn_decode_combine in split order.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int SK_WAVES = 4;  // waves per block, one 16-row W tile each
+constexpr int SK_U = 4;      // 32-deep K steps per unrolled group: 4 x 16 B loads in flight per lane
+constexpr int SK_MIN_STEPS = 4;
+constexpr int SK_TARGET_BLOCKS = 1024;
+
+inline unsigned nblk(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+template <bool F32OUT>
+SLAM_DEVICE void skinny_store(void* Y, const bf16_t* bias, const bf16_t* resid, int m, int n, int N, float v) {
+  const size_t i = (size_t)m * N + n;
+  if (bias) v += bf16_to_f32(bias[n]);
+  if (resid) v += bf16_to_f32(resid[i]);
+  if (F32OUT) reinterpret_cast<float*>(Y)[i] = v;
+  else reinterpret_cast<bf16_t*>(Y)[i] = f32_to_bf16(v);
+}
+
+// grid (ceil(N / 64), splits, ceil(M / 64)); MT = 16-row tiles of X per 64-row chunk
+template <int MT, bool F32OUT>
+__global__ __launch_bounds__(256) void gemm_skinny_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
+                                                          void* __restrict__ Y, float* __restrict__ part,
+                                                          const bf16_t* __restrict__ bias, const bf16_t* __restrict__ resid,
+                                                          int M, int N, int K, int kps) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = (blockIdx.x * SK_WAVES + wave) * 16;
+  if (n0 >= N) return;
+  const int q = lane >> 4, j = lane & 15;
+  const int m_base = blockIdx.z * 64;
+  const int kb = blockIdx.y * kps * 32;
+  const int ke = min(K, kb + kps * 32);
+  const int nr = min(n0 + j, N - 1);  // tail rows re-read the last row; their results are not stored
+  const bf16_t* wrow = W + (size_t)nr * K + 8 * q;
+  const bf16_t* xrow[MT];
+  bool xv[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = m_base + 16 * t + j;
+    xv[t] = m < M;
+    xrow[t] = X + (size_t)(xv[t] ? m : 0) * K + 8 * q;
+  }
+  f32x4_t acc[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const uint4 zero = {0u, 0u, 0u, 0u};
+  for (int k = kb; k < ke; k += 32 * SK_U) {
+    uint4 w[SK_U];
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u) {
+      const int kk = k + 32 * u;
+      w[u] = (kk + 8 * q < ke) ? *reinterpret_cast<const uint4*>(wrow + kk) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < SK_U; ++u) {
+      const int kk = k + 32 * u;
+      const bool kv = kk + 8 * q < ke;
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        const uint4 a = (kv && xv[t]) ? *reinterpret_cast<const uint4*>(xrow[t] + kk) : zero;
+        acc[t] = mfma16(a, w[u], acc[t]);
+      }
+    }
+  }
+  // lane holds acc[t][r] = Y[m_base + 16 t + 4 q + r][n0 + j]
+  const int n = n0 + j;
+  if (n >= N) return;
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = m_base + 16 * t + 4 * q + r;
+      if (m >= M) continue;
+      if (part) part[((size_t)blockIdx.y * M + m) * N + n] = acc[t][r];
+      else skinny_store<F32OUT>(Y, bias, resid, m, n, N, acc[t][r]);
+    }
+}
+
+// Y = sum over splits in split order (+ bias + residual)
+template <bool F32OUT>
+__global__ __launch_bounds__(256) void skinny_reduce_kernel(const float* __restrict__ part, int S, void* __restrict__ Y,
+                                                            const bf16_t* __restrict__ bias, const bf16_t* __restrict__ resid,
+                                                            int M, int N) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t MN = (size_t)M * N;
+  if (i >= MN) return;
+  float v = 0.f;
+  for (int s = 0; s < S; ++s) v += part[s * MN + i];
+  skinny_store<F32OUT>(Y, bias, resid, (int)(i / N), (int)(i % N), N, v);
+}
+
+struct SkinnyPlan {
+  int splits, kps;
+};
+
+// splits of the 32-deep K steps so that the grid has about SK_TARGET_BLOCKS blocks of SK_MIN_STEPS steps or more; fewer when
+// the partials would not fit in ws_bytes
+SkinnyPlan skinny_plan(int M, int N, int K, size_t ws_bytes) {
+  const int ksteps = (K + 31) / 32;
+  const int tiles = (int)nblk((size_t)N, 16 * SK_WAVES) * (int)nblk((size_t)M, 64);
+  const int target = (SK_TARGET_BLOCKS + tiles - 1) / tiles;
+  int kps = (ksteps + target - 1) / target;
+  if (kps < SK_MIN_STEPS) kps = SK_MIN_STEPS;
+  int S = (ksteps + kps - 1) / kps;
+  const size_t per = (size_t)M * N * sizeof(float);
+  if (S > 1 && (size_t)S * per > ws_bytes) {
+    const int smax = (int)(ws_bytes / per);
+    if (smax < 2) {
+      S = 1;
+    } else {
+      kps = (ksteps + smax - 1) / smax;
+      S = (ksteps + kps - 1) / kps;
+    }
+  }
+  if (S <= 1) { S = 1; kps = ksteps; }
+  return {S, kps};
+}
+
+template <bool F32OUT>
+int launch_skinny(const bf16_t* X, const bf16_t* W, void* Y, const bf16_t* bias, const bf16_t* resid, int M, int N, int K,
+                  float* ws, size_t ws_bytes, hipStream_t st) {
+  const SkinnyPlan p = skinny_plan(M, N, K, ws ? ws_bytes : 0);
+  float* part = p.splits > 1 ? ws : nullptr;
+  const dim3 grid(nblk((size_t)N, 16 * SK_WAVES), p.splits, nblk((size_t)M, 64));
+  const int mt = ((M < 64 ? M : 64) + 15) / 16;
+#define SK_CASE(T) \
+  case T: gemm_skinny_kernel<T, F32OUT><<<grid, 256, 0, st>>>(X, W, Y, part, bias, resid, M, N, K, p.kps); break;
+  switch (mt) {
+    SK_CASE(1)
+    SK_CASE(2)
+    SK_CASE(3)
+    default: gemm_skinny_kernel<4, F32OUT><<<grid, 256, 0, st>>>(X, W, Y, part, bias, resid, M, N, K, p.kps); break;
+  }
+#undef SK_CASE
+  if (part) skinny_reduce_kernel<F32OUT><<<nblk((size_t)M * N, 256), 256, 0, st>>>(part, p.splits, Y, bias, resid, M, N);
+  return (int)hipGetLastError();
+}
+
+// ---- decode attention ---------------------------------------------------------------------------------------------------
+SLAM_DEVICE float rescale(float m, float mn) { return m == -INFINITY ? 0.f : fast_exp2(m - mn); }
+
+// dims d0 .. d0 + 7 of one head (columns c0 ..) of the fp32 projection row, + bias, rotate-half RoPE with tables C / S
+template <int HD>
+SLAM_DEVICE void rope8(const float* row, const bf16_t* bias, int c0, int d0, const float* C, const float* S, float* out) {
+  constexpr int half = HD / 2;
+  const bool lo = d0 < half;
+  const int dp = lo ? d0 + half : d0 - half;  // partner dims
+  const int t0 = lo ? d0 : d0 - half;         // table index
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float x = row[c0 + d0 + i], p = row[c0 + dp + i];
+    if (bias) { x += bf16_to_f32(bias[c0 + d0 + i]); p += bf16_to_f32(bias[c0 + dp + i]); }
+    const float c = C[t0 + i], s = S[t0 + i];
+    out[i] = lo ? x * c - p * s : x * c + p * s;
+  }
+}
+
+SLAM_DEVICE void round8(float* v) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = bf16_to_f32(f32_to_bf16(v[i]));
+}
+
+// grid (ns, nKV, B), 256 threads. Key j of the chunk is handled by the LG = HD / 8 lanes of one slot (8 dims each); every slot
+// keeps (m, l, o) for the G query heads of the group. part: [B][nH][ns][HD + 2] = o (unnormalised), m, l.
+template <int HD, int G>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restrict__ qkv, const bf16_t* __restrict__ bias,
+                                                          const float* __restrict__ cs, const float* __restrict__ sn,
+                                                          const float* __restrict__ csq, const float* __restrict__ snq,
+                                                          const int* __restrict__ lens, bf16_t* __restrict__ kc,
+                                                          bf16_t* __restrict__ vc, int cap, int nH, int nKV, int chunk, int ns,
+                                                          float* __restrict__ part) {
+  constexpr int LG = HD / 8, SLOTS = 64 / LG, half = HD / 2;
+  __shared__ float red[4][G][HD + 2];
+  const int s = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane % LG, slot = lane / LG, d0 = sub * 8;
+  const int QKV = (nH + 2 * nKV) * HD;
+  const int pos = lens[b];
+  const int nkeys = min(pos + 1, cap);
+  const float* row = qkv + (size_t)b * QKV;
+  const float* C = cs + (size_t)b * half;
+  const float* S = sn + (size_t)b * half;
+  float qf[G][8];
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    rope8<HD>(row, bias, (g * G + i) * HD, d0, csq + (size_t)b * half, snq + (size_t)b * half, qf[i]);
+    round8(qf[i]);  // the forward stores q pre-scaled in bf16
+  }
+  float m_[G], l_[G], o_[G][8];
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    m_[i] = -INFINITY;
+    l_[i] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o_[i][e] = 0.f;
+  }
+  const size_t cbase = ((size_t)b * nKV + g) * cap;
+  const int c_end = min(s * chunk + chunk, nkeys);
+  for (int j = s * chunk + wave * SLOTS + slot; j < c_end; j += 4 * SLOTS) {
+    float kf[8], vf[8];
+    bf16_t* kp = kc + (cbase + j) * HD + d0;
+    bf16_t* vp = vc + (cbase + j) * HD + d0;
+    if (j == pos) {  // the new token: rotate, round once, append
+      rope8<HD>(row, bias, (nH + g) * HD, d0, C, S, kf);
+      const int cv = (nH + nKV + g) * HD + d0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vf[e] = row[cv + e] + (bias ? bf16_to_f32(bias[cv + e]) : 0.f);
+      const uint4 kb = pack_bf16x8(kf), vb = pack_bf16x8(vf);
+      *reinterpret_cast<uint4*>(kp) = kb;
+      *reinterpret_cast<uint4*>(vp) = vb;
+      unpack_bf16x8(kb, kf);
+      unpack_bf16x8(vb, vf);
+    } else {
+      unpack_bf16x8(*reinterpret_cast<const uint4*>(kp), kf);
+      unpack_bf16x8(*reinterpret_cast<const uint4*>(vp), vf);
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      float sc = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sc += qf[i][e] * kf[e];
+#pragma unroll
+      for (int o = 1; o < LG; o <<= 1) sc += __shfl_xor(sc, o, 64);
+      const float mn = fmaxf(m_[i], sc);
+      const float a = rescale(m_[i], mn), p = fast_exp2(sc - mn);
+      l_[i] = l_[i] * a + p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o_[i][e] = o_[i][e] * a + p * vf[e];
+      m_[i] = mn;
+    }
+  }
+  // slots of a wave: xor butterfly (both partners compute the same sums)
+#pragma unroll
+  for (int off = LG; off < 64; off <<= 1)
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      const float m2 = __shfl_xor(m_[i], off, 64), l2 = __shfl_xor(l_[i], off, 64);
+      const float mn = fmaxf(m_[i], m2);
+      const float a = rescale(m_[i], mn), c = rescale(m2, mn);
+      l_[i] = l_[i] * a + l2 * c;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o_[i][e] = o_[i][e] * a + __shfl_xor(o_[i][e], off, 64) * c;
+      m_[i] = mn;
+    }
+  if (slot == 0) {
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[wave][i][d0 + e] = o_[i][e];
+      if (sub == 0) { red[wave][i][HD] = m_[i]; red[wave][i][HD + 1] = l_[i]; }
+    }
+  }
+  __syncthreads();
+  // waves in wave order
+  const int t = threadIdx.x;
+  if (t < G * LG) {
+    const int i = t / LG, e0 = (t % LG) * 8;
+    float mm = -INFINITY;
+    for (int w = 0; w < 4; ++w) mm = fmaxf(mm, red[w][i][HD]);
+    float l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int w = 0; w < 4; ++w) {
+      const float a = rescale(red[w][i][HD], mm);
+      l += red[w][i][HD + 1] * a;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] += red[w][i][e0 + e] * a;
+    }
+    float* dst = part + (((size_t)b * nH + g * G + i) * ns + s) * (HD + 2);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dst[e0 + e] = o[e];
+    if (e0 == 0) { dst[HD] = mm; dst[HD + 1] = l; }
+  }
+}
+
+// grid (nH, B), HD threads: merge the ns partials of one (row, head) in split order
+template <int HD>
+__global__ __launch_bounds__(128) void attn_decode_combine_kernel(const float* __restrict__ part, int ns, int nH,
+                                                                  bf16_t* __restrict__ out) {
+  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
+  const float* p = part + ((size_t)b * nH + h) * ns * (HD + 2);
+  float mm = -INFINITY;
+  for (int s = 0; s < ns; ++s) mm = fmaxf(mm, p[s * (HD + 2) + HD]);
+  float l = 0.f, o = 0.f;
+  for (int s = 0; s < ns; ++s) {
+    const float a = rescale(p[s * (HD + 2) + HD], mm);
+    l += p[s * (HD + 2) + HD + 1] * a;
+    o += p[s * (HD + 2) + d] * a;
+  }
+  out[((size_t)b * nH + h) * HD + d] = f32_to_bf16(o / l);
+}
+
+// ---- small helpers of prefill / decode -------------------------------------------------------------------------------------
+// K / V columns of rows t < lens[b] of one layer's qkv [B*T][QKV] -> cache rows t of (b, kv head); grid (.., B)
+__global__ __launch_bounds__(256) void kv_scatter_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
+                                                         bf16_t* __restrict__ vc, const int* __restrict__ lens, int T, int nH,
+                                                         int nKV, int hd, int cap) {
+  const int b = blockIdx.y;
+  const int per_row = 2 * nKV * hd / 8;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int t = idx / per_row, c = idx % per_row;
+  if (t >= T || t >= lens[b] || t >= cap) return;
+  const int kv = c / (nKV * hd / 8), r = c % (nKV * hd / 8);
+  const int g = r / (hd / 8), d = (r % (hd / 8)) * 8;
+  const int QKV = (nH + 2 * nKV) * hd;
+  const uint4 v = *reinterpret_cast<const uint4*>(qkv + ((size_t)b * T + t) * QKV + (nH + kv * nKV + g) * hd + d);
+  bf16_t* dst = (kv ? vc : kc) + (((size_t)b * nKV + g) * cap + t) * hd + d;
+  *reinterpret_cast<uint4*>(dst) = v;
+}
+
+// dst[b] = src[b * T + clamp(lens[b] - 1, 0, T - 1)], rows of H bf16
+__global__ __launch_bounds__(256) void gather_last_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst,
+                                                          const int* __restrict__ lens, int B, int T, int H) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int per = H / 8;
+  if (idx >= B * per) return;
+  const int b = idx / per, c = idx % per;
+  const int t = min(max(lens[b] - 1, 0), T - 1);
+  *reinterpret_cast<uint4*>(dst + (size_t)b * H + 8 * c) =
+      *reinterpret_cast<const uint4*>(src + ((size_t)b * T + t) * H + 8 * c);
+}
+
+__global__ void lens_to_pos_kernel(const int* __restrict__ lens, int64_t* __restrict__ pos, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) pos[b] = lens[b];
+}
+
+__global__ void lens_inc_kernel(int* __restrict__ lens, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) lens[b] = lens[b] + 1;
+}
+
+}  // namespace
+
+namespace slam {
+
+size_t gemm_skinny_workspace_bytes(int M, int N, int K) {
+  const SkinnyPlan p = skinny_plan(M, N, K, (size_t)-1);
+  return p.splits > 1 ? (size_t)p.splits * M * N * sizeof(float) : 0;
+}
+
+int gemm_skinny(const bf16_t* X, const bf16_t* W, bf16_t* Y, float* Yf, const bf16_t* bias, const bf16_t* resid, int M, int N,
+                int K, float* ws, size_t ws_bytes, hipStream_t st) {
+  if (M <= 0 || N <= 0 || K <= 0 || (K & 7) || (!Y == !Yf)) return -1;
+  if (((uintptr_t)X | (uintptr_t)W) & 15) return -1;
+  if (Yf) return launch_skinny<true>(X, W, Yf, bias, resid, M, N, K, ws, ws_bytes, st);
+  return launch_skinny<false>(X, W, Y, bias, resid, M, N, K, ws, ws_bytes, st);
+}
+
+size_t attn_decode_part_bytes(int B, int nH, int head_dim, int ns) {
+  return (size_t)B * nH * ns * (head_dim + 2) * sizeof(float);
+}
+
+// keys per split: multiples of 64, about 512 blocks over (splits, KV heads, rows), more keys per split when the partials
+// would not fit in part_bytes
+int attn_decode_chunk(int B, int nH, int nKV, int head_dim, int kv_bound, size_t part_bytes) {
+  const int target = 512 / (B * nKV) > 1 ? 512 / (B * nKV) : 1;
+  int chunk = ((kv_bound + target - 1) / target + 63) / 64 * 64;
+  if (chunk < 64) chunk = 64;
+  while (attn_decode_part_bytes(B, nH, head_dim, (kv_bound + chunk - 1) / chunk) > part_bytes) {
+    if (chunk >= kv_bound) return -1;
+    chunk *= 2;
+  }
+  return chunk;
+}
+
+int attn_decode(const float* qkv, const bf16_t* bias, const float* cs, const float* sn, const float* csq, const float* snq,
+                const int* lens, bf16_t* kc, bf16_t* vc, int cap, int B, int nH, int nKV, int head_dim, int kv_bound, bf16_t* o,
+                float* part, size_t part_bytes, hipStream_t st) {
+  if (B <= 0 || nKV <= 0 || nH % nKV || kv_bound <= 0 || kv_bound > cap) return -1;
+  const int G = nH / nKV;
+  if ((head_dim != 64 && head_dim != 128) || G > 8) return -1;
+  const int chunk = attn_decode_chunk(B, nH, nKV, head_dim, kv_bound, part_bytes);
+  if (chunk <= 0) return -3;
+  const int ns = (kv_bound + chunk - 1) / chunk;
+  const dim3 grid(ns, nKV, B);
+#define AD_CASE(HD, GG)                                                                                                  \
+  case GG:                                                                                                               \
+    attn_decode_kernel<HD, GG><<<grid, 256, 0, st>>>(qkv, bias, cs, sn, csq, snq, lens, kc, vc, cap, nH, nKV, chunk, ns, \
+                                                     part);                                                              \
+    break;
+#define AD_SWITCH(HD) \
+  switch (G) { AD_CASE(HD, 1) AD_CASE(HD, 2) AD_CASE(HD, 3) AD_CASE(HD, 4) AD_CASE(HD, 5) AD_CASE(HD, 6) AD_CASE(HD, 7) AD_CASE(HD, 8) }
+  if (head_dim == 64) {
+    AD_SWITCH(64)
+    attn_decode_combine_kernel<64><<<dim3(nH, B), 64, 0, st>>>(part, ns, nH, o);
+  } else {
+    AD_SWITCH(128)
+    attn_decode_combine_kernel<128><<<dim3(nH, B), 128, 0, st>>>(part, ns, nH, o);
+  }
+#undef AD_SWITCH
+#undef AD_CASE
+  return (int)hipGetLastError();
+}
+
+int kv_scatter(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, const int* lens, int B, int T, int nH, int nKV, int head_dim, int cap,
+               hipStream_t st) {
+  const size_t n = (size_t)T * (2 * nKV * head_dim / 8);
+  kv_scatter_kernel<<<dim3(nblk(n, 256), B), 256, 0, st>>>(qkv, kc, vc, lens, T, nH, nKV, head_dim, cap);
+  return (int)hipGetLastError();
+}
+
+int gather_last_rows(const bf16_t* src, bf16_t* dst, const int* lens, int B, int T, int H, hipStream_t st) {
+  if (H & 7) return -1;
+  gather_last_kernel<<<nblk((size_t)B * (H / 8), 256), 256, 0, st>>>(src, dst, lens, B, T, H);
+  return (int)hipGetLastError();
+}
+
+int lens_to_pos(const int* lens, int64_t* pos, int B, hipStream_t st) {
+  lens_to_pos_kernel<<<nblk((size_t)B, 256), 256, 0, st>>>(lens, pos, B);
+  return (int)hipGetLastError();
+}
+
+int lens_inc(int* lens, int B, hipStream_t st) {
+  lens_inc_kernel<<<nblk((size_t)B, 256), 256, 0, st>>>(lens, B);
+  return (int)hipGetLastError();
+}
+
+}  // namespace slam

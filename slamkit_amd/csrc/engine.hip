@@ -180,6 +180,13 @@ struct SlamEngine {
   const int* cur_seg_s = nullptr;
   const int* cur_seg_e = nullptr;
 
+  // KV cache of slam_prefill / slam_decode_step (caller-owned): per layer K[kv_bmax][nKV][kv_cap][hd] then V (same shape)
+  bf16_t* kv = nullptr;
+  int kv_bmax = 0, kv_cap = 0;
+  int kv_B = 0;          // rows of the last prefill
+  int kv_hi = 0;         // host bound of every row's cached length: the prefill's T, + 1 per decode step
+  bool kv_ready = false; // a prefill filled the bound cache
+
   int fail(int code, const std::string& m) {
     err = m;
     return code;
@@ -496,6 +503,67 @@ int adamw_model(SlamEngine* h, int mode, float* master, void* m, void* v, const 
   return r;
 }
 
+// The decoder layer loop of a forward over M = B*T tokens: segments, attention plan, RoPE tables, embedding and every layer,
+// leaving the last residual stream in hs[L] (slam_forward and slam_prefill continue from there).
+int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_ids, const int32_t* seg_start,
+                   const int32_t* seg_end, int M, int T, hipStream_t st) {
+  const SlamModelDesc& d = h->d;
+  const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads;
+  const bf16_t* P = h->params;
+  if (seg_start) {
+    h->cur_seg_s = seg_start;
+    h->cur_seg_e = seg_end;
+  } else {
+    seg_fill_kernel<<<(M + 255) / 256, 256, 0, st>>>(h->seg_s, h->seg_e, M, T);
+    h->cur_seg_s = h->seg_s;
+    h->cur_seg_e = h->seg_e;
+  }
+  if (h->time_families) h->fam_marks.clear();  // the marks of a step = its last forward + backward
+  CK(attn_plan(h->cur_seg_s, h->cur_seg_e, M, d.head_dim, h->attn_tune, h->attn_plan_buf, st));
+  // queries are stored pre-scaled by head_dim^-0.5 * log2(e) (folded into their rotation tables: one rounding), so the
+  // attention kernels' scores leave the matrix pipe in the exp2 domain
+  const float qscale = 1.44269504088896340736f / sqrtf((float)d.head_dim);
+  CK(rope_table(position_ids, M, T, d.head_dim, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
+  CK(wait_chunk(h, 0, st));
+  CK(wait_params(h, h->off_embed, h->lo[0].ln1, st));
+  CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
+  for (int l = 0; l < L; ++l) {
+    const LayerOff& o = h->lo[l];
+    LayerAct& a = h->la[l];
+    CK(wait_chunk(h, 1 + l, st));
+    CK(wait_params(h, o.ln1, o.ln1 + h->layer_stride, st));
+    TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
+    if (d.head_dim == 64 && (H % 64 == 0) && (h->QKV % 128 == 0)) {  // bias + RoPE fused into the projection epilogue
+      TK(F_QKV_FWD, st, gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
+    } else {
+      const int slot = fam_begin(h, F_QKV_FWD, st);
+      CK(gemm_nt(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, nullptr, M, h->QKV, H, st));
+      CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, d.head_dim, h->cosb, h->sinb, 0, st, nH, qscale));
+      fam_end(h, slot, st);
+    }
+    TK(F_ATTN_FWD, st, attn_fwd(a.qkv, a.o, a.lse, h->cur_seg_s, h->attn_plan_buf, h->attn_tune, M, nH, nKV, d.head_dim, st));
+    TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, nullptr, h->hs[l], M, H, nH * d.head_dim, st));
+    TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
+    const bool timed = h->time_gateup && h->tg_ev.size() == (size_t)(2 * L);
+    if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l], st));
+    {
+      const int slot = fam_begin(h, F_GATEUP_FWD, st);
+      if (h->fuse_swiglu) {
+        CK(gemm_nt_swiglu(a.x2, P + o.wgu, a.gu, a.act, M, 2 * I, H, st));
+      } else {
+        CK(gemm_nt(a.x2, P + o.wgu, a.gu, nullptr, nullptr, M, 2 * I, H, st));
+        CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
+      }
+      fam_end(h, slot, st);
+    }
+    if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l + 1], st));
+    TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], nullptr, a.hmid, M, H, I, st));
+  }
+  CK(join_optimizer(h, st));
+  CK(join_params(h, st));
+  return SLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -662,62 +730,11 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
   const int M = (int)M64;
   const SlamModelDesc& d = h->d;
   hipStream_t st = (hipStream_t)stream;
-  const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads;
+  const int H = d.hidden, L = d.n_layers;
   const bf16_t* P = h->params;
   h->have_fwd = false;
   GemmTuneScope tune_scope(&h->gemm_tune);
-
-  if (seg_start) {
-    h->cur_seg_s = seg_start;
-    h->cur_seg_e = seg_end;
-  } else {
-    seg_fill_kernel<<<(M + 255) / 256, 256, 0, st>>>(h->seg_s, h->seg_e, M, T);
-    h->cur_seg_s = h->seg_s;
-    h->cur_seg_e = h->seg_e;
-  }
-  if (h->time_families) h->fam_marks.clear();  // the marks of a step = its last forward + backward
-  CK(attn_plan(h->cur_seg_s, h->cur_seg_e, M, d.head_dim, h->attn_tune, h->attn_plan_buf, st));
-  // queries are stored pre-scaled by head_dim^-0.5 * log2(e) (folded into their rotation tables: one rounding), so the
-  // attention kernels' scores leave the matrix pipe in the exp2 domain
-  const float qscale = 1.44269504088896340736f / sqrtf((float)d.head_dim);
-  CK(rope_table(position_ids, M, T, d.head_dim, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
-  CK(wait_chunk(h, 0, st));
-  CK(wait_params(h, h->off_embed, h->lo[0].ln1, st));
-  CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
-  for (int l = 0; l < L; ++l) {
-    const LayerOff& o = h->lo[l];
-    LayerAct& a = h->la[l];
-    CK(wait_chunk(h, 1 + l, st));
-    CK(wait_params(h, o.ln1, o.ln1 + h->layer_stride, st));
-    TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
-    if (d.head_dim == 64 && (H % 64 == 0) && (h->QKV % 128 == 0)) {  // bias + RoPE fused into the projection epilogue
-      TK(F_QKV_FWD, st, gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
-    } else {
-      const int slot = fam_begin(h, F_QKV_FWD, st);
-      CK(gemm_nt(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, nullptr, M, h->QKV, H, st));
-      CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, d.head_dim, h->cosb, h->sinb, 0, st, nH, qscale));
-      fam_end(h, slot, st);
-    }
-    TK(F_ATTN_FWD, st, attn_fwd(a.qkv, a.o, a.lse, h->cur_seg_s, h->attn_plan_buf, h->attn_tune, M, nH, nKV, d.head_dim, st));
-    TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, nullptr, h->hs[l], M, H, nH * d.head_dim, st));
-    TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
-    const bool timed = h->time_gateup && h->tg_ev.size() == (size_t)(2 * L);
-    if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l], st));
-    {
-      const int slot = fam_begin(h, F_GATEUP_FWD, st);
-      if (h->fuse_swiglu) {
-        CK(gemm_nt_swiglu(a.x2, P + o.wgu, a.gu, a.act, M, 2 * I, H, st));
-      } else {
-        CK(gemm_nt(a.x2, P + o.wgu, a.gu, nullptr, nullptr, M, 2 * I, H, st));
-        CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
-      }
-      fam_end(h, slot, st);
-    }
-    if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l + 1], st));
-    TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], nullptr, a.hmid, M, H, I, st));
-  }
-  CK(join_optimizer(h, st));
-  CK(join_params(h, st));
+  CK(forward_layers(h, ids, position_ids, seg_start, seg_end, M, T, st));
   TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, M, H, d.rms_eps, st));
   const int VP = h->vpad;
   TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_embed, h->logits, nullptr, nullptr, M, VP, H, st));
@@ -733,6 +750,112 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
   h->T = T;
   h->last_ids = ids;
   h->have_fwd = true;
+  return SLAM_OK;
+}
+
+/* ---- KV-cached generation ---------------------------------------------------------------------------------------------*/
+size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity) {
+  if (!h || max_batch <= 0 || capacity <= 0) return 0;
+  const SlamModelDesc& d = h->d;
+  return (size_t)d.n_layers * 2 * max_batch * d.n_kv_heads * capacity * d.head_dim * sizeof(bf16_t);
+}
+int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity) {
+  if (!h || !cache || max_batch <= 0 || capacity <= 0) return SLAM_EINVAL;
+  if (((uintptr_t)cache) & 255) return h->fail(SLAM_EINVAL, "KV cache must be 256-byte aligned");
+  if (bytes < slam_kv_cache_bytes(h, max_batch, capacity)) return h->fail(SLAM_ENOMEM, "KV cache too small");
+  h->kv = (bf16_t*)cache;
+  h->kv_bmax = max_batch;
+  h->kv_cap = capacity;
+  h->kv_ready = false;
+  return SLAM_OK;
+}
+
+namespace {
+// K and V of layer l in the bound cache
+bf16_t* kv_k(SlamEngine* h, int l) {
+  return h->kv + (size_t)l * 2 * h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim;
+}
+bf16_t* kv_v(SlamEngine* h, int l) { return kv_k(h, l) + (size_t)h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim; }
+
+// decode-time projection: the weight-streaming kernel up to SKINNY_MAX_M rows (split-K partials in the backward-only dact
+// buffer), the tiled GEMM beyond; fp32 outputs always take the streaming kernel (in 64-row chunks)
+int decode_proj(SlamEngine* h, const bf16_t* X, const bf16_t* W, bf16_t* Y, float* Yf, const bf16_t* bias, const bf16_t* resid,
+                int M, int N, int K, hipStream_t st) {
+  if (Yf || M <= SKINNY_MAX_M)
+    return gemm_skinny(X, W, Y, Yf, bias, resid, M, N, K, (float*)h->dact, (size_t)h->max_tokens * h->d.intermediate * sizeof(bf16_t), st);
+  return gemm_nt(X, W, Y, bias, resid, M, N, K, st);
+}
+}  // namespace
+
+int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
+                 slam_stream_t stream) {
+  if (!h || !ids || !lens || !logits_out || B <= 0 || T <= 0) return SLAM_EINVAL;
+  if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
+  if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+  if (B > h->kv_bmax || T > h->kv_cap) return h->fail(SLAM_EINVAL, "prefill batch exceeds the bound KV cache");
+  if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
+  const SlamModelDesc& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = d.hidden, L = d.n_layers, M = B * T;
+  const bf16_t* P = h->params;
+  h->have_fwd = false;
+  h->kv_ready = false;
+  GemmTuneScope tune_scope(&h->gemm_tune);
+  CK(forward_layers(h, ids, nullptr, nullptr, nullptr, M, T, st));
+  for (int l = 0; l < L; ++l)
+    CK(kv_scatter(h->la[l].qkv, kv_k(h, l), kv_v(h, l), lens, B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st));
+  // logits of each row's last prompt token only: gather, final norm, one fp32 head launch over B rows
+  CK(gather_last_rows(h->hs[L], h->dx, lens, B, T, H, st));
+  CK(rmsnorm_fwd(h->dx, P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
+  CK(decode_proj(h, h->hf, P + h->off_embed, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
+  h->kv_B = B;
+  h->kv_hi = T;
+  h->kv_ready = true;
+  return SLAM_OK;
+}
+
+int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B, float* logits_out, slam_stream_t stream) {
+  if (!h || !ids || !lens || !logits_out || B <= 0) return SLAM_EINVAL;
+  if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
+  if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+  if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_decode_step needs a slam_prefill into the bound cache first");
+  if (B != h->kv_B) return h->fail(SLAM_EINVAL, "decode batch differs from the prefill batch");
+  if (h->kv_hi + 1 > h->kv_cap) return h->fail(SLAM_ESTATE, "decode step past the KV cache capacity");
+  if ((int64_t)2 * B > h->max_tokens) return h->fail(SLAM_ENOMEM, "decode needs a workspace of at least 2 B tokens");
+  const SlamModelDesc& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads, hd = d.head_dim;
+  const bf16_t* P = h->params;
+  h->have_fwd = false;
+  GemmTuneScope tune_scope(&h->gemm_tune);
+  CK(join_optimizer(h, st));
+  CK(join_params(h, st));
+  // scratch in buffers only backward reads: fp32 QKV projection (dqkv: B x QKV x 4 bytes <= 2B x QKV x 2), the rows' int64
+  // positions (nlse), attention split partials (the logits buffer)
+  float* qkvf = (float*)h->dqkv;
+  int64_t* pos = (int64_t*)h->nlse;
+  const float qscale = 1.44269504088896340736f / sqrtf((float)hd);
+  CK(lens_to_pos(lens, pos, B, st));
+  CK(rope_table(pos, B, 1, hd, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
+  CK(embed_fwd(ids, P + h->off_embed, h->hs[0], B, H, d.vocab, st));
+  const size_t part_bytes = (size_t)h->max_tokens * h->vpad * sizeof(bf16_t);
+  for (int l = 0; l < L; ++l) {
+    const LayerOff& o = h->lo[l];
+    LayerAct& a = h->la[l];
+    CK(rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, B, H, d.rms_eps, st));
+    CK(decode_proj(h, a.x1, P + o.wqkv, nullptr, qkvf, nullptr, nullptr, B, h->QKV, H, st));
+    CK(attn_decode(qkvf, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, nH, nKV, hd,
+                   h->kv_hi + 1, a.o, (float*)h->logits, part_bytes, st));
+    CK(decode_proj(h, a.o, P + o.wo, a.hmid, nullptr, nullptr, h->hs[l], B, H, nH * hd, st));
+    CK(rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, B, H, d.rms_eps, st));
+    CK(decode_proj(h, a.x2, P + o.wgu, a.gu, nullptr, nullptr, nullptr, B, 2 * I, H, st));
+    CK(swiglu_fwd(a.gu, a.act, B, I, GU_BLK, st));
+    CK(decode_proj(h, a.act, P + o.wd, h->hs[l + 1], nullptr, nullptr, a.hmid, B, H, I, st));
+  }
+  CK(rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
+  CK(decode_proj(h, h->hf, P + h->off_embed, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
+  CK(lens_inc(lens, B, st));
+  h->kv_hi += 1;
   return SLAM_OK;
 }
 
@@ -1456,6 +1579,39 @@ int slam_op_gemm_tn_image(const void* dY, const void* X, float* dW, void* dW_bf1
                           int background, slam_stream_t s) {
   const size_t cap = gemm_tn_workspace_bytes(M, N, K);
   return gemm_tn((const bf16_t*)dY, (const bf16_t*)X, dW, accumulate, M, N, K, N, K, ws, cap, (hipStream_t)s, background, (bf16_t*)dW_bf16);
+}
+size_t slam_op_gemm_skinny_workspace(int M, int N, int K) { return gemm_skinny_workspace_bytes(M, N, K); }
+int slam_op_gemm_skinny(const void* X, const void* W, void* Y, int y_f32, const void* bias, const void* resid, int M, int N, int K,
+                        float* ws, size_t ws_bytes, slam_stream_t s) {
+  return gemm_skinny((const bf16_t*)X, (const bf16_t*)W, y_f32 ? nullptr : (bf16_t*)Y, y_f32 ? (float*)Y : nullptr,
+                     (const bf16_t*)bias, (const bf16_t*)resid, M, N, K, ws, ws_bytes, (hipStream_t)s);
+}
+namespace {
+// slam_op_attn_decode workspace: int64 positions [B], cos / sin / pre-scaled cos / sin tables [B][hd/2], split partials
+size_t attn_decode_op_head(int B, int head_dim) { return (((size_t)B * 8 + 255) & ~(size_t)255) + (((size_t)4 * B * (head_dim / 2) * 4 + 255) & ~(size_t)255); }
+}  // namespace
+size_t slam_op_attn_decode_workspace(int B, int nH, int nKV, int head_dim, int kv_bound) {
+  if (B <= 0 || nKV <= 0 || kv_bound <= 0) return 0;
+  const int chunk = attn_decode_chunk(B, nH, nKV, head_dim, kv_bound, (size_t)-1);
+  return attn_decode_op_head(B, head_dim) + attn_decode_part_bytes(B, nH, head_dim, (kv_bound + chunk - 1) / chunk);
+}
+int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens, void* k_cache, void* v_cache, void* o, void* ws,
+                        size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity, int kv_bound, float theta,
+                        slam_stream_t s) {
+  if (!qkv || !lens || !k_cache || !v_cache || !o || !ws || B <= 0 || (head_dim != 64 && head_dim != 128)) return SLAM_EINVAL;
+  const size_t head = attn_decode_op_head(B, head_dim);
+  if (ws_bytes <= head) return SLAM_ENOMEM;
+  hipStream_t st = (hipStream_t)s;
+  char* w = (char*)ws;
+  int64_t* pos = (int64_t*)w;
+  float* tab = (float*)(w + (((size_t)B * 8 + 255) & ~(size_t)255));
+  const size_t n = (size_t)B * (head_dim / 2);
+  int r = lens_to_pos(lens, pos, B, st);
+  if (r) return r;
+  r = rope_table(pos, B, 1, head_dim, theta, tab, tab + n, tab + 2 * n, tab + 3 * n, 1.44269504088896340736f / sqrtf((float)head_dim), st);
+  if (r) return r;
+  return attn_decode(qkv, (const bf16_t*)bias, tab, tab + n, tab + 2 * n, tab + 3 * n, lens, (bf16_t*)k_cache, (bf16_t*)v_cache,
+                     capacity, B, nH, nKV, head_dim, kv_bound, (bf16_t*)o, (float*)(w + head), ws_bytes - head, st);
 }
 int slam_op_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int M, int H, float eps, slam_stream_t s) {
   return rmsnorm_fwd((const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd, M, H, eps, (hipStream_t)s);

@@ -163,4 +163,29 @@ int colsum_finish_many(const float* part, size_t part_stride, int nb, int N, flo
                        int accumulate, hipStream_t st, bf16_t* img = nullptr,  // img: bf16 image of `out` (same indexing), nullable
                        GradSink* sink = nullptr);
 
+
+// decode.hip (KV-cached generation)
+// Y[M][N] = X[M][K] W[N][K]^T (+ bias[N]) (+ resid[M][N]) for small M: a weight stream on v_mfma_f32_16x16x32_bf16 with split-K.
+// Exactly one of Y (bf16) / Yf (fp32) is non-null. ws: fp32 split-K partials (gemm_skinny_workspace_bytes for the full
+// split; less or none gives fewer splits). Deterministic: partials are summed in split order by a second launch.
+constexpr int SKINNY_MAX_M = 64;  // the engine's decode projections use gemm_skinny up to this many rows, gemm_nt beyond
+size_t gemm_skinny_workspace_bytes(int M, int N, int K);
+int gemm_skinny(const bf16_t* X, const bf16_t* W, bf16_t* Y, float* Yf, const bf16_t* bias, const bf16_t* resid, int M, int N,
+                int K, float* ws, size_t ws_bytes, hipStream_t st);
+// one decode step of attention for one layer: qkv = fp32 [B][(nH + 2 nKV) hd] projection WITHOUT bias; bias + RoPE (tables
+// cs / sn and the pre-scaled csq / snq of rope_table at the rows' positions lens[b]) are applied in fp32 and rounded once;
+// the new K / V go to row lens[b] of kc / vc ([B][nKV][cap][hd] bf16), and o[b] (bf16 [B][nH hd]) attends over rows
+// 0 .. lens[b]. kv_bound >= max(lens) + 1 (host bound, <= cap). part: fp32 split partials (attn_decode_part_bytes).
+size_t attn_decode_part_bytes(int B, int nH, int head_dim, int ns);
+int attn_decode_chunk(int B, int nH, int nKV, int head_dim, int kv_bound, size_t part_bytes);
+int attn_decode(const float* qkv, const bf16_t* bias, const float* cs, const float* sn, const float* csq, const float* snq,
+                const int* lens, bf16_t* kc, bf16_t* vc, int cap, int B, int nH, int nKV, int head_dim, int kv_bound, bf16_t* o,
+                float* part, size_t part_bytes, hipStream_t st);
+// prefill: K / V columns of rows t < lens[b] of one layer's qkv [B*T][QKV] into the cache
+int kv_scatter(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, const int* lens, int B, int T, int nH, int nKV, int head_dim, int cap,
+               hipStream_t st);
+int gather_last_rows(const bf16_t* src, bf16_t* dst, const int* lens, int B, int T, int H, hipStream_t st);
+int lens_to_pos(const int* lens, int64_t* pos, int B, hipStream_t st);
+int lens_inc(int* lens, int B, hipStream_t st);
+
 }  // namespace slam

@@ -68,6 +68,10 @@ def load_library(path: Optional[str] = None):
         "slam_bind_workspace": (C.c_int, [vp, vp, sz, i64]),
         "slam_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
         "slam_backward": (C.c_int, [vp, f32, i32, BUCKET_CB, vp, vp]),
+        "slam_kv_cache_bytes": (sz, [vp, i32, i32]),
+        "slam_bind_kv_cache": (C.c_int, [vp, vp, sz, i32, i32]),
+        "slam_prefill": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
+        "slam_decode_step": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "slam_bucket_stream": (vp, [vp]),
         "slam_set_logit_mask": (C.c_int, [vp, vp]),
         "slam_padded_vocab": (i32, [vp]),
@@ -110,6 +114,11 @@ def load_library(path: Optional[str] = None):
         "slam_op_gemm_tn_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
         "slam_op_gemm_tn": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "slam_op_gemm_tn_image": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
+        "slam_op_gemm_skinny_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
+        "slam_op_gemm_skinny": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
+        "slam_op_attn_decode_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "slam_op_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          f32, vp]),
         "slam_op_rmsnorm_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
         "slam_op_rmsnorm_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_rmsnorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -241,6 +250,25 @@ class Engine:
             cb = BUCKET_CB(lambda _u, off, cnt: bucket_cb(int(off), int(cnt), self.lib.slam_bucket_stream(self.h)))
         self._ck(self.lib.slam_backward(self.h, float(grad_scale), int(bucket_layers), cb, None,
                                         stream if stream is not None else current_stream_ptr()))
+
+    # -- KV-cached generation ---------------------------------------------------------------------
+    def kv_cache_bytes(self, max_batch: int, capacity: int) -> int:
+        return int(self.lib.slam_kv_cache_bytes(self.h, max_batch, capacity))
+
+    def bind_kv_cache(self, cache, max_batch: int, capacity: int):
+        """cache: a 256-byte aligned device buffer of kv_cache_bytes(max_batch, capacity) bytes, kept alive here."""
+        self._keep["kv"] = cache
+        self._ck(self.lib.slam_bind_kv_cache(self.h, _ptr(cache), cache.numel() * cache.element_size(), max_batch, capacity))
+
+    def prefill(self, ids, lens, B: int, T: int, logits_out, stream: Optional[int] = None):
+        """ids int64 [B, T] (right-padded), lens int32 [B]: fills the cache, fp32 logits [B, vocab] of each last prompt token."""
+        self._ck(self.lib.slam_prefill(self.h, _ptr(ids), _ptr(lens), B, T, _ptr(logits_out),
+                                       stream if stream is not None else current_stream_ptr()))
+
+    def decode_step(self, ids, lens, B: int, logits_out, stream: Optional[int] = None):
+        """ids int64 [B]: one token per row at position lens[b]; fp32 logits [B, vocab]; lens += 1 on the device."""
+        self._ck(self.lib.slam_decode_step(self.h, _ptr(ids), _ptr(lens), B, _ptr(logits_out),
+                                           stream if stream is not None else current_stream_ptr()))
 
     def set_logit_mask(self, mask_u8=None):
         """mask_u8: uint8 device tensor of padded_vocab() bytes (non-zero = column outside the softmax) or None."""

@@ -184,6 +184,22 @@ def _right_padded(mask: torch.Tensor) -> bool:
     return bool((m[:, 1:] <= m[:, :-1]).all())
 
 
+def _warp(scores: torch.Tensor, temperature: float, top_k: int, top_p: float) -> torch.Tensor:
+    """HF's sampling warpers in HF's order: temperature, top-k, top-p (at least one token kept)."""
+    if temperature != 1.0:
+        scores = scores / temperature
+    if top_k > 0:
+        kth = torch.topk(scores, min(top_k, scores.shape[-1])).values[:, -1:]
+        scores = scores.masked_fill(scores < kth, float("-inf"))
+    if top_p < 1.0:
+        srt, idx = torch.sort(scores, descending=False)
+        cum = srt.softmax(-1).cumsum(-1)
+        drop = cum <= (1 - top_p)
+        drop[:, -1] = False
+        scores = scores.masked_fill(drop.scatter(1, idx, drop), float("-inf"))
+    return scores
+
+
 class UnitLM(TokenLM):
     """unit_lm.py:82-212 on the HIP engine."""
     base_model_prefix = "lm"
@@ -560,35 +576,113 @@ class UnitLM(TokenLM):
         self._grads_in_bf16 = False
 
     @torch.no_grad()
-    def generate(self, inputs: Optional[torch.Tensor] = None, generation_config=None, max_new_tokens: int = 32,
-                 do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, seed: Optional[int] = None,
-                 **kwargs) -> torch.Tensor:
-        """Minimal sampler for the TokenLM surface (unit_lm.py:196-198): full re-forward per token
-        (no KV cache - evaluation/generation is outside the training hot path)."""
-        if generation_config is not None:
-            max_new_tokens = getattr(generation_config, "max_new_tokens", max_new_tokens) or max_new_tokens
-            do_sample = getattr(generation_config, "do_sample", do_sample)
-        seq = inputs.to(self.device, torch.int64)
-        g = torch.Generator(device=self.device)
-        if seed is not None:
-            g.manual_seed(seed)
-        done = torch.zeros(seq.shape[0], dtype=torch.bool, device=self.device)
-        for _ in range(max_new_tokens):
-            logits = self.forward(seq).logits[:, -1].float()
+    def generate(self, inputs: Optional[torch.Tensor] = None, generation_config=None, max_new_tokens: Optional[int] = None,
+                 do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
+                 seed: Optional[int] = None, input_ids: Optional[torch.Tensor] = None,
+                 attention_mask: Optional[torch.Tensor] = None, bad_words_ids: Optional[List[List[int]]] = None,
+                 top_p: Optional[float] = None, eos_token_id=None, pad_token_id: Optional[int] = None, **kwargs) -> torch.Tensor:
+        """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
+        `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
+        left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
+        first real token, HF's cumsum(mask) - 1), prefilled once, then decoded one token per step (slam_decode_step).
+        Logits are fp32; bad words get -inf, then temperature, top_k and top_p (sampling only). Finished rows are padded
+        with pad_token_id; generation stops when every row has emitted eos_token_id. Explicit arguments override
+        `generation_config`. Returns [B, T_in + n_new] int64: the prompt as passed, padding included, then the new tokens."""
+        gc = generation_config
+
+        def pick(v, name, default):
+            if v is not None:
+                return v
+            g = getattr(gc, name, None) if gc is not None else None
+            return g if g is not None else default
+
+        num_beams = pick(kwargs.pop("num_beams", None), "num_beams", 1)
+        rep = pick(kwargs.pop("repetition_penalty", None), "repetition_penalty", 1.0)
+        if num_beams != 1:
+            raise ValueError("beam search is not supported (num_beams must be 1)")
+        if rep != 1.0:
+            raise ValueError("repetition_penalty is not supported (must be 1.0)")
+        max_new_tokens = int(pick(max_new_tokens, "max_new_tokens", 32))
+        do_sample = bool(pick(do_sample, "do_sample", False))
+        temperature = float(pick(temperature, "temperature", 1.0))
+        top_k = int(pick(top_k, "top_k", 0) or 0)
+        top_p = float(pick(top_p, "top_p", 1.0))
+        eos = pick(eos_token_id, "eos_token_id", self.config.eos_token_id)
+        eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
+        pad = pick(pad_token_id, "pad_token_id", self.config.pad_token_id)
+        if pad is None:
+            pad = eos[0] if eos else 0
+        bad = pick(bad_words_ids, "bad_words_ids", None) or []
+        if any(len(w) != 1 for w in bad):
+            raise ValueError("bad_words_ids: only single-token entries are supported")
+        if inputs is None:
+            inputs = input_ids
+        if inputs is None or inputs.dim() != 2:
+            raise ValueError("generate needs input_ids [B, T]")
+        if max_new_tokens <= 0:
+            return inputs.to(self.device, torch.int64)
+        if kwargs:
+            raise TypeError(f"generate got unsupported arguments {sorted(kwargs)}")
+        dev = self.device
+        seq_in = inputs.to(dev, torch.int64)
+        B, T_in = seq_in.shape
+        mask = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones_like(seq_in, dtype=torch.bool)
+        # compact every row's real tokens to the left (stable: keeps their order)
+        order = torch.sort((~mask).to(torch.int8), dim=1, stable=True).indices
+        lens = mask.sum(1).to(torch.int32)
+        T = int(lens.max())
+        if int(lens.min()) < 1:
+            raise ValueError("every prompt row needs at least one unmasked token")
+        ids = seq_in.gather(1, order)[:, :T]
+        ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, int(pad))).contiguous()
+        if T + max_new_tokens > self.config.max_tokens:
+            raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds max_tokens {self.config.max_tokens}")
+        cap = -(-(T + max_new_tokens) // 64) * 64
+        self._ensure_workspace(max(B * T, 2 * B))
+        nbytes = self.engine.kv_cache_bytes(B, cap)
+        raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        off = (-raw.data_ptr()) % 256
+        self.engine.bind_kv_cache(raw[off:off + nbytes], B, cap)
+        V = self.config.vocab_size
+        logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+        bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
+        eos_t = torch.tensor(eos, dtype=torch.long, device=dev) if eos else None
+        g = None
+        if do_sample and seed is not None:
+            g = torch.Generator(device=dev)
+            g.manual_seed(int(seed))
+        self._hold = (ids, lens)
+        self.engine.prefill(ids, lens, B, T, logits)
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        new = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
+        n = 0
+        for step in range(max_new_tokens):
+            scores = logits
+            if bad_idx is not None:
+                scores = scores.index_fill(1, bad_idx, float("-inf"))
             if do_sample:
-                logits = logits / max(temperature, 1e-6)
-                if top_k:
-                    kth = torch.topk(logits, top_k).values[:, -1:]
-                    logits = logits.masked_fill(logits < kth, float("-inf"))
-                nxt = torch.multinomial(torch.softmax(logits, -1), 1, generator=g)[:, 0]
+                scores = _warp(scores, temperature, top_k, top_p)
+                nxt = torch.multinomial(torch.softmax(scores, -1), 1, generator=g)[:, 0]
             else:
-                nxt = logits.argmax(-1)
-            nxt = torch.where(done, torch.full_like(nxt, self.config.pad_token_id), nxt)
-            seq = torch.cat([seq, nxt[:, None]], 1)
-            done |= nxt == self.config.eos_token_id
-            if bool(done.all()):
-                break
-        return seq
+                nxt = scores.argmax(-1)
+            nxt = torch.where(done, torch.full_like(nxt, int(pad)), nxt)
+            new[:, step] = nxt
+            n = step + 1
+            if eos_t is not None:
+                done |= torch.isin(nxt, eos_t)
+                if (step % 16 == 15 or step + 1 == max_new_tokens) and bool(done.all()):
+                    break
+            if step + 1 < max_new_tokens:
+                self.engine.decode_step(nxt.contiguous(), lens, B, logits)
+        new = new[:, :n]
+        if eos_t is not None and n > 1:
+            # HF stops right after the step on which the last row finished: drop the all-pad columns behind it
+            fin = torch.isin(new, eos_t).cumsum(1) > 0
+            all_done = fin.all(0)
+            if bool(all_done.any()):
+                n = int(all_done.nonzero()[0]) + 1
+                new = new[:, :n]
+        return torch.cat([seq_in, new], 1)
 
     # ---- checkpoints (HF layout) ------------------------------------------------------------------
     def save_pretrained(self, save_directory: str, dtype=torch.bfloat16):
