@@ -66,6 +66,18 @@ typedef void (*slam_bucket_cb)(void* user, int64_t offset, int64_t count);
 
 /* ---- lifetime -------------------------------------------------------------------------------*/
 int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out); /* UnitLM.__init__ :91-112 */
+/* The same for a decoder family: arch 0 = Qwen2 (= slam_engine_create, n_positions ignored), arch 1 = pre-LN OPT as HF
+ * OPTForCausalLM computes it (facebook/opt-125m, the reference's config/model/default.yaml body; the TWIST-1.3B body):
+ * LayerNorm with bias, learned absolute positions (n_positions + 2 rows: HF's offset of 2), ReLU FFN with biases, biases on
+ * out_proj / fc2, no RoPE, tied head. Requires n_kv_heads == n_heads and head_dim 64; rms_eps carries the LayerNorm eps,
+ * rope_theta is ignored; `intermediate` is OPT's ffn_dim. OPT tensor names, in layout order (every offset a multiple of 8,
+ * both embedding tables before layer 0, each layer contiguous from its ln1 at a constant stride, the final norm last):
+ *   embed [Vp][H], pos_embed [n_positions + 2][H],
+ *   layers.N.{ln1, ln1_b [H], wqkv [3 H][H], bqkv [3 H], wo [H][H], bo [H], ln2, ln2_b [H], w1 [F][H], b1 [F], w2 [H][F], b2 [H]},
+ *   norm, norm_b [H].
+ * Positions are position_ids, else 0 .. T-1 per row; both table indices are clamped to the tables (a memory guard: callers
+ * check their ranges). KV-cached generation (slam_prefill / slam_decode_step) is not implemented for OPT: SLAM_EINVAL. */
+int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, SlamEngine** out);
 void slam_engine_destroy(SlamEngine* h);
 const char* slam_last_error(SlamEngine* h);
 const char* slam_version(void);
@@ -322,6 +334,21 @@ int slam_op_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int 
 size_t slam_op_rmsnorm_bwd_workspace(int M, int H);
 int slam_op_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,
                         float* dw, float* ws, int M, int H, slam_stream_t s);
+/* OPT ops. LayerNorm: y = bf16((x - mean) rstd w + b), fp32 statistics from two passes (mean, rstd saved, fp32 [M]);
+ * backward: dx = rstd (g - mean(g) - xhat mean(g xhat)) (+ dres), g = dy w; dw = sum dy xhat, db = sum dy (fp32 [H], stored). */
+int slam_op_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int M, int H, float eps,
+                          slam_stream_t s);
+size_t slam_op_layernorm_bwd_workspace(int M, int H);
+int slam_op_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* dres,
+                          void* dx, float* dw, float* db, float* ws, int M, int H, slam_stream_t s);
+/* out[m] = bf16(E[ids[m]] + P[pos + 2]), pos = position_ids[m] or m % T; prow (int64 [M], nullable) receives pos + 2 */
+int slam_op_embed_pos_fwd(const int64_t* ids, const int64_t* position_ids, const void* E, const void* P, void* out, int64_t* prow,
+                          int M, int H, int V, int T, int n_rows_p, slam_stream_t s);
+/* fc1: act[M,N] = relu(X W^T + bias) (only the post-ReLU activation is stored); fc2 dgrad with the ReLU backward fused into the
+ * epilogue: dact[M,N] = (dY Wt^T) * [act > 0]; the elementwise form d *= [act > 0] (n a multiple of 8) */
+int slam_op_gemm_nt_relu(const void* X, const void* W, void* act, const void* bias, int M, int N, int K, slam_stream_t s);
+int slam_op_gemm_nt_drelu(const void* dY, const void* Wt, void* dact, const void* act, int M, int N, int K, slam_stream_t s);
+int slam_op_relu_bwd(void* d, const void* act, int64_t n, slam_stream_t s);
 int slam_op_rope(void* qkv, int ld, int M, int T, int n_rot_heads, int head_dim, const int64_t* position_ids, float theta,
                  int backward, float* cos_sin_ws /* 2*M*(head_dim/2) floats */, slam_stream_t s);
 int slam_op_swiglu_fwd(const void* gu, void* act, int M, int I, slam_stream_t s);

@@ -15,12 +15,15 @@ constexpr int MAXC_LIMIT = 4;  // chunks of 8 per lane -> hidden <= 2048 (kernel
 
 // ------------------------------------------------------------------------------------------
 // RMSNorm forward: y = bf16( x * rsqrt(mean(x^2)+eps) * w ), fp32 math, rstd saved.
+// LN (OPT's nn.LayerNorm): y = bf16( (x - mu) * rsqrt(var+eps) * w + b ) with mu and var from two passes over the
+// registers (no E[x^2] - mu^2 cancellation); mu and rstd saved.
 // Algorithmic traffic: 4 B/element (read bf16 + write bf16).
-template <int MAXC>
+template <int MAXC, bool LN = false>
 __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16_t* __restrict__ x,
                                                           const bf16_t* __restrict__ w,
                                                           bf16_t* __restrict__ y, float* __restrict__ rstd,
-                                                          int M, int H, float eps) {
+                                                          int M, int H, float eps, const bf16_t* __restrict__ b = nullptr,
+                                                          float* __restrict__ mean = nullptr) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -36,14 +39,32 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16_t* __restri
       float f[8];
       unpack_bf16x8(v[i], f);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
+      for (int j = 0; j < 8; ++j) ss += LN ? f[j] : f[j] * f[j];
     }
   }
   ss = wave_sum(ss);
+  float mu = 0.f;
+  if constexpr (LN) {  // second pass: centred sum of squares
+    mu = ss / (float)H;
+    ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      int c = lane + 64 * i;
+      if (c < nch) {
+        float f[8];
+        unpack_bf16x8(v[i], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ss += (f[j] - mu) * (f[j] - mu);
+      }
+    }
+    ss = wave_sum(ss);
+    if (lane == 0 && mean) mean[row] = mu;
+  }
   const float r = rsqrtf(ss / (float)H + eps);
   if (lane == 0 && rstd) rstd[row] = r;
   uint4* yr = reinterpret_cast<uint4*>(y + (size_t)row * H);
   const uint4* wr = reinterpret_cast<const uint4*>(w);
+  const uint4* br = reinterpret_cast<const uint4*>(b);
 #pragma unroll
   for (int i = 0; i < MAXC; ++i) {
     int c = lane + 64 * i;
@@ -51,32 +72,42 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16_t* __restri
       float f[8], g[8];
       unpack_bf16x8(v[i], f);
       unpack_bf16x8(wr[c], g);
+      if constexpr (LN) {
+        float bb[8];
+        unpack_bf16x8(br[c], bb);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = f[j] * r * g[j];
+        for (int j = 0; j < 8; ++j) f[j] = (f[j] - mu) * r * g[j] + bb[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = f[j] * r * g[j];
+      }
       yr[c] = pack_bf16x8(f);
     }
   }
 }
 
 // RMSNorm backward. dx = rstd*(dy*w - xhat*mean(dy*w*xhat)) (+ dres); dw partial per block.
+// LN: xhat = (x - mu)*rstd, dx = rstd*(g - mean(g) - xhat*mean(g*xhat)) with g = dy*w (+ dres); partials of
+// dw = sum dy*xhat and db = sum dy per block.
 // Each wave walks rows wave, wave+4*gridDim.. accumulating its dw slice in registers.
 // Algorithmic traffic: 6 B/element (+2 with the fused residual-gradient add).
-template <int MAXC>
+template <int MAXC, bool LN = false>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy,
                                                           const bf16_t* __restrict__ x,
                                                           const bf16_t* __restrict__ w,
                                                           const float* __restrict__ rstd,
                                                           const bf16_t* __restrict__ dres,
                                                           bf16_t* __restrict__ dx, float* __restrict__ dw_part,
-                                                          int M, int H) {
+                                                          int M, int H, const float* __restrict__ mean = nullptr,
+                                                          float* __restrict__ db_part = nullptr) {
   __shared__ float red[4][MAXC * 64 * 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nch = H >> 3;
-  float dwa[MAXC][8];
+  float dwa[MAXC][8], dba[MAXC][8];
 #pragma unroll
   for (int i = 0; i < MAXC; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) dwa[i][j] = 0.f;
+    for (int j = 0; j < 8; ++j) { dwa[i][j] = 0.f; dba[i][j] = 0.f; }
   const uint4* wr = reinterpret_cast<const uint4*>(w);
   float wv[MAXC][8];
 #pragma unroll
@@ -102,16 +133,16 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
   const int rstep = gridDim.x * 4;
   int row = blockIdx.x * 4 + wave;
   uint4 cx[MAXC], cdy[MAXC], cdr[MAXC];
-  float cr = 0.f;
-  if (row < M) { load_row(row, cx, cdy, cdr); cr = rstd[row]; }
+  float cr = 0.f, cmu = 0.f;
+  if (row < M) { load_row(row, cx, cdy, cdr); cr = rstd[row]; if constexpr (LN) cmu = mean[row]; }
   for (; row < M; row += rstep) {
     uint4 nx[MAXC], ndy[MAXC], ndr[MAXC];
-    float nr = 0.f;
+    float nr = 0.f, nmu = 0.f;
     const int nrow = row + rstep;
-    if (nrow < M) { load_row(nrow, nx, ndy, ndr); nr = rstd[nrow]; }
+    if (nrow < M) { load_row(nrow, nx, ndy, ndr); nr = rstd[nrow]; if constexpr (LN) nmu = mean[nrow]; }
     const float r = cr;
     float xh[MAXC][8], gy[MAXC][8];
-    float dot = 0.f;
+    float dot = 0.f, gsum = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
       int c = lane + 64 * i;
@@ -121,14 +152,16 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
         unpack_bf16x8(cdy[i], fd);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          xh[i][j] = fx[j] * r;
+          xh[i][j] = LN ? (fx[j] - cmu) * r : fx[j] * r;
           gy[i][j] = fd[j] * wv[i][j];
           dot += gy[i][j] * xh[i][j];
           dwa[i][j] += fd[j] * xh[i][j];
+          if constexpr (LN) { gsum += gy[i][j]; dba[i][j] += fd[j]; }
         }
       }
     }
     dot = wave_sum(dot) / (float)H;
+    if constexpr (LN) gsum = wave_sum(gsum) / (float)H;
     uint4* dxr = reinterpret_cast<uint4*>(dx + (size_t)row * H);
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
@@ -136,7 +169,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
       if (c < nch) {
         float o[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = r * (gy[i][j] - xh[i][j] * dot);
+        for (int j = 0; j < 8; ++j) o[j] = LN ? r * (gy[i][j] - gsum - xh[i][j] * dot) : r * (gy[i][j] - xh[i][j] * dot);
         if (dres) {
           float a[8];
           unpack_bf16x8(cdr[i], a);
@@ -149,6 +182,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) { cx[i] = nx[i]; cdy[i] = ndy[i]; cdr[i] = ndr[i]; }
     cr = nr;
+    cmu = nmu;
   }
   // cross-wave reduction of the dw partials, then one row of dw_part per block
 #pragma unroll
@@ -158,6 +192,16 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
   __syncthreads();
   for (int e = threadIdx.x; e < H; e += 256)
     dw_part[(size_t)blockIdx.x * H + e] = red[0][e] + red[1][e] + red[2][e] + red[3][e];
+  if constexpr (LN) {  // the same for db through the same LDS
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[wave][(lane + 64 * i) * 8 + j] = dba[i][j];
+    __syncthreads();
+    for (int e = threadIdx.x; e < H; e += 256)
+      db_part[(size_t)blockIdx.x * H + e] = red[0][e] + red[1][e] + red[2][e] + red[3][e];
+  }
 }
 
 // column sums of a bf16 matrix (bias gradient): part[blockIdx.y][N] fp32. Block = 16 column chunks (8 columns
@@ -349,6 +393,48 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
   int64_t id = ids[m];
   if (id < 0 || id >= V) id = 0;
   *reinterpret_cast<uint4*>(out + m * H + c * 8) = *reinterpret_cast<const uint4*>(E + (size_t)id * H + c * 8);
+}
+
+// OPT embedding: out[m,:] = bf16(E[ids[m],:] + P[pos[m] + 2,:]) (one rounding), pos = position_ids or m % T; the
+// position row index is also written to prow[m] (the backward's scatter ids). Both indices are clamped to their tables.
+__global__ __launch_bounds__(256) void embed_pos_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
+                                                            const bf16_t* __restrict__ E, const bf16_t* __restrict__ P,
+                                                            bf16_t* __restrict__ out, int64_t* __restrict__ prow, size_t M,
+                                                            int H, int V, int T, int NP) {
+  size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  int nch = H >> 3;
+  if (idx >= M * nch) return;
+  size_t m = idx / nch;
+  int c = idx % nch;
+  int64_t id = ids[m];
+  if (id < 0 || id >= V) id = 0;
+  int64_t p = (pos ? pos[m] : (int64_t)(m % (size_t)T)) + 2;
+  p = p < 0 ? 0 : (p >= NP ? NP - 1 : p);
+  if (c == 0 && prow) prow[m] = p;
+  float a[8], b[8];
+  unpack_bf16x8(*reinterpret_cast<const uint4*>(E + (size_t)id * H + c * 8), a);
+  unpack_bf16x8(*reinterpret_cast<const uint4*>(P + (size_t)p * H + c * 8), b);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a[j] += b[j];
+  *reinterpret_cast<uint4*>(out + m * H + c * 8) = pack_bf16x8(a);
+}
+
+// ReLU backward through the stored post-ReLU activation: d[i] = act[i] > 0 ? d[i] : 0
+__global__ __launch_bounds__(256) void relu_bwd_kernel(bf16_t* __restrict__ d, const bf16_t* __restrict__ act, size_t n8) {
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  const uint4 a = reinterpret_cast<const uint4*>(act)[i];
+  uint4 v = reinterpret_cast<uint4*>(d)[i];
+  const uint32_t aw[4] = {a.x, a.y, a.z, a.w};
+  uint32_t* vw = reinterpret_cast<uint32_t*>(&v);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t lo = aw[k] & 0xffffu, hi = aw[k] >> 16;
+    // a bf16 is > 0 when its sign bit is clear and it is not +0
+    const uint32_t keep = ((lo & 0x8000u) == 0 && lo != 0 ? 0xffffu : 0u) | ((hi & 0x8000u) == 0 && hi != 0 ? 0xffff0000u : 0u);
+    vw[k] &= keep;
+  }
+  reinterpret_cast<uint4*>(d)[i] = v;
 }
 
 // One-hot rows for the gather-side embedding gradient (dE += onehot^T dh0 runs on the wgrad GEMM,
@@ -1056,6 +1142,18 @@ int rmsnorm_fwd(const bf16_t* x, const bf16_t* w, bf16_t* y, float* rstd, int M,
   LAUNCH_RET();
 }
 
+int layernorm_fwd(const bf16_t* x, const bf16_t* w, const bf16_t* b, bf16_t* y, float* mean, float* rstd, int M, int H, float eps,
+                  hipStream_t st) {
+  if ((H & 7) || H > MAXC_LIMIT * 512) return -1;
+  switch ((H / 8 + 63) / 64) {
+    case 1: rmsnorm_fwd_kernel<1, true><<<(M + 3) / 4, 256, 0, st>>>(x, w, y, rstd, M, H, eps, b, mean); break;
+    case 2: rmsnorm_fwd_kernel<2, true><<<(M + 3) / 4, 256, 0, st>>>(x, w, y, rstd, M, H, eps, b, mean); break;
+    case 3: rmsnorm_fwd_kernel<3, true><<<(M + 3) / 4, 256, 0, st>>>(x, w, y, rstd, M, H, eps, b, mean); break;
+    default: rmsnorm_fwd_kernel<4, true><<<(M + 3) / 4, 256, 0, st>>>(x, w, y, rstd, M, H, eps, b, mean); break;
+  }
+  LAUNCH_RET();
+}
+
 int rmsnorm_bwd_blocks(int M) { int b = (M + 15) / 16; return b > 512 ? 512 : (b < 1 ? 1 : b); }  // 2 blocks/CU
 
 // sink (nullable, with dw): how the final values of dw are kept (GradSink, kernels.h)
@@ -1070,6 +1168,19 @@ int rmsnorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float*
     default: rmsnorm_bwd_kernel<4><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, part, M, H); break;
   }
   if (dw) return colsum_finish_many(part, 0, nb, H, dw, 0, 1, accumulate, st, dw_img, sink);  // dw == null: caller finishes later
+  LAUNCH_RET();
+}
+// LayerNorm backward: partial slabs dw_part / db_part [rmsnorm_bwd_blocks(M)][H], finished by the caller (colsum_finish_many)
+int layernorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* mean, const float* rstd, const bf16_t* dres,
+                  bf16_t* dx, float* dw_part, float* db_part, int M, int H, hipStream_t st) {
+  if ((H & 7) || H > MAXC_LIMIT * 512) return -1;
+  int nb = rmsnorm_bwd_blocks(M);
+  switch ((H / 8 + 63) / 64) {
+    case 1: rmsnorm_bwd_kernel<1, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, dw_part, M, H, mean, db_part); break;
+    case 2: rmsnorm_bwd_kernel<2, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, dw_part, M, H, mean, db_part); break;
+    case 3: rmsnorm_bwd_kernel<3, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, dw_part, M, H, mean, db_part); break;
+    default: rmsnorm_bwd_kernel<4, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, dw_part, M, H, mean, db_part); break;
+  }
   LAUNCH_RET();
 }
 // finish `count` equally shaped partial slabs in one launch: out[i] (+)= column sums of part[i]
@@ -1126,6 +1237,17 @@ int swiglu_bwd(bf16_t* gu, const bf16_t* dact, int M, int I, int blk, hipStream_
 
 int embed_fwd(const int64_t* ids, const bf16_t* E, bf16_t* out, int M, int H, int V, hipStream_t st) {
   embed_fwd_kernel<<<nblocks((size_t)M * (H / 8), 256), 256, 0, st>>>(ids, E, out, (size_t)M, H, V);
+  LAUNCH_RET();
+}
+int embed_pos_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const bf16_t* P, bf16_t* out, int64_t* prow, int M, int H,
+                  int V, int T, int NP, hipStream_t st) {
+  if ((H & 7) || T <= 0 || NP <= 0) return -1;
+  embed_pos_fwd_kernel<<<nblocks((size_t)M * (H / 8), 256), 256, 0, st>>>(ids, pos, E, P, out, prow, (size_t)M, H, V, T, NP);
+  LAUNCH_RET();
+}
+int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st) {
+  if (n & 7) return -1;
+  relu_bwd_kernel<<<nblocks(n / 8, 256), 256, 0, st>>>(d, act, n / 8);
   LAUNCH_RET();
 }
 int onehot(const int64_t* ids, bf16_t* oh, int M, int Vp, int V, int pad_id, hipStream_t st) {

@@ -35,14 +35,29 @@ namespace {
 constexpr int VPAD_SMALL = 512;  // vocabularies up to 512 (the speech-unit LMs) use the one-wave CE and one-hot wgrad paths
 constexpr int GU_BLK = 32;  // Wgu rows / gate|up columns come in blocks of 32 gate + 32 up
 
+// OPT (arch 1) keeps fc1 in `wgu` and fc2 in `wd`; ln1_b, bo, ln2_b, b1, b2 are OPT's alone
 struct LayerOff {
   int64_t ln1, wqkv, bqkv, wo, ln2, wgu, wd;
+  int64_t ln1_b = -1, bo = -1, ln2_b = -1, b1 = -1, b2 = -1;
 };
 
+// OPT: gu is [M][I] (the layer's d(act) in backward), act the post-ReLU fc1 output; mu1 / mu2 the LayerNorm means
 struct LayerAct {
   bf16_t *hmid, *x1, *x2, *qkv, *o, *gu, *act;
   float *rstd1, *rstd2, *lse;
+  float *mu1 = nullptr, *mu2 = nullptr;
 };
+
+// an identity rotation: cs = 1, sn = 0, and the query tables carry only the pre-scale (OPT has no RoPE; the attention
+// kernels still take their queries pre-scaled and attn_bwd rotates dq / dk back through these tables)
+__global__ void ident_rope_kernel(float* cs, float* sn, float* csq, float* snq, size_t n, float qscale) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  cs[i] = 1.f;
+  sn[i] = 0.f;
+  csq[i] = qscale;
+  snq[i] = 0.f;
+}
 
 __global__ void seg_fill_kernel(int* seg_start, int* seg_end, int M, int T) {
   int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -56,12 +71,16 @@ __global__ void seg_fill_kernel(int* seg_start, int* seg_end, int M, int T) {
 
 struct SlamEngine {
   SlamModelDesc d;
+  int arch = 0;  // 0 Qwen2, 1 OPT (slam_engine_create_arch)
+  int npos = 0;  // OPT: rows of the learned position table (n_positions + 2, HF's offset)
   int QKV;  // (nH + 2 nKV) * hd
   int vpad = VPAD_SMALL;  // embedding / logits rows: 512, or vocab rounded up to 256 beyond that
   int64_t n_params;
   int64_t off_embed, off_norm, layer_stride = 0;
+  int64_t off_pos = -1, off_norm_b = -1;  // OPT
   std::vector<LayerOff> lo;
   std::vector<SlamTensorInfo> tensors;
+  std::vector<int> layer0;  // indices into `tensors` of layer 0's tensors, in layout order
   std::string err;
 
   bf16_t* params = nullptr;
@@ -168,6 +187,10 @@ struct SlamEngine {
   float *rstdf, *row_loss, *dsum, *dkv_part, *cosb, *sinb, *gemm_ws, *part_ws, *scal;
   float *ln_part, *bias_part;  // per-layer partial slabs: [2L][nb_ln][H], [L][nb_cs][QKV]
   size_t ln_ps = 0, bias_ps = 0;
+  // OPT: LayerNorm bias slabs [2L][nb_ln][H]; bo, b1, b2 slabs [L][nb_cs][H | I | H]; final-norm mean; position rows of the tokens
+  float *lnb_part = nullptr, *bo_part = nullptr, *b1_part = nullptr, *b2_part = nullptr, *muf = nullptr;
+  size_t hb_ps = 0, ib_ps = 0;
+  int64_t* prow = nullptr;
   size_t gemm_ws_bytes = 0;
   int *seg_s, *seg_e, *attn_plan_buf;
 
@@ -226,6 +249,7 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
   e->hs.resize(L + 1);
   e->la.resize(L);
   for (size_t l = 0; l <= L; ++l) e->hs[l] = c.take<bf16_t>(M * H);
+  const bool opt = e->arch == 1;
   for (size_t l = 0; l < L; ++l) {
     LayerAct& a = e->la[l];
     a.hmid = c.take<bf16_t>(M * H);
@@ -233,21 +257,32 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
     a.x2 = c.take<bf16_t>(M * H);
     a.qkv = c.take<bf16_t>(M * e->QKV);
     a.o = c.take<bf16_t>(M * d.n_heads * d.head_dim);
-    a.gu = c.take<bf16_t>(M * 2 * I);
+    a.gu = c.take<bf16_t>(M * (opt ? 1 : 2) * I);
     a.act = c.take<bf16_t>(M * I);
     a.rstd1 = c.take<float>(M);
     a.rstd2 = c.take<float>(M);
     a.lse = c.take<float>(M * d.n_heads);
+    if (opt) {
+      a.mu1 = c.take<float>(M);
+      a.mu2 = c.take<float>(M);
+    }
   }
   e->hf = c.take<bf16_t>(M * H);
   e->rstdf = c.take<float>(M);
+  if (opt) {
+    e->muf = c.take<float>(M);
+    e->prow = c.take<int64_t>(M);
+  }
   const size_t VP = (size_t)e->vpad;
   // ONE [M][Vp] buffer: the loss kernel replaces the logits with d loss / d logits in place (2 x 5 GB -> 5 GB at
   // M = 16384, Vp = 152,320); callers that want the logits get their copy before the loss runs
   e->logits = c.take<bf16_t>(M * VP);
   e->dlogits = e->logits;
-  if (e->vpad == VPAD_SMALL) { e->onehot = c.take<bf16_t>(M * VP); e->embed_ws = nullptr; }
-  else { e->onehot = nullptr; e->embed_ws = c.take<int>(embed_bwd_workspace_ints((int)M, e->vpad)); }
+  // OPT: the position table's scatter shares the scatter workspace with the large-vocabulary one (in order, on one stream)
+  const int scatter_rows = opt ? (e->vpad == VPAD_SMALL || e->npos > e->vpad ? e->npos : e->vpad) : e->vpad;
+  e->onehot = e->vpad == VPAD_SMALL ? c.take<bf16_t>(M * VP) : nullptr;
+  e->embed_ws = nullptr;
+  if (e->vpad != VPAD_SMALL || opt) e->embed_ws = c.take<int>(embed_bwd_workspace_ints((int)M, scatter_rows));
   e->row_loss = c.take<float>(M);
   e->dh_a = c.take<bf16_t>(M * H);
   e->dx = c.take<bf16_t>(M * H);
@@ -272,20 +307,34 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
   if (part < 1024) part = 1024;
   const size_t n_chunks = ((size_t)e->n_params + grad_chunk_elems() - 1) / grad_chunk_elems();  // gradient-norm chunk sums
   if (part < n_chunks) part = n_chunks;
+  if (opt && part < 2 * (size_t)rmsnorm_bwd_blocks((int)M) * H) part = 2 * (size_t)rmsnorm_bwd_blocks((int)M) * H;  // final LN: dw | db
   e->part_ws = c.take<float>(part);
   e->ln_ps = (size_t)rmsnorm_bwd_blocks((int)M) * H;
   e->bias_ps = (size_t)colsum_blocks((int)M) * e->QKV;
   e->ln_part = c.take<float>(e->ln_ps * 2 * L);
   e->bias_part = c.take<float>(e->bias_ps * L);
+  if (opt) {
+    e->hb_ps = (size_t)colsum_blocks((int)M) * H;
+    e->ib_ps = (size_t)colsum_blocks((int)M) * I;
+    e->lnb_part = c.take<float>(e->ln_ps * 2 * L);
+    e->bo_part = c.take<float>(e->hb_ps * L);
+    e->b1_part = c.take<float>(e->ib_ps * L);
+    e->b2_part = c.take<float>(e->hb_ps * L);
+  }
   {  // GradSink slots of one backward: every launch that stores final gradient values, under any plan
     const size_t HD = (size_t)d.n_heads * d.head_dim;
     size_t emb = gemm_tn_sumsq_slots(e->vpad, (int)H);
     const size_t conv = (size_t)f32_to_bf16_sumsq_slots((size_t)e->vpad * H);
     if (conv > emb) emb = conv;
-    const size_t per_layer = gemm_tn_sumsq_slots(e->QKV, (int)H) + gemm_tn_sumsq_slots((int)H, (int)HD) +
-                             gemm_tn_sumsq_slots((int)(2 * I), (int)H) + gemm_tn_sumsq_slots((int)H, (int)I) +
-                             2 * ((H + 15) / 16) + ((size_t)e->QKV + 15) / 16;
-    e->gn_cap = emb + L * per_layer + (H + 15) / 16 + 64;
+    size_t per_layer = gemm_tn_sumsq_slots(e->QKV, (int)H) + gemm_tn_sumsq_slots((int)H, (int)HD) +
+                       gemm_tn_sumsq_slots((int)(2 * I), (int)H) + gemm_tn_sumsq_slots((int)H, (int)I) +
+                       2 * ((H + 15) / 16) + ((size_t)e->QKV + 15) / 16;
+    size_t tail = (H + 15) / 16;
+    if (opt) {  // + fc1 at N = I, the LayerNorm biases, bo, b1, b2, the final norm's bias and the position table's conversion
+      per_layer += gemm_tn_sumsq_slots((int)I, (int)H) + 2 * ((H + 15) / 16) + 2 * ((H + 15) / 16) + (I + 15) / 16;
+      tail += (H + 15) / 16 + (size_t)f32_to_bf16_sumsq_slots((size_t)e->npos * H) + (size_t)e->npos * H / grad_chunk_elems() + 1;
+    }
+    e->gn_cap = emb + L * per_layer + tail + 64;
     e->gn_part = c.take<float>(e->gn_cap);
   }
   e->scal = c.take<float>(64);
@@ -470,7 +519,7 @@ int join_params(SlamEngine* h, hipStream_t st) { return h->pwaits.empty() ? 0 : 
 int adamw_model(SlamEngine* h, int mode, float* master, void* m, void* v, const float* norm_out, double lr, double b1, double b2,
                 double eps, double wd, int step, int zero_grad, int chunk, hipStream_t st) {
   const SlamModelDesc& d = h->d;
-  const int L = d.n_layers, H = d.hidden, I = d.intermediate, HD = d.n_heads * d.head_dim;
+  const int L = d.n_layers, H = d.hidden;
   bf16_t* P = h->params;
   bf16_t* Pt = h->params_t;
   const int g16 = h->gfinal == 2;  // the last backward kept its final values in bf16 only
@@ -486,20 +535,24 @@ int adamw_model(SlamEngine* h, int mode, float* master, void* m, void* v, const 
                          batch, (size_t)h->layer_stride, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st);
   };
   int r = 0;
-  if (chunk < 0 || chunk == 0) r = mat(h->off_embed, h->vpad, H, 1);
+  if (chunk < 0 || chunk == 0) {
+    r = mat(h->off_embed, h->vpad, H, 1);
+    if (!r && h->arch == 1) r = vec(h->off_pos, (size_t)h->npos * H, 1);  // no transposed image: no GEMM reads one
+  }
   if (r) return r;
   const int l0 = chunk < 0 ? 0 : chunk - 1, nl = chunk < 0 ? L : 1;
   if (chunk < 0 || (chunk >= 1 && chunk <= L)) {
-    const LayerOff& o = h->lo[l0];
-    if ((r = vec(o.ln1, (size_t)H, nl))) return r;
-    if ((r = mat(o.wqkv, h->QKV, H, nl))) return r;
-    if ((r = vec(o.bqkv, (size_t)h->QKV, nl))) return r;
-    if ((r = mat(o.wo, H, HD, nl))) return r;
-    if ((r = vec(o.ln2, (size_t)H, nl))) return r;
-    if ((r = mat(o.wgu, 2 * I, H, nl))) return r;
-    if ((r = mat(o.wd, H, I, nl))) return r;
+    // layer 0's tensors in layout order (matrices through the tile kernel, vectors through the strided one), at layer l0
+    for (int ti : h->layer0) {
+      const SlamTensorInfo& t = h->tensors[ti];
+      const int64_t off = t.offset + (int64_t)l0 * h->layer_stride;
+      if ((r = t.cols == 1 ? vec(off, (size_t)t.rows, nl) : mat(off, (int)t.rows, (int)t.cols, nl))) return r;
+    }
   }
-  if (chunk < 0 || chunk == L + 1) r = vec(h->off_norm, (size_t)H, 1);
+  if (chunk < 0 || chunk == L + 1) {
+    r = vec(h->off_norm, (size_t)H, 1);
+    if (!r && h->arch == 1) r = vec(h->off_norm_b, (size_t)H, 1);
+  }
   return r;
 }
 
@@ -523,16 +576,25 @@ int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_id
   // queries are stored pre-scaled by head_dim^-0.5 * log2(e) (folded into their rotation tables: one rounding), so the
   // attention kernels' scores leave the matrix pipe in the exp2 domain
   const float qscale = 1.44269504088896340736f / sqrtf((float)d.head_dim);
-  CK(rope_table(position_ids, M, T, d.head_dim, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
+  const bool opt = h->arch == 1;
+  if (opt) {
+    const size_t n = (size_t)M * (d.head_dim / 2);
+    ident_rope_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(h->cosb, h->sinb, h->cosq, h->sinq, n, qscale);
+    CK((int)hipGetLastError());
+  } else {
+    CK(rope_table(position_ids, M, T, d.head_dim, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
+  }
   CK(wait_chunk(h, 0, st));
   CK(wait_params(h, h->off_embed, h->lo[0].ln1, st));
-  CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
+  if (opt) CK(embed_pos_fwd(ids, position_ids, P + h->off_embed, P + h->off_pos, h->hs[0], h->prow, M, H, d.vocab, T, h->npos, st));
+  else CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
   for (int l = 0; l < L; ++l) {
     const LayerOff& o = h->lo[l];
     LayerAct& a = h->la[l];
     CK(wait_chunk(h, 1 + l, st));
     CK(wait_params(h, o.ln1, o.ln1 + h->layer_stride, st));
-    TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
+    if (opt) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, d.rms_eps, st));
+    else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
     if (d.head_dim == 64 && (H % 64 == 0) && (h->QKV % 128 == 0)) {  // bias + RoPE fused into the projection epilogue
       TK(F_QKV_FWD, st, gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
     } else {
@@ -542,6 +604,13 @@ int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_id
       fam_end(h, slot, st);
     }
     TK(F_ATTN_FWD, st, attn_fwd(a.qkv, a.o, a.lse, h->cur_seg_s, h->attn_plan_buf, h->attn_tune, M, nH, nKV, d.head_dim, st));
+    if (opt) {  // out_proj bias + residual, LayerNorm, fc1 bias + ReLU, fc2 bias + residual
+      TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, P + o.bo, h->hs[l], M, H, nH * d.head_dim, st));
+      TK(F_NORM_FWD, st, layernorm_fwd(a.hmid, P + o.ln2, P + o.ln2_b, a.x2, a.mu2, a.rstd2, M, H, d.rms_eps, st));
+      TK(F_GATEUP_FWD, st, gemm_nt_relu(a.x2, P + o.wgu, a.act, P + o.b1, M, I, H, st));
+      TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], P + o.b2, a.hmid, M, H, I, st));
+      continue;
+    }
     TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, nullptr, h->hs[l], M, H, nH * d.head_dim, st));
     TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
     const bool timed = h->time_gateup && h->tg_ev.size() == (size_t)(2 * L);
@@ -570,35 +639,70 @@ extern "C" {
 
 const char* slam_version(void) { return "slam-engine gfx950 r6"; }
 
-int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out) {
+int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out) { return slam_engine_create_arch(desc, 0, 0, out); }
+
+int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, SlamEngine** out) {
   if (!desc || !out) return SLAM_EINVAL;
   const SlamModelDesc& d = *desc;
+  if (arch != 0 && arch != 1) return SLAM_EINVAL;
   if ((d.head_dim != 64 && d.head_dim != 128) || d.n_heads <= 0 || d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return SLAM_EINVAL;
-  if (d.hidden % 8 || d.hidden > 2048 || d.intermediate % GU_BLK || d.vocab <= 0) return SLAM_EINVAL;
+  if (d.hidden % 8 || d.hidden > 2048 || d.vocab <= 0) return SLAM_EINVAL;
   if (d.n_layers <= 0) return SLAM_EINVAL;
+  if (arch == 0 && d.intermediate % GU_BLK) return SLAM_EINVAL;
+  // OPT: multi-head attention (kv = q heads), head_dim 64, a position table of n_positions + 2 rows
+  if (arch == 1 && (d.n_kv_heads != d.n_heads || d.head_dim != 64 || d.intermediate <= 0 || d.intermediate % 8 || n_positions <= 0))
+    return SLAM_EINVAL;
   SlamEngine* e = new SlamEngine();
   e->d = d;
+  e->arch = arch;
+  e->npos = arch == 1 ? n_positions + 2 : 0;
   e->QKV = (d.n_heads + 2 * d.n_kv_heads) * d.head_dim;
   e->vpad = d.vocab <= VPAD_SMALL ? VPAD_SMALL : ((d.vocab + 255) / 256) * 256;  // 256: the LM-head GEMM can take the 256 x 256 kernel
-  e->fuse_swiglu = (d.hidden % 64 == 0) && ((2 * d.intermediate) % 128 == 0);
+  e->fuse_swiglu = arch == 0 && (d.hidden % 64 == 0) && ((2 * d.intermediate) % 128 == 0);
   int64_t off = 0;
   e->off_embed = off;
   add_tensor(e, "embed", off, e->vpad, d.hidden);
+  if (arch == 1) {
+    e->off_pos = off;
+    add_tensor(e, "pos_embed", off, e->npos, d.hidden);
+  }
   e->lo.resize(d.n_layers);
   for (int l = 0; l < d.n_layers; ++l) {
     std::string p = "layers." + std::to_string(l) + ".";
     LayerOff& o = e->lo[l];
-    o.ln1 = off;  add_tensor(e, p + "ln1", off, d.hidden, 1);
-    o.wqkv = off; add_tensor(e, p + "wqkv", off, e->QKV, d.hidden);
-    o.bqkv = off; add_tensor(e, p + "bqkv", off, e->QKV, 1);
-    o.wo = off;   add_tensor(e, p + "wo", off, d.hidden, d.n_heads * d.head_dim);
-    o.ln2 = off;  add_tensor(e, p + "ln2", off, d.hidden, 1);
-    o.wgu = off;  add_tensor(e, p + "wgu", off, 2 * d.intermediate, d.hidden);
-    o.wd = off;   add_tensor(e, p + "wd", off, d.hidden, d.intermediate);
+    const size_t t0 = e->tensors.size();
+    if (arch == 1) {
+      o.ln1 = off;   add_tensor(e, p + "ln1", off, d.hidden, 1);
+      o.ln1_b = off; add_tensor(e, p + "ln1_b", off, d.hidden, 1);
+      o.wqkv = off;  add_tensor(e, p + "wqkv", off, e->QKV, d.hidden);
+      o.bqkv = off;  add_tensor(e, p + "bqkv", off, e->QKV, 1);
+      o.wo = off;    add_tensor(e, p + "wo", off, d.hidden, d.n_heads * d.head_dim);
+      o.bo = off;    add_tensor(e, p + "bo", off, d.hidden, 1);
+      o.ln2 = off;   add_tensor(e, p + "ln2", off, d.hidden, 1);
+      o.ln2_b = off; add_tensor(e, p + "ln2_b", off, d.hidden, 1);
+      o.wgu = off;   add_tensor(e, p + "w1", off, d.intermediate, d.hidden);
+      o.b1 = off;    add_tensor(e, p + "b1", off, d.intermediate, 1);
+      o.wd = off;    add_tensor(e, p + "w2", off, d.hidden, d.intermediate);
+      o.b2 = off;    add_tensor(e, p + "b2", off, d.hidden, 1);
+    } else {
+      o.ln1 = off;  add_tensor(e, p + "ln1", off, d.hidden, 1);
+      o.wqkv = off; add_tensor(e, p + "wqkv", off, e->QKV, d.hidden);
+      o.bqkv = off; add_tensor(e, p + "bqkv", off, e->QKV, 1);
+      o.wo = off;   add_tensor(e, p + "wo", off, d.hidden, d.n_heads * d.head_dim);
+      o.ln2 = off;  add_tensor(e, p + "ln2", off, d.hidden, 1);
+      o.wgu = off;  add_tensor(e, p + "wgu", off, 2 * d.intermediate, d.hidden);
+      o.wd = off;   add_tensor(e, p + "wd", off, d.hidden, d.intermediate);
+    }
+    if (l == 0)
+      for (size_t i = t0; i < e->tensors.size(); ++i) e->layer0.push_back((int)i);
   }
   e->layer_stride = d.n_layers > 1 ? e->lo[1].ln1 - e->lo[0].ln1 : (off - e->lo[0].ln1);
   e->off_norm = off;
   add_tensor(e, "norm", off, d.hidden, 1);
+  if (arch == 1) {
+    e->off_norm_b = off;
+    add_tensor(e, "norm_b", off, d.hidden, 1);
+  }
   e->n_params = off;
   *out = e;
   return SLAM_OK;
@@ -633,16 +737,16 @@ int slam_refresh_transposed(SlamEngine* h, slam_stream_t stream) {
   const SlamModelDesc& d = h->d;
   const bf16_t* P = h->params;
   bf16_t* Pt = h->params_t;
-  const int H = d.hidden, I = d.intermediate, HD = d.n_heads * d.head_dim;
+  const int H = d.hidden;
   CK(transpose_bf16(P + h->off_embed, Pt + h->off_embed, h->vpad, H, 1, 0, st));
-  // every layer has the same shapes at a constant stride: one launch per weight kind, grid.z = layers
-  const LayerOff& o = h->lo[0];
+  // every layer has the same shapes at a constant stride: one launch per weight kind (layer 0's matrices in layout order),
+  // grid.z = layers
   const int L = d.n_layers;
   const size_t ls = (size_t)h->layer_stride;
-  CK(transpose_bf16(P + o.wqkv, Pt + o.wqkv, h->QKV, H, L, ls, st));
-  CK(transpose_bf16(P + o.wo, Pt + o.wo, H, HD, L, ls, st));
-  CK(transpose_bf16(P + o.wgu, Pt + o.wgu, 2 * I, H, L, ls, st));
-  CK(transpose_bf16(P + o.wd, Pt + o.wd, H, I, L, ls, st));
+  for (int ti : h->layer0) {
+    const SlamTensorInfo& t = h->tensors[ti];
+    if (t.cols > 1) CK(transpose_bf16(P + t.offset, Pt + t.offset, (int)t.rows, (int)t.cols, L, ls, st));
+  }
   return SLAM_OK;
 }
 int slam_bind_params_t(SlamEngine* h, void* params_t_bf16) {
@@ -658,6 +762,8 @@ size_t slam_workspace_bytes(SlamEngine* h, int64_t max_tokens) {
   GemmTuneScope tune_scope(&h->gemm_tune);
   SlamEngine tmp;
   tmp.d = h->d;
+  tmp.arch = h->arch;
+  tmp.npos = h->npos;
   tmp.QKV = h->QKV;
   tmp.vpad = h->vpad;
   tmp.n_params = h->n_params;
@@ -735,7 +841,8 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
   h->have_fwd = false;
   GemmTuneScope tune_scope(&h->gemm_tune);
   CK(forward_layers(h, ids, position_ids, seg_start, seg_end, M, T, st));
-  TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, M, H, d.rms_eps, st));
+  if (h->arch == 1) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[L], P + h->off_norm, P + h->off_norm_b, h->hf, h->muf, h->rstdf, M, H, d.rms_eps, st));
+  else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, M, H, d.rms_eps, st));
   const int VP = h->vpad;
   TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_embed, h->logits, nullptr, nullptr, M, VP, H, st));
   h->have_loss = false;
@@ -791,6 +898,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
                  slam_stream_t stream) {
   if (!h || !ids || !lens || !logits_out || B <= 0 || T <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
+  if (h->arch != 0) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (B > h->kv_bmax || T > h->kv_cap) return h->fail(SLAM_EINVAL, "prefill batch exceeds the bound KV cache");
   if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
@@ -817,6 +925,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
 int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B, float* logits_out, slam_stream_t stream) {
   if (!h || !ids || !lens || !logits_out || B <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
+  if (h->arch != 0) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_decode_step needs a slam_prefill into the bound cache first");
   if (B != h->kv_B) return h->fail(SLAM_EINVAL, "decode batch differs from the prefill batch");
@@ -971,7 +1080,26 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
   CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_embed, VP, H, nullptr, false));  // not final: the gather side adds to it below
   TK(F_HEAD_DGRAD, st, dgrad(h->dlogits, h->off_embed, h->dx, VP, H));
   bf16_t* dh = h->dh_a;  // grad wrt hs[l+1]
-  TK(F_NORM_BWD, st, take(rmsnorm_bwd(h->dx, h->hs[L], P + h->off_norm, h->rstdf, nullptr, dh, G + h->off_norm, acc, h->part_ws, M, H, st, img(h->off_norm), sink())));
+  const bool opt = h->arch == 1;
+  if (opt) {  // final LayerNorm: dw | db slabs in part_ws, one finish launch per tensor
+    const int nbl = rmsnorm_bwd_blocks(M);
+    float* pw = h->part_ws;
+    float* pb = h->part_ws + (size_t)nbl * H;
+    TK(F_NORM_BWD, st, layernorm_bwd(h->dx, h->hs[L], P + h->off_norm, h->muf, h->rstdf, nullptr, dh, pw, pb, M, H, st));
+    CK(take(colsum_finish_many(pw, 0, nbl, H, G + h->off_norm, 0, 1, acc, st, img(h->off_norm), sink())));
+    CK(take(colsum_finish_many(pb, 0, nbl, H, G + h->off_norm_b, 0, 1, acc, st, img(h->off_norm_b), sink())));
+  } else {
+    TK(F_NORM_BWD, st, take(rmsnorm_bwd(h->dx, h->hs[L], P + h->off_norm, h->rstdf, nullptr, dh, G + h->off_norm, acc, h->part_ws, M, H, st, img(h->off_norm), sink())));
+  }
+  // bias column sums of the OPT layers: behind the hand-over of the weight gradient that reads the same operand (aux), else
+  // on the main stream
+  auto bias_cols = [&](const bf16_t* X, int N, float* part) -> int {
+    if (aux) {
+      if (int r = fork()) return r;
+      return colsum_bf16(X, N, M, N, nullptr, 1, part, ws);
+    }
+    return colsum_bf16(X, N, M, N, nullptr, 1, part, st);
+  };
 
   const int bl = bucket_layers > 0 ? bucket_layers : L;
   int64_t bucket_end = h->n_params;  // exclusive end of the not-yet-reported range
@@ -981,6 +1109,40 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
     LayerAct& a = h->la[l];
     bf16_t* dh2 = h->hs[l + 1];                              // grad wrt hmid[l]: hs[l+1] was last read by the norm backward above it
     bf16_t* dqkv = l + 1 < L ? h->la[l + 1].qkv : h->dqkv;   // layer l+1's q|k|v were last read by its attention backward
+    if (opt) {
+      // MLP: fc2 (bias + residual), ReLU, fc1 (bias); d(act) goes to this layer's own gu buffer, which nothing overwrites before
+      // the next forward (the fc1 weight gradient and the b1 column sums read it on the weight-gradient stream)
+      bf16_t* dact = a.gu;
+      CK(bias_cols(dh, H, h->b2_part + (size_t)l * h->hb_ps));
+      CK(wgrad(F_WD_WGRAD, dh, a.act, G + o.wd, H, I, img(o.wd), true, aux));
+      {
+        const int slot = fam_begin(h, F_DOWN_DGRAD, st);
+        if (Pt) {
+          CK(gemm_nt_drelu(dh, Pt + o.wd, dact, a.act, M, I, H, st));  // the ReLU backward in the dgrad epilogue
+        } else {
+          CK(dgrad(dh, o.wd, dact, H, I));
+          CK(relu_bwd(dact, a.act, (size_t)M * I, st));
+        }
+        fam_end(h, slot, st);
+      }
+      CK(bias_cols(dact, I, h->b1_part + (size_t)l * h->ib_ps));
+      CK(wgrad(F_WGU_WGRAD, dact, a.x2, G + o.wgu, I, H, img(o.wgu), true, aux));
+      TK(F_GATEUP_DGRAD, st, dgrad(dact, o.wgu, h->dx, I, H));
+      TK(F_NORM_BWD, st, layernorm_bwd(h->dx, a.hmid, P + o.ln2, a.mu2, a.rstd2, dh, dh2, h->ln_part + (size_t)(2 * l + 1) * h->ln_ps,
+                                       h->lnb_part + (size_t)(2 * l + 1) * h->ln_ps, M, H, st));
+      // attention: out_proj (bias + residual), then the same attention backward as Qwen2 (identity rotation tables)
+      CK(bias_cols(dh2, H, h->bo_part + (size_t)l * h->hb_ps));
+      CK(wgrad(F_WO_WGRAD, dh2, a.o, G + o.wo, H, HD, img(o.wo), true, aux));
+      TK(F_O_DGRAD, st, dgrad(dh2, o.wo, h->d_o, H, HD));
+      TK(F_ATTN_BWD, st, attn_bwd(a.qkv, a.o, h->d_o, a.lse, h->dsum, h->nlse, dqkv, h->dkv_part, h->cur_seg_s, h->cur_seg_e, h->attn_plan_buf, h->attn_tune, h->cosb, h->sinb,
+                  M, nH, nKV, d.head_dim, st));
+      CK(bias_cols(dqkv, h->QKV, h->bias_part + (size_t)l * h->bias_ps));
+      CK(wgrad(F_WQKV_WGRAD, dqkv, a.x1, G + o.wqkv, h->QKV, H, img(o.wqkv), true, aux));
+      TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, h->dx, h->QKV, H));
+      dh = a.hmid;
+      TK(F_NORM_BWD, st, layernorm_bwd(h->dx, h->hs[l], P + o.ln1, a.mu1, a.rstd1, dh2, dh, h->ln_part + (size_t)(2 * l) * h->ln_ps,
+                                       h->lnb_part + (size_t)(2 * l) * h->ln_ps, M, H, st));
+    } else {
     // MLP
     CK(wgrad(F_WD_WGRAD, dh, a.act, G + o.wd, H, I, img(o.wd)));
     {
@@ -1011,6 +1173,7 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
     TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, h->dx, h->QKV, H));
     dh = a.hmid;  // grad wrt hs[l]: hmid[l] was last read by the ln2 backward above
     TK(F_NORM_BWD, st, rmsnorm_bwd(h->dx, h->hs[l], P + o.ln1, a.rstd1, dh2, dh, nullptr, 1, h->ln_part + (size_t)(2 * l) * h->ln_ps, M, H, st));
+    }
     // bucket boundaries: every `bl` layers from the top, and after each of the last two layers so that the
     // final all-reduce (exposed behind the end of backward) only carries layer 0 + the embedding
     const bool boundary = cb && l > 0 && ((((L - l) % bl) == 0) || l <= 2);
@@ -1023,6 +1186,14 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
       CK(take(colsum_finish_many(h->ln_part + (size_t)(2 * l) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln1, (size_t)h->layer_stride, cnt, acc, fs, img(o.ln1), sink())));
       CK(take(colsum_finish_many(h->ln_part + (size_t)(2 * l + 1) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln2, (size_t)h->layer_stride, cnt, acc, fs, img(o.ln2), sink())));
       CK(take(colsum_finish_many(h->bias_part + (size_t)l * h->bias_ps, h->bias_ps, nbc, h->QKV, G + o.bqkv, (size_t)h->layer_stride, cnt, acc, fs, img(o.bqkv), sink())));
+      if (opt) {  // LayerNorm biases, out_proj / fc1 / fc2 biases
+        const size_t ls = (size_t)h->layer_stride;
+        CK(take(colsum_finish_many(h->lnb_part + (size_t)(2 * l) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln1_b, ls, cnt, acc, fs, img(o.ln1_b), sink())));
+        CK(take(colsum_finish_many(h->lnb_part + (size_t)(2 * l + 1) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln2_b, ls, cnt, acc, fs, img(o.ln2_b), sink())));
+        CK(take(colsum_finish_many(h->bo_part + (size_t)l * h->hb_ps, h->hb_ps, nbc, H, G + o.bo, ls, cnt, acc, fs, img(o.bo), sink())));
+        CK(take(colsum_finish_many(h->b1_part + (size_t)l * h->ib_ps, h->ib_ps, nbc, I, G + o.b1, ls, cnt, acc, fs, img(o.b1), sink())));
+        CK(take(colsum_finish_many(h->b2_part + (size_t)l * h->hb_ps, h->hb_ps, nbc, H, G + o.b2, ls, cnt, acc, fs, img(o.b2), sink())));
+      }
       fin_hi = l;
     }
     if (boundary) {
@@ -1041,30 +1212,39 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
   CK(fork());
   {
     const int slot = fam_begin(h, F_EMBED_WGRAD, ws);
+    // a scatter only touches the rows that occur in the batch: a tensor finished by one gets its image from a conversion pass
+    // (which also emits its partials when the values kept are the rounded ones)
+    auto finish_scattered = [&](int64_t off, size_t ne) -> int {
+      if (fin == 2 && !partials) {
+        CK(f32_to_bf16(G + off, IMG + off, ne, ws));
+      } else if (fin == 2) {
+        const int slots = f32_to_bf16_sumsq_slots(ne);
+        if (h->gn_used + (size_t)slots > h->gn_cap) return h->fail(SLAM_ESTATE, "gradient-norm partial slots exhausted");
+        CK(f32_to_bf16_sumsq(G + off, IMG + off, ne, h->gn_part + h->gn_used, ws));
+        h->gn_used += (size_t)slots;
+      } else {
+        if (IMG) CK(f32_to_bf16(G + off, IMG + off, ne, ws));
+        if (partials) {  // fp32 values kept: chunk sums of the tensor's own range (each chunk a partial of the norm)
+          const size_t slots = (ne + grad_chunk_elems() - 1) / grad_chunk_elems();
+          if (h->gn_used + slots > h->gn_cap) return h->fail(SLAM_ESTATE, "gradient-norm partial slots exhausted");
+          CK(grad_sumsq_chunks(G + off, 0, ne, 0, ne, h->gn_part + h->gn_used, ws));
+          h->gn_used += slots;
+        }
+      }
+      return SLAM_OK;
+    };
     if (VP == VPAD_SMALL) {
       CK(onehot(h->last_ids, h->onehot, M, VP, d.vocab, d.pad_token_id, ws));
       CK(take(gemm_tn(h->onehot, dh, G + h->off_embed, 1, M, VP, H, VP, H, h->gemm_ws, h->gemm_ws_bytes, ws, two ? 1 : 0, img(h->off_embed), sink())));
     } else {
       CK(embed_bwd(h->last_ids, dh, G + h->off_embed, M, H, VP, d.vocab, d.pad_token_id, h->embed_ws, ws));
-      // the scatter only touches the rows that occur in the batch (the others keep the head's contribution): this one tensor
-      // gets its image from a conversion pass (which also emits its partials when the values kept are the rounded ones)
-      const size_t ne = (size_t)VP * H;
-      if (fin == 2 && !partials) {
-        CK(f32_to_bf16(G + h->off_embed, IMG + h->off_embed, ne, ws));
-      } else if (fin == 2) {
-        const int slots = f32_to_bf16_sumsq_slots(ne);
-        if (h->gn_used + (size_t)slots > h->gn_cap) return h->fail(SLAM_ESTATE, "gradient-norm partial slots exhausted");
-        CK(f32_to_bf16_sumsq(G + h->off_embed, IMG + h->off_embed, ne, h->gn_part + h->gn_used, ws));
-        h->gn_used += (size_t)slots;
-      } else {
-        if (IMG) CK(f32_to_bf16(G + h->off_embed, IMG + h->off_embed, ne, ws));
-        if (partials) {  // fp32 values kept: their chunk sums (the tensor starts the buffer: chunk-aligned, its end is `n` here)
-          const size_t slots = (ne + grad_chunk_elems() - 1) / grad_chunk_elems();
-          if (h->gn_used + slots > h->gn_cap) return h->fail(SLAM_ESTATE, "gradient-norm partial slots exhausted");
-          CK(grad_sumsq_chunks(G + h->off_embed, 0, ne, 0, ne, h->gn_part + h->gn_used, ws));
-          h->gn_used += slots;
-        }
-      }
+      CK(finish_scattered(h->off_embed, (size_t)VP * H));
+    }
+    if (opt) {  // learned positions: deterministic token-ordered scatter by position row (no padding_idx), zeroed first when storing
+      const size_t ne = (size_t)h->npos * H;
+      if (!acc) CK((int)hipMemsetAsync(G + h->off_pos, 0, ne * sizeof(float), ws));
+      CK(embed_bwd(h->prow, dh, G + h->off_pos, M, H, h->npos, h->npos, -1, h->embed_ws, ws));
+      CK(finish_scattered(h->off_pos, ne));
     }
     fam_end(h, slot, ws);
   }
@@ -1145,7 +1325,7 @@ static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, c
   CK((int)hipEventRecord(h->ev_fork, st));
   CK((int)hipStreamWaitEvent(h->side, h->ev_fork, 0));
   const SlamModelDesc& d = h->d;
-  const int L = d.n_layers, H = d.hidden, I = d.intermediate, HD = d.n_heads * d.head_dim;
+  const int L = d.n_layers, H = d.hidden;
   bf16_t* Pt = h->params_t;
   for (int c = 0; c < L + 2; ++c) {
     if (fused) {
@@ -1160,11 +1340,11 @@ static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, c
         if (c == 0) {
           CK(transpose_bf16(P + h->off_embed, Pt + h->off_embed, h->vpad, H, 1, 0, h->side));
         } else if (c <= L) {
-          const LayerOff& o = h->lo[c - 1];
-          CK(transpose_bf16(P + o.wqkv, Pt + o.wqkv, h->QKV, H, 1, 0, h->side));
-          CK(transpose_bf16(P + o.wo, Pt + o.wo, H, HD, 1, 0, h->side));
-          CK(transpose_bf16(P + o.wgu, Pt + o.wgu, 2 * I, H, 1, 0, h->side));
-          CK(transpose_bf16(P + o.wd, Pt + o.wd, H, I, 1, 0, h->side));
+          for (int ti : h->layer0) {  // layer c - 1's matrices in layout order
+            const SlamTensorInfo& t = h->tensors[ti];
+            const int64_t off = t.offset + (int64_t)(c - 1) * h->layer_stride;
+            if (t.cols > 1) CK(transpose_bf16(P + off, Pt + off, (int)t.rows, (int)t.cols, 1, 0, h->side));
+          }
         }
       }
     }
@@ -1621,6 +1801,37 @@ int slam_op_rmsnorm_bwd(const void* dy, const void* x, const void* w, const floa
                         float* dw, float* ws, int M, int H, slam_stream_t s) {
   return rmsnorm_bwd((const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, rstd, (const bf16_t*)dres, (bf16_t*)dx, dw,
                      0, ws, M, H, (hipStream_t)s);
+}
+int slam_op_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int M, int H, float eps,
+                          slam_stream_t s) {
+  return layernorm_fwd((const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, M, H, eps, (hipStream_t)s);
+}
+size_t slam_op_layernorm_bwd_workspace(int M, int H) { return (size_t)2 * rmsnorm_bwd_blocks(M) * H * sizeof(float); }
+int slam_op_layernorm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* dres,
+                          void* dx, float* dw, float* db, float* ws, int M, int H, slam_stream_t s) {
+  const int nb = rmsnorm_bwd_blocks(M);
+  float* pw = ws;
+  float* pb = ws + (size_t)nb * H;
+  int r = layernorm_bwd((const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, pw, pb,
+                        M, H, (hipStream_t)s);
+  if (r) return r;
+  r = colsum_finish_many(pw, 0, nb, H, dw, 0, 1, 0, (hipStream_t)s);
+  if (r) return r;
+  return colsum_finish_many(pb, 0, nb, H, db, 0, 1, 0, (hipStream_t)s);
+}
+int slam_op_embed_pos_fwd(const int64_t* ids, const int64_t* position_ids, const void* E, const void* P, void* out, int64_t* prow,
+                          int M, int H, int V, int T, int n_rows_p, slam_stream_t s) {
+  return embed_pos_fwd(ids, position_ids, (const bf16_t*)E, (const bf16_t*)P, (bf16_t*)out, prow, M, H, V, T, n_rows_p, (hipStream_t)s);
+}
+int slam_op_gemm_nt_relu(const void* X, const void* W, void* act, const void* bias, int M, int N, int K, slam_stream_t s) {
+  return gemm_nt_relu((const bf16_t*)X, (const bf16_t*)W, (bf16_t*)act, (const bf16_t*)bias, M, N, K, (hipStream_t)s);
+}
+int slam_op_gemm_nt_drelu(const void* dY, const void* Wt, void* dact, const void* act, int M, int N, int K, slam_stream_t s) {
+  return gemm_nt_drelu((const bf16_t*)dY, (const bf16_t*)Wt, (bf16_t*)dact, (const bf16_t*)act, M, N, K, (hipStream_t)s);
+}
+int slam_op_relu_bwd(void* d, const void* act, int64_t n, slam_stream_t s) {
+  if (n < 0) return SLAM_EINVAL;
+  return relu_bwd((bf16_t*)d, (const bf16_t*)act, (size_t)n, (hipStream_t)s);
 }
 int slam_op_rope(void* qkv, int ld, int M, int T, int n_rot_heads, int head_dim, const int64_t* position_ids, float theta,
                  int backward, float* cs_ws, slam_stream_t s) {

@@ -108,6 +108,11 @@ struct GemmArgs {
   int cohorts;        // > 1: the slots of an XCD in this many contiguous cohorts, cohort c starts c * stagger_ticks late (every block)
   int group_cols;     // > 0: tile rasterisation groups are group_rows x group_cols tiles (0 = group_rows x all columns)
   int batch_epilogue_loads;  // persistent 256 x 256 SwiGLU backward: gate|up loads of a whole quadrant issued together (dswiglu_tile)
+  // OPT's ReLU FFN: relu = 1 stores max(C + bias, 0) (fc1 forward); relu_mask [R][ldc] zeroes C where the stored post-ReLU
+  // activation is not > 0 (fc2 dgrad = the ReLU backward). Only the one-block-per-tile epilogues (epilogue8 / epilogue32 /
+  // the 4-column one) have them: the persistent and 256 x 224 launches are not chosen when either is set.
+  int relu;
+  const bf16_t* relu_mask;
 };
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
@@ -279,11 +284,13 @@ SLAM_DEVICE void epilogue8(const GemmArgs& p_, const f32x4_t (&acc)[4][4], int r
     void* C; bf16_t* act; bf16_t* gu; int R, Cn, ldc, nt_store;
     const bf16_t* bias; const bf16_t* resid; const float* rope_cos; const float* rope_sin; int rope_heads;
     const float* rope_cos_q; const float* rope_sin_q; int rope_q_heads;
+    int relu; const bf16_t* relu_mask;
   };
   const Fields p = {p_.C, p_.act, p_.gu, p_.R, p_.Cn, p_.ldc, p_.nt_store,
                   LEAN ? nullptr : p_.bias, LEAN ? nullptr : p_.resid, LEAN ? nullptr : p_.rope_cos,
                   LEAN ? nullptr : p_.rope_sin, LEAN ? 0 : p_.rope_heads,
-                  LEAN ? nullptr : p_.rope_cos_q, LEAN ? nullptr : p_.rope_sin_q, LEAN ? 0 : p_.rope_q_heads};
+                  LEAN ? nullptr : p_.rope_cos_q, LEAN ? nullptr : p_.rope_sin_q, LEAN ? 0 : p_.rope_q_heads,
+                  LEAN ? 0 : p_.relu, LEAN ? nullptr : p_.relu_mask};
   // lane holds C[m][cq(q) .. +7] for q = 0, 1 in fragments (2q, 2q+1): 16-byte accesses throughout
   const int cw = col0 + wn * 64 + g * 8;  // + 32 q
   uint4 bb4[2];
@@ -328,10 +335,14 @@ SLAM_DEVICE void epilogue8(const GemmArgs& p_, const f32x4_t (&acc)[4][4], int r
       }
       continue;
     }
-    uint4 rr4[2];
+    uint4 rr4[2], mm4[2];
     if (p.resid) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) rr4[q] = *reinterpret_cast<const uint4*>(p.resid + rowoff + cw + 32 * q);
+    }
+    if (p.relu_mask) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) mm4[q] = *reinterpret_cast<const uint4*>(p.relu_mask + rowoff + cw + 32 * q);
     }
     float v[2][8];
 #pragma unroll
@@ -349,6 +360,16 @@ SLAM_DEVICE void epilogue8(const GemmArgs& p_, const f32x4_t (&acc)[4][4], int r
         unpack_bf16x8(rr4[q], r);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[q][e] += r[e];
+      }
+      if (p.relu) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[q][e] = fmaxf(v[q][e], 0.f);
+      }
+      if (p.relu_mask) {
+        float a[8];
+        unpack_bf16x8(mm4[q], a);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[q][e] = a[e] > 0.f ? v[q][e] : 0.f;
       }
     }
     // fused RoPE: the wave's 64 columns are one head; q = 0 / 1 hold d and d + 32 of the same lane
@@ -562,11 +583,13 @@ SLAM_DEVICE void epilogue32(const GemmArgs& p_, const f32x16_t (&acc)[2][2], int
     void* C; bf16_t* act; bf16_t* gu; int R, Cn, ldc, nt_store;
     const bf16_t* bias; const bf16_t* resid; const float* rope_cos; const float* rope_sin; int rope_heads;
     const float* rope_cos_q; const float* rope_sin_q; int rope_q_heads;
+    int relu; const bf16_t* relu_mask;
   };
   const Fields p = {p_.C, p_.act, p_.gu, p_.R, p_.Cn, p_.ldc, p_.nt_store,
                   LEAN ? nullptr : p_.bias, LEAN ? nullptr : p_.resid, LEAN ? nullptr : p_.rope_cos,
                   LEAN ? nullptr : p_.rope_sin, LEAN ? 0 : p_.rope_heads,
-                  LEAN ? nullptr : p_.rope_cos_q, LEAN ? nullptr : p_.rope_sin_q, LEAN ? 0 : p_.rope_q_heads};
+                  LEAN ? nullptr : p_.rope_cos_q, LEAN ? nullptr : p_.rope_sin_q, LEAN ? 0 : p_.rope_q_heads,
+                  LEAN ? 0 : p_.relu, LEAN ? nullptr : p_.relu_mask};
   const int cl = cbase + 16 * h;  // + 32 nb
   uint4 bb4[2][2];
   if (p.bias) {
@@ -618,12 +641,18 @@ SLAM_DEVICE void epilogue32(const GemmArgs& p_, const f32x16_t (&acc)[2][2], int
       }
       continue;
     }
-    uint4 rr4[2][2];
+    uint4 rr4[2][2], mm4[2][2];
     if (p.resid) {
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
         for (int u = 0; u < 2; ++u) rr4[nb][u] = *reinterpret_cast<const uint4*>(p.resid + rowoff + cl + 32 * nb + 8 * u);
+    }
+    if (p.relu_mask) {
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) mm4[nb][u] = *reinterpret_cast<const uint4*>(p.relu_mask + rowoff + cl + 32 * nb + 8 * u);
     }
     float v[2][16];
 #pragma unroll
@@ -646,6 +675,19 @@ SLAM_DEVICE void epilogue32(const GemmArgs& p_, const f32x16_t (&acc)[2][2], int
           unpack_bf16x8(rr4[nb][u], r);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[nb][8 * u + e] += r[e];
+        }
+      }
+      if (p.relu) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v[nb][e] = fmaxf(v[nb][e], 0.f);
+      }
+      if (p.relu_mask) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          float a[8];
+          unpack_bf16x8(mm4[nb][u], a);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[nb][8 * u + e] = a[e] > 0.f ? v[nb][8 * u + e] : 0.f;
         }
       }
     }
@@ -972,12 +1014,19 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
         }
       }
     } else {
-      uint2 rr[4];
+      uint2 rr[4], mm[4];
       if (p.resid) {
 #pragma unroll
         for (int fn = 0; fn < NF; ++fn) {
           int n = col0 + wn * NF * 16 + fn * 16 + g * 4;
           rr[fn] = *reinterpret_cast<const uint2*>(p.resid + rowoff + (n < p.Cn ? n : 0));
+        }
+      }
+      if (p.relu_mask) {
+#pragma unroll
+        for (int fn = 0; fn < NF; ++fn) {
+          int n = col0 + wn * NF * 16 + fn * 16 + g * 4;
+          mm[fn] = *reinterpret_cast<const uint2*>(p.relu_mask + rowoff + (n < p.Cn ? n : 0));
         }
       }
       f32x4_t v[NF];
@@ -991,6 +1040,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
         if (p.resid) {
           v[fn][0] += __uint_as_float(rr[fn].x << 16); v[fn][1] += __uint_as_float(rr[fn].x & 0xffff0000u);
           v[fn][2] += __uint_as_float(rr[fn].y << 16); v[fn][3] += __uint_as_float(rr[fn].y & 0xffff0000u);
+        }
+        if (p.relu) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[fn][r] = fmaxf(v[fn][r], 0.f);
+        }
+        if (p.relu_mask) {
+          const float a[4] = {__uint_as_float(mm[fn].x << 16), __uint_as_float(mm[fn].x & 0xffff0000u),
+                              __uint_as_float(mm[fn].y << 16), __uint_as_float(mm[fn].y & 0xffff0000u)};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[fn][r] = a[r] > 0.f ? v[fn][r] : 0.f;
         }
       }
       if constexpr (NF == 4) {
@@ -2334,7 +2393,7 @@ static int launch_256(GemmArgs a, hipStream_t st) {
   const int cus_all = cus_dev;
   const int want = T().g256_persist_cus > 0 ? (T().g256_persist_cus & ~7) : cus_all;
   const int cus = want >= 8 && want < cus_all ? want : cus_all;
-  const bool persist = T().g256_persist && tiles > cus && !a.bias && !a.resid && !a.rope_cos;
+  const bool persist = T().g256_persist && tiles > cus && !a.bias && !a.resid && !a.rope_cos && !a.relu && !a.relu_mask;
   if (T().mf32 && T().g256_w4 && persist) {  // four waves of 128 x 128, persistent
     static bool attr4 = false;
     if (!attr4) {
@@ -2362,7 +2421,7 @@ static int launch_256(GemmArgs a, hipStream_t st) {
 // nt224_min_k: long contractions only (gate|up dgrad, K = 9728): interleaved A/B x3 on the Slam-358M step 311.5-312.0k vs 310.3-310.6k tok/s; with the K = 896 / 1152 dgrads as well: no gain  (field of GemmTune, kernels.h)
 static bool use_nt224(const GemmArgs& a) {
   if (!T().nt224 || (a.R % 256) || (a.Cn % 224) || (a.Kc % BK) || a.Kc < 2 * BK) return false;
-  if (a.bias || a.act || a.gu || a.rope_cos) return false;
+  if (a.bias || a.act || a.gu || a.rope_cos || a.relu || a.relu_mask) return false;
   if (T().nt224 == 2) return true;
   return T().shared && a.Kc >= T().nt224_min_k && (a.R / 256) * (a.Cn / 224) >= 64;
 }
@@ -2404,6 +2463,25 @@ int gemm_nt(const bf16_t* X, const bf16_t* W, bf16_t* Y, const bf16_t* bias, con
              (N + BN - 1) / BN};
   const bool dma_ok = (K % BK == 0) && (N % BN == 0);
   if (dma_ok && T().glds) return launch_nt_dma(a, st);
+  return launch<false, false, false, false>(a, 1, st);
+}
+
+// OPT fc1: act[M,N] = relu(X W^T + bias), only the post-ReLU activation is stored (act > 0 is the backward's mask)
+int gemm_nt_relu(const bf16_t* X, const bf16_t* W, bf16_t* act, const bf16_t* bias, int M, int N, int K, hipStream_t st) {
+  if (check_dims(M, N, K, K, K, N) || (K & 7)) return -1;
+  GemmArgs a{X, W, act, bias, nullptr, nullptr, nullptr, M, N, K, K, K, N, ((K + BK - 1) / BK) * BK, (M + BM - 1) / BM,
+             (N + BN - 1) / BN};
+  a.relu = 1;
+  if ((K % BK == 0) && (N % BN == 0) && T().glds) return launch_nt_dma(a, st);
+  return launch<false, false, false, false>(a, 1, st);
+}
+// OPT fc2 dgrad with the ReLU backward in the epilogue: d(act)[M,N] = (dY[M,K] Wt[N,K]^T) * [act > 0]
+int gemm_nt_drelu(const bf16_t* dY, const bf16_t* Wt, bf16_t* dact, const bf16_t* act, int M, int N, int K, hipStream_t st) {
+  if (check_dims(M, N, K, K, K, N) || (K & 7)) return -1;
+  GemmArgs a{dY, Wt, dact, nullptr, nullptr, nullptr, nullptr, M, N, K, K, K, N, ((K + BK - 1) / BK) * BK, (M + BM - 1) / BM,
+             (N + BN - 1) / BN};
+  a.relu_mask = act;
+  if ((K % BK == 0) && (N % BN == 0) && T().glds) return launch_nt_dma(a, st);
   return launch<false, false, false, false>(a, 1, st);
 }
 

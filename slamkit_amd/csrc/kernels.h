@@ -59,6 +59,10 @@ int gemm_nt_swiglu(const bf16_t* X, const bf16_t* W, bf16_t* Y, bf16_t* act, int
 int gemm_nt_rope(const bf16_t* X, const bf16_t* W, bf16_t* Y, const bf16_t* bias, const float* cs, const float* sn,
                  const float* csq, const float* snq, int q_heads, int rope_heads, int M, int N, int K, hipStream_t st);
 int gemm_nt_dswiglu(const bf16_t* dY, const bf16_t* Wt, bf16_t* gu, int M, int N, int K, hipStream_t st);
+// OPT's ReLU FFN: fc1 act = relu(X W^T + bias) (only the post-ReLU activation is stored); fc2 dgrad with the ReLU backward
+// fused into the epilogue: dact = (dY Wt^T) * [act > 0]
+int gemm_nt_relu(const bf16_t* X, const bf16_t* W, bf16_t* act, const bf16_t* bias, int M, int N, int K, hipStream_t st);
+int gemm_nt_drelu(const bf16_t* dY, const bf16_t* Wt, bf16_t* dact, const bf16_t* act, int M, int N, int K, hipStream_t st);
 int gemm_nn(const bf16_t* dY, const bf16_t* W, bf16_t* dX, const bf16_t* resid, int M, int N, int K,
             hipStream_t st);
 int gemm_tn_splits(int M, int N, int K);
@@ -107,6 +111,12 @@ int attn_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, const float*
 
 // elementwise.hip
 int rmsnorm_fwd(const bf16_t* x, const bf16_t* w, bf16_t* y, float* rstd, int M, int H, float eps, hipStream_t st);
+// LayerNorm (OPT): the compile-time LN variant of the RMSNorm kernels - y = bf16((x - mu) rstd w + b), mu / rstd saved
+int layernorm_fwd(const bf16_t* x, const bf16_t* w, const bf16_t* b, bf16_t* y, float* mean, float* rstd, int M, int H, float eps,
+                  hipStream_t st);
+// dx (+ dres) and per-block partial slabs of dw and db ([rmsnorm_bwd_blocks(M)][H] each; colsum_finish_many finishes them)
+int layernorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* mean, const float* rstd, const bf16_t* dres,
+                  bf16_t* dx, float* dw_part, float* db_part, int M, int H, hipStream_t st);
 int rmsnorm_bwd_blocks(int M);
 int rmsnorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* rstd, const bf16_t* dres,
                 bf16_t* dx, float* dw, int accumulate, float* part, int M, int H, hipStream_t st, bf16_t* dw_img = nullptr,
@@ -122,6 +132,12 @@ int rope_apply(bf16_t* qkv, int ld, int M, int nrot_heads, int head_dim, const f
 int swiglu_fwd(const bf16_t* gu, bf16_t* act, int M, int I, int blk, hipStream_t st);
 int swiglu_bwd(bf16_t* gu, const bf16_t* dact, int M, int I, int blk, hipStream_t st);
 int embed_fwd(const int64_t* ids, const bf16_t* E, bf16_t* out, int M, int H, int V, hipStream_t st);
+// OPT embedding: out = bf16(E[ids] + P[pos + 2]), pos = position_ids or m % T (indices clamped to the tables); the position
+// row of every token goes to prow (int64 [M], nullable) for the backward's scatter
+int embed_pos_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const bf16_t* P, bf16_t* out, int64_t* prow, int M, int H,
+                  int V, int T, int NP, hipStream_t st);
+// d *= [act > 0] (n a multiple of 8): the ReLU backward without the fused fc2 dgrad epilogue
+int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st);
 int onehot(const int64_t* ids, bf16_t* oh, int M, int Vp, int V, int pad_id, hipStream_t st);
 // gather-side embedding gradient for large vocabularies: dE[ids[m]] += dh[m] in token order (deterministic);
 // ws = embed_bwd_workspace_ints(M, Vp) ints

@@ -55,6 +55,7 @@ def load_library(path: Optional[str] = None):
     vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
     sig = {
         "slam_engine_create": (C.c_int, [C.POINTER(SlamModelDesc), C.POINTER(vp)]),
+        "slam_engine_create_arch": (C.c_int, [C.POINTER(SlamModelDesc), i32, i32, C.POINTER(vp)]),
         "slam_engine_destroy": (None, [vp]),
         "slam_last_error": (C.c_char_p, [vp]),
         "slam_version": (C.c_char_p, []),
@@ -122,6 +123,13 @@ def load_library(path: Optional[str] = None):
         "slam_op_rmsnorm_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
         "slam_op_rmsnorm_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_rmsnorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+        "slam_op_layernorm_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
+        "slam_op_layernorm_bwd_workspace": (sz, [C.c_int, C.c_int]),
+        "slam_op_layernorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+        "slam_op_embed_pos_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_gemm_nt_relu": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_gemm_nt_drelu": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_relu_bwd": (C.c_int, [vp, vp, i64, vp]),
         "slam_op_rope": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, f32, C.c_int, vp, vp]),
         "slam_op_swiglu_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "slam_op_swiglu_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
@@ -172,13 +180,15 @@ class TensorSpec:
 class Engine:
     """Thin owner of a SlamEngine handle plus the torch tensors it borrows."""
 
-    def __init__(self, desc: SlamModelDesc):
+    def __init__(self, desc: SlamModelDesc, arch: int = 0, n_positions: int = 0):
+        """arch 0 = Qwen2, 1 = OPT (n_positions = max_position_embeddings; slam_engine_create_arch)."""
         self.lib = load_library()
         self.desc = desc
+        self.arch = arch
         h = C.c_void_p()
-        rc = self.lib.slam_engine_create(C.byref(desc), C.byref(h))
+        rc = self.lib.slam_engine_create_arch(C.byref(desc), arch, n_positions, C.byref(h))
         if rc != 0:
-            raise EngineError(f"slam_engine_create failed ({rc}): unsupported model description")
+            raise EngineError(f"slam_engine_create_arch failed ({rc}): unsupported model description")
         self.h = h
         self.n_params = int(self.lib.slam_param_count(h))
         self.tensors: Dict[str, TensorSpec] = {}

@@ -32,20 +32,62 @@ KNOWN_BASE_CONFIGS = {
     "Qwen/Qwen2.5-1.5B": dict(num_hidden_layers=28, hidden_size=1536, num_attention_heads=12, num_key_value_heads=2,
                               head_dim=128, intermediate_size=8960, rms_norm_eps=1e-6, rope_theta=1000000.0,
                               tie_word_embeddings=True, initializer_range=0.02),
+    # OPT: the reference's default body (config/model/default.yaml base_model_name) and the TWIST-1.3B body
+    "facebook/opt-125m": dict(model_type="opt", num_hidden_layers=12, hidden_size=768, num_attention_heads=12, ffn_dim=3072,
+                              max_position_embeddings=2048, init_std=0.02, tie_word_embeddings=True),
+    "facebook/opt-1.3b": dict(model_type="opt", num_hidden_layers=24, hidden_size=2048, num_attention_heads=32, ffn_dim=8192,
+                              max_position_embeddings=2048, init_std=0.02, tie_word_embeddings=True),
 }
+
+ARCH_QWEN2, ARCH_OPT = 0, 1
 
 
 _HF_DIM_KEYS = ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "head_dim",
                 "intermediate_size", "rms_norm_eps", "rope_theta", "tie_word_embeddings", "initializer_range")
 
 
+def _opt_base_config(c: dict) -> dict:
+    """Engine-side `base_config` of a HuggingFace OPTConfig dict (or of an already converted one: idempotent). Only pre-LN
+    OPT as OPTForCausalLM computes it is supported (OPT-125m, OPT-1.3B); OPT-350m's post-LN + project_in/out layout,
+    other activations, untied heads and hidden > 2048 are refused."""
+    H = int(c["hidden_size"])
+    nH = int(c["num_attention_heads"])
+    if not c.get("do_layer_norm_before", True):
+        raise ValueError("OPT with do_layer_norm_before=False (post-LN, e.g. OPT-350m) is not supported")
+    if c.get("word_embed_proj_dim", H) not in (None, H):
+        raise ValueError(f"OPT with word_embed_proj_dim={c['word_embed_proj_dim']} != hidden_size={H} (project_in/out) "
+                         "is not supported")
+    if not c.get("enable_bias", True):
+        raise ValueError("OPT without biases (enable_bias=False) is not supported")
+    if not c.get("layer_norm_elementwise_affine", True):
+        raise ValueError("OPT LayerNorm without elementwise affine parameters is not supported")
+    if c.get("activation_function", "relu") != "relu":
+        raise ValueError(f"unsupported OPT activation_function {c.get('activation_function')!r} (relu only)")
+    if c.get("_remove_final_layer_norm", False):
+        raise ValueError("OPT with _remove_final_layer_norm=True is not supported")
+    if not c.get("tie_word_embeddings", True):
+        raise ValueError("the engine supports tied embeddings only; this OPT config unties lm_head")
+    if H > 2048:
+        raise ValueError(f"OPT hidden_size {H} > 2048 is not supported")
+    if H % nH or H // nH != 64:
+        raise ValueError(f"OPT head_dim {H / nH:g} is not supported (64 only)")
+    ffn = c.get("ffn_dim", c.get("intermediate_size"))
+    eps = c.get("layer_norm_eps", 1e-5)  # OPTDecoderLayer's nn.LayerNorm default
+    return dict(model_type="opt", num_hidden_layers=int(c["num_hidden_layers"]), hidden_size=H, num_attention_heads=nH,
+                num_key_value_heads=nH, head_dim=64, intermediate_size=int(ffn),
+                max_position_embeddings=int(c["max_position_embeddings"]), layer_norm_eps=float(eps),
+                initializer_range=float(c.get("init_std", c.get("initializer_range", 0.02))), tie_word_embeddings=True)
+
+
 def base_config_from_hf(c: dict) -> dict:
-    """Engine-side `base_config` from a HuggingFace Qwen2 config dict (a text-LM `config.json`, or the `base_config`
+    """Engine-side `base_config` from a HuggingFace Qwen2 or OPT config dict (a text-LM `config.json`, or the `base_config`
     object the reference's UnitLMConfig serialises, unit_lm.py:63-73). transformers 4.x stores `rope_theta` at the top
-    level, 5.x under `rope_parameters`."""
+    level, 5.x under `rope_parameters`. OPT configs keep model_type "opt" in the result."""
     mt = c.get("model_type", "qwen2")
+    if mt == "opt":
+        return _opt_base_config(c)
     if mt not in ("qwen2",):
-        raise ValueError(f"the engine implements the Qwen2 decoder family only (model_type={mt!r})")
+        raise ValueError(f"the engine implements the Qwen2 and OPT decoder families only (model_type={mt!r})")
     if c.get("hidden_act", "silu") != "silu":
         raise ValueError(f"unsupported hidden_act {c.get('hidden_act')!r}")
     if c.get("use_sliding_window"):
@@ -109,6 +151,8 @@ class UnitLMConfig:
                     base_config = base_config_from_hf(json.load(f))
             elif base_model_name in KNOWN_BASE_CONFIGS:
                 base_config = dict(KNOWN_BASE_CONFIGS[base_model_name])
+                if base_config.get("model_type") == "opt":
+                    base_config = base_config_from_hf(base_config)
             else:
                 raise ValueError(f"unknown base model {base_model_name!r}: pass a local HuggingFace directory or "
                                  f"base_config=dict(...) (no hub access); known: {sorted(KNOWN_BASE_CONFIGS)}")
@@ -116,7 +160,7 @@ class UnitLMConfig:
             base_config = base_config_from_hf(base_config)  # the reference's serialised Qwen2Config
         base_config = dict(base_config)
         for k in list(kwargs):
-            if k in ("rope_theta", "rms_norm_eps", "initializer_range"):
+            if k in ("rope_theta", "rms_norm_eps", "initializer_range", "layer_norm_eps"):
                 base_config[k] = kwargs.pop(k)
         base_config.setdefault("head_dim", base_config["hidden_size"] // base_config["num_attention_heads"])
         base_config.setdefault("rms_norm_eps", 1e-6)
@@ -147,12 +191,23 @@ class UnitLMConfig:
                     bos_token_id=self.bos_token_id, eos_token_id=self.eos_token_id, torch_dtype=self.torch_dtype,
                     max_tokens=self.max_tokens)
 
+    @property
+    def is_opt(self) -> bool:
+        return self.base_config.get("model_type") == "opt"
+
+    def engine_arch(self) -> Tuple[int, int]:
+        """(arch, n_positions) of slam_engine_create_arch: Qwen2 = (0, 0), OPT = (1, max_position_embeddings)."""
+        if self.is_opt:
+            return ARCH_OPT, int(self.base_config["max_position_embeddings"])
+        return ARCH_QWEN2, 0
+
     def engine_desc(self) -> E.SlamModelDesc:
         b = self.base_config
+        eps = b["layer_norm_eps"] if self.is_opt else b["rms_norm_eps"]  # OPT: the LayerNorm eps travels in rms_eps
         return E.SlamModelDesc(b["num_hidden_layers"], b["hidden_size"], b["num_attention_heads"],
                                b["num_key_value_heads"], b["head_dim"], b["intermediate_size"], self.vocab_size,
                                self.pad_token_id if self.pad_token_id is not None else -1,
-                               float(b["rms_norm_eps"]), float(b["rope_theta"]))
+                               float(eps), float(b["rope_theta"]))
 
 
 @dataclass
@@ -210,7 +265,7 @@ class UnitLM(TokenLM):
             raise RuntimeError("slamkit_amd.UnitLM needs a ROCm GPU (gfx950); there is no CPU fallback")
         self.config = config
         self.device = torch.device(device or f"cuda:{torch.cuda.current_device()}")
-        self.engine = E.Engine(config.engine_desc())
+        self.engine = E.Engine(config.engine_desc(), *config.engine_arch())
         n = self.engine.n_params
         with torch.cuda.device(self.device):
             self.flat_params = torch.zeros(n, dtype=torch.bfloat16, device=self.device)
@@ -245,9 +300,12 @@ class UnitLM(TokenLM):
 
     # ---- layout ------------------------------------------------------------------------------
     def _build_key_map(self):
+        if self.config.is_opt:
+            return self._build_key_map_opt()
         b, t = self.config.base_config, self.engine.tensors
         nH, nKV, hd, I = b["num_attention_heads"], b["num_key_value_heads"], b["head_dim"], b["intermediate_size"]
         H = b["hidden_size"]
+        self._embed_key = "lm.model.embed_tokens.weight"
         km: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         km["lm.model.embed_tokens.weight"] = (t["embed"].offset, (self.config.vocab_size, H))
         for l in range(b["num_hidden_layers"]):
@@ -268,6 +326,35 @@ class UnitLM(TokenLM):
             km[p + "input_layernorm.weight"] = (t[q + "ln1"].offset, (H,))
             km[p + "post_attention_layernorm.weight"] = (t[q + "ln2"].offset, (H,))
         km["lm.model.norm.weight"] = (t["norm"].offset, (H,))
+        self.key_map = km
+
+    def _build_key_map_opt(self):
+        """HF OPTForCausalLM names under the reference UnitLM's `lm.` prefix (the tied lm_head.weight is not listed)."""
+        b, t = self.config.base_config, self.engine.tensors
+        H, I, L = b["hidden_size"], b["intermediate_size"], b["num_hidden_layers"]
+        km: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
+        d = "lm.model.decoder."
+        self._embed_key = d + "embed_tokens.weight"
+        km[d + "embed_tokens.weight"] = (t["embed"].offset, (self.config.vocab_size, H))
+        km[d + "embed_positions.weight"] = (t["pos_embed"].offset, (t["pos_embed"].rows, H))
+        km[d + "final_layer_norm.weight"] = (t["norm"].offset, (H,))
+        km[d + "final_layer_norm.bias"] = (t["norm_b"].offset, (H,))
+        for l in range(L):
+            p, q = f"{d}layers.{l}.", f"layers.{l}."
+            o, ob = t[q + "wqkv"].offset, t[q + "bqkv"].offset
+            for j, n in enumerate(("q_proj", "k_proj", "v_proj")):  # wqkv rows are q | k | v
+                km[p + f"self_attn.{n}.weight"] = (o + j * H * H, (H, H))
+                km[p + f"self_attn.{n}.bias"] = (ob + j * H, (H,))
+            km[p + "self_attn.out_proj.weight"] = (t[q + "wo"].offset, (H, H))
+            km[p + "self_attn.out_proj.bias"] = (t[q + "bo"].offset, (H,))
+            km[p + "self_attn_layer_norm.weight"] = (t[q + "ln1"].offset, (H,))
+            km[p + "self_attn_layer_norm.bias"] = (t[q + "ln1_b"].offset, (H,))
+            km[p + "fc1.weight"] = (t[q + "w1"].offset, (I, H))
+            km[p + "fc1.bias"] = (t[q + "b1"].offset, (I,))
+            km[p + "fc2.weight"] = (t[q + "w2"].offset, (H, I))
+            km[p + "fc2.bias"] = (t[q + "b2"].offset, (H,))
+            km[p + "final_layer_norm.weight"] = (t[q + "ln2"].offset, (H,))
+            km[p + "final_layer_norm.bias"] = (t[q + "ln2_b"].offset, (H,))
         self.key_map = km
 
     def _view(self, flat: torch.Tensor, key: str, writable: bool = False) -> torch.Tensor:
@@ -318,7 +405,8 @@ class UnitLM(TokenLM):
             else:
                 v.normal_(0.0, std, generator=g)
         if self.config.pad_token_id is not None and self.config.pad_token_id >= 0:
-            self._view(self._weights, "lm.model.embed_tokens.weight", True)[self.config.pad_token_id].zero_()
+            # nn.Embedding(padding_idx): the token table only (OPT's position table has no padding row)
+            self._view(self._weights, self._embed_key, True)[self.config.pad_token_id].zero_()
         self.sync_params_from_master()
 
     def sync_params_from_master(self):
@@ -378,6 +466,8 @@ class UnitLM(TokenLM):
         HuggingFace causal LM's `model.*` / `lm_head.weight` (text-LM weights for TWIST initialisation)."""
         if any(k.startswith("lm.") for k in sd):
             return dict(sd)
+        if any(k.startswith("decoder.") for k in sd):  # a bare OPTModel (HF's base_model_prefix is "model")
+            return {("lm.model." + k if k.startswith("decoder.") else k): v for k, v in sd.items()}
         return {("lm." + k if k.startswith(("model.", "lm_head.")) else k): v for k, v in sd.items()}
 
     @torch.no_grad()
@@ -398,7 +488,7 @@ class UnitLM(TokenLM):
             if k in sd:
                 src = sd[k]
                 shp = self.key_map[k][1]
-                if k == "lm.model.embed_tokens.weight" and src.shape[0] != shp[0]:
+                if k == self._embed_key and src.shape[0] != shp[0]:
                     if src.shape[0] > shp[0]:
                         src = src[:shp[0]]
                     else:
@@ -417,14 +507,17 @@ class UnitLM(TokenLM):
         if not c.get("tie_word_embeddings", True):
             raise ValueError("the engine supports tied embeddings only; this text LM has an untied lm_head")
         want = base_config_from_hf(c)
-        for k in ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "intermediate_size"):
+        if want.get("model_type") != self.config.base_config.get("model_type"):
+            raise ValueError(f"text LM model_type {c.get('model_type')!r} does not match the model's")
+        for k in ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "intermediate_size",
+                  "max_position_embeddings"):
             if want.get(k) != self.config.base_config.get(k):
                 raise ValueError(f"text LM {k}={want.get(k)} != model {k}={self.config.base_config.get(k)}")
         self.load_state_dict(read_hf_weights(path), strict=True)
         return self
 
     def get_input_embeddings(self):
-        return self._view(self.flat_params, "lm.model.embed_tokens.weight")
+        return self._view(self.flat_params, self._embed_key)
 
     def get_output_embeddings(self):
         return self.get_input_embeddings()  # tied
@@ -440,6 +533,18 @@ class UnitLM(TokenLM):
         return self
 
     # ---- forward / backward ---------------------------------------------------------------------
+    def _check_positions(self, T: int, position_ids: Optional[torch.Tensor] = None):
+        """OPT's learned positions: the engine clamps indices to its table (a memory guard), the range check is here - HF
+        fails where a clamped row would silently give wrong outputs. Device position_ids are read back (OPT only)."""
+        if not self.config.is_opt:
+            return
+        npos = int(self.config.base_config["max_position_embeddings"])
+        if position_ids is None:
+            if T > npos:
+                raise ValueError(f"sequence length {T} exceeds OPT's max_position_embeddings {npos}")
+        elif position_ids.numel() and (int(position_ids.min()) < 0 or int(position_ids.max()) >= npos):
+            raise ValueError(f"position_ids outside [0, {npos}) (OPT's max_position_embeddings)")
+
     def _segments(self, position_ids: torch.Tensor):
         """Packed [1, sum T] batches (DataCollatorWithFlattening): per-token sequence bounds from
         position_ids == 0 restarts."""
@@ -472,6 +577,7 @@ class UnitLM(TokenLM):
             # would silently lose its segment bounds (the engine takes segments from a [1, sum T] row only)
             if not bool((position_ids == torch.arange(T, dtype=position_ids.dtype)[None]).all()):
                 raise ValueError("position_ids with batch size > 1 must be plain aranges; packed batches are [1, sum T]")
+        self._check_positions(T, position_ids)
         dev = self.device
         nb = not input_ids.is_cuda and input_ids.is_pinned()  # pinned host batches (the trainer's prefetch thread): async H2D
         ids = input_ids.to(dev, torch.int64, non_blocking=nb)
@@ -531,6 +637,7 @@ class UnitLM(TokenLM):
         """unit_lm.py:184-194 + calc_nll (calculation_utils.py:5-29): pad -> -100, per-sequence
         sum (or mean) of target log-probs."""
         B, T = tokens.shape
+        self._check_positions(T)
         ids = tokens.to(self.device, torch.int64).contiguous()
         lab = ids.clone()
         lab[lab == self.config.pad_token_id] = -100
@@ -557,6 +664,7 @@ class UnitLM(TokenLM):
         `chosen_logps` / `rejected_logps`). Leaves the engine ready for `scale_loss_rows` + `backward`:
         d(-logp_b)/dlogits is stored unscaled (num_items = 1)."""
         B, T = input_ids.shape
+        self._check_positions(T)
         ids = input_ids.to(self.device, torch.int64).contiguous()
         lab = labels.to(self.device, torch.int64).contiguous()
         self._ensure_workspace(B * T)
@@ -588,6 +696,8 @@ class UnitLM(TokenLM):
         Logits are fp32; bad words get -inf, then temperature, top_k and top_p (sampling only). Finished rows are padded
         with pad_token_id; generation stops when every row has emitted eos_token_id. Explicit arguments override
         `generation_config`. Returns [B, T_in + n_new] int64: the prompt as passed, padding included, then the new tokens."""
+        if self.config.is_opt:
+            raise ValueError("generate is not implemented for OPT models (the engine's KV-cached decode covers Qwen2 only)")
         gc = generation_config
 
         def pick(v, name, default):
@@ -696,9 +806,9 @@ class UnitLM(TokenLM):
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, **kwargs) -> "UnitLM":
         """Loads a checkpoint directory written by this engine, by the reference's `UnitLM.save_pretrained`
-        (unit_lm.py:200-212: `config.json` with a serialised Qwen2Config under `base_config`, weights under `lm.model.*`)
-        or - as a convenience for converted text LMs - a raw HuggingFace Qwen2 directory (`model.*` keys; pass
-        vocab_size= to resize). Every parameter must be present in the file: a mismatching layout raises instead of
+        (unit_lm.py:200-212: `config.json` with a serialised Qwen2Config or OPTConfig under `base_config`, weights under
+        `lm.model.*`) or - as a convenience for converted text LMs - a raw HuggingFace Qwen2 or OPT directory (`model.*`
+        keys, or an OPTModel's bare `decoder.*`; pass vocab_size= to resize). Every parameter must be present in the file: a mismatching layout raises instead of
         leaving the model at its random initialisation."""
         path = pretrained_model_name_or_path
         with open(os.path.join(path, "config.json")) as f:
@@ -707,11 +817,12 @@ class UnitLM(TokenLM):
         if "base_config" in c:
             base = c["base_config"]
             name = c.get("base_model_name", "local")
-        elif c.get("model_type") == "qwen2":
+        elif c.get("model_type") == "qwen2" or (c.get("model_type") == "opt" and all(
+                k in c for k in ("num_hidden_layers", "hidden_size", "num_attention_heads", "ffn_dim", "max_position_embeddings"))):
             base, name = c, path
         else:
-            raise ValueError(f"{path}/config.json is neither a UnitLM config (no `base_config`) nor a Qwen2 config "
-                             f"(model_type={c.get('model_type')!r})")
+            raise ValueError(f"{path}/config.json is neither a UnitLM config (no `base_config`) nor a complete Qwen2 or OPT "
+                             f"config (model_type={c.get('model_type')!r})")
         if not (isinstance(name, str) and (name in KNOWN_BASE_CONFIGS or os.path.isdir(name))):
             name = "local"  # e.g. a hub id or a path of the machine that wrote the checkpoint: the dims are in base_config
         cfg = UnitLMConfig(base_model_name=name, base_config=base,
