@@ -362,6 +362,22 @@ size_t slam_op_attn_bwd_workspace(int M, int nH, int head_dim);
 int slam_op_attn_bwd(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* ws,
                      const int32_t* seg_start, const int32_t* seg_end, int M, int nH, int nKV, int head_dim,
                      slam_stream_t s);
+/* the backward as slam_backward calls it: dq / dk are stored rotated back (transpose RoPE) through fp32 cos / sin tables built
+ * from position_ids (NULL: m % T) and theta into table_ws (2 * M * (head_dim / 2) floats, on top of `ws`, which is sized by
+ * slam_op_attn_bwd_workspace as for slam_op_attn_bwd); the V columns are those of slam_op_attn_bwd. */
+int slam_op_attn_bwd_rope(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* ws,
+                          const int32_t* seg_start, const int32_t* seg_end, const int64_t* position_ids, int T, float theta,
+                          int M, int nH, int nKV, int head_dim, float* table_ws, slam_stream_t s);
+/* the fused QKV projection of the head_dim-64 models: Y[M][N] = rope(X[M][K] W[N][K]^T + bias) on the first rope_heads
+ * 64-column heads, the first q_heads of them also times 64^-0.5 * log2(e), the other columns bias only. The four tables
+ * (cos, sin and their pre-scaled copies) are built into table_ws (4 * M * 32 floats) from position_ids (NULL: m % T).
+ * SLAM_EINVAL for K % 64 or N % 128: slam_forward takes the unfused path (gemm_nt + rope) there. */
+int slam_op_gemm_nt_rope(const void* X, const void* W, void* Y, const void* bias /* nullable */, const int64_t* position_ids,
+                         float theta, int q_heads, int rope_heads, int M, int T, int N, int K, float* table_ws, slam_stream_t s);
+/* out[N] (+)= column sums of the bf16 window X[M][0..N) with row stride ld, the way slam_backward forms a bias gradient:
+ * per-row-block partial rows in ws (slam_op_colsum_workspace bytes), added in a fixed order. N and ld multiples of 8. */
+size_t slam_op_colsum_workspace(int M, int N);
+int slam_op_colsum(const void* X, int ld, int M, int N, float* out, int accumulate, float* ws, slam_stream_t s);
 int slam_op_cross_entropy(const void* logits /* bf16 [B*T][Vp] */, const int64_t* labels, double num_items,
                           void* dlogits, float* row_loss, float* scratch2 /* {denom, loss} */, int B, int T,
                           int Vp /* padded row length: 512, or a multiple of 8 beyond */, int V, slam_stream_t s);

@@ -934,7 +934,7 @@ int attn_plan(const int* seg_start, const int* seg_end, int M, int head_dim, Att
   tune = clamp_tune(tune, head_dim);
   const int qt = 64 * tune.jq, kt = 64 * tune.kw;
   const int total = (M + 127) / 128 + (M + qt - 1) / qt + NCH_MAX * ((M + kt - 1) / kt);
-  if ((size_t)total * sizeof(int) > 48 * 1024) return -1;  // M beyond ~260k tokens per micro-batch: the work list no longer fits one block's LDS
+  if ((size_t)total * sizeof(int) > 48 * 1024) return -1;  // M beyond ~143k tokens per micro-batch (11 ints per 128 rows, 12,288 ints): the work list no longer fits one block's LDS
   attn_plan_kernel<<<1, 1024, (size_t)total * sizeof(int), st>>>(seg_start, seg_end, M, qt, kt, tune.nch, plan);
   return (int)hipGetLastError();
 }

@@ -1879,6 +1879,53 @@ int slam_op_attn_bwd(const void* qkv, const void* o, const void* d_o, const floa
   return attn_bwd((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse2, ndsum, nlse, (bf16_t*)dqkv, part, seg_start,
                   seg_end, plan, tune, nullptr, nullptr, M, nH, nKV, head_dim, (hipStream_t)s);
 }
+// the backward as slam_backward runs it: dq / dk leave rotated back through the cos / sin tables of the rows' positions
+int slam_op_attn_bwd_rope(const void* qkv, const void* o, const void* d_o, const float* lse2, void* dqkv, float* ws,
+                          const int32_t* seg_start, const int32_t* seg_end, const int64_t* position_ids, int T, float theta,
+                          int M, int nH, int nKV, int head_dim, float* table_ws, slam_stream_t s) {
+  if (!qkv || !o || !d_o || !lse2 || !dqkv || !ws || !seg_start || !seg_end || !table_ws) return SLAM_EINVAL;
+  if (M <= 0 || nH <= 0 || nKV <= 0 || nH % nKV || (head_dim != 64 && head_dim != 128)) return SLAM_EINVAL;
+  if (!position_ids && T <= 0) return SLAM_EINVAL;
+  float* cs = table_ws;
+  float* sn = table_ws + (size_t)M * (head_dim / 2);
+  int r = rope_table(position_ids, M, T, head_dim, theta, cs, sn, nullptr, nullptr, 1.f, (hipStream_t)s);
+  if (r) return r;
+  float* ndsum = ws;
+  float* nlse = ws + (size_t)M * nH;
+  float* part = ws + (size_t)2 * M * nH;
+  int* plan = reinterpret_cast<int*>(part + attn_bwd_workspace_bytes(M, nH, head_dim) / sizeof(float));
+  const AttnTune tune = attn_default_tune();
+  r = attn_plan(seg_start, seg_end, M, head_dim, tune, plan, (hipStream_t)s);
+  if (r) return r;
+  return attn_bwd((const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse2, ndsum, nlse, (bf16_t*)dqkv, part, seg_start,
+                  seg_end, plan, tune, cs, sn, M, nH, nKV, head_dim, (hipStream_t)s);
+}
+// the QKV projection of the head_dim-64 models: bias + rotate-half RoPE + the query heads' pre-scale in the GEMM epilogue
+int slam_op_gemm_nt_rope(const void* X, const void* W, void* Y, const void* bias, const int64_t* position_ids, float theta,
+                         int q_heads, int rope_heads, int M, int T, int N, int K, float* table_ws, slam_stream_t s) {
+  if (!X || !W || !Y || !table_ws || M <= 0 || N <= 0 || K <= 0) return SLAM_EINVAL;
+  if ((K % 64) || (N % 128)) return SLAM_EINVAL;  // the shapes slam_forward routes to gemm_nt + rope_apply
+  if (q_heads < 0 || rope_heads < q_heads || (size_t)rope_heads * 64 > (size_t)N) return SLAM_EINVAL;
+  if (!position_ids && T <= 0) return SLAM_EINVAL;
+  const size_t n = (size_t)M * 32;
+  float *cs = table_ws, *sn = table_ws + n, *csq = table_ws + 2 * n, *snq = table_ws + 3 * n;
+  int r = rope_table(position_ids, M, T, 64, theta, cs, sn, csq, snq, 1.44269504088896340736f / sqrtf(64.f), (hipStream_t)s);
+  if (r) return r;
+  return gemm_nt_rope((const bf16_t*)X, (const bf16_t*)W, (bf16_t*)Y, (const bf16_t*)bias, cs, sn, csq, snq, q_heads, rope_heads,
+                      M, N, K, (hipStream_t)s);
+}
+// a bias gradient as slam_backward forms it: partial rows per row block, then the fixed-order finish
+size_t slam_op_colsum_workspace(int M, int N) {
+  if (M <= 0 || N <= 0) return 0;
+  return (size_t)colsum_blocks(M) * N * sizeof(float);
+}
+int slam_op_colsum(const void* X, int ld, int M, int N, float* out, int accumulate, float* ws, slam_stream_t s) {
+  if (!X || !out || !ws || M <= 0 || N <= 0 || ld < N) return SLAM_EINVAL;
+  if ((N % 8) || (ld % 8)) return SLAM_EINVAL;  // the kernel reads 16-byte chunks
+  int r = colsum_bf16((const bf16_t*)X, ld, M, N, nullptr, 1, ws, (hipStream_t)s);
+  if (r) return r;
+  return colsum_finish_many(ws, 0, colsum_blocks(M), N, out, 0, 1, accumulate != 0, (hipStream_t)s);
+}
 int slam_op_cross_entropy(const void* logits, const int64_t* labels, double num_items, void* dlogits, float* row_loss,
                           float* scratch2, int B, int T, int Vp, int V, slam_stream_t s) {
   return cross_entropy((const bf16_t*)logits, labels, num_items, (bf16_t*)dlogits, row_loss, scratch2, scratch2 + 1, B,

@@ -136,6 +136,11 @@ def load_library(path: Optional[str] = None):
         "slam_op_attn_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_attn_bwd_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
         "slam_op_attn_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_attn_bwd_rope": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, f32, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            vp, vp]),
+        "slam_op_gemm_nt_rope": (C.c_int, [vp, vp, vp, vp, vp, f32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "slam_op_colsum_workspace": (sz, [C.c_int, C.c_int]),
+        "slam_op_colsum": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
         "slam_op_cross_entropy": (C.c_int, [vp, vp, f64, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_embed_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_embed_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
