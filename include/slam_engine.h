@@ -78,6 +78,16 @@ int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out); /* UnitLM._
  * Positions are position_ids, else 0 .. T-1 per row; both table indices are clamped to the tables (a memory guard: callers
  * check their ranges). KV-cached generation (slam_prefill / slam_decode_step) is not implemented for OPT: SLAM_EINVAL. */
 int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, SlamEngine** out);
+/* The same with model flags (slam_engine_create / slam_engine_create_arch mean flags = 0). Arch 0 takes hidden <= 4096
+ * (rows above 2048 run the two-waves-per-row RMSNorm kernels), arch 1 hidden <= 2048.
+ * SLAM_MODEL_UNTIED_HEAD (arch 0 only; Qwen2.5-7B): the LM head is a tensor of its own, "lm_head" [Vp][H], laid out AFTER
+ * "norm" so that every other tensor keeps the offset it has in the tied layout. Its pad rows [vocab, Vp) are zero and stay
+ * zero, as the embedding's do. Forward, prefill and decode read the head GEMM's weight there; backward writes
+ * d lm_head = dlogits^T hf as that tensor's final value, and the embedding gradient is the gather side alone (rows of ids
+ * absent from the batch, and the pad_token_id row, are exactly zero). Unknown flag bits, or the untied flag with arch 1:
+ * SLAM_EINVAL. */
+#define SLAM_MODEL_UNTIED_HEAD 1
+int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, int32_t flags, SlamEngine** out);
 void slam_engine_destroy(SlamEngine* h);
 const char* slam_last_error(SlamEngine* h);
 const char* slam_version(void);

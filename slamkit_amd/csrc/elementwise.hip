@@ -204,6 +204,165 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
   }
 }
 
+// Wide rows (2048 < hidden <= 4096): a row is split over the two waves of a PAIR, chunk c = (2 i + half) * 64 + lane, so each
+// wave keeps at most 4 chunks in registers - the per-wave register budget of the narrow <3> / <4> instantiations - and the
+// row statistic is the sum of the two waves' partials, exchanged through LDS and always added as (half 0) + (half 1).
+// A block is two pairs (two rows at a time).
+constexpr int WIDE_LIMIT = 8;  // chunks of 8 per lane PAIR -> hidden <= 4096
+
+template <int MAXC>
+__global__ __launch_bounds__(256) void rmsnorm_fwd_wide_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                               bf16_t* __restrict__ y, float* __restrict__ rstd, int M, int H,
+                                                               float eps) {
+  __shared__ float part[2][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int pair = wave >> 1, half = wave & 1;
+  const int row = blockIdx.x * 2 + pair;
+  const bool live = row < M;
+  const int nch = H >> 3;
+  const uint4* xr = reinterpret_cast<const uint4*>(x + (size_t)(live ? row : 0) * H);
+  uint4 v[MAXC];
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    int c = (2 * i + half) * 64 + lane;
+    if (live && c < nch) {
+      v[i] = xr[c];
+      float f[8];
+      unpack_bf16x8(v[i], f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
+    }
+  }
+  ss = wave_sum(ss);
+  if (lane == 0) part[pair][half] = ss;
+  __syncthreads();
+  if (!live) return;
+  const float r = rsqrtf((part[pair][0] + part[pair][1]) / (float)H + eps);
+  if (lane == 0 && half == 0 && rstd) rstd[row] = r;
+  uint4* yr = reinterpret_cast<uint4*>(y + (size_t)row * H);
+  const uint4* wr = reinterpret_cast<const uint4*>(w);
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    int c = (2 * i + half) * 64 + lane;
+    if (c < nch) {
+      float f[8], g[8];
+      unpack_bf16x8(v[i], f);
+      unpack_bf16x8(wr[c], g);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = f[j] * r * g[j];
+      yr[c] = pack_bf16x8(f);
+    }
+  }
+}
+
+// Backward for wide rows: pair p of block b walks rows 2 b + p, + 2 gridDim.x, ...; every block runs the same number of
+// iterations (a pair past the end idles) because the halves of a row meet at a block barrier once per row. The dot partials
+// alternate between two LDS slots, so one barrier per row is enough. Each wave accumulates dw for its own chunks; the two
+// pairs are added through LDS at the end (pair 0 + pair 1): one row of dw_part per block, as in the narrow kernel.
+template <int MAXC>
+__global__ __launch_bounds__(256) void rmsnorm_bwd_wide_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                               const bf16_t* __restrict__ w, const float* __restrict__ rstd,
+                                                               const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
+                                                               float* __restrict__ dw_part, int M, int H) {
+  __shared__ float red[2][MAXC * 2 * 64 * 8];
+  __shared__ float dpart[2][2][2];  // [parity][pair][half]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int pair = wave >> 1, half = wave & 1;
+  const int nch = H >> 3;
+  float dwa[MAXC][8], wv[MAXC][8];
+  const uint4* wr = reinterpret_cast<const uint4*>(w);
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { dwa[i][j] = 0.f; wv[i][j] = 0.f; }
+    int c = (2 * i + half) * 64 + lane;
+    if (c < nch) unpack_bf16x8(wr[c], wv[i]);
+  }
+  auto load_row = [&](int row, uint4* rx, uint4* rdy, uint4* rdr) {
+    const uint4* xr = reinterpret_cast<const uint4*>(x + (size_t)row * H);
+    const uint4* dyr = reinterpret_cast<const uint4*>(dy + (size_t)row * H);
+    const uint4* drr = dres ? reinterpret_cast<const uint4*>(dres + (size_t)row * H) : nullptr;
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      int c = (2 * i + half) * 64 + lane;
+      if (c < nch) {
+        rx[i] = xr[c];
+        rdy[i] = dyr[c];
+        if (drr) rdr[i] = drr[c];
+      }
+    }
+  };
+  const int rstep = gridDim.x * 2;
+  const int first = blockIdx.x * 2;  // pair 0's first row: < M for every launched block
+  const int iters = (M - first + rstep - 1) / rstep;
+  int row = first + pair;
+  uint4 cx[MAXC], cdy[MAXC], cdr[MAXC];
+  float cr = 0.f;
+  if (row < M) { load_row(row, cx, cdy, cdr); cr = rstd[row]; }
+  for (int it = 0; it < iters; ++it, row += rstep) {
+    uint4 nx[MAXC], ndy[MAXC], ndr[MAXC];
+    float nr = 0.f;
+    const int nrow = row + rstep;
+    const bool live = row < M;
+    if (nrow < M) { load_row(nrow, nx, ndy, ndr); nr = rstd[nrow]; }
+    const float r = cr;
+    float xh[MAXC][8], gy[MAXC][8];
+    float dot = 0.f;
+    if (live) {
+#pragma unroll
+      for (int i = 0; i < MAXC; ++i) {
+        int c = (2 * i + half) * 64 + lane;
+        if (c < nch) {
+          float fx[8], fd[8];
+          unpack_bf16x8(cx[i], fx);
+          unpack_bf16x8(cdy[i], fd);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            xh[i][j] = fx[j] * r;
+            gy[i][j] = fd[j] * wv[i][j];
+            dot += gy[i][j] * xh[i][j];
+            dwa[i][j] += fd[j] * xh[i][j];
+          }
+        }
+      }
+    }
+    dot = wave_sum(dot);
+    if (lane == 0) dpart[it & 1][pair][half] = dot;
+    __syncthreads();
+    if (live) {
+      dot = (dpart[it & 1][pair][0] + dpart[it & 1][pair][1]) / (float)H;
+      uint4* dxr = reinterpret_cast<uint4*>(dx + (size_t)row * H);
+#pragma unroll
+      for (int i = 0; i < MAXC; ++i) {
+        int c = (2 * i + half) * 64 + lane;
+        if (c < nch) {
+          float o[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = r * (gy[i][j] - xh[i][j] * dot);
+          if (dres) {
+            float a[8];
+            unpack_bf16x8(cdr[i], a);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] += a[j];
+          }
+          dxr[c] = pack_bf16x8(o);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) { cx[i] = nx[i]; cdy[i] = ndy[i]; cdr[i] = ndr[i]; }
+    cr = nr;
+  }
+  // the two pairs' dw partials, then one row of dw_part per block
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[pair][((2 * i + half) * 64 + lane) * 8 + j] = dwa[i][j];
+  __syncthreads();
+  for (int e = threadIdx.x; e < H; e += 256) dw_part[(size_t)blockIdx.x * H + e] = red[0][e] + red[1][e];
+}
+
 // column sums of a bf16 matrix (bias gradient): part[blockIdx.y][N] fp32. Block = 16 column chunks (8 columns
 // each) x 16 row lanes; a row lane walks rows lane, lane + 16 gridDim.y, ...; the 16 row lanes are combined in
 // LDS in a fixed order. Algorithmic traffic: 2 B/element read.
@@ -1132,7 +1291,12 @@ namespace slam {
 #define LAUNCH_RET() return (int)hipGetLastError()
 
 int rmsnorm_fwd(const bf16_t* x, const bf16_t* w, bf16_t* y, float* rstd, int M, int H, float eps, hipStream_t st) {
-  if ((H & 7) || H > MAXC_LIMIT * 512) return -1;
+  if ((H & 7) || H > WIDE_LIMIT * 512) return -1;
+  if (H > MAXC_LIMIT * 512) {  // wide rows: two waves per row
+    if (H <= 3072) rmsnorm_fwd_wide_kernel<3><<<(M + 1) / 2, 256, 0, st>>>(x, w, y, rstd, M, H, eps);
+    else rmsnorm_fwd_wide_kernel<4><<<(M + 1) / 2, 256, 0, st>>>(x, w, y, rstd, M, H, eps);
+    LAUNCH_RET();
+  }
   switch ((H / 8 + 63) / 64) {
     case 1: rmsnorm_fwd_kernel<1><<<(M + 3) / 4, 256, 0, st>>>(x, w, y, rstd, M, H, eps); break;
     case 2: rmsnorm_fwd_kernel<2><<<(M + 3) / 4, 256, 0, st>>>(x, w, y, rstd, M, H, eps); break;
@@ -1159,8 +1323,12 @@ int rmsnorm_bwd_blocks(int M) { int b = (M + 15) / 16; return b > 512 ? 512 : (b
 // sink (nullable, with dw): how the final values of dw are kept (GradSink, kernels.h)
 int rmsnorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* rstd, const bf16_t* dres,
                 bf16_t* dx, float* dw, int accumulate, float* part, int M, int H, hipStream_t st, bf16_t* dw_img, GradSink* sink) {
-  if ((H & 7) || H > MAXC_LIMIT * 512) return -1;
+  if ((H & 7) || H > WIDE_LIMIT * 512) return -1;
   int nb = rmsnorm_bwd_blocks(M);
+  if (H > MAXC_LIMIT * 512) {  // wide rows: two waves per row, the same grid and the same [nb][H] partial slab
+    if (H <= 3072) rmsnorm_bwd_wide_kernel<3><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, part, M, H);
+    else rmsnorm_bwd_wide_kernel<4><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, part, M, H);
+  } else
   switch ((H / 8 + 63) / 64) {
     case 1: rmsnorm_bwd_kernel<1><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, part, M, H); break;
     case 2: rmsnorm_bwd_kernel<2><<<nb, 256, 0, st>>>(dy, x, w, rstd, dres, dx, part, M, H); break;

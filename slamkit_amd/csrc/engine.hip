@@ -78,6 +78,8 @@ struct SlamEngine {
   int64_t n_params;
   int64_t off_embed, off_norm, layer_stride = 0;
   int64_t off_pos = -1, off_norm_b = -1;  // OPT
+  bool untied = false;   // SLAM_MODEL_UNTIED_HEAD: the head GEMM's weight is the tensor "lm_head" behind the final norm
+  int64_t off_head = 0;  // the head's weight: off_embed when tied
   std::vector<LayerOff> lo;
   std::vector<SlamTensorInfo> tensors;
   std::vector<int> layer0;  // indices into `tensors` of layer 0's tensors, in layout order
@@ -117,7 +119,7 @@ struct SlamEngine {
   int overlap_adamw = 0;
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr;
-  std::vector<hipEvent_t> ev_chunk;  // [0] embedding, [1 + l] layer l, [L + 1] final norm
+  std::vector<hipEvent_t> ev_chunk;  // [0] embedding, [1 + l] layer l, [L + 1] final norm (+ an untied lm_head and its transposed image)
   bool opt_pending = false;
 
   // "bwd_wgrad_stream": the weight-gradient GEMMs of backward run on a second engine-owned stream. They are off the
@@ -330,6 +332,7 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
                        gemm_tn_sumsq_slots((int)(2 * I), (int)H) + gemm_tn_sumsq_slots((int)H, (int)I) +
                        2 * ((H + 15) / 16) + ((size_t)e->QKV + 15) / 16;
     size_t tail = (H + 15) / 16;
+    if (e->untied) tail += gemm_tn_sumsq_slots(e->vpad, (int)H);  // the head's gradient is a final store of its own
     if (opt) {  // + fc1 at N = I, the LayerNorm biases, bo, b1, b2, the final norm's bias and the position table's conversion
       per_layer += gemm_tn_sumsq_slots((int)I, (int)H) + 2 * ((H + 15) / 16) + 2 * ((H + 15) / 16) + (I + 15) / 16;
       tail += (H + 15) / 16 + (size_t)f32_to_bf16_sumsq_slots((size_t)e->npos * H) + (size_t)e->npos * H / grad_chunk_elems() + 1;
@@ -512,7 +515,8 @@ int wait_params(SlamEngine* h, int64_t lo, int64_t hi, hipStream_t st) {
 }
 int join_params(SlamEngine* h, hipStream_t st) { return h->pwaits.empty() ? 0 : wait_params(h, 0, h->n_params, st); }
 
-// AdamW over the parameters [chunk c of the model]: c = 0 embedding, 1 + l = decoder layer l, L + 1 = final norm; c < 0 = all.
+// AdamW over the parameters [chunk c of the model]: c = 0 embedding, 1 + l = decoder layer l, L + 1 = final norm and, with an
+// untied head, lm_head (the tensors behind the layers; forward joins the last chunk before the head GEMM); c < 0 = all.
 // With transposed weight images bound, every matrix goes through the tile kernel that writes its transposed image in the
 // same pass (no separate transpose launch), the vectors between them through the strided kernel.
 // mode 0: fp32 master + fp32 moments, 1: fp32 master + bf16 moments, 2: bf16 parameters + bf16 moments.
@@ -552,6 +556,7 @@ int adamw_model(SlamEngine* h, int mode, float* master, void* m, void* v, const 
   if (chunk < 0 || chunk == L + 1) {
     r = vec(h->off_norm, (size_t)H, 1);
     if (!r && h->arch == 1) r = vec(h->off_norm_b, (size_t)H, 1);
+    if (!r && h->untied) r = mat(h->off_head, h->vpad, H, 1);
   }
   return r;
 }
@@ -642,11 +647,18 @@ const char* slam_version(void) { return "slam-engine gfx950 r6"; }
 int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out) { return slam_engine_create_arch(desc, 0, 0, out); }
 
 int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, SlamEngine** out) {
+  return slam_engine_create_ex(desc, arch, n_positions, 0, out);
+}
+
+int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, int32_t flags, SlamEngine** out) {
   if (!desc || !out) return SLAM_EINVAL;
   const SlamModelDesc& d = *desc;
   if (arch != 0 && arch != 1) return SLAM_EINVAL;
+  if (flags & ~SLAM_MODEL_UNTIED_HEAD) return SLAM_EINVAL;
+  const bool untied = (flags & SLAM_MODEL_UNTIED_HEAD) != 0;
+  if (untied && arch != 0) return SLAM_EINVAL;
   if ((d.head_dim != 64 && d.head_dim != 128) || d.n_heads <= 0 || d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return SLAM_EINVAL;
-  if (d.hidden % 8 || d.hidden > 2048 || d.vocab <= 0) return SLAM_EINVAL;
+  if (d.hidden % 8 || d.hidden > (arch == 0 ? 4096 : 2048) || d.vocab <= 0) return SLAM_EINVAL;  // the row-norm kernels' limits
   if (d.n_layers <= 0) return SLAM_EINVAL;
   if (arch == 0 && d.intermediate % GU_BLK) return SLAM_EINVAL;
   // OPT: multi-head attention (kv = q heads), head_dim 64, a position table of n_positions + 2 rows
@@ -655,6 +667,7 @@ int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_p
   SlamEngine* e = new SlamEngine();
   e->d = d;
   e->arch = arch;
+  e->untied = untied;
   e->npos = arch == 1 ? n_positions + 2 : 0;
   e->QKV = (d.n_heads + 2 * d.n_kv_heads) * d.head_dim;
   e->vpad = d.vocab <= VPAD_SMALL ? VPAD_SMALL : ((d.vocab + 255) / 256) * 256;  // 256: the LM-head GEMM can take the 256 x 256 kernel
@@ -703,6 +716,11 @@ int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_p
     e->off_norm_b = off;
     add_tensor(e, "norm_b", off, d.hidden, 1);
   }
+  e->off_head = e->off_embed;
+  if (untied) {
+    e->off_head = off;
+    add_tensor(e, "lm_head", off, e->vpad, d.hidden);
+  }
   e->n_params = off;
   *out = e;
   return SLAM_OK;
@@ -739,6 +757,7 @@ int slam_refresh_transposed(SlamEngine* h, slam_stream_t stream) {
   bf16_t* Pt = h->params_t;
   const int H = d.hidden;
   CK(transpose_bf16(P + h->off_embed, Pt + h->off_embed, h->vpad, H, 1, 0, st));
+  if (h->untied) CK(transpose_bf16(P + h->off_head, Pt + h->off_head, h->vpad, H, 1, 0, st));
   // every layer has the same shapes at a constant stride: one launch per weight kind (layer 0's matrices in layout order),
   // grid.z = layers
   const int L = d.n_layers;
@@ -766,6 +785,7 @@ size_t slam_workspace_bytes(SlamEngine* h, int64_t max_tokens) {
   tmp.npos = h->npos;
   tmp.QKV = h->QKV;
   tmp.vpad = h->vpad;
+  tmp.untied = h->untied;
   tmp.n_params = h->n_params;
   return carve(&tmp, nullptr, max_tokens);
 }
@@ -844,7 +864,7 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
   if (h->arch == 1) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[L], P + h->off_norm, P + h->off_norm_b, h->hf, h->muf, h->rstdf, M, H, d.rms_eps, st));
   else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, M, H, d.rms_eps, st));
   const int VP = h->vpad;
-  TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_embed, h->logits, nullptr, nullptr, M, VP, H, st));
+  TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_head, h->logits, nullptr, nullptr, M, VP, H, st));
   h->have_loss = false;
   if (logits_out) CK(copy_cols(h->logits, VP, (bf16_t*)logits_out, d.vocab, M, d.vocab, st));
   if (labels) {
@@ -915,7 +935,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   // logits of each row's last prompt token only: gather, final norm, one fp32 head launch over B rows
   CK(gather_last_rows(h->hs[L], h->dx, lens, B, T, H, st));
   CK(rmsnorm_fwd(h->dx, P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
-  CK(decode_proj(h, h->hf, P + h->off_embed, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
+  CK(decode_proj(h, h->hf, P + h->off_head, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
   h->kv_B = B;
   h->kv_hi = T;
   h->kv_ready = true;
@@ -962,7 +982,7 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
     CK(decode_proj(h, a.act, P + o.wd, h->hs[l + 1], nullptr, nullptr, a.hmid, B, H, I, st));
   }
   CK(rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
-  CK(decode_proj(h, h->hf, P + h->off_embed, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
+  CK(decode_proj(h, h->hf, P + h->off_head, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
   CK(lens_inc(lens, B, st));
   h->kv_hi += 1;
   return SLAM_OK;
@@ -992,9 +1012,10 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
   };
   const int VP = h->vpad;
   if (grad_scale != 1.0f) CK(scale_bf16(h->dlogits, (size_t)M * VP, grad_scale, st));
-  // tied head: dE += dlogits^T hf ; dhf = dlogits E
-  // first micro-batch of an optimizer step: every gradient tensor is written exactly once below (the embedding
-  // twice: head first, gather side second), so it may be STORED instead of accumulated and the buffer needs no
+  // tied head: dE += dlogits^T hf ; dhf = dlogits E. Untied head: d lm_head = dlogits^T hf ; dhf = dlogits lm_head
+  // first micro-batch of an optimizer step: every gradient tensor is written exactly once below (the tied embedding
+  // twice: head first, gather side second; untied, lm_head once by the head and the embedding once by the gather side,
+  // which then stores - or zeroes the tensor before its scatter), so it may be STORED instead of accumulated and the buffer needs no
   // zeroing pass (4 B/param written by AdamW + 4 B/param re-read by the wgrad epilogues)
   const int acc = h->overwrite_next ? 0 : 1;
   h->overwrite_next = false;
@@ -1077,8 +1098,9 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
     return r;
   };
 
-  CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_embed, VP, H, nullptr, false));  // not final: the gather side adds to it below
-  TK(F_HEAD_DGRAD, st, dgrad(h->dlogits, h->off_embed, h->dx, VP, H));
+  if (h->untied) CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_head, VP, H, img(h->off_head)));  // the head's own tensor: final
+  else CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_embed, VP, H, nullptr, false));  // not final: the gather side adds to it below
+  TK(F_HEAD_DGRAD, st, dgrad(h->dlogits, h->off_head, h->dx, VP, H));
   bf16_t* dh = h->dh_a;  // grad wrt hs[l+1]
   const bool opt = h->arch == 1;
   if (opt) {  // final LayerNorm: dw | db slabs in part_ws, one finish launch per tensor
@@ -1233,10 +1255,14 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
       }
       return SLAM_OK;
     };
+    // tied: the head wrote (or added to) the tensor above, the gather side always adds. Untied: the gather side is the
+    // embedding gradient's only writer - a storing backward stores (one-hot GEMM) or zeroes first (scatter)
+    const int eacc = h->untied ? acc : 1;
     if (VP == VPAD_SMALL) {
       CK(onehot(h->last_ids, h->onehot, M, VP, d.vocab, d.pad_token_id, ws));
-      CK(take(gemm_tn(h->onehot, dh, G + h->off_embed, 1, M, VP, H, VP, H, h->gemm_ws, h->gemm_ws_bytes, ws, two ? 1 : 0, img(h->off_embed), sink())));
+      CK(take(gemm_tn(h->onehot, dh, G + h->off_embed, eacc, M, VP, H, VP, H, h->gemm_ws, h->gemm_ws_bytes, ws, two ? 1 : 0, img(h->off_embed), sink())));
     } else {
+      if (!eacc) CK((int)hipMemsetAsync(G + h->off_embed, 0, (size_t)VP * H * sizeof(float), ws));
       CK(embed_bwd(h->last_ids, dh, G + h->off_embed, M, H, VP, d.vocab, d.pad_token_id, h->embed_ws, ws));
       CK(finish_scattered(h->off_embed, (size_t)VP * H));
     }
@@ -1345,6 +1371,8 @@ static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, c
             const int64_t off = t.offset + (int64_t)(c - 1) * h->layer_stride;
             if (t.cols > 1) CK(transpose_bf16(P + off, Pt + off, (int)t.rows, (int)t.cols, 1, 0, h->side));
           }
+        } else if (h->untied) {
+          CK(transpose_bf16(P + h->off_head, Pt + h->off_head, h->vpad, H, 1, 0, h->side));
         }
       }
     }

@@ -16,6 +16,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "lib
 _lib = None
 
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
+MODEL_UNTIED_HEAD = 1  # SLAM_MODEL_UNTIED_HEAD
 
 
 class SlamModelDesc(C.Structure):
@@ -56,6 +57,7 @@ def load_library(path: Optional[str] = None):
     sig = {
         "slam_engine_create": (C.c_int, [C.POINTER(SlamModelDesc), C.POINTER(vp)]),
         "slam_engine_create_arch": (C.c_int, [C.POINTER(SlamModelDesc), i32, i32, C.POINTER(vp)]),
+        "slam_engine_create_ex": (C.c_int, [C.POINTER(SlamModelDesc), i32, i32, i32, C.POINTER(vp)]),
         "slam_engine_destroy": (None, [vp]),
         "slam_last_error": (C.c_char_p, [vp]),
         "slam_version": (C.c_char_p, []),
@@ -185,15 +187,16 @@ class TensorSpec:
 class Engine:
     """Thin owner of a SlamEngine handle plus the torch tensors it borrows."""
 
-    def __init__(self, desc: SlamModelDesc, arch: int = 0, n_positions: int = 0):
-        """arch 0 = Qwen2, 1 = OPT (n_positions = max_position_embeddings; slam_engine_create_arch)."""
+    def __init__(self, desc: SlamModelDesc, arch: int = 0, n_positions: int = 0, flags: int = 0):
+        """arch 0 = Qwen2, 1 = OPT (n_positions = max_position_embeddings); flags: MODEL_UNTIED_HEAD (slam_engine_create_ex)."""
         self.lib = load_library()
         self.desc = desc
         self.arch = arch
+        self.flags = flags
         h = C.c_void_p()
-        rc = self.lib.slam_engine_create_arch(C.byref(desc), arch, n_positions, C.byref(h))
+        rc = self.lib.slam_engine_create_ex(C.byref(desc), arch, n_positions, flags, C.byref(h))
         if rc != 0:
-            raise EngineError(f"slam_engine_create_arch failed ({rc}): unsupported model description")
+            raise EngineError(f"slam_engine_create_ex failed ({rc}): unsupported model description")
         self.h = h
         self.n_params = int(self.lib.slam_param_count(h))
         self.tensors: Dict[str, TensorSpec] = {}

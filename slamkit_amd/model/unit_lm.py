@@ -32,6 +32,14 @@ KNOWN_BASE_CONFIGS = {
     "Qwen/Qwen2.5-1.5B": dict(num_hidden_layers=28, hidden_size=1536, num_attention_heads=12, num_key_value_heads=2,
                               head_dim=128, intermediate_size=8960, rms_norm_eps=1e-6, rope_theta=1000000.0,
                               tie_word_embeddings=True, initializer_range=0.02),
+    # the rest of the Qwen2.5 family the reference's interleaved scaling work uses (docs/SIMS.md: up to SIMS-7B). 7B unties
+    # its head and is wider than 2048: the engine's "lm_head" tensor and its two-waves-per-row RMSNorm kernels
+    "Qwen/Qwen2.5-3B": dict(num_hidden_layers=36, hidden_size=2048, num_attention_heads=16, num_key_value_heads=2,
+                            head_dim=128, intermediate_size=11008, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                            tie_word_embeddings=True, initializer_range=0.02),
+    "Qwen/Qwen2.5-7B": dict(num_hidden_layers=28, hidden_size=3584, num_attention_heads=28, num_key_value_heads=4,
+                            head_dim=128, intermediate_size=18944, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                            tie_word_embeddings=False, initializer_range=0.02),
     # OPT: the reference's default body (config/model/default.yaml base_model_name) and the TWIST-1.3B body
     "facebook/opt-125m": dict(model_type="opt", num_hidden_layers=12, hidden_size=768, num_attention_heads=12, ffn_dim=3072,
                               max_position_embeddings=2048, init_std=0.02, tie_word_embeddings=True),
@@ -142,7 +150,7 @@ class UnitLMConfig:
 
     def __init__(self, base_model_name="Qwen/Qwen2.5-0.5B", base_config=None, vocab_size=502, twist_init=False,
                  use_cache=False, pad_token_id=0, bos_token_id=1, eos_token_id=1, torch_dtype="bfloat16",
-                 attn_implementation="flash_attention_2", max_tokens=8192, **kwargs):
+                 attn_implementation="flash_attention_2", max_tokens=8192, tie_word_embeddings=None, **kwargs):
         self.base_model_name = base_model_name
         local_dir = isinstance(base_model_name, str) and os.path.isfile(os.path.join(base_model_name, "config.json"))
         if base_config is None:
@@ -166,10 +174,13 @@ class UnitLMConfig:
         base_config.setdefault("rms_norm_eps", 1e-6)
         base_config.setdefault("rope_theta", 10000.0)
         base_config.setdefault("initializer_range", 0.02)
+        if tie_word_embeddings is not None:  # forwarded into the base config, as the reference's **kwargs are
+            base_config["tie_word_embeddings"] = bool(tie_word_embeddings)
         base_config.setdefault("tie_word_embeddings", True)
+        base_config["tie_word_embeddings"] = bool(base_config["tie_word_embeddings"])
         base_config.update(pad_token_id=pad_token_id, bos_token_id=bos_token_id, eos_token_id=eos_token_id)
-        if not base_config["tie_word_embeddings"]:
-            raise ValueError("the engine supports tied embeddings only (Slam / Qwen2.5-0.5B)")
+        if not base_config["tie_word_embeddings"] and base_config.get("model_type") == "opt":
+            raise ValueError("the engine supports tied embeddings only for OPT; this config unties lm_head")
         self.base_config = base_config
         self.vocab_size = vocab_size
         self.twist_init = twist_init
@@ -182,14 +193,14 @@ class UnitLMConfig:
         self.attn_implementation = attn_implementation
         self._attn_implementation = attn_implementation  # read at cli/train.py:43
         self.max_tokens = max_tokens
-        self.tie_word_embeddings = True
+        self.tie_word_embeddings = base_config["tie_word_embeddings"]
         self.extra = kwargs
 
     def to_dict(self):
         return dict(model_type="speech_language_model", engine="slamkit_amd", base_model_name=self.base_model_name,
                     base_config=self.base_config, vocab_size=self.vocab_size, twist_init=False, pad_token_id=self.pad_token_id,
                     bos_token_id=self.bos_token_id, eos_token_id=self.eos_token_id, torch_dtype=self.torch_dtype,
-                    max_tokens=self.max_tokens)
+                    max_tokens=self.max_tokens, tie_word_embeddings=self.tie_word_embeddings)
 
     @property
     def is_opt(self) -> bool:
@@ -200,6 +211,10 @@ class UnitLMConfig:
         if self.is_opt:
             return ARCH_OPT, int(self.base_config["max_position_embeddings"])
         return ARCH_QWEN2, 0
+
+    def engine_flags(self) -> int:
+        """flags of slam_engine_create_ex: the untied head is a tensor of its own."""
+        return 0 if self.tie_word_embeddings else E.MODEL_UNTIED_HEAD
 
     def engine_desc(self) -> E.SlamModelDesc:
         b = self.base_config
@@ -265,7 +280,7 @@ class UnitLM(TokenLM):
             raise RuntimeError("slamkit_amd.UnitLM needs a ROCm GPU (gfx950); there is no CPU fallback")
         self.config = config
         self.device = torch.device(device or f"cuda:{torch.cuda.current_device()}")
-        self.engine = E.Engine(config.engine_desc(), *config.engine_arch())
+        self.engine = E.Engine(config.engine_desc(), *config.engine_arch(), flags=config.engine_flags())
         n = self.engine.n_params
         with torch.cuda.device(self.device):
             self.flat_params = torch.zeros(n, dtype=torch.bfloat16, device=self.device)
@@ -326,6 +341,10 @@ class UnitLM(TokenLM):
             km[p + "input_layernorm.weight"] = (t[q + "ln1"].offset, (H,))
             km[p + "post_attention_layernorm.weight"] = (t[q + "ln2"].offset, (H,))
         km["lm.model.norm.weight"] = (t["norm"].offset, (H,))
+        self._head_key = None
+        if not self.config.tie_word_embeddings:  # HF's lm_head.weight under the reference's `lm.` prefix
+            self._head_key = "lm.lm_head.weight"
+            km[self._head_key] = (t["lm_head"].offset, (self.config.vocab_size, H))
         self.key_map = km
 
     def _build_key_map_opt(self):
@@ -334,6 +353,7 @@ class UnitLM(TokenLM):
         H, I, L = b["hidden_size"], b["intermediate_size"], b["num_hidden_layers"]
         km: Dict[str, Tuple[int, Tuple[int, ...]]] = {}
         d = "lm.model.decoder."
+        self._head_key = None
         self._embed_key = d + "embed_tokens.weight"
         km[d + "embed_tokens.weight"] = (t["embed"].offset, (self.config.vocab_size, H))
         km[d + "embed_positions.weight"] = (t["pos_embed"].offset, (t["pos_embed"].rows, H))
@@ -391,7 +411,8 @@ class UnitLM(TokenLM):
     @torch.no_grad()
     def init_weights(self, seed: int = 0):
         """HF `_init_weights`: N(0, initializer_range) matrices and embeddings, zero biases, unit
-        norms, zero padding_idx row (unit_lm.py:114-115 -> transformers PreTrainedModel)."""
+        norms, zero padding_idx row of the token table (an untied lm_head is a plain nn.Linear: no zeroed row)
+        (unit_lm.py:114-115 -> transformers PreTrainedModel)."""
         std = float(self.config.base_config["initializer_range"])
         g = torch.Generator(device=self.device).manual_seed(seed)
         self.engine.join()
@@ -472,15 +493,16 @@ class UnitLM(TokenLM):
 
     @torch.no_grad()
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        """Copies the tensors into the fp32 master and refreshes the bf16 images. The tied `lm_head.weight` is accepted and
-        ignored. The embedding follows `resize_token_embeddings` (unit_lm.py:102): a longer matrix is cut to the first
+        """Copies the tensors into the fp32 master and refreshes the bf16 images. A tied model accepts and ignores
+        `lm_head.weight`; an untied one requires it and resizes it exactly as the embedding (HF's resize_token_embeddings
+        resizes both). The embedding follows `resize_token_embeddings` (unit_lm.py:102): a longer matrix is cut to the first
         vocab_size rows; a shorter one fills the new rows with the mean of the old rows (transformers' mean-resizing
         draws them from N(mean, 1e-9 * cov): within 1e-5 of the mean). Returns (missing, unexpected); with `strict`
         either being non-empty raises."""
         self.engine.join()
         sd = self._canonical_keys(sd)
         missing = [k for k in self.key_map if k not in sd]
-        extra = [k for k in sd if k not in self.key_map and not k.endswith("lm_head.weight")]
+        extra = [k for k in sd if k not in self.key_map and not (self._head_key is None and k.endswith("lm_head.weight"))]
         if strict and (missing or extra):
             raise KeyError(f"state_dict mismatch: {len(missing)} missing (first: {missing[:4]}), "
                            f"{len(extra)} unexpected (first: {extra[:4]})")
@@ -488,7 +510,7 @@ class UnitLM(TokenLM):
             if k in sd:
                 src = sd[k]
                 shp = self.key_map[k][1]
-                if k == self._embed_key and src.shape[0] != shp[0]:
+                if k in (self._embed_key, self._head_key) and src.shape[0] != shp[0]:
                     if src.shape[0] > shp[0]:
                         src = src[:shp[0]]
                     else:
@@ -501,11 +523,13 @@ class UnitLM(TokenLM):
 
     def load_hf_text_lm(self, path: str):
         """TWIST initialisation (unit_lm.py:94-102): every weight of a local HuggingFace Qwen2 text LM, embedding rows
-        resized to vocab_size. The text LM must tie its head (an untied `lm_head` would be dropped silently)."""
+        resized to vocab_size (an untied text LM's `lm_head` likewise). The text LM must tie or untie its head as the
+        model does: a mismatch would drop an untied `lm_head` silently, or leave one at its random initialisation."""
         with open(os.path.join(path, "config.json")) as f:
             c = json.load(f)
-        if not c.get("tie_word_embeddings", True):
-            raise ValueError("the engine supports tied embeddings only; this text LM has an untied lm_head")
+        if bool(c.get("tie_word_embeddings", True)) != bool(self.config.tie_word_embeddings):
+            raise ValueError(f"text LM tie_word_embeddings={c.get('tie_word_embeddings', True)} does not match the model's "
+                             f"({self.config.tie_word_embeddings})")
         want = base_config_from_hf(c)
         if want.get("model_type") != self.config.base_config.get("model_type"):
             raise ValueError(f"text LM model_type {c.get('model_type')!r} does not match the model's")
@@ -520,6 +544,8 @@ class UnitLM(TokenLM):
         return self._view(self.flat_params, self._embed_key)
 
     def get_output_embeddings(self):
+        if self._head_key is not None:
+            return self._view(self.flat_params, self._head_key)
         return self.get_input_embeddings()  # tied
 
     def train(self, mode: bool = True):
