@@ -305,7 +305,24 @@ int slam_cast_params(SlamEngine* h, const float* master_f32, slam_stream_t strea
  * 1): slam_backward enqueues the weight-gradient GEMMs on an engine-owned second stream, ordered by events against the
  * dgrad chain on `stream`; `stream` is joined with it before slam_backward returns control of the gradient buffer (every
  * reported bucket range, and the end of the call). "overlap_adamw", "fuse_swiglu", "fuse_dswiglu", "gemm_256",
- * "gemm_256_dswiglu", "gemm_256_persist", "gemm_tn224", "gemm_tn_balanced", "gemm_group_rows" select kernels. */
+ * "gemm_256_dswiglu", "gemm_256_persist", "gemm_tn224", "gemm_tn_balanced", "gemm_group_rows" select kernels.
+ *
+ * "recompute" = 0 | 1 | 2 (default 0; anything else is SLAM_EINVAL, "out of range"): activation recomputation in backward -
+ * gradient checkpointing (the reference's `supports_gradient_checkpointing`, HF TrainingArguments.gradient_checkpointing).
+ * Results are bit-identical at every level: backward re-runs the forward's own launches on the forward's own inputs.
+ *   0  every layer keeps hmid, x1, x2, qkv, o, gu, act, rstd1, rstd2, lse (OPT: + mu1, mu2) from forward to backward.
+ *   1  selective: every layer keeps hmid, qkv, o, gu, the row statistics and lse; x1, x2 and act live in min(n_layers, 3)
+ *      shared slots (layer l uses slot l mod 3) and slam_backward rebuilds them before layer l's weight gradients read them:
+ *      x1 from the residual stream, x2 from hmid, act from gu (with "fuse_swiglu" the fused gate|up launch is re-run, since its
+ *      act comes from fp32 accumulators that gu no longer holds). OPT (arch 1) stores no fc1 pre-activation - its act is the
+ *      post-ReLU value and gu holds d(act) - so there level 1 shares x1 and x2 only and act stays per layer.
+ *   2  full: every layer keeps only its residual stream; all of the above live in the shared slots and slam_backward re-runs
+ *      layer l's forward launches (all but the down projection / fc2) from the residual stream right before the layer's backward,
+ *      on `stream`. slam_prefill then scatters each layer's K / V into the cache inside the layer loop.
+ * The workspace layout depends on the level (slam_workspace_bytes answers for the current one). CHANGING the level while a
+ * workspace is bound unbinds it: slam_forward, slam_prefill, slam_decode_step and slam_backward return SLAM_ESTATE until
+ * slam_bind_workspace is called again. Under "time_families" the re-run launches are recorded under the forward families'
+ * ids (norm_fwd, qkv_fwd, ...), inside the backward part of the record list; "time_gateup" does not time them. */
 int slam_set_option(SlamEngine* h, const char* key, int64_t value);
 
 /* ---- single-op entry points (parity tests call each kernel through the ABI) -------------------*/

@@ -34,6 +34,7 @@ namespace {
 
 constexpr int VPAD_SMALL = 512;  // vocabularies up to 512 (the speech-unit LMs) use the one-wave CE and one-hot wgrad paths
 constexpr int GU_BLK = 32;  // Wgu rows / gate|up columns come in blocks of 32 gate + 32 up
+constexpr int RC_SLOTS = 3;  // "recompute": shared activation slots (layer l uses slot l mod 3; DESIGN.md has the hazard table)
 
 // OPT (arch 1) keeps fc1 in `wgu` and fc2 in `wd`; ln1_b, bo, ln2_b, b1, b2 are OPT's alone
 struct LayerOff {
@@ -160,11 +161,16 @@ struct SlamEngine {
   size_t comm_ev_used = 0;
   bf16_t* last_grad_img = nullptr;      // the image the last slam_backward wrote (slam_allreduce_grads_async, bf16 exchange)
   std::vector<hipEvent_t> ev_w;  // per layer (+1 for the head / embedding): 4 main->side, 3 side->main
+  // "recompute" (see slam_set_option in the header): 0 every layer keeps its forward activations, 1 x1 / x2 / act live in
+  // min(L, 3) shared slots and are rebuilt in backward, 2 the whole LayerAct does and backward re-runs the layer's forward
+  int recompute = 0;
+  std::vector<hipEvent_t> ev_rc;  // per layer: "the weight-gradient stream is done with layer l" (orders the slot re-use)
 
   ~SlamEngine() {
     if (wside) { (void)hipStreamSynchronize(wside); (void)hipStreamDestroy(wside); }
     for (hipEvent_t e : fam_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_w) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_rc) (void)hipEventDestroy(e);
     if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
@@ -252,21 +258,26 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
   e->la.resize(L);
   for (size_t l = 0; l <= L; ++l) e->hs[l] = c.take<bf16_t>(M * H);
   const bool opt = e->arch == 1;
+  // "recompute": layer l shares the buffers named by the level with every layer l' = l (mod S); the first S layers carve them
+  const int rc = e->recompute;
+  const size_t S = rc ? (L < RC_SLOTS ? L : (size_t)RC_SLOTS) : L;
   for (size_t l = 0; l < L; ++l) {
     LayerAct& a = e->la[l];
-    a.hmid = c.take<bf16_t>(M * H);
-    a.x1 = c.take<bf16_t>(M * H);
-    a.x2 = c.take<bf16_t>(M * H);
-    a.qkv = c.take<bf16_t>(M * e->QKV);
-    a.o = c.take<bf16_t>(M * d.n_heads * d.head_dim);
-    a.gu = c.take<bf16_t>(M * (opt ? 1 : 2) * I);
-    a.act = c.take<bf16_t>(M * I);
-    a.rstd1 = c.take<float>(M);
-    a.rstd2 = c.take<float>(M);
-    a.lse = c.take<float>(M * d.n_heads);
+    const LayerAct* s = l < S ? nullptr : &e->la[l % S];  // the layer that carved this layer's slot
+    const bool all = s && rc == 2, xs = s && rc >= 1, as = s && (rc == 2 || (rc == 1 && !opt));
+    a.hmid = all ? s->hmid : c.take<bf16_t>(M * H);
+    a.x1 = xs ? s->x1 : c.take<bf16_t>(M * H);
+    a.x2 = xs ? s->x2 : c.take<bf16_t>(M * H);
+    a.qkv = all ? s->qkv : c.take<bf16_t>(M * e->QKV);
+    a.o = all ? s->o : c.take<bf16_t>(M * d.n_heads * d.head_dim);
+    a.gu = all ? s->gu : c.take<bf16_t>(M * (opt ? 1 : 2) * I);
+    a.act = as ? s->act : c.take<bf16_t>(M * I);
+    a.rstd1 = all ? s->rstd1 : c.take<float>(M);
+    a.rstd2 = all ? s->rstd2 : c.take<float>(M);
+    a.lse = all ? s->lse : c.take<float>(M * d.n_heads);
     if (opt) {
-      a.mu1 = c.take<float>(M);
-      a.mu2 = c.take<float>(M);
+      a.mu1 = all ? s->mu1 : c.take<float>(M);
+      a.mu2 = all ? s->mu2 : c.take<float>(M);
     }
   }
   e->hf = c.take<bf16_t>(M * H);
@@ -561,12 +572,97 @@ int adamw_model(SlamEngine* h, int mode, float* master, void* m, void* v, const 
   return r;
 }
 
-// The decoder layer loop of a forward over M = B*T tokens: segments, attention plan, RoPE tables, embedding and every layer,
-// leaving the last residual stream in hs[L] (slam_forward and slam_prefill continue from there).
-int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_ids, const int32_t* seg_start,
-                   const int32_t* seg_end, int M, int T, hipStream_t st) {
+// K and V of layer l in the bound cache
+bf16_t* kv_k(SlamEngine* h, int l) {
+  return h->kv + (size_t)l * 2 * h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim;
+}
+bf16_t* kv_v(SlamEngine* h, int l) { return kv_k(h, l) + (size_t)h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim; }
+
+// One decoder layer's forward launches over M tokens: hs[l] -> la[l] (-> hs[l + 1]). The one body that slam_forward,
+// slam_prefill and the recomputation in slam_backward share, so a re-run issues the forward's own calls in the forward's own
+// order. `rerun` (backward, "recompute" = 2): the layer's parameters are already final for this step (no chunk / parameter
+// waits), the gate|up timing events are left alone and the down projection is skipped - its only output is hs[l + 1], which
+// backward no longer needs and already re-uses as the gradient of hmid. The caller holds the GemmTuneScope.
+int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
   const SlamModelDesc& d = h->d;
   const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads;
+  const bf16_t* P = h->params;
+  const float qscale = 1.44269504088896340736f / sqrtf((float)d.head_dim);
+  const bool opt = h->arch == 1;
+  const LayerOff& o = h->lo[l];
+  LayerAct& a = h->la[l];
+  if (!rerun) {
+    CK(wait_chunk(h, 1 + l, st));
+    CK(wait_params(h, o.ln1, o.ln1 + h->layer_stride, st));
+  }
+  if (opt) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, d.rms_eps, st));
+  else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
+  if (d.head_dim == 64 && (H % 64 == 0) && (h->QKV % 128 == 0)) {  // bias + RoPE fused into the projection epilogue
+    TK(F_QKV_FWD, st, gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
+  } else {
+    const int slot = fam_begin(h, F_QKV_FWD, st);
+    CK(gemm_nt(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, nullptr, M, h->QKV, H, st));
+    CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, d.head_dim, h->cosb, h->sinb, 0, st, nH, qscale));
+    fam_end(h, slot, st);
+  }
+  TK(F_ATTN_FWD, st, attn_fwd(a.qkv, a.o, a.lse, h->cur_seg_s, h->attn_plan_buf, h->attn_tune, M, nH, nKV, d.head_dim, st));
+  if (opt) {  // out_proj bias + residual, LayerNorm, fc1 bias + ReLU, fc2 bias + residual
+    TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, P + o.bo, h->hs[l], M, H, nH * d.head_dim, st));
+    TK(F_NORM_FWD, st, layernorm_fwd(a.hmid, P + o.ln2, P + o.ln2_b, a.x2, a.mu2, a.rstd2, M, H, d.rms_eps, st));
+    TK(F_GATEUP_FWD, st, gemm_nt_relu(a.x2, P + o.wgu, a.act, P + o.b1, M, I, H, st));
+    if (!rerun) TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], P + o.b2, a.hmid, M, H, I, st));
+    return SLAM_OK;
+  }
+  TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, nullptr, h->hs[l], M, H, nH * d.head_dim, st));
+  TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
+  const bool timed = !rerun && h->time_gateup && h->tg_ev.size() == (size_t)(2 * L);
+  if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l], st));
+  {
+    const int slot = fam_begin(h, F_GATEUP_FWD, st);
+    if (h->fuse_swiglu) {
+      CK(gemm_nt_swiglu(a.x2, P + o.wgu, a.gu, a.act, M, 2 * I, H, st));
+    } else {
+      CK(gemm_nt(a.x2, P + o.wgu, a.gu, nullptr, nullptr, M, 2 * I, H, st));
+      CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
+    }
+    fam_end(h, slot, st);
+  }
+  if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l + 1], st));
+  if (!rerun) TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], nullptr, a.hmid, M, H, I, st));
+  return SLAM_OK;
+}
+
+// "recompute" = 1: layer l's x1, x2 and (Qwen2) act, rebuilt in backward into the layer's shared slot from what the layer
+// kept - hs[l], hmid and gu - by the kernels that made them in the forward, so the bits are the forward's. With the SwiGLU
+// fused into the gate|up projection (fuse_swiglu) act came from the projection's fp32 accumulators, which the stored bf16
+// gate|up no longer holds: that launch is re-run whole and rewrites gu with the values it has. The row statistics are
+// rewritten with their own values too. OPT keeps act (its fc1 pre-activation is never stored): x1 and x2 only.
+int rebuild_selective(SlamEngine* h, int l, int M, hipStream_t st) {
+  const SlamModelDesc& d = h->d;
+  const int H = d.hidden, I = d.intermediate;
+  const bf16_t* P = h->params;
+  const LayerOff& o = h->lo[l];
+  LayerAct& a = h->la[l];
+  if (h->arch == 1) {
+    TK(F_NORM_FWD, st, layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, d.rms_eps, st));
+    TK(F_NORM_FWD, st, layernorm_fwd(a.hmid, P + o.ln2, P + o.ln2_b, a.x2, a.mu2, a.rstd2, M, H, d.rms_eps, st));
+    return SLAM_OK;
+  }
+  TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
+  TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
+  if (h->fuse_swiglu) TK(F_GATEUP_FWD, st, gemm_nt_swiglu(a.x2, P + o.wgu, a.gu, a.act, M, 2 * I, H, st));
+  else TK(F_GATEUP_FWD, st, swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
+  return SLAM_OK;
+}
+
+// The decoder layer loop of a forward over M = B*T tokens: segments, attention plan, RoPE tables, embedding and every layer,
+// leaving the last residual stream in hs[L] (slam_forward and slam_prefill continue from there). kv_lens (slam_prefill over
+// kv_B rows, and only when the layers share their q|k|v buffer): each layer's K / V go to the cache before the next layer
+// overwrites them.
+int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_ids, const int32_t* seg_start,
+                   const int32_t* seg_end, int M, int T, hipStream_t st, const int32_t* kv_lens = nullptr, int kv_B = 0) {
+  const SlamModelDesc& d = h->d;
+  const int H = d.hidden, L = d.n_layers;
   const bf16_t* P = h->params;
   if (seg_start) {
     h->cur_seg_s = seg_start;
@@ -594,44 +690,8 @@ int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_id
   if (opt) CK(embed_pos_fwd(ids, position_ids, P + h->off_embed, P + h->off_pos, h->hs[0], h->prow, M, H, d.vocab, T, h->npos, st));
   else CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
   for (int l = 0; l < L; ++l) {
-    const LayerOff& o = h->lo[l];
-    LayerAct& a = h->la[l];
-    CK(wait_chunk(h, 1 + l, st));
-    CK(wait_params(h, o.ln1, o.ln1 + h->layer_stride, st));
-    if (opt) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, d.rms_eps, st));
-    else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
-    if (d.head_dim == 64 && (H % 64 == 0) && (h->QKV % 128 == 0)) {  // bias + RoPE fused into the projection epilogue
-      TK(F_QKV_FWD, st, gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
-    } else {
-      const int slot = fam_begin(h, F_QKV_FWD, st);
-      CK(gemm_nt(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, nullptr, M, h->QKV, H, st));
-      CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, d.head_dim, h->cosb, h->sinb, 0, st, nH, qscale));
-      fam_end(h, slot, st);
-    }
-    TK(F_ATTN_FWD, st, attn_fwd(a.qkv, a.o, a.lse, h->cur_seg_s, h->attn_plan_buf, h->attn_tune, M, nH, nKV, d.head_dim, st));
-    if (opt) {  // out_proj bias + residual, LayerNorm, fc1 bias + ReLU, fc2 bias + residual
-      TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, P + o.bo, h->hs[l], M, H, nH * d.head_dim, st));
-      TK(F_NORM_FWD, st, layernorm_fwd(a.hmid, P + o.ln2, P + o.ln2_b, a.x2, a.mu2, a.rstd2, M, H, d.rms_eps, st));
-      TK(F_GATEUP_FWD, st, gemm_nt_relu(a.x2, P + o.wgu, a.act, P + o.b1, M, I, H, st));
-      TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], P + o.b2, a.hmid, M, H, I, st));
-      continue;
-    }
-    TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, nullptr, h->hs[l], M, H, nH * d.head_dim, st));
-    TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
-    const bool timed = h->time_gateup && h->tg_ev.size() == (size_t)(2 * L);
-    if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l], st));
-    {
-      const int slot = fam_begin(h, F_GATEUP_FWD, st);
-      if (h->fuse_swiglu) {
-        CK(gemm_nt_swiglu(a.x2, P + o.wgu, a.gu, a.act, M, 2 * I, H, st));
-      } else {
-        CK(gemm_nt(a.x2, P + o.wgu, a.gu, nullptr, nullptr, M, 2 * I, H, st));
-        CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
-      }
-      fam_end(h, slot, st);
-    }
-    if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l + 1], st));
-    TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], nullptr, a.hmid, M, H, I, st));
+    CK(layer_forward(h, l, M, false, st));
+    if (kv_lens) CK(kv_scatter(h->la[l].qkv, kv_k(h, l), kv_v(h, l), kv_lens, kv_B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st));
   }
   CK(join_optimizer(h, st));
   CK(join_params(h, st));
@@ -787,6 +847,7 @@ size_t slam_workspace_bytes(SlamEngine* h, int64_t max_tokens) {
   tmp.vpad = h->vpad;
   tmp.untied = h->untied;
   tmp.n_params = h->n_params;
+  tmp.recompute = h->recompute;
   return carve(&tmp, nullptr, max_tokens);
 }
 int slam_bind_workspace(SlamEngine* h, void* ws, size_t bytes, int64_t max_tokens) {
@@ -836,6 +897,18 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
   if (!strcmp(key, "grad_final_next") && h) {
     if (value < 0 || value > 2) return h->fail(SLAM_EINVAL, "grad_final_next takes 0, 1 or 2");
     h->final_next = (int)value;
+    return SLAM_OK;
+  }
+  if (!strcmp(key, "recompute") && h) {
+    if (value < 0 || value > 2) return h->fail(SLAM_EINVAL, "value out of range for option recompute (0, 1 or 2)");
+    if ((int)value != h->recompute) {  // the workspace layout depends on the level: the bound one no longer fits
+      h->recompute = (int)value;
+      h->ws = nullptr;
+      h->ws_bytes = 0;
+      h->max_tokens = 0;
+      h->have_fwd = h->have_loss = false;
+      h->kv_ready = false;
+    }
     return SLAM_OK;
   }
   if (!strcmp(key, "fuse_swiglu") && h) { h->fuse_swiglu = value != 0; return SLAM_OK; }
@@ -898,12 +971,6 @@ int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_bat
 }
 
 namespace {
-// K and V of layer l in the bound cache
-bf16_t* kv_k(SlamEngine* h, int l) {
-  return h->kv + (size_t)l * 2 * h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim;
-}
-bf16_t* kv_v(SlamEngine* h, int l) { return kv_k(h, l) + (size_t)h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim; }
-
 // decode-time projection: the weight-streaming kernel up to SKINNY_MAX_M rows (split-K partials in the backward-only dact
 // buffer), the tiled GEMM beyond; fp32 outputs always take the streaming kernel (in 64-row chunks)
 int decode_proj(SlamEngine* h, const bf16_t* X, const bf16_t* W, bf16_t* Y, float* Yf, const bf16_t* bias, const bf16_t* resid,
@@ -929,8 +996,10 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   h->have_fwd = false;
   h->kv_ready = false;
   GemmTuneScope tune_scope(&h->gemm_tune);
-  CK(forward_layers(h, ids, nullptr, nullptr, nullptr, M, T, st));
-  for (int l = 0; l < L; ++l)
+  // "recompute" = 2 with more layers than slots: the layers share their q|k|v buffers, so each layer's K / V leave inside the loop
+  const bool shared_qkv = h->recompute == 2 && L > RC_SLOTS;
+  CK(forward_layers(h, ids, nullptr, nullptr, nullptr, M, T, st, shared_qkv ? lens : nullptr, B));
+  for (int l = 0; l < L && !shared_qkv; ++l)
     CK(kv_scatter(h->la[l].qkv, kv_k(h, l), kv_v(h, l), lens, B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st));
   // logits of each row's last prompt token only: gather, final norm, one fp32 head launch over B rows
   CK(gather_last_rows(h->hs[L], h->dx, lens, B, T, H, st));
@@ -1123,6 +1192,27 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
     return colsum_bf16(X, N, M, N, nullptr, 1, part, st);
   };
 
+  // "recompute": layer l's slot (l mod 3) last held layer l + 3. On the caller's stream everything of that layer is behind us;
+  // on the weight-gradient stream its last reader is layer l + 2's Wqkv gradient and bias column sums, whose d(qkv) lives in
+  // la[l + 3].qkv. Layer l + 1's weight gradients touch the slots of layers l + 1 and l + 2 only. So one side -> main edge per
+  // layer, a whole layer old by the time it is waited for ("Activation recomputation", has the table).
+  const int rc = h->recompute;
+  const bool slot_edges = rc && two && L > RC_SLOTS;
+  if (slot_edges && h->ev_rc.empty()) {
+    h->ev_rc.resize((size_t)L);
+    for (auto& ev : h->ev_rc)
+      if (hipEventCreateWithFlags(&ev, sync_event_flags()) != hipSuccess) { h->ev_rc.clear(); return h->fail(SLAM_ESTATE, "hipEventCreate failed"); }
+  }
+  auto rebuild = [&](int l) -> int {
+    if (slot_edges && l + RC_SLOTS - 1 < L) CK((int)hipStreamWaitEvent(st, h->ev_rc[(size_t)l + RC_SLOTS - 1], 0));
+    h->gemm_tune.shared = 0;  // the forward's launches plan for a GPU of their own: so do their re-runs
+    const int r = rc == 2 ? layer_forward(h, l, M, true, st) : rebuild_selective(h, l, M, st);
+    h->gemm_tune.shared = two ? 1 : 0;
+    return r;
+  };
+  // the weight-gradient stream has everything of layer l that reads a shared slot
+  auto slot_done = [&](int l) -> int { return slot_edges && l >= RC_SLOTS - 1 ? (int)hipEventRecord(h->ev_rc[(size_t)l], ws) : 0; };
+
   const int bl = bucket_layers > 0 ? bucket_layers : L;
   int64_t bucket_end = h->n_params;  // exclusive end of the not-yet-reported range
   int fin_hi = L;                    // layers >= fin_hi have their norm/bias partial slabs finished
@@ -1131,6 +1221,7 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
     LayerAct& a = h->la[l];
     bf16_t* dh2 = h->hs[l + 1];                              // grad wrt hmid[l]: hs[l+1] was last read by the norm backward above it
     bf16_t* dqkv = l + 1 < L ? h->la[l + 1].qkv : h->dqkv;   // layer l+1's q|k|v were last read by its attention backward
+    if (rc) CK(rebuild(l));  // before the first reader below, and before the SwiGLU backward overwrites gu
     if (opt) {
       // MLP: fc2 (bias + residual), ReLU, fc1 (bias); d(act) goes to this layer's own gu buffer, which nothing overwrites before
       // the next forward (the fc1 weight gradient and the b1 column sums read it on the weight-gradient stream)
@@ -1160,6 +1251,7 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
                   M, nH, nKV, d.head_dim, st));
       CK(bias_cols(dqkv, h->QKV, h->bias_part + (size_t)l * h->bias_ps));
       CK(wgrad(F_WQKV_WGRAD, dqkv, a.x1, G + o.wqkv, h->QKV, H, img(o.wqkv), true, aux));
+      CK(slot_done(l));
       TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, h->dx, h->QKV, H));
       dh = a.hmid;
       TK(F_NORM_BWD, st, layernorm_bwd(h->dx, h->hs[l], P + o.ln1, a.mu1, a.rstd1, dh2, dh, h->ln_part + (size_t)(2 * l) * h->ln_ps,
@@ -1192,6 +1284,7 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
       CK(colsum_bf16(dqkv, h->QKV, M, h->QKV, nullptr, 1, h->bias_part + (size_t)l * h->bias_ps, st));
     }
     CK(wgrad(F_WQKV_WGRAD, dqkv, a.x1, G + o.wqkv, h->QKV, H, img(o.wqkv), true, aux));
+    CK(slot_done(l));
     TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, h->dx, h->QKV, H));
     dh = a.hmid;  // grad wrt hs[l]: hmid[l] was last read by the ln2 backward above
     TK(F_NORM_BWD, st, rmsnorm_bwd(h->dx, h->hs[l], P + o.ln1, a.rstd1, dh2, dh, nullptr, 1, h->ln_part + (size_t)(2 * l) * h->ln_ps, M, H, st));

@@ -297,6 +297,9 @@ class UnitLM(TokenLM):
                 self.engine.bind_params_t(self.flat_params_t)
             self._ws = None
             self._ws_tokens = 0
+            self._recompute = int(os.environ.get("SLAM_RECOMPUTE", "0"))  # measurement override, like the SLAM_* knobs below
+            if self._recompute:
+                self.engine.set_option("recompute", self._recompute)
             self._ensure_workspace(config.max_tokens)
             self._loss_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
             self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
@@ -399,6 +402,7 @@ class UnitLM(TokenLM):
     def _ensure_workspace(self, tokens: int):
         if tokens <= self._ws_tokens:
             return
+        tokens = max(tokens, getattr(self, "_ws_floor", 0))  # after a level change: the size that was bound before it
         nbytes = self.engine.workspace_bytes(tokens)
         self._ws = None
         self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
@@ -406,6 +410,35 @@ class UnitLM(TokenLM):
         self._ws_aligned = self._ws[off:off + nbytes]
         self.engine.bind_workspace(self._ws_aligned, tokens)
         self._ws_tokens = tokens
+
+    # ---- activation recomputation (HF's names; a run-time mode: configs and checkpoints do not carry it) ------------------
+    supports_gradient_checkpointing = True
+
+    def _set_recompute(self, level: int):
+        level = int(level)
+        if level == getattr(self, "_recompute", 0):
+            return
+        torch.cuda.synchronize(self.device)  # nothing in flight may still use the workspace that is about to go
+        self.engine.set_option("recompute", level)  # unbinds the workspace: its layout depends on the level
+        self._recompute = level
+        self._ws_floor = max(self._ws_tokens, getattr(self, "_ws_floor", 0))
+        self._ws = None
+        self._ws_aligned = None
+        self._ws_tokens = 0  # the next forward / prefill binds a workspace of the new layout
+
+    def gradient_checkpointing_enable(self, level: int = 2, gradient_checkpointing_kwargs=None):
+        """Recompute activations in backward instead of keeping them: level 2 re-runs each layer's forward from its residual
+        stream, level 1 rebuilds only the norm outputs and the MLP activation (slam_set_option "recompute"). Same bits as off."""
+        if level not in (1, 2):
+            raise ValueError("gradient checkpointing level is 1 (selective) or 2 (full layer)")
+        self._set_recompute(level)
+
+    def gradient_checkpointing_disable(self):
+        self._set_recompute(0)
+
+    @property
+    def is_gradient_checkpointing(self) -> bool:
+        return getattr(self, "_recompute", 0) != 0
 
     # ---- parameters ----------------------------------------------------------------------------
     @torch.no_grad()

@@ -44,6 +44,10 @@ class SLAMTrainer:
         self.state = TrainerState()
         self.control = TrainerControl()
         self.rank, self.world = world_info()
+        # as HF's Trainer: args.gradient_checkpointing switches the model's mode on (recompute_level picks the level)
+        rc_level = self.args.get_recompute_level() if hasattr(self.args, "get_recompute_level") else 0
+        if rc_level:
+            model.gradient_checkpointing_enable(level=rc_level)
         dev = model.device
         n = model.engine.n_params
         osd = getattr(self.args, "optim_state_dtype", "float32") or "float32"

@@ -5,10 +5,13 @@ packed micro-batch of --tokens tokens in sequences of --ctx (the interleaved mod
 random-init weights. The body runs at reduced depth (--layers, default 4); --layers 4,28 adds the full depth, which is
 reported as not fitting (one JSON line with "error") when the device runs out of memory.
 
-    python tools/wide_bench.py [--layers 4] [--tokens 16384] [--ctx 2048] [--steps 10] [--warmup 3] [--seed 0]
+    python tools/wide_bench.py [--layers 4] [--tokens 16384] [--ctx 2048] [--steps 10] [--warmup 3] [--seed 0] [--recompute 0]
+
+--recompute 1 | 2 runs the step with activation recomputation in backward (UnitLM.gradient_checkpointing_enable(level)).
 
 Prints one JSON line per depth: tokens/s from the wall time of the timed steps (device-synchronised before and after), the
-median per-step device time, the loss, the peak device memory torch allocated.
+median per-step device time, the loss, the recomputation level, the bytes of the bound engine workspace and the peak device
+memory torch allocated.
 """
 import argparse
 import json
@@ -25,14 +28,18 @@ V = 152064
 BASE = "Qwen/Qwen2.5-7B"
 
 
-def run(layers: int, tokens: int, ctx: int, steps: int, warmup: int, seed: int) -> dict:
+def run(layers: int, tokens: int, ctx: int, steps: int, warmup: int, seed: int, recompute: int = 0) -> dict:
     from slamkit_amd.model import UnitLM, UnitLMConfig
     from slamkit_amd.model.unit_lm import KNOWN_BASE_CONFIGS
     from slamkit_amd.trainer import SLAMTrainer, SLAMTrainingArguments
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.cuda.reset_peak_memory_stats(dev)
     base = dict(KNOWN_BASE_CONFIGS[BASE], num_hidden_layers=layers)
-    model = UnitLM(UnitLMConfig(base_model_name=BASE, base_config=base, vocab_size=V, max_tokens=tokens), seed=seed)
+    # with recomputation the full-size workspace is bound by the first step, in the level's layout: the constructor's own
+    # (level 0) workspace stays small, so the peak below is the level's
+    model = UnitLM(UnitLMConfig(base_model_name=BASE, base_config=base, vocab_size=V, max_tokens=ctx if recompute else tokens), seed=seed)
+    if recompute:
+        model.gradient_checkpointing_enable(level=recompute)
     args = SLAMTrainingArguments(per_device_train_batch_size=1, gradient_accumulation_steps=1, learning_rate=1e-4,
                                  max_grad_norm=0.5, logging_steps=0, optim_state_dtype="bfloat16")
     trainer = SLAMTrainer(model=model, args=args)  # drops the fp32 master: the bf16 parameters are the state
@@ -70,6 +77,7 @@ def run(layers: int, tokens: int, ctx: int, steps: int, warmup: int, seed: int) 
             "params": model.engine.n_params, "tokens_per_s": round(nseq * ctx * steps / dt, 1),
             "ms_per_step": round(1e3 * dt / steps, 3), "ms_per_step_median": round(per[len(per) // 2], 3),
             "loss": round(float(trainer._loss_acc) / max(1, trainer._loss_n), 4),
+            "recompute": recompute, "workspace_bytes": model.engine.workspace_bytes(model._ws_tokens),
             "peak_device_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2),
             "device": torch.cuda.get_device_name(dev)}
 
@@ -82,11 +90,12 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--recompute", type=int, default=0, choices=(0, 1, 2), help="activation recomputation level in backward")
     a = ap.parse_args(argv)
     torch.manual_seed(a.seed)
     for layers in (int(x) for x in a.layers.split(",")):
         try:
-            res = run(layers, a.tokens, a.ctx, a.steps, a.warmup, a.seed)
+            res = run(layers, a.tokens, a.ctx, a.steps, a.warmup, a.seed, a.recompute)
         except torch.cuda.OutOfMemoryError as e:  # reported, not hidden: the depth does not fit this device
             res = {"model": BASE, "layers": layers, "tokens": a.tokens, "error": "out of device memory",
                    "detail": str(e).splitlines()[0][:200],
