@@ -322,7 +322,23 @@ int slam_cast_params(SlamEngine* h, const float* master_f32, slam_stream_t strea
  * The workspace layout depends on the level (slam_workspace_bytes answers for the current one). CHANGING the level while a
  * workspace is bound unbinds it: slam_forward, slam_prefill, slam_decode_step and slam_backward return SLAM_ESTATE until
  * slam_bind_workspace is called again. Under "time_families" the re-run launches are recorded under the forward families'
- * ids (norm_fwd, qkv_fwd, ...), inside the backward part of the record list; "time_gateup" does not time them. */
+ * ids (norm_fwd, qkv_fwd, ...), inside the backward part of the record list; "time_gateup" does not time them.
+ *
+ * "adamw_sr" = 0 | 1 (default 0; anything else is SLAM_EINVAL, "out of range"): stochastic rounding of the bf16 optimizer state.
+ * Round-to-nearest drops every update below half an ulp of the stored value, which at a small learning rate is most of them;
+ * with 1, every fp32 -> bf16 store of STATE adds 16 uniform random bits below the kept mantissa and truncates, so the stored
+ * value is right on average (exact bf16 values never move; inf / NaN convert as before). Rounded that way:
+ *   slam_adamw_step_bf16 / slam_adamw_range_bf16          p, m and v (the bf16 parameters are the state);
+ *   slam_adamw_step_bf16_moments / slam_adamw_range_bf16_moments   m and v (the bf16 working copy of the fp32 master keeps
+ *                                                          round-to-nearest: the master holds the precision);
+ *   slam_adamw_step / slam_adamw_range (fp32 state)        nothing - the option is ignored there.
+ * A transposed weight image carries the same rounded value as the row-major parameter. The generator is stateless
+ * (Philox4x32-10): key = (seed & 0xffffffff, seed >> 32), counter = (i8 & 0xffffffff, i8 >> 32, step, s) with i8 = the
+ * element's index in the flat parameter buffer >> 3, `step` the one the entry point is passed and s = 0 / 1 / 2 for p / m / v;
+ * element j = index & 7 takes bits (w[j >> 1] >> 16 (j & 1)) & 0xffff of the four output words. Hence the result does not
+ * depend on the kernel form ("fuse_adamw_t", the range entry points, how a sharded update splits the buffer), the stream or
+ * the rank, and a run resumed at step k repeats the uninterrupted one. With 0 every bit is what it was without the option.
+ * "adamw_sr_seed" = any int64 (default 0): the seed, read as 64 unsigned bits. */
 int slam_set_option(SlamEngine* h, const char* key, int64_t value);
 
 /* ---- single-op entry points (parity tests call each kernel through the ABI) -------------------*/
@@ -412,6 +428,10 @@ int slam_op_cross_entropy(const void* logits /* bf16 [B*T][Vp] */, const int64_t
 size_t slam_op_embed_bwd_workspace(int M, int Vp);
 int slam_op_embed_bwd(const int64_t* ids, const void* dh /* bf16 [M][H] */, float* dE /* fp32 [Vp][H] */, int M, int H,
                       int Vp, int V, int pad_id, void* ws, slam_stream_t s);
+/* y_bf16[i] = the "adamw_sr" rounding of x[i], with the random bits of flat-buffer index index0 + i of array `which` (0 p, 1 m,
+ * 2 v) at optimizer step `step` (>= 1) under `seed`: what the AdamW kernels apply to their state stores, on its own. */
+int slam_op_sr_round_bf16(const float* x, void* y_bf16, int64_t n, int64_t index0, int64_t seed, int32_t step, int32_t which,
+                          slam_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,55 @@ SLAM_DEVICE uint4 pack_bf16x8(const float* f) {
   return v;
 }
 
+// ---- stochastic rounding fp32 -> bf16 ("adamw_sr") ------------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11): counter-based, stateless - the output depends on (counter, key) alone.
+struct Philox4 { uint32_t w[4]; };
+SLAM_DEVICE Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return {{c0, c1, c2, c3}};
+}
+// what the rounding of one optimizer step is keyed on: the 64-bit seed, the step, and the index in the engine's flat parameter
+// buffer of element 0 of the arrays a kernel was handed
+struct SrKey { uint32_t k0, k1, step, pad; uint64_t base; };
+// the 16 random bits of the 8 consecutive elements [8 * i8, 8 * i8 + 8) of array `which` (0 p, 1 m, 2 v): one call, element j
+// takes sr_r16(w, j). Nothing about the launch enters: every kernel form draws the same bits for the same element.
+SLAM_DEVICE Philox4 sr_bits8(const SrKey& k, uint64_t i8, uint32_t which) {
+  return philox4x32_10((uint32_t)i8, (uint32_t)(i8 >> 32), k.step, which, k.k0, k.k1);
+}
+SLAM_DEVICE uint32_t sr_r16(const Philox4& b, int j) { return (b.w[j >> 1] >> (16 * (j & 1))) & 0xffffu; }
+// finite x: add 16 uniform bits below the kept mantissa, truncate (exact bf16 values never move; the magnitude rounds, so
+// negative values are as unbiased as positive ones); inf / NaN: the round-to-nearest conversion's result
+SLAM_DEVICE uint32_t sr_bf16(float x, uint32_t r16) {
+  const uint32_t u = __float_as_uint(x);
+  if ((u & 0x7f800000u) == 0x7f800000u) return pack_bf16x2(x, 0.f) & 0xffffu;
+  return (u + r16) >> 16;
+}
+// 8 / 4 consecutive elements starting at flat index gi (a multiple of 8 / 4), packed like pack_bf16x8 / store4 pack them
+SLAM_DEVICE uint4 sr_pack_bf16x8(const float* f, const SrKey& k, uint64_t gi, uint32_t which) {
+  const Philox4 b = sr_bits8(k, gi >> 3, which);
+  uint4 v;
+  v.x = sr_bf16(f[0], b.w[0] & 0xffffu) | (sr_bf16(f[1], b.w[0] >> 16) << 16);
+  v.y = sr_bf16(f[2], b.w[1] & 0xffffu) | (sr_bf16(f[3], b.w[1] >> 16) << 16);
+  v.z = sr_bf16(f[4], b.w[2] & 0xffffu) | (sr_bf16(f[5], b.w[2] >> 16) << 16);
+  v.w = sr_bf16(f[6], b.w[3] & 0xffffu) | (sr_bf16(f[7], b.w[3] >> 16) << 16);
+  return v;
+}
+SLAM_DEVICE uint2 sr_pack_bf16x4(const float* f, const SrKey& k, uint64_t gi, uint32_t which) {
+  const Philox4 b = sr_bits8(k, gi >> 3, which);
+  const bool hi = (gi & 4) != 0;
+  const uint32_t w0 = hi ? b.w[2] : b.w[0], w1 = hi ? b.w[3] : b.w[1];
+  uint2 v;
+  v.x = sr_bf16(f[0], w0 & 0xffffu) | (sr_bf16(f[1], w0 >> 16) << 16);
+  v.y = sr_bf16(f[2], w1 & 0xffffu) | (sr_bf16(f[3], w1 >> 16) << 16);
+  return v;
+}
+
 // raw v_exp_f32 (2^x): no denormal-range fix-up code (arguments here are <= 0 or moderate)
 SLAM_DEVICE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 

@@ -990,7 +990,8 @@ __global__ __launch_bounds__(1024) void norm_finish_kernel(const float* __restri
   }
 }
 
-struct AdamHyper { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int zero_grad; };
+// sr: the key of the stochastic rounding of the bf16 state stores (read by the SR = true kernels only)
+struct AdamHyper { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int zero_grad; SrKey sr; };
 template <typename MT> SLAM_DEVICE void load4(const MT* q, float* f);
 template <> SLAM_DEVICE void load4<float>(const float* q, float* f) {
   const float4 t = *reinterpret_cast<const float4*>(q);
@@ -1007,6 +1008,24 @@ SLAM_DEVICE void store4(bf16_t* q, const float* f) {
   o.x = pack_bf16x2(f[0], f[1]); o.y = pack_bf16x2(f[2], f[3]);
   *reinterpret_cast<uint2*>(q) = o;
 }
+// the bf16 store of 4 consecutive state values at flat index gi of array `which`, rounded stochastically when SR
+template <bool SR>
+SLAM_DEVICE uint2 round4(const float* f, const SrKey& k, uint64_t gi, uint32_t which) {
+  if constexpr (SR) return sr_pack_bf16x4(f, k, gi, which);
+  uint2 o;
+  o.x = pack_bf16x2(f[0], f[1]); o.y = pack_bf16x2(f[2], f[3]);
+  return o;
+}
+template <bool SR>
+SLAM_DEVICE uint4 round8(const float* f, const SrKey& k, uint64_t gi, uint32_t which) {
+  if constexpr (SR) return sr_pack_bf16x8(f, k, gi, which);
+  return pack_bf16x8(f);
+}
+template <bool SR, typename MT>
+SLAM_DEVICE void store4_state(MT* q, const float* f, const SrKey& k, uint64_t gi, uint32_t which) {
+  if constexpr (SR && sizeof(MT) == 2) *reinterpret_cast<uint2*>(q) = sr_pack_bf16x4(f, k, gi, which);
+  else store4(q, f);
+}
 // one element of torch.optim.AdamW (fp32 master: adamw_kernel's expression; bf16 state: the fused-kernel form with lerp)
 template <bool MASTER>
 SLAM_DEVICE void adam_elem(float& p, float& m, float& v, float g, const AdamHyper& h) {
@@ -1016,6 +1035,26 @@ SLAM_DEVICE void adam_elem(float& p, float& m, float& v, float g, const AdamHype
   v = h.b2 * v + (1.f - h.b2) * g * g;
   const float den = sqrtf(v) / h.bc2_sqrt + h.eps;
   p -= (h.lr / h.bc1) * (m / den);
+}
+// The same update for the stochastically rounded kernels, with every fp32 operation pinned: no contraction left to the compiler,
+// the fused multiply-adds written out. Round-to-nearest hides a last-bit fp32 difference between two kernel forms (one contracts
+// g * cs into the subtraction, the other does not) except at a tie; stochastic rounding turns it into another bf16 value once
+// in 2^16 elements - and every form must store the same bits.
+template <bool MASTER>
+SLAM_DEVICE void adam_elem_pinned(float& p, float& m, float& v, float g_raw, float cs, const AdamHyper& h) {
+#pragma clang fp contract(off)
+  const float g = g_raw * cs;
+  p = p * (1.f - h.lr * h.wd);
+  if (MASTER) m = __builtin_fmaf(h.b1, m, (1.f - h.b1) * g);
+  else m = __builtin_fmaf(1.f - h.b1, g - m, m);
+  v = __builtin_fmaf(h.b2, v, ((1.f - h.b2) * g) * g);
+  const float den = sqrtf(v) / h.bc2_sqrt + h.eps;
+  p = __builtin_fmaf(-(h.lr / h.bc1), m / den, p);
+}
+template <bool MASTER, bool SR>
+SLAM_DEVICE void adam_update(float& p, float& m, float& v, float g, float cs, const AdamHyper& h) {
+  if constexpr (SR) adam_elem_pinned<MASTER>(p, m, v, g, cs, h);
+  else adam_elem<MASTER>(p, m, v, g * cs, h);
 }
 // torch.optim.AdamW semantics on fp32 master weights; writes the bf16 working copy; optional
 // grad zeroing. Traffic: 30 B/param (fp32 g,p,m,v read; p,m,v + bf16 written), 34 with zeroing.
@@ -1038,7 +1077,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, bf16_
   float4 vv = *reinterpret_cast<float4*>(v + i);
   float ga[4] = {gv.x * cs, gv.y * cs, gv.z * cs, gv.w * cs};
   float pa[4] = {pv.x, pv.y, pv.z, pv.w}, ma[4] = {mv.x, mv.y, mv.z, mv.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
-  const AdamHyper h = {lr, b1, b2, eps, wd, bc1, bc2_sqrt, zero_grad};
+  const AdamHyper h = {lr, b1, b2, eps, wd, bc1, bc2_sqrt, zero_grad, {}};
 #pragma unroll
   for (int j = 0; j < 4; ++j) adam_elem<true>(pa[j], ma[j], va[j], ga[j], h);  // the tile kernel's expression: bit-identical updates
   *reinterpret_cast<float4*>(p + i) = make_float4(pa[0], pa[1], pa[2], pa[3]);
@@ -1057,29 +1096,35 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, bf16_
 // and bf16 Adam moments under torch.optim.AdamW(fused=True)): state is STORED in bf16, every update is computed in fp32
 // from the stored values and rounded once on the way back (torch's fused kernel: opmath fp32, exp_avg by lerp).
 // No fp32 master copy. Traffic: fp32 g read (4) + bf16 p, m, v read and written (12) = 16 B/param.
-template <typename GT>
+// SR ("adamw_sr"): p, m and v are rounded stochastically (sr_bf16), keyed on sr.base + i - the element's index in the flat buffer.
+template <typename GT, bool SR>
 __global__ __launch_bounds__(256) void adamw_bf16_kernel(bf16_t* __restrict__ p, GT* __restrict__ g,
                                                          bf16_t* __restrict__ m, bf16_t* __restrict__ v, size_t n,
                                                          const float* __restrict__ clip, float lr, float b1, float b2,
-                                                         float eps, float wd, float bc1, float bc2_sqrt, int zero_grad) {
+                                                         float eps, float wd, float bc1, float bc2_sqrt, int zero_grad, SrKey sr) {
   size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
   if (i >= n) return;
   const float cs = clip ? clip[1] : 1.f;
   float ga[8];
   load4<GT>(g + i, ga);
   load4<GT>(g + i + 4, ga + 4);
+  if constexpr (!SR) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) ga[j] *= cs;
+    for (int j = 0; j < 8; ++j) ga[j] *= cs;
+  }
   float pa[8], ma[8], va[8];
   unpack_bf16x8(*reinterpret_cast<const uint4*>(p + i), pa);
   unpack_bf16x8(*reinterpret_cast<const uint4*>(m + i), ma);
   unpack_bf16x8(*reinterpret_cast<const uint4*>(v + i), va);
-  const AdamHyper h = {lr, b1, b2, eps, wd, bc1, bc2_sqrt, zero_grad};
+  const AdamHyper h = {lr, b1, b2, eps, wd, bc1, bc2_sqrt, zero_grad, sr};
 #pragma unroll
-  for (int j = 0; j < 8; ++j) adam_elem<false>(pa[j], ma[j], va[j], ga[j], h);
-  *reinterpret_cast<uint4*>(p + i) = pack_bf16x8(pa);
-  *reinterpret_cast<uint4*>(m + i) = pack_bf16x8(ma);
-  *reinterpret_cast<uint4*>(v + i) = pack_bf16x8(va);
+  for (int j = 0; j < 8; ++j) {
+    if constexpr (SR) adam_elem_pinned<false>(pa[j], ma[j], va[j], ga[j], cs, h);
+    else adam_elem<false>(pa[j], ma[j], va[j], ga[j], h);
+  }
+  *reinterpret_cast<uint4*>(p + i) = round8<SR>(pa, sr, sr.base + i, 0);
+  *reinterpret_cast<uint4*>(m + i) = round8<SR>(ma, sr, sr.base + i, 1);
+  *reinterpret_cast<uint4*>(v + i) = round8<SR>(va, sr, sr.base + i, 2);
   if constexpr (sizeof(GT) == 4) {
     if (zero_grad) {
       *reinterpret_cast<float4*>(g + i) = make_float4(0, 0, 0, 0);
@@ -1094,7 +1139,9 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(bf16_t* __restrict__ p,
 // tile is one contiguous 256 B (fp32) / 128 B (bf16) piece of each state array; the updated bf16 tile goes out row-major
 // (pb) and, through a padded LDS tile, column-major (pt[C][R]). Per-element arithmetic is the flat kernels' own.
 // MT = float / bf16_t: storage type of the Adam moments; MASTER: fp32 master weights (else the bf16 parameters ARE the state).
-template <typename MT, bool MASTER, int TC, typename GT>  // tile = 64 rows x TC columns (TC = 64 or 128: 256 B or 512 B fp32 row segments)
+// SR (bf16 moments only): m and v are rounded stochastically, and so is p where it is the state (!MASTER; both images carry the
+// one rounded value); the working copy of an fp32 master keeps round-to-nearest - the master holds the precision.
+template <typename MT, bool MASTER, int TC, typename GT, bool SR>  // tile = 64 rows x TC columns (TC = 64 or 128: 256 B or 512 B fp32 row segments)
 __global__ __launch_bounds__(256) void adamw_tile_kernel(float* __restrict__ p, bf16_t* __restrict__ pb, bf16_t* __restrict__ pt,
                                                          GT* __restrict__ g, MT* __restrict__ m, MT* __restrict__ v, int R, int C,
                                                          size_t batch_stride, const float* __restrict__ clip, AdamHyper h) {
@@ -1115,16 +1162,27 @@ __global__ __launch_bounds__(256) void adamw_tile_kernel(float* __restrict__ p, 
     load4<MT>(m + idx, ma);
     load4<MT>(v + idx, va);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) adam_elem<MASTER>(pa[j], ma[j], va[j], ga[j] * cs, h);
+    for (int j = 0; j < 4; ++j) adam_update<MASTER, SR>(pa[j], ma[j], va[j], ga[j], cs, h);
     if (MASTER) store4(p + idx, pa);
-    store4(m + idx, ma);
-    store4(v + idx, va);
-    store4(pb + idx, pa);
+    store4_state<SR>(m + idx, ma, h.sr, h.sr.base + idx, 1);
+    store4_state<SR>(v + idx, va, h.sr, h.sr.base + idx, 2);
+    uint2 po;
+    if constexpr (SR && !MASTER) {  // rounded once: the row-major store and the transposed image carry the same value
+      po = sr_pack_bf16x4(pa, h.sr, h.sr.base + idx, 0);
+      *reinterpret_cast<uint2*>(pb + idx) = po;
+    } else {
+      store4(pb + idx, pa);
+    }
     if constexpr (sizeof(GT) == 4) {
       if (h.zero_grad) *reinterpret_cast<float4*>(g + idx) = make_float4(0, 0, 0, 0);
     }
+    if constexpr (SR && !MASTER) {
+      T[cc + 0][row] = (uint16_t)(po.x & 0xffffu); T[cc + 1][row] = (uint16_t)(po.x >> 16);
+      T[cc + 2][row] = (uint16_t)(po.y & 0xffffu); T[cc + 3][row] = (uint16_t)(po.y >> 16);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) T[cc + j][row] = (uint16_t)(pack_bf16x2(pa[j], 0.f) & 0xffffu);
+      for (int j = 0; j < 4; ++j) T[cc + j][row] = (uint16_t)(pack_bf16x2(pa[j], 0.f) & 0xffffu);
+    }
   }
   __syncthreads();
 #pragma unroll
@@ -1139,7 +1197,9 @@ __global__ __launch_bounds__(256) void adamw_tile_kernel(float* __restrict__ p, 
 }
 // The recipe's precision end to end (bf16 parameters, moments AND gradients: round 6) with 16-byte accesses: a thread owns 8
 // consecutive columns (one dwordx4 per array and row instead of two dwordx2), 16 threads per 128-column row segment, 16 rows
-// per pass. Per-element arithmetic = adam_elem<false>: the same bits as the kernel above.
+// per pass. Per-element arithmetic = adam_elem<false>: the same bits as the kernel above. SR: one Philox call per array and
+// 16-byte store (sr_pack_bf16x8).
+template <bool SR>
 __global__ __launch_bounds__(256) void adamw_tile_bf16x8_kernel(bf16_t* __restrict__ pb, bf16_t* __restrict__ pt, const bf16_t* __restrict__ g,
                                                                 bf16_t* __restrict__ m, bf16_t* __restrict__ v, int R, int C,
                                                                 size_t batch_stride, const float* __restrict__ clip, AdamHyper h) {
@@ -1168,11 +1228,11 @@ __global__ __launch_bounds__(256) void adamw_tile_bf16x8_kernel(bf16_t* __restri
     unpack_bf16x8(mq[i], ma);
     unpack_bf16x8(vq[i], va);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) adam_elem<false>(pa[j], ma[j], va[j], ga[j] * cs, h);
-    const uint4 po = pack_bf16x8(pa);
+    for (int j = 0; j < 8; ++j) adam_update<false, SR>(pa[j], ma[j], va[j], ga[j], cs, h);
+    const uint4 po = round8<SR>(pa, h.sr, h.sr.base + idx, 0);
     *reinterpret_cast<uint4*>(pb + idx) = po;
-    *reinterpret_cast<uint4*>(m + idx) = pack_bf16x8(ma);
-    *reinterpret_cast<uint4*>(v + idx) = pack_bf16x8(va);
+    *reinterpret_cast<uint4*>(m + idx) = round8<SR>(ma, h.sr, h.sr.base + idx, 1);
+    *reinterpret_cast<uint4*>(v + idx) = round8<SR>(va, h.sr, h.sr.base + idx, 2);
     const uint32_t w[4] = {po.x, po.y, po.z, po.w};
 #pragma unroll
     for (int j = 0; j < 8; ++j) T[cc + j][row] = (uint16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xffffu));
@@ -1189,7 +1249,7 @@ __global__ __launch_bounds__(256) void adamw_tile_bf16x8_kernel(bf16_t* __restri
   }
 }
 // the vectors between the matrices (norm weights, biases): count elements at a constant stride, grid.y = instances
-template <typename MT, bool MASTER, typename GT>
+template <typename MT, bool MASTER, typename GT, bool SR>
 __global__ __launch_bounds__(256) void adamw_strided_kernel(float* __restrict__ p, bf16_t* __restrict__ pb, GT* __restrict__ g,
                                                             MT* __restrict__ m, MT* __restrict__ v, size_t n, size_t stride,
                                                             const float* __restrict__ clip, AdamHyper h) {
@@ -1204,14 +1264,22 @@ __global__ __launch_bounds__(256) void adamw_strided_kernel(float* __restrict__ 
   load4<MT>(m + idx, ma);
   load4<MT>(v + idx, va);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) adam_elem<MASTER>(pa[j], ma[j], va[j], ga[j] * cs, h);
+  for (int j = 0; j < 4; ++j) adam_update<MASTER, SR>(pa[j], ma[j], va[j], ga[j], cs, h);
   if (MASTER) store4(p + idx, pa);
-  store4(m + idx, ma);
-  store4(v + idx, va);
-  store4(pb + idx, pa);
+  store4_state<SR>(m + idx, ma, h.sr, h.sr.base + idx, 1);
+  store4_state<SR>(v + idx, va, h.sr, h.sr.base + idx, 2);
+  *reinterpret_cast<uint2*>(pb + idx) = round4<SR && !MASTER>(pa, h.sr, h.sr.base + idx, 0);
   if constexpr (sizeof(GT) == 4) {
     if (h.zero_grad) *reinterpret_cast<float4*>(g + idx) = make_float4(0, 0, 0, 0);
   }
+}
+// y[i] = sr_bf16(x[i]) with the bits of flat index index0 + i of array `which`: the rounding of the kernels above on its own
+__global__ __launch_bounds__(256) void sr_round_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, size_t n, SrKey k,
+                                                            uint32_t which) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t gi = k.base + i;
+  y[i] = (bf16_t)sr_bf16(x[i], sr_r16(sr_bits8(k, gi >> 3, which), (int)(gi & 7)));
 }
 
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ s, bf16_t* __restrict__ d, size_t n) {
@@ -1503,74 +1571,103 @@ int adamw(float* p, bf16_t* pb, void* g, int g_bf16, float* m, float* v, size_t 
                                                              (float)eps, (float)wd, bc1, bc2s, zero_grad);
   LAUNCH_RET();
 }
+static SrKey sr_key(const AdamSR& sr, int step) {
+  return {(uint32_t)(sr.seed & 0xffffffffu), (uint32_t)(sr.seed >> 32), (uint32_t)step, 0u, (uint64_t)sr.base};
+}
+template <typename GT>
+static void adamw_bf16_launch(bool sr_on, bf16_t* p, GT* g, bf16_t* m, bf16_t* v, size_t n, const float* clip, double lr, double b1,
+                              double b2, double eps, double wd, float bc1, float bc2s, int zero_grad, const SrKey& k, hipStream_t st) {
+  if (sr_on)
+    adamw_bf16_kernel<GT, true><<<nblocks(n / 8, 256), 256, 0, st>>>(p, g, m, v, n, clip, (float)lr, (float)b1, (float)b2, (float)eps,
+                                                                     (float)wd, bc1, bc2s, zero_grad, k);
+  else
+    adamw_bf16_kernel<GT, false><<<nblocks(n / 8, 256), 256, 0, st>>>(p, g, m, v, n, clip, (float)lr, (float)b1, (float)b2, (float)eps,
+                                                                      (float)wd, bc1, bc2s, zero_grad, k);
+}
 int adamw_bf16(bf16_t* p, void* g, int g_bf16, bf16_t* m, bf16_t* v, size_t n, const float* clip, double lr, double b1, double b2,
-               double eps, double wd, int step, int zero_grad, hipStream_t st) {
-  if (n & 7) return -1;
+               double eps, double wd, int step, int zero_grad, const AdamSR& sr, hipStream_t st) {
+  if ((n & 7) || (sr.on && (sr.base & 7))) return -1;
   float bc1 = (float)(1.0 - pow(b1, (double)step));
   float bc2s = (float)sqrt(1.0 - pow(b2, (double)step));
-  if (g_bf16)
-    adamw_bf16_kernel<bf16_t><<<nblocks(n / 8, 256), 256, 0, st>>>(p, (bf16_t*)g, m, v, n, clip, (float)lr, (float)b1, (float)b2,
-                                                                   (float)eps, (float)wd, bc1, bc2s, zero_grad);
-  else
-    adamw_bf16_kernel<float><<<nblocks(n / 8, 256), 256, 0, st>>>(p, (float*)g, m, v, n, clip, (float)lr, (float)b1, (float)b2,
-                                                                  (float)eps, (float)wd, bc1, bc2s, zero_grad);
+  const SrKey k = sr_key(sr, step);
+  if (g_bf16) adamw_bf16_launch<bf16_t>(sr.on, p, (bf16_t*)g, m, v, n, clip, lr, b1, b2, eps, wd, bc1, bc2s, zero_grad, k, st);
+  else adamw_bf16_launch<float>(sr.on, p, (float*)g, m, v, n, clip, lr, b1, b2, eps, wd, bc1, bc2s, zero_grad, k, st);
   LAUNCH_RET();
 }
-static AdamHyper adam_hyper(double lr, double b1, double b2, double eps, double wd, int step, int zero_grad) {
+int sr_round_bf16(const float* x, bf16_t* y, size_t n, int64_t index0, uint64_t seed, int step, int which, hipStream_t st) {
+  if (n == 0) return 0;
+  AdamSR sr;
+  sr.on = 1; sr.seed = seed; sr.base = index0;
+  sr_round_bf16_kernel<<<nblocks(n, 256), 256, 0, st>>>(x, y, n, sr_key(sr, step), (uint32_t)which);
+  LAUNCH_RET();
+}
+static AdamHyper adam_hyper(double lr, double b1, double b2, double eps, double wd, int step, int zero_grad, const AdamSR& sr) {
   // bias corrections in double like torch.optim.AdamW (python floats), then fp32 in the kernel
   AdamHyper h;
   h.lr = (float)lr; h.b1 = (float)b1; h.b2 = (float)b2; h.eps = (float)eps; h.wd = (float)wd;
   h.bc1 = (float)(1.0 - pow(b1, (double)step));
   h.bc2_sqrt = (float)sqrt(1.0 - pow(b2, (double)step));
   h.zero_grad = zero_grad;
+  h.sr = sr_key(sr, step);
   return h;
 }
 template <int TC, typename GT>
-static void adamw_tiles_launch(int mode, dim3 grid, float* p, bf16_t* pb, bf16_t* pt, GT* g, void* m, void* v, int R, int C,
+static void adamw_tiles_launch(int mode, bool sr, dim3 grid, float* p, bf16_t* pb, bf16_t* pt, GT* g, void* m, void* v, int R, int C,
                                size_t batch_stride, const float* clip, const AdamHyper& h, hipStream_t st) {
-  if (mode == 0) adamw_tile_kernel<float, true, TC, GT><<<grid, 256, 0, st>>>(p, pb, pt, g, (float*)m, (float*)v, R, C, batch_stride, clip, h);
-  else if (mode == 1) adamw_tile_kernel<bf16_t, true, TC, GT><<<grid, 256, 0, st>>>(p, pb, pt, g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
-  else adamw_tile_kernel<bf16_t, false, TC, GT><<<grid, 256, 0, st>>>(p, pb, pt, g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
+  if (mode == 0) adamw_tile_kernel<float, true, TC, GT, false><<<grid, 256, 0, st>>>(p, pb, pt, g, (float*)m, (float*)v, R, C, batch_stride, clip, h);
+  else if (mode == 1 && sr) adamw_tile_kernel<bf16_t, true, TC, GT, true><<<grid, 256, 0, st>>>(p, pb, pt, g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
+  else if (mode == 1) adamw_tile_kernel<bf16_t, true, TC, GT, false><<<grid, 256, 0, st>>>(p, pb, pt, g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
+  else if (sr) adamw_tile_kernel<bf16_t, false, TC, GT, true><<<grid, 256, 0, st>>>(p, pb, pt, g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
+  else adamw_tile_kernel<bf16_t, false, TC, GT, false><<<grid, 256, 0, st>>>(p, pb, pt, g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
 }
 // mode 0: fp32 master + fp32 moments; 1: fp32 master + bf16 moments; 2: bf16 parameters + bf16 moments (no master)
 int adamw_tiles(int mode, float* p, bf16_t* pb, bf16_t* pt, void* g, int g_bf16, void* m, void* v, int R, int C, int batch,
                 size_t batch_stride, const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad,
-                hipStream_t st) {
+                const AdamSR& sr, hipStream_t st) {
   if ((R & 63) || (C & 63) || batch < 1 || mode < 0 || mode > 2) return -1;
-  const AdamHyper h = adam_hyper(lr, b1, b2, eps, wd, step, zero_grad);
+  const bool sr_on = sr.on && mode != 0;
+  if (sr_on && ((sr.base & 7) || (batch > 1 && (batch_stride & 7)))) return -1;
+  const AdamHyper h = adam_hyper(lr, b1, b2, eps, wd, step, zero_grad, sr);
   static int tile_cols = 128;  // SLAM_ADAMW_TILE_COLS=64: 256-byte row segments (A/B knob)
   static bool read_env = false;
   if (!read_env) { const char* e = getenv("SLAM_ADAMW_TILE_COLS"); if (e && atoi(e) == 64) tile_cols = 64; read_env = true; }
   static int x8 = -1;  // SLAM_ADAMW_X8=0: the 8-byte-access kernel for the all-bf16 case as well (A/B knob)
   if (x8 < 0) { const char* e = getenv("SLAM_ADAMW_X8"); x8 = !(e && e[0] == '0'); }
   if (tile_cols == 128 && (C % 128 == 0) && mode == 2 && g_bf16 && x8) {
-    adamw_tile_bf16x8_kernel<<<dim3(C / 128, R / 64, batch), 256, 0, st>>>(pb, pt, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
+    const dim3 grid(C / 128, R / 64, batch);
+    if (sr_on) adamw_tile_bf16x8_kernel<true><<<grid, 256, 0, st>>>(pb, pt, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
+    else adamw_tile_bf16x8_kernel<false><<<grid, 256, 0, st>>>(pb, pt, (const bf16_t*)g, (bf16_t*)m, (bf16_t*)v, R, C, batch_stride, clip, h);
   } else if (tile_cols == 128 && (C % 128 == 0)) {
     const dim3 grid(C / 128, R / 64, batch);
-    if (g_bf16) adamw_tiles_launch<128, bf16_t>(mode, grid, p, pb, pt, (bf16_t*)g, m, v, R, C, batch_stride, clip, h, st);
-    else adamw_tiles_launch<128, float>(mode, grid, p, pb, pt, (float*)g, m, v, R, C, batch_stride, clip, h, st);
+    if (g_bf16) adamw_tiles_launch<128, bf16_t>(mode, sr_on, grid, p, pb, pt, (bf16_t*)g, m, v, R, C, batch_stride, clip, h, st);
+    else adamw_tiles_launch<128, float>(mode, sr_on, grid, p, pb, pt, (float*)g, m, v, R, C, batch_stride, clip, h, st);
   } else {
     const dim3 grid(C / 64, R / 64, batch);
-    if (g_bf16) adamw_tiles_launch<64, bf16_t>(mode, grid, p, pb, pt, (bf16_t*)g, m, v, R, C, batch_stride, clip, h, st);
-    else adamw_tiles_launch<64, float>(mode, grid, p, pb, pt, (float*)g, m, v, R, C, batch_stride, clip, h, st);
+    if (g_bf16) adamw_tiles_launch<64, bf16_t>(mode, sr_on, grid, p, pb, pt, (bf16_t*)g, m, v, R, C, batch_stride, clip, h, st);
+    else adamw_tiles_launch<64, float>(mode, sr_on, grid, p, pb, pt, (float*)g, m, v, R, C, batch_stride, clip, h, st);
   }
   LAUNCH_RET();
 }
 template <typename GT>
-static void adamw_strided_launch(int mode, dim3 grid, float* p, bf16_t* pb, GT* g, void* m, void* v, size_t n, size_t stride,
+static void adamw_strided_launch(int mode, bool sr, dim3 grid, float* p, bf16_t* pb, GT* g, void* m, void* v, size_t n, size_t stride,
                                  const float* clip, const AdamHyper& h, hipStream_t st) {
-  if (mode == 0) adamw_strided_kernel<float, true, GT><<<grid, 256, 0, st>>>(p, pb, g, (float*)m, (float*)v, n, stride, clip, h);
-  else if (mode == 1) adamw_strided_kernel<bf16_t, true, GT><<<grid, 256, 0, st>>>(p, pb, g, (bf16_t*)m, (bf16_t*)v, n, stride, clip, h);
-  else adamw_strided_kernel<bf16_t, false, GT><<<grid, 256, 0, st>>>(p, pb, g, (bf16_t*)m, (bf16_t*)v, n, stride, clip, h);
+  if (mode == 0) adamw_strided_kernel<float, true, GT, false><<<grid, 256, 0, st>>>(p, pb, g, (float*)m, (float*)v, n, stride, clip, h);
+  else if (mode == 1 && sr) adamw_strided_kernel<bf16_t, true, GT, true><<<grid, 256, 0, st>>>(p, pb, g, (bf16_t*)m, (bf16_t*)v, n, stride, clip, h);
+  else if (mode == 1) adamw_strided_kernel<bf16_t, true, GT, false><<<grid, 256, 0, st>>>(p, pb, g, (bf16_t*)m, (bf16_t*)v, n, stride, clip, h);
+  else if (sr) adamw_strided_kernel<bf16_t, false, GT, true><<<grid, 256, 0, st>>>(p, pb, g, (bf16_t*)m, (bf16_t*)v, n, stride, clip, h);
+  else adamw_strided_kernel<bf16_t, false, GT, false><<<grid, 256, 0, st>>>(p, pb, g, (bf16_t*)m, (bf16_t*)v, n, stride, clip, h);
 }
 int adamw_strided(int mode, float* p, bf16_t* pb, void* g, int g_bf16, void* m, void* v, size_t n, int batch, size_t stride,
-                  const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad, hipStream_t st) {
+                  const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad, const AdamSR& sr,
+                  hipStream_t st) {
   if ((n & 3) || batch < 1 || mode < 0 || mode > 2) return -1;
   if (n == 0) return 0;
-  const AdamHyper h = adam_hyper(lr, b1, b2, eps, wd, step, zero_grad);
+  const bool sr_on = sr.on && mode != 0;
+  if (sr_on && ((sr.base & 3) || (batch > 1 && (stride & 3)))) return -1;  // a thread's 4 elements share one group of 8
+  const AdamHyper h = adam_hyper(lr, b1, b2, eps, wd, step, zero_grad, sr);
   const dim3 grid(nblocks(n / 4, 256), batch);
-  if (g_bf16) adamw_strided_launch<bf16_t>(mode, grid, p, pb, (bf16_t*)g, m, v, n, stride, clip, h, st);
-  else adamw_strided_launch<float>(mode, grid, p, pb, (float*)g, m, v, n, stride, clip, h, st);
+  if (g_bf16) adamw_strided_launch<bf16_t>(mode, sr_on, grid, p, pb, (bf16_t*)g, m, v, n, stride, clip, h, st);
+  else adamw_strided_launch<float>(mode, sr_on, grid, p, pb, (float*)g, m, v, n, stride, clip, h, st);
   LAUNCH_RET();
 }
 int transpose_bf16(const bf16_t* src, bf16_t* dst, int R, int C, int batch, size_t batch_stride, hipStream_t st) {

@@ -118,6 +118,11 @@ struct SlamEngine {
   bool gn_valid = false;        // ... and whether they describe the gradients the clip will see: not when that backward reported
                                 // buckets to a callback (data parallel: the norm is that of the EXCHANGED gradients, from chunk sums)
   int overlap_adamw = 0;
+  // "adamw_sr" / "adamw_sr_seed": the bf16 state stores of AdamW round stochastically (kernels.h AdamSR); stateless - the bits
+  // follow from the seed, the step the caller passes and the element's index in the flat buffer
+  int adamw_sr = 0;
+  uint64_t adamw_sr_seed = 0;
+  AdamSR sr_at(int64_t base) const { AdamSR s; s.on = adamw_sr; s.seed = adamw_sr_seed; s.base = base; return s; }
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_chunk;  // [0] embedding, [1 + l] layer l, [L + 1] final norm (+ an untied lm_head and its transposed image)
@@ -543,11 +548,12 @@ int adamw_model(SlamEngine* h, int mode, float* master, void* m, void* v, const 
   const size_t esz = mode == 0 ? 4 : 2;
   auto mat = [&](int64_t off, int R, int C, int batch) -> int {
     return adamw_tiles(mode, master ? master + off : nullptr, P + off, Pt + off, G + off * gsz, g16, (char*)m + off * esz,
-                       (char*)v + off * esz, R, C, batch, (size_t)h->layer_stride, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st);
+                       (char*)v + off * esz, R, C, batch, (size_t)h->layer_stride, norm_out, lr, b1, b2, eps, wd, step, zero_grad,
+                       h->sr_at(off), st);
   };
   auto vec = [&](int64_t off, size_t n, int batch) -> int {
     return adamw_strided(mode, master ? master + off : nullptr, P + off, G + off * gsz, g16, (char*)m + off * esz, (char*)v + off * esz, n,
-                         batch, (size_t)h->layer_stride, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st);
+                         batch, (size_t)h->layer_stride, norm_out, lr, b1, b2, eps, wd, step, zero_grad, h->sr_at(off), st);
   };
   int r = 0;
   if (chunk < 0 || chunk == 0) {
@@ -878,6 +884,12 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
     return SLAM_OK;
   }
   if (!strcmp(key, "overlap_adamw") && h) { h->overlap_adamw = value != 0; return SLAM_OK; }
+  if (!strcmp(key, "adamw_sr") && h) {
+    if (value < 0 || value > 1) return h->fail(SLAM_EINVAL, "value out of range for option adamw_sr (0 or 1)");
+    h->adamw_sr = (int)value;
+    return SLAM_OK;
+  }
+  if (!strcmp(key, "adamw_sr_seed") && h) { h->adamw_sr_seed = (uint64_t)value; return SLAM_OK; }
   if (!strcmp(key, "bwd_wgrad_stream") && h) { h->wgrad_stream = value != 0; return SLAM_OK; }
   if (!strcmp(key, "bwd_aux_side") && h) { h->aux_side = value != 0; return SLAM_OK; }
   if (!strcmp(key, "bwd_wgrad_cus") && h) { h->wside_cus = (int)value; return SLAM_OK; }
@@ -1435,8 +1447,10 @@ static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, c
       return SLAM_OK;
     }
     if (mode == 0) CK(adamw(master, h->params, G, g16, (float*)m, (float*)v, (size_t)h->n_params, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st));
-    else if (mode == 2) CK(adamw_bf16(h->params, G, g16, (bf16_t*)m, (bf16_t*)v, (size_t)h->n_params, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st));
-    else CK(adamw_strided(1, master, h->params, G, g16, m, v, (size_t)h->n_params, 1, 0, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st));
+    else if (mode == 2) CK(adamw_bf16(h->params, G, g16, (bf16_t*)m, (bf16_t*)v, (size_t)h->n_params, norm_out, lr, b1, b2, eps, wd, step, zero_grad,
+                                      h->sr_at(0), st));
+    else CK(adamw_strided(1, master, h->params, G, g16, m, v, (size_t)h->n_params, 1, 0, norm_out, lr, b1, b2, eps, wd, step, zero_grad,
+                          h->sr_at(0), st));
     return slam_refresh_transposed(h, stream);
   }
   // "overlap_adamw" (fp32 state): per-layer chunks on the engine's side stream; the next forward waits per layer
@@ -1541,7 +1555,7 @@ int slam_adamw_range_bf16_moments(SlamEngine* h, int64_t offset, int64_t count, 
   CK(join_optimizer(h, st));
   if (count)
     CK(adamw_strided(1, master, h->params + offset, range_grads(h, offset), h->gfinal == 2, m_bf16, v_bf16, (size_t)count, 1, 0, norm_out, lr, b1, b2,
-                     eps, wd, step, zero_grad, st));
+                     eps, wd, step, zero_grad, h->sr_at(offset), st));
   h->params_t_dirty = h->params_t != nullptr;
   return SLAM_OK;
 }
@@ -1556,7 +1570,7 @@ int slam_adamw_range_bf16(SlamEngine* h, int64_t offset, int64_t count, void* m_
   CK(join_optimizer(h, st));
   if (count)
     CK(adamw_bf16(h->params + offset, range_grads(h, offset), h->gfinal == 2, (bf16_t*)m_bf16, (bf16_t*)v_bf16, (size_t)count, norm_out, lr, b1, b2,
-                  eps, wd, step, zero_grad, st));
+                  eps, wd, step, zero_grad, h->sr_at(offset), st));
   h->params_t_dirty = h->params_t != nullptr;
   return SLAM_OK;
 }
@@ -2056,6 +2070,11 @@ size_t slam_op_embed_bwd_workspace(int M, int Vp) { return embed_bwd_workspace_i
 int slam_op_embed_bwd(const int64_t* ids, const void* dh, float* dE, int M, int H, int Vp, int V, int pad_id, void* ws,
                       slam_stream_t s) {
   return embed_bwd(ids, (const bf16_t*)dh, dE, M, H, Vp, V, pad_id, (int*)ws, (hipStream_t)s);
+}
+int slam_op_sr_round_bf16(const float* x, void* y_bf16, int64_t n, int64_t index0, int64_t seed, int32_t step, int32_t which,
+                          slam_stream_t s) {
+  if (!x || !y_bf16 || n < 0 || index0 < 0 || step < 1 || which < 0 || which > 2) return SLAM_EINVAL;
+  return sr_round_bf16(x, (bf16_t*)y_bf16, (size_t)n, index0, (uint64_t)seed, step, which, (hipStream_t)s);
 }
 
 }  // extern "C"

@@ -158,9 +158,15 @@ int grad_norm_from_chunks(const float* chunk_sums, size_t n_chunks, float max_no
 // g_bf16 (here and below): the gradients at g are bf16_t (the last backward kept its final values in bf16 only), else float
 int adamw(float* p, bf16_t* pb, void* g, int g_bf16, float* m, float* v, size_t n, const float* clip, double lr, double b1,
           double b2, double eps, double wd, int step, int zero_grad, hipStream_t st);
+// Stochastic rounding of the bf16 state stores ("adamw_sr"): the random bits of an element are a function of (seed, step, its
+// index in the engine's flat parameter buffer, which array) alone; base = that index for element 0 of the arrays handed over.
+// Rounded: m and v wherever they are bf16, p where the bf16 parameters are the state (mode 2). fp32 state (mode 0) ignores it.
+struct AdamSR { int on = 0; uint64_t seed = 0; int64_t base = 0; };
 // bf16 parameters and bf16 moments updated in place (fp32 arithmetic per element, no master copy)
 int adamw_bf16(bf16_t* p, void* g, int g_bf16, bf16_t* m, bf16_t* v, size_t n, const float* clip, double lr, double b1, double b2,
-               double eps, double wd, int step, int zero_grad, hipStream_t st);
+               double eps, double wd, int step, int zero_grad, const AdamSR& sr, hipStream_t st);
+// y[i] = the stochastic rounding of x[i] as the kernels above apply it to flat index index0 + i of array `which` (0 p, 1 m, 2 v)
+int sr_round_bf16(const float* x, bf16_t* y, size_t n, int64_t index0, uint64_t seed, int step, int which, hipStream_t st);
 int f32_to_bf16(const float* s, bf16_t* d, size_t n, hipStream_t st);
 // the same conversion, emitting one GradSink partial (sum of squares of the rounded values) per 8192-element block
 int f32_to_bf16_sumsq_slots(size_t n);
@@ -170,10 +176,11 @@ int bf16_to_f32(const bf16_t* s, float* d, size_t n, hipStream_t st);
 // image pt[C][R]; mode 0 = fp32 master + fp32 moments, 1 = fp32 master + bf16 moments, 2 = bf16 parameters + bf16 moments.
 int adamw_tiles(int mode, float* p, bf16_t* pb, bf16_t* pt, void* g, int g_bf16, void* m, void* v, int R, int C, int batch,
                 size_t batch_stride, const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad,
-                hipStream_t st);
+                const AdamSR& sr, hipStream_t st);
 // the same update on `batch` vectors of n elements at a constant stride (no transposed image)
 int adamw_strided(int mode, float* p, bf16_t* pb, void* g, int g_bf16, void* m, void* v, size_t n, int batch, size_t stride,
-                  const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad, hipStream_t st);
+                  const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad, const AdamSR& sr,
+                  hipStream_t st);
 int transpose_bf16(const bf16_t* src, bf16_t* dst, int R, int C, int batch, size_t batch_stride, hipStream_t st);
 int colsum_finish_many(const float* part, size_t part_stride, int nb, int N, float* out, size_t out_stride, int count,
                        int accumulate, hipStream_t st, bf16_t* img = nullptr,  // img: bf16 image of `out` (same indexing), nullable

@@ -146,6 +146,7 @@ def load_library(path: Optional[str] = None):
         "slam_op_cross_entropy": (C.c_int, [vp, vp, f64, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_embed_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_embed_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+        "slam_op_sr_round_bf16": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         if path is not None and not hasattr(lib, name):

@@ -53,6 +53,10 @@ class SLAMTrainer:
         osd = getattr(self.args, "optim_state_dtype", "float32") or "float32"
         if osd not in ("float32", "bfloat16", "float32_bf16_moments"):
             raise ValueError(f"optim_state_dtype must be float32, bfloat16 or float32_bf16_moments, got {osd!r}")
+        sr = bool(getattr(self.args, "optim_stochastic_rounding", False))
+        if sr and osd == "float32":  # (fields set after construction get past the arguments' own check)
+            raise ValueError("optim_stochastic_rounding needs bf16 optimizer state (optim_state_dtype bfloat16 or "
+                             "float32_bf16_moments): with float32 state nothing is rounded")
         # state_dtype = precision of the WEIGHT state (fp32 master or the bf16 parameters themselves); moment_dtype = Adam moments
         self.state_dtype = torch.bfloat16 if osd == "bfloat16" else torch.float32
         self.moment_dtype = torch.float32 if osd == "float32" else torch.bfloat16
@@ -107,6 +111,12 @@ class SLAMTrainer:
         # engine option: AdamW + weight-image refresh in per-layer chunks on the engine's side stream; slam_forward
         # waits per layer. Everything that reads the flat buffers with torch goes through UnitLM (which joins first).
         model.engine.set_option("overlap_adamw", 1 if getattr(args, "overlap_optimizer", False) else 0)
+        # stochastic rounding of the bf16 state stores: stateless, keyed on (seed, opt_step, element index) - every rank and
+        # every kernel form draws the same bits, and opt_step is in the checkpoint already
+        if sr:
+            sd = getattr(self.args, "optim_sr_seed", None)
+            model.engine.set_option("adamw_sr_seed", int(getattr(self.args, "seed", 0) if sd is None else sd))
+        model.engine.set_option("adamw_sr", 1 if sr else 0)
 
     # ---- reference hooks ------------------------------------------------------------------------
     def get_num_tokens(self, labels: torch.Tensor) -> int:

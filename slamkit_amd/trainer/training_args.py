@@ -35,6 +35,8 @@ class SLAMTrainingArguments:
     ddp_comm_dtype: Optional[str] = "bfloat16"     # gradient buckets cross xGMI in bf16 (the reference's DDP precision: its gradients are bf16; half the bytes); "float32": reduce the fp32 buffer in place
     ddp_algo: str = "all_reduce"                   # "all_reduce": every rank reduces and updates everything (torch DDP's scheme); "rs_ag": reduce-scatter gradients, AdamW on the owned 1/N shard, all-gather bf16 parameters under the next forward (dp.ShardedGradReducer)
     optim_state_dtype: str = "float32"             # "float32": fp32 master weights + fp32 Adam moments (30 B/param per step); "bfloat16": the recipe's own precision (slam.yaml:9) - bf16 parameters and moments updated in place, no master (16 B/param); "float32_bf16_moments": fp32 master + bf16 moments (22 B/param)
+    optim_stochastic_rounding: bool = False        # bf16 optimizer state is rounded stochastically instead of to nearest (engine option "adamw_sr"): updates below half an ulp of a bf16 weight or moment - most of them at the schedule's low-lr end - survive on average instead of vanishing; same bytes, same traffic. Needs bf16 state (optim_state_dtype bfloat16: p, m, v; float32_bf16_moments: m, v)
+    optim_sr_seed: Optional[int] = None            # seed of that rounding (engine option "adamw_sr_seed"); None = `seed`. The generator is stateless and keyed on the optimizer step: nothing goes into checkpoints, a resumed run repeats the uninterrupted one
     grad_dtype: Optional[str] = None               # precision the FINAL gradients of an optimizer step are kept in for the clip and AdamW: "bfloat16" = the reference's own (bf16 parameters have bf16 .grad, slam.yaml:9): the last backward stores them in bf16 only and emits the norm partials from the same stores; "float32"; None = bfloat16 with optim_state_dtype bfloat16, else float32. Micro-batches always accumulate in fp32
     grad_norm_from_backward: bool = True           # the clip's global norm from the sums of squares the last backward's final-value stores emit (no pass over the gradient buffer); False: the chunked norm pass - the summation order data-parallel runs use (they take the norm after the exchange), for bit-exact comparisons with them
     overwrite_first_grad: bool = True               # first backward of a step stores gradients (no zeroing pass); False = zero in AdamW
@@ -52,6 +54,15 @@ class SLAMTrainingArguments:
     torch_compile: bool = False
     report_to: list = field(default_factory=list)
     run_name: Optional[str] = None
+
+    def __post_init__(self):
+        if self.optim_stochastic_rounding and (self.optim_state_dtype or "float32") == "float32":
+            raise ValueError("optim_stochastic_rounding needs bf16 optimizer state (optim_state_dtype bfloat16 or "
+                             "float32_bf16_moments): with float32 state nothing is rounded")
+
+    def get_sr_seed(self) -> int:
+        """Seed of the stochastic rounding: optim_sr_seed, else `seed`."""
+        return int(self.seed if self.optim_sr_seed is None else self.optim_sr_seed)
 
     def get_recompute_level(self) -> int:
         """Engine recomputation level these arguments ask for (0 = off)."""

@@ -1,6 +1,7 @@
 """Three optimizer steps of the bench workload and nothing else (no timing events, no probes): the process that
 tools/pmc_step.sh wraps in rocprofv3 --pmc. Usage: python tools/one_step.py [slam358m|slam358m_packed|slam358m_padded|qwen1p5b]
-(slam358m_packed: the recipe's data mode - one flattened [1, 8192] row per micro-batch, GA 4 here; slam358m_padded: right-padded rows)"""
+(slam358m_packed: the recipe's data mode - one flattened [1, 8192] row per micro-batch, GA 4 here; slam358m_padded: right-padded rows;
+slam358m reads SLAM_OPTIM_STATE_DTYPE and SLAM_OPTIM_SR=1: stochastic rounding of the bf16 optimizer state)"""
 import os
 import sys
 
@@ -17,7 +18,8 @@ torch.cuda.set_device(0)
 if wl == "slam358m":
     model = UnitLM(UnitLMConfig(base_model_name="Qwen/Qwen2.5-0.5B", rope_theta=10000.0, vocab_size=bench.V, max_tokens=bench.B * bench.T), seed=0)
     tr = SLAMTrainer(model=model, args=SLAMTrainingArguments(per_device_train_batch_size=bench.B, learning_rate=1e-3, max_grad_norm=0.5, logging_steps=0,
-                                                          optim_state_dtype=os.environ.get("SLAM_OPTIM_STATE_DTYPE", "bfloat16")))
+                                                          optim_state_dtype=os.environ.get("SLAM_OPTIM_STATE_DTYPE", "bfloat16"),
+                                                          optim_stochastic_rounding=os.environ.get("SLAM_OPTIM_SR", "0") == "1"))
     n = float(bench.B * bench.T)
     for i in range(3):
         tr.optimizer_step([bench.synth_batch(0, i, dev)], 1e-3, counts=(n, n))
