@@ -224,3 +224,7 @@ SLAM_DEVICE uint2 lds_tr_read(const char* p) {
     hipError_t _e = (expr);                                     \
     if (_e != hipSuccess) return (int)_e;                       \
   } while (0)
+
+// host side of every launcher: blocks for n items at `per` a block; the launch's error as the return value
+inline unsigned nblocks(size_t n, int per) { return (unsigned)((n + per - 1) / per); }
+#define LAUNCH_RET() return (int)hipGetLastError()

@@ -122,7 +122,6 @@ struct SlamEngine {
   // follow from the seed, the step the caller passes and the element's index in the flat buffer
   int adamw_sr = 0;
   uint64_t adamw_sr_seed = 0;
-  AdamSR sr_at(int64_t base) const { AdamSR s; s.on = adamw_sr; s.seed = adamw_sr_seed; s.base = base; return s; }
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_chunk;  // [0] embedding, [1 + l] layer l, [L + 1] final norm (+ an untied lm_head and its transposed image)
@@ -531,51 +530,50 @@ int wait_params(SlamEngine* h, int64_t lo, int64_t hi, hipStream_t st) {
 }
 int join_params(SlamEngine* h, hipStream_t st) { return h->pwaits.empty() ? 0 : wait_params(h, 0, h->n_params, st); }
 
-// AdamW over the parameters [chunk c of the model]: c = 0 embedding, 1 + l = decoder layer l, L + 1 = final norm and, with an
-// untied head, lm_head (the tensors behind the layers; forward joins the last chunk before the head GEMM); c < 0 = all.
-// With transposed weight images bound, every matrix goes through the tile kernel that writes its transposed image in the
-// same pass (no separate transpose launch), the vectors between them through the strided kernel.
-// mode 0: fp32 master + fp32 moments, 1: fp32 master + bf16 moments, 2: bf16 parameters + bf16 moments.
-int adamw_model(SlamEngine* h, int mode, float* master, void* m, void* v, const float* norm_out, double lr, double b1, double b2,
-                double eps, double wd, int step, int zero_grad, int chunk, hipStream_t st) {
-  const SlamModelDesc& d = h->d;
-  const int L = d.n_layers, H = d.hidden;
-  bf16_t* P = h->params;
-  bf16_t* Pt = h->params_t;
-  const int g16 = h->gfinal == 2;  // the last backward kept its final values in bf16 only
-  char* G = g16 ? (char*)h->g16 : (char*)h->grads;
-  const size_t gsz = g16 ? 2 : 4;
-  const size_t esz = mode == 0 ? 4 : 2;
-  auto mat = [&](int64_t off, int R, int C, int batch) -> int {
-    return adamw_tiles(mode, master ? master + off : nullptr, P + off, Pt + off, G + off * gsz, g16, (char*)m + off * esz,
-                       (char*)v + off * esz, R, C, batch, (size_t)h->layer_stride, norm_out, lr, b1, b2, eps, wd, step, zero_grad,
-                       h->sr_at(off), st);
-  };
-  auto vec = [&](int64_t off, size_t n, int batch) -> int {
-    return adamw_strided(mode, master ? master + off : nullptr, P + off, G + off * gsz, g16, (char*)m + off * esz, (char*)v + off * esz, n,
-                         batch, (size_t)h->layer_stride, norm_out, lr, b1, b2, eps, wd, step, zero_grad, h->sr_at(off), st);
-  };
+// The parameter layout as the optimizer and the refresh of the transposed images walk it: fn(offset, rows, cols, batch) for
+// every group of `batch` same-shaped tensors at a stride of layer_stride; cols == 1: a vector of `rows` elements (no GEMM reads
+// a transposed image of one). Here the tensors of layers l0 .. l0 + nl, one group per tensor kind, in layer 0's layout order.
+template <typename F>
+int for_each_layer_tensor(SlamEngine* h, int l0, int nl, F&& fn) {
+  for (int ti : h->layer0) {
+    const SlamTensorInfo& t = h->tensors[ti];
+    if (int r = fn(t.offset + (int64_t)l0 * h->layer_stride, t.rows, (int)t.cols, nl)) return r;
+  }
+  return 0;
+}
+// chunk 0 = embedding (+ OPT's positions), 1 + l = decoder layer l, L + 1 = final norm (+ bias) and, with an untied head, lm_head
+// (the tensors behind the layers; forward joins the last chunk before the head GEMM); chunk < 0 = all, the layers as batches of L
+template <typename F>
+int for_each_param_group(SlamEngine* h, int chunk, F&& fn) {
+  const int L = h->d.n_layers, H = h->d.hidden;
   int r = 0;
-  if (chunk < 0 || chunk == 0) {
-    r = mat(h->off_embed, h->vpad, H, 1);
-    if (!r && h->arch == 1) r = vec(h->off_pos, (size_t)h->npos * H, 1);  // no transposed image: no GEMM reads one
+  if (chunk <= 0) {
+    r = fn(h->off_embed, h->vpad, H, 1);
+    if (!r && h->arch == 1) r = fn(h->off_pos, (int64_t)h->npos * H, 1, 1);
   }
-  if (r) return r;
-  const int l0 = chunk < 0 ? 0 : chunk - 1, nl = chunk < 0 ? L : 1;
-  if (chunk < 0 || (chunk >= 1 && chunk <= L)) {
-    // layer 0's tensors in layout order (matrices through the tile kernel, vectors through the strided one), at layer l0
-    for (int ti : h->layer0) {
-      const SlamTensorInfo& t = h->tensors[ti];
-      const int64_t off = t.offset + (int64_t)l0 * h->layer_stride;
-      if ((r = t.cols == 1 ? vec(off, (size_t)t.rows, nl) : mat(off, (int)t.rows, (int)t.cols, nl))) return r;
-    }
-  }
-  if (chunk < 0 || chunk == L + 1) {
-    r = vec(h->off_norm, (size_t)H, 1);
-    if (!r && h->arch == 1) r = vec(h->off_norm_b, (size_t)H, 1);
-    if (!r && h->untied) r = mat(h->off_head, h->vpad, H, 1);
+  if (!r && chunk < 0) r = for_each_layer_tensor(h, 0, L, fn);
+  if (!r && chunk >= 1 && chunk <= L) r = for_each_layer_tensor(h, chunk - 1, 1, fn);
+  if (!r && (chunk < 0 || chunk == L + 1)) {
+    r = fn(h->off_norm, H, 1, 1);
+    if (!r && h->arch == 1) r = fn(h->off_norm_b, H, 1, 1);
+    if (!r && h->untied) r = fn(h->off_head, h->vpad, H, 1);
   }
   return r;
+}
+// AdamW (`a`: the update at element 0 of the flat buffers) over a chunk of the model with transposed weight images bound:
+// every matrix goes through the tile kernel that writes its transposed image in the same pass (no separate transpose launch),
+// the vectors between them through the strided kernel.
+int adamw_model(SlamEngine* h, const AdamArgs& a, int chunk, hipStream_t st) {
+  return for_each_param_group(h, chunk, [&](int64_t off, int64_t rows, int cols, int batch) {
+    if (cols == 1) return adamw_strided(a.at(off), (size_t)rows, batch, (size_t)h->layer_stride, st);
+    return adamw_tiles(a.at(off), (int)rows, cols, batch, (size_t)h->layer_stride, st);
+  });
+}
+// the separate transpose pass as a visitor of the same walk: one launch per group of matrices, grid.z = batch
+auto transpose_group(SlamEngine* h, hipStream_t st) {
+  return [h, st](int64_t off, int64_t rows, int cols, int batch) {
+    return cols == 1 ? 0 : transpose_bf16(h->params + off, h->params_t + off, (int)rows, cols, batch, (size_t)h->layer_stride, st);
+  };
 }
 
 // K and V of layer l in the bound cache
@@ -818,20 +816,11 @@ int slam_refresh_transposed(SlamEngine* h, slam_stream_t stream) {
   CK(join_optimizer(h, st));
   CK(join_params(h, st));
   h->params_t_dirty = false;
-  const SlamModelDesc& d = h->d;
-  const bf16_t* P = h->params;
-  bf16_t* Pt = h->params_t;
-  const int H = d.hidden;
-  CK(transpose_bf16(P + h->off_embed, Pt + h->off_embed, h->vpad, H, 1, 0, st));
-  if (h->untied) CK(transpose_bf16(P + h->off_head, Pt + h->off_head, h->vpad, H, 1, 0, st));
-  // every layer has the same shapes at a constant stride: one launch per weight kind (layer 0's matrices in layout order),
-  // grid.z = layers
-  const int L = d.n_layers;
-  const size_t ls = (size_t)h->layer_stride;
-  for (int ti : h->layer0) {
-    const SlamTensorInfo& t = h->tensors[ti];
-    if (t.cols > 1) CK(transpose_bf16(P + t.offset, Pt + t.offset, (int)t.rows, (int)t.cols, L, ls, st));
-  }
+  // embedding and head, then every layer at once: the layers have the same shapes at a constant stride
+  const auto tr = transpose_group(h, st);
+  CK(for_each_param_group(h, 0, tr));
+  CK(for_each_param_group(h, h->d.n_layers + 1, tr));
+  CK(for_each_layer_tensor(h, 0, h->d.n_layers, tr));
   return SLAM_OK;
 }
 int slam_bind_params_t(SlamEngine* h, void* params_t_bf16) {
@@ -1426,6 +1415,23 @@ int slam_grad_norm(SlamEngine* h, float max_norm, float* norm_out, slam_stream_t
   return SLAM_OK;
 }
 
+// the update as the engine's state fixes it, at element 0 of the flat buffers (the gradients where the last backward left
+// them); the state arrays are the caller's
+static AdamArgs adam_args(SlamEngine* h, int mode, const float* norm_out, double lr, double b1, double b2, double eps, double wd,
+                          int step, int zero_grad) {
+  AdamArgs a;
+  a.mode = mode;
+  a.params = h->params;
+  a.params_t = h->params_t;
+  a.g_bf16 = h->gfinal == 2;  // the last backward kept its final values in bf16 only (slam_set_grad_image's buffer)
+  a.g = a.g_bf16 ? (void*)h->g16 : (void*)h->grads;
+  a.clip = norm_out;
+  a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps; a.wd = wd;
+  a.step = step; a.zero_grad = zero_grad;
+  a.sr.on = h->adamw_sr; a.sr.seed = h->adamw_sr_seed;
+  return a;
+}
+
 static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, const float* norm_out, double lr, double b1, double b2,
                      double eps, double wd, int32_t step, int32_t zero_grad, slam_stream_t stream) {
   if (!h || !m || !v || step < 1 || (mode != 2 && !master)) return SLAM_EINVAL;
@@ -1435,53 +1441,32 @@ static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, c
   CK(join_optimizer(h, st));
   CK(join_params(h, st));
   const bool fused = h->params_t != nullptr && h->fuse_adamw_t;
-  const int g16 = h->gfinal == 2;  // the last backward kept its final values in bf16 only (slam_set_grad_image's buffer)
-  char* const G = g16 ? (char*)h->g16 : (char*)h->grads;
-  const size_t gsz = g16 ? 2 : 4;
+  AdamArgs a = adam_args(h, mode, norm_out, lr, b1, b2, eps, wd, step, zero_grad);
+  a.master = master; a.m = m; a.v = v;
   // zeroing belongs to the fp32 accumulation buffer: the kernels cannot do it while they read the bf16 image
-  if (g16 && zero_grad) CK((int)hipMemsetAsync(h->grads, 0, (size_t)h->n_params * sizeof(float), st));
+  if (a.g_bf16 && zero_grad) CK((int)hipMemsetAsync(h->grads, 0, (size_t)h->n_params * sizeof(float), st));
   if (!h->overlap_adamw || mode != 0) {
     if (fused) {
-      CK(adamw_model(h, mode, master, m, v, norm_out, lr, b1, b2, eps, wd, step, zero_grad, -1, st));
+      CK(adamw_model(h, a, -1, st));
       h->params_t_dirty = false;
       return SLAM_OK;
     }
-    if (mode == 0) CK(adamw(master, h->params, G, g16, (float*)m, (float*)v, (size_t)h->n_params, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st));
-    else if (mode == 2) CK(adamw_bf16(h->params, G, g16, (bf16_t*)m, (bf16_t*)v, (size_t)h->n_params, norm_out, lr, b1, b2, eps, wd, step, zero_grad,
-                                      h->sr_at(0), st));
-    else CK(adamw_strided(1, master, h->params, G, g16, m, v, (size_t)h->n_params, 1, 0, norm_out, lr, b1, b2, eps, wd, step, zero_grad,
-                          h->sr_at(0), st));
+    CK(adamw_flat(a, (size_t)h->n_params, st));
     return slam_refresh_transposed(h, stream);
   }
   // "overlap_adamw" (fp32 state): per-layer chunks on the engine's side stream; the next forward waits per layer
   CK(ensure_side(h));
   CK((int)hipEventRecord(h->ev_fork, st));
   CK((int)hipStreamWaitEvent(h->side, h->ev_fork, 0));
-  const SlamModelDesc& d = h->d;
-  const int L = d.n_layers, H = d.hidden;
-  bf16_t* Pt = h->params_t;
+  const int L = h->d.n_layers;
   for (int c = 0; c < L + 2; ++c) {
     if (fused) {
-      CK(adamw_model(h, 0, master, m, v, norm_out, lr, b1, b2, eps, wd, step, zero_grad, c, h->side));
+      CK(adamw_model(h, a, c, h->side));
     } else {
       const int64_t lo = c == 0 ? 0 : c <= L ? h->lo[c - 1].ln1 : h->off_norm;
       const int64_t hi = c == 0 ? h->lo[0].ln1 : c < L ? h->lo[c].ln1 : c == L ? h->off_norm : h->n_params;
-      CK(adamw(master + lo, h->params + lo, G + lo * gsz, g16, (float*)m + lo, (float*)v + lo, (size_t)(hi - lo), norm_out, lr, b1, b2, eps, wd, step,
-               zero_grad, h->side));
-      if (Pt) {
-        const bf16_t* P = h->params;
-        if (c == 0) {
-          CK(transpose_bf16(P + h->off_embed, Pt + h->off_embed, h->vpad, H, 1, 0, h->side));
-        } else if (c <= L) {
-          for (int ti : h->layer0) {  // layer c - 1's matrices in layout order
-            const SlamTensorInfo& t = h->tensors[ti];
-            const int64_t off = t.offset + (int64_t)(c - 1) * h->layer_stride;
-            if (t.cols > 1) CK(transpose_bf16(P + off, Pt + off, (int)t.rows, (int)t.cols, 1, 0, h->side));
-          }
-        } else if (h->untied) {
-          CK(transpose_bf16(P + h->off_head, Pt + h->off_head, h->vpad, H, 1, 0, h->side));
-        }
-      }
+      CK(adamw_flat(a.at(lo), (size_t)(hi - lo), h->side));
+      if (h->params_t) CK(for_each_param_group(h, c, transpose_group(h, h->side)));
     }
     CK((int)hipEventRecord(h->ev_chunk[c], h->side));
   }
@@ -1508,11 +1493,6 @@ int slam_adamw_step_bf16(SlamEngine* h, void* exp_avg_bf16, void* exp_avg_sq_bf1
 // ---- sharded optimizer (data-parallel "rs_ag": reduce-scatter gradients, update the owned 1/N shard, all-gather bf16
 // parameters) ------------------------------------------------------------------------------------------------------
 int64_t slam_grad_chunk_elems(void) { return grad_chunk_elems(); }
-// element `offset` of the gradients, in the buffer the last backward left them in
-static void* range_grads(SlamEngine* h, int64_t offset) {
-  return h->gfinal == 2 ? (void*)(h->g16 + offset) : (void*)(h->grads + offset);
-}
-
 int slam_grad_sumsq_chunks(SlamEngine* h, int64_t offset, int64_t count, float* chunk_sums, slam_stream_t stream) {
   if (!h || !chunk_sums || offset < 0 || count < 0) return SLAM_EINVAL;
   if (!h->grads) return h->fail(SLAM_ESTATE, "no gradient buffer bound");
@@ -1531,48 +1511,40 @@ int slam_grad_norm_from_chunks(SlamEngine* h, const float* chunk_sums, float max
   return SLAM_OK;
 }
 
-int slam_adamw_range(SlamEngine* h, int64_t offset, int64_t count, float* master, float* m, float* v, const float* norm_out,
-                     double lr, double b1, double b2, double eps, double wd, int32_t step, int32_t zero_grad,
-                     slam_stream_t stream) {
-  if (!h || !master || !m || !v || step < 1 || offset < 0 || count < 0 || offset + count > h->n_params || (offset & 3) || (count & 3))
+// the three slam_adamw_range* entry points: elements [offset, offset + count) of the engine's buffers against the caller's
+// shard of the state, which starts at that element (master: NULL in mode 2). Mode 2 updates 8 elements per thread, the others 4.
+static int adamw_range_impl(SlamEngine* h, int mode, int64_t offset, int64_t count, float* master, void* m, void* v, const float* norm_out,
+                            double lr, double b1, double b2, double eps, double wd, int32_t step, int32_t zero_grad, slam_stream_t stream) {
+  const int64_t mask = mode == 2 ? 7 : 3;
+  if (!h || (mode != 2 && !master) || !m || !v || step < 1 || offset < 0 || count < 0 || offset + count > h->n_params || (offset & mask) ||
+      (count & mask))
     return SLAM_EINVAL;
   if (!h->grads || !h->params) return h->fail(SLAM_ESTATE, "bind params first");
   hipStream_t st = (hipStream_t)stream;
   CK(join_optimizer(h, st));
-  if (count)
-    CK(adamw(master, h->params + offset, range_grads(h, offset), h->gfinal == 2, m, v, (size_t)count, norm_out, lr, b1, b2, eps, wd, step, zero_grad, st));
+  AdamArgs a = adam_args(h, mode, norm_out, lr, b1, b2, eps, wd, step, zero_grad).at(offset);
+  a.master = master; a.m = m; a.v = v;
+  if (count) CK(adamw_flat(a, (size_t)count, st));
   h->params_t_dirty = h->params_t != nullptr;
   return SLAM_OK;
+}
+
+int slam_adamw_range(SlamEngine* h, int64_t offset, int64_t count, float* master, float* m, float* v, const float* norm_out,
+                     double lr, double b1, double b2, double eps, double wd, int32_t step, int32_t zero_grad,
+                     slam_stream_t stream) {
+  return adamw_range_impl(h, 0, offset, count, master, m, v, norm_out, lr, b1, b2, eps, wd, step, zero_grad, stream);
 }
 
 int slam_adamw_range_bf16_moments(SlamEngine* h, int64_t offset, int64_t count, float* master, void* m_bf16, void* v_bf16,
                                   const float* norm_out, double lr, double b1, double b2, double eps, double wd, int32_t step,
                                   int32_t zero_grad, slam_stream_t stream) {
-  if (!h || !master || !m_bf16 || !v_bf16 || step < 1 || offset < 0 || count < 0 || offset + count > h->n_params || (offset & 3) || (count & 3))
-    return SLAM_EINVAL;
-  if (!h->grads || !h->params) return h->fail(SLAM_ESTATE, "bind params first");
-  hipStream_t st = (hipStream_t)stream;
-  CK(join_optimizer(h, st));
-  if (count)
-    CK(adamw_strided(1, master, h->params + offset, range_grads(h, offset), h->gfinal == 2, m_bf16, v_bf16, (size_t)count, 1, 0, norm_out, lr, b1, b2,
-                     eps, wd, step, zero_grad, h->sr_at(offset), st));
-  h->params_t_dirty = h->params_t != nullptr;
-  return SLAM_OK;
+  return adamw_range_impl(h, 1, offset, count, master, m_bf16, v_bf16, norm_out, lr, b1, b2, eps, wd, step, zero_grad, stream);
 }
 
 int slam_adamw_range_bf16(SlamEngine* h, int64_t offset, int64_t count, void* m_bf16, void* v_bf16, const float* norm_out,
                           double lr, double b1, double b2, double eps, double wd, int32_t step, int32_t zero_grad,
                           slam_stream_t stream) {
-  if (!h || !m_bf16 || !v_bf16 || step < 1 || offset < 0 || count < 0 || offset + count > h->n_params || (offset & 7) || (count & 7))
-    return SLAM_EINVAL;
-  if (!h->grads || !h->params) return h->fail(SLAM_ESTATE, "bind params first");
-  hipStream_t st = (hipStream_t)stream;
-  CK(join_optimizer(h, st));
-  if (count)
-    CK(adamw_bf16(h->params + offset, range_grads(h, offset), h->gfinal == 2, (bf16_t*)m_bf16, (bf16_t*)v_bf16, (size_t)count, norm_out, lr, b1, b2,
-                  eps, wd, step, zero_grad, h->sr_at(offset), st));
-  h->params_t_dirty = h->params_t != nullptr;
-  return SLAM_OK;
+  return adamw_range_impl(h, 2, offset, count, nullptr, m_bf16, v_bf16, norm_out, lr, b1, b2, eps, wd, step, zero_grad, stream);
 }
 
 int slam_add_param_wait(SlamEngine* h, int64_t offset, int64_t count, void* event) {

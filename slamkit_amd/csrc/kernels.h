@@ -150,21 +150,48 @@ int seq_loglik(const float* row_loss, const int64_t* labels, int B, int T, float
 int copy_cols(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int M, int ncols, hipStream_t st);
 int scale_bf16(bf16_t* x, size_t n, float s, hipStream_t st);
 int scale_rows_bf16(bf16_t* x, const float* coef, int M, int T, int ncols, hipStream_t st);
-// part: (n + grad_chunk_elems() - 1) / grad_chunk_elems() floats
-int grad_norm(const float* g, size_t n, float max_norm, float* part, float* out, hipStream_t st);
 int grad_chunk_elems();
 int grad_sumsq_chunks(const void* g, int g_bf16, size_t n, size_t off, size_t cnt, float* chunk_sums, hipStream_t st);
 int grad_norm_from_chunks(const float* chunk_sums, size_t n_chunks, float max_norm, float* out, hipStream_t st);
-// g_bf16 (here and below): the gradients at g are bf16_t (the last backward kept its final values in bf16 only), else float
-int adamw(float* p, bf16_t* pb, void* g, int g_bf16, float* m, float* v, size_t n, const float* clip, double lr, double b1,
-          double b2, double eps, double wd, int step, int zero_grad, hipStream_t st);
 // Stochastic rounding of the bf16 state stores ("adamw_sr"): the random bits of an element are a function of (seed, step, its
 // index in the engine's flat parameter buffer, which array) alone; base = that index for element 0 of the arrays handed over.
 // Rounded: m and v wherever they are bf16, p where the bf16 parameters are the state (mode 2). fp32 state (mode 0) ignores it.
 struct AdamSR { int on = 0; uint64_t seed = 0; int64_t base = 0; };
-// bf16 parameters and bf16 moments updated in place (fp32 arithmetic per element, no master copy)
-int adamw_bf16(bf16_t* p, void* g, int g_bf16, bf16_t* m, bf16_t* v, size_t n, const float* clip, double lr, double b1, double b2,
-               double eps, double wd, int step, int zero_grad, const AdamSR& sr, hipStream_t st);
+// One AdamW update, from the engine's entry points down to the kernel launch: every pointer is at the same element.
+struct AdamArgs {
+  int mode = 0;                // 0 = fp32 master + fp32 moments, 1 = fp32 master + bf16 moments, 2 = bf16 parameters + bf16 moments
+  float* master = nullptr;     // nullable (mode 2: the bf16 parameters are the state, updated in place)
+  bf16_t* params = nullptr;    // the bf16 working copy
+  bf16_t* params_t = nullptr;  // nullable: the transposed weight images (adamw_tiles)
+  void* g = nullptr;           // gradients: float, or bf16_t when g_bf16 (the last backward kept its final values in bf16 only)
+  int g_bf16 = 0;
+  void* m = nullptr;           // moments: float in mode 0, else bf16_t
+  void* v = nullptr;
+  const float* clip = nullptr;  // nullable: slam_grad_norm's output (the gradients are scaled by clip[1])
+  double lr = 0, b1 = 0, b2 = 0, eps = 0, wd = 0;
+  int step = 1, zero_grad = 0;
+  AdamSR sr;
+  // the same update `off` elements further on
+  AdamArgs at(int64_t off) const {
+    AdamArgs a = *this;
+    const int64_t gsz = g_bf16 ? 2 : 4, esz = mode == 0 ? 4 : 2;
+    if (master) a.master = master + off;
+    if (params) a.params = params + off;
+    if (params_t) a.params_t = params_t + off;
+    if (g) a.g = (char*)g + off * gsz;
+    if (m) a.m = (char*)m + off * esz;
+    if (v) a.v = (char*)v + off * esz;
+    a.sr.base = sr.base + off;
+    return a;
+  }
+};
+// n consecutive elements. Mode 2 goes 8 elements per thread (n and, when rounding stochastically, sr.base multiples of 8),
+// modes 0 and 1 four (multiples of 4)
+int adamw_flat(const AdamArgs& a, size_t n, hipStream_t st);
+// `batch` vectors of n elements at a constant stride
+int adamw_strided(const AdamArgs& a, size_t n, int batch, size_t stride, hipStream_t st);
+// `batch` same-shaped [R][C] matrices (64-multiples) at a constant stride, ALSO writing the transposed bf16 image params_t[C][R]
+int adamw_tiles(const AdamArgs& a, int R, int C, int batch, size_t batch_stride, hipStream_t st);
 // y[i] = the stochastic rounding of x[i] as the kernels above apply it to flat index index0 + i of array `which` (0 p, 1 m, 2 v)
 int sr_round_bf16(const float* x, bf16_t* y, size_t n, int64_t index0, uint64_t seed, int step, int which, hipStream_t st);
 int f32_to_bf16(const float* s, bf16_t* d, size_t n, hipStream_t st);
@@ -172,15 +199,6 @@ int f32_to_bf16(const float* s, bf16_t* d, size_t n, hipStream_t st);
 int f32_to_bf16_sumsq_slots(size_t n);
 int f32_to_bf16_sumsq(const float* s, bf16_t* d, size_t n, float* sumsq, hipStream_t st);
 int bf16_to_f32(const bf16_t* s, float* d, size_t n, hipStream_t st);
-// AdamW over `batch` same-shaped [R][C] matrices (64-multiples) at a constant stride that ALSO writes the transposed bf16
-// image pt[C][R]; mode 0 = fp32 master + fp32 moments, 1 = fp32 master + bf16 moments, 2 = bf16 parameters + bf16 moments.
-int adamw_tiles(int mode, float* p, bf16_t* pb, bf16_t* pt, void* g, int g_bf16, void* m, void* v, int R, int C, int batch,
-                size_t batch_stride, const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad,
-                const AdamSR& sr, hipStream_t st);
-// the same update on `batch` vectors of n elements at a constant stride (no transposed image)
-int adamw_strided(int mode, float* p, bf16_t* pb, void* g, int g_bf16, void* m, void* v, size_t n, int batch, size_t stride,
-                  const float* clip, double lr, double b1, double b2, double eps, double wd, int step, int zero_grad, const AdamSR& sr,
-                  hipStream_t st);
 int transpose_bf16(const bf16_t* src, bf16_t* dst, int R, int C, int batch, size_t batch_stride, hipStream_t st);
 int colsum_finish_many(const float* part, size_t part_stride, int nb, int N, float* out, size_t out_stride, int count,
                        int accumulate, hipStream_t st, bf16_t* img = nullptr,  // img: bf16 image of `out` (same indexing), nullable
