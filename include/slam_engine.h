@@ -338,7 +338,32 @@ int slam_cast_params(SlamEngine* h, const float* master_f32, slam_stream_t strea
  * element j = index & 7 takes bits (w[j >> 1] >> 16 (j & 1)) & 0xffff of the four output words. Hence the result does not
  * depend on the kernel form ("fuse_adamw_t", the range entry points, how a sharded update splits the buffer), the stream or
  * the rank, and a run resumed at step k repeats the uninterrupted one. With 0 every bit is what it was without the option.
- * "adamw_sr_seed" = any int64 (default 0): the seed, read as 64 unsigned bits. */
+ * "adamw_sr_seed" = any int64 (default 0): the seed, read as 64 unsigned bits.
+ *
+ * "dropout_thr16" = 0 .. 65535 (default 0; anything else is SLAM_EINVAL, "out of range"; non-zero on a Qwen2 engine, arch 0, is
+ * SLAM_EINVAL too): residual dropout of the OPT family (HF OPTDecoderLayer, `config.dropout`): behind out_proj (site 0) and
+ * behind fc2 (site 1) of every layer, before the residual add. thr = round(p * 65536); q = thr / 65536 is the effective drop
+ * probability and scale = 1 / (1 - q), in fp32. NOTHING IS STORED: forward, backward and recomputation draw the mask again.
+ *   generator  Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (i8 & 0xffffffff, i8 >> 32, call,
+ *              2 * layer + site), i8 = (m * H + n) >> 3 with m the token's row in the [B * T] layout slam_forward is given
+ *              (padding rows included) and n the hidden column;
+ *   element    j = (m * H + n) & 7 takes r16 = (w[j >> 1] >> 16 (j & 1)) & 0xffff of the four output words (the mapping of
+ *              "adamw_sr"); it is DROPPED iff r16 < thr;
+ *   forward    out = bf16(resid + (keep ? y * scale : 0)): fp32 arithmetic, one rounding; y is the projection's bf16 output
+ *              with its bias; a dropped element is resid itself;
+ *   backward   d y = keep ? d out * scale : 0 (rounded to bf16 once, like every gradient between two kernels); the residual
+ *              branch and the LayerNorm backward above it keep the unmasked d out.
+ * The workspace layout depends only on whether the value is non-zero: at 0 slam_workspace_bytes answers what it answered
+ * without the option, otherwise four [max_tokens][hidden] bf16 buffers more (the masked gradients of two layers in flight).
+ * Changing between zero and non-zero while a workspace is bound unbinds it, exactly as "recompute" does; changing between two
+ * non-zero values does not. A backward always uses the threshold, seed and call its own forward ran with.
+ * "dropout_seed" = any int64 (default 0): the seed, read as 64 unsigned bits.
+ * "dropout_call_next" = 0 .. 2^32 - 1: arms dropout for the NEXT slam_forward only, with this call number, and resets itself
+ * (a forward that is refused uses it up as well). That forward remembers (thr, seed, call) for its own slam_backward, the
+ * re-run launches of "recompute" included. A forward that was not armed applies no dropout - evaluation, scoring,
+ * slam_prefill and slam_decode_step never see it - and its launches are those of an engine without the option. Ignored while
+ * "dropout_thr16" is 0. The mask depends on nothing else: not on the stream, the recompute level, "bwd_wgrad_stream" or the
+ * rank, so a caller that numbers its forwards (optimizer step x accumulation steps + micro-batch) repeats a run exactly. */
 int slam_set_option(SlamEngine* h, const char* key, int64_t value);
 
 /* ---- single-op entry points (parity tests call each kernel through the ABI) -------------------*/
@@ -432,6 +457,15 @@ int slam_op_embed_bwd(const int64_t* ids, const void* dh /* bf16 [M][H] */, floa
  * 2 v) at optimizer step `step` (>= 1) under `seed`: what the AdamW kernels apply to their state stores, on its own. */
 int slam_op_sr_round_bf16(const float* x, void* y_bf16, int64_t n, int64_t index0, int64_t seed, int32_t step, int32_t which,
                           slam_stream_t s);
+/* The two kernels of "dropout_thr16" on their own, on bf16 [M][H] (H a multiple of 8): the mask of element (m, n) is the one
+ * the option's text defines for flat index index0 + m * H + n (index0 >= 0, a multiple of 8; the engine passes 0), call number
+ * `call` (0 .. 2^32 - 1) and stream_id = 2 * layer + site. slam_op_dropout_add, in place: y = bf16(resid + (keep ? y * scale :
+ * 0)); slam_op_dropout_bwd: dy_masked = keep ? bf16(dy * scale) : 0, dy itself untouched (another buffer). thr16 = 0 keeps
+ * everything at scale 1. */
+int slam_op_dropout_add(void* y, const void* resid, int M, int H, int32_t thr16, int64_t seed, int64_t call, int32_t stream_id,
+                        int64_t index0, slam_stream_t s);
+int slam_op_dropout_bwd(const void* dy, void* dy_masked, int M, int H, int32_t thr16, int64_t seed, int64_t call, int32_t stream_id,
+                        int64_t index0, slam_stream_t s);
 
 #ifdef __cplusplus
 }

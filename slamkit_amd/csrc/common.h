@@ -84,6 +84,23 @@ SLAM_DEVICE uint2 sr_pack_bf16x4(const float* f, const SrKey& k, uint64_t gi, ui
   return v;
 }
 
+// ---- residual dropout ("dropout_thr16") -----------------------------------------------------------
+// The mask of one dropout site is a function of (seed, call, site id, flat element index) alone - nothing is stored: forward,
+// backward and recomputation draw it again. The same generator and the same element -> 16 bits mapping as sr_bits8 / sr_r16,
+// with the forward's call number where the optimizer has its step and the site id (2 * layer + site) where it has the array.
+struct DropKey { uint32_t k0, k1, call, site, thr; float scale; uint64_t base; };  // base: flat index of element 0 (a multiple of 8)
+SLAM_DEVICE Philox4 drop_bits8(const DropKey& k, uint64_t i8) {
+  return philox4x32_10((uint32_t)i8, (uint32_t)(i8 >> 32), k.call, k.site, k.k0, k.k1);
+}
+// bit j of the result: element j of the eight is KEPT (r16 >= thr)
+SLAM_DEVICE uint32_t drop_keep8(const DropKey& k, uint64_t i8) {
+  const Philox4 b = drop_bits8(k, i8);
+  uint32_t keep = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) keep |= (sr_r16(b, j) >= k.thr ? 1u : 0u) << j;
+  return keep;
+}
+
 // raw v_exp_f32 (2^x): no denormal-range fix-up code (arguments here are <= 0 or moderate)
 SLAM_DEVICE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 

@@ -593,6 +593,39 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(bf16_t* __restrict__ d, c
   reinterpret_cast<uint4*>(d)[i] = v;
 }
 
+// Residual dropout (OPT, "dropout_thr16"): 8 bf16 per lane and iteration - two 16-byte loads, one Philox call, one 16-byte
+// store - grid-stride, no LDS. Forward, in place on y: y = bf16(resid + (keep ? y * scale : 0)), one rounding; a dropped
+// element takes resid's own bits.
+__global__ __launch_bounds__(256) void dropout_add_kernel(bf16_t* __restrict__ y, const bf16_t* __restrict__ resid, size_t n8,
+                                                          DropKey k) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
+    const uint4 yv = reinterpret_cast<const uint4*>(y)[i];
+    const uint4 rv = reinterpret_cast<const uint4*>(resid)[i];
+    const uint32_t keep = drop_keep8(k, (k.base >> 3) + i);
+    float yf[8], rf[8];
+    unpack_bf16x8(yv, yf);
+    unpack_bf16x8(rv, rf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rf[j] = (keep >> j) & 1u ? rf[j] + yf[j] * k.scale : rf[j];
+    reinterpret_cast<uint4*>(y)[i] = pack_bf16x8(rf);
+  }
+}
+// Backward: dm = keep ? bf16(dy * scale) : 0 into a second buffer; dy stays what it was (the residual branch's gradient)
+__global__ __launch_bounds__(256) void dropout_bwd_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dm, size_t n8,
+                                                          DropKey k) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
+    const uint4 dv = reinterpret_cast<const uint4*>(dy)[i];
+    const uint32_t keep = drop_keep8(k, (k.base >> 3) + i);
+    float f[8];
+    unpack_bf16x8(dv, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] = (keep >> j) & 1u ? f[j] * k.scale : 0.f;
+    reinterpret_cast<uint4*>(dm)[i] = pack_bf16x8(f);
+  }
+}
+
 // One-hot rows for the gather-side embedding gradient (dE += onehot^T dh0 runs on the wgrad GEMM,
 // deterministic); the padding_idx column is suppressed like nn.Embedding(padding_idx).
 __global__ __launch_bounds__(256) void onehot_kernel(const int64_t* __restrict__ ids, bf16_t* __restrict__ oh,
@@ -1047,6 +1080,34 @@ int embed_pos_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const
 int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st) {
   if (n & 7) return -1;
   relu_bwd_kernel<<<nblocks(n / 8, 256), 256, 0, st>>>(d, act, n / 8);
+  LAUNCH_RET();
+}
+// thr16 = round(p * 65536): q = thr16 / 65536 is the drop probability, the kept values are scaled by 1 / (1 - q) (fp32)
+static DropKey drop_key(const DropSite& d) {
+  DropKey k;
+  k.k0 = (uint32_t)d.seed; k.k1 = (uint32_t)(d.seed >> 32);
+  k.call = d.call; k.site = d.site; k.thr = (uint32_t)d.thr16;
+  k.scale = 1.0f / (1.0f - (float)d.thr16 / 65536.0f);
+  k.base = (uint64_t)d.index0;
+  return k;
+}
+// memory-bound: about 8 blocks per CU's worth of grid at most, the rest by the stride - with the grid chosen so that every
+// block runs the same number of iterations (3072 blocks of work are 1536 x 2, not 2048 of which half run twice)
+static unsigned dropout_grid(size_t n8) {
+  const size_t b = nblocks(n8, 256);
+  const size_t iters = (b + 2047) / 2048;
+  return (unsigned)((b + iters - 1) / iters);
+}
+int dropout_add(bf16_t* y, const bf16_t* resid, int M, int H, const DropSite& d, hipStream_t st) {
+  if (M <= 0 || H <= 0 || (H & 7) || (d.index0 & 7) || d.index0 < 0 || d.thr16 < 0 || d.thr16 > 65535) return -1;
+  const size_t n8 = (size_t)M * H / 8;
+  dropout_add_kernel<<<dropout_grid(n8), 256, 0, st>>>(y, resid, n8, drop_key(d));
+  LAUNCH_RET();
+}
+int dropout_bwd(const bf16_t* dy, bf16_t* dm, int M, int H, const DropSite& d, hipStream_t st) {
+  if (M <= 0 || H <= 0 || (H & 7) || (d.index0 & 7) || d.index0 < 0 || d.thr16 < 0 || d.thr16 > 65535) return -1;
+  const size_t n8 = (size_t)M * H / 8;
+  dropout_bwd_kernel<<<dropout_grid(n8), 256, 0, st>>>(dy, dm, n8, drop_key(d));
   LAUNCH_RET();
 }
 int onehot(const int64_t* ids, bf16_t* oh, int M, int Vp, int V, int pad_id, hipStream_t st) {

@@ -169,12 +169,24 @@ struct SlamEngine {
   // min(L, 3) shared slots and are rebuilt in backward, 2 the whole LayerAct does and backward re-runs the layer's forward
   int recompute = 0;
   std::vector<hipEvent_t> ev_rc;  // per layer: "the weight-gradient stream is done with layer l" (orders the slot re-use)
+  // Residual dropout (OPT; see slam_set_option in the header). "dropout_call_next" arms the NEXT slam_forward only; that forward
+  // copies (thr, seed, call) into fwd_drop for its own backward and recomputation. Nothing of the mask is stored.
+  int dropout_thr16 = 0;
+  uint64_t dropout_seed = 0;
+  int64_t dropout_call_next = -1;  // -1: not armed
+  bool fwd_drop = false;           // the last slam_forward applied dropout ...
+  DropSite fwd_site;               // ... with these (site and index0 filled per launch)
+  // backward's masked copies of the residual gradients, [layer parity][site] x [M][H]: the weight-gradient stream reads layer
+  // l's after the caller's stream has moved on, so layer l - 2 waits for ev_dm[l] before it overwrites them
+  bf16_t* dmask[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  std::vector<hipEvent_t> ev_dm;   // per layer: "the weight-gradient stream is done with layer l's masked gradients"
 
   ~SlamEngine() {
     if (wside) { (void)hipStreamSynchronize(wside); (void)hipStreamDestroy(wside); }
     for (hipEvent_t e : fam_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_w) (void)hipEventDestroy(e);
     for (hipEvent_t e : ev_rc) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ev_dm) (void)hipEventDestroy(e);
     if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
@@ -356,6 +368,9 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
     e->gn_part = c.take<float>(e->gn_cap);
   }
   e->scal = c.take<float>(64);
+  // "dropout_thr16" != 0: the masked residual gradients, behind everything else (the layout above is the same with and without)
+  for (int p = 0; p < 2; ++p)
+    for (int s = 0; s < 2; ++s) e->dmask[p][s] = e->dropout_thr16 ? c.take<bf16_t>(M * H) : nullptr;
   return (c.off + 255) & ~(size_t)255;
 }
 
@@ -611,10 +626,26 @@ int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
   }
   TK(F_ATTN_FWD, st, attn_fwd(a.qkv, a.o, a.lse, h->cur_seg_s, h->attn_plan_buf, h->attn_tune, M, nH, nKV, d.head_dim, st));
   if (opt) {  // out_proj bias + residual, LayerNorm, fc1 bias + ReLU, fc2 bias + residual
-    TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, P + o.bo, h->hs[l], M, H, nH * d.head_dim, st));
+    // residual dropout (armed forward): the two projections write bias only, the mask and the residual follow in one pass
+    // (site 0 behind out_proj, 1 behind fc2). A re-run draws the forward's own mask again from the call that forward remembered.
+    const bool drop = h->fwd_drop;
+    DropSite ds = h->fwd_site;
+    ds.site = 2u * (uint32_t)l;
+    {
+      const int slot = fam_begin(h, F_O_FWD, st);
+      CK(gemm_nt(a.o, P + o.wo, a.hmid, P + o.bo, drop ? nullptr : h->hs[l], M, H, nH * d.head_dim, st));
+      if (drop) CK(dropout_add(a.hmid, h->hs[l], M, H, ds, st));
+      fam_end(h, slot, st);
+    }
     TK(F_NORM_FWD, st, layernorm_fwd(a.hmid, P + o.ln2, P + o.ln2_b, a.x2, a.mu2, a.rstd2, M, H, d.rms_eps, st));
     TK(F_GATEUP_FWD, st, gemm_nt_relu(a.x2, P + o.wgu, a.act, P + o.b1, M, I, H, st));
-    if (!rerun) TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], P + o.b2, a.hmid, M, H, I, st));
+    if (!rerun) {
+      ds.site += 1;
+      const int slot = fam_begin(h, F_DOWN_FWD, st);
+      CK(gemm_nt(a.act, P + o.wd, h->hs[l + 1], P + o.b2, drop ? nullptr : a.hmid, M, H, I, st));
+      if (drop) CK(dropout_add(h->hs[l + 1], a.hmid, M, H, ds, st));
+      fam_end(h, slot, st);
+    }
     return SLAM_OK;
   }
   TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, nullptr, h->hs[l], M, H, nH * d.head_dim, st));
@@ -843,6 +874,7 @@ size_t slam_workspace_bytes(SlamEngine* h, int64_t max_tokens) {
   tmp.untied = h->untied;
   tmp.n_params = h->n_params;
   tmp.recompute = h->recompute;
+  tmp.dropout_thr16 = h->dropout_thr16;
   return carve(&tmp, nullptr, max_tokens);
 }
 int slam_bind_workspace(SlamEngine* h, void* ws, size_t bytes, int64_t max_tokens) {
@@ -912,6 +944,26 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
     }
     return SLAM_OK;
   }
+  if (!strcmp(key, "dropout_thr16") && h) {
+    if (value < 0 || value > 65535) return h->fail(SLAM_EINVAL, "value out of range for option dropout_thr16 (0 .. 65535)");
+    if (value != 0 && h->arch != 1) return h->fail(SLAM_EINVAL, "dropout_thr16: residual dropout exists for the OPT family only");
+    if ((value != 0) != (h->dropout_thr16 != 0)) {  // the masked-gradient buffers come or go: the bound workspace no longer fits
+      h->ws = nullptr;
+      h->ws_bytes = 0;
+      h->max_tokens = 0;
+      h->have_fwd = h->have_loss = false;
+      h->kv_ready = false;
+    }
+    h->dropout_thr16 = (int)value;
+    if (!value) h->dropout_call_next = -1;
+    return SLAM_OK;
+  }
+  if (!strcmp(key, "dropout_seed") && h) { h->dropout_seed = (uint64_t)value; return SLAM_OK; }
+  if (!strcmp(key, "dropout_call_next") && h) {
+    if (value < 0 || value > 0xffffffffLL) return h->fail(SLAM_EINVAL, "value out of range for option dropout_call_next (0 .. 2^32 - 1)");
+    if (h->dropout_thr16) h->dropout_call_next = value;  // ignored while dropout is off
+    return SLAM_OK;
+  }
   if (!strcmp(key, "fuse_swiglu") && h) { h->fuse_swiglu = value != 0; return SLAM_OK; }
   if (!strcmp(key, "fuse_dswiglu") && h) { h->fuse_dswiglu = value != 0; return SLAM_OK; }
   if (!strcmp(key, "fuse_adamw_t") && h) { h->fuse_adamw_t = value != 0; return SLAM_OK; }
@@ -921,7 +973,11 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
 int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int64_t* position_ids,
                  const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
                  float* loss_out, void* logits_out, slam_stream_t stream) {
-  if (!h || !ids || B <= 0 || T <= 0) return SLAM_EINVAL;
+  if (!h) return SLAM_EINVAL;
+  // "dropout_call_next" arms this call and no other: a refused forward uses it up too, so no later one inherits it
+  const int64_t armed_call = h->dropout_call_next;
+  h->dropout_call_next = -1;
+  if (!ids || B <= 0 || T <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   const int64_t M64 = (int64_t)B * T;
   if (M64 > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
@@ -933,6 +989,14 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
   const int H = d.hidden, L = d.n_layers;
   const bf16_t* P = h->params;
   h->have_fwd = false;
+  // "dropout_call_next" armed this forward and no other: whatever happens below, the next one starts unarmed
+  h->fwd_drop = h->arch == 1 && h->dropout_thr16 > 0 && armed_call >= 0;
+  if (h->fwd_drop) {
+    h->fwd_site = DropSite();
+    h->fwd_site.thr16 = h->dropout_thr16;
+    h->fwd_site.seed = h->dropout_seed;
+    h->fwd_site.call = (uint32_t)armed_call;
+  }
   GemmTuneScope tune_scope(&h->gemm_tune);
   CK(forward_layers(h, ids, position_ids, seg_start, seg_end, M, T, st));
   if (h->arch == 1) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[L], P + h->off_norm, P + h->off_norm_b, h->hf, h->muf, h->rstdf, M, H, d.rms_eps, st));
@@ -995,6 +1059,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   const int H = d.hidden, L = d.n_layers, M = B * T;
   const bf16_t* P = h->params;
   h->have_fwd = false;
+  h->fwd_drop = false;  // generation never drops
   h->kv_ready = false;
   GemmTuneScope tune_scope(&h->gemm_tune);
   // "recompute" = 2 with more layers than slots: the layers share their q|k|v buffers, so each layer's K / V leave inside the loop
@@ -1214,6 +1279,21 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
   // the weight-gradient stream has everything of layer l that reads a shared slot
   auto slot_done = [&](int l) -> int { return slot_edges && l >= RC_SLOTS - 1 ? (int)hipEventRecord(h->ev_rc[(size_t)l], ws) : 0; };
 
+  // residual dropout: this backward belongs to a forward that dropped. The masked copies live in two buffer pairs by layer
+  // parity; on the weight-gradient stream layer l's last reader is its Wo gradient, which layer l - 2 waits for (ev_dm[l])
+  const bool drop = opt && h->fwd_drop;
+  if (drop && !h->dmask[0][0]) return h->fail(SLAM_ESTATE, "dropout: the bound workspace has no masked-gradient buffers");
+  if (drop && two && h->ev_dm.empty()) {
+    h->ev_dm.resize((size_t)L);
+    for (auto& ev : h->ev_dm)
+      if (hipEventCreateWithFlags(&ev, sync_event_flags()) != hipSuccess) { h->ev_dm.clear(); return h->fail(SLAM_ESTATE, "hipEventCreate failed"); }
+  }
+  auto masked = [&](const bf16_t* dy, bf16_t* dm, int l, int site) -> int {
+    DropSite ds = h->fwd_site;
+    ds.site = 2u * (uint32_t)l + (uint32_t)site;
+    return dropout_bwd(dy, dm, M, H, ds, st);
+  };
+
   const int bl = bucket_layers > 0 ? bucket_layers : L;
   int64_t bucket_end = h->n_params;  // exclusive end of the not-yet-reported range
   int fin_hi = L;                    // layers >= fin_hi have their norm/bias partial slabs finished
@@ -1227,14 +1307,22 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
       // MLP: fc2 (bias + residual), ReLU, fc1 (bias); d(act) goes to this layer's own gu buffer, which nothing overwrites before
       // the next forward (the fc1 weight gradient and the b1 column sums read it on the weight-gradient stream)
       bf16_t* dact = a.gu;
-      CK(bias_cols(dh, H, h->b2_part + (size_t)l * h->hb_ps));
-      CK(wgrad(F_WD_WGRAD, dh, a.act, G + o.wd, H, I, img(o.wd), true, aux));
+      // residual dropout: what flows into fc2 / out_proj is the masked, rescaled copy of the residual gradient; the LayerNorm
+      // backward below keeps reading the unmasked dh / dh2 as the residual branch's share
+      const bf16_t* dhm = dh;
+      if (drop) {
+        if (two && l + 2 < L) CK((int)hipStreamWaitEvent(st, h->ev_dm[(size_t)l + 2], 0));  // a whole layer old by now
+        CK(masked(dh, h->dmask[l & 1][1], l, 1));
+        dhm = h->dmask[l & 1][1];
+      }
+      CK(bias_cols(dhm, H, h->b2_part + (size_t)l * h->hb_ps));
+      CK(wgrad(F_WD_WGRAD, dhm, a.act, G + o.wd, H, I, img(o.wd), true, aux));
       {
         const int slot = fam_begin(h, F_DOWN_DGRAD, st);
         if (Pt) {
-          CK(gemm_nt_drelu(dh, Pt + o.wd, dact, a.act, M, I, H, st));  // the ReLU backward in the dgrad epilogue
+          CK(gemm_nt_drelu(dhm, Pt + o.wd, dact, a.act, M, I, H, st));  // the ReLU backward in the dgrad epilogue
         } else {
-          CK(dgrad(dh, o.wd, dact, H, I));
+          CK(dgrad(dhm, o.wd, dact, H, I));
           CK(relu_bwd(dact, a.act, (size_t)M * I, st));
         }
         fam_end(h, slot, st);
@@ -1245,9 +1333,15 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
       TK(F_NORM_BWD, st, layernorm_bwd(h->dx, a.hmid, P + o.ln2, a.mu2, a.rstd2, dh, dh2, h->ln_part + (size_t)(2 * l + 1) * h->ln_ps,
                                        h->lnb_part + (size_t)(2 * l + 1) * h->ln_ps, M, H, st));
       // attention: out_proj (bias + residual), then the same attention backward as Qwen2 (identity rotation tables)
-      CK(bias_cols(dh2, H, h->bo_part + (size_t)l * h->hb_ps));
-      CK(wgrad(F_WO_WGRAD, dh2, a.o, G + o.wo, H, HD, img(o.wo), true, aux));
-      TK(F_O_DGRAD, st, dgrad(dh2, o.wo, h->d_o, H, HD));
+      const bf16_t* dh2m = dh2;
+      if (drop) {
+        CK(masked(dh2, h->dmask[l & 1][0], l, 0));
+        dh2m = h->dmask[l & 1][0];
+      }
+      CK(bias_cols(dh2m, H, h->bo_part + (size_t)l * h->hb_ps));
+      CK(wgrad(F_WO_WGRAD, dh2m, a.o, G + o.wo, H, HD, img(o.wo), true, aux));
+      if (drop && two) CK((int)hipEventRecord(h->ev_dm[(size_t)l], ws));  // the last reader of this layer's masked copies on ws
+      TK(F_O_DGRAD, st, dgrad(dh2m, o.wo, h->d_o, H, HD));
       TK(F_ATTN_BWD, st, attn_bwd(a.qkv, a.o, h->d_o, a.lse, h->dsum, h->nlse, dqkv, h->dkv_part, h->cur_seg_s, h->cur_seg_e, h->attn_plan_buf, h->attn_tune, h->cosb, h->sinb,
                   M, nH, nKV, d.head_dim, st));
       CK(bias_cols(dqkv, h->QKV, h->bias_part + (size_t)l * h->bias_ps));
@@ -2047,6 +2141,31 @@ int slam_op_sr_round_bf16(const float* x, void* y_bf16, int64_t n, int64_t index
                           slam_stream_t s) {
   if (!x || !y_bf16 || n < 0 || index0 < 0 || step < 1 || which < 0 || which > 2) return SLAM_EINVAL;
   return sr_round_bf16(x, (bf16_t*)y_bf16, (size_t)n, index0, (uint64_t)seed, step, which, (hipStream_t)s);
+}
+
+static bool drop_site_ok(int M, int H, int32_t thr16, int64_t call, int32_t stream_id, int64_t index0, DropSite* d) {
+  if (M <= 0 || H <= 0 || (H & 7) || thr16 < 0 || thr16 > 65535 || call < 0 || call > 0xffffffffLL || stream_id < 0 || index0 < 0 ||
+      (index0 & 7))
+    return false;
+  d->thr16 = thr16;
+  d->call = (uint32_t)call;
+  d->site = (uint32_t)stream_id;
+  d->index0 = index0;
+  return true;
+}
+int slam_op_dropout_add(void* y, const void* resid, int M, int H, int32_t thr16, int64_t seed, int64_t call, int32_t stream_id,
+                        int64_t index0, slam_stream_t s) {
+  DropSite d;
+  if (!y || !resid || !drop_site_ok(M, H, thr16, call, stream_id, index0, &d)) return SLAM_EINVAL;
+  d.seed = (uint64_t)seed;
+  return dropout_add((bf16_t*)y, (const bf16_t*)resid, M, H, d, (hipStream_t)s);
+}
+int slam_op_dropout_bwd(const void* dy, void* dy_masked, int M, int H, int32_t thr16, int64_t seed, int64_t call, int32_t stream_id,
+                        int64_t index0, slam_stream_t s) {
+  DropSite d;
+  if (!dy || !dy_masked || dy == dy_masked || !drop_site_ok(M, H, thr16, call, stream_id, index0, &d)) return SLAM_EINVAL;
+  d.seed = (uint64_t)seed;
+  return dropout_bwd((const bf16_t*)dy, (bf16_t*)dy_masked, M, H, d, (hipStream_t)s);
 }
 
 }  // extern "C"

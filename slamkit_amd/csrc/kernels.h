@@ -138,6 +138,14 @@ int embed_pos_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const
                   int V, int T, int NP, hipStream_t st);
 // d *= [act > 0] (n a multiple of 8): the ReLU backward without the fused fc2 dgrad epilogue
 int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st);
+// Residual dropout (OPT): the mask of element (m, n) of a site is a function of (seed, call, site, index0 + m H + n) alone
+// (include/slam_engine.h, "dropout_thr16"); thr16 = round(p * 65536), an element is dropped iff its 16 random bits are below it.
+// H and index0 multiples of 8.
+struct DropSite { int thr16 = 0; uint64_t seed = 0; uint32_t call = 0, site = 0; int64_t index0 = 0; };
+// in place: y = bf16(resid + (keep ? y / (1 - q) : 0))
+int dropout_add(bf16_t* y, const bf16_t* resid, int M, int H, const DropSite& d, hipStream_t st);
+// dm = keep ? bf16(dy / (1 - q)) : 0; dy is left alone
+int dropout_bwd(const bf16_t* dy, bf16_t* dm, int M, int H, const DropSite& d, hipStream_t st);
 int onehot(const int64_t* ids, bf16_t* oh, int M, int Vp, int V, int pad_id, hipStream_t st);
 // gather-side embedding gradient for large vocabularies: dE[ids[m]] += dh[m] in token order (deterministic);
 // ws = embed_bwd_workspace_ints(M, Vp) ints

@@ -147,6 +147,8 @@ def load_library(path: Optional[str] = None):
         "slam_op_embed_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_embed_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "slam_op_sr_round_bf16": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp]),
+        "slam_op_dropout_add": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, i64, i64, i32, i64, vp]),
+        "slam_op_dropout_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, i64, i64, i32, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if path is not None and not hasattr(lib, name):
@@ -248,6 +250,21 @@ class Engine:
 
     def set_option(self, key: str, value: int):
         self._ck(self.lib.slam_set_option(self.h, key.encode(), int(value)))
+
+    # -- residual dropout (OPT; options "dropout_thr16" / "dropout_seed" / "dropout_call_next") --------------------------------
+    def set_dropout(self, thr16: int, seed: Optional[int] = None):
+        """thr16 = round(p * 65536); a change between zero and non-zero unbinds the workspace (bind one again)."""
+        self.set_option("dropout_thr16", int(thr16))
+        if seed is not None:
+            self.set_dropout_seed(seed)
+
+    def set_dropout_seed(self, seed: int):
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF  # 64 unsigned bits, passed as the int64 with the same bits
+        self.set_option("dropout_seed", seed - (1 << 64) if seed >= (1 << 63) else seed)
+
+    def arm_dropout(self, call: int):
+        """The next forward (only) drops, with this call number."""
+        self.set_option("dropout_call_next", int(call))
 
     # -- step ---------------------------------------------------------------------------------
     def forward(self, ids, labels=None, position_ids=None, seg_start=None, seg_end=None, B=1, T=1,

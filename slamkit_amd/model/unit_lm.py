@@ -54,10 +54,17 @@ _HF_DIM_KEYS = ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_
                 "intermediate_size", "rms_norm_eps", "rope_theta", "tie_word_embeddings", "initializer_range")
 
 
+def dropout_thr16(p: float) -> int:
+    """The engine's 16-bit drop threshold of a dropout probability (option "dropout_thr16"): round(p * 65536)."""
+    return int(round(float(p) * 65536.0))
+
+
 def _opt_base_config(c: dict) -> dict:
     """Engine-side `base_config` of a HuggingFace OPTConfig dict (or of an already converted one: idempotent). Only pre-LN
     OPT as OPTForCausalLM computes it is supported (OPT-125m, OPT-1.3B); OPT-350m's post-LN + project_in/out layout,
-    other activations, untied heads and hidden > 2048 are refused."""
+    other activations, untied heads and hidden > 2048 are refused. `dropout` (HF OPTConfig's residual dropout, 0.1 by default
+    there) is carried, absent meaning 0.0; `attention_dropout`, `activation_dropout` and `layerdrop` are not implemented and
+    stay ignored (all three default to 0.0 in HF's OPTConfig)."""
     H = int(c["hidden_size"])
     nH = int(c["num_attention_heads"])
     if not c.get("do_layer_norm_before", True):
@@ -81,10 +88,14 @@ def _opt_base_config(c: dict) -> dict:
         raise ValueError(f"OPT head_dim {H / nH:g} is not supported (64 only)")
     ffn = c.get("ffn_dim", c.get("intermediate_size"))
     eps = c.get("layer_norm_eps", 1e-5)  # OPTDecoderLayer's nn.LayerNorm default
+    p = float(c.get("dropout", 0.0) or 0.0)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"OPT dropout {p} outside [0, 1)")
     return dict(model_type="opt", num_hidden_layers=int(c["num_hidden_layers"]), hidden_size=H, num_attention_heads=nH,
                 num_key_value_heads=nH, head_dim=64, intermediate_size=int(ffn),
                 max_position_embeddings=int(c["max_position_embeddings"]), layer_norm_eps=float(eps),
-                initializer_range=float(c.get("init_std", c.get("initializer_range", 0.02))), tie_word_embeddings=True)
+                initializer_range=float(c.get("init_std", c.get("initializer_range", 0.02))), tie_word_embeddings=True,
+                dropout=p)
 
 
 def base_config_from_hf(c: dict) -> dict:
@@ -170,6 +181,15 @@ class UnitLMConfig:
         for k in list(kwargs):
             if k in ("rope_theta", "rms_norm_eps", "initializer_range", "layer_norm_eps"):
                 base_config[k] = kwargs.pop(k)
+        if "dropout" in kwargs:  # model.config_args.dropout=0.1: the reference's config_args reach OPTConfig the same way
+            base_config["dropout"] = float(kwargs.pop("dropout"))
+        p_drop = float(base_config.get("dropout", 0.0) or 0.0)
+        if base_config.get("model_type") == "opt":
+            if not 0.0 <= p_drop < 1.0 or dropout_thr16(p_drop) > 65535:
+                raise ValueError(f"dropout {p_drop} outside [0, 65535.5 / 65536)")
+            base_config["dropout"] = p_drop
+        elif p_drop != 0.0:
+            raise ValueError(f"dropout={p_drop}: the Qwen2 family has no residual dropout (OPT only)")
         base_config.setdefault("head_dim", base_config["hidden_size"] // base_config["num_attention_heads"])
         base_config.setdefault("rms_norm_eps", 1e-6)
         base_config.setdefault("rope_theta", 10000.0)
@@ -211,6 +231,11 @@ class UnitLMConfig:
         if self.is_opt:
             return ARCH_OPT, int(self.base_config["max_position_embeddings"])
         return ARCH_QWEN2, 0
+
+    @property
+    def dropout(self) -> float:
+        """Residual dropout probability (OPT's `config.dropout`; 0.0 for Qwen2)."""
+        return float(self.base_config.get("dropout", 0.0) or 0.0)
 
     def engine_flags(self) -> int:
         """flags of slam_engine_create_ex: the untied head is a tensor of its own."""
@@ -300,6 +325,12 @@ class UnitLM(TokenLM):
             self._recompute = int(os.environ.get("SLAM_RECOMPUTE", "0"))  # measurement override, like the SLAM_* knobs below
             if self._recompute:
                 self.engine.set_option("recompute", self._recompute)
+            # residual dropout (OPT): on in train() mode only; forward() numbers its armed calls from _drop_call
+            self._drop_thr = dropout_thr16(config.dropout)
+            self._drop_seed = int(seed)
+            self._drop_call = 0
+            if self._drop_thr:
+                self.engine.set_dropout(self._drop_thr, self._drop_seed)  # before the workspace is sized: it adds buffers
             self._ensure_workspace(config.max_tokens)
             self._loss_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
             self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
@@ -582,8 +613,23 @@ class UnitLM(TokenLM):
         return self.get_input_embeddings()  # tied
 
     def train(self, mode: bool = True):
+        """With `config.dropout` > 0 (OPT) training mode is what turns dropout on: forward() then arms the engine for that
+        call. eval(), log_likelihood, sequence_logps and generate never drop."""
         self.training = mode
         return self
+
+    def set_dropout_state(self, seed: Optional[int] = None, call: Optional[int] = None):
+        """The dropout generator's seed (64 bits) and / or the number the next training forward is armed with (it counts up
+        from there, modulo 2^32). The mask is a function of (seed, call, layer, site, element) alone, so setting both replays
+        a forward's mask exactly; the trainer sets `call` before every micro-batch."""
+        if seed is not None:
+            self._drop_seed = int(seed)
+            if self._drop_thr:
+                self.engine.set_dropout_seed(self._drop_seed)
+        if call is not None:
+            if int(call) < 0:
+                raise ValueError("dropout call number must be >= 0")
+            self._drop_call = int(call)
 
     def eval(self):
         return self.train(False)
@@ -666,6 +712,9 @@ class UnitLM(TokenLM):
         if isinstance(num_items_in_batch, torch.Tensor):
             num_items_in_batch = float(num_items_in_batch)
         self._hold = (ids, lab, pos, seg_s, seg_e)  # the engine borrows these until backward
+        if self.training and self._drop_thr:  # this forward only: every other entry point runs unarmed, i.e. without dropout
+            self.engine.arm_dropout(self._drop_call & 0xFFFFFFFF)
+            self._drop_call += 1
         self.engine.forward(ids, lab, pos, seg_s, seg_e, B, T,
                             float(num_items_in_batch) if num_items_in_batch else 0.0,
                             self._loss_buf if lab is not None else None, logits)

@@ -31,6 +31,17 @@ from .training_args import SLAMTrainingArguments, lr_lambda
 logger = logging.getLogger(__name__)
 
 
+DROPOUT_SEED_TAG = 0x44524F50 << 32  # "DROP" in the high half of the Philox key
+
+
+def dropout_seed(seed: int, rank: int) -> int:
+    """Seed of a rank's dropout masks: ((rank << 32) | (seed & 0xffffffff)) ^ DROPOUT_SEED_TAG - injective in
+    (seed mod 2^32, rank), so two ranks of one run never draw the same mask. The tag keeps the dropout generator's key apart
+    from the stochastic rounding's (`adamw_sr_seed` defaults to `args.seed` itself and its counters have the same form):
+    without it rank 0 would build its masks from the words the optimizer rounds with whenever call == step."""
+    return (((int(rank) & 0xFFFFFFFF) << 32) | (int(seed) & 0xFFFFFFFF)) ^ DROPOUT_SEED_TAG
+
+
 class SLAMTrainer:
     def __init__(self, model=None, args: SLAMTrainingArguments = None, data_collator: Callable = None,
                  train_dataset=None, eval_dataset=None, processing_class=None, callbacks: Optional[List[TrainerCallback]] = None):
@@ -117,6 +128,11 @@ class SLAMTrainer:
             sd = getattr(self.args, "optim_sr_seed", None)
             model.engine.set_option("adamw_sr_seed", int(getattr(self.args, "seed", 0) if sd is None else sd))
         model.engine.set_option("adamw_sr", 1 if sr else 0)
+        # residual dropout (OPT): stateless like the rounding above. The seed mixes in the rank so that ranks draw different
+        # masks; the call number is set before every micro-batch (optimizer_step), so a resumed run repeats the uninterrupted one
+        self._sets_dropout = hasattr(model, "set_dropout_state")
+        if self._sets_dropout:
+            model.set_dropout_state(seed=dropout_seed(int(getattr(self.args, "seed", 0) or 0), self.rank))
 
     # ---- reference hooks ------------------------------------------------------------------------
     def get_num_tokens(self, labels: torch.Tensor) -> int:
@@ -299,6 +315,8 @@ class SLAMTrainer:
         for i, mb in enumerate(micro):
             if i == 0 and a.overwrite_first_grad:  # the first backward of the step stores the gradients: no zeroing pass
                 self.model.engine.set_option("grad_overwrite_next", 1)
+            if self._sets_dropout:  # micro-batch i of optimizer step k draws mask number k * GA + i, whenever it runs
+                self.model.set_dropout_state(call=self.state.global_step * a.gradient_accumulation_steps + i)
             loss = self.training_step(self.model, mb, num_items_in_batch=n_items, last_micro=(i == len(micro) - 1),
                                       grad_scale=scale)
             # every micro-batch loss is already normalised by the whole step's token count (global, or this rank's
@@ -417,6 +435,8 @@ class SLAMTrainer:
             if path:
                 self._load_checkpoint(path)
         self.model.zero_grad()
+        if hasattr(self.model, "train"):
+            self.model.train()  # Trainer.train: model.train() - what turns OPT's dropout on, whatever mode the model arrived in
         for cb in self.callbacks:
             cb.on_train_begin(a, self.state, self.control)
         t0, tokens0 = time.time(), self.state.num_input_tokens_seen
@@ -478,15 +498,22 @@ class SLAMTrainer:
         idx = list(range(len(ds)))
         batches = shard_batches([idx[i:i + bs] for i in range(0, len(idx), bs)], self.rank, self.world, even=False)
         tot, cnt = torch.zeros(1, dtype=torch.float64, device=self.model.device), 0.0
-        for b in batches:
-            mb = self.data_collator([ds[i] for i in b])
-            n = float(((mb["labels"][:, 1:]) != -100).sum())
-            if n == 0:
-                continue
-            out = self.model.forward(input_ids=mb["input_ids"], position_ids=mb.get("position_ids"), labels=mb["labels"],
-                                     num_items_in_batch=1.0, return_logits=False)
-            tot += out.loss.double()
-            cnt += n
+        was_training = bool(getattr(self.model, "training", False))  # Trainer.evaluate: model.eval() - no dropout in the metric
+        if was_training and hasattr(self.model, "eval"):
+            self.model.eval()
+        try:
+            for b in batches:
+                mb = self.data_collator([ds[i] for i in b])
+                n = float(((mb["labels"][:, 1:]) != -100).sum())
+                if n == 0:
+                    continue
+                out = self.model.forward(input_ids=mb["input_ids"], position_ids=mb.get("position_ids"), labels=mb["labels"],
+                                         num_items_in_batch=1.0, return_logits=False)
+                tot += out.loss.double()
+                cnt += n
+        finally:
+            if was_training and hasattr(self.model, "train"):
+                self.model.train()
         if self.world > 1:
             t = torch.cat([tot, torch.tensor([cnt], dtype=torch.float64, device=self.model.device)])
             dist.all_reduce(t)
