@@ -130,12 +130,60 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
  *   0 .. lens[b], writes fp32 logits [B][vocab] and increments lens ON THE DEVICE (no host synchronisation). B must be the
  *   prefill's B and the workspace at least 2 B tokens. SLAM_ESTATE without a bound cache, without a prefill, or when the
  *   step could pass `capacity` (the host bound: prefill T + steps so far).
- * Both overwrite the forward activations (slam_backward then needs a new slam_forward). */
+ * Both overwrite the forward activations (slam_backward then needs a new slam_forward).
+ * What generation offers: greedy decoding and temperature / top-k / top-p sampling with banned tokens, EOS and pad handling,
+ * either chosen by the caller from the logits or on the device by slam_sample_tokens (below; top_k 1 .. 256, reproducible
+ * per row). No beam search, no repetition penalty, no OPT. */
 size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity);
 int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity);
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
                  slam_stream_t stream);
 int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B, float* logits_out, slam_stream_t stream);
+
+/* ---- choosing the next token on the device (what HF's logits processors + torch.multinomial do between two decode steps) ----
+ * slam_sample_tokens needs no engine: it reads fp32 logits [B][vocab] (row stride vocab, 4-byte aligned; odd vocabularies
+ * are fine) such as slam_prefill / slam_decode_step wrote, and writes the chosen ids where slam_decode_step reads them, so a
+ * generate loop is  prefill, sample(step 0), { decode_step(next), sample(step k) }  on one stream with nothing in between.
+ * The contract, for row b with row id r = row_ids ? row_ids[b] : b, step s = desc->step and x_i the logit of token i:
+ *   finished   done && done[b]: next[b] = pad_id, the out column gets pad_id, nothing else happens.
+ *   scores     banned tokens (banned[i] != 0) and NaN logits count as -inf; +inf counts as FLT_MAX and -0 as +0. A row
+ *              without a score above -inf emits pad_id and is NOT marked done.
+ *   greedy     (do_sample == 0) the lowest i with x_i == max.
+ *   sampling   k' = min(top_k, number of scores above -inf). The candidates are the k' largest scores ordered by (x descending,
+ *              i ascending); that order is the rank j. A tie at the k-th value goes to the lower id (HF keeps every such tie:
+ *              the one deviation). inv_t = 1.0f / temperature; w_j = expf((x_j - x_0) * inv_t) in fp32, w_0 = 1.
+ *              top_p < 1: tail_j = w_{k'-1} + ... + w_j summed in fp32 from the last rank upward, P = tail_0; rank j > 0 is
+ *              dropped when tail_j <= (1.0f - top_p) * P (HF's rule, cum <= 1 - top_p on the ascending sort, rank 0 always
+ *              kept). The kept ranks are a prefix of m ranks (m = k' for top_p = 1).
+ *              cum_j = w_0 + ... + w_j in fp32, in that order; total = cum_{m-1}; u = (philox.w[0] >> 8) * 2^-24; the token
+ *              is the candidate of the lowest j with cum_j > u * total, or j = m - 1 if there is none.
+ *              Philox4x32-10 (the generator of "adamw_sr" / "dropout_thr16"): counter (r & 0xffffffff, s, r >> 32, 0x53414D50),
+ *              key (seed & 0xffffffff, seed >> 32).
+ *   after      next[b] = token; out[b * out_stride + s] = token when out is given; done[b] = 1 when done is given and the
+ *              token is one of eos_ids[0 .. n_eos).
+ * A row's result depends on (its logits, banned, the description, r) alone: not on B, the row's index, the launch shape or
+ * an earlier call, and it is the same bits on every run (no floating-point atomics). Rows longer than 2048 take two launches
+ * (per-chunk top k into the workspace, then one block per row), shorter ones a single launch.
+ * banned: uint8 [vocab]; row_ids: int64 [B]; eos_ids: int32 [n_eos]; done: uint8 [B]; next: int64 [B]; out: int64 - all device
+ * memory, nullable where the contract says "when given". ws: slam_sample_workspace_bytes(B, vocab, do_sample ? top_k : 1)
+ * bytes of device memory, 8-byte aligned (the function itself is host-only arithmetic: positive for valid arguments, 0 else).
+ * SLAM_EINVAL, before anything is launched or dereferenced on the device: logits, desc or next NULL; B <= 0 (or > 65535);
+ * vocab <= 0; do_sample other than 0 / 1; sampling with top_k outside 1 .. 256; temperature <= 0; top_p outside (0, 1];
+ * n_eos outside 0 .. 16; n_eos > 0 without eos_ids; ws NULL or ws_bytes too small. */
+typedef struct SlamSampleDesc {
+  int32_t do_sample;   /* 0 greedy, 1 sample */
+  int32_t top_k;       /* sampling: 1 .. 256 */
+  float temperature;   /* > 0 */
+  float top_p;         /* (0, 1] */
+  uint64_t seed;
+  uint32_t step;       /* index of the new token: 0 for the one drawn from the prefill logits */
+  int32_t pad_id;
+  int32_t n_eos;       /* 0 .. 16 */
+} SlamSampleDesc;
+size_t slam_sample_workspace_bytes(int32_t B, int32_t vocab, int32_t top_k);
+int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                       const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                       int64_t out_stride, void* ws, size_t ws_bytes, slam_stream_t stream);
 
 /* loss.backward(): accumulates d(loss*grad_scale)/dparam into the bound fp32 gradient buffer.
  * bucket_layers = decoder layers per gradient bucket for the callback (<=0: one bucket). */

@@ -6,7 +6,15 @@
 //  * attn_decode: bias + RoPE of the new token's q / k on the fp32 projection (one rounding, the forward's tables and query
 //    pre-scale), K / V appended to the cache, split-KV flash decoding with every query head of a KV group in one pass over the
 //    group's keys, partial (m, l, o) merged in the log2 domain by attn_decode_combine in split order.
+//  * sample_tokens (slam_sample_tokens): the next token of every row from its fp32 logits, on the device. A candidate is the
+//    64-bit composite (order-preserving image of the score << idbits) | (idmask - id): all composites of a row differ and
+//    "larger" is exactly "higher score, then lower id", so the top k is an exact radix select (integer LDS histograms, 8 bits a
+//    pass, stopping as soon as a digit's bin is taken whole) and needs no float comparison. Rows longer than one chunk go
+//    through two launches: every (chunk, row) block selects its local top k into the workspace, one block per row selects
+//    among those, ranks the k' survivors and does the weights, the top-p cut, the Philox draw and the EOS / done / pad part.
+//    Thread 0 forms the sums in the stated order: no floating-point atomics, nothing depends on the grid.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 
 #include "common.h"
@@ -341,6 +349,252 @@ __global__ void lens_inc_kernel(int* __restrict__ lens, int B) {
   if (b < B) lens[b] = lens[b] + 1;
 }
 
+
+// ---- token sampling ---------------------------------------------------------------------------------------------------------
+constexpr int SP_THREADS = 256;
+constexpr int SP_CHUNK = 2048;   // scores per stage-1 block; rows up to this length take the single launch
+constexpr int SP_MAXK = 256;     // top_k limit (SlamSampleDesc)
+constexpr int SP_CACHE = 4096;   // stage-2 candidates kept in LDS; the rest are re-read from the workspace every pass
+constexpr uint32_t SP_NEG_INF_KEY = 0x007fffffu;  // score_key(-inf): a candidate needs a larger key
+
+typedef unsigned long long u64_t;
+
+// order-preserving integer image of a score: banned / NaN -> -inf, +inf -> FLT_MAX, -0 -> +0
+SLAM_DEVICE uint32_t score_key(float x, bool banned) {
+  if (banned || x != x) x = -INFINITY;
+  x = fminf(x, FLT_MAX);
+  uint32_t u = __float_as_uint(x);
+  if ((u << 1) == 0u) u = 0u;
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+SLAM_DEVICE float key_score(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+
+struct SampleShared {
+  uint32_t hist[256];
+  u64_t sel[SP_MAXK];
+  float x[SP_MAXK];
+  float w[SP_MAXK];
+  int id[SP_MAXK];
+  int red[SP_THREADS / 64];
+  int bc[3];  // the selected digit, the count above it, the digit's own count
+  int cnt;
+};
+
+// scores [c0, c0 + n) of one row as keys in LDS; n <= SP_CHUNK. The row may start at any 4-byte boundary: scalar loads up to
+// the first 16-byte boundary, 16-byte loads from there, scalar loads for the rest.
+SLAM_DEVICE void load_keys(const float* __restrict__ row, const uint8_t* __restrict__ banned, int c0, int n, uint32_t* keys) {
+  const float* p = row + c0;
+  const uint8_t* bn = banned ? banned + c0 : nullptr;
+  int head = (int)((4u - (uint32_t)(((uintptr_t)p >> 2) & 3u)) & 3u);
+  if (head > n) head = n;
+  const int nv = (n - head) >> 2;
+  const int t = threadIdx.x;
+  if (t < head) keys[t] = score_key(p[t], bn && bn[t]);
+  const float4* pv = reinterpret_cast<const float4*>(p + head);
+  for (int v = t; v < nv; v += SP_THREADS) {
+    const float4 f = pv[v];
+    const int i = head + 4 * v;
+    keys[i + 0] = score_key(f.x, bn && bn[i + 0]);
+    keys[i + 1] = score_key(f.y, bn && bn[i + 1]);
+    keys[i + 2] = score_key(f.z, bn && bn[i + 2]);
+    keys[i + 3] = score_key(f.w, bn && bn[i + 3]);
+  }
+  for (int i = head + 4 * nv + t; i < n; i += SP_THREADS) keys[i] = score_key(p[i], bn && bn[i]);
+}
+
+// composites of a chunk held as keys in LDS
+struct KeySrc {
+  const uint32_t* keys;
+  int base, idbits;
+  uint32_t idmask;
+  SLAM_DEVICE u64_t operator()(int i) const { return ((u64_t)keys[i] << idbits) | (u64_t)(idmask - (uint32_t)(base + i)); }
+};
+// composites that stage 1 wrote: the first ncache from LDS, the rest from the workspace
+struct PairSrc {
+  const u64_t* cache;
+  const u64_t* g;
+  int ncache;
+  SLAM_DEVICE u64_t operator()(int i) const { return i < ncache ? cache[i] : g[i]; }
+};
+
+// The min(k, candidates) largest composites of src(0 .. n) into sh.sel, in no particular order; returns their number.
+// Every thread of the block calls it (barriers inside); the result is the same set whatever the order of the items.
+template <class Src>
+SLAM_DEVICE int select_topk(const Src& src, int n, int k, int idbits, SampleShared& sh) {
+  const int t = threadIdx.x, lane = t & 63;
+  const u64_t lowest = ((u64_t)SP_NEG_INF_KEY + 1) << idbits;  // candidates are >= this
+  int c = 0;
+  for (int i = t; i < n; i += SP_THREADS) c += src(i) >= lowest ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) sh.red[t >> 6] = c;
+  if (t == 0) sh.cnt = 0;
+  __syncthreads();
+  int nvalid = 0;
+#pragma unroll
+  for (int w = 0; w < SP_THREADS / 64; ++w) nvalid += sh.red[w];
+  const int kk = k < nvalid ? k : nvalid;
+  if (kk == 0) return 0;
+  const int npass = (32 + idbits + 7) / 8;
+  u64_t prefix = 0, mask = 0;
+  int remaining = kk;
+  for (int p = 0; p < npass; ++p) {
+    const int shift = 8 * (npass - 1 - p);
+    sh.hist[t] = 0;
+    __syncthreads();
+    for (int i = t; i < n; i += SP_THREADS) {
+      const u64_t v = src(i);
+      if (v >= lowest && (v & mask) == prefix) atomicAdd(&sh.hist[(uint32_t)(v >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (t < 64) {  // bins from the top: the first one at which the running count reaches `remaining`
+      int s[4], local = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { s[j] = (int)sh.hist[255 - (4 * lane + j)]; local += s[j]; }
+      int incl = local;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      int run = incl - local;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (run < remaining && run + s[j] >= remaining) { sh.bc[0] = 255 - (4 * lane + j); sh.bc[1] = run; sh.bc[2] = s[j]; }
+        run += s[j];
+      }
+    }
+    __syncthreads();
+    prefix |= (u64_t)sh.bc[0] << shift;
+    mask |= (u64_t)255 << shift;
+    remaining -= sh.bc[1];
+    if (sh.bc[2] == remaining) break;  // the whole bin is in: (v & mask) >= prefix is the selection
+  }
+  for (int i = t; i < n; i += SP_THREADS) {
+    const u64_t v = src(i);
+    if (v >= lowest && (v & mask) >= prefix) {
+      const int slot = atomicAdd(&sh.cnt, 1);
+      if (slot < SP_MAXK) sh.sel[slot] = v;
+    }
+  }
+  __syncthreads();
+  return kk;
+}
+
+struct SampleParams {
+  int do_sample, k, vocab, idbits, nch, pad_id, n_eos;
+  float inv_t, top_p;
+  uint32_t k0, k1, step;
+  long long out_stride;
+};
+
+SLAM_DEVICE void emit_token(long long tok, bool mark, int b, const SampleParams& P, const int* eos_ids, uint8_t* done,
+                            int64_t* next, int64_t* out) {
+  next[b] = tok;
+  if (out) out[(long long)b * P.out_stride + P.step] = tok;
+  if (mark && done)
+    for (int e = 0; e < P.n_eos; ++e)
+      if (eos_ids[e] == (int)tok) { done[b] = 1; break; }
+}
+
+// stage 1, grid (chunks, B): the chunk's top k as composites into ws[b][chunk][k], unused slots 0 (no candidate)
+__global__ __launch_bounds__(SP_THREADS) void sample_select_kernel(const float* __restrict__ logits,
+                                                                   const uint8_t* __restrict__ banned,
+                                                                   const uint8_t* __restrict__ done, SampleParams P,
+                                                                   u64_t* __restrict__ ws) {
+  __shared__ uint32_t keys[SP_CHUNK];
+  __shared__ SampleShared sh;
+  const int ch = blockIdx.x, b = blockIdx.y;
+  if (done && done[b]) return;
+  const int c0 = ch * SP_CHUNK;
+  const int n = min(SP_CHUNK, P.vocab - c0);
+  load_keys(logits + (size_t)b * P.vocab, banned, c0, n, keys);
+  __syncthreads();
+  const KeySrc src{keys, c0, P.idbits, (1u << P.idbits) - 1u};
+  const int kk = select_topk(src, n, P.k, P.idbits, sh);
+  u64_t* dst = ws + ((size_t)b * P.nch + ch) * P.k;
+  for (int i = threadIdx.x; i < P.k; i += SP_THREADS) dst[i] = i < kk ? sh.sel[i] : 0ull;
+}
+
+// one block per row. ROW: the whole row (vocab <= SP_CHUNK) is selected here; else the candidates of stage 1.
+template <bool ROW>
+__global__ __launch_bounds__(SP_THREADS) void sample_finish_kernel(const float* __restrict__ logits,
+                                                                   const uint8_t* __restrict__ banned,
+                                                                   const int64_t* __restrict__ row_ids,
+                                                                   const int* __restrict__ eos_ids, uint8_t* __restrict__ done,
+                                                                   int64_t* __restrict__ next, int64_t* __restrict__ out,
+                                                                   SampleParams P, const u64_t* __restrict__ ws) {
+  __shared__ u64_t buf[ROW ? SP_CHUNK / 2 : SP_CACHE];
+  __shared__ SampleShared sh;
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (done && done[b]) {
+    if (t == 0) emit_token(P.pad_id, false, b, P, eos_ids, done, next, out);
+    return;
+  }
+  int kk;
+  if (ROW) {
+    uint32_t* keys = reinterpret_cast<uint32_t*>(buf);
+    load_keys(logits + (size_t)b * P.vocab, banned, 0, P.vocab, keys);
+    __syncthreads();
+    const KeySrc src{keys, 0, P.idbits, (1u << P.idbits) - 1u};
+    kk = select_topk(src, P.vocab, P.k, P.idbits, sh);
+  } else {
+    const int n = P.nch * P.k;
+    const u64_t* g = ws + (size_t)b * n;
+    const int ncache = n < SP_CACHE ? n : SP_CACHE;
+    for (int i = t; i < ncache; i += SP_THREADS) buf[i] = g[i];
+    __syncthreads();
+    const PairSrc src{buf, g, ncache};
+    kk = select_topk(src, n, P.k, P.idbits, sh);
+  }
+  if (kk == 0) {  // no finite score: pad, the row is not marked done
+    if (t == 0) emit_token(P.pad_id, false, b, P, eos_ids, done, next, out);
+    return;
+  }
+  // rank j = how many of the k' composites are larger: (score descending, id ascending)
+  const uint32_t idmask = (1u << P.idbits) - 1u;
+  if (t < kk) {
+    const u64_t v = sh.sel[t];
+    int r = 0;
+    for (int j = 0; j < kk; ++j) r += sh.sel[j] > v ? 1 : 0;
+    sh.x[r] = key_score((uint32_t)(v >> P.idbits));
+    sh.id[r] = (int)(idmask - ((uint32_t)v & idmask));
+  }
+  __syncthreads();
+  if (!P.do_sample) {
+    if (t == 0) emit_token(sh.id[0], true, b, P, eos_ids, done, next, out);
+    return;
+  }
+  if (t < kk) sh.w[t] = t == 0 ? 1.0f : expf((sh.x[t] - sh.x[0]) * P.inv_t);
+  __syncthreads();
+  if (t != 0) return;
+  int m = kk;
+  if (P.top_p < 1.0f) {
+    float tail = 0.f;
+    for (int j = kk - 1; j >= 0; --j) tail += sh.w[j];
+    const float thr = (1.0f - P.top_p) * tail;
+    tail = 0.f;
+    for (int j = kk - 1; j > 0; --j) {
+      tail += sh.w[j];
+      if (tail <= thr) m = j;  // tail grows towards rank 0: the dropped ranks are a suffix
+      else break;
+    }
+  }
+  float total = 0.f;
+  for (int j = 0; j < m; ++j) total += sh.w[j];
+  const uint64_t r = row_ids ? (uint64_t)row_ids[b] : (uint64_t)b;
+  const Philox4 rnd = philox4x32_10((uint32_t)r, P.step, (uint32_t)(r >> 32), 0x53414D50u, P.k0, P.k1);
+  const float u = (float)(rnd.w[0] >> 8) * 5.9604644775390625e-08f;  // 2^-24
+  const float target = u * total;
+  int pick = m - 1;
+  float cum = 0.f;
+  for (int j = 0; j < m; ++j) {
+    cum += sh.w[j];
+    if (cum > target) { pick = j; break; }
+  }
+  emit_token(sh.id[pick], true, b, P, eos_ids, done, next, out);
+}
+
 }  // namespace
 
 namespace slam {
@@ -424,6 +678,46 @@ int lens_to_pos(const int* lens, int64_t* pos, int B, hipStream_t st) {
 
 int lens_inc(int* lens, int B, hipStream_t st) {
   lens_inc_kernel<<<nblk((size_t)B, 256), 256, 0, st>>>(lens, B);
+  return (int)hipGetLastError();
+}
+
+
+static int sample_chunks(int vocab) { return (vocab + SP_CHUNK - 1) / SP_CHUNK; }
+
+size_t sample_workspace_bytes(int B, int vocab, int top_k) {
+  if (B <= 0 || vocab <= 0) return 0;
+  const int k = top_k < 1 ? 1 : top_k;
+  return (size_t)B * sample_chunks(vocab) * k * sizeof(u64_t);
+}
+
+int sample_tokens(const SampleArgs& a, hipStream_t st) {
+  if (!a.logits || !a.next || a.B <= 0 || a.B > 65535 || a.vocab <= 0 || ((uintptr_t)a.logits & 3)) return -1;
+  const int k = a.do_sample ? a.top_k : 1;
+  if (k < 1 || k > SP_MAXK || !(a.temperature > 0.f) || !(a.top_p > 0.f) || a.top_p > 1.f) return -1;
+  if (a.n_eos < 0 || (a.n_eos > 0 && !a.eos_ids)) return -1;
+  if (!a.ws || ((uintptr_t)a.ws & 7) || a.ws_bytes < sample_workspace_bytes(a.B, a.vocab, k)) return -1;
+  SampleParams P;
+  P.do_sample = a.do_sample ? 1 : 0;
+  P.k = k;
+  P.vocab = a.vocab;
+  P.idbits = 1;
+  while (P.idbits < 31 && (1u << P.idbits) < (uint32_t)a.vocab) ++P.idbits;
+  P.nch = sample_chunks(a.vocab);
+  P.pad_id = a.pad_id;
+  P.n_eos = a.n_eos;
+  P.inv_t = 1.0f / a.temperature;
+  P.top_p = a.top_p;
+  P.k0 = (uint32_t)a.seed;
+  P.k1 = (uint32_t)(a.seed >> 32);
+  P.step = a.step;
+  P.out_stride = a.out_stride;
+  u64_t* ws = reinterpret_cast<u64_t*>(a.ws);
+  if (P.nch == 1) {
+    sample_finish_kernel<true><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws);
+  } else {
+    sample_select_kernel<<<dim3(P.nch, a.B), SP_THREADS, 0, st>>>(a.logits, a.banned, a.done, P, ws);
+    sample_finish_kernel<false><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws);
+  }
   return (int)hipGetLastError();
 }
 

@@ -2168,4 +2168,33 @@ int slam_op_dropout_bwd(const void* dy, void* dy_masked, int M, int H, int32_t t
   return dropout_bwd((const bf16_t*)dy, (bf16_t*)dy_masked, M, H, d, (hipStream_t)s);
 }
 
+size_t slam_sample_workspace_bytes(int32_t B, int32_t vocab, int32_t top_k) { return sample_workspace_bytes(B, vocab, top_k); }
+int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                       const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                       int64_t out_stride, void* ws, size_t ws_bytes, slam_stream_t stream) {
+  if (!desc || (desc->do_sample != 0 && desc->do_sample != 1) || desc->n_eos > 16) return SLAM_EINVAL;
+  SampleArgs a;  // sample_tokens refuses the rest (-1 = SLAM_EINVAL) before it launches anything
+  a.logits = logits;
+  a.B = B;
+  a.vocab = vocab;
+  a.banned = banned;
+  a.do_sample = desc->do_sample;
+  a.top_k = desc->top_k;
+  a.temperature = desc->temperature;
+  a.top_p = desc->top_p;
+  a.seed = desc->seed;
+  a.step = desc->step;
+  a.pad_id = desc->pad_id;
+  a.n_eos = desc->n_eos;
+  a.row_ids = row_ids;
+  a.eos_ids = eos_ids;
+  a.done = done;
+  a.next = next;
+  a.out = out;
+  a.out_stride = out_stride;
+  a.ws = ws;
+  a.ws_bytes = ws_bytes;
+  return sample_tokens(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -236,5 +236,27 @@ int kv_scatter(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, const int* lens, int B
 int gather_last_rows(const bf16_t* src, bf16_t* dst, const int* lens, int B, int T, int H, hipStream_t st);
 int lens_to_pos(const int* lens, int64_t* pos, int B, hipStream_t st);
 int lens_inc(int* lens, int B, hipStream_t st);
+// The next token of every row of fp32 logits [B][vocab] (row stride vocab, any 4-byte alignment), chosen on the device by the
+// contract of include/slam_engine.h (slam_sample_tokens): one argument block from the entry point down to the launches.
+struct SampleArgs {
+  const float* logits = nullptr;
+  int B = 0, vocab = 0;
+  const uint8_t* banned = nullptr;  // nullable: [vocab], non-zero = never chosen
+  int do_sample = 0, top_k = 1;     // greedy ignores top_k, temperature and top_p beyond their range checks
+  float temperature = 1.f, top_p = 1.f;
+  uint64_t seed = 0;
+  uint32_t step = 0;
+  int pad_id = 0, n_eos = 0;
+  const int64_t* row_ids = nullptr;  // nullable: the Philox row id of row b (default b)
+  const int* eos_ids = nullptr;      // device, [n_eos]
+  uint8_t* done = nullptr;           // nullable: [B], read (finished rows emit pad_id) and set (the token is an EOS id)
+  int64_t* next = nullptr;           // [B]
+  int64_t* out = nullptr;            // nullable: out[b * out_stride + step] = the token
+  int64_t out_stride = 0;
+  void* ws = nullptr;                // sample_workspace_bytes(B, vocab, do_sample ? top_k : 1), 8-byte aligned
+  size_t ws_bytes = 0;
+};
+size_t sample_workspace_bytes(int B, int vocab, int top_k);  // host only
+int sample_tokens(const SampleArgs& a, hipStream_t st);
 
 }  // namespace slam

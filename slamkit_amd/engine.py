@@ -31,6 +31,13 @@ class SlamTensorInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("offset", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64)]
 
 
+class SlamSampleDesc(C.Structure):
+    _fields_ = [
+        ("do_sample", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float), ("top_p", C.c_float),
+        ("seed", C.c_uint64), ("step", C.c_uint32), ("pad_id", C.c_int32), ("n_eos", C.c_int32),
+    ]
+
+
 def header_symbols() -> List[str]:
     """Every function name declared in include/slam_engine.h (used by the export test)."""
     hdr = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "slam_engine.h")
@@ -75,6 +82,8 @@ def load_library(path: Optional[str] = None):
         "slam_bind_kv_cache": (C.c_int, [vp, vp, sz, i32, i32]),
         "slam_prefill": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
         "slam_decode_step": (C.c_int, [vp, vp, vp, i32, vp, vp]),
+        "slam_sample_workspace_bytes": (sz, [i32, i32, i32]),
+        "slam_sample_tokens": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
         "slam_bucket_stream": (vp, [vp]),
         "slam_set_logit_mask": (C.c_int, [vp, vp]),
         "slam_padded_vocab": (i32, [vp]),
@@ -173,6 +182,26 @@ def current_stream_ptr() -> int:
 
 class EngineError(RuntimeError):
     pass
+
+
+def sample_workspace_bytes(B: int, vocab: int, top_k: int) -> int:
+    """Bytes of device workspace slam_sample_tokens needs (host arithmetic; top_k = 1 for greedy)."""
+    return int(load_library().slam_sample_workspace_bytes(int(B), int(vocab), int(top_k)))
+
+
+def sample_tokens(logits, desc: SlamSampleDesc, next_ids, ws, banned=None, row_ids=None, eos_ids=None, done=None, out=None,
+                  stream: Optional[int] = None):
+    """slam_sample_tokens: next_ids[b] (int64 [B]) = the token chosen from row b of the fp32 logits [B, vocab] under `desc`
+    (greedy or temperature / top-k / top-p with the stateless Philox draw of (seed, row id, step)). banned uint8 [vocab], row_ids
+    int64 [B], eos_ids int32 [n_eos], done uint8 [B] (read and set), out int64 [B, stride] (column desc.step is written), ws a
+    uint8 tensor of sample_workspace_bytes(...): device tensors, None where optional. Only enqueues work."""
+    B, V = logits.shape
+    rc = load_library().slam_sample_tokens(_ptr(logits), B, V, _ptr(banned), C.byref(desc), _ptr(row_ids), _ptr(eos_ids),
+                                          _ptr(done), _ptr(next_ids), _ptr(out), out.stride(0) if out is not None else 0,
+                                          _ptr(ws), ws.numel() * ws.element_size(),
+                                          stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_sample_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 @dataclass

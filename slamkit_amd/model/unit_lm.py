@@ -796,14 +796,24 @@ class UnitLM(TokenLM):
                  do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
                  seed: Optional[int] = None, input_ids: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, bad_words_ids: Optional[List[List[int]]] = None,
-                 top_p: Optional[float] = None, eos_token_id=None, pad_token_id: Optional[int] = None, **kwargs) -> torch.Tensor:
+                 top_p: Optional[float] = None, eos_token_id=None, pad_token_id: Optional[int] = None,
+                 sampler: Optional[str] = None, sample_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
         first real token, HF's cumsum(mask) - 1), prefilled once, then decoded one token per step (slam_decode_step).
         Logits are fp32; bad words get -inf, then temperature, top_k and top_p (sampling only). Finished rows are padded
         with pad_token_id; generation stops when every row has emitted eos_token_id. Explicit arguments override
-        `generation_config`. Returns [B, T_in + n_new] int64: the prompt as passed, padding included, then the new tokens."""
+        `generation_config`. Returns [B, T_in + n_new] int64: the prompt as passed, padding included, then the new tokens.
+
+        `sampler` selects who picks the token. None / "torch": the torch ops above (torch.multinomial with one generator for
+        the batch: a row's continuation depends on the batch around it). "engine": slam_sample_tokens (include/slam_engine.h)
+        picks it on the device and writes it where the next decode step reads it - no torch op between two engine calls - with a
+        stateless Philox draw keyed on (seed, row id, step): a row's continuation depends on its prompt, the seed and its row id
+        alone, whatever the batch. `sample_ids` (int64 [B], default 0 .. B-1) are those row ids: a sharded evaluation passes the
+        examples' global indices. The engine sampler needs 1 <= top_k <= 256 and temperature > 0 when sampling, top_p in
+        (0, 1] and at most 16 EOS ids (ValueError otherwise); a tie at the k-th score goes to the lower id where HF keeps all
+        ties. seed=None draws a 62-bit seed from torch's default CPU generator."""
         if self.config.is_opt:
             raise ValueError("generate is not implemented for OPT models (the engine's KV-cached decode covers Qwen2 only)")
         gc = generation_config
@@ -841,6 +851,20 @@ class UnitLM(TokenLM):
             return inputs.to(self.device, torch.int64)
         if kwargs:
             raise TypeError(f"generate got unsupported arguments {sorted(kwargs)}")
+        if sampler not in (None, "torch", "engine"):
+            raise ValueError(f"sampler must be None, 'torch' or 'engine', not {sampler!r}")
+        on_device = sampler == "engine"
+        if on_device:
+            if do_sample and not 1 <= top_k <= 256:
+                raise ValueError(f"sampler='engine' samples with 1 <= top_k <= 256 (got top_k={top_k})")
+            if do_sample and not temperature > 0:
+                raise ValueError(f"sampler='engine' needs temperature > 0 (got {temperature})")
+            if do_sample and not 0 < top_p <= 1:
+                raise ValueError(f"sampler='engine' needs 0 < top_p <= 1 (got {top_p})")
+            if len(eos) > 16:
+                raise ValueError(f"sampler='engine' takes at most 16 EOS ids (got {len(eos)})")
+        elif sample_ids is not None:
+            raise ValueError("sample_ids are the row ids of sampler='engine'; the torch sampler has none")
         dev = self.device
         seq_in = inputs.to(dev, torch.int64)
         B, T_in = seq_in.shape
@@ -863,35 +887,39 @@ class UnitLM(TokenLM):
         self.engine.bind_kv_cache(raw[off:off + nbytes], B, cap)
         V = self.config.vocab_size
         logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-        bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
         eos_t = torch.tensor(eos, dtype=torch.long, device=dev) if eos else None
-        g = None
-        if do_sample and seed is not None:
-            g = torch.Generator(device=dev)
-            g.manual_seed(int(seed))
         self._hold = (ids, lens)
-        self.engine.prefill(ids, lens, B, T, logits)
-        done = torch.zeros(B, dtype=torch.bool, device=dev)
         new = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
         n = 0
-        for step in range(max_new_tokens):
-            scores = logits
-            if bad_idx is not None:
-                scores = scores.index_fill(1, bad_idx, float("-inf"))
-            if do_sample:
-                scores = _warp(scores, temperature, top_k, top_p)
-                nxt = torch.multinomial(torch.softmax(scores, -1), 1, generator=g)[:, 0]
-            else:
-                nxt = scores.argmax(-1)
-            nxt = torch.where(done, torch.full_like(nxt, int(pad)), nxt)
-            new[:, step] = nxt
-            n = step + 1
-            if eos_t is not None:
-                done |= torch.isin(nxt, eos_t)
-                if (step % 16 == 15 or step + 1 == max_new_tokens) and bool(done.all()):
-                    break
-            if step + 1 < max_new_tokens:
-                self.engine.decode_step(nxt.contiguous(), lens, B, logits)
+        if on_device:
+            n = self._sample_on_device(logits, new, ids, lens, T, bad, eos, int(pad), do_sample, top_k, temperature, top_p,
+                                       seed, sample_ids)
+        else:
+            bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
+            g = None
+            if do_sample and seed is not None:
+                g = torch.Generator(device=dev)
+                g.manual_seed(int(seed))
+            self.engine.prefill(ids, lens, B, T, logits)
+            done = torch.zeros(B, dtype=torch.bool, device=dev)
+            for step in range(max_new_tokens):
+                scores = logits
+                if bad_idx is not None:
+                    scores = scores.index_fill(1, bad_idx, float("-inf"))
+                if do_sample:
+                    scores = _warp(scores, temperature, top_k, top_p)
+                    nxt = torch.multinomial(torch.softmax(scores, -1), 1, generator=g)[:, 0]
+                else:
+                    nxt = scores.argmax(-1)
+                nxt = torch.where(done, torch.full_like(nxt, int(pad)), nxt)
+                new[:, step] = nxt
+                n = step + 1
+                if eos_t is not None:
+                    done |= torch.isin(nxt, eos_t)
+                    if (step % 16 == 15 or step + 1 == max_new_tokens) and bool(done.all()):
+                        break
+                if step + 1 < max_new_tokens:
+                    self.engine.decode_step(nxt.contiguous(), lens, B, logits)
         new = new[:, :n]
         if eos_t is not None and n > 1:
             # HF stops right after the step on which the last row finished: drop the all-pad columns behind it
@@ -901,6 +929,42 @@ class UnitLM(TokenLM):
                 n = int(all_done.nonzero()[0]) + 1
                 new = new[:, :n]
         return torch.cat([seq_in, new], 1)
+
+    def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids):
+        """The decode loop of generate(sampler="engine"): prefill, sample(step 0), then decode_step(next) / sample(step k). The
+        kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written."""
+        dev = self.device
+        B, V = logits.shape
+        max_new = new.shape[1]
+        if do_sample and seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())
+        desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=top_k if do_sample else 1,
+                                temperature=temperature if do_sample else 1.0, top_p=top_p if do_sample else 1.0,
+                                seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF, step=0, pad_id=pad, n_eos=len(eos))
+        ws = torch.empty(E.sample_workspace_bytes(B, V, desc.top_k), dtype=torch.uint8, device=dev)
+        banned = None
+        if bad:
+            banned = torch.zeros(V, dtype=torch.uint8, device=dev)
+            banned[torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev)] = 1
+        eos_i = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
+        row_ids = None
+        if sample_ids is not None:
+            row_ids = torch.as_tensor(sample_ids).to(dev, torch.int64).contiguous()
+            if row_ids.shape != (B,):
+                raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev)
+        self.engine.prefill(ids, lens, B, T, logits)
+        n = 0
+        for step in range(max_new):
+            desc.step = step
+            E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+            n = step + 1
+            if eos_i is not None and (step % 16 == 15 or n == max_new) and bool(done.all()):
+                break
+            if n < max_new:
+                self.engine.decode_step(nxt, lens, B, logits)
+        return n  # ws / banned / done were used on the current stream only: the allocator reuses them in stream order
 
     # ---- checkpoints (HF layout) ------------------------------------------------------------------
     def save_pretrained(self, save_directory: str, dtype=torch.bfloat16):

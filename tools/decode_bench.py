@@ -10,6 +10,11 @@ Prints one JSON line per measurement:
   floor_ms / floor_share   weight bytes / 6.3 TB/s (every weight is read once per step) and floor / step
   generate_s, reforward_s, speedup   end-to-end greedy generate vs a re-forward loop built here from `forward` (one full
                       forward over the whole sequence per new token), alternated within this call
+With --sampler torch,engine (and --do-sample: temperature 0.8, top_k 25, the reference's evaluation setting) only the end-to-end
+generate is measured, once per sampler and rep, alternating the samplers within this call: one line per sampler with
+`sampler`, `do_sample`, `generate_s` (median) and `generate_s_all`. --sample-op times the token choice alone at (B, V) =
+(8, 502), (8, 152167), (64, 152167), (1, 152167): `engine_us` = one slam_sample_tokens, `torch_us` = the torch sampler's
+per-step ops (bad words, warp, softmax, multinomial, pad, EOS bookkeeping), device events around 200 back-to-back calls.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -77,6 +82,88 @@ def step_bench(m, B, P, steps, tag):
              floor_ms=round(floor, 4), floor_share=round(floor / step, 3), weight_MB=round(wbytes / 1e6, 1), steps_timed=len(st))
     print(json.dumps(r), flush=True)
     return r
+
+
+def e2e_samplers(m, B, P, new, reps, tag, samplers, do_sample):
+    """generate_s of each sampler, alternated rep by rep."""
+    import torch
+    dev = m.device
+    g = torch.Generator(device=dev).manual_seed(1)
+    ids = torch.randint(2, m.config.vocab_size, (B, P), device=dev, generator=g)
+    kw = dict(input_ids=ids, max_new_tokens=new, eos_token_id=[])
+    if do_sample:
+        kw.update(do_sample=True, temperature=0.8, top_k=25, seed=11)
+    m._ensure_workspace(B * (-(-(P + new) // 64) * 64))
+    times = {s: [] for s in samplers}
+    for s in samplers:
+        m.generate(sampler=s, **kw)  # warm-up
+    for _ in range(reps):
+        for s in samplers:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.generate(sampler=s, **kw)
+            torch.cuda.synchronize()
+            times[s].append(time.perf_counter() - t0)
+    for s in samplers:
+        print(json.dumps(dict(bench="generate_e2e", model=tag, B=B, prompt=P, new_tokens=new, sampler=s, do_sample=bool(do_sample),
+                              generate_s=round(statistics.median(times[s]), 4),
+                              generate_s_all=[round(t, 4) for t in times[s]])), flush=True)
+
+
+def sample_op_bench(calls=200, rounds=5):
+    """Device-event time of the token choice alone: slam_sample_tokens against the torch sampler's per-step ops."""
+    import torch
+    from slamkit_amd import engine as E
+    from slamkit_amd.model.unit_lm import _warp
+    dev = torch.device("cuda")
+    for B, V in ((8, 502), (8, 152167), (64, 152167), (1, 152167)):
+        g = torch.Generator(device=dev).manual_seed(V + B)
+        logits = torch.randn(B, V, device=dev, generator=g) * 3.0
+        bad = torch.tensor([3, 4, 5], dtype=torch.long, device=dev)
+        banned = torch.zeros(V, dtype=torch.uint8, device=dev)
+        banned[bad] = 1
+        eos_t = torch.tensor([1], dtype=torch.long, device=dev)
+        eos_i = eos_t.to(torch.int32)
+        new = torch.empty(B, calls, dtype=torch.int64, device=dev)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev)
+        res = dict(bench="sample_op", B=B, vocab=V)
+        for do_sample in (0, 1):
+            desc = E.SlamSampleDesc(do_sample=do_sample, top_k=25, temperature=0.8, top_p=1.0, seed=11, step=0, pad_id=0, n_eos=1)
+            ws = torch.empty(E.sample_workspace_bytes(B, V, 25), dtype=torch.uint8, device=dev)
+            gen = torch.Generator(device=dev).manual_seed(11)
+
+            def engine_calls():
+                done = torch.zeros(B, dtype=torch.uint8, device=dev)
+                for k in range(calls):
+                    desc.step = k
+                    E.sample_tokens(logits, desc, nxt, ws, banned, None, eos_i, done, new)
+
+            def torch_calls():
+                done = torch.zeros(B, dtype=torch.bool, device=dev)
+                for k in range(calls):
+                    scores = logits.index_fill(1, bad, float("-inf"))
+                    if do_sample:
+                        scores = _warp(scores, 0.8, 25, 1.0)
+                        t = torch.multinomial(torch.softmax(scores, -1), 1, generator=gen)[:, 0]
+                    else:
+                        t = scores.argmax(-1)
+                    t = torch.where(done, torch.full_like(t, 0), t)
+                    new[:, k] = t
+                    done |= torch.isin(t, eos_t)
+
+            for name, fn in (("engine", engine_calls), ("torch", torch_calls)):
+                fn()
+                torch.cuda.synchronize()
+            te, tt = [], []
+            for _ in range(rounds):  # alternated
+                te.append(ev_ms(engine_calls) / calls * 1e3)
+                tt.append(ev_ms(torch_calls) / calls * 1e3)
+            tag = "sample" if do_sample else "greedy"
+            res[f"{tag}_engine_us"] = round(statistics.median(te), 2)
+            res[f"{tag}_torch_us"] = round(statistics.median(tt), 2)
+            res[f"{tag}_engine_us_minmax"] = [round(min(te), 2), round(max(te), 2)]
+            res[f"{tag}_torch_us_minmax"] = [round(min(tt), 2), round(max(tt), 2)]
+        print(json.dumps(res), flush=True)
 
 
 def e2e(m, B, P, new, reps, tag, reforward=True):
@@ -148,14 +235,25 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--no-reforward", action="store_true")
     ap.add_argument("--trace-summary", default=None)
+    ap.add_argument("--sampler", default=None, help="torch,engine: end-to-end generate per sampler, alternated")
+    ap.add_argument("--do-sample", action="store_true", help="with --sampler: temperature 0.8, top_k 25 instead of greedy")
+    ap.add_argument("--sample-op", action="store_true", help="time the token choice alone (engine vs torch ops)")
     a = ap.parse_args()
     if a.trace_summary:
         trace_summary(a.trace_summary)
         return
     import torch
     assert torch.cuda.is_available()
+    if a.sample_op:
+        sample_op_bench()
+        return
     for name in a.models.split(","):
         m = build(name, 4096)
+        if a.sampler:
+            e2e_samplers(m, 8, 256, a.steps, a.reps, name, a.sampler.split(","), a.do_sample)
+            del m
+            torch.cuda.empty_cache()
+            continue
         step_bench(m, 8, 256, a.steps, name)
         if name == "slam":
             step_bench(m, 96, 64, min(a.steps, 60), name)
