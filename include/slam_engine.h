@@ -119,6 +119,40 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
                  const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
                  float* loss_out, void* logits_out, slam_stream_t stream);
 
+/* ---- padding-free execution of right-padded batches (HF / TRL `padding_free`) ------------------------------------------------
+ * slam_forward runs a right-padded [B][T] batch position by position: every pad token goes through all layers, the head and
+ * the loss. slam_forward_unpadded runs the same batch as B segments of a flattened [1][M_packed] row - the layout of a packed
+ * batch - and skips the pads. ids / labels: int64 [B][T] device (labels nullable); lens: int32 [B] DEVICE, 1 <= lens[b] <= T
+ * (clamped to [0, T] as a memory guard: callers check their ranges); M_packed: chosen by the host, which knows the collated
+ * mask - a multiple of 64 with sum(lens) <= M_packed <= B * T rounded up to 64, and no more than the bound workspace tokens.
+ * One kernel packs the batch into `scratch` (caller-owned like the KV cache: 256-byte aligned, slam_unpadded_scratch_bytes(B, T)
+ * bytes, BORROWED until slam_backward and the calls below are done); with Mmax = B * T rounded up to 64 it holds
+ *   ids int64 [Mmax] | labels int64 [Mmax] | position_ids int64 [Mmax] | seg_start int32 [Mmax] | seg_end int32 [Mmax] |
+ *   row int32 [Mmax] | off int32 [B + 1]
+ * filled for m' < M_packed by the pack rule (off = exclusive prefix sum of lens): token (b, t), t < lens[b], goes to
+ * m' = off[b] + t with ids'[m'] = ids[b][t], labels'[m'] = t == 0 ? -100 : labels[b][t] (the loss targets labels'[m' + 1]:
+ * the flattening collator's rule), position_ids'[m'] = t, seg_start' = off[b], seg_end' = off[b + 1], row' = b. The tail
+ * [off[B], M_packed) is one dummy segment: the pad id (0 without one), labels -100, positions from 0, row -1. Then the layers,
+ * head and loss run exactly as slam_forward does for that packed row ("recompute", OPT's dropout, the logit mask,
+ * "grad_final_next" and the bucket callback carry over; the dropout mask is keyed on the PACKED element index, so a token's
+ * mask differs from the padded run's). num_items / loss_out as slam_forward. With non-ignored labels at pad positions
+ * slam_forward has loss terms for predicting pads; this path has none. logits_out (nullable): bf16 [B][T][vocab], real positions
+ * from their packed rows, pad positions zero. slam_backward needs no change. slam_last_forward_tokens: token rows the last
+ * forward of either kind executed (B * T, or M_packed), 0 without one.
+ * slam_seq_loglik_unpadded / slam_scale_loss_unpadded: slam_seq_loglik / slam_scale_loss_rows over the remembered segments
+ * (ll_out, cnt_out, seq_coef: fp32 [B] device; the tail's rows are scaled by 0). SLAM_ESTATE unless the last forward was an
+ * unpadded one over B rows (with labels); slam_seq_loglik / slam_scale_loss_rows after an unpadded forward are SLAM_ESTATE too.
+ * slam_op_unpad_pack: the pack kernel alone (no engine), same scratch layout. */
+size_t slam_unpadded_scratch_bytes(int32_t B, int32_t T);
+int slam_forward_unpadded(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T,
+                          int32_t M_packed, void* scratch, size_t scratch_bytes, double num_items, float* loss_out,
+                          void* logits_out, slam_stream_t stream);
+int64_t slam_last_forward_tokens(SlamEngine* h);
+int slam_seq_loglik_unpadded(SlamEngine* h, int32_t B, float* ll_out, float* cnt_out, slam_stream_t stream);
+int slam_scale_loss_unpadded(SlamEngine* h, const float* seq_coef, int32_t B, slam_stream_t stream);
+int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T, int32_t M_packed,
+                       int32_t pad_id, void* scratch, size_t scratch_bytes, slam_stream_t s);
+
 /* ---- KV-cached generation: HF GenerationMixin.generate with use_cache (the reference's speech_lm.py / metric_utils.py call
  * model.generate(input_ids, attention_mask, bad_words_ids, temperature, top_k, max_new_tokens)) ---------------------------
  * The cache is caller-owned like the workspace: bf16, per layer K[max_batch][n_kv_heads][capacity][head_dim] followed by V of

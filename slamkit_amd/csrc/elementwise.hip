@@ -938,6 +938,131 @@ __global__ __launch_bounds__(256) void scale_rows_bf16_kernel(bf16_t* __restrict
   *p = pack_bf16x8(f);
 }
 
+// ---- padding-free execution of right-padded batches (slam_forward_unpadded) ------------------------------------------
+// The pack rule in one launch, one thread per packed position m' in [0, Mp): token (b, t < lens[b]) goes to m' = off[b] + t
+// with off the exclusive prefix sum of lens; [off[B], Mp) is one dummy segment of pad tokens. Every block scans lens itself,
+// 256 rows at a time through LDS with the running total carried along, and a thread takes its row from the chunk whose
+// offsets bracket m' - no second launch, no atomics; block 0 also leaves off[] behind for the kernels below. lens are
+// clamped to [0, T] and segment ends to Mp (a memory guard: callers check their ranges). The 8-byte elements are gathered
+// from row starts of any alignment, so accesses are element-wide.
+// (Every block repeats the scan: B / 256 rounds of 8 barrier pairs per block, nothing at the callers' B of tens to hundreds.
+// Should B reach the thousands, scan once in a launch of its own and let the blocks read off[].)
+__global__ __launch_bounds__(256) void unpad_pack_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ labels,
+                                                         const int32_t* __restrict__ lens, int B, int T, int Mp, int64_t pad_id,
+                                                         int64_t* __restrict__ ids_p, int64_t* __restrict__ lab_p,
+                                                         int64_t* __restrict__ pos_p, int32_t* __restrict__ seg_s,
+                                                         int32_t* __restrict__ seg_e, int32_t* __restrict__ row_p,
+                                                         int32_t* __restrict__ off) {
+  __shared__ int sc[257];  // sc[i] = lens[c] + ... + lens[c + i - 1] of the current chunk
+  const int tid = threadIdx.x;
+  const int m = blockIdx.x * 256 + tid;
+  int base = 0, row = -1, s0 = 0, s1 = 0;
+  if (blockIdx.x == 0 && tid == 0) off[0] = 0;
+  for (int c = 0; c < B; c += 256) {
+    const int b = c + tid;
+    sc[tid + 1] = b < B ? min(max(lens[b], 0), T) : 0;
+    if (tid == 0) sc[0] = 0;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+      const int v = tid >= d ? sc[tid + 1 - d] : 0;
+      __syncthreads();
+      sc[tid + 1] += v;
+      __syncthreads();
+    }
+    if (blockIdx.x == 0 && b < B) off[b + 1] = base + sc[tid + 1];
+    const int total = sc[256];
+    if (row < 0 && m >= base && m < base + total) {
+      const int r = m - base;
+      int lo = 0, hi = 255;  // the last i with sc[i] <= r: its row holds r (empty rows share their offset with the next)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (sc[mid] <= r) lo = mid; else hi = mid - 1;
+      }
+      row = c + lo;
+      s0 = base + sc[lo];
+      s1 = base + sc[lo + 1];
+    }
+    base += total;
+    __syncthreads();
+  }
+  if (m >= Mp) return;
+  if (row >= 0) {
+    const int t = m - s0;
+    const size_t src = (size_t)row * T + t;
+    ids_p[m] = ids[src];
+    if (lab_p) lab_p[m] = t == 0 ? -100 : labels[src];
+    pos_p[m] = t;
+    seg_s[m] = s0;
+    seg_e[m] = min(s1, Mp);
+    row_p[m] = row;
+  } else {
+    ids_p[m] = pad_id;
+    if (lab_p) lab_p[m] = -100;
+    pos_p[m] = m - base;
+    seg_s[m] = base;
+    seg_e[m] = Mp;
+    row_p[m] = -1;
+  }
+}
+
+// Logits back in the batch's own layout: dst[b][t][0 .. V) = packed row off[b] + t for t < lens[b], zeros at the pad positions.
+// One thread per 16-byte chunk when V is a multiple of 8 (every dst row then starts 16-byte aligned), else per element.
+template <int W>
+__global__ __launch_bounds__(256) void unpad_logits_kernel(const bf16_t* __restrict__ src, int Vp, bf16_t* __restrict__ dst, int V,
+                                                           const int32_t* __restrict__ off, size_t BT, int T, int Mp) {
+  const int per = V / W;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= BT * per) return;
+  const size_t bt = idx / per;
+  const int c = (int)(idx % per) * W;
+  const int b = (int)(bt / T), t = (int)(bt % T);
+  const int o = off[b];
+  const bool real = t < off[b + 1] - o && o + t < Mp;  // (rows past Mp exist only when lens broke their contract)
+  if constexpr (W == 8) {
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (real) v = *reinterpret_cast<const uint4*>(src + (size_t)(o + t) * Vp + c);
+    *reinterpret_cast<uint4*>(dst + bt * V + c) = v;
+  } else {
+    dst[bt * V + c] = real ? src[(size_t)(o + t) * Vp + c] : (bf16_t)0;
+  }
+}
+
+// seq_loglik_kernel over packed segments: row b's targets are labels'[off[b] + t + 1] for t + 1 < lens[b]
+__global__ void seq_loglik_unpadded_kernel(const float* __restrict__ row_loss, const int64_t* __restrict__ labels,
+                                           const int32_t* __restrict__ off, int Mp, float* __restrict__ ll,
+                                           float* __restrict__ cnt) {
+  const int b = blockIdx.x;
+  __shared__ float rs[256], rc[256];
+  const int o = off[b], n = min(off[b + 1], Mp) - o;  // (clamped to the packed rows: a memory guard)
+  float s = 0.f, c = 0.f;
+  for (int t = threadIdx.x; t < n - 1; t += 256) {
+    if (labels[(size_t)o + t + 1] != -100) { s -= row_loss[(size_t)o + t]; c += 1.f; }
+  }
+  rs[threadIdx.x] = s; rc[threadIdx.x] = c;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if (threadIdx.x < k) { rs[threadIdx.x] += rs[threadIdx.x + k]; rc[threadIdx.x] += rc[threadIdx.x + k]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { ll[b] = rs[0]; cnt[b] = rc[0]; }
+}
+
+// dlogits[m'][:] *= coef[row of m'], the tail by 0 (scale_rows_bf16_kernel's m / T is a dense-row index)
+__global__ __launch_bounds__(256) void scale_rows_unpadded_bf16_kernel(bf16_t* __restrict__ x, const float* __restrict__ coef,
+                                                                       const int32_t* __restrict__ row, size_t M,
+                                                                       int chunks_per_row) {
+  size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= M * chunks_per_row) return;
+  const int r = row[i / chunks_per_row];
+  const float s = r >= 0 ? coef[r] : 0.f;
+  float f[8];
+  uint4* p = reinterpret_cast<uint4*>(x) + i;
+  unpack_bf16x8(*p, f);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] *= s;
+  *p = pack_bf16x8(f);
+}
+
 __global__ __launch_bounds__(256) void scale_bf16_kernel(bf16_t* __restrict__ x, size_t nchunks, float s) {
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= nchunks) return;
@@ -1153,6 +1278,48 @@ int copy_cols(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int M, int ncol
 int scale_rows_bf16(bf16_t* x, const float* coef, int M, int T, int ncols, hipStream_t st) {
   if (ncols & 7) return -1;
   scale_rows_bf16_kernel<<<nblocks((size_t)M * (ncols / 8), 256), 256, 0, st>>>(x, coef, (size_t)M, T, ncols / 8);
+  LAUNCH_RET();
+}
+static size_t unpad_mmax(int B, int T) { return (((size_t)B * T + 63) / 64) * 64; }
+size_t unpad_scratch_bytes(int B, int T) {
+  if (B <= 0 || T <= 0) return 0;
+  const size_t mm = unpad_mmax(B, T);  // a multiple of 64: every array below starts 256-byte aligned
+  return mm * (3 * sizeof(int64_t) + 3 * sizeof(int32_t)) + (((size_t)(B + 1) * sizeof(int32_t) + 255) & ~(size_t)255);
+}
+UnpadView unpad_view(void* scratch, int B, int T) {
+  const size_t mm = unpad_mmax(B, T);
+  UnpadView v;
+  v.ids = (int64_t*)scratch;
+  v.labels = v.ids + mm;
+  v.pos = v.labels + mm;
+  v.seg_s = (int32_t*)(v.pos + mm);
+  v.seg_e = v.seg_s + mm;
+  v.row = v.seg_e + mm;
+  v.off = v.row + mm;
+  return v;
+}
+int unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int B, int T, int Mp, int pad_id,
+               const UnpadView& v, hipStream_t st) {
+  if (B <= 0 || T <= 0 || Mp <= 0 || (size_t)Mp > unpad_mmax(B, T)) return -1;
+  unpad_pack_kernel<<<nblocks((size_t)Mp, 256), 256, 0, st>>>(ids, labels, lens, B, T, Mp, (int64_t)(pad_id > 0 ? pad_id : 0), v.ids,
+                                                              labels ? v.labels : nullptr, v.pos, v.seg_s, v.seg_e, v.row, v.off);
+  LAUNCH_RET();
+}
+int unpad_logits(const bf16_t* src, int Vp, bf16_t* dst, int V, const int32_t* off, int B, int T, int Mp, hipStream_t st) {
+  if (V <= 0 || V > Vp || (Vp & 7)) return -1;
+  const size_t BT = (size_t)B * T;
+  if (V % 8 == 0) unpad_logits_kernel<8><<<nblocks(BT * (V / 8), 256), 256, 0, st>>>(src, Vp, dst, V, off, BT, T, Mp);
+  else unpad_logits_kernel<1><<<nblocks(BT * V, 256), 256, 0, st>>>(src, Vp, dst, V, off, BT, T, Mp);
+  LAUNCH_RET();
+}
+int seq_loglik_unpadded(const float* row_loss, const int64_t* labels_packed, const int32_t* off, int B, int Mp, float* ll,
+                        float* cnt, hipStream_t st) {
+  seq_loglik_unpadded_kernel<<<B, 256, 0, st>>>(row_loss, labels_packed, off, Mp, ll, cnt);
+  LAUNCH_RET();
+}
+int scale_rows_unpadded_bf16(bf16_t* x, const float* coef, const int32_t* row, int Mp, int ncols, hipStream_t st) {
+  if (ncols & 7) return -1;
+  scale_rows_unpadded_bf16_kernel<<<nblocks((size_t)Mp * (ncols / 8), 256), 256, 0, st>>>(x, coef, row, (size_t)Mp, ncols / 8);
   LAUNCH_RET();
 }
 int scale_bf16(bf16_t* x, size_t n, float s, hipStream_t st) {

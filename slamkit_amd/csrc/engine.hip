@@ -224,6 +224,13 @@ struct SlamEngine {
   bool fuse_swiglu = false, fuse_dswiglu = true;
   bool fuse_adamw_t = true;  // "fuse_adamw_t": AdamW writes the transposed weight images itself (0: separate transpose pass)
   const int64_t* last_ids = nullptr;
+  // the last forward was slam_forward_unpadded over up_B x up_T: (B, T) = (1, M_packed), `up` its packed arrays (borrowed
+  // scratch) - slam_seq_loglik_unpadded / slam_scale_loss_unpadded read them, the dense-row forms are refused
+  bool unpadded = false;
+  UnpadView up{};
+  int up_B = 0, up_T = 0;
+  bool up_has_labels = false;
+  int64_t last_tokens = 0;  // token rows the last forward executed (slam_last_forward_tokens)
   const int* cur_seg_s = nullptr;
   const int* cur_seg_e = nullptr;
 
@@ -970,10 +977,11 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
   return h ? h->fail(SLAM_EINVAL, std::string("unknown option ") + key) : SLAM_EINVAL;
 }
 
-int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int64_t* position_ids,
-                 const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
-                 float* loss_out, void* logits_out, slam_stream_t stream) {
-  if (!h) return SLAM_EINVAL;
+// slam_forward, and the tail of slam_forward_unpadded: `up` = the packed arrays of a padding-free call over up_B x up_T (ids ..
+// seg_end then point into them and (B, T) = (1, M_packed)); its logits go back to the batch's own layout.
+static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int64_t* position_ids,
+                          const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
+                          float* loss_out, void* logits_out, const UnpadView* up, int up_B, int up_T, slam_stream_t stream) {
   // "dropout_call_next" arms this call and no other: a refused forward uses it up too, so no later one inherits it
   const int64_t armed_call = h->dropout_call_next;
   h->dropout_call_next = -1;
@@ -1004,7 +1012,8 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
   const int VP = h->vpad;
   TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_head, h->logits, nullptr, nullptr, M, VP, H, st));
   h->have_loss = false;
-  if (logits_out) CK(copy_cols(h->logits, VP, (bf16_t*)logits_out, d.vocab, M, d.vocab, st));
+  if (logits_out && up) CK(unpad_logits(h->logits, VP, (bf16_t*)logits_out, d.vocab, up->off, up_B, up_T, M, st));
+  else if (logits_out) CK(copy_cols(h->logits, VP, (bf16_t*)logits_out, d.vocab, M, d.vocab, st));
   if (labels) {
     TK(F_LOSS, st, cross_entropy(h->logits, labels, num_items, h->dlogits, h->row_loss, h->scal + 0, h->scal + 1, B, T, VP,
                      d.vocab, h->logit_mask, st));
@@ -1014,8 +1023,57 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
   h->B = B;
   h->T = T;
   h->last_ids = ids;
+  h->unpadded = up != nullptr;
+  if (up) { h->up = *up; h->up_B = up_B; h->up_T = up_T; h->up_has_labels = labels != nullptr; }
+  h->last_tokens = M;
   h->have_fwd = true;
   return SLAM_OK;
+}
+
+int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int64_t* position_ids,
+                 const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
+                 float* loss_out, void* logits_out, slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  return forward_common(h, ids, labels, position_ids, seg_start, seg_end, B, T, num_items, loss_out, logits_out, nullptr, 0, 0,
+                        stream);
+}
+
+size_t slam_unpadded_scratch_bytes(int32_t B, int32_t T) {
+  if (B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffc0LL) return 0;
+  return unpad_scratch_bytes(B, T);
+}
+
+int slam_forward_unpadded(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T,
+                          int32_t M_packed, void* scratch, size_t scratch_bytes, double num_items, float* loss_out,
+                          void* logits_out, slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  const int64_t armed_call = h->dropout_call_next;  // a refused call uses the arming up, as slam_forward does
+  auto refuse = [&](int code, const char* m) { h->dropout_call_next = -1; return h->fail(code, m); };
+  if (!ids || !lens || !scratch || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffc0LL) return refuse(SLAM_EINVAL, "forward_unpadded: bad argument");
+  const int64_t mmax = (((int64_t)B * T + 63) / 64) * 64;
+  if (M_packed <= 0 || (M_packed & 63) || M_packed > mmax) return refuse(SLAM_EINVAL, "M_packed must be a multiple of 64 in (0, B*T rounded up to 64]");
+  if (((uintptr_t)scratch & 255) || scratch_bytes < unpad_scratch_bytes(B, T)) return refuse(SLAM_EINVAL, "scratch: 256-byte aligned, slam_unpadded_scratch_bytes(B, T) bytes");
+  if (!h->params || !h->ws) return refuse(SLAM_ESTATE, "bind params and workspace first");
+  if (M_packed > h->max_tokens) return refuse(SLAM_ENOMEM, "M_packed exceeds bound workspace tokens");
+  if (labels && !loss_out) return refuse(SLAM_EINVAL, "labels given without loss_out");
+  h->have_fwd = false;
+  const UnpadView v = unpad_view(scratch, B, T);
+  int rc = unpad_pack(ids, labels, lens, B, T, M_packed, h->d.pad_token_id, v, (hipStream_t)stream);
+  if (rc != 0) { h->dropout_call_next = -1; return rc; }
+  h->dropout_call_next = armed_call;
+  return forward_common(h, v.ids, labels ? v.labels : nullptr, v.pos, v.seg_s, v.seg_e, 1, M_packed, num_items, loss_out, logits_out,
+                        &v, B, T, stream);
+}
+
+int64_t slam_last_forward_tokens(SlamEngine* h) { return h && h->have_fwd ? h->last_tokens : 0; }
+
+int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T, int32_t M_packed,
+                       int32_t pad_id, void* scratch, size_t scratch_bytes, slam_stream_t s) {
+  if (!ids || !lens || !scratch || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffc0LL) return SLAM_EINVAL;
+  const int64_t mmax = (((int64_t)B * T + 63) / 64) * 64;
+  if (M_packed <= 0 || (M_packed & 63) || M_packed > mmax) return SLAM_EINVAL;
+  if (((uintptr_t)scratch & 255) || scratch_bytes < unpad_scratch_bytes(B, T)) return SLAM_EINVAL;
+  return unpad_pack(ids, labels, lens, B, T, M_packed, pad_id, unpad_view(scratch, B, T), (hipStream_t)s);
 }
 
 /* ---- KV-cached generation ---------------------------------------------------------------------------------------------*/
@@ -1481,15 +1539,33 @@ int32_t slam_padded_vocab(SlamEngine* h) { return h ? h->vpad : 0; }
 int slam_seq_loglik(SlamEngine* h, const int64_t* labels, int32_t B, int32_t T, float* ll_out, float* cnt_out,
                     slam_stream_t stream) {
   if (!h || !labels || !ll_out || !cnt_out) return SLAM_EINVAL;
+  if (h->have_fwd && h->unpadded) return h->fail(SLAM_ESTATE, "seq_loglik after an unpadded forward: use slam_seq_loglik_unpadded");
   if (!h->have_fwd || B != h->B || T != h->T) return h->fail(SLAM_ESTATE, "seq_loglik needs the matching forward");
   CK(seq_loglik(h->row_loss, labels, B, T, ll_out, cnt_out, (hipStream_t)stream));
   return SLAM_OK;
 }
 
+int slam_seq_loglik_unpadded(SlamEngine* h, int32_t B, float* ll_out, float* cnt_out, slam_stream_t stream) {
+  if (!h || !ll_out || !cnt_out) return SLAM_EINVAL;
+  if (!h->have_fwd || !h->unpadded || !h->up_has_labels || B != h->up_B)
+    return h->fail(SLAM_ESTATE, "seq_loglik_unpadded needs the matching unpadded forward with labels");
+  CK(seq_loglik_unpadded(h->row_loss, h->up.labels, h->up.off, B, h->B * h->T, ll_out, cnt_out, (hipStream_t)stream));
+  return SLAM_OK;
+}
+
 int slam_scale_loss_rows(SlamEngine* h, const float* seq_coef, int32_t B, int32_t T, slam_stream_t stream) {
   if (!h || !seq_coef) return SLAM_EINVAL;
+  if (h->have_loss && h->unpadded) return h->fail(SLAM_ESTATE, "scale_loss_rows after an unpadded forward: use slam_scale_loss_unpadded");
   if (!h->have_loss || B != h->B || T != h->T) return h->fail(SLAM_ESTATE, "scale_loss_rows needs the matching forward with labels");
   CK(scale_rows_bf16(h->dlogits, seq_coef, B * T, T, h->vpad, (hipStream_t)stream));
+  return SLAM_OK;
+}
+
+int slam_scale_loss_unpadded(SlamEngine* h, const float* seq_coef, int32_t B, slam_stream_t stream) {
+  if (!h || !seq_coef) return SLAM_EINVAL;
+  if (!h->have_fwd || !h->have_loss || !h->unpadded || B != h->up_B)
+    return h->fail(SLAM_ESTATE, "scale_loss_unpadded needs the matching unpadded forward with labels");
+  CK(scale_rows_unpadded_bf16(h->dlogits, seq_coef, h->up.row, h->B * h->T, h->vpad, (hipStream_t)stream));
   return SLAM_OK;
 }
 

@@ -158,6 +158,25 @@ int seq_loglik(const float* row_loss, const int64_t* labels, int B, int T, float
 int copy_cols(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int M, int ncols, hipStream_t st);
 int scale_bf16(bf16_t* x, size_t n, float s, hipStream_t st);
 int scale_rows_bf16(bf16_t* x, const float* coef, int M, int T, int ncols, hipStream_t st);
+// Padding-free execution of right-padded [B][T] batches (include/slam_engine.h, slam_forward_unpadded): the packed arrays of
+// one batch in caller-owned scratch, every array 256-byte aligned. Mmax = B * T rounded up to 64.
+struct UnpadView {
+  int64_t *ids, *labels, *pos;  // [Mmax]
+  int32_t *seg_s, *seg_e, *row;  // [Mmax]; row = the token's batch row, -1 in the tail
+  int32_t* off;                  // [B + 1] exclusive prefix sum of lens
+};
+size_t unpad_scratch_bytes(int B, int T);
+UnpadView unpad_view(void* scratch, int B, int T);
+// one launch: the pack rule over m' in [0, Mp); labels nullable (v.labels is then left alone)
+int unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int B, int T, int Mp, int pad_id,
+               const UnpadView& v, hipStream_t st);
+// dst[b][t][0 .. V) = t < lens[b] ? src[off[b] + t][0 .. V) : 0   (src: Mp rows, Vp long)
+int unpad_logits(const bf16_t* src, int Vp, bf16_t* dst, int V, const int32_t* off, int B, int T, int Mp, hipStream_t st);
+// per-row sums of -row_loss over valid targets and their counts, over the packed segments (seq_loglik's reduction)
+int seq_loglik_unpadded(const float* row_loss, const int64_t* labels_packed, const int32_t* off, int B, int Mp, float* ll,
+                        float* cnt, hipStream_t st);
+// x[m'][:] *= row[m'] >= 0 ? coef[row[m']] : 0
+int scale_rows_unpadded_bf16(bf16_t* x, const float* coef, const int32_t* row, int Mp, int ncols, hipStream_t st);
 int grad_chunk_elems();
 int grad_sumsq_chunks(const void* g, int g_bf16, size_t n, size_t off, size_t cnt, float* chunk_sums, hipStream_t st);
 int grad_norm_from_chunks(const float* chunk_sums, size_t n_chunks, float max_norm, float* out, hipStream_t st);

@@ -77,6 +77,12 @@ def load_library(path: Optional[str] = None):
         "slam_workspace_bytes": (sz, [vp, i64]),
         "slam_bind_workspace": (C.c_int, [vp, vp, sz, i64]),
         "slam_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
+        "slam_unpadded_scratch_bytes": (sz, [i32, i32]),
+        "slam_forward_unpadded": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, sz, f64, vp, vp, vp]),
+        "slam_last_forward_tokens": (i64, [vp]),
+        "slam_seq_loglik_unpadded": (C.c_int, [vp, i32, vp, vp, vp]),
+        "slam_scale_loss_unpadded": (C.c_int, [vp, vp, i32, vp]),
+        "slam_op_unpad_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
         "slam_backward": (C.c_int, [vp, f32, i32, BUCKET_CB, vp, vp]),
         "slam_kv_cache_bytes": (sz, [vp, i32, i32]),
         "slam_bind_kv_cache": (C.c_int, [vp, vp, sz, i32, i32]),
@@ -204,6 +210,36 @@ def sample_tokens(logits, desc: SlamSampleDesc, next_ids, ws, banned=None, row_i
         raise EngineError(f"slam_sample_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
+def unpadded_scratch_bytes(B: int, T: int) -> int:
+    """Bytes of device scratch slam_forward_unpadded / slam_op_unpad_pack need for a [B, T] batch (host arithmetic)."""
+    return int(load_library().slam_unpadded_scratch_bytes(int(B), int(T)))
+
+
+def unpadded_scratch_views(scratch, B: int, T: int) -> Dict[str, "object"]:
+    """The arrays of the packed batch inside `scratch` (a uint8 device tensor, 256-byte aligned), as include/slam_engine.h lays
+    them out: ids, labels, position_ids int64 [Mmax]; seg_start, seg_end, row int32 [Mmax]; off int32 [B + 1]."""
+    import torch
+    mm = -(-(B * T) // 64) * 64
+    out, o = {}, 0
+    for name, dt, n in (("ids", torch.int64, mm), ("labels", torch.int64, mm), ("position_ids", torch.int64, mm),
+                        ("seg_start", torch.int32, mm), ("seg_end", torch.int32, mm), ("row", torch.int32, mm),
+                        ("off", torch.int32, B + 1)):
+        nb = n * (8 if dt == torch.int64 else 4)
+        out[name] = scratch[o:o + nb].view(dt)
+        o += nb
+    return out
+
+
+def unpad_pack(ids, labels, lens, B: int, T: int, M_packed: int, pad_id: int, scratch, stream: Optional[int] = None):
+    """slam_op_unpad_pack: the pack kernel of the padding-free forward on its own (ids / labels int64 [B, T], lens int32 [B],
+    all device tensors; labels may be None). Read the result with unpadded_scratch_views."""
+    rc = load_library().slam_op_unpad_pack(_ptr(ids), _ptr(labels), _ptr(lens), int(B), int(T), int(M_packed), int(pad_id),
+                                           _ptr(scratch), scratch.numel() * scratch.element_size(),
+                                           stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_op_unpad_pack failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
 @dataclass
 class TensorSpec:
     name: str
@@ -301,6 +337,28 @@ class Engine:
         self._ck(self.lib.slam_forward(self.h, _ptr(ids), _ptr(labels), _ptr(position_ids), _ptr(seg_start),
                                        _ptr(seg_end), B, T, float(num_items), _ptr(loss_out), _ptr(logits_out),
                                        stream if stream is not None else current_stream_ptr()))
+
+    def forward_unpadded(self, ids, labels, lens, B: int, T: int, M_packed: int, scratch, num_items: float = 0.0,
+                         loss_out=None, logits_out=None, stream: Optional[int] = None):
+        """slam_forward_unpadded: the right-padded [B, T] batch run as B segments of M_packed packed tokens. lens int32 [B] on
+        the device; scratch: uint8 device tensor of unpadded_scratch_bytes(B, T), 256-byte aligned, kept alive here (the
+        engine borrows it until backward)."""
+        self._keep["unpad_scratch"] = scratch
+        self._ck(self.lib.slam_forward_unpadded(self.h, _ptr(ids), _ptr(labels), _ptr(lens), B, T, int(M_packed), _ptr(scratch),
+                                                scratch.numel() * scratch.element_size(), float(num_items), _ptr(loss_out),
+                                                _ptr(logits_out), stream if stream is not None else current_stream_ptr()))
+
+    def last_forward_tokens(self) -> int:
+        """Token rows the last forward executed: B * T of a padded call, M_packed of an unpadded one (0 without a forward)."""
+        return int(self.lib.slam_last_forward_tokens(self.h))
+
+    def seq_loglik_unpadded(self, B, ll_out, cnt_out, stream=None):
+        self._ck(self.lib.slam_seq_loglik_unpadded(self.h, B, _ptr(ll_out), _ptr(cnt_out),
+                                                   stream if stream is not None else current_stream_ptr()))
+
+    def scale_loss_unpadded(self, seq_coef, B, stream=None):
+        self._ck(self.lib.slam_scale_loss_unpadded(self.h, _ptr(seq_coef), B,
+                                                   stream if stream is not None else current_stream_ptr()))
 
     def backward(self, grad_scale: float = 1.0, bucket_layers: int = 0,
                  bucket_cb: Optional[Callable[[int, int], None]] = None, stream: Optional[int] = None, final: int = 0):

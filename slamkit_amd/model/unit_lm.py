@@ -341,6 +341,11 @@ class UnitLM(TokenLM):
             if v is not None:
                 self.engine.set_option(opt, int(v))
         self.training = True
+        # padding-free execution (HF / TRL `padding_free`): right-padded batches whose row lengths the host knows run as packed
+        # segments and skip their pads (slam_forward_unpadded). Off by default; the trainers set it from their arguments.
+        self.padding_free = False
+        self._last_unpadded = False
+        self._unpad_buf = None
         self._build_key_map()
         self.init_weights(seed)
         if config.twist_init and not _from_pretrained:
@@ -666,10 +671,21 @@ class UnitLM(TokenLM):
 
     def forward(self, input_ids: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
-                num_items_in_batch=None, return_logits: bool = True, **unused) -> CausalLMOutput:
+                num_items_in_batch=None, return_logits: bool = True, padding_free: Optional[bool] = None, lengths=None,
+                **unused) -> CausalLMOutput:
         """UnitLM.forward (unit_lm.py:135-182). `attention_mask` must be right padding (what
         DataCollatorForLanguageModeling produces): under the causal mask it never changes a real
-        token's output, so the engine does not read it."""
+        token's output, so the engine does not read it.
+
+        `padding_free` (None = `self.padding_free`, False by default): a [B, T] batch without `position_ids` whose row lengths
+        are known ON THE HOST - from a host `attention_mask`, or from `lengths` (a list or CPU tensor of B ints in 1 .. T) -
+        runs as B packed segments of sum(lengths) tokens (rounded up to 64) instead of B * T positions: the pads are never
+        executed. A device mask without `lengths` keeps the padded path (the hot loop does not read it back), and so does a
+        batch that carries `position_ids` (the flattening collator's, already packed). Loss, logits ([B, T, V], zeros at pad
+        positions), `num_items_in_batch` and backward behave as on the padded path, within rounding. Two differences: `labels`
+        that are not -100 at pad positions add loss terms for predicting pads on the padded path and none here; and OPT's
+        dropout mask is keyed on the element index of the layout the forward runs, so a token's mask differs from the padded
+        run's (still a pure function of seed, call, layer, site and packed index)."""
         assert input_ids is not None and input_ids.dim() == 2
         B, T = input_ids.shape
         if attention_mask is not None and not attention_mask.is_cuda and not _right_padded(attention_mask):
@@ -687,6 +703,11 @@ class UnitLM(TokenLM):
         nb = not input_ids.is_cuda and input_ids.is_pinned()  # pinned host batches (the trainer's prefetch thread): async H2D
         ids = input_ids.to(dev, torch.int64, non_blocking=nb)
         lab = labels.to(dev, torch.int64, non_blocking=nb) if labels is not None else None
+        if (self.padding_free if padding_free is None else padding_free) and position_ids is None:
+            lens = self._host_lengths(B, T, attention_mask, lengths)
+            if lens is not None:
+                return self._forward_unpadded(ids, lab, lens, num_items_in_batch, return_logits)
+        self._last_unpadded = False
         pos = position_ids.to(dev, torch.int64, non_blocking=nb) if position_ids is not None else None
         # The LDS-DMA wgrad path needs a token count that is a multiple of 64; collated batches have arbitrary lengths.
         # Right-pad the token axis with pad ids / ignored labels (a dummy trailing segment for packed rows): under the
@@ -727,6 +748,72 @@ class UnitLM(TokenLM):
 
     __call__ = forward
 
+    # ---- padding-free execution ----------------------------------------------------------------------
+    @staticmethod
+    def _host_lengths(B: int, T: int, attention_mask=None, lengths=None) -> Optional[torch.Tensor]:
+        """Row lengths (int32 CPU tensor [B]) when the host knows them: `lengths`, else a host attention_mask (right padding
+        was checked by the caller). None = unknown (a device mask is never read back)."""
+        if lengths is not None:
+            if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+                raise ValueError("lengths must live on the host (a list or a CPU tensor): reading them back would stall the step")
+            lens = torch.as_tensor(lengths).to(torch.int64).reshape(-1)
+        elif attention_mask is not None and not attention_mask.is_cuda:
+            lens = (attention_mask != 0).sum(1).to(torch.int64)
+        else:
+            return None
+        if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > T:
+            raise ValueError(f"padding_free needs {B} row lengths in 1 .. {T}")
+        if isinstance(lengths, torch.Tensor) and lengths.dtype == torch.int32 and lengths.dim() == 1:
+            return lengths  # as handed over: a pinned tensor (the trainer's prefetch pins DPO's collated lengths) stays pinned
+        return lens.to(torch.int32)
+
+    def _unpad_scratch(self, B: int, T: int) -> torch.Tensor:
+        """The packed batch's arrays live here until backward (slam_unpadded_scratch_bytes; grown, never shrunk)."""
+        nbytes = E.unpadded_scratch_bytes(B, T)
+        if self._unpad_buf is None or self._unpad_buf.numel() < nbytes + 256:
+            self._unpad_buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+        off = (-self._unpad_buf.data_ptr()) % 256
+        return self._unpad_buf[off:off + nbytes]
+
+    def _run_unpadded(self, ids, lab, lens: torch.Tensor, num_items: float, logits=None):
+        """slam_forward_unpadded over the device batch ids / lab [B, T] with host lengths `lens`. The workspace is sized by
+        B * T (rounded up to 64), not by this step's packed count, so it is never rebound from step to step."""
+        B, T = ids.shape
+        m_packed = -(-int(lens.sum()) // 64) * 64
+        self._ensure_workspace(-(-(B * T) // 64) * 64)
+        scratch = self._unpad_scratch(B, T)
+        # through pinned memory (the caching host allocator hands the block out again only after the copy has run): the
+        # hot loop has no blocking pageable copy of its own
+        lens_dev = (lens if lens.is_pinned() else lens.pin_memory()).to(self.device, non_blocking=True)
+        self._hold = (ids, lab, lens_dev, scratch)  # the engine borrows these until backward
+        self._last_unpadded = True
+        self.engine.forward_unpadded(ids, lab, lens_dev, B, T, m_packed, scratch, num_items,
+                                     self._loss_buf if lab is not None else None, logits)
+
+    def _forward_unpadded(self, ids, lab, lens, num_items_in_batch, return_logits) -> CausalLMOutput:
+        B, T = ids.shape
+        ids = ids.contiguous()
+        lab = lab.contiguous() if lab is not None else None
+        logits = torch.empty(B, T, self.config.vocab_size, dtype=torch.bfloat16, device=self.device) if return_logits else None
+        if isinstance(num_items_in_batch, torch.Tensor):
+            num_items_in_batch = float(num_items_in_batch)
+        if self.training and self._drop_thr:  # as forward(): this call only
+            self.engine.arm_dropout(self._drop_call & 0xFFFFFFFF)
+            self._drop_call += 1
+        self._run_unpadded(ids, lab, lens, float(num_items_in_batch) if num_items_in_batch else 0.0, logits)
+        loss = None
+        if lab is not None:
+            loss = _EngineLoss.apply(self._anchor, self, self._loss_buf) if torch.is_grad_enabled() else self._loss_buf.clone()
+        return CausalLMOutput(loss=loss, logits=logits)
+
+    def _lengths_from_pad(self, ids: torch.Tensor) -> torch.Tensor:
+        """Row lengths of right-padded token rows from pad_token_id: index of the last non-pad token + 1, at least 1 (pad ids
+        inside a row stay in the row). One read-back when `ids` is on the device."""
+        T = ids.shape[1]
+        real = ids != self.config.pad_token_id
+        last = torch.where(real, torch.arange(1, T + 1, device=ids.device)[None], torch.zeros_like(ids)).amax(1)
+        return last.clamp_(min=1).to(torch.int32).cpu()
+
     def backward(self, grad_scale: float = 1.0, bucket_layers: int = 0, bucket_cb=None, final: int = 0):
         """d(loss * grad_scale)/dparams accumulated into `flat_grads` (fp32). final = 1 | 2 marks the last backward of an
         optimizer step (engine option "grad_final_next"): the gradient-norm partials come out of the final-value stores, and
@@ -741,45 +828,69 @@ class UnitLM(TokenLM):
         self.engine.zero_grads()
 
     @torch.no_grad()
-    def log_likelihood(self, tokens: torch.Tensor, mean_nll: bool, ignore_tokens: Optional[List[int]] = None) -> torch.Tensor:
+    def log_likelihood(self, tokens: torch.Tensor, mean_nll: bool, ignore_tokens: Optional[List[int]] = None,
+                       padding_free: Optional[bool] = None) -> torch.Tensor:
         """unit_lm.py:184-194 + calc_nll (calculation_utils.py:5-29): pad -> -100, per-sequence
-        sum (or mean) of target log-probs."""
+        sum (or mean) of target log-probs. `padding_free` (None = `self.padding_free`): the rows run as packed segments of
+        their own lengths, taken from pad_token_id (one read-back per call when `tokens` is on the device)."""
         B, T = tokens.shape
         self._check_positions(T)
+        pf = self.padding_free if padding_free is None else padding_free
+        lens = self._lengths_from_pad(tokens) if pf else None
         ids = tokens.to(self.device, torch.int64).contiguous()
         lab = ids.clone()
         lab[lab == self.config.pad_token_id] = -100
-        self._ensure_workspace(B * T)
-        self._hold = (ids, lab)
+        if not pf:
+            self._ensure_workspace(B * T)
+            self._hold = (ids, lab)
+            self._last_unpadded = False
         mask = None
         if ignore_tokens is not None:  # logits[:, :, ignore_tokens] = -inf (unit_lm.py:187-188), done inside the CE kernel
             mask = torch.zeros(self.engine.padded_vocab(), dtype=torch.uint8, device=self.device)
             mask[torch.as_tensor(list(ignore_tokens), dtype=torch.long, device=self.device)] = 1
             self.engine.set_logit_mask(mask)
         try:
-            self.engine.forward(ids, lab, None, None, None, B, T, 0.0, self._loss_buf, None)
+            if pf:
+                self._run_unpadded(ids, lab, lens, 0.0)
+            else:
+                self.engine.forward(ids, lab, None, None, None, B, T, 0.0, self._loss_buf, None)
         finally:
             if mask is not None:
                 torch.cuda.current_stream(self.device).synchronize()  # the kernel reads the mask: keep it alive until done
                 self.engine.set_logit_mask(None)
         ll = torch.empty(B, dtype=torch.float32, device=self.device)
         cnt = torch.empty(B, dtype=torch.float32, device=self.device)
-        self.engine.seq_loglik(lab, B, T, ll, cnt)
+        if pf:
+            self.engine.seq_loglik_unpadded(B, ll, cnt)
+        else:
+            self.engine.seq_loglik(lab, B, T, ll, cnt)
         return ll / cnt if mean_nll else ll
 
-    def sequence_logps(self, input_ids: torch.Tensor, labels: torch.Tensor):
+    def sequence_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, padding_free: Optional[bool] = None, lengths=None):
         """Per-sequence sums of target log-probs over the non-ignored labels (what TRL's DPOTrainer calls
         `chosen_logps` / `rejected_logps`). Leaves the engine ready for `scale_loss_rows` + `backward`:
-        d(-logp_b)/dlogits is stored unscaled (num_items = 1)."""
+        d(-logp_b)/dlogits is stored unscaled (num_items = 1). `padding_free` (None = `self.padding_free`) with host `lengths`
+        (list or CPU tensor; without them, taken from pad_token_id when `input_ids` is on the host) runs the rows as packed
+        segments; a device batch without `lengths` keeps the padded path."""
         B, T = input_ids.shape
         self._check_positions(T)
+        lens = None
+        if self.padding_free if padding_free is None else padding_free:
+            if lengths is None and not input_ids.is_cuda:
+                lengths = self._lengths_from_pad(input_ids)
+            lens = self._host_lengths(B, T, None, lengths)
         ids = input_ids.to(self.device, torch.int64).contiguous()
         lab = labels.to(self.device, torch.int64).contiguous()
-        self._ensure_workspace(B * T)
-        self._hold = (ids, lab)
-        self.engine.forward(ids, lab, None, None, None, B, T, 1.0, self._loss_buf, None)
         ll = torch.empty(B, dtype=torch.float32, device=self.device)
         cnt = torch.empty(B, dtype=torch.float32, device=self.device)
+        if lens is not None:
+            self._run_unpadded(ids, lab, lens, 1.0)
+            self.engine.seq_loglik_unpadded(B, ll, cnt)
+            return ll, cnt
+        self._ensure_workspace(B * T)
+        self._hold = (ids, lab)
+        self._last_unpadded = False
+        self.engine.forward(ids, lab, None, None, None, B, T, 1.0, self._loss_buf, None)
         self.engine.seq_loglik(lab, B, T, ll, cnt)
         return ll, cnt
 
@@ -787,7 +898,10 @@ class UnitLM(TokenLM):
         """Backward of sum_b seq_coef[b] * (-logp_b): seq_coef = d loss / d(-logp_b)."""
         coef = seq_coef.to(self.device, torch.float32).contiguous()
         self._hold = self._hold + (coef,)
-        self.engine.scale_loss_rows(coef, B, T)
+        if self._last_unpadded:
+            self.engine.scale_loss_unpadded(coef, B)
+        else:
+            self.engine.scale_loss_rows(coef, B, T)
         self.engine.backward(grad_scale, kw.get("bucket_layers", 0), kw.get("bucket_cb"))
         self._grads_in_bf16 = False
 

@@ -58,6 +58,8 @@ class SLAMDPOTrainer(SLAMTrainer):
         super().__init__(model=model, args=args, data_collator=self._collate_pairs, train_dataset=tok(train_dataset),
                          eval_dataset=tok(eval_dataset), processing_class=processing_class, callbacks=callbacks)
         self.ref_model = ref_model
+        if ref_model is not None and hasattr(ref_model, "padding_free") and getattr(args, "padding_free", False):
+            ref_model.padding_free = True  # the policy was switched on by SLAMTrainer.__init__
         self.pad_id = model.config.pad_token_id
         self._loss_is_rank_mean = True  # each rank accumulates the mean DPO loss of its own pairs
 
@@ -79,7 +81,13 @@ class SLAMDPOTrainer(SLAMTrainer):
         for i, (s, l) in enumerate(zip(seqs, labs)):
             ids[i, : len(s)] = torch.tensor(s)
             lab[i, : len(l)] = torch.tensor(l)
-        return {"input_ids": ids, "labels": lab}
+        # row lengths, on the host: what a padding-free model needs to run the rows as packed segments (unused otherwise)
+        return {"input_ids": ids, "labels": lab, "lengths": torch.tensor([len(s) for s in seqs], dtype=torch.int32)}
+
+    @staticmethod
+    def _lengths_kw(model, mb) -> dict:
+        """The collated row lengths, for a padding-free model only (the padded call is exactly what it was)."""
+        return {"lengths": mb["lengths"]} if getattr(model, "padding_free", False) and "lengths" in mb else {}
 
     @staticmethod
     def dpo_loss(pi_c, pi_r, ref_c, ref_r, beta: float):
@@ -94,9 +102,9 @@ class SLAMDPOTrainer(SLAMTrainer):
             B2, T = ids.shape
             n = B2 // 2
             with torch.no_grad():
-                ref, _ = self.ref_model.sequence_logps(ids, lab)
+                ref, _ = self.ref_model.sequence_logps(ids, lab, **self._lengths_kw(self.ref_model, mb))
                 ref = ref.clone()
-            pol, _ = self.model.sequence_logps(ids, lab)
+            pol, _ = self.model.sequence_logps(ids, lab, **self._lengths_kw(self.model, mb))
             losses, x = self.dpo_loss(pol[:n], pol[n:], ref[:n], ref[n:], a.beta)
             # d mean(loss) / d(-logp): chosen +beta*sigmoid(-x)/n, rejected -beta*sigmoid(-x)/n
             g = a.beta * torch.sigmoid(-x) / (n * nm * self.world)
@@ -139,9 +147,9 @@ class SLAMDPOTrainer(SLAMTrainer):
             mb = self._collate_pairs([ds[i] for i in b])
             ids, lab = mb["input_ids"], mb["labels"]
             n = ids.shape[0] // 2
-            ref, _ = self.ref_model.sequence_logps(ids, lab)
+            ref, _ = self.ref_model.sequence_logps(ids, lab, **self._lengths_kw(self.ref_model, mb))
             ref = ref.clone()
-            pol, _ = self.model.sequence_logps(ids, lab)
+            pol, _ = self.model.sequence_logps(ids, lab, **self._lengths_kw(self.model, mb))
             losses, x = self.dpo_loss(pol[:n], pol[n:], ref[:n], ref[n:], self.args.beta)
             acc += torch.stack([losses.sum(), (x > 0).sum().to(losses.dtype), x.sum(), x.new_tensor(float(n))]).double()
         if self.world > 1:

@@ -59,6 +59,10 @@ class SLAMTrainer:
         rc_level = self.args.get_recompute_level() if hasattr(self.args, "get_recompute_level") else 0
         if rc_level:
             model.gradient_checkpointing_enable(level=rc_level)
+        # padding-free execution of right-padded batches (UnitLM.padding_free): training steps and evaluate() alike. The
+        # argument switches it ON; a model whose owner switched it on already keeps it (the default False never switches off)
+        if hasattr(model, "padding_free") and getattr(self.args, "padding_free", False):
+            model.padding_free = True
         dev = model.device
         n = model.engine.n_params
         osd = getattr(self.args, "optim_state_dtype", "float32") or "float32"
@@ -507,8 +511,10 @@ class SLAMTrainer:
                 n = float(((mb["labels"][:, 1:]) != -100).sum())
                 if n == 0:
                     continue
-                out = self.model.forward(input_ids=mb["input_ids"], position_ids=mb.get("position_ids"), labels=mb["labels"],
-                                         num_items_in_batch=1.0, return_logits=False)
+                # the collated mask is what gives a padding-free model its row lengths; the padded path never reads it
+                am = mb.get("attention_mask") if getattr(self.model, "padding_free", False) else None
+                out = self.model.forward(input_ids=mb["input_ids"], attention_mask=am, position_ids=mb.get("position_ids"),
+                                         labels=mb["labels"], num_items_in_batch=1.0, return_logits=False)
                 tot += out.loss.double()
                 cnt += n
         finally:

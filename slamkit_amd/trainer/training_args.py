@@ -43,6 +43,7 @@ class SLAMTrainingArguments:
     overlap_optimizer: bool = False                # AdamW of the later layers under the next step's first layers (measured neutral: 272.7 vs 273.9 k tok/s)
     gradient_checkpointing: bool = False           # HF's field: recompute each layer's forward in backward (engine option "recompute" = 2) - the activations of 3 layers instead of all; same bits, about a quarter more step time
     recompute_level: Optional[int] = None          # overrides gradient_checkpointing: 1 = selective (norm outputs and the MLP activation only), 2 = full layer
+    padding_free: bool = False                     # HF / TRL's name: right-padded batches (the default collator's, DPO's pairs, evaluation) run as packed segments of their own lengths and skip the pad positions (slam_forward_unpadded; UnitLM.padding_free). True switches the models on; False (the default) leaves a model's own switch alone. Same losses within rounding; OPT's dropout masks follow the packed layout
     dataloader_num_workers: int = 0                # > 0: one background thread collates up to two optimizer steps ahead into pinned host memory (SLAMTrainer._micro_batches)
     min_token_id_count: Optional[int] = None
     max_token_id_count: Optional[int] = None
