@@ -164,15 +164,33 @@ int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t*
  *   0 .. lens[b], writes fp32 logits [B][vocab] and increments lens ON THE DEVICE (no host synchronisation). B must be the
  *   prefill's B and the workspace at least 2 B tokens. SLAM_ESTATE without a bound cache, without a prefill, or when the
  *   step could pass `capacity` (the host bound: prefill T + steps so far).
- * Both overwrite the forward activations (slam_backward then needs a new slam_forward).
+ * slam_kv_repeat: n continuations per prompt from one prefill. Precondition: a successful slam_prefill of B rows, no
+ *   slam_decode_step since, and a bound cache with max_batch >= B n. For every layer, K and V, cache row b (keys
+ *   0 .. lens[b]-1) is copied to rows b n .. b n + n - 1, bit for bit; keys at or beyond lens[b] of a destination row are
+ *   unspecified and no later call reads them. lens: int32 [B n] device, first B entries filled; afterwards
+ *   lens[b n + i] = old lens[b]. logits: nullable, fp32 [B n][vocab], first B rows filled, replicated the same way. Afterwards
+ *   the decode batch is B n: slam_decode_step(.., B n, ..) is the next legal call. n == 1 is a no-op returning SLAM_OK.
+ *   A further slam_kv_repeat(m) before any decode step is legal too: it fans the B n rows out to B n m rows (row r to rows
+ *   r m .. r m + m - 1) under the same argument, given max_batch >= B n m.
+ *   The expansion is in place and destination rows of a low b are source rows of a higher b (B = 3, n = 2: row 1 goes to
+ *   rows 2 and 3 while row 2 is still a source). The scheme: one launch per source row in DESCENDING b on `stream`, each
+ *   covering all layers, K, V, lens and logits. Launch b writes rows [b n, b n + n) except b itself (only row 0 is its own
+ *   destination); for b >= 1 these are all > b, so no launch writes what it reads, and a later launch b' < b reads a row that
+ *   lies below every destination written before it. Hazard-free for every (B, n). Only lens[b] keys are copied (lens is read
+ *   on the device: no host synchronisation), with 16-byte loads and stores of whole key rows.
+ *   Errors, all before any launch: SLAM_EINVAL for h or lens NULL, n < 1 or B n > max_batch; SLAM_ESTATE without a bound
+ *   cache, without a prefill, or after a decode step.
+ * Both prefill and decode overwrite the forward activations (slam_backward then needs a new slam_forward).
  * What generation offers: greedy decoding and temperature / top-k / top-p sampling with banned tokens, EOS and pad handling,
  * either chosen by the caller from the logits or on the device by slam_sample_tokens (below; top_k 1 .. 256, reproducible
- * per row). No beam search, no repetition penalty, no OPT. */
+ * per row); n sampled continuations per prompt from one prefill (slam_kv_repeat), and the model's own log-probability of
+ * every chosen token (slam_token_logprobs, below). No beam search, no repetition penalty, no OPT. */
 size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity);
 int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity);
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
                  slam_stream_t stream);
 int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B, float* logits_out, slam_stream_t stream);
+int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_stream_t stream);
 
 /* ---- choosing the next token on the device (what HF's logits processors + torch.multinomial do between two decode steps) ----
  * slam_sample_tokens needs no engine: it reads fp32 logits [B][vocab] (row stride vocab, 4-byte aligned; odd vocabularies
@@ -218,6 +236,33 @@ size_t slam_sample_workspace_bytes(int32_t B, int32_t vocab, int32_t top_k);
 int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
                        const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
                        int64_t out_stride, void* ws, size_t ws_bytes, slam_stream_t stream);
+
+/* ---- the log-probability of the chosen token (what a second forward + log_softmax + gather would give) ----------------------
+ * slam_token_logprobs needs no engine and runs right behind slam_sample_tokens on the same stream, on the same logits. For
+ * row b, with x_i the RAW logit of token i (no banned mask, no temperature, no truncation; NaN counts as -inf and +inf as
+ * FLT_MAX, the sampler's reading):
+ *   finished && finished[b]:  out[b * out_stride + column] = 0.0f
+ *   otherwise:                out[..] = x[tokens[b]] - (m + logf(S)), the model's own log-softmax (the quantity
+ *                             sequence_logps sums); 0.0f when tokens[b] is outside [0, vocab); -inf when the row has no score
+ *                             above -inf.
+ *   then, when finished is given: finished[b] = done ? done[b] : 0.
+ * With done = the sampler's flags, the EOS token itself gets its log-prob and the pads behind it get 0, with no torch op
+ * between engine calls, also when pad_id is an EOS id.
+ * m and S, in fp32: the row is cut into chunks of 2048 scores (the sampler's chunk). In chunk c, m_c = max x_i and
+ * s_c = sum of expf(x_i - m_c) (0 when m_c = -inf) in this order: thread t of 256 adds the scores t, t + 256, t + 512, .. of
+ * the chunk in that order starting from 0; the 64 lanes of a wave are combined by the xor butterfly v += v[lane ^ o] for
+ * o = 32, 16, 8, 4, 2, 1; the four waves as ((w0 + w1) + w2) + w3. m = max_c m_c; S starts at 0 and takes, in chunk order
+ * from 0, S = fmaf(s_c, expf(m_c - m), S) - ONE rounding per chunk, a fused multiply-add - with chunks of m_c = -inf skipped.
+ * A row of one chunk has S = s_0 (one launch); longer rows take two launches through ws. The result depends on (the row, the token) alone - not on B, the row index, the row's alignment or the
+ * launch shape - and is the same bits on every run: no floating-point atomics.
+ * logits fp32 [B][vocab] (row stride vocab, 4-byte aligned); tokens int64 [B]; done, finished uint8 [B], nullable; out fp32;
+ * ws: slam_token_logprobs_workspace_bytes(B, vocab) bytes, 8-byte aligned (host arithmetic: positive for valid arguments, 0
+ * else). SLAM_EINVAL before any launch: logits, tokens, out or ws NULL; B <= 0 or B > 65535; vocab <= 0; logits not 4-byte
+ * aligned; ws not 8-byte aligned; ws_bytes too small. */
+size_t slam_token_logprobs_workspace_bytes(int32_t B, int32_t vocab);
+int slam_token_logprobs(const float* logits, int32_t B, int32_t vocab, const int64_t* tokens, const uint8_t* done,
+                        uint8_t* finished, float* out, int64_t out_stride, int32_t column, void* ws, size_t ws_bytes,
+                        slam_stream_t stream);
 
 /* loss.backward(): accumulates d(loss*grad_scale)/dparam into the bound fp32 gradient buffer.
  * bucket_layers = decoder layers per gradient bucket for the callback (<=0: one bucket). */

@@ -13,6 +13,16 @@
 //    through two launches: every (chunk, row) block selects its local top k into the workspace, one block per row selects
 //    among those, ranks the k' survivors and does the weights, the top-p cut, the Philox draw and the EOS / done / pad part.
 //    Thread 0 forms the sums in the stated order: no floating-point atomics, nothing depends on the grid.
+//  * kv_repeat (slam_kv_repeat): fans the B prefilled cache rows out to B * n rows in place, row b -> rows b n .. b n + n - 1.
+//    One launch per source row, in DESCENDING b on the one stream, each covering all layers, K and V, lens and the logits row.
+//    Launch b reads row b and writes rows [b n, b n + n) minus b itself (only b = 0 is its own destination); for n >= 2 and
+//    b >= 1 every one of those is > b, so a launch never writes what it reads, the destinations of the launches are disjoint,
+//    and a row b' < b that a later launch reads is below every destination written before it. Only lens[b] keys are copied
+//    (read on the device), as 16-byte loads and stores: bit-exact.
+//  * token_logprobs (slam_token_logprobs): the log-softmax of the raw logits row at one token. Chunks of SP_CHUNK scores; in a
+//    chunk thread t takes scores t, t + 256, .. in that order, the 64 lanes of a wave are summed by the xor butterfly 32, 16,
+//    .., 1, the four waves in wave order; chunks are combined in chunk order, one fused multiply-add each. Rows above one chunk
+//    take two launches.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -595,6 +605,153 @@ __global__ __launch_bounds__(SP_THREADS) void sample_finish_kernel(const float* 
   emit_token(sh.id[pick], true, b, P, eos_ids, done, next, out);
 }
 
+
+// ---- n samples per prompt: cache fan-out ------------------------------------------------------------------------------------
+constexpr int KR_MAX_X = 64;  // blocks along a slab (grid-stride beyond)
+
+// One source row b of the cache -> rows b n .. b n + n - 1 (never onto itself). grid (x, nslab + 1): slab y < nslab is
+// (layer, K | V, kv head) = [cap][hd] bf16 of which the first lens[b] keys are copied; y == nslab replicates lens and logits.
+__global__ __launch_bounds__(256) void kv_repeat_kernel(bf16_t* __restrict__ kv, int* __restrict__ lens,
+                                                        float* __restrict__ logits, int b, int n, int bmax, int nKV, int cap,
+                                                        int hd, int nslab, int vocab) {
+  const int len = lens[b];  // not a destination of this launch
+  const int y = blockIdx.y;
+  const int i0 = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+  if (y == nslab) {
+    for (int i = i0; i < n; i += step)
+      if (b * n + i != b) lens[b * n + i] = len;
+    if (!logits) return;
+    const float* src = logits + (size_t)b * vocab;
+    for (int c = i0; c < vocab; c += step) {
+      const float v = src[c];
+      for (int i = 0; i < n; ++i)
+        if (b * n + i != b) logits[(size_t)(b * n + i) * vocab + c] = v;
+    }
+    return;
+  }
+  const int lk = y / nKV, g = y % nKV;
+  const size_t slab = (size_t)cap * hd;
+  const uint4* src = reinterpret_cast<const uint4*>(kv + (((size_t)lk * bmax + b) * nKV + g) * slab);
+  const int nv = min(max(len, 0), cap) * (hd / 8);
+  for (int v = i0; v < nv; v += step) {
+    const uint4 x = src[v];
+    for (int i = 0; i < n; ++i) {
+      const int r = b * n + i;
+      if (r != b) reinterpret_cast<uint4*>(kv + (((size_t)lk * bmax + r) * nKV + g) * slab)[v] = x;
+    }
+  }
+}
+
+// ---- log-probability of a token -----------------------------------------------------------------------------------------------
+// NaN -> -inf, +inf -> FLT_MAX: the sampler's reading of a score
+SLAM_DEVICE float clean_score(float x) {
+  if (x != x) x = -INFINITY;
+  return fminf(x, FLT_MAX);
+}
+
+// scores [c0, c0 + n) of one row, cleaned, into LDS at their index in the chunk; the loads are those of load_keys
+SLAM_DEVICE void load_scores(const float* __restrict__ row, int c0, int n, float* vals) {
+  const float* p = row + c0;
+  int head = (int)((4u - (uint32_t)(((uintptr_t)p >> 2) & 3u)) & 3u);
+  if (head > n) head = n;
+  const int nv = (n - head) >> 2;
+  const int t = threadIdx.x;
+  if (t < head) vals[t] = clean_score(p[t]);
+  const float4* pv = reinterpret_cast<const float4*>(p + head);
+  for (int v = t; v < nv; v += SP_THREADS) {
+    const float4 f = pv[v];
+    const int i = head + 4 * v;
+    vals[i + 0] = clean_score(f.x);
+    vals[i + 1] = clean_score(f.y);
+    vals[i + 2] = clean_score(f.z);
+    vals[i + 3] = clean_score(f.w);
+  }
+  for (int i = head + 4 * nv + t; i < n; i += SP_THREADS) vals[i] = clean_score(p[i]);
+}
+
+// m = max of vals[0 .. n), s = sum of expf(vals[i] - m) in the stated order (0 when m is -inf). Every thread of the block calls
+// it and gets the same pair.
+SLAM_DEVICE void chunk_max_sum(const float* vals, int n, float* red, float& m, float& s) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  float mx = -INFINITY;
+  for (int i = t; i < n; i += SP_THREADS) mx = fmaxf(mx, vals[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) red[wave] = mx;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float acc = 0.f;
+  if (m != -INFINITY)
+    for (int i = t; i < n; i += SP_THREADS) acc += expf(vals[i] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  s = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+struct LogprobParams {
+  int vocab, nch, column;
+  long long out_stride;
+};
+
+// stage 1, grid (chunks, B): (m_c, s_c) of the chunk into ws[b][chunk]
+__global__ __launch_bounds__(SP_THREADS) void logprob_chunk_kernel(const float* __restrict__ logits,
+                                                                   const uint8_t* __restrict__ finished, LogprobParams P,
+                                                                   float2* __restrict__ ws) {
+  __shared__ float vals[SP_CHUNK];
+  __shared__ float red[SP_THREADS / 64];
+  const int ch = blockIdx.x, b = blockIdx.y;
+  if (finished && finished[b]) return;  // written by the second launch only
+  const int c0 = ch * SP_CHUNK;
+  const int n = min(SP_CHUNK, P.vocab - c0);
+  load_scores(logits + (size_t)b * P.vocab, c0, n, vals);
+  __syncthreads();
+  float m, s;
+  chunk_max_sum(vals, n, red, m, s);
+  if (threadIdx.x == 0) ws[(size_t)b * P.nch + ch] = make_float2(m, s);
+}
+
+// one block per row. ROW: the row is one chunk, reduced here (SP_THREADS threads); else thread 0 combines stage 1's pairs.
+template <bool ROW>
+__global__ __launch_bounds__(SP_THREADS) void logprob_finish_kernel(const float* __restrict__ logits,
+                                                                    const int64_t* __restrict__ tokens,
+                                                                    const uint8_t* __restrict__ done,
+                                                                    uint8_t* __restrict__ finished, float* __restrict__ out,
+                                                                    LogprobParams P, const float2* __restrict__ ws) {
+  __shared__ float vals[ROW ? SP_CHUNK : 1];
+  __shared__ float red[SP_THREADS / 64];
+  __shared__ int fin_s;
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (t == 0) fin_s = finished && finished[b] ? 1 : 0;  // one read: thread 0 rewrites the flag below
+  __syncthreads();
+  const bool fin = fin_s != 0;
+  const float* row = logits + (size_t)b * P.vocab;
+  float m = -INFINITY, s = 0.f;
+  if (!fin) {
+    if (ROW) {
+      load_scores(row, 0, P.vocab, vals);
+      __syncthreads();
+      chunk_max_sum(vals, P.vocab, red, m, s);
+    } else if (t == 0) {
+      const float2* p = ws + (size_t)b * P.nch;
+      for (int c = 0; c < P.nch; ++c) m = fmaxf(m, p[c].x);
+      if (m != -INFINITY)
+        for (int c = 0; c < P.nch; ++c)
+          if (p[c].x != -INFINITY) s = __fmaf_rn(p[c].y, expf(p[c].x - m), s);  // one rounding, as the header states
+    }
+  }
+  if (t != 0) return;
+  float r = 0.f;
+  if (!fin) {
+    const long long tok = tokens[b];
+    if (tok >= 0 && tok < P.vocab) r = m == -INFINITY ? -INFINITY : clean_score(row[tok]) - (m + logf(s));
+  }
+  out[(long long)b * P.out_stride + P.column] = r;
+  if (finished) finished[b] = done ? done[b] : (uint8_t)0;
+}
+
 }  // namespace
 
 namespace slam {
@@ -717,6 +874,45 @@ int sample_tokens(const SampleArgs& a, hipStream_t st) {
   } else {
     sample_select_kernel<<<dim3(P.nch, a.B), SP_THREADS, 0, st>>>(a.logits, a.banned, a.done, P, ws);
     sample_finish_kernel<false><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws);
+  }
+  return (int)hipGetLastError();
+}
+
+int kv_repeat(bf16_t* kv, int* lens, float* logits, int B, int n, int bmax, int L, int nKV, int head_dim, int cap, int kv_bound,
+              int vocab, hipStream_t st) {
+  if (!kv || !lens || B <= 0 || n < 1 || (int64_t)B * n > bmax || (head_dim & 7) || kv_bound <= 0 || kv_bound > cap) return -1;
+  if (n == 1) return 0;
+  const int nslab = L * 2 * nKV;
+  if (nslab + 1 > 65535) return -1;
+  size_t per = (size_t)kv_bound * (head_dim / 8);
+  if (logits && (size_t)vocab > per) per = (size_t)vocab;
+  unsigned gx = nblk(per, 256);
+  if (gx > (unsigned)KR_MAX_X) gx = KR_MAX_X;
+  for (int b = B - 1; b >= 0; --b)  // descending: see the header comment
+    kv_repeat_kernel<<<dim3(gx, nslab + 1), 256, 0, st>>>(kv, lens, logits, b, n, bmax, nKV, cap, head_dim, nslab, vocab);
+  return (int)hipGetLastError();
+}
+
+size_t token_logprobs_workspace_bytes(int B, int vocab) {
+  if (B <= 0 || vocab <= 0) return 0;
+  return (size_t)B * sample_chunks(vocab) * sizeof(float2);
+}
+
+int token_logprobs(const float* logits, int B, int vocab, const int64_t* tokens, const uint8_t* done, uint8_t* finished,
+                   float* out, int64_t out_stride, int column, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!logits || !tokens || !out || B <= 0 || B > 65535 || vocab <= 0 || ((uintptr_t)logits & 3)) return -1;
+  if (!ws || ((uintptr_t)ws & 7) || ws_bytes < token_logprobs_workspace_bytes(B, vocab)) return -1;
+  LogprobParams P;
+  P.vocab = vocab;
+  P.nch = sample_chunks(vocab);
+  P.column = column;
+  P.out_stride = out_stride;
+  float2* w = reinterpret_cast<float2*>(ws);
+  if (P.nch == 1) {
+    logprob_finish_kernel<true><<<B, SP_THREADS, 0, st>>>(logits, tokens, done, finished, out, P, w);
+  } else {
+    logprob_chunk_kernel<<<dim3(P.nch, B), SP_THREADS, 0, st>>>(logits, finished, P, w);
+    logprob_finish_kernel<false><<<B, 64, 0, st>>>(logits, tokens, done, finished, out, P, w);
   }
   return (int)hipGetLastError();
 }

@@ -239,6 +239,7 @@ struct SlamEngine {
   int kv_bmax = 0, kv_cap = 0;
   int kv_B = 0;          // rows of the last prefill
   int kv_hi = 0;         // host bound of every row's cached length: the prefill's T, + 1 per decode step
+  int kv_T = 0;          // the last prefill's T: kv_hi != kv_T once a decode step was taken (slam_kv_repeat)
   bool kv_ready = false; // a prefill filled the bound cache
 
   int fail(int code, const std::string& m) {
@@ -1131,6 +1132,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   CK(decode_proj(h, h->hf, P + h->off_head, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
   h->kv_B = B;
   h->kv_hi = T;
+  h->kv_T = T;
   h->kv_ready = true;
   return SLAM_OK;
 }
@@ -1178,6 +1180,20 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
   CK(decode_proj(h, h->hf, P + h->off_head, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
   CK(lens_inc(lens, B, st));
   h->kv_hi += 1;
+  return SLAM_OK;
+}
+
+int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_stream_t stream) {
+  if (!h || !lens || n < 1) return SLAM_EINVAL;
+  if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+  if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_kv_repeat needs a slam_prefill into the bound cache first");
+  if (h->kv_hi != h->kv_T) return h->fail(SLAM_ESTATE, "slam_kv_repeat after a decode step: prefill again");
+  if ((int64_t)h->kv_B * n > h->kv_bmax) return h->fail(SLAM_EINVAL, "B * n rows exceed the bound KV cache");
+  if (n == 1) return SLAM_OK;
+  const SlamModelDesc& d = h->d;
+  CK(kv_repeat(h->kv, lens, logits, h->kv_B, n, h->kv_bmax, d.n_layers, d.n_kv_heads, d.head_dim, h->kv_cap, h->kv_hi, d.vocab,
+               (hipStream_t)stream));
+  h->kv_B *= n;
   return SLAM_OK;
 }
 
@@ -2271,6 +2287,14 @@ int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint
   a.ws = ws;
   a.ws_bytes = ws_bytes;
   return sample_tokens(a, (hipStream_t)stream);
+}
+
+size_t slam_token_logprobs_workspace_bytes(int32_t B, int32_t vocab) { return token_logprobs_workspace_bytes(B, vocab); }
+int slam_token_logprobs(const float* logits, int32_t B, int32_t vocab, const int64_t* tokens, const uint8_t* done,
+                        uint8_t* finished, float* out, int64_t out_stride, int32_t column, void* ws, size_t ws_bytes,
+                        slam_stream_t stream) {
+  // token_logprobs refuses every bad argument (-1 = SLAM_EINVAL) before it launches anything
+  return token_logprobs(logits, B, vocab, tokens, done, finished, out, out_stride, column, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

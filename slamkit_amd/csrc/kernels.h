@@ -277,5 +277,14 @@ struct SampleArgs {
 };
 size_t sample_workspace_bytes(int B, int vocab, int top_k);  // host only
 int sample_tokens(const SampleArgs& a, hipStream_t st);
+// n samples per prompt: rows 0 .. B-1 of the cache kv (L x { K, V } x [bmax][nKV][cap][head_dim]), of lens and of the nullable
+// logits [.][vocab] fan out in place to rows b n .. b n + n - 1; only lens[b] keys of a row are copied. One launch per source
+// row in descending b (hazard-free for every (B, n): decode.hip's header). kv_bound: host bound of lens.
+int kv_repeat(bf16_t* kv, int* lens, float* logits, int B, int n, int bmax, int L, int nKV, int head_dim, int cap, int kv_bound,
+              int vocab, hipStream_t st);
+// out[b * out_stride + column] = log-softmax of the raw fp32 row b at tokens[b] (include/slam_engine.h: slam_token_logprobs)
+size_t token_logprobs_workspace_bytes(int B, int vocab);  // host only
+int token_logprobs(const float* logits, int B, int vocab, const int64_t* tokens, const uint8_t* done, uint8_t* finished,
+                   float* out, int64_t out_stride, int column, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace slam

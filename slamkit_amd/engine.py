@@ -90,6 +90,9 @@ def load_library(path: Optional[str] = None):
         "slam_decode_step": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "slam_sample_workspace_bytes": (sz, [i32, i32, i32]),
         "slam_sample_tokens": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "slam_kv_repeat": (C.c_int, [vp, i32, vp, vp, vp]),
+        "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
+        "slam_token_logprobs": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, sz, vp]),
         "slam_bucket_stream": (vp, [vp]),
         "slam_set_logit_mask": (C.c_int, [vp, vp]),
         "slam_padded_vocab": (i32, [vp]),
@@ -208,6 +211,23 @@ def sample_tokens(logits, desc: SlamSampleDesc, next_ids, ws, banned=None, row_i
                                           stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_sample_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+def token_logprobs_workspace_bytes(B: int, vocab: int) -> int:
+    """Bytes of device workspace slam_token_logprobs needs (host arithmetic)."""
+    return int(load_library().slam_token_logprobs_workspace_bytes(int(B), int(vocab)))
+
+
+def token_logprobs(logits, tokens, out, column: int, ws, done=None, finished=None, stream: Optional[int] = None):
+    """slam_token_logprobs: out[b, column] (fp32 [B, stride]) = the log-softmax of row b of the raw fp32 logits [B, vocab] at
+    tokens[b] (int64 [B]); 0.0 for rows with finished[b] set, after which finished[b] = done[b] (both uint8 [B], None where
+    unused). ws: a uint8 tensor of token_logprobs_workspace_bytes(B, vocab). Only enqueues work."""
+    B, V = logits.shape
+    rc = load_library().slam_token_logprobs(_ptr(logits), B, V, _ptr(tokens), _ptr(done), _ptr(finished), _ptr(out),
+                                           out.stride(0), int(column), _ptr(ws), ws.numel() * ws.element_size(),
+                                           stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_token_logprobs failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 def unpadded_scratch_bytes(B: int, T: int) -> int:
@@ -392,6 +412,12 @@ class Engine:
         """ids int64 [B]: one token per row at position lens[b]; fp32 logits [B, vocab]; lens += 1 on the device."""
         self._ck(self.lib.slam_decode_step(self.h, _ptr(ids), _ptr(lens), B, _ptr(logits_out),
                                            stream if stream is not None else current_stream_ptr()))
+
+    def kv_repeat(self, n: int, lens, logits=None, stream: Optional[int] = None):
+        """After a prefill of B rows (no decode step yet): cache row b -> rows b n .. b n + n - 1, lens (int32 [B n], first B
+        filled) and the optional fp32 logits [B n, vocab] likewise; the decode batch becomes B n."""
+        self._ck(self.lib.slam_kv_repeat(self.h, int(n), _ptr(lens), _ptr(logits),
+                                         stream if stream is not None else current_stream_ptr()))
 
     def set_logit_mask(self, mask_u8=None):
         """mask_u8: uint8 device tensor of padded_vocab() bytes (non-zero = column outside the softmax) or None."""

@@ -14,7 +14,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass, field
-from typing import Dict, Iterator, List, Optional, Tuple
+from typing import Dict, Iterator, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -272,6 +272,12 @@ class _EngineLoss(torch.autograd.Function):
     def backward(ctx, grad_out):
         ctx.model.backward(float(grad_out))
         return torch.zeros(1, device=grad_out.device), None, None
+
+
+class GenerateOutput(NamedTuple):
+    """generate(return_logprobs=True): the sequences as without it, and the log-probability of every new token."""
+    sequences: torch.Tensor
+    logprobs: torch.Tensor
 
 
 def _right_padded(mask: torch.Tensor) -> bool:
@@ -911,7 +917,8 @@ class UnitLM(TokenLM):
                  seed: Optional[int] = None, input_ids: Optional[torch.Tensor] = None,
                  attention_mask: Optional[torch.Tensor] = None, bad_words_ids: Optional[List[List[int]]] = None,
                  top_p: Optional[float] = None, eos_token_id=None, pad_token_id: Optional[int] = None,
-                 sampler: Optional[str] = None, sample_ids: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+                 sampler: Optional[str] = None, sample_ids: Optional[torch.Tensor] = None,
+                 num_return_sequences: Optional[int] = None, return_logprobs: bool = False, **kwargs):
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
@@ -927,7 +934,21 @@ class UnitLM(TokenLM):
         alone, whatever the batch. `sample_ids` (int64 [B], default 0 .. B-1) are those row ids: a sharded evaluation passes the
         examples' global indices. The engine sampler needs 1 <= top_k <= 256 and temperature > 0 when sampling, top_p in
         (0, 1] and at most 16 EOS ids (ValueError otherwise); a tie at the k-th score goes to the lower id where HF keeps all
-        ties. seed=None draws a 62-bit seed from torch's default CPU generator."""
+        ties. seed=None draws a 62-bit seed from torch's default CPU generator.
+
+        `num_return_sequences` = n (sampling only; HF refuses greedy n-best too) returns [B n, T_in + n_new], row b n + i the
+        i-th sample of prompt b (HF's order), the prompt part repeated as passed. The B prompts are prefilled ONCE, the cache
+        rows fanned out to B n rows (slam_kv_repeat) and B n rows decoded: the workspace is max(B T, 2 B n) tokens, not B n T.
+        With sampler="engine" `sample_ids` has shape [B n] (default 0 .. B n - 1): row b n + i draws what row b n + i of a call
+        on the prompts repeated n times draws; the torch sampler draws one multinomial over B n rows. The tokens of the two
+        calls are equal whenever their logits are equal bit for bit, which holds when the longest prompt (the row stride of
+        the prefill) is a multiple of 128 tokens; at another length the prefill's attention tiles fall differently on the
+        rows of the two batches, the logits differ by rounding (within the model tolerance) and a draw that lands on a
+        boundary may differ.
+
+        `return_logprobs=True` returns GenerateOutput(sequences, logprobs): logprobs fp32 [B n, n_new], the model's own
+        log-softmax (raw fp32 logits: no banned mask, temperature or truncation) of every new token, its EOS included, 0.0
+        behind a row's EOS; trimmed with the sequences. Both samplers get it from slam_token_logprobs."""
         if self.config.is_opt:
             raise ValueError("generate is not implemented for OPT models (the engine's KV-cached decode covers Qwen2 only)")
         gc = generation_config
@@ -961,8 +982,15 @@ class UnitLM(TokenLM):
             inputs = input_ids
         if inputs is None or inputs.dim() != 2:
             raise ValueError("generate needs input_ids [B, T]")
+        nret = int(pick(num_return_sequences, "num_return_sequences", 1))
+        if nret < 1:
+            raise ValueError(f"num_return_sequences must be at least 1 (got {nret})")
+        if nret > 1 and not do_sample:
+            raise ValueError("num_return_sequences > 1 needs do_sample=True (greedy continuations would all be equal)")
         if max_new_tokens <= 0:
-            return inputs.to(self.device, torch.int64)
+            seq = inputs.to(self.device, torch.int64)
+            seq = seq.repeat_interleave(nret, 0) if nret > 1 else seq
+            return GenerateOutput(seq, seq.new_zeros(seq.shape[0], 0, dtype=torch.float32)) if return_logprobs else seq
         if kwargs:
             raise TypeError(f"generate got unsupported arguments {sorted(kwargs)}")
         if sampler not in (None, "torch", "engine"):
@@ -982,6 +1010,7 @@ class UnitLM(TokenLM):
         dev = self.device
         seq_in = inputs.to(dev, torch.int64)
         B, T_in = seq_in.shape
+        BN = B * nret  # rows decoded
         mask = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones_like(seq_in, dtype=torch.bool)
         # compact every row's real tokens to the left (stable: keeps their order)
         order = torch.sort((~mask).to(torch.int8), dim=1, stable=True).indices
@@ -994,20 +1023,26 @@ class UnitLM(TokenLM):
         if T + max_new_tokens > self.config.max_tokens:
             raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds max_tokens {self.config.max_tokens}")
         cap = -(-(T + max_new_tokens) // 64) * 64
-        self._ensure_workspace(max(B * T, 2 * B))
-        nbytes = self.engine.kv_cache_bytes(B, cap)
+        self._ensure_workspace(max(B * T, 2 * BN))
+        nbytes = self.engine.kv_cache_bytes(BN, cap)
         raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
         off = (-raw.data_ptr()) % 256
-        self.engine.bind_kv_cache(raw[off:off + nbytes], B, cap)
+        self.engine.bind_kv_cache(raw[off:off + nbytes], BN, cap)
         V = self.config.vocab_size
-        logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+        logits = torch.empty(BN, V, dtype=torch.float32, device=dev)
         eos_t = torch.tensor(eos, dtype=torch.long, device=dev) if eos else None
+        if nret > 1:  # the B prompt rows first; slam_kv_repeat fills the rest
+            lens = torch.cat([lens, torch.zeros(BN - B, dtype=torch.int32, device=dev)])
         self._hold = (ids, lens)
-        new = torch.empty(B, max_new_tokens, dtype=torch.int64, device=dev)
+        new = torch.empty(BN, max_new_tokens, dtype=torch.int64, device=dev)
+        lp = None
+        if return_logprobs:  # lp[:, k] of step k, the rows' "EOS already emitted" flags, the reduction's workspace
+            lp = (torch.empty(BN, max_new_tokens, dtype=torch.float32, device=dev), torch.zeros(BN, dtype=torch.uint8, device=dev),
+                  torch.empty(E.token_logprobs_workspace_bytes(BN, V), dtype=torch.uint8, device=dev))
         n = 0
         if on_device:
             n = self._sample_on_device(logits, new, ids, lens, T, bad, eos, int(pad), do_sample, top_k, temperature, top_p,
-                                       seed, sample_ids)
+                                       seed, sample_ids, nret, lp)
         else:
             bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
             g = None
@@ -1015,7 +1050,9 @@ class UnitLM(TokenLM):
                 g = torch.Generator(device=dev)
                 g.manual_seed(int(seed))
             self.engine.prefill(ids, lens, B, T, logits)
-            done = torch.zeros(B, dtype=torch.bool, device=dev)
+            if nret > 1:
+                self.engine.kv_repeat(nret, lens, logits)
+            done = torch.zeros(BN, dtype=torch.bool, device=dev)
             for step in range(max_new_tokens):
                 scores = logits
                 if bad_idx is not None:
@@ -1030,10 +1067,13 @@ class UnitLM(TokenLM):
                 n = step + 1
                 if eos_t is not None:
                     done |= torch.isin(nxt, eos_t)
+                if lp is not None:
+                    E.token_logprobs(logits, nxt.contiguous(), lp[0], step, lp[2], done.view(torch.uint8), lp[1])
+                if eos_t is not None:
                     if (step % 16 == 15 or step + 1 == max_new_tokens) and bool(done.all()):
                         break
                 if step + 1 < max_new_tokens:
-                    self.engine.decode_step(nxt.contiguous(), lens, B, logits)
+                    self.engine.decode_step(nxt.contiguous(), lens, BN, logits)
         new = new[:, :n]
         if eos_t is not None and n > 1:
             # HF stops right after the step on which the last row finished: drop the all-pad columns behind it
@@ -1042,11 +1082,14 @@ class UnitLM(TokenLM):
             if bool(all_done.any()):
                 n = int(all_done.nonzero()[0]) + 1
                 new = new[:, :n]
-        return torch.cat([seq_in, new], 1)
+        seq = torch.cat([seq_in.repeat_interleave(nret, 0) if nret > 1 else seq_in, new], 1)
+        return GenerateOutput(seq, lp[0][:, :n].contiguous()) if lp is not None else seq
 
-    def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids):
+    def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids,
+                          nret=1, lp=None):
         """The decode loop of generate(sampler="engine"): prefill, sample(step 0), then decode_step(next) / sample(step k). The
-        kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written."""
+        kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written.
+        logits / new have B n rows: the prompts (ids, the first rows of lens) are prefilled once and fanned out (kv_repeat)."""
         dev = self.device
         B, V = logits.shape
         max_new = new.shape[1]
@@ -1068,11 +1111,15 @@ class UnitLM(TokenLM):
                 raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
         nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        self.engine.prefill(ids, lens, B, T, logits)
+        self.engine.prefill(ids, lens, B // nret, T, logits)
+        if nret > 1:
+            self.engine.kv_repeat(nret, lens, logits)
         n = 0
         for step in range(max_new):
             desc.step = step
             E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+            if lp is not None:
+                E.token_logprobs(logits, nxt, lp[0], step, lp[2], done, lp[1])
             n = step + 1
             if eos_i is not None and (step % 16 == 15 or n == max_new) and bool(done.all()):
                 break

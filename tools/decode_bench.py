@@ -2,6 +2,7 @@
 B = 8, prompt 256, 150 new tokens (config/metric/generate.yaml), on a randomly initialised model.
 
 Usage: python tools/decode_bench.py [--models slam,cfg3] [--steps 150] [--reps 2] [--no-reforward]
+       python tools/decode_bench.py --num-return-sequences 8 [--models slam,cfg3] [--reps 3]
        python tools/decode_bench.py --trace-summary DIR   (per-launch table of the decode kernels from a
                                                             `rocprofv3 --kernel-trace --stats -d DIR -- python tools/decode_bench.py`)
 Prints one JSON line per measurement:
@@ -15,6 +16,13 @@ generate is measured, once per sampler and rep, alternating the samplers within 
 `sampler`, `do_sample`, `generate_s` (median) and `generate_s_all`. --sample-op times the token choice alone at (B, V) =
 (8, 502), (8, 152167), (64, 152167), (1, 152167): `engine_us` = one slam_sample_tokens, `torch_us` = the torch sampler's
 per-step ops (bad words, warp, softmax, multinomial, pad, EOS bookkeeping), device events around 200 back-to-back calls.
+With --num-return-sequences n: end-to-end sampled generate (sampler="engine") of B prompts x n continuations from ONE prefill
+(`way` = "one_prefill": slam_prefill of B rows, slam_kv_repeat, B n rows decoded) against the same call on the prompts repeated
+n times (`way` = "repeated_batch"), alternated rep by rep in this process: one line per way with `generate_s` (median),
+`generate_s_all`, `workspace_tokens` / `workspace_MB` (what generate binds: max(B T, 2 B n) against B n T tokens; host
+arithmetic of slam_workspace_bytes) and `peak_alloc_MB` (torch's peak over the way's first call, weights and cache included).
+Then `kv_repeat_ms` (the fan-out alone behind a prefill, device events, median of 5) and one `logprob_op` line per
+(B n, V) = (64, 502), (64, 152167): `logprobs_us` = one slam_token_logprobs, device events around 200 back-to-back calls.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -166,6 +174,80 @@ def sample_op_bench(calls=200, rounds=5):
         print(json.dumps(res), flush=True)
 
 
+def nbest_bench(name, B, P, new, reps, n):
+    """n continuations per prompt from one prefill against the repeated batch; kv_repeat alone."""
+    import torch
+    m = build(name, -(-(P + new) // 64) * 64)  # the workspace starts small: each way binds what it needs
+    dev = m.device
+    g = torch.Generator(device=dev).manual_seed(1)
+    ids = torch.randint(2, m.config.vocab_size, (B, P), device=dev, generator=g)
+    rep_ids = ids.repeat_interleave(n, 0)
+    kw = dict(max_new_tokens=new, eos_token_id=[], do_sample=True, temperature=0.8, top_k=25, seed=11, sampler="engine")
+    ways = {"one_prefill": lambda: m.generate(input_ids=ids, num_return_sequences=n, **kw),
+            "repeated_batch": lambda: m.generate(input_ids=rep_ids, **kw)}
+    info, outs = {}, {}
+    for w, fn in ways.items():  # warm-up; one_prefill first: the workspace only grows
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        outs[w] = fn()
+        torch.cuda.synchronize()
+        info[w] = dict(workspace_tokens=m._ws_tokens, workspace_MB=round(m.engine.workspace_bytes(m._ws_tokens) / 1e6, 1),
+                       peak_alloc_MB=round(torch.cuda.max_memory_allocated() / 1e6, 1))
+    same = bool(torch.equal(outs["one_prefill"], outs["repeated_batch"]))
+    times = {w: [] for w in ways}
+    for _ in range(reps):
+        for w, fn in ways.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[w].append(time.perf_counter() - t0)
+    for w in ways:
+        print(json.dumps(dict(bench="nbest_e2e", model=name, B=B, n=n, prompt=P, new_tokens=new, way=w, same_tokens=same,
+                              generate_s=round(statistics.median(times[w]), 4),
+                              generate_s_all=[round(t, 4) for t in times[w]], **info[w])), flush=True)
+    cap = -(-(P + new) // 64) * 64
+    cache = torch.empty(m.engine.kv_cache_bytes(B * n, cap), dtype=torch.uint8, device=dev)
+    m.engine.bind_kv_cache(cache, B * n, cap)
+    lens = torch.zeros(B * n, dtype=torch.int32, device=dev)
+    logits = torch.empty(B * n, m.config.vocab_size, dtype=torch.float32, device=dev)
+    t = []
+    for _ in range(6):
+        lens[:B] = P
+        m.engine.prefill(ids, lens, B, P, logits)
+        t.append(ev_ms(lambda: m.engine.kv_repeat(n, lens, logits)))
+    print(json.dumps(dict(bench="kv_repeat", model=name, B=B, n=n, prompt=P, kv_repeat_ms=round(statistics.median(t[1:]), 4),
+                          cache_MB_copied=round(m.engine.kv_cache_bytes(B * (n - 1), P) / 1e6, 1))), flush=True)
+    del m, cache
+    torch.cuda.empty_cache()
+
+
+def logprob_op_bench(calls=200, rounds=5):
+    """Device-event time of slam_token_logprobs alone."""
+    import torch
+    from slamkit_amd import engine as E
+    dev = torch.device("cuda")
+    for B, V in ((64, 502), (64, 152167)):
+        g = torch.Generator(device=dev).manual_seed(V + B)
+        logits = torch.randn(B, V, device=dev, generator=g) * 3.0
+        tok = torch.randint(0, V, (B,), device=dev, generator=g)
+        out = torch.empty(B, calls, dtype=torch.float32, device=dev)
+        ws = torch.empty(E.token_logprobs_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        fin = torch.zeros(B, dtype=torch.uint8, device=dev)
+
+        def run():
+            for k in range(calls):
+                E.token_logprobs(logits, tok, out, k, ws, done, fin)
+
+        run()
+        torch.cuda.synchronize()
+        t = [ev_ms(run) / calls * 1e3 for _ in range(rounds)]
+        print(json.dumps(dict(bench="logprob_op", B=B, vocab=V, logprobs_us=round(statistics.median(t), 2),
+                              logprobs_us_minmax=[round(min(t), 2), round(max(t), 2)],
+                              logits_MB=round(B * V * 4 / 1e6, 2))), flush=True)
+
+
 def e2e(m, B, P, new, reps, tag, reforward=True):
     import torch
     dev = m.device
@@ -238,6 +320,8 @@ def main():
     ap.add_argument("--sampler", default=None, help="torch,engine: end-to-end generate per sampler, alternated")
     ap.add_argument("--do-sample", action="store_true", help="with --sampler: temperature 0.8, top_k 25 instead of greedy")
     ap.add_argument("--sample-op", action="store_true", help="time the token choice alone (engine vs torch ops)")
+    ap.add_argument("--num-return-sequences", type=int, default=0,
+                    help="n: generate of 8 prompts x n from one prefill vs the repeated batch, kv_repeat and token_logprobs alone")
     a = ap.parse_args()
     if a.trace_summary:
         trace_summary(a.trace_summary)
@@ -246,6 +330,11 @@ def main():
     assert torch.cuda.is_available()
     if a.sample_op:
         sample_op_bench()
+        return
+    if a.num_return_sequences > 1:
+        for name in a.models.split(","):
+            nbest_bench(name, 8, 256, a.steps, a.reps, a.num_return_sequences)
+        logprob_op_bench()
         return
     for name in a.models.split(","):
         m = build(name, 4096)
