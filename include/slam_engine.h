@@ -76,7 +76,7 @@ int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out); /* UnitLM._
  *   layers.N.{ln1, ln1_b [H], wqkv [3 H][H], bqkv [3 H], wo [H][H], bo [H], ln2, ln2_b [H], w1 [F][H], b1 [F], w2 [H][F], b2 [H]},
  *   norm, norm_b [H].
  * Positions are position_ids, else 0 .. T-1 per row; both table indices are clamped to the tables (a memory guard: callers
- * check their ranges). KV-cached generation (slam_prefill / slam_decode_step) is not implemented for OPT: SLAM_EINVAL. */
+ * check their ranges). KV-cached generation (slam_prefill / slam_decode_step / slam_extend) is not implemented for OPT: SLAM_EINVAL. */
 int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, SlamEngine** out);
 /* The same with model flags (slam_engine_create / slam_engine_create_arch mean flags = 0). Arch 0 takes hidden <= 4096
  * (rows above 2048 run the two-waves-per-row RMSNorm kernels), arch 1 hidden <= 2048.
@@ -164,8 +164,9 @@ int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t*
  *   0 .. lens[b], writes fp32 logits [B][vocab] and increments lens ON THE DEVICE (no host synchronisation). B must be the
  *   prefill's B and the workspace at least 2 B tokens. SLAM_ESTATE without a bound cache, without a prefill, or when the
  *   step could pass `capacity` (the host bound: prefill T + steps so far).
- * slam_kv_repeat: n continuations per prompt from one prefill. Precondition: a successful slam_prefill of B rows, no
- *   slam_decode_step since, and a bound cache with max_batch >= B n. For every layer, K and V, cache row b (keys
+ * slam_kv_repeat: n continuations per prompt from one prefill. Precondition: a successful slam_prefill of B rows
+ *   (optionally followed by slam_extend calls: a chunked prefill), no slam_decode_step since, and a bound cache with
+ *   max_batch >= B n. For every layer, K and V, cache row b (keys
  *   0 .. lens[b]-1) is copied to rows b n .. b n + n - 1, bit for bit; keys at or beyond lens[b] of a destination row are
  *   unspecified and no later call reads them. lens: int32 [B n] device, first B entries filled; afterwards
  *   lens[b n + i] = old lens[b]. logits: nullable, fp32 [B n][vocab], first B rows filled, replicated the same way. Afterwards
@@ -179,18 +180,48 @@ int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t*
  *   lies below every destination written before it. Hazard-free for every (B, n). Only lens[b] keys are copied (lens is read
  *   on the device: no host synchronisation), with 16-byte loads and stores of whole key rows.
  *   Errors, all before any launch: SLAM_EINVAL for h or lens NULL, n < 1 or B n > max_batch; SLAM_ESTATE without a bound
- *   cache, without a prefill, or after a decode step.
- * Both prefill and decode overwrite the forward activations (slam_backward then needs a new slam_forward).
+ *   cache, without a prefill, or after a decode step. slam_extend calls between the prefill and the fan-out are fine.
+ * slam_extend: appends a chunk of up to T tokens per row behind the keys the cache already holds - chunked prefill, a
+ *   continuation of a cached sequence, teacher-forcing a given continuation, verifying several proposed tokens at once.
+ *   ids: int64 [B][T] device, right-padded with any valid id. new_lens: int32 [B] device, 0 <= new_lens[b] <= T: the real
+ *   tokens of row b are columns 0 .. new_lens[b]-1. lens: int32 [B] device, the rows' key counts - the array
+ *   slam_decode_step advances. Token t of row b runs at position lens[b] + t: one layer loop over B T tokens (the prefill's
+ *   projections, norms and MLP), each layer's K / V of the real tokens appended bit for bit to cache rows lens[b] + t, and
+ *   attention of every real token over cache rows 0 .. lens[b] + t (exp2 domain, fp32 accumulation, on the matrix pipe;
+ *   split partials merged in split order: bit-identical run to run). logits_out: fp32 [B][vocab]; row b receives the logits
+ *   of row b's LAST new token when new_lens[b] > 0 (one head launch over B rows), and lens[b] += new_lens[b] ON THE DEVICE -
+ *   no host synchronisation anywhere. A row with new_lens[b] == 0 is inert: its logits_out row, lens[b] and every one of its
+ *   cache rows keep their bits. The logits of a prompt prefilled in chunks differ from a one-shot slam_prefill's by rounding
+ *   only (another attention kernel, the same maths).
+ *   Preconditions: a bound cache that a slam_prefill filled; B equal to the current decode batch (the prefill's B, times n
+ *   after a slam_kv_repeat); lens[b] + new_lens[b] within the host bound below (it is for every sequence of calls that passes
+ *   these arrays on unchanged). Legal after slam_prefill, after decode steps, after slam_kv_repeat and after another
+ *   slam_extend. The host bound of the cached lengths advances by T whatever new_lens holds. slam_kv_repeat stays legal
+ *   behind any number of slam_extend calls as long as no slam_decode_step ran since the prefill (chunked prefill, then the
+ *   fan-out); once a decode step ran, a slam_extend does not make it legal again.
+ *   Unspecified: cache rows at or beyond lens[b] + new_lens[b]; the values the padded columns computed (nothing reads them:
+ *   their attention output is written as zeros and no K / V of theirs reaches the cache); logits_out and the cache when
+ *   new_lens[b] is outside [0, T] or lens[b] is not the row's key count (the kernels clamp both to the host bound, so such a
+ *   call stays inside the cache).
+ *   Errors, all before any launch: SLAM_EINVAL for a NULL argument, B <= 0, T <= 0, B different from the decode batch, or an
+ *   OPT engine; SLAM_ESTATE without bound parameters / workspace, without a bound cache, without a prefill, or when the host
+ *   bound + T would pass `capacity`; SLAM_ENOMEM when B T, or the 2 B tokens of the decode scratch, exceed the bound workspace
+ *   tokens. Works with every "recompute" level (the layers may share their q|k|v slot: each layer's chunk is consumed before
+ *   the next layer's projection).
+ * Prefill, extend and decode overwrite the forward activations (slam_backward then needs a new slam_forward).
  * What generation offers: greedy decoding and temperature / top-k / top-p sampling with banned tokens, EOS and pad handling,
  * either chosen by the caller from the logits or on the device by slam_sample_tokens (below; top_k 1 .. 256, reproducible
  * per row); n sampled continuations per prompt from one prefill (slam_kv_repeat), and the model's own log-probability of
- * every chosen token (slam_token_logprobs, below). No beam search, no repetition penalty, no OPT. */
+ * every chosen token (slam_token_logprobs, below); prompts prefilled in chunks whose size, not the prompt length, sets the
+ * workspace, and k tokens per row appended to a live cache (slam_extend). No beam search, no repetition penalty, no OPT. */
 size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity);
 int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity);
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
                  slam_stream_t stream);
 int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B, float* logits_out, slam_stream_t stream);
 int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_stream_t stream);
+int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                float* logits_out, slam_stream_t stream);
 
 /* ---- choosing the next token on the device (what HF's logits processors + torch.multinomial do between two decode steps) ----
  * slam_sample_tokens needs no engine: it reads fp32 logits [B][vocab] (row stride vocab, 4-byte aligned; odd vocabularies
@@ -525,6 +556,22 @@ size_t slam_op_attn_decode_workspace(int B, int nH, int nKV, int head_dim, int k
 int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens, void* k_cache, void* v_cache, void* o, void* ws,
                         size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity, int kv_bound, float theta,
                         slam_stream_t s);
+/* chunk attention over the cache (the attention of slam_extend): qkv bf16 [B T][(nH + 2 nKV) head_dim] exactly as the forward's
+ * q|k|v buffer holds it - bias and RoPE applied, queries pre-scaled by head_dim^-0.5 * log2(e) (NOT the fp32 pre-bias row of
+ * slam_op_attn_decode). Row b T + t is token t of row b's chunk, real when t < new_lens[b] (0 <= new_lens[b] <= T);
+ * base_lens[b] (>= 0, may be 0) keys of row b are already in the cache; base_lens[b] + new_lens[b] <= kv_bound <= capacity.
+ * The K and V columns of every real token are copied bit for bit to row base_lens[b] + t of k_cache / v_cache (bf16
+ * [B][nKV][capacity][head_dim]) by a launch of their own, then o[b T + t] (bf16 [B T][nH head_dim]) = softmax attention of the
+ * token's query heads over cache rows 0 .. base_lens[b] + t (16-query tiles on v_mfma_f32_16x16x32_bf16, all heads of a KV
+ * group from one pass over its keys, exp2 domain, fp32 accumulation). Rows t >= new_lens[b] of o are zeros; no cache row
+ * outside [base_lens[b], base_lens[b] + new_lens[b]) is written. Bit-identical run to run (key splits merged in split order).
+ * head_dim 64 or 128, nH / nKV in 1 .. 8; every pointer 16-byte aligned.
+ * ws: slam_op_attn_extend_workspace(B, T, nH, nKV, head_dim, kv_bound) bytes (0 when the launch takes one split; ws may then
+ * be NULL). */
+size_t slam_op_attn_extend_workspace(int B, int T, int nH, int nKV, int head_dim, int kv_bound);
+int slam_op_attn_extend(const void* qkv, const int32_t* base_lens, const int32_t* new_lens, void* k_cache, void* v_cache,
+                        void* o, void* ws, size_t ws_bytes, int B, int T, int nH, int nKV, int head_dim, int capacity,
+                        int kv_bound, slam_stream_t s);
 int slam_op_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int M, int H, float eps, slam_stream_t s);
 size_t slam_op_rmsnorm_bwd_workspace(int M, int H);
 int slam_op_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,

@@ -19,6 +19,10 @@
 //    b >= 1 every one of those is > b, so a launch never writes what it reads, the destinations of the launches are disjoint,
 //    and a row b' < b that a later launch reads is below every destination written before it. Only lens[b] keys are copied
 //    (read on the device), as 16-byte loads and stores: bit-exact.
+//  * attn_extend (slam_extend): a chunk of new tokens per row against the keys already cached. kv_extend_scatter appends the
+//    chunk's K / V first, in a launch of its own; attn_extend then reads keys from the cache only, 16 queries x all heads of a
+//    KV group per block on v_mfma_f32_16x16x32_bf16, scores formed transposed so that P feeds the PV product from the registers
+//    it was computed in. Key splits are merged in split order by attn_extend_combine.
 //  * token_logprobs (slam_token_logprobs): the log-softmax of the raw logits row at one token. Chunks of SP_CHUNK scores; in a
 //    chunk thread t takes scores t, t + 256, .. in that order, the 64 lanes of a wave are summed by the xor butterfly 32, 16,
 //    .., 1, the four waves in wave order; chunks are combined in chunk order, one fused multiply-add each. Rows above one chunk
@@ -357,6 +361,251 @@ __global__ void lens_to_pos_kernel(const int* __restrict__ lens, int64_t* __rest
 __global__ void lens_inc_kernel(int* __restrict__ lens, int B) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b < B) lens[b] = lens[b] + 1;
+}
+
+// ---- chunk attention over the cache (slam_extend) -----------------------------------------------------------------------------
+// Row b appends new_lens[b] tokens behind its base_lens[b] cached keys. Both counts are clamped once per block to what the
+// host bound allows, and every address below is formed from the clamped pair: base in [0, kv_bound], nl in
+// [0, min(T, kv_bound - base)], so no key index reaches kv_bound (<= cap) and no token index reaches T.
+struct ExtRow {
+  int base, nl;
+};
+SLAM_DEVICE ExtRow ext_row(const int* __restrict__ base_lens, const int* __restrict__ new_lens, int b, int T, int kv_bound) {
+  ExtRow r;
+  r.base = min(max(base_lens[b], 0), kv_bound);
+  r.nl = min(max(new_lens[b], 0), min(T, kv_bound - r.base));
+  return r;
+}
+
+// K / V columns of the real tokens t < nl of qkv [B*T][QKV] -> cache rows base + t of (b, kv head); grid (.., B)
+__global__ __launch_bounds__(256) void kv_extend_scatter_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
+                                                                bf16_t* __restrict__ vc, const int* __restrict__ base_lens,
+                                                                const int* __restrict__ new_lens, int T, int nH, int nKV, int hd,
+                                                                int cap, int kv_bound) {
+  const int b = blockIdx.y;
+  const ExtRow R = ext_row(base_lens, new_lens, b, T, kv_bound);
+  const int per_row = 2 * nKV * hd / 8;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int t = idx / per_row, c = idx % per_row;
+  if (t >= R.nl) return;
+  const int kv = c / (nKV * hd / 8), r = c % (nKV * hd / 8);
+  const int g = r / (hd / 8), d = (r % (hd / 8)) * 8;
+  const int QKV = (nH + 2 * nKV) * hd;
+  const uint4 v = *reinterpret_cast<const uint4*>(qkv + ((size_t)b * T + t) * QKV + (nH + kv * nKV + g) * hd + d);
+  bf16_t* dst = (kv ? vc : kc) + (((size_t)b * nKV + g) * cap + R.base + t) * hd + d;
+  *reinterpret_cast<uint4*>(dst) = v;
+}
+
+constexpr int AE_KB = 32;  // keys per LDS stage: two 16-key score tiles = one 32-deep PV step
+
+// grid (ceil(T / 16), ns, B * nKV), 256 threads: one 16-query tile of one (row, KV group) over the keys of split y. The four
+// waves stage each AE_KB-key block of the group once (K row-major, V transposed) and share it: wave w serves query heads
+// w and w + 4 of the group. Scores are formed transposed, S^T = K Q^T, so that a lane ends up with P^T[keys][query] in the
+// B-operand map of the PV product with no exchange: lane l (qd = l >> 4, j = l & 15) holds query j's keys 4 qd + r of the first
+// tile and 16 + 4 qd + r of the second, and V^T is read with its contraction slots in that same key order. The output tile is
+// O^T: lane l holds o[query j][d = 16 dt + 4 qd + r]. part == nullptr (one split): o is normalised and stored, rows t >= nl of
+// the tile as zeros. Else part[((b T + t) nH + h) ns + split][HD + 4] = o (unnormalised), m, l for real rows; a split whose
+// key range starts at or above the tile's last key writes nothing (the combine never reads it).
+template <int HD, int G>
+__global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restrict__ qkv, const int* __restrict__ base_lens,
+                                                          const int* __restrict__ new_lens, const bf16_t* __restrict__ kc,
+                                                          const bf16_t* __restrict__ vc, bf16_t* __restrict__ o,
+                                                          float* __restrict__ part, int T, int nH, int nKV, int cap, int kv_bound,
+                                                          int chunk, int ns) {
+  constexpr int NHW = (G + 3) / 4;      // heads per wave
+  constexpr int KS = HD + 8;            // K row stride (bf16): 16-byte rows, fragment reads spread over the banks
+  constexpr int VS = AE_KB + 4;         // V^T row stride (bf16): 8-byte rows, 18 dwords apart
+  constexpr int DT = HD / 16, KK = HD / 32, PS = HD + 4;
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[AE_KB * KS];
+  __shared__ __attribute__((aligned(16))) bf16_t Vt[HD * VS];
+  const int q0 = blockIdx.x * 16, s = blockIdx.y;
+  const int b = blockIdx.z / nKV, g = blockIdx.z % nKV;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qd = lane >> 4, j = lane & 15;
+  const ExtRow R = ext_row(base_lens, new_lens, b, T, kv_bound);
+  const int QKV = (nH + 2 * nKV) * HD;
+  const int tq = q0 + j;                       // this lane's query (token of the chunk)
+  const bool real = tq < R.nl;
+  const int tile_n = min(q0 + 16, R.nl) - q0;  // real queries of the tile (<= 0: none)
+  const int kend = tile_n > 0 ? R.base + q0 + tile_n : 0;  // keys the tile's last real query sees
+  const int k_lo = s * chunk;
+  const int k_hi = min(k_lo + chunk, kend);
+  if (part && k_lo >= k_hi) return;
+  const int qlim = R.base + min(tq, R.nl - 1);  // last key of this lane's query (clamped for the rows that are not real)
+
+  uint4 qf[NHW][KK];
+  f32x4_t acc[NHW][DT];
+  float m_[NHW], l_[NHW];
+#pragma unroll
+  for (int hh = 0; hh < NHW; ++hh) {
+    const int i = wave + 4 * hh;
+    m_[hh] = -INFINITY;
+    l_[hh] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) acc[hh][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const int tr = max(min(tq, R.nl - 1), 0);
+    const bf16_t* qrow = qkv + ((size_t)b * T + tr) * QKV + (size_t)(g * G + min(i, G - 1)) * HD + 8 * qd;
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) qf[hh][kk] = *reinterpret_cast<const uint4*>(qrow + 32 * kk);
+  }
+  const size_t cbase = ((size_t)b * nKV + g) * cap;
+  const uint4 zero = {0u, 0u, 0u, 0u};
+  constexpr int NV = AE_KB * (HD / 8) / 256;  // 16-byte pieces of a K (and of a V) block per thread
+  uint4 kx[NV], vx[NV];
+  // the block's K / V pieces of this thread into registers; keys at or beyond k_hi as zeros: p = 0 meets 0, never the
+  // cache's bits
+  auto fetch = [&](int kb) {
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      const int v = threadIdx.x + 256 * u;
+      const int kr = v / (HD / 8), d0 = (v % (HD / 8)) * 8;
+      const bool ok = kb + kr < k_hi;
+      const size_t src = (cbase + (ok ? kb + kr : 0)) * HD + d0;
+      kx[u] = ok ? *reinterpret_cast<const uint4*>(kc + src) : zero;
+      vx[u] = ok ? *reinterpret_cast<const uint4*>(vc + src) : zero;
+    }
+  };
+  if (k_lo < k_hi) fetch(k_lo);
+  for (int kb = k_lo; kb < k_hi; kb += AE_KB) {
+    __syncthreads();  // the previous block's fragment reads are done
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      const int v = threadIdx.x + 256 * u;
+      const int kr = v / (HD / 8), d0 = (v % (HD / 8)) * 8;
+      *reinterpret_cast<uint4*>(&Ks[kr * KS + d0]) = kx[u];
+      const uint32_t w[4] = {vx[u].x, vx[u].y, vx[u].z, vx[u].w};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) Vt[(d0 + e) * VS + kr] = (bf16_t)(w[e >> 1] >> (16 * (e & 1)));
+    }
+    if (kb + AE_KB < k_hi) fetch(kb + AE_KB);  // the next block's loads fly under this block's products
+    __syncthreads();
+#pragma unroll
+    for (int hh = 0; hh < NHW; ++hh) {
+      if (wave + 4 * hh >= G) continue;  // wave-uniform
+      // S^T tiles: lane holds key 16 c + 4 qd + r of query j
+      f32x4_t sc[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        sc[c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+          const uint4 kf = *reinterpret_cast<const uint4*>(&Ks[(16 * c + j) * KS + 32 * kk + 8 * qd]);
+          sc[c] = mfma16(kf, qf[hh][kk], sc[c]);
+        }
+      }
+      float mx = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int ka = kb + 16 * c + 4 * qd + r;
+          const float x = (ka < k_hi && ka <= qlim) ? sc[c][r] : -INFINITY;
+          sc[c][r] = x;
+          mx = fmaxf(mx, x);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float mn = fmaxf(m_[hh], mx);
+      const float ms = mn == -INFINITY ? 0.f : mn;  // nothing seen yet: every p below is exp2(-inf) = 0
+      const float a = rescale(m_[hh], mn);
+      float p[8], ps = 0.f;
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          p[4 * c + r] = fast_exp2(sc[c][r] - ms);
+          ps += p[4 * c + r];
+        }
+      l_[hh] = l_[hh] * a + ps;  // this lane's share; the four lanes of a query are summed at the end
+      m_[hh] = mn;
+      const uint4 pf = pack_bf16x8(p);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        const bf16_t* vrow = &Vt[(16 * dt + j) * VS + 4 * qd];
+        const uint2 lo = *reinterpret_cast<const uint2*>(vrow), hi = *reinterpret_cast<const uint2*>(vrow + 16);
+        const uint4 vf = {lo.x, lo.y, hi.x, hi.y};
+        f32x4_t t = acc[hh][dt];
+        t[0] *= a; t[1] *= a; t[2] *= a; t[3] *= a;
+        acc[hh][dt] = mfma16(vf, pf, t);
+      }
+    }
+  }
+#pragma unroll
+  for (int hh = 0; hh < NHW; ++hh) {
+    const int i = wave + 4 * hh;
+    if (i >= G) continue;
+    float l = l_[hh];
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const int hq = g * G + i;
+    if (part) {
+      if (!real) continue;
+      float* dst = part + ((((size_t)b * T + tq) * nH + hq) * ns + s) * PS;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+        *reinterpret_cast<float4*>(dst + 16 * dt + 4 * qd) = make_float4(acc[hh][dt][0], acc[hh][dt][1], acc[hh][dt][2], acc[hh][dt][3]);
+      if (qd == 0) { dst[HD] = m_[hh]; dst[HD + 1] = l; }
+    } else {
+      if (tq >= T) continue;
+      const float inv = real ? 1.f / l : 0.f;
+      bf16_t* dst = o + (((size_t)b * T + tq) * nH + hq) * HD;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        uint2 w = {0u, 0u};
+        if (real) {
+          w.x = pack_bf16x2(acc[hh][dt][0] * inv, acc[hh][dt][1] * inv);
+          w.y = pack_bf16x2(acc[hh][dt][2] * inv, acc[hh][dt][3] * inv);
+        }
+        *reinterpret_cast<uint2*>(dst + 16 * dt + 4 * qd) = w;
+      }
+    }
+  }
+}
+
+// grid (nH, T, B), HD threads: merge the partials of one (token, head) in split order; rows t >= nl become zeros. Only the
+// splits that start at or below the token's own key are read: those are exactly the ones that wrote this row.
+template <int HD>
+__global__ __launch_bounds__(128) void attn_extend_combine_kernel(const float* __restrict__ part,
+                                                                  const int* __restrict__ base_lens,
+                                                                  const int* __restrict__ new_lens, int T, int nH, int kv_bound,
+                                                                  int chunk, int ns, bf16_t* __restrict__ out) {
+  constexpr int PS = HD + 4;
+  const int h = blockIdx.x, t = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
+  const int bt = b * T + t;
+  const ExtRow R = ext_row(base_lens, new_lens, b, T, kv_bound);
+  bf16_t* dst = out + ((size_t)bt * nH + h) * HD + d;
+  if (t >= R.nl) { *dst = 0; return; }
+  const int nsr = min(ns, (R.base + t) / chunk + 1);
+  const float* p = part + ((size_t)bt * nH + h) * ns * PS;
+  float mm = -INFINITY;
+  for (int s = 0; s < nsr; ++s) mm = fmaxf(mm, p[s * PS + HD]);
+  float l = 0.f, acc = 0.f;
+  for (int s = 0; s < nsr; ++s) {
+    const float ms = p[s * PS + HD];
+    if (ms == -INFINITY) continue;  // a split with no key for this query
+    const float a = fast_exp2(ms - mm);
+    l += p[s * PS + HD + 1] * a;
+    acc += p[s * PS + d] * a;
+  }
+  *dst = f32_to_bf16(acc / l);
+}
+
+// pos[b T + t] = lens[b] + t
+__global__ void extend_pos_kernel(const int* __restrict__ lens, int64_t* __restrict__ pos, int B, int T) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < B * T) pos[i] = (int64_t)lens[i / T] + (i % T);
+}
+
+// rows with new tokens take their logits row from src; lens[b] += clamp(new_lens[b], 0, T). grid (.., B)
+__global__ __launch_bounds__(256) void extend_finish_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                            const int* __restrict__ new_lens, int* __restrict__ lens, int T,
+                                                            int vocab) {
+  const int b = blockIdx.y;
+  const int nl = min(max(new_lens[b], 0), T);
+  if (nl == 0) return;
+  const size_t row = (size_t)b * vocab;
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < vocab; c += gridDim.x * 256) dst[row + c] = src[row + c];
+  if (blockIdx.x == 0 && threadIdx.x == 0) lens[b] = lens[b] + nl;
 }
 
 
@@ -835,6 +1084,68 @@ int lens_to_pos(const int* lens, int64_t* pos, int B, hipStream_t st) {
 
 int lens_inc(int* lens, int B, hipStream_t st) {
   lens_inc_kernel<<<nblk((size_t)B, 256), 256, 0, st>>>(lens, B);
+  return (int)hipGetLastError();
+}
+
+size_t attn_extend_part_bytes(int B, int T, int nH, int head_dim, int ns) {
+  return ns > 1 ? (size_t)B * T * nH * ns * (head_dim + 4) * sizeof(float) : 0;
+}
+
+// keys per split: multiples of 64, about 512 blocks over (query tiles, splits, KV heads, rows); more keys per split when the
+// partials would not fit in part_bytes, down to one split, which needs none
+int attn_extend_chunk(int B, int T, int nH, int nKV, int head_dim, int kv_bound, size_t part_bytes) {
+  const int64_t tiles = (int64_t)B * nKV * ((T + 15) / 16);
+  const int target = 512 / tiles > 1 ? (int)(512 / tiles) : 1;
+  int chunk = ((kv_bound + target - 1) / target + 63) / 64 * 64;
+  if (chunk < 64) chunk = 64;
+  while (attn_extend_part_bytes(B, T, nH, head_dim, (kv_bound + chunk - 1) / chunk) > part_bytes) chunk *= 2;
+  return chunk;
+}
+
+int attn_extend(const bf16_t* qkv, const int* base_lens, const int* new_lens, bf16_t* kc, bf16_t* vc, int cap, int B, int T,
+                int nH, int nKV, int head_dim, int kv_bound, bf16_t* o, float* part, size_t part_bytes, hipStream_t st) {
+  if (B <= 0 || T <= 0 || nKV <= 0 || nH % nKV || kv_bound <= 0 || kv_bound > cap) return -1;
+  const int G = nH / nKV;
+  if ((head_dim != 64 && head_dim != 128) || G > 8) return -1;
+  if ((int64_t)B * nKV > 65535 || T > 65535 || (int64_t)B * T > 0x7fffffffLL / (nH * (head_dim + 4))) return -1;
+  if (((uintptr_t)qkv | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)o | (uintptr_t)part) & 15) return -1;
+  const int chunk = attn_extend_chunk(B, T, nH, nKV, head_dim, kv_bound, part ? part_bytes : 0);
+  const int ns = (kv_bound + chunk - 1) / chunk;
+  if (ns > 65535) return -1;
+  float* pp = ns > 1 ? part : nullptr;
+  const size_t n = (size_t)T * (2 * nKV * head_dim / 8);
+  kv_extend_scatter_kernel<<<dim3(nblk(n, 256), B), 256, 0, st>>>(qkv, kc, vc, base_lens, new_lens, T, nH, nKV, head_dim, cap,
+                                                                  kv_bound);
+  const dim3 grid((T + 15) / 16, ns, B * nKV);
+#define AE_CASE(HD, GG)                                                                                                      \
+  case GG:                                                                                                                   \
+    attn_extend_kernel<HD, GG><<<grid, 256, 0, st>>>(qkv, base_lens, new_lens, kc, vc, o, pp, T, nH, nKV, cap, kv_bound, chunk, \
+                                                     ns);                                                                    \
+    break;
+#define AE_SWITCH(HD) \
+  switch (G) { AE_CASE(HD, 1) AE_CASE(HD, 2) AE_CASE(HD, 3) AE_CASE(HD, 4) AE_CASE(HD, 5) AE_CASE(HD, 6) AE_CASE(HD, 7) AE_CASE(HD, 8) }
+  if (head_dim == 64) {
+    AE_SWITCH(64)
+    if (pp) attn_extend_combine_kernel<64><<<dim3(nH, T, B), 64, 0, st>>>(pp, base_lens, new_lens, T, nH, kv_bound, chunk, ns, o);
+  } else {
+    AE_SWITCH(128)
+    if (pp) attn_extend_combine_kernel<128><<<dim3(nH, T, B), 128, 0, st>>>(pp, base_lens, new_lens, T, nH, kv_bound, chunk, ns, o);
+  }
+#undef AE_SWITCH
+#undef AE_CASE
+  return (int)hipGetLastError();
+}
+
+int extend_positions(const int* lens, int64_t* pos, int B, int T, hipStream_t st) {
+  extend_pos_kernel<<<nblk((size_t)B * T, 256), 256, 0, st>>>(lens, pos, B, T);
+  return (int)hipGetLastError();
+}
+
+int extend_finish(const float* src, float* dst, const int* new_lens, int* lens, int B, int T, int vocab, hipStream_t st) {
+  if (B <= 0 || B > 65535) return -1;
+  unsigned gx = nblk((size_t)vocab, 256);
+  if (gx > 64) gx = 64;
+  extend_finish_kernel<<<dim3(gx, B), 256, 0, st>>>(src, dst, new_lens, lens, T, vocab);
   return (int)hipGetLastError();
 }
 

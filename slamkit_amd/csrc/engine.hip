@@ -238,8 +238,9 @@ struct SlamEngine {
   bf16_t* kv = nullptr;
   int kv_bmax = 0, kv_cap = 0;
   int kv_B = 0;          // rows of the last prefill
-  int kv_hi = 0;         // host bound of every row's cached length: the prefill's T, + 1 per decode step
-  int kv_T = 0;          // the last prefill's T: kv_hi != kv_T once a decode step was taken (slam_kv_repeat)
+  int kv_hi = 0;         // host bound of every row's cached length: the prefill's T, + 1 per decode step, + T per slam_extend
+  int kv_T = 0;          // the last prefill's T + the T of every slam_extend that no decode step preceded: kv_hi != kv_T once
+                         // a decode step was taken (slam_kv_repeat)
   bool kv_ready = false; // a prefill filled the bound cache
 
   int fail(int code, const std::string& m) {
@@ -1197,6 +1198,66 @@ int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_
   return SLAM_OK;
 }
 
+int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                float* logits_out, slam_stream_t stream) {
+  if (!h || !ids || !new_lens || !lens || !logits_out || B <= 0 || T <= 0) return SLAM_EINVAL;
+  if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
+  if (h->arch != 0) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
+  if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+  if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
+  if ((int64_t)2 * B > h->max_tokens) return h->fail(SLAM_ENOMEM, "extend needs a workspace of at least 2 B tokens");
+  if ((int64_t)(h->kv_ready ? h->kv_hi : 0) + T > h->kv_cap) return h->fail(SLAM_ESTATE, "extend past the KV cache capacity");
+  if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_extend needs a slam_prefill into the bound cache first");
+  if (B != h->kv_B) return h->fail(SLAM_EINVAL, "extend batch differs from the decode batch");
+  const SlamModelDesc& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads, hd = d.head_dim;
+  const int M = B * T;
+  const bf16_t* P = h->params;
+  h->have_fwd = false;
+  h->fwd_drop = false;
+  GemmTuneScope tune_scope(&h->gemm_tune);
+  CK(join_optimizer(h, st));
+  CK(join_params(h, st));
+  // scratch in buffers only backward and the loss read: the tokens' int64 positions (dh_a), attention split partials and,
+  // behind the layer loop, the fp32 logits of all B rows (the logits buffer: 2 B <= workspace tokens covers 4 B vocab bytes)
+  int64_t* pos = (int64_t*)h->dh_a;
+  const float qscale = 1.44269504088896340736f / sqrtf((float)hd);
+  CK(extend_positions(lens, pos, B, T, st));
+  CK(rope_table(pos, M, T, hd, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
+  CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
+  const size_t part_bytes = (size_t)h->max_tokens * h->vpad * sizeof(bf16_t);
+  const int kv_bound = h->kv_hi + T;
+  const bool fused_rope = M > SKINNY_MAX_M && hd == 64 && (H % 64 == 0) && (h->QKV % 128 == 0);
+  for (int l = 0; l < L; ++l) {
+    const LayerOff& o = h->lo[l];
+    LayerAct& a = h->la[l];
+    CK(rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
+    if (fused_rope) {
+      CK(gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
+    } else {
+      CK(decode_proj(h, a.x1, P + o.wqkv, a.qkv, nullptr, P + o.bqkv, nullptr, M, h->QKV, H, st));
+      CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, hd, h->cosb, h->sinb, 0, st, nH, qscale));
+    }
+    CK(attn_extend(a.qkv, lens, new_lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, T, nH, nKV, hd, kv_bound, a.o, (float*)h->logits,
+                   part_bytes, st));
+    CK(decode_proj(h, a.o, P + o.wo, a.hmid, nullptr, nullptr, h->hs[l], M, H, nH * hd, st));
+    CK(rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
+    CK(decode_proj(h, a.x2, P + o.wgu, a.gu, nullptr, nullptr, nullptr, M, 2 * I, H, st));
+    CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
+    CK(decode_proj(h, a.act, P + o.wd, h->hs[l + 1], nullptr, nullptr, a.hmid, M, H, I, st));
+  }
+  // each row's last real token: gather, final norm, one fp32 head launch over B rows; inert rows keep their logits and lens
+  CK(gather_last_rows(h->hs[L], h->dx, new_lens, B, T, H, st));
+  CK(rmsnorm_fwd(h->dx, P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
+  float* lg = (float*)h->logits;
+  CK(decode_proj(h, h->hf, P + h->off_head, nullptr, lg, nullptr, nullptr, B, d.vocab, H, st));
+  CK(extend_finish(lg, logits_out, new_lens, lens, B, T, d.vocab, st));
+  if (h->kv_hi == h->kv_T) h->kv_T += T;  // no decode step since the prefill: slam_kv_repeat stays legal
+  h->kv_hi += T;
+  return SLAM_OK;
+}
+
 int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_bucket_cb cb, void* user,
                   slam_stream_t stream) {
   if (!h) return SLAM_EINVAL;
@@ -2085,6 +2146,20 @@ int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens,
   if (r) return r;
   return attn_decode(qkv, (const bf16_t*)bias, tab, tab + n, tab + 2 * n, tab + 3 * n, lens, (bf16_t*)k_cache, (bf16_t*)v_cache,
                      capacity, B, nH, nKV, head_dim, kv_bound, (bf16_t*)o, (float*)(w + head), ws_bytes - head, st);
+}
+size_t slam_op_attn_extend_workspace(int B, int T, int nH, int nKV, int head_dim, int kv_bound) {
+  if (B <= 0 || T <= 0 || nH <= 0 || nKV <= 0 || kv_bound <= 0) return 0;
+  const int chunk = attn_extend_chunk(B, T, nH, nKV, head_dim, kv_bound, (size_t)-1);
+  return attn_extend_part_bytes(B, T, nH, head_dim, (kv_bound + chunk - 1) / chunk);
+}
+int slam_op_attn_extend(const void* qkv, const int32_t* base_lens, const int32_t* new_lens, void* k_cache, void* v_cache,
+                        void* o, void* ws, size_t ws_bytes, int B, int T, int nH, int nKV, int head_dim, int capacity,
+                        int kv_bound, slam_stream_t s) {
+  if (!qkv || !base_lens || !new_lens || !k_cache || !v_cache || !o || B <= 0 || T <= 0 || nH <= 0 || nKV <= 0) return SLAM_EINVAL;
+  if ((head_dim != 64 && head_dim != 128) || nH % nKV || nH / nKV > 8 || kv_bound <= 0 || kv_bound > capacity) return SLAM_EINVAL;
+  const int r = attn_extend((const bf16_t*)qkv, base_lens, new_lens, (bf16_t*)k_cache, (bf16_t*)v_cache, capacity, B, T, nH, nKV,
+                            head_dim, kv_bound, (bf16_t*)o, (float*)ws, ws ? ws_bytes : 0, (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
 }
 int slam_op_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int M, int H, float eps, slam_stream_t s) {
   return rmsnorm_fwd((const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, rstd, M, H, eps, (hipStream_t)s);

@@ -255,6 +255,19 @@ int kv_scatter(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, const int* lens, int B
 int gather_last_rows(const bf16_t* src, bf16_t* dst, const int* lens, int B, int T, int H, hipStream_t st);
 int lens_to_pos(const int* lens, int64_t* pos, int B, hipStream_t st);
 int lens_inc(int* lens, int B, hipStream_t st);
+// chunk attention over the cache (slam_extend): qkv = bf16 [B T][(nH + 2 nKV) hd] as the forward holds it (bias and RoPE
+// applied, q pre-scaled). Token t < new_lens[b] of row b: its K / V go to cache row base_lens[b] + t (a launch of its own,
+// first), and o[b T + t] (bf16 [B T][nH hd]) attends over cache rows 0 .. base_lens[b] + t on v_mfma_f32_16x16x32_bf16; rows
+// t >= new_lens[b] of o are zeros. base_lens[b] + new_lens[b] <= kv_bound <= cap (host bound; the kernels clamp to it).
+// part: fp32 split partials (attn_extend_part_bytes), merged in split order; none (or too little) means fewer or one split.
+size_t attn_extend_part_bytes(int B, int T, int nH, int head_dim, int ns);
+int attn_extend_chunk(int B, int T, int nH, int nKV, int head_dim, int kv_bound, size_t part_bytes);
+int attn_extend(const bf16_t* qkv, const int* base_lens, const int* new_lens, bf16_t* kc, bf16_t* vc, int cap, int B, int T,
+                int nH, int nKV, int head_dim, int kv_bound, bf16_t* o, float* part, size_t part_bytes, hipStream_t st);
+// pos[b T + t] = lens[b] + t
+int extend_positions(const int* lens, int64_t* pos, int B, int T, hipStream_t st);
+// dst[b] = src[b] (fp32 [B][vocab]) and lens[b] += new_lens[b] for the rows with new_lens[b] > 0; the others keep their bits
+int extend_finish(const float* src, float* dst, const int* new_lens, int* lens, int B, int T, int vocab, hipStream_t st);
 // The next token of every row of fp32 logits [B][vocab] (row stride vocab, any 4-byte alignment), chosen on the device by the
 // contract of include/slam_engine.h (slam_sample_tokens): one argument block from the entry point down to the launches.
 struct SampleArgs {

@@ -91,6 +91,7 @@ def load_library(path: Optional[str] = None):
         "slam_sample_workspace_bytes": (sz, [i32, i32, i32]),
         "slam_sample_tokens": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
         "slam_kv_repeat": (C.c_int, [vp, i32, vp, vp, vp]),
+        "slam_extend": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
         "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
         "slam_token_logprobs": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, sz, vp]),
         "slam_bucket_stream": (vp, [vp]),
@@ -140,6 +141,9 @@ def load_library(path: Optional[str] = None):
         "slam_op_attn_decode_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "slam_op_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           f32, vp]),
+        "slam_op_attn_extend_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "slam_op_attn_extend": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, vp]),
         "slam_op_rmsnorm_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
         "slam_op_rmsnorm_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_rmsnorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -418,6 +422,13 @@ class Engine:
         filled) and the optional fp32 logits [B n, vocab] likewise; the decode batch becomes B n."""
         self._ck(self.lib.slam_kv_repeat(self.h, int(n), _ptr(lens), _ptr(logits),
                                          stream if stream is not None else current_stream_ptr()))
+
+    def extend(self, ids, new_lens, lens, B: int, T: int, logits_out, stream: Optional[int] = None):
+        """slam_extend: ids int64 [B, T] (right-padded), new_lens int32 [B] (0 .. T real tokens per row), lens int32 [B] (the
+        rows' key counts): appends the chunk behind the cached keys, fp32 logits [B, vocab] of each row's last new token (rows
+        with new_lens 0 keep theirs), lens += new_lens on the device."""
+        self._ck(self.lib.slam_extend(self.h, _ptr(ids), _ptr(new_lens), _ptr(lens), B, T, _ptr(logits_out),
+                                      stream if stream is not None else current_stream_ptr()))
 
     def set_logit_mask(self, mask_u8=None):
         """mask_u8: uint8 device tensor of padded_vocab() bytes (non-zero = column outside the softmax) or None."""

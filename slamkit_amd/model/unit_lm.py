@@ -918,7 +918,8 @@ class UnitLM(TokenLM):
                  attention_mask: Optional[torch.Tensor] = None, bad_words_ids: Optional[List[List[int]]] = None,
                  top_p: Optional[float] = None, eos_token_id=None, pad_token_id: Optional[int] = None,
                  sampler: Optional[str] = None, sample_ids: Optional[torch.Tensor] = None,
-                 num_return_sequences: Optional[int] = None, return_logprobs: bool = False, **kwargs):
+                 num_return_sequences: Optional[int] = None, return_logprobs: bool = False,
+                 prefill_chunk: Optional[int] = None, **kwargs):
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
@@ -948,7 +949,17 @@ class UnitLM(TokenLM):
 
         `return_logprobs=True` returns GenerateOutput(sequences, logprobs): logprobs fp32 [B n, n_new], the model's own
         log-softmax (raw fp32 logits: no banned mask, temperature or truncation) of every new token, its EOS included, 0.0
-        behind a row's EOS; trimmed with the sequences. Both samplers get it from slam_token_logprobs."""
+        behind a row's EOS; trimmed with the sequences. Both samplers get it from slam_token_logprobs.
+
+        `prefill_chunk` = C (an int >= 1; None = the one-shot prefill) prefills the prompts C columns at a time: columns
+        [0, min(T, C)) by slam_prefill, every further block of C columns (the last one exactly as wide as what is left)
+        appended to the cache by slam_extend, rows that have already ended taking no part. The fan-out, both samplers,
+        `num_return_sequences` and `return_logprobs` follow as before. The workspace is max(B min(T, C), 2 B n) tokens instead
+        of max(B T, 2 B n): the chunk, not the prompt length, sets the activation memory. The chunks' attention runs in another
+        kernel than the one-shot prefill's, so the logits differ from it by rounding only (within the model tolerance); a
+        token chosen at a near-tie may differ."""
+        if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
+            raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
         if self.config.is_opt:
             raise ValueError("generate is not implemented for OPT models (the engine's KV-cached decode covers Qwen2 only)")
         gc = generation_config
@@ -1023,7 +1034,7 @@ class UnitLM(TokenLM):
         if T + max_new_tokens > self.config.max_tokens:
             raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds max_tokens {self.config.max_tokens}")
         cap = -(-(T + max_new_tokens) // 64) * 64
-        self._ensure_workspace(max(B * T, 2 * BN))
+        self._ensure_workspace(max(B * (T if prefill_chunk is None else min(T, prefill_chunk)), 2 * BN))
         nbytes = self.engine.kv_cache_bytes(BN, cap)
         raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
         off = (-raw.data_ptr()) % 256
@@ -1042,14 +1053,14 @@ class UnitLM(TokenLM):
         n = 0
         if on_device:
             n = self._sample_on_device(logits, new, ids, lens, T, bad, eos, int(pad), do_sample, top_k, temperature, top_p,
-                                       seed, sample_ids, nret, lp)
+                                       seed, sample_ids, nret, lp, prefill_chunk)
         else:
             bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
             g = None
             if do_sample and seed is not None:
                 g = torch.Generator(device=dev)
                 g.manual_seed(int(seed))
-            self.engine.prefill(ids, lens, B, T, logits)
+            self._prefill(ids, lens, B, T, logits, prefill_chunk)
             if nret > 1:
                 self.engine.kv_repeat(nret, lens, logits)
             done = torch.zeros(BN, dtype=torch.bool, device=dev)
@@ -1085,8 +1096,23 @@ class UnitLM(TokenLM):
         seq = torch.cat([seq_in.repeat_interleave(nret, 0) if nret > 1 else seq_in, new], 1)
         return GenerateOutput(seq, lp[0][:, :n].contiguous()) if lp is not None else seq
 
+    def _prefill(self, ids, lens, B, T, logits, chunk=None):
+        """The prompts into the cache and each row's last-token logits into logits[:B]: slam_prefill over all T columns, or
+        (chunk = C) over the first min(T, C) and slam_extend over every further block of C. lens (first B entries: the prompt
+        lengths) is left as it is; the chunks advance a copy, which ends equal to it."""
+        if chunk is None or T <= chunk:
+            self.engine.prefill(ids, lens, B, T, logits)
+            return
+        full = lens[:B]
+        cur = full.clamp(max=chunk).contiguous()
+        self.engine.prefill(ids[:, :chunk].contiguous(), cur, B, chunk, logits)
+        for c0 in range(chunk, T, chunk):
+            w = min(chunk, T - c0)
+            new_lens = (full - c0).clamp(min=0, max=w).contiguous()
+            self.engine.extend(ids[:, c0:c0 + w].contiguous(), new_lens, cur, B, w, logits)
+
     def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids,
-                          nret=1, lp=None):
+                          nret=1, lp=None, prefill_chunk=None):
         """The decode loop of generate(sampler="engine"): prefill, sample(step 0), then decode_step(next) / sample(step k). The
         kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written.
         logits / new have B n rows: the prompts (ids, the first rows of lens) are prefilled once and fanned out (kv_repeat)."""
@@ -1111,7 +1137,7 @@ class UnitLM(TokenLM):
                 raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
         nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        self.engine.prefill(ids, lens, B // nret, T, logits)
+        self._prefill(ids, lens, B // nret, T, logits, prefill_chunk)
         if nret > 1:
             self.engine.kv_repeat(nret, lens, logits)
         n = 0

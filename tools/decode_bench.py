@@ -3,6 +3,7 @@ B = 8, prompt 256, 150 new tokens (config/metric/generate.yaml), on a randomly i
 
 Usage: python tools/decode_bench.py [--models slam,cfg3] [--steps 150] [--reps 2] [--no-reforward]
        python tools/decode_bench.py --num-return-sequences 8 [--models slam,cfg3] [--reps 3]
+       python tools/decode_bench.py --prefill-chunk 512 [--models slam,cfg3]
        python tools/decode_bench.py --trace-summary DIR   (per-launch table of the decode kernels from a
                                                             `rocprofv3 --kernel-trace --stats -d DIR -- python tools/decode_bench.py`)
 Prints one JSON line per measurement:
@@ -23,6 +24,13 @@ n times (`way` = "repeated_batch"), alternated rep by rep in this process: one l
 arithmetic of slam_workspace_bytes) and `peak_alloc_MB` (torch's peak over the way's first call, weights and cache included).
 Then `kv_repeat_ms` (the fan-out alone behind a prefill, device events, median of 5) and one `logprob_op` line per
 (B n, V) = (64, 502), (64, 152167): `logprobs_us` = one slam_token_logprobs, device events around 200 back-to-back calls.
+With --prefill-chunk C: the prefill of B = 8 x T = 2048 prompts in one slam_prefill (`way` = "one_shot") against slam_prefill
+over the first C columns + slam_extend over every further block of C (`way` = "chunked"), alternated rep by rep in this
+process after a warm-up of each way, device events, median of 5: one line per way with `prefill_ms`, `prefill_ms_all`,
+`workspace_tokens` / `workspace_MB` (what generate binds for that way with n = 1: host arithmetic of slam_workspace_bytes),
+and on the chunked line `ratio` = chunked / one-shot and `logits_rel_rms` (the chunked last-token logits against the one-shot
+ones). --trace-summary also lists the attn_extend / kv_extend_scatter / attn_fwd launches, for the kernel's share from a
+`rocprofv3 --kernel-trace --stats` run of their own.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -222,6 +230,57 @@ def nbest_bench(name, B, P, new, reps, n):
     torch.cuda.empty_cache()
 
 
+def chunked_prefill_bench(name, B, T, C, reps=5):
+    """One slam_prefill of [B, T] against slam_prefill + slam_extend in chunks of C columns."""
+    import torch
+    m = build(name, B * T)
+    dev = m.device
+    V = m.config.vocab_size
+    g = torch.Generator(device=dev).manual_seed(1)
+    ids = torch.randint(2, V, (B, T), device=dev, generator=g)
+    full = torch.full((B,), T, dtype=torch.int32, device=dev)
+    cap = -(-(T + 64) // 64) * 64
+    cache = torch.empty(m.engine.kv_cache_bytes(B, cap), dtype=torch.uint8, device=dev)
+    m.engine.bind_kv_cache(cache, B, cap)
+    m._ensure_workspace(B * T)  # one workspace for both ways: the timed launches are the same whatever is bound
+    logits = {w: torch.empty(B, V, dtype=torch.float32, device=dev) for w in ("one_shot", "chunked")}
+    chunks = [(c0, min(C, T - c0)) for c0 in range(0, T, C)]
+    parts = [(ids[:, c0:c0 + w].contiguous(), (full - c0).clamp(min=0, max=w).contiguous(), w) for c0, w in chunks]
+    cur = torch.empty_like(full)
+
+    def one_shot():
+        m.engine.prefill(ids, full, B, T, logits["one_shot"])
+
+    def chunked():
+        cur.copy_(parts[0][1])
+        m.engine.prefill(parts[0][0], cur, B, parts[0][2], logits["chunked"])
+        for x, nl, w in parts[1:]:
+            m.engine.extend(x, nl, cur, B, w, logits["chunked"])
+
+    ways = {"one_shot": one_shot, "chunked": chunked}
+    for fn in ways.values():  # warm-up of each way
+        fn()
+    torch.cuda.synchronize()
+    assert cur.tolist() == [T] * B
+    times = {w: [] for w in ways}
+    for _ in range(reps):
+        for w, fn in ways.items():
+            times[w].append(ev_ms(fn))
+    a, b = logits["chunked"].double(), logits["one_shot"].double()
+    rel = float((a - b).pow(2).mean().sqrt() / b.pow(2).mean().sqrt())
+    tok = {"one_shot": max(B * T, 2 * B), "chunked": max(B * min(T, C), 2 * B)}
+    med = {w: statistics.median(times[w]) for w in ways}
+    for w in ways:
+        r = dict(bench="chunked_prefill", model=name, B=B, T=T, chunk=C, way=w, prefill_ms=round(med[w], 3),
+                 prefill_ms_all=[round(t, 3) for t in times[w]], workspace_tokens=tok[w],
+                 workspace_MB=round(m.engine.workspace_bytes(tok[w]) / 1e6, 1))
+        if w == "chunked":
+            r.update(ratio=round(med["chunked"] / med["one_shot"], 3), logits_rel_rms=float(f"{rel:.3e}"))
+        print(json.dumps(r), flush=True)
+    del m, cache
+    torch.cuda.empty_cache()
+
+
 def logprob_op_bench(calls=200, rounds=5):
     """Device-event time of slam_token_logprobs alone."""
     import torch
@@ -292,7 +351,8 @@ def trace_summary(d):
     rows = {}
 
     def add(name, gx, gy, gz, us):
-        if not any(k in name for k in ("gemm_skinny", "skinny_reduce", "attn_decode", "rmsnorm_fwd", "swiglu_fwd")):
+        if not any(k in name for k in ("gemm_skinny", "skinny_reduce", "attn_decode", "rmsnorm_fwd", "swiglu_fwd", "attn_extend", "kv_extend_scatter",
+                                       "attn_fwd")):
             return
         short = name.split("(")[0].replace("void ", "").replace("(anonymous namespace)::", "")
         rows.setdefault((short, gx, gy, gz), []).append(us)
@@ -322,6 +382,8 @@ def main():
     ap.add_argument("--sample-op", action="store_true", help="time the token choice alone (engine vs torch ops)")
     ap.add_argument("--num-return-sequences", type=int, default=0,
                     help="n: generate of 8 prompts x n from one prefill vs the repeated batch, kv_repeat and token_logprobs alone")
+    ap.add_argument("--prefill-chunk", type=int, default=0,
+                    help="C: prefill of 8 x 2048 prompts in one slam_prefill vs slam_prefill + slam_extend in chunks of C")
     a = ap.parse_args()
     if a.trace_summary:
         trace_summary(a.trace_summary)
@@ -330,6 +392,10 @@ def main():
     assert torch.cuda.is_available()
     if a.sample_op:
         sample_op_bench()
+        return
+    if a.prefill_chunk > 0:
+        for name in a.models.split(","):
+            chunked_prefill_bench(name, 8, 2048, a.prefill_chunk)
         return
     if a.num_return_sequences > 1:
         for name in a.models.split(","):
