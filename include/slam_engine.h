@@ -400,6 +400,21 @@ int slam_adamw_range_bf16_moments(SlamEngine* h, int64_t offset, int64_t count, 
 int slam_adamw_range_bf16(SlamEngine* h, int64_t offset, int64_t count, void* exp_avg_bf16, void* exp_avg_sq_bf16,
                           const float* norm_out, double lr, double beta1, double beta2, double eps, double weight_decay,
                           int32_t step, int32_t zero_grad, slam_stream_t stream);
+/* Which tensors weight_decay applies to. By default every element of the flat buffer is decayed (p *= 1 - lr * weight_decay).
+ * HF Trainer.create_optimizer decays only the names get_decay_parameter_names returns - no bias, no LayerNorm / RMSNorm
+ * parameter - so a reference run with weight_decay != 0 needs this mask (slamkit_amd: UnitLM.hf_decay_flags(),
+ * training_args.weight_decay_rule = "hf"). decay: HOST array of n_tensors bytes in slam_tensor_info order, decay[i] == 0 =
+ * tensor i is not decayed; n_tensors must equal slam_tensor_count (SLAM_EINVAL otherwise). decay == NULL clears the mask
+ * (n_tensors is ignored) and restores uniform decay: the launches are then exactly those of an engine that never had one.
+ * Host bookkeeping + one small synchronous upload of an engine-owned table (the merged element ranges of the no-decay
+ * tensors; every tensor offset is a multiple of 8, so a kernel thread's 4 or 8 elements never straddle a bound). Legal any
+ * time after create, outside stream capture; survives re-binding of parameters and workspace. Every optimizer entry point
+ * honours it: slam_adamw_step* on the flat path, on the fused walk that writes the transposed images (decided per tensor on
+ * the host: a no-decay tensor is launched with weight_decay = 0) and in the "overlap_adamw" chunks; slam_adamw_range*
+ * wherever a shard cuts a tensor. A no-decay element goes through the same arithmetic with weight_decay = 0 (p * 1.0f is
+ * exact), so a masked step equals, bit for bit, the unmasked step with the caller's weight_decay on the decayed tensors and
+ * the unmasked step with weight_decay = 0 on the others - in every state precision and with "adamw_sr". */
+int slam_set_decay_mask(SlamEngine* h, const uint8_t* decay, int32_t n_tensors);
 /* Another stream (the all-gather of a parameter bucket) is still writing the bound bf16 parameters in [offset, offset +
  * count); `event` (hipEvent_t, owned by the caller, alive until the next forward was enqueued) is recorded behind that
  * write. The next slam_forward waits for it right before its first read of the range - layer by layer, so the gather of

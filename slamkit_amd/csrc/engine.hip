@@ -8,6 +8,7 @@
 #include <dlfcn.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -122,6 +123,14 @@ struct SlamEngine {
   // follow from the seed, the step the caller passes and the element's index in the flat buffer
   int adamw_sr = 0;
   uint64_t adamw_sr_seed = 0;
+  // slam_set_decay_mask: the tensors that take weight_decay = 0, as the sorted bounds of their merged ranges (kernels.h
+  // AdamNoDecay). nd_host decides per parameter group where the optimizer walks the model (adamw_model); nd_dev - engine-owned
+  // device memory, the same bounds + the sentinel - is what the flat and ranged kernels search. Empty / null: uniform decay.
+  std::vector<uint64_t> nd_host;
+  uint64_t* nd_dev = nullptr;
+  bool no_decay(int64_t off) const {
+    return ((std::upper_bound(nd_host.begin(), nd_host.end(), (uint64_t)off) - nd_host.begin()) & 1) != 0;
+  }
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_chunk;  // [0] embedding, [1 + l] layer l, [L + 1] final norm (+ an untied lm_head and its transposed image)
@@ -195,6 +204,7 @@ struct SlamEngine {
     for (hipEvent_t e : comm_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ag_ev) (void)hipEventDestroy(e);
     if (comm_stream) { (void)hipStreamSynchronize(comm_stream); (void)hipStreamDestroy(comm_stream); }
+    if (nd_dev) (void)hipFree(nd_dev);
   }
   // parameter ranges another stream is still writing (sharded optimizer: the bf16 parameter all-gather on the
   // communication stream): the next reader waits for the event right before its first read of the range
@@ -586,11 +596,28 @@ int for_each_param_group(SlamEngine* h, int chunk, F&& fn) {
 }
 // AdamW (`a`: the update at element 0 of the flat buffers) over a chunk of the model with transposed weight images bound:
 // every matrix goes through the tile kernel that writes its transposed image in the same pass (no separate transpose launch),
-// the vectors between them through the strided kernel.
+// the vectors between them through the strided kernel. A group is whole tensors, so the no-decay set (slam_set_decay_mask) is
+// applied here, on the host: a tensor outside the decay set is launched with wd = 0 through the same kernels, and a batch of
+// layers goes out layer by layer only where the flags differ across the layers (never under the HF rule).
 int adamw_model(SlamEngine* h, const AdamArgs& a, int chunk, hipStream_t st) {
   return for_each_param_group(h, chunk, [&](int64_t off, int64_t rows, int cols, int batch) {
-    if (cols == 1) return adamw_strided(a.at(off), (size_t)rows, batch, (size_t)h->layer_stride, st);
-    return adamw_tiles(a.at(off), (int)rows, cols, batch, (size_t)h->layer_stride, st);
+    auto run = [&](int64_t o, int nb, bool decay) {
+      AdamArgs g = a.at(o);
+      g.nd = AdamNoDecay{};
+      if (!decay) g.wd = 0;
+      if (cols == 1) return adamw_strided(g, (size_t)rows, nb, (size_t)h->layer_stride, st);
+      return adamw_tiles(g, (int)rows, cols, nb, (size_t)h->layer_stride, st);
+    };
+    if (h->nd_host.empty()) return run(off, batch, true);
+    const bool nd0 = h->no_decay(off);
+    bool same = true;
+    for (int l = 1; l < batch; ++l) same = same && h->no_decay(off + l * h->layer_stride) == nd0;
+    if (same) return run(off, batch, !nd0);
+    for (int l = 0; l < batch; ++l) {
+      const int64_t o = off + l * h->layer_stride;
+      if (int r = run(o, 1, !h->no_decay(o))) return r;
+    }
+    return 0;
   });
 }
 // the separate transpose pass as a visitor of the same walk: one launch per group of matrices, grid.z = batch
@@ -1676,6 +1703,7 @@ static AdamArgs adam_args(SlamEngine* h, int mode, const float* norm_out, double
   a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps; a.wd = wd;
   a.step = step; a.zero_grad = zero_grad;
   a.sr.on = h->adamw_sr; a.sr.seed = h->adamw_sr_seed;
+  if (h->nd_dev) { a.nd.bounds = h->nd_dev; a.nd.n = (int)h->nd_host.size(); }
   return a;
 }
 
@@ -1792,6 +1820,34 @@ int slam_adamw_range_bf16(SlamEngine* h, int64_t offset, int64_t count, void* m_
                           double lr, double b1, double b2, double eps, double wd, int32_t step, int32_t zero_grad,
                           slam_stream_t stream) {
   return adamw_range_impl(h, 2, offset, count, nullptr, m_bf16, v_bf16, norm_out, lr, b1, b2, eps, wd, step, zero_grad, stream);
+}
+
+int slam_set_decay_mask(SlamEngine* h, const uint8_t* decay, int32_t n_tensors) {
+  if (!h) return SLAM_EINVAL;
+  std::vector<uint64_t> b;
+  if (decay) {
+    const size_t nt = h->tensors.size();
+    if (n_tensors != (int32_t)nt) return h->fail(SLAM_EINVAL, "decay mask: n_tensors must equal slam_tensor_count");
+    for (size_t i = 0; i < nt; ++i) {
+      if (decay[i]) continue;
+      const uint64_t lo = (uint64_t)h->tensors[i].offset, hi = (uint64_t)(i + 1 < nt ? h->tensors[i + 1].offset : h->n_params);
+      if ((lo | hi) & 7) return h->fail(SLAM_EINVAL, "decay mask: tensor bounds must be multiples of 8");
+      if (!b.empty() && b.back() == lo) b.back() = hi;  // adjacent no-decay tensors: one range
+      else { b.push_back(lo); b.push_back(hi); }
+    }
+  }
+  uint64_t* dev = nullptr;
+  if (!b.empty()) {
+    std::vector<uint64_t> up(b);
+    up.push_back(UINT64_MAX);  // the sentinel that ends a thread's walk
+    CK((int)hipMalloc(&dev, up.size() * sizeof(uint64_t)));
+    const int r = (int)hipMemcpy(dev, up.data(), up.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (r) { (void)hipFree(dev); CK(r); }
+  }
+  if (h->nd_dev) CK((int)hipFree(h->nd_dev));  // synchronises with the device: no update in flight still reads the old table
+  h->nd_dev = dev;
+  h->nd_host.swap(b);
+  return SLAM_OK;
 }
 
 int slam_add_param_wait(SlamEngine* h, int64_t offset, int64_t count, void* event) {

@@ -184,6 +184,12 @@ int grad_norm_from_chunks(const float* chunk_sums, size_t n_chunks, float max_no
 // index in the engine's flat parameter buffer, which array) alone; base = that index for element 0 of the arrays handed over.
 // Rounded: m and v wherever they are bf16, p where the bf16 parameters are the state (mode 2). fp32 state (mode 0) ignores it.
 struct AdamSR { int on = 0; uint64_t seed = 0; int64_t base = 0; };
+// The no-decay set (slam_set_decay_mask): half-open ranges of the flat parameter buffer that take weight_decay = 0. bounds
+// (device memory) = lo0, hi0, lo1, hi1, .. - n strictly increasing flat indices, every one a multiple of 8, closed by one
+// sentinel bounds[n] = UINT64_MAX: an element lies in a range iff an odd number of bounds is <= its index, and the 4 or 8
+// consecutive elements of a kernel thread lie in one range or in none. base = the flat index of element 0 of the arrays handed
+// over. bounds == nullptr: wd applies to every element, through the kernels that know nothing of the table.
+struct AdamNoDecay { const uint64_t* bounds = nullptr; int n = 0; int64_t base = 0; };
 // One AdamW update, from the engine's entry points down to the kernel launch: every pointer is at the same element.
 struct AdamArgs {
   int mode = 0;                // 0 = fp32 master + fp32 moments, 1 = fp32 master + bf16 moments, 2 = bf16 parameters + bf16 moments
@@ -198,6 +204,7 @@ struct AdamArgs {
   double lr = 0, b1 = 0, b2 = 0, eps = 0, wd = 0;
   int step = 1, zero_grad = 0;
   AdamSR sr;
+  AdamNoDecay nd;  // honoured by adamw_flat and adamw_strided; adamw_tiles takes one wd for the launch (the caller decides per matrix)
   // the same update `off` elements further on
   AdamArgs at(int64_t off) const {
     AdamArgs a = *this;
@@ -209,11 +216,12 @@ struct AdamArgs {
     if (m) a.m = (char*)m + off * esz;
     if (v) a.v = (char*)v + off * esz;
     a.sr.base = sr.base + off;
+    a.nd.base = nd.base + off;
     return a;
   }
 };
 // n consecutive elements. Mode 2 goes 8 elements per thread (n and, when rounding stochastically, sr.base multiples of 8),
-// modes 0 and 1 four (multiples of 4)
+// modes 0 and 1 four (multiples of 4); with a no-decay table nd.base is a multiple of 8 / 4 as well
 int adamw_flat(const AdamArgs& a, size_t n, hipStream_t st);
 // `batch` vectors of n elements at a constant stride
 int adamw_strided(const AdamArgs& a, size_t n, int batch, size_t stride, hipStream_t st);

@@ -83,6 +83,11 @@ __global__ __launch_bounds__(1024) void norm_finish_kernel(const float* __restri
 
 // sr: the key of the stochastic rounding of the bf16 state stores (read by the SR = true kernels only)
 struct AdamHyper { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int zero_grad; SrKey sr; };
+// the no-decay table (kernels.h AdamNoDecay) as the last argument of a MASKED kernel; the others take an empty one and stay,
+// instruction for instruction, the kernels they were before there was a table
+struct NoDecayTab { const uint64_t* b; int n; uint64_t base; };
+struct NoTab {};
+template <bool MASKED> using NdArg = std::conditional_t<MASKED, NoDecayTab, NoTab>;
 template <typename MT> SLAM_DEVICE void load4(const MT* q, float* f);
 template <> SLAM_DEVICE void load4<float>(const float* q, float* f) {
   const float4 t = *reinterpret_cast<const float4*>(q);
@@ -147,15 +152,43 @@ SLAM_DEVICE void adam_update(float& p, float& m, float& v, float g, float cs, co
   if constexpr (SR) adam_elem_pinned<MASTER>(p, m, v, g, cs, h);
   else adam_elem<MASTER>(p, m, v, g * cs, h);
 }
+// MASKED kernels: the hyper-parameters of the thread whose 4 or 8 consecutive elements start at flat index gi - wd = 0 when they
+// lie in a range of the no-decay table, so that the element goes through the one expression of adam_elem (p * 1.0f is exact).
+// The position in the table = the number of bounds <= gi; odd = inside a range. `first` is the flat index of the block's
+// first element, the same for every thread: its binary search runs once per wave on scalar loads of uniform addresses (a table
+// of a few hundred bounds: 8 or 9 dependent loads, issued behind the thread's own state loads so that the latencies overlap), and a
+// thread walks on from there to its own group - no step at all in the blocks that no bound cuts, which is nearly all of them
+// (Slam-358M: 146 bounds in 358 M elements; a block covers 1024 or 2048). The sentinel ends the walk. Measured cost
+// (profiles/decay_rule.md): nothing with bf16 gradients, +1 % on the flat kernel with fp32 gradients.
+// first / gi arrive relative to the arrays handed over (nd.base = the flat index of their element 0).
+template <bool MASKED>
+SLAM_DEVICE AdamHyper hyper_at(const AdamHyper& h, const NdArg<MASKED>& nd, uint64_t first, uint64_t gi) {
+  if constexpr (MASKED) {
+    first += nd.base; gi += nd.base;
+    int lo = 0, hi = nd.n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (nd.b[mid] <= first) lo = mid + 1;
+      else hi = mid;
+    }
+    while (nd.b[lo] <= gi) ++lo;
+    AdamHyper r = h;
+    if (lo & 1) r.wd = 0.f;
+    return r;
+  } else {
+    return h;
+  }
+}
 // The Slam recipe's optimizer precision (/root/reference config/model/slam.yaml:9 torch_dtype bfloat16 -> bf16 parameters
 // and bf16 Adam moments under torch.optim.AdamW(fused=True)): state is STORED in bf16, every update is computed in fp32
 // from the stored values and rounded once on the way back (torch's fused kernel: opmath fp32, exp_avg by lerp).
 // No fp32 master copy. Traffic: fp32 g read (4) + bf16 p, m, v read and written (12) = 16 B/param.
 // SR ("adamw_sr"): p, m and v are rounded stochastically (sr_bf16), keyed on sr.base + i - the element's index in the flat buffer.
-template <typename GT, bool SR>
+// MASKED: wd per thread from the no-decay table (nd.base + i = the flat index).
+template <typename GT, bool SR, bool MASKED>
 __global__ __launch_bounds__(256) void adamw_bf16_kernel(bf16_t* __restrict__ p, GT* __restrict__ g,
                                                          bf16_t* __restrict__ m, bf16_t* __restrict__ v, size_t n,
-                                                         const float* __restrict__ clip, AdamHyper h) {
+                                                         const float* __restrict__ clip, AdamHyper h0, NdArg<MASKED> nd) {
   size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
   if (i >= n) return;
   const float cs = clip ? clip[1] : 1.f;
@@ -166,6 +199,7 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(bf16_t* __restrict__ p,
   unpack_bf16x8(*reinterpret_cast<const uint4*>(p + i), pa);
   unpack_bf16x8(*reinterpret_cast<const uint4*>(m + i), ma);
   unpack_bf16x8(*reinterpret_cast<const uint4*>(v + i), va);
+  const AdamHyper h = hyper_at<MASKED>(h0, nd, (uint64_t)blockIdx.x * 2048, i);
 #pragma unroll
   for (int j = 0; j < 8; ++j) adam_update<false, SR>(pa[j], ma[j], va[j], ga[j], cs, h);
   *reinterpret_cast<uint4*>(p + i) = round8<SR>(pa, h.sr, h.sr.base + i, 0);
@@ -292,10 +326,10 @@ __global__ __launch_bounds__(256) void adamw_tile_bf16x8_kernel(bf16_t* __restri
   for (int q = 0; q < TC / 64; ++q) store_tile_t<TC>(T, pt, boff, R, r0, c0, q);
 }
 // the vectors between the matrices (norm weights, biases): count elements at a constant stride, grid.y = instances
-template <typename MT, bool MASTER, typename GT, bool SR>
+template <typename MT, bool MASTER, typename GT, bool SR, bool MASKED>
 __global__ __launch_bounds__(256) void adamw_strided_kernel(float* __restrict__ p, bf16_t* __restrict__ pb, GT* __restrict__ g,
                                                             MT* __restrict__ m, MT* __restrict__ v, size_t n, size_t stride,
-                                                            const float* __restrict__ clip, AdamHyper h) {
+                                                            const float* __restrict__ clip, AdamHyper h0, NdArg<MASKED> nd) {
   const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i >= n) return;
   const size_t idx = (size_t)blockIdx.y * stride + i;
@@ -306,6 +340,7 @@ __global__ __launch_bounds__(256) void adamw_strided_kernel(float* __restrict__ 
   else load4<bf16_t>(pb + idx, pa);
   load4<MT>(m + idx, ma);
   load4<MT>(v + idx, va);
+  const AdamHyper h = hyper_at<MASKED>(h0, nd, (uint64_t)blockIdx.y * stride + (uint64_t)blockIdx.x * 1024, idx);
 #pragma unroll
   for (int j = 0; j < 4; ++j) adam_update<MASTER, SR>(pa[j], ma[j], va[j], ga[j], cs, h);
   if (MASTER) store4(p + idx, pa);
@@ -423,6 +458,10 @@ int sr_round_bf16(const float* x, bf16_t* y, size_t n, int64_t index0, uint64_t 
   sr_round_bf16_kernel<<<nblocks(n, 256), 256, 0, st>>>(x, y, n, sr_key(sr, step), (uint32_t)which);
   LAUNCH_RET();
 }
+template <bool MASKED> static NdArg<MASKED> nd_arg(const AdamArgs& a) {
+  if constexpr (MASKED) return {a.nd.bounds, a.nd.n, (uint64_t)a.nd.base};
+  else return {};
+}
 static AdamHyper adam_hyper(const AdamArgs& a) {
   // bias corrections in double like torch.optim.AdamW (python floats), then fp32 in the kernel
   AdamHyper h;
@@ -481,26 +520,34 @@ int adamw_strided(const AdamArgs& a, size_t n, int batch, size_t stride, hipStre
   if ((n & 3) || batch < 1 || a.mode < 0 || a.mode > 2) return -1;
   if (n == 0) return 0;
   const bool sr_on = a.sr.on && a.mode != 0;
-  if (sr_on && ((a.sr.base & 3) || (batch > 1 && (stride & 3)))) return -1;  // a thread's 4 elements share one group of 8
+  const bool masked = a.nd.bounds != nullptr;
+  if ((sr_on && (a.sr.base & 3)) || (masked && (a.nd.base & 3)) || ((sr_on || masked) && batch > 1 && (stride & 3)))
+    return -1;  // a thread's 4 elements share one group of 8
   const AdamHyper h = adam_hyper(a);
   adam_dispatch(a, sr_on, [&](auto m16, auto master, auto g16, auto sr) {
-    using MT = Elem<decltype(m16)>;
-    using GT = Elem<decltype(g16)>;
-    adamw_strided_kernel<MT, decltype(master)::value, GT, decltype(sr)::value><<<dim3(nblocks(n / 4, 256), batch), 256, 0, st>>>(
-        a.master, a.params, (GT*)a.g, (MT*)a.m, (MT*)a.v, n, stride, a.clip, h);
+    with_flag(masked, [&](auto mk) {
+      using MT = Elem<decltype(m16)>;
+      using GT = Elem<decltype(g16)>;
+      adamw_strided_kernel<MT, decltype(master)::value, GT, decltype(sr)::value, decltype(mk)::value>
+          <<<dim3(nblocks(n / 4, 256), batch), 256, 0, st>>>(a.master, a.params, (GT*)a.g, (MT*)a.m, (MT*)a.v, n, stride, a.clip, h,
+                                                             nd_arg<decltype(mk)::value>(a));
+    });
   });
   LAUNCH_RET();
 }
 int adamw_flat(const AdamArgs& a, size_t n, hipStream_t st) {
   if (a.mode != 2) return adamw_strided(a, n, 1, 0, st);  // one instance of the strided kernel
   // bf16 parameters and bf16 moments updated in place, 8 elements (16 bytes per array) per thread
-  if ((n & 7) || (a.sr.on && (a.sr.base & 7))) return -1;
+  const bool masked = a.nd.bounds != nullptr;
+  if ((n & 7) || (a.sr.on && (a.sr.base & 7)) || (masked && (a.nd.base & 7))) return -1;
   const AdamHyper h = adam_hyper(a);
   with_flag(a.g_bf16, [&](auto g16) {
     with_flag(a.sr.on, [&](auto sr) {
-      using GT = Elem<decltype(g16)>;
-      adamw_bf16_kernel<GT, decltype(sr)::value><<<nblocks(n / 8, 256), 256, 0, st>>>(a.params, (GT*)a.g, (bf16_t*)a.m, (bf16_t*)a.v, n,
-                                                                                   a.clip, h);
+      with_flag(masked, [&](auto mk) {
+        using GT = Elem<decltype(g16)>;
+        adamw_bf16_kernel<GT, decltype(sr)::value, decltype(mk)::value><<<nblocks(n / 8, 256), 256, 0, st>>>(
+            a.params, (GT*)a.g, (bf16_t*)a.m, (bf16_t*)a.v, n, a.clip, h, nd_arg<decltype(mk)::value>(a));
+      });
     });
   });
   LAUNCH_RET();

@@ -109,6 +109,7 @@ def load_library(path: Optional[str] = None):
         "slam_grad_norm_from_chunks": (C.c_int, [vp, vp, f32, vp, vp]),
         "slam_adamw_range": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
         "slam_adamw_range_bf16": (C.c_int, [vp, i64, i64, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
+        "slam_set_decay_mask": (C.c_int, [vp, vp, i32]),
         "slam_add_param_wait": (C.c_int, [vp, i64, i64, vp]),
         "slam_param_wait_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "slam_param_wait_untimed": (C.c_int, [vp, C.POINTER(C.c_int64)]),
@@ -507,6 +508,15 @@ class Engine:
             self._ck(self.lib.slam_adamw_range(self.h, o, n, _ptr(master[o:o + n]), _ptr(exp_avg[o:o + n]), _ptr(exp_avg_sq[o:o + n]),
                                                _ptr(norm_out), float(lr), float(beta1), float(beta2), float(eps),
                                                float(weight_decay), int(step), int(bool(zero_grad)), st))
+
+    def set_decay_mask(self, flags=None):
+        """slam_set_decay_mask: flags = one truthy / falsy value per engine tensor, in `tensors` order (falsy = weight_decay does
+        not apply to that tensor); None clears the mask (every tensor is decayed again)."""
+        if flags is None:
+            self._ck(self.lib.slam_set_decay_mask(self.h, None, len(self.tensors)))
+            return
+        buf = (C.c_uint8 * len(flags))(*[1 if f else 0 for f in flags])
+        self._ck(self.lib.slam_set_decay_mask(self.h, buf, len(flags)))
 
     def add_param_wait(self, offset: int, count: int, event):
         """event: a recorded torch.cuda.Event; kept alive here until the next forward consumed it."""

@@ -11,8 +11,10 @@ HIP library or a GPU, construction fails.
 """
 from __future__ import annotations
 
+import bisect
 import json
 import os
+import re
 from dataclasses import dataclass, field
 from typing import Dict, Iterator, List, NamedTuple, Optional, Tuple
 
@@ -57,6 +59,19 @@ _HF_DIM_KEYS = ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_
 def dropout_thr16(p: float) -> int:
     """The engine's 16-bit drop threshold of a dropout probability (option "dropout_thr16"): round(p * 65536)."""
     return int(round(float(p) * 65536.0))
+
+
+# transformers Trainer.get_decay_parameter_names: forbidden_name_patterns (regular expressions searched in the parameter name)
+HF_NO_DECAY_PATTERNS = (r"bias", r"layernorm", r"rmsnorm", r"(?:^|\.)norm(?:$|\.)", r"_norm(?:$|\.)")
+
+
+def hf_name_is_decayed(name: str, is_opt: bool) -> bool:
+    """Whether HF's Trainer applies weight_decay to the parameter `name` of a Qwen2 / OPT causal LM. Besides the name patterns
+    HF excludes the parameters of every nn.LayerNorm module: OPT's `*_layer_norm` (Qwen2's norms are Qwen2RMSNorm - no
+    nn.LayerNorm - and go by name)."""
+    if any(re.search(p, name.lower()) for p in HF_NO_DECAY_PATTERNS):
+        return False
+    return not (is_opt and "layer_norm." in name)
 
 
 def _opt_base_config(c: dict) -> dict:
@@ -421,6 +436,25 @@ class UnitLM(TokenLM):
             km[p + "final_layer_norm.weight"] = (t[q + "ln2"].offset, (H,))
             km[p + "final_layer_norm.bias"] = (t[q + "ln2_b"].offset, (H,))
         self.key_map = km
+
+    def hf_decay_flags(self) -> List[bool]:
+        """HF Trainer's weight-decay rule per engine tensor, in `engine.tensors` order: True = decayed. Restated from
+        transformers `Trainer.get_decay_parameter_names`: every parameter except those of an nn.LayerNorm and those whose name
+        matches one of HF_NO_DECAY_PATTERNS. The rule is applied to the HF names the key map puts into each engine tensor; the
+        parts of a fused tensor (wqkv, bqkv, wgu) must agree. Embeddings, OPT's positions and an untied lm_head are decayed."""
+        by_tensor: Dict[str, List[str]] = {}
+        starts = sorted((t.offset, name) for name, t in self.engine.tensors.items())
+        for key, ent in self.key_map.items():
+            i = bisect.bisect_right(starts, (ent[0], chr(0x10FFFF))) - 1
+            by_tensor.setdefault(starts[i][1], []).append(key)
+        flags = []
+        for name in self.engine.tensors:
+            keys = by_tensor.get(name)
+            assert keys, f"engine tensor {name} has no HF name"
+            decayed = {hf_name_is_decayed(k, self.config.is_opt) for k in keys}
+            assert len(decayed) == 1, f"the HF names of {name} disagree about weight decay: {keys}"
+            flags.append(decayed.pop())
+        return flags
 
     def _view(self, flat: torch.Tensor, key: str, writable: bool = False) -> torch.Tensor:
         """HF-named window of a flat engine buffer. gate_proj / up_proj live interleaved in 32-row blocks:

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from .callbacks import TrainerCallback, TrainerControl, TrainerState
 from .dp import GradBucketReducer, ShardedGradReducer, all_reduce_scalar, host_group, seeded_batches, shard_batches, world_info
-from .training_args import SLAMTrainingArguments, lr_lambda
+from .training_args import SLAMTrainingArguments, check_weight_decay_rule, lr_lambda
 
 logger = logging.getLogger(__name__)
 
@@ -132,6 +132,13 @@ class SLAMTrainer:
             sd = getattr(self.args, "optim_sr_seed", None)
             model.engine.set_option("adamw_sr_seed", int(getattr(self.args, "seed", 0) if sd is None else sd))
         model.engine.set_option("adamw_sr", 1 if sr else 0)
+        # weight_decay_rule "hf": the engine keeps the mask, so the replicated step, the sharded ranges (rs_ag) and the overlapped
+        # chunks all honour it - nothing below passes it on. "all" makes no engine call: the launches stay what they were
+        # (fields set after construction get past the arguments' own check)
+        if check_weight_decay_rule(getattr(self.args, "weight_decay_rule", "all")) == "hf":
+            if not hasattr(model, "hf_decay_flags"):
+                raise ValueError("weight_decay_rule='hf' needs a model that knows its HF parameter names (UnitLM.hf_decay_flags)")
+            model.engine.set_decay_mask(model.hf_decay_flags())
         # residual dropout (OPT): stateless like the rounding above. The seed mixes in the rank so that ranks draw different
         # masks; the call number is set before every micro-batch (optimizer_step), so a resumed run repeats the uninterrupted one
         self._sets_dropout = hasattr(model, "set_dropout_state")

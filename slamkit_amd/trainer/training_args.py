@@ -20,6 +20,7 @@ class SLAMTrainingArguments:
     per_device_eval_batch_size: int = 8
     gradient_accumulation_steps: int = 1
     weight_decay: float = 0.0
+    weight_decay_rule: str = "all"                 # which tensors weight_decay applies to. "all": every element of the flat parameter buffer (the engine's historical behaviour; at weight_decay 0 - every shipped recipe - the two rules coincide). "hf": HF Trainer.create_optimizer's rule - no bias, no LayerNorm / RMSNorm parameter (UnitLM.hf_decay_flags -> slam_set_decay_mask): what reproduces a reference run with a non-zero weight_decay
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_epsilon: float = 1e-8
@@ -57,6 +58,7 @@ class SLAMTrainingArguments:
     run_name: Optional[str] = None
 
     def __post_init__(self):
+        check_weight_decay_rule(self.weight_decay_rule)
         if self.optim_stochastic_rounding and (self.optim_state_dtype or "float32") == "float32":
             raise ValueError("optim_stochastic_rounding needs bf16 optimizer state (optim_state_dtype bfloat16 or "
                              "float32_bf16_moments): with float32 state nothing is rounded")
@@ -76,6 +78,12 @@ class SLAMTrainingArguments:
     def get_warmup_steps(self, num_training_steps: int) -> int:
         """TrainingArguments.get_warmup_steps: warmup_steps wins when > 0, else ceil(ratio * steps)."""
         return self.warmup_steps if self.warmup_steps > 0 else math.ceil(num_training_steps * self.warmup_ratio)
+
+
+def check_weight_decay_rule(rule) -> str:
+    if rule not in ("all", "hf"):
+        raise ValueError(f"weight_decay_rule must be 'all' or 'hf', got {rule!r}")
+    return rule
 
 
 def lr_lambda(args: SLAMTrainingArguments, step: int, num_training_steps: int) -> float:
