@@ -182,7 +182,8 @@ int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t*
  *   Errors, all before any launch: SLAM_EINVAL for h or lens NULL, n < 1 or B n > max_batch; SLAM_ESTATE without a bound
  *   cache, without a prefill, or after a decode step. slam_extend calls between the prefill and the fan-out are fine.
  * slam_extend: appends a chunk of up to T tokens per row behind the keys the cache already holds - chunked prefill, a
- *   continuation of a cached sequence, teacher-forcing a given continuation, verifying several proposed tokens at once.
+ *   continuation of a cached sequence. (Teacher-forcing a given continuation or verifying several proposed tokens at once
+ *   needs every chunk position scored: slam_extend_score, below.)
  *   ids: int64 [B][T] device, right-padded with any valid id. new_lens: int32 [B] device, 0 <= new_lens[b] <= T: the real
  *   tokens of row b are columns 0 .. new_lens[b]-1. lens: int32 [B] device, the rows' key counts - the array
  *   slam_decode_step advances. Token t of row b runs at position lens[b] + t: one layer loop over B T tokens (the prefill's
@@ -222,6 +223,29 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
 int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_stream_t stream);
 int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
                 float* logits_out, slam_stream_t stream);
+
+/* ---- scoring a given continuation through the cache (teacher forcing, verifying proposed tokens, a frozen reference's
+ * log-probs of sampled continuations) ------------------------------------------------------------------------------------------
+ * slam_extend_score is slam_extend - the same body, the same launches in the same order, so for equal arguments the cache,
+ * lens and logits_out are bit-identical to slam_extend's - plus, between the layer loop and the last-token head, the final
+ * norm of all B T chunk rows and the LM head fused with the row statistics (slam_op_score_rows below: fp32 scores that are
+ * never rounded to bf16 and never stored).
+ *   lp_out   fp32 [B][T] device. Column t with 1 <= t < new_lens[b]: the log-prob OF ids[b][t] given the cache and
+ *            ids[b][0 .. t). Columns t >= max(1, new_lens[b]) are 0.0f. Column 0 is NEVER written: it belongs to the caller,
+ *            who fills it with slam_token_logprobs(column = 0, out_stride = T) on the logits the rows held before this call
+ *            (a prefill's, a decode step's or the previous chunk's logits_out). Chunks chain the same way.
+ *   argmax_out  int64 [B][T] device, nullable. t < new_lens[b]: the greedy next token after position t (the lowest id of the
+ *            largest score, -1 when no score is above -inf); -1 for t >= new_lens[b]. A proposed token ids[b][t + 1] is
+ *            accepted iff it equals argmax_out[b][t].
+ * The logit mask (slam_set_logit_mask) is honoured: a masked column counts as -inf, a masked target gives -inf. The rows of
+ * padded positions are computed and dropped. Scratch, all in buffers the call leaves free behind the layer loop: the rows'
+ * targets (int64 [B T]) in the backward-only d(qkv) buffer; the chunk partials ([B T][chunks] x 16 bytes) and the targets'
+ * scores at the start of the logits buffer - the attention split partials that lived there are dead by then, and the
+ * last-token fp32 logits are written there only behind these launches (one stream); the normed rows in the final-norm
+ * buffer, which the last-token norm then overwrites. Errors: those of slam_extend, plus SLAM_EINVAL for a NULL lp_out, all
+ * before any launch; an OPT engine returns SLAM_EINVAL as slam_extend does. */
+int slam_extend_score(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                      float* logits_out, float* lp_out, int64_t* argmax_out, slam_stream_t stream);
 
 /* ---- choosing the next token on the device (what HF's logits processors + torch.multinomial do between two decode steps) ----
  * slam_sample_tokens needs no engine: it reads fp32 logits [B][vocab] (row stride vocab, 4-byte aligned; odd vocabularies
@@ -562,6 +586,32 @@ int slam_op_gemm_tn_image(const void* dY, const void* X, float* dW, void* dW_bf1
 size_t slam_op_gemm_skinny_workspace(int M, int N, int K);
 int slam_op_gemm_skinny(const void* X, const void* W, void* Y, int y_f32, const void* bias, const void* resid, int M, int N, int K,
                         float* ws, size_t ws_bytes, slam_stream_t s);
+/* LM head fused with the row statistics, alone (the hot path of slam_extend_score). X bf16 [M][K] (K % 8 == 0), W bf16 [V][K],
+ * both 16-byte aligned. x_i = the fp32 accumulator of v_mfma_f32_16x16x32_bf16 for row m against vocabulary row i, K taken
+ * in ascending steps of 32 (a last partial step is zero-filled): its order depends on K alone. x_i is never rounded to bf16
+ * and never stored as an [M][V] array. Each score is read as the sampler reads it: NaN counts as -inf, +inf as FLT_MAX; a
+ * column i with colmask[i] != 0 (colmask: nullable, uint8, at least V bytes) counts as -inf.
+ *   lp[m]      x_target - (m + logf(S)) for target = targets[m] (int64 [M]); 0.0f when the target is outside [0, V) (-100: no
+ *              target); -inf when the target is masked or the row has no score above -inf.
+ *   argmax[m]  (int64 [M], nullable) the id of the largest x_i, the LOWEST id among equals; -1 when no score is above -inf.
+ * m and S, in fp32. The vocabulary is cut into chunks of SLAM_SCORE_CHUNK = 512 columns; the width depends on nothing else.
+ * A chunk is 8 groups of 64 consecutive columns. In a group, with m_g = max x_i and e_i = expf(x_i - m_g): for j = 0 .. 15,
+ * a_j = (((0 + e_j) + e_{16+j}) + e_{32+j}) + e_{48+j} over the group's columns j, 16 + j, 32 + j, 48 + j (a column at or
+ * beyond V, or masked, has e = 0); the sixteen a_j are summed by the xor butterfly a_j += a_{j ^ o} for o = 8, 4, 2, 1, which
+ * gives s_g (0 when m_g = -inf). The groups of a chunk are combined in group order, m_c = max m_g, s_c starting at 0 and
+ * taking s_c = fmaf(s_g, expf(m_g - m_c), s_c) with groups of m_g = -inf skipped. Each chunk yields (m_c, s_c, best value,
+ * best id); the chunks are combined in chunk order the same way, m = max m_c; S = fmaf(s_c, expf(m_c - m), S), skipping chunks
+ * of m_c = -inf - one rounding per part. The best id moves to a later group / chunk only on a strictly larger value.
+ * No floating-point atomics: the chunk partials go through ws and a SECOND launch merges them in chunk order. A row's result
+ * depends on (its X row, W, its target, the mask) alone - not on M, the row's index or the grid - and is the same bits on
+ * every run. Tail rows and tail columns are never read out of bounds.
+ * ws: slam_op_score_rows_workspace(M, V) bytes of device memory, 16-byte aligned (host arithmetic; 0 for M or V outside the ranges below).
+ * SLAM_EINVAL before any launch: X, W, targets, lp or ws NULL; M <= 0 or M > 33554431; V <= 0 or V > 33553920 (65535 chunks); K <= 0 or K % 8 != 0; X, W
+ * or ws not 16-byte aligned; targets / argmax not 8-byte, lp not 4-byte aligned; ws_bytes too small. */
+#define SLAM_SCORE_CHUNK 512
+size_t slam_op_score_rows_workspace(int M, int V);
+int slam_op_score_rows(const void* X, const void* W, const int64_t* targets, const uint8_t* colmask, float* lp, int64_t* argmax,
+                       int M, int V, int K, void* ws, size_t ws_bytes, slam_stream_t s);
 /* one decode step of attention: qkv fp32 [B][(nH + 2 nKV) head_dim] projection without bias, bias bf16 [..] (nullable), lens
  * int32 [B] device = the new token's position. Bias and RoPE are applied in fp32 (queries pre-scaled as in the forward), the
  * new K / V rows are written to row lens[b] of k_cache / v_cache (bf16 [B][nKV][capacity][head_dim]) and o (bf16

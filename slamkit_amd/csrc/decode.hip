@@ -1001,6 +1001,184 @@ __global__ __launch_bounds__(SP_THREADS) void logprob_finish_kernel(const float*
   if (finished) finished[b] = done ? done[b] : (uint8_t)0;
 }
 
+// ---- fused head + row statistics (slam_op_score_rows, slam_extend_score) -----------------------------------------------------
+// x[m][i] = the fp32 accumulator of X row m against W row i; it lives in the accumulator registers only. The vocabulary is
+// cut into chunks of SCORE_CHUNK columns, a chunk into SCORE_GROUPS groups of 64 consecutive columns. One block = 64 rows x
+// one chunk; wave w forms groups 2 w and 2 w + 1 one after the other, a group as 4 column tiles x MT row tiles of
+// v_mfma_f32_16x16x32_bf16 with both operands loaded 16 B per lane straight into the operand registers (the four waves read
+// the same X rows: L1; the row blocks of one chunk are neighbours in the grid and read the same W rows: L2).
+// Group statistics of a row, lane j of a 16-lane set holding columns j, 16 + j, 32 + j, 48 + j of the group:
+//   m_g = max; s_g = ((((0 + e_j) + e_16+j) + e_32+j) + e_48+j) with e_i = expf(x_i - m_g), then the 16 lanes by the xor
+//   butterfly 8, 4, 2, 1 (0 when m_g = -inf); best = the largest score, the lowest id among equals.
+// Groups, then chunks, are combined in ascending order by score_merge: one fused multiply-add per part.
+constexpr int SCORE_CHUNK = 512;
+constexpr int SCORE_GROUPS = SCORE_CHUNK / 64;
+constexpr int SCORE_U = 2;      // 32-deep K steps per unrolled group: 16 x 16 B loads in flight per lane
+constexpr int SCORE_NONE = 0x7fffffff;  // id of "no score above -inf"
+
+struct ScoreStat {
+  float m, s, bv;
+  int bi;
+};
+
+// parts in ascending order: (m, S) as the header states, best by strictly-greater (the earlier part holds the lower ids)
+SLAM_DEVICE void score_merge(ScoreStat& a, float m_max, const float4& p) {
+  if (p.x != -INFINITY) a.s = __fmaf_rn(p.y, expf(p.x - m_max), a.s);
+  if (p.z > a.bv) { a.bv = p.z; a.bi = __float_as_int(p.w); }
+}
+
+// grid (ceil(M / 64), chunks), 256 threads. part[m][chunk] = (m_c, s_c, best value, best id as int bits); xt[m] = the cleaned,
+// masked score of targets[m], written by the one lane of the grid that holds it.
+template <int MT>
+__global__ __launch_bounds__(256) void score_rows_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
+                                                         const int64_t* __restrict__ targets,
+                                                         const uint8_t* __restrict__ colmask, int M, int V, int K, int nch,
+                                                         float4* __restrict__ part, float* __restrict__ xt) {
+  __shared__ float4 grp[SCORE_GROUPS][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = lane >> 4, j = lane & 15;
+  const int m_base = blockIdx.x * 64;
+  const int c0 = blockIdx.y * SCORE_CHUNK;
+  const bf16_t* xrow[MT];
+  bool xv[MT];
+  int tgt[MT][4];  // the target column of row 16 t + 4 q + r, -1: none in [0, V)
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = m_base + 16 * t + j;
+    xv[t] = m < M;
+    xrow[t] = X + (size_t)(xv[t] ? m : 0) * K + 8 * q;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int mr = m_base + 16 * t + 4 * q + r;
+      const long long tv = mr < M ? (long long)targets[mr] : -1;
+      tgt[t][r] = tv >= 0 && tv < V ? (int)tv : -1;
+    }
+  }
+  const uint4 zero = {0u, 0u, 0u, 0u};
+  for (int p = 0; p < 2; ++p) {
+    const int g = 2 * wave + p;
+    const int g0 = c0 + 64 * g;
+    if (g0 >= V) {  // wave-uniform: a group past the vocabulary holds no score
+      grp[g][lane] = make_float4(-INFINITY, 0.f, -INFINITY, __int_as_float(SCORE_NONE));
+      continue;
+    }
+    size_t woff[4];  // element offset of this lane's 8 W values at k = 0
+    unsigned dead = 0;  // bit nt: column g0 + 16 nt + j is past the vocabulary or masked
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      const int n = g0 + 16 * nt + j;
+      const int nr = min(n, V - 1);  // tail columns re-read the last row; their scores count as -inf
+      woff[nt] = (size_t)nr * K + 8 * q;
+      if (n >= V || (colmask && colmask[nr])) dead |= 1u << nt;
+    }
+    f32x4_t acc[MT][4];
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[t][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < K; k0 += 32 * SCORE_U) {
+      uint4 w[SCORE_U][4], a[SCORE_U][MT];
+#pragma unroll
+      for (int u = 0; u < SCORE_U; ++u) {
+        const int k = k0 + 32 * u;
+        const bool kv = k + 8 * q < K;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) w[u][nt] = kv ? *reinterpret_cast<const uint4*>(W + woff[nt] + k) : zero;
+#pragma unroll
+        for (int t = 0; t < MT; ++t) a[u][t] = (kv && xv[t]) ? *reinterpret_cast<const uint4*>(xrow[t] + k) : zero;
+      }
+#pragma unroll
+      for (int u = 0; u < SCORE_U; ++u)
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) acc[t][nt] = mfma16(a[u][t], w[u][nt], acc[t][nt]);
+    }
+    // lane holds acc[t][nt][r] = x[m_base + 16 t + 4 q + r][g0 + 16 nt + j]
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m_base + 16 * t + 4 * q + r;
+        float x[4];
+        float mg = -INFINITY, bv = -INFINITY;
+        int bi = SCORE_NONE;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          const int n = g0 + 16 * nt + j;
+          x[nt] = (dead >> nt) & 1u ? -INFINITY : clean_score(acc[t][nt][r]);
+          mg = fmaxf(mg, x[nt]);
+          if (x[nt] > bv) { bv = x[nt]; bi = n; }
+          if (tgt[t][r] == n) xt[m] = x[nt];
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+          mg = fmaxf(mg, __shfl_xor(mg, o, 64));
+          const float ov = __shfl_xor(bv, o, 64);
+          const int oi = __shfl_xor(bi, o, 64);
+          if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        float s = 0.f;
+        if (mg != -INFINITY) {
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) s += expf(x[nt] - mg);
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (j == 0) grp[g][16 * t + 4 * q + r] = make_float4(mg, s, bv, __int_as_float(bi));
+      }
+  }
+  __syncthreads();
+  const int row = threadIdx.x, m = m_base + row;
+  if (row >= 16 * MT || m >= M) return;
+  float mc = -INFINITY;
+#pragma unroll
+  for (int g = 0; g < SCORE_GROUPS; ++g) mc = fmaxf(mc, grp[g][row].x);
+  ScoreStat a = {mc, 0.f, -INFINITY, SCORE_NONE};
+#pragma unroll
+  for (int g = 0; g < SCORE_GROUPS; ++g) score_merge(a, mc, grp[g][row]);
+  part[(size_t)m * nch + blockIdx.y] = make_float4(a.m, a.s, a.bv, __int_as_float(a.bi));
+}
+
+// one thread per row: the chunks in chunk order. Plain form (new_lens == nullptr): lp[m], argmax[m]. Chunk form (slam_extend_score;
+// row m = b T + t): lp[b T + t + 1] for t + 1 < T, the log-prob when t + 1 < new_lens[b] and 0 else - column 0 is never
+// written; argmax[b T + t] = -1 for t >= new_lens[b].
+__global__ __launch_bounds__(256) void score_finish_kernel(const float4* __restrict__ part, const float* __restrict__ xt,
+                                                           const int64_t* __restrict__ targets, int M, int V, int nch,
+                                                           const int* __restrict__ new_lens, int T, float* __restrict__ lp,
+                                                           int64_t* __restrict__ argmax) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const float4* p = part + (size_t)m * nch;
+  float mm = -INFINITY;
+  for (int c = 0; c < nch; ++c) mm = fmaxf(mm, p[c].x);
+  ScoreStat a = {mm, 0.f, -INFINITY, SCORE_NONE};
+  for (int c = 0; c < nch; ++c) score_merge(a, mm, p[c]);
+  const long long tok = targets[m];
+  float r = 0.f;
+  if (tok >= 0 && tok < V) r = mm == -INFINITY ? -INFINITY : xt[m] - (mm + logf(a.s));
+  const long long best = a.bv == -INFINITY ? -1 : (long long)a.bi;
+  if (!new_lens) {
+    lp[m] = r;
+    if (argmax) argmax[m] = best;
+    return;
+  }
+  const int b = m / T, t = m % T;
+  const int nl = min(max(new_lens[b], 0), T);
+  if (t + 1 < T) lp[m + 1] = t + 1 < nl ? r : 0.f;
+  if (argmax) argmax[m] = t < nl ? best : -1;
+}
+
+// targets of the chunk's rows: row b T + t scores ids[b][t + 1] when that is a real token of the chunk, nothing (-100) else
+__global__ __launch_bounds__(256) void extend_targets_kernel(const int64_t* __restrict__ ids, const int* __restrict__ new_lens,
+                                                             int64_t* __restrict__ tg, int B, int T) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * T) return;
+  const int b = i / T, t = i % T;
+  const int nl = min(max(new_lens[b], 0), T);
+  tg[i] = t + 1 < nl ? ids[i + 1] : -100;
+}
+
 }  // namespace
 
 namespace slam {
@@ -1225,6 +1403,43 @@ int token_logprobs(const float* logits, int B, int vocab, const int64_t* tokens,
     logprob_chunk_kernel<<<dim3(P.nch, B), SP_THREADS, 0, st>>>(logits, finished, P, w);
     logprob_finish_kernel<false><<<B, 64, 0, st>>>(logits, tokens, done, finished, out, P, w);
   }
+  return (int)hipGetLastError();
+}
+
+static int score_chunks(int V) { return (V + SCORE_CHUNK - 1) / SCORE_CHUNK; }
+
+size_t score_rows_workspace_bytes(int M, int V) {
+  if (M <= 0 || V <= 0 || M > SCORE_MAX_M || V > SCORE_MAX_V) return 0;
+  return (size_t)M * score_chunks(V) * sizeof(float4) + (size_t)M * sizeof(float);
+}
+
+int score_rows(const bf16_t* X, const bf16_t* W, const int64_t* targets, const uint8_t* colmask, int M, int V, int K,
+               const int* new_lens, int T, float* lp, int64_t* argmax, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!X || !W || !targets || !lp || !ws || M <= 0 || M > SCORE_MAX_M || V <= 0 || V > SCORE_MAX_V || K <= 0 || (K & 7)) return -1;
+  if (((uintptr_t)X | (uintptr_t)W | (uintptr_t)ws) & 15) return -1;
+  if (((uintptr_t)targets | (uintptr_t)argmax) & 7 || ((uintptr_t)lp & 3)) return -1;
+  if (ws_bytes < score_rows_workspace_bytes(M, V)) return -1;
+  if (new_lens && (T <= 0 || M % T)) return -1;
+  const int nch = score_chunks(V);
+  float4* part = reinterpret_cast<float4*>(ws);
+  float* xt = reinterpret_cast<float*>(part + (size_t)M * nch);
+  const dim3 grid(nblk((size_t)M, 64), nch);
+  const int mt = ((M < 64 ? M : 64) + 15) / 16;
+#define SR_CASE(MT) \
+  case MT: score_rows_kernel<MT><<<grid, 256, 0, st>>>(X, W, targets, colmask, M, V, K, nch, part, xt); break;
+  switch (mt) {
+    SR_CASE(1)
+    SR_CASE(2)
+    SR_CASE(3)
+    default: score_rows_kernel<4><<<grid, 256, 0, st>>>(X, W, targets, colmask, M, V, K, nch, part, xt); break;
+  }
+#undef SR_CASE
+  score_finish_kernel<<<nblk((size_t)M, 256), 256, 0, st>>>(part, xt, targets, M, V, nch, new_lens, T, lp, argmax);
+  return (int)hipGetLastError();
+}
+
+int extend_targets(const int64_t* ids, const int* new_lens, int64_t* tg, int B, int T, hipStream_t st) {
+  extend_targets_kernel<<<nblk((size_t)B * T, 256), 256, 0, st>>>(ids, new_lens, tg, B, T);
   return (int)hipGetLastError();
 }
 

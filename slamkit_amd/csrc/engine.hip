@@ -1225,9 +1225,12 @@ int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_
   return SLAM_OK;
 }
 
-int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
-                float* logits_out, slam_stream_t stream) {
-  if (!h || !ids || !new_lens || !lens || !logits_out || B <= 0 || T <= 0) return SLAM_EINVAL;
+namespace {
+// slam_extend and slam_extend_score: one body. score = false is slam_extend, launch for launch; score = true adds, between the
+// layer loop and the last-token head, the final norm of all B T rows and the fused head + row statistics.
+int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                  float* logits_out, bool score, float* lp_out, int64_t* argmax_out, slam_stream_t stream) {
+  if (!h || !ids || !new_lens || !lens || !logits_out || B <= 0 || T <= 0 || (score && !lp_out)) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch != 0) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
@@ -1237,6 +1240,8 @@ int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int3
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_extend needs a slam_prefill into the bound cache first");
   if (B != h->kv_B) return h->fail(SLAM_EINVAL, "extend batch differs from the decode batch");
   const SlamModelDesc& d = h->d;
+  if (score && score_rows_workspace_bytes(B * T, d.vocab) > (size_t)h->max_tokens * h->vpad * sizeof(bf16_t))
+    return h->fail(SLAM_ENOMEM, "chunk partials exceed the logits buffer");
   hipStream_t st = (hipStream_t)stream;
   const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads, hd = d.head_dim;
   const int M = B * T;
@@ -1274,6 +1279,16 @@ int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int3
     CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
     CK(decode_proj(h, a.act, P + o.wd, h->hs[l + 1], nullptr, nullptr, a.hmid, M, H, I, st));
   }
+  if (score) {
+    // every chunk position: final norm of the B T rows, then the head fused with the row statistics. Scratch behind the layer
+    // loop: the targets (int64 [B T]) in the backward-only dqkv buffer, chunk partials and target scores at the start of the
+    // logits buffer (the attention partials are dead; the last-token logits below overwrite it after these launches)
+    int64_t* tg = (int64_t*)h->dqkv;
+    CK(extend_targets(ids, new_lens, tg, B, T, st));
+    CK(rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, M, H, d.rms_eps, st));
+    CK(score_rows(h->hf, P + h->off_head, tg, h->logit_mask, M, d.vocab, H, new_lens, T, lp_out, argmax_out, h->logits,
+                  part_bytes, st));
+  }
   // each row's last real token: gather, final norm, one fp32 head launch over B rows; inert rows keep their logits and lens
   CK(gather_last_rows(h->hs[L], h->dx, new_lens, B, T, H, st));
   CK(rmsnorm_fwd(h->dx, P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
@@ -1283,6 +1298,17 @@ int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int3
   if (h->kv_hi == h->kv_T) h->kv_T += T;  // no decode step since the prefill: slam_kv_repeat stays legal
   h->kv_hi += T;
   return SLAM_OK;
+}
+}  // namespace
+
+int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                float* logits_out, slam_stream_t stream) {
+  return extend_common(h, ids, new_lens, lens, B, T, logits_out, false, nullptr, nullptr, stream);
+}
+
+int slam_extend_score(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                      float* logits_out, float* lp_out, int64_t* argmax_out, slam_stream_t stream) {
+  return extend_common(h, ids, new_lens, lens, B, T, logits_out, true, lp_out, argmax_out, stream);
 }
 
 int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_bucket_cb cb, void* user,
@@ -2175,6 +2201,17 @@ int slam_op_gemm_skinny(const void* X, const void* W, void* Y, int y_f32, const 
                         float* ws, size_t ws_bytes, slam_stream_t s) {
   return gemm_skinny((const bf16_t*)X, (const bf16_t*)W, y_f32 ? nullptr : (bf16_t*)Y, y_f32 ? (float*)Y : nullptr,
                      (const bf16_t*)bias, (const bf16_t*)resid, M, N, K, ws, ws_bytes, (hipStream_t)s);
+}
+size_t slam_op_score_rows_workspace(int M, int V) { return score_rows_workspace_bytes(M, V); }
+int slam_op_score_rows(const void* X, const void* W, const int64_t* targets, const uint8_t* colmask, float* lp, int64_t* argmax,
+                       int M, int V, int K, void* ws, size_t ws_bytes, slam_stream_t s) {
+  if (!X || !W || !targets || !lp || !ws || M <= 0 || M > SCORE_MAX_M || V <= 0 || V > SCORE_MAX_V || K <= 0 || (K & 7))
+    return SLAM_EINVAL;
+  if ((((uintptr_t)X | (uintptr_t)W | (uintptr_t)ws) & 15) || (((uintptr_t)targets | (uintptr_t)argmax) & 7) || ((uintptr_t)lp & 3))
+    return SLAM_EINVAL;
+  if (ws_bytes < score_rows_workspace_bytes(M, V)) return SLAM_EINVAL;
+  return score_rows((const bf16_t*)X, (const bf16_t*)W, targets, colmask, M, V, K, nullptr, 0, lp, argmax, ws, ws_bytes,
+                    (hipStream_t)s);
 }
 namespace {
 // slam_op_attn_decode workspace: int64 positions [B], cos / sin / pre-scaled cos / sin tables [B][hd/2], split partials

@@ -307,5 +307,17 @@ int kv_repeat(bf16_t* kv, int* lens, float* logits, int B, int n, int bmax, int 
 size_t token_logprobs_workspace_bytes(int B, int vocab);  // host only
 int token_logprobs(const float* logits, int B, int vocab, const int64_t* tokens, const uint8_t* done, uint8_t* finished,
                    float* out, int64_t out_stride, int column, void* ws, size_t ws_bytes, hipStream_t st);
+// LM head fused with the row statistics (include/slam_engine.h: slam_op_score_rows): for row m of X (bf16 [M][K]) against the
+// head W (bf16 [V][K]) on v_mfma_f32_16x16x32_bf16, lp = log-softmax at targets[m] and argmax = the lowest id of the largest
+// score, from fp32 accumulators that are never stored. colmask: nullable, >= V bytes, non-zero = the column counts as -inf.
+// new_lens == nullptr: lp [M], argmax [M] (nullable). new_lens given (slam_extend_score, M = B T): lp[b][t + 1] and
+// argmax[b][t] by that call's layout. ws: score_rows_workspace_bytes(M, V), 16-byte aligned: chunk partials and target scores.
+constexpr int SCORE_MAX_M = 0x7fffffc0 / 64;
+constexpr int SCORE_MAX_V = 65535 * 512;  // one grid row of blocks per chunk
+size_t score_rows_workspace_bytes(int M, int V);       // host only
+int score_rows(const bf16_t* X, const bf16_t* W, const int64_t* targets, const uint8_t* colmask, int M, int V, int K,
+               const int* new_lens, int T, float* lp, int64_t* argmax, void* ws, size_t ws_bytes, hipStream_t st);
+// tg[b T + t] = ids[b][t + 1] when t + 1 < new_lens[b], -100 else
+int extend_targets(const int64_t* ids, const int* new_lens, int64_t* tg, int B, int T, hipStream_t st);
 
 }  // namespace slam

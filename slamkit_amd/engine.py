@@ -92,6 +92,7 @@ def load_library(path: Optional[str] = None):
         "slam_sample_tokens": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
         "slam_kv_repeat": (C.c_int, [vp, i32, vp, vp, vp]),
         "slam_extend": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
+        "slam_extend_score": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
         "slam_token_logprobs": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, sz, vp]),
         "slam_bucket_stream": (vp, [vp]),
@@ -139,6 +140,8 @@ def load_library(path: Optional[str] = None):
         "slam_op_gemm_tn_image": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
         "slam_op_gemm_skinny_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
         "slam_op_gemm_skinny": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
+        "slam_op_score_rows_workspace": (sz, [C.c_int, C.c_int]),
+        "slam_op_score_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
         "slam_op_attn_decode_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "slam_op_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           f32, vp]),
@@ -233,6 +236,32 @@ def token_logprobs(logits, tokens, out, column: int, ws, done=None, finished=Non
                                            stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_token_logprobs failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+SCORE_CHUNK = 512  # SLAM_SCORE_CHUNK: vocabulary columns per chunk of slam_op_score_rows
+
+
+def score_rows_workspace_bytes(M: int, vocab: int) -> int:
+    """Bytes of device workspace slam_op_score_rows needs (host arithmetic; 0 for invalid sizes)."""
+    return int(load_library().slam_op_score_rows_workspace(int(M), int(vocab)))
+
+
+def score_rows(X, W, targets, lp, argmax=None, colmask=None, ws=None, stream: Optional[int] = None):
+    """slam_op_score_rows: the LM head fused with the row statistics. X bf16 [M, K], W bf16 [V, K], targets int64 [M] (-100: no
+    target): lp[m] (fp32 [M]) = the log-softmax of row m's fp32 scores at targets[m], argmax[m] (int64 [M], optional) = the
+    lowest id of the largest score. colmask uint8 [>= V]: non-zero = the column counts as -inf. ws: a uint8 tensor of
+    score_rows_workspace_bytes(M, V) (allocated here when None). Only enqueues work; returns ws."""
+    import torch
+    M, K = X.shape
+    V = W.shape[0]
+    if ws is None:
+        ws = torch.empty(max(score_rows_workspace_bytes(M, V), 16), dtype=torch.uint8, device=X.device)
+    rc = load_library().slam_op_score_rows(_ptr(X), _ptr(W), _ptr(targets), _ptr(colmask), _ptr(lp), _ptr(argmax), M, V, K,
+                                          _ptr(ws), ws.numel() * ws.element_size(),
+                                          stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_op_score_rows failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+    return ws
 
 
 def unpadded_scratch_bytes(B: int, T: int) -> int:
@@ -430,6 +459,16 @@ class Engine:
         with new_lens 0 keep theirs), lens += new_lens on the device."""
         self._ck(self.lib.slam_extend(self.h, _ptr(ids), _ptr(new_lens), _ptr(lens), B, T, _ptr(logits_out),
                                       stream if stream is not None else current_stream_ptr()))
+
+    def extend_score(self, ids, new_lens, lens, B: int, T: int, logits_out, lp_out, argmax_out=None,
+                     stream: Optional[int] = None):
+        """slam_extend_score: slam_extend (same cache, lens and logits_out bits) that also scores the chunk. lp_out fp32 [B, T]:
+        column t, 1 <= t < new_lens[b], = the log-prob of ids[b, t] given the cache and ids[b, :t]; columns at or beyond
+        max(1, new_lens[b]) = 0; column 0 is left to the caller (token_logprobs on the logits the rows held before the call).
+        argmax_out int64 [B, T], optional: the greedy next token after position t (t < new_lens[b]), else -1."""
+        self._ck(self.lib.slam_extend_score(self.h, _ptr(ids), _ptr(new_lens), _ptr(lens), B, T, _ptr(logits_out),
+                                            _ptr(lp_out), _ptr(argmax_out),
+                                            stream if stream is not None else current_stream_ptr()))
 
     def set_logit_mask(self, mask_u8=None):
         """mask_u8: uint8 device tensor of padded_vocab() bytes (non-zero = column outside the softmax) or None."""

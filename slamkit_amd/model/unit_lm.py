@@ -1130,6 +1130,128 @@ class UnitLM(TokenLM):
         seq = torch.cat([seq_in.repeat_interleave(nret, 0) if nret > 1 else seq_in, new], 1)
         return GenerateOutput(seq, lp[0][:, :n].contiguous()) if lp is not None else seq
 
+    @torch.no_grad()
+    def score_continuations(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, continuations=None,
+                            continuation_lengths=None, num_per_prompt: int = 1, score_chunk: Optional[int] = None,
+                            prefill_chunk: Optional[int] = None, return_argmax: bool = False,
+                            ignore_tokens: Optional[List[int]] = None):
+        """This model's log-probs of given continuations of the prompts, through the KV cache: the scoring half of
+        generate(num_return_sequences=n, return_logprobs=True). input_ids [B, T_in] (+ attention_mask, any padding side);
+        continuations int64 [B n, T_c], right-padded, rows b n .. b n + n - 1 continuing prompt b (generate's order:
+        `out[:, T_in:]` feeds straight in); continuation_lengths [B n] (0 .. T_c real tokens per row; default T_c; 0 is legal).
+        Returns fp32 [B n, T_c]: the log-softmax (fp32 scores, never rounded to bf16) of every continuation token given the
+        prompt and the tokens before it, 0.0 at pads. return_argmax=True returns (logprobs, argmax): argmax int64 [B n, T_c], the
+        model's greedy choice FOR continuation position t (position t is accepted by a verifier iff it equals argmax[:, t]),
+        -1 at pads.
+
+        The prompts are compacted and prefilled ONCE (in chunks of `prefill_chunk` columns if given), the cache fanned out
+        to B n rows (slam_kv_repeat), and the continuations appended `score_chunk` columns at a time by slam_extend_score
+        (None = one block): a block's first column is slam_token_logprobs on the logits the rows held before it (the prefill's,
+        then the previous block's last-token logits), every other column comes from the fused head. The workspace is
+        max(B min(T, prefill_chunk), B n score_chunk, 2 B n) tokens, and no [B n, T + T_c] batch is formed. Inside the loop
+        the engine calls follow each other with no torch op between them (every block's operands are built before it).
+        `ignore_tokens` sets the logit mask (those columns count as -inf) for the call and clears it afterwards. Known
+        exception to the no-torch-op rule: with `ignore_tokens`, one in-place fill of those columns of the last-token logits
+        follows each block, because slam_token_logprobs reads raw logits and takes no mask."""
+        n = num_per_prompt
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"num_per_prompt must be an int >= 1 (got {n!r})")
+        for name, v in (("score_chunk", score_chunk), ("prefill_chunk", prefill_chunk)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+                raise ValueError(f"{name} must be None or an int >= 1 (got {v!r})")
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("score_continuations needs input_ids [B, T]")
+        if continuations is None or continuations.dim() != 2:
+            raise ValueError("score_continuations needs continuations [B * num_per_prompt, T_c]")
+        B, BN, Tc = input_ids.shape[0], input_ids.shape[0] * n, continuations.shape[1]
+        if continuations.shape[0] != BN:
+            raise ValueError(f"continuations has {continuations.shape[0]} rows; {B} prompts x num_per_prompt {n} need {BN}")
+        if continuation_lengths is not None and tuple(continuation_lengths.shape) != (BN,):
+            raise ValueError(f"continuation_lengths must have shape [{BN}], got {list(continuation_lengths.shape)}")
+        if self.config.is_opt:
+            raise ValueError("score_continuations is not implemented for OPT models (the engine's KV cache covers Qwen2 only)")
+        dev = self.device
+        seq_in = input_ids.to(dev, torch.int64)
+        cont = continuations.to(dev, torch.int64)
+        clens = (torch.full((BN,), Tc, dtype=torch.int32, device=dev) if continuation_lengths is None
+                 else continuation_lengths.to(dev, torch.int32))
+        if continuation_lengths is not None and BN and (int(clens.min()) < 0 or int(clens.max()) > Tc):
+            raise ValueError(f"continuation_lengths must lie in [0, {Tc}]")
+        if Tc == 0:
+            z = torch.zeros(BN, 0, dtype=torch.float32, device=dev)
+            return (z, torch.zeros(BN, 0, dtype=torch.int64, device=dev)) if return_argmax else z
+        mask = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones_like(seq_in, dtype=torch.bool)
+        order = torch.sort((~mask).to(torch.int8), dim=1, stable=True).indices  # real tokens to the left, as generate does
+        lens = mask.sum(1).to(torch.int32)
+        T = int(lens.max())
+        if int(lens.min()) < 1:
+            raise ValueError("every prompt row needs at least one unmasked token")
+        pad = self.config.pad_token_id if self.config.pad_token_id is not None else 0
+        ids = seq_in.gather(1, order)[:, :T]
+        ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, int(pad))).contiguous()
+        if T + Tc > self.config.max_tokens:
+            raise ValueError(f"prompt length {T} + continuation length {Tc} exceeds max_tokens {self.config.max_tokens}")
+        C = Tc if score_chunk is None else min(score_chunk, Tc)
+        cap = -(-(T + Tc) // 64) * 64
+        self._ensure_workspace(max(B * (T if prefill_chunk is None else min(T, prefill_chunk)), BN * C, 2 * BN))
+        nbytes = self.engine.kv_cache_bytes(BN, cap)
+        raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        off = (-raw.data_ptr()) % 256
+        self.engine.bind_kv_cache(raw[off:off + nbytes], BN, cap)
+        V = self.config.vocab_size
+        logits = torch.empty(BN, V, dtype=torch.float32, device=dev)
+        if n > 1:
+            lens = torch.cat([lens, torch.zeros(BN - B, dtype=torch.int32, device=dev)])
+        # every block's operands, built before the first engine call: ids, real tokens per row, the first column's token and its
+        # "row has no token here" flag (slam_token_logprobs writes 0.0 for it), the block's outputs
+        valid = torch.arange(Tc, device=dev)[None] < clens[:, None]
+        cont = torch.where(valid, cont, torch.full_like(cont, int(pad)))
+        blocks = []
+        for c0 in range(0, Tc, C):
+            w = min(C, Tc - c0)
+            blk = cont[:, c0:c0 + w].contiguous()
+            blocks.append((w, blk, (clens - c0).clamp(min=0, max=w).contiguous(), blk[:, 0].contiguous(),
+                           (clens <= c0).to(torch.uint8).contiguous(), torch.empty(BN, w, dtype=torch.float32, device=dev),
+                           torch.empty(BN, w, dtype=torch.int64, device=dev) if return_argmax else None))
+        lpws = torch.empty(E.token_logprobs_workspace_bytes(BN, V), dtype=torch.uint8, device=dev)
+        first = None
+        if return_argmax:  # position 0's greedy choice: slam_sample_tokens (greedy) on the prefill logits
+            first = torch.empty(BN, dtype=torch.int64, device=dev)
+            gdesc = E.SlamSampleDesc(do_sample=0, top_k=1, temperature=1.0, top_p=1.0, seed=0, step=0, pad_id=int(pad), n_eos=0)
+            sws = torch.empty(E.sample_workspace_bytes(BN, V, 1), dtype=torch.uint8, device=dev)
+        lmask = ign = None
+        if ignore_tokens is not None:
+            ign = torch.as_tensor(list(ignore_tokens), dtype=torch.long, device=dev)
+            lmask = torch.zeros(self.engine.padded_vocab(), dtype=torch.uint8, device=dev)
+            lmask[ign] = 1
+            self.engine.set_logit_mask(lmask)
+        self._hold = (ids, lens, blocks)
+        try:
+            self._prefill(ids, lens, B, T, logits, prefill_chunk)
+            if n > 1:
+                self.engine.kv_repeat(n, lens, logits)
+            if ign is not None:
+                logits.index_fill_(1, ign, float("-inf"))
+            if first is not None:
+                E.sample_tokens(logits, gdesc, first, sws, lmask)
+            for w, blk, nl, tok0, inert, lp_b, am_b in blocks:
+                # `inert` is the kernel's in/out `finished` array: read (1 = write 0.0 for the row), then overwritten with
+                # `done` (none: zeros). Each block owns its tensor and it is used exactly once.
+                E.token_logprobs(logits, tok0, lp_b, column=0, ws=lpws, done=None, finished=inert)
+                self.engine.extend_score(blk, nl, lens, BN, w, logits, lp_b, am_b)
+                if ign is not None:
+                    logits.index_fill_(1, ign, float("-inf"))
+        finally:
+            if lmask is not None:
+                torch.cuda.current_stream(dev).synchronize()  # the kernels read the mask: keep it alive until done
+                self.engine.set_logit_mask(None)
+        lp = torch.cat([b[5] for b in blocks], 1) if len(blocks) > 1 else blocks[0][5]
+        if not return_argmax:
+            return lp
+        # argmax_out[:, t] is the choice AFTER position t: shift by one behind the prefill's choice
+        am = torch.cat([first[:, None]] + [b[6] for b in blocks], 1)[:, :Tc]
+        return lp, torch.where(valid, am, torch.full_like(am, -1))
+
     def _prefill(self, ids, lens, B, T, logits, chunk=None):
         """The prompts into the cache and each row's last-token logits into logits[:B]: slam_prefill over all T columns, or
         (chunk = C) over the first min(T, C) and slam_extend over every further block of C. lens (first B entries: the prompt
