@@ -34,7 +34,7 @@ extern "C" {
 typedef struct SlamEngine SlamEngine;
 typedef void* slam_stream_t; /* hipStream_t */
 
-/* Qwen2-shaped decoder description (UnitLMConfig.base_config, unit_lm.py:32-79; Slam-358M values
+/* Qwen2- / Qwen3-shaped decoder description (UnitLMConfig.base_config, unit_lm.py:32-79; Slam-358M values
  * from config/model/slam.yaml + Qwen2.5-0.5B). */
 typedef struct SlamModelDesc {
   int32_t n_layers;      /* 24  */
@@ -51,7 +51,7 @@ typedef struct SlamModelDesc {
 
 typedef struct SlamTensorInfo {
   char name[64];      /* "embed", "layers.3.wqkv", "layers.3.bqkv", "layers.3.wo", "layers.3.ln1",
-                         "layers.3.ln2", "layers.3.wgu", "layers.3.wd", "norm".
+                         "layers.3.ln2", "layers.3.wgu", "layers.3.wd", "norm" (Qwen3: "layers.3.q_norm", "layers.3.k_norm").
                          wqkv rows = q | k | v; wgu rows = blocks of 32 gate_proj rows followed by the
                          matching 32 up_proj rows (row 64b+j = gate[32b+j], row 64b+32+j = up[32b+j]) */
   int64_t offset;     /* element offset in the flat parameter / gradient buffers */
@@ -76,11 +76,18 @@ int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out); /* UnitLM._
  *   layers.N.{ln1, ln1_b [H], wqkv [3 H][H], bqkv [3 H], wo [H][H], bo [H], ln2, ln2_b [H], w1 [F][H], b1 [F], w2 [H][F], b2 [H]},
  *   norm, norm_b [H].
  * Positions are position_ids, else 0 .. T-1 per row; both table indices are clamped to the tables (a memory guard: callers
- * check their ranges). KV-cached generation (slam_prefill / slam_decode_step / slam_extend) is not implemented for OPT: SLAM_EINVAL. */
+ * check their ranges). KV-cached generation (slam_prefill / slam_decode_step / slam_extend) is not implemented for OPT: SLAM_EINVAL.
+ * Arch 3 = Qwen3: the Qwen2 body (RMSNorm, RoPE, grouped-query attention, SwiGLU, the Qwen2 limits: hidden % 8 and <= 4096,
+ * intermediate a multiple of 32, head_dim 64 or 128, n_heads a multiple of n_kv_heads with at most 8 query heads per KV head;
+ * n_positions ignored) with no q / k / v bias and an RMSNorm over head_dim on every q and every k head before RoPE
+ * (slam_op_qknorm_rope_fwd below). n_heads * head_dim need not equal hidden. Its layer tensors, in layout order:
+ *   layers.N.{ln1 [H], wqkv [(nH + 2 nKV) hd][H], q_norm [hd], k_norm [hd], wo [H][nH hd], ln2 [H], wgu [2 I][H], wd [H][I]}
+ * - there is no bqkv. Everything the Qwen2 family offers (training, "recompute", the untied head, KV-cached generation and
+ * scoring) holds for arch 3; "Qwen2 only" below means arch 0 and 3. Arch 2 is not a family: SLAM_EINVAL. */
 int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, SlamEngine** out);
-/* The same with model flags (slam_engine_create / slam_engine_create_arch mean flags = 0). Arch 0 takes hidden <= 4096
+/* The same with model flags (slam_engine_create / slam_engine_create_arch mean flags = 0). Arch 0 and 3 take hidden <= 4096
  * (rows above 2048 run the two-waves-per-row RMSNorm kernels), arch 1 hidden <= 2048.
- * SLAM_MODEL_UNTIED_HEAD (arch 0 only; Qwen2.5-7B): the LM head is a tensor of its own, "lm_head" [Vp][H], laid out AFTER
+ * SLAM_MODEL_UNTIED_HEAD (arch 0 and 3; Qwen2.5-7B): the LM head is a tensor of its own, "lm_head" [Vp][H], laid out AFTER
  * "norm" so that every other tensor keeps the offset it has in the tied layout. Its pad rows [vocab, Vp) are zero and stay
  * zero, as the embedding's do. Forward, prefill and decode read the head GEMM's weight there; backward writes
  * d lm_head = dlogits^T hf as that tensor's final value, and the embedding gradient is the gather side alone (rows of ids
@@ -507,7 +514,8 @@ int slam_cast_params(SlamEngine* h, const float* master_f32, slam_stream_t strea
  * "recompute" = 0 | 1 | 2 (default 0; anything else is SLAM_EINVAL, "out of range"): activation recomputation in backward -
  * gradient checkpointing (the reference's `supports_gradient_checkpointing`, HF TrainingArguments.gradient_checkpointing).
  * Results are bit-identical at every level: backward re-runs the forward's own launches on the forward's own inputs.
- *   0  every layer keeps hmid, x1, x2, qkv, o, gu, act, rstd1, rstd2, lse (OPT: + mu1, mu2) from forward to backward.
+ *   0  every layer keeps hmid, x1, x2, qkv, o, gu, act, rstd1, rstd2, lse (OPT: + mu1, mu2; Qwen3: + the raw q|k columns and
+ *      the heads' rstd) from forward to backward.
  *   1  selective: every layer keeps hmid, qkv, o, gu, the row statistics and lse; x1, x2 and act live in min(n_layers, 3)
  *      shared slots (layer l uses slot l mod 3) and slam_backward rebuilds them before layer l's weight gradients read them:
  *      x1 from the residual stream, x2 from hmid, act from gu (with "fuse_swiglu" the fused gate|up launch is re-run, since its
@@ -658,6 +666,29 @@ int slam_op_gemm_nt_drelu(const void* dY, const void* Wt, void* dact, const void
 int slam_op_relu_bwd(void* d, const void* act, int64_t n, slam_stream_t s);
 int slam_op_rope(void* qkv, int ld, int M, int T, int n_rot_heads, int head_dim, const int64_t* position_ids, float theta,
                  int backward, float* cos_sin_ws /* 2*M*(head_dim/2) floats */, slam_stream_t s);
+/* Qwen3's per-head q / k RMSNorm (arch 3), on qkv [M][(nH + 2 nKV) head_dim] (head_dim 64 or 128). For every token and every q
+ * or k head, x = the head as the projection wrote it (bf16): rstd = rsqrt(mean_d(x^2) + eps), y = x rstd w with w = w_q for the
+ * nH query heads and w_k for the nKV key heads (bf16 [head_dim] each, shared by the heads).
+ * slam_op_qknorm_rope_fwd: y is rotated (rotate-half RoPE, tables built from position_ids - NULL: m % T - and theta into table_ws,
+ *   4 * M * (head_dim / 2) floats; the query heads also take head_dim^-0.5 * log2(e)) and stored in place, all in fp32 with ONE
+ *   rounding to bf16; the v columns are not touched. raw_out (bf16 [M][(nH + nKV) head_dim], nullable) receives the q|k input
+ *   bits, rstd_out (fp32 [M][nH + nKV], nullable) the statistics: what the backward needs.
+ * slam_op_qknorm_bwd: in place on the q|k columns of dqkv, which hold dy = the gradient of y (slam_op_attn_bwd_rope's output):
+ *   g = dy w, dx = rstd (g - xhat mean_d(g xhat)), xhat = raw rstd; dw_q [head_dim] = the sum over tokens and query heads of
+ *   dy xhat, dw_k likewise (fp32, stored). Per-block partial slabs in ws (slam_op_qknorm_bwd_workspace bytes) are added in block
+ *   order: no floating-point atomics, the same bits every run.
+ * slam_op_qknorm_rows_f32: the decode-time form - the q and k heads of fp32 rows [B][(nH + 2 nKV) head_dim] are replaced by y
+ *   (fp32, no rounding to bf16); slam_op_attn_decode then rotates and rounds once, with bias = NULL.
+ * SLAM_EINVAL before any launch: a NULL pointer (other than the nullable ones), M / B / T / nH / nKV <= 0, head_dim not 64 or 128,
+ * or M (nH + nKV) head_dim / 8 >= 2^31 - 1024 (the kernels index heads in 32 bits). */
+int slam_op_qknorm_rope_fwd(void* qkv, const void* w_q, const void* w_k, const int64_t* position_ids, float theta, float eps,
+                            int M, int T, int nH, int nKV, int head_dim, void* raw_out, float* rstd_out, float* table_ws,
+                            slam_stream_t s);
+size_t slam_op_qknorm_bwd_workspace(int M, int nH, int nKV, int head_dim);
+int slam_op_qknorm_bwd(void* dqkv, const void* raw, const float* rstd, const void* w_q, const void* w_k, float* dw_q, float* dw_k,
+                       float* ws, int M, int nH, int nKV, int head_dim, slam_stream_t s);
+int slam_op_qknorm_rows_f32(float* qkv, const void* w_q, const void* w_k, float eps, int B, int nH, int nKV, int head_dim,
+                            slam_stream_t s);
 int slam_op_swiglu_fwd(const void* gu, void* act, int M, int I, slam_stream_t s);
 int slam_op_swiglu_bwd(void* gu_inout, const void* dact, int M, int I, slam_stream_t s);
 /* attention ops: the QUERY columns of qkv are expected PRE-SCALED by head_dim^-0.5 * log2(e) (the engine's QKV projection

@@ -1074,6 +1074,181 @@ __global__ __launch_bounds__(256) void scale_bf16_kernel(bf16_t* __restrict__ x,
   *p = pack_bf16x8(f);
 }
 
+// ------------------------------------------------------------------------------------------
+// Qwen3: per-head RMSNorm of the q and k heads (one learned weight [HD] for all q heads, one for all k heads), before RoPE.
+// All three kernels number the q|k heads of the batch flat, head g = m * (nH + nKV) + h, and give each head to HD / 8
+// consecutive lanes, 8 dims (16 bytes of bf16) per lane: a wave covers 64 / (HD / 8) consecutive heads, every lane group is
+// whole, and the head statistics are an xor butterfly over the group's lanes. The rotate-half partner of dims d0 .. d0 + 7
+// lives in lane (sub ^ HD / 16) of the same group.
+//
+// Forward: y = x rstd w in fp32, rotated with the engine's tables (csq / snq for the query heads: the pre-scale), ONE rounding
+// at the in-place store. raw / rstd_out (nullable): the input bits [M][(nH + nKV) HD] and rstd [M][nH + nKV] for backward.
+// Algorithmic traffic: 2 B/element read, 2 (+ 2 with the saved copy) written; the tables are [M][HD / 2] fp32, read once per head.
+template <int HD>
+__global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(bf16_t* __restrict__ qkv, int ld, uint32_t total, int nH, int nQK,
+                                                              const bf16_t* __restrict__ wq, const bf16_t* __restrict__ wk,
+                                                              const float* __restrict__ cs, const float* __restrict__ sn,
+                                                              const float* __restrict__ csq, const float* __restrict__ snq,
+                                                              float eps, bf16_t* __restrict__ raw, float* __restrict__ rstd_out) {
+  constexpr int LG = HD / 8, half = HD / 2;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;  // the launcher keeps total * LG below 2^31: 32-bit index arithmetic
+  const uint32_t g = t / LG;
+  const int d0 = (int)(t % LG) * 8;
+  const bool ok = g < total;  // the same for every lane of a group; nobody leaves before the shuffles
+  const uint32_t m = ok ? g / (uint32_t)nQK : 0;
+  const int h = ok ? (int)(g - m * (uint32_t)nQK) : 0;
+  const bool isq = h < nH;
+  bf16_t* p = qkv + (size_t)m * ld + (size_t)h * HD + d0;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (ok) v = *reinterpret_cast<const uint4*>(p);
+  float x[8], w[8], c[8], s[8];
+  unpack_bf16x8(v, x);
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ss += x[j] * x[j];
+#pragma unroll
+  for (int o = LG / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  const float r = rsqrtf(ss / (float)HD + eps);
+  unpack_bf16x8(*reinterpret_cast<const uint4*>((isq ? wq : wk) + d0), w);
+  const bool lo = d0 < half;
+  const size_t tb = (size_t)m * half + (lo ? d0 : d0 - half);
+  const float4* cp = reinterpret_cast<const float4*>((isq ? csq : cs) + tb);
+  const float4* sp = reinterpret_cast<const float4*>((isq ? snq : sn) + tb);
+  *reinterpret_cast<float4*>(c) = cp[0]; *reinterpret_cast<float4*>(c + 4) = cp[1];
+  *reinterpret_cast<float4*>(s) = sp[0]; *reinterpret_cast<float4*>(s + 4) = sp[1];
+  float y[8], o8[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) y[j] = x[j] * r * w[j];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float pr = __shfl_xor(y[j], LG / 2, 64);  // the rotate-half partner dim
+    o8[j] = lo ? y[j] * c[j] - pr * s[j] : y[j] * c[j] + pr * s[j];
+  }
+  if (!ok) return;
+  *reinterpret_cast<uint4*>(p) = pack_bf16x8(o8);
+  if (raw) *reinterpret_cast<uint4*>(raw + (size_t)g * HD + d0) = v;
+  if (rstd_out && d0 == 0) rstd_out[g] = r;
+}
+
+// Backward, in place on the q|k columns of d(qkv) (dy = the gradient of the normed, un-rotated head, as attn_bwd leaves it):
+// g = dy w, dx = rstd (g - xhat mean_d(g xhat)), xhat = raw rstd. dw_q / dw_k partials: every lane sums dy xhat of its 8 dims
+// over the heads it meets (wave `wave` of block b takes the 64 / LG-head chunks 4 b + wave, + 4 gridDim, ..), the lane groups
+// of a wave are combined by an xor butterfly, the four waves through LDS in wave order: part_q / part_k [gridDim][HD],
+// finished by colsum_finish_many in block order - the same bits every run. Traffic: 4 B/element read, 2 written.
+template <int HD>
+__global__ __launch_bounds__(256) void qknorm_bwd_kernel(bf16_t* __restrict__ dqkv, int ld, const bf16_t* __restrict__ raw,
+                                                         const float* __restrict__ rstd, const bf16_t* __restrict__ wq,
+                                                         const bf16_t* __restrict__ wk, uint32_t total, int nH, int nQK,
+                                                         float* __restrict__ part_q, float* __restrict__ part_k) {
+  constexpr int LG = HD / 8, HPW = 64 / LG;
+  __shared__ float red[4][2][HD];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int d0 = (lane % LG) * 8, slot = lane / LG;
+  float wqv[8], wkv[8], aq[8], ak[8];
+  unpack_bf16x8(*reinterpret_cast<const uint4*>(wq + d0), wqv);
+  unpack_bf16x8(*reinterpret_cast<const uint4*>(wk + d0), wkv);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { aq[j] = 0.f; ak[j] = 0.f; }
+  struct Item { uint4 x, dy; float r; bf16_t* dp; bool isq, ok; };
+  auto load = [&](uint32_t chunk) {
+    Item it;
+    const uint32_t g = chunk * HPW + slot;
+    it.ok = g < total;
+    it.x = it.dy = make_uint4(0, 0, 0, 0);
+    it.r = 0.f;
+    it.dp = nullptr;
+    it.isq = true;
+    if (it.ok) {
+      const uint32_t m = g / (uint32_t)nQK;
+      const int h = (int)(g - m * (uint32_t)nQK);
+      it.isq = h < nH;
+      it.dp = dqkv + (size_t)m * ld + (size_t)h * HD + d0;
+      it.x = *reinterpret_cast<const uint4*>(raw + (size_t)g * HD + d0);
+      it.dy = *reinterpret_cast<const uint4*>(it.dp);
+      it.r = rstd[g];
+    }
+    return it;
+  };
+  const uint32_t nchunks = (total + HPW - 1) / HPW, step = gridDim.x * 4u;
+  uint32_t c = blockIdx.x * 4u + wave;
+  Item cur{};
+  if (c < nchunks) cur = load(c);
+  for (; c < nchunks; c += step) {  // the next chunk's loads are in flight while this one is reduced
+    Item nxt{};
+    if (c + step < nchunks) nxt = load(c + step);
+    float fx[8], fd[8], xh[8], gy[8];
+    unpack_bf16x8(cur.x, fx);
+    unpack_bf16x8(cur.dy, fd);
+    float dot = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      xh[j] = fx[j] * cur.r;
+      gy[j] = fd[j] * (cur.isq ? wqv[j] : wkv[j]);
+      dot += gy[j] * xh[j];
+      const float dwj = fd[j] * xh[j];
+      aq[j] += cur.isq ? dwj : 0.f;
+      ak[j] += cur.isq ? 0.f : dwj;
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+    dot /= (float)HD;
+    float o8[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o8[j] = cur.r * (gy[j] - xh[j] * dot);
+    if (cur.ok) *reinterpret_cast<uint4*>(cur.dp) = pack_bf16x8(o8);
+    cur = nxt;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+#pragma unroll
+    for (int o = LG; o < 64; o <<= 1) {
+      aq[j] += __shfl_xor(aq[j], o, 64);
+      ak[j] += __shfl_xor(ak[j], o, 64);
+    }
+  }
+  if (slot == 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { red[wave][0][d0 + j] = aq[j]; red[wave][1][d0 + j] = ak[j]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 * HD) {
+    const int k = threadIdx.x / HD, e = threadIdx.x % HD;
+    (k ? part_k : part_q)[(size_t)blockIdx.x * HD + e] = red[0][k][e] + red[1][k][e] + red[2][k][e] + red[3][k][e];
+  }
+}
+
+// Decode: the q and k heads of the fp32 projection rows [B][ld], normalised in place (fp32 in, fp32 out, weight applied);
+// attn_decode then rotates and rounds once.
+template <int HD>
+__global__ __launch_bounds__(256) void qknorm_rows_f32_kernel(float* __restrict__ qkv, int ld, uint32_t total, int nH, int nQK,
+                                                              const bf16_t* __restrict__ wq, const bf16_t* __restrict__ wk,
+                                                              float eps) {
+  constexpr int LG = HD / 8;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t g = t / LG;
+  const int d0 = (int)(t % LG) * 8;
+  const bool ok = g < total;
+  const uint32_t m = ok ? g / (uint32_t)nQK : 0;
+  const int h = ok ? (int)(g - m * (uint32_t)nQK) : 0;
+  float* p = qkv + (size_t)m * ld + (size_t)h * HD + d0;
+  float x[8] = {0, 0, 0, 0, 0, 0, 0, 0}, w[8];
+  if (ok) {
+    *reinterpret_cast<float4*>(x) = reinterpret_cast<const float4*>(p)[0];
+    *reinterpret_cast<float4*>(x + 4) = reinterpret_cast<const float4*>(p)[1];
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ss += x[j] * x[j];
+#pragma unroll
+  for (int o = LG / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (!ok) return;
+  const float r = rsqrtf(ss / (float)HD + eps);
+  unpack_bf16x8(*reinterpret_cast<const uint4*>((h < nH ? wq : wk) + d0), w);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = x[j] * r * w[j];
+  reinterpret_cast<float4*>(p)[0] = *reinterpret_cast<float4*>(x);
+  reinterpret_cast<float4*>(p)[1] = *reinterpret_cast<float4*>(x + 4);
+}
 
 }  // namespace
 
@@ -1178,6 +1353,56 @@ int rope_apply(bf16_t* qkv, int ld, int M, int nrot_heads, int head_dim, const f
   if (head_dim & 15) return -1;
   rope_kernel<<<nblocks((size_t)M * nrot_heads * (head_dim / 16), 256), 256, 0, st>>>(qkv, ld, M, nrot_heads, head_dim, cs, sn,
                                                                                      backward ? -1.f : 1.f, q_heads, q_scale);
+  LAUNCH_RET();
+}
+
+// Qwen3's per-head q / k RMSNorm. -1: a shape or pointer the kernels do not take (nothing is launched)
+static bool qknorm_shape_ok(int M, int nH, int nKV, int head_dim, int ld) {
+  if (!(M > 0 && nH > 0 && nKV > 0 && (head_dim == 64 || head_dim == 128) && ld >= (nH + nKV) * head_dim && (ld & 7) == 0)) return false;
+  // the kernels index heads and threads in 32 bits: M (nH + nKV) head_dim / 8 threads (+ a block of slack) must stay below 2^31
+  return (uint64_t)M * (uint64_t)(nH + nKV) * (uint64_t)(head_dim / 8) < (1ull << 31) - 1024;
+}
+
+int qknorm_rope_fwd(bf16_t* qkv, int ld, int M, int nH, int nKV, int head_dim, const bf16_t* wq, const bf16_t* wk, const float* cs,
+                    const float* sn, const float* csq, const float* snq, float eps, bf16_t* raw_save, float* rstd_save,
+                    hipStream_t st) {
+  if (!qkv || !wq || !wk || !cs || !sn || !csq || !snq || !qknorm_shape_ok(M, nH, nKV, head_dim, ld)) return -1;
+  const int nQK = nH + nKV;
+  const uint32_t total = (uint32_t)M * (uint32_t)nQK;
+  const unsigned grid = nblocks((size_t)total * (head_dim / 8), 256);
+  if (head_dim == 64) qknorm_rope_fwd_kernel<64><<<grid, 256, 0, st>>>(qkv, ld, total, nH, nQK, wq, wk, cs, sn, csq, snq, eps, raw_save, rstd_save);
+  else qknorm_rope_fwd_kernel<128><<<grid, 256, 0, st>>>(qkv, ld, total, nH, nQK, wq, wk, cs, sn, csq, snq, eps, raw_save, rstd_save);
+  LAUNCH_RET();
+}
+
+// one wave per 64 / (head_dim / 8) heads at a time, four waves a block, at most 1024 blocks (4 per CU)
+int qknorm_bwd_blocks(int M, int nH, int nKV, int head_dim) {
+  if (M <= 0 || nH <= 0 || nKV <= 0 || (head_dim != 64 && head_dim != 128)) return 1;
+  const size_t hpw = 64 / (head_dim / 8), chunks = ((size_t)M * (nH + nKV) + hpw - 1) / hpw;
+  const size_t b = (chunks + 3) / 4;
+  return b > 1024 ? 1024 : (int)b;
+}
+
+// nb: blocks = rows of the partial slabs (1 .. qknorm_bwd_blocks(..); fewer blocks walk more heads each)
+int qknorm_bwd(bf16_t* dqkv, int ld, int M, int nH, int nKV, int head_dim, const bf16_t* raw, const float* rstd, const bf16_t* wq,
+               const bf16_t* wk, int nb, float* part_q, float* part_k, hipStream_t st) {
+  if (!dqkv || !raw || !rstd || !wq || !wk || !part_q || !part_k || !qknorm_shape_ok(M, nH, nKV, head_dim, ld)) return -1;
+  if (nb < 1 || nb > qknorm_bwd_blocks(M, nH, nKV, head_dim)) return -1;
+  const int nQK = nH + nKV;
+  const uint32_t total = (uint32_t)M * (uint32_t)nQK;
+  if (head_dim == 64) qknorm_bwd_kernel<64><<<nb, 256, 0, st>>>(dqkv, ld, raw, rstd, wq, wk, total, nH, nQK, part_q, part_k);
+  else qknorm_bwd_kernel<128><<<nb, 256, 0, st>>>(dqkv, ld, raw, rstd, wq, wk, total, nH, nQK, part_q, part_k);
+  LAUNCH_RET();
+}
+
+int qknorm_rows_f32(float* qkv, int ld, int B, int nH, int nKV, int head_dim, const bf16_t* wq, const bf16_t* wk, float eps,
+                    hipStream_t st) {
+  if (!qkv || !wq || !wk || !qknorm_shape_ok(B, nH, nKV, head_dim, ld)) return -1;
+  const int nQK = nH + nKV;
+  const uint32_t total = (uint32_t)B * (uint32_t)nQK;
+  const unsigned grid = nblocks((size_t)total * (head_dim / 8), 256);
+  if (head_dim == 64) qknorm_rows_f32_kernel<64><<<grid, 256, 0, st>>>(qkv, ld, total, nH, nQK, wq, wk, eps);
+  else qknorm_rows_f32_kernel<128><<<grid, 256, 0, st>>>(qkv, ld, total, nH, nQK, wq, wk, eps);
   LAUNCH_RET();
 }
 

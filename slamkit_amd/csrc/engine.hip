@@ -37,10 +37,12 @@ constexpr int VPAD_SMALL = 512;  // vocabularies up to 512 (the speech-unit LMs)
 constexpr int GU_BLK = 32;  // Wgu rows / gate|up columns come in blocks of 32 gate + 32 up
 constexpr int RC_SLOTS = 3;  // "recompute": shared activation slots (layer l uses slot l mod 3; DESIGN.md has the hazard table)
 
-// OPT (arch 1) keeps fc1 in `wgu` and fc2 in `wd`; ln1_b, bo, ln2_b, b1, b2 are OPT's alone
+// OPT (arch 1) keeps fc1 in `wgu` and fc2 in `wd`; ln1_b, bo, ln2_b, b1, b2 are OPT's alone. Qwen3 (arch 3) has no bqkv (-1);
+// q_norm, k_norm are Qwen3's alone
 struct LayerOff {
   int64_t ln1, wqkv, bqkv, wo, ln2, wgu, wd;
   int64_t ln1_b = -1, bo = -1, ln2_b = -1, b1 = -1, b2 = -1;
+  int64_t q_norm = -1, k_norm = -1;
 };
 
 // OPT: gu is [M][I] (the layer's d(act) in backward), act the post-ReLU fc1 output; mu1 / mu2 the LayerNorm means
@@ -48,6 +50,9 @@ struct LayerAct {
   bf16_t *hmid, *x1, *x2, *qkv, *o, *gu, *act;
   float *rstd1, *rstd2, *lse;
   float *mu1 = nullptr, *mu2 = nullptr;
+  // Qwen3: the raw (pre-norm) q|k columns of the projection [M][(nH + nKV) hd] and the heads' rstd [M][nH + nKV]
+  bf16_t* qk_raw = nullptr;
+  float* qk_rstd = nullptr;
 };
 
 // an identity rotation: cs = 1, sn = 0, and the query tables carry only the pre-scale (OPT has no RoPE; the attention
@@ -73,7 +78,7 @@ __global__ void seg_fill_kernel(int* seg_start, int* seg_end, int M, int T) {
 
 struct SlamEngine {
   SlamModelDesc d;
-  int arch = 0;  // 0 Qwen2, 1 OPT (slam_engine_create_arch)
+  int arch = 0;  // 0 Qwen2, 1 OPT, 3 Qwen3 (slam_engine_create_arch)
   int npos = 0;  // OPT: rows of the learned position table (n_positions + 2, HF's offset)
   int QKV;  // (nH + 2 nKV) * hd
   int vpad = VPAD_SMALL;  // embedding / logits rows: 512, or vocab rounded up to 256 beyond that
@@ -219,7 +224,9 @@ struct SlamEngine {
   float* nlse = nullptr;
   float *cosq = nullptr, *sinq = nullptr;  // the query heads' RoPE tables: cos / sin times head_dim^-0.5 * log2(e)
   float *rstdf, *row_loss, *dsum, *dkv_part, *cosb, *sinb, *gemm_ws, *part_ws, *scal;
-  float *ln_part, *bias_part;  // per-layer partial slabs: [2L][nb_ln][H], [L][nb_cs][QKV]
+  // per-layer partial slabs: [2L][nb_ln][H], [L][nb_cs][QKV]. Qwen3 has no q|k|v bias: layer l's slab holds the partials of
+  // dw_q [qn_blocks][hd] and, behind them, of dw_k (qn_blocks caps the launch so that both fit)
+  float *ln_part, *bias_part;
   size_t ln_ps = 0, bias_ps = 0;
   // OPT: LayerNorm bias slabs [2L][nb_ln][H]; bo, b1, b2 slabs [L][nb_cs][H | I | H]; final-norm mean; position rows of the tokens
   float *lnb_part = nullptr, *bo_part = nullptr, *b1_part = nullptr, *b2_part = nullptr, *muf = nullptr;
@@ -313,6 +320,11 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
     if (opt) {
       a.mu1 = all ? s->mu1 : c.take<float>(M);
       a.mu2 = all ? s->mu2 : c.take<float>(M);
+    }
+    if (e->arch == 3) {  // kept per layer wherever qkv is: backward needs xhat of the heads the in-place store overwrote
+      const size_t nQK = (size_t)d.n_heads + d.n_kv_heads;
+      a.qk_raw = all ? s->qk_raw : c.take<bf16_t>(M * nQK * d.head_dim);
+      a.qk_rstd = all ? s->qk_rstd : c.take<float>(M * nQK);
     }
   }
   e->hf = c.take<bf16_t>(M * H);
@@ -633,6 +645,15 @@ bf16_t* kv_k(SlamEngine* h, int l) {
 }
 bf16_t* kv_v(SlamEngine* h, int l) { return kv_k(h, l) + (size_t)h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim; }
 
+// Qwen3: blocks of the q / k norm backward over M tokens - what the kernel would like, capped so that the two partial slabs
+// fit the layer's (otherwise unused) bias slab of colsum_blocks(M) x QKV floats: at least 3 / 2 colsum_blocks(M) blocks
+int qn_blocks(const SlamEngine* h, int M) {
+  const SlamModelDesc& d = h->d;
+  const int want = qknorm_bwd_blocks(M, d.n_heads, d.n_kv_heads, d.head_dim);
+  const int cap = (int)((size_t)colsum_blocks(M) * h->QKV / (2 * (size_t)d.head_dim));
+  return want < cap ? want : cap;
+}
+
 // One decoder layer's forward launches over M tokens: hs[l] -> la[l] (-> hs[l + 1]). The one body that slam_forward,
 // slam_prefill and the recomputation in slam_backward share, so a re-run issues the forward's own calls in the forward's own
 // order. `rerun` (backward, "recompute" = 2): the layer's parameters are already final for this step (no chunk / parameter
@@ -652,7 +673,13 @@ int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
   }
   if (opt) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, d.rms_eps, st));
   else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
-  if (d.head_dim == 64 && (H % 64 == 0) && (h->QKV % 128 == 0)) {  // bias + RoPE fused into the projection epilogue
+  if (h->arch == 3) {  // Qwen3: no bias; per-head RMSNorm + RoPE in one pass behind the projection (never the fused epilogue)
+    const int slot = fam_begin(h, F_QKV_FWD, st);
+    CK(gemm_nt(a.x1, P + o.wqkv, a.qkv, nullptr, nullptr, M, h->QKV, H, st));
+    CK(qknorm_rope_fwd(a.qkv, h->QKV, M, nH, nKV, d.head_dim, P + o.q_norm, P + o.k_norm, h->cosb, h->sinb, h->cosq, h->sinq,
+                       d.rms_eps, a.qk_raw, a.qk_rstd, st));
+    fam_end(h, slot, st);
+  } else if (d.head_dim == 64 && (H % 64 == 0) && (h->QKV % 128 == 0)) {  // bias + RoPE fused into the projection epilogue
     TK(F_QKV_FWD, st, gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
   } else {
     const int slot = fam_begin(h, F_QKV_FWD, st);
@@ -784,14 +811,15 @@ int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_p
 int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, int32_t flags, SlamEngine** out) {
   if (!desc || !out) return SLAM_EINVAL;
   const SlamModelDesc& d = *desc;
-  if (arch != 0 && arch != 1) return SLAM_EINVAL;
+  if (arch != 0 && arch != 1 && arch != 3) return SLAM_EINVAL;  // 2 is not a family
   if (flags & ~SLAM_MODEL_UNTIED_HEAD) return SLAM_EINVAL;
   const bool untied = (flags & SLAM_MODEL_UNTIED_HEAD) != 0;
-  if (untied && arch != 0) return SLAM_EINVAL;
+  if (untied && arch == 1) return SLAM_EINVAL;
   if ((d.head_dim != 64 && d.head_dim != 128) || d.n_heads <= 0 || d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return SLAM_EINVAL;
-  if (d.hidden % 8 || d.hidden > (arch == 0 ? 4096 : 2048) || d.vocab <= 0) return SLAM_EINVAL;  // the row-norm kernels' limits
+  if (d.hidden % 8 || d.hidden > (arch == 1 ? 2048 : 4096) || d.vocab <= 0) return SLAM_EINVAL;  // the row-norm kernels' limits
   if (d.n_layers <= 0) return SLAM_EINVAL;
-  if (arch == 0 && d.intermediate % GU_BLK) return SLAM_EINVAL;
+  if (arch != 1 && d.intermediate % GU_BLK) return SLAM_EINVAL;
+  if (arch == 3 && (d.intermediate <= 0 || d.n_heads / d.n_kv_heads > 8)) return SLAM_EINVAL;  // the decode kernels' group limit
   // OPT: multi-head attention (kv = q heads), head_dim 64, a position table of n_positions + 2 rows
   if (arch == 1 && (d.n_kv_heads != d.n_heads || d.head_dim != 64 || d.intermediate <= 0 || d.intermediate % 8 || n_positions <= 0))
     return SLAM_EINVAL;
@@ -802,7 +830,7 @@ int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_pos
   e->npos = arch == 1 ? n_positions + 2 : 0;
   e->QKV = (d.n_heads + 2 * d.n_kv_heads) * d.head_dim;
   e->vpad = d.vocab <= VPAD_SMALL ? VPAD_SMALL : ((d.vocab + 255) / 256) * 256;  // 256: the LM-head GEMM can take the 256 x 256 kernel
-  e->fuse_swiglu = arch == 0 && (d.hidden % 64 == 0) && ((2 * d.intermediate) % 128 == 0);
+  e->fuse_swiglu = arch != 1 && (d.hidden % 64 == 0) && ((2 * d.intermediate) % 128 == 0);
   int64_t off = 0;
   e->off_embed = off;
   add_tensor(e, "embed", off, e->vpad, d.hidden);
@@ -828,6 +856,16 @@ int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_pos
       o.b1 = off;    add_tensor(e, p + "b1", off, d.intermediate, 1);
       o.wd = off;    add_tensor(e, p + "w2", off, d.hidden, d.intermediate);
       o.b2 = off;    add_tensor(e, p + "b2", off, d.hidden, 1);
+    } else if (arch == 3) {
+      o.ln1 = off;    add_tensor(e, p + "ln1", off, d.hidden, 1);
+      o.wqkv = off;   add_tensor(e, p + "wqkv", off, e->QKV, d.hidden);
+      o.bqkv = -1;
+      o.q_norm = off; add_tensor(e, p + "q_norm", off, d.head_dim, 1);
+      o.k_norm = off; add_tensor(e, p + "k_norm", off, d.head_dim, 1);
+      o.wo = off;     add_tensor(e, p + "wo", off, d.hidden, d.n_heads * d.head_dim);
+      o.ln2 = off;    add_tensor(e, p + "ln2", off, d.hidden, 1);
+      o.wgu = off;    add_tensor(e, p + "wgu", off, 2 * d.intermediate, d.hidden);
+      o.wd = off;     add_tensor(e, p + "wd", off, d.hidden, d.intermediate);
     } else {
       o.ln1 = off;  add_tensor(e, p + "ln1", off, d.hidden, 1);
       o.wqkv = off; add_tensor(e, p + "wqkv", off, e->QKV, d.hidden);
@@ -1137,7 +1175,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
                  slam_stream_t stream) {
   if (!h || !ids || !lens || !logits_out || B <= 0 || T <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
-  if (h->arch != 0) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
+  if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (B > h->kv_bmax || T > h->kv_cap) return h->fail(SLAM_EINVAL, "prefill batch exceeds the bound KV cache");
   if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
@@ -1168,7 +1206,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
 int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B, float* logits_out, slam_stream_t stream) {
   if (!h || !ids || !lens || !logits_out || B <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
-  if (h->arch != 0) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
+  if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_decode_step needs a slam_prefill into the bound cache first");
   if (B != h->kv_B) return h->fail(SLAM_EINVAL, "decode batch differs from the prefill batch");
@@ -1187,6 +1225,7 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
   float* qkvf = (float*)h->dqkv;
   int64_t* pos = (int64_t*)h->nlse;
   const float qscale = 1.44269504088896340736f / sqrtf((float)hd);
+  const bool q3 = h->arch == 3;
   CK(lens_to_pos(lens, pos, B, st));
   CK(rope_table(pos, B, 1, hd, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
   CK(embed_fwd(ids, P + h->off_embed, h->hs[0], B, H, d.vocab, st));
@@ -1196,7 +1235,9 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
     LayerAct& a = h->la[l];
     CK(rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, B, H, d.rms_eps, st));
     CK(decode_proj(h, a.x1, P + o.wqkv, nullptr, qkvf, nullptr, nullptr, B, h->QKV, H, st));
-    CK(attn_decode(qkvf, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, nH, nKV, hd,
+    // Qwen3: the q and k heads are normalised in the fp32 row; attn_decode then rotates and rounds once, without a bias
+    if (q3) CK(qknorm_rows_f32(qkvf, h->QKV, B, nH, nKV, hd, P + o.q_norm, P + o.k_norm, d.rms_eps, st));
+    CK(attn_decode(qkvf, q3 ? nullptr : P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, nH, nKV, hd,
                    h->kv_hi + 1, a.o, (float*)h->logits, part_bytes, st));
     CK(decode_proj(h, a.o, P + o.wo, a.hmid, nullptr, nullptr, h->hs[l], B, H, nH * hd, st));
     CK(rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, B, H, d.rms_eps, st));
@@ -1232,7 +1273,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
                   float* logits_out, bool score, float* lp_out, int64_t* argmax_out, slam_stream_t stream) {
   if (!h || !ids || !new_lens || !lens || !logits_out || B <= 0 || T <= 0 || (score && !lp_out)) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
-  if (h->arch != 0) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
+  if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
   if ((int64_t)2 * B > h->max_tokens) return h->fail(SLAM_ENOMEM, "extend needs a workspace of at least 2 B tokens");
@@ -1260,7 +1301,8 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
   CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
   const size_t part_bytes = (size_t)h->max_tokens * h->vpad * sizeof(bf16_t);
   const int kv_bound = h->kv_hi + T;
-  const bool fused_rope = M > SKINNY_MAX_M && hd == 64 && (H % 64 == 0) && (h->QKV % 128 == 0);
+  const bool q3 = h->arch == 3;  // Qwen3: no bias, and the per-head norm sits between the projection and the rotation
+  const bool fused_rope = !q3 && M > SKINNY_MAX_M && hd == 64 && (H % 64 == 0) && (h->QKV % 128 == 0);
   for (int l = 0; l < L; ++l) {
     const LayerOff& o = h->lo[l];
     LayerAct& a = h->la[l];
@@ -1268,8 +1310,9 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
     if (fused_rope) {
       CK(gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
     } else {
-      CK(decode_proj(h, a.x1, P + o.wqkv, a.qkv, nullptr, P + o.bqkv, nullptr, M, h->QKV, H, st));
-      CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, hd, h->cosb, h->sinb, 0, st, nH, qscale));
+      CK(decode_proj(h, a.x1, P + o.wqkv, a.qkv, nullptr, q3 ? nullptr : P + o.bqkv, nullptr, M, h->QKV, H, st));
+      if (q3) CK(qknorm_rope_fwd(a.qkv, h->QKV, M, nH, nKV, hd, P + o.q_norm, P + o.k_norm, h->cosb, h->sinb, h->cosq, h->sinq, d.rms_eps, nullptr, nullptr, st));
+      else CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, hd, h->cosb, h->sinb, 0, st, nH, qscale));
     }
     CK(attn_extend(a.qkv, lens, new_lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, T, nH, nKV, hd, kv_bound, a.o, (float*)h->logits,
                    part_bytes, st));
@@ -1425,7 +1468,8 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
   else CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_embed, VP, H, nullptr, false));  // not final: the gather side adds to it below
   TK(F_HEAD_DGRAD, st, dgrad(h->dlogits, h->off_head, h->dx, VP, H));
   bf16_t* dh = h->dh_a;  // grad wrt hs[l+1]
-  const bool opt = h->arch == 1;
+  const bool opt = h->arch == 1, q3 = h->arch == 3;
+  const int qnb = q3 ? qn_blocks(h, M) : 0;
   if (opt) {  // final LayerNorm: dw | db slabs in part_ws, one finish launch per tensor
     const int nbl = rmsnorm_bwd_blocks(M);
     float* pw = h->part_ws;
@@ -1560,13 +1604,19 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
     TK(F_O_DGRAD, st, dgrad(dh2, o.wo, h->d_o, H, HD));
     TK(F_ATTN_BWD, st, attn_bwd(a.qkv, a.o, h->d_o, a.lse, h->dsum, h->nlse, dqkv, h->dkv_part, h->cur_seg_s, h->cur_seg_e, h->attn_plan_buf, h->attn_tune, h->cosb, h->sinb,
                 M, nH, nKV, d.head_dim, st));  // dq / dk come out already rotated back
-    if (aux) {  // behind the same hand-over as the Wqkv gradient: both read d(qkv)
+    if (q3) {
+      // Qwen3: dq / dk are gradients of the NORMED heads; the per-head norm backward turns them into gradients of the
+      // projection in place, before the Wqkv weight gradient and the dgrad read d(qkv). No bias, so no column sums.
+      float* pq = h->bias_part + (size_t)l * h->bias_ps;
+      TK(F_NORM_BWD, st, qknorm_bwd(dqkv, h->QKV, M, nH, nKV, d.head_dim, a.qk_raw, a.qk_rstd, P + o.q_norm, P + o.k_norm, qnb, pq,
+                                    pq + (size_t)qnb * d.head_dim, st));
+    } else if (aux) {  // behind the same hand-over as the Wqkv gradient: both read d(qkv)
       CK(fork());
       CK(colsum_bf16(dqkv, h->QKV, M, h->QKV, nullptr, 1, h->bias_part + (size_t)l * h->bias_ps, ws));
     } else {
       CK(colsum_bf16(dqkv, h->QKV, M, h->QKV, nullptr, 1, h->bias_part + (size_t)l * h->bias_ps, st));
     }
-    CK(wgrad(F_WQKV_WGRAD, dqkv, a.x1, G + o.wqkv, h->QKV, H, img(o.wqkv), true, aux));
+    CK(wgrad(F_WQKV_WGRAD, dqkv, a.x1, G + o.wqkv, h->QKV, H, img(o.wqkv), true, aux && !q3));
     CK(slot_done(l));
     TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, h->dx, h->QKV, H));
     dh = a.hmid;  // grad wrt hs[l]: hmid[l] was last read by the ln2 backward above
@@ -1583,7 +1633,14 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
       if (aux) CK(fork());
       CK(take(colsum_finish_many(h->ln_part + (size_t)(2 * l) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln1, (size_t)h->layer_stride, cnt, acc, fs, img(o.ln1), sink())));
       CK(take(colsum_finish_many(h->ln_part + (size_t)(2 * l + 1) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln2, (size_t)h->layer_stride, cnt, acc, fs, img(o.ln2), sink())));
-      CK(take(colsum_finish_many(h->bias_part + (size_t)l * h->bias_ps, h->bias_ps, nbc, h->QKV, G + o.bqkv, (size_t)h->layer_stride, cnt, acc, fs, img(o.bqkv), sink())));
+      if (q3) {  // the q / k norm weights: two more slabs, finished like the layer norms'
+        const size_t ls = (size_t)h->layer_stride;
+        const float* pq = h->bias_part + (size_t)l * h->bias_ps;
+        CK(take(colsum_finish_many(pq, h->bias_ps, qnb, d.head_dim, G + o.q_norm, ls, cnt, acc, fs, img(o.q_norm), sink())));
+        CK(take(colsum_finish_many(pq + (size_t)qnb * d.head_dim, h->bias_ps, qnb, d.head_dim, G + o.k_norm, ls, cnt, acc, fs, img(o.k_norm), sink())));
+      } else {
+        CK(take(colsum_finish_many(h->bias_part + (size_t)l * h->bias_ps, h->bias_ps, nbc, h->QKV, G + o.bqkv, (size_t)h->layer_stride, cnt, acc, fs, img(o.bqkv), sink())));
+      }
       if (opt) {  // LayerNorm biases, out_proj / fc1 / fc2 biases
         const size_t ls = (size_t)h->layer_stride;
         CK(take(colsum_finish_many(h->lnb_part + (size_t)(2 * l) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln1_b, ls, cnt, acc, fs, img(o.ln1_b), sink())));
@@ -2300,6 +2357,47 @@ int slam_op_rope(void* qkv, int ld, int M, int T, int n_rot_heads, int head_dim,
   int r = rope_table(position_ids, M, T, head_dim, theta, cs_ws, cs_ws + (size_t)M * half, nullptr, nullptr, 1.f, (hipStream_t)s);
   if (r) return r;
   return rope_apply((bf16_t*)qkv, ld, M, n_rot_heads, head_dim, cs_ws, cs_ws + (size_t)M * half, backward, (hipStream_t)s);
+}
+// the argument ranges of the three q / k norm entry points, checked before anything is launched (the kernels index heads in
+// 32 bits: elementwise.hip)
+static bool qknorm_dims_ok(int M, int nH, int nKV, int head_dim) {
+  if (M <= 0 || nH <= 0 || nKV <= 0 || (head_dim != 64 && head_dim != 128)) return false;
+  return (uint64_t)M * (uint64_t)(nH + nKV) * (uint64_t)(head_dim / 8) < (1ull << 31) - 1024;
+}
+int slam_op_qknorm_rope_fwd(void* qkv, const void* w_q, const void* w_k, const int64_t* position_ids, float theta, float eps,
+                            int M, int T, int nH, int nKV, int head_dim, void* raw_out, float* rstd_out, float* table_ws,
+                            slam_stream_t s) {
+  if (!qkv || !w_q || !w_k || !table_ws || T <= 0 || !qknorm_dims_ok(M, nH, nKV, head_dim)) return SLAM_EINVAL;
+  const size_t n = (size_t)M * (head_dim / 2);
+  const float qscale = 1.44269504088896340736f / sqrtf((float)head_dim);
+  int r = rope_table(position_ids, M, T, head_dim, theta, table_ws, table_ws + n, table_ws + 2 * n, table_ws + 3 * n, qscale, (hipStream_t)s);
+  if (r) return r;
+  r = qknorm_rope_fwd((bf16_t*)qkv, (nH + 2 * nKV) * head_dim, M, nH, nKV, head_dim, (const bf16_t*)w_q, (const bf16_t*)w_k, table_ws,
+                      table_ws + n, table_ws + 2 * n, table_ws + 3 * n, eps, (bf16_t*)raw_out, rstd_out, (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
+}
+size_t slam_op_qknorm_bwd_workspace(int M, int nH, int nKV, int head_dim) {
+  if (!qknorm_dims_ok(M, nH, nKV, head_dim)) return 0;
+  return (size_t)2 * qknorm_bwd_blocks(M, nH, nKV, head_dim) * head_dim * sizeof(float);
+}
+int slam_op_qknorm_bwd(void* dqkv, const void* raw, const float* rstd, const void* w_q, const void* w_k, float* dw_q, float* dw_k,
+                       float* ws, int M, int nH, int nKV, int head_dim, slam_stream_t s) {
+  if (!dqkv || !raw || !rstd || !w_q || !w_k || !dw_q || !dw_k || !ws || !qknorm_dims_ok(M, nH, nKV, head_dim)) return SLAM_EINVAL;
+  const int nb = qknorm_bwd_blocks(M, nH, nKV, head_dim);
+  float* pk = ws + (size_t)nb * head_dim;
+  int r = qknorm_bwd((bf16_t*)dqkv, (nH + 2 * nKV) * head_dim, M, nH, nKV, head_dim, (const bf16_t*)raw, rstd, (const bf16_t*)w_q,
+                     (const bf16_t*)w_k, nb, ws, pk, (hipStream_t)s);
+  if (r) return r == -1 ? SLAM_EINVAL : r;
+  r = colsum_finish_many(ws, 0, nb, head_dim, dw_q, 0, 1, 0, (hipStream_t)s);
+  if (r) return r;
+  return colsum_finish_many(pk, 0, nb, head_dim, dw_k, 0, 1, 0, (hipStream_t)s);
+}
+int slam_op_qknorm_rows_f32(float* qkv, const void* w_q, const void* w_k, float eps, int B, int nH, int nKV, int head_dim,
+                            slam_stream_t s) {
+  if (!qkv || !w_q || !w_k || !qknorm_dims_ok(B, nH, nKV, head_dim)) return SLAM_EINVAL;
+  const int r = qknorm_rows_f32(qkv, (nH + 2 * nKV) * head_dim, B, nH, nKV, head_dim, (const bf16_t*)w_q, (const bf16_t*)w_k, eps,
+                                (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
 }
 int slam_op_swiglu_fwd(const void* gu, void* act, int M, int I, slam_stream_t s) {
   return swiglu_fwd((const bf16_t*)gu, (bf16_t*)act, M, I, I, (hipStream_t)s);

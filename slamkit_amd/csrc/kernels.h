@@ -129,6 +129,22 @@ int rope_table(const int64_t* pos, int M, int T, int head_dim, float theta, floa
                float qscale, hipStream_t st);
 int rope_apply(bf16_t* qkv, int ld, int M, int nrot_heads, int head_dim, const float* cs, const float* sn, int backward,
                hipStream_t st, int q_heads = 0, float q_scale = 1.f);
+// Qwen3: RMSNorm over head_dim (64 or 128) of every q and k head of qkv [M][ld] with the weights wq / wk [head_dim], then
+// rotate-half RoPE (csq / snq for the nH query heads), fp32 throughout, one rounding at the in-place store; the v columns are
+// not touched. raw_save (bf16 [M][(nH + nKV) head_dim]: the input bits) and rstd_save (fp32 [M][nH + nKV]) are nullable.
+// -1 = unsupported shape or a null pointer, before any launch (qknorm_bwd and qknorm_rows_f32 alike).
+int qknorm_rope_fwd(bf16_t* qkv, int ld, int M, int nH, int nKV, int head_dim, const bf16_t* wq, const bf16_t* wk, const float* cs,
+                    const float* sn, const float* csq, const float* snq, float eps, bf16_t* raw_save, float* rstd_save,
+                    hipStream_t st);
+// in place on the q|k columns of dqkv: dx = rstd (dy w - xhat mean_d(dy w xhat)); part_q / part_k: per-block partial slabs
+// [nb][head_dim] of dw_q / dw_k = sum dy xhat (colsum_finish_many finishes them, in block order); nb = the launch's blocks,
+// 1 .. qknorm_bwd_blocks(..) (the count the kernel likes best)
+int qknorm_bwd_blocks(int M, int nH, int nKV, int head_dim);
+int qknorm_bwd(bf16_t* dqkv, int ld, int M, int nH, int nKV, int head_dim, const bf16_t* raw, const float* rstd, const bf16_t* wq,
+               const bf16_t* wk, int nb, float* part_q, float* part_k, hipStream_t st);
+// decode: the q and k heads of the fp32 projection rows [B][ld] normalised in place (weight applied, no rounding to bf16)
+int qknorm_rows_f32(float* qkv, int ld, int B, int nH, int nKV, int head_dim, const bf16_t* wq, const bf16_t* wk, float eps,
+                    hipStream_t st);
 int swiglu_fwd(const bf16_t* gu, bf16_t* act, int M, int I, int blk, hipStream_t st);
 int swiglu_bwd(bf16_t* gu, const bf16_t* dact, int M, int I, int blk, hipStream_t st);
 int embed_fwd(const int64_t* ids, const bf16_t* E, bf16_t* out, int M, int H, int V, hipStream_t st);

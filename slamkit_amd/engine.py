@@ -159,6 +159,10 @@ def load_library(path: Optional[str] = None):
         "slam_op_gemm_nt_drelu": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_relu_bwd": (C.c_int, [vp, vp, i64, vp]),
         "slam_op_rope": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, f32, C.c_int, vp, vp]),
+        "slam_op_qknorm_rope_fwd": (C.c_int, [vp, vp, vp, vp, f32, f32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "slam_op_qknorm_bwd_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int]),
+        "slam_op_qknorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_qknorm_rows_f32": (C.c_int, [vp, vp, vp, f32, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_swiglu_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "slam_op_swiglu_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
         "slam_op_attn_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
@@ -310,7 +314,8 @@ class Engine:
     """Thin owner of a SlamEngine handle plus the torch tensors it borrows."""
 
     def __init__(self, desc: SlamModelDesc, arch: int = 0, n_positions: int = 0, flags: int = 0):
-        """arch 0 = Qwen2, 1 = OPT (n_positions = max_position_embeddings); flags: MODEL_UNTIED_HEAD (slam_engine_create_ex)."""
+        """arch 0 = Qwen2, 1 = OPT (n_positions = max_position_embeddings), 3 = Qwen3; flags: MODEL_UNTIED_HEAD
+        (slam_engine_create_ex)."""
         self.lib = load_library()
         self.desc = desc
         self.arch = arch

@@ -42,6 +42,15 @@ KNOWN_BASE_CONFIGS = {
     "Qwen/Qwen2.5-7B": dict(num_hidden_layers=28, hidden_size=3584, num_attention_heads=28, num_key_value_heads=4,
                             head_dim=128, intermediate_size=18944, rms_norm_eps=1e-6, rope_theta=1000000.0,
                             tie_word_embeddings=False, initializer_range=0.02),
+    # Qwen3: the current small Qwen text LMs (per-head q / k RMSNorm, no q/k/v bias, head_dim a field of its own). These
+    # numbers restate the published configs and cannot be checked without the hub: a local HuggingFace directory as
+    # base_model_name remains the authoritative route (its config.json is read instead)
+    "Qwen/Qwen3-0.6B": dict(model_type="qwen3", num_hidden_layers=28, hidden_size=1024, num_attention_heads=16,
+                            num_key_value_heads=8, head_dim=128, intermediate_size=3072, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                            tie_word_embeddings=True, initializer_range=0.02),
+    "Qwen/Qwen3-1.7B": dict(model_type="qwen3", num_hidden_layers=28, hidden_size=2048, num_attention_heads=16,
+                            num_key_value_heads=8, head_dim=128, intermediate_size=6144, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                            tie_word_embeddings=True, initializer_range=0.02),
     # OPT: the reference's default body (config/model/default.yaml base_model_name) and the TWIST-1.3B body
     "facebook/opt-125m": dict(model_type="opt", num_hidden_layers=12, hidden_size=768, num_attention_heads=12, ffn_dim=3072,
                               max_position_embeddings=2048, init_std=0.02, tie_word_embeddings=True),
@@ -50,6 +59,7 @@ KNOWN_BASE_CONFIGS = {
 }
 
 ARCH_QWEN2, ARCH_OPT = 0, 1
+ARCH_QWEN3 = 3  # 2 is not a family (the engine refuses it)
 
 
 _HF_DIM_KEYS = ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "head_dim",
@@ -114,19 +124,29 @@ def _opt_base_config(c: dict) -> dict:
 
 
 def base_config_from_hf(c: dict) -> dict:
-    """Engine-side `base_config` from a HuggingFace Qwen2 or OPT config dict (a text-LM `config.json`, or the `base_config`
-    object the reference's UnitLMConfig serialises, unit_lm.py:63-73). transformers 4.x stores `rope_theta` at the top
-    level, 5.x under `rope_parameters`. OPT configs keep model_type "opt" in the result."""
+    """Engine-side `base_config` from a HuggingFace Qwen2, Qwen3 or OPT config dict (a text-LM `config.json`, or the
+    `base_config` object the reference's UnitLMConfig serialises, unit_lm.py:63-73). transformers 4.x stores `rope_theta` at
+    the top level, 5.x under `rope_parameters`. OPT and Qwen3 configs keep their model_type ("opt", "qwen3") in the result.
+    Qwen3 (dense only: `qwen3_moe` is refused): no q/k/v bias (`attention_bias=True` is refused), full attention in every
+    layer, `head_dim` from the config (hidden_size // num_attention_heads when absent)."""
     mt = c.get("model_type", "qwen2")
     if mt == "opt":
         return _opt_base_config(c)
-    if mt not in ("qwen2",):
-        raise ValueError(f"the engine implements the Qwen2 and OPT decoder families only (model_type={mt!r})")
+    if mt not in ("qwen2", "qwen3"):
+        raise ValueError(f"the engine implements the Qwen2 and OPT decoder families, and Qwen3, only (model_type={mt!r})")
     if c.get("hidden_act", "silu") != "silu":
         raise ValueError(f"unsupported hidden_act {c.get('hidden_act')!r}")
     if c.get("use_sliding_window"):
         raise ValueError("sliding-window attention is not supported")
     out = {k: c[k] for k in _HF_DIM_KEYS if k in c and c[k] is not None}
+    if mt == "qwen3":
+        if c.get("attention_bias"):
+            raise ValueError("Qwen3 with attention_bias=True is not supported (the engine's Qwen3 layers have no q/k/v bias)")
+        other = sorted({str(t) for t in (c.get("layer_types") or []) if t != "full_attention"})
+        if other:
+            raise ValueError(f"Qwen3 layer_types other than 'full_attention' are not supported: {other}")
+        out["model_type"] = "qwen3"
+        out.setdefault("head_dim", int(c["hidden_size"]) // int(c["num_attention_heads"]))
     rp = c.get("rope_parameters") or c.get("rope_scaling") or {}
     if "rope_theta" not in out and isinstance(rp, dict) and rp.get("rope_theta") is not None:
         out["rope_theta"] = rp["rope_theta"]
@@ -241,11 +261,15 @@ class UnitLMConfig:
     def is_opt(self) -> bool:
         return self.base_config.get("model_type") == "opt"
 
+    @property
+    def is_qwen3(self) -> bool:
+        return self.base_config.get("model_type") == "qwen3"
+
     def engine_arch(self) -> Tuple[int, int]:
-        """(arch, n_positions) of slam_engine_create_arch: Qwen2 = (0, 0), OPT = (1, max_position_embeddings)."""
+        """(arch, n_positions) of slam_engine_create_arch: Qwen2 = (0, 0), OPT = (1, max_position_embeddings), Qwen3 = (3, 0)."""
         if self.is_opt:
             return ARCH_OPT, int(self.base_config["max_position_embeddings"])
-        return ARCH_QWEN2, 0
+        return (ARCH_QWEN3 if self.is_qwen3 else ARCH_QWEN2), 0
 
     @property
     def dropout(self) -> float:
@@ -389,10 +413,14 @@ class UnitLM(TokenLM):
             km[p + "self_attn.q_proj.weight"] = (o, (nH * hd, H))
             km[p + "self_attn.k_proj.weight"] = (o + nH * hd * H, (nKV * hd, H))
             km[p + "self_attn.v_proj.weight"] = (o + (nH + nKV) * hd * H, (nKV * hd, H))
-            o = t[q + "bqkv"].offset
-            km[p + "self_attn.q_proj.bias"] = (o, (nH * hd,))
-            km[p + "self_attn.k_proj.bias"] = (o + nH * hd, (nKV * hd,))
-            km[p + "self_attn.v_proj.bias"] = (o + (nH + nKV) * hd, (nKV * hd,))
+            if self.config.is_qwen3:  # no q/k/v bias; one RMSNorm weight over head_dim for the q heads, one for the k heads
+                km[p + "self_attn.q_norm.weight"] = (t[q + "q_norm"].offset, (hd,))
+                km[p + "self_attn.k_norm.weight"] = (t[q + "k_norm"].offset, (hd,))
+            else:
+                o = t[q + "bqkv"].offset
+                km[p + "self_attn.q_proj.bias"] = (o, (nH * hd,))
+                km[p + "self_attn.k_proj.bias"] = (o + nH * hd, (nKV * hd,))
+                km[p + "self_attn.v_proj.bias"] = (o + (nH + nKV) * hd, (nKV * hd,))
             km[p + "self_attn.o_proj.weight"] = (t[q + "wo"].offset, (H, nH * hd))
             o = t[q + "wgu"].offset  # rows interleaved in blocks of 32 gate / 32 up (slam_engine.h)
             km[p + "mlp.gate_proj.weight"] = (o, (I, H), 0)
@@ -631,7 +659,7 @@ class UnitLM(TokenLM):
         return missing, extra
 
     def load_hf_text_lm(self, path: str):
-        """TWIST initialisation (unit_lm.py:94-102): every weight of a local HuggingFace Qwen2 text LM, embedding rows
+        """TWIST initialisation (unit_lm.py:94-102): every weight of a local HuggingFace Qwen2 / Qwen3 / OPT text LM, embedding rows
         resized to vocab_size (an untied text LM's `lm_head` likewise). The text LM must tie or untie its head as the
         model does: a mismatch would drop an untied `lm_head` silently, or leave one at its random initialisation."""
         with open(os.path.join(path, "config.json")) as f:
@@ -642,8 +670,11 @@ class UnitLM(TokenLM):
         want = base_config_from_hf(c)
         if want.get("model_type") != self.config.base_config.get("model_type"):
             raise ValueError(f"text LM model_type {c.get('model_type')!r} does not match the model's")
-        for k in ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "intermediate_size",
-                  "max_position_embeddings"):
+        keys = ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "intermediate_size",
+                "max_position_embeddings")
+        if self.config.is_qwen3:
+            keys += ("head_dim",)  # a field of its own there
+        for k in keys:
             if want.get(k) != self.config.base_config.get(k):
                 raise ValueError(f"text LM {k}={want.get(k)} != model {k}={self.config.base_config.get(k)}")
         self.load_state_dict(read_hf_weights(path), strict=True)
@@ -1332,11 +1363,11 @@ class UnitLM(TokenLM):
         if "base_config" in c:
             base = c["base_config"]
             name = c.get("base_model_name", "local")
-        elif c.get("model_type") == "qwen2" or (c.get("model_type") == "opt" and all(
+        elif c.get("model_type") in ("qwen2", "qwen3") or (c.get("model_type") == "opt" and all(
                 k in c for k in ("num_hidden_layers", "hidden_size", "num_attention_heads", "ffn_dim", "max_position_embeddings"))):
             base, name = c, path
         else:
-            raise ValueError(f"{path}/config.json is neither a UnitLM config (no `base_config`) nor a complete Qwen2 or OPT "
+            raise ValueError(f"{path}/config.json is neither a UnitLM config (no `base_config`) nor a complete Qwen2, Qwen3 or OPT "
                              f"config (model_type={c.get('model_type')!r})")
         if not (isinstance(name, str) and (name in KNOWN_BASE_CONFIGS or os.path.isdir(name))):
             name = "local"  # e.g. a hub id or a path of the machine that wrote the checkpoint: the dims are in base_config
