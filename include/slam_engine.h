@@ -221,7 +221,9 @@ int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t*
  * either chosen by the caller from the logits or on the device by slam_sample_tokens (below; top_k 1 .. 256, reproducible
  * per row); n sampled continuations per prompt from one prefill (slam_kv_repeat), and the model's own log-probability of
  * every chosen token (slam_token_logprobs, below); prompts prefilled in chunks whose size, not the prompt length, sets the
- * workspace, and k tokens per row appended to a live cache (slam_extend). No beam search, no repetition penalty, no OPT. */
+ * workspace, and k tokens per row appended to a live cache (slam_extend); bans that depend on a row's own history - no
+ * repeated n-gram, multi-token bad words, no EOS yet - on the device (slam_constrain_scores, below). No beam search, no
+ * repetition penalty, no OPT. */
 size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity);
 int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity);
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
@@ -298,6 +300,62 @@ size_t slam_sample_workspace_bytes(int32_t B, int32_t vocab, int32_t top_k);
 int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
                        const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
                        int64_t out_stride, void* ws, size_t ws_bytes, slam_stream_t stream);
+
+/* ---- per-row bans that depend on the row's own history (HF's no_repeat_ngram_size, multi-token bad_words_ids,
+ * min_new_tokens / min_length, begin_suppress_tokens), between the logits and slam_sample_tokens ------------------------------
+ * slam_constrain_scores needs no engine. It reads fp32 logits [B][vocab] (row stride vocab, 4-byte aligned; odd vocabularies
+ * are fine) and writes scores [B][vocab] of the same layout:
+ *   scores[b][i] = -inf for every token i that row b bans, the BITS of logits[b][i] (NaN and +-inf included) everywhere else.
+ * scores may be the same pointer as logits: then only the bans are written. (slam_token_logprobs is defined on the raw
+ * logits, so a caller who wants log-probs gives scores a buffer of its own, samples from scores and scores the logits.)
+ * The history h of row b at step s = desc->step (s new tokens exist) is, with pb = b / n_per_prompt and
+ * pl = prompt_len[pb] clamped to [0, prompt_stride]:
+ *   h[0 .. pl)        = prompt[pb * prompt_stride + 0 .. pl)   (right-padded prompt ids; pads are not history)
+ *   h[pl .. pl + s)   = new_tokens[b * new_stride + 0 .. s)    (the `out` buffer of slam_sample_tokens)
+ * and Lh = pl + s. prompt_len is a copy of the lengths taken BEFORE decoding: slam_decode_step increments its lens.
+ * Bans, all restating transformers' logits processors on h:
+ *   n-gram     n = no_repeat_ngram >= 1 (0 = off): nothing when Lh < n; else, with p = h[Lh - n + 1 .. Lh) (the last n - 1
+ *              tokens), every j in 0 .. Lh - n with h[j .. j + n - 1) == p bans h[j + n - 1]. n = 1 bans every token seen.
+ *   sequences  n_seqs bad word sequences, sequence q = seq_tokens[seq_offsets[q] .. seq_offsets[q + 1]), of length Lw: bans
+ *              its last token when 2 <= Lw <= Lh and the last Lw - 1 history tokens equal its first Lw - 1. A sequence with
+ *              Lw < 2, Lw > SLAM_CONSTRAIN_MAX_SEQ_LEN or offsets outside [0, n_seq_tokens] is ignored (single-token bad
+ *              words belong in the sampler's banned[vocab]).
+ *   ban_eos    (0 / 1, decided per step by the caller: s < min_new_tokens, or prompt width + s < min_length) bans
+ *              eos_ids[0 .. n_eos).
+ *   begin      begin_ids[0 .. n_begin) are banned when s == 0.
+ * A history token or list entry outside [0, vocab) bans nothing and nothing is written for it (it still takes part in the
+ * comparisons). A row with done && done[b] is copied, not edited. A row's result depends on (its logits, its history, the
+ * description) alone - not on B, the row's index or the launch shape - and is the same bits on every run: behind the copy
+ * the only stores are of one constant, so there are no atomics. One launch: grid (chunks of 2048 scores, B); a block copies
+ * its chunk (16-byte accesses where logits and scores are equally aligned, 4-byte at the ragged ends and otherwise), then
+ * scans the history and stores the bans that fall inside its own chunk.
+ * prompt int64 [B / n_per_prompt][prompt_stride]; prompt_len int32 [B / n_per_prompt]; new_tokens int64 [B][new_stride]
+ * (nullable when step == 0); done uint8 [B], nullable; eos_ids int32 [n_eos]; begin_ids int32 [n_begin]; seq_tokens int32
+ * [n_seq_tokens]; seq_offsets int32 [n_seqs + 1] - all device memory.
+ * SLAM_EINVAL, before anything is launched or dereferenced on the device: logits, scores, desc, prompt or prompt_len NULL;
+ * B <= 0 or B > 65535; vocab <= 0; no_repeat_ngram < 0; n_per_prompt < 1; B % n_per_prompt != 0; ban_eos other than 0 / 1;
+ * step or prompt_stride outside 0 .. 2^30; step > 0 with new_tokens NULL or new_stride < step; n_eos outside 0 .. 16, n_begin
+ * outside 0 .. SLAM_CONSTRAIN_MAX_BEGIN, n_seqs outside 0 .. SLAM_CONSTRAIN_MAX_SEQS, n_seq_tokens outside
+ * 0 .. SLAM_CONSTRAIN_MAX_SEQS * SLAM_CONSTRAIN_MAX_SEQ_LEN; a positive count without its list(s); logits, scores or an
+ * int32 list not 4-byte aligned, prompt or new_tokens not 8-byte aligned. */
+#define SLAM_CONSTRAIN_MAX_SEQS 256
+#define SLAM_CONSTRAIN_MAX_SEQ_LEN 16
+#define SLAM_CONSTRAIN_MAX_BEGIN 256
+typedef struct SlamConstrainDesc {
+  int32_t step;            /* s: new tokens that exist; 0 for the token drawn from the prefill logits */
+  int32_t no_repeat_ngram; /* n >= 1, 0 = off */
+  int32_t n_per_prompt;    /* rows b n .. b n + n - 1 share prompt b */
+  int32_t prompt_stride;   /* row stride of prompt, in tokens */
+  int32_t ban_eos;         /* 0 / 1 */
+  int32_t n_eos;           /* 0 .. 16 */
+  int32_t n_begin;         /* 0 .. SLAM_CONSTRAIN_MAX_BEGIN */
+  int32_t n_seqs;          /* 0 .. SLAM_CONSTRAIN_MAX_SEQS */
+  int32_t n_seq_tokens;    /* length of seq_tokens */
+} SlamConstrainDesc;
+int slam_constrain_scores(const float* logits, float* scores, int32_t B, int32_t vocab, const SlamConstrainDesc* desc,
+                          const int64_t* prompt, const int32_t* prompt_len, const int64_t* new_tokens, int64_t new_stride,
+                          const uint8_t* done, const int32_t* eos_ids, const int32_t* begin_ids, const int32_t* seq_tokens,
+                          const int32_t* seq_offsets, slam_stream_t stream);
 
 /* ---- the log-probability of the chosen token (what a second forward + log_softmax + gather would give) ----------------------
  * slam_token_logprobs needs no engine and runs right behind slam_sample_tokens on the same stream, on the same logits. For

@@ -23,6 +23,10 @@
 //    chunk's K / V first, in a launch of its own; attn_extend then reads keys from the cache only, 16 queries x all heads of a
 //    KV group per block on v_mfma_f32_16x16x32_bf16, scores formed transposed so that P feeds the PV product from the registers
 //    it was computed in. Key splits are merged in split order by attn_extend_combine.
+//  * constrain_scores (slam_constrain_scores): -inf for the tokens a row's own history bans (no repeated n-gram, bad word
+//    sequences, EOS ids while the row is too short, begin-suppressed ids), the logits' bits elsewhere. Grid (chunks, B): a
+//    block copies its chunk (not in place), then scans the history and stores the bans inside its own chunk. One constant is
+//    stored, so equal stores may race: no atomics, no ordering between blocks.
 //  * token_logprobs (slam_token_logprobs): the log-softmax of the raw logits row at one token. Chunks of SP_CHUNK scores; in a
 //    chunk thread t takes scores t, t + 256, .. in that order, the 64 lanes of a wave are summed by the xor butterfly 32, 16,
 //    .., 1, the four waves in wave order; chunks are combined in chunk order, one fused multiply-add each. Rows above one chunk
@@ -1001,6 +1005,89 @@ __global__ __launch_bounds__(SP_THREADS) void logprob_finish_kernel(const float*
   if (finished) finished[b] = done ? done[b] : (uint8_t)0;
 }
 
+// ---- per-row bans between the logits and the token choice (slam_constrain_scores) -------------------------------------------
+// grid (chunks of SP_CHUNK, B). The block copies its chunk of the row bit for bit (skipped in place), then scans the row's
+// history and stores -inf for the bans that fall inside its own chunk: no block writes into another's chunk, so there is no
+// ordering between blocks, and the only stores behind the copy are of one constant (equal stores may race, harmlessly).
+struct ConstrainParams {
+  int vocab, step, ngram, n_per_prompt, prompt_stride, ban_eos, n_eos, n_begin, n_seqs, n_seq_tokens;
+  long long new_stride;
+};
+
+// h[j] of a row: the prompt's real tokens, then the new ones
+struct ConstrainHistory {
+  const int64_t* prompt;
+  const int64_t* fresh;
+  int pl;
+  SLAM_DEVICE long long at(int j) const { return j < pl ? prompt[j] : fresh[j - pl]; }
+};
+
+__global__ __launch_bounds__(SP_THREADS) void constrain_scores_kernel(
+    const float* logits, float* scores, const int64_t* __restrict__ prompt, const int* __restrict__ prompt_len,
+    const int64_t* __restrict__ fresh, const uint8_t* __restrict__ done, const int* __restrict__ eos_ids,
+    const int* __restrict__ begin_ids, const int* __restrict__ seq_tokens, const int* __restrict__ seq_offsets,
+    ConstrainParams P) {
+  const int ch = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+  const int c0 = ch * SP_CHUNK;
+  const int n = min(SP_CHUNK, P.vocab - c0);
+  float* srow = scores + (size_t)b * P.vocab;
+  if (logits != scores) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(logits + (size_t)b * P.vocab + c0);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(srow + c0);
+    int head = 0, nv = 0;
+    if ((((uintptr_t)src ^ (uintptr_t)dst) & 15) == 0) {  // equally aligned: 16-byte body, 4-byte ragged ends
+      head = (int)((4u - (uint32_t)(((uintptr_t)src >> 2) & 3u)) & 3u);
+      if (head > n) head = n;
+      nv = (n - head) >> 2;
+    }
+    if (t < head) dst[t] = src[t];
+    const uint4* sv = reinterpret_cast<const uint4*>(src + head);
+    uint4* dv = reinterpret_cast<uint4*>(dst + head);
+    for (int v = t; v < nv; v += SP_THREADS) dv[v] = sv[v];
+    for (int i = head + 4 * nv + t; i < n; i += SP_THREADS) dst[i] = src[i];
+    __syncthreads();  // the bans below land on words other threads of this block copied
+  }
+  if (done && done[b]) return;
+  const int pb = b / P.n_per_prompt;
+  ConstrainHistory h;
+  h.pl = min(max(prompt_len[pb], 0), P.prompt_stride);
+  h.prompt = prompt + (size_t)pb * P.prompt_stride;
+  h.fresh = fresh + (long long)b * P.new_stride;  // dereferenced only for step > 0
+  const int Lh = h.pl + P.step;
+  const long long lo = c0, hi = c0 + n;  // a ban outside [lo, hi) is another block's, or nobody's
+  const int ng = P.ngram;
+  if (ng > 0 && Lh >= ng) {
+    const int p0 = Lh - ng + 1;  // the last ng - 1 tokens
+    for (int j = t; j <= Lh - ng; j += SP_THREADS) {
+      bool eq = true;
+      for (int k = 0; k < ng - 1 && eq; ++k) eq = h.at(j + k) == h.at(p0 + k);
+      if (!eq) continue;
+      const long long tok = h.at(j + ng - 1);
+      if (tok >= lo && tok < hi) srow[tok] = -INFINITY;
+    }
+  }
+  for (int i = t; i < P.n_seqs; i += SP_THREADS) {
+    const int o0 = seq_offsets[i], o1 = seq_offsets[i + 1];
+    if (o0 < 0 || o1 > P.n_seq_tokens || o1 - o0 < 2 || o1 - o0 > slam::CONSTRAIN_MAX_SEQ_LEN) continue;
+    const int Lw = o1 - o0;
+    if (Lw > Lh) continue;
+    bool eq = true;
+    for (int k = 0; k < Lw - 1 && eq; ++k) eq = h.at(Lh - (Lw - 1) + k) == (long long)seq_tokens[o0 + k];
+    if (!eq) continue;
+    const long long tok = seq_tokens[o1 - 1];
+    if (tok >= lo && tok < hi) srow[tok] = -INFINITY;
+  }
+  if (P.ban_eos && t < P.n_eos) {
+    const long long tok = eos_ids[t];
+    if (tok >= lo && tok < hi) srow[tok] = -INFINITY;
+  }
+  if (P.step == 0)
+    for (int i = t; i < P.n_begin; i += SP_THREADS) {
+      const long long tok = begin_ids[i];
+      if (tok >= lo && tok < hi) srow[tok] = -INFINITY;
+    }
+}
+
 // ---- fused head + row statistics (slam_op_score_rows, slam_extend_score) -----------------------------------------------------
 // x[m][i] = the fp32 accumulator of X row m against W row i; it lives in the accumulator registers only. The vocabulary is
 // cut into chunks of SCORE_CHUNK columns, a chunk into SCORE_GROUPS groups of 64 consecutive columns. One block = 64 rows x
@@ -1364,6 +1451,35 @@ int sample_tokens(const SampleArgs& a, hipStream_t st) {
     sample_select_kernel<<<dim3(P.nch, a.B), SP_THREADS, 0, st>>>(a.logits, a.banned, a.done, P, ws);
     sample_finish_kernel<false><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws);
   }
+  return (int)hipGetLastError();
+}
+
+int constrain_scores(const ConstrainArgs& a, hipStream_t st) {
+  if (!a.logits || !a.scores || !a.prompt || !a.prompt_len || a.B <= 0 || a.B > 65535 || a.vocab <= 0) return -1;
+  if (((uintptr_t)a.logits | (uintptr_t)a.scores | (uintptr_t)a.prompt_len) & 3 || ((uintptr_t)a.prompt | (uintptr_t)a.fresh) & 7)
+    return -1;
+  if (a.step < 0 || a.step > CONSTRAIN_MAX_HISTORY || a.prompt_stride < 0 || a.prompt_stride > CONSTRAIN_MAX_HISTORY) return -1;
+  if (a.step > 0 && (!a.fresh || a.new_stride < a.step)) return -1;
+  if (a.ngram < 0 || a.n_per_prompt < 1 || a.B % a.n_per_prompt) return -1;
+  if (a.n_eos < 0 || a.n_eos > 16 || (a.n_eos > 0 && (!a.eos_ids || ((uintptr_t)a.eos_ids & 3)))) return -1;
+  if (a.n_begin < 0 || a.n_begin > CONSTRAIN_MAX_BEGIN || (a.n_begin > 0 && (!a.begin_ids || ((uintptr_t)a.begin_ids & 3)))) return -1;
+  if (a.n_seqs < 0 || a.n_seqs > CONSTRAIN_MAX_SEQS || a.n_seq_tokens < 0 || a.n_seq_tokens > CONSTRAIN_MAX_SEQS * CONSTRAIN_MAX_SEQ_LEN)
+    return -1;
+  if (a.n_seqs > 0 && (!a.seq_tokens || !a.seq_offsets || (((uintptr_t)a.seq_tokens | (uintptr_t)a.seq_offsets) & 3))) return -1;
+  ConstrainParams P;
+  P.vocab = a.vocab;
+  P.step = a.step;
+  P.ngram = a.ngram;
+  P.n_per_prompt = a.n_per_prompt;
+  P.prompt_stride = a.prompt_stride;
+  P.ban_eos = a.ban_eos ? 1 : 0;
+  P.n_eos = a.n_eos;
+  P.n_begin = a.n_begin;
+  P.n_seqs = a.n_seqs;
+  P.n_seq_tokens = a.n_seq_tokens;
+  P.new_stride = a.new_stride;
+  constrain_scores_kernel<<<dim3(sample_chunks(a.vocab), a.B), SP_THREADS, 0, st>>>(
+      a.logits, a.scores, a.prompt, a.prompt_len, a.fresh, a.done, a.eos_ids, a.begin_ids, a.seq_tokens, a.seq_offsets, P);
   return (int)hipGetLastError();
 }
 

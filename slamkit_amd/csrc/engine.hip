@@ -2555,6 +2555,40 @@ int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint
   return sample_tokens(a, (hipStream_t)stream);
 }
 
+int slam_constrain_scores(const float* logits, float* scores, int32_t B, int32_t vocab, const SlamConstrainDesc* desc,
+                          const int64_t* prompt, const int32_t* prompt_len, const int64_t* new_tokens, int64_t new_stride,
+                          const uint8_t* done, const int32_t* eos_ids, const int32_t* begin_ids, const int32_t* seq_tokens,
+                          const int32_t* seq_offsets, slam_stream_t stream) {
+  if (!desc || (desc->ban_eos != 0 && desc->ban_eos != 1)) return SLAM_EINVAL;
+  static_assert(SLAM_CONSTRAIN_MAX_SEQS == CONSTRAIN_MAX_SEQS && SLAM_CONSTRAIN_MAX_SEQ_LEN == CONSTRAIN_MAX_SEQ_LEN &&
+                    SLAM_CONSTRAIN_MAX_BEGIN == CONSTRAIN_MAX_BEGIN,
+                "the header's caps are the kernels'");
+  ConstrainArgs a;  // constrain_scores refuses the rest (-1 = SLAM_EINVAL) before it launches anything
+  a.logits = logits;
+  a.scores = scores;
+  a.B = B;
+  a.vocab = vocab;
+  a.step = desc->step;
+  a.ngram = desc->no_repeat_ngram;
+  a.n_per_prompt = desc->n_per_prompt;
+  a.prompt_stride = desc->prompt_stride;
+  a.ban_eos = desc->ban_eos;
+  a.n_eos = desc->n_eos;
+  a.n_begin = desc->n_begin;
+  a.n_seqs = desc->n_seqs;
+  a.n_seq_tokens = desc->n_seq_tokens;
+  a.prompt = prompt;
+  a.prompt_len = prompt_len;
+  a.fresh = new_tokens;
+  a.new_stride = new_stride;
+  a.done = done;
+  a.eos_ids = eos_ids;
+  a.begin_ids = begin_ids;
+  a.seq_tokens = seq_tokens;
+  a.seq_offsets = seq_offsets;
+  return constrain_scores(a, (hipStream_t)stream);
+}
+
 size_t slam_token_logprobs_workspace_bytes(int32_t B, int32_t vocab) { return token_logprobs_workspace_bytes(B, vocab); }
 int slam_token_logprobs(const float* logits, int32_t B, int32_t vocab, const int64_t* tokens, const uint8_t* done,
                         uint8_t* finished, float* out, int64_t out_stride, int32_t column, void* ws, size_t ws_bytes,

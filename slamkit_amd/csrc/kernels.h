@@ -314,6 +314,29 @@ struct SampleArgs {
 };
 size_t sample_workspace_bytes(int B, int vocab, int top_k);  // host only
 int sample_tokens(const SampleArgs& a, hipStream_t st);
+// scores[b][i] = -inf for the tokens row b's history bans, the bits of logits[b][i] elsewhere (include/slam_engine.h:
+// slam_constrain_scores). scores may be logits: then only the bans are written.
+constexpr int CONSTRAIN_MAX_SEQS = 256;      // bad word sequences (SLAM_CONSTRAIN_MAX_SEQS)
+constexpr int CONSTRAIN_MAX_SEQ_LEN = 16;    // tokens per sequence (SLAM_CONSTRAIN_MAX_SEQ_LEN)
+constexpr int CONSTRAIN_MAX_BEGIN = 256;     // begin_suppress ids (SLAM_CONSTRAIN_MAX_BEGIN)
+constexpr int CONSTRAIN_MAX_HISTORY = 1 << 30;  // bound of step and of prompt_stride: their sum stays an int
+struct ConstrainArgs {
+  const float* logits = nullptr;
+  float* scores = nullptr;
+  int B = 0, vocab = 0;
+  int step = 0, ngram = 0, n_per_prompt = 1, prompt_stride = 0;
+  int ban_eos = 0, n_eos = 0, n_begin = 0, n_seqs = 0, n_seq_tokens = 0;
+  const int64_t* prompt = nullptr;    // [B / n_per_prompt][prompt_stride], right-padded
+  const int* prompt_len = nullptr;    // [B / n_per_prompt]
+  const int64_t* fresh = nullptr;     // [B][new_stride]: the new tokens; nullable at step 0
+  int64_t new_stride = 0;
+  const uint8_t* done = nullptr;      // nullable: [B], non-zero = the row is copied, not edited
+  const int* eos_ids = nullptr;       // [n_eos]
+  const int* begin_ids = nullptr;     // [n_begin]
+  const int* seq_tokens = nullptr;    // [n_seq_tokens]
+  const int* seq_offsets = nullptr;   // [n_seqs + 1]
+};
+int constrain_scores(const ConstrainArgs& a, hipStream_t st);
 // n samples per prompt: rows 0 .. B-1 of the cache kv (L x { K, V } x [bmax][nKV][cap][head_dim]), of lens and of the nullable
 // logits [.][vocab] fan out in place to rows b n .. b n + n - 1; only lens[b] keys of a row are copied. One launch per source
 // row in descending b (hazard-free for every (B, n): decode.hip's header). kv_bound: host bound of lens.

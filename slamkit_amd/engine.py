@@ -38,6 +38,18 @@ class SlamSampleDesc(C.Structure):
     ]
 
 
+class SlamConstrainDesc(C.Structure):
+    _fields_ = [
+        ("step", C.c_int32), ("no_repeat_ngram", C.c_int32), ("n_per_prompt", C.c_int32), ("prompt_stride", C.c_int32),
+        ("ban_eos", C.c_int32), ("n_eos", C.c_int32), ("n_begin", C.c_int32), ("n_seqs", C.c_int32), ("n_seq_tokens", C.c_int32),
+    ]
+
+
+CONSTRAIN_MAX_SEQS = 256     # SLAM_CONSTRAIN_MAX_SEQS: multi-token bad word sequences per call
+CONSTRAIN_MAX_SEQ_LEN = 16   # SLAM_CONSTRAIN_MAX_SEQ_LEN: tokens per sequence
+CONSTRAIN_MAX_BEGIN = 256    # SLAM_CONSTRAIN_MAX_BEGIN: begin_suppress ids
+
+
 def header_symbols() -> List[str]:
     """Every function name declared in include/slam_engine.h (used by the export test)."""
     hdr = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "slam_engine.h")
@@ -90,6 +102,7 @@ def load_library(path: Optional[str] = None):
         "slam_decode_step": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "slam_sample_workspace_bytes": (sz, [i32, i32, i32]),
         "slam_sample_tokens": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "slam_constrain_scores": (C.c_int, [vp, vp, i32, i32, C.POINTER(SlamConstrainDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
         "slam_kv_repeat": (C.c_int, [vp, i32, vp, vp, vp]),
         "slam_extend": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
         "slam_extend_score": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
@@ -223,6 +236,23 @@ def sample_tokens(logits, desc: SlamSampleDesc, next_ids, ws, banned=None, row_i
                                           stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_sample_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+def constrain_scores(logits, scores, desc: SlamConstrainDesc, prompt, prompt_len, new=None, done=None, eos_ids=None,
+                     begin_ids=None, seq_tokens=None, seq_offsets=None, stream: Optional[int] = None):
+    """slam_constrain_scores: scores[b] (fp32 [B, vocab]; may be `logits` itself) = row b of the fp32 logits with -inf at every
+    token that row's history bans under `desc` (no-repeat n-gram, bad word sequences, ban_eos, begin_suppress). prompt int64
+    [B / n_per_prompt, stride] right-padded, prompt_len int32 (a copy taken before decoding), new int64 [B, stride] (the
+    sampler's out buffer; columns < desc.step are read), done uint8 [B], eos_ids / begin_ids / seq_tokens / seq_offsets int32:
+    device tensors, None where unused. desc.prompt_stride is set from `prompt`. Only enqueues work."""
+    B, V = logits.shape
+    desc.prompt_stride = int(prompt.stride(0))
+    rc = load_library().slam_constrain_scores(_ptr(logits), _ptr(scores), B, V, C.byref(desc), _ptr(prompt), _ptr(prompt_len),
+                                             _ptr(new), new.stride(0) if new is not None else 0, _ptr(done), _ptr(eos_ids),
+                                             _ptr(begin_ids), _ptr(seq_tokens), _ptr(seq_offsets),
+                                             stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_constrain_scores failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 def token_logprobs_workspace_bytes(B: int, vocab: int) -> int:

@@ -340,6 +340,87 @@ def _warp(scores: torch.Tensor, temperature: float, top_k: int, top_p: float) ->
     return scores
 
 
+class _ConstraintPlan(NamedTuple):
+    """generate's history-dependent bans, validated on the host (no device): what slam_constrain_scores will be asked for."""
+    ngram: int
+    min_new: int
+    min_length: int
+    begin: List[int]
+    seqs: List[List[int]]   # bad word sequences of two tokens and more
+    single: List[int]       # single-token bad words + suppress_tokens: the vocabulary-wide mask
+    eos: List[int]
+    active: bool            # some step needs the constrain kernel
+
+
+def _constraint_plan(no_repeat_ngram_size, min_new_tokens, min_length, begin_suppress, suppress, bad, eos) -> _ConstraintPlan:
+    def count(v, name):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be an int >= 0 (got {v!r})")
+        return v
+
+    ngram = count(no_repeat_ngram_size, "no_repeat_ngram_size")
+    min_new = count(min_new_tokens, "min_new_tokens")
+    min_len = count(min_length, "min_length")
+    begin = [int(t) for t in begin_suppress]
+    if len(begin) > E.CONSTRAIN_MAX_BEGIN:
+        raise ValueError(f"begin_suppress_tokens: at most {E.CONSTRAIN_MAX_BEGIN} ids (got {len(begin)})")
+    single = [int(t) for t in suppress]
+    seqs = []
+    for w in bad:
+        w = [int(t) for t in w]
+        if len(w) < 1:
+            raise ValueError("bad_words_ids: an entry needs at least one token")
+        if len(w) > E.CONSTRAIN_MAX_SEQ_LEN:
+            raise ValueError(f"bad_words_ids: an entry has at most {E.CONSTRAIN_MAX_SEQ_LEN} tokens (got {len(w)})")
+        if len(w) == 1:
+            single.append(w[0])
+        else:
+            seqs.append(w)
+    if len(seqs) > E.CONSTRAIN_MAX_SEQS:
+        raise ValueError(f"bad_words_ids: at most {E.CONSTRAIN_MAX_SEQS} multi-token entries (got {len(seqs)})")
+    eos = [int(t) for t in eos]
+    if (min_new > 0 or min_len > 0) and len(eos) > 16:
+        raise ValueError(f"min_new_tokens / min_length take at most 16 EOS ids (got {len(eos)})")
+    active = ngram > 0 or bool(seqs) or bool(begin) or (bool(eos) and (min_new > 0 or min_len > 0))
+    return _ConstraintPlan(ngram, min_new, min_len, begin, seqs, single, eos, active)
+
+
+class _Constrainer:
+    """The device side of a _ConstraintPlan for one generate call: the lists, the prompts and the scores buffer. apply() is one
+    slam_constrain_scores launch, or none when the step has nothing to ban."""
+
+    def __init__(self, plan: _ConstraintPlan, ids, prompt_len, t_in: int, nret: int, new, keep_logits: bool, dev):
+        def i32(v):
+            return torch.tensor(v, dtype=torch.int32, device=dev) if len(v) else None
+
+        self.plan, self.ids, self.prompt_len, self.t_in, self.new = plan, ids, prompt_len, t_in, new
+        self.eos, self.begin = i32(plan.eos), i32(plan.begin)
+        self.seq_tokens = i32([t for w in plan.seqs for t in w])
+        off = [0]
+        for w in plan.seqs:
+            off.append(off[-1] + len(w))
+        self.seq_offsets = i32(off) if plan.seqs else None
+        self.desc = E.SlamConstrainDesc(step=0, no_repeat_ngram=plan.ngram, n_per_prompt=nret, prompt_stride=0, ban_eos=0,
+                                        n_eos=len(plan.eos), n_begin=len(plan.begin), n_seqs=len(plan.seqs),
+                                        n_seq_tokens=off[-1])
+        self.keep_logits = keep_logits  # slam_token_logprobs reads the raw logits: the bans go into a buffer of their own
+        self.scores = None
+
+    def apply(self, logits, step: int, done):
+        p = self.plan
+        ban_eos = bool(p.eos) and (step < p.min_new or self.t_in + step < p.min_length)
+        if not (p.ngram > 0 or p.seqs or ban_eos or (step == 0 and p.begin)):
+            return logits
+        if self.keep_logits and self.scores is None:
+            self.scores = torch.empty_like(logits)
+        out = self.scores if self.keep_logits else logits
+        self.desc.step = step
+        self.desc.ban_eos = int(ban_eos)
+        E.constrain_scores(logits, out, self.desc, self.ids, self.prompt_len, self.new, done, self.eos, self.begin,
+                           self.seq_tokens, self.seq_offsets)
+        return out
+
+
 class UnitLM(TokenLM):
     """unit_lm.py:82-212 on the HIP engine."""
     base_model_prefix = "lm"
@@ -984,7 +1065,9 @@ class UnitLM(TokenLM):
                  top_p: Optional[float] = None, eos_token_id=None, pad_token_id: Optional[int] = None,
                  sampler: Optional[str] = None, sample_ids: Optional[torch.Tensor] = None,
                  num_return_sequences: Optional[int] = None, return_logprobs: bool = False,
-                 prefill_chunk: Optional[int] = None, **kwargs):
+                 prefill_chunk: Optional[int] = None, no_repeat_ngram_size: Optional[int] = None,
+                 min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
+                 begin_suppress_tokens: Optional[List[int]] = None, suppress_tokens: Optional[List[int]] = None, **kwargs):
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
@@ -1022,7 +1105,19 @@ class UnitLM(TokenLM):
         `num_return_sequences` and `return_logprobs` follow as before. The workspace is max(B min(T, C), 2 B n) tokens instead
         of max(B T, 2 B n): the chunk, not the prompt length, sets the activation memory. The chunks' attention runs in another
         kernel than the one-shot prefill's, so the logits differ from it by rounding only (within the model tolerance); a
-        token chosen at a near-tie may differ."""
+        token chosen at a near-tie may differ.
+
+        Bans that depend on a row's own history, as HF's logits processors compute them, applied to the fp32 logits before
+        everything else by one HIP launch per step (slam_constrain_scores, include/slam_engine.h) under both samplers:
+        `no_repeat_ngram_size` = n (no n-gram of a row occurs twice; 0 = off), `bad_words_ids` entries of any length >= 1 (a
+        multi-token entry bans its last token behind its prefix; at most 256 such entries of at most 16 tokens, ValueError
+        above), `min_new_tokens` and `min_length` (no EOS id while fewer than min_new_tokens new tokens exist, or while the
+        prompt width as passed plus the new tokens is below min_length), `begin_suppress_tokens` (banned for the first new token,
+        at most 256 ids) and `suppress_tokens` (banned at every step, merged with the single-token bad words). A row's history
+        is its REAL tokens: the prompt without its padding, then its new tokens. HF's windows run over input_ids as passed,
+        left-pad ids included; the two agree unless a window contains a pad id. `return_logprobs` still returns the raw-logit
+        log-probs: the bans are then written into a scores buffer of their own, which only the token choice reads. With every
+        one of these options off, no launch is added and the output is what it was without them."""
         if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
             raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
         if self.config.is_opt:
@@ -1051,9 +1146,11 @@ class UnitLM(TokenLM):
         pad = pick(pad_token_id, "pad_token_id", self.config.pad_token_id)
         if pad is None:
             pad = eos[0] if eos else 0
-        bad = pick(bad_words_ids, "bad_words_ids", None) or []
-        if any(len(w) != 1 for w in bad):
-            raise ValueError("bad_words_ids: only single-token entries are supported")
+        plan = _constraint_plan(pick(no_repeat_ngram_size, "no_repeat_ngram_size", 0), pick(min_new_tokens, "min_new_tokens", 0),
+                                pick(min_length, "min_length", 0), pick(begin_suppress_tokens, "begin_suppress_tokens", None) or [],
+                                pick(suppress_tokens, "suppress_tokens", None) or [],
+                                pick(bad_words_ids, "bad_words_ids", None) or [], eos)
+        bad = [[t] for t in plan.single]  # the vocabulary-wide mask; the history-dependent bans are plan's
         if inputs is None:
             inputs = input_ids
         if inputs is None or inputs.dim() != 2:
@@ -1116,9 +1213,11 @@ class UnitLM(TokenLM):
             lp = (torch.empty(BN, max_new_tokens, dtype=torch.float32, device=dev), torch.zeros(BN, dtype=torch.uint8, device=dev),
                   torch.empty(E.token_logprobs_workspace_bytes(BN, V), dtype=torch.uint8, device=dev))
         n = 0
+        # prompt_len: a copy, because slam_decode_step advances lens
+        cons = _Constrainer(plan, ids, lens[:B].clone(), T_in, nret, new, lp is not None, dev) if plan.active else None
         if on_device:
             n = self._sample_on_device(logits, new, ids, lens, T, bad, eos, int(pad), do_sample, top_k, temperature, top_p,
-                                       seed, sample_ids, nret, lp, prefill_chunk)
+                                       seed, sample_ids, nret, lp, prefill_chunk, cons)
         else:
             bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
             g = None
@@ -1130,7 +1229,7 @@ class UnitLM(TokenLM):
                 self.engine.kv_repeat(nret, lens, logits)
             done = torch.zeros(BN, dtype=torch.bool, device=dev)
             for step in range(max_new_tokens):
-                scores = logits
+                scores = logits if cons is None else cons.apply(logits, step, done.view(torch.uint8))
                 if bad_idx is not None:
                     scores = scores.index_fill(1, bad_idx, float("-inf"))
                 if do_sample:
@@ -1299,10 +1398,11 @@ class UnitLM(TokenLM):
             self.engine.extend(ids[:, c0:c0 + w].contiguous(), new_lens, cur, B, w, logits)
 
     def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids,
-                          nret=1, lp=None, prefill_chunk=None):
+                          nret=1, lp=None, prefill_chunk=None, cons=None):
         """The decode loop of generate(sampler="engine"): prefill, sample(step 0), then decode_step(next) / sample(step k). The
         kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written.
-        logits / new have B n rows: the prompts (ids, the first rows of lens) are prefilled once and fanned out (kv_repeat)."""
+        logits / new have B n rows: the prompts (ids, the first rows of lens) are prefilled once and fanned out (kv_repeat).
+        cons (a _Constrainer) puts slam_constrain_scores in front of the sampler; the log-probs keep reading the raw logits."""
         dev = self.device
         B, V = logits.shape
         max_new = new.shape[1]
@@ -1330,7 +1430,8 @@ class UnitLM(TokenLM):
         n = 0
         for step in range(max_new):
             desc.step = step
-            E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+            E.sample_tokens(logits if cons is None else cons.apply(logits, step, done), desc, nxt, ws, banned, row_ids, eos_i,
+                            done, new)
             if lp is not None:
                 E.token_logprobs(logits, nxt, lp[0], step, lp[2], done, lp[1])
             n = step + 1

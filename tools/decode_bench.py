@@ -31,6 +31,11 @@ process after a warm-up of each way, device events, median of 5: one line per wa
 and on the chunked line `ratio` = chunked / one-shot and `logits_rel_rms` (the chunked last-token logits against the one-shot
 ones). --trace-summary also lists the attn_extend / kv_extend_scatter / attn_fwd launches, for the kernel's share from a
 `rocprofv3 --kernel-trace --stats` run of their own.
+--constrain-op times slam_constrain_scores alone at (B, V) = (8, 502), (8, 152167), (64, 152167): a history of 256 prompt + 150
+new tokens per row, no_repeat_ngram 3, device events around 200 back-to-back calls, five rounds alternating `inplace_us`
+(scores is logits: only the bans are written) and `copy_us` (scores in a buffer of its own), with `copy_floor_us` =
+2 B V 4 bytes / 6.3 TB/s. With --sampler S --no-repeat-ngram n: end-to-end greedy generate with sampler S, without and with
+no_repeat_ngram_size = n, alternated rep by rep: one line per setting with `no_repeat_ngram_size`, `generate_s`, `generate_s_all`.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -124,6 +129,63 @@ def e2e_samplers(m, B, P, new, reps, tag, samplers, do_sample):
         print(json.dumps(dict(bench="generate_e2e", model=tag, B=B, prompt=P, new_tokens=new, sampler=s, do_sample=bool(do_sample),
                               generate_s=round(statistics.median(times[s]), 4),
                               generate_s_all=[round(t, 4) for t in times[s]])), flush=True)
+
+
+def e2e_no_repeat(m, B, P, new, reps, tag, sampler, n):
+    """generate_s without and with no_repeat_ngram_size = n, alternated rep by rep."""
+    import torch
+    dev = m.device
+    g = torch.Generator(device=dev).manual_seed(1)
+    ids = torch.randint(2, m.config.vocab_size, (B, P), device=dev, generator=g)
+    kw = dict(input_ids=ids, max_new_tokens=new, eos_token_id=[], sampler=sampler)
+    m._ensure_workspace(B * (-(-(P + new) // 64) * 64))
+    times = {k: [] for k in (0, n)}
+    for k in times:
+        m.generate(no_repeat_ngram_size=k, **kw)  # warm-up
+    for _ in range(reps):
+        for k in times:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.generate(no_repeat_ngram_size=k, **kw)
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    for k in times:
+        print(json.dumps(dict(bench="generate_e2e", model=tag, B=B, prompt=P, new_tokens=new, sampler=sampler, no_repeat_ngram_size=k,
+                              generate_s=round(statistics.median(times[k]), 4),
+                              generate_s_all=[round(t, 4) for t in times[k]])), flush=True)
+
+
+def constrain_op_bench(calls=200, rounds=5, prompt=256, new_tokens=150, n=3):
+    """Device-event time of slam_constrain_scores alone, in place and into a buffer of its own."""
+    import torch
+    from slamkit_amd import engine as E
+    dev = torch.device("cuda")
+    for B, V in ((8, 502), (8, 152167), (64, 152167)):
+        g = torch.Generator(device=dev).manual_seed(V + B)
+        logits = torch.randn(B, V, device=dev, generator=g) * 3.0
+        scores = torch.empty_like(logits)
+        ids = torch.randint(2, V, (B, prompt), device=dev, generator=g)
+        plen = torch.full((B,), prompt, dtype=torch.int32, device=dev)
+        new = torch.randint(2, V, (B, new_tokens), device=dev, generator=g)
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        desc = E.SlamConstrainDesc(step=new_tokens, no_repeat_ngram=n, n_per_prompt=1, prompt_stride=0, ban_eos=0, n_eos=0,
+                                   n_begin=0, n_seqs=0, n_seq_tokens=0)
+
+        def run(out):
+            for _ in range(calls):
+                E.constrain_scores(logits, out, desc, ids, plen, new, done)
+
+        for out in (logits, scores):
+            run(out)
+        torch.cuda.synchronize()
+        ti, tc = [], []
+        for _ in range(rounds):  # alternated
+            ti.append(ev_ms(lambda: run(logits)) / calls * 1e3)
+            tc.append(ev_ms(lambda: run(scores)) / calls * 1e3)
+        print(json.dumps(dict(bench="constrain_op", B=B, vocab=V, history=prompt + new_tokens, no_repeat_ngram=n,
+                              inplace_us=round(statistics.median(ti), 2), inplace_us_minmax=[round(min(ti), 2), round(max(ti), 2)],
+                              copy_us=round(statistics.median(tc), 2), copy_us_minmax=[round(min(tc), 2), round(max(tc), 2)],
+                              copy_floor_us=round(2 * B * V * 4 / HBM_BPS * 1e6, 2))), flush=True)
 
 
 def sample_op_bench(calls=200, rounds=5):
@@ -380,6 +442,9 @@ def main():
     ap.add_argument("--sampler", default=None, help="torch,engine: end-to-end generate per sampler, alternated")
     ap.add_argument("--do-sample", action="store_true", help="with --sampler: temperature 0.8, top_k 25 instead of greedy")
     ap.add_argument("--sample-op", action="store_true", help="time the token choice alone (engine vs torch ops)")
+    ap.add_argument("--constrain-op", action="store_true", help="time slam_constrain_scores alone (in place and copying)")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0,
+                    help="n, with --sampler S: end-to-end greedy generate without and with no_repeat_ngram_size=n, alternated")
     ap.add_argument("--num-return-sequences", type=int, default=0,
                     help="n: generate of 8 prompts x n from one prefill vs the repeated batch, kv_repeat and token_logprobs alone")
     ap.add_argument("--prefill-chunk", type=int, default=0,
@@ -393,6 +458,9 @@ def main():
     if a.sample_op:
         sample_op_bench()
         return
+    if a.constrain_op:
+        constrain_op_bench()
+        return
     if a.prefill_chunk > 0:
         for name in a.models.split(","):
             chunked_prefill_bench(name, 8, 2048, a.prefill_chunk)
@@ -405,7 +473,11 @@ def main():
     for name in a.models.split(","):
         m = build(name, 4096)
         if a.sampler:
-            e2e_samplers(m, 8, 256, a.steps, a.reps, name, a.sampler.split(","), a.do_sample)
+            if a.no_repeat_ngram > 0:
+                for smp in a.sampler.split(","):
+                    e2e_no_repeat(m, 8, 256, a.steps, a.reps, name, smp, a.no_repeat_ngram)
+            else:
+                e2e_samplers(m, 8, 256, a.steps, a.reps, name, a.sampler.split(","), a.do_sample)
             del m
             torch.cuda.empty_cache()
             continue
