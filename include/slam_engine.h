@@ -439,6 +439,24 @@ int slam_seq_loglik(SlamEngine* h, const int64_t* labels, int32_t B, int32_t T, 
  * by seq_coef[b] (fp32 [B] device) - e.g. +-beta*sigmoid(-x)/n for the sigmoid DPO loss - then slam_backward. */
 int slam_scale_loss_rows(SlamEngine* h, const float* seq_coef, int32_t B, int32_t T, slam_stream_t stream);
 
+/* Label smoothing of the training loss (HF TrainingArguments.label_smoothing_factor: transformers.trainer_pt_utils.LabelSmoother
+ * with shift_labels). epsilon in [0, 1), else SLAM_EINVAL; it persists until changed and applies to the loss of every following
+ * slam_forward / slam_forward_unpadded that is given labels. 0 (the default) launches the plain loss kernels: the bits of an
+ * engine that never called this. With V = vocab_size (never the padded row length), p = softmax(z) and lse = logsumexp(z) over
+ * the V real columns of a position whose target y is valid:
+ *     nll_t = lse - z_y        smooth_t = lse - (1 / V) sum_v z_v        (= the mean over v of -log p_v)
+ *     loss = ((1 - epsilon) sum_t nll_t + epsilon sum_t smooth_t) / denom
+ *     d loss / d z_j = (p_j - (1 - epsilon) [j == y] - epsilon / V) / denom  for j < V, exactly 0 in the pad columns
+ * denom as without smoothing: num_items when positive, else the number of valid targets. Smoothing runs inside the loss kernels'
+ * own passes over the logits (no further read or write of a row). Summation order, fixed, so that equal inputs give equal bits:
+ * sum_v z_v in fp32 - each thread its columns in ascending order, the lanes of a wave by the xor butterfly, the waves of a row's
+ * block in wave order; the two sums over t in double, in the order the plain loss sums its rows, combined as written above.
+ * The per-row values that slam_seq_loglik / slam_seq_loglik_unpadded read stay the PLAIN nll_t: after a smoothed forward they
+ * return what they return after a plain one. Refused with SLAM_ESTATE: a forward with labels and epsilon > 0 while a logit
+ * mask is set (modality-restricted scoring is a likelihood, not a training loss), and slam_scale_loss_rows /
+ * slam_scale_loss_unpadded after a smoothed forward (sequence objectives are defined on the plain log-likelihood). */
+int slam_set_label_smoothing(SlamEngine* h, float epsilon);
+
 /* ---- optimizer step: HF Trainer clip_grad_norm_ + torch AdamW --------------
  * norm_out: fp32 [2] device = {global grad norm, clip coefficient}.
  * Where the gradients are read from follows the last slam_backward: the fp32 buffer of slam_bind_params, or - after a
@@ -777,6 +795,12 @@ int slam_op_colsum(const void* X, int ld, int M, int N, float* out, int accumula
 int slam_op_cross_entropy(const void* logits /* bf16 [B*T][Vp] */, const int64_t* labels, double num_items,
                           void* dlogits, float* row_loss, float* scratch2 /* {denom, loss} */, int B, int T,
                           int Vp /* padded row length: 512, or a multiple of 8 beyond */, int V, slam_stream_t s);
+/* the loss launch under slam_set_label_smoothing(epsilon): row_loss [B*T] = the plain nll_t as above, row_smooth [B*T] = smooth_t
+ * (both 0 on ignored rows), scratch2[1] = the smoothed loss, dlogits (may alias logits) its gradient. epsilon = 0 is
+ * slam_op_cross_entropy itself (row_smooth is then not written and may be NULL); outside [0, 1): SLAM_EINVAL. */
+int slam_op_cross_entropy_smooth(const void* logits /* bf16 [B*T][Vp] */, const int64_t* labels, double num_items,
+                                 void* dlogits, float* row_loss, float* row_smooth, float* scratch2 /* {denom, loss} */, int B,
+                                 int T, int Vp, int V, float epsilon, slam_stream_t s);
 /* gather-side embedding gradient for vocabularies beyond 512: dE[ids[m]] += dh[m], token order (deterministic) */
 size_t slam_op_embed_bwd_workspace(int M, int Vp);
 int slam_op_embed_bwd(const int64_t* ids, const void* dh /* bf16 [M][H] */, float* dE /* fp32 [Vp][H] */, int M, int H,

@@ -666,13 +666,22 @@ __global__ void count_valid_kernel(const int64_t* __restrict__ labels, int B, in
   if (threadIdx.x == 0) denom[0] = num_items > 0.0 ? (float)num_items : (float)red[0];
 }
 
+// Label smoothing (HF LabelSmoother; include/slam_engine.h, slam_set_label_smoothing) is the SMOOTH = true instantiation of the
+// two row kernels and of loss_finish_kernel; SMOOTH = false compiles to the code these kernels were without it. Per valid row,
+//   row_loss = lse - z_y (the PLAIN nll, whatever eps),  row_smooth = lse - (1 / V) sum_{v on} z_v,
+//   d loss / d z_j = (p_j - (1 - eps) [j == y] - eps / V) / denom  on the "on" columns, exactly 0 on the others.
+// sum_v z_v is taken in the pass that forms max and sum, in fp32: per thread in column order, lanes by the xor butterfly, waves
+// in wave order - the same bits every run. No extra read or write of the row.
+
 // one wave per row, Vp == 512 (64 lanes x 8)
 // (logits and dlogits may be the SAME buffer: a lane reads its chunk into registers before it writes it)
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void ce_kernel(const bf16_t* logits,
                                                  const int64_t* __restrict__ labels,
                                                  const float* __restrict__ denom, bf16_t* dlogits,
                                                  float* __restrict__ row_loss, int B, int T, int Vp, int V,
-                                                 const uint8_t* __restrict__ colmask) {
+                                                 const uint8_t* __restrict__ colmask, float eps,
+                                                 float* __restrict__ row_smooth) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int M = B * T;
@@ -684,6 +693,7 @@ __global__ __launch_bounds__(256) void ce_kernel(const bf16_t* logits,
   if (!valid) {  // wave-uniform
     if (dl) *dl = make_uint4(0, 0, 0, 0);
     if (lane == 0) row_loss[m] = 0.f;
+    if constexpr (SMOOTH) { if (lane == 0) row_smooth[m] = 0.f; }
     return;
   }
   float f[8];
@@ -696,9 +706,10 @@ __global__ __launch_bounds__(256) void ce_kernel(const bf16_t* logits,
 #pragma unroll
     for (int j = 0; j < 8; ++j) on[j] = (lane * 8 + j < V) && !(((j < 4 ? mk.x : mk.y) >> (8 * (j & 3))) & 0xff);
   }
-  float mx = -3.0e38f;
+  float mx = -3.0e38f, zs = 0.f;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
+    if constexpr (SMOOTH) zs += on[j] ? f[j] : 0.f;
     if (!on[j]) f[j] = -3.0e38f;
     mx = fmaxf(mx, f[j]);
   }
@@ -718,6 +729,12 @@ __global__ __launch_bounds__(256) void ce_kernel(const bf16_t* logits,
     if (lane * 8 + j == (int)tgt) tl = f[j];
   tl = wave_sum(tl);
   if (lane == 0) row_loss[m] = (colmask && colmask[tgt]) ? INFINITY : lse - tl;
+  float uni = 0.f;  // eps / V, the uniform part of the smoothed target
+  if constexpr (SMOOTH) {
+    zs = wave_sum(zs);
+    uni = eps / (float)V;
+    if (lane == 0) row_smooth[m] = lse - zs / (float)V;
+  }
   if (dl) {
     const float sc = 1.f / denom[0];
     const float inv = 1.f / s;
@@ -725,7 +742,12 @@ __global__ __launch_bounds__(256) void ce_kernel(const bf16_t* logits,
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float pj = e[j] * inv;
-      if (lane * 8 + j == (int)tgt) pj -= 1.f;
+      if constexpr (SMOOTH) {
+        if (on[j]) pj -= uni;  // never on a pad column: those stay exact zeros
+        if (lane * 8 + j == (int)tgt) pj -= 1.f - eps;
+      } else {
+        if (lane * 8 + j == (int)tgt) pj -= 1.f;
+      }
       o[j] = pj * sc;
     }
     *dl = pack_bf16x8(o);
@@ -737,12 +759,15 @@ __global__ __launch_bounds__(256) void ce_kernel(const bf16_t* logits,
 // Algorithmic traffic: 2 B/logit read + 2 B/logit written.
 // (logits and dlogits may be the SAME buffer - the engine's training path: the gradient replaces the logits chunk by
 //  chunk in the second pass, after the barrier behind the first pass and after thread 0 has read the target logit)
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
                                                      const int64_t* __restrict__ labels,
                                                      const float* __restrict__ denom, bf16_t* dlogits,
                                                      float* __restrict__ row_loss, int B, int T, int Vp, int V,
-                                                     const uint8_t* __restrict__ colmask) {
+                                                     const uint8_t* __restrict__ colmask, float eps,
+                                                     float* __restrict__ row_smooth) {
   __shared__ float red_m[4], red_s[4];
+  __shared__ float red_z[SMOOTH ? 4 : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m = blockIdx.x;
   const int t = m % T;
@@ -755,10 +780,11 @@ __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
     if (dl)
       for (int c = tid; c < nch; c += 256) dl[c] = make_uint4(0, 0, 0, 0);
     if (tid == 0) row_loss[m] = 0.f;
+    if constexpr (SMOOTH) { if (tid == 0) row_smooth[m] = 0.f; }
     return;
   }
   const float tgt_logit = tid == 0 ? bf16_to_f32(logits[(size_t)m * Vp + tgt]) : 0.f;  // read before any in-place write
-  float mx = -3.0e38f, sm = 0.f;
+  float mx = -3.0e38f, sm = 0.f, zs = 0.f;
   for (int c = tid; c < nch; c += 256) {
     float f[8];
     unpack_bf16x8(lr[c], f);
@@ -768,6 +794,7 @@ __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       on[j] = (c * 8 + j < V) && !(((j < 4 ? mk.x : mk.y) >> (8 * (j & 3))) & 0xff);
+      if constexpr (SMOOTH) zs += on[j] ? f[j] : 0.f;
       if (!on[j]) f[j] = -3.0e38f;
       cm = fmaxf(cm, f[j]);
     }
@@ -781,6 +808,10 @@ __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
   const float wm = wave_max(mx);
   sm = wave_sum(sm * __expf(mx - wm));
   if (lane == 0) { red_m[wave] = wm; red_s[wave] = sm; }
+  if constexpr (SMOOTH) {
+    zs = wave_sum(zs);
+    if (lane == 0) red_z[wave] = zs;
+  }
   __syncthreads();
   const float bm = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
   float bs = 0.f;
@@ -788,6 +819,11 @@ __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
   for (int w = 0; w < 4; ++w) bs += red_s[w] * __expf(red_m[w] - bm);
   const float lse = bm + logf(bs);
   if (tid == 0) row_loss[m] = (colmask && colmask[tgt]) ? INFINITY : lse - tgt_logit;
+  float uni = 0.f;  // eps / V, the uniform part of the smoothed target
+  if constexpr (SMOOTH) {
+    uni = eps / (float)V;
+    if (tid == 0) row_smooth[m] = lse - (((red_z[0] + red_z[1]) + red_z[2]) + red_z[3]) / (float)V;
+  }
   if (dl) {
     const float sc = 1.f / denom[0];
     for (int c = tid; c < nch; c += 256) {
@@ -799,7 +835,12 @@ __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
         const int col = c * 8 + j;
         const bool onj = (col < V) && !(((j < 4 ? mk.x : mk.y) >> (8 * (j & 3))) & 0xff);
         float pj = onj ? __expf(f[j] - lse) : 0.f;
-        if (col == (int)tgt) pj -= 1.f;
+        if constexpr (SMOOTH) {
+          if (onj) pj -= uni;  // never on a pad column: those stay exact zeros
+          if (col == (int)tgt) pj -= 1.f - eps;
+        } else {
+          if (col == (int)tgt) pj -= 1.f;
+        }
         o[j] = pj * sc;
       }
       dl[c] = pack_bf16x8(o);
@@ -882,18 +923,32 @@ __global__ __launch_bounds__(256) void embed_scatter_kernel(const bf16_t* __rest
 }
 
 // loss = sum(row_loss) / denom  (single block, fixed order -> deterministic)
+// SMOOTH: loss = ((1 - eps) sum(row_loss) + eps sum(row_smooth)) / denom, each sum in that same order, in double
+template <bool SMOOTH>
 __global__ void loss_finish_kernel(const float* __restrict__ row_loss, int M, const float* __restrict__ denom,
-                                   float* __restrict__ loss) {
+                                   float* __restrict__ loss, float eps, const float* __restrict__ row_smooth) {
   __shared__ double red[256];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < M; i += 256) s += (double)row_loss[i];
+  __shared__ double red2[SMOOTH ? 256 : 1];
+  double s = 0.0, s2 = 0.0;
+  for (int i = threadIdx.x; i < M; i += 256) {
+    s += (double)row_loss[i];
+    if constexpr (SMOOTH) s2 += (double)row_smooth[i];
+  }
   red[threadIdx.x] = s;
+  if constexpr (SMOOTH) red2[threadIdx.x] = s2;
   __syncthreads();
   for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    if (threadIdx.x < k) {
+      red[threadIdx.x] += red[threadIdx.x + k];
+      if constexpr (SMOOTH) red2[threadIdx.x] += red2[threadIdx.x + k];
+    }
     __syncthreads();
   }
-  if (threadIdx.x == 0) loss[0] = denom[0] > 0.f ? (float)(red[0] / (double)denom[0]) : 0.f;
+  if (threadIdx.x == 0) {
+    double tot = red[0];
+    if constexpr (SMOOTH) tot = (1.0 - (double)eps) * red[0] + (double)eps * red2[0];
+    loss[0] = denom[0] > 0.f ? (float)(tot / (double)denom[0]) : 0.f;
+  }
 }
 
 // Per-sequence sum of -row_loss over valid targets (log-likelihood, unit_lm.py:184-194 shape)
@@ -1483,13 +1538,22 @@ int embed_bwd(const int64_t* ids, const bf16_t* dh, float* dE, int M, int H, int
 }
 
 int cross_entropy(const bf16_t* logits, const int64_t* labels, double num_items, bf16_t* dlogits, float* row_loss,
-                  float* denom, float* loss, int B, int T, int Vp, int V, const uint8_t* colmask, hipStream_t st) {
+                  float* denom, float* loss, int B, int T, int Vp, int V, const uint8_t* colmask, float eps, float* row_smooth,
+                  hipStream_t st) {
   if (Vp < 512 || (Vp & 7) || V > Vp) return -1;
+  if (!(eps >= 0.f && eps < 1.f)) return -1;
+  if (eps > 0.f && (!row_smooth || colmask || V <= 0)) return -1;  // smoothing over a masked vocabulary is not defined here
   int M = B * T;
   count_valid_kernel<<<1, 256, 0, st>>>(labels, B, T, num_items, denom);
-  if (Vp == 512) ce_kernel<<<(M + 3) / 4, 256, 0, st>>>(logits, labels, denom, dlogits, row_loss, B, T, Vp, V, colmask);
-  else ce_big_kernel<<<M, 256, 0, st>>>(logits, labels, denom, dlogits, row_loss, B, T, Vp, V, colmask);
-  loss_finish_kernel<<<1, 256, 0, st>>>(row_loss, M, denom, loss);
+  if (eps > 0.f) {
+    if (Vp == 512) ce_kernel<true><<<(M + 3) / 4, 256, 0, st>>>(logits, labels, denom, dlogits, row_loss, B, T, Vp, V, colmask, eps, row_smooth);
+    else ce_big_kernel<true><<<M, 256, 0, st>>>(logits, labels, denom, dlogits, row_loss, B, T, Vp, V, colmask, eps, row_smooth);
+    loss_finish_kernel<true><<<1, 256, 0, st>>>(row_loss, M, denom, loss, eps, row_smooth);
+  } else {
+    if (Vp == 512) ce_kernel<false><<<(M + 3) / 4, 256, 0, st>>>(logits, labels, denom, dlogits, row_loss, B, T, Vp, V, colmask, 0.f, nullptr);
+    else ce_big_kernel<false><<<M, 256, 0, st>>>(logits, labels, denom, dlogits, row_loss, B, T, Vp, V, colmask, 0.f, nullptr);
+    loss_finish_kernel<false><<<1, 256, 0, st>>>(row_loss, M, denom, loss, 0.f, nullptr);
+  }
   LAUNCH_RET();
 }
 int seq_loglik(const float* row_loss, const int64_t* labels, int B, int T, float* ll, float* cnt, hipStream_t st) {

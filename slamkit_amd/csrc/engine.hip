@@ -105,6 +105,12 @@ struct SlamEngine {
   bf16_t *hf, *logits, *dlogits, *onehot, *dh_a, *dx, *dact, *dqkv, *d_o;
   int* embed_ws = nullptr;
   const uint8_t* logit_mask = nullptr;  // optional [vpad] bytes: non-zero = column excluded from the softmax
+  // slam_set_label_smoothing: epsilon of the loss of every following forward with labels (0 = the plain kernels). The per-row
+  // smooth terms live in `dsum` (M * n_heads floats that only the attention backward uses): they are written and summed inside
+  // the loss launch sequence itself, so nothing else sees them. loss_smoothed: the last forward's d loss / d logits carries
+  // the smoothed target (the sequence-objective scalings refuse it).
+  float label_smoothing = 0.f;
+  bool loss_smoothed = false;
 
   // optimizer overlap ("overlap_adamw"): AdamW + the weight-image refresh run in per-layer chunks on an
   // engine-owned side stream; the next forward waits for chunk l right before layer l, so the HBM-bound update of
@@ -1058,6 +1064,8 @@ static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labe
   if (M64 > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
   if ((seg_start == nullptr) != (seg_end == nullptr)) return h->fail(SLAM_EINVAL, "seg_start/seg_end both or none");
   if (labels && !loss_out) return h->fail(SLAM_EINVAL, "labels given without loss_out");
+  if (labels && h->label_smoothing > 0.f && h->logit_mask)
+    return h->fail(SLAM_ESTATE, "label smoothing with a logit mask set: masked scoring is a likelihood, not a training loss");
   const int M = (int)M64;
   const SlamModelDesc& d = h->d;
   hipStream_t st = (hipStream_t)stream;
@@ -1083,9 +1091,10 @@ static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labe
   else if (logits_out) CK(copy_cols(h->logits, VP, (bf16_t*)logits_out, d.vocab, M, d.vocab, st));
   if (labels) {
     TK(F_LOSS, st, cross_entropy(h->logits, labels, num_items, h->dlogits, h->row_loss, h->scal + 0, h->scal + 1, B, T, VP,
-                     d.vocab, h->logit_mask, st));
+                     d.vocab, h->logit_mask, h->label_smoothing, h->dsum, st));
     CK((int)hipMemcpyAsync(loss_out, h->scal + 1, sizeof(float), hipMemcpyDeviceToDevice, st));
     h->have_loss = true;
+    h->loss_smoothed = h->label_smoothing > 0.f;
   }
   h->B = B;
   h->T = T;
@@ -1723,6 +1732,13 @@ int slam_set_logit_mask(SlamEngine* h, const uint8_t* mask) {
 }
 int32_t slam_padded_vocab(SlamEngine* h) { return h ? h->vpad : 0; }
 
+int slam_set_label_smoothing(SlamEngine* h, float epsilon) {
+  if (!h) return SLAM_EINVAL;
+  if (!(epsilon >= 0.f && epsilon < 1.f)) return h->fail(SLAM_EINVAL, "label smoothing epsilon must be in [0, 1)");
+  h->label_smoothing = epsilon;
+  return SLAM_OK;
+}
+
 int slam_seq_loglik(SlamEngine* h, const int64_t* labels, int32_t B, int32_t T, float* ll_out, float* cnt_out,
                     slam_stream_t stream) {
   if (!h || !labels || !ll_out || !cnt_out) return SLAM_EINVAL;
@@ -1744,6 +1760,7 @@ int slam_scale_loss_rows(SlamEngine* h, const float* seq_coef, int32_t B, int32_
   if (!h || !seq_coef) return SLAM_EINVAL;
   if (h->have_loss && h->unpadded) return h->fail(SLAM_ESTATE, "scale_loss_rows after an unpadded forward: use slam_scale_loss_unpadded");
   if (!h->have_loss || B != h->B || T != h->T) return h->fail(SLAM_ESTATE, "scale_loss_rows needs the matching forward with labels");
+  if (h->loss_smoothed) return h->fail(SLAM_ESTATE, "scale_loss_rows after a label-smoothed forward: sequence objectives need the plain loss");
   CK(scale_rows_bf16(h->dlogits, seq_coef, B * T, T, h->vpad, (hipStream_t)stream));
   return SLAM_OK;
 }
@@ -1752,6 +1769,7 @@ int slam_scale_loss_unpadded(SlamEngine* h, const float* seq_coef, int32_t B, sl
   if (!h || !seq_coef) return SLAM_EINVAL;
   if (!h->have_fwd || !h->have_loss || !h->unpadded || B != h->up_B)
     return h->fail(SLAM_ESTATE, "scale_loss_unpadded needs the matching unpadded forward with labels");
+  if (h->loss_smoothed) return h->fail(SLAM_ESTATE, "scale_loss_unpadded after a label-smoothed forward: sequence objectives need the plain loss");
   CK(scale_rows_unpadded_bf16(h->dlogits, seq_coef, h->up.row, h->B * h->T, h->vpad, (hipStream_t)stream));
   return SLAM_OK;
 }
@@ -2488,7 +2506,15 @@ int slam_op_colsum(const void* X, int ld, int M, int N, float* out, int accumula
 int slam_op_cross_entropy(const void* logits, const int64_t* labels, double num_items, void* dlogits, float* row_loss,
                           float* scratch2, int B, int T, int Vp, int V, slam_stream_t s) {
   return cross_entropy((const bf16_t*)logits, labels, num_items, (bf16_t*)dlogits, row_loss, scratch2, scratch2 + 1, B,
-                       T, Vp, V, nullptr, (hipStream_t)s);
+                       T, Vp, V, nullptr, 0.f, nullptr, (hipStream_t)s);
+}
+int slam_op_cross_entropy_smooth(const void* logits, const int64_t* labels, double num_items, void* dlogits, float* row_loss,
+                                 float* row_smooth, float* scratch2, int B, int T, int Vp, int V, float epsilon,
+                                 slam_stream_t s) {
+  if (!logits || !labels || !row_loss || !scratch2 || B <= 0 || T <= 0 || V <= 0) return SLAM_EINVAL;
+  if (!(epsilon >= 0.f && epsilon < 1.f) || (epsilon > 0.f && !row_smooth)) return SLAM_EINVAL;
+  return cross_entropy((const bf16_t*)logits, labels, num_items, (bf16_t*)dlogits, row_loss, scratch2, scratch2 + 1, B,
+                       T, Vp, V, nullptr, epsilon, row_smooth, (hipStream_t)s);
 }
 size_t slam_op_embed_bwd_workspace(int M, int Vp) { return embed_bwd_workspace_ints(M, Vp) * sizeof(int); }
 int slam_op_embed_bwd(const int64_t* ids, const void* dh, float* dE, int M, int H, int Vp, int V, int pad_id, void* ws,

@@ -168,8 +168,12 @@ int onehot(const int64_t* ids, bf16_t* oh, int M, int Vp, int V, int pad_id, hip
 size_t embed_bwd_workspace_ints(int M, int Vp);
 int embed_bwd(const int64_t* ids, const bf16_t* dh, float* dE, int M, int H, int Vp, int V, int pad_id, int* ws,
               hipStream_t st);
+// eps = label smoothing in [0, 1) (HF LabelSmoother over the V real columns): 0 launches the plain kernels and never touches
+// row_smooth; > 0 needs row_smooth (M floats: lse - mean_v z_v per valid row, 0 on ignored rows) and no colmask, else -1.
+// row_loss is the plain nll either way; loss = ((1 - eps) sum row_loss + eps sum row_smooth) / denom.
 int cross_entropy(const bf16_t* logits, const int64_t* labels, double num_items, bf16_t* dlogits, float* row_loss,
-                  float* denom, float* loss, int B, int T, int Vp, int V, const uint8_t* colmask, hipStream_t st);
+                  float* denom, float* loss, int B, int T, int Vp, int V, const uint8_t* colmask, float eps, float* row_smooth,
+                  hipStream_t st);
 int seq_loglik(const float* row_loss, const int64_t* labels, int B, int T, float* ll, float* cnt, hipStream_t st);
 int copy_cols(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int M, int ncols, hipStream_t st);
 int scale_bf16(bf16_t* x, size_t n, float s, hipStream_t st);

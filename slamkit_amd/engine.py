@@ -113,6 +113,7 @@ def load_library(path: Optional[str] = None):
         "slam_padded_vocab": (i32, [vp]),
         "slam_seq_loglik": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         "slam_scale_loss_rows": (C.c_int, [vp, vp, i32, i32, vp]),
+        "slam_set_label_smoothing": (C.c_int, [vp, f32]),
         "slam_grad_norm": (C.c_int, [vp, f32, vp, vp]),
         "slam_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
         "slam_adamw_step_bf16": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
@@ -187,6 +188,7 @@ def load_library(path: Optional[str] = None):
         "slam_op_colsum_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_colsum": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
         "slam_op_cross_entropy": (C.c_int, [vp, vp, f64, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_cross_entropy_smooth": (C.c_int, [vp, vp, f64, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
         "slam_op_embed_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_embed_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "slam_op_sr_round_bf16": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp]),
@@ -511,6 +513,11 @@ class Engine:
 
     def padded_vocab(self) -> int:
         return int(self.lib.slam_padded_vocab(self.h))
+
+    def set_label_smoothing(self, eps: float):
+        """slam_set_label_smoothing: epsilon in [0, 1) of the loss of every following forward with labels, until changed
+        (0 = the plain loss kernels). EngineError outside the range."""
+        self._ck(self.lib.slam_set_label_smoothing(self.h, float(eps)))
 
     def seq_loglik(self, labels, B, T, ll_out, cnt_out, stream=None):
         self._ck(self.lib.slam_seq_loglik(self.h, _ptr(labels), B, T, _ptr(ll_out), _ptr(cnt_out),

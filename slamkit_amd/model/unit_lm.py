@@ -472,6 +472,7 @@ class UnitLM(TokenLM):
         self.padding_free = False
         self._last_unpadded = False
         self._unpad_buf = None
+        self._smoothing = 0.0  # the engine's label-smoothing epsilon as last set here (_set_label_smoothing)
         self._build_key_map()
         self.init_weights(seed)
         if config.twist_init and not _from_pretrained:
@@ -824,7 +825,7 @@ class UnitLM(TokenLM):
     def forward(self, input_ids: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
                 num_items_in_batch=None, return_logits: bool = True, padding_free: Optional[bool] = None, lengths=None,
-                **unused) -> CausalLMOutput:
+                label_smoothing: float = 0.0, **unused) -> CausalLMOutput:
         """UnitLM.forward (unit_lm.py:135-182). `attention_mask` must be right padding (what
         DataCollatorForLanguageModeling produces): under the causal mask it never changes a real
         token's output, so the engine does not read it.
@@ -837,7 +838,12 @@ class UnitLM(TokenLM):
         positions), `num_items_in_batch` and backward behave as on the padded path, within rounding. Two differences: `labels`
         that are not -100 at pad positions add loss terms for predicting pads on the padded path and none here; and OPT's
         dropout mask is keyed on the element index of the layout the forward runs, so a token's mask differs from the padded
-        run's (still a pure function of seed, call, layer, site and packed index)."""
+        run's (still a pure function of seed, call, layer, site and packed index).
+
+        `label_smoothing` (HF `TrainingArguments.label_smoothing_factor`, in [0, 1)): the loss of THIS call is HF's
+        `LabelSmoother(epsilon)` over the vocab_size real columns, (1 - eps) * nll + eps * mean_v(-log p_v), summed over the
+        valid targets and divided as the plain loss is; backward follows it. A per-call argument, as HF keeps smoothing in the
+        trainer: a bare `model(...)` never smooths, and 0 is the plain loss kernels, bit for bit."""
         assert input_ids is not None and input_ids.dim() == 2
         B, T = input_ids.shape
         if attention_mask is not None and not attention_mask.is_cuda and not _right_padded(attention_mask):
@@ -855,6 +861,7 @@ class UnitLM(TokenLM):
         nb = not input_ids.is_cuda and input_ids.is_pinned()  # pinned host batches (the trainer's prefetch thread): async H2D
         ids = input_ids.to(dev, torch.int64, non_blocking=nb)
         lab = labels.to(dev, torch.int64, non_blocking=nb) if labels is not None else None
+        self._set_label_smoothing(label_smoothing)
         if (self.padding_free if padding_free is None else padding_free) and position_ids is None:
             lens = self._host_lengths(B, T, attention_mask, lengths)
             if lens is not None:
@@ -899,6 +906,15 @@ class UnitLM(TokenLM):
         return CausalLMOutput(loss=loss, logits=logits)
 
     __call__ = forward
+
+    def _set_label_smoothing(self, eps: float):
+        """The engine keeps epsilon until it is changed: set it only when this call's differs from the last one set."""
+        eps = float(eps or 0.0)
+        if not 0.0 <= eps < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {eps}")
+        if eps != self._smoothing:
+            self.engine.set_label_smoothing(eps)
+            self._smoothing = eps
 
     # ---- padding-free execution ----------------------------------------------------------------------
     @staticmethod
@@ -987,6 +1003,7 @@ class UnitLM(TokenLM):
         their own lengths, taken from pad_token_id (one read-back per call when `tokens` is on the device)."""
         B, T = tokens.shape
         self._check_positions(T)
+        self._set_label_smoothing(0.0)  # a likelihood, never a smoothed loss
         pf = self.padding_free if padding_free is None else padding_free
         lens = self._lengths_from_pad(tokens) if pf else None
         ids = tokens.to(self.device, torch.int64).contiguous()
@@ -1026,6 +1043,7 @@ class UnitLM(TokenLM):
         segments; a device batch without `lengths` keeps the padded path."""
         B, T = input_ids.shape
         self._check_positions(T)
+        self._set_label_smoothing(0.0)  # sequence objectives are defined on the plain log-likelihood
         lens = None
         if self.padding_free if padding_free is None else padding_free:
             if lengths is None and not input_ids.is_cuda:

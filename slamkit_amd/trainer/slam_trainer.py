@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from .callbacks import TrainerCallback, TrainerControl, TrainerState
 from .dp import GradBucketReducer, ShardedGradReducer, all_reduce_scalar, host_group, seeded_batches, shard_batches, world_info
-from .training_args import SLAMTrainingArguments, check_weight_decay_rule, lr_lambda
+from .training_args import SLAMTrainingArguments, check_label_smoothing, check_weight_decay_rule, lr_lambda
 
 logger = logging.getLogger(__name__)
 
@@ -63,6 +63,11 @@ class SLAMTrainer:
         # argument switches it ON; a model whose owner switched it on already keeps it (the default False never switches off)
         if hasattr(model, "padding_free") and getattr(self.args, "padding_free", False):
             model.padding_free = True
+        # label smoothing (HF's label_smoothing_factor): handed to the model per call, in training_step and evaluate() alike
+        # (HF's prediction_step goes through compute_loss too). 0 passes nothing: the calls stay what they were
+        # (fields set after construction get past the arguments' own check)
+        eps = check_label_smoothing(getattr(self.args, "label_smoothing_factor", 0.0))
+        self._smooth_kw = {"label_smoothing": eps} if eps else {}
         dev = model.device
         n = model.engine.n_params
         osd = getattr(self.args, "optim_state_dtype", "float32") or "float32"
@@ -161,7 +166,7 @@ class SLAMTrainer:
         Returns the (device) loss tensor without synchronising."""
         out = model.forward(input_ids=inputs["input_ids"], attention_mask=inputs.get("attention_mask"),
                             position_ids=inputs.get("position_ids"), labels=inputs["labels"],
-                            num_items_in_batch=num_items_in_batch, return_logits=False)
+                            num_items_in_batch=num_items_in_batch, return_logits=False, **self._smooth_kw)
         loss = out.loss.detach()
         if last_micro and (self.world > 1 or self.reducer.force):
             # bf16 exchange: this backward writes the communication image itself (no pack pass); with bf16 final gradients the
@@ -521,7 +526,7 @@ class SLAMTrainer:
                 # the collated mask is what gives a padding-free model its row lengths; the padded path never reads it
                 am = mb.get("attention_mask") if getattr(self.model, "padding_free", False) else None
                 out = self.model.forward(input_ids=mb["input_ids"], attention_mask=am, position_ids=mb.get("position_ids"),
-                                         labels=mb["labels"], num_items_in_batch=1.0, return_logits=False)
+                                         labels=mb["labels"], num_items_in_batch=1.0, return_logits=False, **self._smooth_kw)
                 tot += out.loss.double()
                 cnt += n
         finally:

@@ -45,6 +45,7 @@ class SLAMTrainingArguments:
     gradient_checkpointing: bool = False           # HF's field: recompute each layer's forward in backward (engine option "recompute" = 2) - the activations of 3 layers instead of all; same bits, about a quarter more step time
     recompute_level: Optional[int] = None          # overrides gradient_checkpointing: 1 = selective (norm outputs and the MLP activation only), 2 = full layer
     padding_free: bool = False                     # HF / TRL's name: right-padded batches (the default collator's, DPO's pairs, evaluation) run as packed segments of their own lengths and skip the pad positions (slam_forward_unpadded; UnitLM.padding_free). True switches the models on; False (the default) leaves a model's own switch alone. Same losses within rounding; OPT's dropout masks follow the packed layout
+    label_smoothing_factor: float = 0.0            # HF's field: epsilon of transformers' LabelSmoother, in [0, 1). The training loss, the logged `loss` and `eval_loss` become (1 - eps) * nll + eps * mean_v(-log p_v) over the vocab_size columns, computed inside the engine's loss kernels (UnitLM.forward(label_smoothing=), slam_set_label_smoothing). 0 (the default) is the plain loss, bit for bit. SLAMDPOTrainer refuses a non-zero value (TRL's own label_smoothing is another quantity)
     dataloader_num_workers: int = 0                # > 0: one background thread collates up to two optimizer steps ahead into pinned host memory (SLAMTrainer._micro_batches)
     min_token_id_count: Optional[int] = None
     max_token_id_count: Optional[int] = None
@@ -59,6 +60,7 @@ class SLAMTrainingArguments:
 
     def __post_init__(self):
         check_weight_decay_rule(self.weight_decay_rule)
+        check_label_smoothing(self.label_smoothing_factor)
         if self.optim_stochastic_rounding and (self.optim_state_dtype or "float32") == "float32":
             raise ValueError("optim_stochastic_rounding needs bf16 optimizer state (optim_state_dtype bfloat16 or "
                              "float32_bf16_moments): with float32 state nothing is rounded")
@@ -84,6 +86,13 @@ def check_weight_decay_rule(rule) -> str:
     if rule not in ("all", "hf"):
         raise ValueError(f"weight_decay_rule must be 'all' or 'hf', got {rule!r}")
     return rule
+
+
+def check_label_smoothing(eps) -> float:
+    eps = float(eps or 0.0)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing_factor must be in [0, 1), got {eps}")
+    return eps
 
 
 def lr_lambda(args: SLAMTrainingArguments, step: int, num_training_steps: int) -> float:
