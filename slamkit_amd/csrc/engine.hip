@@ -660,6 +660,13 @@ int qn_blocks(const SlamEngine* h, int M) {
   return want < cap ? want : cap;
 }
 
+// The family's row norm over M rows: LayerNorm with a bias and a saved mean (OPT; boff and mu are OPT's alone), else RMSNorm
+int norm_fwd(SlamEngine* h, const bf16_t* x, int64_t woff, int64_t boff, bf16_t* y, float* mu, float* rstd, int M, hipStream_t st) {
+  const bf16_t* P = h->params;
+  if (h->arch == 1) return layernorm_fwd(x, P + woff, P + boff, y, mu, rstd, M, h->d.hidden, h->d.rms_eps, st);
+  return rmsnorm_fwd(x, P + woff, y, rstd, M, h->d.hidden, h->d.rms_eps, st);
+}
+
 // One decoder layer's forward launches over M tokens: hs[l] -> la[l] (-> hs[l + 1]). The one body that slam_forward,
 // slam_prefill and the recomputation in slam_backward share, so a re-run issues the forward's own calls in the forward's own
 // order. `rerun` (backward, "recompute" = 2): the layer's parameters are already final for this step (no chunk / parameter
@@ -677,8 +684,7 @@ int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
     CK(wait_chunk(h, 1 + l, st));
     CK(wait_params(h, o.ln1, o.ln1 + h->layer_stride, st));
   }
-  if (opt) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, d.rms_eps, st));
-  else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
+  TK(F_NORM_FWD, st, norm_fwd(h, h->hs[l], o.ln1, o.ln1_b, a.x1, a.mu1, a.rstd1, M, st));
   if (h->arch == 3) {  // Qwen3: no bias; per-head RMSNorm + RoPE in one pass behind the projection (never the fused epilogue)
     const int slot = fam_begin(h, F_QKV_FWD, st);
     CK(gemm_nt(a.x1, P + o.wqkv, a.qkv, nullptr, nullptr, M, h->QKV, H, st));
@@ -706,7 +712,7 @@ int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
       if (drop) CK(dropout_add(a.hmid, h->hs[l], M, H, ds, st));
       fam_end(h, slot, st);
     }
-    TK(F_NORM_FWD, st, layernorm_fwd(a.hmid, P + o.ln2, P + o.ln2_b, a.x2, a.mu2, a.rstd2, M, H, d.rms_eps, st));
+    TK(F_NORM_FWD, st, norm_fwd(h, a.hmid, o.ln2, o.ln2_b, a.x2, a.mu2, a.rstd2, M, st));
     TK(F_GATEUP_FWD, st, gemm_nt_relu(a.x2, P + o.wgu, a.act, P + o.b1, M, I, H, st));
     if (!rerun) {
       ds.site += 1;
@@ -718,7 +724,7 @@ int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
     return SLAM_OK;
   }
   TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, nullptr, h->hs[l], M, H, nH * d.head_dim, st));
-  TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
+  TK(F_NORM_FWD, st, norm_fwd(h, a.hmid, o.ln2, o.ln2_b, a.x2, a.mu2, a.rstd2, M, st));
   const bool timed = !rerun && h->time_gateup && h->tg_ev.size() == (size_t)(2 * L);
   if (timed) CK((int)hipEventRecord(h->tg_ev[2 * l], st));
   {
@@ -742,18 +748,13 @@ int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
 // gate|up no longer holds: that launch is re-run whole and rewrites gu with the values it has. The row statistics are
 // rewritten with their own values too. OPT keeps act (its fc1 pre-activation is never stored): x1 and x2 only.
 int rebuild_selective(SlamEngine* h, int l, int M, hipStream_t st) {
-  const SlamModelDesc& d = h->d;
-  const int H = d.hidden, I = d.intermediate;
+  const int H = h->d.hidden, I = h->d.intermediate;
   const bf16_t* P = h->params;
   const LayerOff& o = h->lo[l];
   LayerAct& a = h->la[l];
-  if (h->arch == 1) {
-    TK(F_NORM_FWD, st, layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, d.rms_eps, st));
-    TK(F_NORM_FWD, st, layernorm_fwd(a.hmid, P + o.ln2, P + o.ln2_b, a.x2, a.mu2, a.rstd2, M, H, d.rms_eps, st));
-    return SLAM_OK;
-  }
-  TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
-  TK(F_NORM_FWD, st, rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
+  TK(F_NORM_FWD, st, norm_fwd(h, h->hs[l], o.ln1, o.ln1_b, a.x1, a.mu1, a.rstd1, M, st));
+  TK(F_NORM_FWD, st, norm_fwd(h, a.hmid, o.ln2, o.ln2_b, a.x2, a.mu2, a.rstd2, M, st));
+  if (h->arch == 1) return SLAM_OK;
   if (h->fuse_swiglu) TK(F_GATEUP_FWD, st, gemm_nt_swiglu(a.x2, P + o.wgu, a.gu, a.act, M, 2 * I, H, st));
   else TK(F_GATEUP_FWD, st, swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
   return SLAM_OK;
@@ -1082,8 +1083,7 @@ static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labe
   }
   GemmTuneScope tune_scope(&h->gemm_tune);
   CK(forward_layers(h, ids, position_ids, seg_start, seg_end, M, T, st));
-  if (h->arch == 1) TK(F_NORM_FWD, st, layernorm_fwd(h->hs[L], P + h->off_norm, P + h->off_norm_b, h->hf, h->muf, h->rstdf, M, H, d.rms_eps, st));
-  else TK(F_NORM_FWD, st, rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, M, H, d.rms_eps, st));
+  TK(F_NORM_FWD, st, norm_fwd(h, h->hs[L], h->off_norm, h->off_norm_b, h->hf, h->muf, h->rstdf, M, st));
   const int VP = h->vpad;
   TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_head, h->logits, nullptr, nullptr, M, VP, H, st));
   h->have_loss = false;
@@ -1178,6 +1178,26 @@ int decode_proj(SlamEngine* h, const bf16_t* X, const bf16_t* W, bf16_t* Y, floa
     return gemm_skinny(X, W, Y, Yf, bias, resid, M, N, K, (float*)h->dact, (size_t)h->max_tokens * h->d.intermediate * sizeof(bf16_t), st);
   return gemm_nt(X, W, Y, bias, resid, M, N, K, st);
 }
+// The second half of a cached layer over M rows (la[l].o -> hs[l + 1]): out-projection + residual, norm, gate|up, SwiGLU, down +
+// residual. static: a function of an unnamed namespace inside extern "C" keeps its C name and appears in the dynamic symbol table
+static int cached_mlp(SlamEngine* h, int l, int M, hipStream_t st) {
+  const int H = h->d.hidden, I = h->d.intermediate, HD = h->d.n_heads * h->d.head_dim;
+  const bf16_t* P = h->params;
+  const LayerOff& o = h->lo[l];
+  LayerAct& a = h->la[l];
+  CK(decode_proj(h, a.o, P + o.wo, a.hmid, nullptr, nullptr, h->hs[l], M, H, HD, st));
+  CK(norm_fwd(h, a.hmid, o.ln2, o.ln2_b, a.x2, a.mu2, a.rstd2, M, st));
+  CK(decode_proj(h, a.x2, P + o.wgu, a.gu, nullptr, nullptr, nullptr, M, 2 * I, H, st));
+  CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
+  CK(decode_proj(h, a.act, P + o.wd, h->hs[l + 1], nullptr, nullptr, a.hmid, M, H, I, st));
+  return SLAM_OK;
+}
+// The last-token head of prefill, decode step and extend: final norm of the B rows of x, one fp32 head launch over them
+static int last_token_head(SlamEngine* h, const bf16_t* x, int B, float* logits, hipStream_t st) {
+  CK(norm_fwd(h, x, h->off_norm, h->off_norm_b, h->hf, h->muf, h->rstdf, B, st));
+  CK(decode_proj(h, h->hf, h->params + h->off_head, nullptr, logits, nullptr, nullptr, B, h->d.vocab, h->d.hidden, st));
+  return SLAM_OK;
+}
 }  // namespace
 
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
@@ -1191,7 +1211,6 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   const SlamModelDesc& d = h->d;
   hipStream_t st = (hipStream_t)stream;
   const int H = d.hidden, L = d.n_layers, M = B * T;
-  const bf16_t* P = h->params;
   h->have_fwd = false;
   h->fwd_drop = false;  // generation never drops
   h->kv_ready = false;
@@ -1203,8 +1222,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
     CK(kv_scatter(h->la[l].qkv, kv_k(h, l), kv_v(h, l), lens, B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st));
   // logits of each row's last prompt token only: gather, final norm, one fp32 head launch over B rows
   CK(gather_last_rows(h->hs[L], h->dx, lens, B, T, H, st));
-  CK(rmsnorm_fwd(h->dx, P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
-  CK(decode_proj(h, h->hf, P + h->off_head, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
+  CK(last_token_head(h, h->dx, B, logits_out, st));
   h->kv_B = B;
   h->kv_hi = T;
   h->kv_T = T;
@@ -1223,7 +1241,7 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
   if ((int64_t)2 * B > h->max_tokens) return h->fail(SLAM_ENOMEM, "decode needs a workspace of at least 2 B tokens");
   const SlamModelDesc& d = h->d;
   hipStream_t st = (hipStream_t)stream;
-  const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads, hd = d.head_dim;
+  const int H = d.hidden, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads, hd = d.head_dim;
   const bf16_t* P = h->params;
   h->have_fwd = false;
   GemmTuneScope tune_scope(&h->gemm_tune);
@@ -1242,20 +1260,15 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
   for (int l = 0; l < L; ++l) {
     const LayerOff& o = h->lo[l];
     LayerAct& a = h->la[l];
-    CK(rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, B, H, d.rms_eps, st));
+    CK(norm_fwd(h, h->hs[l], o.ln1, o.ln1_b, a.x1, a.mu1, a.rstd1, B, st));
     CK(decode_proj(h, a.x1, P + o.wqkv, nullptr, qkvf, nullptr, nullptr, B, h->QKV, H, st));
     // Qwen3: the q and k heads are normalised in the fp32 row; attn_decode then rotates and rounds once, without a bias
     if (q3) CK(qknorm_rows_f32(qkvf, h->QKV, B, nH, nKV, hd, P + o.q_norm, P + o.k_norm, d.rms_eps, st));
     CK(attn_decode(qkvf, q3 ? nullptr : P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, nH, nKV, hd,
                    h->kv_hi + 1, a.o, (float*)h->logits, part_bytes, st));
-    CK(decode_proj(h, a.o, P + o.wo, a.hmid, nullptr, nullptr, h->hs[l], B, H, nH * hd, st));
-    CK(rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, B, H, d.rms_eps, st));
-    CK(decode_proj(h, a.x2, P + o.wgu, a.gu, nullptr, nullptr, nullptr, B, 2 * I, H, st));
-    CK(swiglu_fwd(a.gu, a.act, B, I, GU_BLK, st));
-    CK(decode_proj(h, a.act, P + o.wd, h->hs[l + 1], nullptr, nullptr, a.hmid, B, H, I, st));
+    CK(cached_mlp(h, l, B, st));
   }
-  CK(rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
-  CK(decode_proj(h, h->hf, P + h->off_head, nullptr, logits_out, nullptr, nullptr, B, d.vocab, H, st));
+  CK(last_token_head(h, h->hs[L], B, logits_out, st));
   CK(lens_inc(lens, B, st));
   h->kv_hi += 1;
   return SLAM_OK;
@@ -1293,7 +1306,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
   if (score && score_rows_workspace_bytes(B * T, d.vocab) > (size_t)h->max_tokens * h->vpad * sizeof(bf16_t))
     return h->fail(SLAM_ENOMEM, "chunk partials exceed the logits buffer");
   hipStream_t st = (hipStream_t)stream;
-  const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads, hd = d.head_dim;
+  const int H = d.hidden, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads, hd = d.head_dim;
   const int M = B * T;
   const bf16_t* P = h->params;
   h->have_fwd = false;
@@ -1315,7 +1328,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
   for (int l = 0; l < L; ++l) {
     const LayerOff& o = h->lo[l];
     LayerAct& a = h->la[l];
-    CK(rmsnorm_fwd(h->hs[l], P + o.ln1, a.x1, a.rstd1, M, H, d.rms_eps, st));
+    CK(norm_fwd(h, h->hs[l], o.ln1, o.ln1_b, a.x1, a.mu1, a.rstd1, M, st));
     if (fused_rope) {
       CK(gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, nH + nKV, M, h->QKV, H, st));
     } else {
@@ -1325,11 +1338,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
     }
     CK(attn_extend(a.qkv, lens, new_lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, T, nH, nKV, hd, kv_bound, a.o, (float*)h->logits,
                    part_bytes, st));
-    CK(decode_proj(h, a.o, P + o.wo, a.hmid, nullptr, nullptr, h->hs[l], M, H, nH * hd, st));
-    CK(rmsnorm_fwd(a.hmid, P + o.ln2, a.x2, a.rstd2, M, H, d.rms_eps, st));
-    CK(decode_proj(h, a.x2, P + o.wgu, a.gu, nullptr, nullptr, nullptr, M, 2 * I, H, st));
-    CK(swiglu_fwd(a.gu, a.act, M, I, GU_BLK, st));
-    CK(decode_proj(h, a.act, P + o.wd, h->hs[l + 1], nullptr, nullptr, a.hmid, M, H, I, st));
+    CK(cached_mlp(h, l, M, st));
   }
   if (score) {
     // every chunk position: final norm of the B T rows, then the head fused with the row statistics. Scratch behind the layer
@@ -1337,15 +1346,14 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
     // logits buffer (the attention partials are dead; the last-token logits below overwrite it after these launches)
     int64_t* tg = (int64_t*)h->dqkv;
     CK(extend_targets(ids, new_lens, tg, B, T, st));
-    CK(rmsnorm_fwd(h->hs[L], P + h->off_norm, h->hf, h->rstdf, M, H, d.rms_eps, st));
+    CK(norm_fwd(h, h->hs[L], h->off_norm, h->off_norm_b, h->hf, h->muf, h->rstdf, M, st));
     CK(score_rows(h->hf, P + h->off_head, tg, h->logit_mask, M, d.vocab, H, new_lens, T, lp_out, argmax_out, h->logits,
                   part_bytes, st));
   }
   // each row's last real token: gather, final norm, one fp32 head launch over B rows; inert rows keep their logits and lens
   CK(gather_last_rows(h->hs[L], h->dx, new_lens, B, T, H, st));
-  CK(rmsnorm_fwd(h->dx, P + h->off_norm, h->hf, h->rstdf, B, H, d.rms_eps, st));
   float* lg = (float*)h->logits;
-  CK(decode_proj(h, h->hf, P + h->off_head, nullptr, lg, nullptr, nullptr, B, d.vocab, H, st));
+  CK(last_token_head(h, h->dx, B, lg, st));
   CK(extend_finish(lg, logits_out, new_lens, lens, B, T, d.vocab, st));
   if (h->kv_hi == h->kv_T) h->kv_T += T;  // no decode step since the prefill: slam_kv_repeat stays legal
   h->kv_hi += T;
@@ -1363,340 +1371,286 @@ int slam_extend_score(SlamEngine* h, const int64_t* ids, const int32_t* new_lens
   return extend_common(h, ids, new_lens, lens, B, T, logits_out, true, lp_out, argmax_out, stream);
 }
 
-int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_bucket_cb cb, void* user,
-                  slam_stream_t stream) {
-  if (!h) return SLAM_EINVAL;
-  if (!h->have_fwd || !h->have_loss) return h->fail(SLAM_ESTATE, "backward needs a forward with labels");
-  if (!h->grads) return h->fail(SLAM_ESTATE, "no gradient buffer bound");
+namespace {
+// One slam_backward call: what its steps share, and the steps. slam_backward fills it (begin), then runs head(), layer(l) from
+// the top layer down with finish_slabs() at the bucket boundaries, embedding() and the join. The decoder layer is written
+// once: the families differ in which projections carry a bias, in the norm and the activation (DESIGN.md §5 has the table).
+// Weight-gradient launches go to the main stream, or (bwd_wgrad_stream) to the side stream `ws` behind an event that the
+// main stream records once their operands exist. Every cross-stream edge costs the recording AND the waiting stream a
+// barrier packet (~6 us of queue bubble each, measured in the kernel trace), so the schedule keeps them few:
+//  * no side -> main edges at all: every gradient a weight-gradient GEMM reads lives in a buffer nothing overwrites
+//    until the next forward - the gradient of hs[l] goes into layer l's (dead) hmid buffer, the gradient of hmid[l]
+//    into the (dead) hs[l+1] buffer, d(qkv) of layer l into layer l+1's (dead) qkv buffer; all three are buffers only
+//    main-stream kernels read, and only earlier in this backward;
+//  * main -> side: one event per weight-gradient GEMM, recorded as soon as its operands exist. Handing them over in
+//    batches (two or one event per layer) was measured and is worse (+0.8 / +1.5 ms per Slam-358M step): the side stream
+//    needs its work as early as it can have it.
+struct Backward {
+  SlamEngine* const h;
+  const hipStream_t st;  // the caller's stream: the dgrad / attention / norm chain
   const SlamModelDesc& d = h->d;
-  hipStream_t st = (hipStream_t)stream;
-  CK(join_optimizer(h, st));
-  CK(join_params(h, st));
-  h->ag_ev_used = 0;  // every parameter arrival has been waited for: the pool is free for the next step's gathers
-  if (h->params_t_dirty) CK(slam_refresh_transposed(h, stream));
-  const int M = h->B * h->T;
-  const int H = d.hidden, I = d.intermediate, L = d.n_layers, nH = d.n_heads, nKV = d.n_kv_heads;
-  const int HD = nH * d.head_dim;
-  const bf16_t* P = h->params;
-  float* G = h->grads;
+  const int M = h->B * h->T, H = d.hidden, I = d.intermediate, L = d.n_layers;
+  const bf16_t *const P = h->params, *const Pt = h->params_t;  // Pt: the transposed weight images (nullable)
+  float* const G = h->grads;
+  const bool opt = h->arch == 1, q3 = h->arch == 3;
+  const bool two = h->wgrad_stream != 0, aux = two && h->aux_side != 0;  // bwd_wgrad_stream, bwd_aux_side
+  const int rc = h->recompute;
+  const bool slot_edges = rc && two && L > RC_SLOTS, drop = opt && h->fwd_drop;
+  const int qnb = q3 ? qn_blocks(h, M) : 0;  // Qwen3: blocks of the q / k norm backward
+  hipStream_t ws = st;     // the weight gradients' stream: h->wside with bwd_wgrad_stream (begin)
+  int acc = 1, fin = 0;    // 0: this backward stores gradients, 1: it adds to them; "grad_final_next" of this call
+  bf16_t* IMG = nullptr;   // bf16 image of the gradients (nullable)
+  bool partials = false;   // the final-value stores emit sum-of-squares partials
+  GradSink sink_store{};   // of the launch in flight: sink() fills it, take() reads what the launch used
+  int ev_used = 0;         // events of ev_w handed out by edge()
+  bf16_t* dh = nullptr;    // the gradient on its way down: wrt hs[l + 1] when layer(l) starts, wrt hs[l] when it returns
 
-  const bf16_t* Pt = h->params_t;
-  // dX[M,K] = dY[M,N] W[N,K]: with a transposed image W^T[K,N] it is the contraction-contiguous form
-  auto dgrad = [&](const bf16_t* dY, int64_t woff, bf16_t* dX, int N, int K) -> int {
-    return Pt ? gemm_nt(dY, Pt + woff, dX, nullptr, nullptr, M, K, N, st) : gemm_nn(dY, P + woff, dX, nullptr, M, N, K, st);
-  };
-  const int VP = h->vpad;
-  if (grad_scale != 1.0f) CK(scale_bf16(h->dlogits, (size_t)M * VP, grad_scale, st));
-  // tied head: dE += dlogits^T hf ; dhf = dlogits E. Untied head: d lm_head = dlogits^T hf ; dhf = dlogits lm_head
-  // first micro-batch of an optimizer step: every gradient tensor is written exactly once below (the tied embedding
-  // twice: head first, gather side second; untied, lm_head once by the head and the embedding once by the gather side,
-  // which then stores - or zeroes the tensor before its scatter), so it may be STORED instead of accumulated and the buffer needs no
-  // zeroing pass (4 B/param written by AdamW + 4 B/param re-read by the wgrad epilogues)
-  const int acc = h->overwrite_next ? 0 : 1;
-  h->overwrite_next = false;
-  // bf16 communication image of the gradients (slam_set_grad_image): written by the SAME kernels that store the final fp32
-  // values (unsplit weight-gradient tiles, slab reduces, the norm / bias finish kernel) - no conversion pass over the buffer
-  bf16_t* const IMG = h->grad_img;
-  h->grad_img = nullptr;
-  h->last_grad_img = IMG;
-  auto img = [&](int64_t off) -> bf16_t* { return IMG ? IMG + off : nullptr; };
-  // last backward of an optimizer step ("grad_final_next"): sum-of-squares partials from the final-value stores, and
-  // (mode 2) final values in the bf16 image only. Every launch that stores final values takes its slots in launch order.
-  const int fin = h->final_next;
-  h->final_next = 0;
-  h->gfinal = 0;
-  h->g16 = nullptr;
-  if (fin == 2 && !IMG) return h->fail(SLAM_ESTATE, "grad_final_next = 2 needs slam_set_grad_image before the backward");
-  // known from here on: the bucket callbacks below run INSIDE this call, and the engine-side exchange they may start
-  // (slam_allreduce_grads_async / slam_reduce_scatter_grads_async) asks where the gradients live
-  h->gfinal = fin;
-  h->g16 = fin == 2 ? IMG : nullptr;
-  const bool partials = fin && !cb && h->norm_partials;  // with a bucket callback the gradients are about to be exchanged: partials of the local ones are of no use
-  h->gn_valid = false;
-  if (partials) {
-    CK((int)hipMemsetAsync(h->gn_part, 0, h->gn_cap * sizeof(float), st));  // blocks without a final store leave their slot alone
-    h->gn_used = 0;
+  int make_events(std::vector<hipEvent_t>& ev) {  // one per layer, created by the first call that needs them
+    if (!ev.empty()) return SLAM_OK;
+    ev.resize((size_t)L);
+    for (auto& e : ev)
+      if (hipEventCreateWithFlags(&e, sync_event_flags()) != hipSuccess) { ev.clear(); return h->fail(SLAM_ESTATE, "hipEventCreate failed"); }
+    return SLAM_OK;
   }
-  GradSink sink_store;
-  auto sink = [&]() -> GradSink* {  // the slots from gn_used on; take(r) after the launch
+  // consumes what armed this call (grad_overwrite_next, the gradient image, grad_final_next) and readies streams and events
+  int begin(float grad_scale, bool have_cb) {
+    if (grad_scale != 1.0f) CK(scale_bf16(h->dlogits, (size_t)M * h->vpad, grad_scale, st));
+    // first micro-batch of an optimizer step: every gradient tensor is written exactly once below (the tied embedding
+    // twice: head first, gather side second; untied, lm_head once by the head and the embedding once by the gather side,
+    // which then stores - or zeroes the tensor before its scatter), so it may be STORED instead of accumulated and the buffer needs no
+    // zeroing pass (4 B/param written by AdamW + 4 B/param re-read by the wgrad epilogues)
+    acc = h->overwrite_next ? 0 : 1;
+    h->overwrite_next = false;
+    // bf16 communication image of the gradients (slam_set_grad_image): written by the SAME kernels that store the final fp32
+    // values (unsplit weight-gradient tiles, slab reduces, the norm / bias finish kernel) - no conversion pass over the buffer
+    h->last_grad_img = IMG = h->grad_img;
+    h->grad_img = nullptr;
+    // last backward of an optimizer step ("grad_final_next"): sum-of-squares partials from the final-value stores, and
+    // (mode 2) final values in the bf16 image only. Every launch that stores final values takes its slots in launch order.
+    fin = h->final_next;
+    h->final_next = 0;
+    h->gfinal = 0;
+    h->g16 = nullptr;
+    if (fin == 2 && !IMG) return h->fail(SLAM_ESTATE, "grad_final_next = 2 needs slam_set_grad_image before the backward");
+    // known from here on: the bucket callbacks run INSIDE this call, and the engine-side exchange they may start
+    // (slam_allreduce_grads_async / slam_reduce_scatter_grads_async) asks where the gradients live
+    h->gfinal = fin;
+    h->g16 = fin == 2 ? IMG : nullptr;
+    partials = fin && !have_cb && h->norm_partials;  // with a bucket callback the gradients are about to be exchanged: partials of the local ones are of no use
+    h->gn_valid = false;
+    if (partials) {
+      CK((int)hipMemsetAsync(h->gn_part, 0, h->gn_cap * sizeof(float), st));  // blocks without a final store leave their slot alone
+      h->gn_used = 0;
+    }
+    if (two) CK(ensure_wside(h));
+    ws = two ? h->wside : st;
+    // "recompute": layer l's slot (l mod 3) last held layer l + 3. On the caller's stream everything of that layer is behind us;
+    // on the weight-gradient stream its last reader is layer l + 2's Wqkv gradient and bias column sums, whose d(qkv) lives in
+    // la[l + 3].qkv. Layer l + 1's weight gradients touch the slots of layers l + 1 and l + 2 only. So one side -> main edge per
+    // layer (ev_rc), a whole layer old by the time it is waited for ("Activation recomputation", has the table).
+    if (int r = slot_edges ? make_events(h->ev_rc) : 0) return r;
+    // residual dropout: this backward belongs to a forward that dropped. The masked copies live in two buffer pairs by layer
+    // parity; on the weight-gradient stream layer l's last reader is its Wo gradient, which layer l - 2 waits for (ev_dm[l])
+    if (drop && !h->dmask[0][0]) return h->fail(SLAM_ESTATE, "dropout: the bound workspace has no masked-gradient buffers");
+    if (int r = drop && two ? make_events(h->ev_dm) : 0) return r;
+    return SLAM_OK;
+  }
+  int edge(hipStream_t from, hipStream_t to) {  // `to` continues after everything enqueued on `from` so far
+    if (from == to) return 0;
+    if ((size_t)ev_used >= h->ev_w.size()) return SLAM_ESTATE;
+    hipEvent_t e = h->ev_w[ev_used++];
+    if (hipError_t r = hipEventRecord(e, from)) return (int)r;
+    return (int)hipStreamWaitEvent(to, e, 0);
+  }
+  int fork() { return two ? edge(st, ws) : 0; }
+  bf16_t* img(int64_t off) const { return IMG ? IMG + off : nullptr; }
+  GradSink* sink() {  // the slots from gn_used on; take(r) after the launch
     if (!fin) return nullptr;
     sink_store.img_only = fin == 2;
     sink_store.sumsq = partials ? h->gn_part + h->gn_used : nullptr;
     sink_store.cap = (int)(h->gn_cap - h->gn_used);
     sink_store.used = 0;
     return &sink_store;
-  };
-  auto take = [&](int r) -> int {
+  }
+  int take(int r) {
     if (partials && r == 0) h->gn_used += (size_t)sink_store.used;
     return r;
-  };
-
-  // weight-gradient launches: on the main stream, or (bwd_wgrad_stream) on the side stream `ws` behind an event that the
-  // main stream records once their operands exist. Every cross-stream edge costs the recording AND the waiting stream a
-  // barrier packet (~6 us of queue bubble each, measured in the kernel trace), so the schedule keeps them few:
-  //  * no side -> main edges at all: every gradient a weight-gradient GEMM reads lives in a buffer nothing overwrites
-  //    until the next forward - the gradient of hs[l] goes into layer l's (dead) hmid buffer, the gradient of hmid[l]
-  //    into the (dead) hs[l+1] buffer, d(qkv) of layer l into layer l+1's (dead) qkv buffer; all three are buffers only
-  //    main-stream kernels read, and only earlier in this backward;
-  //  * main -> side: one event per weight-gradient GEMM, recorded as soon as its operands exist. Handing them over in
-  //    batches (two or one event per layer) was measured and is worse (+0.8 / +1.5 ms per Slam-358M step): the side stream
-  //    needs its work as early as it can have it.
-  const bool two = h->wgrad_stream != 0;
-  if (two) CK(ensure_wside(h));
-  GemmTuneScope tune_scope(&h->gemm_tune);
-  struct SharedGuard {  // dgrad launches of this call may plan for a GPU they share with the wgrad stream
-    GemmTune* t;
-    SharedGuard(GemmTune* t_, int on) : t(t_) { t->shared = on; }
-    ~SharedGuard() { t->shared = 0; }
-  } shared_guard(&h->gemm_tune, two ? 1 : 0);
-  hipStream_t ws = two ? h->wside : st;
-  int ev_used = 0;
-  auto edge = [&](hipStream_t from, hipStream_t to) -> int {  // `to` continues after everything enqueued on `from` so far
-    if (from == to) return 0;
-    if ((size_t)ev_used >= h->ev_w.size()) return SLAM_ESTATE;
-    hipEvent_t e = h->ev_w[ev_used++];
-    hipError_t r = hipEventRecord(e, from);
-    if (r != hipSuccess) return (int)r;
-    return (int)hipStreamWaitEvent(to, e, 0);
-  };
-  auto fork = [&]() -> int { return two ? edge(st, ws) : 0; };
-  const bool aux = two && h->aux_side != 0;
-  // dW (+)= a^T b on a weight-gradient stream
+  }
+  // dX[M,K] = dY[M,N] W[N,K]: with a transposed image W^T[K,N] it is the contraction-contiguous form
+  int dgrad(const bf16_t* dY, int64_t woff, bf16_t* dX, int N, int K) {
+    return Pt ? gemm_nt(dY, Pt + woff, dX, nullptr, nullptr, M, K, N, st) : gemm_nn(dY, P + woff, dX, nullptr, M, N, K, st);
+  }
+  // dW (+)= a^T b on the weight-gradient stream. handed_over: ws already waits for everything enqueued on st so far
   // is_final: the launch stores the tensor's final values (everything but the head's half of the tied embedding gradient)
-  auto wgrad = [&](int fam, const bf16_t* a, const bf16_t* b, float* g, int n, int k, bf16_t* gi, bool is_final = true,
-                   bool handed_over = false) -> int {  // handed_over: ws already waits for everything enqueued on st so far
-    if (!handed_over)
-      if (int r = fork()) return r;
+  int wgrad(int fam, const bf16_t* a, const bf16_t* b, float* g, int n, int k, bf16_t* gi, bool is_final = true, bool handed_over = false) {
+    if (!handed_over) CK(fork());
     const int slot = fam_begin(h, fam, ws);
     const int r = take(gemm_tn(a, b, g, acc, M, n, k, n, k, h->gemm_ws, h->gemm_ws_bytes, ws, two ? 1 : 0, gi, is_final ? sink() : nullptr));
     fam_end(h, slot, ws);
     return r;
-  };
-
-  if (h->untied) CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_head, VP, H, img(h->off_head)));  // the head's own tensor: final
-  else CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_embed, VP, H, nullptr, false));  // not final: the gather side adds to it below
-  TK(F_HEAD_DGRAD, st, dgrad(h->dlogits, h->off_head, h->dx, VP, H));
-  bf16_t* dh = h->dh_a;  // grad wrt hs[l+1]
-  const bool opt = h->arch == 1, q3 = h->arch == 3;
-  const int qnb = q3 ? qn_blocks(h, M) : 0;
-  if (opt) {  // final LayerNorm: dw | db slabs in part_ws, one finish launch per tensor
-    const int nbl = rmsnorm_bwd_blocks(M);
-    float* pw = h->part_ws;
-    float* pb = h->part_ws + (size_t)nbl * H;
-    TK(F_NORM_BWD, st, layernorm_bwd(h->dx, h->hs[L], P + h->off_norm, h->muf, h->rstdf, nullptr, dh, pw, pb, M, H, st));
-    CK(take(colsum_finish_many(pw, 0, nbl, H, G + h->off_norm, 0, 1, acc, st, img(h->off_norm), sink())));
-    CK(take(colsum_finish_many(pb, 0, nbl, H, G + h->off_norm_b, 0, 1, acc, st, img(h->off_norm_b), sink())));
-  } else {
-    TK(F_NORM_BWD, st, take(rmsnorm_bwd(h->dx, h->hs[L], P + h->off_norm, h->rstdf, nullptr, dh, G + h->off_norm, acc, h->part_ws, M, H, st, img(h->off_norm), sink())));
   }
-  // bias column sums of the OPT layers: behind the hand-over of the weight gradient that reads the same operand (aux), else
-  // on the main stream
-  auto bias_cols = [&](const bf16_t* X, int N, float* part) -> int {
-    if (aux) {
-      if (int r = fork()) return r;
-      return colsum_bf16(X, N, M, N, nullptr, 1, part, ws);
+  // A projection's gradients from dY [M][n] and its input X [M][k]. The bias column sums go to the layer's slab `bias_part`
+  // (null: the projection has no bias): on the weight-gradient stream behind a hand-over (aux), which then serves the
+  // weight gradient too - both read dY - else on the main stream. Then the weight gradient.
+  int proj_wgrad(int fam, const bf16_t* dY, const bf16_t* X, int64_t woff, int n, int k, float* bias_part) {
+    const bool side_cols = bias_part && aux;
+    if (side_cols) CK(fork());
+    if (bias_part) CK(colsum_bf16(dY, n, M, n, nullptr, 1, bias_part, side_cols ? ws : st));
+    return wgrad(fam, dY, X, G + woff, n, k, img(woff), true, side_cols);
+  }
+  // one launch that finishes `cnt` same-shaped tensors (the first at `off`) from their partial slabs, on `s`
+  int finish(const float* part, size_t part_stride, int nb, int N, int64_t off, size_t out_stride, int cnt, hipStream_t s) {
+    return take(colsum_finish_many(part, part_stride, nb, N, G + off, out_stride, cnt, acc, s, img(off), sink()));
+  }
+  // The family's norm backward: dx = d(norm)(dy) + dres, and per-block partials of the weight (LayerNorm: and bias) gradient.
+  // slab >= 0: a layer's norm - the partials go to that slab of ln_part (lnb_part) and finish_slabs reduces them. slab < 0:
+  // the final norm - partials in part_ws; the RMSNorm kernel finishes its weight gradient itself, head() LayerNorm's two.
+  int norm_bwd(const bf16_t* dy, const bf16_t* x, int64_t woff, const float* mu, const float* rstd, const bf16_t* dres, bf16_t* dx, int slab) {
+    const bool last = slab < 0;
+    float* pw = last ? h->part_ws : h->ln_part + (size_t)slab * h->ln_ps;
+    const int slot = fam_begin(h, F_NORM_BWD, st);
+    if (opt) {
+      float* pb = last ? h->part_ws + (size_t)rmsnorm_bwd_blocks(M) * H : h->lnb_part + (size_t)slab * h->ln_ps;
+      CK(layernorm_bwd(dy, x, P + woff, mu, rstd, dres, dx, pw, pb, M, H, st));
+    } else {
+      const int r = rmsnorm_bwd(dy, x, P + woff, rstd, dres, dx, last ? G + woff : nullptr, last ? acc : 1, pw, M, H, st,
+                                last ? img(woff) : nullptr, last ? sink() : nullptr);
+      CK(last ? take(r) : r);
     }
-    return colsum_bf16(X, N, M, N, nullptr, 1, part, st);
-  };
-
-  // "recompute": layer l's slot (l mod 3) last held layer l + 3. On the caller's stream everything of that layer is behind us;
-  // on the weight-gradient stream its last reader is layer l + 2's Wqkv gradient and bias column sums, whose d(qkv) lives in
-  // la[l + 3].qkv. Layer l + 1's weight gradients touch the slots of layers l + 1 and l + 2 only. So one side -> main edge per
-  // layer, a whole layer old by the time it is waited for ("Activation recomputation", has the table).
-  const int rc = h->recompute;
-  const bool slot_edges = rc && two && L > RC_SLOTS;
-  if (slot_edges && h->ev_rc.empty()) {
-    h->ev_rc.resize((size_t)L);
-    for (auto& ev : h->ev_rc)
-      if (hipEventCreateWithFlags(&ev, sync_event_flags()) != hipSuccess) { h->ev_rc.clear(); return h->fail(SLAM_ESTATE, "hipEventCreate failed"); }
+    fam_end(h, slot, st);
+    return SLAM_OK;
   }
-  auto rebuild = [&](int l) -> int {
+  int rebuild(int l) {
     if (slot_edges && l + RC_SLOTS - 1 < L) CK((int)hipStreamWaitEvent(st, h->ev_rc[(size_t)l + RC_SLOTS - 1], 0));
     h->gemm_tune.shared = 0;  // the forward's launches plan for a GPU of their own: so do their re-runs
     const int r = rc == 2 ? layer_forward(h, l, M, true, st) : rebuild_selective(h, l, M, st);
     h->gemm_tune.shared = two ? 1 : 0;
     return r;
-  };
-  // the weight-gradient stream has everything of layer l that reads a shared slot
-  auto slot_done = [&](int l) -> int { return slot_edges && l >= RC_SLOTS - 1 ? (int)hipEventRecord(h->ev_rc[(size_t)l], ws) : 0; };
-
-  // residual dropout: this backward belongs to a forward that dropped. The masked copies live in two buffer pairs by layer
-  // parity; on the weight-gradient stream layer l's last reader is its Wo gradient, which layer l - 2 waits for (ev_dm[l])
-  const bool drop = opt && h->fwd_drop;
-  if (drop && !h->dmask[0][0]) return h->fail(SLAM_ESTATE, "dropout: the bound workspace has no masked-gradient buffers");
-  if (drop && two && h->ev_dm.empty()) {
-    h->ev_dm.resize((size_t)L);
-    for (auto& ev : h->ev_dm)
-      if (hipEventCreateWithFlags(&ev, sync_event_flags()) != hipSuccess) { h->ev_dm.clear(); return h->fail(SLAM_ESTATE, "hipEventCreate failed"); }
   }
-  auto masked = [&](const bf16_t* dy, bf16_t* dm, int l, int site) -> int {
+  // the weight-gradient stream has everything of layer l that reads a shared slot
+  int slot_done(int l) { return slot_edges && l >= RC_SLOTS - 1 ? (int)hipEventRecord(h->ev_rc[(size_t)l], ws) : 0; }
+  // residual dropout: dy becomes its masked, rescaled copy - what flows into the projection in front of `site`
+  int masked(const bf16_t*& dy, int l, int site) {
     DropSite ds = h->fwd_site;
     ds.site = 2u * (uint32_t)l + (uint32_t)site;
-    return dropout_bwd(dy, dm, M, H, ds, st);
-  };
-
-  const int bl = bucket_layers > 0 ? bucket_layers : L;
-  int64_t bucket_end = h->n_params;  // exclusive end of the not-yet-reported range
-  int fin_hi = L;                    // layers >= fin_hi have their norm/bias partial slabs finished
-  for (int l = L - 1; l >= 0; --l) {
+    bf16_t* dm = h->dmask[l & 1][site];
+    const int r = dropout_bwd(dy, dm, M, H, ds, st);
+    dy = dm;
+    return r;
+  }
+  // LM head and final norm: dlogits -> dh, the gradient wrt hs[L]
+  int head() {
+    // tied head: dE += dlogits^T hf ; dhf = dlogits E - not final, the gather side adds to the tensor in embedding().
+    // Untied head: d lm_head = dlogits^T hf ; dhf = dlogits lm_head - the head's own tensor (off_head), final
+    CK(wgrad(F_HEAD_WGRAD, h->dlogits, h->hf, G + h->off_head, h->vpad, H, h->untied ? img(h->off_head) : nullptr, h->untied));
+    TK(F_HEAD_DGRAD, st, dgrad(h->dlogits, h->off_head, h->dx, h->vpad, H));
+    dh = h->dh_a;
+    CK(norm_bwd(h->dx, h->hs[L], h->off_norm, h->muf, h->rstdf, nullptr, dh, -1));
+    if (opt) {  // final LayerNorm: dw | db slabs in part_ws, one finish launch per tensor
+      const int nbl = rmsnorm_bwd_blocks(M);
+      CK(finish(h->part_ws, 0, nbl, H, h->off_norm, 0, 1, st));
+      CK(finish(h->part_ws + (size_t)nbl * H, 0, nbl, H, h->off_norm_b, 0, 1, st));
+    }
+    return SLAM_OK;
+  }
+  // One decoder layer, for every family: dh (wrt hs[l + 1]) -> dh (wrt hs[l]), the layer's weight gradients and its partial slabs
+  int layer(int l) {
+    const int nH = d.n_heads, nKV = d.n_kv_heads, HD = nH * d.head_dim, GU = opt ? I : 2 * I;  // GU: columns of gate|up / fc1
     const LayerOff& o = h->lo[l];
     LayerAct& a = h->la[l];
     bf16_t* dh2 = h->hs[l + 1];                              // grad wrt hmid[l]: hs[l+1] was last read by the norm backward above it
     bf16_t* dqkv = l + 1 < L ? h->la[l + 1].qkv : h->dqkv;   // layer l+1's q|k|v were last read by its attention backward
-    if (rc) CK(rebuild(l));  // before the first reader below, and before the SwiGLU backward overwrites gu
-    if (opt) {
-      // MLP: fc2 (bias + residual), ReLU, fc1 (bias); d(act) goes to this layer's own gu buffer, which nothing overwrites before
-      // the next forward (the fc1 weight gradient and the b1 column sums read it on the weight-gradient stream)
-      bf16_t* dact = a.gu;
-      // residual dropout: what flows into fc2 / out_proj is the masked, rescaled copy of the residual gradient; the LayerNorm
-      // backward below keeps reading the unmasked dh / dh2 as the residual branch's share
-      const bf16_t* dhm = dh;
-      if (drop) {
-        if (two && l + 2 < L) CK((int)hipStreamWaitEvent(st, h->ev_dm[(size_t)l + 2], 0));  // a whole layer old by now
-        CK(masked(dh, h->dmask[l & 1][1], l, 1));
-        dhm = h->dmask[l & 1][1];
-      }
-      CK(bias_cols(dhm, H, h->b2_part + (size_t)l * h->hb_ps));
-      CK(wgrad(F_WD_WGRAD, dhm, a.act, G + o.wd, H, I, img(o.wd), true, aux));
-      {
-        const int slot = fam_begin(h, F_DOWN_DGRAD, st);
-        if (Pt) {
-          CK(gemm_nt_drelu(dhm, Pt + o.wd, dact, a.act, M, I, H, st));  // the ReLU backward in the dgrad epilogue
-        } else {
-          CK(dgrad(dhm, o.wd, dact, H, I));
-          CK(relu_bwd(dact, a.act, (size_t)M * I, st));
-        }
-        fam_end(h, slot, st);
-      }
-      CK(bias_cols(dact, I, h->b1_part + (size_t)l * h->ib_ps));
-      CK(wgrad(F_WGU_WGRAD, dact, a.x2, G + o.wgu, I, H, img(o.wgu), true, aux));
-      TK(F_GATEUP_DGRAD, st, dgrad(dact, o.wgu, h->dx, I, H));
-      TK(F_NORM_BWD, st, layernorm_bwd(h->dx, a.hmid, P + o.ln2, a.mu2, a.rstd2, dh, dh2, h->ln_part + (size_t)(2 * l + 1) * h->ln_ps,
-                                       h->lnb_part + (size_t)(2 * l + 1) * h->ln_ps, M, H, st));
-      // attention: out_proj (bias + residual), then the same attention backward as Qwen2 (identity rotation tables)
-      const bf16_t* dh2m = dh2;
-      if (drop) {
-        CK(masked(dh2, h->dmask[l & 1][0], l, 0));
-        dh2m = h->dmask[l & 1][0];
-      }
-      CK(bias_cols(dh2m, H, h->bo_part + (size_t)l * h->hb_ps));
-      CK(wgrad(F_WO_WGRAD, dh2m, a.o, G + o.wo, H, HD, img(o.wo), true, aux));
-      if (drop && two) CK((int)hipEventRecord(h->ev_dm[(size_t)l], ws));  // the last reader of this layer's masked copies on ws
-      TK(F_O_DGRAD, st, dgrad(dh2m, o.wo, h->d_o, H, HD));
-      TK(F_ATTN_BWD, st, attn_bwd(a.qkv, a.o, h->d_o, a.lse, h->dsum, h->nlse, dqkv, h->dkv_part, h->cur_seg_s, h->cur_seg_e, h->attn_plan_buf, h->attn_tune, h->cosb, h->sinb,
-                  M, nH, nKV, d.head_dim, st));
-      CK(bias_cols(dqkv, h->QKV, h->bias_part + (size_t)l * h->bias_ps));
-      CK(wgrad(F_WQKV_WGRAD, dqkv, a.x1, G + o.wqkv, h->QKV, H, img(o.wqkv), true, aux));
-      CK(slot_done(l));
-      TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, h->dx, h->QKV, H));
-      dh = a.hmid;
-      TK(F_NORM_BWD, st, layernorm_bwd(h->dx, h->hs[l], P + o.ln1, a.mu1, a.rstd1, dh2, dh, h->ln_part + (size_t)(2 * l) * h->ln_ps,
-                                       h->lnb_part + (size_t)(2 * l) * h->ln_ps, M, H, st));
+    if (rc) CK(rebuild(l));  // before the first reader below, and before the activation backward overwrites gu
+    // MLP: down / fc2 (OPT: bias), activation, gate|up / fc1 (OPT: bias). d(gate|up) [M][2I] (OPT: d(fc1) [M][I]) goes to this layer's own gu
+    // buffer, which nothing overwrites before the next forward (its weight gradient and OPT's b1 column sums read it on the side stream)
+    // residual dropout: what flows into fc2 / out_proj is the masked, rescaled copy of the residual gradient; the norm
+    // backward below keeps reading the unmasked dh / dh2 as the residual branch's share
+    const bf16_t *dhm = dh, *dh2m = dh2;
+    if (drop && two && l + 2 < L) CK((int)hipStreamWaitEvent(st, h->ev_dm[(size_t)l + 2], 0));  // a whole layer old by now
+    if (drop) CK(masked(dhm, l, 1));
+    CK(proj_wgrad(F_WD_WGRAD, dhm, a.act, o.wd, H, I, opt ? h->b2_part + (size_t)l * h->hb_ps : nullptr));
+    const int slot = fam_begin(h, F_DOWN_DGRAD, st);
+    if (opt && Pt) CK(gemm_nt_drelu(dhm, Pt + o.wd, a.gu, a.act, M, I, H, st));  // the ReLU backward in the dgrad epilogue
+    else if (opt) {
+      CK(dgrad(dhm, o.wd, a.gu, H, I));
+      CK(relu_bwd(a.gu, a.act, (size_t)M * I, st));
+    } else if (Pt && h->fuse_dswiglu && (I % 128 == 0) && (H % 64 == 0)) {
+      CK(gemm_nt_dswiglu(dhm, Pt + o.wd, a.gu, M, I, H, st));  // d(act) stays in registers; a.gu -> d(gate|up)
     } else {
-    // MLP
-    CK(wgrad(F_WD_WGRAD, dh, a.act, G + o.wd, H, I, img(o.wd)));
-    {
-      const int slot = fam_begin(h, F_DOWN_DGRAD, st);
-      if (Pt && h->fuse_dswiglu && (I % 128 == 0) && (H % 64 == 0)) {
-        CK(gemm_nt_dswiglu(dh, Pt + o.wd, a.gu, M, I, H, st));  // d(act) stays in registers; a.gu -> d(gate|up)
-      } else {
-        CK(dgrad(dh, o.wd, h->dact, H, I));
-        CK(swiglu_bwd(a.gu, h->dact, M, I, GU_BLK, st));  // a.gu now holds d(gate|up)
-      }
-      fam_end(h, slot, st);
+      CK(dgrad(dhm, o.wd, h->dact, H, I));
+      CK(swiglu_bwd(a.gu, h->dact, M, I, GU_BLK, st));  // a.gu now holds d(gate|up)
     }
-    CK(wgrad(F_WGU_WGRAD, a.gu, a.x2, G + o.wgu, 2 * I, H, img(o.wgu)));
-    TK(F_GATEUP_DGRAD, st, dgrad(a.gu, o.wgu, h->dx, 2 * I, H));
-    TK(F_NORM_BWD, st, rmsnorm_bwd(h->dx, a.hmid, P + o.ln2, a.rstd2, dh, dh2, nullptr, 1, h->ln_part + (size_t)(2 * l + 1) * h->ln_ps, M, H, st));
-    // attention
-    CK(wgrad(F_WO_WGRAD, dh2, a.o, G + o.wo, H, HD, img(o.wo)));
-    TK(F_O_DGRAD, st, dgrad(dh2, o.wo, h->d_o, H, HD));
+    fam_end(h, slot, st);
+    CK(proj_wgrad(F_WGU_WGRAD, a.gu, a.x2, o.wgu, GU, H, opt ? h->b1_part + (size_t)l * h->ib_ps : nullptr));
+    TK(F_GATEUP_DGRAD, st, dgrad(a.gu, o.wgu, h->dx, GU, H));
+    CK(norm_bwd(h->dx, a.hmid, o.ln2, a.mu2, a.rstd2, dh, dh2, 2 * l + 1));
+    // attention: out projection (OPT: bias; both: residual), then one attention backward (OPT: identity rotation tables)
+    if (drop) CK(masked(dh2m, l, 0));
+    CK(proj_wgrad(F_WO_WGRAD, dh2m, a.o, o.wo, H, HD, opt ? h->bo_part + (size_t)l * h->hb_ps : nullptr));
+    if (drop && two) CK((int)hipEventRecord(h->ev_dm[(size_t)l], ws));  // the last reader of this layer's masked copies on ws
+    TK(F_O_DGRAD, st, dgrad(dh2m, o.wo, h->d_o, H, HD));
     TK(F_ATTN_BWD, st, attn_bwd(a.qkv, a.o, h->d_o, a.lse, h->dsum, h->nlse, dqkv, h->dkv_part, h->cur_seg_s, h->cur_seg_e, h->attn_plan_buf, h->attn_tune, h->cosb, h->sinb,
                 M, nH, nKV, d.head_dim, st));  // dq / dk come out already rotated back
-    if (q3) {
-      // Qwen3: dq / dk are gradients of the NORMED heads; the per-head norm backward turns them into gradients of the
-      // projection in place, before the Wqkv weight gradient and the dgrad read d(qkv). No bias, so no column sums.
-      float* pq = h->bias_part + (size_t)l * h->bias_ps;
-      TK(F_NORM_BWD, st, qknorm_bwd(dqkv, h->QKV, M, nH, nKV, d.head_dim, a.qk_raw, a.qk_rstd, P + o.q_norm, P + o.k_norm, qnb, pq,
-                                    pq + (size_t)qnb * d.head_dim, st));
-    } else if (aux) {  // behind the same hand-over as the Wqkv gradient: both read d(qkv)
-      CK(fork());
-      CK(colsum_bf16(dqkv, h->QKV, M, h->QKV, nullptr, 1, h->bias_part + (size_t)l * h->bias_ps, ws));
-    } else {
-      CK(colsum_bf16(dqkv, h->QKV, M, h->QKV, nullptr, 1, h->bias_part + (size_t)l * h->bias_ps, st));
-    }
-    CK(wgrad(F_WQKV_WGRAD, dqkv, a.x1, G + o.wqkv, h->QKV, H, img(o.wqkv), true, aux && !q3));
+    float* qkv_part = h->bias_part + (size_t)l * h->bias_ps;
+    // Qwen3: dq / dk are gradients of the NORMED heads; the per-head norm backward turns them into gradients of the
+    // projection in place, before the Wqkv weight gradient and the dgrad read d(qkv). No bias, so no column sums: the
+    // slab holds the partials of dw_q and dw_k, and the weight gradient takes a hand-over of its own
+    if (q3) TK(F_NORM_BWD, st, qknorm_bwd(dqkv, h->QKV, M, nH, nKV, d.head_dim, a.qk_raw, a.qk_rstd, P + o.q_norm, P + o.k_norm, qnb, qkv_part,
+                                          qkv_part + (size_t)qnb * d.head_dim, st));
+    CK(proj_wgrad(F_WQKV_WGRAD, dqkv, a.x1, o.wqkv, h->QKV, H, q3 ? nullptr : qkv_part));
     CK(slot_done(l));
     TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, h->dx, h->QKV, H));
     dh = a.hmid;  // grad wrt hs[l]: hmid[l] was last read by the ln2 backward above
-    TK(F_NORM_BWD, st, rmsnorm_bwd(h->dx, h->hs[l], P + o.ln1, a.rstd1, dh2, dh, nullptr, 1, h->ln_part + (size_t)(2 * l) * h->ln_ps, M, H, st));
+    CK(norm_bwd(h->dx, h->hs[l], o.ln1, a.mu1, a.rstd1, dh2, dh, 2 * l));
+    return SLAM_OK;
+  }
+  // The layers [l, l + cnt) are complete: finish their norm / bias partial slabs, one launch per kind of tensor. The order of
+  // these launches is the order of their sum-of-squares slots, and slam_grad_norm adds the partials in slot order.
+  int finish_slabs(int l, int cnt) {
+    const LayerOff& o = h->lo[l];
+    const int hd = d.head_dim, nbl = rmsnorm_bwd_blocks(M), nbc = colsum_blocks(M);
+    const size_t ls = (size_t)h->layer_stride, lnp = h->ln_ps;
+    hipStream_t fs = aux ? ws : st;  // aux: after the norm backward above (the hand-over) and the column sums already on ws
+    if (aux) CK(fork());
+    CK(finish(h->ln_part + (size_t)(2 * l) * lnp, 2 * lnp, nbl, H, o.ln1, ls, cnt, fs));
+    CK(finish(h->ln_part + (size_t)(2 * l + 1) * lnp, 2 * lnp, nbl, H, o.ln2, ls, cnt, fs));
+    const float* pq = h->bias_part + (size_t)l * h->bias_ps;
+    if (q3) {  // the q / k norm weights: two more slabs, finished like the layer norms'
+      CK(finish(pq, h->bias_ps, qnb, hd, o.q_norm, ls, cnt, fs));
+      CK(finish(pq + (size_t)qnb * hd, h->bias_ps, qnb, hd, o.k_norm, ls, cnt, fs));
+    } else {
+      CK(finish(pq, h->bias_ps, nbc, h->QKV, o.bqkv, ls, cnt, fs));
     }
-    // bucket boundaries: every `bl` layers from the top, and after each of the last two layers so that the
-    // final all-reduce (exposed behind the end of backward) only carries layer 0 + the embedding
-    const bool boundary = cb && l > 0 && ((((L - l) % bl) == 0) || l <= 2);
-    if (l == 0 || boundary) {
-      // the layers [l, fin_hi) are complete: finish their norm / bias partial slabs in three launches
-      const int cnt = fin_hi - l;
-      const int nbl = rmsnorm_bwd_blocks(M), nbc = colsum_blocks(M);
-      hipStream_t fs = aux ? ws : st;  // aux: after the norm backward above (the hand-over) and the column sums already on ws
-      if (aux) CK(fork());
-      CK(take(colsum_finish_many(h->ln_part + (size_t)(2 * l) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln1, (size_t)h->layer_stride, cnt, acc, fs, img(o.ln1), sink())));
-      CK(take(colsum_finish_many(h->ln_part + (size_t)(2 * l + 1) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln2, (size_t)h->layer_stride, cnt, acc, fs, img(o.ln2), sink())));
-      if (q3) {  // the q / k norm weights: two more slabs, finished like the layer norms'
-        const size_t ls = (size_t)h->layer_stride;
-        const float* pq = h->bias_part + (size_t)l * h->bias_ps;
-        CK(take(colsum_finish_many(pq, h->bias_ps, qnb, d.head_dim, G + o.q_norm, ls, cnt, acc, fs, img(o.q_norm), sink())));
-        CK(take(colsum_finish_many(pq + (size_t)qnb * d.head_dim, h->bias_ps, qnb, d.head_dim, G + o.k_norm, ls, cnt, acc, fs, img(o.k_norm), sink())));
-      } else {
-        CK(take(colsum_finish_many(h->bias_part + (size_t)l * h->bias_ps, h->bias_ps, nbc, h->QKV, G + o.bqkv, (size_t)h->layer_stride, cnt, acc, fs, img(o.bqkv), sink())));
-      }
-      if (opt) {  // LayerNorm biases, out_proj / fc1 / fc2 biases
-        const size_t ls = (size_t)h->layer_stride;
-        CK(take(colsum_finish_many(h->lnb_part + (size_t)(2 * l) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln1_b, ls, cnt, acc, fs, img(o.ln1_b), sink())));
-        CK(take(colsum_finish_many(h->lnb_part + (size_t)(2 * l + 1) * h->ln_ps, 2 * h->ln_ps, nbl, H, G + o.ln2_b, ls, cnt, acc, fs, img(o.ln2_b), sink())));
-        CK(take(colsum_finish_many(h->bo_part + (size_t)l * h->hb_ps, h->hb_ps, nbc, H, G + o.bo, ls, cnt, acc, fs, img(o.bo), sink())));
-        CK(take(colsum_finish_many(h->b1_part + (size_t)l * h->ib_ps, h->ib_ps, nbc, I, G + o.b1, ls, cnt, acc, fs, img(o.b1), sink())));
-        CK(take(colsum_finish_many(h->b2_part + (size_t)l * h->hb_ps, h->hb_ps, nbc, H, G + o.b2, ls, cnt, acc, fs, img(o.b2), sink())));
-      }
-      fin_hi = l;
+    if (opt) {  // LayerNorm biases, out_proj / fc1 / fc2 biases
+      CK(finish(h->lnb_part + (size_t)(2 * l) * lnp, 2 * lnp, nbl, H, o.ln1_b, ls, cnt, fs));
+      CK(finish(h->lnb_part + (size_t)(2 * l + 1) * lnp, 2 * lnp, nbl, H, o.ln2_b, ls, cnt, fs));
+      CK(finish(h->bo_part + (size_t)l * h->hb_ps, h->hb_ps, nbc, H, o.bo, ls, cnt, fs));
+      CK(finish(h->b1_part + (size_t)l * h->ib_ps, h->ib_ps, nbc, I, o.b1, ls, cnt, fs));
+      CK(finish(h->b2_part + (size_t)l * h->hb_ps, h->hb_ps, nbc, H, o.b2, ls, cnt, fs));
     }
-    if (boundary) {
-      // the side stream is in order: its last launch of layer l covers every wgrad of the range. Order it after the
-      // finish kernels above as well and hand IT to the consumer (slam_bucket_stream): main does not stall here.
-      if (!aux) CK(fork());  // aux: the finish kernels ARE on the side stream, behind a hand-over of their own
-      h->bucket_stream = two ? ws : nullptr;
-      cb(user, o.ln1, bucket_end - o.ln1);
-      h->bucket_stream = nullptr;
-      bucket_end = o.ln1;
-    }
+    return SLAM_OK;
+  }
+  // a scatter only touches the rows that occur in the batch: a tensor finished by one gets its image from a conversion pass
+  // (which also emits its partials when the values kept are the rounded ones)
+  int finish_scattered(int64_t off, size_t ne) {
+    const bool fused = fin == 2 && partials;  // the conversion sums the squares of the rounded values it stores
+    const size_t chunks = (ne + grad_chunk_elems() - 1) / grad_chunk_elems();  // fp32 values kept: chunk sums of the tensor's own range
+    const size_t slots = !partials ? 0 : fused ? (size_t)f32_to_bf16_sumsq_slots(ne) : chunks;
+    if (h->gn_used + slots > h->gn_cap) return h->fail(SLAM_ESTATE, "gradient-norm partial slots exhausted");
+    float* part = h->gn_part + h->gn_used;
+    if (fused) CK(f32_to_bf16_sumsq(G + off, IMG + off, ne, part, ws));
+    else if (IMG) CK(f32_to_bf16(G + off, IMG + off, ne, ws));  // "grad_final_next" = 2 always has one
+    if (partials && !fused) CK(grad_sumsq_chunks(G + off, 0, ne, 0, ne, part, ws));
+    h->gn_used += slots;
+    return SLAM_OK;
   }
   // gather-side embedding gradient (padding_idx row suppressed): small vocabularies run it as
   // dE += onehot(ids)^T dh0 on the wgrad GEMM, large ones as a token-ordered scatter; both deterministic
   // (on the wgrad stream: ordered after the head's contribution to the same rows)
-  CK(fork());
-  {
+  int embedding() {
+    const int VP = h->vpad;
+    CK(fork());
     const int slot = fam_begin(h, F_EMBED_WGRAD, ws);
-    // a scatter only touches the rows that occur in the batch: a tensor finished by one gets its image from a conversion pass
-    // (which also emits its partials when the values kept are the rounded ones)
-    auto finish_scattered = [&](int64_t off, size_t ne) -> int {
-      if (fin == 2 && !partials) {
-        CK(f32_to_bf16(G + off, IMG + off, ne, ws));
-      } else if (fin == 2) {
-        const int slots = f32_to_bf16_sumsq_slots(ne);
-        if (h->gn_used + (size_t)slots > h->gn_cap) return h->fail(SLAM_ESTATE, "gradient-norm partial slots exhausted");
-        CK(f32_to_bf16_sumsq(G + off, IMG + off, ne, h->gn_part + h->gn_used, ws));
-        h->gn_used += (size_t)slots;
-      } else {
-        if (IMG) CK(f32_to_bf16(G + off, IMG + off, ne, ws));
-        if (partials) {  // fp32 values kept: chunk sums of the tensor's own range (each chunk a partial of the norm)
-          const size_t slots = (ne + grad_chunk_elems() - 1) / grad_chunk_elems();
-          if (h->gn_used + slots > h->gn_cap) return h->fail(SLAM_ESTATE, "gradient-norm partial slots exhausted");
-          CK(grad_sumsq_chunks(G + off, 0, ne, 0, ne, h->gn_part + h->gn_used, ws));
-          h->gn_used += slots;
-        }
-      }
-      return SLAM_OK;
-    };
     // tied: the head wrote (or added to) the tensor above, the gather side always adds. Untied: the gather side is the
     // embedding gradient's only writer - a storing backward stores (one-hot GEMM) or zeroes first (scatter)
     const int eacc = h->untied ? acc : 1;
@@ -1715,11 +1669,57 @@ int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_b
       CK(finish_scattered(h->off_pos, ne));
     }
     fam_end(h, slot, ws);
+    return SLAM_OK;
   }
-  if (two) CK(edge(ws, st));  // join: everything after slam_backward on `stream` sees complete gradients
+};
+}  // namespace
+
+int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_bucket_cb cb, void* user,
+                  slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  if (!h->have_fwd || !h->have_loss) return h->fail(SLAM_ESTATE, "backward needs a forward with labels");
+  if (!h->grads) return h->fail(SLAM_ESTATE, "no gradient buffer bound");
+  hipStream_t st = (hipStream_t)stream;
+  CK(join_optimizer(h, st));
+  CK(join_params(h, st));
+  h->ag_ev_used = 0;  // every parameter arrival has been waited for: the pool is free for the next step's gathers
+  if (h->params_t_dirty) CK(slam_refresh_transposed(h, stream));
+  Backward b{h, st};
+  if (int r = b.begin(grad_scale, cb != nullptr)) return r;
+  GemmTuneScope tune_scope(&h->gemm_tune);
+  struct SharedGuard {  // dgrad launches of this call may plan for a GPU they share with the wgrad stream
+    GemmTune* t;
+    SharedGuard(GemmTune* t_, int on) : t(t_) { t->shared = on; }
+    ~SharedGuard() { t->shared = 0; }
+  } shared_guard(&h->gemm_tune, b.two ? 1 : 0);
+  if (int r = b.head()) return r;
+  const int L = b.L, bl = bucket_layers > 0 ? bucket_layers : L;
+  int64_t bucket_end = h->n_params;  // exclusive end of the not-yet-reported range
+  int fin_hi = L;                    // layers >= fin_hi have their norm/bias partial slabs finished
+  for (int l = L - 1; l >= 0; --l) {
+    if (int r = b.layer(l)) return r;
+    // bucket boundaries: every `bl` layers from the top, and after each of the last two layers so that the
+    // final all-reduce (exposed behind the end of backward) only carries layer 0 + the embedding
+    const bool boundary = cb && l > 0 && ((((L - l) % bl) == 0) || l <= 2);
+    if (l == 0 || boundary) {
+      if (int r = b.finish_slabs(l, fin_hi - l)) return r;
+      fin_hi = l;
+    }
+    if (boundary) {
+      // the side stream is in order: its last launch of layer l covers every wgrad of the range. Order it after the
+      // finish kernels above as well and hand IT to the consumer (slam_bucket_stream): main does not stall here.
+      if (!b.aux) CK(b.fork());  // aux: the finish kernels ARE on the side stream, behind a hand-over of their own
+      h->bucket_stream = b.two ? b.ws : nullptr;
+      cb(user, h->lo[l].ln1, bucket_end - h->lo[l].ln1);
+      h->bucket_stream = nullptr;
+      bucket_end = h->lo[l].ln1;
+    }
+  }
+  if (int r = b.embedding()) return r;
+  if (b.two) CK(b.edge(b.ws, st));  // join: everything after slam_backward on `stream` sees complete gradients
   if (cb) cb(user, 0, bucket_end);
   h->have_loss = false;  // a.gu was consumed; a second backward needs a new forward
-  h->gn_valid = partials;
+  h->gn_valid = b.partials;
   return SLAM_OK;
 }
 
