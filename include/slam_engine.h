@@ -222,8 +222,9 @@ int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t*
  * per row); n sampled continuations per prompt from one prefill (slam_kv_repeat), and the model's own log-probability of
  * every chosen token (slam_token_logprobs, below); prompts prefilled in chunks whose size, not the prompt length, sets the
  * workspace, and k tokens per row appended to a live cache (slam_extend); bans that depend on a row's own history - no
- * repeated n-gram, multi-token bad words, no EOS yet - on the device (slam_constrain_scores, below). No beam search, no
- * repetition penalty, no OPT. */
+ * repeated n-gram, multi-token bad words, no EOS yet - on the device (slam_constrain_scores, below); a draft model's proposals
+ * verified K + 1 positions at a time and rolled back where the target disagrees (slam_extend_logits, slam_sample_tokens_at,
+ * slam_spec_accept, slam_kv_rewind, below). No beam search, no repetition penalty, no OPT. */
 size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity);
 int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity);
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
@@ -255,6 +256,31 @@ int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int3
  * before any launch; an OPT engine returns SLAM_EINVAL as slam_extend does. */
 int slam_extend_score(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
                       float* logits_out, float* lp_out, int64_t* argmax_out, slam_stream_t stream);
+
+/* ---- verifying proposed tokens under a sampler: the logits of every chunk position, and the rollback (draft-model
+ * speculative decoding: HF's generate(assistant_model=)) -----------------------------------------------------------------------
+ * slam_extend_logits is the third mode of the body slam_extend and slam_extend_score share: the same launches in the same
+ * order up to the end of the layer loop, so for equal arguments the cache and lens are bit-identical to slam_extend's. Instead
+ * of the last-token head it runs the final norm of all B T chunk rows and the fp32 LM head over all of them (the projection
+ * kernel of slam_prefill / slam_decode_step's head; in groups of at most half the bound workspace tokens, each group through
+ * the logits buffer, whose attention partials are dead by then).
+ *   logits_all  fp32 [B][T][vocab] device, caller-owned. Row (b, t) with t < new_lens[b] receives the logits after token t of
+ *               row b: what slam_decode_step would have written had the chunk been fed one token at a time, up to the
+ *               rounding between the two attention kernels. Rows with t >= new_lens[b] are NOT written: they keep their bits.
+ *   lens[b] += new_lens[b] on the device, by a launch of its own behind the head; a row with new_lens[b] == 0 is inert.
+ * There is no logits_out: row (b, new_lens[b] - 1) holds what slam_extend would have put there. The logit mask is NOT applied
+ * (the sampler's `banned` does that). The host bound advances by T, as under slam_extend. Errors: those of slam_extend (with
+ * logits_all in the place of logits_out), all before any launch.
+ * slam_kv_rewind is host-only: it sets the host bound of the cached lengths to hi, 1 <= hi <= the current bound. The caller
+ * promises lens[b] <= hi for every row of the arrays it passes on (after it lowered them itself: lowering lens[b] IS the
+ * rollback - keys at or beyond lens[b] are unspecified and the next append overwrites them). The kernels keep clamping to the
+ * bound, so a broken promise stays inside the cache. Without this call the bound - and with it the split count of the decode /
+ * extend attention and the room left below `capacity` - grows by T per slam_extend_logits whatever was kept. slam_kv_repeat is
+ * refused afterwards (SLAM_ESTATE), as it is after a decode step. SLAM_EINVAL for h NULL or hi outside the range; SLAM_ESTATE
+ * without a bound, prefilled cache. */
+int slam_extend_logits(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                       float* logits_all, slam_stream_t stream);
+int slam_kv_rewind(SlamEngine* h, int32_t hi);
 
 /* ---- choosing the next token on the device (what HF's logits processors + torch.multinomial do between two decode steps) ----
  * slam_sample_tokens needs no engine: it reads fp32 logits [B][vocab] (row stride vocab, 4-byte aligned; odd vocabularies
@@ -300,6 +326,52 @@ size_t slam_sample_workspace_bytes(int32_t B, int32_t vocab, int32_t top_k);
 int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
                        const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
                        int64_t out_stride, void* ws, size_t ws_bytes, slam_stream_t stream);
+/* slam_sample_tokens_at is slam_sample_tokens - the same kernels with one more nullable pointer - for rows that sit at
+ * different steps: the K + 1 positions of a verified chunk, or sequences that have emitted different numbers of tokens. Row b
+ * belongs to sequence q = b / group and is its column j = b % group. Its row id is r = row_ids ? row_ids[q] : q, its step is
+ * s = desc->step + (steps ? steps[q] : 0) + j (uint32 arithmetic), and out[b * out_stride + out_col] receives the token when
+ * out is given. done and next are indexed by b; logits has B rows. Everything else is slam_sample_tokens' contract, word for
+ * word: a row's token is the one slam_sample_tokens picks from the same logits with row id r at step s.
+ * steps: uint32 [B / group] device, nullable; row_ids: int64 [B / group]. SLAM_EINVAL as slam_sample_tokens, plus group < 1,
+ * B not a multiple of group, or out_col < 0. slam_sample_tokens is the case steps = NULL, group = 1, out_col = desc->step. */
+int slam_sample_tokens_at(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                          const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                          int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group, int32_t out_col,
+                          slam_stream_t stream);
+
+/* ---- the acceptance rule of draft-model speculative decoding, on the device -------------------------------------------------
+ * slam_spec_accept needs no engine. One round of assisted generation proposes K tokens per row with a draft model, lets the
+ * target sample its own token at every chunk position (slam_extend_logits + slam_sample_tokens_at with the SAME stateless
+ * draw the draft used), and keeps the target's tokens up to and including the first one the draft did not propose. Because
+ * the draw is a function of (logits, seed, row id, step), the kept tokens are exactly what one-token-per-step decoding emits.
+ * Per row b, with x0 = chunk[b][0] the pending token (emitted, not yet in the target's cache), d_i = chunk[b][i] (1 <= i <= K)
+ * the proposals and t_j = tgt[b][j] (0 <= j <= K) the target's token for the position behind column j:
+ *   done[b] != 0 on entry: the row emits nothing (m = 0, lag = 0).
+ *   otherwise   n_acc = the largest n <= K with d_i == t_{i-1} for all 1 <= i <= n. The candidates are t_0 .. t_{n_acc}; they
+ *               are cut to max_new - n_new[b] tokens, then behind the first one that is an eos_ids entry (which sets done[b] =
+ *               1); m >= 1 tokens remain (a row whose budget is not positive emits none and is marked done). Reaching
+ *               n_new[b] + m == max_new sets done[b] = 1 too.
+ * Writes, all of them plain stores of the row's own thread:
+ *   out[b * out_stride + n_new[b] + i] = t_i for i < m (nothing else of out is touched); n_new[b] += m;
+ *   lens_t[b] = prompt_len[b] + n_new[b] - 1   the target's key count, ABSOLUTE - this store is the rollback;
+ *   lag = (m == K + 1); lens_d[b] = lens_t[b] - lag   the draft's key count: after full acceptance its cache lacks d_K;
+ *   chunk[b][0] = the last emitted token (unchanged when m = 0);
+ *   draft_ids[b][0 .. 2) = lag ? { d_K, t_K } : { chunk[b][0], pad_id }; draft_new_lens[b] = done ? 0 : 1 + lag   (the
+ *               draft's catch-up block for slam_extend with T = 2); tgt_new_lens[b] = done ? 0 : K + 1;
+ *   stats int32 [5] = { rows not done after the round, max lens_t, max lens_d (both over ALL rows: the arguments of
+ *               slam_kv_rewind), tokens emitted this round (sum of m), proposals among them (sum of min(m, n_acc)) }.
+ * Rows that are done get lens_t / lens_d written too: the draft's decode steps advance every row. The invariant a round
+ * starts from and ends in: the committed sequence of row b is its prompt plus n_new[b] tokens; the target's cache holds it
+ * without its last token, the draft's cache that prefix without `lag` more tokens.
+ * One launch of one block, a thread per row; integer work only, the five sums / maxima combined through shared memory in a
+ * fixed order (no atomics). chunk, tgt: int64 [B][K + 1]; n_new, prompt_len, lens_t, lens_d, draft_new_lens, tgt_new_lens:
+ * int32 [B]; done: uint8 [B]; out: int64 [B][out_stride]; draft_ids: int64 [B][2]; eos_ids: int32 [n_eos] - all device memory.
+ * SLAM_EINVAL before the launch: a NULL array (eos_ids may be NULL when n_eos == 0); B outside 1 .. 1024; K outside 1 .. 15;
+ * n_eos outside 0 .. 16; max_new < 1 or out_stride < max_new. */
+int slam_spec_accept(int64_t* chunk, const int64_t* tgt, int32_t B, int32_t K, int32_t max_new, int32_t pad_id,
+                     const int32_t* eos_ids, int32_t n_eos, const int32_t* prompt_len, int32_t* n_new, uint8_t* done,
+                     int64_t* out, int64_t out_stride, int32_t* lens_t, int32_t* lens_d, int64_t* draft_ids,
+                     int32_t* draft_new_lens, int32_t* tgt_new_lens, int32_t* stats, slam_stream_t stream);
 
 /* ---- per-row bans that depend on the row's own history (HF's no_repeat_ngram_size, multi-token bad_words_ids,
  * min_new_tokens / min_length, begin_suppress_tokens), between the logits and slam_sample_tokens ------------------------------

@@ -612,6 +612,97 @@ __global__ __launch_bounds__(256) void extend_finish_kernel(const float* __restr
   if (blockIdx.x == 0 && threadIdx.x == 0) lens[b] = lens[b] + nl;
 }
 
+// slam_extend_logits: chunk rows [m0, m0 + rows) of fp32 logits (src row 0 = chunk row m0) to dst[B T][vocab]; only the rows
+// (b, t) with t < new_lens[b] are stored. grid (.., rows)
+__global__ __launch_bounds__(256) void extend_store_rows_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                                const int* __restrict__ new_lens, int m0, int T, int vocab) {
+  const int m = m0 + blockIdx.y;
+  const int b = m / T, t = m - b * T;
+  if (t >= new_lens[b]) return;
+  const float* s = src + (size_t)blockIdx.y * vocab;
+  float* d = dst + (size_t)m * vocab;
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < vocab; c += gridDim.x * 256) d[c] = s[c];
+}
+
+// lens[b] += clamp(new_lens[b], 0, T)
+__global__ void lens_add_kernel(int* __restrict__ lens, const int* __restrict__ new_lens, int B, int T) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) lens[b] = lens[b] + min(max(new_lens[b], 0), T);
+}
+
+// ---- speculative decoding: the acceptance rule (include/slam_engine.h: slam_spec_accept) --------------------------------------
+struct SpecParams {
+  int B, K, max_new, pad_id, n_eos;
+  long long out_stride;
+};
+
+// one block of 1024 threads, thread b = row b. Integer work only; the five statistics go through LDS in a fixed order.
+__global__ __launch_bounds__(1024) void spec_accept_kernel(int64_t* __restrict__ chunk, const int64_t* __restrict__ tgt,
+                                                           const int* __restrict__ eos_ids, const int* __restrict__ prompt_len,
+                                                           int* __restrict__ n_new, uint8_t* __restrict__ done,
+                                                           int64_t* __restrict__ out, int* __restrict__ lens_t,
+                                                           int* __restrict__ lens_d, int64_t* __restrict__ draft_ids,
+                                                           int* __restrict__ draft_new_lens, int* __restrict__ tgt_new_lens,
+                                                           int* __restrict__ stats, SpecParams P) {
+  __shared__ int red[5][16];
+  const int b = threadIdx.x, lane = b & 63;
+  int live = 0, lt = 0, ld = 0, emitted = 0, accepted = 0;
+  if (b < P.B) {
+    int64_t* ch = chunk + (size_t)b * (P.K + 1);
+    const int64_t* tg = tgt + (size_t)b * (P.K + 1);
+    const int nn = min(max(n_new[b], 0), P.max_new);
+    bool dn = done[b] != 0;
+    int m = 0, nacc = 0;
+    if (!dn) {
+      while (nacc < P.K && ch[nacc + 1] == tg[nacc]) ++nacc;
+      m = min(nacc + 1, P.max_new - nn);  // the budget; not positive only for a row that should have been done
+      for (int i = 0; i < m; ++i) {
+        bool is_eos = false;
+        for (int e = 0; e < P.n_eos; ++e) is_eos = is_eos || (int64_t)eos_ids[e] == tg[i];
+        if (is_eos) { m = i + 1; dn = true; break; }
+      }
+      if (nn + m >= P.max_new) dn = true;
+      for (int i = 0; i < m; ++i) out[(long long)b * P.out_stride + nn + i] = tg[i];
+      emitted = m;
+      accepted = min(m, nacc);
+    }
+    const int lag = m == P.K + 1 ? 1 : 0;
+    const int64_t last = m > 0 ? tg[m - 1] : ch[0];
+    const int64_t dK = ch[P.K];
+    lt = prompt_len[b] + nn + m - 1;
+    ld = lt - lag;
+    n_new[b] = nn + m;
+    lens_t[b] = lt;
+    lens_d[b] = ld;
+    ch[0] = last;
+    draft_ids[2 * b] = lag ? dK : last;
+    draft_ids[2 * b + 1] = lag ? tg[P.K] : (int64_t)P.pad_id;
+    draft_new_lens[b] = dn ? 0 : 1 + lag;
+    tgt_new_lens[b] = dn ? 0 : P.K + 1;
+    done[b] = dn ? 1 : 0;
+    live = dn ? 0 : 1;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    live += __shfl_xor(live, o, 64);
+    emitted += __shfl_xor(emitted, o, 64);
+    accepted += __shfl_xor(accepted, o, 64);
+    lt = max(lt, __shfl_xor(lt, o, 64));
+    ld = max(ld, __shfl_xor(ld, o, 64));
+  }
+  if (lane == 0) {
+    const int w = b >> 6;
+    red[0][w] = live; red[1][w] = lt; red[2][w] = ld; red[3][w] = emitted; red[4][w] = accepted;
+  }
+  __syncthreads();
+  if (b == 0) {
+    for (int w = 1; w < 16; ++w) {
+      live += red[0][w]; lt = max(lt, red[1][w]); ld = max(ld, red[2][w]); emitted += red[3][w]; accepted += red[4][w];
+    }
+    stats[0] = live; stats[1] = lt; stats[2] = ld; stats[3] = emitted; stats[4] = accepted;
+  }
+}
+
 
 // ---- token sampling ---------------------------------------------------------------------------------------------------------
 constexpr int SP_THREADS = 256;
@@ -748,13 +839,14 @@ struct SampleParams {
   int do_sample, k, vocab, idbits, nch, pad_id, n_eos;
   float inv_t, top_p;
   uint32_t k0, k1, step;
-  long long out_stride;
+  long long out_stride, out_col;
+  int group;  // rows per sequence: row b is column b % group of sequence b / group (slam_sample_tokens_at)
 };
 
 SLAM_DEVICE void emit_token(long long tok, bool mark, int b, const SampleParams& P, const int* eos_ids, uint8_t* done,
                             int64_t* next, int64_t* out) {
   next[b] = tok;
-  if (out) out[(long long)b * P.out_stride + P.step] = tok;
+  if (out) out[(long long)b * P.out_stride + P.out_col] = tok;
   if (mark && done)
     for (int e = 0; e < P.n_eos; ++e)
       if (eos_ids[e] == (int)tok) { done[b] = 1; break; }
@@ -786,7 +878,8 @@ __global__ __launch_bounds__(SP_THREADS) void sample_finish_kernel(const float* 
                                                                    const int64_t* __restrict__ row_ids,
                                                                    const int* __restrict__ eos_ids, uint8_t* __restrict__ done,
                                                                    int64_t* __restrict__ next, int64_t* __restrict__ out,
-                                                                   SampleParams P, const u64_t* __restrict__ ws) {
+                                                                   SampleParams P, const u64_t* __restrict__ ws,
+                                                                   const uint32_t* __restrict__ steps) {
   __shared__ u64_t buf[ROW ? SP_CHUNK / 2 : SP_CACHE];
   __shared__ SampleShared sh;
   const int b = blockIdx.x, t = threadIdx.x;
@@ -845,8 +938,10 @@ __global__ __launch_bounds__(SP_THREADS) void sample_finish_kernel(const float* 
   }
   float total = 0.f;
   for (int j = 0; j < m; ++j) total += sh.w[j];
-  const uint64_t r = row_ids ? (uint64_t)row_ids[b] : (uint64_t)b;
-  const Philox4 rnd = philox4x32_10((uint32_t)r, P.step, (uint32_t)(r >> 32), 0x53414D50u, P.k0, P.k1);
+  const int q = b / P.group;  // the row's sequence; group = 1 and steps = NULL are slam_sample_tokens
+  const uint64_t r = row_ids ? (uint64_t)row_ids[q] : (uint64_t)q;
+  const uint32_t step = P.step + (steps ? steps[q] : 0u) + (uint32_t)(b - q * P.group);
+  const Philox4 rnd = philox4x32_10((uint32_t)r, step, (uint32_t)(r >> 32), 0x53414D50u, P.k0, P.k1);
   const float u = (float)(rnd.w[0] >> 8) * 5.9604644775390625e-08f;  // 2^-24
   const float target = u * total;
   int pick = m - 1;
@@ -1414,6 +1509,39 @@ int extend_finish(const float* src, float* dst, const int* new_lens, int* lens, 
   return (int)hipGetLastError();
 }
 
+int extend_store_rows(const float* src, float* dst, const int* new_lens, int m0, int rows, int B, int T, int vocab,
+                      hipStream_t st) {
+  if (rows <= 0 || rows > 65535 || m0 < 0 || T <= 0 || (int64_t)m0 + rows > (int64_t)B * T) return -1;
+  unsigned gx = nblk((size_t)vocab, 256);
+  if (gx > 64) gx = 64;
+  extend_store_rows_kernel<<<dim3(gx, rows), 256, 0, st>>>(src, dst, new_lens, m0, T, vocab);
+  return (int)hipGetLastError();
+}
+
+int lens_add(int* lens, const int* new_lens, int B, int T, hipStream_t st) {
+  lens_add_kernel<<<nblk((size_t)B, 256), 256, 0, st>>>(lens, new_lens, B, T);
+  return (int)hipGetLastError();
+}
+
+int spec_accept(const SpecArgs& a, hipStream_t st) {
+  if (!a.chunk || !a.tgt || !a.prompt_len || !a.n_new || !a.done || !a.out || !a.lens_t || !a.lens_d || !a.draft_ids ||
+      !a.draft_new_lens || !a.tgt_new_lens || !a.stats)
+    return -1;
+  if (a.B < 1 || a.B > SPEC_MAX_B || a.K < 1 || a.K > SPEC_MAX_K || a.n_eos < 0 || a.n_eos > 16 || (a.n_eos > 0 && !a.eos_ids))
+    return -1;
+  if (a.max_new < 1 || a.out_stride < a.max_new) return -1;
+  SpecParams P;
+  P.B = a.B;
+  P.K = a.K;
+  P.max_new = a.max_new;
+  P.pad_id = a.pad_id;
+  P.n_eos = a.n_eos;
+  P.out_stride = a.out_stride;
+  spec_accept_kernel<<<1, 1024, 0, st>>>(a.chunk, a.tgt, a.eos_ids, a.prompt_len, a.n_new, a.done, a.out, a.lens_t, a.lens_d,
+                                          a.draft_ids, a.draft_new_lens, a.tgt_new_lens, a.stats, P);
+  return (int)hipGetLastError();
+}
+
 
 static int sample_chunks(int vocab) { return (vocab + SP_CHUNK - 1) / SP_CHUNK; }
 
@@ -1428,6 +1556,7 @@ int sample_tokens(const SampleArgs& a, hipStream_t st) {
   const int k = a.do_sample ? a.top_k : 1;
   if (k < 1 || k > SP_MAXK || !(a.temperature > 0.f) || !(a.top_p > 0.f) || a.top_p > 1.f) return -1;
   if (a.n_eos < 0 || (a.n_eos > 0 && !a.eos_ids)) return -1;
+  if (a.group < 1 || a.B % a.group != 0) return -1;
   if (!a.ws || ((uintptr_t)a.ws & 7) || a.ws_bytes < sample_workspace_bytes(a.B, a.vocab, k)) return -1;
   SampleParams P;
   P.do_sample = a.do_sample ? 1 : 0;
@@ -1444,12 +1573,14 @@ int sample_tokens(const SampleArgs& a, hipStream_t st) {
   P.k1 = (uint32_t)(a.seed >> 32);
   P.step = a.step;
   P.out_stride = a.out_stride;
+  P.out_col = a.out_col >= 0 ? a.out_col : (long long)a.step;
+  P.group = a.group;
   u64_t* ws = reinterpret_cast<u64_t*>(a.ws);
   if (P.nch == 1) {
-    sample_finish_kernel<true><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws);
+    sample_finish_kernel<true><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws, a.steps);
   } else {
     sample_select_kernel<<<dim3(P.nch, a.B), SP_THREADS, 0, st>>>(a.logits, a.banned, a.done, P, ws);
-    sample_finish_kernel<false><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws);
+    sample_finish_kernel<false><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws, a.steps);
   }
   return (int)hipGetLastError();
 }

@@ -1289,10 +1289,13 @@ int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_
 }
 
 namespace {
-// slam_extend and slam_extend_score: one body. score = false is slam_extend, launch for launch; score = true adds, between the
-// layer loop and the last-token head, the final norm of all B T rows and the fused head + row statistics.
+// slam_extend, slam_extend_score and slam_extend_logits: one body. EXT_LAST is slam_extend, launch for launch; EXT_SCORE adds,
+// between the layer loop and the last-token head, the final norm of all B T rows and the fused head + row statistics; EXT_ALL
+// replaces the last-token head by the final norm and the fp32 head of all B T rows (logits_out is then the [B][T][vocab] array).
+enum ExtendMode { EXT_LAST, EXT_SCORE, EXT_ALL };
 int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
-                  float* logits_out, bool score, float* lp_out, int64_t* argmax_out, slam_stream_t stream) {
+                  float* logits_out, ExtendMode mode, float* lp_out, int64_t* argmax_out, slam_stream_t stream) {
+  const bool score = mode == EXT_SCORE;
   if (!h || !ids || !new_lens || !lens || !logits_out || B <= 0 || T <= 0 || (score && !lp_out)) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
@@ -1350,6 +1353,22 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
     CK(score_rows(h->hf, P + h->off_head, tg, h->logit_mask, M, d.vocab, H, new_lens, T, lp_out, argmax_out, h->logits,
                   part_bytes, st));
   }
+  if (mode == EXT_ALL) {
+    // every chunk position: final norm of the B T rows, then the fp32 head in groups of G rows through the logits buffer (the
+    // attention partials are dead; G fp32 rows of vocab fit in 2 G bf16 rows of vpad), each group's real rows stored behind it
+    CK(norm_fwd(h, h->hs[L], h->off_norm, h->off_norm_b, h->hf, h->muf, h->rstdf, M, st));
+    const int G = (int)std::min<int64_t>(h->max_tokens / 2, 32768);
+    float* lg = (float*)h->logits;
+    for (int m0 = 0; m0 < M; m0 += G) {
+      const int rows = std::min(G, M - m0);
+      CK(decode_proj(h, h->hf + (size_t)m0 * H, P + h->off_head, nullptr, lg, nullptr, nullptr, rows, d.vocab, H, st));
+      CK(extend_store_rows(lg, logits_out, new_lens, m0, rows, B, T, d.vocab, st));
+    }
+    CK(lens_add(lens, new_lens, B, T, st));
+    if (h->kv_hi == h->kv_T) h->kv_T += T;
+    h->kv_hi += T;
+    return SLAM_OK;
+  }
   // each row's last real token: gather, final norm, one fp32 head launch over B rows; inert rows keep their logits and lens
   CK(gather_last_rows(h->hs[L], h->dx, new_lens, B, T, H, st));
   float* lg = (float*)h->logits;
@@ -1363,12 +1382,27 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
 
 int slam_extend(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
                 float* logits_out, slam_stream_t stream) {
-  return extend_common(h, ids, new_lens, lens, B, T, logits_out, false, nullptr, nullptr, stream);
+  return extend_common(h, ids, new_lens, lens, B, T, logits_out, EXT_LAST, nullptr, nullptr, stream);
 }
 
 int slam_extend_score(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
                       float* logits_out, float* lp_out, int64_t* argmax_out, slam_stream_t stream) {
-  return extend_common(h, ids, new_lens, lens, B, T, logits_out, true, lp_out, argmax_out, stream);
+  return extend_common(h, ids, new_lens, lens, B, T, logits_out, EXT_SCORE, lp_out, argmax_out, stream);
+}
+
+int slam_extend_logits(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, int32_t* lens, int32_t B, int32_t T,
+                       float* logits_all, slam_stream_t stream) {
+  return extend_common(h, ids, new_lens, lens, B, T, logits_all, EXT_ALL, nullptr, nullptr, stream);
+}
+
+int slam_kv_rewind(SlamEngine* h, int32_t hi) {
+  if (!h) return SLAM_EINVAL;
+  if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+  if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_kv_rewind needs a slam_prefill into the bound cache first");
+  if (hi < 1 || hi > h->kv_hi) return h->fail(SLAM_EINVAL, "slam_kv_rewind: hi outside 1 .. the current bound");
+  h->kv_hi = hi;
+  h->kv_T = -1;  // as after a decode step: slam_kv_repeat is refused until the next prefill
+  return SLAM_OK;
 }
 
 namespace {
@@ -2553,9 +2587,11 @@ int slam_op_dropout_bwd(const void* dy, void* dy_masked, int M, int H, int32_t t
 }
 
 size_t slam_sample_workspace_bytes(int32_t B, int32_t vocab, int32_t top_k) { return sample_workspace_bytes(B, vocab, top_k); }
-int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
-                       const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
-                       int64_t out_stride, void* ws, size_t ws_bytes, slam_stream_t stream) {
+// slam_sample_tokens and slam_sample_tokens_at: one argument block; the plain call is steps = NULL, group = 1, out_col = step
+static int sample_any(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                      const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                      int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group, int64_t out_col,
+                      slam_stream_t stream) {
   if (!desc || (desc->do_sample != 0 && desc->do_sample != 1) || desc->n_eos > 16) return SLAM_EINVAL;
   SampleArgs a;  // sample_tokens refuses the rest (-1 = SLAM_EINVAL) before it launches anything
   a.logits = logits;
@@ -2576,9 +2612,54 @@ int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint
   a.next = next;
   a.out = out;
   a.out_stride = out_stride;
+  a.steps = steps;
+  a.group = group;
+  a.out_col = out_col;
   a.ws = ws;
   a.ws_bytes = ws_bytes;
   return sample_tokens(a, (hipStream_t)stream);
+}
+int slam_sample_tokens(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                       const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                       int64_t out_stride, void* ws, size_t ws_bytes, slam_stream_t stream) {
+  return sample_any(logits, B, vocab, banned, desc, row_ids, eos_ids, done, next, out, out_stride, ws, ws_bytes, nullptr, 1, -1,
+                    stream);
+}
+int slam_sample_tokens_at(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                          const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                          int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group, int32_t out_col,
+                          slam_stream_t stream) {
+  if (group < 1 || out_col < 0 || ((uintptr_t)steps & 3)) return SLAM_EINVAL;
+  return sample_any(logits, B, vocab, banned, desc, row_ids, eos_ids, done, next, out, out_stride, ws, ws_bytes, steps, group,
+                    out_col, stream);
+}
+
+int slam_spec_accept(int64_t* chunk, const int64_t* tgt, int32_t B, int32_t K, int32_t max_new, int32_t pad_id,
+                     const int32_t* eos_ids, int32_t n_eos, const int32_t* prompt_len, int32_t* n_new, uint8_t* done,
+                     int64_t* out, int64_t out_stride, int32_t* lens_t, int32_t* lens_d, int64_t* draft_ids,
+                     int32_t* draft_new_lens, int32_t* tgt_new_lens, int32_t* stats, slam_stream_t stream) {
+  static_assert(SPEC_MAX_B == 1024 && SPEC_MAX_K == 15, "the header's limits are the kernel's");
+  SpecArgs a;  // spec_accept refuses every bad argument (-1 = SLAM_EINVAL) before it launches anything
+  a.chunk = chunk;
+  a.tgt = tgt;
+  a.B = B;
+  a.K = K;
+  a.max_new = max_new;
+  a.pad_id = pad_id;
+  a.n_eos = n_eos;
+  a.eos_ids = eos_ids;
+  a.prompt_len = prompt_len;
+  a.n_new = n_new;
+  a.done = done;
+  a.out = out;
+  a.out_stride = out_stride;
+  a.lens_t = lens_t;
+  a.lens_d = lens_d;
+  a.draft_ids = draft_ids;
+  a.draft_new_lens = draft_new_lens;
+  a.tgt_new_lens = tgt_new_lens;
+  a.stats = stats;
+  return spec_accept(a, (hipStream_t)stream);
 }
 
 int slam_constrain_scores(const float* logits, float* scores, int32_t B, int32_t vocab, const SlamConstrainDesc* desc,

@@ -296,6 +296,32 @@ int attn_extend(const bf16_t* qkv, const int* base_lens, const int* new_lens, bf
 int extend_positions(const int* lens, int64_t* pos, int B, int T, hipStream_t st);
 // dst[b] = src[b] (fp32 [B][vocab]) and lens[b] += new_lens[b] for the rows with new_lens[b] > 0; the others keep their bits
 int extend_finish(const float* src, float* dst, const int* new_lens, int* lens, int B, int T, int vocab, hipStream_t st);
+// slam_extend_logits: rows [m0, m0 + rows) of the chunk's fp32 logits (src row 0 = chunk row m0) into dst [B T][vocab], only
+// where t < new_lens[b]; and lens[b] += clamp(new_lens[b], 0, T)
+int extend_store_rows(const float* src, float* dst, const int* new_lens, int m0, int rows, int B, int T, int vocab,
+                      hipStream_t st);
+int lens_add(int* lens, const int* new_lens, int B, int T, hipStream_t st);
+// The acceptance rule of speculative decoding (include/slam_engine.h: slam_spec_accept): one block, a thread per row.
+constexpr int SPEC_MAX_B = 1024;
+constexpr int SPEC_MAX_K = 15;
+struct SpecArgs {
+  int64_t* chunk = nullptr;        // [B][K + 1]: pending token, then the K proposals; column 0 is rewritten
+  const int64_t* tgt = nullptr;    // [B][K + 1]: the target's token behind every column
+  int B = 0, K = 0, max_new = 0, pad_id = 0, n_eos = 0;
+  const int* eos_ids = nullptr;    // device, [n_eos]
+  const int* prompt_len = nullptr;
+  int* n_new = nullptr;
+  uint8_t* done = nullptr;
+  int64_t* out = nullptr;          // [B][out_stride]
+  int64_t out_stride = 0;
+  int* lens_t = nullptr;
+  int* lens_d = nullptr;
+  int64_t* draft_ids = nullptr;    // [B][2]
+  int* draft_new_lens = nullptr;
+  int* tgt_new_lens = nullptr;
+  int* stats = nullptr;            // [5]
+};
+int spec_accept(const SpecArgs& a, hipStream_t st);
 // The next token of every row of fp32 logits [B][vocab] (row stride vocab, any 4-byte alignment), chosen on the device by the
 // contract of include/slam_engine.h (slam_sample_tokens): one argument block from the entry point down to the launches.
 struct SampleArgs {
@@ -313,6 +339,9 @@ struct SampleArgs {
   int64_t* next = nullptr;           // [B]
   int64_t* out = nullptr;            // nullable: out[b * out_stride + step] = the token
   int64_t out_stride = 0;
+  const uint32_t* steps = nullptr;   // nullable: [B / group], added to step per sequence (slam_sample_tokens_at)
+  int group = 1;                     // rows per sequence: row b draws with row id (b / group) at step + steps[..] + b % group
+  int64_t out_col = -1;              // the column of out; negative = step
   void* ws = nullptr;                // sample_workspace_bytes(B, vocab, do_sample ? top_k : 1), 8-byte aligned
   size_t ws_bytes = 0;
 };

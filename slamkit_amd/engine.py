@@ -106,6 +106,11 @@ def load_library(path: Optional[str] = None):
         "slam_kv_repeat": (C.c_int, [vp, i32, vp, vp, vp]),
         "slam_extend": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
         "slam_extend_score": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "slam_extend_logits": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
+        "slam_kv_rewind": (C.c_int, [vp, i32]),
+        "slam_sample_tokens_at": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp, i32,
+                                            i32, vp]),
+        "slam_spec_accept": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
         "slam_token_logprobs": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, sz, vp]),
         "slam_bucket_stream": (vp, [vp]),
@@ -238,6 +243,42 @@ def sample_tokens(logits, desc: SlamSampleDesc, next_ids, ws, banned=None, row_i
                                           stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_sample_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+def sample_tokens_at(logits, desc: SlamSampleDesc, next_ids, ws, steps=None, group: int = 1, out_col: int = 0, banned=None,
+                     row_ids=None, eos_ids=None, done=None, out=None, stream: Optional[int] = None):
+    """slam_sample_tokens_at: sample_tokens for rows at different steps. Row b of the fp32 logits [B, vocab] is column
+    b % group of sequence b // group: it draws with row id row_ids[b // group] (default b // group) at step
+    desc.step + steps[b // group] + b % group, and out[b, out_col] receives the token. steps: int32 / uint32 [B // group]
+    (non-negative), None = zeros. next_ids / done are indexed by b. Only enqueues work."""
+    B, V = logits.shape
+    rc = load_library().slam_sample_tokens_at(_ptr(logits), B, V, _ptr(banned), C.byref(desc), _ptr(row_ids), _ptr(eos_ids),
+                                             _ptr(done), _ptr(next_ids), _ptr(out), out.stride(0) if out is not None else 0,
+                                             _ptr(ws), ws.numel() * ws.element_size(), _ptr(steps), int(group), int(out_col),
+                                             stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_sample_tokens_at failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+SPEC_MAX_ROWS = 1024  # slam_spec_accept: one block, a thread per row
+SPEC_MAX_K = 15       # proposals per round
+SPEC_STATS = ("live", "max_lens_t", "max_lens_d", "emitted", "accepted")
+
+
+def spec_accept(chunk, tgt, K: int, max_new: int, pad_id: int, eos_ids, prompt_len, n_new, done, out, lens_t, lens_d, draft_ids,
+                draft_new_lens, tgt_new_lens, stats, stream: Optional[int] = None):
+    """slam_spec_accept: the acceptance rule of one round of assisted generation for all B rows in one launch (the contract is
+    in include/slam_engine.h). chunk / tgt int64 [B, K + 1]; prompt_len / n_new / lens_t / lens_d / draft_new_lens /
+    tgt_new_lens int32 [B]; done uint8 [B]; out int64 [B, >= max_new]; draft_ids int64 [B, 2]; stats int32 [5] (SPEC_STATS);
+    eos_ids int32 or None. Only enqueues work."""
+    B = chunk.shape[0]
+    rc = load_library().slam_spec_accept(_ptr(chunk), _ptr(tgt), B, int(K), int(max_new), int(pad_id), _ptr(eos_ids),
+                                        0 if eos_ids is None else int(eos_ids.numel()), _ptr(prompt_len), _ptr(n_new), _ptr(done),
+                                        _ptr(out), out.stride(0), _ptr(lens_t), _ptr(lens_d), _ptr(draft_ids),
+                                        _ptr(draft_new_lens), _ptr(tgt_new_lens), _ptr(stats),
+                                        stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_spec_accept failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 def constrain_scores(logits, scores, desc: SlamConstrainDesc, prompt, prompt_len, new=None, done=None, eos_ids=None,
@@ -506,6 +547,16 @@ class Engine:
         self._ck(self.lib.slam_extend_score(self.h, _ptr(ids), _ptr(new_lens), _ptr(lens), B, T, _ptr(logits_out),
                                             _ptr(lp_out), _ptr(argmax_out),
                                             stream if stream is not None else current_stream_ptr()))
+
+    def extend_logits(self, ids, new_lens, lens, B: int, T: int, logits_all, stream: Optional[int] = None):
+        """slam_extend_logits: slam_extend (same cache and lens bits) that writes the fp32 logits of EVERY real chunk position:
+        logits_all fp32 [B, T, vocab]; rows t >= new_lens[b] keep their bits. Only enqueues work."""
+        self._ck(self.lib.slam_extend_logits(self.h, _ptr(ids), _ptr(new_lens), _ptr(lens), B, T, _ptr(logits_all),
+                                             stream if stream is not None else current_stream_ptr()))
+
+    def kv_rewind(self, hi: int):
+        """slam_kv_rewind: lower the host bound of the cached lengths to hi (host only; the caller has lowered lens itself)."""
+        self._ck(self.lib.slam_kv_rewind(self.h, int(hi)))
 
     def set_logit_mask(self, mask_u8=None):
         """mask_u8: uint8 device tensor of padded_vocab() bytes (non-zero = column outside the softmax) or None."""

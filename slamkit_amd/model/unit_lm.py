@@ -1085,7 +1085,8 @@ class UnitLM(TokenLM):
                  num_return_sequences: Optional[int] = None, return_logprobs: bool = False,
                  prefill_chunk: Optional[int] = None, no_repeat_ngram_size: Optional[int] = None,
                  min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
-                 begin_suppress_tokens: Optional[List[int]] = None, suppress_tokens: Optional[List[int]] = None, **kwargs):
+                 begin_suppress_tokens: Optional[List[int]] = None, suppress_tokens: Optional[List[int]] = None,
+                 assistant_model: Optional["UnitLM"] = None, num_assistant_tokens: Optional[int] = None, **kwargs):
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
@@ -1135,7 +1136,24 @@ class UnitLM(TokenLM):
         is its REAL tokens: the prompt without its padding, then its new tokens. HF's windows run over input_ids as passed,
         left-pad ids included; the two agree unless a window contains a pad id. `return_logprobs` still returns the raw-logit
         log-probs: the bans are then written into a scores buffer of their own, which only the token choice reads. With every
-        one of these options off, no launch is added and the output is what it was without them."""
+        one of these options off, no launch is added and the output is what it was without them.
+
+        `assistant_model` = a smaller UnitLM over the same unit vocabulary (HF's assisted generation, draft-model speculative
+        decoding). Per round the draft proposes `num_assistant_tokens` = K tokens per row (an int 1 .. 15, default 4; constant:
+        HF's heuristic schedule is not implemented), the target scores the pending token and the K proposals in one chunk
+        (slam_extend_logits) and samples its own token at every chunk position, and slam_spec_accept keeps the target's tokens
+        up to and including the first one the draft did not propose - 1 .. K + 1 tokens per row and round for one stream of the
+        target's weights. Both models draw with the engine sampler's stateless draw of (seed, row id, step), so token s of row
+        r is sample(the target's logits after the prefix; seed, r, s) whatever the draft proposed: the output does not depend
+        on the draft, on K or on whether a draft was used, up to the rounding between the chunk attention and the decode-step
+        attention (the caveat of `prefill_chunk`). An assistant implies the engine sampler: greedy works under sampler=None
+        too, do_sample=True needs sampler="engine". Rejected tokens are rolled back by lowering the rows' cached lengths
+        (slam_kv_rewind). One host synchronisation per round (the read-back of five counters), none per token;
+        `self.last_assist_stats` = {"rounds", "proposed", "accepted", "tokens"} afterwards. Refused (ValueError): a draft that
+        is not a UnitLM, is OPT, is this model, sits on another device or has another vocab_size; num_return_sequences > 1;
+        return_logprobs; the history-dependent bans (no_repeat_ngram_size, multi-token bad words, min_new_tokens / min_length,
+        begin_suppress_tokens) - single-token bad words and suppress_tokens work. With assistant_model=None generate is what
+        it was, launch for launch."""
         if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
             raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
         if self.config.is_opt:
@@ -1186,7 +1204,12 @@ class UnitLM(TokenLM):
             raise TypeError(f"generate got unsupported arguments {sorted(kwargs)}")
         if sampler not in (None, "torch", "engine"):
             raise ValueError(f"sampler must be None, 'torch' or 'engine', not {sampler!r}")
-        on_device = sampler == "engine"
+        assist_k = None
+        if assistant_model is not None:
+            assist_k = self._check_assistant(assistant_model, num_assistant_tokens, nret, return_logprobs, plan, do_sample, sampler)
+        elif num_assistant_tokens is not None:
+            raise ValueError("num_assistant_tokens needs an assistant_model")
+        on_device = sampler == "engine" or assist_k is not None
         if on_device:
             if do_sample and not 1 <= top_k <= 256:
                 raise ValueError(f"sampler='engine' samples with 1 <= top_k <= 256 (got top_k={top_k})")
@@ -1213,6 +1236,14 @@ class UnitLM(TokenLM):
         ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, int(pad))).contiguous()
         if T + max_new_tokens > self.config.max_tokens:
             raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds max_tokens {self.config.max_tokens}")
+        if assist_k is not None:
+            new, n = self._generate_assisted(assistant_model, assist_k, ids, lens, T, max_new_tokens, bad, eos, int(pad), do_sample,
+                                             top_k, temperature, top_p, seed, sample_ids, prefill_chunk)
+            if eos and n > 1:  # the plain path's trim: stop right behind the step on which the last row finished
+                all_done = (torch.isin(new, torch.tensor(eos, dtype=torch.long, device=dev)).cumsum(1) > 0).all(0)
+                if bool(all_done.any()):
+                    new = new[:, :int(all_done.nonzero()[0]) + 1]
+            return torch.cat([seq_in, new], 1)
         cap = -(-(T + max_new_tokens) // 64) * 64
         self._ensure_workspace(max(B * (T if prefill_chunk is None else min(T, prefill_chunk)), 2 * BN))
         nbytes = self.engine.kv_cache_bytes(BN, cap)
@@ -1458,6 +1489,139 @@ class UnitLM(TokenLM):
             if n < max_new:
                 self.engine.decode_step(nxt, lens, B, logits)
         return n  # ws / banned / done were used on the current stream only: the allocator reuses them in stream order
+
+    def _check_assistant(self, draft, k, nret, return_logprobs, plan, do_sample, sampler) -> int:
+        """The ValueErrors of generate(assistant_model=); returns K."""
+        if not isinstance(draft, UnitLM):
+            raise ValueError(f"assistant_model must be a UnitLM (got {type(draft).__name__})")
+        if draft is self:
+            raise ValueError("assistant_model must be another model than the target (it needs a KV cache of its own)")
+        if draft.config.is_opt:
+            raise ValueError("assistant_model must not be an OPT model (the engine's KV-cached decode covers Qwen2 only)")
+        if torch.device(draft.device) != torch.device(self.device):
+            raise ValueError(f"assistant_model is on {draft.device}, the target on {self.device}")
+        if draft.config.vocab_size != self.config.vocab_size:
+            raise ValueError(f"assistant_model has vocab_size {draft.config.vocab_size}, the target {self.config.vocab_size}: "
+                             f"assisted generation needs one unit vocabulary")
+        k = 4 if k is None else k
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= E.SPEC_MAX_K:
+            raise ValueError(f"num_assistant_tokens must be an int 1 .. {E.SPEC_MAX_K} (got {k!r}); HF's heuristic schedule is "
+                             f"not implemented")
+        if nret > 1:
+            raise ValueError("assistant_model does not support num_return_sequences > 1")
+        if return_logprobs:
+            raise ValueError("assistant_model does not support return_logprobs")
+        if plan.active:
+            raise ValueError("assistant_model does not support history-dependent constraints (no_repeat_ngram_size, multi-token "
+                             "bad_words_ids, min_new_tokens / min_length, begin_suppress_tokens)")
+        if do_sample and sampler != "engine":
+            raise ValueError("assistant_model with do_sample=True needs sampler='engine': draft and target must share the "
+                             "stateless draw")
+        return k
+
+    _assist_trace = None      # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after)
+    last_assist_stats = None
+
+    def _generate_assisted(self, draft, K, ids, lens, T, max_new, bad, eos, pad, do_sample, top_k, temperature, top_p, seed,
+                           sample_ids, prefill_chunk=None):
+        """generate(assistant_model=draft): draft-model speculative decoding on the two engines' KV caches. ids [B, T] the
+        compacted prompts, lens int32 [B] their lengths. Returns (new [B, n] int64, pad behind a row's end; n). State at the
+        start of a round: the committed sequence of row b is its prompt + n_new[b] tokens, the target's
+        cache holds it without its last token (lens_t), the draft's cache that prefix without `lag` more tokens (lens_d)."""
+        dev = self.device
+        B, V = ids.shape[0], self.config.vocab_size
+        if B > E.SPEC_MAX_ROWS:
+            raise ValueError(f"assistant_model takes at most {E.SPEC_MAX_ROWS} rows (got {B})")
+        if T + max_new > draft.config.max_tokens:
+            raise ValueError(f"prompt length {T} + max_new_tokens {max_new} exceeds the assistant's max_tokens "
+                             f"{draft.config.max_tokens}")
+        K1 = K + 1
+        pre = B * (T if prefill_chunk is None else min(T, prefill_chunk))
+        cap = -(-(T + max_new + K) // 64) * 64
+        self._ensure_workspace(max(pre, B * K1, 2 * B))
+        draft._ensure_workspace(max(pre, 2 * B))
+        caches = []
+        for m in (self, draft):
+            nbytes = m.engine.kv_cache_bytes(B, cap)
+            raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+            off = (-raw.data_ptr()) % 256
+            m.engine.bind_kv_cache(raw[off:off + nbytes], B, cap)
+            caches.append(raw)
+        if do_sample and seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())
+        desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=top_k if do_sample else 1,
+                                temperature=temperature if do_sample else 1.0, top_p=top_p if do_sample else 1.0,
+                                seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF, step=0, pad_id=pad, n_eos=len(eos))
+        ws = torch.empty(E.sample_workspace_bytes(B * K1, V, desc.top_k), dtype=torch.uint8, device=dev)
+        banned = None
+        if bad:
+            banned = torch.zeros(V, dtype=torch.uint8, device=dev)
+            banned[torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev)] = 1
+        eos_i = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
+        row_ids = None
+        if sample_ids is not None:
+            row_ids = torch.as_tensor(sample_ids).to(dev, torch.int64).contiguous()
+            if row_ids.shape != (B,):
+                raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
+        prompt_len = lens.clone()
+        lens_t, lens_d = lens.clone(), lens.clone()
+        logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+        logits_d = torch.empty(B, V, dtype=torch.float32, device=dev)
+        self._prefill(ids, lens, B, T, logits, prefill_chunk)
+        draft._prefill(ids, lens, B, T, logits_d, prefill_chunk)
+        # token 0 from the target's prefill logits, by the plain sampler: new[:, 0], done on an EOS id
+        new = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev)
+        E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+        desc.n_eos = 0  # from here on slam_spec_accept looks for the EOS ids: a proposal that is one ends nothing yet
+        if max_new == 1:
+            done.fill_(1)
+        live = done == 0
+        n_new = torch.ones(B, dtype=torch.int32, device=dev)
+        chunk = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
+        chunk[:, 0] = nxt
+        tgt = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
+        draft_ids = torch.full((B, 2), pad, dtype=torch.int64, device=dev)
+        draft_ids[:, 0] = nxt
+        draft_new_lens = live.to(torch.int32)
+        tgt_new_lens = draft_new_lens * K1
+        logits_all = torch.zeros(B, K1, V, dtype=torch.float32, device=dev)
+        stats = torch.zeros(5, dtype=torch.int32, device=dev)
+        self._hold = (ids, lens, caches, chunk, tgt, logits_all)
+        n_live = int(live.sum())
+        rounds = proposed = accepted = 0
+        tokens = B
+        trace = self._assist_trace
+        while n_live > 0:
+            # draft: catch up with the committed sequence, then K proposals into chunk[:, 1 ..]
+            draft.engine.extend(draft_ids, draft_new_lens, lens_d, B, 2, logits_d)
+            for j in range(1, K1):
+                desc.step = j - 1
+                E.sample_tokens_at(logits_d, desc, nxt, ws, n_new, 1, j, banned, row_ids, None, None, chunk)
+                if j < K:
+                    draft.engine.decode_step(nxt, lens_d, B, logits_d)
+            # target: the logits behind every chunk column, and its own token there with the draw the draft used
+            self.engine.extend_logits(chunk, tgt_new_lens, lens_t, B, K1, logits_all)
+            desc.step = 0
+            E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
+            if trace is not None:
+                rec = (chunk.cpu(), logits_all.cpu(), n_new.cpu(), tgt.cpu())
+            E.spec_accept(chunk, tgt, K, max_new, pad, eos_i, prompt_len, n_new, done, new, lens_t, lens_d, draft_ids,
+                          draft_new_lens, tgt_new_lens, stats)
+            st = stats.tolist()  # the round's one host synchronisation
+            if trace is not None:
+                trace.append(rec + (n_new.cpu(),))
+            self.engine.kv_rewind(max(1, st[1]))
+            draft.engine.kv_rewind(max(1, st[2]))
+            rounds += 1
+            proposed += n_live * K
+            accepted += st[4]
+            tokens += st[3]
+            n_live = st[0]
+        self.last_assist_stats = {"rounds": rounds, "proposed": proposed, "accepted": accepted, "tokens": tokens}
+        n = int(n_new.max())
+        return new[:, :n], n
 
     # ---- checkpoints (HF layout) ------------------------------------------------------------------
     def save_pretrained(self, save_directory: str, dtype=torch.bfloat16):
