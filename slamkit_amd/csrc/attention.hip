@@ -835,7 +835,7 @@ __global__ __launch_bounds__(256, (DkvCfg<ND, KW>::OCC)) void attn_bwd_dkv_kerne
 #pragma unroll
       for (int fd = 0; fd < 4 * ND; ++fd) {
         *reinterpret_cast<float4*>(dkp + fd * 16 + g * 4) =
-            make_float4(dk[i][fd][0] * LN2, dk[i][fd][1] * LN2, dk[i][fd][2] * LN2, dk[i][fd][3] * LN2);  // Q tiles are pre-scaled: scale / (scale log2 e)
+            make_float4(dk[i][fd][0], dk[i][fd][1], dk[i][fd][2], dk[i][fd][3]);  // in units of 1 / ln 2: attn_dkv_reduce_kernel scales
         *reinterpret_cast<float4*>(dvp + fd * 16 + g * 4) =
             make_float4(dv[i][fd][0], dv[i][fd][1], dv[i][fd][2], dv[i][fd][3]);
       }
@@ -857,11 +857,31 @@ __global__ __launch_bounds__(256) void attn_dkv_reduce_kernel(AttnArgs p, int KT
   int which = (int)(r / p.M);
   const int nch = dkv_range(p.seg_end, p.M, (m / KT) * KT, KT, p.nch, 0).nch;
   float4 a = make_float4(0, 0, 0, 0), b = a;
-  for (int i = 0; i < nch; ++i) {
-    const float* src = p.dkv_part + ((((size_t)i * 2 + which) * p.nKV + kvh) * p.M + m) * D + c * 4;
-    float4 v = *reinterpret_cast<const float4*>(src), w = *reinterpret_cast<const float4*>(src + HALF);
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    b.x += w.x; b.y += w.y; b.z += w.z; b.w += w.w;
+  if (which == 0) {
+    // dK: the Q tiles are pre-scaled, so the partials arrive times log2(e) and are scaled by scale / (scale log2 e) = ln 2 here,
+    // each partial on its own (a rounded multiply, then the add). Every partial is thus rounded at ITS
+    // magnitude, and an element whose chunks cancel exactly would be left with the difference of those roundings (1e-7 .. 1e-6
+    // where the value is zero: tests/test_gpu_attn_exact.py). The unscaled partials are summed alongside: where THAT sum is
+    // exactly zero the element is zero.
+    float4 za = a, zb = a;
+    for (int i = 0; i < nch; ++i) {
+#pragma clang fp contract(off)  // multiply, round, then add: an fma would round once and change the sum
+      const float* src = p.dkv_part + ((((size_t)i * 2) * p.nKV + kvh) * p.M + m) * D + c * 4;
+      float4 v = *reinterpret_cast<const float4*>(src), w = *reinterpret_cast<const float4*>(src + HALF);
+      za.x += v.x; za.y += v.y; za.z += v.z; za.w += v.w;
+      zb.x += w.x; zb.y += w.y; zb.z += w.z; zb.w += w.w;
+      a.x += v.x * LN2; a.y += v.y * LN2; a.z += v.z * LN2; a.w += v.w * LN2;
+      b.x += w.x * LN2; b.y += w.y * LN2; b.z += w.z * LN2; b.w += w.w * LN2;
+    }
+    a.x = za.x == 0.f ? 0.f : a.x; a.y = za.y == 0.f ? 0.f : a.y; a.z = za.z == 0.f ? 0.f : a.z; a.w = za.w == 0.f ? 0.f : a.w;
+    b.x = zb.x == 0.f ? 0.f : b.x; b.y = zb.y == 0.f ? 0.f : b.y; b.z = zb.z == 0.f ? 0.f : b.z; b.w = zb.w == 0.f ? 0.f : b.w;
+  } else {
+    for (int i = 0; i < nch; ++i) {
+      const float* src = p.dkv_part + ((((size_t)i * 2 + 1) * p.nKV + kvh) * p.M + m) * D + c * 4;
+      float4 v = *reinterpret_cast<const float4*>(src), w = *reinterpret_cast<const float4*>(src + HALF);
+      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+      b.x += w.x; b.y += w.y; b.z += w.z; b.w += w.w;
+    }
   }
   if (which == 0 && p.rope_cs) {
     const float4 c4 = *reinterpret_cast<const float4*>(p.rope_cs + (size_t)m * HALF + c * 4);
