@@ -224,7 +224,8 @@ int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t*
  * workspace, and k tokens per row appended to a live cache (slam_extend); bans that depend on a row's own history - no
  * repeated n-gram, multi-token bad words, no EOS yet - on the device (slam_constrain_scores, below); a draft model's proposals
  * verified K + 1 positions at a time and rolled back where the target disagrees (slam_extend_logits, slam_sample_tokens_at,
- * slam_spec_accept, slam_kv_rewind, below). No beam search, no repetition penalty, no OPT. */
+ * slam_spec_accept, slam_kv_rewind, below), or proposals looked up in the row's own history (slam_ngram_propose, below). No
+ * beam search, no repetition penalty, no OPT. */
 size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity);
 int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity);
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
@@ -372,6 +373,40 @@ int slam_spec_accept(int64_t* chunk, const int64_t* tgt, int32_t B, int32_t K, i
                      const int32_t* eos_ids, int32_t n_eos, const int32_t* prompt_len, int32_t* n_new, uint8_t* done,
                      int64_t* out, int64_t out_stride, int32_t* lens_t, int32_t* lens_d, int64_t* draft_ids,
                      int32_t* draft_new_lens, int32_t* tgt_new_lens, int32_t* stats, slam_stream_t stream);
+
+/* ---- proposals without a draft model: the tokens that followed an earlier occurrence of the row's own last n-gram (HF's
+ * generate(prompt_lookup_num_tokens=, max_matching_ngram_size=), PromptLookupCandidateGenerator) -----------------------------
+ * slam_ngram_propose needs no engine. It fills the proposal columns of the chunk that slam_extend_logits verifies and
+ * slam_spec_accept judges. The history h of row b is, with pl = prompt_len[b] clamped to [0, prompt_stride] and
+ * s = n_new[b] clamped to [0, new_stride]:
+ *   h[0 .. pl)        = prompt[b * prompt_stride + 0 .. pl)   (right-padded prompt ids; pads are not history)
+ *   h[pl .. pl + s)   = new_tokens[b * new_stride + 0 .. s)   (the `out` buffer of slam_spec_accept, with the n_new it keeps)
+ * and Lh = pl + s: the layout slam_constrain_scores reads. Nothing outside these two ranges is read.
+ * The rule, restating transformers' PromptLookupCandidateGenerator.get_candidates:
+ *   match      for n = min(max_ngram, Lh - 1) down to 1: the smallest idx in [0, Lh - n) with h[idx .. idx + n) ==
+ *              h[Lh - n .. Lh). The tail window itself is no candidate; a window that overlaps it is. The longest n with any
+ *              match wins, within it the EARLIEST match.
+ *   proposals  h[idx + n .. min(idx + n + K, Lh)), cut in front of the first token that is an eos_ids entry. What is left,
+ *              n_prop[b] tokens (0 .. K), goes to chunk[b][1 .. 1 + n_prop[b]). A cut that leaves nothing proposes nothing:
+ *              there is no fall-back to a shorter n or a later match (HF's behaviour). No match at any n, and Lh <= 1,
+ *              propose nothing.
+ *   finished   done[b] != 0: n_prop[b] = 0.
+ *   fill       chunk[b][1 + n_prop[b] .. K] = fill_id. Column 0 is NEVER touched: slam_spec_accept owns it.
+ *   stats      int32 [2], nullable = { rows with n_prop[b] > 0, the sum of n_prop[b] }, by a second launch of one block behind
+ *              the first, combined through shared memory in a fixed order (no atomics).
+ * One block per row: every thread takes the window ends e = t, t + 256, .. of [0, Lh - 1), counts how many tokens back from e
+ * equal the tokens back from the end of h (at most min(max_ngram, Lh - 1)), and the block keeps the longest count, the lowest e
+ * among equals; idx + n = e + 1. Integer work only: the same bits on every run, whatever B.
+ * chunk int64 [B][K + 1]; n_prop, prompt_len, n_new int32 [B]; prompt int64 [B][prompt_stride]; new_tokens int64
+ * [B][new_stride]; done uint8 [B]; eos_ids int32 [n_eos] - all device memory.
+ * SLAM_EINVAL before any launch: a NULL array (eos_ids may be NULL when n_eos == 0; stats may be NULL); B outside 1 .. 1024
+ * (slam_spec_accept's limit); K outside 1 .. 15; max_ngram outside 1 .. SLAM_NGRAM_MAX; n_eos outside 0 .. 16; a negative
+ * stride or one of 2^30 or more. */
+#define SLAM_NGRAM_MAX 16
+int slam_ngram_propose(int64_t* chunk, int32_t* n_prop, int32_t B, int32_t K, int32_t max_ngram, int32_t fill_id,
+                       const int64_t* prompt, int64_t prompt_stride, const int32_t* prompt_len, const int64_t* new_tokens,
+                       int64_t new_stride, const int32_t* n_new, const uint8_t* done, const int32_t* eos_ids, int32_t n_eos,
+                       int32_t* stats, slam_stream_t stream);
 
 /* ---- per-row bans that depend on the row's own history (HF's no_repeat_ngram_size, multi-token bad_words_ids,
  * min_new_tokens / min_length, begin_suppress_tokens), between the logits and slam_sample_tokens ------------------------------

@@ -31,6 +31,10 @@
 //    chunk thread t takes scores t, t + 256, .. in that order, the 64 lanes of a wave are summed by the xor butterfly 32, 16,
 //    .., 1, the four waves in wave order; chunks are combined in chunk order, one fused multiply-add each. Rows above one chunk
 //    take two launches.
+//  * ngram_propose (slam_ngram_propose): prompt-lookup proposals. One block per row scans the row's history once: thread t
+//    takes the window ends t, t + 256, .., counts the tokens that match backwards from the end of the history, and a 64-bit
+//    key (count << 32 | ~end) picks the longest match, the earliest among equals. Integers only; the two statistics by a second
+//    one-block launch in a fixed order.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -700,6 +704,103 @@ __global__ __launch_bounds__(1024) void spec_accept_kernel(int64_t* __restrict__
       live += red[0][w]; lt = max(lt, red[1][w]); ld = max(ld, red[2][w]); emitted += red[3][w]; accepted += red[4][w];
     }
     stats[0] = live; stats[1] = lt; stats[2] = ld; stats[3] = emitted; stats[4] = accepted;
+  }
+}
+
+// ---- prompt-lookup proposals (include/slam_engine.h: slam_ngram_propose) -----------------------------------------------------
+constexpr int NG_THREADS = 256;
+struct NgramParams {
+  int K, max_ngram, fill_id, n_eos;
+  long long prompt_stride, new_stride;
+};
+
+// h[j] of a row: the prompt's real tokens, then the new ones (ConstrainHistory's layout)
+struct NgramHistory {
+  const int64_t* prompt;
+  const int64_t* fresh;
+  int pl;
+  SLAM_DEVICE int64_t at(int j) const { return j < pl ? prompt[j] : fresh[j - pl]; }
+};
+
+// grid B, one block per row. back(e) = the number of j < min(max_ngram, Lh - 1, e + 1) with h[e - j] == h[Lh - 1 - j] for all
+// smaller j too: a window of n tokens ending at e (e <= Lh - 2, so the tail window is none) matches the last n tokens iff
+// back(e) >= n. The longest n with a match is max back(e), its earliest window the lowest such e; the proposals start at e + 1.
+__global__ __launch_bounds__(NG_THREADS) void ngram_propose_kernel(int64_t* __restrict__ chunk, int* __restrict__ n_prop,
+                                                                   const int64_t* __restrict__ prompt,
+                                                                   const int* __restrict__ prompt_len,
+                                                                   const int64_t* __restrict__ fresh,
+                                                                   const int* __restrict__ n_new,
+                                                                   const uint8_t* __restrict__ done,
+                                                                   const int* __restrict__ eos_ids, NgramParams P) {
+  __shared__ unsigned long long red[NG_THREADS / 64];
+  __shared__ int stop[slam::SPEC_MAX_K + 1];
+  const int b = blockIdx.x, t = threadIdx.x;
+  NgramHistory h;
+  h.pl = (int)min((long long)max(prompt_len[b], 0), P.prompt_stride);
+  const int nn = (int)min((long long)max(n_new[b], 0), P.new_stride);
+  h.prompt = prompt + (long long)b * P.prompt_stride;
+  h.fresh = fresh + (long long)b * P.new_stride;  // dereferenced only for nn > 0
+  const int Lh = h.pl + nn;
+  unsigned long long key = 0;  // (back << 32) | ~e: larger is "longer, then earlier"; 0 = no match
+  if (done[b] == 0 && Lh >= 2) {
+    const int nmax = min(P.max_ngram, Lh - 1);
+    for (int e = t; e < Lh - 1; e += NG_THREADS) {
+      const int lim = min(nmax, e + 1);
+      int back = 0;
+      while (back < lim && h.at(e - back) == h.at(Lh - 1 - back)) ++back;
+      if (back > 0) {
+        const unsigned long long k = ((unsigned long long)back << 32) | (unsigned long long)(0xffffffffu - (uint32_t)e);
+        key = k > key ? k : key;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(key, o, 64);
+    key = other > key ? other : key;
+  }
+  if ((t & 63) == 0) red[t >> 6] = key;
+  __syncthreads();
+  key = red[0];
+#pragma unroll
+  for (int w = 1; w < NG_THREADS / 64; ++w) key = red[w] > key ? red[w] : key;
+  int start = 0, count = 0;
+  if (key != 0) {
+    start = (int)(0xffffffffu - (uint32_t)key) + 1;  // idx + n
+    count = min(P.K, Lh - start);                    // >= 1: e <= Lh - 2
+  }
+  int64_t tok = P.fill_id;
+  bool is_eos = false;
+  if (t < count) {
+    tok = h.at(start + t);
+    for (int e = 0; e < P.n_eos; ++e) is_eos = is_eos || (int64_t)eos_ids[e] == tok;
+  }
+  if (t < P.K) stop[t] = (t < count && !is_eos) ? 0 : 1;  // the proposals end in front of column 1 + t
+  __syncthreads();
+  if (t < P.K) {
+    int np = 0;
+    while (np < P.K && !stop[np]) ++np;
+    chunk[(size_t)b * (P.K + 1) + 1 + t] = t < np ? tok : (int64_t)P.fill_id;
+    if (t == 0) n_prop[b] = np;
+  }
+}
+
+// one block of 1024 threads, thread b = row b: { rows with a proposal, the sum of n_prop } through LDS in a fixed order
+__global__ __launch_bounds__(1024) void ngram_stats_kernel(const int* __restrict__ n_prop, int B, int* __restrict__ stats) {
+  __shared__ int red[2][16];
+  const int b = threadIdx.x, lane = b & 63;
+  int total = b < B ? n_prop[b] : 0;
+  int rows = total > 0 ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    rows += __shfl_xor(rows, o, 64);
+    total += __shfl_xor(total, o, 64);
+  }
+  if (lane == 0) { red[0][b >> 6] = rows; red[1][b >> 6] = total; }
+  __syncthreads();
+  if (b == 0) {
+    for (int w = 1; w < 16; ++w) { rows += red[0][w]; total += red[1][w]; }
+    stats[0] = rows; stats[1] = total;
   }
 }
 
@@ -1539,6 +1640,24 @@ int spec_accept(const SpecArgs& a, hipStream_t st) {
   P.out_stride = a.out_stride;
   spec_accept_kernel<<<1, 1024, 0, st>>>(a.chunk, a.tgt, a.eos_ids, a.prompt_len, a.n_new, a.done, a.out, a.lens_t, a.lens_d,
                                           a.draft_ids, a.draft_new_lens, a.tgt_new_lens, a.stats, P);
+  return (int)hipGetLastError();
+}
+
+int ngram_propose(const NgramArgs& a, hipStream_t st) {
+  if (!a.chunk || !a.n_prop || !a.prompt || !a.prompt_len || !a.fresh || !a.n_new || !a.done) return -1;
+  if (a.B < 1 || a.B > SPEC_MAX_B || a.K < 1 || a.K > SPEC_MAX_K || a.max_ngram < 1 || a.max_ngram > NGRAM_MAX) return -1;
+  if (a.n_eos < 0 || a.n_eos > 16 || (a.n_eos > 0 && !a.eos_ids)) return -1;
+  if (a.prompt_stride < 0 || a.prompt_stride > NGRAM_MAX_STRIDE || a.new_stride < 0 || a.new_stride > NGRAM_MAX_STRIDE) return -1;
+  NgramParams P;
+  P.K = a.K;
+  P.max_ngram = a.max_ngram;
+  P.fill_id = a.fill_id;
+  P.n_eos = a.n_eos;
+  P.prompt_stride = a.prompt_stride;
+  P.new_stride = a.new_stride;
+  ngram_propose_kernel<<<a.B, NG_THREADS, 0, st>>>(a.chunk, a.n_prop, a.prompt, a.prompt_len, a.fresh, a.n_new, a.done,
+                                                   a.eos_ids, P);
+  if (a.stats) ngram_stats_kernel<<<1, 1024, 0, st>>>(a.n_prop, a.B, a.stats);
   return (int)hipGetLastError();
 }
 

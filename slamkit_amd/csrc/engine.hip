@@ -2662,6 +2662,31 @@ int slam_spec_accept(int64_t* chunk, const int64_t* tgt, int32_t B, int32_t K, i
   return spec_accept(a, (hipStream_t)stream);
 }
 
+int slam_ngram_propose(int64_t* chunk, int32_t* n_prop, int32_t B, int32_t K, int32_t max_ngram, int32_t fill_id,
+                       const int64_t* prompt, int64_t prompt_stride, const int32_t* prompt_len, const int64_t* new_tokens,
+                       int64_t new_stride, const int32_t* n_new, const uint8_t* done, const int32_t* eos_ids, int32_t n_eos,
+                       int32_t* stats, slam_stream_t stream) {
+  static_assert(SLAM_NGRAM_MAX == NGRAM_MAX, "the header's limit is the kernel's");
+  NgramArgs a;  // ngram_propose refuses every bad argument (-1 = SLAM_EINVAL) before it launches anything
+  a.chunk = chunk;
+  a.n_prop = n_prop;
+  a.B = B;
+  a.K = K;
+  a.max_ngram = max_ngram;
+  a.fill_id = fill_id;
+  a.prompt = prompt;
+  a.prompt_stride = prompt_stride;
+  a.prompt_len = prompt_len;
+  a.fresh = new_tokens;
+  a.new_stride = new_stride;
+  a.n_new = n_new;
+  a.done = done;
+  a.eos_ids = eos_ids;
+  a.n_eos = n_eos;
+  a.stats = stats;
+  return ngram_propose(a, (hipStream_t)stream);
+}
+
 int slam_constrain_scores(const float* logits, float* scores, int32_t B, int32_t vocab, const SlamConstrainDesc* desc,
                           const int64_t* prompt, const int32_t* prompt_len, const int64_t* new_tokens, int64_t new_stride,
                           const uint8_t* done, const int32_t* eos_ids, const int32_t* begin_ids, const int32_t* seq_tokens,

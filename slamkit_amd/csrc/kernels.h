@@ -322,6 +322,24 @@ struct SpecArgs {
   int* stats = nullptr;            // [5]
 };
 int spec_accept(const SpecArgs& a, hipStream_t st);
+// Prompt-lookup proposals (include/slam_engine.h: slam_ngram_propose): one block per row; a second one-block launch for stats.
+constexpr int NGRAM_MAX = 16;            // longest n-gram matched (SLAM_NGRAM_MAX)
+constexpr int NGRAM_MAX_STRIDE = (1 << 30) - 1;  // bound of the two strides: a history length stays an int
+struct NgramArgs {
+  int64_t* chunk = nullptr;         // [B][K + 1]: columns 1 .. K are written, column 0 never
+  int* n_prop = nullptr;            // [B]
+  int B = 0, K = 0, max_ngram = 0, fill_id = 0, n_eos = 0;
+  const int64_t* prompt = nullptr;  // [B][prompt_stride], right-padded
+  int64_t prompt_stride = 0;
+  const int* prompt_len = nullptr;
+  const int64_t* fresh = nullptr;   // [B][new_stride]: the new tokens
+  int64_t new_stride = 0;
+  const int* n_new = nullptr;
+  const uint8_t* done = nullptr;
+  const int* eos_ids = nullptr;     // device, [n_eos]
+  int* stats = nullptr;             // nullable: [2]
+};
+int ngram_propose(const NgramArgs& a, hipStream_t st);
 // The next token of every row of fp32 logits [B][vocab] (row stride vocab, any 4-byte alignment), chosen on the device by the
 // contract of include/slam_engine.h (slam_sample_tokens): one argument block from the entry point down to the launches.
 struct SampleArgs {

@@ -111,6 +111,7 @@ def load_library(path: Optional[str] = None):
         "slam_sample_tokens_at": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp, i32,
                                             i32, vp]),
         "slam_spec_accept": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "slam_ngram_propose": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, vp, vp]),
         "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
         "slam_token_logprobs": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, sz, vp]),
         "slam_bucket_stream": (vp, [vp]),
@@ -279,6 +280,25 @@ def spec_accept(chunk, tgt, K: int, max_new: int, pad_id: int, eos_ids, prompt_l
                                         stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_spec_accept failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+NGRAM_MAX = 16  # slam_ngram_propose: the longest n-gram matched (SLAM_NGRAM_MAX)
+NGRAM_STATS = ("rows", "proposed")
+
+
+def ngram_propose(chunk, n_prop, max_ngram: int, fill_id: int, prompt, prompt_len, new, n_new, done, eos_ids=None, stats=None,
+                  stream: Optional[int] = None):
+    """slam_ngram_propose: prompt-lookup proposals for all B rows (the contract is in include/slam_engine.h). chunk int64
+    [B, K + 1] (columns 1 .. K are written, column 0 never); n_prop / prompt_len / n_new int32 [B]; prompt int64 [B, stride]
+    right-padded; new int64 [B, stride] (the out buffer of spec_accept); done uint8 [B]; eos_ids int32 or None; stats int32 [2]
+    (NGRAM_STATS) or None. Only enqueues work."""
+    B, K1 = chunk.shape
+    rc = load_library().slam_ngram_propose(_ptr(chunk), _ptr(n_prop), B, K1 - 1, int(max_ngram), int(fill_id), _ptr(prompt),
+                                          prompt.stride(0), _ptr(prompt_len), _ptr(new), new.stride(0), _ptr(n_new), _ptr(done),
+                                          _ptr(eos_ids), 0 if eos_ids is None else int(eos_ids.numel()), _ptr(stats),
+                                          stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_ngram_propose failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 def constrain_scores(logits, scores, desc: SlamConstrainDesc, prompt, prompt_len, new=None, done=None, eos_ids=None,

@@ -1086,7 +1086,8 @@ class UnitLM(TokenLM):
                  prefill_chunk: Optional[int] = None, no_repeat_ngram_size: Optional[int] = None,
                  min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
                  begin_suppress_tokens: Optional[List[int]] = None, suppress_tokens: Optional[List[int]] = None,
-                 assistant_model: Optional["UnitLM"] = None, num_assistant_tokens: Optional[int] = None, **kwargs):
+                 assistant_model: Optional["UnitLM"] = None, num_assistant_tokens: Optional[int] = None,
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None, **kwargs):
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
@@ -1153,7 +1154,20 @@ class UnitLM(TokenLM):
         is not a UnitLM, is OPT, is this model, sits on another device or has another vocab_size; num_return_sequences > 1;
         return_logprobs; the history-dependent bans (no_repeat_ngram_size, multi-token bad words, min_new_tokens / min_length,
         begin_suppress_tokens) - single-token bad words and suppress_tokens work. With assistant_model=None generate is what
-        it was, launch for launch."""
+        it was, launch for launch.
+
+        `prompt_lookup_num_tokens` = K (an int 1 .. 15; HF's prompt-lookup decoding, PromptLookupCandidateGenerator) is assisted
+        generation without a second model: per round one integer kernel (slam_ngram_propose) looks up the row's own last
+        n-gram - n = `max_matching_ngram_size` (an int 1 .. 16, default 2) down to 1, the longest n with an earlier occurrence,
+        the earliest occurrence of that n - and proposes up to K of the tokens that followed it, cut in front of an EOS id. The
+        target then verifies all K + 1 chunk columns of every live row, columns without a proposal holding pad_token_id, and
+        slam_spec_accept keeps its tokens as above: every emitted token is the target's own draw, so the output does not
+        depend on K, on n or on whether lookup is used (same rounding caveat), and sampling yields the target's distribution.
+        Up to 1024 rows; both arguments are also read from `generation_config`. `self.last_assist_stats["proposed"]` counts
+        the tokens actually proposed (not rows x K). Refused (ValueError): together with assistant_model;
+        max_matching_ngram_size without prompt_lookup_num_tokens; K or n out of range; and the assistant's list
+        (num_return_sequences > 1, return_logprobs, history-dependent bans, do_sample without sampler="engine"). With both
+        arguments absent generate is what it was, launch for launch."""
         if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
             raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
         if self.config.is_opt:
@@ -1205,11 +1219,19 @@ class UnitLM(TokenLM):
         if sampler not in (None, "torch", "engine"):
             raise ValueError(f"sampler must be None, 'torch' or 'engine', not {sampler!r}")
         assist_k = None
+        lookup_k = pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None)
+        lookup_n = pick(max_matching_ngram_size, "max_matching_ngram_size", None)
+        if lookup_k is not None:
+            if assistant_model is not None:
+                raise ValueError("prompt_lookup_num_tokens and assistant_model exclude each other: one source of proposals")
+            lookup_n = self._check_lookup(lookup_k, lookup_n, nret, return_logprobs, plan, do_sample, sampler)
+        elif lookup_n is not None:
+            raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
         if assistant_model is not None:
             assist_k = self._check_assistant(assistant_model, num_assistant_tokens, nret, return_logprobs, plan, do_sample, sampler)
         elif num_assistant_tokens is not None:
             raise ValueError("num_assistant_tokens needs an assistant_model")
-        on_device = sampler == "engine" or assist_k is not None
+        on_device = sampler == "engine" or assist_k is not None or lookup_k is not None
         if on_device:
             if do_sample and not 1 <= top_k <= 256:
                 raise ValueError(f"sampler='engine' samples with 1 <= top_k <= 256 (got top_k={top_k})")
@@ -1236,9 +1258,13 @@ class UnitLM(TokenLM):
         ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, int(pad))).contiguous()
         if T + max_new_tokens > self.config.max_tokens:
             raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds max_tokens {self.config.max_tokens}")
-        if assist_k is not None:
-            new, n = self._generate_assisted(assistant_model, assist_k, ids, lens, T, max_new_tokens, bad, eos, int(pad), do_sample,
-                                             top_k, temperature, top_p, seed, sample_ids, prefill_chunk)
+        if assist_k is not None or lookup_k is not None:
+            if assist_k is not None:
+                new, n = self._generate_assisted(assistant_model, assist_k, ids, lens, T, max_new_tokens, bad, eos, int(pad),
+                                                 do_sample, top_k, temperature, top_p, seed, sample_ids, prefill_chunk)
+            else:
+                new, n = self._generate_lookup(lookup_k, lookup_n, ids, lens, T, max_new_tokens, bad, eos, int(pad), do_sample,
+                                               top_k, temperature, top_p, seed, sample_ids, prefill_chunk)
             if eos and n > 1:  # the plain path's trim: stop right behind the step on which the last row finished
                 all_done = (torch.isin(new, torch.tensor(eos, dtype=torch.long, device=dev)).cumsum(1) > 0).all(0)
                 if bool(all_done.any()):
@@ -1616,6 +1642,114 @@ class UnitLM(TokenLM):
             draft.engine.kv_rewind(max(1, st[2]))
             rounds += 1
             proposed += n_live * K
+            accepted += st[4]
+            tokens += st[3]
+            n_live = st[0]
+        self.last_assist_stats = {"rounds": rounds, "proposed": proposed, "accepted": accepted, "tokens": tokens}
+        n = int(n_new.max())
+        return new[:, :n], n
+
+    def _check_lookup(self, k, n, nret, return_logprobs, plan, do_sample, sampler) -> int:
+        """The ValueErrors of generate(prompt_lookup_num_tokens=); returns max_matching_ngram_size."""
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= E.SPEC_MAX_K:
+            raise ValueError(f"prompt_lookup_num_tokens must be an int 1 .. {E.SPEC_MAX_K} (got {k!r})")
+        n = 2 if n is None else n
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= E.NGRAM_MAX:
+            raise ValueError(f"max_matching_ngram_size must be an int 1 .. {E.NGRAM_MAX} (got {n!r})")
+        if nret > 1:
+            raise ValueError("prompt_lookup_num_tokens does not support num_return_sequences > 1")
+        if return_logprobs:
+            raise ValueError("prompt_lookup_num_tokens does not support return_logprobs")
+        if plan.active:
+            raise ValueError("prompt_lookup_num_tokens does not support history-dependent constraints (no_repeat_ngram_size, "
+                             "multi-token bad_words_ids, min_new_tokens / min_length, begin_suppress_tokens)")
+        if do_sample and sampler != "engine":
+            raise ValueError("prompt_lookup_num_tokens with do_sample=True needs sampler='engine': the verified positions are "
+                             "drawn with the stateless draw")
+        return n
+
+    _lookup_trace = None  # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after, n_prop)
+
+    def _generate_lookup(self, K, ngram, ids, lens, T, max_new, bad, eos, pad, do_sample, top_k, temperature, top_p, seed,
+                         sample_ids, prefill_chunk=None):
+        """generate(prompt_lookup_num_tokens=K): _generate_assisted without the draft model, its cache and its catch-up
+        steps. The proposals of a round come from slam_ngram_propose on the row's own history (ids, then `new` up to n_new);
+        all K + 1 chunk columns of a live row are verified, the ones without a proposal holding `pad`, so every row of
+        logits_all that the sampler reads for a live row is a real conditional of this round. Returns
+        (new [B, n] int64, pad behind a row's end; n)."""
+        dev = self.device
+        B, V = ids.shape[0], self.config.vocab_size
+        if B > E.SPEC_MAX_ROWS:
+            raise ValueError(f"prompt_lookup_num_tokens takes at most {E.SPEC_MAX_ROWS} rows (got {B})")
+        K1 = K + 1
+        pre = B * (T if prefill_chunk is None else min(T, prefill_chunk))
+        cap = -(-(T + max_new + K) // 64) * 64
+        self._ensure_workspace(max(pre, B * K1, 2 * B))
+        nbytes = self.engine.kv_cache_bytes(B, cap)
+        raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        off = (-raw.data_ptr()) % 256
+        self.engine.bind_kv_cache(raw[off:off + nbytes], B, cap)
+        if do_sample and seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)).item())
+        desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=top_k if do_sample else 1,
+                                temperature=temperature if do_sample else 1.0, top_p=top_p if do_sample else 1.0,
+                                seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF, step=0, pad_id=pad, n_eos=len(eos))
+        ws = torch.empty(E.sample_workspace_bytes(B * K1, V, desc.top_k), dtype=torch.uint8, device=dev)
+        banned = None
+        if bad:
+            banned = torch.zeros(V, dtype=torch.uint8, device=dev)
+            banned[torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev)] = 1
+        eos_i = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
+        row_ids = None
+        if sample_ids is not None:
+            row_ids = torch.as_tensor(sample_ids).to(dev, torch.int64).contiguous()
+            if row_ids.shape != (B,):
+                raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
+        prompt_len = lens.clone()
+        lens_t = lens.clone()
+        logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+        self._prefill(ids, lens, B, T, logits, prefill_chunk)
+        # token 0 from the prefill logits, by the plain sampler: new[:, 0], done on an EOS id
+        new = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev)
+        E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+        desc.n_eos = 0  # from here on slam_spec_accept looks for the EOS ids
+        if max_new == 1:
+            done.fill_(1)
+        live = done == 0
+        n_new = torch.ones(B, dtype=torch.int32, device=dev)
+        n_prop = torch.zeros(B, dtype=torch.int32, device=dev)
+        chunk = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
+        chunk[:, 0] = nxt
+        tgt = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
+        tgt_new_lens = live.to(torch.int32) * K1
+        # the draft side of slam_spec_accept: written every round, read by nothing
+        lens_d = torch.empty(B, dtype=torch.int32, device=dev)
+        draft_ids = torch.empty(B, 2, dtype=torch.int64, device=dev)
+        draft_new_lens = torch.empty(B, dtype=torch.int32, device=dev)
+        logits_all = torch.zeros(B, K1, V, dtype=torch.float32, device=dev)
+        stats = torch.zeros(7, dtype=torch.int32, device=dev)  # slam_spec_accept's five, then slam_ngram_propose's two
+        self._hold = (ids, lens, raw, chunk, tgt, logits_all)
+        n_live = int(live.sum())
+        rounds = proposed = accepted = 0
+        tokens = B
+        trace = self._lookup_trace
+        while n_live > 0:
+            E.ngram_propose(chunk, n_prop, ngram, pad, ids, prompt_len, new, n_new, done, eos_i, stats[5:])
+            self.engine.extend_logits(chunk, tgt_new_lens, lens_t, B, K1, logits_all)
+            desc.step = 0
+            E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
+            if trace is not None:
+                rec = (chunk.cpu(), logits_all.cpu(), n_new.cpu(), tgt.cpu())
+            E.spec_accept(chunk, tgt, K, max_new, pad, eos_i, prompt_len, n_new, done, new, lens_t, lens_d, draft_ids,
+                          draft_new_lens, tgt_new_lens, stats)
+            st = stats.tolist()  # the round's one host synchronisation
+            if trace is not None:
+                trace.append(rec + (n_new.cpu(), n_prop.cpu()))
+            self.engine.kv_rewind(max(1, st[1]))
+            rounds += 1
+            proposed += st[6]
             accepted += st[4]
             tokens += st[3]
             n_live = st[0]

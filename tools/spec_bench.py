@@ -2,7 +2,7 @@
 decoding, on randomly initialised models: a Slam-358M-shaped draft under a Qwen2.5-1.5B-shaped and a Qwen2.5-7B-shaped target,
 one unit vocabulary of 502, a prompt of 256 tokens in both caches, B in {1, 8}, K in {2, 4, 8}.
 
-Usage: python tools/spec_bench.py [--targets cfg3,7b] [--batches 1,8] [--ks 2,4,8] [--reps 20] [--prompt 256]
+Usage: python tools/spec_bench.py [--targets cfg3,7b] [--batches 1,8] [--ks 2,4,8] [--reps 20] [--prompt 256] [--lookup]
 
 Per (target, B, K) one JSON line with wall-clock medians in ms, the host synchronised before and behind every timed part (the
 launch cost of a part is inside its figure, as it is in the loop):
@@ -17,7 +17,18 @@ launch cost of a part is inside its figure, as it is in the loop):
                 generation to match plain decoding; above K + 1 no acceptance rate can reach it
 Rounds and plain steps are alternated rep by rep in one process; every rep starts from the same cache lengths (the rollback
 restores them). Random weights accept nothing, so this tool measures COST only: the speed-up at a real acceptance rate needs a
-trained draft / target pair and is not claimed from these figures."""
+trained draft / target pair and is not claimed from these figures.
+
+--lookup adds prompt-lookup decoding (generate(prompt_lookup_num_tokens=)) to the same reps - lookup parts, lookup round, draft
+parts, draft round and plain steps alternated rep by rep in the one process - and prints a second line per (target, B, K):
+  propose_ms    slam_ngram_propose (max_ngram 2) on the 256-token prompt plus one new token, its two statistics included
+  verify_ms     as above (the same launches)
+  accept_ms     slam_spec_accept, the read-back of the seven counters, the target's slam_kv_rewind
+  round_ms      the three parts back to back with the one synchronisation
+  break_even_tokens_per_round   round_ms / plain_step_ms, and draft_break_even_tokens_per_round of the same reps beside it
+and, before the targets, one line per (B, history length) of the proposal kernel alone (no model; 50 calls back to back per
+timed window, the figure is the window / 50): random ids over the 502 units at max_ngram 2 and 16, and the worst case of a
+constant history, where every window matches max_ngram = 16 tokens back."""
 import argparse
 import json
 import os
@@ -46,7 +57,35 @@ def wall_ms(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def bench(target, draft, tag, B, K, P, reps):
+def bench_propose(dev, B, Lh, K, reps):
+    """slam_ngram_propose alone on histories of Lh tokens (all but one in the prompt), wall clock with the launch inside."""
+    import torch
+    from slamkit_amd import engine as E
+    g = torch.Generator(device=dev).manual_seed(B + Lh)
+    chunk = torch.ones(B, K + 1, dtype=torch.int64, device=dev)
+    n_prop = torch.zeros(B, dtype=torch.int32, device=dev)
+    stats = torch.zeros(2, dtype=torch.int32, device=dev)
+    plen = torch.full((B,), Lh - 1, dtype=torch.int32, device=dev)
+    n_new = torch.ones(B, dtype=torch.int32, device=dev)
+    done = torch.zeros(B, dtype=torch.uint8, device=dev)
+    out = {}
+    for name, mx in (("random", 2), ("random16", 16), ("constant16", 16)):
+        prompt = torch.randint(2, VOCAB, (B, Lh - 1), device=dev, generator=g)
+        if name == "constant16":
+            prompt.fill_(7)
+        new = prompt[:, :8].clone()
+
+        def many():  # 50 back to back per timed window: one call is a few microseconds of kernel behind its launches
+            for _ in range(50):
+                E.ngram_propose(chunk, n_prop, mx, 0, prompt, plen, new, n_new, done, None, stats)
+
+        t = [wall_ms(many) / 50 for _ in range(reps + 2)][2:]
+        out[name + "_ms"] = round(statistics.median(t), 4)
+        out[name + "_proposed"] = int(stats[1])
+    print(json.dumps(dict(bench="ngram_propose", B=B, history=Lh, K=K, **out, reps=reps)), flush=True)
+
+
+def bench(target, draft, tag, B, K, P, reps, lookup=False):
     import torch
     from slamkit_amd import engine as E
     dev, V, K1 = target.device, VOCAB, K + 1
@@ -76,7 +115,10 @@ def bench(target, draft, tag, B, K, P, reps):
     draft_new_lens = torch.ones(B, dtype=torch.int32, device=dev)
     tgt_new_lens = torch.full((B,), K1, dtype=torch.int32, device=dev)
     logits_all = torch.zeros(B, K1, V, dtype=torch.float32, device=dev)
-    stats = torch.zeros(5, dtype=torch.int32, device=dev)
+    stats = torch.zeros(7, dtype=torch.int32, device=dev)  # slam_spec_accept's five, slam_ngram_propose's two
+    n_prop = torch.zeros(B, dtype=torch.int32, device=dev)
+    scratch = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, 2, dtype=torch.int64, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev))  # the draft side of slam_spec_accept under lookup: read by nothing
 
     def reset():
         for t in (lens_t, lens_d):
@@ -114,6 +156,21 @@ def bench(target, draft, tag, B, K, P, reps):
         verify_part()
         accept_part()
 
+    def propose_part():
+        E.ngram_propose(chunk, n_prop, 2, 0, ids, prompt_len, new, n_new, done, None, stats[5:])
+
+    def lookup_accept_part():
+        E.spec_accept(chunk, tgt, K, new.shape[1], 0, None, prompt_len, n_new, done, new, lens_t, scratch[0], scratch[1],
+                      scratch[2], tgt_new_lens, stats)
+        st = stats.tolist()
+        target.engine.kv_rewind(max(1, st[1]))
+        return st
+
+    def lookup_round():
+        propose_part()
+        verify_part()
+        lookup_accept_part()
+
     def plain():
         for s in range(K1):
             desc.step = s
@@ -121,8 +178,19 @@ def bench(target, draft, tag, B, K, P, reps):
             target.engine.decode_step(nxt, lens_t, B, logits)
 
     t = {k: [] for k in ("draft", "verify", "accept", "round", "plain")}
+    tl = {k: [] for k in ("propose", "verify", "accept", "round")}
     emitted = 0
     for rep in range(reps + 2):  # two warm-up reps
+        if lookup:
+            reset()
+            la = wall_ms(propose_part)
+            lb = wall_ms(verify_part)
+            lc = wall_ms(lookup_accept_part)
+            reset()
+            lr = wall_ms(lookup_round)
+            if rep >= 2:
+                for k, v in zip(tl, (la, lb, lc, lr)):
+                    tl[k].append(v)
         reset()
         a = wall_ms(draft_part)
         b = wall_ms(verify_part)
@@ -142,6 +210,14 @@ def bench(target, draft, tag, B, K, P, reps):
                           round_ms_minmax=[round(min(t["round"]), 4), round(max(t["round"]), 4)],
                           plain_step_ms=round(step, 4), break_even_tokens_per_round=round(med["round"] / step, 3),
                           max_tokens_per_round=K1, emitted_last_round=emitted, reps=reps)), flush=True)
+    if lookup:
+        ml = {k: statistics.median(v) for k, v in tl.items()}
+        print(json.dumps(dict(bench="lookup_round", target=tag, B=B, K=K, prompt=P, vocab=V, max_ngram=2,
+                              **{f"{k}_ms": round(v, 4) for k, v in ml.items()},
+                              round_ms_minmax=[round(min(tl["round"]), 4), round(max(tl["round"]), 4)],
+                              plain_step_ms=round(step, 4), break_even_tokens_per_round=round(ml["round"] / step, 3),
+                              draft_break_even_tokens_per_round=round(med["round"] / step, 3), max_tokens_per_round=K1,
+                              proposed_last_round=int(stats[6]), reps=reps)), flush=True)
 
 
 def main():
@@ -151,15 +227,20 @@ def main():
     ap.add_argument("--ks", default="2,4,8")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--prompt", type=int, default=256)
+    ap.add_argument("--lookup", action="store_true", help="also time prompt-lookup rounds, and the proposal kernel alone")
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available()
+    if a.lookup:
+        for B in (1, 8, 64):
+            for Lh in (257, 2048, 8192):
+                bench_propose(torch.device("cuda"), B, Lh, 4, a.reps)
     draft = build("slam", 4096)
     for name in a.targets.split(","):
         target = build(name, 4096)
         for B in (int(x) for x in a.batches.split(",")):
             for K in (int(x) for x in a.ks.split(",")):
-                bench(target, draft, name, B, K, a.prompt, a.reps)
+                bench(target, draft, name, B, K, a.prompt, a.reps, a.lookup)
         del target
         torch.cuda.empty_cache()
 
