@@ -826,6 +826,9 @@ __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
   }
   if (dl) {
     const float sc = 1.f / denom[0];
+    // p = exp(z - max) / sum, as in ce_kernel - not exp(z - lse): lse = max + log(sum) is rounded at the magnitude of the
+    // logits, and half an ulp of |lse| in the exponent is a relative error of 1e-3 in every p of a row of logits near 3e4
+    const float inv = 1.f / bs;
     for (int c = tid; c < nch; c += 256) {
       float f[8], o[8];
       unpack_bf16x8(lr[c], f);
@@ -834,7 +837,7 @@ __global__ __launch_bounds__(256) void ce_big_kernel(const bf16_t* logits,
       for (int j = 0; j < 8; ++j) {
         const int col = c * 8 + j;
         const bool onj = (col < V) && !(((j < 4 ? mk.x : mk.y) >> (8 * (j & 3))) & 0xff);
-        float pj = onj ? __expf(f[j] - lse) : 0.f;
+        float pj = onj ? __expf(f[j] - bm) * inv : 0.f;
         if constexpr (SMOOTH) {
           if (onj) pj -= uni;  // never on a pad column: those stay exact zeros
           if (col == (int)tgt) pj -= 1.f - eps;
