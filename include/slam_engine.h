@@ -339,6 +339,48 @@ int slam_sample_tokens_at(const float* logits, int32_t B, int32_t vocab, const u
                           const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
                           int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group, int32_t out_col,
                           slam_stream_t stream);
+/* slam_sample_tokens_warped is slam_sample_tokens_at followed by the second half of HF's warper chain (min_p, typical_p,
+ * epsilon_cutoff, eta_cutoff, in GenerationMixin._get_logits_processor's order) on the ranked candidates: HF applies these
+ * after top-k, so they only see the k' <= 256 candidates the sampler already holds, and no second pass over the vocabulary
+ * is made. warp == NULL or all four off ({0, 1, 0, 0}) IS slam_sample_tokens_at: the same launches, the same tokens, done,
+ * next and out, bit for bit. Greedy (do_sample == 0) ignores the warp description beyond its range check, as HF ignores
+ * warpers when it does not sample. min_tokens_to_keep is 1 throughout.
+ * The contract continues slam_sample_tokens' at the top-p prefix: ranks 0 .. m-1 by (x descending, id ascending), fp32 weights
+ * w_j = expf(a_j), a_j = (x_j - x_0) * inv_t (a_0 = 0, w_0 = 1). S is the set of ranks still kept (at first 0 .. m-1); every
+ * step below that is on acts on the S the steps before it left. All arithmetic is fp32, one operation at a time:
+ *   Z_S   = the sum of w_j over j in S, added in ascending rank order starting from 0.0f.
+ *   p_j   = w_j / Z_S;   log p_j = a_j - logf(Z_S)   (from the scaled score, not logf(p_j): finite where w_j underflows).
+ *   H_S   = -(the sum of p_j * log p_j over j in S with w_j > 0, added in ascending rank order from 0.0f)   ("0 log 0 = 0").
+ *   min_p       on for 0 < min_p <= 1 (0 off). w_top = the weight of the lowest rank in S. Rank j leaves S when
+ *               w_j < min_p * w_top (HF's probs < min_p * max prob; the normaliser cancels). The lowest rank never leaves.
+ *   typical_p   on for 0 < typical_p < 1 (1 off). s_j = fabsf(-log p_j - H_S). S is ordered by (s ascending, rank ascending):
+ *               HF's torch.sort leaves the order of equal s unspecified, this tie rule is ours (the second deviation, beside
+ *               the tie at the k-th score). c_i = p of the first i + 1 ranks of that order, added in that order from 0.0f.
+ *               last = min(#{i : c_i < typical_p}, |S| - 1). Rank j leaves S when s_j > s of the last-th rank of the order;
+ *               the first rank of the order never leaves. S need no longer be a prefix afterwards: rank 0 can leave.
+ *   epsilon_cutoff  on for 0 < eps < 1 (0 off). Rank j leaves S when p_j < eps, unless x_j equals the score of the lowest
+ *               rank in S (HF exempts scores >= the top-1 score, so every tie at the top stays).
+ *   eta_cutoff  on for 0 < eps < 1 (0 off). eta = fminf(eps, sqrtf(eps) * expf(-H_S)); rank j leaves S when p_j < eta, with
+ *               the same exemption.
+ *   draw        cum runs over the ranks of S in ascending rank order (cum += w_j from 0.0f); total = the last cum; u is the
+ *               SAME Philox word as without warpers (one draw per (row id, step), nothing further is consumed); the token
+ *               is the candidate of the lowest rank in S with cum > u * total, or of the highest rank in S if there is none.
+ * The sums run in the stated order on one thread, the typical_p order is formed by counting (position = the number of ranks
+ * of S that come first), so a row's result is the same bits on every run and does not depend on B, the row's index or the
+ * launch shape (no floating-point atomics). Because the chain runs on the top-k candidates it equals HF's exactly when
+ * 1 <= top_k <= 256 is part of the request. The workspace is slam_sample_tokens_at's (slam_sample_workspace_bytes).
+ * SLAM_EINVAL, before anything is launched or dereferenced on the device: slam_sample_tokens_at's list, plus min_p outside
+ * [0, 1], typical_p outside (0, 1], epsilon_cutoff or eta_cutoff outside [0, 1), or a NaN in any of the four. */
+typedef struct SlamWarpDesc {
+  float min_p;           /* [0, 1], 0 = off */
+  float typical_p;       /* (0, 1], 1 = off */
+  float epsilon_cutoff;  /* [0, 1), 0 = off */
+  float eta_cutoff;      /* [0, 1), 0 = off */
+} SlamWarpDesc;
+int slam_sample_tokens_warped(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                              const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                              int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group,
+                              int32_t out_col, const SlamWarpDesc* warp, slam_stream_t stream);
 
 /* ---- the acceptance rule of draft-model speculative decoding, on the device -------------------------------------------------
  * slam_spec_accept needs no engine. One round of assisted generation proposes K tokens per row with a draft model, lets the

@@ -13,6 +13,9 @@
 //    through two launches: every (chunk, row) block selects its local top k into the workspace, one block per row selects
 //    among those, ranks the k' survivors and does the weights, the top-p cut, the Philox draw and the EOS / done / pad part.
 //    Thread 0 forms the sums in the stated order: no floating-point atomics, nothing depends on the grid.
+//    slam_sample_tokens_warped adds min_p / typical_p / epsilon_cutoff / eta_cutoff (HF's order) between the top-p cut and the
+//    draw as a further instantiation of that last kernel: a thread per rank holds its membership of the kept set, thread 0
+//    forms each normaliser and entropy in rank order, the typical_p order is formed by counting as the rank is.
 //  * kv_repeat (slam_kv_repeat): fans the B prefilled cache rows out to B * n rows in place, row b -> rows b n .. b n + n - 1.
 //    One launch per source row, in DESCENDING b on the one stream, each covering all layers, K and V, lens and the logits row.
 //    Launch b reads row b and writes rows [b n, b n + n) minus b itself (only b = 0 is its own destination); for n >= 2 and
@@ -972,14 +975,89 @@ __global__ __launch_bounds__(SP_THREADS) void sample_select_kernel(const float* 
   for (int i = threadIdx.x; i < P.k; i += SP_THREADS) dst[i] = i < kk ? sh.sel[i] : 0ull;
 }
 
+// slam_sample_tokens_warped: the description of the plain call, then min_p / typical_p / epsilon_cutoff / eta_cutoff
+struct WarpSampleParams : SampleParams {
+  float min_p, typical_p, eps_cut, eta_cut;
+};
+template <bool WARP> struct SampleParamsOf { typedef SampleParams type; };
+template <> struct SampleParamsOf<true> { typedef WarpSampleParams type; };
+
+// LDS of the warper chain; a thread owns the rank of its index. The float arrays are read 16 bytes at a time.
+struct alignas(16) WarpShared {
+  float kw[SP_MAXK];    // w_j of the ranks in S, 0 for the others (adding 0 keeps the bits of a sum over S in rank order)
+  float term[SP_MAXK];  // p_j log p_j of the ranks in S with w_j > 0, 0 for the others
+  float s[SP_MAXK];     // typical_p: s_j of the ranks in S, NaN for the others (a NaN never counts as "in front")
+  float op[SP_MAXK];    // typical_p: p in the (s, rank) order
+  float os[SP_MAXK];    // typical_p: s in that order
+  u64_t mask[SP_THREADS / 64];  // membership of S, a bit per rank
+  float Z, logZ, H, cut;
+  int n, top, last;     // |S|, its lowest and its highest rank
+};
+
+// a[0] + a[1] + .. + a[n - 1] in that order from 0.0f, on one thread. a is zero behind n up to the next multiple of 4 (x + 0
+// is x): 16-byte LDS loads and no branch, so the loads run ahead of the dependent adds.
+SLAM_DEVICE float seq_sum(const float* a, int n) {
+  const float4* v = reinterpret_cast<const float4*>(a);
+  float s = 0.f;
+#pragma unroll 8
+  for (int i = 0; i < (n + 3) >> 2; ++i) {
+    const float4 f = v[i];
+    s += f.x;
+    s += f.y;
+    s += f.z;
+    s += f.w;
+  }
+  return s;
+}
+
+// Z_S and log Z_S, summed by thread 0 in rank order, |S| and the lowest and highest rank of S from the waves' ballots; every
+// thread of the block calls it with its own rank's membership and weight (barriers inside).
+SLAM_DEVICE void warp_normaliser(WarpShared& wsh, int kk, bool in, float w) {
+  const int t = threadIdx.x;
+  wsh.kw[t] = in ? w : 0.f;
+  const u64_t m = __ballot(in);
+  if ((t & 63) == 0) wsh.mask[t >> 6] = m;
+  __syncthreads();
+  if (t == 0) {
+    const float z = seq_sum(wsh.kw, kk);
+    int n = 0, top = -1, last = 0;
+#pragma unroll
+    for (int v = 0; v < SP_THREADS / 64; ++v) {
+      const u64_t b = wsh.mask[v];
+      if (b) {
+        n += __popcll(b);
+        if (top < 0) top = 64 * v + __ffsll((long long)b) - 1;
+        last = 64 * v + 63 - __clzll((long long)b);
+      }
+    }
+    wsh.Z = z;
+    wsh.logZ = logf(z);
+    wsh.n = n;
+    wsh.top = top < 0 ? 0 : top;
+    wsh.last = last;
+  }
+  __syncthreads();
+}
+
+// H_S behind warp_normaliser: -(sum of p_j log p_j over S, w_j > 0) in rank order on thread 0. p, lp: this rank's.
+SLAM_DEVICE void warp_entropy(WarpShared& wsh, int kk, bool in, float w, float p, float lp) {
+  const int t = threadIdx.x;
+  wsh.term[t] = (in && w > 0.f) ? p * lp : 0.f;
+  __syncthreads();
+  if (t == 0) wsh.H = -seq_sum(wsh.term, kk);
+  __syncthreads();
+}
+
 // one block per row. ROW: the whole row (vocab <= SP_CHUNK) is selected here; else the candidates of stage 1.
-template <bool ROW>
+// WARP: the warper chain of slam_sample_tokens_warped between the top-p prefix and the draw (sampling only).
+template <bool ROW, bool WARP = false>
 __global__ __launch_bounds__(SP_THREADS) void sample_finish_kernel(const float* __restrict__ logits,
                                                                    const uint8_t* __restrict__ banned,
                                                                    const int64_t* __restrict__ row_ids,
                                                                    const int* __restrict__ eos_ids, uint8_t* __restrict__ done,
                                                                    int64_t* __restrict__ next, int64_t* __restrict__ out,
-                                                                   SampleParams P, const u64_t* __restrict__ ws,
+                                                                   typename SampleParamsOf<WARP>::type P,
+                                                                   const u64_t* __restrict__ ws,
                                                                    const uint32_t* __restrict__ steps) {
   __shared__ u64_t buf[ROW ? SP_CHUNK / 2 : SP_CACHE];
   __shared__ SampleShared sh;
@@ -1024,6 +1102,117 @@ __global__ __launch_bounds__(SP_THREADS) void sample_finish_kernel(const float* 
   }
   if (t < kk) sh.w[t] = t == 0 ? 1.0f : expf((sh.x[t] - sh.x[0]) * P.inv_t);
   __syncthreads();
+  if constexpr (WARP) {
+    __shared__ WarpShared wsh;
+    if (t == 0) {  // the top-p prefix, as in the plain kernel below
+      int m = kk;
+      if (P.top_p < 1.0f) {
+        float tail = 0.f;
+        for (int j = kk - 1; j >= 0; --j) tail += sh.w[j];
+        const float thr = (1.0f - P.top_p) * tail;
+        tail = 0.f;
+        for (int j = kk - 1; j > 0; --j) {
+          tail += sh.w[j];
+          if (tail <= thr) m = j;
+          else break;
+        }
+      }
+      wsh.n = m;
+    }
+    __syncthreads();
+    // thread t owns rank t: its membership of S, its scaled score a, weight w and score x
+    const bool cand = t < kk;
+    bool in = t < wsh.n;
+    const float x = cand ? sh.x[t] : 0.f;
+    const float a = (cand && t > 0) ? (x - sh.x[0]) * P.inv_t : 0.f;
+    const float w = cand ? sh.w[t] : 0.f;
+    if (P.min_p > 0.f) {  // S is a prefix: its lowest rank is 0
+      if (in && w < P.min_p * sh.w[0]) in = false;
+    }
+    if (P.typical_p < 1.0f) {
+      warp_normaliser(wsh, kk, in, w);
+      const float p = w / wsh.Z, lp = a - wsh.logZ;
+      warp_entropy(wsh, kk, in, w, p, lp);
+      const float s = fabsf(-lp - wsh.H);
+      wsh.s[t] = in ? s : __uint_as_float(0x7fc00000u);
+      __syncthreads();
+      if (in) {  // position in the (s ascending, rank ascending) order = the number of ranks of S in front
+        const float4* sv = reinterpret_cast<const float4*>(wsh.s);
+        int pos = 0;
+        for (int i = 0; i < (kk + 3) >> 2; ++i) {
+          const float4 f = sv[i];
+          const int j = 4 * i;
+          pos += (f.x < s || (f.x == s && j + 0 < t)) ? 1 : 0;
+          pos += (f.y < s || (f.y == s && j + 1 < t)) ? 1 : 0;
+          pos += (f.z < s || (f.z == s && j + 2 < t)) ? 1 : 0;
+          pos += (f.w < s || (f.w == s && j + 3 < t)) ? 1 : 0;
+        }
+        wsh.op[pos] = p;
+        wsh.os[pos] = s;
+      }
+      __syncthreads();
+      if (t == 0) {  // c_i is non-decreasing: #{c_i < mass} is the first i with c_i >= mass; no branch, as in seq_sum
+        const float4* pv = reinterpret_cast<const float4*>(wsh.op);
+        const int n = wsh.n;
+        int last = n - 1;
+        bool found = false;
+        float c = 0.f;
+#pragma unroll 4
+        for (int i = 0; i < (n + 3) >> 2; ++i) {
+          const float4 f = pv[i];
+          const float e[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            c += e[q];
+            const bool hit = !found && 4 * i + q < n && !(c < P.typical_p);
+            last = hit ? 4 * i + q : last;
+            found = found || hit;
+          }
+        }
+        wsh.cut = wsh.os[last];
+      }
+      __syncthreads();
+      if (in && s > wsh.cut) in = false;
+    }
+    if (P.eps_cut > 0.f) {
+      warp_normaliser(wsh, kk, in, w);
+      const float p = w / wsh.Z;
+      if (in && p < P.eps_cut && x != sh.x[wsh.top]) in = false;
+    }
+    if (P.eta_cut > 0.f) {
+      warp_normaliser(wsh, kk, in, w);
+      const float p = w / wsh.Z, lp = a - wsh.logZ;
+      warp_entropy(wsh, kk, in, w, p, lp);
+      const float eta = fminf(P.eta_cut, sqrtf(P.eta_cut) * expf(-wsh.H));
+      if (in && p < eta && x != sh.x[wsh.top]) in = false;
+    }
+    warp_normaliser(wsh, kk, in, w);  // total = Z of the final S: the same adds in the same order as cum below
+    if (t != 0) return;
+    const float total = wsh.Z;
+    const int q = b / P.group;
+    const uint64_t r = row_ids ? (uint64_t)row_ids[q] : (uint64_t)q;
+    const uint32_t step = P.step + (steps ? steps[q] : 0u) + (uint32_t)(b - q * P.group);
+    const Philox4 rnd = philox4x32_10((uint32_t)r, step, (uint32_t)(r >> 32), 0x53414D50u, P.k0, P.k1);
+    const float u = (float)(rnd.w[0] >> 8) * 5.9604644775390625e-08f;  // 2^-24
+    const float target = u * total;
+    // cum stands still on a rank outside S (its kw is 0), so the first rank with cum > target is in S
+    const float4* wv = reinterpret_cast<const float4*>(wsh.kw);
+    const int last = wsh.last;
+    int pick = -1;
+    float cum = 0.f;
+#pragma unroll 4
+    for (int i = 0; i < (kk + 3) >> 2; ++i) {
+      const float4 f = wv[i];
+      const float e[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        cum += e[c];
+        pick = (pick < 0 && cum > target) ? 4 * i + c : pick;
+      }
+    }
+    emit_token(sh.id[pick < 0 ? last : pick], true, b, P, eos_ids, done, next, out);
+    return;
+  }
   if (t != 0) return;
   int m = kk;
   if (P.top_p < 1.0f) {
@@ -1677,7 +1866,15 @@ int sample_tokens(const SampleArgs& a, hipStream_t st) {
   if (a.n_eos < 0 || (a.n_eos > 0 && !a.eos_ids)) return -1;
   if (a.group < 1 || a.B % a.group != 0) return -1;
   if (!a.ws || ((uintptr_t)a.ws & 7) || a.ws_bytes < sample_workspace_bytes(a.B, a.vocab, k)) return -1;
-  SampleParams P;
+  // the negated forms refuse NaN
+  if (!(a.min_p >= 0.f && a.min_p <= 1.f) || !(a.typical_p > 0.f && a.typical_p <= 1.f)) return -1;
+  if (!(a.epsilon_cutoff >= 0.f && a.epsilon_cutoff < 1.f) || !(a.eta_cutoff >= 0.f && a.eta_cutoff < 1.f)) return -1;
+  const bool warped = a.do_sample && (a.min_p > 0.f || a.typical_p < 1.f || a.epsilon_cutoff > 0.f || a.eta_cutoff > 0.f);
+  WarpSampleParams P;
+  P.min_p = a.min_p;
+  P.typical_p = a.typical_p;
+  P.eps_cut = a.epsilon_cutoff;
+  P.eta_cut = a.eta_cutoff;
   P.do_sample = a.do_sample ? 1 : 0;
   P.k = k;
   P.vocab = a.vocab;
@@ -1695,6 +1892,15 @@ int sample_tokens(const SampleArgs& a, hipStream_t st) {
   P.out_col = a.out_col >= 0 ? a.out_col : (long long)a.step;
   P.group = a.group;
   u64_t* ws = reinterpret_cast<u64_t*>(a.ws);
+  if (warped) {  // stage 1 is the plain call's; the chain runs behind the ranking of the finish kernel
+    if (P.nch == 1) {
+      sample_finish_kernel<true, true><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws, a.steps);
+    } else {
+      sample_select_kernel<<<dim3(P.nch, a.B), SP_THREADS, 0, st>>>(a.logits, a.banned, a.done, P, ws);
+      sample_finish_kernel<false, true><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws, a.steps);
+    }
+    return (int)hipGetLastError();
+  }
   if (P.nch == 1) {
     sample_finish_kernel<true><<<a.B, SP_THREADS, 0, st>>>(a.logits, a.banned, a.row_ids, a.eos_ids, a.done, a.next, a.out, P, ws, a.steps);
   } else {

@@ -2591,9 +2591,15 @@ size_t slam_sample_workspace_bytes(int32_t B, int32_t vocab, int32_t top_k) { re
 static int sample_any(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
                       const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
                       int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group, int64_t out_col,
-                      slam_stream_t stream) {
+                      slam_stream_t stream, const SlamWarpDesc* warp = nullptr) {
   if (!desc || (desc->do_sample != 0 && desc->do_sample != 1) || desc->n_eos > 16) return SLAM_EINVAL;
   SampleArgs a;  // sample_tokens refuses the rest (-1 = SLAM_EINVAL) before it launches anything
+  if (warp) {
+    a.min_p = warp->min_p;
+    a.typical_p = warp->typical_p;
+    a.epsilon_cutoff = warp->epsilon_cutoff;
+    a.eta_cutoff = warp->eta_cutoff;
+  }
   a.logits = logits;
   a.B = B;
   a.vocab = vocab;
@@ -2632,6 +2638,15 @@ int slam_sample_tokens_at(const float* logits, int32_t B, int32_t vocab, const u
   if (group < 1 || out_col < 0 || ((uintptr_t)steps & 3)) return SLAM_EINVAL;
   return sample_any(logits, B, vocab, banned, desc, row_ids, eos_ids, done, next, out, out_stride, ws, ws_bytes, steps, group,
                     out_col, stream);
+}
+int slam_sample_tokens_warped(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                              const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                              int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group,
+                              int32_t out_col, const SlamWarpDesc* warp, slam_stream_t stream) {
+  static_assert(sizeof(SlamWarpDesc) == 16 && sizeof(SlamSampleDesc) == 40, "the header's layouts");
+  if (group < 1 || out_col < 0 || ((uintptr_t)steps & 3)) return SLAM_EINVAL;
+  return sample_any(logits, B, vocab, banned, desc, row_ids, eos_ids, done, next, out, out_stride, ws, ws_bytes, steps, group,
+                    out_col, stream, warp);
 }
 
 int slam_spec_accept(int64_t* chunk, const int64_t* tgt, int32_t B, int32_t K, int32_t max_new, int32_t pad_id,

@@ -362,6 +362,9 @@ struct SampleArgs {
   int64_t out_col = -1;              // the column of out; negative = step
   void* ws = nullptr;                // sample_workspace_bytes(B, vocab, do_sample ? top_k : 1), 8-byte aligned
   size_t ws_bytes = 0;
+  // slam_sample_tokens_warped: the second half of HF's warper chain on the ranked candidates. All four off (the defaults),
+  // or greedy, takes the launches of slam_sample_tokens_at.
+  float min_p = 0.f, typical_p = 1.f, epsilon_cutoff = 0.f, eta_cutoff = 0.f;
 };
 size_t sample_workspace_bytes(int B, int vocab, int top_k);  // host only
 int sample_tokens(const SampleArgs& a, hipStream_t st);

@@ -38,6 +38,18 @@ class SlamSampleDesc(C.Structure):
     ]
 
 
+class SlamWarpDesc(C.Structure):
+    """The second half of HF's warper chain for slam_sample_tokens_warped; the defaults are "all off"."""
+    _fields_ = [("min_p", C.c_float), ("typical_p", C.c_float), ("epsilon_cutoff", C.c_float), ("eta_cutoff", C.c_float)]
+
+    def __init__(self, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+        super().__init__(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+
+    @property
+    def active(self) -> bool:
+        return self.min_p > 0 or self.typical_p < 1 or self.epsilon_cutoff > 0 or self.eta_cutoff > 0
+
+
 class SlamConstrainDesc(C.Structure):
     _fields_ = [
         ("step", C.c_int32), ("no_repeat_ngram", C.c_int32), ("n_per_prompt", C.c_int32), ("prompt_stride", C.c_int32),
@@ -110,6 +122,8 @@ def load_library(path: Optional[str] = None):
         "slam_kv_rewind": (C.c_int, [vp, i32]),
         "slam_sample_tokens_at": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp, i32,
                                             i32, vp]),
+        "slam_sample_tokens_warped": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp,
+                                                i32, i32, C.POINTER(SlamWarpDesc), vp]),
         "slam_spec_accept": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "slam_ngram_propose": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, vp, vp]),
         "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
@@ -259,6 +273,23 @@ def sample_tokens_at(logits, desc: SlamSampleDesc, next_ids, ws, steps=None, gro
                                              stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_sample_tokens_at failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+def sample_tokens_warped(logits, desc: SlamSampleDesc, next_ids, ws, warp: Optional[SlamWarpDesc], steps=None, group: int = 1,
+                         out_col: Optional[int] = None, banned=None, row_ids=None, eos_ids=None, done=None, out=None,
+                         stream: Optional[int] = None):
+    """slam_sample_tokens_warped: sample_tokens_at with min_p / typical_p / epsilon_cutoff / eta_cutoff (`warp`, a
+    SlamWarpDesc; None or all off = sample_tokens_at itself) applied to the ranked top-k candidates behind top-p.
+    out_col=None writes column desc.step, which with steps=None and group=1 makes this sample_tokens' call. Only enqueues work."""
+    B, V = logits.shape
+    rc = load_library().slam_sample_tokens_warped(_ptr(logits), B, V, _ptr(banned), C.byref(desc), _ptr(row_ids), _ptr(eos_ids),
+                                                 _ptr(done), _ptr(next_ids), _ptr(out), out.stride(0) if out is not None else 0,
+                                                 _ptr(ws), ws.numel() * ws.element_size(), _ptr(steps), int(group),
+                                                 int(desc.step if out_col is None else out_col),
+                                                 C.byref(warp) if warp is not None else None,
+                                                 stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_sample_tokens_warped failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 SPEC_MAX_ROWS = 1024  # slam_spec_accept: one block, a thread per row

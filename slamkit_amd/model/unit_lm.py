@@ -324,8 +324,10 @@ def _right_padded(mask: torch.Tensor) -> bool:
     return bool((m[:, 1:] <= m[:, :-1]).all())
 
 
-def _warp(scores: torch.Tensor, temperature: float, top_k: int, top_p: float) -> torch.Tensor:
-    """HF's sampling warpers in HF's order: temperature, top-k, top-p (at least one token kept)."""
+def _warp(scores: torch.Tensor, temperature: float, top_k: int, top_p: float, min_p: float = 0.0, typical_p: float = 1.0,
+          epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0) -> torch.Tensor:
+    """HF's sampling warpers in HF's order: temperature, top-k, top-p, min_p, typical_p, epsilon_cutoff, eta_cutoff (at least
+    one token kept; each is HF's own definition on the full row, on what the warpers before it left finite)."""
     if temperature != 1.0:
         scores = scores / temperature
     if top_k > 0:
@@ -337,6 +339,29 @@ def _warp(scores: torch.Tensor, temperature: float, top_k: int, top_p: float) ->
         drop = cum <= (1 - top_p)
         drop[:, -1] = False
         scores = scores.masked_fill(drop.scatter(1, idx, drop), float("-inf"))
+    if min_p > 0.0:  # MinPLogitsWarper: probs < min_p * max prob
+        probs = scores.softmax(-1)
+        scores = scores.masked_fill(probs < min_p * probs.amax(-1, keepdim=True), float("-inf"))
+    if typical_p < 1.0:  # TypicalLogitsWarper: the tokens whose -log p is closest to the entropy, up to the mass
+        logp = scores.log_softmax(-1)
+        ent = -(logp * logp.exp()).nansum(-1, keepdim=True)
+        srt, idx = torch.sort((-logp - ent).abs(), descending=False)
+        cum = scores.gather(-1, idx).softmax(-1).cumsum(-1)
+        last = (cum < typical_p).sum(-1, keepdim=True).clamp_(max=scores.shape[-1] - 1)
+        drop = srt > srt.gather(1, last)
+        drop[:, 0] = False
+        scores = scores.masked_fill(drop.scatter(1, idx, drop), float("-inf"))
+    if epsilon_cutoff > 0.0:  # EpsilonLogitsWarper: probs < epsilon, every top-1 score exempt
+        drop = (scores.softmax(-1) < epsilon_cutoff) & (scores < scores.amax(-1, keepdim=True))
+        scores = scores.masked_fill(drop, float("-inf"))
+    if eta_cutoff > 0.0:  # EtaLogitsWarper: probs < min(epsilon, sqrt(epsilon) exp(-entropy))
+        logp = scores.log_softmax(-1)
+        probs = logp.exp()
+        ent = -(logp * probs).nansum(-1, keepdim=True)
+        eps = torch.tensor(eta_cutoff, dtype=scores.dtype, device=scores.device)
+        eta = torch.min(eps, torch.sqrt(eps) * torch.exp(-ent))
+        drop = (scores.softmax(-1) < eta) & (scores < scores.amax(-1, keepdim=True))
+        scores = scores.masked_fill(drop, float("-inf"))
     return scores
 
 
@@ -1087,7 +1112,9 @@ class UnitLM(TokenLM):
                  min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
                  begin_suppress_tokens: Optional[List[int]] = None, suppress_tokens: Optional[List[int]] = None,
                  assistant_model: Optional["UnitLM"] = None, num_assistant_tokens: Optional[int] = None,
-                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None, **kwargs):
+                 prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
+                 min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                 eta_cutoff: Optional[float] = None, **kwargs):
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
@@ -1167,7 +1194,22 @@ class UnitLM(TokenLM):
         the tokens actually proposed (not rows x K). Refused (ValueError): together with assistant_model;
         max_matching_ngram_size without prompt_lookup_num_tokens; K or n out of range; and the assistant's list
         (num_return_sequences > 1, return_logprobs, history-dependent bans, do_sample without sampler="engine"). With both
-        arguments absent generate is what it was, launch for launch."""
+        arguments absent generate is what it was, launch for launch.
+
+        `min_p`, `typical_p`, `epsilon_cutoff`, `eta_cutoff` (sampling only; also read from `generation_config`) are the
+        second half of HF's warper chain, applied in HF's order behind temperature, top_k and top_p: min_p in [0, 1] (0 off)
+        drops tokens below min_p times the top probability; typical_p in (0, 1] (1 off) keeps the tokens whose -log p is
+        closest to the entropy up to that mass; epsilon_cutoff in [0, 1) (0 off) drops probabilities below it; eta_cutoff in
+        [0, 1) (0 off) drops those below min(eps, sqrt(eps) exp(-entropy)); ValueError outside these ranges. Each warper
+        renormalises what the ones before it kept and keeps at least one token. The torch sampler applies HF's definitions
+        to the full row, so top_k=0 works there. The engine sampler applies them to the ranked top-k candidates inside the
+        sampling kernel (slam_sample_tokens_warped: no further launch, no further random word, still no torch op between two
+        engine calls), which is HF's chain exactly when 1 <= top_k <= 256 is part of the request - it has to be under this
+        sampler. Two deviations from HF: a tie at the k-th score goes to the lower id (HF keeps every tie), and tokens with
+        equal |-log p - entropy| are ordered by rank, (score descending, id ascending), where torch.sort leaves their order
+        open. Assisted and prompt-lookup decoding verify with the same chain (the draft proposes with it too), so their
+        tokens stay the target's own draws. Greedy decoding ignores the four, as HF does. With all four absent or off
+        generate calls what it called before, launch for launch."""
         if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
             raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
         if self.config.is_opt:
@@ -1191,6 +1233,21 @@ class UnitLM(TokenLM):
         temperature = float(pick(temperature, "temperature", 1.0))
         top_k = int(pick(top_k, "top_k", 0) or 0)
         top_p = float(pick(top_p, "top_p", 1.0))
+        min_p = float(pick(min_p, "min_p", 0.0))
+        typical_p = float(pick(typical_p, "typical_p", 1.0))
+        epsilon_cutoff = float(pick(epsilon_cutoff, "epsilon_cutoff", 0.0))
+        eta_cutoff = float(pick(eta_cutoff, "eta_cutoff", 0.0))
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1] (got {min_p})")
+        if not 0.0 < typical_p <= 1.0:
+            raise ValueError(f"typical_p must be in (0, 1] (got {typical_p})")
+        for name, v in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
+            if not 0.0 <= v < 1.0:
+                raise ValueError(f"{name} must be in [0, 1) (got {v})")
+        late = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+        # the engine sampler's description of them: None (the plain entry points) unless one is on and tokens are sampled
+        warp = E.SlamWarpDesc(**late)
+        warp = warp if do_sample and warp.active else None
         eos = pick(eos_token_id, "eos_token_id", self.config.eos_token_id)
         eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
         pad = pick(pad_token_id, "pad_token_id", self.config.pad_token_id)
@@ -1261,10 +1318,10 @@ class UnitLM(TokenLM):
         if assist_k is not None or lookup_k is not None:
             if assist_k is not None:
                 new, n = self._generate_assisted(assistant_model, assist_k, ids, lens, T, max_new_tokens, bad, eos, int(pad),
-                                                 do_sample, top_k, temperature, top_p, seed, sample_ids, prefill_chunk)
+                                                 do_sample, top_k, temperature, top_p, seed, sample_ids, prefill_chunk, warp)
             else:
                 new, n = self._generate_lookup(lookup_k, lookup_n, ids, lens, T, max_new_tokens, bad, eos, int(pad), do_sample,
-                                               top_k, temperature, top_p, seed, sample_ids, prefill_chunk)
+                                               top_k, temperature, top_p, seed, sample_ids, prefill_chunk, warp)
             if eos and n > 1:  # the plain path's trim: stop right behind the step on which the last row finished
                 all_done = (torch.isin(new, torch.tensor(eos, dtype=torch.long, device=dev)).cumsum(1) > 0).all(0)
                 if bool(all_done.any()):
@@ -1292,7 +1349,7 @@ class UnitLM(TokenLM):
         cons = _Constrainer(plan, ids, lens[:B].clone(), T_in, nret, new, lp is not None, dev) if plan.active else None
         if on_device:
             n = self._sample_on_device(logits, new, ids, lens, T, bad, eos, int(pad), do_sample, top_k, temperature, top_p,
-                                       seed, sample_ids, nret, lp, prefill_chunk, cons)
+                                       seed, sample_ids, nret, lp, prefill_chunk, cons, warp)
         else:
             bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
             g = None
@@ -1308,7 +1365,7 @@ class UnitLM(TokenLM):
                 if bad_idx is not None:
                     scores = scores.index_fill(1, bad_idx, float("-inf"))
                 if do_sample:
-                    scores = _warp(scores, temperature, top_k, top_p)
+                    scores = _warp(scores, temperature, top_k, top_p, **late)
                     nxt = torch.multinomial(torch.softmax(scores, -1), 1, generator=g)[:, 0]
                 else:
                     nxt = scores.argmax(-1)
@@ -1473,7 +1530,7 @@ class UnitLM(TokenLM):
             self.engine.extend(ids[:, c0:c0 + w].contiguous(), new_lens, cur, B, w, logits)
 
     def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids,
-                          nret=1, lp=None, prefill_chunk=None, cons=None):
+                          nret=1, lp=None, prefill_chunk=None, cons=None, warp=None):
         """The decode loop of generate(sampler="engine"): prefill, sample(step 0), then decode_step(next) / sample(step k). The
         kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written.
         logits / new have B n rows: the prompts (ids, the first rows of lens) are prefilled once and fanned out (kv_repeat).
@@ -1505,8 +1562,11 @@ class UnitLM(TokenLM):
         n = 0
         for step in range(max_new):
             desc.step = step
-            E.sample_tokens(logits if cons is None else cons.apply(logits, step, done), desc, nxt, ws, banned, row_ids, eos_i,
-                            done, new)
+            scores = logits if cons is None else cons.apply(logits, step, done)
+            if warp is None:
+                E.sample_tokens(scores, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+            else:
+                E.sample_tokens_warped(scores, desc, nxt, ws, warp, None, 1, None, banned, row_ids, eos_i, done, new)
             if lp is not None:
                 E.token_logprobs(logits, nxt, lp[0], step, lp[2], done, lp[1])
             n = step + 1
@@ -1549,7 +1609,7 @@ class UnitLM(TokenLM):
     last_assist_stats = None
 
     def _generate_assisted(self, draft, K, ids, lens, T, max_new, bad, eos, pad, do_sample, top_k, temperature, top_p, seed,
-                           sample_ids, prefill_chunk=None):
+                           sample_ids, prefill_chunk=None, warp=None):
         """generate(assistant_model=draft): draft-model speculative decoding on the two engines' KV caches. ids [B, T] the
         compacted prompts, lens int32 [B] their lengths. Returns (new [B, n] int64, pad behind a row's end; n). State at the
         start of a round: the committed sequence of row b is its prompt + n_new[b] tokens, the target's
@@ -1599,7 +1659,10 @@ class UnitLM(TokenLM):
         new = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
         nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+        if warp is None:
+            E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+        else:
+            E.sample_tokens_warped(logits, desc, nxt, ws, warp, None, 1, None, banned, row_ids, eos_i, done, new)
         desc.n_eos = 0  # from here on slam_spec_accept looks for the EOS ids: a proposal that is one ends nothing yet
         if max_new == 1:
             done.fill_(1)
@@ -1624,13 +1687,19 @@ class UnitLM(TokenLM):
             draft.engine.extend(draft_ids, draft_new_lens, lens_d, B, 2, logits_d)
             for j in range(1, K1):
                 desc.step = j - 1
-                E.sample_tokens_at(logits_d, desc, nxt, ws, n_new, 1, j, banned, row_ids, None, None, chunk)
+                if warp is None:
+                    E.sample_tokens_at(logits_d, desc, nxt, ws, n_new, 1, j, banned, row_ids, None, None, chunk)
+                else:
+                    E.sample_tokens_warped(logits_d, desc, nxt, ws, warp, n_new, 1, j, banned, row_ids, None, None, chunk)
                 if j < K:
                     draft.engine.decode_step(nxt, lens_d, B, logits_d)
             # target: the logits behind every chunk column, and its own token there with the draw the draft used
             self.engine.extend_logits(chunk, tgt_new_lens, lens_t, B, K1, logits_all)
             desc.step = 0
-            E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
+            if warp is None:
+                E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
+            else:
+                E.sample_tokens_warped(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, warp, n_new, K1, 0, banned, row_ids)
             if trace is not None:
                 rec = (chunk.cpu(), logits_all.cpu(), n_new.cpu(), tgt.cpu())
             E.spec_accept(chunk, tgt, K, max_new, pad, eos_i, prompt_len, n_new, done, new, lens_t, lens_d, draft_ids,
@@ -1671,7 +1740,7 @@ class UnitLM(TokenLM):
     _lookup_trace = None  # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after, n_prop)
 
     def _generate_lookup(self, K, ngram, ids, lens, T, max_new, bad, eos, pad, do_sample, top_k, temperature, top_p, seed,
-                         sample_ids, prefill_chunk=None):
+                         sample_ids, prefill_chunk=None, warp=None):
         """generate(prompt_lookup_num_tokens=K): _generate_assisted without the draft model, its cache and its catch-up
         steps. The proposals of a round come from slam_ngram_propose on the row's own history (ids, then `new` up to n_new);
         all K + 1 chunk columns of a live row are verified, the ones without a proposal holding `pad`, so every row of
@@ -1713,7 +1782,10 @@ class UnitLM(TokenLM):
         new = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
         nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+        if warp is None:
+            E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
+        else:
+            E.sample_tokens_warped(logits, desc, nxt, ws, warp, None, 1, None, banned, row_ids, eos_i, done, new)
         desc.n_eos = 0  # from here on slam_spec_accept looks for the EOS ids
         if max_new == 1:
             done.fill_(1)
@@ -1739,7 +1811,10 @@ class UnitLM(TokenLM):
             E.ngram_propose(chunk, n_prop, ngram, pad, ids, prompt_len, new, n_new, done, eos_i, stats[5:])
             self.engine.extend_logits(chunk, tgt_new_lens, lens_t, B, K1, logits_all)
             desc.step = 0
-            E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
+            if warp is None:
+                E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
+            else:
+                E.sample_tokens_warped(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, warp, n_new, K1, 0, banned, row_ids)
             if trace is not None:
                 rec = (chunk.cpu(), logits_all.cpu(), n_new.cpu(), tgt.cpu())
             E.spec_accept(chunk, tgt, K, max_new, pad, eos_i, prompt_len, n_new, done, new, lens_t, lens_d, draft_ids,

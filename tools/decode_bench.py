@@ -36,6 +36,11 @@ new tokens per row, no_repeat_ngram 3, device events around 200 back-to-back cal
 (scores is logits: only the bans are written) and `copy_us` (scores in a buffer of its own), with `copy_floor_us` =
 2 B V 4 bytes / 6.3 TB/s. With --sampler S --no-repeat-ngram n: end-to-end greedy generate with sampler S, without and with
 no_repeat_ngram_size = n, alternated rep by rep: one line per setting with `no_repeat_ngram_size`, `generate_s`, `generate_s_all`.
+--sample-op --warp times slam_sample_tokens_warped beside slam_sample_tokens at (B, V) = (8, 502), (8, 152167), (64, 152167)
+and top_k 25 and 256: `plain_us`, `warped_all_us` (min_p 0.05, typical_p 0.95, epsilon 1e-3, eta 2e-3) and `warped_typical_us`
+(typical_p 0.9 alone), device events around 200 back-to-back calls, five alternating rounds, median and [min, max]. With
+--sampler engine --warp: end-to-end sampled generate (temperature 0.8, top_k 25) without (`way` = "plain") and with those four
+warpers (`way` = "warped"), alternated rep by rep.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -244,6 +249,79 @@ def sample_op_bench(calls=200, rounds=5):
         print(json.dumps(res), flush=True)
 
 
+WARP_ALL = dict(min_p=0.05, typical_p=0.95, epsilon_cutoff=1e-3, eta_cutoff=2e-3)
+
+
+def warp_op_bench(calls=200, rounds=5):
+    """Device-event time of slam_sample_tokens_warped (all four warpers on, and typical_p alone) beside slam_sample_tokens."""
+    import torch
+    from slamkit_amd import engine as E
+    dev = torch.device("cuda")
+    for B, V in ((8, 502), (8, 152167), (64, 152167)):
+        g = torch.Generator(device=dev).manual_seed(V + B)
+        logits = torch.randn(B, V, device=dev, generator=g) * 3.0
+        banned = torch.zeros(V, dtype=torch.uint8, device=dev)
+        banned[torch.tensor([3, 4, 5], device=dev)] = 1
+        eos_i = torch.tensor([1], dtype=torch.int32, device=dev)
+        new = torch.empty(B, calls, dtype=torch.int64, device=dev)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev)
+        for top_k in (25, 256):
+            desc = E.SlamSampleDesc(do_sample=1, top_k=top_k, temperature=0.8, top_p=1.0, seed=11, step=0, pad_id=0, n_eos=1)
+            ws = torch.empty(E.sample_workspace_bytes(B, V, top_k), dtype=torch.uint8, device=dev)
+
+            def run(warp):
+                def fn():
+                    done = torch.zeros(B, dtype=torch.uint8, device=dev)
+                    for k in range(calls):
+                        desc.step = k
+                        if warp is None:
+                            E.sample_tokens(logits, desc, nxt, ws, banned, None, eos_i, done, new)
+                        else:
+                            E.sample_tokens_warped(logits, desc, nxt, ws, warp, None, 1, None, banned, None, eos_i, done, new)
+                return fn
+
+            ways = {"plain": run(None), "warped_all": run(E.SlamWarpDesc(**WARP_ALL)),
+                    "warped_typical": run(E.SlamWarpDesc(typical_p=0.9))}
+            for fn in ways.values():
+                fn()
+            torch.cuda.synchronize()
+            t = {w: [] for w in ways}
+            for _ in range(rounds):  # alternated
+                for w, fn in ways.items():
+                    t[w].append(ev_ms(fn) / calls * 1e3)
+            res = dict(bench="warp_op", B=B, vocab=V, top_k=top_k)
+            for w in ways:
+                res[f"{w}_us"] = round(statistics.median(t[w]), 2)
+                res[f"{w}_us_minmax"] = [round(min(t[w]), 2), round(max(t[w]), 2)]
+            print(json.dumps(res), flush=True)
+
+
+def e2e_warp(m, B, P, new, reps, tag):
+    """generate_s of the engine sampler (temperature 0.8, top_k 25) without and with the four warpers, alternated rep by rep."""
+    import torch
+    dev = m.device
+    g = torch.Generator(device=dev).manual_seed(1)
+    ids = torch.randint(2, m.config.vocab_size, (B, P), device=dev, generator=g)
+    kw = dict(input_ids=ids, max_new_tokens=new, eos_token_id=[], do_sample=True, temperature=0.8, top_k=25, seed=11,
+              sampler="engine")
+    m._ensure_workspace(B * (-(-(P + new) // 64) * 64))
+    ways = {"plain": {}, "warped": WARP_ALL}
+    times = {w: [] for w in ways}
+    for extra in ways.values():
+        m.generate(**kw, **extra)  # warm-up
+    for _ in range(reps):
+        for w, extra in ways.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.generate(**kw, **extra)
+            torch.cuda.synchronize()
+            times[w].append(time.perf_counter() - t0)
+    for w in ways:
+        print(json.dumps(dict(bench="generate_e2e_warp", model=tag, B=B, prompt=P, new_tokens=new, way=w,
+                              generate_s=round(statistics.median(times[w]), 4),
+                              generate_s_all=[round(t, 4) for t in times[w]])), flush=True)
+
+
 def nbest_bench(name, B, P, new, reps, n):
     """n continuations per prompt from one prefill against the repeated batch; kv_repeat alone."""
     import torch
@@ -442,6 +520,9 @@ def main():
     ap.add_argument("--sampler", default=None, help="torch,engine: end-to-end generate per sampler, alternated")
     ap.add_argument("--do-sample", action="store_true", help="with --sampler: temperature 0.8, top_k 25 instead of greedy")
     ap.add_argument("--sample-op", action="store_true", help="time the token choice alone (engine vs torch ops)")
+    ap.add_argument("--warp", action="store_true",
+                    help="with --sample-op: slam_sample_tokens_warped beside slam_sample_tokens; with --sampler engine: "
+                         "sampled generate without and with min_p / typical_p / epsilon_cutoff / eta_cutoff")
     ap.add_argument("--constrain-op", action="store_true", help="time slam_constrain_scores alone (in place and copying)")
     ap.add_argument("--no-repeat-ngram", type=int, default=0,
                     help="n, with --sampler S: end-to-end greedy generate without and with no_repeat_ngram_size=n, alternated")
@@ -456,7 +537,10 @@ def main():
     import torch
     assert torch.cuda.is_available()
     if a.sample_op:
-        sample_op_bench()
+        if a.warp:
+            warp_op_bench()
+        else:
+            sample_op_bench()
         return
     if a.constrain_op:
         constrain_op_bench()
@@ -473,7 +557,9 @@ def main():
     for name in a.models.split(","):
         m = build(name, 4096)
         if a.sampler:
-            if a.no_repeat_ngram > 0:
+            if a.warp:
+                e2e_warp(m, 8, 256, a.steps, a.reps, name)
+            elif a.no_repeat_ngram > 0:
                 for smp in a.sampler.split(","):
                     e2e_no_repeat(m, 8, 256, a.steps, a.reps, name, smp, a.no_repeat_ngram)
             else:
