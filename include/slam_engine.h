@@ -283,6 +283,41 @@ int slam_extend_logits(SlamEngine* h, const int64_t* ids, const int32_t* new_len
                        float* logits_all, slam_stream_t stream);
 int slam_kv_rewind(SlamEngine* h, int32_t hi);
 
+/* ---- decoding from FP8 weights: an exact, power-of-two-scaled e4m3 copy of the decode projections ----
+ * A decode step (and an extend pass of up to 64 rows) is one stream of the weights. This copy halves the bytes of that stream
+ * for wqkv, wo, wgu and wd of every layer (and the head matrix when include_head) without a second model: quantising REPLACES
+ * the bf16 parameters by the values the codes stand for, so the bf16 kernels (prefill, extend above 64 rows, slam_forward,
+ * scoring) and the FP8 stream compute the same model, bit for bit.
+ * The rule, per row n of a matrix W[N][K], amax = max_k |W[n][k]| = f 2^x with 1 <= f < 2:
+ *   e[n] = 0 for a zero row, else the smallest integer with amax <= 448 2^e - x - 8 when f <= 1.75, x - 7 above, taken from
+ *          the bf16 bits - clamped to [-100, 120];
+ *   q[n][k] = the OCP e4m3fn code of W[n][k] 2^-e[n], round to nearest even, the sign of zero kept (|value| <= 448 by
+ *          construction: the NaN codes 0x7F / 0xFF never appear and nothing saturates);
+ *   Wdq[n][k] = value(q[n][k]) 2^e[n], exact in bf16.
+ * The decode kernel turns code -> fp32 -> times 2^e -> high 16 bits and feeds the MFMA exactly as the bf16 kernel is fed from
+ * Wdq: same lanes, same K order, same split plan, same reduce launch. Non-finite weights are outside the contract (the caller
+ * checks). A row whose amax reaches 1.9375 * 2^127 rounds up to 2^128: do not quantise such weights.
+ * Storage: exponents are int8, one per row. Codes take N K bytes; their order inside a row is PRIVATE to the engine (every
+ * 64-deep K block is permuted so that a lane's 16-byte load holds its operands of two MFMA steps): read them back with
+ * slam_op_dequantize_rows_fp8 only. The path needs K % 64 == 0 for every matrix - hidden, intermediate and
+ * n_heads * head_dim multiples of 64; other engines are refused at bind time and decode stays on bf16.
+ * slam_decode_w8_bytes: the buffer for all matrices (256-byte aligned sub-buffers; 0 for a refused engine or OPT).
+ * slam_bind_decode_w8: caller-owned device buffer, 256-byte aligned; NULL unbinds. Resets the launch counter. SLAM_EINVAL with
+ *   a message for OPT (arch 1: no decode path) and for a refused K; SLAM_ENOMEM for a short buffer. State 1 afterwards.
+ * slam_quantize_decode_w8: joins the optimizer and pending parameter all-gathers (as slam_decode_step does), quantises the
+ *   bound parameters IN PLACE (they become Wdq), refreshes the transposed images if bound, and marks the codes valid (state 2).
+ *   With a tied head and include_head the head matrix IS the embedding table: its first `vocab` rows become Wdq too, so the
+ *   embedding lookup changes with it. A caller that keeps an fp32 master copies Wdq into it itself.
+ * slam_decode_w8_state: 0 unbound, 1 bound but stale, 2 valid. Every entry point that writes or rebinds the parameters drops 2
+ *   to 1 - slam_bind_params, slam_cast_params, every slam_adamw_*, slam_allgather_params_async, and slam_refresh_transposed
+ *   (what a caller that wrote the buffer itself must call anyway). Decode then runs the bf16 kernels: always correct.
+ * slam_decode_w8_launches: FP8 projection launches since the bind (4 per layer, + 1 with the head, per decode step). */
+size_t slam_decode_w8_bytes(SlamEngine* h, int32_t include_head);
+int slam_bind_decode_w8(SlamEngine* h, void* buf, size_t bytes, int32_t include_head);
+int slam_quantize_decode_w8(SlamEngine* h, slam_stream_t stream);
+int slam_decode_w8_state(SlamEngine* h);
+int64_t slam_decode_w8_launches(SlamEngine* h);
+
 /* ---- choosing the next token on the device (what HF's logits processors + torch.multinomial do between two decode steps) ----
  * slam_sample_tokens needs no engine: it reads fp32 logits [B][vocab] (row stride vocab, 4-byte aligned; odd vocabularies
  * are fine) such as slam_prefill / slam_decode_step wrote, and writes the chosen ids where slam_decode_step reads them, so a
@@ -819,6 +854,19 @@ int slam_op_gemm_tn_image(const void* dY, const void* X, float* dW, void* dW_bf1
 size_t slam_op_gemm_skinny_workspace(int M, int N, int K);
 int slam_op_gemm_skinny(const void* X, const void* W, void* Y, int y_f32, const void* bias, const void* resid, int M, int N, int K,
                         float* ws, size_t ws_bytes, slam_stream_t s);
+/* The FP8 weight stream of slam_quantize_decode_w8 on one matrix (the rule and the storage are stated there). K % 64 == 0, W
+ * and codes 16-byte aligned, else SLAM_EINVAL. One allocation of slam_op_w8_bytes(N, K) holds the codes at offset 0 and the
+ * int8 exponents at slam_op_w8_exps_offset(N, K) (both 0 for a refused K); the calls take the two pointers.
+ * slam_op_quantize_rows_fp8: codes and exponents from W bf16 [N][K], and W rewritten in place with Wdq.
+ * slam_op_dequantize_rows_fp8: W bf16 [N][K] row-major = Wdq from codes and exponents.
+ * slam_op_gemm_skinny_w8: slam_op_gemm_skinny with codes + exponents in place of W; the bits of
+ * slam_op_gemm_skinny(X, Wdq, ..) with the same workspace size. */
+size_t slam_op_w8_bytes(int N, int K);
+size_t slam_op_w8_exps_offset(int N, int K);
+int slam_op_quantize_rows_fp8(void* W, void* codes, void* exps, int N, int K, slam_stream_t s);
+int slam_op_dequantize_rows_fp8(const void* codes, const void* exps, void* W, int N, int K, slam_stream_t s);
+int slam_op_gemm_skinny_w8(const void* X, const void* codes, const void* exps, void* Y, int y_f32, const void* bias,
+                           const void* resid, int M, int N, int K, float* ws, size_t ws_bytes, slam_stream_t s);
 /* LM head fused with the row statistics, alone (the hot path of slam_extend_score). X bf16 [M][K] (K % 8 == 0), W bf16 [V][K],
  * both 16-byte aligned. x_i = the fp32 accumulator of v_mfma_f32_16x16x32_bf16 for row m against vocabulary row i, K taken
  * in ascending steps of 32 (a last partial step is zero-filled): its order depends on K alone. x_i is never rounded to bf16

@@ -21,6 +21,11 @@ SLAM_DEVICE uint32_t pack_bf16x2(float lo, float hi) {
 }
 SLAM_DEVICE bf16_t f32_to_bf16(float f) { return (bf16_t)(pack_bf16x2(f, 0.f) & 0xffffu); }
 
+// the high halves of two fp32 values as a bf16 pair (truncation: for values that are exact in bf16), one v_perm_b32
+SLAM_DEVICE uint32_t bf16_hi_pair(float lo, float hi) {
+  return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
+}
+
 SLAM_DEVICE void unpack_bf16x8(const uint4& v, float* f) {
   f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
   f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);

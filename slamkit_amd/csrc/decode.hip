@@ -182,6 +182,107 @@ int launch_skinny(const bf16_t* X, const bf16_t* W, void* Y, const bf16_t* bias,
   return (int)hipGetLastError();
 }
 
+// ---- the same stream from FP8 codes (kernels.h: W8_K_GRAIN, w8_code_pos) --------------------------------------------------
+constexpr int SK8_U = 2;  // 64-deep code blocks per unrolled group: the K depth of gemm_skinny_kernel's group
+
+// eight codes (two dwords) -> the B operand: code -> fp32 (v_cvt_pk_f32_fp8) -> times the row's 2^e (exact) -> high 16 bits
+SLAM_DEVICE uint4 w8_operand(uint32_t c0, uint32_t c1, float sc) {
+  const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)c0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)c0, true);
+  const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)c1, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)c1, true);
+  uint4 w;
+  w.x = bf16_hi_pair(a.x * sc, a.y * sc);
+  w.y = bf16_hi_pair(b.x * sc, b.y * sc);
+  w.z = bf16_hi_pair(c.x * sc, c.y * sc);
+  w.w = bf16_hi_pair(d.x * sc, d.y * sc);
+  return w;
+}
+
+// gemm_skinny_kernel with W read as codes Q[N][K] (K a multiple of 64) and exponents E[N]: same grid, same K range per block,
+// the 32-deep steps of a lane in the same order with the same operands. A lane's 16-byte load holds its codes of the two steps
+// of one 64-deep block; a K range that starts in the middle of a block (odd kps) skips that block's first step, one that ends
+// there its second. Every bound below is a multiple of 32, so a step is valid or not for the whole wave.
+template <int MT, bool F32OUT>
+__global__ __launch_bounds__(256) void gemm_skinny_w8_kernel(const bf16_t* __restrict__ X, const uint8_t* __restrict__ Q,
+                                                             const int8_t* __restrict__ E, void* __restrict__ Y,
+                                                             float* __restrict__ part, const bf16_t* __restrict__ bias,
+                                                             const bf16_t* __restrict__ resid, int M, int N, int K, int kps) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n0 = (blockIdx.x * SK_WAVES + wave) * 16;
+  if (n0 >= N) return;
+  const int q = lane >> 4, j = lane & 15;
+  const int m_base = blockIdx.z * 64;
+  const int kb = blockIdx.y * kps * 32;
+  const int ke = min(K, kb + kps * 32);
+  const int nr = min(n0 + j, N - 1);  // tail rows re-read the last row; their results are not stored
+  const uint8_t* qrow = Q + (size_t)nr * K + 16 * q;
+  const float sc = __uint_as_float((uint32_t)((int)E[nr] + 127) << 23);  // lane j owns row n0 + j: its scale is a lane constant
+  const bf16_t* xrow[MT];
+  bool xv[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    const int m = m_base + 16 * t + j;
+    xv[t] = m < M;
+    xrow[t] = X + (size_t)(xv[t] ? m : 0) * K + 8 * q;
+  }
+  f32x4_t acc[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const uint4 zero = {0u, 0u, 0u, 0u};
+  for (int k = kb & ~63; k < ke; k += 64 * SK8_U) {
+    uint4 c[SK8_U];
+#pragma unroll
+    for (int u = 0; u < SK8_U; ++u) {
+      const int kk = k + 64 * u;
+      c[u] = kk < ke ? *reinterpret_cast<const uint4*>(qrow + kk) : zero;  // kk < ke <= K, K % 64 == 0: the block is whole
+    }
+#pragma unroll
+    for (int u = 0; u < SK8_U; ++u)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int kk = k + 64 * u + 32 * s;
+        if (kk < kb || kk >= ke) continue;
+        const uint4 w = s ? w8_operand(c[u].z, c[u].w, sc) : w8_operand(c[u].x, c[u].y, sc);
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          const uint4 a = xv[t] ? *reinterpret_cast<const uint4*>(xrow[t] + kk) : zero;
+          acc[t] = mfma16(a, w, acc[t]);
+        }
+      }
+  }
+  // lane holds acc[t][r] = Y[m_base + 16 t + 4 q + r][n0 + j]
+  const int n = n0 + j;
+  if (n >= N) return;
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = m_base + 16 * t + 4 * q + r;
+      if (m >= M) continue;
+      if (part) part[((size_t)blockIdx.y * M + m) * N + n] = acc[t][r];
+      else skinny_store<F32OUT>(Y, bias, resid, m, n, N, acc[t][r]);
+    }
+}
+
+template <bool F32OUT>
+int launch_skinny_w8(const bf16_t* X, const uint8_t* Q, const int8_t* E, void* Y, const bf16_t* bias, const bf16_t* resid, int M,
+                     int N, int K, float* ws, size_t ws_bytes, hipStream_t st) {
+  const SkinnyPlan p = skinny_plan(M, N, K, ws ? ws_bytes : 0);
+  float* part = p.splits > 1 ? ws : nullptr;
+  const dim3 grid(nblk((size_t)N, 16 * SK_WAVES), p.splits, nblk((size_t)M, 64));
+  const int mt = ((M < 64 ? M : 64) + 15) / 16;
+#define SK8_CASE(T) \
+  case T: gemm_skinny_w8_kernel<T, F32OUT><<<grid, 256, 0, st>>>(X, Q, E, Y, part, bias, resid, M, N, K, p.kps); break;
+  switch (mt) {
+    SK8_CASE(1)
+    SK8_CASE(2)
+    SK8_CASE(3)
+    default: gemm_skinny_w8_kernel<4, F32OUT><<<grid, 256, 0, st>>>(X, Q, E, Y, part, bias, resid, M, N, K, p.kps); break;
+  }
+#undef SK8_CASE
+  if (part) skinny_reduce_kernel<F32OUT><<<nblk((size_t)M * N, 256), 256, 0, st>>>(part, p.splits, Y, bias, resid, M, N);
+  return (int)hipGetLastError();
+}
+
 // ---- decode attention ---------------------------------------------------------------------------------------------------
 SLAM_DEVICE float rescale(float m, float mn) { return m == -INFINITY ? 0.f : fast_exp2(m - mn); }
 
@@ -1666,6 +1767,14 @@ int gemm_skinny(const bf16_t* X, const bf16_t* W, bf16_t* Y, float* Yf, const bf
   if (((uintptr_t)X | (uintptr_t)W) & 15) return -1;
   if (Yf) return launch_skinny<true>(X, W, Yf, bias, resid, M, N, K, ws, ws_bytes, st);
   return launch_skinny<false>(X, W, Y, bias, resid, M, N, K, ws, ws_bytes, st);
+}
+
+int gemm_skinny_w8(const bf16_t* X, const uint8_t* Q, const int8_t* E, bf16_t* Y, float* Yf, const bf16_t* bias,
+                   const bf16_t* resid, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st) {
+  if (!E || M <= 0 || N <= 0 || K <= 0 || (K % W8_K_GRAIN) || (!Y == !Yf)) return -1;
+  if (((uintptr_t)X | (uintptr_t)Q) & 15) return -1;
+  if (Yf) return launch_skinny_w8<true>(X, Q, E, Yf, bias, resid, M, N, K, ws, ws_bytes, st);
+  return launch_skinny_w8<false>(X, Q, E, Y, bias, resid, M, N, K, ws, ws_bytes, st);
 }
 
 size_t attn_decode_part_bytes(int B, int nH, int head_dim, int ns) {

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -265,6 +266,15 @@ struct SlamEngine {
   int kv_T = 0;          // the last prefill's T + the T of every slam_extend that no decode step preceded: kv_hi != kv_T once
                          // a decode step was taken (slam_kv_repeat)
   bool kv_ready = false; // a prefill filled the bound cache
+
+  // FP8 copy of the decode projections (slam_bind_decode_w8, caller-owned): codes + exponents of wqkv, wo, wgu, wd of every
+  // layer, then of the head matrix when w8_head. w8_valid: the codes describe the bound parameters (slam_quantize_decode_w8
+  // set it; every entry point that writes or rebinds parameters clears it, and decode_proj then reads the bf16 parameters)
+  struct W8Mat { int N, K; uint8_t* q; int8_t* e; };
+  char* w8 = nullptr;
+  bool w8_head = false, w8_valid = false;
+  int64_t w8_launches = 0;
+  std::unordered_map<int64_t, W8Mat> w8_mats;  // by the matrix's offset in the parameter buffer
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -918,10 +928,17 @@ int slam_bind_params(SlamEngine* h, void* params_bf16, float* grads_f32) {
   if (!h || !params_bf16) return SLAM_EINVAL;
   h->params = (bf16_t*)params_bf16;
   h->grads = grads_f32;
+  h->w8_valid = false;
   return SLAM_OK;
 }
+static int refresh_transposed_images(SlamEngine* h, slam_stream_t stream);
+// the caller wrote the parameters: FP8 decode codes made from the earlier values are stale
 int slam_refresh_transposed(SlamEngine* h, slam_stream_t stream) {
   if (!h) return SLAM_EINVAL;
+  h->w8_valid = false;
+  return refresh_transposed_images(h, stream);
+}
+static int refresh_transposed_images(SlamEngine* h, slam_stream_t stream) {
   if (!h->params_t) return SLAM_OK;
   if (!h->params) return h->fail(SLAM_ESTATE, "bind params first");
   hipStream_t st = (hipStream_t)stream;
@@ -1174,9 +1191,44 @@ namespace {
 // buffer), the tiled GEMM beyond; fp32 outputs always take the streaming kernel (in 64-row chunks)
 int decode_proj(SlamEngine* h, const bf16_t* X, const bf16_t* W, bf16_t* Y, float* Yf, const bf16_t* bias, const bf16_t* resid,
                 int M, int N, int K, hipStream_t st) {
-  if (Yf || M <= SKINNY_MAX_M)
-    return gemm_skinny(X, W, Y, Yf, bias, resid, M, N, K, (float*)h->dact, (size_t)h->max_tokens * h->d.intermediate * sizeof(bf16_t), st);
+  if (Yf || M <= SKINNY_MAX_M) {
+    float* ws = (float*)h->dact;
+    const size_t ws_bytes = (size_t)h->max_tokens * h->d.intermediate * sizeof(bf16_t);
+    // valid FP8 codes of this matrix: the same stream at half the bytes, the same bits (the parameters hold Wdq)
+    if (h->w8_valid) {
+      const auto it = h->w8_mats.find(W - h->params);
+      if (it != h->w8_mats.end() && it->second.N == N && it->second.K == K) {
+        ++h->w8_launches;
+        return gemm_skinny_w8(X, it->second.q, it->second.e, Y, Yf, bias, resid, M, N, K, ws, ws_bytes, st);
+      }
+    }
+    return gemm_skinny(X, W, Y, Yf, bias, resid, M, N, K, ws, ws_bytes, st);
+  }
   return gemm_nt(X, W, Y, bias, resid, M, N, K, st);
+}
+// the matrices of the FP8 decode copy in buffer order: offset in the parameter buffer, N, K
+struct W8Shape { int64_t off; int N, K; };
+static std::vector<W8Shape> w8_matrix_list(const SlamEngine* h, bool include_head) {
+  const SlamModelDesc& d = h->d;
+  const int HD = d.n_heads * d.head_dim;
+  std::vector<W8Shape> v;
+  for (int l = 0; l < d.n_layers; ++l) {
+    const LayerOff& o = h->lo[l];
+    v.push_back({o.wqkv, h->QKV, d.hidden});
+    v.push_back({o.wo, d.hidden, HD});
+    v.push_back({o.wgu, 2 * d.intermediate, d.hidden});
+    v.push_back({o.wd, d.hidden, d.intermediate});
+  }
+  if (include_head) v.push_back({h->off_head, d.vocab, d.hidden});
+  return v;
+}
+// why the FP8 decode copy cannot exist for this engine (nullptr: it can)
+static const char* w8_refusal(const SlamEngine* h) {
+  if (h->arch == 1) return "FP8 decode weights: the OPT family has no decode path";
+  const SlamModelDesc& d = h->d;
+  if (d.hidden % W8_K_GRAIN || d.intermediate % W8_K_GRAIN || (d.n_heads * d.head_dim) % W8_K_GRAIN)
+    return "FP8 decode weights need hidden, intermediate and n_heads * head_dim to be multiples of 64";
+  return nullptr;
 }
 // The second half of a cached layer over M rows (la[l].o -> hs[l + 1]): out-projection + residual, norm, gate|up, SwiGLU, down +
 // residual. static: a function of an unnamed namespace inside extern "C" keeps its C name and appears in the dynamic symbol table
@@ -1199,6 +1251,55 @@ static int last_token_head(SlamEngine* h, const bf16_t* x, int B, float* logits,
   return SLAM_OK;
 }
 }  // namespace
+
+size_t slam_decode_w8_bytes(SlamEngine* h, int32_t include_head) {
+  if (!h || w8_refusal(h)) return 0;
+  size_t bytes = 0;
+  for (const W8Shape& m : w8_matrix_list(h, include_head != 0)) bytes += w8_bytes(m.N, m.K);
+  return bytes;
+}
+
+int slam_bind_decode_w8(SlamEngine* h, void* buf, size_t bytes, int32_t include_head) {
+  if (!h) return SLAM_EINVAL;
+  h->w8 = nullptr;
+  h->w8_valid = false;
+  h->w8_head = false;
+  h->w8_launches = 0;
+  h->w8_mats.clear();
+  if (!buf) return SLAM_OK;
+  if (const char* why = w8_refusal(h)) return h->fail(SLAM_EINVAL, why);
+  if (((uintptr_t)buf) & 255) return h->fail(SLAM_EINVAL, "FP8 decode weights must be 256-byte aligned");
+  if (bytes < slam_decode_w8_bytes(h, include_head)) return h->fail(SLAM_ENOMEM, "FP8 decode weight buffer too small");
+  char* p = (char*)buf;
+  for (const W8Shape& m : w8_matrix_list(h, include_head != 0)) {
+    h->w8_mats[m.off] = SlamEngine::W8Mat{m.N, m.K, (uint8_t*)p, (int8_t*)(p + w8_exps_offset(m.N, m.K))};
+    p += w8_bytes(m.N, m.K);
+  }
+  h->w8 = (char*)buf;
+  h->w8_head = include_head != 0;
+  return SLAM_OK;
+}
+
+int slam_quantize_decode_w8(SlamEngine* h, slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  if (!h->params) return h->fail(SLAM_ESTATE, "bind params first");
+  if (!h->w8) return h->fail(SLAM_ESTATE, "bind FP8 decode weights first (slam_bind_decode_w8)");
+  hipStream_t st = (hipStream_t)stream;
+  CK(join_optimizer(h, st));
+  CK(join_params(h, st));
+  h->w8_valid = false;
+  for (const auto& kv : h->w8_mats) {  // rows are independent and the matrices disjoint: the order does not matter
+    const SlamEngine::W8Mat& m = kv.second;
+    const int r = quantize_rows_fp8(h->params + kv.first, m.q, m.e, m.N, m.K, st);
+    if (r) return r == -1 ? h->fail(SLAM_EINVAL, "FP8 decode weights: a parameter matrix is not 16-byte aligned") : r;
+  }
+  CK(refresh_transposed_images(h, stream));
+  h->w8_valid = true;
+  return SLAM_OK;
+}
+
+int slam_decode_w8_state(SlamEngine* h) { return !h || !h->w8 ? 0 : h->w8_valid ? 2 : 1; }
+int64_t slam_decode_w8_launches(SlamEngine* h) { return h ? h->w8_launches : 0; }
 
 int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
                  slam_stream_t stream) {
@@ -1850,6 +1951,7 @@ static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, c
   hipStream_t st = (hipStream_t)stream;
   CK(join_optimizer(h, st));
   CK(join_params(h, st));
+  h->w8_valid = false;
   const bool fused = h->params_t != nullptr && h->fuse_adamw_t;
   AdamArgs a = adam_args(h, mode, norm_out, lr, b1, b2, eps, wd, step, zero_grad);
   a.master = master; a.m = m; a.v = v;
@@ -1932,6 +2034,7 @@ static int adamw_range_impl(SlamEngine* h, int mode, int64_t offset, int64_t cou
   if (!h->grads || !h->params) return h->fail(SLAM_ESTATE, "bind params first");
   hipStream_t st = (hipStream_t)stream;
   CK(join_optimizer(h, st));
+  h->w8_valid = false;
   AdamArgs a = adam_args(h, mode, norm_out, lr, b1, b2, eps, wd, step, zero_grad).at(offset);
   a.master = master; a.m = m; a.v = v;
   if (count) CK(adamw_flat(a, (size_t)count, st));
@@ -2214,6 +2317,7 @@ int slam_allgather_params_async(SlamEngine* h, int64_t offset, int64_t count, sl
   CK((int)hipEventRecord(ev, h->comm_stream));
   h->pwaits.push_back({offset, offset + count, ev});
   h->params_t_dirty = h->params_t != nullptr;
+  h->w8_valid = false;
   return SLAM_OK;
 }
 
@@ -2310,6 +2414,23 @@ int slam_op_gemm_skinny(const void* X, const void* W, void* Y, int y_f32, const 
                         float* ws, size_t ws_bytes, slam_stream_t s) {
   return gemm_skinny((const bf16_t*)X, (const bf16_t*)W, y_f32 ? nullptr : (bf16_t*)Y, y_f32 ? (float*)Y : nullptr,
                      (const bf16_t*)bias, (const bf16_t*)resid, M, N, K, ws, ws_bytes, (hipStream_t)s);
+}
+size_t slam_op_w8_bytes(int N, int K) { return (N <= 0 || K <= 0 || K % W8_K_GRAIN) ? 0 : w8_bytes(N, K); }
+size_t slam_op_w8_exps_offset(int N, int K) { return (N <= 0 || K <= 0 || K % W8_K_GRAIN) ? 0 : w8_exps_offset(N, K); }
+int slam_op_quantize_rows_fp8(void* W, void* codes, void* exps, int N, int K, slam_stream_t s) {
+  const int r = quantize_rows_fp8((bf16_t*)W, (uint8_t*)codes, (int8_t*)exps, N, K, (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
+}
+int slam_op_dequantize_rows_fp8(const void* codes, const void* exps, void* W, int N, int K, slam_stream_t s) {
+  const int r = dequantize_rows_fp8((const uint8_t*)codes, (const int8_t*)exps, (bf16_t*)W, N, K, (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
+}
+int slam_op_gemm_skinny_w8(const void* X, const void* codes, const void* exps, void* Y, int y_f32, const void* bias, const void* resid,
+                           int M, int N, int K, float* ws, size_t ws_bytes, slam_stream_t s) {
+  const int r = gemm_skinny_w8((const bf16_t*)X, (const uint8_t*)codes, (const int8_t*)exps, y_f32 ? nullptr : (bf16_t*)Y,
+                               y_f32 ? (float*)Y : nullptr, (const bf16_t*)bias, (const bf16_t*)resid, M, N, K, ws, ws_bytes,
+                               (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
 }
 size_t slam_op_score_rows_workspace(int M, int V) { return score_rows_workspace_bytes(M, V); }
 int slam_op_score_rows(const void* X, const void* W, const int64_t* targets, const uint8_t* colmask, float* lp, int64_t* argmax,

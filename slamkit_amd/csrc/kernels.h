@@ -268,6 +268,23 @@ constexpr int SKINNY_MAX_M = 64;  // the engine's decode projections use gemm_sk
 size_t gemm_skinny_workspace_bytes(int M, int N, int K);
 int gemm_skinny(const bf16_t* X, const bf16_t* W, bf16_t* Y, float* Yf, const bf16_t* bias, const bf16_t* resid, int M, int N,
                 int K, float* ws, size_t ws_bytes, hipStream_t st);
+// FP8 weight stream (quant.hip, decode.hip): W[N][K] as e4m3fn codes Q[N][K] + per-row int8 exponents E[N], Wdq = value(Q) 2^E.
+// K must be a multiple of W8_K_GRAIN: the codes of a row keep their 64-deep K block but not their order inside it - byte
+// w8_code_pos(k) of the row holds the code of column k, so that the 16 bytes at 64 b + 16 q are, for MFMA lane quarter q, the 8
+// codes of columns 64 b + 8 q .. + 7 followed by those of columns 64 b + 32 + 8 q .. + 7 (two consecutive 32-deep steps).
+constexpr int W8_K_GRAIN = 64;
+constexpr int W8_EXP_MIN = -100, W8_EXP_MAX = 120;
+__host__ __device__ inline int w8_code_pos(int k) { return (k & ~63) | (((k >> 3) & 3) << 4) | (((k >> 5) & 1) << 3) | (k & 7); }
+inline size_t w8_align(size_t b) { return (b + 255) & ~(size_t)255; }
+inline size_t w8_exps_offset(int N, int K) { return w8_align((size_t)N * K); }        // codes first, exponents 256-byte aligned
+inline size_t w8_bytes(int N, int K) { return w8_exps_offset(N, K) + w8_align((size_t)N); }
+// quantize: Q, E from W, and W rewritten in place with Wdq. dequantize: W[N][K] row-major from Q, E. -1: bad argument.
+int quantize_rows_fp8(bf16_t* W, uint8_t* Q, int8_t* E, int N, int K, hipStream_t st);
+int dequantize_rows_fp8(const uint8_t* Q, const int8_t* E, bf16_t* W, int N, int K, hipStream_t st);
+// gemm_skinny with the W operand read as codes: the MFMA sees exactly the bf16 values of Wdq in the lanes and the K order of
+// gemm_skinny(X, Wdq, ..), under the same split plan and reduce launch - the same bits.
+int gemm_skinny_w8(const bf16_t* X, const uint8_t* Q, const int8_t* E, bf16_t* Y, float* Yf, const bf16_t* bias,
+                   const bf16_t* resid, int M, int N, int K, float* ws, size_t ws_bytes, hipStream_t st);
 // one decode step of attention for one layer: qkv = fp32 [B][(nH + 2 nKV) hd] projection WITHOUT bias; bias + RoPE (tables
 // cs / sn and the pre-scaled csq / snq of rope_table at the rows' positions lens[b]) are applied in fp32 and rounded once;
 // the new K / V go to row lens[b] of kc / vc ([B][nKV][cap][hd] bf16), and o[b] (bf16 [B][nH hd]) attends over rows

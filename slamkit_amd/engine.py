@@ -174,6 +174,16 @@ def load_library(path: Optional[str] = None):
         "slam_op_gemm_tn_image": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
         "slam_op_gemm_skinny_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
         "slam_op_gemm_skinny": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
+        "slam_op_w8_bytes": (sz, [C.c_int, C.c_int]),
+        "slam_op_w8_exps_offset": (sz, [C.c_int, C.c_int]),
+        "slam_op_quantize_rows_fp8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+        "slam_op_dequantize_rows_fp8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
+        "slam_op_gemm_skinny_w8": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
+        "slam_decode_w8_bytes": (sz, [vp, i32]),
+        "slam_bind_decode_w8": (C.c_int, [vp, vp, sz, i32]),
+        "slam_quantize_decode_w8": (C.c_int, [vp, vp]),
+        "slam_decode_w8_state": (C.c_int, [vp]),
+        "slam_decode_w8_launches": (i64, [vp]),
         "slam_op_score_rows_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_score_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
         "slam_op_attn_decode_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -488,6 +498,26 @@ class Engine:
 
     def refresh_transposed(self, stream=None):
         self._ck(self.lib.slam_refresh_transposed(self.h, stream if stream is not None else current_stream_ptr()))
+
+    # -- FP8 copy of the decode projections (slam_bind_decode_w8 in the header) ------------------------------------------------
+    def decode_w8_bytes(self, include_head: bool = False) -> int:
+        """0: the engine refuses the path (OPT, or a K that is no multiple of 64)."""
+        return int(self.lib.slam_decode_w8_bytes(self.h, int(bool(include_head))))
+
+    def bind_decode_w8(self, buf, include_head: bool = False):
+        """buf: uint8 device tensor of decode_w8_bytes(include_head); None unbinds."""
+        self._keep["w8"] = buf
+        n = 0 if buf is None else buf.numel() * buf.element_size()
+        self._ck(self.lib.slam_bind_decode_w8(self.h, _ptr(buf), n, int(bool(include_head))))
+
+    def quantize_decode_w8(self, stream=None):
+        self._ck(self.lib.slam_quantize_decode_w8(self.h, stream if stream is not None else current_stream_ptr()))
+
+    def decode_w8_state(self) -> int:
+        return int(self.lib.slam_decode_w8_state(self.h))
+
+    def decode_w8_launches(self) -> int:
+        return int(self.lib.slam_decode_w8_launches(self.h))
 
     def workspace_bytes(self, max_tokens: int) -> int:
         return int(self.lib.slam_workspace_bytes(self.h, max_tokens))

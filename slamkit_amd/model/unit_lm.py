@@ -686,6 +686,76 @@ class UnitLM(TokenLM):
         self.engine.join()
         self.flat_master = None
 
+    # ---- decoding from FP8 weights (slam_bind_decode_w8 in the header) ------------------------------------------------------
+    def _w8_matrices(self, include_head: bool):
+        """(kind, offset, rows, cols) of the matrices the FP8 decode copy covers, in the engine's buffer order."""
+        t = self.engine.tensors
+        out = []
+        for l in range(self.engine.desc.n_layers):
+            for kind in ("wqkv", "wo", "wgu", "wd"):
+                s = t[f"layers.{l}.{kind}"]
+                out.append((kind, s.offset, s.rows, s.cols))
+        if include_head:
+            s = t["lm_head"] if "lm_head" in t else t["embed"]  # a tied head is the embedding table; its pad rows stay
+            out.append(("head", s.offset, self.engine.desc.vocab, s.cols))
+        return out
+
+    @torch.no_grad()
+    def quantize_decode_weights(self, dtype: str = "fp8_e4m3", include_head: bool = False) -> dict:
+        """Replace the decode projections (q|k|v, out, gate|up, down of every layer; the LM head with `include_head`) by their
+        nearest values on a per-row power-of-two-scaled e4m3 grid and keep the codes for the decode step: generate, scoring and
+        speculative verification then stream one byte per weight instead of two, and every other path computes the same model
+        from the bf16 parameters, which now hold those values (so does the fp32 master, if there is one, and a checkpoint saved
+        afterwards is an ordinary bf16 checkpoint of the quantised model). With a tied head and `include_head` the embedding
+        table is quantised, being the same tensor. Any later write of the parameters (load_state_dict, an optimizer step) drops
+        the codes silently; decode goes on in bf16. Returns the relative RMS error per matrix kind and the byte counts."""
+        if self.config.is_opt:
+            raise ValueError("quantize_decode_weights: the OPT family has no KV-cached decode path")
+        if dtype != "fp8_e4m3":
+            raise ValueError(f"quantize_decode_weights: unknown dtype {dtype!r} (only 'fp8_e4m3')")
+        eng = self.engine
+        nbytes = eng.decode_w8_bytes(include_head)
+        if nbytes == 0:
+            raise ValueError("quantize_decode_weights: hidden_size, intermediate_size and num_attention_heads * head_dim must be "
+                             "multiples of 64 for the FP8 decode path")
+        eng.join()
+        mats = self._w8_matrices(include_head)
+        P = self.flat_params
+        finite = torch.ones((), dtype=torch.bool, device=self.device)
+        for _, off, r, c in mats:
+            finite &= torch.isfinite(P[off:off + r * c]).all()
+        if not bool(finite):
+            raise ValueError("quantize_decode_weights: non-finite weights")
+        before = P.clone()
+        with torch.cuda.device(self.device):
+            buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            a = (-buf.data_ptr()) % 256
+            self._w8_buf = buf[a:a + nbytes]
+            eng.bind_decode_w8(self._w8_buf, include_head)
+            eng.quantize_decode_w8()
+        err, ref, bf16_bytes, fp8_bytes = {}, {}, 0, 0
+        for kind, off, r, c in mats:
+            w, q = before[off:off + r * c].float(), P[off:off + r * c].float()
+            err[kind] = err.get(kind, 0.0) + (q - w).double().square().sum()
+            ref[kind] = ref.get(kind, 0.0) + w.double().square().sum()
+            if self.flat_master is not None:
+                self.flat_master[off:off + r * c].copy_(q)
+            bf16_bytes += 2 * r * c
+            fp8_bytes += r * c + r
+        del before
+        return {"dtype": dtype, "include_head": bool(include_head), "bf16_bytes": bf16_bytes, "fp8_bytes": fp8_bytes,
+                "rel_rms": {k: float((err[k] / ref[k]).sqrt()) if float(ref[k]) > 0 else 0.0 for k in err}}
+
+    def drop_decode_weights(self):
+        """Unbind the FP8 codes: decode streams the bf16 parameters again, which keep the quantised values."""
+        self.engine.bind_decode_w8(None)
+        self._w8_buf = None
+
+    @property
+    def decode_weights(self) -> Optional[str]:
+        """"fp8_e4m3" while the decode step reads valid FP8 codes, else None."""
+        return "fp8_e4m3" if self.engine.decode_w8_state() == 2 else None
+
     @property
     def _weights(self) -> torch.Tensor:
         """The authoritative flat weight buffer: fp32 master when there is one, else the bf16 parameters."""

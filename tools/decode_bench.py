@@ -4,6 +4,7 @@ B = 8, prompt 256, 150 new tokens (config/metric/generate.yaml), on a randomly i
 Usage: python tools/decode_bench.py [--models slam,cfg3] [--steps 150] [--reps 2] [--no-reforward]
        python tools/decode_bench.py --num-return-sequences 8 [--models slam,cfg3] [--reps 3]
        python tools/decode_bench.py --prefill-chunk 512 [--models slam,cfg3]
+       python tools/decode_bench.py --decode-weights fp8 --include-head --models slam,cfg3,7b
        python tools/decode_bench.py --trace-summary DIR   (per-launch table of the decode kernels from a
                                                             `rocprofv3 --kernel-trace --stats -d DIR -- python tools/decode_bench.py`)
 Prints one JSON line per measurement:
@@ -41,6 +42,13 @@ and top_k 25 and 256: `plain_us`, `warped_all_us` (min_p 0.05, typical_p 0.95, e
 (typical_p 0.9 alone), device events around 200 back-to-back calls, five alternating rounds, median and [min, max]. With
 --sampler engine --warp: end-to-end sampled generate (temperature 0.8, top_k 25) without (`way` = "plain") and with those four
 warpers (`way` = "warped"), alternated rep by rep.
+--decode-weights fp8 [--include-head] [--models slam,cfg3,7b] [--batches 1,8,64] [--blocks 3]: the decode step from bf16
+weights (codes dropped) and from FP8 codes (UnitLM.quantize_decode_weights), in alternating blocks within this process, prompt
+256, device events, 10 warm-up steps per block: one `decode_w8` line per (model, B) with `bf16_step_ms` / `fp8_step_ms` (median
+over the blocks, `_all` the blocks), `bf16_over_fp8` (median of the per-block ratios, `_minmax`), the bytes a step streams
+(`bf16_MB`, `fp8_MB`) and their 6.3 TB/s floors, and `w8_launches_per_step`. --decode-weights bf16 runs the bf16 blocks alone
+through calls every earlier revision has: the same file, copied into a parent checkout, measures it for an A-B-A comparison.
+`7b` is the Qwen2.5-7B body with the unit vocabulary.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -60,6 +68,7 @@ HBM_BPS = 6.3e12
 MODELS = {
     "slam": ("Qwen/Qwen2.5-0.5B", 502),
     "cfg3": ("Qwen/Qwen2.5-1.5B", 152576),
+    "7b": ("Qwen/Qwen2.5-7B", 502),  # the SIMS-7B body with the unit vocabulary, as in tools/spec_bench.py
 }
 
 
@@ -79,7 +88,45 @@ def build(name, max_tokens):
     return UnitLM(UnitLMConfig(base_model_name=base, vocab_size=vocab, max_tokens=max_tokens), allocate_grads=False, seed=0)
 
 
-def step_bench(m, B, P, steps, tag):
+def w8_bench(name, batches, P, steps, blocks, fp8, include_head):
+    """The decode step from bf16 weights (codes dropped) and from FP8 codes (UnitLM.quantize_decode_weights), in alternating
+    blocks within this process. With fp8 false only the bf16 blocks run, through calls every earlier revision has - the same
+    file measures a parent checkout for the A-B-A comparison."""
+    import torch
+    m = build(name, 4096)
+    info = None
+    if fp8:  # quantise once up front: every block then runs the same model
+        info = m.quantize_decode_weights(include_head=include_head)
+        m.drop_decode_weights()
+    for B in batches:
+        t = {"bf16": [], "fp8": []}
+        last = {}
+        for _ in range(blocks):
+            last["bf16"] = step_bench(m, B, P, steps, name, quiet=True)
+            t["bf16"].append(last["bf16"]["step_ms"])
+            if fp8:
+                m.quantize_decode_weights(include_head=include_head)
+                n0 = m.engine.decode_w8_launches()
+                last["fp8"] = step_bench(m, B, P, steps, name, quiet=True, saved=info["bf16_bytes"] - info["fp8_bytes"])
+                last["fp8"]["w8_launches_per_step"] = (m.engine.decode_w8_launches() - n0) / (steps - 1)
+                t["fp8"].append(last["fp8"]["step_ms"])
+                m.drop_decode_weights()
+        r = dict(bench="decode_w8", model=name, B=B, prompt=P, steps_timed=last["bf16"]["steps_timed"], blocks=blocks,
+                 bf16_step_ms=round(statistics.median(t["bf16"]), 4), bf16_step_ms_all=t["bf16"],
+                 bf16_MB=last["bf16"]["weight_MB"], bf16_floor_ms=last["bf16"]["floor_ms"])
+        if fp8:
+            ratios = [b / f for b, f in zip(t["bf16"], t["fp8"])]
+            r.update(fp8_step_ms=round(statistics.median(t["fp8"]), 4), fp8_step_ms_all=t["fp8"], fp8_MB=last["fp8"]["weight_MB"],
+                     fp8_floor_ms=last["fp8"]["floor_ms"], include_head=bool(include_head),
+                     w8_launches_per_step=last["fp8"]["w8_launches_per_step"],
+                     bf16_over_fp8=round(statistics.median(ratios), 3),
+                     bf16_over_fp8_minmax=[round(min(ratios), 3), round(max(ratios), 3)])
+        print(json.dumps(r), flush=True)
+    del m
+    torch.cuda.empty_cache()
+
+
+def step_bench(m, B, P, steps, tag, quiet=False, saved=0):
     import torch
     dev = m.device
     V = m.config.vocab_size
@@ -101,12 +148,13 @@ def step_bench(m, B, P, steps, tag):
         t = ev_ms(lambda: m.engine.decode_step(tok, lens, B, logits))
         if k >= 10:
             st.append(t)
-    wbytes = 2 * m.engine.n_params
+    wbytes = 2 * m.engine.n_params - saved  # saved: what the FP8 codes take off the stream
     step = statistics.median(st)
     floor = wbytes / HBM_BPS * 1e3
     r = dict(bench="decode", model=tag, B=B, prompt=P, prefill_ms=round(statistics.median(pre), 3), step_ms=round(step, 4),
              floor_ms=round(floor, 4), floor_share=round(floor / step, 3), weight_MB=round(wbytes / 1e6, 1), steps_timed=len(st))
-    print(json.dumps(r), flush=True)
+    if not quiet:
+        print(json.dumps(r), flush=True)
     return r
 
 
@@ -530,12 +578,22 @@ def main():
                     help="n: generate of 8 prompts x n from one prefill vs the repeated batch, kv_repeat and token_logprobs alone")
     ap.add_argument("--prefill-chunk", type=int, default=0,
                     help="C: prefill of 8 x 2048 prompts in one slam_prefill vs slam_prefill + slam_extend in chunks of C")
+    ap.add_argument("--decode-weights", default=None, choices=["bf16", "fp8"],
+                    help="decode step per model and batch: fp8 alternates blocks from bf16 weights and from FP8 codes; bf16 runs "
+                         "the bf16 blocks alone")
+    ap.add_argument("--batches", default="1,8,64", help="with --decode-weights")
+    ap.add_argument("--blocks", type=int, default=3, help="with --decode-weights: alternations per (model, batch)")
+    ap.add_argument("--include-head", action="store_true", help="with --decode-weights fp8: FP8 codes for the LM head too")
     a = ap.parse_args()
     if a.trace_summary:
         trace_summary(a.trace_summary)
         return
     import torch
     assert torch.cuda.is_available()
+    if a.decode_weights:
+        for name in a.models.split(","):
+            w8_bench(name, [int(b) for b in a.batches.split(",")], 256, a.steps, a.blocks, a.decode_weights == "fp8", a.include_head)
+        return
     if a.sample_op:
         if a.warp:
             warp_op_bench()
