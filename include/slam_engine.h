@@ -681,7 +681,9 @@ int slam_grad_sumsq_chunks(SlamEngine* h, int64_t offset, int64_t count, float* 
 int slam_grad_norm_from_chunks(SlamEngine* h, const float* chunk_sums, float max_norm, float* norm_out, slam_stream_t stream);
 /* slam_adamw_step on elements [offset, offset + count) only (multiples of 4; 8 for the bf16-state form): master / exp_avg /
  * exp_avg_sq point at THE RANGE'S first element (compact per-shard storage or base + offset of full-size buffers). Does not
- * refresh the transposed weight images: the next slam_backward does, after every pending parameter write has landed. */
+ * refresh the transposed weight images: the next slam_backward does, after every pending parameter write has landed.
+ * zero_grad != 0 (here and in slam_adamw_step*) clears the fp32 gradient buffer over exactly the updated elements, whichever buffer
+ * the gradients were read from: after a "grad_final_next" = 2 backward the bf16 image keeps its values and the fp32 buffer is cleared. */
 int slam_adamw_range(SlamEngine* h, int64_t offset, int64_t count, float* master_f32, float* exp_avg, float* exp_avg_sq,
                      const float* norm_out, double lr, double beta1, double beta2, double eps, double weight_decay,
                      int32_t step, int32_t zero_grad, slam_stream_t stream);

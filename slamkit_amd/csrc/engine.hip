@@ -2037,6 +2037,8 @@ static int adamw_range_impl(SlamEngine* h, int mode, int64_t offset, int64_t cou
   h->w8_valid = false;
   AdamArgs a = adam_args(h, mode, norm_out, lr, b1, b2, eps, wd, step, zero_grad).at(offset);
   a.master = master; a.m = m; a.v = v;
+  // as in adamw_any: the kernels cannot clear the fp32 accumulation buffer while they read the bf16 image - here the range only
+  if (a.g_bf16 && zero_grad && count) CK((int)hipMemsetAsync(h->grads + offset, 0, (size_t)count * sizeof(float), st));
   if (count) CK(adamw_flat(a, (size_t)count, st));
   h->params_t_dirty = h->params_t != nullptr;
   return SLAM_OK;
