@@ -568,6 +568,45 @@ int slam_token_logprobs(const float* logits, int32_t B, int32_t vocab, const int
                         uint8_t* finished, float* out, int64_t out_stride, int32_t column, void* ws, size_t ws_bytes,
                         slam_stream_t stream);
 
+/* ---- classifier-free guidance (HF's guidance_scale), both branches in one decode batch ---------------------------------------
+ * slam_cfg_scores needs no engine and changes no engine state: slam_prefill, slam_kv_repeat and slam_decode_step take any row
+ * count, and the guided layout is a convention of the caller. logits is fp32 [2 B][vocab] (row stride vocab): row b holds the
+ * conditional scores x of sequence b, row B + b its unconditional scores y. scores is fp32 [B][vocab] and must not overlap
+ * logits (slam_token_logprobs keeps reading the raw rows afterwards). With g = guidance_scale:
+ *   reading      x_i and y_i are read as the sampler and slam_token_logprobs read a score: NaN counts as -inf, +inf as FLT_MAX.
+ *   statistics   (m_x, S_x) of row b and (m_y, S_y) of row B + b are slam_token_logprobs' m and S (above): chunks of 2048 scores,
+ *                256 threads striding, the xor butterfly, ((w0 + w1) + w2) + w3, chunks combined in chunk order by
+ *                S = fmaf(s_c, expf(m_c - m), S). The two calls run the same device code.
+ *   normalisers  L_x = m_x + logf(S_x), L_y = m_y + logf(S_y), in fp32.
+ *   combination  a_i = x_i - L_x, u_i = y_i - L_y, d_i = a_i - u_i, scores[b][i] = (g * d_i) + u_i: transformers'
+ *                guidance_scale * (scores - uncond) + uncond on the two log-softmaxes. Each of the three operations is rounded
+ *                to fp32 on its own; none is contracted into a fused multiply-add.
+ *   non-finite   (deviations: transformers produces NaN there) a_i = -inf gives -inf; u_i = -inf with a_i finite gives a_i; a
+ *                row whose conditional scores are all -inf gives -inf throughout; a row whose unconditional scores are all
+ *                -inf gives a_i throughout.
+ * A row's result depends on its two input rows and g alone - not on B, the row index, the rows' alignment or the launch
+ * shape - and is the same bits on every run: no floating-point atomics. Rows of one chunk take one launch; longer rows take
+ * two: the per-chunk (m_c, s_c) of all 2 B rows into ws (slam_token_logprobs' first launch), then the finish. Grid
+ * (chunks, B), as slam_constrain_scores. A block stages its chunk of both rows in LDS with 16-byte loads from each row's first
+ * 16-byte boundary and stores with 16-byte accesses from the first 16-byte boundary of the scores row (every access is 16
+ * bytes wide where the rows are equally aligned); 4-byte accesses at the ragged ends, so odd vocabularies are fine.
+ * ws: slam_cfg_workspace_bytes(B, vocab) bytes, 8-byte aligned (host arithmetic: positive for valid arguments, 0 else); it is
+ * required for rows of one chunk too.
+ * SLAM_EINVAL before any launch or device dereference: logits, scores or ws NULL; B <= 0 or 2 B > 65535; vocab <= 0; a
+ * non-finite guidance_scale; logits or scores not 4-byte aligned; ws not 8-byte aligned; ws_bytes too small; the ranges
+ * logits[0 .. 2 B vocab) and scores[0 .. B vocab) overlapping.
+ *
+ * slam_cfg_mirror_tokens: next[B + b] = next[b] for b in 0 .. B-1 (int64, device memory, 8-byte aligned): the sampler writes
+ * next[0 .. B) for the conditional rows and slam_decode_step reads next[0 .. 2 B), so a guided step under the engine sampler
+ * still has no torch op between two engine calls. SLAM_EINVAL: next NULL or misaligned; B outside 1 .. 32767.
+ * The guided step, in transformers' processor order (guidance first): slam_cfg_scores(logits -> scores),
+ * slam_constrain_scores(in place on scores), slam_sample_tokens over the B rows of scores, slam_token_logprobs on the raw
+ * conditional rows logits[0 .. B), slam_cfg_mirror_tokens, slam_decode_step over 2 B rows. */
+size_t slam_cfg_workspace_bytes(int32_t B, int32_t vocab);
+int slam_cfg_scores(const float* logits, int32_t B, int32_t vocab, float guidance_scale, float* scores, void* ws,
+                    size_t ws_bytes, slam_stream_t stream);
+int slam_cfg_mirror_tokens(int64_t* next, int32_t B, slam_stream_t stream);
+
 /* loss.backward(): accumulates d(loss*grad_scale)/dparam into the bound fp32 gradient buffer.
  * bucket_layers = decoder layers per gradient bucket for the callback (<=0: one bucket). */
 int slam_backward(SlamEngine* h, float grad_scale, int32_t bucket_layers, slam_bucket_cb cb, void* user,

@@ -34,6 +34,10 @@
 //    chunk thread t takes scores t, t + 256, .. in that order, the 64 lanes of a wave are summed by the xor butterfly 32, 16,
 //    .., 1, the four waves in wave order; chunks are combined in chunk order, one fused multiply-add each. Rows above one chunk
 //    take two launches.
+//  * cfg_scores (slam_cfg_scores): classifier-free guidance. Logits rows b and B + b (conditional, unconditional) into scores
+//    row b = g (a - u) + u of their log-softmaxes, on token_logprobs' own chunk statistics (the same device functions; rows
+//    above one chunk reuse its first launch over the 2 B rows). Grid (chunks, B); three separately rounded operations.
+//    cfg_mirror_tokens copies the B chosen tokens behind themselves for the decode step over 2 B rows.
 //  * ngram_propose (slam_ngram_propose): prompt-lookup proposals. One block per row scans the row's history once: thread t
 //    takes the window ends t, t + 256, .., counts the tokens that match backwards from the end of the history, and a 64-bit
 //    key (count << 32 | ~end) picks the longest match, the earliest among equals. Integers only; the two statistics by a second
@@ -1430,6 +1434,16 @@ SLAM_DEVICE void chunk_max_sum(const float* vals, int n, float* red, float& m, f
   s = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// (m, S) of a row from stage 1's pairs p[0 .. nch), in chunk order. One thread calls it.
+SLAM_DEVICE void combine_chunks(const float2* p, int nch, float& m, float& s) {
+  m = -INFINITY;
+  s = 0.f;
+  for (int c = 0; c < nch; ++c) m = fmaxf(m, p[c].x);
+  if (m != -INFINITY)
+    for (int c = 0; c < nch; ++c)
+      if (p[c].x != -INFINITY) s = __fmaf_rn(p[c].y, expf(p[c].x - m), s);  // one rounding, as the header states
+}
+
 struct LogprobParams {
   int vocab, nch, column;
   long long out_stride;
@@ -1474,11 +1488,7 @@ __global__ __launch_bounds__(SP_THREADS) void logprob_finish_kernel(const float*
       __syncthreads();
       chunk_max_sum(vals, P.vocab, red, m, s);
     } else if (t == 0) {
-      const float2* p = ws + (size_t)b * P.nch;
-      for (int c = 0; c < P.nch; ++c) m = fmaxf(m, p[c].x);
-      if (m != -INFINITY)
-        for (int c = 0; c < P.nch; ++c)
-          if (p[c].x != -INFINITY) s = __fmaf_rn(p[c].y, expf(p[c].x - m), s);  // one rounding, as the header states
+      combine_chunks(ws + (size_t)b * P.nch, P.nch, m, s);
     }
   }
   if (t != 0) return;
@@ -1489,6 +1499,82 @@ __global__ __launch_bounds__(SP_THREADS) void logprob_finish_kernel(const float*
   }
   out[(long long)b * P.out_stride + P.column] = r;
   if (finished) finished[b] = done ? done[b] : (uint8_t)0;
+}
+
+// ---- classifier-free guidance (slam_cfg_scores) --------------------------------------------------------------------------------
+// One guided score from the cleaned pair (x, y) and the rows' log-normalisers. x_dead / y_dead: the row has no score above -inf.
+// Three operations, each rounded on its own: a fused multiply-add would round g d + u once and change the bits.
+SLAM_DEVICE float cfg_combine(float x, float y, float Lx, float Ly, float g, bool x_dead, bool y_dead) {
+#pragma clang fp contract(off)
+  if (x_dead) return -INFINITY;
+  const float a = x - Lx;
+  if (a == -INFINITY) return -INFINITY;
+  if (y_dead) return a;
+  const float u = y - Ly;
+  if (u == -INFINITY) return a;
+  const float d = a - u;
+  const float gd = g * d;
+  return gd + u;
+}
+
+struct CfgParams {
+  int vocab, nch, B;
+  float g;
+};
+
+// grid (chunks, B). Row b (x) and row B + b (y) of logits, chunk blockIdx.x, into scores row b. ROW: the rows are one chunk and
+// their statistics are formed here; else thread 0 (x) and thread 64 (y) combine the pairs logprob_chunk_kernel left in ws for
+// the 2 B rows. The chunk of both rows is staged in LDS by load_scores (16-byte loads from each row's own first 16-byte
+// boundary) and leaves by 16-byte stores from the first 16-byte boundary of the scores row, 4-byte ones at the ragged ends.
+template <bool ROW>
+__global__ __launch_bounds__(SP_THREADS) void cfg_scores_kernel(const float* __restrict__ logits, float* __restrict__ scores,
+                                                                CfgParams P, const float2* __restrict__ ws) {
+  __shared__ float vx[SP_CHUNK];
+  __shared__ float vy[SP_CHUNK];
+  __shared__ float red[SP_THREADS / 64];
+  __shared__ float st[4];
+  const int ch = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+  const int c0 = ch * SP_CHUNK;
+  const int n = min(SP_CHUNK, P.vocab - c0);
+  load_scores(logits + (size_t)b * P.vocab, c0, n, vx);
+  load_scores(logits + (size_t)(P.B + b) * P.vocab, c0, n, vy);
+  __syncthreads();
+  float mx, sx, my, sy;
+  if (ROW) {
+    chunk_max_sum(vx, n, red, mx, sx);
+    __syncthreads();  // red is reused
+    chunk_max_sum(vy, n, red, my, sy);
+  } else {
+    if (t == 0) combine_chunks(ws + (size_t)b * P.nch, P.nch, st[0], st[1]);
+    if (t == 64) combine_chunks(ws + (size_t)(P.B + b) * P.nch, P.nch, st[2], st[3]);
+    __syncthreads();
+    mx = st[0], sx = st[1], my = st[2], sy = st[3];
+  }
+  const bool x_dead = mx == -INFINITY, y_dead = my == -INFINITY;
+  const float Lx = mx + logf(sx), Ly = my + logf(sy);  // unused when the row is dead
+  const float g = P.g;
+  float* dst = scores + (size_t)b * P.vocab + c0;
+  int head = (int)((4u - (uint32_t)(((uintptr_t)dst >> 2) & 3u)) & 3u);
+  if (head > n) head = n;
+  const int nv = (n - head) >> 2;
+  if (t < head) dst[t] = cfg_combine(vx[t], vy[t], Lx, Ly, g, x_dead, y_dead);
+  float4* dv = reinterpret_cast<float4*>(dst + head);
+  for (int v = t; v < nv; v += SP_THREADS) {
+    const int i = head + 4 * v;
+    float4 f;
+    f.x = cfg_combine(vx[i + 0], vy[i + 0], Lx, Ly, g, x_dead, y_dead);
+    f.y = cfg_combine(vx[i + 1], vy[i + 1], Lx, Ly, g, x_dead, y_dead);
+    f.z = cfg_combine(vx[i + 2], vy[i + 2], Lx, Ly, g, x_dead, y_dead);
+    f.w = cfg_combine(vx[i + 3], vy[i + 3], Lx, Ly, g, x_dead, y_dead);
+    dv[v] = f;
+  }
+  for (int i = head + 4 * nv + t; i < n; i += SP_THREADS) dst[i] = cfg_combine(vx[i], vy[i], Lx, Ly, g, x_dead, y_dead);
+}
+
+// next[B + b] = next[b]: the unconditional twins decode the token their conditional row drew
+__global__ __launch_bounds__(256) void cfg_mirror_kernel(int64_t* next, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B) next[B + b] = next[b];
 }
 
 // ---- per-row bans between the logits and the token choice (slam_constrain_scores) -------------------------------------------
@@ -2084,6 +2170,43 @@ int token_logprobs(const float* logits, int B, int vocab, const int64_t* tokens,
     logprob_chunk_kernel<<<dim3(P.nch, B), SP_THREADS, 0, st>>>(logits, finished, P, w);
     logprob_finish_kernel<false><<<B, 64, 0, st>>>(logits, tokens, done, finished, out, P, w);
   }
+  return (int)hipGetLastError();
+}
+
+size_t cfg_workspace_bytes(int B, int vocab) {
+  if (B <= 0 || 2 * (int64_t)B > 65535 || vocab <= 0) return 0;
+  return (size_t)2 * B * sample_chunks(vocab) * sizeof(float2);
+}
+
+int cfg_scores(const float* logits, int B, int vocab, float g, float* scores, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!logits || !scores || !ws || B <= 0 || 2 * (int64_t)B > 65535 || vocab <= 0 || !isfinite(g)) return -1;
+  if ((((uintptr_t)logits | (uintptr_t)scores) & 3) || ((uintptr_t)ws & 7) || ws_bytes < cfg_workspace_bytes(B, vocab)) return -1;
+  const uintptr_t l0 = (uintptr_t)logits, s0 = (uintptr_t)scores;
+  const size_t row = (size_t)vocab * sizeof(float);
+  if (l0 < s0 + (size_t)B * row && s0 < l0 + (size_t)2 * B * row) return -1;  // the raw rows are read again afterwards
+  CfgParams P;
+  P.vocab = vocab;
+  P.nch = sample_chunks(vocab);
+  P.B = B;
+  P.g = g;
+  float2* w = reinterpret_cast<float2*>(ws);
+  if (P.nch == 1) {
+    cfg_scores_kernel<true><<<dim3(1, B), SP_THREADS, 0, st>>>(logits, scores, P, w);
+  } else {
+    LogprobParams L;
+    L.vocab = vocab;
+    L.nch = P.nch;
+    L.column = 0;
+    L.out_stride = 0;
+    logprob_chunk_kernel<<<dim3(P.nch, 2 * B), SP_THREADS, 0, st>>>(logits, nullptr, L, w);
+    cfg_scores_kernel<false><<<dim3(P.nch, B), SP_THREADS, 0, st>>>(logits, scores, P, w);
+  }
+  return (int)hipGetLastError();
+}
+
+int cfg_mirror_tokens(int64_t* next, int B, hipStream_t st) {
+  if (!next || ((uintptr_t)next & 7) || B < 1 || B > 32767) return -1;
+  cfg_mirror_kernel<<<nblk((size_t)B, 256), 256, 0, st>>>(next, B);
   return (int)hipGetLastError();
 }
 

@@ -2867,4 +2867,14 @@ int slam_token_logprobs(const float* logits, int32_t B, int32_t vocab, const int
   return token_logprobs(logits, B, vocab, tokens, done, finished, out, out_stride, column, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t slam_cfg_workspace_bytes(int32_t B, int32_t vocab) { return cfg_workspace_bytes(B, vocab); }
+int slam_cfg_scores(const float* logits, int32_t B, int32_t vocab, float guidance_scale, float* scores, void* ws,
+                    size_t ws_bytes, slam_stream_t stream) {
+  // cfg_scores refuses every bad argument (-1 = SLAM_EINVAL) before it launches anything
+  return cfg_scores(logits, B, vocab, guidance_scale, scores, ws, ws_bytes, (hipStream_t)stream);
+}
+int slam_cfg_mirror_tokens(int64_t* next, int32_t B, slam_stream_t stream) {
+  return cfg_mirror_tokens(next, B, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -417,6 +417,11 @@ int kv_repeat(bf16_t* kv, int* lens, float* logits, int B, int n, int bmax, int 
 size_t token_logprobs_workspace_bytes(int B, int vocab);  // host only
 int token_logprobs(const float* logits, int B, int vocab, const int64_t* tokens, const uint8_t* done, uint8_t* finished,
                    float* out, int64_t out_stride, int column, void* ws, size_t ws_bytes, hipStream_t st);
+// classifier-free guidance (include/slam_engine.h: slam_cfg_scores): scores[b] = g (a - u) + u from the log-softmax a of logits
+// row b and u of row B + b, on token_logprobs' row statistics; ws holds the (m_c, s_c) pairs of the 2 B rows.
+size_t cfg_workspace_bytes(int B, int vocab);  // host only
+int cfg_scores(const float* logits, int B, int vocab, float g, float* scores, void* ws, size_t ws_bytes, hipStream_t st);
+int cfg_mirror_tokens(int64_t* next, int B, hipStream_t st);  // next[B + b] = next[b]
 // LM head fused with the row statistics (include/slam_engine.h: slam_op_score_rows): for row m of X (bf16 [M][K]) against the
 // head W (bf16 [V][K]) on v_mfma_f32_16x16x32_bf16, lp = log-softmax at targets[m] and argmax = the lowest id of the largest
 // score, from fp32 accumulators that are never stored. colmask: nullable, >= V bytes, non-zero = the column counts as -inf.

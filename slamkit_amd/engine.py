@@ -128,6 +128,9 @@ def load_library(path: Optional[str] = None):
         "slam_ngram_propose": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, vp, vp]),
         "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
         "slam_token_logprobs": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, sz, vp]),
+        "slam_cfg_workspace_bytes": (sz, [i32, i32]),
+        "slam_cfg_scores": (C.c_int, [vp, i32, i32, f32, vp, vp, sz, vp]),
+        "slam_cfg_mirror_tokens": (C.c_int, [vp, i32, vp]),
         "slam_bucket_stream": (vp, [vp]),
         "slam_set_logit_mask": (C.c_int, [vp, vp]),
         "slam_padded_vocab": (i32, [vp]),
@@ -374,6 +377,34 @@ def token_logprobs(logits, tokens, out, column: int, ws, done=None, finished=Non
                                            stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_token_logprobs failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+def cfg_workspace_bytes(B: int, vocab: int) -> int:
+    """Bytes of device workspace slam_cfg_scores needs for B guided sequences (host arithmetic; 0 for invalid arguments)."""
+    return int(load_library().slam_cfg_workspace_bytes(int(B), int(vocab)))
+
+
+def cfg_scores(logits, guidance_scale: float, scores, ws, stream: Optional[int] = None):
+    """slam_cfg_scores: scores[b] (fp32 [B, vocab], no overlap with logits) = g (a - u) + u, a the log-softmax of row b of the
+    fp32 logits [2 B, vocab] (conditional) and u that of row B + b (unconditional). ws: a uint8 tensor of
+    cfg_workspace_bytes(B, vocab). Only enqueues work."""
+    B2, V = logits.shape
+    if B2 % 2 or tuple(scores.shape) != (B2 // 2, V) or not (logits.is_contiguous() and scores.is_contiguous()):
+        raise ValueError(f"cfg_scores: contiguous logits [2 B, V] and scores [B, V] (got {list(logits.shape)}, {list(scores.shape)})")
+    rc = load_library().slam_cfg_scores(_ptr(logits), B2 // 2, V, float(guidance_scale), _ptr(scores), _ptr(ws),
+                                       ws.numel() * ws.element_size(), stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_cfg_scores failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+def cfg_mirror_tokens(next_ids, stream: Optional[int] = None):
+    """slam_cfg_mirror_tokens: next_ids[B + b] = next_ids[b] on an int64 [2 B] device tensor. Only enqueues work."""
+    n = int(next_ids.numel())
+    if n % 2 or not next_ids.is_contiguous():
+        raise ValueError(f"cfg_mirror_tokens: a contiguous int64 tensor of 2 B entries (got {n})")
+    rc = load_library().slam_cfg_mirror_tokens(_ptr(next_ids), n // 2, stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_cfg_mirror_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 SCORE_CHUNK = 512  # SLAM_SCORE_CHUNK: vocabulary columns per chunk of slam_op_score_rows

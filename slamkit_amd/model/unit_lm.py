@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import bisect
 import json
+import math
 import os
 import re
 from dataclasses import dataclass, field
@@ -444,6 +445,41 @@ class _Constrainer:
         E.constrain_scores(logits, out, self.desc, self.ids, self.prompt_len, self.new, done, self.eos, self.begin,
                            self.seq_tokens, self.seq_offsets)
         return out
+
+
+def _compact_rows(seq: torch.Tensor, attention_mask, pad: int, what: str):
+    """Every row's real tokens moved to the left (stable: their order is kept), pad behind them: (ids [B, T] int64 contiguous,
+    lens int32 [B], T = the longest row). seq is on the device already; attention_mask None = every token is real."""
+    dev = seq.device
+    mask = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones_like(seq, dtype=torch.bool)
+    order = torch.sort((~mask).to(torch.int8), dim=1, stable=True).indices
+    lens = mask.sum(1).to(torch.int32)
+    T = int(lens.max())
+    if int(lens.min()) < 1:
+        raise ValueError(f"every {what} row needs at least one unmasked token")
+    ids = seq.gather(1, order)[:, :T]
+    ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, pad)).contiguous()
+    return ids, lens, T
+
+
+class _Guidance:
+    """Classifier-free guidance of one generate call. The logits hold n conditional rows, then their n unconditional twins;
+    apply() is slam_cfg_scores into a scores buffer of n rows, mirror() copies the n chosen tokens behind themselves so that
+    the decode step feeds both branches the same token."""
+
+    def __init__(self, scale: float, n: int, vocab: int, dev):
+        self.scale, self.n = float(scale), n
+        self.scores = torch.empty(n, vocab, dtype=torch.float32, device=dev)
+        self.ws = torch.empty(E.cfg_workspace_bytes(n, vocab), dtype=torch.uint8, device=dev)
+        self.next = torch.empty(2 * n, dtype=torch.int64, device=dev)  # [:n] is where the token choice is written
+
+    def apply(self, logits):
+        E.cfg_scores(logits, self.scale, self.scores, self.ws)
+        return self.scores
+
+    def mirror(self):
+        E.cfg_mirror_tokens(self.next)
+        return self.next
 
 
 class UnitLM(TokenLM):
@@ -1184,7 +1220,9 @@ class UnitLM(TokenLM):
                  assistant_model: Optional["UnitLM"] = None, num_assistant_tokens: Optional[int] = None,
                  prompt_lookup_num_tokens: Optional[int] = None, max_matching_ngram_size: Optional[int] = None,
                  min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
-                 eta_cutoff: Optional[float] = None, **kwargs):
+                 eta_cutoff: Optional[float] = None, guidance_scale: Optional[float] = None,
+                 negative_prompt_ids: Optional[torch.Tensor] = None,
+                 negative_prompt_attention_mask: Optional[torch.Tensor] = None, **kwargs):
         """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
         `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
         left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
@@ -1279,7 +1317,29 @@ class UnitLM(TokenLM):
         equal |-log p - entropy| are ordered by rank, (score descending, id ascending), where torch.sort leaves their order
         open. Assisted and prompt-lookup decoding verify with the same chain (the draft proposes with it too), so their
         tokens stay the target's own draws. Greedy decoding ignores the four, as HF does. With all four absent or off
-        generate calls what it called before, launch for launch."""
+        generate calls what it called before, launch for launch.
+
+        `guidance_scale` = g (a finite float; also read from `generation_config`) other than 1 turns on classifier-free
+        guidance, HF's UnbatchedClassifierFreeGuidanceLogitsProcessor: the scores become g (a - u) + u, a the log-softmax of
+        the row's logits and u that of an unconditional twin that reads `negative_prompt_ids` [B, T_neg] (with
+        `negative_prompt_attention_mask`, any padding side, compacted like the prompts) or, without them, the row's last real
+        prompt token, followed by the same new tokens. HF runs the twin as a second forward per step; here it rides in the same
+        decode batch. One prefill covers 2 B rows, the B prompts and then the B unconditional prompts, right-padded to
+        max(T, T_neg); `num_return_sequences` = n fans all of them out, rows [0, B n) conditional in HF's order and rows
+        [B n, 2 B n) their twins; the cache holds 2 B n rows of roundup(max(T, T_neg) + max_new_tokens, 64) and the workspace
+        max(2 B min(max(T, T_neg), prefill_chunk), 4 B n) tokens. Per step, in HF's processor order (guidance first):
+        slam_cfg_scores (include/slam_engine.h) from the 2 B n logits rows into B n rows of scores, the history bans in place
+        on those, the single-token mask and the token choice over the B n rows (`sample_ids` keeps B n entries),
+        slam_token_logprobs on the raw conditional rows for `return_logprobs` (the model's own log-softmax, as above),
+        slam_cfg_mirror_tokens, and the decode step over 2 B n rows. Both samplers; the engine sampler still has no torch op
+        between two engine calls. Deviations from HF: a right-padded prompt's default unconditional token is its last REAL
+        token (HF takes the last column, a pad); every branch's real tokens start at position 0 (HF runs the unconditional
+        branch without position_ids, so a padded negative prompt counts its pads as positions; unpadded ones agree); where HF
+        would produce NaN (a -inf on either side) the header's rules apply. ValueError: a non-finite guidance_scale; negative
+        prompts (or their mask) while guidance is off - HF ignores them silently -, with another batch size than B or with an
+        empty row; max(T, T_neg) + max_new_tokens above max_tokens; guidance together with assistant_model or
+        prompt_lookup_num_tokens (the verify pass would need guided chunk scores). With guidance_scale absent or 1 generate
+        calls what it called before, launch for launch."""
         if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
             raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
         if self.config.is_opt:
@@ -1348,6 +1408,20 @@ class UnitLM(TokenLM):
         assist_k = None
         lookup_k = pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None)
         lookup_n = pick(max_matching_ngram_size, "max_matching_ngram_size", None)
+        guidance_scale = pick(guidance_scale, "guidance_scale", None)
+        guided = False
+        if guidance_scale is not None:
+            guidance_scale = float(guidance_scale)
+            if not math.isfinite(guidance_scale):
+                raise ValueError(f"guidance_scale must be finite (got {guidance_scale})")
+            guided = guidance_scale != 1.0
+        if not guided and (negative_prompt_ids is not None or negative_prompt_attention_mask is not None):
+            raise ValueError("negative_prompt_ids / negative_prompt_attention_mask need a guidance_scale other than 1")
+        if guided and negative_prompt_ids is None and negative_prompt_attention_mask is not None:
+            raise ValueError("negative_prompt_attention_mask needs negative_prompt_ids")
+        if guided and (assistant_model is not None or lookup_k is not None):
+            raise ValueError("guidance_scale does not combine with assistant_model or prompt_lookup_num_tokens "
+                             "(the verify pass would need guided chunk scores)")
         if lookup_k is not None:
             if assistant_model is not None:
                 raise ValueError("prompt_lookup_num_tokens and assistant_model exclude each other: one source of proposals")
@@ -1374,17 +1448,28 @@ class UnitLM(TokenLM):
         seq_in = inputs.to(dev, torch.int64)
         B, T_in = seq_in.shape
         BN = B * nret  # rows decoded
-        mask = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones_like(seq_in, dtype=torch.bool)
-        # compact every row's real tokens to the left (stable: keeps their order)
-        order = torch.sort((~mask).to(torch.int8), dim=1, stable=True).indices
-        lens = mask.sum(1).to(torch.int32)
-        T = int(lens.max())
-        if int(lens.min()) < 1:
-            raise ValueError("every prompt row needs at least one unmasked token")
-        ids = seq_in.gather(1, order)[:, :T]
-        ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, int(pad))).contiguous()
+        ids, lens, T = _compact_rows(seq_in, attention_mask, int(pad), "prompt")
+        cfg = None
+        if guided:
+            # the unconditional prompts: the negative prompts, or each row's last real token (HF's input_ids[:, -1:])
+            if negative_prompt_ids is not None:
+                neg = negative_prompt_ids.to(dev, torch.int64)
+                if neg.dim() != 2 or neg.shape[0] != B:
+                    raise ValueError(f"negative_prompt_ids must be [{B}, T_neg] (got {list(neg.shape)})")
+                if negative_prompt_attention_mask is not None and negative_prompt_attention_mask.shape != neg.shape:
+                    raise ValueError("negative_prompt_attention_mask must have the shape of negative_prompt_ids")
+                nids, nlens, Tn = _compact_rows(neg, negative_prompt_attention_mask, int(pad), "negative prompt")
+            else:
+                nids, nlens, Tn = ids.gather(1, (lens.long() - 1)[:, None]), torch.ones_like(lens), 1
+            # one batch of 2 B rows, right-padded to the longer width: the B prompts, then their B unconditional twins
+            both = torch.full((2 * B, max(T, Tn)), int(pad), dtype=torch.int64, device=dev)
+            both[:B, :T] = ids
+            both[B:, :Tn] = nids
+            ids, lens, T = both, torch.cat([lens, nlens]), max(T, Tn)
         if T + max_new_tokens > self.config.max_tokens:
             raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds max_tokens {self.config.max_tokens}")
+        if guided:
+            cfg = _Guidance(guidance_scale, BN, self.config.vocab_size, dev)
         if assist_k is not None or lookup_k is not None:
             if assist_k is not None:
                 new, n = self._generate_assisted(assistant_model, assist_k, ids, lens, T, max_new_tokens, bad, eos, int(pad),
@@ -1398,16 +1483,18 @@ class UnitLM(TokenLM):
                     new = new[:, :int(all_done.nonzero()[0]) + 1]
             return torch.cat([seq_in, new], 1)
         cap = -(-(T + max_new_tokens) // 64) * 64
-        self._ensure_workspace(max(B * (T if prefill_chunk is None else min(T, prefill_chunk)), 2 * BN))
-        nbytes = self.engine.kv_cache_bytes(BN, cap)
+        # rows prefilled and rows in the cache: under guidance the conditional rows, then as many unconditional ones
+        P, R = (B, BN) if cfg is None else (2 * B, 2 * BN)
+        self._ensure_workspace(max(P * (T if prefill_chunk is None else min(T, prefill_chunk)), 2 * R))
+        nbytes = self.engine.kv_cache_bytes(R, cap)
         raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
         off = (-raw.data_ptr()) % 256
-        self.engine.bind_kv_cache(raw[off:off + nbytes], BN, cap)
+        self.engine.bind_kv_cache(raw[off:off + nbytes], R, cap)
         V = self.config.vocab_size
-        logits = torch.empty(BN, V, dtype=torch.float32, device=dev)
+        logits = torch.empty(R, V, dtype=torch.float32, device=dev)
         eos_t = torch.tensor(eos, dtype=torch.long, device=dev) if eos else None
-        if nret > 1:  # the B prompt rows first; slam_kv_repeat fills the rest
-            lens = torch.cat([lens, torch.zeros(BN - B, dtype=torch.int32, device=dev)])
+        if nret > 1:  # the prefilled rows first; slam_kv_repeat fills the rest
+            lens = torch.cat([lens, torch.zeros(R - P, dtype=torch.int32, device=dev)])
         self._hold = (ids, lens)
         new = torch.empty(BN, max_new_tokens, dtype=torch.int64, device=dev)
         lp = None
@@ -1416,22 +1503,27 @@ class UnitLM(TokenLM):
                   torch.empty(E.token_logprobs_workspace_bytes(BN, V), dtype=torch.uint8, device=dev))
         n = 0
         # prompt_len: a copy, because slam_decode_step advances lens
-        cons = _Constrainer(plan, ids, lens[:B].clone(), T_in, nret, new, lp is not None, dev) if plan.active else None
+        # under guidance the bans edit the guided scores in place: the raw logits stay whole for the log-probs anyway
+        cons = None
+        if plan.active:
+            cons = _Constrainer(plan, ids[:B], lens[:B].clone(), T_in, nret, new, lp is not None and cfg is None, dev)
         if on_device:
             n = self._sample_on_device(logits, new, ids, lens, T, bad, eos, int(pad), do_sample, top_k, temperature, top_p,
-                                       seed, sample_ids, nret, lp, prefill_chunk, cons, warp)
+                                       seed, sample_ids, nret, lp, prefill_chunk, cons, warp, cfg)
         else:
             bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
             g = None
             if do_sample and seed is not None:
                 g = torch.Generator(device=dev)
                 g.manual_seed(int(seed))
-            self._prefill(ids, lens, B, T, logits, prefill_chunk)
+            self._prefill(ids, lens, P, T, logits, prefill_chunk)
             if nret > 1:
                 self.engine.kv_repeat(nret, lens, logits)
             done = torch.zeros(BN, dtype=torch.bool, device=dev)
             for step in range(max_new_tokens):
-                scores = logits if cons is None else cons.apply(logits, step, done.view(torch.uint8))
+                scores = logits if cfg is None else cfg.apply(logits)
+                if cons is not None:
+                    scores = cons.apply(scores, step, done.view(torch.uint8))
                 if bad_idx is not None:
                     scores = scores.index_fill(1, bad_idx, float("-inf"))
                 if do_sample:
@@ -1445,12 +1537,16 @@ class UnitLM(TokenLM):
                 if eos_t is not None:
                     done |= torch.isin(nxt, eos_t)
                 if lp is not None:
-                    E.token_logprobs(logits, nxt.contiguous(), lp[0], step, lp[2], done.view(torch.uint8), lp[1])
+                    E.token_logprobs(logits[:BN], nxt.contiguous(), lp[0], step, lp[2], done.view(torch.uint8), lp[1])
                 if eos_t is not None:
                     if (step % 16 == 15 or step + 1 == max_new_tokens) and bool(done.all()):
                         break
                 if step + 1 < max_new_tokens:
-                    self.engine.decode_step(nxt.contiguous(), lens, BN, logits)
+                    if cfg is None:
+                        self.engine.decode_step(nxt.contiguous(), lens, BN, logits)
+                    else:
+                        cfg.next[:BN] = nxt
+                        self.engine.decode_step(cfg.mirror(), lens, R, logits)
         new = new[:, :n]
         if eos_t is not None and n > 1:
             # HF stops right after the step on which the last row finished: drop the all-pad columns behind it
@@ -1600,13 +1696,16 @@ class UnitLM(TokenLM):
             self.engine.extend(ids[:, c0:c0 + w].contiguous(), new_lens, cur, B, w, logits)
 
     def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids,
-                          nret=1, lp=None, prefill_chunk=None, cons=None, warp=None):
+                          nret=1, lp=None, prefill_chunk=None, cons=None, warp=None, cfg=None):
         """The decode loop of generate(sampler="engine"): prefill, sample(step 0), then decode_step(next) / sample(step k). The
         kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written.
         logits / new have B n rows: the prompts (ids, the first rows of lens) are prefilled once and fanned out (kv_repeat).
-        cons (a _Constrainer) puts slam_constrain_scores in front of the sampler; the log-probs keep reading the raw logits."""
+        cons (a _Constrainer) puts slam_constrain_scores in front of the sampler; the log-probs keep reading the raw logits.
+        cfg (a _Guidance): logits holds cfg.n conditional rows and their unconditional twins; slam_cfg_scores comes first, only
+        the conditional rows are sampled and scored, and slam_cfg_mirror_tokens hands every twin its row's token."""
         dev = self.device
-        B, V = logits.shape
+        R, V = logits.shape                # rows in the cache
+        B = R if cfg is None else cfg.n    # rows sampled
         max_new = new.shape[1]
         if do_sample and seed is None:
             seed = int(torch.randint(0, 1 << 62, (1,)).item())
@@ -1625,25 +1724,27 @@ class UnitLM(TokenLM):
             if row_ids.shape != (B,):
                 raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        self._prefill(ids, lens, B // nret, T, logits, prefill_chunk)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev) if cfg is None else cfg.next[:B]
+        self._prefill(ids, lens, R // nret, T, logits, prefill_chunk)
         if nret > 1:
             self.engine.kv_repeat(nret, lens, logits)
         n = 0
         for step in range(max_new):
             desc.step = step
-            scores = logits if cons is None else cons.apply(logits, step, done)
+            scores = logits if cfg is None else cfg.apply(logits)
+            if cons is not None:
+                scores = cons.apply(scores, step, done)
             if warp is None:
                 E.sample_tokens(scores, desc, nxt, ws, banned, row_ids, eos_i, done, new)
             else:
                 E.sample_tokens_warped(scores, desc, nxt, ws, warp, None, 1, None, banned, row_ids, eos_i, done, new)
             if lp is not None:
-                E.token_logprobs(logits, nxt, lp[0], step, lp[2], done, lp[1])
+                E.token_logprobs(logits[:B], nxt, lp[0], step, lp[2], done, lp[1])
             n = step + 1
             if eos_i is not None and (step % 16 == 15 or n == max_new) and bool(done.all()):
                 break
             if n < max_new:
-                self.engine.decode_step(nxt, lens, B, logits)
+                self.engine.decode_step(nxt if cfg is None else cfg.mirror(), lens, R, logits)
         return n  # ws / banned / done were used on the current stream only: the allocator reuses them in stream order
 
     def _check_assistant(self, draft, k, nret, return_logprobs, plan, do_sample, sampler) -> int:

@@ -2,6 +2,7 @@
 B = 8, prompt 256, 150 new tokens (config/metric/generate.yaml), on a randomly initialised model.
 
 Usage: python tools/decode_bench.py [--models slam,cfg3] [--steps 150] [--reps 2] [--no-reforward]
+       python tools/decode_bench.py --cfg --models slam,cfg3,7b [--batches 1,8,32] [--blocks 3]
        python tools/decode_bench.py --num-return-sequences 8 [--models slam,cfg3] [--reps 3]
        python tools/decode_bench.py --prefill-chunk 512 [--models slam,cfg3]
        python tools/decode_bench.py --decode-weights fp8 --include-head --models slam,cfg3,7b
@@ -49,6 +50,16 @@ over the blocks, `_all` the blocks), `bf16_over_fp8` (median of the per-block ra
 (`bf16_MB`, `fp8_MB`) and their 6.3 TB/s floors, and `w8_launches_per_step`. --decode-weights bf16 runs the bf16 blocks alone
 through calls every earlier revision has: the same file, copied into a parent checkout, measures it for an A-B-A comparison.
 `7b` is the Qwen2.5-7B body with the unit vocabulary.
+--cfg [--models slam,cfg3,7b] [--batches 1,8,32] [--blocks 3]: the guided decode step of classifier-free guidance - one
+slam_cfg_scores over the 2 B logits rows, one slam_cfg_mirror_tokens, one slam_decode_step over 2 B rows - against the plain
+step at B (slam_decode_step alone: launches this option does not touch), as plain - guided - plain blocks within this process,
+prompt 256, device events per step, 10 warm-up steps per block: one `cfg_step` line per (model, B, neg_len) with
+`plain_step_ms` (median over all plain blocks, `_all` the blocks), `guided_step_ms` and `guided_over_plain` (median of the
+per-block ratios against the mean of the two plain blocks around it, `_minmax`). neg_len is the length of the unconditional
+rows' prompts: 1 (generate's default, the last prompt token) and 256 (a negative prompt as long as the prompt). Then one
+`cfg_op` line per (B, V) in {8, 32} x {502, 152576}: `cfg_scores_us` = one slam_cfg_scores (device events around 200
+back-to-back calls, five rounds), `bytes_MB` = what it moves (2 B rows read, B written; rows above one chunk are read twice) and
+`GBps`, `floor_us` = bytes / 6.3 TB/s; and `mirror_us` = one slam_cfg_mirror_tokens.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -124,6 +135,93 @@ def w8_bench(name, batches, P, steps, blocks, fp8, include_head):
         print(json.dumps(r), flush=True)
     del m
     torch.cuda.empty_cache()
+
+
+def cfg_step_bench(name, batches, P, steps, blocks, scale=1.5):
+    """The guided step (slam_cfg_scores + slam_cfg_mirror_tokens + slam_decode_step over 2 B rows) between two plain steps at B."""
+    import torch
+    from slamkit_amd import engine as E
+    m = build(name, 4096)
+    dev = m.device
+    V = m.config.vocab_size
+    cap = -(-(P + steps) // 64) * 64  # every block prefills again
+
+    def block(rows, lens0, guided):
+        g = torch.Generator(device=dev).manual_seed(0)
+        ids = torch.randint(2, V, (rows, P), device=dev, generator=g)
+        lens = lens0.clone()
+        logits = torch.empty(rows, V, dtype=torch.float32, device=dev)
+        m.engine.prefill(ids, lens, rows, P, logits)
+        tok = torch.ones(rows, dtype=torch.int64, device=dev)
+        if guided:
+            scores = torch.empty(rows // 2, V, dtype=torch.float32, device=dev)
+            ws = torch.empty(E.cfg_workspace_bytes(rows // 2, V), dtype=torch.uint8, device=dev)
+
+        def step():
+            if guided:
+                E.cfg_scores(logits, scale, scores, ws)
+                E.cfg_mirror_tokens(tok)
+            m.engine.decode_step(tok, lens, rows, logits)
+
+        st = [ev_ms(step) for _ in range(steps)]
+        return statistics.median(st[10:])
+
+    for B in batches:
+        m._ensure_workspace(max(2 * B * P, 4 * B))
+        cache = torch.empty(m.engine.kv_cache_bytes(2 * B, cap), dtype=torch.uint8, device=dev)
+        m.engine.bind_kv_cache(cache, 2 * B, cap)
+        full = torch.full((B,), P, dtype=torch.int32, device=dev)
+        for neg_len in (1, P):
+            both = torch.cat([full, torch.full((B,), neg_len, dtype=torch.int32, device=dev)])
+            plain, guided, ratios = [block(B, full, False)], [], []
+            for _ in range(blocks):
+                guided.append(block(2 * B, both, True))
+                plain.append(block(B, full, False))
+                ratios.append(guided[-1] / (0.5 * (plain[-2] + plain[-1])))
+            print(json.dumps(dict(bench="cfg_step", model=name, B=B, prompt=P, neg_len=neg_len, steps_timed=steps - 10, blocks=blocks,
+                                  plain_step_ms=round(statistics.median(plain), 4), plain_step_ms_all=[round(t, 4) for t in plain],
+                                  guided_step_ms=round(statistics.median(guided), 4),
+                                  guided_step_ms_all=[round(t, 4) for t in guided],
+                                  guided_over_plain=round(statistics.median(ratios), 3),
+                                  guided_over_plain_minmax=[round(min(ratios), 3), round(max(ratios), 3)])), flush=True)
+        del cache
+    del m
+    torch.cuda.empty_cache()
+
+
+def cfg_op_bench(calls=200, rounds=5):
+    """Device-event time of slam_cfg_scores and of slam_cfg_mirror_tokens alone."""
+    import torch
+    from slamkit_amd import engine as E
+    dev = torch.device("cuda")
+    for B, V in ((8, 502), (32, 502), (8, 152576), (32, 152576)):
+        g = torch.Generator(device=dev).manual_seed(V + B)
+        logits = torch.randn(2 * B, V, device=dev, generator=g) * 3.0
+        scores = torch.empty(B, V, dtype=torch.float32, device=dev)
+        ws = torch.empty(E.cfg_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
+        nxt = torch.ones(2 * B, dtype=torch.int64, device=dev)
+
+        def run_scores():
+            for _ in range(calls):
+                E.cfg_scores(logits, 1.5, scores, ws)
+
+        def run_mirror():
+            for _ in range(calls):
+                E.cfg_mirror_tokens(nxt)
+
+        run_scores()
+        run_mirror()
+        torch.cuda.synchronize()
+        ts, tm = [], []
+        for _ in range(rounds):  # alternated
+            ts.append(ev_ms(run_scores) / calls * 1e3)
+            tm.append(ev_ms(run_mirror) / calls * 1e3)
+        nbytes = (3 if V <= 2048 else 5) * B * V * 4  # rows above one chunk: the statistics' launch reads both rows first
+        us = statistics.median(ts)
+        print(json.dumps(dict(bench="cfg_op", B=B, vocab=V, cfg_scores_us=round(us, 2),
+                              cfg_scores_us_minmax=[round(min(ts), 2), round(max(ts), 2)], bytes_MB=round(nbytes / 1e6, 3),
+                              GBps=round(nbytes / us / 1e3, 1), floor_us=round(nbytes / HBM_BPS * 1e6, 3),
+                              mirror_us=round(statistics.median(tm), 2))), flush=True)
 
 
 def step_bench(m, B, P, steps, tag, quiet=False, saved=0):
@@ -581,7 +679,10 @@ def main():
     ap.add_argument("--decode-weights", default=None, choices=["bf16", "fp8"],
                     help="decode step per model and batch: fp8 alternates blocks from bf16 weights and from FP8 codes; bf16 runs "
                          "the bf16 blocks alone")
-    ap.add_argument("--batches", default="1,8,64", help="with --decode-weights")
+    ap.add_argument("--cfg", action="store_true",
+                    help="classifier-free guidance: the guided step (2 B rows + slam_cfg_scores + the mirror) between plain steps "
+                         "at B (--batches, default 1,8,32), then slam_cfg_scores and slam_cfg_mirror_tokens alone")
+    ap.add_argument("--batches", default=None, help="with --decode-weights (default 1,8,64) or --cfg (default 1,8,32)")
     ap.add_argument("--blocks", type=int, default=3, help="with --decode-weights: alternations per (model, batch)")
     ap.add_argument("--include-head", action="store_true", help="with --decode-weights fp8: FP8 codes for the LM head too")
     a = ap.parse_args()
@@ -590,9 +691,14 @@ def main():
         return
     import torch
     assert torch.cuda.is_available()
+    if a.cfg:
+        for name in a.models.split(","):
+            cfg_step_bench(name, [int(b) for b in (a.batches or "1,8,32").split(",")], 256, min(a.steps, 60), a.blocks)
+        cfg_op_bench()
+        return
     if a.decode_weights:
         for name in a.models.split(","):
-            w8_bench(name, [int(b) for b in a.batches.split(",")], 256, a.steps, a.blocks, a.decode_weights == "fp8", a.include_head)
+            w8_bench(name, [int(b) for b in (a.batches or "1,8,64").split(",")], 256, a.steps, a.blocks, a.decode_weights == "fp8", a.include_head)
         return
     if a.sample_op:
         if a.warp:
