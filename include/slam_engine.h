@@ -680,6 +680,32 @@ int slam_scale_loss_rows(SlamEngine* h, const float* seq_coef, int32_t B, int32_
  * slam_scale_loss_unpadded after a smoothed forward (sequence objectives are defined on the plain log-likelihood). */
 int slam_set_label_smoothing(SlamEngine* h, float epsilon);
 
+/* NEFTune (HF TrainingArguments.neftune_noise_alpha: transformers.integrations.neftune.neftune_post_forward_hook): uniform noise
+ * on the input embeddings of a TRAINING forward, out = E[ids] + U(-mag, mag), mag = alpha / sqrt(T * H). alpha >= 0 and finite,
+ * else SLAM_EINVAL with a message; 0 (the default) is off; alpha and seed (read as 64 unsigned bits) persist until changed. The
+ * call adds no buffer: a bound workspace stays bound. The noise is drawn INSIDE the embedding gather of an armed forward - no
+ * launch, no buffer and no pass over [M][H] more - and NOTHING IS STORED: it is an additive constant, so backward is unchanged,
+ * and no "recompute" level re-runs the embedding launch (the residual streams are kept).
+ *   generator  Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (i8 & 0xffffffff, i8 >> 32, call, 0x4E454654),
+ *              i8 = i >> 3, i = m * H + h the flat index of the element in the [M][H] layout that is launched. The last counter
+ *              word is where "dropout_thr16" has 2 * layer + site: the two never draw the same bits under one seed;
+ *   element    j = i & 7 takes r16 = (w[j >> 1] >> 16 (j & 1)) & 0xffff (the mapping of "adamw_sr" / "dropout_thr16");
+ *   scale      s = (float)((double)alpha / sqrt((double)T * H) / 65536.0), on the host, once per forward: T of slam_forward, the
+ *              padded width T of slam_forward_unpadded (HF sees [B, T]; a flattened packed batch is [1, M]);
+ *   noise      t = 2 r16 - 65535 as a float (exact: an odd integer in [-65535, 65535]); n = t * s, ONE fp32 multiply rounded to
+ *              nearest, never contracted into the add. 65536 levels symmetric about 0, |n| <= 65535 s < mag;
+ *   output     Qwen2 / Qwen3: out = bf16(e + n), e the bf16 table entry as fp32; OPT: out = bf16((E + P) + n), the two fp32
+ *              adds in this order (HF adds the noise to the token embedding before the positions: the same sum up to the
+ *              order). One rounding to nearest-even. Ids outside [0, vocab) read row 0, as unarmed, and get noise.
+ * Option "neftune_call_next" = 0 .. 2^32 - 1 (slam_set_option; anything else is SLAM_EINVAL, "out of range") arms the NEXT
+ * slam_forward / slam_forward_unpadded and no other, with this call number, and resets itself; a forward that is refused uses
+ * it up as well. Ignored while alpha is 0. A forward that was not armed launches the plain gather - the instruction stream of an
+ * engine that never called this - and slam_prefill, slam_decode_step, the slam_extend family and every scoring path never draw
+ * noise. Under slam_forward_unpadded the element index is the PACKED one (the "dropout_thr16" contract): a token's noise
+ * differs from the padded run's. The noise depends on nothing else - not on the stream, the recompute level or the rank - so a
+ * caller that numbers its forwards (optimizer step x accumulation steps + micro-batch) repeats a run exactly. */
+int slam_set_neftune(SlamEngine* h, float alpha, int64_t seed);
+
 /* ---- optimizer step: HF Trainer clip_grad_norm_ + torch AdamW --------------
  * norm_out: fp32 [2] device = {global grad norm, clip coefficient}.
  * Where the gradients are read from follows the last slam_backward: the fp32 buffer of slam_bind_params, or - after a
@@ -1056,6 +1082,16 @@ int slam_op_dropout_add(void* y, const void* resid, int M, int H, int32_t thr16,
                         int64_t index0, slam_stream_t s);
 int slam_op_dropout_bwd(const void* dy, void* dy_masked, int M, int H, int32_t thr16, int64_t seed, int64_t call, int32_t stream_id,
                         int64_t index0, slam_stream_t s);
+/* out [M][H] = E[ids[m]] (ids outside [0, V) read row 0): the plain gather of the Qwen2 / Qwen3 forward, H a multiple of 8 */
+int slam_op_embed_fwd(const int64_t* ids, const void* E, void* out, int M, int H, int V, slam_stream_t s);
+/* The embedding launch of an armed forward on its own (slam_set_neftune): out [M][H] bf16 = the gather of ids from E [V][H]
+ * (+ row pos + 2 of P [n_rows_p][H], pos = position_ids[m] or m % T; prow as slam_op_embed_pos_fwd) plus the noise of flat index
+ * index0 + m * H + h under (seed, call) at scale s. P = NULL: no position table (position_ids, prow, T and n_rows_p are not
+ * read). SLAM_EINVAL before any launch: ids, E or out NULL, M <= 0, V <= 0, H % 8 != 0, with P a T or n_rows_p <= 0, s negative or not finite, call outside
+ * 0 .. 2^32 - 1, index0 negative or no multiple of 8 (the engine's own launches pass 0). */
+int slam_op_embed_noise_fwd(const int64_t* ids, const int64_t* position_ids, const void* E, const void* P, void* out, int64_t* prow,
+                            int M, int H, int V, int T, int n_rows_p, float s, int64_t seed, int64_t call, int64_t index0,
+                            slam_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,12 @@ SLAM_DEVICE uint32_t drop_keep8(const DropKey& k, uint64_t i8) {
   return keep;
 }
 
+// ---- NEFTune ("neftune_call_next") ----------------------------------------------------------------
+// The noise of an embedding output element is a function of (seed, call, flat element index) alone, on the generator and the
+// element -> 16 bits mapping of the dropout sites; its site word is a constant no dropout site (2 * layer + site) reaches.
+#define NEFT_SITE 0x4E454654u
+struct NeftKey { uint32_t k0 = 0, k1 = 0, call = 0; float s = 0.f; uint64_t base = 0; };  // s: noise per level; base: as DropKey's
+
 // raw v_exp_f32 (2^x): no denormal-range fix-up code (arguments here are <= 0 or moderate)
 SLAM_DEVICE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 

@@ -537,10 +537,26 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(bf16_t* __restrict__ gu
 }
 
 // ------------------------------------------------------------------------------------------
-// Embedding gather: out[m,:] = E[ids[m],:]
-__global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restrict__ ids,
-                                                        const bf16_t* __restrict__ E, bf16_t* __restrict__ out,
-                                                        size_t M, int H, int V) {
+// NEFTune ("neftune_call_next", include/slam_engine.h): uniform noise on the embedding output, drawn inside the gather. The eight
+// elements of a lane's chunk share one Philox call; element j of chunk i8 takes t = 2 r16 - 65535 (exact: an odd integer) and
+// n = t * s, one uncontracted fp32 multiply, is added to the fp32 value the plain gather would store.
+SLAM_DEVICE void neft_add8(float* a, const NeftKey& k, uint64_t i8) {
+  // the multiply and the add round separately (__fmul_rn + __fadd_rn): the operators under this pragma, because the two
+  // intrinsics are plain operators in the runtime's headers and the compiler fuses them into one fma all the same
+#pragma clang fp contract(off)
+  const Philox4 b = philox4x32_10((uint32_t)i8, (uint32_t)(i8 >> 32), k.call, NEFT_SITE, k.k0, k.k1);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float n = (float)(2 * (int)sr_r16(b, j) - 65535) * k.s;
+    a[j] = a[j] + n;
+  }
+}
+
+// Embedding gather: out[m,:] = E[ids[m],:]; NOISE: out[m,:] = bf16(E[ids[m],:] + n), one rounding. The unarmed kernel keeps
+// its name and arguments: its instantiation is the code it was before the noisy one existed.
+template <bool NOISE>
+SLAM_DEVICE void embed_fwd_body(const int64_t* __restrict__ ids, const bf16_t* __restrict__ E, bf16_t* __restrict__ out, size_t M,
+                                int H, int V, const NeftKey& k) {
   size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   int nch = H >> 3;
   if (idx >= M * nch) return;
@@ -548,15 +564,32 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
   int c = idx % nch;
   int64_t id = ids[m];
   if (id < 0 || id >= V) id = 0;
-  *reinterpret_cast<uint4*>(out + m * H + c * 8) = *reinterpret_cast<const uint4*>(E + (size_t)id * H + c * 8);
+  if (NOISE) {
+    float a[8];
+    unpack_bf16x8(*reinterpret_cast<const uint4*>(E + (size_t)id * H + c * 8), a);
+    neft_add8(a, k, (k.base >> 3) + idx);
+    *reinterpret_cast<uint4*>(out + m * H + c * 8) = pack_bf16x8(a);
+  } else {
+    *reinterpret_cast<uint4*>(out + m * H + c * 8) = *reinterpret_cast<const uint4*>(E + (size_t)id * H + c * 8);
+  }
+}
+__global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restrict__ ids,
+                                                        const bf16_t* __restrict__ E, bf16_t* __restrict__ out,
+                                                        size_t M, int H, int V) {
+  embed_fwd_body<false>(ids, E, out, M, H, V, NeftKey());
+}
+__global__ __launch_bounds__(256) void embed_noise_fwd_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ E,
+                                                              bf16_t* __restrict__ out, size_t M, int H, int V, NeftKey k) {
+  embed_fwd_body<true>(ids, E, out, M, H, V, k);
 }
 
 // OPT embedding: out[m,:] = bf16(E[ids[m],:] + P[pos[m] + 2,:]) (one rounding), pos = position_ids or m % T; the
 // position row index is also written to prow[m] (the backward's scatter ids). Both indices are clamped to their tables.
-__global__ __launch_bounds__(256) void embed_pos_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
-                                                            const bf16_t* __restrict__ E, const bf16_t* __restrict__ P,
-                                                            bf16_t* __restrict__ out, int64_t* __restrict__ prow, size_t M,
-                                                            int H, int V, int T, int NP) {
+// NOISE: out[m,:] = bf16((E + P) + n), the two fp32 adds in this order.
+template <bool NOISE>
+SLAM_DEVICE void embed_pos_fwd_body(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos, const bf16_t* __restrict__ E,
+                                    const bf16_t* __restrict__ P, bf16_t* __restrict__ out, int64_t* __restrict__ prow, size_t M,
+                                    int H, int V, int T, int NP, const NeftKey& k) {
   size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   int nch = H >> 3;
   if (idx >= M * nch) return;
@@ -572,7 +605,20 @@ __global__ __launch_bounds__(256) void embed_pos_fwd_kernel(const int64_t* __res
   unpack_bf16x8(*reinterpret_cast<const uint4*>(P + (size_t)p * H + c * 8), b);
 #pragma unroll
   for (int j = 0; j < 8; ++j) a[j] += b[j];
+  if (NOISE) neft_add8(a, k, (k.base >> 3) + idx);
   *reinterpret_cast<uint4*>(out + m * H + c * 8) = pack_bf16x8(a);
+}
+__global__ __launch_bounds__(256) void embed_pos_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
+                                                            const bf16_t* __restrict__ E, const bf16_t* __restrict__ P,
+                                                            bf16_t* __restrict__ out, int64_t* __restrict__ prow, size_t M,
+                                                            int H, int V, int T, int NP) {
+  embed_pos_fwd_body<false>(ids, pos, E, P, out, prow, M, H, V, T, NP, NeftKey());
+}
+__global__ __launch_bounds__(256) void embed_pos_noise_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
+                                                                  const bf16_t* __restrict__ E, const bf16_t* __restrict__ P,
+                                                                  bf16_t* __restrict__ out, int64_t* __restrict__ prow, size_t M,
+                                                                  int H, int V, int T, int NP, NeftKey k) {
+  embed_pos_fwd_body<true>(ids, pos, E, P, out, prow, M, H, V, T, NP, k);
 }
 
 // ReLU backward through the stored post-ReLU activation: d[i] = act[i] > 0 ? d[i] : 0
@@ -1483,6 +1529,18 @@ int embed_pos_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const
                   int V, int T, int NP, hipStream_t st) {
   if ((H & 7) || T <= 0 || NP <= 0) return -1;
   embed_pos_fwd_kernel<<<nblocks((size_t)M * (H / 8), 256), 256, 0, st>>>(ids, pos, E, P, out, prow, (size_t)M, H, V, T, NP);
+  LAUNCH_RET();
+}
+int embed_noise_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const bf16_t* P, bf16_t* out, int64_t* prow, int M, int H,
+                    int V, int T, int NP, const NeftSite& n, hipStream_t st) {
+  if (M <= 0 || H <= 0 || (H & 7) || !(n.s >= 0.f) || !__builtin_isfinite(n.s) || n.index0 < 0 || (n.index0 & 7)) return -1;
+  if (P && (T <= 0 || NP <= 0)) return -1;
+  NeftKey k;
+  k.k0 = (uint32_t)n.seed; k.k1 = (uint32_t)(n.seed >> 32);
+  k.call = n.call; k.s = n.s; k.base = (uint64_t)n.index0;
+  const unsigned grid = nblocks((size_t)M * (H / 8), 256);
+  if (P) embed_pos_noise_fwd_kernel<<<grid, 256, 0, st>>>(ids, pos, E, P, out, prow, (size_t)M, H, V, T, NP, k);
+  else embed_noise_fwd_kernel<<<grid, 256, 0, st>>>(ids, E, out, (size_t)M, H, V, k);
   LAUNCH_RET();
 }
 int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st) {

@@ -197,6 +197,14 @@ struct SlamEngine {
   int64_t dropout_call_next = -1;  // -1: not armed
   bool fwd_drop = false;           // the last slam_forward applied dropout ...
   DropSite fwd_site;               // ... with these (site and index0 filled per launch)
+  // NEFTune (slam_set_neftune in the header): "neftune_call_next" arms the NEXT slam_forward only; that forward's embedding
+  // launch draws the noise. Nothing is stored and nothing re-runs the launch: the residual streams hs[l] are kept at every
+  // "recompute" level.
+  float neftune_alpha = 0.f;
+  uint64_t neftune_seed = 0;
+  int64_t neftune_call_next = -1;  // -1: not armed
+  bool fwd_neft = false;           // forward_layers launches the noisy gather ...
+  NeftSite fwd_neft_site;          // ... with these
   // backward's masked copies of the residual gradients, [layer parity][site] x [M][H]: the weight-gradient stream reads layer
   // l's after the caller's stream has moved on, so layer l - 2 waits for ev_dm[l] before it overwrites them
   bf16_t* dmask[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -802,7 +810,10 @@ int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_id
   }
   CK(wait_chunk(h, 0, st));
   CK(wait_params(h, h->off_embed, h->lo[0].ln1, st));
-  if (opt) CK(embed_pos_fwd(ids, position_ids, P + h->off_embed, P + h->off_pos, h->hs[0], h->prow, M, H, d.vocab, T, h->npos, st));
+  if (h->fwd_neft)
+    CK(embed_noise_fwd(ids, position_ids, P + h->off_embed, opt ? P + h->off_pos : nullptr, h->hs[0], opt ? h->prow : nullptr, M, H,
+                       d.vocab, T, h->npos, h->fwd_neft_site, st));
+  else if (opt) CK(embed_pos_fwd(ids, position_ids, P + h->off_embed, P + h->off_pos, h->hs[0], h->prow, M, H, d.vocab, T, h->npos, st));
   else CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
   for (int l = 0; l < L; ++l) {
     CK(layer_forward(h, l, M, false, st));
@@ -1062,6 +1073,11 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
     if (h->dropout_thr16) h->dropout_call_next = value;  // ignored while dropout is off
     return SLAM_OK;
   }
+  if (!strcmp(key, "neftune_call_next") && h) {
+    if (value < 0 || value > 0xffffffffLL) return h->fail(SLAM_EINVAL, "value out of range for option neftune_call_next (0 .. 2^32 - 1)");
+    if (h->neftune_alpha > 0.f) h->neftune_call_next = value;  // ignored while NEFTune is off
+    return SLAM_OK;
+  }
   if (!strcmp(key, "fuse_swiglu") && h) { h->fuse_swiglu = value != 0; return SLAM_OK; }
   if (!strcmp(key, "fuse_dswiglu") && h) { h->fuse_dswiglu = value != 0; return SLAM_OK; }
   if (!strcmp(key, "fuse_adamw_t") && h) { h->fuse_adamw_t = value != 0; return SLAM_OK; }
@@ -1074,8 +1090,10 @@ static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labe
                           const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
                           float* loss_out, void* logits_out, const UnpadView* up, int up_B, int up_T, slam_stream_t stream) {
   // "dropout_call_next" arms this call and no other: a refused forward uses it up too, so no later one inherits it
-  const int64_t armed_call = h->dropout_call_next;
+  const int64_t armed_call = h->dropout_call_next, neft_call = h->neftune_call_next;
   h->dropout_call_next = -1;
+  h->neftune_call_next = -1;
+  h->fwd_neft = false;
   if (!ids || B <= 0 || T <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   const int64_t M64 = (int64_t)B * T;
@@ -1098,8 +1116,19 @@ static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labe
     h->fwd_site.seed = h->dropout_seed;
     h->fwd_site.call = (uint32_t)armed_call;
   }
+  // "neftune_call_next", the same way: s from the batch as the caller passed it (a padding-free call's padded width), the
+  // element index from the layout that is launched
+  if (h->neftune_alpha > 0.f && neft_call >= 0) {
+    h->fwd_neft = true;
+    h->fwd_neft_site = NeftSite();
+    h->fwd_neft_site.s = (float)((double)h->neftune_alpha / sqrt((double)(up ? up_T : T) * (double)H) / 65536.0);
+    h->fwd_neft_site.seed = h->neftune_seed;
+    h->fwd_neft_site.call = (uint32_t)neft_call;
+  }
   GemmTuneScope tune_scope(&h->gemm_tune);
-  CK(forward_layers(h, ids, position_ids, seg_start, seg_end, M, T, st));
+  const int fl = forward_layers(h, ids, position_ids, seg_start, seg_end, M, T, st);
+  h->fwd_neft = false;  // this forward's launch and no other
+  CK(fl);
   TK(F_NORM_FWD, st, norm_fwd(h, h->hs[L], h->off_norm, h->off_norm_b, h->hf, h->muf, h->rstdf, M, st));
   const int VP = h->vpad;
   TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_head, h->logits, nullptr, nullptr, M, VP, H, st));
@@ -1140,8 +1169,8 @@ int slam_forward_unpadded(SlamEngine* h, const int64_t* ids, const int64_t* labe
                           int32_t M_packed, void* scratch, size_t scratch_bytes, double num_items, float* loss_out,
                           void* logits_out, slam_stream_t stream) {
   if (!h) return SLAM_EINVAL;
-  const int64_t armed_call = h->dropout_call_next;  // a refused call uses the arming up, as slam_forward does
-  auto refuse = [&](int code, const char* m) { h->dropout_call_next = -1; return h->fail(code, m); };
+  const int64_t armed_call = h->dropout_call_next, neft_call = h->neftune_call_next;  // a refused call uses the arming up, as slam_forward does
+  auto refuse = [&](int code, const char* m) { h->dropout_call_next = h->neftune_call_next = -1; return h->fail(code, m); };
   if (!ids || !lens || !scratch || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffc0LL) return refuse(SLAM_EINVAL, "forward_unpadded: bad argument");
   const int64_t mmax = (((int64_t)B * T + 63) / 64) * 64;
   if (M_packed <= 0 || (M_packed & 63) || M_packed > mmax) return refuse(SLAM_EINVAL, "M_packed must be a multiple of 64 in (0, B*T rounded up to 64]");
@@ -1152,8 +1181,9 @@ int slam_forward_unpadded(SlamEngine* h, const int64_t* ids, const int64_t* labe
   h->have_fwd = false;
   const UnpadView v = unpad_view(scratch, B, T);
   int rc = unpad_pack(ids, labels, lens, B, T, M_packed, h->d.pad_token_id, v, (hipStream_t)stream);
-  if (rc != 0) { h->dropout_call_next = -1; return rc; }
+  if (rc != 0) { h->dropout_call_next = h->neftune_call_next = -1; return rc; }
   h->dropout_call_next = armed_call;
+  h->neftune_call_next = neft_call;
   return forward_common(h, v.ids, labels ? v.labels : nullptr, v.pos, v.seg_s, v.seg_e, 1, M_packed, num_items, loss_out, logits_out,
                         &v, B, T, stream);
 }
@@ -1313,7 +1343,8 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   hipStream_t st = (hipStream_t)stream;
   const int H = d.hidden, L = d.n_layers, M = B * T;
   h->have_fwd = false;
-  h->fwd_drop = false;  // generation never drops
+  h->fwd_drop = false;  // generation never drops ...
+  h->fwd_neft = false;  // ... and never draws NEFTune noise
   h->kv_ready = false;
   GemmTuneScope tune_scope(&h->gemm_tune);
   // "recompute" = 2 with more layers than slots: the layers share their q|k|v buffers, so each layer's K / V leave inside the loop
@@ -1871,6 +1902,15 @@ int slam_set_label_smoothing(SlamEngine* h, float epsilon) {
   if (!h) return SLAM_EINVAL;
   if (!(epsilon >= 0.f && epsilon < 1.f)) return h->fail(SLAM_EINVAL, "label smoothing epsilon must be in [0, 1)");
   h->label_smoothing = epsilon;
+  return SLAM_OK;
+}
+
+int slam_set_neftune(SlamEngine* h, float alpha, int64_t seed) {
+  if (!h) return SLAM_EINVAL;
+  if (!(alpha >= 0.f) || !__builtin_isfinite(alpha)) return h->fail(SLAM_EINVAL, "neftune alpha must be finite and >= 0");
+  h->neftune_alpha = alpha;
+  h->neftune_seed = (uint64_t)seed;
+  if (alpha == 0.f) h->neftune_call_next = -1;
   return SLAM_OK;
 }
 
@@ -2515,6 +2555,24 @@ int slam_op_layernorm_bwd(const void* dy, const void* x, const void* w, const fl
 int slam_op_embed_pos_fwd(const int64_t* ids, const int64_t* position_ids, const void* E, const void* P, void* out, int64_t* prow,
                           int M, int H, int V, int T, int n_rows_p, slam_stream_t s) {
   return embed_pos_fwd(ids, position_ids, (const bf16_t*)E, (const bf16_t*)P, (bf16_t*)out, prow, M, H, V, T, n_rows_p, (hipStream_t)s);
+}
+int slam_op_embed_fwd(const int64_t* ids, const void* E, void* out, int M, int H, int V, slam_stream_t s) {
+  if (!ids || !E || !out || M <= 0 || H <= 0 || (H & 7) || V <= 0) return SLAM_EINVAL;
+  return embed_fwd(ids, (const bf16_t*)E, (bf16_t*)out, M, H, V, (hipStream_t)s);
+}
+int slam_op_embed_noise_fwd(const int64_t* ids, const int64_t* position_ids, const void* E, const void* P, void* out, int64_t* prow,
+                            int M, int H, int V, int T, int n_rows_p, float s, int64_t seed, int64_t call, int64_t index0,
+                            slam_stream_t stream) {
+  if (!ids || !E || !out || M <= 0 || H <= 0 || (H & 7) || V <= 0 || !(s >= 0.f) || !__builtin_isfinite(s) || call < 0 ||
+      call > 0xffffffffLL || index0 < 0 || (index0 & 7) || (P && (T <= 0 || n_rows_p <= 0)))
+    return SLAM_EINVAL;
+  NeftSite n;
+  n.s = s;
+  n.seed = (uint64_t)seed;
+  n.call = (uint32_t)call;
+  n.index0 = index0;
+  return embed_noise_fwd(ids, position_ids, (const bf16_t*)E, (const bf16_t*)P, (bf16_t*)out, prow, M, H, V, T, n_rows_p, n,
+                         (hipStream_t)stream);
 }
 int slam_op_gemm_nt_relu(const void* X, const void* W, void* act, const void* bias, int M, int N, int K, slam_stream_t s) {
   return gemm_nt_relu((const bf16_t*)X, (const bf16_t*)W, (bf16_t*)act, (const bf16_t*)bias, M, N, K, (hipStream_t)s);

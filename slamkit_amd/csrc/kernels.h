@@ -152,6 +152,12 @@ int embed_fwd(const int64_t* ids, const bf16_t* E, bf16_t* out, int M, int H, in
 // row of every token goes to prow (int64 [M], nullable) for the backward's scatter
 int embed_pos_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const bf16_t* P, bf16_t* out, int64_t* prow, int M, int H,
                   int V, int T, int NP, hipStream_t st);
+// NEFTune (include/slam_engine.h, slam_set_neftune): the gather above with noise, out = bf16(E[ids] (+ P[pos + 2]) + n), n =
+// (2 r16 - 65535) * s with the 16 random bits of (seed, call, site 0x4E454654, index0 + m H + h). P == nullptr: no position
+// table (pos, prow, T and NP are not read). H and index0 multiples of 8, s finite and >= 0.
+struct NeftSite { float s = 0.f; uint64_t seed = 0; uint32_t call = 0; int64_t index0 = 0; };
+int embed_noise_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, const bf16_t* P, bf16_t* out, int64_t* prow, int M, int H,
+                    int V, int T, int NP, const NeftSite& n, hipStream_t st);
 // d *= [act > 0] (n a multiple of 8): the ReLU backward without the fused fc2 dgrad epilogue
 int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st);
 // Residual dropout (OPT): the mask of element (m, n) of a site is a function of (seed, call, site, index0 + m H + n) alone

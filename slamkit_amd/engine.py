@@ -137,6 +137,7 @@ def load_library(path: Optional[str] = None):
         "slam_seq_loglik": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         "slam_scale_loss_rows": (C.c_int, [vp, vp, i32, i32, vp]),
         "slam_set_label_smoothing": (C.c_int, [vp, f32]),
+        "slam_set_neftune": (C.c_int, [vp, f32, i64]),
         "slam_grad_norm": (C.c_int, [vp, f32, vp, vp]),
         "slam_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
         "slam_adamw_step_bf16": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
@@ -227,6 +228,9 @@ def load_library(path: Optional[str] = None):
         "slam_op_sr_round_bf16": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp]),
         "slam_op_dropout_add": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, i64, i64, i32, i64, vp]),
         "slam_op_dropout_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, i64, i64, i32, i64, vp]),
+        "slam_op_embed_fwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_embed_noise_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, i64, i64, i64,
+                                              vp]),
     }
     for name, (res, args) in sig.items():
         if path is not None and not hasattr(lib, name):
@@ -574,6 +578,16 @@ class Engine:
     def arm_dropout(self, call: int):
         """The next forward (only) drops, with this call number."""
         self.set_option("dropout_call_next", int(call))
+
+    # -- NEFTune (slam_set_neftune, option "neftune_call_next") ---------------------------------------------------------------
+    def set_neftune(self, alpha: float, seed: int = 0):
+        """alpha = HF's neftune_noise_alpha (0 = off; EngineError when negative or not finite); seed: 64 bits. Adds no buffer."""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF  # 64 unsigned bits, passed as the int64 with the same bits
+        self._ck(self.lib.slam_set_neftune(self.h, float(alpha), seed - (1 << 64) if seed >= (1 << 63) else seed))
+
+    def arm_neftune(self, call: int):
+        """The next forward (only) draws embedding noise, with this call number."""
+        self.set_option("neftune_call_next", int(call))
 
     # -- step ---------------------------------------------------------------------------------
     def forward(self, ids, labels=None, position_ids=None, seg_start=None, seg_end=None, B=1, T=1,

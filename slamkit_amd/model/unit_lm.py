@@ -518,6 +518,11 @@ class UnitLM(TokenLM):
             self._drop_call = 0
             if self._drop_thr:
                 self.engine.set_dropout(self._drop_thr, self._drop_seed)  # before the workspace is sized: it adds buffers
+            # NEFTune (set_neftune): off until asked for; forward() numbers its armed calls from _neft_call
+            self._neft_alpha = 0.0
+            self._neft_seed = int(seed)
+            self._neft_call = 0
+            self._neft_engine_alpha = 0.0  # what the engine was last given (_arm_neftune)
             self._ensure_workspace(config.max_tokens)
             self._loss_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
             self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
@@ -903,7 +908,7 @@ class UnitLM(TokenLM):
 
     def train(self, mode: bool = True):
         """With `config.dropout` > 0 (OPT) training mode is what turns dropout on: forward() then arms the engine for that
-        call. eval(), log_likelihood, sequence_logps and generate never drop."""
+        call. eval(), log_likelihood, sequence_logps and generate never drop. The same holds for NEFTune's noise (set_neftune)."""
         self.training = mode
         return self
 
@@ -919,6 +924,46 @@ class UnitLM(TokenLM):
             if int(call) < 0:
                 raise ValueError("dropout call number must be >= 0")
             self._drop_call = int(call)
+
+    def set_neftune(self, alpha: Optional[float], seed: Optional[int] = None):
+        """NEFTune (HF `TrainingArguments.neftune_noise_alpha`): uniform noise of magnitude alpha / sqrt(T * H) on the input
+        embeddings of every forward() in train() mode, drawn inside the embedding kernel (include/slam_engine.h,
+        slam_set_neftune). None or 0 switches it off: the launches are then those of a model that never had the option.
+        eval(), log_likelihood, sequence_logps, score_continuations and generate never add noise. `seed`: the generator's 64
+        bits (default: the seed set last, initially the model's)."""
+        alpha = float(alpha or 0.0)
+        if not (alpha >= 0.0 and math.isfinite(alpha)):
+            raise ValueError(f"neftune_noise_alpha must be finite and >= 0, got {alpha}")
+        if seed is not None:
+            self._neft_seed = int(seed)
+        self._neft_alpha = alpha
+        self._neft_engine_alpha = alpha
+        self.engine.set_neftune(alpha, self._neft_seed)
+
+    def set_neftune_state(self, seed: Optional[int] = None, call: Optional[int] = None):
+        """The noise generator's seed (64 bits) and / or the number the next training forward is armed with (it counts up
+        from there, modulo 2^32). The noise is a function of (seed, call, element) alone, so setting both replays a forward's
+        noise exactly; the trainer sets `call` before every micro-batch."""
+        if seed is not None:
+            self._neft_seed = int(seed)
+            self.engine.set_neftune(self._neft_engine_alpha, self._neft_seed)
+        if call is not None:
+            if int(call) < 0:
+                raise ValueError("neftune call number must be >= 0")
+            self._neft_call = int(call)
+
+    def _arm_neftune(self, t_run: int, t_passed: int):
+        """Arm the engine's next forward when training with NEFTune on. HF's magnitude is alpha / sqrt(T * H) with the T of
+        the batch AS PASSED; the engine takes T from the call it runs, so a forward whose token axis was padded up to a
+        multiple of 64 (t_run > t_passed) hands the engine alpha * sqrt(t_run / t_passed) for that call."""
+        if not (self.training and self._neft_alpha > 0.0):
+            return
+        a = self._neft_alpha if t_run == t_passed else self._neft_alpha * math.sqrt(t_run / t_passed)
+        if a != self._neft_engine_alpha:
+            self.engine.set_neftune(a, self._neft_seed)
+            self._neft_engine_alpha = a
+        self.engine.arm_neftune(self._neft_call & 0xFFFFFFFF)
+        self._neft_call += 1
 
     def eval(self):
         return self.train(False)
@@ -1026,6 +1071,7 @@ class UnitLM(TokenLM):
         if self.training and self._drop_thr:  # this forward only: every other entry point runs unarmed, i.e. without dropout
             self.engine.arm_dropout(self._drop_call & 0xFFFFFFFF)
             self._drop_call += 1
+        self._arm_neftune(T, T0)
         self.engine.forward(ids, lab, pos, seg_s, seg_e, B, T,
                             float(num_items_in_batch) if num_items_in_batch else 0.0,
                             self._loss_buf if lab is not None else None, logits)
@@ -1099,6 +1145,7 @@ class UnitLM(TokenLM):
         if self.training and self._drop_thr:  # as forward(): this call only
             self.engine.arm_dropout(self._drop_call & 0xFFFFFFFF)
             self._drop_call += 1
+        self._arm_neftune(T, T)  # the engine takes s from the padded width it is given
         self._run_unpadded(ids, lab, lens, float(num_items_in_batch) if num_items_in_batch else 0.0, logits)
         loss = None
         if lab is not None:

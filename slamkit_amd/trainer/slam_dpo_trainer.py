@@ -56,6 +56,9 @@ class SLAMDPOTrainer(SLAMTrainer):
         if float(getattr(args, "label_smoothing_factor", 0.0) or 0.0) != 0.0:
             raise ValueError("label_smoothing_factor is the language-modelling loss's smoothing (HF LabelSmoother); the DPO loss "
                              "is defined on plain log-likelihoods (TRL's own label_smoothing is another quantity, not implemented)")
+        if float(getattr(args, "neftune_noise_alpha", None) or 0.0) != 0.0:
+            raise ValueError("neftune_noise_alpha: TRL applies NEFTune to the policy's forward; the DPO path here scores "
+                             "sequences through the engine's unarmed forward and does not implement it")
         tok = lambda ds: None if ds is None else [  # noqa: E731
             self.tokenize_row(r, processing_class, args.max_prompt_length, args.max_completion_length) for r in ds]
         super().__init__(model=model, args=args, data_collator=self._collate_pairs, train_dataset=tok(train_dataset),

@@ -26,7 +26,8 @@ import torch.distributed as dist
 
 from .callbacks import TrainerCallback, TrainerControl, TrainerState
 from .dp import GradBucketReducer, ShardedGradReducer, all_reduce_scalar, host_group, seeded_batches, shard_batches, world_info
-from .training_args import SLAMTrainingArguments, check_label_smoothing, check_weight_decay_rule, lr_lambda
+from .training_args import (SLAMTrainingArguments, check_label_smoothing, check_neftune_alpha, check_weight_decay_rule,
+                            lr_lambda)
 
 logger = logging.getLogger(__name__)
 
@@ -149,6 +150,11 @@ class SLAMTrainer:
         self._sets_dropout = hasattr(model, "set_dropout_state")
         if self._sets_dropout:
             model.set_dropout_state(seed=dropout_seed(int(getattr(self.args, "seed", 0) or 0), self.rank))
+        # NEFTune (HF's neftune_noise_alpha): checked here, switched on and off by train() (fields set after construction get
+        # past the arguments' own check)
+        self._neftune = check_neftune_alpha(getattr(self.args, "neftune_noise_alpha", None))
+        if self._neftune and not hasattr(model, "set_neftune"):
+            raise ValueError("neftune_noise_alpha needs a model that draws the noise in its embedding kernel (UnitLM.set_neftune)")
 
     # ---- reference hooks ------------------------------------------------------------------------
     def get_num_tokens(self, labels: torch.Tensor) -> int:
@@ -333,6 +339,8 @@ class SLAMTrainer:
                 self.model.engine.set_option("grad_overwrite_next", 1)
             if self._sets_dropout:  # micro-batch i of optimizer step k draws mask number k * GA + i, whenever it runs
                 self.model.set_dropout_state(call=self.state.global_step * a.gradient_accumulation_steps + i)
+            if self._neftune:  # the same numbering for NEFTune's noise
+                self.model.set_neftune_state(call=self.state.global_step * a.gradient_accumulation_steps + i)
             loss = self.training_step(self.model, mb, num_items_in_batch=n_items, last_micro=(i == len(micro) - 1),
                                       grad_scale=scale)
             # every micro-batch loss is already normalised by the whole step's token count (global, or this rank's
@@ -443,6 +451,18 @@ class SLAMTrainer:
 
     # ---- train ------------------------------------------------------------------------------------------------
     def train(self, resume_from_checkpoint=None):
+        """Trainer.train. `neftune_noise_alpha`: the noise is on from here until this returns - HF's Trainer attaches its
+        embedding hook at the start of train() and removes it at the end - with the rank's seed, so ranks draw different
+        noise; evaluate() inside runs in eval mode and adds none."""
+        if not self._neftune:
+            return self._train(resume_from_checkpoint)
+        self.model.set_neftune(self._neftune, seed=dropout_seed(int(getattr(self.args, "seed", 0) or 0), self.rank))
+        try:
+            return self._train(resume_from_checkpoint)
+        finally:
+            self.model.set_neftune(0.0)
+
+    def _train(self, resume_from_checkpoint=None):
         a = self.args
         max_steps, epochs, updates_per_epoch = self._plan()
         self.state.max_steps = max_steps

@@ -46,6 +46,7 @@ class SLAMTrainingArguments:
     recompute_level: Optional[int] = None          # overrides gradient_checkpointing: 1 = selective (norm outputs and the MLP activation only), 2 = full layer
     padding_free: bool = False                     # HF / TRL's name: right-padded batches (the default collator's, DPO's pairs, evaluation) run as packed segments of their own lengths and skip the pad positions (slam_forward_unpadded; UnitLM.padding_free). True switches the models on; False (the default) leaves a model's own switch alone. Same losses within rounding; OPT's dropout masks follow the packed layout
     label_smoothing_factor: float = 0.0            # HF's field: epsilon of transformers' LabelSmoother, in [0, 1). The training loss, the logged `loss` and `eval_loss` become (1 - eps) * nll + eps * mean_v(-log p_v) over the vocab_size columns, computed inside the engine's loss kernels (UnitLM.forward(label_smoothing=), slam_set_label_smoothing). 0 (the default) is the plain loss, bit for bit. SLAMDPOTrainer refuses a non-zero value (TRL's own label_smoothing is another quantity)
+    neftune_noise_alpha: Optional[float] = None    # HF's field (NEFTune; HF recommends 5 - 15): uniform noise of magnitude alpha / sqrt(T * H) on the input embeddings of the TRAINING forwards, drawn inside the embedding kernel (UnitLM.set_neftune, slam_set_neftune): no launch and no buffer more. SLAMTrainer.train() switches it on at its start and off when it returns, as HF's Trainer attaches and removes its hook; evaluate() adds none. Stateless, keyed on (seed, rank, optimizer step, micro-batch): nothing goes into checkpoints, a resumed run repeats the uninterrupted one. None or 0 (the default): every launch is what it was without the field. SLAMDPOTrainer refuses a non-zero value
     dataloader_num_workers: int = 0                # > 0: one background thread collates up to two optimizer steps ahead into pinned host memory (SLAMTrainer._micro_batches)
     min_token_id_count: Optional[int] = None
     max_token_id_count: Optional[int] = None
@@ -61,6 +62,7 @@ class SLAMTrainingArguments:
     def __post_init__(self):
         check_weight_decay_rule(self.weight_decay_rule)
         check_label_smoothing(self.label_smoothing_factor)
+        check_neftune_alpha(self.neftune_noise_alpha)
         if self.optim_stochastic_rounding and (self.optim_state_dtype or "float32") == "float32":
             raise ValueError("optim_stochastic_rounding needs bf16 optimizer state (optim_state_dtype bfloat16 or "
                              "float32_bf16_moments): with float32 state nothing is rounded")
@@ -93,6 +95,14 @@ def check_label_smoothing(eps) -> float:
     if not 0.0 <= eps < 1.0:
         raise ValueError(f"label_smoothing_factor must be in [0, 1), got {eps}")
     return eps
+
+
+def check_neftune_alpha(alpha) -> float:
+    """neftune_noise_alpha as a float, None meaning 0 (off); finite and >= 0."""
+    alpha = float(alpha or 0.0)
+    if not (alpha >= 0.0 and math.isfinite(alpha)):
+        raise ValueError(f"neftune_noise_alpha must be finite and >= 0 (None or 0: off), got {alpha}")
+    return alpha
 
 
 def lr_lambda(args: SLAMTrainingArguments, step: int, num_training_steps: int) -> float:
