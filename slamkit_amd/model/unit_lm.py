@@ -17,11 +17,13 @@ import math
 import os
 import re
 from dataclasses import dataclass, field
-from typing import Dict, Iterator, List, NamedTuple, Optional, Tuple
+from typing import Dict, Iterator, List, Optional, Tuple
 
 import torch
 
 from .. import engine as E
+from . import generation
+from .generation import GenerateOutput, _constraint_plan, _warp  # noqa: F401 - tests and tools import them from here
 from .token_lm import TokenLM
 
 # Qwen2.5-0.5B body (config/model/slam.yaml:7 base_model_name) - the hub is unreachable from a
@@ -314,172 +316,9 @@ class _EngineLoss(torch.autograd.Function):
         return torch.zeros(1, device=grad_out.device), None, None
 
 
-class GenerateOutput(NamedTuple):
-    """generate(return_logprobs=True): the sequences as without it, and the log-probability of every new token."""
-    sequences: torch.Tensor
-    logprobs: torch.Tensor
-
-
 def _right_padded(mask: torch.Tensor) -> bool:
     m = mask.to(torch.int64)
     return bool((m[:, 1:] <= m[:, :-1]).all())
-
-
-def _warp(scores: torch.Tensor, temperature: float, top_k: int, top_p: float, min_p: float = 0.0, typical_p: float = 1.0,
-          epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0) -> torch.Tensor:
-    """HF's sampling warpers in HF's order: temperature, top-k, top-p, min_p, typical_p, epsilon_cutoff, eta_cutoff (at least
-    one token kept; each is HF's own definition on the full row, on what the warpers before it left finite)."""
-    if temperature != 1.0:
-        scores = scores / temperature
-    if top_k > 0:
-        kth = torch.topk(scores, min(top_k, scores.shape[-1])).values[:, -1:]
-        scores = scores.masked_fill(scores < kth, float("-inf"))
-    if top_p < 1.0:
-        srt, idx = torch.sort(scores, descending=False)
-        cum = srt.softmax(-1).cumsum(-1)
-        drop = cum <= (1 - top_p)
-        drop[:, -1] = False
-        scores = scores.masked_fill(drop.scatter(1, idx, drop), float("-inf"))
-    if min_p > 0.0:  # MinPLogitsWarper: probs < min_p * max prob
-        probs = scores.softmax(-1)
-        scores = scores.masked_fill(probs < min_p * probs.amax(-1, keepdim=True), float("-inf"))
-    if typical_p < 1.0:  # TypicalLogitsWarper: the tokens whose -log p is closest to the entropy, up to the mass
-        logp = scores.log_softmax(-1)
-        ent = -(logp * logp.exp()).nansum(-1, keepdim=True)
-        srt, idx = torch.sort((-logp - ent).abs(), descending=False)
-        cum = scores.gather(-1, idx).softmax(-1).cumsum(-1)
-        last = (cum < typical_p).sum(-1, keepdim=True).clamp_(max=scores.shape[-1] - 1)
-        drop = srt > srt.gather(1, last)
-        drop[:, 0] = False
-        scores = scores.masked_fill(drop.scatter(1, idx, drop), float("-inf"))
-    if epsilon_cutoff > 0.0:  # EpsilonLogitsWarper: probs < epsilon, every top-1 score exempt
-        drop = (scores.softmax(-1) < epsilon_cutoff) & (scores < scores.amax(-1, keepdim=True))
-        scores = scores.masked_fill(drop, float("-inf"))
-    if eta_cutoff > 0.0:  # EtaLogitsWarper: probs < min(epsilon, sqrt(epsilon) exp(-entropy))
-        logp = scores.log_softmax(-1)
-        probs = logp.exp()
-        ent = -(logp * probs).nansum(-1, keepdim=True)
-        eps = torch.tensor(eta_cutoff, dtype=scores.dtype, device=scores.device)
-        eta = torch.min(eps, torch.sqrt(eps) * torch.exp(-ent))
-        drop = (scores.softmax(-1) < eta) & (scores < scores.amax(-1, keepdim=True))
-        scores = scores.masked_fill(drop, float("-inf"))
-    return scores
-
-
-class _ConstraintPlan(NamedTuple):
-    """generate's history-dependent bans, validated on the host (no device): what slam_constrain_scores will be asked for."""
-    ngram: int
-    min_new: int
-    min_length: int
-    begin: List[int]
-    seqs: List[List[int]]   # bad word sequences of two tokens and more
-    single: List[int]       # single-token bad words + suppress_tokens: the vocabulary-wide mask
-    eos: List[int]
-    active: bool            # some step needs the constrain kernel
-
-
-def _constraint_plan(no_repeat_ngram_size, min_new_tokens, min_length, begin_suppress, suppress, bad, eos) -> _ConstraintPlan:
-    def count(v, name):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-            raise ValueError(f"{name} must be an int >= 0 (got {v!r})")
-        return v
-
-    ngram = count(no_repeat_ngram_size, "no_repeat_ngram_size")
-    min_new = count(min_new_tokens, "min_new_tokens")
-    min_len = count(min_length, "min_length")
-    begin = [int(t) for t in begin_suppress]
-    if len(begin) > E.CONSTRAIN_MAX_BEGIN:
-        raise ValueError(f"begin_suppress_tokens: at most {E.CONSTRAIN_MAX_BEGIN} ids (got {len(begin)})")
-    single = [int(t) for t in suppress]
-    seqs = []
-    for w in bad:
-        w = [int(t) for t in w]
-        if len(w) < 1:
-            raise ValueError("bad_words_ids: an entry needs at least one token")
-        if len(w) > E.CONSTRAIN_MAX_SEQ_LEN:
-            raise ValueError(f"bad_words_ids: an entry has at most {E.CONSTRAIN_MAX_SEQ_LEN} tokens (got {len(w)})")
-        if len(w) == 1:
-            single.append(w[0])
-        else:
-            seqs.append(w)
-    if len(seqs) > E.CONSTRAIN_MAX_SEQS:
-        raise ValueError(f"bad_words_ids: at most {E.CONSTRAIN_MAX_SEQS} multi-token entries (got {len(seqs)})")
-    eos = [int(t) for t in eos]
-    if (min_new > 0 or min_len > 0) and len(eos) > 16:
-        raise ValueError(f"min_new_tokens / min_length take at most 16 EOS ids (got {len(eos)})")
-    active = ngram > 0 or bool(seqs) or bool(begin) or (bool(eos) and (min_new > 0 or min_len > 0))
-    return _ConstraintPlan(ngram, min_new, min_len, begin, seqs, single, eos, active)
-
-
-class _Constrainer:
-    """The device side of a _ConstraintPlan for one generate call: the lists, the prompts and the scores buffer. apply() is one
-    slam_constrain_scores launch, or none when the step has nothing to ban."""
-
-    def __init__(self, plan: _ConstraintPlan, ids, prompt_len, t_in: int, nret: int, new, keep_logits: bool, dev):
-        def i32(v):
-            return torch.tensor(v, dtype=torch.int32, device=dev) if len(v) else None
-
-        self.plan, self.ids, self.prompt_len, self.t_in, self.new = plan, ids, prompt_len, t_in, new
-        self.eos, self.begin = i32(plan.eos), i32(plan.begin)
-        self.seq_tokens = i32([t for w in plan.seqs for t in w])
-        off = [0]
-        for w in plan.seqs:
-            off.append(off[-1] + len(w))
-        self.seq_offsets = i32(off) if plan.seqs else None
-        self.desc = E.SlamConstrainDesc(step=0, no_repeat_ngram=plan.ngram, n_per_prompt=nret, prompt_stride=0, ban_eos=0,
-                                        n_eos=len(plan.eos), n_begin=len(plan.begin), n_seqs=len(plan.seqs),
-                                        n_seq_tokens=off[-1])
-        self.keep_logits = keep_logits  # slam_token_logprobs reads the raw logits: the bans go into a buffer of their own
-        self.scores = None
-
-    def apply(self, logits, step: int, done):
-        p = self.plan
-        ban_eos = bool(p.eos) and (step < p.min_new or self.t_in + step < p.min_length)
-        if not (p.ngram > 0 or p.seqs or ban_eos or (step == 0 and p.begin)):
-            return logits
-        if self.keep_logits and self.scores is None:
-            self.scores = torch.empty_like(logits)
-        out = self.scores if self.keep_logits else logits
-        self.desc.step = step
-        self.desc.ban_eos = int(ban_eos)
-        E.constrain_scores(logits, out, self.desc, self.ids, self.prompt_len, self.new, done, self.eos, self.begin,
-                           self.seq_tokens, self.seq_offsets)
-        return out
-
-
-def _compact_rows(seq: torch.Tensor, attention_mask, pad: int, what: str):
-    """Every row's real tokens moved to the left (stable: their order is kept), pad behind them: (ids [B, T] int64 contiguous,
-    lens int32 [B], T = the longest row). seq is on the device already; attention_mask None = every token is real."""
-    dev = seq.device
-    mask = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones_like(seq, dtype=torch.bool)
-    order = torch.sort((~mask).to(torch.int8), dim=1, stable=True).indices
-    lens = mask.sum(1).to(torch.int32)
-    T = int(lens.max())
-    if int(lens.min()) < 1:
-        raise ValueError(f"every {what} row needs at least one unmasked token")
-    ids = seq.gather(1, order)[:, :T]
-    ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, pad)).contiguous()
-    return ids, lens, T
-
-
-class _Guidance:
-    """Classifier-free guidance of one generate call. The logits hold n conditional rows, then their n unconditional twins;
-    apply() is slam_cfg_scores into a scores buffer of n rows, mirror() copies the n chosen tokens behind themselves so that
-    the decode step feeds both branches the same token."""
-
-    def __init__(self, scale: float, n: int, vocab: int, dev):
-        self.scale, self.n = float(scale), n
-        self.scores = torch.empty(n, vocab, dtype=torch.float32, device=dev)
-        self.ws = torch.empty(E.cfg_workspace_bytes(n, vocab), dtype=torch.uint8, device=dev)
-        self.next = torch.empty(2 * n, dtype=torch.int64, device=dev)  # [:n] is where the token choice is written
-
-    def apply(self, logits):
-        E.cfg_scores(logits, self.scale, self.scores, self.ws)
-        return self.scores
-
-    def mirror(self):
-        E.cfg_mirror_tokens(self.next)
-        return self.next
 
 
 class UnitLM(TokenLM):
@@ -1253,6 +1092,11 @@ class UnitLM(TokenLM):
         self.engine.backward(grad_scale, kw.get("bucket_layers", 0), kw.get("bucket_cb"))
         self._grads_in_bf16 = False
 
+    # ---- KV-cached generation: generation.py ------------------------------------------------------
+    _assist_trace = None      # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after)
+    _lookup_trace = None      # the same for prompt lookup, and n_prop behind them
+    last_assist_stats = None  # {"rounds", "proposed", "accepted", "tokens"} of the last speculative generate
+
     @torch.no_grad()
     def generate(self, inputs: Optional[torch.Tensor] = None, generation_config=None, max_new_tokens: Optional[int] = None,
                  do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
@@ -1270,785 +1114,25 @@ class UnitLM(TokenLM):
                  eta_cutoff: Optional[float] = None, guidance_scale: Optional[float] = None,
                  negative_prompt_ids: Optional[torch.Tensor] = None,
                  negative_prompt_attention_mask: Optional[torch.Tensor] = None, **kwargs):
-        """HF `generate` on the engine's KV cache (unit_lm.py:196-198; the reference calls
-        `generate(input_ids=, attention_mask=, bad_words_ids=[[t], ...], temperature=, top_k=, max_new_tokens=)` with
-        left-padded prompts). Prompts of either padding side are compacted to per-row lengths (positions start at each row's
-        first real token, HF's cumsum(mask) - 1), prefilled once, then decoded one token per step (slam_decode_step).
-        Logits are fp32; bad words get -inf, then temperature, top_k and top_p (sampling only). Finished rows are padded
-        with pad_token_id; generation stops when every row has emitted eos_token_id. Explicit arguments override
-        `generation_config`. Returns [B, T_in + n_new] int64: the prompt as passed, padding included, then the new tokens.
-
-        `sampler` selects who picks the token. None / "torch": the torch ops above (torch.multinomial with one generator for
-        the batch: a row's continuation depends on the batch around it). "engine": slam_sample_tokens (include/slam_engine.h)
-        picks it on the device and writes it where the next decode step reads it - no torch op between two engine calls - with a
-        stateless Philox draw keyed on (seed, row id, step): a row's continuation depends on its prompt, the seed and its row id
-        alone, whatever the batch. `sample_ids` (int64 [B], default 0 .. B-1) are those row ids: a sharded evaluation passes the
-        examples' global indices. The engine sampler needs 1 <= top_k <= 256 and temperature > 0 when sampling, top_p in
-        (0, 1] and at most 16 EOS ids (ValueError otherwise); a tie at the k-th score goes to the lower id where HF keeps all
-        ties. seed=None draws a 62-bit seed from torch's default CPU generator.
-
-        `num_return_sequences` = n (sampling only; HF refuses greedy n-best too) returns [B n, T_in + n_new], row b n + i the
-        i-th sample of prompt b (HF's order), the prompt part repeated as passed. The B prompts are prefilled ONCE, the cache
-        rows fanned out to B n rows (slam_kv_repeat) and B n rows decoded: the workspace is max(B T, 2 B n) tokens, not B n T.
-        With sampler="engine" `sample_ids` has shape [B n] (default 0 .. B n - 1): row b n + i draws what row b n + i of a call
-        on the prompts repeated n times draws; the torch sampler draws one multinomial over B n rows. The tokens of the two
-        calls are equal whenever their logits are equal bit for bit, which holds when the longest prompt (the row stride of
-        the prefill) is a multiple of 128 tokens; at another length the prefill's attention tiles fall differently on the
-        rows of the two batches, the logits differ by rounding (within the model tolerance) and a draw that lands on a
-        boundary may differ.
-
-        `return_logprobs=True` returns GenerateOutput(sequences, logprobs): logprobs fp32 [B n, n_new], the model's own
-        log-softmax (raw fp32 logits: no banned mask, temperature or truncation) of every new token, its EOS included, 0.0
-        behind a row's EOS; trimmed with the sequences. Both samplers get it from slam_token_logprobs.
-
-        `prefill_chunk` = C (an int >= 1; None = the one-shot prefill) prefills the prompts C columns at a time: columns
-        [0, min(T, C)) by slam_prefill, every further block of C columns (the last one exactly as wide as what is left)
-        appended to the cache by slam_extend, rows that have already ended taking no part. The fan-out, both samplers,
-        `num_return_sequences` and `return_logprobs` follow as before. The workspace is max(B min(T, C), 2 B n) tokens instead
-        of max(B T, 2 B n): the chunk, not the prompt length, sets the activation memory. The chunks' attention runs in another
-        kernel than the one-shot prefill's, so the logits differ from it by rounding only (within the model tolerance); a
-        token chosen at a near-tie may differ.
-
-        Bans that depend on a row's own history, as HF's logits processors compute them, applied to the fp32 logits before
-        everything else by one HIP launch per step (slam_constrain_scores, include/slam_engine.h) under both samplers:
-        `no_repeat_ngram_size` = n (no n-gram of a row occurs twice; 0 = off), `bad_words_ids` entries of any length >= 1 (a
-        multi-token entry bans its last token behind its prefix; at most 256 such entries of at most 16 tokens, ValueError
-        above), `min_new_tokens` and `min_length` (no EOS id while fewer than min_new_tokens new tokens exist, or while the
-        prompt width as passed plus the new tokens is below min_length), `begin_suppress_tokens` (banned for the first new token,
-        at most 256 ids) and `suppress_tokens` (banned at every step, merged with the single-token bad words). A row's history
-        is its REAL tokens: the prompt without its padding, then its new tokens. HF's windows run over input_ids as passed,
-        left-pad ids included; the two agree unless a window contains a pad id. `return_logprobs` still returns the raw-logit
-        log-probs: the bans are then written into a scores buffer of their own, which only the token choice reads. With every
-        one of these options off, no launch is added and the output is what it was without them.
-
-        `assistant_model` = a smaller UnitLM over the same unit vocabulary (HF's assisted generation, draft-model speculative
-        decoding). Per round the draft proposes `num_assistant_tokens` = K tokens per row (an int 1 .. 15, default 4; constant:
-        HF's heuristic schedule is not implemented), the target scores the pending token and the K proposals in one chunk
-        (slam_extend_logits) and samples its own token at every chunk position, and slam_spec_accept keeps the target's tokens
-        up to and including the first one the draft did not propose - 1 .. K + 1 tokens per row and round for one stream of the
-        target's weights. Both models draw with the engine sampler's stateless draw of (seed, row id, step), so token s of row
-        r is sample(the target's logits after the prefix; seed, r, s) whatever the draft proposed: the output does not depend
-        on the draft, on K or on whether a draft was used, up to the rounding between the chunk attention and the decode-step
-        attention (the caveat of `prefill_chunk`). An assistant implies the engine sampler: greedy works under sampler=None
-        too, do_sample=True needs sampler="engine". Rejected tokens are rolled back by lowering the rows' cached lengths
-        (slam_kv_rewind). One host synchronisation per round (the read-back of five counters), none per token;
-        `self.last_assist_stats` = {"rounds", "proposed", "accepted", "tokens"} afterwards. Refused (ValueError): a draft that
-        is not a UnitLM, is OPT, is this model, sits on another device or has another vocab_size; num_return_sequences > 1;
-        return_logprobs; the history-dependent bans (no_repeat_ngram_size, multi-token bad words, min_new_tokens / min_length,
-        begin_suppress_tokens) - single-token bad words and suppress_tokens work. With assistant_model=None generate is what
-        it was, launch for launch.
-
-        `prompt_lookup_num_tokens` = K (an int 1 .. 15; HF's prompt-lookup decoding, PromptLookupCandidateGenerator) is assisted
-        generation without a second model: per round one integer kernel (slam_ngram_propose) looks up the row's own last
-        n-gram - n = `max_matching_ngram_size` (an int 1 .. 16, default 2) down to 1, the longest n with an earlier occurrence,
-        the earliest occurrence of that n - and proposes up to K of the tokens that followed it, cut in front of an EOS id. The
-        target then verifies all K + 1 chunk columns of every live row, columns without a proposal holding pad_token_id, and
-        slam_spec_accept keeps its tokens as above: every emitted token is the target's own draw, so the output does not
-        depend on K, on n or on whether lookup is used (same rounding caveat), and sampling yields the target's distribution.
-        Up to 1024 rows; both arguments are also read from `generation_config`. `self.last_assist_stats["proposed"]` counts
-        the tokens actually proposed (not rows x K). Refused (ValueError): together with assistant_model;
-        max_matching_ngram_size without prompt_lookup_num_tokens; K or n out of range; and the assistant's list
-        (num_return_sequences > 1, return_logprobs, history-dependent bans, do_sample without sampler="engine"). With both
-        arguments absent generate is what it was, launch for launch.
-
-        `min_p`, `typical_p`, `epsilon_cutoff`, `eta_cutoff` (sampling only; also read from `generation_config`) are the
-        second half of HF's warper chain, applied in HF's order behind temperature, top_k and top_p: min_p in [0, 1] (0 off)
-        drops tokens below min_p times the top probability; typical_p in (0, 1] (1 off) keeps the tokens whose -log p is
-        closest to the entropy up to that mass; epsilon_cutoff in [0, 1) (0 off) drops probabilities below it; eta_cutoff in
-        [0, 1) (0 off) drops those below min(eps, sqrt(eps) exp(-entropy)); ValueError outside these ranges. Each warper
-        renormalises what the ones before it kept and keeps at least one token. The torch sampler applies HF's definitions
-        to the full row, so top_k=0 works there. The engine sampler applies them to the ranked top-k candidates inside the
-        sampling kernel (slam_sample_tokens_warped: no further launch, no further random word, still no torch op between two
-        engine calls), which is HF's chain exactly when 1 <= top_k <= 256 is part of the request - it has to be under this
-        sampler. Two deviations from HF: a tie at the k-th score goes to the lower id (HF keeps every tie), and tokens with
-        equal |-log p - entropy| are ordered by rank, (score descending, id ascending), where torch.sort leaves their order
-        open. Assisted and prompt-lookup decoding verify with the same chain (the draft proposes with it too), so their
-        tokens stay the target's own draws. Greedy decoding ignores the four, as HF does. With all four absent or off
-        generate calls what it called before, launch for launch.
-
-        `guidance_scale` = g (a finite float; also read from `generation_config`) other than 1 turns on classifier-free
-        guidance, HF's UnbatchedClassifierFreeGuidanceLogitsProcessor: the scores become g (a - u) + u, a the log-softmax of
-        the row's logits and u that of an unconditional twin that reads `negative_prompt_ids` [B, T_neg] (with
-        `negative_prompt_attention_mask`, any padding side, compacted like the prompts) or, without them, the row's last real
-        prompt token, followed by the same new tokens. HF runs the twin as a second forward per step; here it rides in the same
-        decode batch. One prefill covers 2 B rows, the B prompts and then the B unconditional prompts, right-padded to
-        max(T, T_neg); `num_return_sequences` = n fans all of them out, rows [0, B n) conditional in HF's order and rows
-        [B n, 2 B n) their twins; the cache holds 2 B n rows of roundup(max(T, T_neg) + max_new_tokens, 64) and the workspace
-        max(2 B min(max(T, T_neg), prefill_chunk), 4 B n) tokens. Per step, in HF's processor order (guidance first):
-        slam_cfg_scores (include/slam_engine.h) from the 2 B n logits rows into B n rows of scores, the history bans in place
-        on those, the single-token mask and the token choice over the B n rows (`sample_ids` keeps B n entries),
-        slam_token_logprobs on the raw conditional rows for `return_logprobs` (the model's own log-softmax, as above),
-        slam_cfg_mirror_tokens, and the decode step over 2 B n rows. Both samplers; the engine sampler still has no torch op
-        between two engine calls. Deviations from HF: a right-padded prompt's default unconditional token is its last REAL
-        token (HF takes the last column, a pad); every branch's real tokens start at position 0 (HF runs the unconditional
-        branch without position_ids, so a padded negative prompt counts its pads as positions; unpadded ones agree); where HF
-        would produce NaN (a -inf on either side) the header's rules apply. ValueError: a non-finite guidance_scale; negative
-        prompts (or their mask) while guidance is off - HF ignores them silently -, with another batch size than B or with an
-        empty row; max(T, T_neg) + max_new_tokens above max_tokens; guidance together with assistant_model or
-        prompt_lookup_num_tokens (the verify pass would need guided chunk scores). With guidance_scale absent or 1 generate
-        calls what it called before, launch for launch."""
-        if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
-            raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
-        if self.config.is_opt:
-            raise ValueError("generate is not implemented for OPT models (the engine's KV-cached decode covers Qwen2 only)")
-        gc = generation_config
-
-        def pick(v, name, default):
-            if v is not None:
-                return v
-            g = getattr(gc, name, None) if gc is not None else None
-            return g if g is not None else default
-
-        num_beams = pick(kwargs.pop("num_beams", None), "num_beams", 1)
-        rep = pick(kwargs.pop("repetition_penalty", None), "repetition_penalty", 1.0)
-        if num_beams != 1:
-            raise ValueError("beam search is not supported (num_beams must be 1)")
-        if rep != 1.0:
-            raise ValueError("repetition_penalty is not supported (must be 1.0)")
-        max_new_tokens = int(pick(max_new_tokens, "max_new_tokens", 32))
-        do_sample = bool(pick(do_sample, "do_sample", False))
-        temperature = float(pick(temperature, "temperature", 1.0))
-        top_k = int(pick(top_k, "top_k", 0) or 0)
-        top_p = float(pick(top_p, "top_p", 1.0))
-        min_p = float(pick(min_p, "min_p", 0.0))
-        typical_p = float(pick(typical_p, "typical_p", 1.0))
-        epsilon_cutoff = float(pick(epsilon_cutoff, "epsilon_cutoff", 0.0))
-        eta_cutoff = float(pick(eta_cutoff, "eta_cutoff", 0.0))
-        if not 0.0 <= min_p <= 1.0:
-            raise ValueError(f"min_p must be in [0, 1] (got {min_p})")
-        if not 0.0 < typical_p <= 1.0:
-            raise ValueError(f"typical_p must be in (0, 1] (got {typical_p})")
-        for name, v in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
-            if not 0.0 <= v < 1.0:
-                raise ValueError(f"{name} must be in [0, 1) (got {v})")
-        late = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
-        # the engine sampler's description of them: None (the plain entry points) unless one is on and tokens are sampled
-        warp = E.SlamWarpDesc(**late)
-        warp = warp if do_sample and warp.active else None
-        eos = pick(eos_token_id, "eos_token_id", self.config.eos_token_id)
-        eos = [] if eos is None else ([int(eos)] if isinstance(eos, int) else [int(e) for e in eos])
-        pad = pick(pad_token_id, "pad_token_id", self.config.pad_token_id)
-        if pad is None:
-            pad = eos[0] if eos else 0
-        plan = _constraint_plan(pick(no_repeat_ngram_size, "no_repeat_ngram_size", 0), pick(min_new_tokens, "min_new_tokens", 0),
-                                pick(min_length, "min_length", 0), pick(begin_suppress_tokens, "begin_suppress_tokens", None) or [],
-                                pick(suppress_tokens, "suppress_tokens", None) or [],
-                                pick(bad_words_ids, "bad_words_ids", None) or [], eos)
-        bad = [[t] for t in plan.single]  # the vocabulary-wide mask; the history-dependent bans are plan's
-        if inputs is None:
-            inputs = input_ids
-        if inputs is None or inputs.dim() != 2:
-            raise ValueError("generate needs input_ids [B, T]")
-        nret = int(pick(num_return_sequences, "num_return_sequences", 1))
-        if nret < 1:
-            raise ValueError(f"num_return_sequences must be at least 1 (got {nret})")
-        if nret > 1 and not do_sample:
-            raise ValueError("num_return_sequences > 1 needs do_sample=True (greedy continuations would all be equal)")
-        if max_new_tokens <= 0:
-            seq = inputs.to(self.device, torch.int64)
-            seq = seq.repeat_interleave(nret, 0) if nret > 1 else seq
-            return GenerateOutput(seq, seq.new_zeros(seq.shape[0], 0, dtype=torch.float32)) if return_logprobs else seq
-        if kwargs:
-            raise TypeError(f"generate got unsupported arguments {sorted(kwargs)}")
-        if sampler not in (None, "torch", "engine"):
-            raise ValueError(f"sampler must be None, 'torch' or 'engine', not {sampler!r}")
-        assist_k = None
-        lookup_k = pick(prompt_lookup_num_tokens, "prompt_lookup_num_tokens", None)
-        lookup_n = pick(max_matching_ngram_size, "max_matching_ngram_size", None)
-        guidance_scale = pick(guidance_scale, "guidance_scale", None)
-        guided = False
-        if guidance_scale is not None:
-            guidance_scale = float(guidance_scale)
-            if not math.isfinite(guidance_scale):
-                raise ValueError(f"guidance_scale must be finite (got {guidance_scale})")
-            guided = guidance_scale != 1.0
-        if not guided and (negative_prompt_ids is not None or negative_prompt_attention_mask is not None):
-            raise ValueError("negative_prompt_ids / negative_prompt_attention_mask need a guidance_scale other than 1")
-        if guided and negative_prompt_ids is None and negative_prompt_attention_mask is not None:
-            raise ValueError("negative_prompt_attention_mask needs negative_prompt_ids")
-        if guided and (assistant_model is not None or lookup_k is not None):
-            raise ValueError("guidance_scale does not combine with assistant_model or prompt_lookup_num_tokens "
-                             "(the verify pass would need guided chunk scores)")
-        if lookup_k is not None:
-            if assistant_model is not None:
-                raise ValueError("prompt_lookup_num_tokens and assistant_model exclude each other: one source of proposals")
-            lookup_n = self._check_lookup(lookup_k, lookup_n, nret, return_logprobs, plan, do_sample, sampler)
-        elif lookup_n is not None:
-            raise ValueError("max_matching_ngram_size needs prompt_lookup_num_tokens")
-        if assistant_model is not None:
-            assist_k = self._check_assistant(assistant_model, num_assistant_tokens, nret, return_logprobs, plan, do_sample, sampler)
-        elif num_assistant_tokens is not None:
-            raise ValueError("num_assistant_tokens needs an assistant_model")
-        on_device = sampler == "engine" or assist_k is not None or lookup_k is not None
-        if on_device:
-            if do_sample and not 1 <= top_k <= 256:
-                raise ValueError(f"sampler='engine' samples with 1 <= top_k <= 256 (got top_k={top_k})")
-            if do_sample and not temperature > 0:
-                raise ValueError(f"sampler='engine' needs temperature > 0 (got {temperature})")
-            if do_sample and not 0 < top_p <= 1:
-                raise ValueError(f"sampler='engine' needs 0 < top_p <= 1 (got {top_p})")
-            if len(eos) > 16:
-                raise ValueError(f"sampler='engine' takes at most 16 EOS ids (got {len(eos)})")
-        elif sample_ids is not None:
-            raise ValueError("sample_ids are the row ids of sampler='engine'; the torch sampler has none")
-        dev = self.device
-        seq_in = inputs.to(dev, torch.int64)
-        B, T_in = seq_in.shape
-        BN = B * nret  # rows decoded
-        ids, lens, T = _compact_rows(seq_in, attention_mask, int(pad), "prompt")
-        cfg = None
-        if guided:
-            # the unconditional prompts: the negative prompts, or each row's last real token (HF's input_ids[:, -1:])
-            if negative_prompt_ids is not None:
-                neg = negative_prompt_ids.to(dev, torch.int64)
-                if neg.dim() != 2 or neg.shape[0] != B:
-                    raise ValueError(f"negative_prompt_ids must be [{B}, T_neg] (got {list(neg.shape)})")
-                if negative_prompt_attention_mask is not None and negative_prompt_attention_mask.shape != neg.shape:
-                    raise ValueError("negative_prompt_attention_mask must have the shape of negative_prompt_ids")
-                nids, nlens, Tn = _compact_rows(neg, negative_prompt_attention_mask, int(pad), "negative prompt")
-            else:
-                nids, nlens, Tn = ids.gather(1, (lens.long() - 1)[:, None]), torch.ones_like(lens), 1
-            # one batch of 2 B rows, right-padded to the longer width: the B prompts, then their B unconditional twins
-            both = torch.full((2 * B, max(T, Tn)), int(pad), dtype=torch.int64, device=dev)
-            both[:B, :T] = ids
-            both[B:, :Tn] = nids
-            ids, lens, T = both, torch.cat([lens, nlens]), max(T, Tn)
-        if T + max_new_tokens > self.config.max_tokens:
-            raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds max_tokens {self.config.max_tokens}")
-        if guided:
-            cfg = _Guidance(guidance_scale, BN, self.config.vocab_size, dev)
-        if assist_k is not None or lookup_k is not None:
-            if assist_k is not None:
-                new, n = self._generate_assisted(assistant_model, assist_k, ids, lens, T, max_new_tokens, bad, eos, int(pad),
-                                                 do_sample, top_k, temperature, top_p, seed, sample_ids, prefill_chunk, warp)
-            else:
-                new, n = self._generate_lookup(lookup_k, lookup_n, ids, lens, T, max_new_tokens, bad, eos, int(pad), do_sample,
-                                               top_k, temperature, top_p, seed, sample_ids, prefill_chunk, warp)
-            if eos and n > 1:  # the plain path's trim: stop right behind the step on which the last row finished
-                all_done = (torch.isin(new, torch.tensor(eos, dtype=torch.long, device=dev)).cumsum(1) > 0).all(0)
-                if bool(all_done.any()):
-                    new = new[:, :int(all_done.nonzero()[0]) + 1]
-            return torch.cat([seq_in, new], 1)
-        cap = -(-(T + max_new_tokens) // 64) * 64
-        # rows prefilled and rows in the cache: under guidance the conditional rows, then as many unconditional ones
-        P, R = (B, BN) if cfg is None else (2 * B, 2 * BN)
-        self._ensure_workspace(max(P * (T if prefill_chunk is None else min(T, prefill_chunk)), 2 * R))
-        nbytes = self.engine.kv_cache_bytes(R, cap)
-        raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        off = (-raw.data_ptr()) % 256
-        self.engine.bind_kv_cache(raw[off:off + nbytes], R, cap)
-        V = self.config.vocab_size
-        logits = torch.empty(R, V, dtype=torch.float32, device=dev)
-        eos_t = torch.tensor(eos, dtype=torch.long, device=dev) if eos else None
-        if nret > 1:  # the prefilled rows first; slam_kv_repeat fills the rest
-            lens = torch.cat([lens, torch.zeros(R - P, dtype=torch.int32, device=dev)])
-        self._hold = (ids, lens)
-        new = torch.empty(BN, max_new_tokens, dtype=torch.int64, device=dev)
-        lp = None
-        if return_logprobs:  # lp[:, k] of step k, the rows' "EOS already emitted" flags, the reduction's workspace
-            lp = (torch.empty(BN, max_new_tokens, dtype=torch.float32, device=dev), torch.zeros(BN, dtype=torch.uint8, device=dev),
-                  torch.empty(E.token_logprobs_workspace_bytes(BN, V), dtype=torch.uint8, device=dev))
-        n = 0
-        # prompt_len: a copy, because slam_decode_step advances lens
-        # under guidance the bans edit the guided scores in place: the raw logits stay whole for the log-probs anyway
-        cons = None
-        if plan.active:
-            cons = _Constrainer(plan, ids[:B], lens[:B].clone(), T_in, nret, new, lp is not None and cfg is None, dev)
-        if on_device:
-            n = self._sample_on_device(logits, new, ids, lens, T, bad, eos, int(pad), do_sample, top_k, temperature, top_p,
-                                       seed, sample_ids, nret, lp, prefill_chunk, cons, warp, cfg)
-        else:
-            bad_idx = torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev) if bad else None
-            g = None
-            if do_sample and seed is not None:
-                g = torch.Generator(device=dev)
-                g.manual_seed(int(seed))
-            self._prefill(ids, lens, P, T, logits, prefill_chunk)
-            if nret > 1:
-                self.engine.kv_repeat(nret, lens, logits)
-            done = torch.zeros(BN, dtype=torch.bool, device=dev)
-            for step in range(max_new_tokens):
-                scores = logits if cfg is None else cfg.apply(logits)
-                if cons is not None:
-                    scores = cons.apply(scores, step, done.view(torch.uint8))
-                if bad_idx is not None:
-                    scores = scores.index_fill(1, bad_idx, float("-inf"))
-                if do_sample:
-                    scores = _warp(scores, temperature, top_k, top_p, **late)
-                    nxt = torch.multinomial(torch.softmax(scores, -1), 1, generator=g)[:, 0]
-                else:
-                    nxt = scores.argmax(-1)
-                nxt = torch.where(done, torch.full_like(nxt, int(pad)), nxt)
-                new[:, step] = nxt
-                n = step + 1
-                if eos_t is not None:
-                    done |= torch.isin(nxt, eos_t)
-                if lp is not None:
-                    E.token_logprobs(logits[:BN], nxt.contiguous(), lp[0], step, lp[2], done.view(torch.uint8), lp[1])
-                if eos_t is not None:
-                    if (step % 16 == 15 or step + 1 == max_new_tokens) and bool(done.all()):
-                        break
-                if step + 1 < max_new_tokens:
-                    if cfg is None:
-                        self.engine.decode_step(nxt.contiguous(), lens, BN, logits)
-                    else:
-                        cfg.next[:BN] = nxt
-                        self.engine.decode_step(cfg.mirror(), lens, R, logits)
-        new = new[:, :n]
-        if eos_t is not None and n > 1:
-            # HF stops right after the step on which the last row finished: drop the all-pad columns behind it
-            fin = torch.isin(new, eos_t).cumsum(1) > 0
-            all_done = fin.all(0)
-            if bool(all_done.any()):
-                n = int(all_done.nonzero()[0]) + 1
-                new = new[:, :n]
-        seq = torch.cat([seq_in.repeat_interleave(nret, 0) if nret > 1 else seq_in, new], 1)
-        return GenerateOutput(seq, lp[0][:, :n].contiguous()) if lp is not None else seq
+        """HF `generate` on the engine's KV cache: [B, T_in + n_new] int64, the prompt as passed and then the new tokens, or
+        GenerateOutput(sequences, logprobs) under return_logprobs. Explicit arguments override `generation_config`; any other
+        keyword is a TypeError. generation.py has every argument's contract. Prompts: inputs / input_ids, attention_mask,
+        eos_token_id, pad_token_id. Length: max_new_tokens, min_new_tokens, min_length. Sampling: do_sample, temperature,
+        top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, seed, sampler, sample_ids. Bans: bad_words_ids,
+        suppress_tokens, begin_suppress_tokens, no_repeat_ngram_size. Outputs: num_return_sequences, return_logprobs. Prefill:
+        prefill_chunk. Speculative: assistant_model, num_assistant_tokens, prompt_lookup_num_tokens, max_matching_ngram_size.
+        Guidance: guidance_scale, negative_prompt_ids, negative_prompt_attention_mask."""
+        return generation.generate(self, generation_config, kwargs, dict(locals()))  # stays the first statement: the arguments
 
     @torch.no_grad()
     def score_continuations(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, continuations=None,
                             continuation_lengths=None, num_per_prompt: int = 1, score_chunk: Optional[int] = None,
                             prefill_chunk: Optional[int] = None, return_argmax: bool = False,
                             ignore_tokens: Optional[List[int]] = None):
-        """This model's log-probs of given continuations of the prompts, through the KV cache: the scoring half of
-        generate(num_return_sequences=n, return_logprobs=True). input_ids [B, T_in] (+ attention_mask, any padding side);
-        continuations int64 [B n, T_c], right-padded, rows b n .. b n + n - 1 continuing prompt b (generate's order:
-        `out[:, T_in:]` feeds straight in); continuation_lengths [B n] (0 .. T_c real tokens per row; default T_c; 0 is legal).
-        Returns fp32 [B n, T_c]: the log-softmax (fp32 scores, never rounded to bf16) of every continuation token given the
-        prompt and the tokens before it, 0.0 at pads. return_argmax=True returns (logprobs, argmax): argmax int64 [B n, T_c], the
-        model's greedy choice FOR continuation position t (position t is accepted by a verifier iff it equals argmax[:, t]),
-        -1 at pads.
-
-        The prompts are compacted and prefilled ONCE (in chunks of `prefill_chunk` columns if given), the cache fanned out
-        to B n rows (slam_kv_repeat), and the continuations appended `score_chunk` columns at a time by slam_extend_score
-        (None = one block): a block's first column is slam_token_logprobs on the logits the rows held before it (the prefill's,
-        then the previous block's last-token logits), every other column comes from the fused head. The workspace is
-        max(B min(T, prefill_chunk), B n score_chunk, 2 B n) tokens, and no [B n, T + T_c] batch is formed. Inside the loop
-        the engine calls follow each other with no torch op between them (every block's operands are built before it).
-        `ignore_tokens` sets the logit mask (those columns count as -inf) for the call and clears it afterwards. Known
-        exception to the no-torch-op rule: with `ignore_tokens`, one in-place fill of those columns of the last-token logits
-        follows each block, because slam_token_logprobs reads raw logits and takes no mask."""
-        n = num_per_prompt
-        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
-            raise ValueError(f"num_per_prompt must be an int >= 1 (got {n!r})")
-        for name, v in (("score_chunk", score_chunk), ("prefill_chunk", prefill_chunk)):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
-                raise ValueError(f"{name} must be None or an int >= 1 (got {v!r})")
-        if input_ids is None or input_ids.dim() != 2:
-            raise ValueError("score_continuations needs input_ids [B, T]")
-        if continuations is None or continuations.dim() != 2:
-            raise ValueError("score_continuations needs continuations [B * num_per_prompt, T_c]")
-        B, BN, Tc = input_ids.shape[0], input_ids.shape[0] * n, continuations.shape[1]
-        if continuations.shape[0] != BN:
-            raise ValueError(f"continuations has {continuations.shape[0]} rows; {B} prompts x num_per_prompt {n} need {BN}")
-        if continuation_lengths is not None and tuple(continuation_lengths.shape) != (BN,):
-            raise ValueError(f"continuation_lengths must have shape [{BN}], got {list(continuation_lengths.shape)}")
-        if self.config.is_opt:
-            raise ValueError("score_continuations is not implemented for OPT models (the engine's KV cache covers Qwen2 only)")
-        dev = self.device
-        seq_in = input_ids.to(dev, torch.int64)
-        cont = continuations.to(dev, torch.int64)
-        clens = (torch.full((BN,), Tc, dtype=torch.int32, device=dev) if continuation_lengths is None
-                 else continuation_lengths.to(dev, torch.int32))
-        if continuation_lengths is not None and BN and (int(clens.min()) < 0 or int(clens.max()) > Tc):
-            raise ValueError(f"continuation_lengths must lie in [0, {Tc}]")
-        if Tc == 0:
-            z = torch.zeros(BN, 0, dtype=torch.float32, device=dev)
-            return (z, torch.zeros(BN, 0, dtype=torch.int64, device=dev)) if return_argmax else z
-        mask = (attention_mask.to(dev) != 0) if attention_mask is not None else torch.ones_like(seq_in, dtype=torch.bool)
-        order = torch.sort((~mask).to(torch.int8), dim=1, stable=True).indices  # real tokens to the left, as generate does
-        lens = mask.sum(1).to(torch.int32)
-        T = int(lens.max())
-        if int(lens.min()) < 1:
-            raise ValueError("every prompt row needs at least one unmasked token")
-        pad = self.config.pad_token_id if self.config.pad_token_id is not None else 0
-        ids = seq_in.gather(1, order)[:, :T]
-        ids = torch.where(torch.arange(T, device=dev)[None] < lens[:, None], ids, torch.full_like(ids, int(pad))).contiguous()
-        if T + Tc > self.config.max_tokens:
-            raise ValueError(f"prompt length {T} + continuation length {Tc} exceeds max_tokens {self.config.max_tokens}")
-        C = Tc if score_chunk is None else min(score_chunk, Tc)
-        cap = -(-(T + Tc) // 64) * 64
-        self._ensure_workspace(max(B * (T if prefill_chunk is None else min(T, prefill_chunk)), BN * C, 2 * BN))
-        nbytes = self.engine.kv_cache_bytes(BN, cap)
-        raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        off = (-raw.data_ptr()) % 256
-        self.engine.bind_kv_cache(raw[off:off + nbytes], BN, cap)
-        V = self.config.vocab_size
-        logits = torch.empty(BN, V, dtype=torch.float32, device=dev)
-        if n > 1:
-            lens = torch.cat([lens, torch.zeros(BN - B, dtype=torch.int32, device=dev)])
-        # every block's operands, built before the first engine call: ids, real tokens per row, the first column's token and its
-        # "row has no token here" flag (slam_token_logprobs writes 0.0 for it), the block's outputs
-        valid = torch.arange(Tc, device=dev)[None] < clens[:, None]
-        cont = torch.where(valid, cont, torch.full_like(cont, int(pad)))
-        blocks = []
-        for c0 in range(0, Tc, C):
-            w = min(C, Tc - c0)
-            blk = cont[:, c0:c0 + w].contiguous()
-            blocks.append((w, blk, (clens - c0).clamp(min=0, max=w).contiguous(), blk[:, 0].contiguous(),
-                           (clens <= c0).to(torch.uint8).contiguous(), torch.empty(BN, w, dtype=torch.float32, device=dev),
-                           torch.empty(BN, w, dtype=torch.int64, device=dev) if return_argmax else None))
-        lpws = torch.empty(E.token_logprobs_workspace_bytes(BN, V), dtype=torch.uint8, device=dev)
-        first = None
-        if return_argmax:  # position 0's greedy choice: slam_sample_tokens (greedy) on the prefill logits
-            first = torch.empty(BN, dtype=torch.int64, device=dev)
-            gdesc = E.SlamSampleDesc(do_sample=0, top_k=1, temperature=1.0, top_p=1.0, seed=0, step=0, pad_id=int(pad), n_eos=0)
-            sws = torch.empty(E.sample_workspace_bytes(BN, V, 1), dtype=torch.uint8, device=dev)
-        lmask = ign = None
-        if ignore_tokens is not None:
-            ign = torch.as_tensor(list(ignore_tokens), dtype=torch.long, device=dev)
-            lmask = torch.zeros(self.engine.padded_vocab(), dtype=torch.uint8, device=dev)
-            lmask[ign] = 1
-            self.engine.set_logit_mask(lmask)
-        self._hold = (ids, lens, blocks)
-        try:
-            self._prefill(ids, lens, B, T, logits, prefill_chunk)
-            if n > 1:
-                self.engine.kv_repeat(n, lens, logits)
-            if ign is not None:
-                logits.index_fill_(1, ign, float("-inf"))
-            if first is not None:
-                E.sample_tokens(logits, gdesc, first, sws, lmask)
-            for w, blk, nl, tok0, inert, lp_b, am_b in blocks:
-                # `inert` is the kernel's in/out `finished` array: read (1 = write 0.0 for the row), then overwritten with
-                # `done` (none: zeros). Each block owns its tensor and it is used exactly once.
-                E.token_logprobs(logits, tok0, lp_b, column=0, ws=lpws, done=None, finished=inert)
-                self.engine.extend_score(blk, nl, lens, BN, w, logits, lp_b, am_b)
-                if ign is not None:
-                    logits.index_fill_(1, ign, float("-inf"))
-        finally:
-            if lmask is not None:
-                torch.cuda.current_stream(dev).synchronize()  # the kernels read the mask: keep it alive until done
-                self.engine.set_logit_mask(None)
-        lp = torch.cat([b[5] for b in blocks], 1) if len(blocks) > 1 else blocks[0][5]
-        if not return_argmax:
-            return lp
-        # argmax_out[:, t] is the choice AFTER position t: shift by one behind the prefill's choice
-        am = torch.cat([first[:, None]] + [b[6] for b in blocks], 1)[:, :Tc]
-        return lp, torch.where(valid, am, torch.full_like(am, -1))
-
-    def _prefill(self, ids, lens, B, T, logits, chunk=None):
-        """The prompts into the cache and each row's last-token logits into logits[:B]: slam_prefill over all T columns, or
-        (chunk = C) over the first min(T, C) and slam_extend over every further block of C. lens (first B entries: the prompt
-        lengths) is left as it is; the chunks advance a copy, which ends equal to it."""
-        if chunk is None or T <= chunk:
-            self.engine.prefill(ids, lens, B, T, logits)
-            return
-        full = lens[:B]
-        cur = full.clamp(max=chunk).contiguous()
-        self.engine.prefill(ids[:, :chunk].contiguous(), cur, B, chunk, logits)
-        for c0 in range(chunk, T, chunk):
-            w = min(chunk, T - c0)
-            new_lens = (full - c0).clamp(min=0, max=w).contiguous()
-            self.engine.extend(ids[:, c0:c0 + w].contiguous(), new_lens, cur, B, w, logits)
-
-    def _sample_on_device(self, logits, new, ids, lens, T, bad, eos, pad, do_sample, top_k, temperature, top_p, seed, sample_ids,
-                          nret=1, lp=None, prefill_chunk=None, cons=None, warp=None, cfg=None):
-        """The decode loop of generate(sampler="engine"): prefill, sample(step 0), then decode_step(next) / sample(step k). The
-        kernel writes new[:, k] and the done flags; the host only looks at them every 16 steps. Returns the columns written.
-        logits / new have B n rows: the prompts (ids, the first rows of lens) are prefilled once and fanned out (kv_repeat).
-        cons (a _Constrainer) puts slam_constrain_scores in front of the sampler; the log-probs keep reading the raw logits.
-        cfg (a _Guidance): logits holds cfg.n conditional rows and their unconditional twins; slam_cfg_scores comes first, only
-        the conditional rows are sampled and scored, and slam_cfg_mirror_tokens hands every twin its row's token."""
-        dev = self.device
-        R, V = logits.shape                # rows in the cache
-        B = R if cfg is None else cfg.n    # rows sampled
-        max_new = new.shape[1]
-        if do_sample and seed is None:
-            seed = int(torch.randint(0, 1 << 62, (1,)).item())
-        desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=top_k if do_sample else 1,
-                                temperature=temperature if do_sample else 1.0, top_p=top_p if do_sample else 1.0,
-                                seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF, step=0, pad_id=pad, n_eos=len(eos))
-        ws = torch.empty(E.sample_workspace_bytes(B, V, desc.top_k), dtype=torch.uint8, device=dev)
-        banned = None
-        if bad:
-            banned = torch.zeros(V, dtype=torch.uint8, device=dev)
-            banned[torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev)] = 1
-        eos_i = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
-        row_ids = None
-        if sample_ids is not None:
-            row_ids = torch.as_tensor(sample_ids).to(dev, torch.int64).contiguous()
-            if row_ids.shape != (B,):
-                raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
-        done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        nxt = torch.empty(B, dtype=torch.int64, device=dev) if cfg is None else cfg.next[:B]
-        self._prefill(ids, lens, R // nret, T, logits, prefill_chunk)
-        if nret > 1:
-            self.engine.kv_repeat(nret, lens, logits)
-        n = 0
-        for step in range(max_new):
-            desc.step = step
-            scores = logits if cfg is None else cfg.apply(logits)
-            if cons is not None:
-                scores = cons.apply(scores, step, done)
-            if warp is None:
-                E.sample_tokens(scores, desc, nxt, ws, banned, row_ids, eos_i, done, new)
-            else:
-                E.sample_tokens_warped(scores, desc, nxt, ws, warp, None, 1, None, banned, row_ids, eos_i, done, new)
-            if lp is not None:
-                E.token_logprobs(logits[:B], nxt, lp[0], step, lp[2], done, lp[1])
-            n = step + 1
-            if eos_i is not None and (step % 16 == 15 or n == max_new) and bool(done.all()):
-                break
-            if n < max_new:
-                self.engine.decode_step(nxt if cfg is None else cfg.mirror(), lens, R, logits)
-        return n  # ws / banned / done were used on the current stream only: the allocator reuses them in stream order
-
-    def _check_assistant(self, draft, k, nret, return_logprobs, plan, do_sample, sampler) -> int:
-        """The ValueErrors of generate(assistant_model=); returns K."""
-        if not isinstance(draft, UnitLM):
-            raise ValueError(f"assistant_model must be a UnitLM (got {type(draft).__name__})")
-        if draft is self:
-            raise ValueError("assistant_model must be another model than the target (it needs a KV cache of its own)")
-        if draft.config.is_opt:
-            raise ValueError("assistant_model must not be an OPT model (the engine's KV-cached decode covers Qwen2 only)")
-        if torch.device(draft.device) != torch.device(self.device):
-            raise ValueError(f"assistant_model is on {draft.device}, the target on {self.device}")
-        if draft.config.vocab_size != self.config.vocab_size:
-            raise ValueError(f"assistant_model has vocab_size {draft.config.vocab_size}, the target {self.config.vocab_size}: "
-                             f"assisted generation needs one unit vocabulary")
-        k = 4 if k is None else k
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= E.SPEC_MAX_K:
-            raise ValueError(f"num_assistant_tokens must be an int 1 .. {E.SPEC_MAX_K} (got {k!r}); HF's heuristic schedule is "
-                             f"not implemented")
-        if nret > 1:
-            raise ValueError("assistant_model does not support num_return_sequences > 1")
-        if return_logprobs:
-            raise ValueError("assistant_model does not support return_logprobs")
-        if plan.active:
-            raise ValueError("assistant_model does not support history-dependent constraints (no_repeat_ngram_size, multi-token "
-                             "bad_words_ids, min_new_tokens / min_length, begin_suppress_tokens)")
-        if do_sample and sampler != "engine":
-            raise ValueError("assistant_model with do_sample=True needs sampler='engine': draft and target must share the "
-                             "stateless draw")
-        return k
-
-    _assist_trace = None      # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after)
-    last_assist_stats = None
-
-    def _generate_assisted(self, draft, K, ids, lens, T, max_new, bad, eos, pad, do_sample, top_k, temperature, top_p, seed,
-                           sample_ids, prefill_chunk=None, warp=None):
-        """generate(assistant_model=draft): draft-model speculative decoding on the two engines' KV caches. ids [B, T] the
-        compacted prompts, lens int32 [B] their lengths. Returns (new [B, n] int64, pad behind a row's end; n). State at the
-        start of a round: the committed sequence of row b is its prompt + n_new[b] tokens, the target's
-        cache holds it without its last token (lens_t), the draft's cache that prefix without `lag` more tokens (lens_d)."""
-        dev = self.device
-        B, V = ids.shape[0], self.config.vocab_size
-        if B > E.SPEC_MAX_ROWS:
-            raise ValueError(f"assistant_model takes at most {E.SPEC_MAX_ROWS} rows (got {B})")
-        if T + max_new > draft.config.max_tokens:
-            raise ValueError(f"prompt length {T} + max_new_tokens {max_new} exceeds the assistant's max_tokens "
-                             f"{draft.config.max_tokens}")
-        K1 = K + 1
-        pre = B * (T if prefill_chunk is None else min(T, prefill_chunk))
-        cap = -(-(T + max_new + K) // 64) * 64
-        self._ensure_workspace(max(pre, B * K1, 2 * B))
-        draft._ensure_workspace(max(pre, 2 * B))
-        caches = []
-        for m in (self, draft):
-            nbytes = m.engine.kv_cache_bytes(B, cap)
-            raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-            off = (-raw.data_ptr()) % 256
-            m.engine.bind_kv_cache(raw[off:off + nbytes], B, cap)
-            caches.append(raw)
-        if do_sample and seed is None:
-            seed = int(torch.randint(0, 1 << 62, (1,)).item())
-        desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=top_k if do_sample else 1,
-                                temperature=temperature if do_sample else 1.0, top_p=top_p if do_sample else 1.0,
-                                seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF, step=0, pad_id=pad, n_eos=len(eos))
-        ws = torch.empty(E.sample_workspace_bytes(B * K1, V, desc.top_k), dtype=torch.uint8, device=dev)
-        banned = None
-        if bad:
-            banned = torch.zeros(V, dtype=torch.uint8, device=dev)
-            banned[torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev)] = 1
-        eos_i = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
-        row_ids = None
-        if sample_ids is not None:
-            row_ids = torch.as_tensor(sample_ids).to(dev, torch.int64).contiguous()
-            if row_ids.shape != (B,):
-                raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
-        prompt_len = lens.clone()
-        lens_t, lens_d = lens.clone(), lens.clone()
-        logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-        logits_d = torch.empty(B, V, dtype=torch.float32, device=dev)
-        self._prefill(ids, lens, B, T, logits, prefill_chunk)
-        draft._prefill(ids, lens, B, T, logits_d, prefill_chunk)
-        # token 0 from the target's prefill logits, by the plain sampler: new[:, 0], done on an EOS id
-        new = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
-        done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        if warp is None:
-            E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
-        else:
-            E.sample_tokens_warped(logits, desc, nxt, ws, warp, None, 1, None, banned, row_ids, eos_i, done, new)
-        desc.n_eos = 0  # from here on slam_spec_accept looks for the EOS ids: a proposal that is one ends nothing yet
-        if max_new == 1:
-            done.fill_(1)
-        live = done == 0
-        n_new = torch.ones(B, dtype=torch.int32, device=dev)
-        chunk = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
-        chunk[:, 0] = nxt
-        tgt = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
-        draft_ids = torch.full((B, 2), pad, dtype=torch.int64, device=dev)
-        draft_ids[:, 0] = nxt
-        draft_new_lens = live.to(torch.int32)
-        tgt_new_lens = draft_new_lens * K1
-        logits_all = torch.zeros(B, K1, V, dtype=torch.float32, device=dev)
-        stats = torch.zeros(5, dtype=torch.int32, device=dev)
-        self._hold = (ids, lens, caches, chunk, tgt, logits_all)
-        n_live = int(live.sum())
-        rounds = proposed = accepted = 0
-        tokens = B
-        trace = self._assist_trace
-        while n_live > 0:
-            # draft: catch up with the committed sequence, then K proposals into chunk[:, 1 ..]
-            draft.engine.extend(draft_ids, draft_new_lens, lens_d, B, 2, logits_d)
-            for j in range(1, K1):
-                desc.step = j - 1
-                if warp is None:
-                    E.sample_tokens_at(logits_d, desc, nxt, ws, n_new, 1, j, banned, row_ids, None, None, chunk)
-                else:
-                    E.sample_tokens_warped(logits_d, desc, nxt, ws, warp, n_new, 1, j, banned, row_ids, None, None, chunk)
-                if j < K:
-                    draft.engine.decode_step(nxt, lens_d, B, logits_d)
-            # target: the logits behind every chunk column, and its own token there with the draw the draft used
-            self.engine.extend_logits(chunk, tgt_new_lens, lens_t, B, K1, logits_all)
-            desc.step = 0
-            if warp is None:
-                E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
-            else:
-                E.sample_tokens_warped(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, warp, n_new, K1, 0, banned, row_ids)
-            if trace is not None:
-                rec = (chunk.cpu(), logits_all.cpu(), n_new.cpu(), tgt.cpu())
-            E.spec_accept(chunk, tgt, K, max_new, pad, eos_i, prompt_len, n_new, done, new, lens_t, lens_d, draft_ids,
-                          draft_new_lens, tgt_new_lens, stats)
-            st = stats.tolist()  # the round's one host synchronisation
-            if trace is not None:
-                trace.append(rec + (n_new.cpu(),))
-            self.engine.kv_rewind(max(1, st[1]))
-            draft.engine.kv_rewind(max(1, st[2]))
-            rounds += 1
-            proposed += n_live * K
-            accepted += st[4]
-            tokens += st[3]
-            n_live = st[0]
-        self.last_assist_stats = {"rounds": rounds, "proposed": proposed, "accepted": accepted, "tokens": tokens}
-        n = int(n_new.max())
-        return new[:, :n], n
-
-    def _check_lookup(self, k, n, nret, return_logprobs, plan, do_sample, sampler) -> int:
-        """The ValueErrors of generate(prompt_lookup_num_tokens=); returns max_matching_ngram_size."""
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= E.SPEC_MAX_K:
-            raise ValueError(f"prompt_lookup_num_tokens must be an int 1 .. {E.SPEC_MAX_K} (got {k!r})")
-        n = 2 if n is None else n
-        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= E.NGRAM_MAX:
-            raise ValueError(f"max_matching_ngram_size must be an int 1 .. {E.NGRAM_MAX} (got {n!r})")
-        if nret > 1:
-            raise ValueError("prompt_lookup_num_tokens does not support num_return_sequences > 1")
-        if return_logprobs:
-            raise ValueError("prompt_lookup_num_tokens does not support return_logprobs")
-        if plan.active:
-            raise ValueError("prompt_lookup_num_tokens does not support history-dependent constraints (no_repeat_ngram_size, "
-                             "multi-token bad_words_ids, min_new_tokens / min_length, begin_suppress_tokens)")
-        if do_sample and sampler != "engine":
-            raise ValueError("prompt_lookup_num_tokens with do_sample=True needs sampler='engine': the verified positions are "
-                             "drawn with the stateless draw")
-        return n
-
-    _lookup_trace = None  # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after, n_prop)
-
-    def _generate_lookup(self, K, ngram, ids, lens, T, max_new, bad, eos, pad, do_sample, top_k, temperature, top_p, seed,
-                         sample_ids, prefill_chunk=None, warp=None):
-        """generate(prompt_lookup_num_tokens=K): _generate_assisted without the draft model, its cache and its catch-up
-        steps. The proposals of a round come from slam_ngram_propose on the row's own history (ids, then `new` up to n_new);
-        all K + 1 chunk columns of a live row are verified, the ones without a proposal holding `pad`, so every row of
-        logits_all that the sampler reads for a live row is a real conditional of this round. Returns
-        (new [B, n] int64, pad behind a row's end; n)."""
-        dev = self.device
-        B, V = ids.shape[0], self.config.vocab_size
-        if B > E.SPEC_MAX_ROWS:
-            raise ValueError(f"prompt_lookup_num_tokens takes at most {E.SPEC_MAX_ROWS} rows (got {B})")
-        K1 = K + 1
-        pre = B * (T if prefill_chunk is None else min(T, prefill_chunk))
-        cap = -(-(T + max_new + K) // 64) * 64
-        self._ensure_workspace(max(pre, B * K1, 2 * B))
-        nbytes = self.engine.kv_cache_bytes(B, cap)
-        raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        off = (-raw.data_ptr()) % 256
-        self.engine.bind_kv_cache(raw[off:off + nbytes], B, cap)
-        if do_sample and seed is None:
-            seed = int(torch.randint(0, 1 << 62, (1,)).item())
-        desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=top_k if do_sample else 1,
-                                temperature=temperature if do_sample else 1.0, top_p=top_p if do_sample else 1.0,
-                                seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF, step=0, pad_id=pad, n_eos=len(eos))
-        ws = torch.empty(E.sample_workspace_bytes(B * K1, V, desc.top_k), dtype=torch.uint8, device=dev)
-        banned = None
-        if bad:
-            banned = torch.zeros(V, dtype=torch.uint8, device=dev)
-            banned[torch.tensor([w[0] for w in bad], dtype=torch.long, device=dev)] = 1
-        eos_i = torch.tensor(eos, dtype=torch.int32, device=dev) if eos else None
-        row_ids = None
-        if sample_ids is not None:
-            row_ids = torch.as_tensor(sample_ids).to(dev, torch.int64).contiguous()
-            if row_ids.shape != (B,):
-                raise ValueError(f"sample_ids must have shape [{B}], got {list(row_ids.shape)}")
-        prompt_len = lens.clone()
-        lens_t = lens.clone()
-        logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-        self._prefill(ids, lens, B, T, logits, prefill_chunk)
-        # token 0 from the prefill logits, by the plain sampler: new[:, 0], done on an EOS id
-        new = torch.full((B, max_new), pad, dtype=torch.int64, device=dev)
-        done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        if warp is None:
-            E.sample_tokens(logits, desc, nxt, ws, banned, row_ids, eos_i, done, new)
-        else:
-            E.sample_tokens_warped(logits, desc, nxt, ws, warp, None, 1, None, banned, row_ids, eos_i, done, new)
-        desc.n_eos = 0  # from here on slam_spec_accept looks for the EOS ids
-        if max_new == 1:
-            done.fill_(1)
-        live = done == 0
-        n_new = torch.ones(B, dtype=torch.int32, device=dev)
-        n_prop = torch.zeros(B, dtype=torch.int32, device=dev)
-        chunk = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
-        chunk[:, 0] = nxt
-        tgt = torch.full((B, K1), pad, dtype=torch.int64, device=dev)
-        tgt_new_lens = live.to(torch.int32) * K1
-        # the draft side of slam_spec_accept: written every round, read by nothing
-        lens_d = torch.empty(B, dtype=torch.int32, device=dev)
-        draft_ids = torch.empty(B, 2, dtype=torch.int64, device=dev)
-        draft_new_lens = torch.empty(B, dtype=torch.int32, device=dev)
-        logits_all = torch.zeros(B, K1, V, dtype=torch.float32, device=dev)
-        stats = torch.zeros(7, dtype=torch.int32, device=dev)  # slam_spec_accept's five, then slam_ngram_propose's two
-        self._hold = (ids, lens, raw, chunk, tgt, logits_all)
-        n_live = int(live.sum())
-        rounds = proposed = accepted = 0
-        tokens = B
-        trace = self._lookup_trace
-        while n_live > 0:
-            E.ngram_propose(chunk, n_prop, ngram, pad, ids, prompt_len, new, n_new, done, eos_i, stats[5:])
-            self.engine.extend_logits(chunk, tgt_new_lens, lens_t, B, K1, logits_all)
-            desc.step = 0
-            if warp is None:
-                E.sample_tokens_at(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, n_new, K1, 0, banned, row_ids)
-            else:
-                E.sample_tokens_warped(logits_all.view(B * K1, V), desc, tgt.view(-1), ws, warp, n_new, K1, 0, banned, row_ids)
-            if trace is not None:
-                rec = (chunk.cpu(), logits_all.cpu(), n_new.cpu(), tgt.cpu())
-            E.spec_accept(chunk, tgt, K, max_new, pad, eos_i, prompt_len, n_new, done, new, lens_t, lens_d, draft_ids,
-                          draft_new_lens, tgt_new_lens, stats)
-            st = stats.tolist()  # the round's one host synchronisation
-            if trace is not None:
-                trace.append(rec + (n_new.cpu(), n_prop.cpu()))
-            self.engine.kv_rewind(max(1, st[1]))
-            rounds += 1
-            proposed += st[6]
-            accepted += st[4]
-            tokens += st[3]
-            n_live = st[0]
-        self.last_assist_stats = {"rounds": rounds, "proposed": proposed, "accepted": accepted, "tokens": tokens}
-        n = int(n_new.max())
-        return new[:, :n], n
+        """This model's log-probs (and greedy choices) of given continuations of the prompts, through the KV cache: the
+        scoring half of generate(num_return_sequences=n, return_logprobs=True). The contract is in generation.py."""
+        return generation.score_continuations(self, input_ids, attention_mask, continuations, continuation_lengths,
+                                              num_per_prompt, score_chunk, prefill_chunk, return_argmax, ignore_tokens)
 
     # ---- checkpoints (HF layout) ------------------------------------------------------------------
     def save_pretrained(self, save_directory: str, dtype=torch.bfloat16):
