@@ -773,6 +773,64 @@ int slam_adamw_range_bf16(SlamEngine* h, int64_t offset, int64_t count, void* ex
  * exact), so a masked step equals, bit for bit, the unmasked step with the caller's weight_decay on the decayed tensors and
  * the unmasked step with weight_decay = 0 on the others - in every state precision and with "adamw_sr". */
 int slam_set_decay_mask(SlamEngine* h, const uint8_t* decay, int32_t n_tensors);
+
+/* ---- Adafactor: HF Trainer's optim = "adafactor" ------------------------------------------------------------------------
+ * transformers.optimization.Adafactor as Trainer.get_optimizer_cls_and_kwargs builds it: scale_parameter = False, relative_step =
+ * False, beta1 = None (no first moment), eps = (1e-30, 1e-3), clip_threshold = 1.0, decay_rate = -0.8; eps[1] and the
+ * parameter's own RMS are unused when scale_parameter is off. Per HF parameter tensor at step t (1-based), in fp32:
+ *   g = gradient * norm_out[1];  beta = 1 - t^decay_rate;  s = g^2 + eps1
+ *   matrix [R][C]:  row[r] <- beta row[r] + (1 - beta) mean_c s[r][c];   col[c] <- beta col[c] + (1 - beta) mean_r s[r][c]
+ *                   u[r][c] = g[r][c] rsqrt(row[r] / mean_r row) rsqrt(col[c])
+ *   vector:         v <- beta v + (1 - beta) s;   u = g rsqrt(v)
+ *   d = max(1, sqrt(mean u^2) / clip_threshold);   p <- p - weight_decay lr p;   p <- p - lr u / d
+ * The reductions are per HF tensor, and HF's tensors are not the engine's (wqkv = q | k | v, bqkv likewise, wgu = gate / up in
+ * interleaved 32-row groups, the embedding padded to 512-row multiples): the caller describes them once.
+ *
+ * SlamAdafactorSegment = one HF parameter laid over the flat buffer: `offset` (elements) of its first row - for pattern 1 / 2
+ * of the engine tensor that holds it -, HF `rows` x `cols`, `factored` (1: a matrix with row and column factors; 0: a vector,
+ * rows = 1 and cols = its length) and the row `pattern`: 0 = row r is the r-th row of cols elements behind `offset`; 1 / 2 =
+ * "groups of 32 rows every 64" with phase 0 / 32: row r is row (r / 32) 64 + phase + r % 32 behind `offset` (rows % 32 == 0).
+ *
+ * slam_adafactor_set_segments: validates and uploads the table (host bookkeeping + one small synchronous upload; outside stream
+ *   capture). SLAM_EINVAL with a message: n < 1, a NULL table, rows or cols < 1, a vector with rows != 1, an unknown pattern or
+ *   pattern rows that are no multiple of 32, offset or cols not a multiple of 8, a segment that leaves [0, slam_param_count), two
+ *   segments that share an element. segs == NULL with n == 0 clears the table. The table survives re-binding of parameters and
+ *   workspaces, like the decay mask. Elements that no segment covers (the embedding's pad rows) are never written by a step.
+ * slam_adafactor_sizes: state_floats = the length of the caller's fp32 state buffer: per segment, in table order and without
+ *   gaps, rows + cols floats (the row factors, then the column factors) when factored, cols when not; zeros before step 1.
+ *   workspace_bytes = the bytes slam_adafactor_bind_workspace needs. SLAM_ESTATE without a table.
+ * slam_adafactor_bind_workspace: caller-owned device memory, 16-byte aligned, at least workspace_bytes (SLAM_ENOMEM when
+ *   shorter); NULL unbinds. Nothing beyond workspace_bytes is touched; the contents need not survive between steps.
+ *
+ * slam_adafactor_step: one update of every segment. master_f32 == NULL is the recipe's precision: the bound bf16 parameters are
+ *   the only copy - read, updated in fp32 and rounded once on the way back; otherwise the fp32 master is updated and the bf16
+ *   copy written from it. state_f32 is never rounded. The gradients are read where the last backward left them (the fp32 buffer,
+ *   or the bf16 image after "grad_final_next" = 2); norm_out (nullable) is slam_grad_norm's output, whose [1] scales them.
+ *   weight_decay honours slam_set_decay_mask per engine tensor (every HF part of a fused tensor has one class): a masked step
+ *   equals, bit for bit, the unmasked step on the decayed segments and the weight_decay = 0 step on the others. zero_grad != 0
+ *   clears the whole fp32 gradient buffer behind the update, whichever buffer the gradients were read from. The transposed
+ *   weight images are refreshed as after slam_adamw_step. "adamw_sr" = 1: with master_f32 == NULL the stored bf16 parameter is
+ *   the stochastic rounding of the fp32 result - array 0 of slam_op_sr_round_bf16, keyed on ("adamw_sr_seed", step, flat index);
+ *   with a master the option does nothing.
+ *   Six launches for the whole model (+ the image refresh), blocks finding their segment through the table; no atomics. Every
+ *   sum runs in an order fixed by the segment's shape - tiles of 256 rows x 256 columns; the orders are listed at the top of
+ *   csrc/adafactor.hip - so a step gives the same bits on every run, with zero_grad 0 or 1, and from either gradient buffer
+ *   given equal values.
+ *   Refused with a message: no segment table or no bound workspace (SLAM_ESTATE); "overlap_adamw" on (SLAM_ESTATE: the
+ *   overlapped chunks belong to AdamW); state_f32 NULL or step < 1 (SLAM_EINVAL). There is no ranged form: a shard of the flat
+ *   buffer cuts rows and columns. */
+typedef struct SlamAdafactorSegment {
+  int64_t offset;
+  int32_t rows, cols;
+  int32_t factored;
+  int32_t pattern;
+} SlamAdafactorSegment;
+int slam_adafactor_set_segments(SlamEngine* h, const SlamAdafactorSegment* segs, int32_t n);
+int slam_adafactor_sizes(SlamEngine* h, int64_t* state_floats, size_t* workspace_bytes);
+int slam_adafactor_bind_workspace(SlamEngine* h, void* workspace, size_t bytes);
+int slam_adafactor_step(SlamEngine* h, float* master_f32, float* state_f32, const float* norm_out, double lr, double eps1,
+                        double clip_threshold, double decay_rate, double weight_decay, int32_t step, int32_t zero_grad,
+                        slam_stream_t stream);
 /* Another stream (the all-gather of a parameter bucket) is still writing the bound bf16 parameters in [offset, offset +
  * count); `event` (hipEvent_t, owned by the caller, alive until the next forward was enqueued) is recorded behind that
  * write. The next slam_forward waits for it right before its first read of the range - layer by layer, so the gather of

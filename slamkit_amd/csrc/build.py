@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIB_DIR, "libslam_engine.so")
-SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "decode.hip", "quant.hip", "engine.hip"]
+SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "decode.hip", "quant.hip", "engine.hip"]
 HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "slam_engine.h")]
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified file); without it the
 # attention kernels spend 256 v_accvgpr_read/write per K/V tile moving the online-softmax state around.

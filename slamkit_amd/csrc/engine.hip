@@ -143,6 +143,11 @@ struct SlamEngine {
   bool no_decay(int64_t off) const {
     return ((std::upper_bound(nd_host.begin(), nd_host.end(), (uint64_t)off) - nd_host.begin()) & 1) != 0;
   }
+  // slam_adafactor_set_segments: the HF parameters over the flat buffer (kernels.h AfSeg), laid out over state and workspace;
+  // af_plan.segs - engine-owned device memory - is what the kernels search. af_ws: the caller's workspace.
+  std::vector<AfSeg> af_host;
+  AfPlan af_plan;
+  float* af_ws = nullptr;
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_chunk;  // [0] embedding, [1 + l] layer l, [L + 1] final norm (+ an untied lm_head and its transposed image)
@@ -225,6 +230,7 @@ struct SlamEngine {
     for (hipEvent_t e : ag_ev) (void)hipEventDestroy(e);
     if (comm_stream) { (void)hipStreamSynchronize(comm_stream); (void)hipStreamDestroy(comm_stream); }
     if (nd_dev) (void)hipFree(nd_dev);
+    if (af_plan.segs) (void)hipFree((void*)af_plan.segs);
   }
   // parameter ranges another stream is still writing (sharded optimizer: the bf16 parameter all-gather on the
   // communication stream): the next reader waits for the event right before its first read of the range
@@ -2128,6 +2134,106 @@ int slam_set_decay_mask(SlamEngine* h, const uint8_t* decay, int32_t n_tensors) 
   h->nd_dev = dev;
   h->nd_host.swap(b);
   return SLAM_OK;
+}
+
+// ---- Adafactor (the contract is in the header; the kernels in adafactor.hip) ---------------------------------------------
+int slam_adafactor_set_segments(SlamEngine* h, const SlamAdafactorSegment* segs, int32_t n) {
+  if (!h) return SLAM_EINVAL;
+  std::vector<AfSeg> t;
+  if (segs || n) {
+    if (!segs || n < 1) return h->fail(SLAM_EINVAL, "adafactor segments: a table of n >= 1 segments, or NULL and 0 to clear");
+    std::vector<std::pair<int64_t, int64_t>> iv;  // the element intervals the segments cover
+    int64_t tiles = 0;
+    for (int32_t i = 0; i < n; ++i) {
+      const SlamAdafactorSegment& g = segs[i];
+      const std::string at = "adafactor segment " + std::to_string(i) + ": ";
+      if (g.rows < 1 || g.cols < 1) return h->fail(SLAM_EINVAL, at + "rows and cols must be positive");
+      if (g.factored != 0 && g.factored != 1) return h->fail(SLAM_EINVAL, at + "factored is 0 or 1");
+      if (!g.factored && g.rows != 1) return h->fail(SLAM_EINVAL, at + "a vector (factored = 0) has rows = 1 and cols = its length");
+      if (g.pattern < 0 || g.pattern > 2) return h->fail(SLAM_EINVAL, at + "pattern is 0 (contiguous), 1 or 2 (32 rows of every 64, phase 0 or 32)");
+      if (g.pattern && (g.rows % 32)) return h->fail(SLAM_EINVAL, at + "rows in groups of 32 need rows % 32 == 0");
+      if ((g.offset & 7) || (g.cols & 7)) return h->fail(SLAM_EINVAL, at + "misaligned: offset and cols must be multiples of 8");
+      const int64_t c = g.cols;
+      const int64_t span = g.pattern ? ((int64_t)(g.rows / 32 - 1) * 64 + (g.pattern == 2 ? 32 : 0) + 32) * c : (int64_t)g.rows * c;
+      if (g.offset < 0 || g.offset > h->n_params || span > h->n_params - g.offset)
+        return h->fail(SLAM_EINVAL, at + "out of range: it leaves [0, slam_param_count)");
+      if (!g.pattern) {
+        iv.push_back({g.offset, g.offset + span});
+      } else {
+        for (int64_t k = 0; k < g.rows / 32; ++k) {
+          const int64_t lo = g.offset + (k * 64 + (g.pattern == 2 ? 32 : 0)) * c;
+          iv.push_back({lo, lo + 32 * c});
+        }
+      }
+      AfSeg s;
+      s.off = g.offset; s.rows = g.rows; s.cols = g.cols; s.factored = g.factored;
+      s.phase = g.pattern == 0 ? -1 : g.pattern == 1 ? 0 : 32;
+      tiles += (int64_t)((g.rows + AF_TILE_ROWS - 1) / AF_TILE_ROWS) * ((g.cols + AF_TILE_COLS - 1) / AF_TILE_COLS);
+      t.push_back(s);
+    }
+    if (tiles > 0x7fffffff) return h->fail(SLAM_EINVAL, "adafactor segments: more tiles than one launch holds");
+    std::sort(iv.begin(), iv.end());
+    for (size_t i = 1; i < iv.size(); ++i)
+      if (iv[i].first < iv[i - 1].second) return h->fail(SLAM_EINVAL, "adafactor segments overlap: two segments share an element");
+  }
+  AfPlan plan;
+  AfSeg* dev = nullptr;
+  if (!t.empty()) {
+    adafactor_layout(t.data(), (int)t.size(), &plan);
+    CK((int)hipMalloc(&dev, t.size() * sizeof(AfSeg)));
+    const int r = (int)hipMemcpy(dev, t.data(), t.size() * sizeof(AfSeg), hipMemcpyHostToDevice);
+    if (r) { (void)hipFree(dev); CK(r); }
+    plan.segs = dev;
+  }
+  if (h->af_plan.segs) CK((int)hipFree((void*)h->af_plan.segs));  // synchronises with the device: no step in flight reads the old table
+  h->af_plan = plan;
+  h->af_host.swap(t);
+  h->af_ws = nullptr;  // sized for the table that went
+  return SLAM_OK;
+}
+int slam_adafactor_sizes(SlamEngine* h, int64_t* state_floats, size_t* workspace_bytes) {
+  if (!h || !state_floats || !workspace_bytes) return SLAM_EINVAL;
+  if (h->af_host.empty()) return h->fail(SLAM_ESTATE, "adafactor: no segment table (slam_adafactor_set_segments)");
+  *state_floats = h->af_plan.state_floats;
+  *workspace_bytes = (size_t)h->af_plan.ws_floats * sizeof(float);
+  return SLAM_OK;
+}
+int slam_adafactor_bind_workspace(SlamEngine* h, void* workspace, size_t bytes) {
+  if (!h) return SLAM_EINVAL;
+  if (!workspace) { h->af_ws = nullptr; return SLAM_OK; }
+  if (h->af_host.empty()) return h->fail(SLAM_ESTATE, "adafactor: no segment table (slam_adafactor_set_segments)");
+  if (((uintptr_t)workspace) & 15) return h->fail(SLAM_EINVAL, "adafactor workspace must be 16-byte aligned");
+  if (bytes < (size_t)h->af_plan.ws_floats * sizeof(float)) return h->fail(SLAM_ENOMEM, "adafactor workspace too small");
+  h->af_ws = (float*)workspace;
+  return SLAM_OK;
+}
+int slam_adafactor_step(SlamEngine* h, float* master, float* state, const float* norm_out, double lr, double eps1,
+                        double clip_threshold, double decay_rate, double wd, int32_t step, int32_t zero_grad, slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  if (h->af_host.empty()) return h->fail(SLAM_ESTATE, "adafactor step without a segment table (slam_adafactor_set_segments)");
+  if (h->overlap_adamw) return h->fail(SLAM_ESTATE, "adafactor step with overlap_adamw on: the overlapped chunks belong to AdamW");
+  if (!state) return h->fail(SLAM_EINVAL, "adafactor step: state_f32 is NULL");
+  if (step < 1) return h->fail(SLAM_EINVAL, "adafactor step: step counts from 1");
+  if (!(clip_threshold > 0)) return h->fail(SLAM_EINVAL, "adafactor step: clip_threshold must be positive");
+  if (!h->af_ws) return h->fail(SLAM_ESTATE, "adafactor step without a workspace (slam_adafactor_bind_workspace)");
+  if (!h->grads || !h->params) return h->fail(SLAM_ESTATE, "bind params first");
+  hipStream_t st = (hipStream_t)stream;
+  CK(join_optimizer(h, st));
+  CK(join_params(h, st));
+  h->w8_valid = false;
+  AfArgs a;
+  a.master = master; a.params = h->params; a.state = state; a.ws = h->af_ws; a.clip = norm_out;
+  a.g_bf16 = h->gfinal == 2;  // the last backward kept its final values in bf16 only (slam_set_grad_image's buffer)
+  a.g = a.g_bf16 ? (const void*)h->g16 : (const void*)h->grads;
+  const double beta = 1.0 - pow((double)step, decay_rate);  // HF: python doubles, fp32 in the kernel
+  a.lr = (float)lr; a.eps1 = (float)eps1; a.clip_threshold = (float)clip_threshold; a.wd = (float)wd;
+  a.beta = (float)beta; a.one_minus_beta = (float)(1.0 - beta);
+  a.step = step;
+  a.sr.on = h->adamw_sr; a.sr.seed = h->adamw_sr_seed;
+  if (h->nd_dev) { a.nd.bounds = h->nd_dev; a.nd.n = (int)h->nd_host.size(); }
+  CK(adafactor_step(h->af_plan, a, st));
+  if (zero_grad) CK((int)hipMemsetAsync(h->grads, 0, (size_t)h->n_params * sizeof(float), st));
+  return slam_refresh_transposed(h, stream);
 }
 
 int slam_add_param_wait(SlamEngine* h, int64_t offset, int64_t count, void* event) {

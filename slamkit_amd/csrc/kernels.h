@@ -255,6 +255,40 @@ int adamw_strided(const AdamArgs& a, size_t n, int batch, size_t stride, hipStre
 int adamw_tiles(const AdamArgs& a, int R, int C, int batch, size_t batch_stride, hipStream_t st);
 // y[i] = the stochastic rounding of x[i] as the kernels above apply it to flat index index0 + i of array `which` (0 p, 1 m, 2 v)
 int sr_round_bf16(const float* x, bf16_t* y, size_t n, int64_t index0, uint64_t seed, int step, int which, hipStream_t st);
+// ---- Adafactor (adafactor.hip; the contract is in include/slam_engine.h: slam_adafactor_step) ---------------------------------
+// One HF parameter laid over the flat buffer, as the kernels read it. HF row r is row r of the engine tensor at `off`
+// (phase < 0) or row (r / 32) * 64 + phase + r % 32 of it (gate / up: groups of 32 rows every 64). A vector is rows = 1,
+// cols = numel. A factored segment owns rows + cols state floats (the row factors, then the column factors), a vector numel.
+constexpr int AF_TILE_ROWS = 256, AF_TILE_COLS = 256;  // a block's tile; tiles of a segment are numbered row block major
+struct AfSeg {
+  int64_t off = 0, state = 0;          // first element in the flat buffer / first float in the state buffer
+  int64_t rowpart = 0, colpart = 0;    // workspace floats: row partials [rows][n_cb], column partials [n_rb][cols]
+  int rows = 0, cols = 0, factored = 0, phase = -1;
+  int tile0 = 0, n_rb = 0, n_cb = 0;   // first tile; row blocks and column blocks
+  int fin0 = 0;                        // first block of the factor finish (256 factors a block; none for a vector)
+};
+struct AfPlan {
+  const AfSeg* segs = nullptr;  // device
+  int n_segs = 0, n_tiles = 0, n_fin = 0;
+  int64_t state_floats = 0;
+  int64_t segmean = 0, segd = 0, tilepart = 0, ws_floats = 0;  // workspace floats: [n_segs], [n_segs], [n_tiles]; the total
+};
+struct AfArgs {
+  float* master = nullptr;     // nullable: the bf16 parameters are the only copy
+  bf16_t* params = nullptr;
+  const void* g = nullptr;     // float, or bf16_t when g_bf16
+  int g_bf16 = 0;
+  float* state = nullptr;
+  float* ws = nullptr;
+  const float* clip = nullptr;  // nullable: slam_grad_norm's output
+  float lr = 0, eps1 = 0, clip_threshold = 1, beta = 0, one_minus_beta = 1, wd = 0;
+  int step = 1;
+  AdamSR sr;       // rounds the bf16 parameters where they are the only copy; base is not used (a tile knows its flat index)
+  AdamNoDecay nd;  // a segment whose first element lies in a range takes wd = 0
+};
+// host: lays the segments (off, rows, cols, factored, phase given) out over state and workspace; fills the rest and `plan`
+void adafactor_layout(AfSeg* segs, int n, AfPlan* plan);
+int adafactor_step(const AfPlan& plan, const AfArgs& a, hipStream_t st);
 int f32_to_bf16(const float* s, bf16_t* d, size_t n, hipStream_t st);
 // the same conversion, emitting one GradSink partial (sum of squares of the rounded values) per 8192-element block
 int f32_to_bf16_sumsq_slots(size_t n);

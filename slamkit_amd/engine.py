@@ -31,6 +31,12 @@ class SlamTensorInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("offset", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64)]
 
 
+class SlamAdafactorSegment(C.Structure):
+    """One HF parameter laid over the flat buffer (slam_adafactor_set_segments). pattern 0: contiguous rows; 1 / 2: groups of
+    32 rows every 64 behind `offset`, phase 0 / 32 (gate_proj / up_proj inside wgu)."""
+    _fields_ = [("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("factored", C.c_int32), ("pattern", C.c_int32)]
+
+
 class SlamSampleDesc(C.Structure):
     _fields_ = [
         ("do_sample", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float), ("top_p", C.c_float),
@@ -149,6 +155,10 @@ def load_library(path: Optional[str] = None):
         "slam_adamw_range": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
         "slam_adamw_range_bf16": (C.c_int, [vp, i64, i64, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
         "slam_set_decay_mask": (C.c_int, [vp, vp, i32]),
+        "slam_adafactor_set_segments": (C.c_int, [vp, C.POINTER(SlamAdafactorSegment), i32]),
+        "slam_adafactor_sizes": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
+        "slam_adafactor_bind_workspace": (C.c_int, [vp, vp, sz]),
+        "slam_adafactor_step": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
         "slam_add_param_wait": (C.c_int, [vp, i64, i64, vp]),
         "slam_param_wait_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "slam_param_wait_untimed": (C.c_int, [vp, C.POINTER(C.c_int64)]),
@@ -775,6 +785,38 @@ class Engine:
             return
         buf = (C.c_uint8 * len(flags))(*[1 if f else 0 for f in flags])
         self._ck(self.lib.slam_set_decay_mask(self.h, buf, len(flags)))
+
+    # -- Adafactor (HF Trainer's optim = "adafactor") -------------------------------------------------------
+    def adafactor_set_segments(self, segments=None):
+        """slam_adafactor_set_segments: `segments` = [(offset, rows, cols, factored, pattern)] - one HF parameter each
+        (UnitLM.hf_param_segments() yields them behind the name); None clears the table. Returns (state floats, workspace
+        bytes) of the new table ((0, 0) when cleared)."""
+        if not segments:
+            self._ck(self.lib.slam_adafactor_set_segments(self.h, None, 0))
+            return 0, 0
+        buf = (SlamAdafactorSegment * len(segments))(*[SlamAdafactorSegment(int(o), int(r), int(c), int(bool(f)), int(p))
+                                                       for o, r, c, f, p in segments])
+        self._ck(self.lib.slam_adafactor_set_segments(self.h, buf, len(segments)))
+        return self.adafactor_sizes()
+
+    def adafactor_sizes(self):
+        """(floats of the fp32 state buffer, bytes of the workspace) for the segment table that is set."""
+        n, b = C.c_int64(0), C.c_size_t(0)
+        self._ck(self.lib.slam_adafactor_sizes(self.h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def adafactor_bind_workspace(self, ws=None):
+        """ws: a device tensor of at least the workspace bytes, 16-byte aligned (kept alive here); None unbinds."""
+        self._keep["adafactor_ws"] = ws
+        self._ck(self.lib.slam_adafactor_bind_workspace(self.h, _ptr(ws), 0 if ws is None else ws.numel() * ws.element_size()))
+
+    def adafactor_step(self, master, state, norm_out, lr, step, weight_decay=0.0, eps1=1e-30, clip_threshold=1.0,
+                       decay_rate=-0.8, zero_grad=True, stream=None):
+        """slam_adafactor_step: master = the fp32 master weights, or None when the bf16 parameters are the only copy; state =
+        the fp32 factor buffer of adafactor_sizes(); the defaults are HF Adafactor's."""
+        self._ck(self.lib.slam_adafactor_step(self.h, _ptr(master), _ptr(state), _ptr(norm_out), float(lr), float(eps1),
+                                              float(clip_threshold), float(decay_rate), float(weight_decay), int(step),
+                                              int(bool(zero_grad)), stream if stream is not None else current_stream_ptr()))
 
     def add_param_wait(self, offset: int, count: int, event):
         """event: a recorded torch.cuda.Event; kept alive here until the next forward consumed it."""

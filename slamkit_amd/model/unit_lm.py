@@ -87,6 +87,27 @@ def hf_name_is_decayed(name: str, is_opt: bool) -> bool:
     return not (is_opt and "layer_norm." in name)
 
 
+@dataclass(frozen=True)
+class HFParamSegment:
+    """One HF parameter over the engine's flat buffer (UnitLM.hf_param_segments). pattern 0: `rows` contiguous rows of `cols`
+    elements at `offset`; 1 / 2: groups of 32 rows every 64 behind `offset`, phase 0 / 32 (gate_proj / up_proj inside wgu)."""
+    name: str
+    shape: Tuple[int, ...]
+    offset: int
+    rows: int
+    cols: int
+    factored: bool
+    pattern: int
+
+    @property
+    def entry(self) -> Tuple[int, int, int, int, int]:
+        return (self.offset, self.rows, self.cols, int(self.factored), self.pattern)
+
+    @property
+    def state_floats(self) -> int:
+        return self.rows + self.cols if self.factored else self.cols
+
+
 def _opt_base_config(c: dict) -> dict:
     """Engine-side `base_config` of a HuggingFace OPTConfig dict (or of an already converted one: idempotent). Only pre-LN
     OPT as OPTForCausalLM computes it is supported (OPT-125m, OPT-1.3B); OPT-350m's post-LN + project_in/out layout,
@@ -470,6 +491,23 @@ class UnitLM(TokenLM):
             assert len(decayed) == 1, f"the HF names of {name} disagree about weight decay: {keys}"
             flags.append(decayed.pop())
         return flags
+
+    def hf_param_segments(self) -> List[HFParamSegment]:
+        """The HF parameters over the flat buffer, in `key_map` order: what an optimizer that reduces per HF tensor (Adafactor:
+        row and column factors and an update clip of each tensor's own) needs instead of the engine's fused tensors. q_proj /
+        k_proj / v_proj and the three q/k/v biases are segments of their own inside wqkv / bqkv, gate_proj / up_proj are the two
+        phases of wgu's 32-row groups, the embedding is [vocab][H] without its pad rows, and a tied head is the embedding
+        (HF: one parameter). A matrix is factored as HF's Adafactor does it (two or more dimensions), a vector is not.
+        `HFParamSegment.entry` is the row of `Engine.adafactor_set_segments`."""
+        out = []
+        for key, ent in self.key_map.items():
+            off, shp = int(ent[0]), tuple(int(s) for s in ent[1])
+            if len(shp) == 1:
+                out.append(HFParamSegment(key, shp, off, 1, shp[0], False, 0))
+            else:
+                assert len(shp) == 2, f"{key}: no HF decoder parameter here has more than two dimensions"
+                out.append(HFParamSegment(key, shp, off, shp[0], shp[1], True, 1 + int(ent[2]) if len(ent) == 3 else 0))
+        return out
 
     def _view(self, flat: torch.Tensor, key: str, writable: bool = False) -> torch.Tensor:
         """HF-named window of a flat engine buffer. gate_proj / up_proj live interleaved in 32-row blocks:

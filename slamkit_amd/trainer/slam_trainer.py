@@ -26,8 +26,8 @@ import torch.distributed as dist
 
 from .callbacks import TrainerCallback, TrainerControl, TrainerState
 from .dp import GradBucketReducer, ShardedGradReducer, all_reduce_scalar, host_group, seeded_batches, shard_batches, world_info
-from .training_args import (SLAMTrainingArguments, check_label_smoothing, check_neftune_alpha, check_weight_decay_rule,
-                            lr_lambda)
+from .training_args import (SLAMTrainingArguments, check_label_smoothing, check_neftune_alpha, check_optim,
+                            check_weight_decay_rule, lr_lambda)
 
 logger = logging.getLogger(__name__)
 
@@ -41,6 +41,18 @@ def dropout_seed(seed: int, rank: int) -> int:
     from the stochastic rounding's (`adamw_sr_seed` defaults to `args.seed` itself and its counters have the same form):
     without it rank 0 would build its masks from the words the optimizer rounds with whenever call == step."""
     return (((int(rank) & 0xFFFFFFFF) << 32) | (int(seed) & 0xFFFFFFFF)) ^ DROPOUT_SEED_TAG
+
+
+def check_checkpoint_optim(st: dict, adafactor: bool, path: str = "optimizer.pt"):
+    """An optimizer.pt holds the state of ONE optimizer kind: Adafactor's factors ("adafactor_state") or AdamW's moments
+    ("exp_avg", "exp_avg_sq"). Resuming one under the other is an error, not a silent zero state."""
+    has_af = "adafactor_state" in st
+    if adafactor and not has_af:
+        raise ValueError(f"{path} is an AdamW checkpoint (it holds exp_avg / exp_avg_sq, no Adafactor state): it cannot be "
+                         f"resumed under optim='adafactor'")
+    if not adafactor and (has_af or "exp_avg" not in st or "exp_avg_sq" not in st):
+        raise ValueError(f"{path} is an Adafactor checkpoint (it holds no exp_avg / exp_avg_sq): it cannot be resumed under an "
+                         f"AdamW optim; set optim='adafactor'")
 
 
 class SLAMTrainer:
@@ -74,6 +86,20 @@ class SLAMTrainer:
         osd = getattr(self.args, "optim_state_dtype", "float32") or "float32"
         if osd not in ("float32", "bfloat16", "float32_bf16_moments"):
             raise ValueError(f"optim_state_dtype must be float32, bfloat16 or float32_bf16_moments, got {osd!r}")
+        # optim = "adafactor": HF's Adafactor on slam_adafactor_step instead of AdamW. The AdamW names change nothing below: not
+        # one engine call more (fields set after construction get past the arguments' own check)
+        self._adafactor = check_optim(getattr(self.args, "optim", "adamw_torch") or "adamw_torch") == "adafactor"
+        if self._adafactor:
+            if osd == "float32_bf16_moments":
+                raise ValueError("optim='adafactor' keeps no Adam moments: optim_state_dtype is float32 (fp32 master weights) or "
+                                 "bfloat16 (the bf16 parameters are the only copy), not float32_bf16_moments")
+            if (getattr(self.args, "ddp_algo", "all_reduce") or "all_reduce") == "rs_ag":
+                raise ValueError("optim='adafactor' reduces over the rows and columns of whole tensors: a shard of the flat buffer "
+                                 "cuts them, so ddp_algo='rs_ag' is not available (use all_reduce)")
+            if getattr(self.args, "overlap_optimizer", False):
+                raise ValueError("optim='adafactor' has no overlapped form: overlap_optimizer belongs to the fp32-state AdamW")
+            if not hasattr(model, "hf_param_segments"):
+                raise ValueError("optim='adafactor' needs a model that knows its HF parameter tensors (UnitLM.hf_param_segments)")
         sr = bool(getattr(self.args, "optim_stochastic_rounding", False))
         if sr and osd == "float32":  # (fields set after construction get past the arguments' own check)
             raise ValueError("optim_stochastic_rounding needs bf16 optimizer state (optim_state_dtype bfloat16 or "
@@ -96,8 +122,17 @@ class SLAMTrainer:
         self._final_mode = (2 if gd == "bfloat16" else 1) if hasattr(model, "enable_bf16_grads") else 0
         if self._final_mode:
             model.engine.set_option("grad_norm_partials", 1 if getattr(self.args, "grad_norm_from_backward", True) else 0)
-        self.exp_avg = torch.zeros(n, dtype=self.moment_dtype, device=dev)
-        self.exp_avg_sq = torch.zeros(n, dtype=self.moment_dtype, device=dev)
+        if self._adafactor:
+            # no exp_avg / exp_avg_sq - that is the point: rows + cols fp32 factors per HF matrix, numel per vector, and the
+            # kernels' partial sums. The table is set once; the engine keeps it
+            self.exp_avg = self.exp_avg_sq = None
+            n_state, ws_bytes = model.engine.adafactor_set_segments([s.entry for s in model.hf_param_segments()])
+            self.adafactor_state = torch.zeros(n_state, dtype=torch.float32, device=dev)
+            self._adafactor_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            model.engine.adafactor_bind_workspace(self._adafactor_ws)
+        else:
+            self.exp_avg = torch.zeros(n, dtype=self.moment_dtype, device=dev)
+            self.exp_avg_sq = torch.zeros(n, dtype=self.moment_dtype, device=dev)
         self.norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
         cd = getattr(self.args, "ddp_comm_dtype", None)
         algo = getattr(self.args, "ddp_algo", "all_reduce") or "all_reduce"
@@ -366,7 +401,10 @@ class SLAMTrainer:
         a, eng = self.args, self.model.engine
         eng.grad_norm(a.max_grad_norm if a.max_grad_norm else 0.0, self.norm_out)
         self.opt_step += 1
-        if self.state_dtype == torch.bfloat16:
+        if self._adafactor:  # HF's defaults: eps1 1e-30, clip_threshold 1, decay_rate -0.8; the scheduler's lr
+            eng.adafactor_step(None if self.state_dtype == torch.bfloat16 else self.model.flat_master, self.adafactor_state,
+                               self.norm_out, lr, self.opt_step, weight_decay=a.weight_decay, zero_grad=zero_grad)
+        elif self.state_dtype == torch.bfloat16:
             eng.adamw_step_bf16(self.exp_avg, self.exp_avg_sq, self.norm_out, lr, a.adam_beta1, a.adam_beta2,
                                 a.adam_epsilon, a.weight_decay, self.opt_step, zero_grad=zero_grad)
         else:
@@ -580,8 +618,11 @@ class SLAMTrainer:
             path = self._ckpt_dir(self.state.global_step)
             self.model.save_pretrained(path)
             self.model.engine.join()
-            torch.save({"master": self.model._weights.cpu(), "exp_avg": self.exp_avg.cpu(),
-                        "exp_avg_sq": self.exp_avg_sq.cpu(), "opt_step": self.opt_step}, os.path.join(path, "optimizer.pt"))
+            if self._adafactor:
+                opt = {"optim": "adafactor", "adafactor_state": self.adafactor_state.cpu()}
+            else:
+                opt = {"exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu()}
+            torch.save({"master": self.model._weights.cpu(), **opt, "opt_step": self.opt_step}, os.path.join(path, "optimizer.pt"))
             with open(os.path.join(path, "trainer_state.json"), "w") as f:
                 json.dump({"global_step": self.state.global_step, "epoch": self.state.epoch,
                            "num_input_tokens_seen": self.state.num_input_tokens_seen,
@@ -599,11 +640,15 @@ class SLAMTrainer:
 
     def _load_checkpoint(self, path: str):
         st = torch.load(os.path.join(path, "optimizer.pt"), map_location="cpu")
+        check_checkpoint_optim(st, self._adafactor, path)  # before anything is overwritten
         self.model.engine.join()
         self.model._weights.copy_(st["master"])
         self.model.sync_params_from_master()
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
+        if self._adafactor:
+            self.adafactor_state.copy_(st["adafactor_state"])
+        else:
+            self.exp_avg.copy_(st["exp_avg"])
+            self.exp_avg_sq.copy_(st["exp_avg_sq"])
         self.opt_step = int(st["opt_step"])
         with open(os.path.join(path, "trainer_state.json")) as f:
             s = json.load(f)

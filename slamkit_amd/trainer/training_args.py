@@ -21,6 +21,7 @@ class SLAMTrainingArguments:
     gradient_accumulation_steps: int = 1
     weight_decay: float = 0.0
     weight_decay_rule: str = "all"                 # which tensors weight_decay applies to. "all": every element of the flat parameter buffer (the engine's historical behaviour; at weight_decay 0 - every shipped recipe - the two rules coincide). "hf": HF Trainer.create_optimizer's rule - no bias, no LayerNorm / RMSNorm parameter (UnitLM.hf_decay_flags -> slam_set_decay_mask): what reproduces a reference run with a non-zero weight_decay
+    optim: str = "adamw_torch"                     # HF's field. "adamw_torch" / "adamw_torch_fused": AdamW (the engine's slam_adamw_* kernels; the two names make the same calls). "adafactor": transformers.optimization.Adafactor as HF's Trainer builds it (scale_parameter = False, relative_step = False, no first moment; lr from the scheduler, clip_grad_norm_ first) on slam_adafactor_step: one fp32 number per row and per column of every HF matrix instead of two Adam moments per element. optim_state_dtype "float32" keeps the fp32 master, "bfloat16" drops it; "float32_bf16_moments", ddp_algo "rs_ag" and overlap_optimizer are refused (there are no moments; a shard cuts rows and columns). adam_beta1 / adam_beta2 / adam_epsilon are unused then
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_epsilon: float = 1e-8
@@ -61,6 +62,7 @@ class SLAMTrainingArguments:
 
     def __post_init__(self):
         check_weight_decay_rule(self.weight_decay_rule)
+        check_optim(self.optim)
         check_label_smoothing(self.label_smoothing_factor)
         check_neftune_alpha(self.neftune_noise_alpha)
         if self.optim_stochastic_rounding and (self.optim_state_dtype or "float32") == "float32":
@@ -88,6 +90,16 @@ def check_weight_decay_rule(rule) -> str:
     if rule not in ("all", "hf"):
         raise ValueError(f"weight_decay_rule must be 'all' or 'hf', got {rule!r}")
     return rule
+
+
+OPTIM_ADAMW = ("adamw_torch", "adamw_torch_fused")
+OPTIM_NAMES = OPTIM_ADAMW + ("adafactor",)
+
+
+def check_optim(name) -> str:
+    if name not in OPTIM_NAMES:
+        raise ValueError(f"optim must be one of 'adamw_torch', 'adamw_torch_fused' or 'adafactor', got {name!r}")
+    return name
 
 
 def check_label_smoothing(eps) -> float:
