@@ -1,4 +1,5 @@
-"""Build libslam_engine.so (gfx950) in-tree: hipcc per translation unit, then one shared link.
+"""Build libslam_engine.so (gfx950) in-tree: hipcc per translation unit, then one shared link under exports.map, which keeps
+the dynamic symbol table to the slam_* functions of include/slam_engine.h (tests/test_abi_exports.py).
 
 Usage: python -m slamkit_amd.csrc.build [--force] [--probes]
 
@@ -15,8 +16,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIB_DIR, "libslam_engine.so")
-SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "decode.hip", "quant.hip", "engine.hip"]
+SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "decode.hip", "sampling.hip", "quant.hip",
+           "engine.hip", "engine_cache.hip", "engine_optim.hip", "engine_comm.hip", "ops.hip"]
 HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "slam_engine.h")]
+ENGINE_HEADER = "engine_impl.h"  # private to the engine*.hip files, and a dependency of those alone
+# The library exports the functions of include/slam_engine.h and nothing else: every other symbol is bound inside it
+EXPORT_MAP = os.path.join(HERE, "exports.map")
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified file); without it the
 # attention kernels spend 256 v_accvgpr_read/write per K/V tile moving the online-softmax state around.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-mllvm", "-amdgpu-mfma-vgpr-form"]
@@ -51,7 +56,7 @@ def build(force=False, verbose=True, probes=False):
     def compile_one(src):
         s = os.path.join(HERE, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
-        if force or _stale(o, [s] + hdrs):
+        if force or _stale(o, [s] + hdrs + ([os.path.join(HERE, ENGINE_HEADER)] if src.startswith("engine") else [])):
             cmd = [hipcc] + FLAGS + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
@@ -60,8 +65,8 @@ def build(force=False, verbose=True, probes=False):
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         objs = list(ex.map(compile_one, SOURCES))
-    if force or _stale(LIB, objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+    if force or _stale(LIB, objs + [EXPORT_MAP]):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + EXPORT_MAP, "-o", LIB] + objs
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

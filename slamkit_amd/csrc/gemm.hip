@@ -36,7 +36,7 @@
 
 namespace slam {
 // ---- tuning state: one GemmTune per engine (kernels.h). The dispatch functions below read the CURRENT one, which an
-// engine entry point installs for the duration of its call (GemmTuneScope in engine.hip); outside any engine call - the
+// engine entry point installs for the duration of its call (GemmTuneScope in engine*.hip); outside any engine call - the
 // single-op entry points - the process default is current. Two engines in one process (DPO: policy + reference) no longer
 // share or toggle each other's settings.
 static GemmTune g_default_tune;

@@ -358,110 +358,11 @@ int extend_finish(const float* src, float* dst, const int* new_lens, int* lens, 
 int extend_store_rows(const float* src, float* dst, const int* new_lens, int m0, int rows, int B, int T, int vocab,
                       hipStream_t st);
 int lens_add(int* lens, const int* new_lens, int B, int T, hipStream_t st);
-// The acceptance rule of speculative decoding (include/slam_engine.h: slam_spec_accept): one block, a thread per row.
-constexpr int SPEC_MAX_B = 1024;
-constexpr int SPEC_MAX_K = 15;
-struct SpecArgs {
-  int64_t* chunk = nullptr;        // [B][K + 1]: pending token, then the K proposals; column 0 is rewritten
-  const int64_t* tgt = nullptr;    // [B][K + 1]: the target's token behind every column
-  int B = 0, K = 0, max_new = 0, pad_id = 0, n_eos = 0;
-  const int* eos_ids = nullptr;    // device, [n_eos]
-  const int* prompt_len = nullptr;
-  int* n_new = nullptr;
-  uint8_t* done = nullptr;
-  int64_t* out = nullptr;          // [B][out_stride]
-  int64_t out_stride = 0;
-  int* lens_t = nullptr;
-  int* lens_d = nullptr;
-  int64_t* draft_ids = nullptr;    // [B][2]
-  int* draft_new_lens = nullptr;
-  int* tgt_new_lens = nullptr;
-  int* stats = nullptr;            // [5]
-};
-int spec_accept(const SpecArgs& a, hipStream_t st);
-// Prompt-lookup proposals (include/slam_engine.h: slam_ngram_propose): one block per row; a second one-block launch for stats.
-constexpr int NGRAM_MAX = 16;            // longest n-gram matched (SLAM_NGRAM_MAX)
-constexpr int NGRAM_MAX_STRIDE = (1 << 30) - 1;  // bound of the two strides: a history length stays an int
-struct NgramArgs {
-  int64_t* chunk = nullptr;         // [B][K + 1]: columns 1 .. K are written, column 0 never
-  int* n_prop = nullptr;            // [B]
-  int B = 0, K = 0, max_ngram = 0, fill_id = 0, n_eos = 0;
-  const int64_t* prompt = nullptr;  // [B][prompt_stride], right-padded
-  int64_t prompt_stride = 0;
-  const int* prompt_len = nullptr;
-  const int64_t* fresh = nullptr;   // [B][new_stride]: the new tokens
-  int64_t new_stride = 0;
-  const int* n_new = nullptr;
-  const uint8_t* done = nullptr;
-  const int* eos_ids = nullptr;     // device, [n_eos]
-  int* stats = nullptr;             // nullable: [2]
-};
-int ngram_propose(const NgramArgs& a, hipStream_t st);
-// The next token of every row of fp32 logits [B][vocab] (row stride vocab, any 4-byte alignment), chosen on the device by the
-// contract of include/slam_engine.h (slam_sample_tokens): one argument block from the entry point down to the launches.
-struct SampleArgs {
-  const float* logits = nullptr;
-  int B = 0, vocab = 0;
-  const uint8_t* banned = nullptr;  // nullable: [vocab], non-zero = never chosen
-  int do_sample = 0, top_k = 1;     // greedy ignores top_k, temperature and top_p beyond their range checks
-  float temperature = 1.f, top_p = 1.f;
-  uint64_t seed = 0;
-  uint32_t step = 0;
-  int pad_id = 0, n_eos = 0;
-  const int64_t* row_ids = nullptr;  // nullable: the Philox row id of row b (default b)
-  const int* eos_ids = nullptr;      // device, [n_eos]
-  uint8_t* done = nullptr;           // nullable: [B], read (finished rows emit pad_id) and set (the token is an EOS id)
-  int64_t* next = nullptr;           // [B]
-  int64_t* out = nullptr;            // nullable: out[b * out_stride + step] = the token
-  int64_t out_stride = 0;
-  const uint32_t* steps = nullptr;   // nullable: [B / group], added to step per sequence (slam_sample_tokens_at)
-  int group = 1;                     // rows per sequence: row b draws with row id (b / group) at step + steps[..] + b % group
-  int64_t out_col = -1;              // the column of out; negative = step
-  void* ws = nullptr;                // sample_workspace_bytes(B, vocab, do_sample ? top_k : 1), 8-byte aligned
-  size_t ws_bytes = 0;
-  // slam_sample_tokens_warped: the second half of HF's warper chain on the ranked candidates. All four off (the defaults),
-  // or greedy, takes the launches of slam_sample_tokens_at.
-  float min_p = 0.f, typical_p = 1.f, epsilon_cutoff = 0.f, eta_cutoff = 0.f;
-};
-size_t sample_workspace_bytes(int B, int vocab, int top_k);  // host only
-int sample_tokens(const SampleArgs& a, hipStream_t st);
-// scores[b][i] = -inf for the tokens row b's history bans, the bits of logits[b][i] elsewhere (include/slam_engine.h:
-// slam_constrain_scores). scores may be logits: then only the bans are written.
-constexpr int CONSTRAIN_MAX_SEQS = 256;      // bad word sequences (SLAM_CONSTRAIN_MAX_SEQS)
-constexpr int CONSTRAIN_MAX_SEQ_LEN = 16;    // tokens per sequence (SLAM_CONSTRAIN_MAX_SEQ_LEN)
-constexpr int CONSTRAIN_MAX_BEGIN = 256;     // begin_suppress ids (SLAM_CONSTRAIN_MAX_BEGIN)
-constexpr int CONSTRAIN_MAX_HISTORY = 1 << 30;  // bound of step and of prompt_stride: their sum stays an int
-struct ConstrainArgs {
-  const float* logits = nullptr;
-  float* scores = nullptr;
-  int B = 0, vocab = 0;
-  int step = 0, ngram = 0, n_per_prompt = 1, prompt_stride = 0;
-  int ban_eos = 0, n_eos = 0, n_begin = 0, n_seqs = 0, n_seq_tokens = 0;
-  const int64_t* prompt = nullptr;    // [B / n_per_prompt][prompt_stride], right-padded
-  const int* prompt_len = nullptr;    // [B / n_per_prompt]
-  const int64_t* fresh = nullptr;     // [B][new_stride]: the new tokens; nullable at step 0
-  int64_t new_stride = 0;
-  const uint8_t* done = nullptr;      // nullable: [B], non-zero = the row is copied, not edited
-  const int* eos_ids = nullptr;       // [n_eos]
-  const int* begin_ids = nullptr;     // [n_begin]
-  const int* seq_tokens = nullptr;    // [n_seq_tokens]
-  const int* seq_offsets = nullptr;   // [n_seqs + 1]
-};
-int constrain_scores(const ConstrainArgs& a, hipStream_t st);
 // n samples per prompt: rows 0 .. B-1 of the cache kv (L x { K, V } x [bmax][nKV][cap][head_dim]), of lens and of the nullable
 // logits [.][vocab] fan out in place to rows b n .. b n + n - 1; only lens[b] keys of a row are copied. One launch per source
 // row in descending b (hazard-free for every (B, n): decode.hip's header). kv_bound: host bound of lens.
 int kv_repeat(bf16_t* kv, int* lens, float* logits, int B, int n, int bmax, int L, int nKV, int head_dim, int cap, int kv_bound,
               int vocab, hipStream_t st);
-// out[b * out_stride + column] = log-softmax of the raw fp32 row b at tokens[b] (include/slam_engine.h: slam_token_logprobs)
-size_t token_logprobs_workspace_bytes(int B, int vocab);  // host only
-int token_logprobs(const float* logits, int B, int vocab, const int64_t* tokens, const uint8_t* done, uint8_t* finished,
-                   float* out, int64_t out_stride, int column, void* ws, size_t ws_bytes, hipStream_t st);
-// classifier-free guidance (include/slam_engine.h: slam_cfg_scores): scores[b] = g (a - u) + u from the log-softmax a of logits
-// row b and u of row B + b, on token_logprobs' row statistics; ws holds the (m_c, s_c) pairs of the 2 B rows.
-size_t cfg_workspace_bytes(int B, int vocab);  // host only
-int cfg_scores(const float* logits, int B, int vocab, float g, float* scores, void* ws, size_t ws_bytes, hipStream_t st);
-int cfg_mirror_tokens(int64_t* next, int B, hipStream_t st);  // next[B + b] = next[b]
 // LM head fused with the row statistics (include/slam_engine.h: slam_op_score_rows): for row m of X (bf16 [M][K]) against the
 // head W (bf16 [V][K]) on v_mfma_f32_16x16x32_bf16, lp = log-softmax at targets[m] and argmax = the lowest id of the largest
 // score, from fp32 accumulators that are never stored. colmask: nullable, >= V bytes, non-zero = the column counts as -inf.

@@ -16,6 +16,41 @@ def test_library_exports_every_declared_symbol():
     assert sorted(lib._slam_signatures) == names
 
 
+def _defined_dynamic_symbols(path):
+    """Names in the dynamic symbol table of `path` that the library itself defines: nm -D, or ROCm's llvm-readelf."""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm")
+    if nm:
+        out = subprocess.run([nm, "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return {ln.split()[-1].split("@")[0] for ln in out.splitlines() if ln.strip()}
+    readelf = shutil.which("llvm-readelf") or next(
+        (p for p in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), d, "llvm-readelf") for d in ("llvm/bin", "lib/llvm/bin", "bin"))
+         if os.path.exists(p)), None)
+    assert readelf, "neither nm nor llvm-readelf found: the exported symbols cannot be read"
+    out = subprocess.run([readelf, "--dyn-syms", "-W", path], capture_output=True, text=True, check=True).stdout
+    syms = set()
+    for ln in out.splitlines():  # Num: Value Size Type Bind Vis Ndx Name
+        f = ln.split()
+        if len(f) == 8 and f[0].endswith(":") and f[0][:-1].isdigit() and f[6] != "UND" and f[3] != "SECTION":
+            syms.add(f[7].split("@")[0])
+    return syms
+
+
+def test_library_exports_nothing_but_the_declared_abi():
+    """The dynamic symbol table of libslam_engine.so (and of the probes build, where it has been built) is the set of functions
+    include/slam_engine.h declares, exactly: no internal launcher, no SlamEngine member, no C++ runtime instantiation that a
+    consumer's own symbols could preempt or share (csrc/exports.map)."""
+    from slamkit_amd.csrc import build as B
+    declared = set(E.header_symbols())
+    assert os.path.exists(B.LIB), B.LIB
+    for path in (B.LIB, B.PROBES_LIB):
+        if not os.path.exists(path):
+            continue
+        got = _defined_dynamic_symbols(path)
+        assert got == declared, (path, sorted(got - declared)[:20], sorted(declared - got)[:20])
+
+
 def test_engine_layout_without_gpu():
     lib = E.load_library()
     assert b"gfx950" in lib.slam_version()
