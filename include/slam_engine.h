@@ -1123,6 +1123,19 @@ int slam_op_cross_entropy(const void* logits /* bf16 [B*T][Vp] */, const int64_t
 int slam_op_cross_entropy_smooth(const void* logits /* bf16 [B*T][Vp] */, const int64_t* labels, double num_items,
                                  void* dlogits, float* row_loss, float* row_smooth, float* scratch2 /* {denom, loss} */, int B,
                                  int T, int Vp, int V, float epsilon, slam_stream_t s);
+/* The movers and scalers of the logits / d-logits buffer, one launch each; all bf16, all exact or rounded once. SLAM_EINVAL before
+ * any launch for a null pointer, a non-positive size, a row stride below ncols, V > Vp, Vp % 8, n % 8 or (the scalers) ncols % 8.
+ * copy_cols: dst[m][0 .. ncols) = src[m][0 .. ncols) with row strides ld_src / ld_dst (slam_forward's logits_out).
+ * unpad_logits: dst[b][t][0 .. V) = t < off[b + 1] - off[b] ? src[off[b] + t][0 .. V) : +0, src = Mp rows of Vp, off = int32 [B + 1]
+ *   (slam_op_unpad_pack leaves it behind the six [Mmax] arrays of its scratch).
+ * scale_bf16: x[i] = bf16(x[i] * scale), i < n (slam_backward's grad_scale).
+ * scale_rows_bf16: x[m][:] *= coef[m / T], x = [M][ncols] (slam_scale_loss_rows).
+ * scale_rows_unpadded_bf16: x[m][:] *= row[m] >= 0 ? coef[row[m]] : 0, x = [Mp][ncols], row = int32 [Mp] (slam_scale_loss_unpadded). */
+int slam_op_copy_cols(const void* src, int ld_src, void* dst, int ld_dst, int M, int ncols, slam_stream_t s);
+int slam_op_unpad_logits(const void* src, int Vp, void* dst, int V, const int32_t* off, int B, int T, int Mp, slam_stream_t s);
+int slam_op_scale_bf16(void* x, int64_t n, float scale, slam_stream_t s);
+int slam_op_scale_rows_bf16(void* x, const float* coef, int M, int T, int ncols, slam_stream_t s);
+int slam_op_scale_rows_unpadded_bf16(void* x, const float* coef, const int32_t* row, int Mp, int ncols, slam_stream_t s);
 /* gather-side embedding gradient for vocabularies beyond 512: dE[ids[m]] += dh[m], token order (deterministic) */
 size_t slam_op_embed_bwd_workspace(int M, int Vp);
 int slam_op_embed_bwd(const int64_t* ids, const void* dh /* bf16 [M][H] */, float* dE /* fp32 [Vp][H] */, int M, int H,

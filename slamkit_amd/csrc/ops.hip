@@ -346,6 +346,27 @@ int slam_op_cross_entropy_smooth(const void* logits, const int64_t* labels, doub
   return cross_entropy((const bf16_t*)logits, labels, num_items, (bf16_t*)dlogits, row_loss, scratch2, scratch2 + 1, B,
                        T, Vp, V, nullptr, epsilon, row_smooth, (hipStream_t)s);
 }
+// the movers and scalers of the logits / d-logits buffer (slam_forward's logits_out, slam_backward's grad_scale, the DPO row weights)
+int slam_op_copy_cols(const void* src, int ld_src, void* dst, int ld_dst, int M, int ncols, slam_stream_t s) {
+  if (!src || !dst || M <= 0 || ncols <= 0 || ld_src < ncols || ld_dst < ncols) return SLAM_EINVAL;
+  return copy_cols((const bf16_t*)src, ld_src, (bf16_t*)dst, ld_dst, M, ncols, (hipStream_t)s);
+}
+int slam_op_unpad_logits(const void* src, int Vp, void* dst, int V, const int32_t* off, int B, int T, int Mp, slam_stream_t s) {
+  if (!src || !dst || !off || B <= 0 || T <= 0 || Mp <= 0 || V <= 0 || V > Vp || (Vp & 7)) return SLAM_EINVAL;
+  return unpad_logits((const bf16_t*)src, Vp, (bf16_t*)dst, V, off, B, T, Mp, (hipStream_t)s);
+}
+int slam_op_scale_bf16(void* x, int64_t n, float scale, slam_stream_t s) {
+  if (!x || n <= 0 || (n & 7)) return SLAM_EINVAL;  // the kernel goes in 16-byte chunks
+  return scale_bf16((bf16_t*)x, (size_t)n, scale, (hipStream_t)s);
+}
+int slam_op_scale_rows_bf16(void* x, const float* coef, int M, int T, int ncols, slam_stream_t s) {
+  if (!x || !coef || M <= 0 || T <= 0 || ncols <= 0 || (ncols & 7)) return SLAM_EINVAL;
+  return scale_rows_bf16((bf16_t*)x, coef, M, T, ncols, (hipStream_t)s);
+}
+int slam_op_scale_rows_unpadded_bf16(void* x, const float* coef, const int32_t* row, int Mp, int ncols, slam_stream_t s) {
+  if (!x || !coef || !row || Mp <= 0 || ncols <= 0 || (ncols & 7)) return SLAM_EINVAL;
+  return scale_rows_unpadded_bf16((bf16_t*)x, coef, row, Mp, ncols, (hipStream_t)s);
+}
 size_t slam_op_embed_bwd_workspace(int M, int Vp) { return embed_bwd_workspace_ints(M, Vp) * sizeof(int); }
 int slam_op_embed_bwd(const int64_t* ids, const void* dh, float* dE, int M, int H, int Vp, int V, int pad_id, void* ws,
                       slam_stream_t s) {

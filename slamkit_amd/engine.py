@@ -233,6 +233,11 @@ def load_library(path: Optional[str] = None):
         "slam_op_colsum": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
         "slam_op_cross_entropy": (C.c_int, [vp, vp, f64, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_cross_entropy_smooth": (C.c_int, [vp, vp, f64, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
+        "slam_op_copy_cols": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_unpad_logits": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_scale_bf16": (C.c_int, [vp, i64, f32, vp]),
+        "slam_op_scale_rows_bf16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_scale_rows_unpadded_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
         "slam_op_embed_bwd_workspace": (sz, [C.c_int, C.c_int]),
         "slam_op_embed_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
         "slam_op_sr_round_bf16": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp]),

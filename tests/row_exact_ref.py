@@ -20,6 +20,18 @@ dw, db) use DELTA_SUM = M 2^-24 + 2^-16, the strictly sequential worst case - le
 terms. DELTA is a property of this reference, not of the kernels: tests/test_row_exact_host.py runs an fp32 restatement of
 every formula with strictly sequential reductions through the same rule and requires 0 violations.
 
+Rows longer than that budget (the real vocabulary: Vp = 152,320 is 75 steps of 8 columns for each of ce_big_kernel's 256
+threads) get DELTA as a function of the per-lane step count n, delta_steps(n), derived the same way. A step of 8 columns costs
+a lane's running value at most 8 roundoffs: the plain sums (the smoothing term sum_v z_v) add 8 terms, and the online softmax
+sum pays 8 adds inside the step for the terms that join and, for the ones already there, one product with exp(old max - new
+max), one add and the two ulp of that exp (4 <= 8; the ARGUMENT errors of the rescaling exps telescope: old max - new max summed
+over the steps is at most row max - z, the argument the single exp of the budget above already pays for). So a lane pays at
+most 8 n roundoffs where the budget above carries 32, and delta_steps(n) = DELTA + max(0, 8 n - 32) 2^-24: DELTA itself up to
+n = 4 (every case of test_gpu_row_exact.py: Vp <= 4104 is 3 steps), 2^-16 + 568 2^-24 = 4.9e-5 at n = 75. Legitimate for the same
+reason as DELTA_SUM: S is the sum of the absolute terms, and every term of these sums passes through at most that many
+roundings. tests/test_far_rows_host.py proves it the way test_row_exact_host.py proves DELTA: an fp32 restatement with every
+lane strictly sequential, at Vp = 152,320, 0 violations.
+
 One term the budget above does not carry, found by the -3e4 cross-entropy row: a kernel that forms p = exp(z - lse) with
 lse = max + log(sum) rounded to fp32 pays half an ulp of |lse| in the EXPONENT, i.e. a relative error ulp(|lse|) / 2 in p.
 That is 1.9e-6 at |lse| < 64 (inside the budget) and 1e-3 at |lse| = 3e4 (not). The rule does not grow to admit it; the
@@ -52,6 +64,16 @@ BAND_BITS = {BF16: 0x7FD5, F32: 0x7FD5AAAA}   # NaN payloads no kernel produces
 
 def delta_sum(M):
     return M * 2.0 ** -24 + DELTA
+
+
+def delta_steps(n):
+    """DELTA for a row whose lanes run n sequential steps of 8 columns (the module docstring derives it); DELTA up to n = 4."""
+    return DELTA + max(0, 8 * int(n) - 32) * 2.0 ** -24
+
+
+def ce_big_steps(Vp):
+    """Steps per thread of ce_big_kernel: 16-byte chunks of a row dealt round-robin to 256 threads."""
+    return -(-(Vp // 8) // 256)
 
 
 # ------------------------------------------------------------------------------------------------ rounding and the rule
@@ -341,23 +363,22 @@ def ce_targets(labels, V):
     return tgt.reshape(-1), count
 
 
-def cross_entropy(z, labels, V, num_items, eps=0.0):
-    """z [M][Vp] float64 (columns >= V are outside the softmax, whatever they hold).
-    -> dict of (ref, S) pairs: dlogits [M][Vp], row_loss, row_smooth, loss; and denom (exact)."""
+def cross_entropy_rows(z, tgt, V, denom, eps=0.0):
+    """The per-row part of `cross_entropy` for any run of rows, on z's device: z [rows][Vp] float64, tgt [rows] (ce_targets'
+    numbering: -1 = not scored), denom fixed beforehand. -> dict of (ref, S) pairs: dlogits, row_loss, row_smooth; valid."""
     M, Vp = z.shape
-    tgt, count = ce_targets(labels, V)
-    denom = float(num_items) if num_items > 0 else float(count)
+    tgt = tgt.to(z.device)
     valid = tgt >= 0
     zz = z[:, :V]
     mx = zz.max(-1, keepdim=True).values
     lse = (mx + torch.log(torch.exp(zz - mx).sum(-1, keepdim=True)))[:, 0]
     p = torch.exp(zz - lse[:, None])
-    onehot = torch.zeros(M, V, dtype=F64)
+    onehot = torch.zeros(M, V, dtype=F64, device=z.device)
     rows = valid.nonzero()[:, 0]
     onehot[rows, tgt[rows]] = 1.0
     zy = (zz * onehot).sum(-1)
-    d = torch.zeros(M, Vp, dtype=F64)
-    Sd = torch.zeros(M, Vp, dtype=F64)
+    d = torch.zeros(M, Vp, dtype=F64, device=z.device)
+    Sd = torch.zeros(M, Vp, dtype=F64, device=z.device)
     if denom > 0:
         d[:, :V] = (p - (1.0 - eps) * onehot - eps / V) / denom
         Sd[:, :V] = (p + (1.0 - eps) * onehot + eps / V) / denom
@@ -366,6 +387,16 @@ def cross_entropy(z, labels, V, num_items, eps=0.0):
     row_loss, S_rl = (lse - zy) * v, (lse.abs() + zy.abs()) * v
     zm = zz.mean(-1)
     row_smooth, S_rs = (lse - zm) * v, (lse.abs() + zm.abs()) * v
+    return {"dlogits": (d, Sd), "row_loss": (row_loss, S_rl), "row_smooth": (row_smooth, S_rs), "valid": valid}
+
+
+def cross_entropy(z, labels, V, num_items, eps=0.0):
+    """z [M][Vp] float64 (columns >= V are outside the softmax, whatever they hold).
+    -> dict of (ref, S) pairs: dlogits [M][Vp], row_loss, row_smooth, loss; and denom (exact)."""
+    tgt, count = ce_targets(labels, V)
+    denom = float(num_items) if num_items > 0 else float(count)
+    r = cross_entropy_rows(z, tgt, V, denom, eps)
+    (d, Sd), (row_loss, S_rl), (row_smooth, S_rs), valid = r["dlogits"], r["row_loss"], r["row_smooth"], r["valid"]
     if denom > 0:
         loss = ((1.0 - eps) * row_loss.sum() + eps * row_smooth.sum()) / denom
         S_loss = ((1.0 - eps) * S_rl.sum() + eps * S_rs.sum()) / denom
