@@ -831,6 +831,92 @@ int slam_adafactor_bind_workspace(SlamEngine* h, void* workspace, size_t bytes);
 int slam_adafactor_step(SlamEngine* h, float* master_f32, float* state_f32, const float* norm_out, double lr, double eps1,
                         double clip_threshold, double decay_rate, double weight_decay, int32_t step, int32_t zero_grad,
                         slam_stream_t stream);
+
+/* ---- Muon: optim = "muon" ----------------------------------------------------------------------------------------------------
+ * torch.optim.Muon as torch 2.10 defines it (torch/optim/_muon.py: _single_tensor_muon, _zeropower_via_newtonschulz), per HF
+ * parameter tensor, for the 2-D weights of the decoder layers (q/k/v/o and the MLP matrices); everything else - embeddings, an
+ * untied head, norm weights, biases - stays with AdamW, which the caller runs through slam_adamw_range* over the runs of the
+ * flat buffer that no Muon matrix covers.
+ *
+ * For an HF matrix W [rows][cols] with momentum buffer B (fp32, rows * cols floats in HF row-major order, zeros before step 1):
+ *   prepare  g = gradient * norm_out[1];  B <- mu B + (1 - mu) g;  U = (1 - mu) g + mu B (nesterov) or B;  X = bf16(U).
+ *            fp32, every multiplication and addition rounded by itself; mu = (float)momentum, 1 - mu = (float)(1.0 - momentum).
+ *   pack     X is stored [n][m], n = min(rows, cols), m = max(rows, cols): transposed when rows > cols.
+ *   norm     s = sum of x^2 over bf16 X in fp32 (order: csrc/muon.hip), nrm = max(bf16(sqrtf(s)), bf16(eps)): torch's norm of a
+ *            bf16 tensor is rounded to bf16 before the clamp;  X <- bf16(X / nrm), a correctly rounded fp32 division.
+ *   iterate  ns_steps times:  A = bf16(X X^T);  P = bf16(b A + c (A A));  X <- bf16(a X + P X).  Every product is accumulated in
+ *            fp32 by v_mfma_f32_16x16x32_bf16 over the contraction index in ascending 32-deep steps and rounded to bf16 once,
+ *            after the epilogue fmaf(beta, R, alpha * acc) (alpha * acc alone when there is no R). A and P are symmetric to the
+ *            bit: only the 128 x 128 tiles on or below the diagonal are computed and an off-diagonal tile is stored twice.
+ *   apply    O = X (transposed back when rows > cols); in fp32, each operation rounded by itself:
+ *            p <- p * (float)(1.0 - lr weight_decay);  p <- p - (float)(lr ratio) * O, ratio (double) = 1 for adjust_lr 0 (none),
+ *            sqrt(max(1, rows / cols)) for 1 ("original"), 0.2 sqrt(max(rows, cols)) for 2 ("match_rms_adamw").
+ *            master_f32 given: the master is updated and the bf16 parameter written from it; NULL: the bf16 parameter is read,
+ *            updated and rounded once - with "adamw_sr" = 1 stochastically, array 0 of slam_op_sr_round_bf16 keyed on
+ *            ("adamw_sr_seed", step, flat index), as slam_adafactor_step does. slam_set_decay_mask is honoured per segment.
+ * No atomics anywhere: a step gives the same bits on every run, with zero_grad 0 or 1 and from either gradient buffer given
+ * equal values.
+ *
+ * SlamMuonSegment = one Muon matrix over the flat buffer; offset / rows / cols / pattern as SlamAdafactorSegment's.
+ * slam_muon_set_segments: validates and uploads the table (one small synchronous upload; outside stream capture). SLAM_EINVAL
+ *   with a message: n < 1, a NULL table, rows or cols < 1, a segment that is not a matrix (rows or cols < 2), an unknown pattern
+ *   or pattern rows that are no multiple of 32, offset, rows or cols not a multiple of 8, a segment that leaves [0,
+ *   slam_param_count), two segments that share an element, more than 64 distinct shapes. NULL with n == 0 clears the table.
+ *   Segments of equal (rows, cols) form a shape class; the classes are numbered in order of first appearance.
+ * slam_muon_sizes: momentum_floats = the length of the caller's fp32 momentum buffer (the segments in table order, without gaps);
+ *   workspace_bytes for slam_muon_bind_workspace. SLAM_ESTATE without a table.
+ * slam_muon_bind_workspace: caller-owned device memory, 256-byte aligned, at least workspace_bytes (SLAM_ENOMEM when shorter);
+ *   NULL unbinds. Nothing beyond workspace_bytes is touched; the contents need not survive between steps. The workspace holds
+ *   the packed bf16 image of EVERY Muon matrix (2 bytes per Muon element: prepare and apply are one launch each for the whole
+ *   model) and, sized by the largest class because the classes are iterated one after another, a second packed image and the two
+ *   Gram buffers, plus one float per 64 x 64 tile. Slam-358M: 716 MB + 418 MB + 2 x 77 MB + 0.3 MB.
+ * slam_muon_class_count / slam_muon_class_info: the shape classes and where the workspace holds them: the class's `count` packed
+ *   [n][m] matrices lie at x_byte_offset at the stride n * m elements, their sum-of-squares partials (`parts` floats a matrix)
+ *   at part_byte_offset.
+ *
+ * slam_muon_step: prepare (one launch) - per class: norm and scale (one launch), 3 ns_steps product launches over the class as
+ *   one batch - apply (one launch), all on `stream`: 2 + classes (1 + 3 ns_steps) launches whatever the number of layers. Only
+ *   Muon elements are written. zero_grad != 0 clears the Muon elements of the fp32 gradient buffer (the AdamW ranges clear
+ *   theirs). `step` (>= 1) only keys the stochastic rounding. The transposed weight images are left stale as after
+ *   slam_adamw_range*: the next slam_backward, or slam_refresh_transposed, refreshes them.
+ *   Refused with a message: "overlap_adamw" on, no segment table or no bound workspace (SLAM_ESTATE); ns_steps outside 1 .. 16,
+ *   momentum_f32 NULL, momentum outside [0, 1), adjust_lr outside 0 .. 2, step < 1 (SLAM_EINVAL). There is no ranged form.
+ * The single-op doors (tests): slam_op_muon_prepare (momentum update, packed X and partials into the workspace), slam_op_muon_ns
+ *   (orthogonalise `batch` packed [n][m] matrices, n <= m, multiples of 8, in place at `stride` elements; partials == NULL: the
+ *   sums of squares are taken here, over 8192-element chunks; ws: slam_op_muon_ns_workspace bytes, 256-byte aligned) and
+ *   slam_op_muon_apply (o_packed == NULL: the workspace's packed image). slam_muon_step equals slam_op_muon_prepare, slam_op_muon_ns
+ *   per class on the workspace with prepare's partials, slam_op_muon_apply, bit for bit. slam_op_muon_syrk: C[i] = beta R[i] +
+ *   alpha X[i] X[i]^T; slam_op_muon_mm: Y[i] = beta R[i] + alpha P[i] X[i] (P [n][n], X [n][m]); R nullable; strides in elements,
+ *   multiples of 8; R and the output share the output's row length. */
+typedef struct SlamMuonSegment {
+  int64_t offset;
+  int32_t rows, cols;
+  int32_t pattern;
+  int32_t reserved;
+} SlamMuonSegment;
+typedef struct SlamMuonClass {
+  int32_t rows, cols, n, m, count, parts;
+  int64_t x_byte_offset, part_byte_offset;
+} SlamMuonClass;
+int slam_muon_set_segments(SlamEngine* h, const SlamMuonSegment* segs, int32_t n);
+int slam_muon_sizes(SlamEngine* h, int64_t* momentum_floats, size_t* workspace_bytes);
+int slam_muon_bind_workspace(SlamEngine* h, void* workspace, size_t bytes);
+int32_t slam_muon_class_count(SlamEngine* h);
+int slam_muon_class_info(SlamEngine* h, int32_t i, SlamMuonClass* out);
+int slam_muon_step(SlamEngine* h, float* master_f32, float* momentum_f32, const float* norm_out, double lr, double weight_decay,
+                   double momentum, int32_t nesterov, int32_t ns_steps, double a, double b, double c, double eps, int32_t adjust_lr,
+                   int32_t step, int32_t zero_grad, slam_stream_t stream);
+int slam_op_muon_prepare(SlamEngine* h, float* momentum_f32, const float* norm_out, double momentum, int32_t nesterov,
+                         int32_t zero_grad, slam_stream_t stream);
+size_t slam_op_muon_ns_workspace(int32_t batch, int32_t n, int32_t m);
+int slam_op_muon_ns(void* x_bf16, int32_t batch, int32_t n, int32_t m, int64_t stride, const float* partials, int32_t parts,
+                    int32_t ns_steps, double a, double b, double c, double eps, void* ws, size_t ws_bytes, slam_stream_t stream);
+int slam_op_muon_apply(SlamEngine* h, float* master_f32, const void* o_packed_bf16, double lr, double weight_decay,
+                       int32_t adjust_lr, int32_t step, slam_stream_t stream);
+int slam_op_muon_syrk(const void* x, const void* r, void* c, int32_t batch, int32_t n, int32_t m, int64_t stride_x, int64_t stride_r,
+                      int64_t stride_c, float alpha, float beta, slam_stream_t stream);
+int slam_op_muon_mm(const void* p, const void* x, const void* r, void* y, int32_t batch, int32_t n, int32_t m, int64_t stride_p,
+                    int64_t stride_x, int64_t stride_r, int64_t stride_y, float alpha, float beta, slam_stream_t stream);
 /* Another stream (the all-gather of a parameter bucket) is still writing the bound bf16 parameters in [offset, offset +
  * count); `event` (hipEvent_t, owned by the caller, alive until the next forward was enqueued) is recorded behind that
  * write. The next slam_forward waits for it right before its first read of the range - layer by layer, so the gather of

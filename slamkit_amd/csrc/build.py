@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIB_DIR, "libslam_engine.so")
-SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "decode.hip", "sampling.hip", "quant.hip",
+SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "muon.hip", "decode.hip", "sampling.hip", "quant.hip",
            "engine.hip", "engine_cache.hip", "engine_optim.hip", "engine_comm.hip", "ops.hip"]
 HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "slam_engine.h")]
 ENGINE_HEADER = "engine_impl.h"  # private to the engine*.hip files, and a dependency of those alone

@@ -116,6 +116,11 @@ struct SlamEngine {
   std::vector<AfSeg> af_host;
   AfPlan af_plan;
   float* af_ws = nullptr;
+  // slam_muon_set_segments: the Muon matrices (kernels.h MuSeg, class order); mu_plan.segs is engine-owned device memory.
+  // mu_ws: the caller's workspace (mu_plan.ws_bytes).
+  std::vector<MuSeg> mu_host;
+  MuPlan mu_plan;
+  char* mu_ws = nullptr;
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_chunk;  // [0] embedding, [1 + l] layer l, [L + 1] final norm (+ an untied lm_head and its transposed image)
@@ -199,6 +204,7 @@ struct SlamEngine {
     if (comm_stream) { (void)hipStreamSynchronize(comm_stream); (void)hipStreamDestroy(comm_stream); }
     if (nd_dev) (void)hipFree(nd_dev);
     if (af_plan.segs) (void)hipFree((void*)af_plan.segs);
+    if (mu_plan.segs) (void)hipFree((void*)mu_plan.segs);
   }
   // parameter ranges another stream is still writing (sharded optimizer: the bf16 parameter all-gather on the
   // communication stream): the next reader waits for the event right before its first read of the range

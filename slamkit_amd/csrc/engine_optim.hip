@@ -1,5 +1,5 @@
-// The optimizer side of a SlamEngine (include/slam_engine.h): gradient norm and clip, the AdamW and Adafactor entry points, the
-// no-decay set, the bf16 gradient image, slam_zero_grads and slam_cast_params. The kernels are in optimizer.hip and adafactor.hip.
+// The optimizer side of a SlamEngine (include/slam_engine.h): gradient norm and clip, the AdamW, Adafactor and Muon entry points, the
+// no-decay set, the bf16 gradient image, slam_zero_grads and slam_cast_params. The kernels are in optimizer.hip, adafactor.hip and muon.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -316,6 +316,188 @@ int slam_adafactor_step(SlamEngine* h, float* master, float* state, const float*
   CK(adafactor_step(h->af_plan, a, st));
   if (zero_grad) CK((int)hipMemsetAsync(h->grads, 0, (size_t)h->n_params * sizeof(float), st));
   return slam_refresh_transposed(h, stream);
+}
+
+// ---- Muon (the contract is in the header; the kernels in muon.hip) ---------------------------------------------------------
+int slam_muon_set_segments(SlamEngine* h, const SlamMuonSegment* segs, int32_t n) {
+  if (!h) return SLAM_EINVAL;
+  std::vector<MuSeg> t;
+  if (segs || n) {
+    if (!segs || n < 1) return h->fail(SLAM_EINVAL, "muon segments: a table of n >= 1 segments, or NULL and 0 to clear");
+    std::vector<std::pair<int64_t, int64_t>> iv;  // the element intervals the segments cover
+    for (int32_t i = 0; i < n; ++i) {
+      const SlamMuonSegment& g = segs[i];
+      const std::string at = "muon segment " + std::to_string(i) + ": ";
+      if (g.rows < 1 || g.cols < 1) return h->fail(SLAM_EINVAL, at + "rows and cols must be positive");
+      if (g.rows < 2 || g.cols < 2) return h->fail(SLAM_EINVAL, at + "not a matrix: Muon takes 2-D weights only");
+      if (g.pattern < 0 || g.pattern > 2) return h->fail(SLAM_EINVAL, at + "pattern is 0 (contiguous), 1 or 2 (32 rows of every 64, phase 0 or 32)");
+      if (g.pattern && (g.rows % 32)) return h->fail(SLAM_EINVAL, at + "rows in groups of 32 need rows % 32 == 0");
+      if ((g.offset & 7) || (g.cols & 7) || (g.rows & 7)) return h->fail(SLAM_EINVAL, at + "misaligned: offset, rows and cols must be multiples of 8");
+      const int64_t c = g.cols;
+      const int64_t span = g.pattern ? ((int64_t)(g.rows / 32 - 1) * 64 + (g.pattern == 2 ? 32 : 0) + 32) * c : (int64_t)g.rows * c;
+      if (g.offset < 0 || g.offset > h->n_params || span > h->n_params - g.offset)
+        return h->fail(SLAM_EINVAL, at + "out of range: it leaves [0, slam_param_count)");
+      if (!g.pattern) {
+        iv.push_back({g.offset, g.offset + span});
+      } else {
+        for (int64_t k = 0; k < g.rows / 32; ++k) {
+          const int64_t lo = g.offset + (k * 64 + (g.pattern == 2 ? 32 : 0)) * c;
+          iv.push_back({lo, lo + 32 * c});
+        }
+      }
+      MuSeg s;
+      s.off = g.offset; s.rows = g.rows; s.cols = g.cols;
+      s.phase = g.pattern == 0 ? -1 : g.pattern == 1 ? 0 : 32;
+      t.push_back(s);
+    }
+    std::sort(iv.begin(), iv.end());
+    for (size_t i = 1; i < iv.size(); ++i)
+      if (iv[i].first < iv[i - 1].second) return h->fail(SLAM_EINVAL, "muon segments overlap: two segments share an element");
+  }
+  MuPlan plan;
+  MuSeg* dev = nullptr;
+  if (!t.empty()) {
+    if (muon_layout(t.data(), (int)t.size(), &plan))
+      return h->fail(SLAM_EINVAL, "muon segments: more shape classes or tiles than one step holds");
+    for (int c = 0; c < plan.n_classes; ++c)
+      if (plan.cls[c].count > 65535) return h->fail(SLAM_EINVAL, "muon segments: more than 65535 matrices of one shape");
+    CK((int)hipMalloc(&dev, t.size() * sizeof(MuSeg)));
+    const int r = (int)hipMemcpy(dev, t.data(), t.size() * sizeof(MuSeg), hipMemcpyHostToDevice);
+    if (r) { (void)hipFree(dev); CK(r); }
+    plan.segs = dev;
+  }
+  if (h->mu_plan.segs) CK((int)hipFree((void*)h->mu_plan.segs));  // synchronises with the device: no step in flight reads the old table
+  h->mu_plan = plan;
+  h->mu_host.swap(t);
+  h->mu_ws = nullptr;  // sized for the table that went
+  return SLAM_OK;
+}
+int slam_muon_sizes(SlamEngine* h, int64_t* momentum_floats, size_t* workspace_bytes) {
+  if (!h || !momentum_floats || !workspace_bytes) return SLAM_EINVAL;
+  if (h->mu_host.empty()) return h->fail(SLAM_ESTATE, "muon: no segment table (slam_muon_set_segments)");
+  *momentum_floats = h->mu_plan.elems;
+  *workspace_bytes = h->mu_plan.ws_bytes;
+  return SLAM_OK;
+}
+int slam_muon_bind_workspace(SlamEngine* h, void* workspace, size_t bytes) {
+  if (!h) return SLAM_EINVAL;
+  if (!workspace) { h->mu_ws = nullptr; return SLAM_OK; }
+  if (h->mu_host.empty()) return h->fail(SLAM_ESTATE, "muon: no segment table (slam_muon_set_segments)");
+  if (((uintptr_t)workspace) & 255) return h->fail(SLAM_EINVAL, "muon workspace must be 256-byte aligned");
+  if (bytes < h->mu_plan.ws_bytes) return h->fail(SLAM_ENOMEM, "muon workspace too small");
+  h->mu_ws = (char*)workspace;
+  return SLAM_OK;
+}
+int32_t slam_muon_class_count(SlamEngine* h) { return h ? h->mu_plan.n_classes : SLAM_EINVAL; }
+int slam_muon_class_info(SlamEngine* h, int32_t i, SlamMuonClass* out) {
+  if (!h || !out) return SLAM_EINVAL;
+  if (i < 0 || i >= h->mu_plan.n_classes) return h->fail(SLAM_EINVAL, "muon class index out of range");
+  const MuClass& k = h->mu_plan.cls[i];
+  out->rows = k.rows; out->cols = k.cols; out->n = k.n; out->m = k.m; out->count = k.count; out->parts = k.parts;
+  out->x_byte_offset = (int64_t)h->mu_plan.x_off + k.pack * 2;
+  out->part_byte_offset = (int64_t)h->mu_plan.part_off + (int64_t)k.part0 * 4;
+  return SLAM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// what the three Muon launch groups share: the checks of a call that touches the engine's buffers, and the arguments
+int muon_begin(SlamEngine* h, const char* what, hipStream_t st, MuArgs* a) {
+  if (h->overlap_adamw) return h->fail(SLAM_ESTATE, std::string(what) + " with overlap_adamw on: the overlapped chunks belong to AdamW");
+  if (h->mu_host.empty()) return h->fail(SLAM_ESTATE, std::string(what) + " without a segment table (slam_muon_set_segments)");
+  if (!h->mu_ws) return h->fail(SLAM_ESTATE, std::string(what) + " without a workspace (slam_muon_bind_workspace)");
+  if (!h->grads || !h->params) return h->fail(SLAM_ESTATE, "bind params first");
+  CK(join_optimizer(h, st));
+  CK(join_params(h, st));
+  a->params = h->params; a->ws = h->mu_ws;
+  a->g_bf16 = h->gfinal == 2;  // the last backward kept its final values in bf16 only (slam_set_grad_image's buffer)
+  a->g = a->g_bf16 ? (const void*)h->g16 : (const void*)h->grads;
+  a->sr.on = h->adamw_sr; a->sr.seed = h->adamw_sr_seed;
+  if (h->nd_dev) { a->nd.bounds = h->nd_dev; a->nd.n = (int)h->nd_host.size(); }
+  return SLAM_OK;
+}
+int muon_momentum_args(SlamEngine* h, const char* what, float* mom, const float* norm_out, double momentum, int nesterov, int zero_grad,
+                       MuArgs* a) {
+  if (!mom) return h->fail(SLAM_EINVAL, std::string(what) + ": momentum_f32 is NULL");
+  if (!(momentum >= 0.0 && momentum < 1.0)) return h->fail(SLAM_EINVAL, std::string(what) + ": momentum must lie in [0, 1)");
+  a->mom = mom; a->clip = norm_out;
+  a->mu = (float)momentum; a->omm = (float)(1.0 - momentum);
+  a->nesterov = nesterov != 0;
+  a->gzero = zero_grad ? h->grads : nullptr;
+  return SLAM_OK;
+}
+int muon_apply_args(SlamEngine* h, const char* what, float* master, double lr, double wd, int adjust_lr, int step, MuArgs* a) {
+  if (adjust_lr < 0 || adjust_lr > 2) return h->fail(SLAM_EINVAL, std::string(what) + ": adjust_lr is 0 (none), 1 (original) or 2 (match_rms_adamw)");
+  if (step < 1) return h->fail(SLAM_EINVAL, std::string(what) + ": step counts from 1");
+  a->master = master; a->lr = lr; a->wd = wd; a->adjust_lr = adjust_lr; a->step = step;
+  return SLAM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int slam_muon_step(SlamEngine* h, float* master, float* mom, const float* norm_out, double lr, double wd, double momentum,
+                   int32_t nesterov, int32_t ns_steps, double a, double b, double c, double eps, int32_t adjust_lr, int32_t step,
+                   int32_t zero_grad, slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  MuArgs m;
+  if (ns_steps < 1 || ns_steps > 16) return h->fail(SLAM_EINVAL, "muon step: ns_steps must lie in 1 .. 16");
+  if (int r = muon_momentum_args(h, "muon step", mom, norm_out, momentum, nesterov, zero_grad, &m)) return r;
+  if (int r = muon_apply_args(h, "muon step", master, lr, wd, adjust_lr, step, &m)) return r;
+  if (int r = muon_begin(h, "muon step", st, &m)) return r;
+  h->w8_valid = false;
+  m.ns_steps = ns_steps; m.a = (float)a; m.b = (float)b; m.c = (float)c; m.eps = (float)eps;
+  CK(muon_step(h->mu_plan, m, st));
+  h->params_t_dirty = h->params_t != nullptr;
+  return SLAM_OK;
+}
+int slam_op_muon_prepare(SlamEngine* h, float* mom, const float* norm_out, double momentum, int32_t nesterov, int32_t zero_grad,
+                         slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  MuArgs m;
+  if (int r = muon_momentum_args(h, "muon prepare", mom, norm_out, momentum, nesterov, zero_grad, &m)) return r;
+  if (int r = muon_begin(h, "muon prepare", (hipStream_t)stream, &m)) return r;
+  CK(muon_prepare(h->mu_plan, m, (hipStream_t)stream));
+  return SLAM_OK;
+}
+int slam_op_muon_apply(SlamEngine* h, float* master, const void* o_packed, double lr, double wd, int32_t adjust_lr, int32_t step,
+                       slam_stream_t stream) {
+  if (!h) return SLAM_EINVAL;
+  MuArgs m;
+  if (int r = muon_apply_args(h, "muon apply", master, lr, wd, adjust_lr, step, &m)) return r;
+  if (int r = muon_begin(h, "muon apply", (hipStream_t)stream, &m)) return r;
+  h->w8_valid = false;
+  CK(muon_apply(h->mu_plan, m, o_packed ? (const bf16_t*)o_packed : (const bf16_t*)(h->mu_ws + h->mu_plan.x_off), (hipStream_t)stream));
+  h->params_t_dirty = h->params_t != nullptr;
+  return SLAM_OK;
+}
+size_t slam_op_muon_ns_workspace(int32_t batch, int32_t n, int32_t m) { return muon_ns_workspace_bytes(batch, n, m); }
+int slam_op_muon_ns(void* x, int32_t batch, int32_t n, int32_t m, int64_t stride, const float* partials, int32_t parts,
+                    int32_t ns_steps, double a, double b, double c, double eps, void* ws, size_t ws_bytes, slam_stream_t stream) {
+  const size_t need = muon_ns_workspace_bytes(batch, n, m);
+  if (!x || !ws || !need || n > m || ns_steps < 1 || ns_steps > 16 || (partials && parts < 1) || (((uintptr_t)ws) & 255) ||
+      (((uintptr_t)x) & 15))
+    return SLAM_EINVAL;
+  if (ws_bytes < need) return SLAM_ENOMEM;
+  const size_t xy = ((size_t)batch * n * m * 2 + 255) & ~(size_t)255, aa = ((size_t)batch * n * n * 2 + 255) & ~(size_t)255;
+  char* w = (char*)ws;
+  const int r = muon_ns((bf16_t*)x, batch, n, m, stride, partials, parts, ns_steps, (float)a, (float)b, (float)c, (float)eps,
+                        (bf16_t*)w, (bf16_t*)(w + xy), (bf16_t*)(w + xy + aa), (float*)(w + xy + 2 * aa), (hipStream_t)stream);
+  return r < 0 ? SLAM_EINVAL : r;
+}
+int slam_op_muon_syrk(const void* x, const void* r, void* c, int32_t batch, int32_t n, int32_t m, int64_t stride_x, int64_t stride_r,
+                      int64_t stride_c, float alpha, float beta, slam_stream_t stream) {
+  const int e = muon_syrk((const bf16_t*)x, (const bf16_t*)r, (bf16_t*)c, batch, n, m, stride_x, stride_r, stride_c, alpha, beta,
+                          (hipStream_t)stream);
+  return e < 0 ? SLAM_EINVAL : e;
+}
+int slam_op_muon_mm(const void* p, const void* x, const void* r, void* y, int32_t batch, int32_t n, int32_t m, int64_t stride_p,
+                    int64_t stride_x, int64_t stride_r, int64_t stride_y, float alpha, float beta, slam_stream_t stream) {
+  const int e = muon_mm((const bf16_t*)p, (const bf16_t*)x, (const bf16_t*)r, (bf16_t*)y, batch, n, m, stride_p, stride_x, stride_r,
+                        stride_y, alpha, beta, (hipStream_t)stream);
+  return e < 0 ? SLAM_EINVAL : e;
 }
 
 // fp32 gradient range <-> bf16 communication image (the data-parallel exchange in bf16: the reference's DDP reduces bf16

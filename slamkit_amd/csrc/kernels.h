@@ -289,6 +289,66 @@ struct AfArgs {
 // host: lays the segments (off, rows, cols, factored, phase given) out over state and workspace; fills the rest and `plan`
 void adafactor_layout(AfSeg* segs, int n, AfPlan* plan);
 int adafactor_step(const AfPlan& plan, const AfArgs& a, hipStream_t st);
+// ---- Muon (muon.hip; the contract is in include/slam_engine.h: slam_muon_step) ------------------------------------------------
+// One Muon matrix: an HF [rows][cols] weight over the flat buffer (row pattern as AfSeg), its rows * cols momentum floats (HF
+// row-major, segments in TABLE order) and its packed bf16 image [n][m], n = min(rows, cols), m = max(rows, cols): the matrix
+// itself, or its transpose when rows > cols. The kernels' table is sorted by shape class (stable), so the packed images and the
+// sum-of-squares partials of one class lie behind each other at the constant strides n * m and `parts`.
+constexpr int MU_TILE = 64;  // prepare / apply: a block owns 64 rows x 64 columns of the HF matrix; tiles numbered row block major
+struct MuSeg {
+  int64_t off = 0, mom = 0, pack = 0;  // first element: flat buffer / momentum buffer / packed buffer
+  int rows = 0, cols = 0, phase = -1;
+  int tile0 = 0, n_tc = 0;             // first tile (= first partial); column tiles
+};
+struct MuClass {
+  int rows = 0, cols = 0, n = 0, m = 0, count = 0;
+  int64_t pack = 0;         // first packed element of the class
+  int part0 = 0, parts = 0; // first partial of the class; partials (tiles) of one matrix
+};
+constexpr int MU_MAX_CLASSES = 64;
+struct MuPlan {
+  const MuSeg* segs = nullptr;  // device, class order
+  int n_segs = 0, n_tiles = 0, n_classes = 0;
+  MuClass cls[MU_MAX_CLASSES];
+  int64_t elems = 0;            // Muon elements = momentum floats = packed elements
+  // workspace bytes (each region 256-byte aligned): packed X [elems] | Y [max count n m] | A, P [max count n n] | partials [n_tiles]
+  size_t x_off = 0, y_off = 0, a_off = 0, p_off = 0, part_off = 0, ws_bytes = 0;
+};
+struct MuArgs {
+  float* master = nullptr;   // nullable: the bf16 parameters are the only copy
+  bf16_t* params = nullptr;
+  const void* g = nullptr;   // float, or bf16_t when g_bf16
+  int g_bf16 = 0;
+  float* gzero = nullptr;    // nullable: the fp32 gradient buffer, whose Muon elements the prepare launch clears
+  float* mom = nullptr;
+  char* ws = nullptr;
+  const float* clip = nullptr;
+  double lr = 0, wd = 0;
+  float mu = 0.95f, omm = 0.05f;
+  int nesterov = 1, ns_steps = 5, adjust_lr = 2, step = 1;
+  float a = 3.4445f, b = -4.7750f, c = 2.0315f, eps = 1e-7f;
+  AdamSR sr;
+  AdamNoDecay nd;
+};
+// host: segs (off, rows, cols, phase given, table order) -> mom offsets, class order, tiles, packed offsets; fills `plan` but segs
+// (the caller uploads the sorted table). -1: more than MU_MAX_CLASSES shape classes or more tiles than a launch holds.
+int muon_layout(MuSeg* segs, int n, MuPlan* plan);
+int muon_prepare(const MuPlan& plan, const MuArgs& a, hipStream_t st);
+int muon_apply(const MuPlan& plan, const MuArgs& a, const bf16_t* o_packed, hipStream_t st);
+int muon_step(const MuPlan& plan, const MuArgs& a, hipStream_t st);
+// C[i] = beta R[i] + alpha X[i] X[i]^T ([n][n] from [n][m]; lower-triangle tiles, mirrored) and Y[i] = beta R[i] + alpha P[i] X[i]
+// ([n][n] x [n][m]); n, m and the strides (elements) multiples of 8; R nullable (then beta is not read)
+int muon_syrk(const bf16_t* X, const bf16_t* R, bf16_t* C, int batch, int n, int m, int64_t sx, int64_t sr, int64_t sc, float alpha,
+              float beta, hipStream_t st);
+int muon_mm(const bf16_t* P, const bf16_t* X, const bf16_t* R, bf16_t* Y, int batch, int n, int m, int64_t sp, int64_t sx, int64_t sr,
+            int64_t sy, float alpha, float beta, hipStream_t st);
+// Newton-Schulz on `batch` packed [n][m] matrices (n <= m) at stride sx, in place. part: `parts` partial sums of squares per
+// matrix at stride parts, or nullptr: computed here into the scratch (muon_ns_partials per matrix). Y [batch n m], A, P [batch n n].
+constexpr int MU_NORM_CHUNK = 8192;
+inline int muon_ns_partials(int n, int m) { return (int)(((int64_t)n * m + MU_NORM_CHUNK - 1) / MU_NORM_CHUNK); }
+size_t muon_ns_workspace_bytes(int batch, int n, int m);
+int muon_ns(bf16_t* X, int batch, int n, int m, int64_t sx, const float* part, int parts, int ns_steps, float a, float b, float c,
+            float eps, bf16_t* Y, bf16_t* A, bf16_t* P, float* part_scratch, hipStream_t st);
 int f32_to_bf16(const float* s, bf16_t* d, size_t n, hipStream_t st);
 // the same conversion, emitting one GradSink partial (sum of squares of the rounded values) per 8192-element block
 int f32_to_bf16_sumsq_slots(size_t n);

@@ -37,6 +37,22 @@ class SlamAdafactorSegment(C.Structure):
     _fields_ = [("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("factored", C.c_int32), ("pattern", C.c_int32)]
 
 
+class SlamMuonSegment(C.Structure):
+    """One Muon matrix over the flat buffer (slam_muon_set_segments); offset / rows / cols / pattern as SlamAdafactorSegment's."""
+    _fields_ = [("offset", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("pattern", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SlamMuonClass(C.Structure):
+    """One shape class of the Muon table and where the bound workspace holds its packed matrices and partials."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("n", C.c_int32), ("m", C.c_int32), ("count", C.c_int32),
+                ("parts", C.c_int32), ("x_byte_offset", C.c_int64), ("part_byte_offset", C.c_int64)]
+
+
+MUON_ADJUST_LR = {None: 0, "original": 1, "match_rms_adamw": 2}  # slam_muon_step's adjust_lr
+MUON_NS_COEFFICIENTS = (3.4445, -4.7750, 2.0315)               # torch.optim.Muon's defaults
+MUON_EPS = 1e-7
+
+
 class SlamSampleDesc(C.Structure):
     _fields_ = [
         ("do_sample", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float), ("top_p", C.c_float),
@@ -159,6 +175,18 @@ def load_library(path: Optional[str] = None):
         "slam_adafactor_sizes": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
         "slam_adafactor_bind_workspace": (C.c_int, [vp, vp, sz]),
         "slam_adafactor_step": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
+        "slam_muon_set_segments": (C.c_int, [vp, C.POINTER(SlamMuonSegment), i32]),
+        "slam_muon_sizes": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
+        "slam_muon_bind_workspace": (C.c_int, [vp, vp, sz]),
+        "slam_muon_class_count": (i32, [vp]),
+        "slam_muon_class_info": (C.c_int, [vp, i32, C.POINTER(SlamMuonClass)]),
+        "slam_muon_step": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, i32, i32, f64, f64, f64, f64, i32, i32, i32, vp]),
+        "slam_op_muon_prepare": (C.c_int, [vp, vp, vp, f64, i32, i32, vp]),
+        "slam_op_muon_ns_workspace": (sz, [i32, i32, i32]),
+        "slam_op_muon_ns": (C.c_int, [vp, i32, i32, i32, i64, vp, i32, i32, f64, f64, f64, f64, vp, sz, vp]),
+        "slam_op_muon_apply": (C.c_int, [vp, vp, vp, f64, f64, i32, i32, vp]),
+        "slam_op_muon_syrk": (C.c_int, [vp, vp, vp, i32, i32, i32, i64, i64, i64, f32, f32, vp]),
+        "slam_op_muon_mm": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, f32, f32, vp]),
         "slam_add_param_wait": (C.c_int, [vp, i64, i64, vp]),
         "slam_param_wait_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "slam_param_wait_untimed": (C.c_int, [vp, C.POINTER(C.c_int64)]),
@@ -263,6 +291,16 @@ def _ptr(t) -> Optional[int]:
     return None if t is None else int(t.data_ptr())
 
 
+class _Shifted:
+    """t[a:b] of this = t[a + shift : b + shift] of the tensor (Engine.adamw_range with compact moments)."""
+
+    def __init__(self, t, shift):
+        self.t, self.shift, self.dtype = t, shift, t.dtype
+
+    def __getitem__(self, sl):
+        return self.t[sl.start + self.shift: sl.stop + self.shift]
+
+
 def current_stream_ptr() -> int:
     import torch
     return int(torch.cuda.current_stream().cuda_stream)
@@ -270,6 +308,44 @@ def current_stream_ptr() -> int:
 
 class EngineError(RuntimeError):
     pass
+
+
+def muon_ns_workspace_bytes(batch: int, n: int, m: int) -> int:
+    """Bytes of the scratch slam_op_muon_ns needs for `batch` packed [n][m] matrices (0: a shape it refuses)."""
+    return int(load_library().slam_op_muon_ns_workspace(int(batch), int(n), int(m)))
+
+
+def muon_ns(x, batch: int, n: int, m: int, stride: int, ws, ns_steps=5, ns_coefficients=MUON_NS_COEFFICIENTS, eps=MUON_EPS,
+            partials=None, parts: int = 0, stream: Optional[int] = None):
+    """slam_op_muon_ns: Newton-Schulz on `batch` packed bf16 [n][m] matrices (n <= m) at `stride` elements, in place. ws: a
+    256-byte aligned device tensor of muon_ns_workspace_bytes; partials: the fp32 sum-of-squares partials (`parts` a matrix) of
+    slam_op_muon_prepare, or None to have them taken here."""
+    a, b, c = ns_coefficients
+    rc = load_library().slam_op_muon_ns(_ptr(x), int(batch), int(n), int(m), int(stride), _ptr(partials), int(parts), int(ns_steps),
+                                        float(a), float(b), float(c), float(eps), _ptr(ws), ws.numel() * ws.element_size(),
+                                        stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_op_muon_ns failed ({rc})")
+
+
+def muon_syrk(x, r, c, batch: int, n: int, m: int, stride_x: int, stride_r: int, stride_c: int, alpha: float, beta: float,
+              stream: Optional[int] = None):
+    """slam_op_muon_syrk: C[i] = beta R[i] + alpha X[i] X[i]^T (bf16 [n][n] from [n][m]); r = None: no R."""
+    rc = load_library().slam_op_muon_syrk(_ptr(x), _ptr(r), _ptr(c), int(batch), int(n), int(m), int(stride_x), int(stride_r),
+                                          int(stride_c), float(alpha), float(beta),
+                                          stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_op_muon_syrk failed ({rc})")
+
+
+def muon_mm(p, x, r, y, batch: int, n: int, m: int, stride_p: int, stride_x: int, stride_r: int, stride_y: int, alpha: float,
+            beta: float, stream: Optional[int] = None):
+    """slam_op_muon_mm: Y[i] = beta R[i] + alpha P[i] X[i] (P [n][n], X / R / Y [n][m], bf16); r = None: no R."""
+    rc = load_library().slam_op_muon_mm(_ptr(p), _ptr(x), _ptr(r), _ptr(y), int(batch), int(n), int(m), int(stride_p), int(stride_x),
+                                        int(stride_r), int(stride_y), float(alpha), float(beta),
+                                        stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_op_muon_mm failed ({rc})")
 
 
 def sample_workspace_bytes(B: int, vocab: int, top_k: int) -> int:
@@ -762,11 +838,15 @@ class Engine:
                                                      stream if stream is not None else current_stream_ptr()))
 
     def adamw_range(self, offset: int, count: int, master, exp_avg, exp_avg_sq, norm_out, lr, beta1, beta2, eps, weight_decay,
-                    step, zero_grad=False, stream=None):
+                    step, zero_grad=False, stream=None, state_offset=None):
         """AdamW on elements [offset, offset + count): master / exp_avg / exp_avg_sq are FULL-SIZE flat tensors here (the
-        range's slices are passed down); master = None selects the bf16-state form."""
+        range's slices are passed down); master = None selects the bf16-state form. state_offset: the moments are COMPACT
+        tensors instead, and the range's moments start at that element of them (optim = "muon": no moments for Muon's elements)."""
         import torch
         o, n = int(offset), int(count)
+        if state_offset is not None:
+            so = int(state_offset)
+            exp_avg, exp_avg_sq = _Shifted(exp_avg, so - o), _Shifted(exp_avg_sq, so - o)
         st = stream if stream is not None else current_stream_ptr()
         if master is None:
             self._ck(self.lib.slam_adamw_range_bf16(self.h, o, n, _ptr(exp_avg[o:o + n]), _ptr(exp_avg_sq[o:o + n]), _ptr(norm_out),
@@ -822,6 +902,57 @@ class Engine:
         self._ck(self.lib.slam_adafactor_step(self.h, _ptr(master), _ptr(state), _ptr(norm_out), float(lr), float(eps1),
                                               float(clip_threshold), float(decay_rate), float(weight_decay), int(step),
                                               int(bool(zero_grad)), stream if stream is not None else current_stream_ptr()))
+
+    # -- Muon (optim = "muon") ----------------------------------------------------------------------------
+    def muon_set_segments(self, segments=None):
+        """slam_muon_set_segments: `segments` = [(offset, rows, cols, pattern)] - one decoder matrix each
+        (UnitLM.hf_muon_segments() yields them behind the name); None clears the table. Returns (momentum floats, workspace
+        bytes) of the new table ((0, 0) when cleared)."""
+        if not segments:
+            self._ck(self.lib.slam_muon_set_segments(self.h, None, 0))
+            return 0, 0
+        buf = (SlamMuonSegment * len(segments))(*[SlamMuonSegment(int(o), int(r), int(c), int(p), 0) for o, r, c, p in segments])
+        self._ck(self.lib.slam_muon_set_segments(self.h, buf, len(segments)))
+        return self.muon_sizes()
+
+    def muon_sizes(self):
+        """(floats of the fp32 momentum buffer, bytes of the workspace) for the segment table that is set."""
+        n, b = C.c_int64(0), C.c_size_t(0)
+        self._ck(self.lib.slam_muon_sizes(self.h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def muon_bind_workspace(self, ws=None):
+        """ws: a device tensor of at least the workspace bytes, 256-byte aligned (kept alive here); None unbinds."""
+        self._keep["muon_ws"] = ws
+        self._ck(self.lib.slam_muon_bind_workspace(self.h, _ptr(ws), 0 if ws is None else ws.numel() * ws.element_size()))
+
+    def muon_classes(self):
+        """The shape classes of the table: [SlamMuonClass]."""
+        out = []
+        for i in range(int(self.lib.slam_muon_class_count(self.h))):
+            c = SlamMuonClass()
+            self._ck(self.lib.slam_muon_class_info(self.h, i, C.byref(c)))
+            out.append(c)
+        return out
+
+    def muon_step(self, master, momentum_buf, norm_out, lr, step, weight_decay=0.0, momentum=0.95, nesterov=True, ns_steps=5,
+                  ns_coefficients=MUON_NS_COEFFICIENTS, eps=MUON_EPS, adjust_lr="match_rms_adamw", zero_grad=True, stream=None):
+        """slam_muon_step: master = the fp32 master weights, or None when the bf16 parameters are the only copy; momentum_buf =
+        the fp32 buffer of muon_sizes(). Updates the Muon matrices only: the caller runs adamw_range over the rest."""
+        a, b, c = ns_coefficients
+        self._ck(self.lib.slam_muon_step(self.h, _ptr(master), _ptr(momentum_buf), _ptr(norm_out), float(lr), float(weight_decay),
+                                         float(momentum), int(bool(nesterov)), int(ns_steps), float(a), float(b), float(c),
+                                         float(eps), MUON_ADJUST_LR[adjust_lr], int(step), int(bool(zero_grad)),
+                                         stream if stream is not None else current_stream_ptr()))
+
+    def op_muon_prepare(self, momentum_buf, norm_out, momentum=0.95, nesterov=True, zero_grad=False, stream=None):
+        self._ck(self.lib.slam_op_muon_prepare(self.h, _ptr(momentum_buf), _ptr(norm_out), float(momentum), int(bool(nesterov)),
+                                               int(bool(zero_grad)), stream if stream is not None else current_stream_ptr()))
+
+    def op_muon_apply(self, master, o_packed, lr, step, weight_decay=0.0, adjust_lr="match_rms_adamw", stream=None):
+        self._ck(self.lib.slam_op_muon_apply(self.h, _ptr(master), _ptr(o_packed), float(lr), float(weight_decay),
+                                             MUON_ADJUST_LR[adjust_lr], int(step),
+                                             stream if stream is not None else current_stream_ptr()))
 
     def add_param_wait(self, offset: int, count: int, event):
         """event: a recorded torch.cuda.Event; kept alive here until the next forward consumed it."""

@@ -87,6 +87,15 @@ def hf_name_is_decayed(name: str, is_opt: bool) -> bool:
     return not (is_opt and "layer_norm." in name)
 
 
+MUON_PROJECTIONS = ("q_proj", "k_proj", "v_proj", "o_proj", "out_proj", "gate_proj", "up_proj", "down_proj", "fc1", "fc2")
+
+
+def hf_name_is_muon(name: str) -> bool:
+    """Whether optim = "muon" gives the HF parameter `name` to Muon: `<...>.layers.<i>.<...>.<projection>.weight`."""
+    parts = name.split(".")
+    return "layers" in parts and len(parts) >= 2 and parts[-1] == "weight" and parts[-2] in MUON_PROJECTIONS
+
+
 @dataclass(frozen=True)
 class HFParamSegment:
     """One HF parameter over the engine's flat buffer (UnitLM.hf_param_segments). pattern 0: `rows` contiguous rows of `cols`
@@ -102,6 +111,10 @@ class HFParamSegment:
     @property
     def entry(self) -> Tuple[int, int, int, int, int]:
         return (self.offset, self.rows, self.cols, int(self.factored), self.pattern)
+
+    @property
+    def muon_entry(self) -> Tuple[int, int, int, int]:
+        return (self.offset, self.rows, self.cols, self.pattern)
 
     @property
     def state_floats(self) -> int:
@@ -508,6 +521,13 @@ class UnitLM(TokenLM):
                 assert len(shp) == 2, f"{key}: no HF decoder parameter here has more than two dimensions"
                 out.append(HFParamSegment(key, shp, off, shp[0], shp[1], True, 1 + int(ent[2]) if len(ent) == 3 else 0))
         return out
+
+    def hf_muon_segments(self) -> List[HFParamSegment]:
+        """The subset of hf_param_segments() that optim = "muon" hands to Muon, chosen by HF name: the 2-D weights of the decoder
+        layers - q_proj / k_proj / v_proj, o_proj (OPT: out_proj) and the MLP matrices gate_proj / up_proj / down_proj (OPT: fc1 /
+        fc2). Token and position embeddings, an untied lm_head, every norm weight (q / k norms included) and every bias are not
+        Muon's. `HFParamSegment.muon_entry` is the row of `Engine.muon_set_segments`."""
+        return [s for s in self.hf_param_segments() if hf_name_is_muon(s.name) and len(s.shape) == 2]
 
     def _view(self, flat: torch.Tensor, key: str, writable: bool = False) -> torch.Tensor:
         """HF-named window of a flat engine buffer. gate_proj / up_proj live interleaved in 32-row blocks:

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from .callbacks import TrainerCallback, TrainerControl, TrainerState
 from .dp import GradBucketReducer, ShardedGradReducer, all_reduce_scalar, host_group, seeded_batches, shard_batches, world_info
-from .training_args import (SLAMTrainingArguments, check_label_smoothing, check_neftune_alpha, check_optim,
+from .training_args import (SLAMTrainingArguments, check_label_smoothing, check_muon, check_neftune_alpha, check_optim,
                             check_weight_decay_rule, lr_lambda)
 
 logger = logging.getLogger(__name__)
@@ -43,16 +43,47 @@ def dropout_seed(seed: int, rank: int) -> int:
     return (((int(rank) & 0xFFFFFFFF) << 32) | (int(seed) & 0xFFFFFFFF)) ^ DROPOUT_SEED_TAG
 
 
-def check_checkpoint_optim(st: dict, adafactor: bool, path: str = "optimizer.pt"):
-    """An optimizer.pt holds the state of ONE optimizer kind: Adafactor's factors ("adafactor_state") or AdamW's moments
-    ("exp_avg", "exp_avg_sq"). Resuming one under the other is an error, not a silent zero state."""
+def check_checkpoint_optim(st: dict, adafactor, path: str = "optimizer.pt"):
+    """An optimizer.pt holds the state of ONE optimizer kind: Adafactor's factors ("adafactor_state"), AdamW's moments
+    ("exp_avg", "exp_avg_sq"), or Muon's momentum buffer with the AdamW moments of the other elements ("optim": "muon").
+    Resuming one under another is an error, not a silent zero state. `adafactor`: True / False (Adafactor / AdamW), or "muon"."""
     has_af = "adafactor_state" in st
+    is_muon = st.get("optim") == "muon" or "muon_momentum" in st
+    if adafactor == "muon":
+        if not is_muon or "exp_avg" not in st or "exp_avg_sq" not in st:
+            raise ValueError(f"{path} is {'an Adafactor' if has_af else 'an AdamW'} checkpoint (no Muon momentum buffer): it cannot "
+                             f"be resumed under optim='muon'")
+        return
+    if is_muon:
+        raise ValueError(f"{path} is a Muon checkpoint (a momentum buffer, AdamW moments for the other elements only): it cannot "
+                         f"be resumed under optim={'adafactor' if adafactor else 'adamw_torch'!r}; set optim='muon'")
     if adafactor and not has_af:
         raise ValueError(f"{path} is an AdamW checkpoint (it holds exp_avg / exp_avg_sq, no Adafactor state): it cannot be "
                          f"resumed under optim='adafactor'")
     if not adafactor and (has_af or "exp_avg" not in st or "exp_avg_sq" not in st):
         raise ValueError(f"{path} is an Adafactor checkpoint (it holds no exp_avg / exp_avg_sq): it cannot be resumed under an "
                          f"AdamW optim; set optim='adafactor'")
+
+
+def muon_adamw_runs(entries, n_params: int):
+    """The contiguous runs of [0, n_params) that no Muon matrix covers - what AdamW updates under optim = "muon" - as
+    [(offset, count, state offset)]: the moments of those elements are compact, run after run. `entries` = the rows of
+    Engine.muon_set_segments: (offset, rows, cols, pattern), pattern 1 / 2 = 32 rows of every 64, phase 0 / 32."""
+    iv = []
+    for off, rows, cols, pat in entries:
+        if not pat:
+            iv.append((off, off + rows * cols))
+        else:
+            iv.extend((off + (k * 64 + (32 if pat == 2 else 0)) * cols, off + (k * 64 + (32 if pat == 2 else 0) + 32) * cols)
+                      for k in range(rows // 32))
+    runs, pos, so = [], 0, 0
+    for lo, hi in sorted(iv) + [(n_params, n_params)]:
+        assert lo >= pos, "Muon segments overlap"
+        if lo > pos:
+            runs.append((pos, lo - pos, so))
+            so += lo - pos
+        pos = hi
+    return runs
 
 
 class SLAMTrainer:
@@ -88,7 +119,22 @@ class SLAMTrainer:
             raise ValueError(f"optim_state_dtype must be float32, bfloat16 or float32_bf16_moments, got {osd!r}")
         # optim = "adafactor": HF's Adafactor on slam_adafactor_step instead of AdamW. The AdamW names change nothing below: not
         # one engine call more (fields set after construction get past the arguments' own check)
-        self._adafactor = check_optim(getattr(self.args, "optim", "adamw_torch") or "adamw_torch") == "adafactor"
+        kind = check_optim(getattr(self.args, "optim", "adamw_torch") or "adamw_torch")
+        self._adafactor = kind == "adafactor"
+        # optim = "muon": torch.optim.Muon on slam_muon_step for the decoder layers' matrices, AdamW (slam_adamw_range*) for the rest
+        self._muon = kind == "muon"
+        if self._muon:
+            check_muon(self.args)
+            if osd == "float32_bf16_moments":
+                raise ValueError("optim='muon' keeps an fp32 momentum buffer and AdamW moments for the non-Muon elements only: "
+                                 "optim_state_dtype is float32 or bfloat16, not float32_bf16_moments")
+            if (getattr(self.args, "ddp_algo", "all_reduce") or "all_reduce") == "rs_ag":
+                raise ValueError("optim='muon' orthogonalises whole matrices: a shard of the flat buffer cuts them, so "
+                                 "ddp_algo='rs_ag' is not available (use all_reduce)")
+            if getattr(self.args, "overlap_optimizer", False):
+                raise ValueError("optim='muon' has no overlapped form: overlap_optimizer belongs to the fp32-state AdamW")
+            if not hasattr(model, "hf_muon_segments"):
+                raise ValueError("optim='muon' needs a model that knows its decoder matrices (UnitLM.hf_muon_segments)")
         if self._adafactor:
             if osd == "float32_bf16_moments":
                 raise ValueError("optim='adafactor' keeps no Adam moments: optim_state_dtype is float32 (fp32 master weights) or "
@@ -130,6 +176,23 @@ class SLAMTrainer:
             self.adafactor_state = torch.zeros(n_state, dtype=torch.float32, device=dev)
             self._adafactor_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             model.engine.adafactor_bind_workspace(self._adafactor_ws)
+        elif self._muon:
+            # 4 B of momentum per Muon element, and Adam moments for the OTHER elements only, compact: a full-size exp_avg /
+            # exp_avg_sq pair would throw away the memory Muon saves. The table and the complement are computed once
+            entries = [s.muon_entry for s in model.hf_muon_segments()]
+            n_mom, ws_bytes = model.engine.muon_set_segments(entries)
+            self.muon_momentum = torch.zeros(n_mom, dtype=torch.float32, device=dev)
+            self._muon_ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
+            pad = (-self._muon_ws.data_ptr()) % 256
+            model.engine.muon_bind_workspace(self._muon_ws[pad:pad + ws_bytes])
+            self._adamw_runs = muon_adamw_runs(entries, n)
+            n_adam = sum(c for _, c, _ in self._adamw_runs)
+            self.exp_avg = torch.zeros(n_adam, dtype=self.moment_dtype, device=dev)
+            self.exp_avg_sq = torch.zeros(n_adam, dtype=self.moment_dtype, device=dev)
+            self.optimizer_state_bytes = (4 * n_mom + 2 * n_adam * self.exp_avg.element_size(), ws_bytes)
+            logger.info("optim=muon: %d Muon elements (%.1f MB of momentum), %d AdamW elements (%.1f MB of moments), "
+                        "%.1f MB of workspace", n_mom, 4e-6 * n_mom, n_adam, 2e-6 * n_adam * self.exp_avg.element_size(),
+                        1e-6 * ws_bytes)
         else:
             self.exp_avg = torch.zeros(n, dtype=self.moment_dtype, device=dev)
             self.exp_avg_sq = torch.zeros(n, dtype=self.moment_dtype, device=dev)
@@ -404,6 +467,15 @@ class SLAMTrainer:
         if self._adafactor:  # HF's defaults: eps1 1e-30, clip_threshold 1, decay_rate -0.8; the scheduler's lr
             eng.adafactor_step(None if self.state_dtype == torch.bfloat16 else self.model.flat_master, self.adafactor_state,
                                self.norm_out, lr, self.opt_step, weight_decay=a.weight_decay, zero_grad=zero_grad)
+        elif self._muon:  # the Muon matrices, then AdamW on every run of the flat buffer between them
+            master = None if self.state_dtype == torch.bfloat16 else self.model.flat_master
+            eng.muon_step(master, self.muon_momentum, self.norm_out, lr, self.opt_step, weight_decay=a.weight_decay,
+                          momentum=a.muon_momentum, nesterov=a.muon_nesterov, ns_steps=a.muon_ns_steps,
+                          adjust_lr=a.muon_adjust_lr, zero_grad=zero_grad)
+            for off, cnt, so in self._adamw_runs:
+                eng.adamw_range(off, cnt, master, self.exp_avg, self.exp_avg_sq, self.norm_out, lr, a.adam_beta1, a.adam_beta2,
+                                a.adam_epsilon, a.weight_decay, self.opt_step, zero_grad=zero_grad, state_offset=so)
+            eng.refresh_transposed()  # both left the transposed weight images stale
         elif self.state_dtype == torch.bfloat16:
             eng.adamw_step_bf16(self.exp_avg, self.exp_avg_sq, self.norm_out, lr, a.adam_beta1, a.adam_beta2,
                                 a.adam_epsilon, a.weight_decay, self.opt_step, zero_grad=zero_grad)
@@ -620,6 +692,9 @@ class SLAMTrainer:
             self.model.engine.join()
             if self._adafactor:
                 opt = {"optim": "adafactor", "adafactor_state": self.adafactor_state.cpu()}
+            elif self._muon:  # the moments are compact: the runs of muon_adamw_runs, one after another
+                opt = {"optim": "muon", "muon_momentum": self.muon_momentum.cpu(), "exp_avg": self.exp_avg.cpu(),
+                       "exp_avg_sq": self.exp_avg_sq.cpu()}
             else:
                 opt = {"exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu()}
             torch.save({"master": self.model._weights.cpu(), **opt, "opt_step": self.opt_step}, os.path.join(path, "optimizer.pt"))
@@ -640,13 +715,17 @@ class SLAMTrainer:
 
     def _load_checkpoint(self, path: str):
         st = torch.load(os.path.join(path, "optimizer.pt"), map_location="cpu")
-        check_checkpoint_optim(st, self._adafactor, path)  # before anything is overwritten
+        check_checkpoint_optim(st, "muon" if self._muon else self._adafactor, path)  # before anything is overwritten
+        if self._muon and (st["muon_momentum"].numel() != self.muon_momentum.numel() or st["exp_avg"].numel() != self.exp_avg.numel()):
+            raise ValueError(f"{path} is a Muon checkpoint of another model or segment table")
         self.model.engine.join()
         self.model._weights.copy_(st["master"])
         self.model.sync_params_from_master()
         if self._adafactor:
             self.adafactor_state.copy_(st["adafactor_state"])
         else:
+            if self._muon:
+                self.muon_momentum.copy_(st["muon_momentum"])
             self.exp_avg.copy_(st["exp_avg"])
             self.exp_avg_sq.copy_(st["exp_avg_sq"])
         self.opt_step = int(st["opt_step"])

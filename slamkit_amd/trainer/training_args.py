@@ -22,6 +22,10 @@ class SLAMTrainingArguments:
     weight_decay: float = 0.0
     weight_decay_rule: str = "all"                 # which tensors weight_decay applies to. "all": every element of the flat parameter buffer (the engine's historical behaviour; at weight_decay 0 - every shipped recipe - the two rules coincide). "hf": HF Trainer.create_optimizer's rule - no bias, no LayerNorm / RMSNorm parameter (UnitLM.hf_decay_flags -> slam_set_decay_mask): what reproduces a reference run with a non-zero weight_decay
     optim: str = "adamw_torch"                     # HF's field. "adamw_torch" / "adamw_torch_fused": AdamW (the engine's slam_adamw_* kernels; the two names make the same calls). "adafactor": transformers.optimization.Adafactor as HF's Trainer builds it (scale_parameter = False, relative_step = False, no first moment; lr from the scheduler, clip_grad_norm_ first) on slam_adafactor_step: one fp32 number per row and per column of every HF matrix instead of two Adam moments per element. optim_state_dtype "float32" keeps the fp32 master, "bfloat16" drops it; "float32_bf16_moments", ddp_algo "rs_ag" and overlap_optimizer are refused (there are no moments; a shard cuts rows and columns). adam_beta1 / adam_beta2 / adam_epsilon are unused then
+    muon_momentum: float = 0.95                    # optim = "muon" (torch.optim.Muon on slam_muon_step): the decoder layers' matrices (q/k/v/o and the MLP weights, per HF tensor) take Muon - an fp32 momentum buffer, Nesterov, five Newton-Schulz iterations on batched HIP GEMMs -, every other parameter (embeddings, an untied head, norms, biases) AdamW with adam_beta1 / adam_beta2 / adam_epsilon through slam_adamw_range*, with moments for those elements only. optim_state_dtype "float32" or "bfloat16"; "float32_bf16_moments", ddp_algo "rs_ag" and overlap_optimizer are refused
+    muon_nesterov: bool = True
+    muon_ns_steps: int = 5                         # Newton-Schulz iterations, 1 .. 16
+    muon_adjust_lr: Optional[str] = "match_rms_adamw"  # torch's adjust_lr_fn: "match_rms_adamw" (lr * 0.2 sqrt(max(rows, cols)): a recipe tuned for AdamW keeps its lr and weight_decay), "original" (lr * sqrt(max(1, rows / cols))), None (lr as it is)
     adam_beta1: float = 0.9
     adam_beta2: float = 0.999
     adam_epsilon: float = 1e-8
@@ -63,6 +67,7 @@ class SLAMTrainingArguments:
     def __post_init__(self):
         check_weight_decay_rule(self.weight_decay_rule)
         check_optim(self.optim)
+        check_muon(self)
         check_label_smoothing(self.label_smoothing_factor)
         check_neftune_alpha(self.neftune_noise_alpha)
         if self.optim_stochastic_rounding and (self.optim_state_dtype or "float32") == "float32":
@@ -93,13 +98,27 @@ def check_weight_decay_rule(rule) -> str:
 
 
 OPTIM_ADAMW = ("adamw_torch", "adamw_torch_fused")
-OPTIM_NAMES = OPTIM_ADAMW + ("adafactor",)
+OPTIM_NAMES = OPTIM_ADAMW + ("adafactor", "muon")
+MUON_ADJUST_LR = ("match_rms_adamw", "original", None)
 
 
 def check_optim(name) -> str:
     if name not in OPTIM_NAMES:
-        raise ValueError(f"optim must be one of 'adamw_torch', 'adamw_torch_fused' or 'adafactor', got {name!r}")
+        raise ValueError(f"optim must be one of 'adamw_torch', 'adamw_torch_fused', 'adafactor' or 'muon', got {name!r}")
     return name
+
+
+def check_muon(args):
+    """The muon_* fields, whatever `optim` is (a typo should not wait for the day the optimizer is switched)."""
+    mu = getattr(args, "muon_momentum", 0.95)
+    if not (isinstance(mu, (int, float)) and 0.0 <= float(mu) < 1.0):
+        raise ValueError(f"muon_momentum must lie in [0, 1), got {mu!r}")
+    ns = getattr(args, "muon_ns_steps", 5)
+    if not (isinstance(ns, int) and 1 <= ns <= 16):
+        raise ValueError(f"muon_ns_steps must be an integer in 1 .. 16, got {ns!r}")
+    adj = getattr(args, "muon_adjust_lr", "match_rms_adamw")
+    if adj not in MUON_ADJUST_LR:
+        raise ValueError(f"muon_adjust_lr must be 'match_rms_adamw', 'original' or None, got {adj!r}")
 
 
 def check_label_smoothing(eps) -> float:
