@@ -149,16 +149,37 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
  * slam_seq_loglik_unpadded / slam_scale_loss_unpadded: slam_seq_loglik / slam_scale_loss_rows over the remembered segments
  * (ll_out, cnt_out, seq_coef: fp32 [B] device; the tail's rows are scaled by 0). SLAM_ESTATE unless the last forward was an
  * unpadded one over B rows (with labels); slam_seq_loglik / slam_scale_loss_rows after an unpadded forward are SLAM_ESTATE too.
- * slam_op_unpad_pack: the pack kernel alone (no engine), same scratch layout. */
+ * slam_op_unpad_pack: the pack kernel alone (no engine), same scratch layout.
+ *
+ * Span batches (left- and both-side-padded rows: HF generate's output, TRL's prompt-left / completion-right pairs):
+ * slam_forward_unpadded_spans takes the first real column of every row as well. Row b's real tokens are the columns
+ * [starts[b], starts[b] + lens[b]) with 1 <= lens[b], 0 <= starts[b], starts[b] + lens[b] <= T; starts: int32 [B] DEVICE, read
+ * only inside this call (by the pack and by the logits scatter), NULL = all zero = right padding: slam_forward_unpadded IS
+ * this call with starts = NULL, launch for launch and bit for bit. starts are clamped to [0, T] and lens to [0, T - starts]
+ * (a memory guard). The pack rule with spans: token (b, t), starts[b] <= t < starts[b] + lens[b], goes to
+ * m' = off[b] + (t - starts[b]) with ids'[m'] = ids[b][t], position_ids'[m'] = t - starts[b] (a row's real tokens count from 0
+ * in every family: OPT's own cumsum(mask) - 1 rule in HF, and for RoPE the same relative distances as HF's aranges),
+ * labels'[m'] = t == starts[b] ? -100 : labels[b][t] (the first real token of a row is never a target: HF predicts it from
+ * a pad query). off, seg_start', seg_end', row', the dummy tail, the scratch size and its layout are those above.
+ * logits_out: bf16 [B][T][vocab], row b's real columns from their packed rows, zeros on both sides. Everything after the pack -
+ * layers, head, loss, num_items, slam_backward, slam_seq_loglik_unpadded, slam_scale_loss_unpadded, "recompute", label
+ * smoothing, the logit mask, NEFTune (scaled by the padded width T), OPT's dropout (keyed on the packed index) - is the
+ * padding-free path unchanged: a span batch and the same rows right-padded run the same launches on the same packed arrays.
+ * slam_op_unpad_pack_spans: slam_op_unpad_pack with starts (nullable). */
 size_t slam_unpadded_scratch_bytes(int32_t B, int32_t T);
 int slam_forward_unpadded(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T,
                           int32_t M_packed, void* scratch, size_t scratch_bytes, double num_items, float* loss_out,
                           void* logits_out, slam_stream_t stream);
+int slam_forward_unpadded_spans(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int32_t* starts,
+                                const int32_t* lens, int32_t B, int32_t T, int32_t M_packed, void* scratch, size_t scratch_bytes,
+                                double num_items, float* loss_out, void* logits_out, slam_stream_t stream);
 int64_t slam_last_forward_tokens(SlamEngine* h);
 int slam_seq_loglik_unpadded(SlamEngine* h, int32_t B, float* ll_out, float* cnt_out, slam_stream_t stream);
 int slam_scale_loss_unpadded(SlamEngine* h, const float* seq_coef, int32_t B, slam_stream_t stream);
 int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T, int32_t M_packed,
                        int32_t pad_id, void* scratch, size_t scratch_bytes, slam_stream_t s);
+int slam_op_unpad_pack_spans(const int64_t* ids, const int64_t* labels, const int32_t* starts, const int32_t* lens, int32_t B,
+                             int32_t T, int32_t M_packed, int32_t pad_id, void* scratch, size_t scratch_bytes, slam_stream_t s);
 
 /* ---- KV-cached generation: HF GenerationMixin.generate with use_cache (the reference's speech_lm.py / metric_utils.py call
  * model.generate(input_ids, attention_mask, bad_words_ids, temperature, top_k, max_new_tokens)) ---------------------------
@@ -1214,11 +1235,15 @@ int slam_op_cross_entropy_smooth(const void* logits /* bf16 [B*T][Vp] */, const 
  * copy_cols: dst[m][0 .. ncols) = src[m][0 .. ncols) with row strides ld_src / ld_dst (slam_forward's logits_out).
  * unpad_logits: dst[b][t][0 .. V) = t < off[b + 1] - off[b] ? src[off[b] + t][0 .. V) : +0, src = Mp rows of Vp, off = int32 [B + 1]
  *   (slam_op_unpad_pack leaves it behind the six [Mmax] arrays of its scratch).
+ * unpad_logits_spans: the same with row b's real columns starting at starts[b] (int32 [B], nullable = 0, clamped to [0, T]):
+ *   dst[b][t][0 .. V) = 0 <= t - starts[b] < off[b + 1] - off[b] ? src[off[b] + t - starts[b]][0 .. V) : +0.
  * scale_bf16: x[i] = bf16(x[i] * scale), i < n (slam_backward's grad_scale).
  * scale_rows_bf16: x[m][:] *= coef[m / T], x = [M][ncols] (slam_scale_loss_rows).
  * scale_rows_unpadded_bf16: x[m][:] *= row[m] >= 0 ? coef[row[m]] : 0, x = [Mp][ncols], row = int32 [Mp] (slam_scale_loss_unpadded). */
 int slam_op_copy_cols(const void* src, int ld_src, void* dst, int ld_dst, int M, int ncols, slam_stream_t s);
 int slam_op_unpad_logits(const void* src, int Vp, void* dst, int V, const int32_t* off, int B, int T, int Mp, slam_stream_t s);
+int slam_op_unpad_logits_spans(const void* src, int Vp, void* dst, int V, const int32_t* off, const int32_t* starts, int B, int T,
+                               int Mp, slam_stream_t s);
 int slam_op_scale_bf16(void* x, int64_t n, float scale, slam_stream_t s);
 int slam_op_scale_rows_bf16(void* x, const float* coef, int M, int T, int ncols, slam_stream_t s);
 int slam_op_scale_rows_unpadded_bf16(void* x, const float* coef, const int32_t* row, int Mp, int ncols, slam_stream_t s);

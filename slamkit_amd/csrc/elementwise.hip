@@ -1042,17 +1042,19 @@ __global__ __launch_bounds__(256) void scale_rows_bf16_kernel(bf16_t* __restrict
   *p = pack_bf16x8(f);
 }
 
-// ---- padding-free execution of right-padded batches (slam_forward_unpadded) ------------------------------------------
-// The pack rule in one launch, one thread per packed position m' in [0, Mp): token (b, t < lens[b]) goes to m' = off[b] + t
-// with off the exclusive prefix sum of lens; [off[B], Mp) is one dummy segment of pad tokens. Every block scans lens itself,
+// ---- padding-free execution of padded batches (slam_forward_unpadded, slam_forward_unpadded_spans) -------------------
+// The pack rule in one launch, one thread per packed position m' in [0, Mp): token (b, starts[b] + t), t < lens[b], goes to
+// m' = off[b] + t with off the exclusive prefix sum of lens (starts == nullptr: every row starts at column 0, right padding);
+// [off[B], Mp) is one dummy segment of pad tokens. Every block scans lens itself,
 // 256 rows at a time through LDS with the running total carried along, and a thread takes its row from the chunk whose
-// offsets bracket m' - no second launch, no atomics; block 0 also leaves off[] behind for the kernels below. lens are
-// clamped to [0, T] and segment ends to Mp (a memory guard: callers check their ranges). The 8-byte elements are gathered
-// from row starts of any alignment, so accesses are element-wide.
+// offsets bracket m' - no second launch, no atomics; block 0 also leaves off[] behind for the kernels below. starts are
+// clamped to [0, T], lens to [0, T - starts] and segment ends to Mp (a memory guard: callers check their ranges). The 8-byte
+// elements are gathered from row starts of any alignment, so accesses are element-wide.
 // (Every block repeats the scan: B / 256 rounds of 8 barrier pairs per block, nothing at the callers' B of tens to hundreds.
 // Should B reach the thousands, scan once in a launch of its own and let the blocks read off[].)
 __global__ __launch_bounds__(256) void unpad_pack_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ labels,
-                                                         const int32_t* __restrict__ lens, int B, int T, int Mp, int64_t pad_id,
+                                                         const int32_t* __restrict__ starts, const int32_t* __restrict__ lens,
+                                                         int B, int T, int Mp, int64_t pad_id,
                                                          int64_t* __restrict__ ids_p, int64_t* __restrict__ lab_p,
                                                          int64_t* __restrict__ pos_p, int32_t* __restrict__ seg_s,
                                                          int32_t* __restrict__ seg_e, int32_t* __restrict__ row_p,
@@ -1064,7 +1066,7 @@ __global__ __launch_bounds__(256) void unpad_pack_kernel(const int64_t* __restri
   if (blockIdx.x == 0 && tid == 0) off[0] = 0;
   for (int c = 0; c < B; c += 256) {
     const int b = c + tid;
-    sc[tid + 1] = b < B ? min(max(lens[b], 0), T) : 0;
+    sc[tid + 1] = b < B ? min(max(lens[b], 0), T - (starts ? min(max(starts[b], 0), T) : 0)) : 0;
     if (tid == 0) sc[0] = 0;
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {
@@ -1092,7 +1094,7 @@ __global__ __launch_bounds__(256) void unpad_pack_kernel(const int64_t* __restri
   if (m >= Mp) return;
   if (row >= 0) {
     const int t = m - s0;
-    const size_t src = (size_t)row * T + t;
+    const size_t src = (size_t)row * T + (starts ? min(max(starts[row], 0), T) : 0) + t;
     ids_p[m] = ids[src];
     if (lab_p) lab_p[m] = t == 0 ? -100 : labels[src];
     pos_p[m] = t;
@@ -1109,19 +1111,22 @@ __global__ __launch_bounds__(256) void unpad_pack_kernel(const int64_t* __restri
   }
 }
 
-// Logits back in the batch's own layout: dst[b][t][0 .. V) = packed row off[b] + t for t < lens[b], zeros at the pad positions.
+// Logits back in the batch's own layout: dst[b][starts[b] + t][0 .. V) = packed row off[b] + t for t < lens[b], zeros at the pad
+// positions on either side (starts == nullptr: 0; clamped to [0, T] as the pack clamps it).
 // One thread per 16-byte chunk when V is a multiple of 8 (every dst row then starts 16-byte aligned), else per element.
 template <int W>
 __global__ __launch_bounds__(256) void unpad_logits_kernel(const bf16_t* __restrict__ src, int Vp, bf16_t* __restrict__ dst, int V,
-                                                           const int32_t* __restrict__ off, size_t BT, int T, int Mp) {
+                                                           const int32_t* __restrict__ off, const int32_t* __restrict__ starts,
+                                                           size_t BT, int T, int Mp) {
   const int per = V / W;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= BT * per) return;
   const size_t bt = idx / per;
   const int c = (int)(idx % per) * W;
-  const int b = (int)(bt / T), t = (int)(bt % T);
+  const int b = (int)(bt / T);
+  const int t = (int)(bt % T) - (starts ? min(max(starts[b], 0), T) : 0);  // the column within the row's span
   const int o = off[b];
-  const bool real = t < off[b + 1] - o && o + t < Mp;  // (rows past Mp exist only when lens broke their contract)
+  const bool real = t >= 0 && t < off[b + 1] - o && o + t < Mp;  // (rows past Mp exist only when lens broke their contract)
   if constexpr (W == 8) {
     uint4 v = make_uint4(0, 0, 0, 0);
     if (real) v = *reinterpret_cast<const uint4*>(src + (size_t)(o + t) * Vp + c);
@@ -1648,18 +1653,20 @@ UnpadView unpad_view(void* scratch, int B, int T) {
   v.off = v.row + mm;
   return v;
 }
-int unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int B, int T, int Mp, int pad_id,
-               const UnpadView& v, hipStream_t st) {
+int unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* starts, const int32_t* lens, int B, int T, int Mp,
+               int pad_id, const UnpadView& v, hipStream_t st) {
   if (B <= 0 || T <= 0 || Mp <= 0 || (size_t)Mp > unpad_mmax(B, T)) return -1;
-  unpad_pack_kernel<<<nblocks((size_t)Mp, 256), 256, 0, st>>>(ids, labels, lens, B, T, Mp, (int64_t)(pad_id > 0 ? pad_id : 0), v.ids,
-                                                              labels ? v.labels : nullptr, v.pos, v.seg_s, v.seg_e, v.row, v.off);
+  unpad_pack_kernel<<<nblocks((size_t)Mp, 256), 256, 0, st>>>(ids, labels, starts, lens, B, T, Mp, (int64_t)(pad_id > 0 ? pad_id : 0),
+                                                              v.ids, labels ? v.labels : nullptr, v.pos, v.seg_s, v.seg_e, v.row,
+                                                              v.off);
   LAUNCH_RET();
 }
-int unpad_logits(const bf16_t* src, int Vp, bf16_t* dst, int V, const int32_t* off, int B, int T, int Mp, hipStream_t st) {
+int unpad_logits(const bf16_t* src, int Vp, bf16_t* dst, int V, const int32_t* off, const int32_t* starts, int B, int T, int Mp,
+                 hipStream_t st) {
   if (V <= 0 || V > Vp || (Vp & 7)) return -1;
   const size_t BT = (size_t)B * T;
-  if (V % 8 == 0) unpad_logits_kernel<8><<<nblocks(BT * (V / 8), 256), 256, 0, st>>>(src, Vp, dst, V, off, BT, T, Mp);
-  else unpad_logits_kernel<1><<<nblocks(BT * V, 256), 256, 0, st>>>(src, Vp, dst, V, off, BT, T, Mp);
+  if (V % 8 == 0) unpad_logits_kernel<8><<<nblocks(BT * (V / 8), 256), 256, 0, st>>>(src, Vp, dst, V, off, starts, BT, T, Mp);
+  else unpad_logits_kernel<1><<<nblocks(BT * V, 256), 256, 0, st>>>(src, Vp, dst, V, off, starts, BT, T, Mp);
   LAUNCH_RET();
 }
 int seq_loglik_unpadded(const float* row_loss, const int64_t* labels_packed, const int32_t* off, int B, int Mp, float* ll,

@@ -748,11 +748,13 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
 
 }  // extern "C"
 
-// slam_forward, and the tail of slam_forward_unpadded: `up` = the packed arrays of a padding-free call over up_B x up_T (ids ..
-// seg_end then point into them and (B, T) = (1, M_packed)); its logits go back to the batch's own layout.
+// slam_forward, and the tail of slam_forward_unpadded_spans: `up` = the packed arrays of a padding-free call over up_B x up_T
+// (ids .. seg_end then point into them and (B, T) = (1, M_packed)); its logits go back to the batch's own layout, row b's from
+// column up_starts[b] on (nullable: 0; the caller's array, read in this call only).
 static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int64_t* position_ids,
                           const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
-                          float* loss_out, void* logits_out, const UnpadView* up, int up_B, int up_T, slam_stream_t stream) {
+                          float* loss_out, void* logits_out, const UnpadView* up, const int32_t* up_starts, int up_B, int up_T,
+                          slam_stream_t stream) {
   // "dropout_call_next" arms this call and no other: a refused forward uses it up too, so no later one inherits it
   const int64_t armed_call = h->dropout_call_next, neft_call = h->neftune_call_next;
   h->dropout_call_next = -1;
@@ -797,7 +799,7 @@ static int forward_common(SlamEngine* h, const int64_t* ids, const int64_t* labe
   const int VP = h->vpad;
   TK(F_HEAD_FWD, st, gemm_nt(h->hf, P + h->off_head, h->logits, nullptr, nullptr, M, VP, H, st));
   h->have_loss = false;
-  if (logits_out && up) CK(unpad_logits(h->logits, VP, (bf16_t*)logits_out, d.vocab, up->off, up_B, up_T, M, st));
+  if (logits_out && up) CK(unpad_logits(h->logits, VP, (bf16_t*)logits_out, d.vocab, up->off, up_starts, up_B, up_T, M, st));
   else if (logits_out) CK(copy_cols(h->logits, VP, (bf16_t*)logits_out, d.vocab, M, d.vocab, st));
   if (labels) {
     TK(F_LOSS, st, cross_entropy(h->logits, labels, num_items, h->dlogits, h->row_loss, h->scal + 0, h->scal + 1, B, T, VP,
@@ -822,8 +824,8 @@ int slam_forward(SlamEngine* h, const int64_t* ids, const int64_t* labels, const
                  const int32_t* seg_start, const int32_t* seg_end, int32_t B, int32_t T, double num_items,
                  float* loss_out, void* logits_out, slam_stream_t stream) {
   if (!h) return SLAM_EINVAL;
-  return forward_common(h, ids, labels, position_ids, seg_start, seg_end, B, T, num_items, loss_out, logits_out, nullptr, 0, 0,
-                        stream);
+  return forward_common(h, ids, labels, position_ids, seg_start, seg_end, B, T, num_items, loss_out, logits_out, nullptr, nullptr, 0,
+                        0, stream);
 }
 
 size_t slam_unpadded_scratch_bytes(int32_t B, int32_t T) {
@@ -834,6 +836,13 @@ size_t slam_unpadded_scratch_bytes(int32_t B, int32_t T) {
 int slam_forward_unpadded(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T,
                           int32_t M_packed, void* scratch, size_t scratch_bytes, double num_items, float* loss_out,
                           void* logits_out, slam_stream_t stream) {
+  return slam_forward_unpadded_spans(h, ids, labels, nullptr, lens, B, T, M_packed, scratch, scratch_bytes, num_items, loss_out,
+                                     logits_out, stream);
+}
+
+int slam_forward_unpadded_spans(SlamEngine* h, const int64_t* ids, const int64_t* labels, const int32_t* starts,
+                                const int32_t* lens, int32_t B, int32_t T, int32_t M_packed, void* scratch, size_t scratch_bytes,
+                                double num_items, float* loss_out, void* logits_out, slam_stream_t stream) {
   if (!h) return SLAM_EINVAL;
   const int64_t armed_call = h->dropout_call_next, neft_call = h->neftune_call_next;  // a refused call uses the arming up, as slam_forward does
   auto refuse = [&](int code, const char* m) { h->dropout_call_next = h->neftune_call_next = -1; return h->fail(code, m); };
@@ -846,12 +855,12 @@ int slam_forward_unpadded(SlamEngine* h, const int64_t* ids, const int64_t* labe
   if (labels && !loss_out) return refuse(SLAM_EINVAL, "labels given without loss_out");
   h->have_fwd = false;
   const UnpadView v = unpad_view(scratch, B, T);
-  int rc = unpad_pack(ids, labels, lens, B, T, M_packed, h->d.pad_token_id, v, (hipStream_t)stream);
+  int rc = unpad_pack(ids, labels, starts, lens, B, T, M_packed, h->d.pad_token_id, v, (hipStream_t)stream);
   if (rc != 0) { h->dropout_call_next = h->neftune_call_next = -1; return rc; }
   h->dropout_call_next = armed_call;
   h->neftune_call_next = neft_call;
   return forward_common(h, v.ids, labels ? v.labels : nullptr, v.pos, v.seg_s, v.seg_e, 1, M_packed, num_items, loss_out, logits_out,
-                        &v, B, T, stream);
+                        &v, starts, B, T, stream);
 }
 
 int64_t slam_last_forward_tokens(SlamEngine* h) { return h && h->have_fwd ? h->last_tokens : 0; }

@@ -184,7 +184,7 @@ int seq_loglik(const float* row_loss, const int64_t* labels, int B, int T, float
 int copy_cols(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int M, int ncols, hipStream_t st);
 int scale_bf16(bf16_t* x, size_t n, float s, hipStream_t st);
 int scale_rows_bf16(bf16_t* x, const float* coef, int M, int T, int ncols, hipStream_t st);
-// Padding-free execution of right-padded [B][T] batches (include/slam_engine.h, slam_forward_unpadded): the packed arrays of
+// Padding-free execution of padded [B][T] batches (include/slam_engine.h, slam_forward_unpadded / _spans): the packed arrays of
 // one batch in caller-owned scratch, every array 256-byte aligned. Mmax = B * T rounded up to 64.
 struct UnpadView {
   int64_t *ids, *labels, *pos;  // [Mmax]
@@ -193,11 +193,13 @@ struct UnpadView {
 };
 size_t unpad_scratch_bytes(int B, int T);
 UnpadView unpad_view(void* scratch, int B, int T);
-// one launch: the pack rule over m' in [0, Mp); labels nullable (v.labels is then left alone)
-int unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int B, int T, int Mp, int pad_id,
-               const UnpadView& v, hipStream_t st);
-// dst[b][t][0 .. V) = t < lens[b] ? src[off[b] + t][0 .. V) : 0   (src: Mp rows, Vp long)
-int unpad_logits(const bf16_t* src, int Vp, bf16_t* dst, int V, const int32_t* off, int B, int T, int Mp, hipStream_t st);
+// one launch: the pack rule over m' in [0, Mp); labels nullable (v.labels is then left alone); starts nullable (int32 [B], the
+// first real column of each row; nullptr = 0, right padding)
+int unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* starts, const int32_t* lens, int B, int T, int Mp,
+               int pad_id, const UnpadView& v, hipStream_t st);
+// dst[b][starts[b] + t][0 .. V) = src[off[b] + t][0 .. V) for t < lens[b], 0 elsewhere   (src: Mp rows, Vp long; starts nullable)
+int unpad_logits(const bf16_t* src, int Vp, bf16_t* dst, int V, const int32_t* off, const int32_t* starts, int B, int T, int Mp,
+                 hipStream_t st);
 // per-row sums of -row_loss over valid targets and their counts, over the packed segments (seq_loglik's reduction)
 int seq_loglik_unpadded(const float* row_loss, const int64_t* labels_packed, const int32_t* off, int B, int Mp, float* ll,
                         float* cnt, hipStream_t st);

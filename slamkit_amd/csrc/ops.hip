@@ -35,13 +35,17 @@ static bool drop_site_ok(int M, int H, int32_t thr16, int64_t call, int32_t stre
 
 extern "C" {
 
-int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T, int32_t M_packed,
-                       int32_t pad_id, void* scratch, size_t scratch_bytes, slam_stream_t s) {
+int slam_op_unpad_pack_spans(const int64_t* ids, const int64_t* labels, const int32_t* starts, const int32_t* lens, int32_t B,
+                             int32_t T, int32_t M_packed, int32_t pad_id, void* scratch, size_t scratch_bytes, slam_stream_t s) {
   if (!ids || !lens || !scratch || B <= 0 || T <= 0 || (int64_t)B * T > 0x7fffffc0LL) return SLAM_EINVAL;
   const int64_t mmax = (((int64_t)B * T + 63) / 64) * 64;
   if (M_packed <= 0 || (M_packed & 63) || M_packed > mmax) return SLAM_EINVAL;
   if (((uintptr_t)scratch & 255) || scratch_bytes < unpad_scratch_bytes(B, T)) return SLAM_EINVAL;
-  return unpad_pack(ids, labels, lens, B, T, M_packed, pad_id, unpad_view(scratch, B, T), (hipStream_t)s);
+  return unpad_pack(ids, labels, starts, lens, B, T, M_packed, pad_id, unpad_view(scratch, B, T), (hipStream_t)s);
+}
+int slam_op_unpad_pack(const int64_t* ids, const int64_t* labels, const int32_t* lens, int32_t B, int32_t T, int32_t M_packed,
+                       int32_t pad_id, void* scratch, size_t scratch_bytes, slam_stream_t s) {
+  return slam_op_unpad_pack_spans(ids, labels, nullptr, lens, B, T, M_packed, pad_id, scratch, scratch_bytes, s);
 }
 
 // ---- single-op entry points ------------------------------------------------------------------
@@ -351,9 +355,13 @@ int slam_op_copy_cols(const void* src, int ld_src, void* dst, int ld_dst, int M,
   if (!src || !dst || M <= 0 || ncols <= 0 || ld_src < ncols || ld_dst < ncols) return SLAM_EINVAL;
   return copy_cols((const bf16_t*)src, ld_src, (bf16_t*)dst, ld_dst, M, ncols, (hipStream_t)s);
 }
-int slam_op_unpad_logits(const void* src, int Vp, void* dst, int V, const int32_t* off, int B, int T, int Mp, slam_stream_t s) {
+int slam_op_unpad_logits_spans(const void* src, int Vp, void* dst, int V, const int32_t* off, const int32_t* starts, int B, int T,
+                               int Mp, slam_stream_t s) {
   if (!src || !dst || !off || B <= 0 || T <= 0 || Mp <= 0 || V <= 0 || V > Vp || (Vp & 7)) return SLAM_EINVAL;
-  return unpad_logits((const bf16_t*)src, Vp, (bf16_t*)dst, V, off, B, T, Mp, (hipStream_t)s);
+  return unpad_logits((const bf16_t*)src, Vp, (bf16_t*)dst, V, off, starts, B, T, Mp, (hipStream_t)s);
+}
+int slam_op_unpad_logits(const void* src, int Vp, void* dst, int V, const int32_t* off, int B, int T, int Mp, slam_stream_t s) {
+  return slam_op_unpad_logits_spans(src, Vp, dst, V, off, nullptr, B, T, Mp, s);
 }
 int slam_op_scale_bf16(void* x, int64_t n, float scale, slam_stream_t s) {
   if (!x || n <= 0 || (n & 7)) return SLAM_EINVAL;  // the kernel goes in 16-byte chunks

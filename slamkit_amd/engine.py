@@ -125,10 +125,12 @@ def load_library(path: Optional[str] = None):
         "slam_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
         "slam_unpadded_scratch_bytes": (sz, [i32, i32]),
         "slam_forward_unpadded": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, sz, f64, vp, vp, vp]),
+        "slam_forward_unpadded_spans": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, f64, vp, vp, vp]),
         "slam_last_forward_tokens": (i64, [vp]),
         "slam_seq_loglik_unpadded": (C.c_int, [vp, i32, vp, vp, vp]),
         "slam_scale_loss_unpadded": (C.c_int, [vp, vp, i32, vp]),
         "slam_op_unpad_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+        "slam_op_unpad_pack_spans": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
         "slam_backward": (C.c_int, [vp, f32, i32, BUCKET_CB, vp, vp]),
         "slam_kv_cache_bytes": (sz, [vp, i32, i32]),
         "slam_bind_kv_cache": (C.c_int, [vp, vp, sz, i32, i32]),
@@ -263,6 +265,7 @@ def load_library(path: Optional[str] = None):
         "slam_op_cross_entropy_smooth": (C.c_int, [vp, vp, f64, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
         "slam_op_copy_cols": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_unpad_logits": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
+        "slam_op_unpad_logits_spans": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_scale_bf16": (C.c_int, [vp, i64, f32, vp]),
         "slam_op_scale_rows_bf16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
         "slam_op_scale_rows_unpadded_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -558,6 +561,28 @@ def unpad_pack(ids, labels, lens, B: int, T: int, M_packed: int, pad_id: int, sc
         raise EngineError(f"slam_op_unpad_pack failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
+def unpad_pack_spans(ids, labels, starts, lens, B: int, T: int, M_packed: int, pad_id: int, scratch,
+                     stream: Optional[int] = None):
+    """slam_op_unpad_pack_spans: unpad_pack for span batches - row b's real tokens are the columns starts[b] .. starts[b] +
+    lens[b] - 1 (starts int32 [B] on the device; None = right padding, slam_op_unpad_pack's own launch)."""
+    rc = load_library().slam_op_unpad_pack_spans(_ptr(ids), _ptr(labels), _ptr(starts), _ptr(lens), int(B), int(T),
+                                                 int(M_packed), int(pad_id), _ptr(scratch),
+                                                 scratch.numel() * scratch.element_size(),
+                                                 stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_op_unpad_pack_spans failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+def unpad_logits_spans(src, dst, off, starts, B: int, T: int, M_packed: int, stream: Optional[int] = None):
+    """slam_op_unpad_logits_spans: packed bf16 logits src [M_packed, Vp] back to dst [B, T, V] - row b's real columns from
+    starts[b] on (int32 [B] on the device, None = 0), exact zeros elsewhere. off: int32 [B + 1], as the pack leaves it."""
+    rc = load_library().slam_op_unpad_logits_spans(_ptr(src), int(src.shape[-1]), _ptr(dst), int(dst.shape[-1]), _ptr(off),
+                                                   _ptr(starts), int(B), int(T), int(M_packed),
+                                                   stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_op_unpad_logits_spans failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
 @dataclass
 class TensorSpec:
     name: str
@@ -696,6 +721,16 @@ class Engine:
         self._ck(self.lib.slam_forward_unpadded(self.h, _ptr(ids), _ptr(labels), _ptr(lens), B, T, int(M_packed), _ptr(scratch),
                                                 scratch.numel() * scratch.element_size(), float(num_items), _ptr(loss_out),
                                                 _ptr(logits_out), stream if stream is not None else current_stream_ptr()))
+
+    def forward_unpadded_spans(self, ids, labels, starts, lens, B: int, T: int, M_packed: int, scratch, num_items: float = 0.0,
+                               loss_out=None, logits_out=None, stream: Optional[int] = None):
+        """slam_forward_unpadded_spans: forward_unpadded for a span batch - row b's real tokens are the columns starts[b] ..
+        starts[b] + lens[b] - 1 (starts int32 [B] on the device, read inside the call only; None = right padding)."""
+        self._keep["unpad_scratch"] = scratch
+        self._ck(self.lib.slam_forward_unpadded_spans(self.h, _ptr(ids), _ptr(labels), _ptr(starts), _ptr(lens), B, T,
+                                                      int(M_packed), _ptr(scratch), scratch.numel() * scratch.element_size(),
+                                                      float(num_items), _ptr(loss_out), _ptr(logits_out),
+                                                      stream if stream is not None else current_stream_ptr()))
 
     def last_forward_tokens(self) -> int:
         """Token rows the last forward executed: B * T of a padded call, M_packed of an unpadded one (0 without a forward)."""

@@ -355,6 +355,25 @@ def _right_padded(mask: torch.Tensor) -> bool:
     return bool((m[:, 1:] <= m[:, :-1]).all())
 
 
+def mask_spans(mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A host attention_mask [B, T] read as spans: (starts, lens), int32 CPU tensors [B] - row b's ones are the columns
+    starts[b] .. starts[b] + lens[b] - 1. One contiguous run of ones per row: right padding (starts 0), left padding
+    (starts + lens = T) or both. A row of zeros or a row with a hole is a ValueError."""
+    m = mask != 0
+    B, T = m.shape
+    lens = m.sum(1)
+    if B and int(lens.min()) < 1:
+        raise ValueError(f"attention_mask row {int(lens.argmin())} is all zeros: every row needs at least one real token")
+    col = torch.arange(T)[None]
+    starts = torch.where(m, col, T).amin(1)
+    last = torch.where(m, col, -1).amax(1)
+    holes = last - starts + 1 != lens
+    if bool(holes.any()):
+        raise ValueError(f"attention_mask row {int(holes.to(torch.int64).argmax())} has a hole: only one contiguous run of ones "
+                         "per row is supported (right, left or both-side padding)")
+    return starts.to(torch.int32), lens.to(torch.int32)
+
+
 class UnitLM(TokenLM):
     """unit_lm.py:82-212 on the HIP engine."""
     base_model_prefix = "lm"
@@ -409,6 +428,10 @@ class UnitLM(TokenLM):
         # padding-free execution (HF / TRL `padding_free`): right-padded batches whose row lengths the host knows run as packed
         # segments and skip their pads (slam_forward_unpadded). Off by default; the trainers set it from their arguments.
         self.padding_free = False
+        # span masks: host attention masks with left or both-side padding (generate's output, prompt-left / completion-right
+        # pairs) run as packed segments from each row's first real column (slam_forward_unpadded_spans). Off by default: a mask
+        # that is not right padding then raises as it always did; `forward(..., span_masks=True)` switches one call on.
+        self.span_masks = False
         self._last_unpadded = False
         self._unpad_buf = None
         self._smoothing = 0.0  # the engine's label-smoothing epsilon as last set here (_set_label_smoothing)
@@ -898,10 +921,20 @@ class UnitLM(TokenLM):
     def forward(self, input_ids: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
                 num_items_in_batch=None, return_logits: bool = True, padding_free: Optional[bool] = None, lengths=None,
-                label_smoothing: float = 0.0, **unused) -> CausalLMOutput:
-        """UnitLM.forward (unit_lm.py:135-182). `attention_mask` must be right padding (what
-        DataCollatorForLanguageModeling produces): under the causal mask it never changes a real
-        token's output, so the engine does not read it.
+                label_smoothing: float = 0.0, starts=None, span_masks: Optional[bool] = None, **unused) -> CausalLMOutput:
+        """UnitLM.forward (unit_lm.py:135-182). Right padding (what DataCollatorForLanguageModeling produces) never changes
+        a real token's output under the causal mask, so the dense route does not read the mask. By default a host
+        `attention_mask` that is not right padding is a ValueError, as it always was.
+
+        Span batches: with `span_masks` on (None = `self.span_masks`, False by default) a host mask holds one contiguous run of
+        ones per row (a hole or a row of zeros is a ValueError that says so), and one with left or both-side padding
+        (`generate`'s output, TRL's prompt-left / completion-right pairs) runs as B packed segments whatever `padding_free`
+        says; there is no dense route for it. So does any batch given `starts=` with `lengths=` (lists or CPU tensors of B
+        ints: row b's real tokens are the columns starts[b] .. starts[b] + lengths[b] - 1; for device batches), with or without
+        the switch. A row's real tokens count positions from 0 (HF's rule for OPT; for RoPE the same relative
+        distances), so at its real positions a row gives what it gives run alone. The first real token of a row is never a
+        target, pad positions are never executed (labels there add nothing) and their logits are zeros. `position_ids`
+        with a span batch is a ValueError. A DEVICE mask is not read back and is taken as right padding.
 
         `padding_free` (None = `self.padding_free`, False by default): a [B, T] batch without `position_ids` whose row lengths
         are known ON THE HOST - from a host `attention_mask`, or from `lengths` (a list or CPU tensor of B ints in 1 .. T) -
@@ -919,11 +952,12 @@ class UnitLM(TokenLM):
         trainer: a bare `model(...)` never smooths, and 0 is the plain loss kernels, bit for bit."""
         assert input_ids is not None and input_ids.dim() == 2
         B, T = input_ids.shape
-        if attention_mask is not None and not attention_mask.is_cuda and not _right_padded(attention_mask):
-            # collated batches arrive on the host (the trainer's boundary): checked there. A DEVICE mask is not read back -
-            # that would stall the host behind the previous step's kernels in the hot loop; callers that build masks on
-            # the device (synthetic benches, DPO's padded pairs) construct right padding by definition.
-            raise ValueError("only right-padded attention_mask is supported")
+        # collated batches arrive on the host (the trainer's boundary): their masks are read there. A DEVICE mask is not read
+        # back - that would stall the host behind the previous step's kernels in the hot loop; callers that build masks on
+        # the device (synthetic benches, DPO's padded pairs) construct right padding by definition, or pass starts / lengths.
+        span = self._host_spans(B, T, attention_mask, lengths, starts, self.span_masks if span_masks is None else span_masks)
+        if span is not None and position_ids is not None:
+            raise ValueError("position_ids with a left- or both-side-padded batch: a span batch takes its positions from the mask")
         if position_ids is not None and B > 1 and not position_ids.is_cuda:
             # [B > 1, T] with positions is the dense layout (every row 0..T-1); a packed batch mis-shaped as several rows
             # would silently lose its segment bounds (the engine takes segments from a [1, sum T] row only)
@@ -935,6 +969,8 @@ class UnitLM(TokenLM):
         ids = input_ids.to(dev, torch.int64, non_blocking=nb)
         lab = labels.to(dev, torch.int64, non_blocking=nb) if labels is not None else None
         self._set_label_smoothing(label_smoothing)
+        if span is not None:
+            return self._forward_unpadded(ids, lab, span[1], num_items_in_batch, return_logits, starts=span[0])
         if (self.padding_free if padding_free is None else padding_free) and position_ids is None:
             lens = self._host_lengths(B, T, attention_mask, lengths)
             if lens is not None:
@@ -1009,6 +1045,34 @@ class UnitLM(TokenLM):
             return lengths  # as handed over: a pinned tensor (the trainer's prefetch pins DPO's collated lengths) stays pinned
         return lens.to(torch.int32)
 
+    @staticmethod
+    def _host_spans(B: int, T: int, attention_mask=None, lengths=None, starts=None, span_masks: bool = False):
+        """(starts, lens), int32 CPU tensors [B], when the host knows a SPAN batch: some row's real tokens start past column
+        0. From `starts` with `lengths`, else - with `span_masks` on - from a host attention_mask (read by mask_spans, which
+        refuses holes and rows of zeros; explicit `lengths` without `starts` mean right padding). With `span_masks` off a host
+        mask that is not right padding is refused. None = right padding or unknown: the dense or padding-free routes."""
+        if starts is None:
+            if attention_mask is None or attention_mask.is_cuda:
+                return None
+            if not span_masks:
+                if not _right_padded(attention_mask):
+                    raise ValueError("only right-padded attention_mask is supported by default: switch span masks on (UnitLM.span_masks "
+                                     "= True, or span_masks=True for one call) for left- or both-side-padded rows")
+                return None
+            st, ln = mask_spans(attention_mask)
+            if lengths is not None or ln.numel() != B:
+                return None
+        else:
+            if lengths is None:
+                raise ValueError("starts needs lengths: a span is (start, length)")
+            if any(isinstance(x, torch.Tensor) and x.is_cuda for x in (starts, lengths)):
+                raise ValueError("starts and lengths must live on the host (lists or CPU tensors): reading them back would stall the step")
+            st = torch.as_tensor(starts).to(torch.int64).reshape(-1)
+            ln = torch.as_tensor(lengths).to(torch.int64).reshape(-1)
+            if st.numel() != B or ln.numel() != B or int(st.min()) < 0 or int(ln.min()) < 1 or int((st + ln).max()) > T:
+                raise ValueError(f"a span batch needs {B} rows with 0 <= starts, 1 <= lengths and starts + lengths <= {T}")
+        return (st.to(torch.int32), ln.to(torch.int32)) if bool(st.any()) else None
+
     def _unpad_scratch(self, B: int, T: int) -> torch.Tensor:
         """The packed batch's arrays live here until backward (slam_unpadded_scratch_bytes; grown, never shrunk)."""
         nbytes = E.unpadded_scratch_bytes(B, T)
@@ -1017,9 +1081,10 @@ class UnitLM(TokenLM):
         off = (-self._unpad_buf.data_ptr()) % 256
         return self._unpad_buf[off:off + nbytes]
 
-    def _run_unpadded(self, ids, lab, lens: torch.Tensor, num_items: float, logits=None):
-        """slam_forward_unpadded over the device batch ids / lab [B, T] with host lengths `lens`. The workspace is sized by
-        B * T (rounded up to 64), not by this step's packed count, so it is never rebound from step to step."""
+    def _run_unpadded(self, ids, lab, lens: torch.Tensor, num_items: float, logits=None, starts: Optional[torch.Tensor] = None):
+        """slam_forward_unpadded over the device batch ids / lab [B, T] with host lengths `lens` - with host `starts` its span
+        form, slam_forward_unpadded_spans. The workspace is sized by B * T (rounded up to 64), not by this step's packed
+        count, so it is never rebound from step to step."""
         B, T = ids.shape
         m_packed = -(-int(lens.sum()) // 64) * 64
         self._ensure_workspace(-(-(B * T) // 64) * 64)
@@ -1029,10 +1094,16 @@ class UnitLM(TokenLM):
         lens_dev = (lens if lens.is_pinned() else lens.pin_memory()).to(self.device, non_blocking=True)
         self._hold = (ids, lab, lens_dev, scratch)  # the engine borrows these until backward
         self._last_unpadded = True
+        if starts is not None:
+            starts_dev = (starts if starts.is_pinned() else starts.pin_memory()).to(self.device, non_blocking=True)
+            self._hold = self._hold + (starts_dev,)
+            self.engine.forward_unpadded_spans(ids, lab, starts_dev, lens_dev, B, T, m_packed, scratch, num_items,
+                                               self._loss_buf if lab is not None else None, logits)
+            return
         self.engine.forward_unpadded(ids, lab, lens_dev, B, T, m_packed, scratch, num_items,
                                      self._loss_buf if lab is not None else None, logits)
 
-    def _forward_unpadded(self, ids, lab, lens, num_items_in_batch, return_logits) -> CausalLMOutput:
+    def _forward_unpadded(self, ids, lab, lens, num_items_in_batch, return_logits, starts=None) -> CausalLMOutput:
         B, T = ids.shape
         ids = ids.contiguous()
         lab = lab.contiguous() if lab is not None else None
@@ -1043,7 +1114,7 @@ class UnitLM(TokenLM):
             self.engine.arm_dropout(self._drop_call & 0xFFFFFFFF)
             self._drop_call += 1
         self._arm_neftune(T, T)  # the engine takes s from the padded width it is given
-        self._run_unpadded(ids, lab, lens, float(num_items_in_batch) if num_items_in_batch else 0.0, logits)
+        self._run_unpadded(ids, lab, lens, float(num_items_in_batch) if num_items_in_batch else 0.0, logits, starts)
         loss = None
         if lab is not None:
             loss = _EngineLoss.apply(self._anchor, self, self._loss_buf) if torch.is_grad_enabled() else self._loss_buf.clone()
@@ -1110,26 +1181,33 @@ class UnitLM(TokenLM):
             self.engine.seq_loglik(lab, B, T, ll, cnt)
         return ll / cnt if mean_nll else ll
 
-    def sequence_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, padding_free: Optional[bool] = None, lengths=None):
+    def sequence_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, padding_free: Optional[bool] = None, lengths=None,
+                       attention_mask: Optional[torch.Tensor] = None, starts=None, span_masks: Optional[bool] = None):
         """Per-sequence sums of target log-probs over the non-ignored labels (what TRL's DPOTrainer calls
         `chosen_logps` / `rejected_logps`). Leaves the engine ready for `scale_loss_rows` + `backward`:
         d(-logp_b)/dlogits is stored unscaled (num_items = 1). `padding_free` (None = `self.padding_free`) with host `lengths`
         (list or CPU tensor; without them, taken from pad_token_id when `input_ids` is on the host) runs the rows as packed
-        segments; a device batch without `lengths` keeps the padded path."""
+        segments; a device batch without `lengths` keeps the padded path. A host `attention_mask`, or `starts` with `lengths`,
+        is read as `forward` reads it: with `span_masks` on (None = `self.span_masks`) a left- or both-side-padded batch
+        (`generate`'s output with its mask) runs as a span batch whatever `padding_free` says, a right-padded mask gives the
+        row lengths."""
         B, T = input_ids.shape
         self._check_positions(T)
         self._set_label_smoothing(0.0)  # sequence objectives are defined on the plain log-likelihood
         lens = None
-        if self.padding_free if padding_free is None else padding_free:
-            if lengths is None and not input_ids.is_cuda:
+        span = self._host_spans(B, T, attention_mask, lengths, starts, self.span_masks if span_masks is None else span_masks)
+        if span is not None:
+            span, lens = span
+        elif self.padding_free if padding_free is None else padding_free:
+            if lengths is None and attention_mask is None and not input_ids.is_cuda:
                 lengths = self._lengths_from_pad(input_ids)
-            lens = self._host_lengths(B, T, None, lengths)
+            lens = self._host_lengths(B, T, attention_mask, lengths)
         ids = input_ids.to(self.device, torch.int64).contiguous()
         lab = labels.to(self.device, torch.int64).contiguous()
         ll = torch.empty(B, dtype=torch.float32, device=self.device)
         cnt = torch.empty(B, dtype=torch.float32, device=self.device)
         if lens is not None:
-            self._run_unpadded(ids, lab, lens, 1.0)
+            self._run_unpadded(ids, lab, lens, 1.0, starts=span)
             self.engine.seq_loglik_unpadded(B, ll, cnt)
             return ll, cnt
         self._ensure_workspace(B * T)

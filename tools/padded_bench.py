@@ -2,7 +2,7 @@
 same trainer with `padding_free` off and on, in alternating blocks of steps (device-synchronised host timing around every
 block; 10 warm-up steps per mode before its first block).
 
-    python tools/padded_bench.py [--steps 150] [--rounds 3] [--warmup 10] [--only train,dpo,ll]
+    python tools/padded_bench.py [--steps 150] [--rounds 3] [--warmup 10] [--only train,dpo,ll] [--pad-side right|left|both]
 
   train  bench.py's `extras.padded` workload (bench.synth_padded_358m: seed 4321, [8, 1024] rows of lengths U{256..1024},
          Slam-358M, bf16 optimizer state) through SLAMTrainer.optimizer_step; one instrumented step per mode adds the
@@ -10,6 +10,12 @@ block; 10 warm-up steps per mode before its first block).
   ll     UnitLM.log_likelihood on sWUGGY / sBLIMP-shaped batches: [32, 256] rows of lengths U{20..256}, the same model.
   dpo    bench.py's `--workload dpo` pairs (8 pairs = 16 sequences per step, prompt U{25..75}, completions U{50..150})
          through SLAMDPOTrainer.optimizer_step: policy forward + backward and the reference model's forward.
+
+  span   (`--pad-side left` or `both`; replaces the three above) the `train` rows shifted to the left edge / the middle of their
+         [8, 1024] batch and run as span batches (slam_forward_unpadded_spans, from the host mask), against the same rows
+         right-padded under padding_free: the same launches apart from the pack and its start offsets.
+  pack   (`--only pack`) the pack launch alone at 8 x 1024 and 300 x 7: slam_op_unpad_pack_spans with starts, with NULL, and
+         slam_op_unpad_pack, alternating; with `--parent-lib PATH` also slam_op_unpad_pack of that build of the parent commit.
 
 Prints one JSON line per workload - tokens/s (non-ignored labels) and ms/step of both modes from the summed blocks, the ratio
 per round (its spread is the run-to-run spread), the fill (real tokens / positions) and the bound 1 / fill - then the same
@@ -139,6 +145,95 @@ def bench_train_and_ll(a, dev, res):
     torch.cuda.empty_cache()
 
 
+def bench_span(a, dev, res):
+    """The extras.padded rows at the other edge (or in the middle) of their batch, against themselves right-padded."""
+    from slamkit_amd.model import UnitLM, UnitLMConfig
+    from slamkit_amd.trainer import SLAMTrainer, SLAMTrainingArguments
+    B, T = bench.B, bench.T
+    model = UnitLM(UnitLMConfig(base_model_name="Qwen/Qwen2.5-0.5B", rope_theta=10000.0, vocab_size=V, max_tokens=B * T), seed=0)
+    args = SLAMTrainingArguments(per_device_train_batch_size=B, gradient_accumulation_steps=1, learning_rate=1e-3, max_grad_norm=0.5,
+                                 logging_steps=0, optim_state_dtype="bfloat16")
+    tr = SLAMTrainer(model=model, args=args)
+    made = [bench.synth_padded_358m(0, 400 + s, dev) for s in range(4)]
+    col = torch.arange(T)[None]
+    right_mb, span_mb = [], []
+    for mb, lens in made:
+        ln = torch.tensor(lens)[:, None]
+        st = (T - ln) if a.pad_side == "left" else (T - ln) // 2
+        right_mb.append([dict(mb, attention_mask=(col < ln).long())])
+        moved = {k: torch.stack([torch.roll(v[b], int(st[b])) for b in range(B)]) for k, v in mb.items()}
+        span_mb.append([dict(moved, attention_mask=((col >= st) & (col < st + ln)).long())])
+    counts = [float(sum(lens)) for _, lens in made]
+    model.padding_free = True  # the right-padded rows run packed; the span rows run packed whatever that switch says
+    model.span_masks = True    # host masks that are not right padding are honoured (off by default)
+
+    def step_of(batches):
+        return lambda i: tr.optimizer_step(batches[i % 4], 1e-3, counts=(counts[i % 4],) * 2)
+    name = a.pad_side + "_span"
+    secs = alternate({"right_padding_free": step_of(right_mb), name: step_of(span_mb)}, a.steps, a.rounds, a.warmup)
+    row = lambda x: {"ms_per_step": round(1e3 * sum(x) / (a.steps * len(x)), 3),  # noqa: E731
+                     "tokens_per_s": round(sum(counts) / 4 * a.steps * len(x) / sum(x), 1),
+                     "ms_per_step_per_round": [round(1e3 * t / a.steps, 3) for t in x]}
+    ratios = [r / s for r, s in zip(secs["right_padding_free"], secs[name])]
+    r = {"workload": "span", "pad_side": a.pad_side, "steps_per_block": a.steps, "rounds": a.rounds,
+         "what": f"Slam-358M optimizer step, [8, 1024] rows of lengths U{{256..1024}}, seed 4321 (bench.py extras.padded): "
+                 f"padding on the {a.pad_side} side(s) as a span batch against right padding under padding_free",
+         "right_padding_free": row(secs["right_padding_free"]), name: row(secs[name]),
+         "ratio_right_over_span": round(sum(secs["right_padding_free"]) / sum(secs[name]), 4),
+         "ratio_per_round": [round(x, 4) for x in ratios], "ratio_spread": round(max(ratios) - min(ratios), 4)}
+    res.append(r)
+    print(json.dumps(r), flush=True)
+    model.padding_free = False
+    del tr, model
+    torch.cuda.empty_cache()
+
+
+def bench_pack(a, dev, res):
+    """Microseconds per pack launch, back to back on one stream between two events; the variants alternate, 3 rounds."""
+    import ctypes as C
+    from slamkit_amd import engine as E
+    lib = E.load_library()
+    doors = {"spans": (lib, True, "s"), "spans_null": (lib, True, None), "unpad_pack": (lib, False, None)}
+    if a.parent_lib:
+        old = C.CDLL(a.parent_lib)
+        vp, i32 = C.c_void_p, C.c_int32
+        old.slam_op_unpad_pack.restype = C.c_int
+        old.slam_op_unpad_pack.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, C.c_size_t, vp]
+        doors["parent_unpad_pack"] = (old, False, None)
+    n = 2000
+    for B, T in ((8, 1024), (300, 7)):
+        g = torch.Generator().manual_seed(B)
+        ids = torch.randint(1, V, (B, T), generator=g).to(dev)
+        lens_h = torch.randint(1, T + 1, (B,), generator=g)
+        lens = lens_h.to(torch.int32).to(dev)
+        starts = (T - lens_h).to(torch.int32).to(dev)  # left padding
+        Mp = -(-int(lens_h.sum()) // 64) * 64
+        nbytes = E.unpadded_scratch_bytes(B, T)
+        raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+        o = (-raw.data_ptr()) % 256
+        sp, st = raw.data_ptr() + o, E.current_stream_ptr()
+
+        def launch(door):
+            l, spans, s = doors[door]
+            if spans:
+                return l.slam_op_unpad_pack_spans(ids.data_ptr(), ids.data_ptr(), starts.data_ptr() if s else None, lens.data_ptr(),
+                                                  B, T, Mp, 0, sp, nbytes, st)
+            return l.slam_op_unpad_pack(ids.data_ptr(), ids.data_ptr(), lens.data_ptr(), B, T, Mp, 0, sp, nbytes, st)
+        us = {k: [] for k in doors}
+        for r in range(4):  # round 0 warms up
+            for k in doors:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    assert launch(k) == 0
+                e1.record()
+                torch.cuda.synchronize()
+                if r:
+                    us[k].append(round(1e3 * e0.elapsed_time(e1) / n, 3))
+        res.append({"workload": "pack", "B": B, "T": T, "M_packed": Mp, "launches_per_block": n, "us_per_launch_per_round": us})
+        print(json.dumps(res[-1]), flush=True)
+
+
 def bench_dpo(a, dev, res):
     from slamkit_amd.model import UnitLM, UnitLMConfig
     from slamkit_amd.trainer import DPOConfig, SLAMDPOTrainer
@@ -199,6 +294,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="blocks per mode")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--only", default="train,ll,dpo")
+    ap.add_argument("--pad-side", choices=["right", "left", "both"], default="right",
+                    help="left / both: the train rows as span batches against themselves right-padded under padding_free")
+    ap.add_argument("--parent-lib", default=None, help="--only pack: a libslam_engine.so built from the parent commit")
     a = ap.parse_args()
     a.only = set(a.only.split(","))
     a.steps = max(4, a.steps // 4 * 4)
@@ -206,13 +304,19 @@ def main():
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     res = []
-    if a.only & {"train", "ll"}:
-        bench_train_and_ll(a, dev, res)
-    if "dpo" in a.only:
-        bench_dpo(a, dev, res)
+    if "pack" in a.only:
+        bench_pack(a, dev, res)
+    elif a.pad_side != "right":
+        bench_span(a, dev, res)
+    else:
+        if a.only & {"train", "ll"}:
+            bench_train_and_ll(a, dev, res)
+        if "dpo" in a.only:
+            bench_dpo(a, dev, res)
     print(json.dumps({"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "device": torch.cuda.get_device_name(0),
                       "torch": torch.__version__, "hip": torch.version.hip}))
-    print(markdown(res))
+    if any("padded" in r for r in res):
+        print(markdown(res))
 
 
 if __name__ == "__main__":
