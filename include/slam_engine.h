@@ -304,6 +304,34 @@ int slam_extend_logits(SlamEngine* h, const int64_t* ids, const int32_t* new_len
                        float* logits_all, slam_stream_t stream);
 int slam_kv_rewind(SlamEngine* h, int32_t hi);
 
+/* ---- an FP8 KV cache: e4m3 codes with one power-of-two exponent per key / value vector ----------------------------------------
+ * The cache is the other large stream of a decode step and what bounds rows x context on one card. The _ex calls take its
+ * element type: SLAM_KV_BF16 (what slam_kv_cache_bytes / slam_bind_kv_cache mean, unchanged) or SLAM_KV_FP8_E4M3.
+ * Format of SLAM_KV_FP8_E4M3:
+ *   Granularity: one key vector or one value vector - one (layer, K | V, row, kv head, position), head_dim elements - is
+ *   head_dim e4m3 codes plus one int8 exponent e. The vector's bf16 elements (K after RoPE, both as the bf16 cache would have
+ *   stored them) take the place of a weight row in the rule stated under "decoding from FP8 weights" below, word for word:
+ *   e = 0 for an all-zero vector, else the smallest integer with amax <= 448 2^e from the bf16 bits, clamped to [-100, 120];
+ *   code = e4m3fn of x 2^-e, round to nearest even, the sign of zero kept; the NaN codes never appear and nothing saturates.
+ *   The value a code stands for, value(code) 2^e, is exact in bf16.
+ *   Layout: all codes first, uint8 [n_layers][2][max_batch][n_kv_heads][capacity][head_dim] in dim order (no permutation), then
+ *   all exponents, int8 [n_layers][2][max_batch][n_kv_heads][capacity]; index 0 of the second axis is K. The buffer is 256-byte
+ *   aligned: (head_dim + 1) bytes per vector against 2 head_dim. A caller may read it (tests do); rows at or beyond a row's
+ *   length are unspecified, as in the bf16 cache.
+ *   Non-finite K / V are NOT checked on the device and are outside the contract, as non-finite weights are.
+ * What runs on it: slam_prefill (also under "recompute" = 2, which scatters per layer inside the loop), slam_decode_step, the
+ * three slam_extend* calls and slam_kv_repeat pick their kernels from the bound type; slam_kv_rewind is host-only and does not
+ * care. Only the quantisation of K and V is lossy: every kernel computes, bit for bit, what its bf16 form computes over a bf16
+ * cache holding the dequantised values - the same grid, lanes, softmax order and merges. A token appended by a decode step or
+ * a chunk is rounded to bf16, quantised, stored, and used in that same call as dequantised.
+ * slam_kv_cache_bytes_ex: 0 for a NULL engine, non-positive sizes, another dtype, or FP8 on an OPT engine.
+ * slam_bind_kv_cache_ex: as slam_bind_kv_cache; SLAM_EINVAL with a message for a dtype other than the two and for FP8 on an
+ *   OPT engine (the family has no cached generation at all). Rebinding resets the prefill state, as before. */
+#define SLAM_KV_BF16 0
+#define SLAM_KV_FP8_E4M3 1
+size_t slam_kv_cache_bytes_ex(SlamEngine* h, int32_t max_batch, int32_t capacity, int32_t dtype);
+int slam_bind_kv_cache_ex(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity, int32_t dtype);
+
 /* ---- decoding from FP8 weights: an exact, power-of-two-scaled e4m3 copy of the decode projections ----
  * A decode step (and an extend pass of up to 64 rows) is one stream of the weights. This copy halves the bytes of that stream
  * for wqkv, wo, wgu and wd of every layer (and the head matrix when include_head) without a second model: quantising REPLACES
@@ -1150,6 +1178,27 @@ size_t slam_op_attn_extend_workspace(int B, int T, int nH, int nKV, int head_dim
 int slam_op_attn_extend(const void* qkv, const int32_t* base_lens, const int32_t* new_lens, void* k_cache, void* v_cache,
                         void* o, void* ws, size_t ws_bytes, int B, int T, int nH, int nKV, int head_dim, int capacity,
                         int kv_bound, slam_stream_t s);
+
+/* The FP8 KV cache's kernels alone (format: slam_bind_kv_cache_ex). k_codes / v_codes: uint8 [B][nKV][capacity][head_dim], 16-byte
+ * aligned; k_exps / v_exps: int8 [B][nKV][capacity] - one layer's slices of the cache with max_batch = B.
+ * slam_op_kv_scatter_fp8: the prefill's scatter - K / V columns of tokens t < lens[b] of qkv (bf16 [B T][(nH + 2 nKV) head_dim],
+ *   rotated) to cache rows t. slam_op_kv_extend_scatter_fp8: a chunk's - tokens t < new_lens[b] to rows base_lens[b] + t, both
+ *   clamped to kv_bound <= capacity. Nothing else of the buffers is written.
+ * slam_op_attn_decode_fp8 / slam_op_attn_extend_fp8: slam_op_attn_decode / slam_op_attn_extend with the cache in this form, the
+ *   same workspace sizes; o equals, bit for bit, the bf16 door's o over a bf16 cache holding value(code) 2^e.
+ * SLAM_EINVAL before any launch: a NULL pointer, a misaligned code array, head_dim not 64 or 128, and the bf16 doors' own list. */
+int slam_op_kv_scatter_fp8(const void* qkv, const int32_t* lens, void* k_codes, void* v_codes, void* k_exps, void* v_exps, int B, int T,
+                           int nH, int nKV, int head_dim, int capacity, slam_stream_t s);
+int slam_op_kv_extend_scatter_fp8(const void* qkv, const int32_t* base_lens, const int32_t* new_lens, void* k_codes, void* v_codes,
+                                  void* k_exps, void* v_exps, int B, int T, int nH, int nKV, int head_dim, int capacity, int kv_bound,
+                                  slam_stream_t s);
+int slam_op_attn_decode_fp8(const float* qkv, const void* bias, const int32_t* lens, void* k_codes, void* v_codes, void* k_exps,
+                            void* v_exps, void* o, void* ws, size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity,
+                            int kv_bound, float theta, slam_stream_t s);
+int slam_op_attn_extend_fp8(const void* qkv, const int32_t* base_lens, const int32_t* new_lens, void* k_codes, void* v_codes,
+                            void* k_exps, void* v_exps, void* o, void* ws, size_t ws_bytes, int B, int T, int nH, int nKV,
+                            int head_dim, int capacity, int kv_bound, slam_stream_t s);
+
 int slam_op_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int M, int H, float eps, slam_stream_t s);
 size_t slam_op_rmsnorm_bwd_workspace(int M, int H);
 int slam_op_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rstd, const void* dres, void* dx,

@@ -16,15 +16,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIB_DIR, "libslam_engine.so")
-SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "muon.hip", "decode.hip", "sampling.hip", "quant.hip",
+SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "muon.hip", "decode.hip", "decode_kv8.hip", "sampling.hip", "quant.hip",
            "engine.hip", "engine_cache.hip", "engine_optim.hip", "engine_comm.hip", "ops.hip"]
-HEADERS = ["common.h", "kernels.h", os.path.join("..", "..", "include", "slam_engine.h")]
+HEADERS = ["common.h", "kernels.h", "decode_attn.h", os.path.join("..", "..", "include", "slam_engine.h")]
 ENGINE_HEADER = "engine_impl.h"  # private to the engine*.hip files, and a dependency of those alone
 # The library exports the functions of include/slam_engine.h and nothing else: every other symbol is bound inside it
 EXPORT_MAP = os.path.join(HERE, "exports.map")
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in VGPRs (gfx950 has a unified file); without it the
 # attention kernels spend 256 v_accvgpr_read/write per K/V tile moving the online-softmax state around.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-mllvm", "-amdgpu-mfma-vgpr-form"]
+# Translation units that are built without the packed fp32 VALU forms (v_pk_fma_f32 and its kin): new kernels start here
+EXTRA_FLAGS = {"decode_kv8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -57,7 +59,7 @@ def build(force=False, verbose=True, probes=False):
         s = os.path.join(HERE, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         if force or _stale(o, [s] + hdrs + ([os.path.join(HERE, ENGINE_HEADER)] if src.startswith("engine") else [])):
-            cmd = [hipcc] + FLAGS + ["-c", s, "-o", o]
+            cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)

@@ -40,6 +40,53 @@ SLAM_DEVICE uint4 pack_bf16x8(const float* f) {
   return v;
 }
 
+// ---- power-of-two-scaled OCP e4m3fn (the rule of include/slam_engine.h: FP8 decode weights, FP8 KV cache) --------------
+// One rule for a weight row (quant.hip) and for a cached key / value vector (decode.hip): nothing here knows which.
+constexpr int FP8_EXP_MIN = -100, FP8_EXP_MAX = 120;
+// the exponent on the 15 magnitude bits of the bf16 amax: 0 for zero, else the smallest e with amax <= 448 2^e, clamped
+SLAM_DEVICE int fp8_exponent(int a) {
+  if (a == 0) return 0;
+  const int xb = a >> 7, m = a & 0x7f;
+  if (xb == 0) return FP8_EXP_MIN;  // bf16 subnormals: x <= -127
+  const int e = xb - 127 - (m <= 96 ? 8 : 7);
+  return min(max(e, FP8_EXP_MIN), FP8_EXP_MAX);
+}
+SLAM_DEVICE float pow2i(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
+// the largest of the 15-bit magnitudes of eight packed bf16
+SLAM_DEVICE int bf16x8_amax_bits(const uint4& v) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  int a = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a = max(a, max((int)(w[i] & 0x7fffu), (int)((w[i] >> 16) & 0x7fffu)));
+  return a;
+}
+// eight packed bf16 times inv = 2^-e -> eight codes (v_cvt_pk_fp8_f32: round to nearest even, the sign of zero kept)
+SLAM_DEVICE uint2 fp8_encode8(const uint4& v, float inv) {
+  float f[8];
+  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
+  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
+  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
+  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
+  int c0 = 0, c1 = 0;
+  c0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, c0, false);
+  c0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, c0, true);
+  c1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, c1, false);
+  c1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, c1, true);
+  return uint2{(uint32_t)c0, (uint32_t)c1};
+}
+// the four codes of one dword -> two dwords of bf16 pairs: code -> fp32 (v_cvt_pk_f32_fp8) -> times 2^e (exact) -> high 16 bits
+SLAM_DEVICE uint2 fp8_dequant4(uint32_t c, float sc) {
+  const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c, true);
+  uint2 r;
+  r.x = bf16_hi_pair(lo.x * sc, lo.y * sc);
+  r.y = bf16_hi_pair(hi.x * sc, hi.y * sc);
+  return r;
+}
+SLAM_DEVICE uint4 fp8_dequant8(const uint2& c, float sc) {
+  const uint2 a = fp8_dequant4(c.x, sc), b = fp8_dequant4(c.y, sc);
+  return uint4{a.x, a.y, b.x, b.y};
+}
+
 // ---- stochastic rounding fp32 -> bf16 ("adamw_sr") ------------------------------------------------
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, stateless - the output depends on (counter, key) alone.
 struct Philox4 { uint32_t w[4]; };

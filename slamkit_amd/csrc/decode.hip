@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "decode_attn.h"
 #include "kernels.h"
 
 namespace {
@@ -262,158 +263,6 @@ int launch_skinny_w8(const bf16_t* X, const uint8_t* Q, const int8_t* E, void* Y
   return (int)hipGetLastError();
 }
 
-// ---- decode attention ---------------------------------------------------------------------------------------------------
-SLAM_DEVICE float rescale(float m, float mn) { return m == -INFINITY ? 0.f : fast_exp2(m - mn); }
-
-// dims d0 .. d0 + 7 of one head (columns c0 ..) of the fp32 projection row, + bias, rotate-half RoPE with tables C / S
-template <int HD>
-SLAM_DEVICE void rope8(const float* row, const bf16_t* bias, int c0, int d0, const float* C, const float* S, float* out) {
-  constexpr int half = HD / 2;
-  const bool lo = d0 < half;
-  const int dp = lo ? d0 + half : d0 - half;  // partner dims
-  const int t0 = lo ? d0 : d0 - half;         // table index
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    float x = row[c0 + d0 + i], p = row[c0 + dp + i];
-    if (bias) { x += bf16_to_f32(bias[c0 + d0 + i]); p += bf16_to_f32(bias[c0 + dp + i]); }
-    const float c = C[t0 + i], s = S[t0 + i];
-    out[i] = lo ? x * c - p * s : x * c + p * s;
-  }
-}
-
-SLAM_DEVICE void round8(float* v) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = bf16_to_f32(f32_to_bf16(v[i]));
-}
-
-// grid (ns, nKV, B), 256 threads. Key j of the chunk is handled by the LG = HD / 8 lanes of one slot (8 dims each); every slot
-// keeps (m, l, o) for the G query heads of the group. part: [B][nH][ns][HD + 2] = o (unnormalised), m, l.
-template <int HD, int G>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restrict__ qkv, const bf16_t* __restrict__ bias,
-                                                          const float* __restrict__ cs, const float* __restrict__ sn,
-                                                          const float* __restrict__ csq, const float* __restrict__ snq,
-                                                          const int* __restrict__ lens, bf16_t* __restrict__ kc,
-                                                          bf16_t* __restrict__ vc, int cap, int nH, int nKV, int chunk, int ns,
-                                                          float* __restrict__ part) {
-  constexpr int LG = HD / 8, SLOTS = 64 / LG, half = HD / 2;
-  __shared__ float red[4][G][HD + 2];
-  const int s = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % LG, slot = lane / LG, d0 = sub * 8;
-  const int QKV = (nH + 2 * nKV) * HD;
-  const int pos = lens[b];
-  const int nkeys = min(pos + 1, cap);
-  const float* row = qkv + (size_t)b * QKV;
-  const float* C = cs + (size_t)b * half;
-  const float* S = sn + (size_t)b * half;
-  float qf[G][8];
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    rope8<HD>(row, bias, (g * G + i) * HD, d0, csq + (size_t)b * half, snq + (size_t)b * half, qf[i]);
-    round8(qf[i]);  // the forward stores q pre-scaled in bf16
-  }
-  float m_[G], l_[G], o_[G][8];
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    m_[i] = -INFINITY;
-    l_[i] = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o_[i][e] = 0.f;
-  }
-  const size_t cbase = ((size_t)b * nKV + g) * cap;
-  const int c_end = min(s * chunk + chunk, nkeys);
-  for (int j = s * chunk + wave * SLOTS + slot; j < c_end; j += 4 * SLOTS) {
-    float kf[8], vf[8];
-    bf16_t* kp = kc + (cbase + j) * HD + d0;
-    bf16_t* vp = vc + (cbase + j) * HD + d0;
-    if (j == pos) {  // the new token: rotate, round once, append
-      rope8<HD>(row, bias, (nH + g) * HD, d0, C, S, kf);
-      const int cv = (nH + nKV + g) * HD + d0;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vf[e] = row[cv + e] + (bias ? bf16_to_f32(bias[cv + e]) : 0.f);
-      const uint4 kb = pack_bf16x8(kf), vb = pack_bf16x8(vf);
-      *reinterpret_cast<uint4*>(kp) = kb;
-      *reinterpret_cast<uint4*>(vp) = vb;
-      unpack_bf16x8(kb, kf);
-      unpack_bf16x8(vb, vf);
-    } else {
-      unpack_bf16x8(*reinterpret_cast<const uint4*>(kp), kf);
-      unpack_bf16x8(*reinterpret_cast<const uint4*>(vp), vf);
-    }
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-      float sc = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sc += qf[i][e] * kf[e];
-#pragma unroll
-      for (int o = 1; o < LG; o <<= 1) sc += __shfl_xor(sc, o, 64);
-      const float mn = fmaxf(m_[i], sc);
-      const float a = rescale(m_[i], mn), p = fast_exp2(sc - mn);
-      l_[i] = l_[i] * a + p;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o_[i][e] = o_[i][e] * a + p * vf[e];
-      m_[i] = mn;
-    }
-  }
-  // slots of a wave: xor butterfly (both partners compute the same sums)
-#pragma unroll
-  for (int off = LG; off < 64; off <<= 1)
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-      const float m2 = __shfl_xor(m_[i], off, 64), l2 = __shfl_xor(l_[i], off, 64);
-      const float mn = fmaxf(m_[i], m2);
-      const float a = rescale(m_[i], mn), c = rescale(m2, mn);
-      l_[i] = l_[i] * a + l2 * c;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o_[i][e] = o_[i][e] * a + __shfl_xor(o_[i][e], off, 64) * c;
-      m_[i] = mn;
-    }
-  if (slot == 0) {
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[wave][i][d0 + e] = o_[i][e];
-      if (sub == 0) { red[wave][i][HD] = m_[i]; red[wave][i][HD + 1] = l_[i]; }
-    }
-  }
-  __syncthreads();
-  // waves in wave order
-  const int t = threadIdx.x;
-  if (t < G * LG) {
-    const int i = t / LG, e0 = (t % LG) * 8;
-    float mm = -INFINITY;
-    for (int w = 0; w < 4; ++w) mm = fmaxf(mm, red[w][i][HD]);
-    float l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int w = 0; w < 4; ++w) {
-      const float a = rescale(red[w][i][HD], mm);
-      l += red[w][i][HD + 1] * a;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] += red[w][i][e0 + e] * a;
-    }
-    float* dst = part + (((size_t)b * nH + g * G + i) * ns + s) * (HD + 2);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dst[e0 + e] = o[e];
-    if (e0 == 0) { dst[HD] = mm; dst[HD + 1] = l; }
-  }
-}
-
-// grid (nH, B), HD threads: merge the ns partials of one (row, head) in split order
-template <int HD>
-__global__ __launch_bounds__(128) void attn_decode_combine_kernel(const float* __restrict__ part, int ns, int nH,
-                                                                  bf16_t* __restrict__ out) {
-  const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-  const float* p = part + ((size_t)b * nH + h) * ns * (HD + 2);
-  float mm = -INFINITY;
-  for (int s = 0; s < ns; ++s) mm = fmaxf(mm, p[s * (HD + 2) + HD]);
-  float l = 0.f, o = 0.f;
-  for (int s = 0; s < ns; ++s) {
-    const float a = rescale(p[s * (HD + 2) + HD], mm);
-    l += p[s * (HD + 2) + HD + 1] * a;
-    o += p[s * (HD + 2) + d] * a;
-  }
-  out[((size_t)b * nH + h) * HD + d] = f32_to_bf16(o / l);
-}
-
 // ---- small helpers of prefill / decode -------------------------------------------------------------------------------------
 // K / V columns of rows t < lens[b] of one layer's qkv [B*T][QKV] -> cache rows t of (b, kv head); grid (.., B)
 __global__ __launch_bounds__(256) void kv_scatter_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
@@ -454,20 +303,6 @@ __global__ void lens_inc_kernel(int* __restrict__ lens, int B) {
   if (b < B) lens[b] = lens[b] + 1;
 }
 
-// ---- chunk attention over the cache (slam_extend) -----------------------------------------------------------------------------
-// Row b appends new_lens[b] tokens behind its base_lens[b] cached keys. Both counts are clamped once per block to what the
-// host bound allows, and every address below is formed from the clamped pair: base in [0, kv_bound], nl in
-// [0, min(T, kv_bound - base)], so no key index reaches kv_bound (<= cap) and no token index reaches T.
-struct ExtRow {
-  int base, nl;
-};
-SLAM_DEVICE ExtRow ext_row(const int* __restrict__ base_lens, const int* __restrict__ new_lens, int b, int T, int kv_bound) {
-  ExtRow r;
-  r.base = min(max(base_lens[b], 0), kv_bound);
-  r.nl = min(max(new_lens[b], 0), min(T, kv_bound - r.base));
-  return r;
-}
-
 // K / V columns of the real tokens t < nl of qkv [B*T][QKV] -> cache rows base + t of (b, kv head); grid (.., B)
 __global__ __launch_bounds__(256) void kv_extend_scatter_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                                 bf16_t* __restrict__ vc, const int* __restrict__ base_lens,
@@ -487,199 +322,6 @@ __global__ __launch_bounds__(256) void kv_extend_scatter_kernel(const bf16_t* __
   *reinterpret_cast<uint4*>(dst) = v;
 }
 
-constexpr int AE_KB = 32;  // keys per LDS stage: two 16-key score tiles = one 32-deep PV step
-
-// grid (ceil(T / 16), ns, B * nKV), 256 threads: one 16-query tile of one (row, KV group) over the keys of split y. The four
-// waves stage each AE_KB-key block of the group once (K row-major, V transposed) and share it: wave w serves query heads
-// w and w + 4 of the group. Scores are formed transposed, S^T = K Q^T, so that a lane ends up with P^T[keys][query] in the
-// B-operand map of the PV product with no exchange: lane l (qd = l >> 4, j = l & 15) holds query j's keys 4 qd + r of the first
-// tile and 16 + 4 qd + r of the second, and V^T is read with its contraction slots in that same key order. The output tile is
-// O^T: lane l holds o[query j][d = 16 dt + 4 qd + r]. part == nullptr (one split): o is normalised and stored, rows t >= nl of
-// the tile as zeros. Else part[((b T + t) nH + h) ns + split][HD + 4] = o (unnormalised), m, l for real rows; a split whose
-// key range starts at or above the tile's last key writes nothing (the combine never reads it).
-template <int HD, int G>
-__global__ __launch_bounds__(256) void attn_extend_kernel(const bf16_t* __restrict__ qkv, const int* __restrict__ base_lens,
-                                                          const int* __restrict__ new_lens, const bf16_t* __restrict__ kc,
-                                                          const bf16_t* __restrict__ vc, bf16_t* __restrict__ o,
-                                                          float* __restrict__ part, int T, int nH, int nKV, int cap, int kv_bound,
-                                                          int chunk, int ns) {
-  constexpr int NHW = (G + 3) / 4;      // heads per wave
-  constexpr int KS = HD + 8;            // K row stride (bf16): 16-byte rows, fragment reads spread over the banks
-  constexpr int VS = AE_KB + 4;         // V^T row stride (bf16): 8-byte rows, 18 dwords apart
-  constexpr int DT = HD / 16, KK = HD / 32, PS = HD + 4;
-  __shared__ __attribute__((aligned(16))) bf16_t Ks[AE_KB * KS];
-  __shared__ __attribute__((aligned(16))) bf16_t Vt[HD * VS];
-  const int q0 = blockIdx.x * 16, s = blockIdx.y;
-  const int b = blockIdx.z / nKV, g = blockIdx.z % nKV;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int qd = lane >> 4, j = lane & 15;
-  const ExtRow R = ext_row(base_lens, new_lens, b, T, kv_bound);
-  const int QKV = (nH + 2 * nKV) * HD;
-  const int tq = q0 + j;                       // this lane's query (token of the chunk)
-  const bool real = tq < R.nl;
-  const int tile_n = min(q0 + 16, R.nl) - q0;  // real queries of the tile (<= 0: none)
-  const int kend = tile_n > 0 ? R.base + q0 + tile_n : 0;  // keys the tile's last real query sees
-  const int k_lo = s * chunk;
-  const int k_hi = min(k_lo + chunk, kend);
-  if (part && k_lo >= k_hi) return;
-  const int qlim = R.base + min(tq, R.nl - 1);  // last key of this lane's query (clamped for the rows that are not real)
-
-  uint4 qf[NHW][KK];
-  f32x4_t acc[NHW][DT];
-  float m_[NHW], l_[NHW];
-#pragma unroll
-  for (int hh = 0; hh < NHW; ++hh) {
-    const int i = wave + 4 * hh;
-    m_[hh] = -INFINITY;
-    l_[hh] = 0.f;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc[hh][dt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int tr = max(min(tq, R.nl - 1), 0);
-    const bf16_t* qrow = qkv + ((size_t)b * T + tr) * QKV + (size_t)(g * G + min(i, G - 1)) * HD + 8 * qd;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) qf[hh][kk] = *reinterpret_cast<const uint4*>(qrow + 32 * kk);
-  }
-  const size_t cbase = ((size_t)b * nKV + g) * cap;
-  const uint4 zero = {0u, 0u, 0u, 0u};
-  constexpr int NV = AE_KB * (HD / 8) / 256;  // 16-byte pieces of a K (and of a V) block per thread
-  uint4 kx[NV], vx[NV];
-  // the block's K / V pieces of this thread into registers; keys at or beyond k_hi as zeros: p = 0 meets 0, never the
-  // cache's bits
-  auto fetch = [&](int kb) {
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int v = threadIdx.x + 256 * u;
-      const int kr = v / (HD / 8), d0 = (v % (HD / 8)) * 8;
-      const bool ok = kb + kr < k_hi;
-      const size_t src = (cbase + (ok ? kb + kr : 0)) * HD + d0;
-      kx[u] = ok ? *reinterpret_cast<const uint4*>(kc + src) : zero;
-      vx[u] = ok ? *reinterpret_cast<const uint4*>(vc + src) : zero;
-    }
-  };
-  if (k_lo < k_hi) fetch(k_lo);
-  for (int kb = k_lo; kb < k_hi; kb += AE_KB) {
-    __syncthreads();  // the previous block's fragment reads are done
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int v = threadIdx.x + 256 * u;
-      const int kr = v / (HD / 8), d0 = (v % (HD / 8)) * 8;
-      *reinterpret_cast<uint4*>(&Ks[kr * KS + d0]) = kx[u];
-      const uint32_t w[4] = {vx[u].x, vx[u].y, vx[u].z, vx[u].w};
-#pragma unroll
-      for (int e = 0; e < 8; ++e) Vt[(d0 + e) * VS + kr] = (bf16_t)(w[e >> 1] >> (16 * (e & 1)));
-    }
-    if (kb + AE_KB < k_hi) fetch(kb + AE_KB);  // the next block's loads fly under this block's products
-    __syncthreads();
-#pragma unroll
-    for (int hh = 0; hh < NHW; ++hh) {
-      if (wave + 4 * hh >= G) continue;  // wave-uniform
-      // S^T tiles: lane holds key 16 c + 4 qd + r of query j
-      f32x4_t sc[2];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        sc[c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < KK; ++kk) {
-          const uint4 kf = *reinterpret_cast<const uint4*>(&Ks[(16 * c + j) * KS + 32 * kk + 8 * qd]);
-          sc[c] = mfma16(kf, qf[hh][kk], sc[c]);
-        }
-      }
-      float mx = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ka = kb + 16 * c + 4 * qd + r;
-          const float x = (ka < k_hi && ka <= qlim) ? sc[c][r] : -INFINITY;
-          sc[c][r] = x;
-          mx = fmaxf(mx, x);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mn = fmaxf(m_[hh], mx);
-      const float ms = mn == -INFINITY ? 0.f : mn;  // nothing seen yet: every p below is exp2(-inf) = 0
-      const float a = rescale(m_[hh], mn);
-      float p[8], ps = 0.f;
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          p[4 * c + r] = fast_exp2(sc[c][r] - ms);
-          ps += p[4 * c + r];
-        }
-      l_[hh] = l_[hh] * a + ps;  // this lane's share; the four lanes of a query are summed at the end
-      m_[hh] = mn;
-      const uint4 pf = pack_bf16x8(p);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const bf16_t* vrow = &Vt[(16 * dt + j) * VS + 4 * qd];
-        const uint2 lo = *reinterpret_cast<const uint2*>(vrow), hi = *reinterpret_cast<const uint2*>(vrow + 16);
-        const uint4 vf = {lo.x, lo.y, hi.x, hi.y};
-        f32x4_t t = acc[hh][dt];
-        t[0] *= a; t[1] *= a; t[2] *= a; t[3] *= a;
-        acc[hh][dt] = mfma16(vf, pf, t);
-      }
-    }
-  }
-#pragma unroll
-  for (int hh = 0; hh < NHW; ++hh) {
-    const int i = wave + 4 * hh;
-    if (i >= G) continue;
-    float l = l_[hh];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const int hq = g * G + i;
-    if (part) {
-      if (!real) continue;
-      float* dst = part + ((((size_t)b * T + tq) * nH + hq) * ns + s) * PS;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-        *reinterpret_cast<float4*>(dst + 16 * dt + 4 * qd) = make_float4(acc[hh][dt][0], acc[hh][dt][1], acc[hh][dt][2], acc[hh][dt][3]);
-      if (qd == 0) { dst[HD] = m_[hh]; dst[HD + 1] = l; }
-    } else {
-      if (tq >= T) continue;
-      const float inv = real ? 1.f / l : 0.f;
-      bf16_t* dst = o + (((size_t)b * T + tq) * nH + hq) * HD;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        uint2 w = {0u, 0u};
-        if (real) {
-          w.x = pack_bf16x2(acc[hh][dt][0] * inv, acc[hh][dt][1] * inv);
-          w.y = pack_bf16x2(acc[hh][dt][2] * inv, acc[hh][dt][3] * inv);
-        }
-        *reinterpret_cast<uint2*>(dst + 16 * dt + 4 * qd) = w;
-      }
-    }
-  }
-}
-
-// grid (nH, T, B), HD threads: merge the partials of one (token, head) in split order; rows t >= nl become zeros. Only the
-// splits that start at or below the token's own key are read: those are exactly the ones that wrote this row.
-template <int HD>
-__global__ __launch_bounds__(128) void attn_extend_combine_kernel(const float* __restrict__ part,
-                                                                  const int* __restrict__ base_lens,
-                                                                  const int* __restrict__ new_lens, int T, int nH, int kv_bound,
-                                                                  int chunk, int ns, bf16_t* __restrict__ out) {
-  constexpr int PS = HD + 4;
-  const int h = blockIdx.x, t = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-  const int bt = b * T + t;
-  const ExtRow R = ext_row(base_lens, new_lens, b, T, kv_bound);
-  bf16_t* dst = out + ((size_t)bt * nH + h) * HD + d;
-  if (t >= R.nl) { *dst = 0; return; }
-  const int nsr = min(ns, (R.base + t) / chunk + 1);
-  const float* p = part + ((size_t)bt * nH + h) * ns * PS;
-  float mm = -INFINITY;
-  for (int s = 0; s < nsr; ++s) mm = fmaxf(mm, p[s * PS + HD]);
-  float l = 0.f, acc = 0.f;
-  for (int s = 0; s < nsr; ++s) {
-    const float ms = p[s * PS + HD];
-    if (ms == -INFINITY) continue;  // a split with no key for this query
-    const float a = fast_exp2(ms - mm);
-    l += p[s * PS + HD + 1] * a;
-    acc += p[s * PS + d] * a;
-  }
-  *dst = f32_to_bf16(acc / l);
-}
 
 // pos[b T + t] = lens[b] + t
 __global__ void extend_pos_kernel(const int* __restrict__ lens, int64_t* __restrict__ pos, int B, int T) {
@@ -982,30 +624,8 @@ int attn_decode_chunk(int B, int nH, int nKV, int head_dim, int kv_bound, size_t
 int attn_decode(const float* qkv, const bf16_t* bias, const float* cs, const float* sn, const float* csq, const float* snq,
                 const int* lens, bf16_t* kc, bf16_t* vc, int cap, int B, int nH, int nKV, int head_dim, int kv_bound, bf16_t* o,
                 float* part, size_t part_bytes, hipStream_t st) {
-  if (B <= 0 || nKV <= 0 || nH % nKV || kv_bound <= 0 || kv_bound > cap) return -1;
-  const int G = nH / nKV;
-  if ((head_dim != 64 && head_dim != 128) || G > 8) return -1;
-  const int chunk = attn_decode_chunk(B, nH, nKV, head_dim, kv_bound, part_bytes);
-  if (chunk <= 0) return -3;
-  const int ns = (kv_bound + chunk - 1) / chunk;
-  const dim3 grid(ns, nKV, B);
-#define AD_CASE(HD, GG)                                                                                                  \
-  case GG:                                                                                                               \
-    attn_decode_kernel<HD, GG><<<grid, 256, 0, st>>>(qkv, bias, cs, sn, csq, snq, lens, kc, vc, cap, nH, nKV, chunk, ns, \
-                                                     part);                                                              \
-    break;
-#define AD_SWITCH(HD) \
-  switch (G) { AD_CASE(HD, 1) AD_CASE(HD, 2) AD_CASE(HD, 3) AD_CASE(HD, 4) AD_CASE(HD, 5) AD_CASE(HD, 6) AD_CASE(HD, 7) AD_CASE(HD, 8) }
-  if (head_dim == 64) {
-    AD_SWITCH(64)
-    attn_decode_combine_kernel<64><<<dim3(nH, B), 64, 0, st>>>(part, ns, nH, o);
-  } else {
-    AD_SWITCH(128)
-    attn_decode_combine_kernel<128><<<dim3(nH, B), 128, 0, st>>>(part, ns, nH, o);
-  }
-#undef AD_SWITCH
-#undef AD_CASE
-  return (int)hipGetLastError();
+  return attn_decode_launch<false>(qkv, bias, cs, sn, csq, snq, lens, kc, vc, nullptr, nullptr, cap, B, nH, nKV, head_dim, kv_bound,
+                                   o, part, part_bytes, st);
 }
 
 int kv_scatter(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, const int* lens, int B, int T, int nH, int nKV, int head_dim, int cap,
@@ -1048,36 +668,14 @@ int attn_extend_chunk(int B, int T, int nH, int nKV, int head_dim, int kv_bound,
 
 int attn_extend(const bf16_t* qkv, const int* base_lens, const int* new_lens, bf16_t* kc, bf16_t* vc, int cap, int B, int T,
                 int nH, int nKV, int head_dim, int kv_bound, bf16_t* o, float* part, size_t part_bytes, hipStream_t st) {
-  if (B <= 0 || T <= 0 || nKV <= 0 || nH % nKV || kv_bound <= 0 || kv_bound > cap) return -1;
-  const int G = nH / nKV;
-  if ((head_dim != 64 && head_dim != 128) || G > 8) return -1;
-  if ((int64_t)B * nKV > 65535 || T > 65535 || (int64_t)B * T > 0x7fffffffLL / (nH * (head_dim + 4))) return -1;
-  if (((uintptr_t)qkv | (uintptr_t)kc | (uintptr_t)vc | (uintptr_t)o | (uintptr_t)part) & 15) return -1;
-  const int chunk = attn_extend_chunk(B, T, nH, nKV, head_dim, kv_bound, part ? part_bytes : 0);
-  const int ns = (kv_bound + chunk - 1) / chunk;
-  if (ns > 65535) return -1;
-  float* pp = ns > 1 ? part : nullptr;
+  int chunk, ns;
+  float* pp;
+  if (int r = attn_extend_plan(qkv, kc, vc, o, part, part_bytes, cap, B, T, nH, nKV, head_dim, kv_bound, &chunk, &ns, &pp)) return r;
   const size_t n = (size_t)T * (2 * nKV * head_dim / 8);
   kv_extend_scatter_kernel<<<dim3(nblk(n, 256), B), 256, 0, st>>>(qkv, kc, vc, base_lens, new_lens, T, nH, nKV, head_dim, cap,
                                                                   kv_bound);
-  const dim3 grid((T + 15) / 16, ns, B * nKV);
-#define AE_CASE(HD, GG)                                                                                                      \
-  case GG:                                                                                                                   \
-    attn_extend_kernel<HD, GG><<<grid, 256, 0, st>>>(qkv, base_lens, new_lens, kc, vc, o, pp, T, nH, nKV, cap, kv_bound, chunk, \
-                                                     ns);                                                                    \
-    break;
-#define AE_SWITCH(HD) \
-  switch (G) { AE_CASE(HD, 1) AE_CASE(HD, 2) AE_CASE(HD, 3) AE_CASE(HD, 4) AE_CASE(HD, 5) AE_CASE(HD, 6) AE_CASE(HD, 7) AE_CASE(HD, 8) }
-  if (head_dim == 64) {
-    AE_SWITCH(64)
-    if (pp) attn_extend_combine_kernel<64><<<dim3(nH, T, B), 64, 0, st>>>(pp, base_lens, new_lens, T, nH, kv_bound, chunk, ns, o);
-  } else {
-    AE_SWITCH(128)
-    if (pp) attn_extend_combine_kernel<128><<<dim3(nH, T, B), 128, 0, st>>>(pp, base_lens, new_lens, T, nH, kv_bound, chunk, ns, o);
-  }
-#undef AE_SWITCH
-#undef AE_CASE
-  return (int)hipGetLastError();
+  return attn_extend_launch<false>(qkv, base_lens, new_lens, kc, vc, nullptr, nullptr, cap, B, T, nH, nKV, head_dim, kv_bound, o, pp,
+                                   chunk, ns, st);
 }
 
 int extend_positions(const int* lens, int64_t* pos, int B, int T, hipStream_t st) {

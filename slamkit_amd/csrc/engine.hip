@@ -478,7 +478,7 @@ int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_id
   else CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
   for (int l = 0; l < L; ++l) {
     CK(layer_forward(h, l, M, false, st));
-    if (kv_lens) CK(kv_scatter(h->la[l].qkv, kv_k(h, l), kv_v(h, l), kv_lens, kv_B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st));
+    if (kv_lens) CK(cache_scatter(h, l, kv_lens, kv_B, T, st));
   }
   CK(join_optimizer(h, st));
   CK(join_params(h, st));

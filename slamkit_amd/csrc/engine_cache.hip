@@ -71,6 +71,27 @@ static int last_token_head(SlamEngine* h, const bf16_t* x, int B, float* logits,
   return SLAM_OK;
 }
 
+// The three attention-side calls of cached generation on layer l, each in the bound cache's form
+int cache_attn_decode(SlamEngine* h, int l, const float* qkvf, const bf16_t* bias, const int* lens, int B, bf16_t* o, size_t part_bytes,
+                      hipStream_t st) {
+  const SlamModelDesc& d = h->d;
+  if (h->kv_dtype == SLAM_KV_FP8_E4M3)
+    return attn_decode_fp8(qkvf, bias, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv8_codes(h, l, 0), kv8_codes(h, l, 1),
+                           kv8_exps(h, l, 0), kv8_exps(h, l, 1), h->kv_cap, B, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_hi + 1, o,
+                           (float*)h->logits, part_bytes, st);
+  return attn_decode(qkvf, bias, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, d.n_heads,
+                     d.n_kv_heads, d.head_dim, h->kv_hi + 1, o, (float*)h->logits, part_bytes, st);
+}
+int cache_attn_extend(SlamEngine* h, int l, const bf16_t* qkv, const int* lens, const int* new_lens, int B, int T, int kv_bound,
+                      bf16_t* o, size_t part_bytes, hipStream_t st) {
+  const SlamModelDesc& d = h->d;
+  if (h->kv_dtype == SLAM_KV_FP8_E4M3)
+    return attn_extend_fp8(qkv, lens, new_lens, kv8_codes(h, l, 0), kv8_codes(h, l, 1), kv8_exps(h, l, 0), kv8_exps(h, l, 1),
+                           h->kv_cap, B, T, d.n_heads, d.n_kv_heads, d.head_dim, kv_bound, o, (float*)h->logits, part_bytes, st);
+  return attn_extend(qkv, lens, new_lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, T, d.n_heads, d.n_kv_heads, d.head_dim, kv_bound, o,
+                     (float*)h->logits, part_bytes, st);
+}
+
 // slam_extend, slam_extend_score and slam_extend_logits: one body. EXT_LAST is slam_extend, launch for launch; EXT_SCORE adds,
 // between the layer loop and the last-token head, the final norm of all B T rows and the fused head + row statistics; EXT_ALL
 // replaces the last-token head by the final norm and the fp32 head of all B T rows (logits_out is then the [B][T][vocab] array).
@@ -121,8 +142,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
       if (q3) CK(qknorm_rope_fwd(a.qkv, h->QKV, M, nH, nKV, hd, P + o.q_norm, P + o.k_norm, h->cosb, h->sinb, h->cosq, h->sinq, d.rms_eps, nullptr, nullptr, st));
       else CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, hd, h->cosb, h->sinb, 0, st, nH, qscale));
     }
-    CK(attn_extend(a.qkv, lens, new_lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, T, nH, nKV, hd, kv_bound, a.o, (float*)h->logits,
-                   part_bytes, st));
+    CK(cache_attn_extend(h, l, a.qkv, lens, new_lens, B, T, kv_bound, a.o, part_bytes, st));
     CK(cached_mlp(h, l, M, st));
   }
   if (score) {
@@ -162,22 +182,44 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
 }
 }  // namespace
 
+namespace slam_impl {
+int cache_scatter(SlamEngine* h, int l, const int32_t* lens, int B, int T, hipStream_t st) {
+  const SlamModelDesc& d = h->d;
+  if (h->kv_dtype == SLAM_KV_FP8_E4M3)
+    return kv_scatter_fp8(h->la[l].qkv, kv8_codes(h, l, 0), kv8_codes(h, l, 1), kv8_exps(h, l, 0), kv8_exps(h, l, 1), lens, B, T,
+                          d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st);
+  return kv_scatter(h->la[l].qkv, kv_k(h, l), kv_v(h, l), lens, B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st);
+}
+}  // namespace slam_impl
+
 extern "C" {
 
-size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity) {
-  if (!h || max_batch <= 0 || capacity <= 0) return 0;
+size_t slam_kv_cache_bytes_ex(SlamEngine* h, int32_t max_batch, int32_t capacity, int32_t dtype) {
+  if (!h || max_batch <= 0 || capacity <= 0 || (dtype != SLAM_KV_BF16 && dtype != SLAM_KV_FP8_E4M3)) return 0;
   const SlamModelDesc& d = h->d;
-  return (size_t)d.n_layers * 2 * max_batch * d.n_kv_heads * capacity * d.head_dim * sizeof(bf16_t);
+  const size_t vectors = (size_t)d.n_layers * 2 * max_batch * d.n_kv_heads * capacity;
+  if (dtype == SLAM_KV_BF16) return vectors * d.head_dim * sizeof(bf16_t);
+  return h->arch == 1 ? 0 : vectors * (d.head_dim + 1);  // codes, then one exponent byte per vector
 }
-int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity) {
+int slam_bind_kv_cache_ex(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity, int32_t dtype) {
   if (!h || !cache || max_batch <= 0 || capacity <= 0) return SLAM_EINVAL;
+  if (dtype != SLAM_KV_BF16 && dtype != SLAM_KV_FP8_E4M3)
+    return h->fail(SLAM_EINVAL, "KV cache dtype must be SLAM_KV_BF16 (0) or SLAM_KV_FP8_E4M3 (1)");
+  if (dtype == SLAM_KV_FP8_E4M3 && h->arch == 1) return h->fail(SLAM_EINVAL, "FP8 KV cache: the OPT family has no KV cache");
   if (((uintptr_t)cache) & 255) return h->fail(SLAM_EINVAL, "KV cache must be 256-byte aligned");
-  if (bytes < slam_kv_cache_bytes(h, max_batch, capacity)) return h->fail(SLAM_ENOMEM, "KV cache too small");
+  if (bytes < slam_kv_cache_bytes_ex(h, max_batch, capacity, dtype)) return h->fail(SLAM_ENOMEM, "KV cache too small");
   h->kv = (bf16_t*)cache;
+  h->kv_dtype = dtype;
   h->kv_bmax = max_batch;
   h->kv_cap = capacity;
   h->kv_ready = false;
   return SLAM_OK;
+}
+size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity) {
+  return slam_kv_cache_bytes_ex(h, max_batch, capacity, SLAM_KV_BF16);
+}
+int slam_bind_kv_cache(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity) {
+  return slam_bind_kv_cache_ex(h, cache, bytes, max_batch, capacity, SLAM_KV_BF16);
 }
 
 size_t slam_decode_w8_bytes(SlamEngine* h, int32_t include_head) {
@@ -249,7 +291,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   const bool shared_qkv = h->recompute == 2 && L > RC_SLOTS;
   CK(forward_layers(h, ids, nullptr, nullptr, nullptr, M, T, st, shared_qkv ? lens : nullptr, B));
   for (int l = 0; l < L && !shared_qkv; ++l)
-    CK(kv_scatter(h->la[l].qkv, kv_k(h, l), kv_v(h, l), lens, B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st));
+    CK(cache_scatter(h, l, lens, B, T, st));
   // logits of each row's last prompt token only: gather, final norm, one fp32 head launch over B rows
   CK(gather_last_rows(h->hs[L], h->dx, lens, B, T, H, st));
   CK(last_token_head(h, h->dx, B, logits_out, st));
@@ -294,8 +336,7 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
     CK(decode_proj(h, a.x1, P + o.wqkv, nullptr, qkvf, nullptr, nullptr, B, h->QKV, H, st));
     // Qwen3: the q and k heads are normalised in the fp32 row; attn_decode then rotates and rounds once, without a bias
     if (q3) CK(qknorm_rows_f32(qkvf, h->QKV, B, nH, nKV, hd, P + o.q_norm, P + o.k_norm, d.rms_eps, st));
-    CK(attn_decode(qkvf, q3 ? nullptr : P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, nH, nKV, hd,
-                   h->kv_hi + 1, a.o, (float*)h->logits, part_bytes, st));
+    CK(cache_attn_decode(h, l, qkvf, q3 ? nullptr : P + o.bqkv, lens, B, a.o, part_bytes, st));
     CK(cached_mlp(h, l, B, st));
   }
   CK(last_token_head(h, h->hs[L], B, logits_out, st));
@@ -312,8 +353,12 @@ int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_
   if ((int64_t)h->kv_B * n > h->kv_bmax) return h->fail(SLAM_EINVAL, "B * n rows exceed the bound KV cache");
   if (n == 1) return SLAM_OK;
   const SlamModelDesc& d = h->d;
-  CK(kv_repeat(h->kv, lens, logits, h->kv_B, n, h->kv_bmax, d.n_layers, d.n_kv_heads, d.head_dim, h->kv_cap, h->kv_hi, d.vocab,
-               (hipStream_t)stream));
+  if (h->kv_dtype == SLAM_KV_FP8_E4M3)
+    CK(kv_repeat_fp8(kv8_codes(h, 0, 0), kv8_exps(h, 0, 0), lens, logits, h->kv_B, n, h->kv_bmax, d.n_layers, d.n_kv_heads, d.head_dim,
+                     h->kv_cap, h->kv_hi, d.vocab, (hipStream_t)stream));
+  else
+    CK(kv_repeat(h->kv, lens, logits, h->kv_B, n, h->kv_bmax, d.n_layers, d.n_kv_heads, d.head_dim, h->kv_cap, h->kv_hi, d.vocab,
+                 (hipStream_t)stream));
   h->kv_B *= n;
   return SLAM_OK;
 }

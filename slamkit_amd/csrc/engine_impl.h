@@ -248,6 +248,7 @@ struct SlamEngine {
 
   // KV cache of slam_prefill / slam_decode_step (caller-owned): per layer K[kv_bmax][nKV][kv_cap][hd] then V (same shape)
   bf16_t* kv = nullptr;
+  int kv_dtype = 0;      // SLAM_KV_BF16, or SLAM_KV_FP8_E4M3: all codes in the same order, one byte each, then all exponents
   int kv_bmax = 0, kv_cap = 0;
   int kv_B = 0;          // rows of the last prefill
   int kv_hi = 0;         // host bound of every row's cached length: the prefill's T, + 1 per decode step, + T per slam_extend
@@ -355,5 +356,14 @@ inline bf16_t* kv_k(SlamEngine* h, int l) {
   return h->kv + (size_t)l * 2 * h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim;
 }
 inline bf16_t* kv_v(SlamEngine* h, int l) { return kv_k(h, l) + (size_t)h->kv_bmax * h->d.n_kv_heads * h->kv_cap * h->d.head_dim; }
+
+// the FP8 form: codes / exponents of layer l's K (v = 0) or V (v = 1)
+inline size_t kv8_vectors(SlamEngine* h) { return (size_t)h->kv_bmax * h->d.n_kv_heads * h->kv_cap; }  // of one (layer, K | V)
+inline uint8_t* kv8_codes(SlamEngine* h, int l, int v) { return (uint8_t*)h->kv + ((size_t)l * 2 + v) * kv8_vectors(h) * h->d.head_dim; }
+inline int8_t* kv8_exps(SlamEngine* h, int l, int v) {
+  return (int8_t*)h->kv + (size_t)h->d.n_layers * 2 * kv8_vectors(h) * h->d.head_dim + ((size_t)l * 2 + v) * kv8_vectors(h);
+}
+// layer l's K / V rows t < lens[b] of la[l].qkv into the bound cache, in its form (engine_cache.hip)
+int cache_scatter(SlamEngine* h, int l, const int32_t* lens, int B, int T, hipStream_t st);
 
 }  // namespace slam_impl

@@ -425,6 +425,24 @@ int lens_add(int* lens, const int* new_lens, int B, int T, hipStream_t st);
 // row in descending b (hazard-free for every (B, n): decode.hip's header). kv_bound: host bound of lens.
 int kv_repeat(bf16_t* kv, int* lens, float* logits, int B, int n, int bmax, int L, int nKV, int head_dim, int cap, int kv_bound,
               int vocab, hipStream_t st);
+// decode_kv8.hip: the FP8 form of the cache (include/slam_engine.h: SLAM_KV_FP8_E4M3). One layer's K and V as codes kc / vc
+// ([B][nKV][cap][hd] bytes, dim order, 16-byte aligned) and exponents ke / ve (int8 [B][nKV][cap]); a vector's exponent and codes
+// follow the rule of quantize_rows_fp8 for a weight row. Each call is its bf16 namesake with the cache read and written in this
+// form: attn_decode_fp8 / attn_extend_fp8 return, bit for bit, what attn_decode / attn_extend return over a bf16 cache holding
+// value(code) 2^e, and append the new tokens quantised. -1: bad argument.
+int kv_scatter_fp8(const bf16_t* qkv, uint8_t* kc, uint8_t* vc, int8_t* ke, int8_t* ve, const int* lens, int B, int T, int nH,
+                   int nKV, int head_dim, int cap, hipStream_t st);
+int kv_extend_scatter_fp8(const bf16_t* qkv, uint8_t* kc, uint8_t* vc, int8_t* ke, int8_t* ve, const int* base_lens,
+                          const int* new_lens, int B, int T, int nH, int nKV, int head_dim, int cap, int kv_bound, hipStream_t st);
+int attn_decode_fp8(const float* qkv, const bf16_t* bias, const float* cs, const float* sn, const float* csq, const float* snq,
+                    const int* lens, uint8_t* kc, uint8_t* vc, int8_t* ke, int8_t* ve, int cap, int B, int nH, int nKV,
+                    int head_dim, int kv_bound, bf16_t* o, float* part, size_t part_bytes, hipStream_t st);
+int attn_extend_fp8(const bf16_t* qkv, const int* base_lens, const int* new_lens, uint8_t* kc, uint8_t* vc, int8_t* ke, int8_t* ve,
+                    int cap, int B, int T, int nH, int nKV, int head_dim, int kv_bound, bf16_t* o, float* part, size_t part_bytes,
+                    hipStream_t st);
+// codes: L x { K, V } x [bmax][nKV][cap][head_dim] bytes, exps: L x { K, V } x [bmax][nKV][cap]
+int kv_repeat_fp8(uint8_t* codes, int8_t* exps, int* lens, float* logits, int B, int n, int bmax, int L, int nKV, int head_dim,
+                  int cap, int kv_bound, int vocab, hipStream_t st);
 // LM head fused with the row statistics (include/slam_engine.h: slam_op_score_rows): for row m of X (bf16 [M][K]) against the
 // head W (bf16 [V][K]) on v_mfma_f32_16x16x32_bf16, lp = log-softmax at targets[m] and argmax = the lowest id of the largest
 // score, from fp32 accumulators that are never stored. colmask: nullable, >= V bytes, non-zero = the column counts as -inf.

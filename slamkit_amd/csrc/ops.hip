@@ -119,9 +119,10 @@ size_t slam_op_attn_decode_workspace(int B, int nH, int nKV, int head_dim, int k
   const int chunk = attn_decode_chunk(B, nH, nKV, head_dim, kv_bound, (size_t)-1);
   return attn_decode_op_head(B, head_dim) + attn_decode_part_bytes(B, nH, head_dim, (kv_bound + chunk - 1) / chunk);
 }
-int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens, void* k_cache, void* v_cache, void* o, void* ws,
-                        size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity, int kv_bound, float theta,
-                        slam_stream_t s) {
+// both cache forms: k_exps == nullptr is the bf16 door
+static int attn_decode_op(const float* qkv, const void* bias, const int32_t* lens, void* k_cache, void* v_cache, void* k_exps,
+                          void* v_exps, void* o, void* ws, size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity,
+                          int kv_bound, float theta, slam_stream_t s) {
   if (!qkv || !lens || !k_cache || !v_cache || !o || !ws || B <= 0 || (head_dim != 64 && head_dim != 128)) return SLAM_EINVAL;
   const size_t head = attn_decode_op_head(B, head_dim);
   if (ws_bytes <= head) return SLAM_ENOMEM;
@@ -134,8 +135,50 @@ int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens,
   if (r) return r;
   r = rope_table(pos, B, 1, head_dim, theta, tab, tab + n, tab + 2 * n, tab + 3 * n, 1.44269504088896340736f / sqrtf((float)head_dim), st);
   if (r) return r;
+  if (k_exps)
+    return attn_decode_fp8(qkv, (const bf16_t*)bias, tab, tab + n, tab + 2 * n, tab + 3 * n, lens, (uint8_t*)k_cache, (uint8_t*)v_cache,
+                           (int8_t*)k_exps, (int8_t*)v_exps, capacity, B, nH, nKV, head_dim, kv_bound, (bf16_t*)o, (float*)(w + head),
+                           ws_bytes - head, st);
   return attn_decode(qkv, (const bf16_t*)bias, tab, tab + n, tab + 2 * n, tab + 3 * n, lens, (bf16_t*)k_cache, (bf16_t*)v_cache,
                      capacity, B, nH, nKV, head_dim, kv_bound, (bf16_t*)o, (float*)(w + head), ws_bytes - head, st);
+}
+int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens, void* k_cache, void* v_cache, void* o, void* ws,
+                        size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity, int kv_bound, float theta,
+                        slam_stream_t s) {
+  return attn_decode_op(qkv, bias, lens, k_cache, v_cache, nullptr, nullptr, o, ws, ws_bytes, B, nH, nKV, head_dim, capacity, kv_bound,
+                        theta, s);
+}
+int slam_op_attn_decode_fp8(const float* qkv, const void* bias, const int32_t* lens, void* k_codes, void* v_codes, void* k_exps,
+                            void* v_exps, void* o, void* ws, size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity,
+                            int kv_bound, float theta, slam_stream_t s) {
+  if (!k_exps || !v_exps) return SLAM_EINVAL;
+  const int r = attn_decode_op(qkv, bias, lens, k_codes, v_codes, k_exps, v_exps, o, ws, ws_bytes, B, nH, nKV, head_dim, capacity,
+                               kv_bound, theta, s);
+  return r == -1 ? SLAM_EINVAL : r;
+}
+int slam_op_kv_scatter_fp8(const void* qkv, const int32_t* lens, void* k_codes, void* v_codes, void* k_exps, void* v_exps, int B, int T,
+                           int nH, int nKV, int head_dim, int capacity, slam_stream_t s) {
+  const int r = kv_scatter_fp8((const bf16_t*)qkv, (uint8_t*)k_codes, (uint8_t*)v_codes, (int8_t*)k_exps, (int8_t*)v_exps, lens, B, T, nH,
+                               nKV, head_dim, capacity, (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
+}
+int slam_op_kv_extend_scatter_fp8(const void* qkv, const int32_t* base_lens, const int32_t* new_lens, void* k_codes, void* v_codes,
+                                  void* k_exps, void* v_exps, int B, int T, int nH, int nKV, int head_dim, int capacity, int kv_bound,
+                                  slam_stream_t s) {
+  const int r = kv_extend_scatter_fp8((const bf16_t*)qkv, (uint8_t*)k_codes, (uint8_t*)v_codes, (int8_t*)k_exps, (int8_t*)v_exps,
+                                      base_lens, new_lens, B, T, nH, nKV, head_dim, capacity, kv_bound, (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
+}
+int slam_op_attn_extend_fp8(const void* qkv, const int32_t* base_lens, const int32_t* new_lens, void* k_codes, void* v_codes,
+                            void* k_exps, void* v_exps, void* o, void* ws, size_t ws_bytes, int B, int T, int nH, int nKV,
+                            int head_dim, int capacity, int kv_bound, slam_stream_t s) {
+  if (!qkv || !base_lens || !new_lens || !k_codes || !v_codes || !k_exps || !v_exps || !o || B <= 0 || T <= 0 || nH <= 0 || nKV <= 0)
+    return SLAM_EINVAL;
+  if ((head_dim != 64 && head_dim != 128) || nH % nKV || nH / nKV > 8 || kv_bound <= 0 || kv_bound > capacity) return SLAM_EINVAL;
+  const int r = attn_extend_fp8((const bf16_t*)qkv, base_lens, new_lens, (uint8_t*)k_codes, (uint8_t*)v_codes, (int8_t*)k_exps,
+                                (int8_t*)v_exps, capacity, B, T, nH, nKV, head_dim, kv_bound, (bf16_t*)o, (float*)ws, ws ? ws_bytes : 0,
+                                (hipStream_t)s);
+  return r == -1 ? SLAM_EINVAL : r;
 }
 size_t slam_op_attn_extend_workspace(int B, int T, int nH, int nKV, int head_dim, int kv_bound) {
   if (B <= 0 || T <= 0 || nH <= 0 || nKV <= 0 || kv_bound <= 0) return 0;

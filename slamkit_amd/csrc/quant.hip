@@ -24,24 +24,7 @@ SLAM_DEVICE int wave_max_i(int v) {
   return v;
 }
 
-// the exponent rule on the 15 magnitude bits of amax
-SLAM_DEVICE int w8_exponent(int a) {
-  if (a == 0) return 0;
-  const int xb = a >> 7, m = a & 0x7f;
-  if (xb == 0) return slam::W8_EXP_MIN;  // bf16 subnormals: x <= -127
-  const int e = xb - 127 - (m <= 96 ? 8 : 7);
-  return min(max(e, slam::W8_EXP_MIN), slam::W8_EXP_MAX);
-}
-SLAM_DEVICE float pow2i(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
-
-// the four codes of one dword -> two dwords of bf16 pairs: code -> fp32 -> times 2^e (exact) -> high 16 bits
-SLAM_DEVICE uint2 w8_dequant4(uint32_t c, float sc) {
-  const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c, true);
-  uint2 r;
-  r.x = bf16_hi_pair(lo.x * sc, lo.y * sc);
-  r.y = bf16_hi_pair(hi.x * sc, hi.y * sc);
-  return r;
-}
+static_assert(FP8_EXP_MIN == slam::W8_EXP_MIN && FP8_EXP_MAX == slam::W8_EXP_MAX, "one exponent range (common.h, kernels.h)");
 
 // grid ceil(N / 4) x 256 threads: wave w of block b owns row 4 b + w; a lane takes the 8-element chunks lane, lane + 64, ..
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(bf16_t* __restrict__ W, uint8_t* __restrict__ Q,
@@ -54,26 +37,17 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(bf16_t* __restri
   const int chunks = K >> 3;
   int a = 0;
   for (int c = lane; c < chunks; c += 64) {
-    const uint4 v = *reinterpret_cast<const uint4*>(wrow + 8 * c);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a = max(a, max((int)(w[i] & 0x7fffu), (int)((w[i] >> 16) & 0x7fffu)));
+    a = max(a, bf16x8_amax_bits(*reinterpret_cast<const uint4*>(wrow + 8 * c)));
   }
   a = wave_max_i(a);
-  const int e = w8_exponent(a);
+  const int e = fp8_exponent(a);
   if (lane == 0) E[n] = (int8_t)e;
   const float inv = pow2i(-e), sc = pow2i(e);
   for (int c = lane; c < chunks; c += 64) {
     const uint4 v = *reinterpret_cast<const uint4*>(wrow + 8 * c);
-    float f[8];
-    unpack_bf16x8(v, f);
-    int c0 = 0, c1 = 0;
-    c0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, c0, false);
-    c0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, c0, true);
-    c1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, c1, false);
-    c1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, c1, true);
-    *reinterpret_cast<uint2*>(qrow + slam::w8_code_pos(8 * c)) = uint2{(uint32_t)c0, (uint32_t)c1};
-    const uint2 d0 = w8_dequant4((uint32_t)c0, sc), d1 = w8_dequant4((uint32_t)c1, sc);
+    const uint2 q = fp8_encode8(v, inv);
+    *reinterpret_cast<uint2*>(qrow + slam::w8_code_pos(8 * c)) = q;
+    const uint2 d0 = fp8_dequant4(q.x, sc), d1 = fp8_dequant4(q.y, sc);
     *reinterpret_cast<uint4*>(wrow + 8 * c) = uint4{d0.x, d0.y, d1.x, d1.y};
   }
 }
@@ -88,7 +62,7 @@ __global__ __launch_bounds__(256) void dequantize_rows_fp8_kernel(const uint8_t*
   const float sc = pow2i(E[n]);
   for (int c = lane; c < (K >> 3); c += 64) {
     const uint2 q = *reinterpret_cast<const uint2*>(qrow + slam::w8_code_pos(8 * c));
-    const uint2 d0 = w8_dequant4(q.x, sc), d1 = w8_dequant4(q.y, sc);
+    const uint2 d0 = fp8_dequant4(q.x, sc), d1 = fp8_dequant4(q.y, sc);
     *reinterpret_cast<uint4*>(wrow + 8 * c) = uint4{d0.x, d0.y, d1.x, d1.y};
   }
 }

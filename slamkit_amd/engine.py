@@ -134,6 +134,8 @@ def load_library(path: Optional[str] = None):
         "slam_backward": (C.c_int, [vp, f32, i32, BUCKET_CB, vp, vp]),
         "slam_kv_cache_bytes": (sz, [vp, i32, i32]),
         "slam_bind_kv_cache": (C.c_int, [vp, vp, sz, i32, i32]),
+        "slam_kv_cache_bytes_ex": (sz, [vp, i32, i32, i32]),
+        "slam_bind_kv_cache_ex": (C.c_int, [vp, vp, sz, i32, i32, i32]),
         "slam_prefill": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
         "slam_decode_step": (C.c_int, [vp, vp, vp, i32, vp, vp]),
         "slam_sample_workspace_bytes": (sz, [i32, i32, i32]),
@@ -234,6 +236,10 @@ def load_library(path: Optional[str] = None):
         "slam_op_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           f32, vp]),
         "slam_op_attn_extend_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "slam_op_kv_scatter_fp8": (C.c_int, [vp] * 6 + [C.c_int] * 6 + [vp]),
+        "slam_op_kv_extend_scatter_fp8": (C.c_int, [vp] * 7 + [C.c_int] * 7 + [vp]),
+        "slam_op_attn_decode_fp8": (C.c_int, [vp] * 9 + [sz] + [C.c_int] * 6 + [C.c_float, vp]),
+        "slam_op_attn_extend_fp8": (C.c_int, [vp] * 9 + [sz] + [C.c_int] * 7 + [vp]),
         "slam_op_attn_extend": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, vp]),
         "slam_op_rmsnorm_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
@@ -307,6 +313,16 @@ class _Shifted:
 def current_stream_ptr() -> int:
     import torch
     return int(torch.cuda.current_stream().cuda_stream)
+
+
+KV_CACHE_DTYPES = {"bfloat16": 0, "fp8_e4m3": 1}  # SLAM_KV_BF16, SLAM_KV_FP8_E4M3
+
+
+def kv_dtype_code(dtype) -> int:
+    """The C ABI's code of a KV cache dtype name; anything but the two names is a ValueError."""
+    if not isinstance(dtype, str) or dtype not in KV_CACHE_DTYPES:
+        raise ValueError(f'kv_cache_dtype must be "bfloat16" or "fp8_e4m3" (got {dtype!r})')
+    return KV_CACHE_DTYPES[dtype]
 
 
 class EngineError(RuntimeError):
@@ -759,13 +775,15 @@ class Engine:
                                         stream if stream is not None else current_stream_ptr()))
 
     # -- KV-cached generation ---------------------------------------------------------------------
-    def kv_cache_bytes(self, max_batch: int, capacity: int) -> int:
-        return int(self.lib.slam_kv_cache_bytes(self.h, max_batch, capacity))
+    def kv_cache_bytes(self, max_batch: int, capacity: int, dtype: str = "bfloat16") -> int:
+        return int(self.lib.slam_kv_cache_bytes_ex(self.h, max_batch, capacity, kv_dtype_code(dtype)))
 
-    def bind_kv_cache(self, cache, max_batch: int, capacity: int):
-        """cache: a 256-byte aligned device buffer of kv_cache_bytes(max_batch, capacity) bytes, kept alive here."""
+    def bind_kv_cache(self, cache, max_batch: int, capacity: int, dtype: str = "bfloat16"):
+        """cache: a 256-byte aligned device buffer of kv_cache_bytes(max_batch, capacity, dtype) bytes, kept alive here. dtype:
+        "bfloat16", or "fp8_e4m3" - e4m3 codes with one power-of-two exponent per key / value vector (include/slam_engine.h)."""
+        code = kv_dtype_code(dtype)
         self._keep["kv"] = cache
-        self._ck(self.lib.slam_bind_kv_cache(self.h, _ptr(cache), cache.numel() * cache.element_size(), max_batch, capacity))
+        self._ck(self.lib.slam_bind_kv_cache_ex(self.h, _ptr(cache), cache.numel() * cache.element_size(), max_batch, capacity, code))
 
     def prefill(self, ids, lens, B: int, T: int, logits_out, stream: Optional[int] = None):
         """ids int64 [B, T] (right-padded), lens int32 [B]: fills the cache, fp32 logits [B, vocab] of each last prompt token."""

@@ -298,12 +298,14 @@ class _Guidance:
         return self.next
 
 
-def _bind_cache(model, rows: int, cap: int):
-    """A KV cache of `rows` x `cap` positions bound to the model's engine, 256-byte aligned inside the raw buffer returned."""
-    nbytes = model.engine.kv_cache_bytes(rows, cap)
+def _bind_cache(model, rows: int, cap: int, dtype: Optional[str] = None):
+    """A KV cache of `rows` x `cap` positions bound to the model's engine, 256-byte aligned inside the raw buffer returned.
+    dtype: this call's `kv_cache_dtype`; None = the model's own `kv_cache_dtype`."""
+    dtype = model.kv_cache_dtype if dtype is None else dtype
+    nbytes = model.engine.kv_cache_bytes(rows, cap, dtype)
     raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=model.device)
     off = (-raw.data_ptr()) % 256
-    model.engine.bind_kv_cache(raw[off:off + nbytes], rows, cap)
+    model.engine.bind_kv_cache(raw[off:off + nbytes], rows, cap, dtype)
     return raw
 
 
@@ -345,6 +347,7 @@ class _Request(NamedTuple):
     on_device: bool = False          # the engine sampler picks the tokens
     guidance_scale: Optional[float] = None   # not None: guidance is on
     proposer: Optional[object] = None        # a _DraftProposer or a _LookupProposer: the speculative path
+    kv_dtype: str = "bfloat16"               # the target's cache: "bfloat16" or "fp8_e4m3" (a draft model keeps its own setting)
 
 
 def _resolve(model, gc, extra: dict, a: dict) -> _Request:
@@ -363,6 +366,8 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
         g = getattr(gc, name, None) if gc is not None else None
         return g if g is not None else default
 
+    kv_dtype = pick("kv_cache_dtype", model.kv_cache_dtype)
+    E.kv_dtype_code(kv_dtype)  # a ValueError that names the two
     num_beams = pick("num_beams", 1)
     rep = pick("repetition_penalty", 1.0)
     if num_beams != 1:
@@ -402,7 +407,7 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
     if nret > 1 and not do_sample:
         raise ValueError("num_return_sequences > 1 needs do_sample=True (greedy continuations would all be equal)")
     rq = _Request(inputs, max_new, nret, a["return_logprobs"], do_sample, temperature, top_k, top_p, late, warp, eos, int(pad),
-                  plan, a["seed"], a["sample_ids"], prefill_chunk)
+                  plan, a["seed"], a["sample_ids"], prefill_chunk, kv_dtype=kv_dtype)
     if max_new <= 0:
         return rq
     if extra:
@@ -681,7 +686,7 @@ def _speculate(model, rq: _Request, ids, lens, T: int):
     model._ensure_workspace(max(pre, B * K1, 2 * B))
     if draft is not None:
         draft._ensure_workspace(max(pre, 2 * B))
-    caches = [_bind_cache(m, B, cap) for m in (model, draft) if m is not None]
+    caches = [_bind_cache(model, B, cap, rq.kv_dtype)] + ([_bind_cache(draft, B, cap)] if draft is not None else [])
     sampler = _EngineSampler(rq, B, B * K1, V, dev)
     prompt_len, lens_t = lens.clone(), lens.clone()
     logits = torch.empty(B, V, dtype=torch.float32, device=dev)
@@ -792,7 +797,7 @@ def generate(model, gc, extra: dict, args: dict):
     # rows prefilled and rows in the cache: under guidance the conditional rows, then as many unconditional ones
     P, R = (B, BN) if cfg is None else (2 * B, 2 * BN)
     model._ensure_workspace(max(P * (T if rq.prefill_chunk is None else min(T, rq.prefill_chunk)), 2 * R))
-    raw = _bind_cache(model, R, cap)  # noqa: F841 - alive until the call returns
+    raw = _bind_cache(model, R, cap, rq.kv_dtype)  # noqa: F841 - alive until the call returns
     logits = torch.empty(R, V, dtype=torch.float32, device=dev)
     eos_t = torch.tensor(rq.eos, dtype=torch.long, device=dev) if rq.eos else None
     if nret > 1:  # the prefilled rows first; slam_kv_repeat fills the rest
@@ -822,8 +827,10 @@ def generate(model, gc, extra: dict, args: dict):
 
 
 def score_continuations(model, input_ids, attention_mask, continuations, continuation_lengths, num_per_prompt, score_chunk,
-                        prefill_chunk, return_argmax, ignore_tokens):
+                        prefill_chunk, return_argmax, ignore_tokens, kv_cache_dtype=None):
     """UnitLM.score_continuations (the module's documentation has the contract)."""
+    if kv_cache_dtype is not None:
+        E.kv_dtype_code(kv_cache_dtype)
     n = num_per_prompt
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
         raise ValueError(f"num_per_prompt must be an int >= 1 (got {n!r})")
@@ -858,7 +865,7 @@ def score_continuations(model, input_ids, attention_mask, continuations, continu
     C = Tc if score_chunk is None else min(score_chunk, Tc)
     cap = -(-(T + Tc) // 64) * 64
     model._ensure_workspace(max(B * (T if prefill_chunk is None else min(T, prefill_chunk)), BN * C, 2 * BN))
-    raw = _bind_cache(model, BN, cap)  # noqa: F841 - alive until the call returns
+    raw = _bind_cache(model, BN, cap, kv_cache_dtype)  # noqa: F841 - alive until the call returns
     V = model.config.vocab_size
     logits = torch.empty(BN, V, dtype=torch.float32, device=dev)
     if n > 1:

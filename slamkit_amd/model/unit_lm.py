@@ -1231,6 +1231,7 @@ class UnitLM(TokenLM):
     # ---- KV-cached generation: generation.py ------------------------------------------------------
     _assist_trace = None      # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after)
     _lookup_trace = None      # the same for prompt lookup, and n_prop behind them
+    kv_cache_dtype = "bfloat16"  # the KV cache of generate / score_continuations: "bfloat16" or "fp8_e4m3" (per call: kv_cache_dtype=)
     last_assist_stats = None  # {"rounds", "proposed", "accepted", "tokens"} of the last speculative generate
 
     @torch.no_grad()
@@ -1249,7 +1250,8 @@ class UnitLM(TokenLM):
                  min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
                  eta_cutoff: Optional[float] = None, guidance_scale: Optional[float] = None,
                  negative_prompt_ids: Optional[torch.Tensor] = None,
-                 negative_prompt_attention_mask: Optional[torch.Tensor] = None, **kwargs):
+                 negative_prompt_attention_mask: Optional[torch.Tensor] = None, kv_cache_dtype: Optional[str] = None,
+                 **kwargs):
         """HF `generate` on the engine's KV cache: [B, T_in + n_new] int64, the prompt as passed and then the new tokens, or
         GenerateOutput(sequences, logprobs) under return_logprobs. Explicit arguments override `generation_config`; any other
         keyword is a TypeError. generation.py has every argument's contract. Prompts: inputs / input_ids, attention_mask,
@@ -1257,18 +1259,20 @@ class UnitLM(TokenLM):
         top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, seed, sampler, sample_ids. Bans: bad_words_ids,
         suppress_tokens, begin_suppress_tokens, no_repeat_ngram_size. Outputs: num_return_sequences, return_logprobs. Prefill:
         prefill_chunk. Speculative: assistant_model, num_assistant_tokens, prompt_lookup_num_tokens, max_matching_ngram_size.
-        Guidance: guidance_scale, negative_prompt_ids, negative_prompt_attention_mask."""
+        Guidance: guidance_scale, negative_prompt_ids, negative_prompt_attention_mask. Cache: kv_cache_dtype ("bfloat16" or
+        "fp8_e4m3"; default: this model's `kv_cache_dtype`)."""
         return generation.generate(self, generation_config, kwargs, dict(locals()))  # stays the first statement: the arguments
 
     @torch.no_grad()
     def score_continuations(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, continuations=None,
                             continuation_lengths=None, num_per_prompt: int = 1, score_chunk: Optional[int] = None,
                             prefill_chunk: Optional[int] = None, return_argmax: bool = False,
-                            ignore_tokens: Optional[List[int]] = None):
+                            ignore_tokens: Optional[List[int]] = None, kv_cache_dtype: Optional[str] = None):
         """This model's log-probs (and greedy choices) of given continuations of the prompts, through the KV cache: the
         scoring half of generate(num_return_sequences=n, return_logprobs=True). The contract is in generation.py."""
         return generation.score_continuations(self, input_ids, attention_mask, continuations, continuation_lengths,
-                                              num_per_prompt, score_chunk, prefill_chunk, return_argmax, ignore_tokens)
+                                              num_per_prompt, score_chunk, prefill_chunk, return_argmax, ignore_tokens,
+                                              kv_cache_dtype)
 
     # ---- checkpoints (HF layout) ------------------------------------------------------------------
     def save_pretrained(self, save_directory: str, dtype=torch.bfloat16):
