@@ -465,6 +465,49 @@ int slam_sample_tokens_warped(const float* logits, int32_t B, int32_t vocab, con
                               const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
                               int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group,
                               int32_t out_col, const SlamWarpDesc* warp, slam_stream_t stream);
+/* slam_sample_tokens_full chooses over the WHOLE vocabulary: desc->top_k must be 0. Ancestral sampling from the model's own
+ * distribution, pure nucleus sampling (top_p alone) and min_p / epsilon_cutoff without a top-k, with the draw of (seed, row id,
+ * step) and the argument list of slam_sample_tokens_warped. There is no ranked candidate list; instead every weight becomes an
+ * integer mass and everything behind it is integer arithmetic, so the result does not depend on how the row is split over
+ * lanes, waves, blocks or launches: no floating-point atomics, the same bits every run, by construction.
+ * For row b, with row id r and step s as in slam_sample_tokens_at:
+ *   scores     as slam_sample_tokens: banned and NaN count as -inf, +inf as FLT_MAX, -0 as +0; a row without a score above -inf
+ *              emits pad_id and is not marked done. finished rows, next, out, done and eos_ids: slam_sample_tokens_at's, word
+ *              for word.
+ *   greedy     (do_sample == 0) the lowest i with x_i == max.
+ *   weights    x_max the row maximum; sc = (1.0f / temperature) * 1.44269504f in fp32; y_i = (x_i - x_max) * sc in fp32 (two
+ *              roundings); w_i = exp2(y_i) by the device's v_exp_f32; q_i = (uint64_t)(w_i * 2^40), truncated. q_max = 2^40
+ *              exactly. A token whose weight is below 2^-40 of the maximum's has mass 0 and is NEVER drawn (HF would draw it
+ *              with a probability below 2^-40). Q = the sum of all q_i (below 2^63: vocab <= 2^22).
+ *   cuts       every warper is a threshold on q: the kept set is { i : q_i >= c } with c <= q_max, so the maximum always stays
+ *              (min_tokens_to_keep = 1). HF's order (top-p, min-p, epsilon), each on what the ones before it kept:
+ *              top_p < 1: thr = (uint64_t)((double)(1.0f - top_p) * (double)Q), lowered to Q - 1 if it is not below Q;
+ *                S(v) = the sum of the q_k <= v; token i is kept iff S(q_i) > thr; c_p = the smallest kept value. This is HF's
+ *                "drop while the ascending cumulative sum <= 1 - top_p" with one deviation: ALL tokens that tie at the cut
+ *                value are kept (HF's sort cuts among them in an unspecified order).
+ *              min_p > 0: c_m = (uint64_t)((double)min_p * (double)q_max) (the ratio to the maximum survives renormalisation).
+ *              epsilon_cutoff > 0: Q1 = the sum of the q_i >= max(c_p, c_m); c_e = (double)epsilon_cutoff * (double)Q1 in
+ *                double, rounded up to an integer.
+ *              c = min(q_max, max(c_p, c_m, c_e)), a cut that is off counting as 0.
+ *   draw       Q2 = the sum of the kept q_i; Philox4x32-10 with slam_sample_tokens' counter and key;
+ *              t = mulhi64(((uint64_t)w[0] << 32) | w[1], Q2), an integer in [0, Q2); the token is the lowest id i with q_i >= c
+ *              whose prefix sum of kept masses, in id order, exceeds t.
+ * typical_p and eta_cutoff need a floating-point entropy and stay outside this rule: warp->typical_p must be 1 and
+ * warp->eta_cutoff 0 (warp == NULL: all off).
+ * Rows of up to SLAM_SAMPLE_FULL_SMALL_MAX scores take one launch (one block per row, masses in LDS); longer rows are cut into
+ * chunks of 2048 scores over a grid (chunks, B) and take 2 (greedy), 2 (sampling), + 4 (top_p < 1), + 1 (epsilon_cutoff > 0)
+ * launches, the masses recomputed from the logits in each. No block waits for another one.
+ * ws: slam_sample_full_workspace_bytes(B, vocab) bytes of device memory, 8-byte aligned (host-only arithmetic: positive for
+ * valid arguments, 0 else); every call clears what it uses, nothing depends on an earlier call.
+ * SLAM_EINVAL, before anything is launched or dereferenced on the device: slam_sample_tokens_warped's list with "top_k other
+ * than 0" in place of its top_k range (greedy included), typical_p other than 1, eta_cutoff other than 0, vocab above 2^22, or
+ * a temperature so small that sc is not finite. */
+#define SLAM_SAMPLE_FULL_SMALL_MAX 4096
+size_t slam_sample_full_workspace_bytes(int32_t B, int32_t vocab);
+int slam_sample_tokens_full(const float* logits, int32_t B, int32_t vocab, const uint8_t* banned, const SlamSampleDesc* desc,
+                            const int64_t* row_ids, const int32_t* eos_ids, uint8_t* done, int64_t* next, int64_t* out,
+                            int64_t out_stride, void* ws, size_t ws_bytes, const uint32_t* steps, int32_t group, int32_t out_col,
+                            const SlamWarpDesc* warp, slam_stream_t stream);
 
 /* ---- the acceptance rule of draft-model speculative decoding, on the device -------------------------------------------------
  * slam_spec_accept needs no engine. One round of assisted generation proposes K tokens per row with a draft model, lets the

@@ -150,6 +150,9 @@ def load_library(path: Optional[str] = None):
                                             i32, vp]),
         "slam_sample_tokens_warped": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp,
                                                 i32, i32, C.POINTER(SlamWarpDesc), vp]),
+        "slam_sample_full_workspace_bytes": (sz, [i32, i32]),
+        "slam_sample_tokens_full": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp,
+                                              i32, i32, C.POINTER(SlamWarpDesc), vp]),
         "slam_spec_accept": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "slam_ngram_propose": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, vp, vp]),
         "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
@@ -417,6 +420,31 @@ def sample_tokens_warped(logits, desc: SlamSampleDesc, next_ids, ws, warp: Optio
                                                  stream if stream is not None else current_stream_ptr())
     if rc != 0:
         raise EngineError(f"slam_sample_tokens_warped failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+
+
+SAMPLE_FULL_SMALL_MAX = 4096  # SLAM_SAMPLE_FULL_SMALL_MAX: rows up to this length take slam_sample_tokens_full's one-block form
+
+
+def sample_full_workspace_bytes(B: int, vocab: int) -> int:
+    """Bytes of device workspace slam_sample_tokens_full needs (host arithmetic; 0 for invalid arguments)."""
+    return int(load_library().slam_sample_full_workspace_bytes(int(B), int(vocab)))
+
+
+def sample_tokens_full(logits, desc: SlamSampleDesc, next_ids, ws, warp: Optional[SlamWarpDesc] = None, steps=None,
+                       group: int = 1, out_col: Optional[int] = None, banned=None, row_ids=None, eos_ids=None, done=None,
+                       out=None, stream: Optional[int] = None):
+    """slam_sample_tokens_full: sample_tokens_warped's arguments, chosen over the whole vocabulary (desc.top_k must be 0):
+    temperature, top_p, min_p and epsilon_cutoff as thresholds on integer masses, the draw of (seed, row id, step). `warp` may
+    set min_p and epsilon_cutoff only. ws: a uint8 tensor of sample_full_workspace_bytes(B, vocab). Only enqueues work."""
+    B, V = logits.shape
+    rc = load_library().slam_sample_tokens_full(_ptr(logits), B, V, _ptr(banned), C.byref(desc), _ptr(row_ids), _ptr(eos_ids),
+                                               _ptr(done), _ptr(next_ids), _ptr(out), out.stride(0) if out is not None else 0,
+                                               _ptr(ws), ws.numel() * ws.element_size(), _ptr(steps), int(group),
+                                               int(desc.step if out_col is None else out_col),
+                                               C.byref(warp) if warp is not None else None,
+                                               stream if stream is not None else current_stream_ptr())
+    if rc != 0:
+        raise EngineError(f"slam_sample_tokens_full failed ({rc})" + (": invalid argument" if rc == -1 else ""))
 
 
 SPEC_MAX_ROWS = 1024  # slam_spec_accept: one block, a thread per row

@@ -87,6 +87,19 @@ tokens with equal |-log p - entropy| are ordered by rank, (score descending, id 
 open. Assisted and prompt-lookup decoding verify with the same chain (the draft proposes with it too), so their tokens stay the
 target's own draws. Greedy decoding ignores the four, as HF does.
 
+`sampler="engine_full"` is the engine sampler over the WHOLE vocabulary (slam_sample_tokens_full): ancestral sampling from the
+model's own distribution, pure nucleus sampling (top_p alone), min_p / epsilon_cutoff without a top-k - the cases in which the
+torch sampler's tokens depend on the batch around a row. When sampling, top_k must be 0 (explicitly or in `generation_config`;
+ValueError otherwise, pointing to sampler="engine"). temperature, top_p, min_p, epsilon_cutoff, seed and `sample_ids` mean what
+they mean under "engine"; typical_p != 1 and eta_cutoff != 0 are a ValueError (they need a floating-point entropy). The rule
+(include/slam_engine.h): a token's weight is the integer q = floor(exp2((x - x_max) / temperature * log2 e) 2^40), every warper
+is a threshold on q (top-p keeps every token that ties at its cut value, where HF's sort cuts among them arbitrarily; a token
+below 2^-40 of the top weight is never drawn), and the draw walks the kept masses in id order with 64 Philox bits of (seed, row
+id, step) - integers throughout, so a row's tokens are the same alone, in any batch and on any rank. Everything that acts on the
+scores before the choice or on rows after it runs exactly as under "engine": greedy, num_return_sequences, return_logprobs,
+prefill_chunk, kv_cache_dtype, the FP8 decode weights, the history bans and guidance_scale, still with no torch op between two
+engine calls. assistant_model and prompt_lookup_num_tokens are refused under it (ValueError).
+
 `guidance_scale` = g (a finite float; also read from `generation_config`) other than 1 turns on classifier-free guidance, HF's
 UnbatchedClassifierFreeGuidanceLogitsProcessor: the scores become g (a - u) + u, a the log-softmax of the row's logits and u
 that of an unconditional twin that reads `negative_prompt_ids` [B, T_neg] (with `negative_prompt_attention_mask`, any padding
@@ -345,6 +358,7 @@ class _Request(NamedTuple):
     sample_ids: Optional[torch.Tensor]
     prefill_chunk: Optional[int]
     on_device: bool = False          # the engine sampler picks the tokens
+    full_vocab: bool = False         # ... with slam_sample_tokens_full (sampler="engine_full": top_k = 0)
     guidance_scale: Optional[float] = None   # not None: guidance is on
     proposer: Optional[object] = None        # a _DraftProposer or a _LookupProposer: the speculative path
     kv_dtype: str = "bfloat16"               # the target's cache: "bfloat16" or "fp8_e4m3" (a draft model keeps its own setting)
@@ -413,8 +427,9 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
     if extra:
         raise TypeError(f"generate got unsupported arguments {sorted(extra)}")
     sampler = a["sampler"]
-    if sampler not in (None, "torch", "engine"):
-        raise ValueError(f"sampler must be None, 'torch' or 'engine', not {sampler!r}")
+    if sampler not in (None, "torch", "engine", "engine_full"):
+        raise ValueError(f"sampler must be None, 'torch', 'engine' or 'engine_full', not {sampler!r}")
+    full_vocab = sampler == "engine_full"
     draft, neg, neg_mask = a["assistant_model"], a["negative_prompt_ids"], a["negative_prompt_attention_mask"]
     lookup_k, lookup_n = pick("prompt_lookup_num_tokens", None), pick("max_matching_ngram_size", None)
     guidance_scale = pick("guidance_scale", None)
@@ -431,6 +446,9 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
     if guided and (draft is not None or lookup_k is not None):
         raise ValueError("guidance_scale does not combine with assistant_model or prompt_lookup_num_tokens "
                          "(the verify pass would need guided chunk scores)")
+    if full_vocab and (draft is not None or lookup_k is not None):
+        raise ValueError("sampler='engine_full' does not combine with assistant_model or prompt_lookup_num_tokens yet "
+                         "(their verify pass draws with sampler='engine')")
     if lookup_k is not None:
         if draft is not None:
             raise ValueError("prompt_lookup_num_tokens and assistant_model exclude each other: one source of proposals")
@@ -441,10 +459,18 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
         proposer = _DraftProposer(model, draft, a["num_assistant_tokens"], rq, sampler)
     elif a["num_assistant_tokens"] is not None:
         raise ValueError("num_assistant_tokens needs an assistant_model")
-    on_device = sampler == "engine" or proposer is not None
+    on_device = sampler in ("engine", "engine_full") or proposer is not None
     if on_device:
-        if do_sample and not 1 <= top_k <= 256:
-            raise ValueError(f"sampler='engine' samples with 1 <= top_k <= 256 (got top_k={top_k})")
+        if full_vocab:
+            if do_sample and top_k != 0:
+                raise ValueError(f"sampler='engine_full' samples over the whole vocabulary: top_k must be 0 (got top_k={top_k}); "
+                                 f"sampler='engine' takes 1 <= top_k <= 256")
+            if do_sample and (late["typical_p"] != 1.0 or late["eta_cutoff"] != 0.0):
+                raise ValueError("sampler='engine_full' takes no typical_p or eta_cutoff: both need a floating-point entropy, "
+                                 "which its integer rule leaves out (use sampler='engine' with a top_k, or the torch sampler)")
+        elif do_sample and not 1 <= top_k <= 256:
+            raise ValueError(f"sampler='engine' samples with 1 <= top_k <= 256 (got top_k={top_k}); "
+                             f"sampler='engine_full' samples with top_k=0")
         if do_sample and not temperature > 0:
             raise ValueError(f"sampler='engine' needs temperature > 0 (got {temperature})")
         if do_sample and not 0 < top_p <= 1:
@@ -453,21 +479,24 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
             raise ValueError(f"sampler='engine' takes at most 16 EOS ids (got {len(eos)})")
     elif rq.sample_ids is not None:
         raise ValueError("sample_ids are the row ids of sampler='engine'; the torch sampler has none")
-    return rq._replace(on_device=on_device, guidance_scale=guidance_scale if guided else None, proposer=proposer)
+    return rq._replace(on_device=on_device, full_vocab=full_vocab, guidance_scale=guidance_scale if guided else None, proposer=proposer)
 
 
 class _EngineSampler:
     """The engine sampler of one generate call. `rows` is the shape of `sample_ids`, `draws` the most logits rows one launch
-    reads. Only pick() and pick_at() choose between the plain and the warped entry points; callers set desc.step and n_eos."""
+    reads. Only pick() and pick_at() choose between the plain, the warped and the whole-vocabulary entry points; callers set
+    desc.step and n_eos. pick_at serves the speculative paths, which sampler="engine_full" refuses."""
 
     def __init__(self, rq: _Request, rows: int, draws: int, vocab: int, dev):
         do_sample, seed = rq.do_sample, rq.seed
         if do_sample and seed is None:
             seed = int(torch.randint(0, 1 << 62, (1,)).item())
-        self.desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=rq.top_k if do_sample else 1,
+        self.full = rq.full_vocab
+        self.desc = E.SlamSampleDesc(do_sample=int(do_sample), top_k=0 if self.full else rq.top_k if do_sample else 1,
                                      temperature=rq.temperature if do_sample else 1.0, top_p=rq.top_p if do_sample else 1.0,
                                      seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF, step=0, pad_id=rq.pad, n_eos=len(rq.eos))
-        self.ws = torch.empty(E.sample_workspace_bytes(draws, vocab, self.desc.top_k), dtype=torch.uint8, device=dev)
+        nbytes = E.sample_full_workspace_bytes(draws, vocab) if self.full else E.sample_workspace_bytes(draws, vocab, self.desc.top_k)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.banned = None
         if rq.plan.single:  # the vocabulary-wide mask; the history-dependent bans are the _Constrainer's
             self.banned = torch.zeros(vocab, dtype=torch.uint8, device=dev)
@@ -481,7 +510,10 @@ class _EngineSampler:
         self.warp = rq.warp
 
     def pick(self, scores, nxt, done, out):
-        if self.warp is None:
+        if self.full:
+            E.sample_tokens_full(scores, self.desc, nxt, self.ws, self.warp, None, 1, None, self.banned, self.row_ids,
+                                 self.eos_i, done, out)
+        elif self.warp is None:
             E.sample_tokens(scores, self.desc, nxt, self.ws, self.banned, self.row_ids, self.eos_i, done, out)
         else:
             E.sample_tokens_warped(scores, self.desc, nxt, self.ws, self.warp, None, 1, None, self.banned, self.row_ids,
