@@ -26,8 +26,8 @@ import torch.distributed as dist
 
 from .callbacks import TrainerCallback, TrainerControl, TrainerState
 from .dp import GradBucketReducer, ShardedGradReducer, all_reduce_scalar, host_group, seeded_batches, shard_batches, world_info
-from .training_args import (SLAMTrainingArguments, check_label_smoothing, check_muon, check_neftune_alpha, check_optim,
-                            check_weight_decay_rule, lr_lambda)
+from .optimizers import check_checkpoint_optim, check_supported, make_optimizer, muon_adamw_runs  # noqa: F401 - imported from here too
+from .training_args import SLAMTrainingArguments, check_label_smoothing, check_neftune_alpha, check_weight_decay_rule, lr_lambda
 
 logger = logging.getLogger(__name__)
 
@@ -43,50 +43,30 @@ def dropout_seed(seed: int, rank: int) -> int:
     return (((int(rank) & 0xFFFFFFFF) << 32) | (int(seed) & 0xFFFFFFFF)) ^ DROPOUT_SEED_TAG
 
 
-def check_checkpoint_optim(st: dict, adafactor, path: str = "optimizer.pt"):
-    """An optimizer.pt holds the state of ONE optimizer kind: Adafactor's factors ("adafactor_state"), AdamW's moments
-    ("exp_avg", "exp_avg_sq"), or Muon's momentum buffer with the AdamW moments of the other elements ("optim": "muon").
-    Resuming one under another is an error, not a silent zero state. `adafactor`: True / False (Adafactor / AdamW), or "muon"."""
-    has_af = "adafactor_state" in st
-    is_muon = st.get("optim") == "muon" or "muon_momentum" in st
-    if adafactor == "muon":
-        if not is_muon or "exp_avg" not in st or "exp_avg_sq" not in st:
-            raise ValueError(f"{path} is {'an Adafactor' if has_af else 'an AdamW'} checkpoint (no Muon momentum buffer): it cannot "
-                             f"be resumed under optim='muon'")
-        return
-    if is_muon:
-        raise ValueError(f"{path} is a Muon checkpoint (a momentum buffer, AdamW moments for the other elements only): it cannot "
-                         f"be resumed under optim={'adafactor' if adafactor else 'adamw_torch'!r}; set optim='muon'")
-    if adafactor and not has_af:
-        raise ValueError(f"{path} is an AdamW checkpoint (it holds exp_avg / exp_avg_sq, no Adafactor state): it cannot be "
-                         f"resumed under optim='adafactor'")
-    if not adafactor and (has_af or "exp_avg" not in st or "exp_avg_sq" not in st):
-        raise ValueError(f"{path} is an Adafactor checkpoint (it holds no exp_avg / exp_avg_sq): it cannot be resumed under an "
-                         f"AdamW optim; set optim='adafactor'")
+def _optimizer_state(name: str) -> property:
+    """trainer.<name> is optimizer.state[name]: read, assigned (None frees the tensor) and deleted there, so the optimizer never
+    keeps a buffer its owner let go of. A name the optimizer's kind does not have is no attribute."""
+    def get(self):
+        try:
+            return self.optimizer.state[name]
+        except KeyError:
+            raise AttributeError(name) from None
 
+    def set_(self, value):
+        self.optimizer.state[name] = value
 
-def muon_adamw_runs(entries, n_params: int):
-    """The contiguous runs of [0, n_params) that no Muon matrix covers - what AdamW updates under optim = "muon" - as
-    [(offset, count, state offset)]: the moments of those elements are compact, run after run. `entries` = the rows of
-    Engine.muon_set_segments: (offset, rows, cols, pattern), pattern 1 / 2 = 32 rows of every 64, phase 0 / 32."""
-    iv = []
-    for off, rows, cols, pat in entries:
-        if not pat:
-            iv.append((off, off + rows * cols))
-        else:
-            iv.extend((off + (k * 64 + (32 if pat == 2 else 0)) * cols, off + (k * 64 + (32 if pat == 2 else 0) + 32) * cols)
-                      for k in range(rows // 32))
-    runs, pos, so = [], 0, 0
-    for lo, hi in sorted(iv) + [(n_params, n_params)]:
-        assert lo >= pos, "Muon segments overlap"
-        if lo > pos:
-            runs.append((pos, lo - pos, so))
-            so += lo - pos
-        pos = hi
-    return runs
+    def del_(self):
+        try:
+            del self.optimizer.state[name]
+        except KeyError:
+            raise AttributeError(name) from None
+    return property(get, set_, del_)
 
 
 class SLAMTrainer:
+    exp_avg, exp_avg_sq, adafactor_state, muon_momentum = map(_optimizer_state, ("exp_avg", "exp_avg_sq", "adafactor_state",
+                                                                                 "muon_momentum"))
+
     def __init__(self, model=None, args: SLAMTrainingArguments = None, data_collator: Callable = None,
                  train_dataset=None, eval_dataset=None, processing_class=None, callbacks: Optional[List[TrainerCallback]] = None):
         self.model = model
@@ -113,39 +93,10 @@ class SLAMTrainer:
         eps = check_label_smoothing(getattr(self.args, "label_smoothing_factor", 0.0))
         self._smooth_kw = {"label_smoothing": eps} if eps else {}
         dev = model.device
-        n = model.engine.n_params
         osd = getattr(self.args, "optim_state_dtype", "float32") or "float32"
         if osd not in ("float32", "bfloat16", "float32_bf16_moments"):
             raise ValueError(f"optim_state_dtype must be float32, bfloat16 or float32_bf16_moments, got {osd!r}")
-        # optim = "adafactor": HF's Adafactor on slam_adafactor_step instead of AdamW. The AdamW names change nothing below: not
-        # one engine call more (fields set after construction get past the arguments' own check)
-        kind = check_optim(getattr(self.args, "optim", "adamw_torch") or "adamw_torch")
-        self._adafactor = kind == "adafactor"
-        # optim = "muon": torch.optim.Muon on slam_muon_step for the decoder layers' matrices, AdamW (slam_adamw_range*) for the rest
-        self._muon = kind == "muon"
-        if self._muon:
-            check_muon(self.args)
-            if osd == "float32_bf16_moments":
-                raise ValueError("optim='muon' keeps an fp32 momentum buffer and AdamW moments for the non-Muon elements only: "
-                                 "optim_state_dtype is float32 or bfloat16, not float32_bf16_moments")
-            if (getattr(self.args, "ddp_algo", "all_reduce") or "all_reduce") == "rs_ag":
-                raise ValueError("optim='muon' orthogonalises whole matrices: a shard of the flat buffer cuts them, so "
-                                 "ddp_algo='rs_ag' is not available (use all_reduce)")
-            if getattr(self.args, "overlap_optimizer", False):
-                raise ValueError("optim='muon' has no overlapped form: overlap_optimizer belongs to the fp32-state AdamW")
-            if not hasattr(model, "hf_muon_segments"):
-                raise ValueError("optim='muon' needs a model that knows its decoder matrices (UnitLM.hf_muon_segments)")
-        if self._adafactor:
-            if osd == "float32_bf16_moments":
-                raise ValueError("optim='adafactor' keeps no Adam moments: optim_state_dtype is float32 (fp32 master weights) or "
-                                 "bfloat16 (the bf16 parameters are the only copy), not float32_bf16_moments")
-            if (getattr(self.args, "ddp_algo", "all_reduce") or "all_reduce") == "rs_ag":
-                raise ValueError("optim='adafactor' reduces over the rows and columns of whole tensors: a shard of the flat buffer "
-                                 "cuts them, so ddp_algo='rs_ag' is not available (use all_reduce)")
-            if getattr(self.args, "overlap_optimizer", False):
-                raise ValueError("optim='adafactor' has no overlapped form: overlap_optimizer belongs to the fp32-state AdamW")
-            if not hasattr(model, "hf_param_segments"):
-                raise ValueError("optim='adafactor' needs a model that knows its HF parameter tensors (UnitLM.hf_param_segments)")
+        check_supported(self.args, model, osd)  # what the optimizer `optim` names cannot be combined with
         sr = bool(getattr(self.args, "optim_stochastic_rounding", False))
         if sr and osd == "float32":  # (fields set after construction get past the arguments' own check)
             raise ValueError("optim_stochastic_rounding needs bf16 optimizer state (optim_state_dtype bfloat16 or "
@@ -168,34 +119,7 @@ class SLAMTrainer:
         self._final_mode = (2 if gd == "bfloat16" else 1) if hasattr(model, "enable_bf16_grads") else 0
         if self._final_mode:
             model.engine.set_option("grad_norm_partials", 1 if getattr(self.args, "grad_norm_from_backward", True) else 0)
-        if self._adafactor:
-            # no exp_avg / exp_avg_sq - that is the point: rows + cols fp32 factors per HF matrix, numel per vector, and the
-            # kernels' partial sums. The table is set once; the engine keeps it
-            self.exp_avg = self.exp_avg_sq = None
-            n_state, ws_bytes = model.engine.adafactor_set_segments([s.entry for s in model.hf_param_segments()])
-            self.adafactor_state = torch.zeros(n_state, dtype=torch.float32, device=dev)
-            self._adafactor_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            model.engine.adafactor_bind_workspace(self._adafactor_ws)
-        elif self._muon:
-            # 4 B of momentum per Muon element, and Adam moments for the OTHER elements only, compact: a full-size exp_avg /
-            # exp_avg_sq pair would throw away the memory Muon saves. The table and the complement are computed once
-            entries = [s.muon_entry for s in model.hf_muon_segments()]
-            n_mom, ws_bytes = model.engine.muon_set_segments(entries)
-            self.muon_momentum = torch.zeros(n_mom, dtype=torch.float32, device=dev)
-            self._muon_ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=dev)
-            pad = (-self._muon_ws.data_ptr()) % 256
-            model.engine.muon_bind_workspace(self._muon_ws[pad:pad + ws_bytes])
-            self._adamw_runs = muon_adamw_runs(entries, n)
-            n_adam = sum(c for _, c, _ in self._adamw_runs)
-            self.exp_avg = torch.zeros(n_adam, dtype=self.moment_dtype, device=dev)
-            self.exp_avg_sq = torch.zeros(n_adam, dtype=self.moment_dtype, device=dev)
-            self.optimizer_state_bytes = (4 * n_mom + 2 * n_adam * self.exp_avg.element_size(), ws_bytes)
-            logger.info("optim=muon: %d Muon elements (%.1f MB of momentum), %d AdamW elements (%.1f MB of moments), "
-                        "%.1f MB of workspace", n_mom, 4e-6 * n_mom, n_adam, 2e-6 * n_adam * self.exp_avg.element_size(),
-                        1e-6 * ws_bytes)
-        else:
-            self.exp_avg = torch.zeros(n, dtype=self.moment_dtype, device=dev)
-            self.exp_avg_sq = torch.zeros(n, dtype=self.moment_dtype, device=dev)
+        self.optimizer = make_optimizer(self.args, model, self.state_dtype, self.moment_dtype)
         self.norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
         cd = getattr(self.args, "ddp_comm_dtype", None)
         algo = getattr(self.args, "ddp_algo", "all_reduce") or "all_reduce"
@@ -460,28 +384,11 @@ class SLAMTrainer:
             self._clip_and_update(lr, zero_grad=zero_grad)
 
     def _clip_and_update(self, lr: float, zero_grad: bool):
-        """clip_grad_norm_ + AdamW on the flat buffers, in the configured state precision."""
-        a, eng = self.args, self.model.engine
-        eng.grad_norm(a.max_grad_norm if a.max_grad_norm else 0.0, self.norm_out)
+        """clip_grad_norm_ + the optimizer's step on the flat buffers, in the configured state precision."""
+        a = self.args
+        self.model.engine.grad_norm(a.max_grad_norm if a.max_grad_norm else 0.0, self.norm_out)
         self.opt_step += 1
-        if self._adafactor:  # HF's defaults: eps1 1e-30, clip_threshold 1, decay_rate -0.8; the scheduler's lr
-            eng.adafactor_step(None if self.state_dtype == torch.bfloat16 else self.model.flat_master, self.adafactor_state,
-                               self.norm_out, lr, self.opt_step, weight_decay=a.weight_decay, zero_grad=zero_grad)
-        elif self._muon:  # the Muon matrices, then AdamW on every run of the flat buffer between them
-            master = None if self.state_dtype == torch.bfloat16 else self.model.flat_master
-            eng.muon_step(master, self.muon_momentum, self.norm_out, lr, self.opt_step, weight_decay=a.weight_decay,
-                          momentum=a.muon_momentum, nesterov=a.muon_nesterov, ns_steps=a.muon_ns_steps,
-                          adjust_lr=a.muon_adjust_lr, zero_grad=zero_grad)
-            for off, cnt, so in self._adamw_runs:
-                eng.adamw_range(off, cnt, master, self.exp_avg, self.exp_avg_sq, self.norm_out, lr, a.adam_beta1, a.adam_beta2,
-                                a.adam_epsilon, a.weight_decay, self.opt_step, zero_grad=zero_grad, state_offset=so)
-            eng.refresh_transposed()  # both left the transposed weight images stale
-        elif self.state_dtype == torch.bfloat16:
-            eng.adamw_step_bf16(self.exp_avg, self.exp_avg_sq, self.norm_out, lr, a.adam_beta1, a.adam_beta2,
-                                a.adam_epsilon, a.weight_decay, self.opt_step, zero_grad=zero_grad)
-        else:
-            eng.adamw_step(self.model.flat_master, self.exp_avg, self.exp_avg_sq, self.norm_out, lr, a.adam_beta1,
-                           a.adam_beta2, a.adam_epsilon, a.weight_decay, self.opt_step, zero_grad=zero_grad)
+        self.optimizer.step(lr, self.opt_step, self.norm_out, zero_grad)
 
     def _clip_and_update_sharded(self, lr: float, zero_grad: bool):
         """ddp_algo = rs_ag: after the reduce-scatters every rank holds the summed gradient of its own shard of each bucket
@@ -500,10 +407,7 @@ class SLAMTrainer:
             dist.all_reduce(cs, op=dist.ReduceOp.SUM, group=red.group)
         eng.grad_norm_from_chunks(cs, a.max_grad_norm if a.max_grad_norm else 0.0, self.norm_out)
         self.opt_step += 1
-        master = None if self.state_dtype == torch.bfloat16 else self.model.flat_master
-        for off, cnt in list(red.owned) + ([(tail_off, tail_cnt)] if tail_cnt else []):
-            eng.adamw_range(off, cnt, master, self.exp_avg, self.exp_avg_sq, self.norm_out, lr, a.adam_beta1, a.adam_beta2,
-                            a.adam_epsilon, a.weight_decay, self.opt_step, zero_grad=False)
+        self.optimizer.step_ranges(list(red.owned) + ([(tail_off, tail_cnt)] if tail_cnt else []), lr, self.opt_step, self.norm_out)
         if zero_grad:  # accumulate-mode backward: the regions this rank does not own hold partial sums, clear everything
             eng.zero_grads()
         red.gather_params(eng)
@@ -517,7 +421,8 @@ class SLAMTrainer:
             return
         self.model.engine.join()
         w, r = self.world, self.rank
-        bufs = [self.exp_avg, self.exp_avg_sq] + ([self.model.flat_master] if self.state_dtype == torch.float32 else [])
+        bufs = [t for t in self.optimizer.state.values() if t is not None]
+        bufs += [self.model.flat_master] if self.state_dtype == torch.float32 else []
         for lo, hi in red.last_buckets:
             s = (hi - lo) // w
             for b in bufs:
@@ -690,14 +595,8 @@ class SLAMTrainer:
             path = self._ckpt_dir(self.state.global_step)
             self.model.save_pretrained(path)
             self.model.engine.join()
-            if self._adafactor:
-                opt = {"optim": "adafactor", "adafactor_state": self.adafactor_state.cpu()}
-            elif self._muon:  # the moments are compact: the runs of muon_adamw_runs, one after another
-                opt = {"optim": "muon", "muon_momentum": self.muon_momentum.cpu(), "exp_avg": self.exp_avg.cpu(),
-                       "exp_avg_sq": self.exp_avg_sq.cpu()}
-            else:
-                opt = {"exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu()}
-            torch.save({"master": self.model._weights.cpu(), **opt, "opt_step": self.opt_step}, os.path.join(path, "optimizer.pt"))
+            torch.save({"master": self.model._weights.cpu(), **self.optimizer.state_dict(), "opt_step": self.opt_step},
+                       os.path.join(path, "optimizer.pt"))
             with open(os.path.join(path, "trainer_state.json"), "w") as f:
                 json.dump({"global_step": self.state.global_step, "epoch": self.state.epoch,
                            "num_input_tokens_seen": self.state.num_input_tokens_seen,
@@ -715,19 +614,12 @@ class SLAMTrainer:
 
     def _load_checkpoint(self, path: str):
         st = torch.load(os.path.join(path, "optimizer.pt"), map_location="cpu")
-        check_checkpoint_optim(st, "muon" if self._muon else self._adafactor, path)  # before anything is overwritten
-        if self._muon and (st["muon_momentum"].numel() != self.muon_momentum.numel() or st["exp_avg"].numel() != self.exp_avg.numel()):
-            raise ValueError(f"{path} is a Muon checkpoint of another model or segment table")
+        check_checkpoint_optim(st, self.optimizer.kind, path)  # before anything is overwritten
+        self.optimizer.check_state_sizes(st, path)
         self.model.engine.join()
         self.model._weights.copy_(st["master"])
         self.model.sync_params_from_master()
-        if self._adafactor:
-            self.adafactor_state.copy_(st["adafactor_state"])
-        else:
-            if self._muon:
-                self.muon_momentum.copy_(st["muon_momentum"])
-            self.exp_avg.copy_(st["exp_avg"])
-            self.exp_avg_sq.copy_(st["exp_avg_sq"])
+        self.optimizer.load_state_dict(st)
         self.opt_step = int(st["opt_step"])
         with open(os.path.join(path, "trainer_state.json")) as f:
             s = json.load(f)

@@ -285,12 +285,12 @@ def test_checkpoint_kind_mismatch_is_an_error(tmp_path):
     from slamkit_amd.trainer.slam_trainer import check_checkpoint_optim
     adam = {"master": 0, "exp_avg": 0, "exp_avg_sq": 0, "opt_step": 3}
     fact = {"master": 0, "optim": "adafactor", "adafactor_state": 0, "opt_step": 3}
-    check_checkpoint_optim(adam, False)
-    check_checkpoint_optim(fact, True)
+    check_checkpoint_optim(adam, "adamw")
+    check_checkpoint_optim(fact, "adafactor")
     with pytest.raises(ValueError, match="AdamW checkpoint"):
-        check_checkpoint_optim(adam, True)
+        check_checkpoint_optim(adam, "adafactor")
     with pytest.raises(ValueError, match="Adafactor checkpoint"):
-        check_checkpoint_optim(fact, False)
+        check_checkpoint_optim(fact, "adamw")
     # through the trainer: an AdamW run's optimizer.pt under optim = "adafactor", before anything is overwritten
     tr, model = _stub_trainer(optim="adamw_torch", output_dir=str(tmp_path))
     tr.save_checkpoint()

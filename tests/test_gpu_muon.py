@@ -391,7 +391,7 @@ def test_model_under_muon_against_adamw_and_the_restatement(fam):
     # the non-Muon elements: AdamW's bits
     assert torch.equal(ibits(mm._weights)[~covd], ibits(ma._weights)[~covd])
     assert torch.equal(ibits(mm.flat_params)[~covd], ibits(ma.flat_params)[~covd])
-    for off, cnt, so in tm._adamw_runs:
+    for off, cnt, so in tm.optimizer.adamw_runs:
         assert torch.equal(ibits(tm.exp_avg[so:so + cnt]), ibits(ta.exp_avg[off:off + cnt]))
         assert torch.equal(ibits(tm.exp_avg_sq[so:so + cnt]), ibits(ta.exp_avg_sq[off:off + cnt]))
     assert tm.exp_avg.numel() == n - int(cov.sum()) and float(tm.exp_avg.abs().max()) > 0
@@ -442,7 +442,7 @@ def test_trainer_loss_goes_down_under_muon(osd):
     tr = SLAMTrainer(model=m, args=a, data_collator=coll, train_dataset=ds)
     n_mu = sum(s.rows * s.cols for s in m.hf_muon_segments())
     assert tr.muon_momentum.numel() == n_mu and tr.exp_avg.numel() == m.engine.n_params - n_mu
-    assert tr.optimizer_state_bytes[0] == 4 * n_mu + 2 * tr.exp_avg.numel() * tr.exp_avg.element_size()
+    assert tr.optimizer.state_bytes[0] == 4 * n_mu + 2 * tr.exp_avg.numel() * tr.exp_avg.element_size()
     state = tr.train()
     losses = [r["loss"] for r in state.log_history if "loss" in r]
     print("muon", osd, [round(x, 3) for x in losses])

@@ -198,7 +198,7 @@ def test_trainer_call_order_under_muon_and_no_new_call_elsewhere():
     assert model.engine.calls == ["muon_set_segments", "muon_bind_workspace"]       # the table once, then the workspace
     assert tr.muon_momentum.numel() == 32 and tr.muon_momentum.dtype == torch.float32
     assert tr.exp_avg.numel() == tr.exp_avg_sq.numel() == n - 128                    # moments for AdamW's elements only
-    assert tr.optimizer_state_bytes == (4 * 32 + 2 * 4 * (n - 128), 512)
+    assert tr.optimizer.state_bytes == (4 * 32 + 2 * 4 * (n - 128), 512)
     del model.engine.calls[:]
     tr._clip_and_update(1e-3, zero_grad=True)
     assert tr.opt_step == 1
@@ -232,9 +232,9 @@ def test_checkpoint_kinds(tmp_path):
     adam = {"master": 0, "exp_avg": 0, "exp_avg_sq": 0, "opt_step": 3}
     fact = {"master": 0, "optim": "adafactor", "adafactor_state": 0, "opt_step": 3}
     muon = {"master": 0, "optim": "muon", "muon_momentum": 0, "exp_avg": 0, "exp_avg_sq": 0, "opt_step": 3}
-    check_checkpoint_optim(adam, False), check_checkpoint_optim(fact, True), check_checkpoint_optim(muon, "muon")   # the existing calls
-    for st, kind, word in ((muon, False, "Muon checkpoint"), (muon, True, "Muon checkpoint"), (adam, "muon", "AdamW checkpoint"),
-                           (fact, "muon", "Adafactor checkpoint"), (adam, True, "AdamW checkpoint"), (fact, False, "Adafactor checkpoint")):
+    check_checkpoint_optim(adam, "adamw"), check_checkpoint_optim(fact, "adafactor"), check_checkpoint_optim(muon, "muon")   # the existing calls
+    for st, kind, word in ((muon, "adamw", "Muon checkpoint"), (muon, "adafactor", "Muon checkpoint"), (adam, "muon", "AdamW checkpoint"),
+                           (fact, "muon", "Adafactor checkpoint"), (adam, "adafactor", "AdamW checkpoint"), (fact, "adamw", "Adafactor checkpoint")):
         with pytest.raises(ValueError, match=word):
             check_checkpoint_optim(st, kind)
     # through the trainer: optimizer.pt carries the kind, the momentum buffer and the compact moments; the other kinds refuse it

@@ -180,8 +180,8 @@ def main(argv=None):
                "optimizer_phase_ms_median": round(pm, 3), "optimizer_phase_ms_min": round(pl, 3), "optimizer_phase_ms_max": round(ph, 3),
                "peak_allocated_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 3)}
         if optim == "muon":
-            run["state_bytes"], run["workspace_bytes"] = tr.optimizer_state_bytes
-            run["adamw_ranges"] = len(tr._adamw_runs)
+            run["state_bytes"], run["workspace_bytes"] = tr.optimizer.state_bytes
+            run["adamw_ranges"] = len(tr.optimizer.adamw_runs)
             classes = [(c.rows, c.cols, c.count) for c in model.engine.muon_classes()]
             run["launches_per_step"] = 2 + len(classes) * (1 + 3 * tr.args.muon_ns_steps)
         res["runs"].append(run)
