@@ -332,6 +332,47 @@ int slam_kv_rewind(SlamEngine* h, int32_t hi);
 size_t slam_kv_cache_bytes_ex(SlamEngine* h, int32_t max_batch, int32_t capacity, int32_t dtype);
 int slam_bind_kv_cache_ex(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity, int32_t dtype);
 
+/* ---- a shared-prompt cache: the n samples of a prompt attend one copy of its keys ----------------------------------------------
+ * slam_kv_repeat copies a prompt's keys into n cache rows, and every decode step then reads them n times. This mode keeps them
+ * once, in a prompt store, and the ordinary cache holds only what each row appended behind its prompt. bf16 only, Qwen2 and
+ * Qwen3 families; without these calls every launch is what it was.
+ * slam_kv_prefix_bytes / slam_bind_kv_prefix: the prompt store is caller-owned, 256-byte aligned: bf16
+ *   [n_layers][2][max_prompts][n_kv_heads][prefix_capacity][head_dim] (index 0 of the second axis is K, stored after RoPE),
+ *   followed by an engine-owned int32 [max_prompts] array of prompt lengths: n_layers x 2 x max_prompts x n_kv_heads x
+ *   prefix_capacity x head_dim x 2 + 4 max_prompts bytes. slam_kv_prefix_bytes is 0 for a NULL engine, non-positive sizes or an
+ *   OPT engine. slam_bind_kv_prefix(buf = NULL) unbinds the store; binding or unbinding resets its prefill state and leaves the
+ *   shared mode. SLAM_EINVAL for h NULL, non-positive sizes, a misaligned buffer or an OPT engine; SLAM_ENOMEM for too few bytes.
+ * slam_prefill_prefix: slam_prefill, launch for launch, except that each layer's K / V rows go to the prompt store (the same
+ *   scatter launch with the store's base and capacity) and that lens is copied to the store's length array behind the head. The
+ *   logits are bit-identical to slam_prefill's. The ordinary cache is neither needed nor touched, but its prefill state is
+ *   reset. Errors, all before any launch: slam_prefill's, with SLAM_ESTATE for no bound store and SLAM_EINVAL for B above
+ *   max_prompts or T above prefix_capacity.
+ * slam_kv_share: slam_kv_repeat's contract without the copy. Precondition: a slam_prefill_prefix of B prompts and a bound bf16
+ *   cache (slam_bind_kv_cache) of max_batch >= B n rows. lens: int32 [B n] device, the first B entries filled; afterwards
+ *   lens[b n + i] = old lens[b]. logits: nullable, fp32 [B n][vocab], first B rows filled, replicated the same way (one launch
+ *   per source row in descending b, slam_kv_repeat's hazard argument). No key is copied: row r belongs to prompt r / n, and
+ *   lens[r] stays the row's ABSOLUTE key count - prompt + appended - so RoPE positions, the samplers, slam_constrain_scores and
+ *   slam_token_logprobs see what they see after slam_kv_repeat. Afterwards the decode batch is B n and the engine is in the
+ *   shared mode: key k >= plen of row r sits at index k - plen[r / n] of the ordinary cache, whose `capacity` therefore bounds
+ *   the appended tokens alone, not prompt + new. n == 1 is legal (and not a no-op: it enters the mode).
+ *   Errors, all before any launch: SLAM_EINVAL for h or lens NULL, n < 1, an FP8 cache, or B n > max_batch; SLAM_ESTATE without a
+ *   bound cache, without a bound store, without a slam_prefill_prefix since the store was bound, or when called twice.
+ * slam_decode_step in the shared mode: the signature and everything but the attention are unchanged. Per layer the attention
+ *   is three launches over one partials buffer: the prompt's keys for all n G queries of a (prompt, KV head) on
+ *   v_mfma_f32_16x16x32_bf16 (queries rotated and rounded once from the fp32 row, the bits the per-key kernel uses; P rounded to
+ *   bf16 as under slam_extend; only keys k < the prompt's length are read), the keys behind the prompt with the per-key kernel,
+ *   which also appends the new token at index lens[r] - plen bit for bit as an unshared step would, and the existing combine
+ *   over prefix splits, then suffix splits, in split order: no atomics, bit-identical run to run. Logits differ from the
+ *   unshared path's by rounding only. SLAM_ESTATE when the appended tokens would pass `capacity`; SLAM_ENOMEM when the logits
+ *   buffer cannot hold one split of each part.
+ * Leaving the mode: slam_prefill, slam_bind_kv_cache*, slam_bind_kv_prefix and slam_prefill_prefix. In the mode slam_extend,
+ *   slam_extend_score, slam_extend_logits, slam_kv_repeat and slam_kv_rewind return SLAM_ESTATE with a message. */
+size_t slam_kv_prefix_bytes(SlamEngine* h, int32_t max_prompts, int32_t prefix_capacity);
+int slam_bind_kv_prefix(SlamEngine* h, void* buf, size_t bytes, int32_t max_prompts, int32_t prefix_capacity);
+int slam_prefill_prefix(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
+                        slam_stream_t stream);
+int slam_kv_share(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_stream_t stream);
+
 /* ---- decoding from FP8 weights: an exact, power-of-two-scaled e4m3 copy of the decode projections ----
  * A decode step (and an extend pass of up to 64 rows) is one stream of the weights. This copy halves the bytes of that stream
  * for wqkv, wo, wgu and wd of every layer (and the head matrix when include_head) without a second model: quantising REPLACES
@@ -1205,6 +1246,22 @@ size_t slam_op_attn_decode_workspace(int B, int nH, int nKV, int head_dim, int k
 int slam_op_attn_decode(const float* qkv, const void* bias, const int32_t* lens, void* k_cache, void* v_cache, void* o, void* ws,
                         size_t ws_bytes, int B, int nH, int nKV, int head_dim, int capacity, int kv_bound, float theta,
                         slam_stream_t s);
+/* the attention launches of one decode step in the shared-prompt mode (slam_kv_share), alone. R = P n rows; row r belongs to
+ * prompt r / n. qkv fp32 [R][(nH + 2 nKV) head_dim], bias, theta as for slam_op_attn_decode; lens int32 [R] device = the rows'
+ * ABSOLUTE key counts (the new token's position); plens int32 [P] device = the prompts' lengths, 1 <= plens[r / n] <= lens[r].
+ * k_prefix / v_prefix: bf16 [P][nKV][prefix_capacity][head_dim], read at keys k < plens[p] only and never written. k_cache /
+ * v_cache: bf16 [R][nKV][capacity][head_dim], the keys behind the prompt: read at indices below lens[r] - plens[r / n], and the
+ * new K / V written at exactly that index - the bits slam_op_attn_decode appends for the same row and position. o: bf16
+ * [R][nH head_dim]. prefix_bound >= max(plens), <= prefix_capacity; kv_bound >= max(lens[r] - plens[r / n]) + 1, <= capacity
+ * (host bounds; the kernels clamp to them). ws: slam_op_attn_decode_shared_workspace(..) bytes, 16-byte aligned: positions and
+ * RoPE tables of R rows as under slam_op_attn_decode, then the partials [R nH][ns_prefix + ns_suffix][head_dim + 2]. Less is
+ * legal down to one split of each part; below that SLAM_ENOMEM, before any launch (nothing is written). SLAM_EINVAL: a NULL
+ * argument, sizes or bounds out of range, head_dim other than 64 / 128, nH / nKV > 8, P n > 65535, misaligned buffers. */
+size_t slam_op_attn_decode_shared_workspace(int P, int n, int nH, int nKV, int head_dim, int prefix_bound, int kv_bound);
+int slam_op_attn_decode_shared(const float* qkv, const void* bias, const int32_t* lens, const int32_t* plens, int n,
+                               const void* k_prefix, const void* v_prefix, int prefix_capacity, void* k_cache, void* v_cache,
+                               int capacity, void* o, void* ws, size_t ws_bytes, int P, int nH, int nKV, int head_dim,
+                               int prefix_bound, int kv_bound, float theta, slam_stream_t s);
 /* chunk attention over the cache (the attention of slam_extend): qkv bf16 [B T][(nH + 2 nKV) head_dim] exactly as the forward's
  * q|k|v buffer holds it - bias and RoPE applied, queries pre-scaled by head_dim^-0.5 * log2(e) (NOT the fp32 pre-bias row of
  * slam_op_attn_decode). Row b T + t is token t of row b's chunk, real when t < new_lens[b] (0 <= new_lens[b] <= T);

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIB_DIR, "libslam_engine.so")
-SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "muon.hip", "decode.hip", "decode_kv8.hip", "sampling.hip", "sampling_full.hip", "quant.hip",
+SOURCES = ["gemm.hip", "attention.hip", "elementwise.hip", "optimizer.hip", "adafactor.hip", "muon.hip", "decode.hip", "decode_kv8.hip", "decode_shared.hip", "sampling.hip", "sampling_full.hip", "quant.hip",
            "engine.hip", "engine_cache.hip", "engine_optim.hip", "engine_comm.hip", "ops.hip"]
 HEADERS = ["common.h", "kernels.h", "decode_attn.h", os.path.join("..", "..", "include", "slam_engine.h")]
 ENGINE_HEADER = "engine_impl.h"  # private to the engine*.hip files, and a dependency of those alone
@@ -27,7 +27,7 @@ EXPORT_MAP = os.path.join(HERE, "exports.map")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 # Translation units that are built without the packed fp32 VALU forms (v_pk_fma_f32 and its kin): new kernels start here
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"decode_kv8.hip": NO_PACKED_FP32, "sampling_full.hip": NO_PACKED_FP32}
+EXTRA_FLAGS = {"decode_kv8.hip": NO_PACKED_FP32, "sampling_full.hip": NO_PACKED_FP32, "decode_shared.hip": NO_PACKED_FP32}
 
 
 def _hipcc():

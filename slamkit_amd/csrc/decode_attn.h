@@ -65,21 +65,33 @@ SLAM_DEVICE void round8(float* v) {
 // a bf16 cache of the dequantised keys would have handed the same lane, and everything behind it is the same text. The new
 // token is rounded to bf16 as ever, quantised in registers (its LG lanes are all here: they share j), stored as codes +
 // exponent and scored as dequantised: round once, then use what the cache holds.
-template <int HD, int G, bool F8>
+// SH (shared-prompt decode, decode_shared.hip; bf16 only): row b belongs to prompt b / sh.n, whose sh.plens[b / sh.n] keys live
+// in the prompt store and are served by attn_prefix_kernel. This cache then holds only the keys behind the prompt: key k of the
+// row sits at index k - plen, the new token at lens[b] - plen, and the partials go behind the prefix splits of the row
+// (split sh.ns_off + s of sh.ns_tot). Tables, queries, lanes and merges are the same text; SH = false holds no trace of it.
+struct DecodeNoShare {};
+struct DecodeShare {
+  const int* plens;  // [prompts]
+  int n, ns_off, ns_tot;
+};
+template <int HD, int G, bool F8, bool SH = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restrict__ qkv, const bf16_t* __restrict__ bias,
                                                           const float* __restrict__ cs, const float* __restrict__ sn,
                                                           const float* __restrict__ csq, const float* __restrict__ snq,
                                                           const int* __restrict__ lens, kv_elem_t<F8>* __restrict__ kc,
                                                           kv_elem_t<F8>* __restrict__ vc, int8_t* __restrict__ ke,
                                                           int8_t* __restrict__ ve, int cap, int nH, int nKV, int chunk, int ns,
-                                                          float* __restrict__ part) {
+                                                          float* __restrict__ part,
+                                                          std::conditional_t<SH, DecodeShare, DecodeNoShare> sh = {}) {
+  static_assert(!(SH && F8), "the shared-prompt mode is bf16 only");
   constexpr int LG = HD / 8, SLOTS = 64 / LG, half = HD / 2;
   __shared__ float red[4][G][HD + 2];
   const int s = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane % LG, slot = lane / LG, d0 = sub * 8;
   const int QKV = (nH + 2 * nKV) * HD;
-  const int pos = lens[b];
+  int pos = lens[b];
+  if constexpr (SH) pos = max(pos - max(sh.plens[b / sh.n], 0), 0);  // index of the new token among the keys behind the prompt
   const int nkeys = min(pos + 1, cap);
   const float* row = qkv + (size_t)b * QKV;
   const float* C = cs + (size_t)b * half;
@@ -186,6 +198,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const float* __restric
       for (int e = 0; e < 8; ++e) o[e] += red[w][i][e0 + e] * a;
     }
     float* dst = part + (((size_t)b * nH + g * G + i) * ns + s) * (HD + 2);
+    if constexpr (SH) dst = part + (((size_t)b * nH + g * G + i) * sh.ns_tot + sh.ns_off + s) * (HD + 2);
 #pragma unroll
     for (int e = 0; e < 8; ++e) dst[e0 + e] = o[e];
     if (e0 == 0) { dst[HD] = mm; dst[HD + 1] = l; }

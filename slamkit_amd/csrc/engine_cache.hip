@@ -1,6 +1,6 @@
 // KV-cached generation on a SlamEngine (include/slam_engine.h): the cache binding, the FP8 copy of the decode projections,
-// slam_prefill, slam_decode_step, slam_kv_repeat, the three slam_extend* entry points and slam_kv_rewind. The kernels are in
-// decode.hip and quant.hip; the prefill runs the training forward's own layer loop (forward_layers, engine.hip).
+// slam_prefill, slam_decode_step, slam_kv_repeat, the three slam_extend* entry points, slam_kv_rewind and the shared-prompt mode
+// (slam_bind_kv_prefix, slam_prefill_prefix, slam_kv_share). The kernels are in decode.hip, decode_shared.hip and quant.hip; the prefill runs the training forward's own layer loop (forward_layers, engine.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -75,6 +75,10 @@ static int last_token_head(SlamEngine* h, const bf16_t* x, int B, float* logits,
 int cache_attn_decode(SlamEngine* h, int l, const float* qkvf, const bf16_t* bias, const int* lens, int B, bf16_t* o, size_t part_bytes,
                       hipStream_t st) {
   const SlamModelDesc& d = h->d;
+  if (h->kv_shared)  // lens are absolute; every row has taken kv_hi - kvp_T steps, so its keys behind the prompt number that + 1
+    return attn_decode_shared(qkvf, bias, h->cosb, h->sinb, h->cosq, h->sinq, lens, h->kvp_lens, h->kv_n, kvp_kv(h, l, 0),
+                              kvp_kv(h, l, 1), h->kvp_cap, h->kvp_T, kv_k(h, l), kv_v(h, l), h->kv_cap, h->kv_hi - h->kvp_T + 1,
+                              B / h->kv_n, d.n_heads, d.n_kv_heads, d.head_dim, o, (float*)h->logits, part_bytes, st);
   if (h->kv_dtype == SLAM_KV_FP8_E4M3)
     return attn_decode_fp8(qkvf, bias, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv8_codes(h, l, 0), kv8_codes(h, l, 1),
                            kv8_exps(h, l, 0), kv8_exps(h, l, 1), h->kv_cap, B, d.n_heads, d.n_kv_heads, d.head_dim, h->kv_hi + 1, o,
@@ -103,6 +107,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+  if (h->kv_shared) return h->fail(SLAM_ESTATE, "slam_extend* in the shared-prompt mode: prefill again to leave it");
   if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
   if ((int64_t)2 * B > h->max_tokens) return h->fail(SLAM_ENOMEM, "extend needs a workspace of at least 2 B tokens");
   if ((int64_t)(h->kv_ready ? h->kv_hi : 0) + T > h->kv_cap) return h->fail(SLAM_ESTATE, "extend past the KV cache capacity");
@@ -185,6 +190,8 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
 namespace slam_impl {
 int cache_scatter(SlamEngine* h, int l, const int32_t* lens, int B, int T, hipStream_t st) {
   const SlamModelDesc& d = h->d;
+  if (h->kvp_scatter)  // slam_prefill_prefix: the same launch with the prompt store's base and capacity
+    return kv_scatter(h->la[l].qkv, kvp_kv(h, l, 0), kvp_kv(h, l, 1), lens, B, T, d.n_heads, d.n_kv_heads, d.head_dim, h->kvp_cap, st);
   if (h->kv_dtype == SLAM_KV_FP8_E4M3)
     return kv_scatter_fp8(h->la[l].qkv, kv8_codes(h, l, 0), kv8_codes(h, l, 1), kv8_exps(h, l, 0), kv8_exps(h, l, 1), lens, B, T,
                           d.n_heads, d.n_kv_heads, d.head_dim, h->kv_cap, st);
@@ -213,6 +220,7 @@ int slam_bind_kv_cache_ex(SlamEngine* h, void* cache, size_t bytes, int32_t max_
   h->kv_bmax = max_batch;
   h->kv_cap = capacity;
   h->kv_ready = false;
+  h->kv_shared = false;
   return SLAM_OK;
 }
 size_t slam_kv_cache_bytes(SlamEngine* h, int32_t max_batch, int32_t capacity) {
@@ -271,13 +279,19 @@ int slam_quantize_decode_w8(SlamEngine* h, slam_stream_t stream) {
 int slam_decode_w8_state(SlamEngine* h) { return !h || !h->w8 ? 0 : h->w8_valid ? 2 : 1; }
 int64_t slam_decode_w8_launches(SlamEngine* h) { return h ? h->w8_launches : 0; }
 
-int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
-                 slam_stream_t stream) {
+// slam_prefill, and (prefix) slam_prefill_prefix: the same launches, the scatter aimed at the prompt store
+static int prefill_common(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
+                          slam_stream_t stream, bool prefix) {
   if (!h || !ids || !lens || !logits_out || B <= 0 || T <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
-  if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
-  if (B > h->kv_bmax || T > h->kv_cap) return h->fail(SLAM_EINVAL, "prefill batch exceeds the bound KV cache");
+  if (prefix) {
+    if (!h->kvp) return h->fail(SLAM_ESTATE, "bind a prompt store first (slam_bind_kv_prefix)");
+    if (B > h->kvp_pmax || T > h->kvp_cap) return h->fail(SLAM_EINVAL, "prefill batch exceeds the bound prompt store");
+  } else {
+    if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+    if (B > h->kv_bmax || T > h->kv_cap) return h->fail(SLAM_EINVAL, "prefill batch exceeds the bound KV cache");
+  }
   if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
   const SlamModelDesc& d = h->d;
   hipStream_t st = (hipStream_t)stream;
@@ -286,6 +300,13 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   h->fwd_drop = false;  // generation never drops ...
   h->fwd_neft = false;  // ... and never draws NEFTune noise
   h->kv_ready = false;
+  h->kv_shared = false;
+  if (prefix) h->kvp_ready = false;
+  struct ScatterScope {  // cache_scatter's target for the launches below, whichever way they return
+    SlamEngine* h;
+    ~ScatterScope() { h->kvp_scatter = false; }
+  } scatter_scope{h};
+  h->kvp_scatter = prefix;
   GemmTuneScope tune_scope(&h->gemm_tune);
   // "recompute" = 2 with more layers than slots: the layers share their q|k|v buffers, so each layer's K / V leave inside the loop
   const bool shared_qkv = h->recompute == 2 && L > RC_SLOTS;
@@ -295,9 +316,70 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
   // logits of each row's last prompt token only: gather, final norm, one fp32 head launch over B rows
   CK(gather_last_rows(h->hs[L], h->dx, lens, B, T, H, st));
   CK(last_token_head(h, h->dx, B, logits_out, st));
+  if (prefix) {
+    CK(lens_copy(lens, h->kvp_lens, B, st));
+    h->kvp_B = B;
+    h->kvp_T = T;
+    h->kvp_ready = true;
+    return SLAM_OK;
+  }
   h->kv_B = B;
   h->kv_hi = T;
   h->kv_T = T;
+  h->kv_ready = true;
+  return SLAM_OK;
+}
+
+int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
+                 slam_stream_t stream) {
+  return prefill_common(h, ids, lens, B, T, logits_out, stream, false);
+}
+
+size_t slam_kv_prefix_bytes(SlamEngine* h, int32_t max_prompts, int32_t prefix_capacity) {
+  if (!h || max_prompts <= 0 || prefix_capacity <= 0 || h->arch == 1) return 0;
+  const SlamModelDesc& d = h->d;
+  return (size_t)d.n_layers * 2 * max_prompts * d.n_kv_heads * prefix_capacity * d.head_dim * sizeof(bf16_t) +
+         (size_t)max_prompts * sizeof(int32_t);
+}
+
+int slam_bind_kv_prefix(SlamEngine* h, void* buf, size_t bytes, int32_t max_prompts, int32_t prefix_capacity) {
+  if (!h) return SLAM_EINVAL;
+  h->kvp = nullptr;
+  h->kvp_lens = nullptr;
+  h->kvp_ready = false;
+  if (h->kv_shared) { h->kv_shared = false; h->kv_ready = false; }  // the rows' prompts are gone
+  if (!buf) return SLAM_OK;
+  if (max_prompts <= 0 || prefix_capacity <= 0) return SLAM_EINVAL;
+  if (h->arch == 1) return h->fail(SLAM_EINVAL, "prompt store: the OPT family has no KV cache");
+  if (((uintptr_t)buf) & 255) return h->fail(SLAM_EINVAL, "prompt store must be 256-byte aligned");
+  const size_t need = slam_kv_prefix_bytes(h, max_prompts, prefix_capacity);
+  if (bytes < need) return h->fail(SLAM_ENOMEM, "prompt store too small");
+  h->kvp = (bf16_t*)buf;
+  h->kvp_lens = (int*)((char*)buf + need - (size_t)max_prompts * sizeof(int32_t));
+  h->kvp_pmax = max_prompts;
+  h->kvp_cap = prefix_capacity;
+  return SLAM_OK;
+}
+
+int slam_prefill_prefix(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,
+                        slam_stream_t stream) {
+  return prefill_common(h, ids, lens, B, T, logits_out, stream, true);
+}
+
+int slam_kv_share(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_stream_t stream) {
+  if (!h || !lens || n < 1) return SLAM_EINVAL;
+  if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
+  if (h->kv_dtype != SLAM_KV_BF16) return h->fail(SLAM_EINVAL, "slam_kv_share needs a bf16 KV cache (the shared-prompt mode has no FP8 form)");
+  if (!h->kvp) return h->fail(SLAM_ESTATE, "bind a prompt store first (slam_bind_kv_prefix)");
+  if (!h->kvp_ready) return h->fail(SLAM_ESTATE, "slam_kv_share needs a slam_prefill_prefix into the bound prompt store first");
+  if (h->kv_shared) return h->fail(SLAM_ESTATE, "slam_kv_share twice: prefill the prompt store again");
+  if ((int64_t)h->kvp_B * n > h->kv_bmax) return h->fail(SLAM_EINVAL, "B * n rows exceed the bound KV cache");
+  CK(kv_share_fan(lens, logits, h->kvp_B, n, h->d.vocab, (hipStream_t)stream));
+  h->kv_B = h->kvp_B * n;
+  h->kv_n = n;
+  h->kv_hi = h->kvp_T;  // the host bound stays absolute, as lens does
+  h->kv_T = -1;
+  h->kv_shared = true;
   h->kv_ready = true;
   return SLAM_OK;
 }
@@ -309,7 +391,7 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_decode_step needs a slam_prefill into the bound cache first");
   if (B != h->kv_B) return h->fail(SLAM_EINVAL, "decode batch differs from the prefill batch");
-  if (h->kv_hi + 1 > h->kv_cap) return h->fail(SLAM_ESTATE, "decode step past the KV cache capacity");
+  if (h->kv_hi + 1 - (h->kv_shared ? h->kvp_T : 0) > h->kv_cap) return h->fail(SLAM_ESTATE, "decode step past the KV cache capacity");
   if ((int64_t)2 * B > h->max_tokens) return h->fail(SLAM_ENOMEM, "decode needs a workspace of at least 2 B tokens");
   const SlamModelDesc& d = h->d;
   hipStream_t st = (hipStream_t)stream;
@@ -349,6 +431,7 @@ int slam_kv_repeat(SlamEngine* h, int32_t n, int32_t* lens, float* logits, slam_
   if (!h || !lens || n < 1) return SLAM_EINVAL;
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_kv_repeat needs a slam_prefill into the bound cache first");
+  if (h->kv_shared) return h->fail(SLAM_ESTATE, "slam_kv_repeat in the shared-prompt mode: prefill again to leave it");
   if (h->kv_hi != h->kv_T) return h->fail(SLAM_ESTATE, "slam_kv_repeat after a decode step: prefill again");
   if ((int64_t)h->kv_B * n > h->kv_bmax) return h->fail(SLAM_EINVAL, "B * n rows exceed the bound KV cache");
   if (n == 1) return SLAM_OK;
@@ -382,6 +465,7 @@ int slam_kv_rewind(SlamEngine* h, int32_t hi) {
   if (!h) return SLAM_EINVAL;
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_kv_rewind needs a slam_prefill into the bound cache first");
+  if (h->kv_shared) return h->fail(SLAM_ESTATE, "slam_kv_rewind in the shared-prompt mode: prefill again to leave it");
   if (hi < 1 || hi > h->kv_hi) return h->fail(SLAM_EINVAL, "slam_kv_rewind: hi outside 1 .. the current bound");
   h->kv_hi = hi;
   h->kv_T = -1;  // as after a decode step: slam_kv_repeat is refused until the next prefill

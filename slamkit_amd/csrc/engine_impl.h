@@ -256,6 +256,17 @@ struct SlamEngine {
                          // a decode step was taken (slam_kv_repeat)
   bool kv_ready = false; // a prefill filled the bound cache
 
+  // Prompt store of the shared-prompt mode (slam_bind_kv_prefix, caller-owned): per layer K[kvp_pmax][nKV][kvp_cap][hd] then V,
+  // bf16, and behind all layers the prompts' lengths, int32 [kvp_pmax], written by slam_prefill_prefix
+  bf16_t* kvp = nullptr;
+  int* kvp_lens = nullptr;
+  int kvp_pmax = 0, kvp_cap = 0;
+  int kvp_B = 0, kvp_T = 0;     // prompts and width of the last slam_prefill_prefix
+  bool kvp_ready = false;       // a slam_prefill_prefix filled the bound store
+  bool kvp_scatter = false;     // inside slam_prefill_prefix: cache_scatter writes the store
+  bool kv_shared = false;       // slam_kv_share ran: row r reads prompt r / kv_n from the store, `kv` holds the keys behind it
+  int kv_n = 1;
+
   // FP8 copy of the decode projections (slam_bind_decode_w8, caller-owned): codes + exponents of wqkv, wo, wgu, wd of every
   // layer, then of the head matrix when w8_head. w8_valid: the codes describe the bound parameters (slam_quantize_decode_w8
   // set it; every entry point that writes or rebinds parameters clears it, and decode_proj then reads the bf16 parameters)
@@ -363,7 +374,12 @@ inline uint8_t* kv8_codes(SlamEngine* h, int l, int v) { return (uint8_t*)h->kv 
 inline int8_t* kv8_exps(SlamEngine* h, int l, int v) {
   return (int8_t*)h->kv + (size_t)h->d.n_layers * 2 * kv8_vectors(h) * h->d.head_dim + ((size_t)l * 2 + v) * kv8_vectors(h);
 }
-// layer l's K / V rows t < lens[b] of la[l].qkv into the bound cache, in its form (engine_cache.hip)
+// K (v = 0) or V (v = 1) of layer l in the bound prompt store
+inline bf16_t* kvp_kv(SlamEngine* h, int l, int v) {
+  return h->kvp + ((size_t)l * 2 + v) * h->kvp_pmax * h->d.n_kv_heads * h->kvp_cap * h->d.head_dim;
+}
+// layer l's K / V rows t < lens[b] of la[l].qkv into the bound cache, in its form - or, inside slam_prefill_prefix, into the
+// prompt store (engine_cache.hip)
 int cache_scatter(SlamEngine* h, int l, const int32_t* lens, int B, int T, hipStream_t st);
 
 }  // namespace slam_impl

@@ -425,6 +425,24 @@ int lens_add(int* lens, const int* new_lens, int B, int T, hipStream_t st);
 // row in descending b (hazard-free for every (B, n): decode.hip's header). kv_bound: host bound of lens.
 int kv_repeat(bf16_t* kv, int* lens, float* logits, int B, int n, int bmax, int L, int nKV, int head_dim, int cap, int kv_bound,
               int vocab, hipStream_t st);
+// decode_shared.hip: one decode step of attention with the prompt keys shared (include/slam_engine.h: slam_kv_share). Row r of
+// the R = P n rows belongs to prompt r / n; qkv, bias, tables, lens and o are attn_decode's over R rows, lens[r] the row's
+// ABSOLUTE key count. Keys k < plens[r / n] are read from the prompt store pk / pv ([P][nKV][pcap][hd] bf16) on the matrix pipe,
+// keys behind it from kc / vc ([R][nKV][cap][hd]) at index k - plen; the new K / V go to index lens[r] - plen there. pbound >=
+// max(plens), sbound >= max(lens[r] - plen) + 1 (host bounds, <= pcap / cap). -3: part_bytes holds not even one split each.
+struct SharedPlan {
+  int qt, qgroups;   // 16-query tiles per wave (1 or 2), blocks of 64 qt queries per (prompt, KV head)
+  int pchunk, nsp;   // prefix keys per split (a multiple of 32), prefix splits
+  int schunk, nss;   // suffix keys per split (a multiple of 64), suffix splits
+};
+int attn_shared_plan(int P, int n, int nH, int nKV, int head_dim, int pbound, int sbound, size_t part_bytes, SharedPlan* p);
+int attn_decode_shared(const float* qkv, const bf16_t* bias, const float* cs, const float* sn, const float* csq, const float* snq,
+                       const int* lens, const int* plens, int n, const bf16_t* pk, const bf16_t* pv, int pcap, int pbound, bf16_t* kc,
+                       bf16_t* vc, int cap, int sbound, int P, int nH, int nKV, int head_dim, bf16_t* o, float* part,
+                       size_t part_bytes, hipStream_t st);
+// lens[b] and the nullable fp32 logits row b -> rows b n .. b n + n - 1 in place (kv_repeat's launch scheme, no key copied)
+int kv_share_fan(int* lens, float* logits, int B, int n, int vocab, hipStream_t st);
+int lens_copy(const int* src, int* dst, int B, hipStream_t st);
 // decode_kv8.hip: the FP8 form of the cache (include/slam_engine.h: SLAM_KV_FP8_E4M3). One layer's K and V as codes kc / vc
 // ([B][nKV][cap][hd] bytes, dim order, 16-byte aligned) and exponents ke / ve (int8 [B][nKV][cap]); a vector's exponent and codes
 // follow the rule of quantize_rows_fp8 for a weight row. Each call is its bf16 namesake with the cache read and written in this

@@ -156,6 +156,38 @@ int slam_op_attn_decode_fp8(const float* qkv, const void* bias, const int32_t* l
                                kv_bound, theta, s);
   return r == -1 ? SLAM_EINVAL : r;
 }
+size_t slam_op_attn_decode_shared_workspace(int P, int n, int nH, int nKV, int head_dim, int prefix_bound, int kv_bound) {
+  SharedPlan p;
+  if (attn_shared_plan(P, n, nH, nKV, head_dim, prefix_bound, kv_bound, (size_t)-1, &p)) return 0;
+  return attn_decode_op_head(P * n, head_dim) + attn_decode_part_bytes(P * n, nH, head_dim, p.nsp + p.nss);
+}
+int slam_op_attn_decode_shared(const float* qkv, const void* bias, const int32_t* lens, const int32_t* plens, int n,
+                               const void* k_prefix, const void* v_prefix, int prefix_capacity, void* k_cache, void* v_cache,
+                               int capacity, void* o, void* ws, size_t ws_bytes, int P, int nH, int nKV, int head_dim,
+                               int prefix_bound, int kv_bound, float theta, slam_stream_t s) {
+  if (!qkv || !lens || !plens || !k_prefix || !v_prefix || !k_cache || !v_cache || !o || !ws || P <= 0 || n <= 0 ||
+      (head_dim != 64 && head_dim != 128) || (int64_t)P * n > 65535)
+    return SLAM_EINVAL;
+  if (prefix_bound <= 0 || prefix_bound > prefix_capacity || kv_bound <= 0 || kv_bound > capacity) return SLAM_EINVAL;
+  const int R = P * n;
+  const size_t head = attn_decode_op_head(R, head_dim);
+  if (ws_bytes <= head) return SLAM_ENOMEM;
+  SharedPlan p;  // refused here, before the table launches: a call without room for one split each writes nothing
+  if (int r = attn_shared_plan(P, n, nH, nKV, head_dim, prefix_bound, kv_bound, ws_bytes - head, &p)) return r == -1 ? SLAM_EINVAL : r;
+  hipStream_t st = (hipStream_t)s;
+  char* w = (char*)ws;
+  int64_t* pos = (int64_t*)w;
+  float* tab = (float*)(w + (((size_t)R * 8 + 255) & ~(size_t)255));
+  const size_t m = (size_t)R * (head_dim / 2);
+  int r = lens_to_pos(lens, pos, R, st);
+  if (r) return r;
+  r = rope_table(pos, R, 1, head_dim, theta, tab, tab + m, tab + 2 * m, tab + 3 * m, 1.44269504088896340736f / sqrtf((float)head_dim), st);
+  if (r) return r;
+  r = attn_decode_shared(qkv, (const bf16_t*)bias, tab, tab + m, tab + 2 * m, tab + 3 * m, lens, plens, n, (const bf16_t*)k_prefix,
+                         (const bf16_t*)v_prefix, prefix_capacity, prefix_bound, (bf16_t*)k_cache, (bf16_t*)v_cache, capacity, kv_bound,
+                         P, nH, nKV, head_dim, (bf16_t*)o, (float*)(w + head), ws_bytes - head, st);
+  return r == -1 ? SLAM_EINVAL : r;
+}
 int slam_op_kv_scatter_fp8(const void* qkv, const int32_t* lens, void* k_codes, void* v_codes, void* k_exps, void* v_exps, int B, int T,
                            int nH, int nKV, int head_dim, int capacity, slam_stream_t s) {
   const int r = kv_scatter_fp8((const bf16_t*)qkv, (uint8_t*)k_codes, (uint8_t*)v_codes, (int8_t*)k_exps, (int8_t*)v_exps, lens, B, T, nH,

@@ -142,6 +142,10 @@ def load_library(path: Optional[str] = None):
         "slam_sample_tokens": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
         "slam_constrain_scores": (C.c_int, [vp, vp, i32, i32, C.POINTER(SlamConstrainDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
         "slam_kv_repeat": (C.c_int, [vp, i32, vp, vp, vp]),
+        "slam_kv_prefix_bytes": (sz, [vp, i32, i32]),
+        "slam_bind_kv_prefix": (C.c_int, [vp, vp, sz, i32, i32]),
+        "slam_prefill_prefix": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
+        "slam_kv_share": (C.c_int, [vp, i32, vp, vp, vp]),
         "slam_extend": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
         "slam_extend_score": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "slam_extend_logits": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
@@ -241,6 +245,9 @@ def load_library(path: Optional[str] = None):
         "slam_op_attn_extend_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "slam_op_kv_scatter_fp8": (C.c_int, [vp] * 6 + [C.c_int] * 6 + [vp]),
         "slam_op_kv_extend_scatter_fp8": (C.c_int, [vp] * 7 + [C.c_int] * 7 + [vp]),
+        "slam_op_attn_decode_shared_workspace": (sz, [C.c_int] * 7),
+        "slam_op_attn_decode_shared": (C.c_int, [vp] * 4 + [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, sz] + [C.c_int] * 6 +
+                                       [C.c_float, vp]),
         "slam_op_attn_decode_fp8": (C.c_int, [vp] * 9 + [sz] + [C.c_int] * 6 + [C.c_float, vp]),
         "slam_op_attn_extend_fp8": (C.c_int, [vp] * 9 + [sz] + [C.c_int] * 7 + [vp]),
         "slam_op_attn_extend": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -828,6 +835,29 @@ class Engine:
         filled) and the optional fp32 logits [B n, vocab] likewise; the decode batch becomes B n."""
         self._ck(self.lib.slam_kv_repeat(self.h, int(n), _ptr(lens), _ptr(logits),
                                          stream if stream is not None else current_stream_ptr()))
+
+    # the shared-prompt mode (include/slam_engine.h: slam_kv_share): one copy of each prompt's keys for its n rows
+    def kv_prefix_bytes(self, max_prompts: int, prefix_capacity: int) -> int:
+        return int(self.lib.slam_kv_prefix_bytes(self.h, max_prompts, prefix_capacity))
+
+    def bind_kv_prefix(self, buf, max_prompts: int = 0, prefix_capacity: int = 0):
+        """buf: a 256-byte aligned device buffer of kv_prefix_bytes(max_prompts, prefix_capacity) bytes, kept alive here; None
+        unbinds the prompt store."""
+        self._keep["kv_prefix"] = buf
+        nbytes = 0 if buf is None else buf.numel() * buf.element_size()
+        self._ck(self.lib.slam_bind_kv_prefix(self.h, _ptr(buf), nbytes, max_prompts, prefix_capacity))
+
+    def prefill_prefix(self, ids, lens, B: int, T: int, logits_out, stream: Optional[int] = None):
+        """slam_prefill whose K / V go to the prompt store: the same fp32 logits [B, vocab], bit for bit."""
+        self._ck(self.lib.slam_prefill_prefix(self.h, _ptr(ids), _ptr(lens), B, T, _ptr(logits_out),
+                                              stream if stream is not None else current_stream_ptr()))
+
+    def kv_share(self, n: int, lens, logits=None, stream: Optional[int] = None):
+        """After a prefill_prefix of B prompts: kv_repeat's fan-out of lens (int32 [B n], first B filled) and the optional fp32
+        logits [B n, vocab] with no key copied; the decode batch becomes B n, row r reading prompt r // n from the store and
+        the bound bf16 cache holding only what the rows append. lens stay absolute key counts."""
+        self._ck(self.lib.slam_kv_share(self.h, int(n), _ptr(lens), _ptr(logits),
+                                        stream if stream is not None else current_stream_ptr()))
 
     def extend(self, ids, new_lens, lens, B: int, T: int, logits_out, stream: Optional[int] = None):
         """slam_extend: ids int64 [B, T] (right-padded), new_lens int32 [B] (0 .. T real tokens per row), lens int32 [B] (the

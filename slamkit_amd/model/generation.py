@@ -119,6 +119,15 @@ non-finite guidance_scale; negative prompts (or their mask) while guidance is of
 batch size than B or with an empty row; max(T, T_neg) + max_new_tokens above max_tokens; guidance together with assistant_model
 or prompt_lookup_num_tokens (the verify pass would need guided chunk scores).
 
+`share_prompt_cache=True` (also the model attribute `share_prompt_cache` and `generation_config`) keeps each prompt's keys once
+for its `num_return_sequences` rows: a prompt store of P x roundup(T, 64) positions (P = B, or 2 B under guidance) filled by
+slam_prefill_prefix, an ordinary cache of R x roundup(max_new_tokens, 64) positions for what the R = P n rows append, and
+slam_kv_share(n) in the place of slam_kv_repeat; the decode loop is the same calls. The prefill logits - and so the first token
+- are the unshared call's bits; later logits differ by rounding only (the prompt part of the attention runs on the matrix pipe),
+so a token at a near-tie may differ, as under `prefill_chunk`. Both engine samplers, the torch sampler, the history bans,
+`return_logprobs`, the FP8 decode weights and guidance follow as without it. ValueError: together with
+kv_cache_dtype="fp8_e4m3", prefill_chunk, assistant_model or prompt_lookup_num_tokens. score_continuations does not take it.
+
 score_continuations
 -------------------
 This model's log-probs of given continuations of the prompts, through the KV cache: the scoring half of
@@ -322,10 +331,23 @@ def _bind_cache(model, rows: int, cap: int, dtype: Optional[str] = None):
     return raw
 
 
-def _prefill(model, ids, lens, B, T, logits, chunk=None):
+def _bind_prefix(model, prompts: int, cap: int):
+    """A prompt store of `prompts` x `cap` positions (share_prompt_cache) bound to the model's engine, as _bind_cache binds a cache."""
+    nbytes = model.engine.kv_prefix_bytes(prompts, cap)
+    raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=model.device)
+    off = (-raw.data_ptr()) % 256
+    model.engine.bind_kv_prefix(raw[off:off + nbytes], prompts, cap)
+    return raw
+
+
+def _prefill(model, ids, lens, B, T, logits, chunk=None, shared=False):
     """The prompts into the cache and each row's last-token logits into logits[:B]: slam_prefill over all T columns, or
     (chunk = C) over the first min(T, C) and slam_extend over every further block of C. lens (first B entries: the prompt
-    lengths) is left as it is; the chunks advance a copy, which ends equal to it."""
+    lengths) is left as it is; the chunks advance a copy, which ends equal to it. shared: slam_prefill_prefix, into the prompt
+    store (one shot: share_prompt_cache refuses prefill_chunk)."""
+    if shared:
+        model.engine.prefill_prefix(ids, lens, B, T, logits)
+        return
     if chunk is None or T <= chunk:
         model.engine.prefill(ids, lens, B, T, logits)
         return
@@ -362,6 +384,7 @@ class _Request(NamedTuple):
     guidance_scale: Optional[float] = None   # not None: guidance is on
     proposer: Optional[object] = None        # a _DraftProposer or a _LookupProposer: the speculative path
     kv_dtype: str = "bfloat16"               # the target's cache: "bfloat16" or "fp8_e4m3" (a draft model keeps its own setting)
+    share_prompt: bool = False               # one copy of each prompt's keys for its num_return_sequences rows (slam_kv_share)
 
 
 def _resolve(model, gc, extra: dict, a: dict) -> _Request:
@@ -382,6 +405,15 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
 
     kv_dtype = pick("kv_cache_dtype", model.kv_cache_dtype)
     E.kv_dtype_code(kv_dtype)  # a ValueError that names the two
+    share_prompt = bool(pick("share_prompt_cache", getattr(model, "share_prompt_cache", False)))
+    if share_prompt:  # bf16, one-shot prefill, plain decode steps: what slam_kv_share covers
+        lookup = pick("prompt_lookup_num_tokens", None)
+        for on, what in ((kv_dtype != "bfloat16", f"kv_cache_dtype={kv_dtype!r} (the prompt store is bf16)"),
+                         (prefill_chunk is not None, "prefill_chunk (the prompt store is filled in one pass)"),
+                         (a["assistant_model"] is not None, "assistant_model (the verify pass appends chunks)"),
+                         (lookup is not None, "prompt_lookup_num_tokens (the verify pass appends chunks)")):
+            if on:
+                raise ValueError(f"share_prompt_cache does not combine with {what}")
     num_beams = pick("num_beams", 1)
     rep = pick("repetition_penalty", 1.0)
     if num_beams != 1:
@@ -421,7 +453,7 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
     if nret > 1 and not do_sample:
         raise ValueError("num_return_sequences > 1 needs do_sample=True (greedy continuations would all be equal)")
     rq = _Request(inputs, max_new, nret, a["return_logprobs"], do_sample, temperature, top_k, top_p, late, warp, eos, int(pad),
-                  plan, a["seed"], a["sample_ids"], prefill_chunk, kv_dtype=kv_dtype)
+                  plan, a["seed"], a["sample_ids"], prefill_chunk, kv_dtype=kv_dtype, share_prompt=share_prompt)
     if max_new <= 0:
         return rq
     if extra:
@@ -828,8 +860,15 @@ def generate(model, gc, extra: dict, args: dict):
     cap = -(-(T + max_new) // 64) * 64
     # rows prefilled and rows in the cache: under guidance the conditional rows, then as many unconditional ones
     P, R = (B, BN) if cfg is None else (2 * B, 2 * BN)
-    model._ensure_workspace(max(P * (T if rq.prefill_chunk is None else min(T, rq.prefill_chunk)), 2 * R))
-    raw = _bind_cache(model, R, cap, rq.kv_dtype)  # noqa: F841 - alive until the call returns
+    ws_tokens = max(P * (T if rq.prefill_chunk is None else min(T, rq.prefill_chunk)), 2 * R)
+    if rq.share_prompt:  # the logits buffer holds the attention partials: room for one split of each part at the least
+        d = model.engine.desc
+        ws_tokens = max(ws_tokens, -(-R * d.n_heads * 2 * (d.head_dim + 2) * 4 // (2 * model.engine.padded_vocab())))
+    model._ensure_workspace(ws_tokens)
+    if rq.share_prompt:  # the prompts once, in a store of their own; the cache holds what the rows append
+        raw = (_bind_prefix(model, P, -(-T // 64) * 64), _bind_cache(model, R, -(-max_new // 64) * 64, rq.kv_dtype))  # noqa: F841
+    else:
+        raw = _bind_cache(model, R, cap, rq.kv_dtype)  # noqa: F841 - alive until the call returns
     logits = torch.empty(R, V, dtype=torch.float32, device=dev)
     eos_t = torch.tensor(rq.eos, dtype=torch.long, device=dev) if rq.eos else None
     if nret > 1:  # the prefilled rows first; slam_kv_repeat fills the rest
@@ -849,10 +888,14 @@ def generate(model, gc, extra: dict, args: dict):
         picker = _EnginePicker(rq, new, None if cfg is None else cfg.slot, V, dev)
     else:
         picker = _TorchPicker(rq, new, eos_t, dev)
-    _prefill(model, ids, lens, P, T, logits, rq.prefill_chunk)
-    if nret > 1:
+    _prefill(model, ids, lens, P, T, logits, rq.prefill_chunk, rq.share_prompt)
+    if rq.share_prompt:
+        model.engine.kv_share(nret, lens, logits)
+    elif nret > 1:
         model.engine.kv_repeat(nret, lens, logits)
     n = _decode(model, rq, picker, logits, lens, lp, cons, cfg)
+    if rq.share_prompt:
+        model.engine.bind_kv_prefix(None)  # the store dies with this call: leave the shared mode with it
     new, n = _trim(new[:, :n], n, eos_t)
     seq = torch.cat([seq_in.repeat_interleave(nret, 0) if nret > 1 else seq_in, new], 1)
     return GenerateOutput(seq, lp[0][:, :n].contiguous()) if lp is not None else seq

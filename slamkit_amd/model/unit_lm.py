@@ -1232,6 +1232,7 @@ class UnitLM(TokenLM):
     _assist_trace = None      # a list: every round appends CPU copies of (chunk, logits_all, n_new before, tgt, n_new after)
     _lookup_trace = None      # the same for prompt lookup, and n_prop behind them
     kv_cache_dtype = "bfloat16"  # the KV cache of generate / score_continuations: "bfloat16" or "fp8_e4m3" (per call: kv_cache_dtype=)
+    share_prompt_cache = False   # generate: keep each prompt's keys once for its num_return_sequences rows (per call: share_prompt_cache=)
     last_assist_stats = None  # {"rounds", "proposed", "accepted", "tokens"} of the last speculative generate
 
     @torch.no_grad()
@@ -1251,7 +1252,7 @@ class UnitLM(TokenLM):
                  eta_cutoff: Optional[float] = None, guidance_scale: Optional[float] = None,
                  negative_prompt_ids: Optional[torch.Tensor] = None,
                  negative_prompt_attention_mask: Optional[torch.Tensor] = None, kv_cache_dtype: Optional[str] = None,
-                 **kwargs):
+                 share_prompt_cache: Optional[bool] = None, **kwargs):
         """HF `generate` on the engine's KV cache: [B, T_in + n_new] int64, the prompt as passed and then the new tokens, or
         GenerateOutput(sequences, logprobs) under return_logprobs. Explicit arguments override `generation_config`; any other
         keyword is a TypeError. generation.py has every argument's contract. Prompts: inputs / input_ids, attention_mask,
@@ -1260,7 +1261,8 @@ class UnitLM(TokenLM):
         suppress_tokens, begin_suppress_tokens, no_repeat_ngram_size. Outputs: num_return_sequences, return_logprobs. Prefill:
         prefill_chunk. Speculative: assistant_model, num_assistant_tokens, prompt_lookup_num_tokens, max_matching_ngram_size.
         Guidance: guidance_scale, negative_prompt_ids, negative_prompt_attention_mask. Cache: kv_cache_dtype ("bfloat16" or
-        "fp8_e4m3"; default: this model's `kv_cache_dtype`)."""
+        "fp8_e4m3"; default: this model's `kv_cache_dtype`), share_prompt_cache (the rows of a prompt attend one copy of its keys:
+        less cache and less traffic for num_return_sequences > 1; bf16 cache, one-shot prefill, no speculative path)."""
         return generation.generate(self, generation_config, kwargs, dict(locals()))  # stays the first statement: the arguments
 
     @torch.no_grad()

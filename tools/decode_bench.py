@@ -60,6 +60,13 @@ rows' prompts: 1 (generate's default, the last prompt token) and 256 (a negative
 `cfg_op` line per (B, V) in {8, 32} x {502, 152576}: `cfg_scores_us` = one slam_cfg_scores (device events around 200
 back-to-back calls, five rounds), `bytes_MB` = what it moves (2 B rows read, B written; rows above one chunk are read twice) and
 `GBps`, `floor_us` = bytes / 6.3 TB/s; and `mirror_us` = one slam_cfg_mirror_tokens.
+--share-prompt N[,N..] [--models slam,cfg3] [--batches 1,8] [--prompts 256,1024,2048] [--blocks 3]: the decode step over B x n
+rows behind slam_prefill + slam_kv_repeat (`repeat_step_ms`: the path without the option) and behind slam_prefill_prefix +
+slam_kv_share (`share_step_ms`), as alternating blocks within this process, each block its own prefill, device events per step, 10
+warm-up steps per block: one `share_prompt` line per (model, B, T, n) with the medians over the blocks (`_all` the blocks),
+`repeat_over_share` (median of the per-block ratios, `_minmax`) and the bytes each mode binds for `--steps` new tokens
+(`repeat_cache_MB`; `share_cache_MB` = prompt store + suffix cache). The prefix / suffix / combine durations come from a
+`rocprofv3 --kernel-trace --stats` run of this option, read by --trace-summary.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -222,6 +229,59 @@ def cfg_op_bench(calls=200, rounds=5):
                               cfg_scores_us_minmax=[round(min(ts), 2), round(max(ts), 2)], bytes_MB=round(nbytes / 1e6, 3),
                               GBps=round(nbytes / us / 1e3, 1), floor_us=round(nbytes / HBM_BPS * 1e6, 3),
                               mirror_us=round(statistics.median(tm), 2))), flush=True)
+
+
+def share_bench(name, batches, prompts, ns, steps, blocks):
+    """The decode step over B n rows with the prompt keys copied n times (slam_kv_repeat) and shared (slam_kv_share)."""
+    import torch
+    new = 64 * -(-steps // 64)
+    m = build(name, max(prompts) + new)
+    dev, V, eng = m.device, m.config.vocab_size, m.engine
+    for B in batches:
+        for T in prompts:
+            g = torch.Generator(device=dev).manual_seed(0)
+            ids = torch.randint(2, V, (B, T), device=dev, generator=g)
+            for n in ns:
+                rows = B * n
+                d = eng.desc  # as generate sizes it: the logits buffer holds one split of each part's partials at the least
+                m._ensure_workspace(max(B * T, 2 * rows, -(-rows * d.n_heads * 2 * (d.head_dim + 2) * 4 // (2 * eng.padded_vocab()))))
+                sizes = dict(repeat=eng.kv_cache_bytes(rows, T + new), share=eng.kv_prefix_bytes(B, T) + eng.kv_cache_bytes(rows, new))
+                bufs = [torch.empty(eng.kv_cache_bytes(rows, T + new), dtype=torch.uint8, device=dev),
+                        torch.empty(eng.kv_prefix_bytes(B, T), dtype=torch.uint8, device=dev)]
+                logits = torch.empty(rows, V, dtype=torch.float32, device=dev)
+                tok = torch.ones(rows, dtype=torch.int64, device=dev)
+
+                def block(share):
+                    lens = torch.zeros(rows, dtype=torch.int32, device=dev)
+                    lens[:B] = T
+                    if share:
+                        eng.bind_kv_prefix(bufs[1], B, T)
+                        eng.bind_kv_cache(bufs[0], rows, new)
+                        eng.prefill_prefix(ids, lens, B, T, logits)
+                        eng.kv_share(n, lens, logits)
+                    else:
+                        eng.bind_kv_cache(bufs[0], rows, T + new)
+                        eng.prefill(ids, lens, B, T, logits)
+                        eng.kv_repeat(n, lens, logits)
+                    st = [ev_ms(lambda: eng.decode_step(tok, lens, rows, logits)) for _ in range(steps - 1)]
+                    return statistics.median(st[10:])
+
+                t = {"repeat": [], "share": []}
+                for _ in range(blocks):
+                    t["repeat"].append(block(False))
+                    t["share"].append(block(True))
+                ratios = [a / b for a, b in zip(t["repeat"], t["share"])]
+                print(json.dumps(dict(bench="share_prompt", model=name, B=B, T=T, n=n, steps_timed=steps - 11, blocks=blocks,
+                                      repeat_step_ms=round(statistics.median(t["repeat"]), 4), repeat_step_ms_all=[round(x, 4) for x in t["repeat"]],
+                                      share_step_ms=round(statistics.median(t["share"]), 4), share_step_ms_all=[round(x, 4) for x in t["share"]],
+                                      repeat_over_share=round(statistics.median(ratios), 3),
+                                      repeat_over_share_minmax=[round(min(ratios), 3), round(max(ratios), 3)],
+                                      repeat_cache_MB=round(sizes["repeat"] / 1e6, 1), share_cache_MB=round(sizes["share"] / 1e6, 1))), flush=True)
+                eng.bind_kv_prefix(None)
+                del bufs, logits
+                torch.cuda.empty_cache()
+    del m
+    torch.cuda.empty_cache()
 
 
 def step_bench(m, B, P, steps, tag, quiet=False, saved=0):
@@ -637,7 +697,7 @@ def trace_summary(d):
     rows = {}
 
     def add(name, gx, gy, gz, us):
-        if not any(k in name for k in ("gemm_skinny", "skinny_reduce", "attn_decode", "rmsnorm_fwd", "swiglu_fwd", "attn_extend", "kv_extend_scatter",
+        if not any(k in name for k in ("gemm_skinny", "skinny_reduce", "attn_decode", "attn_prefix", "rmsnorm_fwd", "swiglu_fwd", "attn_extend", "kv_extend_scatter",
                                        "attn_fwd")):
             return
         short = name.split("(")[0].replace("void ", "").replace("(anonymous namespace)::", "")
@@ -682,7 +742,11 @@ def main():
     ap.add_argument("--cfg", action="store_true",
                     help="classifier-free guidance: the guided step (2 B rows + slam_cfg_scores + the mirror) between plain steps "
                          "at B (--batches, default 1,8,32), then slam_cfg_scores and slam_cfg_mirror_tokens alone")
-    ap.add_argument("--batches", default=None, help="with --decode-weights (default 1,8,64) or --cfg (default 1,8,32)")
+    ap.add_argument("--share-prompt", default=None,
+                    help="N[,N..]: the decode step over B x N rows behind slam_kv_repeat and behind slam_kv_share, alternating blocks "
+                         "(--batches, default 1,8; --prompts, default 256,1024,2048)")
+    ap.add_argument("--prompts", default="256,1024,2048", help="with --share-prompt: prompt lengths")
+    ap.add_argument("--batches", default=None, help="with --decode-weights (default 1,8,64), --cfg (default 1,8,32) or --share-prompt (1,8)")
     ap.add_argument("--blocks", type=int, default=3, help="with --decode-weights: alternations per (model, batch)")
     ap.add_argument("--include-head", action="store_true", help="with --decode-weights fp8: FP8 codes for the LM head too")
     a = ap.parse_args()
@@ -691,6 +755,11 @@ def main():
         return
     import torch
     assert torch.cuda.is_available()
+    if a.share_prompt:
+        for name in a.models.split(","):
+            share_bench(name, [int(b) for b in (a.batches or "1,8").split(",")], [int(t) for t in a.prompts.split(",")],
+                        [int(n) for n in a.share_prompt.split(",")], min(a.steps, 60), a.blocks)
+        return
     if a.cfg:
         for name in a.models.split(","):
             cfg_step_bench(name, [int(b) for b in (a.batches or "1,8,32").split(",")], 256, min(a.steps, 60), a.blocks)
