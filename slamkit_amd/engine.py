@@ -15,8 +15,7 @@ from typing import Callable, Dict, List, Optional
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libslam_engine.so")
 _lib = None
 
-BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
-MODEL_UNTIED_HEAD = 1  # SLAM_MODEL_UNTIED_HEAD
+BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)  # slam_bucket_cb
 
 
 class SlamModelDesc(C.Structure):
@@ -79,17 +78,93 @@ class SlamConstrainDesc(C.Structure):
     ]
 
 
-CONSTRAIN_MAX_SEQS = 256     # SLAM_CONSTRAIN_MAX_SEQS: multi-token bad word sequences per call
-CONSTRAIN_MAX_SEQ_LEN = 16   # SLAM_CONSTRAIN_MAX_SEQ_LEN: tokens per sequence
-CONSTRAIN_MAX_BEGIN = 256    # SLAM_CONSTRAIN_MAX_BEGIN: begin_suppress ids
+# ---- include/slam_engine.h is the one description of the ABI: functions, integer constants and struct layouts are read from it --
+_SCALARS = {"void": None, "char": C.c_char, "int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64,
+            "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double,
+            "slam_stream_t": C.c_void_p, "slam_bucket_cb": BUCKET_CB}
+# The host out-parameters: the only pointers the wrappers hand over as ctypes objects (byref of a scalar, a ctypes array)
+# instead of a device address, so they keep a typed pointer and ctypes refuses an object of another width.
+# function -> {parameter index: pointee}
+_HOST_OUT = {
+    "slam_adafactor_sizes": {1: C.c_int64, 2: C.c_size_t},
+    "slam_muon_sizes": {1: C.c_int64, 2: C.c_size_t},
+    "slam_param_wait_ms": {1: C.c_float},
+    "slam_param_wait_untimed": {1: C.c_int64},
+    "slam_gateup_launch_ms": {1: C.c_float},
+    "slam_family_ms": {1: C.c_int32, 2: C.c_float, 4: C.c_int32},
+}
+
+
+def _ctype(decl: str, where: str, field: bool = False):
+    """(name, ctypes type) of one C declaration such as `const float* x`, `int32_t n`, `char name[64]` or a bare return type.
+    An array is a pointer as a parameter and `type * n` as a struct field. TypeError, naming `where`, for anything else."""
+    m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)\s*(\w*)\s*(?:\[(\d*)\])?", decl.strip())
+    if not m:
+        raise TypeError(f"{where}: cannot read the declaration {decl.strip()!r}")
+    base, stars, name, dim = m.groups()
+    n_ptr = len(stars) + (dim is not None and not field)
+    mirror = globals().get(base)
+    if n_ptr == 0:
+        if base not in _SCALARS:
+            raise TypeError(f"{where}: no ctypes type for {base!r}")
+        t = _SCALARS[base]
+    elif (base, n_ptr) == ("char", 1):
+        t = C.c_char_p
+    elif (base, n_ptr) == ("SlamEngine", 2):
+        t = C.POINTER(C.c_void_p)
+    elif n_ptr == 1 and isinstance(mirror, type) and issubclass(mirror, C.Structure):
+        t = C.POINTER(mirror)
+    else:
+        t = C.c_void_p
+    return name, t * int(dim) if field and dim else t
+
+
+def _parse_header(text: str):
+    """What a header in the style of include/slam_engine.h declares, typed by _ctype:
+    ({function: (restype, [argtypes])}, {integer #define: value}, {struct: [(field, type)]})."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    defines = {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    structs = {}
+    for struct, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        fields = structs[struct] = []
+        for stmt in filter(str.strip, body.split(";")):
+            first, *more = stmt.split(",")  # `int64_t rows, cols`: plain further names share the first one's type
+            name, t = _ctype(first, f"{struct}: {first.strip()}", field=True)
+            if not all(n.strip().isidentifier() for n in more):
+                raise TypeError(f"{struct}: cannot read the declaration {stmt.strip()!r}")
+            fields += [(name, t)] + [(n.strip(), t) for n in more]
+    text = re.sub(r"typedef\b[^;{]*(\{[^}]*\})?[^;]*;", "", text)
+    functions = {}
+    for stmt in text.split(";"):
+        if "(" not in stmt:
+            continue
+        m = re.search(r"([\w\s*]+?)\b(slam_\w+)\s*\(([^()]*)\)\s*$", stmt)
+        if not m:
+            raise TypeError(f"cannot read the declaration {' '.join(stmt.split())!r}")
+        res, fn, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        args = [_ctype(p, f"{fn}, parameter {i}")[1] for i, p in enumerate(params)]
+        for i, pointee in _HOST_OUT.get(fn, {}).items():
+            args[i] = C.POINTER(pointee)
+        functions[fn] = (_ctype(res, f"{fn}, return type")[1], args)
+    return functions, defines, structs
+
+
+with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "slam_engine.h")) as _f:
+    _FUNCTIONS, _DEFINES, _STRUCTS = _parse_header(_f.read())  # once per process
+
+MODEL_UNTIED_HEAD = _DEFINES["SLAM_MODEL_UNTIED_HEAD"]
+EINVAL, EUNSUPPORTED = _DEFINES["SLAM_EINVAL"], _DEFINES["SLAM_EUNSUPPORTED"]
+CONSTRAIN_MAX_SEQS = _DEFINES["SLAM_CONSTRAIN_MAX_SEQS"]        # multi-token bad word sequences per call
+CONSTRAIN_MAX_SEQ_LEN = _DEFINES["SLAM_CONSTRAIN_MAX_SEQ_LEN"]  # tokens per sequence
+CONSTRAIN_MAX_BEGIN = _DEFINES["SLAM_CONSTRAIN_MAX_BEGIN"]      # begin_suppress ids
+COMM_ID_BYTES = _DEFINES["SLAM_COMM_ID_BYTES"]                  # ncclGetUniqueId's blob
 
 
 def header_symbols() -> List[str]:
     """Every function name declared in include/slam_engine.h (used by the export test)."""
-    hdr = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "slam_engine.h")
-    txt = open(hdr).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(slam_[a-z0-9_]+)\s*\(", txt)) - {"slam_bucket_cb"})
+    return sorted(_FUNCTIONS)
 
 
 def load_library(path: Optional[str] = None):
@@ -106,201 +181,13 @@ def load_library(path: Optional[str] = None):
         raise OSError(f"{p} not found: build it with `python -m slamkit_amd.csrc.build` "
                       f"(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(p)
-    vp, i32, i64, f32, f64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
-    sig = {
-        "slam_engine_create": (C.c_int, [C.POINTER(SlamModelDesc), C.POINTER(vp)]),
-        "slam_engine_create_arch": (C.c_int, [C.POINTER(SlamModelDesc), i32, i32, C.POINTER(vp)]),
-        "slam_engine_create_ex": (C.c_int, [C.POINTER(SlamModelDesc), i32, i32, i32, C.POINTER(vp)]),
-        "slam_engine_destroy": (None, [vp]),
-        "slam_last_error": (C.c_char_p, [vp]),
-        "slam_version": (C.c_char_p, []),
-        "slam_param_count": (i64, [vp]),
-        "slam_tensor_count": (i32, [vp]),
-        "slam_tensor_info": (C.c_int, [vp, i32, C.POINTER(SlamTensorInfo)]),
-        "slam_bind_params": (C.c_int, [vp, vp, vp]),
-        "slam_bind_params_t": (C.c_int, [vp, vp]),
-        "slam_refresh_transposed": (C.c_int, [vp, vp]),
-        "slam_workspace_bytes": (sz, [vp, i64]),
-        "slam_bind_workspace": (C.c_int, [vp, vp, sz, i64]),
-        "slam_forward": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f64, vp, vp, vp]),
-        "slam_unpadded_scratch_bytes": (sz, [i32, i32]),
-        "slam_forward_unpadded": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, sz, f64, vp, vp, vp]),
-        "slam_forward_unpadded_spans": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, f64, vp, vp, vp]),
-        "slam_last_forward_tokens": (i64, [vp]),
-        "slam_seq_loglik_unpadded": (C.c_int, [vp, i32, vp, vp, vp]),
-        "slam_scale_loss_unpadded": (C.c_int, [vp, vp, i32, vp]),
-        "slam_op_unpad_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
-        "slam_op_unpad_pack_spans": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
-        "slam_backward": (C.c_int, [vp, f32, i32, BUCKET_CB, vp, vp]),
-        "slam_kv_cache_bytes": (sz, [vp, i32, i32]),
-        "slam_bind_kv_cache": (C.c_int, [vp, vp, sz, i32, i32]),
-        "slam_kv_cache_bytes_ex": (sz, [vp, i32, i32, i32]),
-        "slam_bind_kv_cache_ex": (C.c_int, [vp, vp, sz, i32, i32, i32]),
-        "slam_prefill": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
-        "slam_decode_step": (C.c_int, [vp, vp, vp, i32, vp, vp]),
-        "slam_sample_workspace_bytes": (sz, [i32, i32, i32]),
-        "slam_sample_tokens": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp]),
-        "slam_constrain_scores": (C.c_int, [vp, vp, i32, i32, C.POINTER(SlamConstrainDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
-        "slam_kv_repeat": (C.c_int, [vp, i32, vp, vp, vp]),
-        "slam_kv_prefix_bytes": (sz, [vp, i32, i32]),
-        "slam_bind_kv_prefix": (C.c_int, [vp, vp, sz, i32, i32]),
-        "slam_prefill_prefix": (C.c_int, [vp, vp, vp, i32, i32, vp, vp]),
-        "slam_kv_share": (C.c_int, [vp, i32, vp, vp, vp]),
-        "slam_extend": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
-        "slam_extend_score": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
-        "slam_extend_logits": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp]),
-        "slam_kv_rewind": (C.c_int, [vp, i32]),
-        "slam_sample_tokens_at": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp, i32,
-                                            i32, vp]),
-        "slam_sample_tokens_warped": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp,
-                                                i32, i32, C.POINTER(SlamWarpDesc), vp]),
-        "slam_sample_full_workspace_bytes": (sz, [i32, i32]),
-        "slam_sample_tokens_full": (C.c_int, [vp, i32, i32, vp, C.POINTER(SlamSampleDesc), vp, vp, vp, vp, vp, i64, vp, sz, vp,
-                                              i32, i32, C.POINTER(SlamWarpDesc), vp]),
-        "slam_spec_accept": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
-        "slam_ngram_propose": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, i64, vp, vp, vp, i32, vp, vp]),
-        "slam_token_logprobs_workspace_bytes": (sz, [i32, i32]),
-        "slam_token_logprobs": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, i64, i32, vp, sz, vp]),
-        "slam_cfg_workspace_bytes": (sz, [i32, i32]),
-        "slam_cfg_scores": (C.c_int, [vp, i32, i32, f32, vp, vp, sz, vp]),
-        "slam_cfg_mirror_tokens": (C.c_int, [vp, i32, vp]),
-        "slam_bucket_stream": (vp, [vp]),
-        "slam_set_logit_mask": (C.c_int, [vp, vp]),
-        "slam_padded_vocab": (i32, [vp]),
-        "slam_seq_loglik": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
-        "slam_scale_loss_rows": (C.c_int, [vp, vp, i32, i32, vp]),
-        "slam_set_label_smoothing": (C.c_int, [vp, f32]),
-        "slam_set_neftune": (C.c_int, [vp, f32, i64]),
-        "slam_grad_norm": (C.c_int, [vp, f32, vp, vp]),
-        "slam_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
-        "slam_adamw_step_bf16": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
-        "slam_adamw_step_bf16_moments": (C.c_int, [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
-        "slam_adamw_range_bf16_moments": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
-        "slam_grad_chunk_elems": (i64, []),
-        "slam_grad_sumsq_chunks": (C.c_int, [vp, i64, i64, vp, vp]),
-        "slam_grad_norm_from_chunks": (C.c_int, [vp, vp, f32, vp, vp]),
-        "slam_adamw_range": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
-        "slam_adamw_range_bf16": (C.c_int, [vp, i64, i64, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
-        "slam_set_decay_mask": (C.c_int, [vp, vp, i32]),
-        "slam_adafactor_set_segments": (C.c_int, [vp, C.POINTER(SlamAdafactorSegment), i32]),
-        "slam_adafactor_sizes": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
-        "slam_adafactor_bind_workspace": (C.c_int, [vp, vp, sz]),
-        "slam_adafactor_step": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, f64, f64, i32, i32, vp]),
-        "slam_muon_set_segments": (C.c_int, [vp, C.POINTER(SlamMuonSegment), i32]),
-        "slam_muon_sizes": (C.c_int, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
-        "slam_muon_bind_workspace": (C.c_int, [vp, vp, sz]),
-        "slam_muon_class_count": (i32, [vp]),
-        "slam_muon_class_info": (C.c_int, [vp, i32, C.POINTER(SlamMuonClass)]),
-        "slam_muon_step": (C.c_int, [vp, vp, vp, vp, f64, f64, f64, i32, i32, f64, f64, f64, f64, i32, i32, i32, vp]),
-        "slam_op_muon_prepare": (C.c_int, [vp, vp, vp, f64, i32, i32, vp]),
-        "slam_op_muon_ns_workspace": (sz, [i32, i32, i32]),
-        "slam_op_muon_ns": (C.c_int, [vp, i32, i32, i32, i64, vp, i32, i32, f64, f64, f64, f64, vp, sz, vp]),
-        "slam_op_muon_apply": (C.c_int, [vp, vp, vp, f64, f64, i32, i32, vp]),
-        "slam_op_muon_syrk": (C.c_int, [vp, vp, vp, i32, i32, i32, i64, i64, i64, f32, f32, vp]),
-        "slam_op_muon_mm": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i64, i64, i64, i64, f32, f32, vp]),
-        "slam_add_param_wait": (C.c_int, [vp, i64, i64, vp]),
-        "slam_param_wait_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
-        "slam_param_wait_untimed": (C.c_int, [vp, C.POINTER(C.c_int64)]),
-        "slam_comm_unique_id": (C.c_int, [vp, C.c_int32]),
-        "slam_comm_init": (C.c_int, [vp, vp, C.c_int32, C.c_int32]),
-        "slam_comm_destroy": (C.c_int, [vp]),
-        "slam_allreduce_grads_async": (C.c_int, [vp, i64, i64, C.c_int32, vp]),
-        "slam_comm_finish": (C.c_int, [vp, vp]),
-        "slam_reduce_scatter_grads_async": (C.c_int, [vp, i64, i64, C.c_int32, vp]),
-        "slam_allgather_params_async": (C.c_int, [vp, i64, i64, vp]),
-        "slam_gateup_launch_ms": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int32]),
-        "slam_family_ms": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]),
-        "slam_family_name": (C.c_char_p, [C.c_int32]),
-        "slam_pack_grads_bf16": (C.c_int, [vp, i64, i64, vp, vp]),
-        "slam_unpack_grads_bf16": (C.c_int, [vp, i64, i64, vp, vp]),
-        "slam_set_grad_image": (C.c_int, [vp, vp]),
-        "slam_join": (C.c_int, [vp, vp]),
-        "slam_zero_grads": (C.c_int, [vp, vp]),
-        "slam_cast_params": (C.c_int, [vp, vp, vp]),
-        "slam_set_option": (C.c_int, [vp, C.c_char_p, i64]),
-        "slam_op_gemm_nt": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_gemm_nt_swiglu": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_gemm_nt_dswiglu": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_gemm_nn": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_gemm_tn_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
-        "slam_op_gemm_tn": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
-        "slam_op_gemm_tn_image": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]),
-        "slam_op_gemm_skinny_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
-        "slam_op_gemm_skinny": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
-        "slam_op_w8_bytes": (sz, [C.c_int, C.c_int]),
-        "slam_op_w8_exps_offset": (sz, [C.c_int, C.c_int]),
-        "slam_op_quantize_rows_fp8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-        "slam_op_dequantize_rows_fp8": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-        "slam_op_gemm_skinny_w8": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
-        "slam_decode_w8_bytes": (sz, [vp, i32]),
-        "slam_bind_decode_w8": (C.c_int, [vp, vp, sz, i32]),
-        "slam_quantize_decode_w8": (C.c_int, [vp, vp]),
-        "slam_decode_w8_state": (C.c_int, [vp]),
-        "slam_decode_w8_launches": (i64, [vp]),
-        "slam_op_score_rows_workspace": (sz, [C.c_int, C.c_int]),
-        "slam_op_score_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, sz, vp]),
-        "slam_op_attn_decode_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-        "slam_op_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          f32, vp]),
-        "slam_op_attn_extend_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-        "slam_op_kv_scatter_fp8": (C.c_int, [vp] * 6 + [C.c_int] * 6 + [vp]),
-        "slam_op_kv_extend_scatter_fp8": (C.c_int, [vp] * 7 + [C.c_int] * 7 + [vp]),
-        "slam_op_attn_decode_shared_workspace": (sz, [C.c_int] * 7),
-        "slam_op_attn_decode_shared": (C.c_int, [vp] * 4 + [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, sz] + [C.c_int] * 6 +
-                                       [C.c_float, vp]),
-        "slam_op_attn_decode_fp8": (C.c_int, [vp] * 9 + [sz] + [C.c_int] * 6 + [C.c_float, vp]),
-        "slam_op_attn_extend_fp8": (C.c_int, [vp] * 9 + [sz] + [C.c_int] * 7 + [vp]),
-        "slam_op_attn_extend": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, vp]),
-        "slam_op_rmsnorm_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
-        "slam_op_rmsnorm_bwd_workspace": (sz, [C.c_int, C.c_int]),
-        "slam_op_rmsnorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
-        "slam_op_layernorm_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, vp]),
-        "slam_op_layernorm_bwd_workspace": (sz, [C.c_int, C.c_int]),
-        "slam_op_layernorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]),
-        "slam_op_embed_pos_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_gemm_nt_relu": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_gemm_nt_drelu": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_relu_bwd": (C.c_int, [vp, vp, i64, vp]),
-        "slam_op_rope": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, f32, C.c_int, vp, vp]),
-        "slam_op_qknorm_rope_fwd": (C.c_int, [vp, vp, vp, vp, f32, f32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
-        "slam_op_qknorm_bwd_workspace": (sz, [C.c_int, C.c_int, C.c_int, C.c_int]),
-        "slam_op_qknorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_qknorm_rows_f32": (C.c_int, [vp, vp, vp, f32, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_swiglu_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
-        "slam_op_swiglu_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, vp]),
-        "slam_op_attn_fwd": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_attn_bwd_workspace": (sz, [C.c_int, C.c_int, C.c_int]),
-        "slam_op_attn_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_attn_bwd_rope": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, f32, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            vp, vp]),
-        "slam_op_gemm_nt_rope": (C.c_int, [vp, vp, vp, vp, vp, f32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
-        "slam_op_colsum_workspace": (sz, [C.c_int, C.c_int]),
-        "slam_op_colsum": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
-        "slam_op_cross_entropy": (C.c_int, [vp, vp, f64, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_cross_entropy_smooth": (C.c_int, [vp, vp, f64, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]),
-        "slam_op_copy_cols": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_unpad_logits": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_unpad_logits_spans": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_scale_bf16": (C.c_int, [vp, i64, f32, vp]),
-        "slam_op_scale_rows_bf16": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_scale_rows_unpadded_bf16": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp]),
-        "slam_op_embed_bwd_workspace": (sz, [C.c_int, C.c_int]),
-        "slam_op_embed_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
-        "slam_op_sr_round_bf16": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp]),
-        "slam_op_dropout_add": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, i64, i64, i32, i64, vp]),
-        "slam_op_dropout_bwd": (C.c_int, [vp, vp, C.c_int, C.c_int, i32, i64, i64, i32, i64, vp]),
-        "slam_op_embed_fwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
-        "slam_op_embed_noise_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, i64, i64, i64,
-                                              vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _FUNCTIONS.items():
         if path is not None and not hasattr(lib, name):
             continue  # an explicitly named OTHER build (A/B tooling against an older library): bind what it has
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-    lib._slam_signatures = sig
+    lib._slam_signatures = _FUNCTIONS
     if path is None:
         _lib = lib
     return lib
@@ -325,7 +212,7 @@ def current_stream_ptr() -> int:
     return int(torch.cuda.current_stream().cuda_stream)
 
 
-KV_CACHE_DTYPES = {"bfloat16": 0, "fp8_e4m3": 1}  # SLAM_KV_BF16, SLAM_KV_FP8_E4M3
+KV_CACHE_DTYPES = {"bfloat16": _DEFINES["SLAM_KV_BF16"], "fp8_e4m3": _DEFINES["SLAM_KV_FP8_E4M3"]}
 
 
 def kv_dtype_code(dtype) -> int:
@@ -394,7 +281,7 @@ def sample_tokens(logits, desc: SlamSampleDesc, next_ids, ws, banned=None, row_i
                                           _ptr(ws), ws.numel() * ws.element_size(),
                                           stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_sample_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_sample_tokens failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def sample_tokens_at(logits, desc: SlamSampleDesc, next_ids, ws, steps=None, group: int = 1, out_col: int = 0, banned=None,
@@ -409,7 +296,7 @@ def sample_tokens_at(logits, desc: SlamSampleDesc, next_ids, ws, steps=None, gro
                                              _ptr(ws), ws.numel() * ws.element_size(), _ptr(steps), int(group), int(out_col),
                                              stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_sample_tokens_at failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_sample_tokens_at failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def sample_tokens_warped(logits, desc: SlamSampleDesc, next_ids, ws, warp: Optional[SlamWarpDesc], steps=None, group: int = 1,
@@ -426,10 +313,10 @@ def sample_tokens_warped(logits, desc: SlamSampleDesc, next_ids, ws, warp: Optio
                                                  C.byref(warp) if warp is not None else None,
                                                  stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_sample_tokens_warped failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_sample_tokens_warped failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
-SAMPLE_FULL_SMALL_MAX = 4096  # SLAM_SAMPLE_FULL_SMALL_MAX: rows up to this length take slam_sample_tokens_full's one-block form
+SAMPLE_FULL_SMALL_MAX = _DEFINES["SLAM_SAMPLE_FULL_SMALL_MAX"]  # rows up to this length take slam_sample_tokens_full's one-block form
 
 
 def sample_full_workspace_bytes(B: int, vocab: int) -> int:
@@ -451,7 +338,7 @@ def sample_tokens_full(logits, desc: SlamSampleDesc, next_ids, ws, warp: Optiona
                                                C.byref(warp) if warp is not None else None,
                                                stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_sample_tokens_full failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_sample_tokens_full failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 SPEC_MAX_ROWS = 1024  # slam_spec_accept: one block, a thread per row
@@ -472,10 +359,10 @@ def spec_accept(chunk, tgt, K: int, max_new: int, pad_id: int, eos_ids, prompt_l
                                         _ptr(draft_new_lens), _ptr(tgt_new_lens), _ptr(stats),
                                         stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_spec_accept failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_spec_accept failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
-NGRAM_MAX = 16  # slam_ngram_propose: the longest n-gram matched (SLAM_NGRAM_MAX)
+NGRAM_MAX = _DEFINES["SLAM_NGRAM_MAX"]  # slam_ngram_propose: the longest n-gram matched
 NGRAM_STATS = ("rows", "proposed")
 
 
@@ -491,7 +378,7 @@ def ngram_propose(chunk, n_prop, max_ngram: int, fill_id: int, prompt, prompt_le
                                           _ptr(eos_ids), 0 if eos_ids is None else int(eos_ids.numel()), _ptr(stats),
                                           stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_ngram_propose failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_ngram_propose failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def constrain_scores(logits, scores, desc: SlamConstrainDesc, prompt, prompt_len, new=None, done=None, eos_ids=None,
@@ -508,7 +395,7 @@ def constrain_scores(logits, scores, desc: SlamConstrainDesc, prompt, prompt_len
                                              _ptr(begin_ids), _ptr(seq_tokens), _ptr(seq_offsets),
                                              stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_constrain_scores failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_constrain_scores failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def token_logprobs_workspace_bytes(B: int, vocab: int) -> int:
@@ -525,7 +412,7 @@ def token_logprobs(logits, tokens, out, column: int, ws, done=None, finished=Non
                                            out.stride(0), int(column), _ptr(ws), ws.numel() * ws.element_size(),
                                            stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_token_logprobs failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_token_logprobs failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def cfg_workspace_bytes(B: int, vocab: int) -> int:
@@ -543,7 +430,7 @@ def cfg_scores(logits, guidance_scale: float, scores, ws, stream: Optional[int] 
     rc = load_library().slam_cfg_scores(_ptr(logits), B2 // 2, V, float(guidance_scale), _ptr(scores), _ptr(ws),
                                        ws.numel() * ws.element_size(), stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_cfg_scores failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_cfg_scores failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def cfg_mirror_tokens(next_ids, stream: Optional[int] = None):
@@ -553,10 +440,10 @@ def cfg_mirror_tokens(next_ids, stream: Optional[int] = None):
         raise ValueError(f"cfg_mirror_tokens: a contiguous int64 tensor of 2 B entries (got {n})")
     rc = load_library().slam_cfg_mirror_tokens(_ptr(next_ids), n // 2, stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_cfg_mirror_tokens failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_cfg_mirror_tokens failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
-SCORE_CHUNK = 512  # SLAM_SCORE_CHUNK: vocabulary columns per chunk of slam_op_score_rows
+SCORE_CHUNK = _DEFINES["SLAM_SCORE_CHUNK"]  # vocabulary columns per chunk of slam_op_score_rows
 
 
 def score_rows_workspace_bytes(M: int, vocab: int) -> int:
@@ -578,7 +465,7 @@ def score_rows(X, W, targets, lp, argmax=None, colmask=None, ws=None, stream: Op
                                           _ptr(ws), ws.numel() * ws.element_size(),
                                           stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_op_score_rows failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_op_score_rows failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
     return ws
 
 
@@ -609,7 +496,7 @@ def unpad_pack(ids, labels, lens, B: int, T: int, M_packed: int, pad_id: int, sc
                                            _ptr(scratch), scratch.numel() * scratch.element_size(),
                                            stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_op_unpad_pack failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_op_unpad_pack failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def unpad_pack_spans(ids, labels, starts, lens, B: int, T: int, M_packed: int, pad_id: int, scratch,
@@ -621,7 +508,7 @@ def unpad_pack_spans(ids, labels, starts, lens, B: int, T: int, M_packed: int, p
                                                  scratch.numel() * scratch.element_size(),
                                                  stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_op_unpad_pack_spans failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_op_unpad_pack_spans failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 def unpad_logits_spans(src, dst, off, starts, B: int, T: int, M_packed: int, stream: Optional[int] = None):
@@ -631,7 +518,7 @@ def unpad_logits_spans(src, dst, off, starts, B: int, T: int, M_packed: int, str
                                                    _ptr(starts), int(B), int(T), int(M_packed),
                                                    stream if stream is not None else current_stream_ptr())
     if rc != 0:
-        raise EngineError(f"slam_op_unpad_logits_spans failed ({rc})" + (": invalid argument" if rc == -1 else ""))
+        raise EngineError(f"slam_op_unpad_logits_spans failed ({rc})" + (": invalid argument" if rc == EINVAL else ""))
 
 
 @dataclass
@@ -1118,14 +1005,14 @@ class Engine:
     @staticmethod
     def comm_unique_id() -> bytes:
         """128 bytes from ncclGetUniqueId (rank 0 calls this and ships them to every rank)."""
-        buf = C.create_string_buffer(128)
-        rc = load_library().slam_comm_unique_id(buf, 128)
+        buf = C.create_string_buffer(COMM_ID_BYTES)
+        rc = load_library().slam_comm_unique_id(buf, COMM_ID_BYTES)
         if rc != 0:
-            raise RuntimeError(f"slam_comm_unique_id failed with {rc}" + (" (librccl.so.1 not found)" if rc == -4 else ""))
+            raise RuntimeError(f"slam_comm_unique_id failed with {rc}" + (" (librccl.so.1 not found)" if rc == EUNSUPPORTED else ""))
         return buf.raw
 
     def comm_init(self, unique_id: bytes, rank: int, world: int):
-        self._ck(self.lib.slam_comm_init(self.h, C.create_string_buffer(unique_id, 128), int(rank), int(world)))
+        self._ck(self.lib.slam_comm_init(self.h, C.create_string_buffer(unique_id, COMM_ID_BYTES), int(rank), int(world)))
 
     def comm_destroy(self):
         self._ck(self.lib.slam_comm_destroy(self.h))

@@ -16,6 +16,65 @@ def test_library_exports_every_declared_symbol():
     assert sorted(lib._slam_signatures) == names
 
 
+def _type_name(t):
+    return "void" if t is None else "BUCKET_CB" if t is E.BUCKET_CB else t.__name__
+
+
+def test_derived_signatures_equal_the_hand_written_table():
+    """The bindings read from include/slam_engine.h equal, entry for entry, the table load_library used to restate by hand:
+    tests/golden/abi_signatures.json is that table's _slam_signatures (ctypes class names), frozen when the table was deleted.
+    It proves that deletion and is no second source of truth: a pull request that changes the header regenerates it from
+    lib._slam_signatures with _type_name above."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "abi_signatures.json")) as f:
+        frozen = json.load(f)
+    got = {n: [_type_name(r), [_type_name(a) for a in args]] for n, (r, args) in E.load_library()._slam_signatures.items()}
+    assert len(frozen) == 177 and sorted(got) == sorted(frozen)
+    for n in frozen:
+        assert got[n] == frozen[n], n
+    # the override table holds the functions with a typed scalar pointer (the host out-parameters) and nothing else
+    typed = {n for n, (_, args) in frozen.items() if any(a.startswith("LP_c_") and a != "LP_c_void_p" for a in args)}
+    assert typed == set(E._HOST_OUT) and len(typed) == 6
+
+
+def test_header_reader_on_synthetic_headers():
+    import pytest
+    # a prototype over three lines; a comment and the callback typedef that only look like functions; void and struct pointers
+    fns, defines, structs = E._parse_header(
+        "#ifndef X_H\n#define X_H\n#define SLAM_A 7\n#define SLAM_B (-3)   /* slam_no( */\n#define SLAM_NOT_INT 1.5\n"
+        "/* int slam_foo(int x); */\ntypedef struct SlamEngine SlamEngine;\n"
+        "typedef void (*slam_bucket_cb)(void* user, int64_t offset, int64_t count);\n"
+        "typedef struct SlamPair { int64_t a, b; char tag[8]; float* p; } SlamPair;\n"
+        "const char* slam_three(SlamEngine* h, const SlamWarpDesc* w,\n     const int64_t ids[],\n"
+        "     slam_bucket_cb cb, SlamEngine** out, const SlamPair* unmirrored, size_t n);\n"
+        "void slam_none(void);\n#endif\n")
+    assert fns == {"slam_three": (C.c_char_p, [C.c_void_p, C.POINTER(E.SlamWarpDesc), C.c_void_p, E.BUCKET_CB, C.POINTER(C.c_void_p),
+                                               C.c_void_p, C.c_size_t]),
+                   "slam_none": (None, [])}
+    assert defines == {"SLAM_A": 7, "SLAM_B": -3}
+    assert structs == {"SlamPair": [("a", C.c_int64), ("b", C.c_int64), ("tag", C.c_char * 8), ("p", C.c_void_p)]}
+    # a type the rule does not know is an error that names the function, never a default
+    with pytest.raises(TypeError, match="slam_bad, parameter 1.*'uint16_t'"):
+        E._parse_header("int slam_ok(int a);\nint slam_bad(int a, uint16_t b);\n")
+    with pytest.raises(TypeError, match="slam_worse, return type"):
+        E._parse_header("long slam_worse(int a);\n")
+    with pytest.raises(TypeError, match="slam_two_words, parameter 0"):
+        E._parse_header("int slam_two_words(unsigned int a);\n")
+    with pytest.raises(TypeError, match="cannot read"):
+        E._parse_header("int slam_fnptr(void (*cb)(int));\n")
+
+
+def test_struct_mirrors_match_the_header():
+    """Every struct of include/slam_engine.h with a body, parsed by the rule that types the functions, is mirrored in engine.py
+    by a ctypes.Structure of the same field names, order and types (arrays as type * n)."""
+    assert len(E._STRUCTS) == 8
+    for name, fields in E._STRUCTS.items():
+        cls = getattr(E, name)
+        assert issubclass(cls, C.Structure) and list(cls._fields_) == fields, name
+    mirrors = {n for n, v in vars(E).items() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    assert mirrors == set(E._STRUCTS)
+
+
 def _defined_dynamic_symbols(path):
     """Names in the dynamic symbol table of `path` that the library itself defines: nm -D, or ROCm's llvm-readelf."""
     import shutil
