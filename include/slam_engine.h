@@ -365,8 +365,17 @@ int slam_bind_kv_cache_ex(SlamEngine* h, void* cache, size_t bytes, int32_t max_
  *   over prefix splits, then suffix splits, in split order: no atomics, bit-identical run to run. Logits differ from the
  *   unshared path's by rounding only. SLAM_ESTATE when the appended tokens would pass `capacity`; SLAM_ENOMEM when the logits
  *   buffer cannot hold one split of each part.
- * Leaving the mode: slam_prefill, slam_bind_kv_cache*, slam_bind_kv_prefix and slam_prefill_prefix. In the mode slam_extend,
- *   slam_extend_score, slam_extend_logits, slam_kv_repeat and slam_kv_rewind return SLAM_ESTATE with a message. */
+ * slam_extend_score and slam_extend_logits in the shared mode: the signatures, the outputs' contracts and everything but the
+ *   attention are unchanged, and lens stays absolute (RoPE positions, targets, row statistics and the last-token head read it as
+ *   they do outside the mode). Token t < new_lens[r] of row r goes to index lens[r] - plen[r / n] + t of the ordinary cache (the
+ *   unshared scatter launch over shifted bases), and the attention is ONE launch per layer with no partials: a block of 16 chunk
+ *   tokens x one row x one KV head walks the prompt's keys k < plen from the store (no causal mask) and then each row's own keys 0 .. lens[r] - plen + t from the cache (causal), softmax state in
+ *   registers across both, on v_mfma_f32_16x16x32_bf16, P rounded to bf16. No atomics, bit-identical run to run; results differ
+ *   from the unshared calls' by rounding only. Neither call writes the prompt store. SLAM_ESTATE when the appended tokens would
+ *   pass `capacity`: (tokens appended since slam_kv_share) + T <= capacity, as for slam_decode_step.
+ * Leaving the mode: slam_prefill, slam_bind_kv_cache*, slam_bind_kv_prefix and slam_prefill_prefix. In the mode slam_extend
+ *   (a sequence continues with slam_decode_step; slam_extend_score returns the same last-token logits), slam_kv_repeat and
+ *   slam_kv_rewind return SLAM_ESTATE with a message. */
 size_t slam_kv_prefix_bytes(SlamEngine* h, int32_t max_prompts, int32_t prefix_capacity);
 int slam_bind_kv_prefix(SlamEngine* h, void* buf, size_t bytes, int32_t max_prompts, int32_t prefix_capacity);
 int slam_prefill_prefix(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t B, int32_t T, float* logits_out,

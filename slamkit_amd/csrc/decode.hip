@@ -666,14 +666,20 @@ int attn_extend_chunk(int B, int T, int nH, int nKV, int head_dim, int kv_bound,
   return chunk;
 }
 
+int kv_extend_scatter(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, const int* base_lens, const int* new_lens, int B, int T, int nH,
+                      int nKV, int head_dim, int cap, int kv_bound, hipStream_t st) {
+  const size_t n = (size_t)T * (2 * nKV * head_dim / 8);
+  kv_extend_scatter_kernel<<<dim3(nblk(n, 256), B), 256, 0, st>>>(qkv, kc, vc, base_lens, new_lens, T, nH, nKV, head_dim, cap,
+                                                                  kv_bound);
+  return (int)hipGetLastError();
+}
+
 int attn_extend(const bf16_t* qkv, const int* base_lens, const int* new_lens, bf16_t* kc, bf16_t* vc, int cap, int B, int T,
                 int nH, int nKV, int head_dim, int kv_bound, bf16_t* o, float* part, size_t part_bytes, hipStream_t st) {
   int chunk, ns;
   float* pp;
   if (int r = attn_extend_plan(qkv, kc, vc, o, part, part_bytes, cap, B, T, nH, nKV, head_dim, kv_bound, &chunk, &ns, &pp)) return r;
-  const size_t n = (size_t)T * (2 * nKV * head_dim / 8);
-  kv_extend_scatter_kernel<<<dim3(nblk(n, 256), B), 256, 0, st>>>(qkv, kc, vc, base_lens, new_lens, T, nH, nKV, head_dim, cap,
-                                                                  kv_bound);
+  if (int r = kv_extend_scatter(qkv, kc, vc, base_lens, new_lens, B, T, nH, nKV, head_dim, cap, kv_bound, st)) return r;
   return attn_extend_launch<false>(qkv, base_lens, new_lens, kc, vc, nullptr, nullptr, cap, B, T, nH, nKV, head_dim, kv_bound, o, pp,
                                    chunk, ns, st);
 }

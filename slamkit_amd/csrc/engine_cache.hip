@@ -86,9 +86,13 @@ int cache_attn_decode(SlamEngine* h, int l, const float* qkvf, const bf16_t* bia
   return attn_decode(qkvf, bias, h->cosb, h->sinb, h->cosq, h->sinq, lens, kv_k(h, l), kv_v(h, l), h->kv_cap, B, d.n_heads,
                      d.n_kv_heads, d.head_dim, h->kv_hi + 1, o, (float*)h->logits, part_bytes, st);
 }
-int cache_attn_extend(SlamEngine* h, int l, const bf16_t* qkv, const int* lens, const int* new_lens, int B, int T, int kv_bound,
-                      bf16_t* o, size_t part_bytes, hipStream_t st) {
+// shared mode: lens are absolute, bases the rows' shifted bases (extend_common), kv_bound the bound of the keys behind the prompts
+int cache_attn_extend(SlamEngine* h, int l, const bf16_t* qkv, const int* lens, const int* new_lens, const int* bases, int B, int T,
+                      int kv_bound, bf16_t* o, size_t part_bytes, hipStream_t st) {
   const SlamModelDesc& d = h->d;
+  if (h->kv_shared)
+    return attn_extend_shared(qkv, lens, new_lens, bases, h->kvp_lens, h->kv_n, kvp_kv(h, l, 0), kvp_kv(h, l, 1), h->kvp_cap, h->kvp_T,
+                              kv_k(h, l), kv_v(h, l), h->kv_cap, kv_bound, B / h->kv_n, T, d.n_heads, d.n_kv_heads, d.head_dim, o, st);
   if (h->kv_dtype == SLAM_KV_FP8_E4M3)
     return attn_extend_fp8(qkv, lens, new_lens, kv8_codes(h, l, 0), kv8_codes(h, l, 1), kv8_exps(h, l, 0), kv8_exps(h, l, 1),
                            h->kv_cap, B, T, d.n_heads, d.n_kv_heads, d.head_dim, kv_bound, o, (float*)h->logits, part_bytes, st);
@@ -107,13 +111,17 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
-  if (h->kv_shared) return h->fail(SLAM_ESTATE, "slam_extend* in the shared-prompt mode: prefill again to leave it");
+  // shared mode: the two scoring calls run (two-region chunk attention); a sequence continues with slam_decode_step
+  if (h->kv_shared && mode == EXT_LAST) return h->fail(SLAM_ESTATE, "slam_extend* in the shared-prompt mode: prefill again to leave it");
   if ((int64_t)B * T > h->max_tokens) return h->fail(SLAM_ENOMEM, "B*T exceeds bound workspace tokens");
   if ((int64_t)2 * B > h->max_tokens) return h->fail(SLAM_ENOMEM, "extend needs a workspace of at least 2 B tokens");
-  if ((int64_t)(h->kv_ready ? h->kv_hi : 0) + T > h->kv_cap) return h->fail(SLAM_ESTATE, "extend past the KV cache capacity");
+  if ((int64_t)(h->kv_ready ? h->kv_hi - (h->kv_shared ? h->kvp_T : 0) : 0) + T > h->kv_cap)
+    return h->fail(SLAM_ESTATE, "extend past the KV cache capacity");
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_extend needs a slam_prefill into the bound cache first");
   if (B != h->kv_B) return h->fail(SLAM_EINVAL, "extend batch differs from the decode batch");
   const SlamModelDesc& d = h->d;
+  if (h->kv_shared && (size_t)B * T * sizeof(int64_t) + (size_t)B * sizeof(int) > (size_t)h->max_tokens * d.hidden * sizeof(bf16_t))
+    return h->fail(SLAM_ENOMEM, "positions and shifted bases exceed their scratch buffer");
   if (score && score_rows_workspace_bytes(B * T, d.vocab) > (size_t)h->max_tokens * h->vpad * sizeof(bf16_t))
     return h->fail(SLAM_ENOMEM, "chunk partials exceed the logits buffer");
   hipStream_t st = (hipStream_t)stream;
@@ -127,13 +135,16 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
   CK(join_params(h, st));
   // scratch in buffers only backward and the loss read: the tokens' int64 positions (dh_a), attention split partials and,
   // behind the layer loop, the fp32 logits of all B rows (the logits buffer: 2 B <= workspace tokens covers 4 B vocab bytes)
+  // shared mode: behind the positions, the rows' shifted bases (int32 [B]) - where the chunk's keys go in the ordinary cache
   int64_t* pos = (int64_t*)h->dh_a;
+  int* bases = (int*)(pos + (size_t)B * T);
   const float qscale = 1.44269504088896340736f / sqrtf((float)hd);
   CK(extend_positions(lens, pos, B, T, st));
   CK(rope_table(pos, M, T, hd, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
   CK(embed_fwd(ids, P + h->off_embed, h->hs[0], M, H, d.vocab, st));
   const size_t part_bytes = (size_t)h->max_tokens * h->vpad * sizeof(bf16_t);
-  const int kv_bound = h->kv_hi + T;
+  const int kv_bound = h->kv_hi - (h->kv_shared ? h->kvp_T : 0) + T;
+  if (h->kv_shared) CK(shifted_bases(lens, h->kvp_lens, h->kv_n, bases, B, st));
   const bool q3 = h->arch == 3;  // Qwen3: no bias, and the per-head norm sits between the projection and the rotation
   const bool fused_rope = !q3 && M > SKINNY_MAX_M && hd == 64 && (H % 64 == 0) && (h->QKV % 128 == 0);
   for (int l = 0; l < L; ++l) {
@@ -147,7 +158,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
       if (q3) CK(qknorm_rope_fwd(a.qkv, h->QKV, M, nH, nKV, hd, P + o.q_norm, P + o.k_norm, h->cosb, h->sinb, h->cosq, h->sinq, d.rms_eps, nullptr, nullptr, st));
       else CK(rope_apply(a.qkv, h->QKV, M, nH + nKV, hd, h->cosb, h->sinb, 0, st, nH, qscale));
     }
-    CK(cache_attn_extend(h, l, a.qkv, lens, new_lens, B, T, kv_bound, a.o, part_bytes, st));
+    CK(cache_attn_extend(h, l, a.qkv, lens, new_lens, bases, B, T, kv_bound, a.o, part_bytes, st));
     CK(cached_mlp(h, l, M, st));
   }
   if (score) {

@@ -411,6 +411,9 @@ size_t attn_extend_part_bytes(int B, int T, int nH, int head_dim, int ns);
 int attn_extend_chunk(int B, int T, int nH, int nKV, int head_dim, int kv_bound, size_t part_bytes);
 int attn_extend(const bf16_t* qkv, const int* base_lens, const int* new_lens, bf16_t* kc, bf16_t* vc, int cap, int B, int T,
                 int nH, int nKV, int head_dim, int kv_bound, bf16_t* o, float* part, size_t part_bytes, hipStream_t st);
+// attn_extend's first launch alone: the chunk's K / V columns of the real tokens into cache rows base_lens[b] + t
+int kv_extend_scatter(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, const int* base_lens, const int* new_lens, int B, int T, int nH,
+                      int nKV, int head_dim, int cap, int kv_bound, hipStream_t st);
 // pos[b T + t] = lens[b] + t
 int extend_positions(const int* lens, int64_t* pos, int B, int T, hipStream_t st);
 // dst[b] = src[b] (fp32 [B][vocab]) and lens[b] += new_lens[b] for the rows with new_lens[b] > 0; the others keep their bits
@@ -440,6 +443,15 @@ int attn_decode_shared(const float* qkv, const bf16_t* bias, const float* cs, co
                        const int* lens, const int* plens, int n, const bf16_t* pk, const bf16_t* pv, int pcap, int pbound, bf16_t* kc,
                        bf16_t* vc, int cap, int sbound, int P, int nH, int nKV, int head_dim, bf16_t* o, float* part,
                        size_t part_bytes, hipStream_t st);
+// Chunk attention in the shared mode (slam_extend_score / slam_extend_logits): attn_extend's contract over the R = P n rows with
+// each row's keys in two places. qkv, new_lens, o as attn_extend takes them; lens[r] the row's ABSOLUTE key count before the chunk.
+// bases[r] = max(lens[r] - plens[r / n], 0) (shifted_bases, once per chunk): token t < new_lens[r] goes to index bases[r] + t of
+// kc / vc (the unshared scatter launch), then ONE launch attends keys k < plens[r / n] in the store and the keys behind them in
+// the cache - no partials, no combine. pbound >= max(plens), sbound >= max(bases[r] + new_lens[r]) (host bounds, <= pcap / cap).
+int shifted_bases(const int* lens, const int* plens, int n, int* bases, int R, hipStream_t st);
+int attn_extend_shared(const bf16_t* qkv, const int* lens, const int* new_lens, const int* bases, const int* plens, int n,
+                       const bf16_t* pk, const bf16_t* pv, int pcap, int pbound, bf16_t* kc, bf16_t* vc, int cap, int sbound, int P,
+                       int T, int nH, int nKV, int head_dim, bf16_t* o, hipStream_t st);
 // lens[b] and the nullable fp32 logits row b -> rows b n .. b n + n - 1 in place (kv_repeat's launch scheme, no key copied)
 int kv_share_fan(int* lens, float* logits, int B, int n, int vocab, hipStream_t st);
 int lens_copy(const int* src, int* dst, int B, hipStream_t st);

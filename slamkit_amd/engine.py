@@ -758,14 +758,16 @@ class Engine:
         """slam_extend_score: slam_extend (same cache, lens and logits_out bits) that also scores the chunk. lp_out fp32 [B, T]:
         column t, 1 <= t < new_lens[b], = the log-prob of ids[b, t] given the cache and ids[b, :t]; columns at or beyond
         max(1, new_lens[b]) = 0; column 0 is left to the caller (token_logprobs on the logits the rows held before the call).
-        argmax_out int64 [B, T], optional: the greedy next token after position t (t < new_lens[b]), else -1."""
+        argmax_out int64 [B, T], optional: the greedy next token after position t (t < new_lens[b]), else -1. Legal after
+        kv_share: lens stay absolute, the chunk's keys go behind each row's own keys, the prompt's are read from the store."""
         self._ck(self.lib.slam_extend_score(self.h, _ptr(ids), _ptr(new_lens), _ptr(lens), B, T, _ptr(logits_out),
                                             _ptr(lp_out), _ptr(argmax_out),
                                             stream if stream is not None else current_stream_ptr()))
 
     def extend_logits(self, ids, new_lens, lens, B: int, T: int, logits_all, stream: Optional[int] = None):
         """slam_extend_logits: slam_extend (same cache and lens bits) that writes the fp32 logits of EVERY real chunk position:
-        logits_all fp32 [B, T, vocab]; rows t >= new_lens[b] keep their bits. Only enqueues work."""
+        logits_all fp32 [B, T, vocab]; rows t >= new_lens[b] keep their bits. Only enqueues work. Legal after kv_share, as
+        extend_score is."""
         self._ck(self.lib.slam_extend_logits(self.h, _ptr(ids), _ptr(new_lens), _ptr(lens), B, T, _ptr(logits_all),
                                              stream if stream is not None else current_stream_ptr()))
 

@@ -126,7 +126,8 @@ slam_kv_share(n) in the place of slam_kv_repeat; the decode loop is the same cal
 - are the unshared call's bits; later logits differ by rounding only (the prompt part of the attention runs on the matrix pipe),
 so a token at a near-tie may differ, as under `prefill_chunk`. Both engine samplers, the torch sampler, the history bans,
 `return_logprobs`, the FP8 decode weights and guidance follow as without it. ValueError: together with
-kv_cache_dtype="fp8_e4m3", prefill_chunk, assistant_model or prompt_lookup_num_tokens. score_continuations does not take it.
+kv_cache_dtype="fp8_e4m3", prefill_chunk, assistant_model or prompt_lookup_num_tokens. score_continuations takes it per call
+(below).
 
 score_continuations
 -------------------
@@ -146,6 +147,14 @@ score_chunk, 2 B n) tokens, and no [B n, T + T_c] batch is formed. Inside the lo
 torch op between them (every block's operands are built before it). `ignore_tokens` sets the logit mask (those columns count as
 -inf) for the call and clears it afterwards. Known exception to the no-torch-op rule: with `ignore_tokens`, one in-place fill
 of those columns of the last-token logits follows each block, because slam_token_logprobs reads raw logits and takes no mask.
+
+`share_prompt_cache=True` (this call's argument only: the model attribute of that name keeps meaning generate) scores on the
+shared-prompt cache: a prompt store of B x roundup(T, 64) positions filled by slam_prefill_prefix, an ordinary cache of B n x
+roundup(T_c, 64) positions for the continuations alone, slam_kv_share(n) in the place of slam_kv_repeat, and the same block loop:
+in the mode slam_extend_score's attention is one two-region launch per layer (the prompt's keys from the store, then the
+row's own keys). B (roundup(T, 64) + n roundup(T_c, 64)) positions are bound, not B n roundup(T + T_c, 64),
+and no key is copied. Column 0 is the unshared call's bits (the same prefill); the rest differs by rounding only. n == 1 is
+legal. ValueError, before any engine call: together with an FP8 cache (this call's kv_cache_dtype or the model's) or prefill_chunk.
 """
 import math
 import types
@@ -902,10 +911,16 @@ def generate(model, gc, extra: dict, args: dict):
 
 
 def score_continuations(model, input_ids, attention_mask, continuations, continuation_lengths, num_per_prompt, score_chunk,
-                        prefill_chunk, return_argmax, ignore_tokens, kv_cache_dtype=None):
+                        prefill_chunk, return_argmax, ignore_tokens, kv_cache_dtype=None, share_prompt_cache=False):
     """UnitLM.score_continuations (the module's documentation has the contract)."""
     if kv_cache_dtype is not None:
         E.kv_dtype_code(kv_cache_dtype)
+    share = bool(share_prompt_cache)
+    if share:  # bf16, one-shot prefill: what slam_kv_share covers
+        if (kv_cache_dtype if kv_cache_dtype is not None else getattr(model, "kv_cache_dtype", "bfloat16")) == "fp8_e4m3":
+            raise ValueError("share_prompt_cache does not combine with kv_cache_dtype='fp8_e4m3' (the prompt store is bf16)")
+        if prefill_chunk is not None:
+            raise ValueError("share_prompt_cache does not combine with prefill_chunk (the prompt store is filled in one pass)")
     n = num_per_prompt
     if isinstance(n, bool) or not isinstance(n, int) or n < 1:
         raise ValueError(f"num_per_prompt must be an int >= 1 (got {n!r})")
@@ -938,9 +953,11 @@ def score_continuations(model, input_ids, attention_mask, continuations, continu
     if T + Tc > model.config.max_tokens:
         raise ValueError(f"prompt length {T} + continuation length {Tc} exceeds max_tokens {model.config.max_tokens}")
     C = Tc if score_chunk is None else min(score_chunk, Tc)
-    cap = -(-(T + Tc) // 64) * 64
     model._ensure_workspace(max(B * (T if prefill_chunk is None else min(T, prefill_chunk)), BN * C, 2 * BN))
-    raw = _bind_cache(model, BN, cap, kv_cache_dtype)  # noqa: F841 - alive until the call returns
+    if share:  # the prompts once in the store; the cache holds the continuations alone
+        raw = (_bind_prefix(model, B, -(-T // 64) * 64), _bind_cache(model, BN, -(-Tc // 64) * 64, kv_cache_dtype))  # noqa: F841
+    else:
+        raw = _bind_cache(model, BN, -(-(T + Tc) // 64) * 64, kv_cache_dtype)  # noqa: F841 - alive until the call returns
     V = model.config.vocab_size
     logits = torch.empty(BN, V, dtype=torch.float32, device=dev)
     if n > 1:
@@ -970,8 +987,10 @@ def score_continuations(model, input_ids, attention_mask, continuations, continu
         model.engine.set_logit_mask(lmask)
     model._hold = (ids, lens, blocks)
     try:
-        _prefill(model, ids, lens, B, T, logits, prefill_chunk)
-        if n > 1:
+        _prefill(model, ids, lens, B, T, logits, prefill_chunk, share)
+        if share:
+            model.engine.kv_share(n, lens, logits)  # n == 1 too: it enters the mode
+        elif n > 1:
             model.engine.kv_repeat(n, lens, logits)
         if ign is not None:
             logits.index_fill_(1, ign, float("-inf"))
@@ -988,6 +1007,8 @@ def score_continuations(model, input_ids, attention_mask, continuations, continu
         if lmask is not None:
             torch.cuda.current_stream(dev).synchronize()  # the kernels read the mask: keep it alive until done
             model.engine.set_logit_mask(None)
+    if share:
+        model.engine.bind_kv_prefix(None)  # the store dies with this call: leave the shared mode with it
     lp = torch.cat([b[5] for b in blocks], 1) if len(blocks) > 1 else blocks[0][5]
     if not return_argmax:
         return lp

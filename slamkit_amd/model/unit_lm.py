@@ -1269,12 +1269,15 @@ class UnitLM(TokenLM):
     def score_continuations(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, continuations=None,
                             continuation_lengths=None, num_per_prompt: int = 1, score_chunk: Optional[int] = None,
                             prefill_chunk: Optional[int] = None, return_argmax: bool = False,
-                            ignore_tokens: Optional[List[int]] = None, kv_cache_dtype: Optional[str] = None):
+                            ignore_tokens: Optional[List[int]] = None, kv_cache_dtype: Optional[str] = None,
+                            share_prompt_cache: bool = False):
         """This model's log-probs (and greedy choices) of given continuations of the prompts, through the KV cache: the
-        scoring half of generate(num_return_sequences=n, return_logprobs=True). The contract is in generation.py."""
+        scoring half of generate(num_return_sequences=n, return_logprobs=True). The contract is in generation.py.
+        share_prompt_cache (per call only; the model attribute of that name is generate's): the num_per_prompt rows of a prompt
+        attend one copy of its keys (bf16 cache, one-shot prefill)."""
         return generation.score_continuations(self, input_ids, attention_mask, continuations, continuation_lengths,
                                               num_per_prompt, score_chunk, prefill_chunk, return_argmax, ignore_tokens,
-                                              kv_cache_dtype)
+                                              kv_cache_dtype, share_prompt_cache)
 
     # ---- checkpoints (HF layout) ------------------------------------------------------------------
     def save_pretrained(self, save_directory: str, dtype=torch.bfloat16):

@@ -67,6 +67,13 @@ warm-up steps per block: one `share_prompt` line per (model, B, T, n) with the m
 `repeat_over_share` (median of the per-block ratios, `_minmax`) and the bytes each mode binds for `--steps` new tokens
 (`repeat_cache_MB`; `share_cache_MB` = prompt store + suffix cache). The prefix / suffix / combine durations come from a
 `rocprofv3 --kernel-trace --stats` run of this option, read by --trace-summary.
+--share-score N[,N..] [--models slam] [--batches 1,8] [--prompts 256,1024,2048] [--cont 150] [--score-chunk 64] [--blocks 3]:
+the engine calls of score_continuations(num_per_prompt=N) over B prompts of T tokens and B x N continuations of --cont tokens,
+unshared (slam_prefill + slam_kv_repeat, `repeat_*`) and shared (slam_prefill_prefix + slam_kv_share, `share_*`), as alternating
+blocks within this process after one untimed pass of each: `*_score_ms` = device events around the slam_extend_score loop,
+`*_setup_ms` = around the prefill and the fan-out before it (where the unshared route pays its key copy); one `share_score` line
+per (model, B, T, n) with the medians over the blocks, the per-block lists, `repeat_over_share` of setup + score, and the bytes
+each route binds. The kernels' own durations come from a `rocprofv3 --kernel-trace --stats` run of this option.
 A second Slam-358M run at B = 96 (above the 64-row limit of the weight-streaming kernel: its bf16 projections take the tiled
 GEMM) gives the decode step on the other side of the kernel selection.
 """
@@ -277,6 +284,69 @@ def share_bench(name, batches, prompts, ns, steps, blocks):
                                       repeat_over_share=round(statistics.median(ratios), 3),
                                       repeat_over_share_minmax=[round(min(ratios), 3), round(max(ratios), 3)],
                                       repeat_cache_MB=round(sizes["repeat"] / 1e6, 1), share_cache_MB=round(sizes["share"] / 1e6, 1))), flush=True)
+                eng.bind_kv_prefix(None)
+                del bufs, logits
+                torch.cuda.empty_cache()
+    del m
+    torch.cuda.empty_cache()
+
+
+def score_bench(name, batches, prompts, ns, Tc, chunk, blocks):
+    """score_continuations' engine calls behind slam_kv_repeat and behind slam_kv_share (two-region chunk attention)."""
+    import torch
+    cap_c = 64 * -(-Tc // 64)
+    m = build(name, max(prompts) + cap_c)
+    dev, V, eng = m.device, m.config.vocab_size, m.engine
+    for B in batches:
+        for T in prompts:
+            g = torch.Generator(device=dev).manual_seed(0)
+            ids = torch.randint(2, V, (B, T), device=dev, generator=g)
+            for n in ns:
+                rows, cap_p, cap_u = B * n, 64 * -(-T // 64), 64 * -(-(T + Tc) // 64)
+                m._ensure_workspace(max(B * T, rows * chunk, 2 * rows))
+                sizes = dict(repeat=eng.kv_cache_bytes(rows, cap_u), share=eng.kv_prefix_bytes(B, cap_p) + eng.kv_cache_bytes(rows, cap_c))
+                bufs = [torch.empty(sizes["repeat"], dtype=torch.uint8, device=dev),
+                        torch.empty(eng.kv_prefix_bytes(B, cap_p), dtype=torch.uint8, device=dev)]
+                logits = torch.empty(rows, V, dtype=torch.float32, device=dev)
+                cont = torch.randint(2, V, (rows, Tc), device=dev, generator=g)
+                blks = [(cont[:, c0:c0 + chunk].contiguous(), min(chunk, Tc - c0)) for c0 in range(0, Tc, chunk)]
+                blks = [(b, w, torch.full((rows,), w, dtype=torch.int32, device=dev), torch.empty(rows, w, device=dev)) for b, w in blks]
+
+                def block(share):
+                    lens = torch.zeros(rows, dtype=torch.int32, device=dev)
+                    lens[:B] = T
+
+                    def setup():
+                        if share:
+                            eng.bind_kv_prefix(bufs[1], B, cap_p)
+                            eng.bind_kv_cache(bufs[0], rows, cap_c)
+                            eng.prefill_prefix(ids, lens, B, T, logits)
+                            eng.kv_share(n, lens, logits)
+                        else:
+                            eng.bind_kv_cache(bufs[0], rows, cap_u)
+                            eng.prefill(ids, lens, B, T, logits)
+                            eng.kv_repeat(n, lens, logits)
+
+                    def score():
+                        for b, w, nl, lp in blks:
+                            eng.extend_score(b, nl, lens, rows, w, logits, lp)
+                    return ev_ms(setup), ev_ms(score)
+
+                block(False), block(True)  # untimed: both routes warm
+                t = {"repeat": [], "share": []}
+                for _ in range(blocks):
+                    t["repeat"].append(block(False))
+                    t["share"].append(block(True))
+                ratios = [sum(a) / sum(b) for a, b in zip(t["repeat"], t["share"])]
+                out = dict(bench="share_score", model=name, B=B, T=T, n=n, cont=Tc, score_chunk=chunk, blocks=blocks)
+                for k in ("repeat", "share"):
+                    for i, part in enumerate(("setup", "score")):
+                        out[f"{k}_{part}_ms"] = round(statistics.median(x[i] for x in t[k]), 4)
+                        out[f"{k}_{part}_ms_all"] = [round(x[i], 4) for x in t[k]]
+                out.update(repeat_over_share=round(statistics.median(ratios), 3),
+                           repeat_over_share_minmax=[round(min(ratios), 3), round(max(ratios), 3)],
+                           repeat_cache_MB=round(sizes["repeat"] / 1e6, 1), share_cache_MB=round(sizes["share"] / 1e6, 1))
+                print(json.dumps(out), flush=True)
                 eng.bind_kv_prefix(None)
                 del bufs, logits
                 torch.cuda.empty_cache()
@@ -745,7 +815,12 @@ def main():
     ap.add_argument("--share-prompt", default=None,
                     help="N[,N..]: the decode step over B x N rows behind slam_kv_repeat and behind slam_kv_share, alternating blocks "
                          "(--batches, default 1,8; --prompts, default 256,1024,2048)")
-    ap.add_argument("--prompts", default="256,1024,2048", help="with --share-prompt: prompt lengths")
+    ap.add_argument("--share-score", default=None,
+                    help="N[,N..]: score_continuations' engine calls over B x N rows behind slam_kv_repeat and behind slam_kv_share, "
+                         "alternating blocks (--batches, default 1,8; --prompts; --cont; --score-chunk)")
+    ap.add_argument("--cont", type=int, default=150, help="with --share-score: continuation length")
+    ap.add_argument("--score-chunk", type=int, default=64, help="with --share-score: columns per slam_extend_score")
+    ap.add_argument("--prompts", default="256,1024,2048", help="with --share-prompt / --share-score: prompt lengths")
     ap.add_argument("--batches", default=None, help="with --decode-weights (default 1,8,64), --cfg (default 1,8,32) or --share-prompt (1,8)")
     ap.add_argument("--blocks", type=int, default=3, help="with --decode-weights: alternations per (model, batch)")
     ap.add_argument("--include-head", action="store_true", help="with --decode-weights fp8: FP8 codes for the LM head too")
@@ -759,6 +834,11 @@ def main():
         for name in a.models.split(","):
             share_bench(name, [int(b) for b in (a.batches or "1,8").split(",")], [int(t) for t in a.prompts.split(",")],
                         [int(n) for n in a.share_prompt.split(",")], min(a.steps, 60), a.blocks)
+        return
+    if a.share_score:
+        for name in a.models.split(","):
+            score_bench(name, [int(b) for b in (a.batches or "1,8").split(",")], [int(t) for t in a.prompts.split(",")],
+                        [int(n) for n in a.share_score.split(",")], a.cont, a.score_chunk, a.blocks)
         return
     if a.cfg:
         for name in a.models.split(","):
