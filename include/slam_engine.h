@@ -1158,6 +1158,42 @@ int slam_cast_params(SlamEngine* h, const float* master_f32, slam_stream_t strea
  * the rank, and a run resumed at step k repeats the uninterrupted one. With 0 every bit is what it was without the option.
  * "adamw_sr_seed" = any int64 (default 0): the seed, read as 64 unsigned bits.
  *
+ * "adamw_state8" = 0 | 1 (default 0; anything else is SLAM_EINVAL, "out of range"): 8-bit block-wise Adam moments. With 1,
+ * slam_adamw_step_bf16 and slam_adamw_step_bf16_moments read their two moment arguments as the allocations described here
+ * instead of bf16 arrays; with 0 every launch is what it was without the option. The format is this project's own (the idea
+ * of bitsandbytes' 8-bit optimizers: a block-wise maximum and a non-linear 256-entry code; no bit compatibility is claimed).
+ *   block      256 consecutive elements of the flat parameter buffer, N = slam_param_count; the last block may be short, and
+ *              a block may straddle two tensors (the flat AdamW kernels ignore tensor borders in the same way).
+ *   allocation per moment ONE buffer: uint8 codes[N], then, at the next multiple of 256 bytes, float absmax[ceil(N / 256)]:
+ *              bytes = (N + 255) / 256 * 256 + 4 * ((N + 255) / 256)      (integer division; 256-byte aligned base)
+ *              Nothing behind codes[N] up to the absmax array, and nothing behind the absmax array, is read or written.
+ *              All zero bytes are the zero state.
+ *   exp_avg    code c = 128 s + k, s the sign bit, k = 0 .. 127: value 0 at k = 0, else 2^-((127 - k) / 8). k = 0 is
+ *              stored with s = 0.
+ *   exp_avg_sq code k = 0 .. 255: value 0 at k = 0, else 2^-((255 - k) / 8) (it holds squares: twice the range).
+ *              Both tables t[] are computed in float64 and rounded to fp32 once.
+ *   quantise   absmax = the maximum of |x| over the block; absmax == 0 stores code 0 everywhere and divides nothing. Else
+ *              y = |x| / absmax (one IEEE fp32 division) and k = the number of fp32 midpoints mid[j] = (t[j] + t[j + 1]) / 2
+ *              with y > mid[j]: the nearest table value in the linear domain, a value ON a midpoint to the lower magnitude.
+ *              The codes are always round-to-nearest, whatever "adamw_sr" says.
+ *   dequantise t[k] * absmax (one fp32 multiply), the sign bit set exactly.
+ *   update     per element in fp32, m = deq(exp_avg), v = deq(exp_avg_sq), g = gradient * norm_out[1] read where the step reads
+ *              it today (the fp32 buffer, or the bf16 image after "grad_final_next" = 2): the expressions of the bf16-moment
+ *              kernels, in their order - m' = b1 m + (1 - b1) g under slam_adamw_step_bf16_moments, the lerp form
+ *              m' = m + (1 - b1) (g - m) under slam_adamw_step_bf16; v' = b2 v + (1 - b2) g g;
+ *              p' = p (1 - lr wd) - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps) - so a block's update IS an AdamW step started
+ *              from the dequantised state. The parameter moves by the UNQUANTISED m', v'; then m' and v' are quantised
+ *              against the new block maxima. slam_set_decay_mask, zero_grad and the clip coefficient act as they do without the
+ *              option. "adamw_sr" = 1 rounds the bf16 parameter store of slam_adamw_step_bf16 stochastically, as today (array 0
+ *              of slam_op_sr_round_bf16); the master's working copy keeps round-to-nearest.
+ *   images     one flat launch (a wave per state block), then the transposed weight images are refreshed by the pass
+ *              slam_refresh_transposed runs: the in-kernel 64 x 64 transpose of the other forms is NOT reproduced here, and
+ *              "fuse_adamw_t" and "overlap_adamw" do not apply to this form.
+ *   refused    slam_adamw_range_bf16 and slam_adamw_range_bf16_moments return SLAM_EINVAL while the option is 1: a shard cuts
+ *              a block. slam_adamw_step / slam_adamw_range (fp32 state) ignore the option, as they ignore "adamw_sr".
+ * A non-finite gradient makes its element's parameter non-finite as in every AdamW form; its block's stored moments are then
+ * unspecified.
+ *
  * "dropout_thr16" = 0 .. 65535 (default 0; anything else is SLAM_EINVAL, "out of range"; non-zero on a Qwen2 engine, arch 0, is
  * SLAM_EINVAL too): residual dropout of the OPT family (HF OPTDecoderLayer, `config.dropout`): behind out_proj (site 0) and
  * behind fc2 (site 1) of every layer, before the residual add. thr = round(p * 65536); q = thr / 65536 is the effective drop

@@ -681,6 +681,11 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
     h->adamw_sr = (int)value;
     return SLAM_OK;
   }
+  if (!strcmp(key, "adamw_state8") && h) {
+    if (value < 0 || value > 1) return h->fail(SLAM_EINVAL, "value out of range for option adamw_state8 (0 or 1)");
+    h->adamw_state8 = (int)value;
+    return SLAM_OK;
+  }
   if (!strcmp(key, "adamw_sr_seed") && h) { h->adamw_sr_seed = (uint64_t)value; return SLAM_OK; }
   if (!strcmp(key, "bwd_wgrad_stream") && h) { h->wgrad_stream = value != 0; return SLAM_OK; }
   if (!strcmp(key, "bwd_aux_side") && h) { h->aux_side = value != 0; return SLAM_OK; }

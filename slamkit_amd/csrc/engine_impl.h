@@ -103,6 +103,8 @@ struct SlamEngine {
   // follow from the seed, the step the caller passes and the element's index in the flat buffer
   int adamw_sr = 0;
   uint64_t adamw_sr_seed = 0;
+  // "adamw_state8": the bf16-moment entry points read their moment arguments as 8-bit block-wise allocations (kernels.h adamw_q8)
+  int adamw_state8 = 0;
   // slam_set_decay_mask: the tensors that take weight_decay = 0, as the sorted bounds of their merged ranges (kernels.h
   // AdamNoDecay). nd_host decides per parameter group where the optimizer walks the model (adamw_model); nd_dev - engine-owned
   // device memory, the same bounds + the sentinel - is what the flat and ranged kernels search. Empty / null: uniform decay.

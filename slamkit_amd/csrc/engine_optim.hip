@@ -66,6 +66,11 @@ static int adamw_any(SlamEngine* h, int mode, float* master, void* m, void* v, c
   a.master = master; a.m = m; a.v = v;
   // zeroing belongs to the fp32 accumulation buffer: the kernels cannot do it while they read the bf16 image
   if (a.g_bf16 && zero_grad) CK((int)hipMemsetAsync(h->grads, 0, (size_t)h->n_params * sizeof(float), st));
+  if (h->adamw_state8 && mode != 0) {  // m / v are 8-bit block-wise allocations: one flat launch, then the transposed images
+    a.nd.base = 0;
+    CK(adamw_q8(a, (size_t)h->n_params, st));
+    return slam_refresh_transposed(h, stream);
+  }
   if (!h->overlap_adamw || mode != 0) {
     if (fused) {
       CK(adamw_model(h, a, -1, st));
@@ -104,6 +109,8 @@ static int adamw_range_impl(SlamEngine* h, int mode, int64_t offset, int64_t cou
       (count & mask))
     return SLAM_EINVAL;
   if (!h->grads || !h->params) return h->fail(SLAM_ESTATE, "bind params first");
+  if (h->adamw_state8 && mode != 0)
+    return h->fail(SLAM_EINVAL, "adamw_state8 is on: a range cuts a 256-element state block (use slam_adamw_step_bf16 / _bf16_moments)");
   hipStream_t st = (hipStream_t)stream;
   CK(join_optimizer(h, st));
   h->w8_valid = false;

@@ -255,6 +255,12 @@ int adamw_flat(const AdamArgs& a, size_t n, hipStream_t st);
 int adamw_strided(const AdamArgs& a, size_t n, int batch, size_t stride, hipStream_t st);
 // `batch` same-shaped [R][C] matrices (64-multiples) at a constant stride, ALSO writing the transposed bf16 image params_t[C][R]
 int adamw_tiles(const AdamArgs& a, int R, int C, int batch, size_t batch_stride, hipStream_t st);
+// AdamW on 8-bit block-wise moments ("adamw_state8", include/slam_engine.h): n consecutive elements from element 0 of a state block
+// (n a multiple of 4), a.m / a.v = the two allocations of adam8_state_bytes(n) bytes: codes[n], then 256-byte aligned
+// float absmax[ceil(n / 256)]. Mode 1 (fp32 master) or 2 (the bf16 parameters are the state); sr rounds the bf16 parameters of mode 2
+// only, the codes never; nd as in adamw_flat. Does not write the transposed images.
+inline size_t adam8_state_bytes(size_t n) { return ((n + 255) & ~(size_t)255) + ((n + 255) / 256) * sizeof(float); }
+int adamw_q8(const AdamArgs& a, size_t n, hipStream_t st);
 // y[i] = the stochastic rounding of x[i] as the kernels above apply it to flat index index0 + i of array `which` (0 p, 1 m, 2 v)
 int sr_round_bf16(const float* x, bf16_t* y, size_t n, int64_t index0, uint64_t seed, int step, int which, hipStream_t st);
 // ---- Adafactor (adafactor.hip; the contract is in include/slam_engine.h: slam_adafactor_step) ---------------------------------

@@ -351,6 +351,124 @@ __global__ __launch_bounds__(256) void adamw_strided_kernel(float* __restrict__ 
     if (h.zero_grad) *reinterpret_cast<float4*>(g + idx) = make_float4(0, 0, 0, 0);
   }
 }
+// ---- AdamW on 8-bit block-wise moments ("adamw_state8"; the format and the rule are in include/slam_engine.h) ---------------------
+// A state block = 256 consecutive elements of the flat buffer = ONE WAVE: lane l owns elements 4 l .. 4 l + 3 of it, so a lane's
+// codes of a moment are one dword, its gradients and parameters one load each, and the block maximum that has to be known before
+// the first code can be stored is a wave-wide maximum of register values - nothing of a block ever goes through memory between the
+// arithmetic and the store. The 4 waves of a thread block share the code tables and their decision midpoints in LDS (3 KB, built by
+// the launch's first instructions from eight fp32 constants: no buffer to bind). The grid is persistent: 4 waves a thread block,
+// a fixed number of thread blocks per CU, each wave striding over the state blocks.
+// t[k] = 2^-((K - k) / 8) for k >= 1 as fp32(2^-(r / 8)) times an exact power of two: the float64 value rounded to fp32 once
+SLAM_DEVICE float q8_value(int j) {  // 2^-(j / 8), j >= 0
+  constexpr float mant[8] = {0x1.000000p+0f, 0x1.d5818ep-1f, 0x1.ae89fap-1f, 0x1.8ace54p-1f,
+                             0x1.6a09e6p-1f, 0x1.4bfdaep-1f, 0x1.306fe0p-1f, 0x1.172b84p-1f};
+  return mant[j & 7] * pow2i(-(j >> 3));
+}
+struct Q8Tables {
+  float tm[128], mm[128];  // exp_avg: values of k = 0 .. 127, midpoints (t[k] + t[k + 1]) / 2 of k = 0 .. 126 (+inf behind them)
+  float tv[256], mv[256];  // exp_avg_sq: k = 0 .. 255, midpoints of k = 0 .. 254
+};
+SLAM_DEVICE void q8_build_tables(Q8Tables& s) {
+  const int t = threadIdx.x;  // 256 threads
+  s.tv[t] = t ? q8_value(255 - t) : 0.f;
+  if (t < 128) s.tm[t] = t ? q8_value(127 - t) : 0.f;
+  __syncthreads();
+  s.mv[t] = t < 255 ? (s.tv[t] + s.tv[t + 1]) * 0.5f : __builtin_inff();
+  if (t < 128) s.mm[t] = t < 127 ? (s.tm[t] + s.tm[t + 1]) * 0.5f : __builtin_inff();
+  __syncthreads();
+}
+// the number of midpoints below y = the code of the nearest table value (a value ON a midpoint takes the lower code): STEPS
+// dependent LDS reads, no branch - every lane of the wave walks its own path through the table in lockstep
+template <int STEPS>
+SLAM_DEVICE uint32_t q8_code(const float* mid, float y) {
+  uint32_t k = 0;
+#pragma unroll
+  for (int s = 1 << (STEPS - 1); s > 0; s >>= 1) k += y > mid[k + s - 1] ? s : 0;
+  return k;
+}
+// max over the wave of v >= 0, in every lane: two quad permutes and two row mirrors (DPP) leave the row's maximum in each of its
+// 16 lanes, four lane reads join the rows - no LDS, and the result is wave-uniform. Every lane of the wave must be active.
+SLAM_DEVICE float q8_wave_max(float v) {
+#define Q8_DPP_MAX(ctrl) v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, true)))
+  Q8_DPP_MAX(0xB1);   // quad_perm [1, 0, 3, 2]
+  Q8_DPP_MAX(0x4E);   // quad_perm [2, 3, 0, 1]
+  Q8_DPP_MAX(0x141);  // row_half_mirror
+  Q8_DPP_MAX(0x140);  // row_mirror
+#undef Q8_DPP_MAX
+  const int b = __float_as_int(v);
+  return fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(b, 0)), __int_as_float(__builtin_amdgcn_readlane(b, 16))),
+               fmaxf(__int_as_float(__builtin_amdgcn_readlane(b, 32)), __int_as_float(__builtin_amdgcn_readlane(b, 48))));
+}
+SLAM_DEVICE size_t q8_absmax_offset(size_t n) { return (n + 255) & ~(size_t)255; }  // bytes: codes[n], then 256-byte aligned absmax[]
+// t[k] * absmax: one fp32 multiply that no later add may absorb
+SLAM_DEVICE float q8_deq(float t, float scale) {
+#pragma clang fp contract(off)
+  return t * scale;
+}
+// MASTER: fp32 master weights (p) with the bf16 working copy pb written from them, moment lines b1 m + (1 - b1) g; else the bf16
+// parameters pb are the state and the moment line is the lerp form - adam_update, the expressions of the bf16-state kernels.
+// SR (!MASTER only): the bf16 parameter store rounds stochastically; the codes never do. Per state block and lane: load (codes,
+// absmax, g, p) -> dequantise -> adam_update from the dequantised moments (p moves by the unquantised m', v') -> store p, clear g
+// -> two wave maxima -> 4 x (7 + 8)-step searches -> two code dwords; lane 0 stores the two maxima.
+template <typename GT, bool MASTER, bool SR, bool MASKED>
+__global__ __launch_bounds__(256) void adamw_q8_kernel(float* __restrict__ p, bf16_t* __restrict__ pb, GT* __restrict__ g,
+                                                       uint8_t* __restrict__ m8, uint8_t* __restrict__ v8, size_t n,
+                                                       const float* __restrict__ clip, AdamHyper h0, NdArg<MASKED> nd) {
+  __shared__ Q8Tables s;
+  q8_build_tables(s);
+  const int lane = threadIdx.x & 63;
+  const size_t nb = (n + 255) >> 8;
+  float* __restrict__ am = reinterpret_cast<float*>(m8 + q8_absmax_offset(n));
+  float* __restrict__ av = reinterpret_cast<float*>(v8 + q8_absmax_offset(n));
+  const float cs = clip ? clip[1] : 1.f;
+  for (size_t b = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < nb; b += (size_t)gridDim.x * 4) {
+    const size_t e = b * 256 + (size_t)lane * 4;
+    const bool on = e < n;  // n is a multiple of 4: a lane's four elements exist together; the short last block masks its lanes
+    float ga[4] = {0.f, 0.f, 0.f, 0.f}, pa[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t cm = 0, cv = 0;
+    if (on) {
+      cm = *reinterpret_cast<const uint32_t*>(m8 + e);
+      cv = *reinterpret_cast<const uint32_t*>(v8 + e);
+      load4<GT>(g + e, ga);
+      if (MASTER) load4<float>(p + e, pa);
+      else load4<bf16_t>(pb + e, pa);
+    }
+    const float sm = am[b], sv = av[b];
+    float ma[4], va[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t c = (cm >> (8 * j)) & 0xffu;
+      ma[j] = __uint_as_float(__float_as_uint(q8_deq(s.tm[c & 127u], sm)) | ((c & 128u) << 24));  // the sign bit, exactly
+      va[j] = q8_deq(s.tv[(cv >> (8 * j)) & 0xffu], sv);
+    }
+    const AdamHyper h = hyper_at<MASKED>(h0, nd, (uint64_t)b * 256, e);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) adam_update<MASTER, SR>(pa[j], ma[j], va[j], ga[j], cs, h);
+    if (on) {
+      if (MASTER) store4(p + e, pa);
+      *reinterpret_cast<uint2*>(pb + e) = round4<SR && !MASTER>(pa, h.sr, h.sr.base + e, 0);
+      if constexpr (sizeof(GT) == 4) {
+        if (h.zero_grad) *reinterpret_cast<float4*>(g + e) = make_float4(0, 0, 0, 0);
+      }
+    }
+    const float xm = q8_wave_max(on ? fmaxf(fmaxf(fabsf(ma[0]), fabsf(ma[1])), fmaxf(fabsf(ma[2]), fabsf(ma[3]))) : 0.f);
+    const float xv = q8_wave_max(on ? fmaxf(fmaxf(va[0], va[1]), fmaxf(va[2], va[3])) : 0.f);
+    cm = cv = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t km = q8_code<7>(s.mm, xm > 0.f ? fabsf(ma[j]) / xm : 0.f);
+      const uint32_t kv = q8_code<8>(s.mv, xv > 0.f ? va[j] / xv : 0.f);
+      cm |= (km ? km | ((__float_as_uint(ma[j]) >> 24) & 128u) : 0u) << (8 * j);  // k = 0 is stored without a sign
+      cv |= kv << (8 * j);
+    }
+    if (on) {
+      *reinterpret_cast<uint32_t*>(m8 + e) = cm;
+      *reinterpret_cast<uint32_t*>(v8 + e) = cv;
+    }
+    if (lane == 0) { am[b] = xm; av[b] = xv; }
+  }
+}
+
 // y[i] = sr_bf16(x[i]) with the bits of flat index index0 + i of array `which`: the rounding of the kernels above on its own
 __global__ __launch_bounds__(256) void sr_round_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, size_t n, SrKey k,
                                                             uint32_t which) {
@@ -547,6 +665,39 @@ int adamw_flat(const AdamArgs& a, size_t n, hipStream_t st) {
         using GT = Elem<decltype(g16)>;
         adamw_bf16_kernel<GT, decltype(sr)::value, decltype(mk)::value><<<nblocks(n / 8, 256), 256, 0, st>>>(
             a.params, (GT*)a.g, (bf16_t*)a.m, (bf16_t*)a.v, n, a.clip, h, nd_arg<decltype(mk)::value>(a));
+      });
+    });
+  });
+  LAUNCH_RET();
+}
+// the whole flat buffer on 8-bit block-wise moments (a.m / a.v: the allocations of adam8_state_bytes(n)); mode 1 or 2
+int adamw_q8(const AdamArgs& a, size_t n, hipStream_t st) {
+  if (a.mode != 1 && a.mode != 2) return -1;
+  const bool masked = a.nd.bounds != nullptr;
+  const bool sr_on = a.sr.on && a.mode == 2;  // the bf16 parameters are rounded only where they are the state
+  if ((n & 3) || (sr_on && (a.sr.base & 3)) || (masked && (a.nd.base & 7))) return -1;
+  if (n == 0) return 0;
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, c = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1) c = 256;
+    cus = c;
+  }
+  // persistent: 8 thread blocks (32 waves) per CU hide the dependent LDS reads of the searches; fewer when the buffer is small
+  const size_t want = ((n + 255) / 256 + 3) / 4, cap = (size_t)cus * 8;
+  const unsigned grid = (unsigned)(want < cap ? want : cap);
+  const AdamHyper h = adam_hyper(a);
+  with_flag(a.g_bf16, [&](auto g16) {
+    with_flag(a.mode == 1, [&](auto master) {
+      with_flag(sr_on, [&](auto sr) {
+        with_flag(masked, [&](auto mk) {
+          using GT = Elem<decltype(g16)>;
+          constexpr bool MASTER = decltype(master)::value, SR = decltype(sr)::value && !MASTER;
+          if constexpr (MASTER && decltype(sr)::value) return;  // never reached: sr_on needs mode 2
+          else
+            adamw_q8_kernel<GT, MASTER, SR, decltype(mk)::value><<<grid, 256, 0, st>>>(
+                a.master, a.params, (GT*)a.g, (uint8_t*)a.m, (uint8_t*)a.v, n, a.clip, h, nd_arg<decltype(mk)::value>(a));
+        });
       });
     });
   });

@@ -802,7 +802,7 @@ class Engine:
     def adamw_step(self, master, exp_avg, exp_avg_sq, norm_out, lr, beta1, beta2, eps, weight_decay, step,
                    zero_grad=True, stream=None):
         import torch
-        if exp_avg.dtype == torch.bfloat16:  # fp32 master + bf16 moments
+        if exp_avg.dtype in (torch.bfloat16, torch.uint8):  # fp32 master + bf16 moments (uint8: the "adamw_state8" allocations)
             self._ck(self.lib.slam_adamw_step_bf16_moments(self.h, _ptr(master), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(norm_out),
                                                            float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
                                                            int(step), int(bool(zero_grad)),
@@ -817,11 +817,20 @@ class Engine:
                         stream=None):
         """bf16 parameters + bf16 moments, updated in place (the recipe's optimizer precision)."""
         import torch
-        assert exp_avg.dtype == torch.bfloat16 and exp_avg_sq.dtype == torch.bfloat16
+        assert exp_avg.dtype == exp_avg_sq.dtype and exp_avg.dtype in (torch.bfloat16, torch.uint8)  # uint8: "adamw_state8"
         self._ck(self.lib.slam_adamw_step_bf16(self.h, _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(norm_out), float(lr),
                                                float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
                                                int(bool(zero_grad)),
                                                stream if stream is not None else current_stream_ptr()))
+
+    @staticmethod
+    def adam8_state_layout(n: int):
+        """(bytes of ONE 8-bit moment allocation of n elements, byte offset of its absmax array, number of 256-element state
+        blocks) - slam_engine.h's formula under "adamw_state8": uint8 codes[n], then, 256-byte aligned, float absmax[blocks]."""
+        n = int(n)
+        blocks = (n + 255) // 256
+        off = (n + 255) // 256 * 256
+        return off + 4 * blocks, off, blocks
 
     # -- sharded optimizer step (data-parallel "rs_ag") ----------------------------------------------------
     def grad_chunk_info(self):

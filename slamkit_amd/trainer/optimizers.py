@@ -113,6 +113,49 @@ class AdamW(Optimizer):
                             a.adam_epsilon, a.weight_decay, step, zero_grad=False)
 
 
+class AdamW8bit(Optimizer):
+    """AdamW on 8-bit block-wise moments (engine option "adamw_state8"): per moment one byte per element and one fp32 maximum
+    per 256 elements of the flat buffer - 2 (1 + 4 / 256) B/param instead of 4. One uint8 allocation per moment, laid out as
+    slam_engine.h says; `state` holds the two views of each (codes, absmax), which are what optimizer.pt carries. The step is
+    slam_adamw_step_bf16 / _bf16_moments under the option, which is on for the length of the call only: an engine that another
+    trainer steps with bf16 moments never sees it."""
+    kind = "adamw_8bit"
+    options = ("adamw_bnb_8bit",)
+    state_dtypes = ("bfloat16", "float32_bf16_moments")
+    state_reason = ("keeps both Adam moments in 8 bits: optim_state_dtype is bfloat16 (the bf16 parameters are the only copy) or "
+                    "float32_bf16_moments (fp32 master weights)")
+    whole_reason = "quantises whole 256-element blocks of the flat buffer"
+    file_keys = ("exp_avg_codes", "exp_avg_absmax", "exp_avg_sq_codes", "exp_avg_sq_absmax")
+    a_checkpoint, holds = "an 8-bit AdamW checkpoint", "it holds codes and block maxima, no bf16 or fp32 moments"
+
+    def __init__(self, args, model, state_dtype, moment_dtype):
+        super().__init__(args, model, state_dtype, moment_dtype)
+        from ..engine import Engine
+        n = model.engine.n_params
+        nbytes, off, blocks = Engine.adam8_state_layout(n)
+        self._alloc = [torch.zeros(nbytes, dtype=torch.uint8, device=model.device) for _ in range(2)]
+        for name, a in zip(("exp_avg", "exp_avg_sq"), self._alloc):
+            self.state[name + "_codes"] = a[:n]
+            self.state[name + "_absmax"] = a[off:off + 4 * blocks].view(torch.float32)
+
+    @property
+    def state_bytes(self):
+        return sum(a.numel() for a in self._alloc), 0
+
+    def step(self, lr, step, norm_out, zero_grad):
+        a, eng, (m8, v8) = self.args, self.model.engine, self._alloc
+        eng.set_option("adamw_state8", 1)
+        try:
+            if self.state_dtype == torch.bfloat16:
+                eng.adamw_step_bf16(m8, v8, norm_out, lr, a.adam_beta1, a.adam_beta2, a.adam_epsilon, a.weight_decay, step,
+                                    zero_grad=zero_grad)
+            else:
+                eng.adamw_step(self.model.flat_master, m8, v8, norm_out, lr, a.adam_beta1, a.adam_beta2, a.adam_epsilon,
+                               a.weight_decay, step, zero_grad=zero_grad)
+        finally:
+            eng.set_option("adamw_state8", 0)
+
+
 class Adafactor(Optimizer):
     """HF's Adafactor on slam_adafactor_step. No exp_avg / exp_avg_sq - that is the point: rows + cols fp32 factors per HF matrix,
     numel per vector, and the kernels' partial sums. The table is set once; the engine keeps it."""
@@ -181,7 +224,7 @@ class Muon(Optimizer):
         eng.refresh_transposed()  # both left the transposed weight images stale
 
 
-KINDS = {c.kind: c for c in (AdamW, Adafactor, Muon)}
+KINDS = {c.kind: c for c in (AdamW, AdamW8bit, Adafactor, Muon)}
 BY_OPTION = {o: c for c in KINDS.values() for o in c.options}
 
 
@@ -213,10 +256,11 @@ def make_optimizer(args, model, state_dtype, moment_dtype) -> Optimizer:
 
 def check_checkpoint_optim(st: dict, kind: str, path: str = "optimizer.pt"):
     """An optimizer.pt holds the state of ONE optimizer kind: Adafactor's factors ("adafactor_state"), AdamW's moments
-    ("exp_avg", "exp_avg_sq"), or Muon's momentum buffer with the AdamW moments of the other elements ("optim": "muon").
-    Resuming one under another is an error, not a silent zero state. `kind`: "adamw", "adafactor" or "muon"."""
+    ("exp_avg", "exp_avg_sq"), their 8-bit codes and block maxima ("optim": "adamw_8bit"), or Muon's momentum buffer with the AdamW
+    moments of the other elements ("optim": "muon"). Resuming one under another is an error, not a silent zero state. `kind`:
+    "adamw", "adamw_8bit", "adafactor" or "muon"."""
     want = KINDS[kind]
-    found = next((c for c in (Muon, Adafactor) if st.get("optim") == c.kind or c.file_keys[0] in st), AdamW)
+    found = next((c for c in (Muon, Adafactor, AdamW8bit) if st.get("optim") == c.kind or c.file_keys[0] in st), AdamW)
     if found is want and all(k in st for k in want.file_keys):
         return
     if found is want:  # the kind's mark without its tensors: what the file lacks is what another kind does not keep

@@ -21,7 +21,7 @@ class SLAMTrainingArguments:
     gradient_accumulation_steps: int = 1
     weight_decay: float = 0.0
     weight_decay_rule: str = "all"                 # which tensors weight_decay applies to. "all": every element of the flat parameter buffer (the engine's historical behaviour; at weight_decay 0 - every shipped recipe - the two rules coincide). "hf": HF Trainer.create_optimizer's rule - no bias, no LayerNorm / RMSNorm parameter (UnitLM.hf_decay_flags -> slam_set_decay_mask): what reproduces a reference run with a non-zero weight_decay
-    optim: str = "adamw_torch"                     # HF's field. "adamw_torch" / "adamw_torch_fused": AdamW (the engine's slam_adamw_* kernels; the two names make the same calls). "adafactor": transformers.optimization.Adafactor as HF's Trainer builds it (scale_parameter = False, relative_step = False, no first moment; lr from the scheduler, clip_grad_norm_ first) on slam_adafactor_step: one fp32 number per row and per column of every HF matrix instead of two Adam moments per element. optim_state_dtype "float32" keeps the fp32 master, "bfloat16" drops it; "float32_bf16_moments", ddp_algo "rs_ag" and overlap_optimizer are refused (there are no moments; a shard cuts rows and columns). adam_beta1 / adam_beta2 / adam_epsilon are unused then
+    optim: str = "adamw_torch"                     # HF's field. "adamw_torch" / "adamw_torch_fused": AdamW (the engine's slam_adamw_* kernels; the two names make the same calls). "adafactor": transformers.optimization.Adafactor as HF's Trainer builds it (scale_parameter = False, relative_step = False, no first moment; lr from the scheduler, clip_grad_norm_ first) on slam_adafactor_step: one fp32 number per row and per column of every HF matrix instead of two Adam moments per element. optim_state_dtype "float32" keeps the fp32 master, "bfloat16" drops it; "float32_bf16_moments", ddp_algo "rs_ag" and overlap_optimizer are refused (there are no moments; a shard cuts rows and columns). adam_beta1 / adam_beta2 / adam_epsilon are unused then. "adamw_bnb_8bit": AdamW on 8-bit block-wise moments (engine option "adamw_state8": one byte per element and one fp32 maximum per 256 elements, 2.03 B/param of moments instead of 4); optim_state_dtype "bfloat16" or "float32_bf16_moments"; "float32", ddp_algo "rs_ag" and overlap_optimizer are refused. HF's other spelling "adamw_8bit" is not accepted
     muon_momentum: float = 0.95                    # optim = "muon" (torch.optim.Muon on slam_muon_step): the decoder layers' matrices (q/k/v/o and the MLP weights, per HF tensor) take Muon - an fp32 momentum buffer, Nesterov, five Newton-Schulz iterations on batched HIP GEMMs -, every other parameter (embeddings, an untied head, norms, biases) AdamW with adam_beta1 / adam_beta2 / adam_epsilon through slam_adamw_range*, with moments for those elements only. optim_state_dtype "float32" or "bfloat16"; "float32_bf16_moments", ddp_algo "rs_ag" and overlap_optimizer are refused
     muon_nesterov: bool = True
     muon_ns_steps: int = 5                         # Newton-Schulz iterations, 1 .. 16
@@ -98,13 +98,14 @@ def check_weight_decay_rule(rule) -> str:
 
 
 OPTIM_ADAMW = ("adamw_torch", "adamw_torch_fused")
-OPTIM_NAMES = OPTIM_ADAMW + ("adafactor", "muon")
+OPTIM_ADAMW_8BIT = ("adamw_bnb_8bit",)  # HF's other spelling, "adamw_8bit", stays refused (tests/test_adafactor_host.py names it so)
+OPTIM_NAMES = OPTIM_ADAMW + ("adafactor", "muon") + OPTIM_ADAMW_8BIT
 MUON_ADJUST_LR = ("match_rms_adamw", "original", None)
 
 
 def check_optim(name) -> str:
     if name not in OPTIM_NAMES:
-        raise ValueError(f"optim must be one of 'adamw_torch', 'adamw_torch_fused', 'adafactor' or 'muon', got {name!r}")
+        raise ValueError(f"optim must be one of 'adamw_torch', 'adamw_torch_fused', 'adafactor', 'muon' or 'adamw_bnb_8bit', got {name!r}")
     return name
 
 
