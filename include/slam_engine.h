@@ -83,11 +83,30 @@ int slam_engine_create(const SlamModelDesc* desc, SlamEngine** out); /* UnitLM._
  * (slam_op_qknorm_rope_fwd below). n_heads * head_dim need not equal hidden. Its layer tensors, in layout order:
  *   layers.N.{ln1 [H], wqkv [(nH + 2 nKV) hd][H], q_norm [hd], k_norm [hd], wo [H][nH hd], ln2 [H], wgu [2 I][H], wd [H][I]}
  * - there is no bqkv. Everything the Qwen2 family offers (training, "recompute", the untied head, KV-cached generation and
- * scoring) holds for arch 3; "Qwen2 only" below means arch 0 and 3. Arch 2 is not a family: SLAM_EINVAL. */
+ * scoring) holds for arch 3; "Qwen2 only" below means arch 0 and 3. Arch 2 is not a family: SLAM_EINVAL.
+ * Arch 4 = GPT-NeoX (Pythia) as HF GPTNeoXForCausalLM computes it with use_parallel_residual: x_out = x + attn(ln1(x)) +
+ * mlp(ln2(x)), LayerNorm with bias (rms_eps carries layer_norm_eps), biases on every projection, exact (erf) GELU FFN, multi-head
+ * attention with rotate-half RoPE over the first r dims of every q and k head (dim i pairs with i + r / 2; the other dims pass
+ * through). n_positions carries r: even, a multiple of 8, 8 <= r <= head_dim (r == head_dim is the Qwen2 rotation). Requires
+ * n_kv_heads == n_heads, head_dim 64 or 128, hidden % 64 == 0 and <= 2048, intermediate % 64 == 0; SLAM_MODEL_UNTIED_HEAD is
+ * allowed (Pythia's embed_out). No position table. Tensor names, in layout order:
+ *   embed [Vp][H],
+ *   layers.N.{ln1, ln1_b, ln2, ln2_b [H], wqkv [3 H][H] (rows q | k | v; HF's query_key_value is [n_heads][3][head_dim]), bqkv [3 H],
+ *             wo [H][H], bo [H], w1 [F][H], b1 [F], w2 [H][F], b2 [H]},
+ *   norm, norm_b [H], and lm_head [Vp][H] when untied.
+ * Both LayerNorms of a layer read the same row: one forward launch writes both outputs and one mean / rstd pair, one backward
+ * launch returns dx = d + LNbwd(dy1; ln1) + LNbwd(dy2; ln2) (fp32, one rounding) and the four weight / bias partial slabs. Option
+ * "neox_split_ln" = 1 (default 0; arch 4 only, else SLAM_EINVAL) runs the single LayerNorm kernels twice instead (backward: their
+ * fp32 terms and an add) - the same bits, kept as a cross-check and for A/B timing; a forward must be followed by its backward
+ * under the same setting. The FFN keeps the fc1 pre-activation pre = bf16(x2 w1^T + b1) and act = bf16(gelu(float(pre))): the fc2
+ * dgrad multiplies by gelu'(float(pre)) in its epilogue, and "recompute" = 1 rebuilds act from pre. Training, "recompute",
+ * padding-free and span batches, packed segments, label smoothing, NEFTune, every optimizer and the data-parallel step work as for
+ * OPT; residual dropout, KV-cached generation, scoring, the FP8 decode weights and the FP8 cache are refused as for arch 1, with
+ * a message that names the family. */
 int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, SlamEngine** out);
 /* The same with model flags (slam_engine_create / slam_engine_create_arch mean flags = 0). Arch 0 and 3 take hidden <= 4096
- * (rows above 2048 run the two-waves-per-row RMSNorm kernels), arch 1 hidden <= 2048.
- * SLAM_MODEL_UNTIED_HEAD (arch 0 and 3; Qwen2.5-7B): the LM head is a tensor of its own, "lm_head" [Vp][H], laid out AFTER
+ * (rows above 2048 run the two-waves-per-row RMSNorm kernels), arch 1 and 4 hidden <= 2048.
+ * SLAM_MODEL_UNTIED_HEAD (arch 0, 3 and 4; Qwen2.5-7B, Pythia): the LM head is a tensor of its own, "lm_head" [Vp][H], laid out AFTER
  * "norm" so that every other tensor keeps the offset it has in the tied layout. Its pad rows [vocab, Vp) are zero and stay
  * zero, as the embedding's do. Forward, prefill and decode read the head GEMM's weight there; backward writes
  * d lm_head = dlogits^T hf as that tensor's final value, and the embedding gradient is the gather side alone (rows of ids

@@ -88,7 +88,20 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const bf16_t* __restri
 // dw = sum dy*xhat and db = sum dy per block.
 // Each wave walks rows wave, wave+4*gridDim.. accumulating its dw slice in registers.
 // Algorithmic traffic: 6 B/element (+2 with the fused residual-gradient add).
-template <int MAXC, bool LN = false>
+// F32 (GPT-NeoX's "neox_split_ln" cross-check): dx is a float buffer that takes the backward term itself, unrounded and without
+// dres - the summand the dual kernel below forms in registers. Which products the compiler folds into fused multiply-adds is
+// its own choice per kernel, so the F32 form and the dual kernel pin() the same intermediate values: g = dy w, xhat mean(g xhat),
+// the bracket and the term are each rounded once in both, and the two results agree bit for bit.
+SLAM_DEVICE float pin(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+SLAM_DEVICE float ln_bwd_term(float r, float gy, float gsum, float xh, float dot) {
+  const float u = pin(xh * dot);
+  const float w = pin((gy - gsum) - u);
+  return pin(r * w);
+}
+template <int MAXC, bool LN = false, bool F32 = false>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy,
                                                           const bf16_t* __restrict__ x,
                                                           const bf16_t* __restrict__ w,
@@ -150,7 +163,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           xh[i][j] = LN ? (fx[j] - cmu) * r : fx[j] * r;
-          gy[i][j] = fd[j] * wv[i][j];
+          gy[i][j] = F32 ? pin(fd[j] * wv[i][j]) : fd[j] * wv[i][j];
           dot += gy[i][j] * xh[i][j];
           dwa[i][j] += fd[j] * xh[i][j];
           if constexpr (LN) { gsum += gy[i][j]; dba[i][j] += fd[j]; }
@@ -167,6 +180,14 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
         float o[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = LN ? r * (gy[i][j] - gsum - xh[i][j] * dot) : r * (gy[i][j] - xh[i][j] * dot);
+        if constexpr (F32) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = ln_bwd_term(r, gy[i][j], gsum, xh[i][j], dot);
+          float4* fo = reinterpret_cast<float4*>(reinterpret_cast<float*>(dx) + (size_t)row * H) + 2 * c;
+          fo[0] = make_float4(o[0], o[1], o[2], o[3]);
+          fo[1] = make_float4(o[4], o[5], o[6], o[7]);
+          continue;
+        }
         if (dres) {
           float a[8];
           unpack_bf16x8(cdr[i], a);
@@ -199,6 +220,210 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
     for (int e = threadIdx.x; e < H; e += 256)
       db_part[(size_t)blockIdx.x * H + e] = red[0][e] + red[1][e] + red[2][e] + red[3][e];
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// GPT-NeoX's parallel residual: both LayerNorms of a layer read the same row and share its statistics.
+// Forward: one pass over x, statistics by the two-pass rule above, y1 = bf16((x - mu) rstd w1 + b1) and y2 likewise with
+// (w2, b2) - per output the expression of rmsnorm_fwd_kernel<.., true>, so each is the bits layernorm_fwd gives for it.
+// Algorithmic traffic: 6 B/element (read bf16, write two) against 8 for two launches.
+template <int MAXC>
+__global__ __launch_bounds__(256) void layernorm_dual_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w1,
+                                                                 const bf16_t* __restrict__ b1, const bf16_t* __restrict__ w2,
+                                                                 const bf16_t* __restrict__ b2, bf16_t* __restrict__ y1,
+                                                                 bf16_t* __restrict__ y2, float* __restrict__ mean,
+                                                                 float* __restrict__ rstd, int M, int H, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int nch = H >> 3;
+  const uint4* xr = reinterpret_cast<const uint4*>(x + (size_t)row * H);
+  uint4 v[MAXC];
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    int c = lane + 64 * i;
+    if (c < nch) {
+      v[i] = xr[c];
+      float f[8];
+      unpack_bf16x8(v[i], f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss += f[j];
+    }
+  }
+  ss = wave_sum(ss);
+  const float mu = ss / (float)H;
+  ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    int c = lane + 64 * i;
+    if (c < nch) {
+      float f[8];
+      unpack_bf16x8(v[i], f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss += (f[j] - mu) * (f[j] - mu);
+    }
+  }
+  ss = wave_sum(ss);
+  const float r = rsqrtf(ss / (float)H + eps);
+  if (lane == 0) { mean[row] = mu; rstd[row] = r; }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    uint4* yr = reinterpret_cast<uint4*>((k ? y2 : y1) + (size_t)row * H);
+    const uint4* wr = reinterpret_cast<const uint4*>(k ? w2 : w1);
+    const uint4* br = reinterpret_cast<const uint4*>(k ? b2 : b1);
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      int c = lane + 64 * i;
+      if (c < nch) {
+        float f[8], g[8], bb[8];
+        unpack_bf16x8(v[i], f);
+        unpack_bf16x8(wr[c], g);
+        unpack_bf16x8(br[c], bb);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = (f[j] - mu) * r * g[j] + bb[j];
+        yr[c] = pack_bf16x8(f);
+      }
+    }
+  }
+}
+
+// Backward of the pair: dx = bf16((d + t1) + t2), t_k = rstd (g_k - mean(g_k) - xhat mean(g_k xhat)), g_k = dy_k w_k - each
+// term formed in fp32 in the order of rmsnorm_bwd_kernel<.., true> (its F32 form: the same pinned roundings) and added to the
+// direct residual gradient d (the split form adds the stored fp32 terms: dual_add_kernel). One pass reads x, dy1, dy2, d (8 B/element) and writes
+// dx (2 B) against 2 x (6 + 2) for two chained launches; x, xhat, mean and rstd are read and formed once.
+// Split of the work: as the single kernel - one wave per row, four rows in flight per block, rows strided by 4 gridDim over
+// rmsnorm_bwd_blocks(M) blocks, so every block adds the rows of its dw / db partials in the single kernel's order. The weights
+// stay packed (2 x MAXC uint4) and are unpacked per use; the four partial accumulators are 4 x 8 MAXC floats. At MAXC = 4
+// (hidden 2048) that is 128 accumulator + 32 weight + 2 x 64 row (current and prefetched) + 96 xhat / g registers: 466 of the
+// 512 a wave of a 256-thread block may use (no scratch), one wave per SIMD. LDS: the single kernel's 4 x 8 MAXC x 64 floats (32 KB at MAXC = 4), used four
+// times in a row.
+template <int MAXC>
+__global__ __launch_bounds__(256) void layernorm_dual_bwd_kernel(const bf16_t* __restrict__ dy1, const bf16_t* __restrict__ dy2,
+                                                                 const bf16_t* __restrict__ x, const bf16_t* __restrict__ w1,
+                                                                 const bf16_t* __restrict__ w2, const float* __restrict__ mean,
+                                                                 const float* __restrict__ rstd, const bf16_t* __restrict__ d,
+                                                                 bf16_t* __restrict__ dx, float* __restrict__ dw1_part,
+                                                                 float* __restrict__ db1_part, float* __restrict__ dw2_part,
+                                                                 float* __restrict__ db2_part, int M, int H) {
+  __shared__ float red[4][MAXC * 64 * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nch = H >> 3;
+  float dwa[2][MAXC][8], dba[2][MAXC][8];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { dwa[k][i][j] = 0.f; dba[k][i][j] = 0.f; }
+  uint4 wp[2][MAXC];
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    int c = lane + 64 * i;
+    if (c < nch) {
+      wp[0][i] = reinterpret_cast<const uint4*>(w1)[c];
+      wp[1][i] = reinterpret_cast<const uint4*>(w2)[c];
+    }
+  }
+  auto load_row = [&](int row, uint4* rx, uint4* r1, uint4* r2, uint4* rd) {
+    const size_t o = (size_t)row * H;
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      int c = lane + 64 * i;
+      if (c < nch) {
+        rx[i] = reinterpret_cast<const uint4*>(x + o)[c];
+        r1[i] = reinterpret_cast<const uint4*>(dy1 + o)[c];
+        r2[i] = reinterpret_cast<const uint4*>(dy2 + o)[c];
+        rd[i] = reinterpret_cast<const uint4*>(d + o)[c];
+      }
+    }
+  };
+  const int rstep = gridDim.x * 4;
+  int row = blockIdx.x * 4 + wave;
+  uint4 cx[MAXC], c1[MAXC], c2[MAXC], cd[MAXC];
+  float cr = 0.f, cmu = 0.f;
+  if (row < M) { load_row(row, cx, c1, c2, cd); cr = rstd[row]; cmu = mean[row]; }
+  for (; row < M; row += rstep) {
+    uint4 nx[MAXC], n1[MAXC], n2[MAXC], nd[MAXC];
+    float nr = 0.f, nmu = 0.f;
+    const int nrow = row + rstep;
+    if (nrow < M) { load_row(nrow, nx, n1, n2, nd); nr = rstd[nrow]; nmu = mean[nrow]; }
+    const float r = cr;
+    float xh[MAXC][8], gy[2][MAXC][8];
+    float dot[2] = {0.f, 0.f}, gsum[2] = {0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+#pragma unroll
+      for (int i = 0; i < MAXC; ++i) {
+        int c = lane + 64 * i;
+        if (c < nch) {
+          float fx[8], fd[8], wv[8];
+          unpack_bf16x8(cx[i], fx);
+          unpack_bf16x8(k ? c2[i] : c1[i], fd);
+          unpack_bf16x8(wp[k][i], wv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            xh[i][j] = (fx[j] - cmu) * r;
+            gy[k][i][j] = pin(fd[j] * wv[j]);
+            dot[k] += gy[k][i][j] * xh[i][j];
+            dwa[k][i][j] += fd[j] * xh[i][j];
+            gsum[k] += gy[k][i][j];
+            dba[k][i][j] += fd[j];
+          }
+        }
+      }
+      dot[k] = wave_sum(dot[k]) / (float)H;
+      gsum[k] = wave_sum(gsum[k]) / (float)H;
+    }
+    uint4* dxr = reinterpret_cast<uint4*>(dx + (size_t)row * H);
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      int c = lane + 64 * i;
+      if (c < nch) {
+        float o[8], t[2][8];
+        unpack_bf16x8(cd[i], o);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) t[k][j] = ln_bwd_term(r, gy[k][i][j], gsum[k], xh[i][j], dot[k]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = pin(o[j] + t[0][j]) + t[1][j];
+        dxr[c] = pack_bf16x8(o);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) { cx[i] = nx[i]; c1[i] = n1[i]; c2[i] = n2[i]; cd[i] = nd[i]; }
+    cr = nr;
+    cmu = nmu;
+  }
+  // the four partial rows of the block, one after the other through the same LDS, each as the single kernel reduces its own
+  float* const outs[4] = {dw1_part, db1_part, dw2_part, db2_part};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (q) __syncthreads();
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[wave][(lane + 64 * i) * 8 + j] = (q & 1) ? dba[q >> 1][i][j] : dwa[q >> 1][i][j];
+    __syncthreads();
+    for (int e = threadIdx.x; e < H; e += 256)
+      outs[q][(size_t)blockIdx.x * H + e] = red[0][e] + red[1][e] + red[2][e] + red[3][e];
+  }
+}
+
+// the split form's add: dx = bf16((d + t1) + t2) from the stored fp32 terms (n8 chunks of 8)
+__global__ __launch_bounds__(256) void dual_add_kernel(const bf16_t* __restrict__ d, const float* __restrict__ t1,
+                                                       const float* __restrict__ t2, bf16_t* __restrict__ dx, size_t n8) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  float o[8];
+  unpack_bf16x8(reinterpret_cast<const uint4*>(d)[i], o);
+  const float4 a0 = reinterpret_cast<const float4*>(t1)[2 * i], a1 = reinterpret_cast<const float4*>(t1)[2 * i + 1];
+  const float4 b0 = reinterpret_cast<const float4*>(t2)[2 * i], b1 = reinterpret_cast<const float4*>(t2)[2 * i + 1];
+  const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w}, b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = pin(o[j] + a[j]) + b[j];
+  reinterpret_cast<uint4*>(dx)[i] = pack_bf16x8(o);
 }
 
 // Wide rows (2048 < hidden <= 4096): a row is split over the two waves of a PAIR, chunk c = (2 i + half) * 64 + lane, so each
@@ -490,6 +715,51 @@ __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ qkv, int
   *reinterpret_cast<uint4*>(base + half) = pack_bf16x8(o2);
 }
 
+// GPT-NeoX's partial rotary embedding, in place on the first `nrot` heads (q then k) of qkv [M][ld]: rotate-half over the first
+// rot dims of a head, dim i paired with i + rot/2 (tables [M][rot/2], fp32, one rounding); the other hd - rot dims pass through.
+// One thread per 8 dims of a head: unit u < rot/8 owns the rotated dims 4u .. 4u+3 and their partners (8-byte accesses),
+// a later unit the pass-through dims 8u .. 8u+7. Forward (dir = +1): the q_heads query heads leave multiplied by q_scale,
+// pass-through dims included (the attention kernels take q pre-scaled); k pass-through units do nothing. Backward (dir = -1,
+// q_heads = 0): the transpose rotation of dq / dk, pass-through untouched.
+__global__ __launch_bounds__(256) void rope_partial_kernel(bf16_t* __restrict__ qkv, int ld, int M, int nrot, int hd, int rot,
+                                                           const float* __restrict__ cs, const float* __restrict__ sn,
+                                                           float dir, int q_heads, float q_scale) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int uph = hd >> 3, per_row = nrot * uph, half = rot >> 1;
+  if (idx >= (size_t)M * per_row) return;
+  const int m = (int)(idx / per_row), r = (int)(idx % per_row);
+  const int head = r / uph, u = r % uph;
+  const float hs = head < q_heads ? q_scale : 1.f;
+  bf16_t* hb = qkv + (size_t)m * ld + head * hd;
+  if (u >= (rot >> 3)) {  // pass-through dims
+    if (head >= q_heads) return;
+    float f[8];
+    unpack_bf16x8(*reinterpret_cast<const uint4*>(hb + u * 8), f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] *= hs;
+    *reinterpret_cast<uint4*>(hb + u * 8) = pack_bf16x8(f);
+    return;
+  }
+  const uint2 lo = *reinterpret_cast<const uint2*>(hb + u * 4), hi = *reinterpret_cast<const uint2*>(hb + half + u * 4);
+  const float4 c4 = *reinterpret_cast<const float4*>(cs + (size_t)m * half + u * 4);
+  const float4 s4 = *reinterpret_cast<const float4*>(sn + (size_t)m * half + u * 4);
+  const float a[4] = {__uint_as_float(lo.x << 16), __uint_as_float(lo.x & 0xffff0000u), __uint_as_float(lo.y << 16), __uint_as_float(lo.y & 0xffff0000u)};
+  const float b[4] = {__uint_as_float(hi.x << 16), __uint_as_float(hi.x & 0xffff0000u), __uint_as_float(hi.y << 16), __uint_as_float(hi.y & 0xffff0000u)};
+  const float c[4] = {c4.x, c4.y, c4.z, c4.w}, s[4] = {s4.x, s4.y, s4.z, s4.w};
+  float o1[4], o2[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float sj = s[j] * dir;
+    o1[j] = (a[j] * c[j] - b[j] * sj) * hs;
+    o2[j] = (b[j] * c[j] + a[j] * sj) * hs;
+  }
+  uint2 w1, w2;
+  w1.x = pack_bf16x2(o1[0], o1[1]); w1.y = pack_bf16x2(o1[2], o1[3]);
+  w2.x = pack_bf16x2(o2[0], o2[1]); w2.y = pack_bf16x2(o2[2], o2[3]);
+  *reinterpret_cast<uint2*>(hb + u * 4) = w1;
+  *reinterpret_cast<uint2*>(hb + half + u * 4) = w2;
+}
+
 // ------------------------------------------------------------------------------------------
 // SwiGLU: gu [M][2I] -> act [M][I]. Column layout of gu: blocks of `blk` gate columns followed by the
 // matching `blk` up columns (blk = I: the plain gate|up halves; blk = 32: the engine's interleaved
@@ -619,6 +889,34 @@ __global__ __launch_bounds__(256) void embed_pos_noise_fwd_kernel(const int64_t*
                                                                   bf16_t* __restrict__ out, int64_t* __restrict__ prow, size_t M,
                                                                   int H, int V, int T, int NP, NeftKey k) {
   embed_pos_fwd_body<true>(ids, pos, E, P, out, prow, M, H, V, T, NP, k);
+}
+
+// exact (erf) GELU: gemm.hip's epilogue forms, for the shapes and recompute passes that run outside a GEMM
+SLAM_DEVICE float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+SLAM_DEVICE float dgelu_erf(float x) {
+  return 0.5f * (1.f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
+}
+// act = bf16(gelu(float(pre))): recompute level 1 rebuilds the activation from the stored pre-activation
+__global__ __launch_bounds__(256) void gelu_fwd_kernel(const bf16_t* __restrict__ pre, bf16_t* __restrict__ act, size_t n8) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  float f[8];
+  unpack_bf16x8(reinterpret_cast<const uint4*>(pre)[i], f);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = gelu_erf(f[j]);
+  reinterpret_cast<uint4*>(act)[i] = pack_bf16x8(f);
+}
+// pre = bf16(float(d) * gelu'(float(pre))): the GELU backward without the fused dgrad epilogue; the pre-activation buffer becomes
+// its own gradient (as swiglu_bwd leaves d(gate|up) in gu)
+__global__ __launch_bounds__(256) void gelu_bwd_kernel(bf16_t* __restrict__ pre, const bf16_t* __restrict__ d, size_t n8) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  float f[8], p[8];
+  unpack_bf16x8(reinterpret_cast<const uint4*>(d)[i], f);
+  unpack_bf16x8(reinterpret_cast<const uint4*>(pre)[i], p);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] *= dgelu_erf(p[j]);
+  reinterpret_cast<uint4*>(pre)[i] = pack_bf16x8(f);
 }
 
 // ReLU backward through the stored post-ReLU activation: d[i] = act[i] > 0 ? d[i] : 0
@@ -1424,6 +1722,52 @@ int layernorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const floa
   }
   LAUNCH_RET();
 }
+// GPT-NeoX: both LayerNorms of a layer over the same rows in one pass; one mean / rstd pair. -1: unsupported H
+int layernorm_dual_fwd(const bf16_t* x, const bf16_t* w1, const bf16_t* b1, const bf16_t* w2, const bf16_t* b2, bf16_t* y1, bf16_t* y2,
+                       float* mean, float* rstd, int M, int H, float eps, hipStream_t st) {
+  if ((H & 7) || H > MAXC_LIMIT * 512) return -1;
+  const int g = (M + 3) / 4;
+  switch ((H / 8 + 63) / 64) {
+    case 1: layernorm_dual_fwd_kernel<1><<<g, 256, 0, st>>>(x, w1, b1, w2, b2, y1, y2, mean, rstd, M, H, eps); break;
+    case 2: layernorm_dual_fwd_kernel<2><<<g, 256, 0, st>>>(x, w1, b1, w2, b2, y1, y2, mean, rstd, M, H, eps); break;
+    case 3: layernorm_dual_fwd_kernel<3><<<g, 256, 0, st>>>(x, w1, b1, w2, b2, y1, y2, mean, rstd, M, H, eps); break;
+    default: layernorm_dual_fwd_kernel<4><<<g, 256, 0, st>>>(x, w1, b1, w2, b2, y1, y2, mean, rstd, M, H, eps); break;
+  }
+  LAUNCH_RET();
+}
+// dx = bf16((d + t1) + t2) and the four partial slabs [rmsnorm_bwd_blocks(M)][H] (colsum_finish_many finishes them)
+int layernorm_dual_bwd(const bf16_t* dy1, const bf16_t* dy2, const bf16_t* x, const bf16_t* w1, const bf16_t* w2, const float* mean,
+                       const float* rstd, const bf16_t* d, bf16_t* dx, float* dw1_part, float* db1_part, float* dw2_part,
+                       float* db2_part, int M, int H, hipStream_t st) {
+  if ((H & 7) || H > MAXC_LIMIT * 512 || !d) return -1;
+  const int nb = rmsnorm_bwd_blocks(M);
+  switch ((H / 8 + 63) / 64) {
+    case 1: layernorm_dual_bwd_kernel<1><<<nb, 256, 0, st>>>(dy1, dy2, x, w1, w2, mean, rstd, d, dx, dw1_part, db1_part, dw2_part, db2_part, M, H); break;
+    case 2: layernorm_dual_bwd_kernel<2><<<nb, 256, 0, st>>>(dy1, dy2, x, w1, w2, mean, rstd, d, dx, dw1_part, db1_part, dw2_part, db2_part, M, H); break;
+    case 3: layernorm_dual_bwd_kernel<3><<<nb, 256, 0, st>>>(dy1, dy2, x, w1, w2, mean, rstd, d, dx, dw1_part, db1_part, dw2_part, db2_part, M, H); break;
+    default: layernorm_dual_bwd_kernel<4><<<nb, 256, 0, st>>>(dy1, dy2, x, w1, w2, mean, rstd, d, dx, dw1_part, db1_part, dw2_part, db2_part, M, H); break;
+  }
+  LAUNCH_RET();
+}
+// the split form of the above ("neox_split_ln"): layernorm_bwd's kernel with its term left in fp32 (t [M][H], no dres, unrounded)
+int layernorm_bwd_term(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* mean, const float* rstd, float* t,
+                       float* dw_part, float* db_part, int M, int H, hipStream_t st) {
+  if ((H & 7) || H > MAXC_LIMIT * 512) return -1;
+  const int nb = rmsnorm_bwd_blocks(M);
+  bf16_t* o = reinterpret_cast<bf16_t*>(t);
+  switch ((H / 8 + 63) / 64) {
+    case 1: rmsnorm_bwd_kernel<1, true, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, nullptr, o, dw_part, M, H, mean, db_part); break;
+    case 2: rmsnorm_bwd_kernel<2, true, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, nullptr, o, dw_part, M, H, mean, db_part); break;
+    case 3: rmsnorm_bwd_kernel<3, true, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, nullptr, o, dw_part, M, H, mean, db_part); break;
+    default: rmsnorm_bwd_kernel<4, true, true><<<nb, 256, 0, st>>>(dy, x, w, rstd, nullptr, o, dw_part, M, H, mean, db_part); break;
+  }
+  LAUNCH_RET();
+}
+int dual_add(const bf16_t* d, const float* t1, const float* t2, bf16_t* dx, size_t n, hipStream_t st) {
+  if (n & 7) return -1;
+  dual_add_kernel<<<nblocks(n / 8, 256), 256, 0, st>>>(d, t1, t2, dx, n / 8);
+  LAUNCH_RET();
+}
 // finish `count` equally shaped partial slabs in one launch: out[i] (+)= column sums of part[i]
 int colsum_finish_many(const float* part, size_t part_stride, int nb, int N, float* out, size_t out_stride, int count,
                        int accumulate, hipStream_t st, bf16_t* img, GradSink* sink) {
@@ -1462,6 +1806,14 @@ int rope_apply(bf16_t* qkv, int ld, int M, int nrot_heads, int head_dim, const f
   if (head_dim & 15) return -1;
   rope_kernel<<<nblocks((size_t)M * nrot_heads * (head_dim / 16), 256), 256, 0, st>>>(qkv, ld, M, nrot_heads, head_dim, cs, sn,
                                                                                      backward ? -1.f : 1.f, q_heads, q_scale);
+  LAUNCH_RET();
+}
+
+int rope_partial(bf16_t* qkv, int ld, int M, int nrot_heads, int head_dim, int rot, const float* cs, const float* sn, int backward,
+                 hipStream_t st, int q_heads, float q_scale) {
+  if ((head_dim & 7) || (rot & 7) || rot < 8 || rot > head_dim || (ld & 7)) return -1;
+  rope_partial_kernel<<<nblocks((size_t)M * nrot_heads * (head_dim / 8), 256), 256, 0, st>>>(qkv, ld, M, nrot_heads, head_dim, rot, cs, sn,
+                                                                                            backward ? -1.f : 1.f, q_heads, q_scale);
   LAUNCH_RET();
 }
 
@@ -1554,6 +1906,17 @@ int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st) {
   LAUNCH_RET();
 }
 // thr16 = round(p * 65536): q = thr16 / 65536 is the drop probability, the kept values are scaled by 1 / (1 - q) (fp32)
+int gelu_fwd(const bf16_t* pre, bf16_t* act, size_t n, hipStream_t st) {
+  if (n & 7) return -1;
+  gelu_fwd_kernel<<<nblocks(n / 8, 256), 256, 0, st>>>(pre, act, n / 8);
+  LAUNCH_RET();
+}
+int gelu_bwd(bf16_t* pre, const bf16_t* d, size_t n, hipStream_t st) {
+  if (n & 7) return -1;
+  gelu_bwd_kernel<<<nblocks(n / 8, 256), 256, 0, st>>>(pre, d, n / 8);
+  LAUNCH_RET();
+}
+
 static DropKey drop_key(const DropSite& d) {
   DropKey k;
   k.k0 = (uint32_t)d.seed; k.k1 = (uint32_t)(d.seed >> 32);

@@ -64,7 +64,7 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
   e->hs.resize(L + 1);
   e->la.resize(L);
   for (size_t l = 0; l <= L; ++l) e->hs[l] = c.take<bf16_t>(M * H);
-  const bool opt = e->arch == 1;
+  const bool opt = e->arch == 1, ln = e->ln();
   // "recompute": layer l shares the buffers named by the level with every layer l' = l (mod S); the first S layers carve them
   const int rc = e->recompute;
   const size_t S = rc ? (L < RC_SLOTS ? L : (size_t)RC_SLOTS) : L;
@@ -77,12 +77,12 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
     a.x2 = xs ? s->x2 : c.take<bf16_t>(M * H);
     a.qkv = all ? s->qkv : c.take<bf16_t>(M * e->QKV);
     a.o = all ? s->o : c.take<bf16_t>(M * d.n_heads * d.head_dim);
-    a.gu = all ? s->gu : c.take<bf16_t>(M * (opt ? 1 : 2) * I);
+    a.gu = all ? s->gu : c.take<bf16_t>(M * (ln ? 1 : 2) * I);
     a.act = as ? s->act : c.take<bf16_t>(M * I);
     a.rstd1 = all ? s->rstd1 : c.take<float>(M);
     a.rstd2 = all ? s->rstd2 : c.take<float>(M);
     a.lse = all ? s->lse : c.take<float>(M * d.n_heads);
-    if (opt) {
+    if (ln) {  // GPT-NeoX's two norms share one mean (mu2 is carved and unused)
       a.mu1 = all ? s->mu1 : c.take<float>(M);
       a.mu2 = all ? s->mu2 : c.take<float>(M);
     }
@@ -94,10 +94,8 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
   }
   e->hf = c.take<bf16_t>(M * H);
   e->rstdf = c.take<float>(M);
-  if (opt) {
-    e->muf = c.take<float>(M);
-    e->prow = c.take<int64_t>(M);
-  }
+  if (ln) e->muf = c.take<float>(M);
+  if (opt) e->prow = c.take<int64_t>(M);
   const size_t VP = (size_t)e->vpad;
   // ONE [M][Vp] buffer: the loss kernel replaces the logits with d loss / d logits in place (2 x 5 GB -> 5 GB at
   // M = 16384, Vp = 152,320); callers that want the logits get their copy before the loss runs
@@ -132,13 +130,13 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
   if (part < 1024) part = 1024;
   const size_t n_chunks = ((size_t)e->n_params + grad_chunk_elems() - 1) / grad_chunk_elems();  // gradient-norm chunk sums
   if (part < n_chunks) part = n_chunks;
-  if (opt && part < 2 * (size_t)rmsnorm_bwd_blocks((int)M) * H) part = 2 * (size_t)rmsnorm_bwd_blocks((int)M) * H;  // final LN: dw | db
+  if (ln && part < 2 * (size_t)rmsnorm_bwd_blocks((int)M) * H) part = 2 * (size_t)rmsnorm_bwd_blocks((int)M) * H;  // final LN: dw | db
   e->part_ws = c.take<float>(part);
   e->ln_ps = (size_t)rmsnorm_bwd_blocks((int)M) * H;
   e->bias_ps = (size_t)colsum_blocks((int)M) * e->QKV;
   e->ln_part = c.take<float>(e->ln_ps * 2 * L);
   e->bias_part = c.take<float>(e->bias_ps * L);
-  if (opt) {
+  if (ln) {
     e->hb_ps = (size_t)colsum_blocks((int)M) * H;
     e->ib_ps = (size_t)colsum_blocks((int)M) * I;
     e->lnb_part = c.take<float>(e->ln_ps * 2 * L);
@@ -156,7 +154,7 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
                        2 * ((H + 15) / 16) + ((size_t)e->QKV + 15) / 16;
     size_t tail = (H + 15) / 16;
     if (e->untied) tail += gemm_tn_sumsq_slots(e->vpad, (int)H);  // the head's gradient is a final store of its own
-    if (opt) {  // + fc1 at N = I, the LayerNorm biases, bo, b1, b2, the final norm's bias and the position table's conversion
+    if (ln) {  // + fc1 at N = I, the LayerNorm biases, bo, b1, b2, the final norm's bias and the position table's conversion
       per_layer += gemm_tn_sumsq_slots((int)I, (int)H) + 2 * ((H + 15) / 16) + 2 * ((H + 15) / 16) + (I + 15) / 16;
       tail += (H + 15) / 16 + (size_t)f32_to_bf16_sumsq_slots((size_t)e->npos * H) + (size_t)e->npos * H / grad_chunk_elems() + 1;
     }
@@ -164,6 +162,7 @@ size_t carve(SlamEngine* e, char* base, int64_t Mmax) {
     e->gn_part = c.take<float>(e->gn_cap);
   }
   e->scal = c.take<float>(64);
+  if (e->arch == 4) e->ln_t = c.take<float>(2 * M * H);  // "neox_split_ln": the two fp32 LayerNorm-backward terms
   // "dropout_thr16" != 0: the masked residual gradients, behind everything else (the layout above is the same with and without)
   for (int p = 0; p < 2; ++p)
     for (int s = 0; s < 2; ++s) e->dmask[p][s] = e->dropout_thr16 ? c.take<bf16_t>(M * H) : nullptr;
@@ -334,13 +333,27 @@ int join_params(SlamEngine* h, hipStream_t st) { return h->pwaits.empty() ? 0 : 
 // The family's row norm over M rows: LayerNorm with a bias and a saved mean (OPT; boff and mu are OPT's alone), else RMSNorm
 int norm_fwd(SlamEngine* h, const bf16_t* x, int64_t woff, int64_t boff, bf16_t* y, float* mu, float* rstd, int M, hipStream_t st) {
   const bf16_t* P = h->params;
-  if (h->arch == 1) return layernorm_fwd(x, P + woff, P + boff, y, mu, rstd, M, h->d.hidden, h->d.rms_eps, st);
+  if (h->ln()) return layernorm_fwd(x, P + woff, P + boff, y, mu, rstd, M, h->d.hidden, h->d.rms_eps, st);
   return rmsnorm_fwd(x, P + woff, y, rstd, M, h->d.hidden, h->d.rms_eps, st);
 }
 
 }  // namespace slam_impl
 
 namespace {
+
+// GPT-NeoX: the layer's two LayerNorms of hs[l] -> x1, x2 with one mean / rstd: one pass, or ("neox_split_ln") the single
+// kernel twice - the same bits, and the second launch rewrites the statistics with their own values
+int neox_norms_fwd(SlamEngine* h, int l, int M, hipStream_t st) {
+  const bf16_t* P = h->params;
+  const LayerOff& o = h->lo[l];
+  LayerAct& a = h->la[l];
+  const int H = h->d.hidden;
+  const float eps = h->d.rms_eps;
+  if (!h->neox_split_ln)
+    return layernorm_dual_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, P + o.ln2, P + o.ln2_b, a.x1, a.x2, a.mu1, a.rstd1, M, H, eps, st);
+  if (int r = layernorm_fwd(h->hs[l], P + o.ln1, P + o.ln1_b, a.x1, a.mu1, a.rstd1, M, H, eps, st)) return r;
+  return layernorm_fwd(h->hs[l], P + o.ln2, P + o.ln2_b, a.x2, a.mu1, a.rstd1, M, H, eps, st);
+}
 
 // One decoder layer's forward launches over M tokens: hs[l] -> la[l] (-> hs[l + 1]). The one body that slam_forward,
 // slam_prefill and the recomputation in slam_backward share, so a re-run issues the forward's own calls in the forward's own
@@ -358,6 +371,23 @@ int layer_forward(SlamEngine* h, int l, int M, bool rerun, hipStream_t st) {
   if (!rerun) {
     CK(wait_chunk(h, 1 + l, st));
     CK(wait_params(h, o.ln1, o.ln1 + h->layer_stride, st));
+  }
+  if (h->arch == 4) {  // GPT-NeoX: x_out = x + attn(ln1(x)) + mlp(ln2(x)) - both norms read hs[l]
+    TK(F_NORM_FWD, st, neox_norms_fwd(h, l, M, st));
+    if (h->rot == d.head_dim && d.head_dim == 64) {  // full rotation: bias + RoPE in the projection epilogue, as Qwen2
+      TK(F_QKV_FWD, st, gemm_nt_rope(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, h->cosb, h->sinb, h->cosq, h->sinq, nH, 2 * nH, M, h->QKV, H, st));
+    } else {
+      const int slot = fam_begin(h, F_QKV_FWD, st);
+      CK(gemm_nt(a.x1, P + o.wqkv, a.qkv, P + o.bqkv, nullptr, M, h->QKV, H, st));
+      if (h->rot == d.head_dim) CK(rope_apply(a.qkv, h->QKV, M, 2 * nH, d.head_dim, h->cosb, h->sinb, 0, st, nH, qscale));
+      else CK(rope_partial(a.qkv, h->QKV, M, 2 * nH, d.head_dim, h->rot, h->cosq, h->sinq, 0, st, nH, qscale));
+      fam_end(h, slot, st);
+    }
+    TK(F_ATTN_FWD, st, attn_fwd(a.qkv, a.o, a.lse, h->cur_seg_s, h->attn_plan_buf, h->attn_tune, M, nH, nKV, d.head_dim, st));
+    TK(F_O_FWD, st, gemm_nt(a.o, P + o.wo, a.hmid, P + o.bo, h->hs[l], M, H, nH * d.head_dim, st));  // hmid = x + attn
+    TK(F_GATEUP_FWD, st, gemm_nt_gelu(a.x2, P + o.wgu, a.gu, a.act, P + o.b1, M, I, H, st));        // gu = pre, act = gelu(pre)
+    if (!rerun) TK(F_DOWN_FWD, st, gemm_nt(a.act, P + o.wd, h->hs[l + 1], P + o.b2, a.hmid, M, H, I, st));
+    return SLAM_OK;
   }
   TK(F_NORM_FWD, st, norm_fwd(h, h->hs[l], o.ln1, o.ln1_b, a.x1, a.mu1, a.rstd1, M, st));
   if (h->arch == 3) {  // Qwen3: no bias; per-head RMSNorm + RoPE in one pass behind the projection (never the fused epilogue)
@@ -427,6 +457,11 @@ int rebuild_selective(SlamEngine* h, int l, int M, hipStream_t st) {
   const bf16_t* P = h->params;
   const LayerOff& o = h->lo[l];
   LayerAct& a = h->la[l];
+  if (h->arch == 4) {  // GPT-NeoX: act from the stored pre-activation by the epilogue's own expression on the same rounded input
+    TK(F_NORM_FWD, st, neox_norms_fwd(h, l, M, st));
+    TK(F_GATEUP_FWD, st, gelu_fwd(a.gu, a.act, (size_t)M * I, st));
+    return SLAM_OK;
+  }
   TK(F_NORM_FWD, st, norm_fwd(h, h->hs[l], o.ln1, o.ln1_b, a.x1, a.mu1, a.rstd1, M, st));
   TK(F_NORM_FWD, st, norm_fwd(h, a.hmid, o.ln2, o.ln2_b, a.x2, a.mu2, a.rstd2, M, st));
   if (h->arch == 1) return SLAM_OK;
@@ -462,10 +497,13 @@ int forward_layers(SlamEngine* h, const int64_t* ids, const int64_t* position_id
   // attention kernels' scores leave the matrix pipe in the exp2 domain
   const float qscale = 1.44269504088896340736f / sqrtf((float)d.head_dim);
   const bool opt = h->arch == 1;
-  if (opt) {
+  if (opt || (h->arch == 4 && h->rot != d.head_dim)) {
     const size_t n = (size_t)M * (d.head_dim / 2);
     ident_rope_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(h->cosb, h->sinb, h->cosq, h->sinq, n, qscale);
     CK((int)hipGetLastError());
+    // GPT-NeoX, partial rotation: attn_bwd leaves dq / dk unrotated (the identity tables above) and rope_partial turns them back;
+    // the rotation's own tables [M][rot / 2] go where the pre-scaled query tables live (the scale rides on rope_partial)
+    if (!opt) CK(rope_table(position_ids, M, T, h->rot, d.rope_theta, h->cosq, h->sinq, nullptr, nullptr, qscale, st));
   } else {
     CK(rope_table(position_ids, M, T, d.head_dim, d.rope_theta, h->cosb, h->sinb, h->cosq, h->sinq, qscale, st));
   }
@@ -516,26 +554,32 @@ int slam_engine_create_arch(const SlamModelDesc* desc, int32_t arch, int32_t n_p
 int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_positions, int32_t flags, SlamEngine** out) {
   if (!desc || !out) return SLAM_EINVAL;
   const SlamModelDesc& d = *desc;
-  if (arch != 0 && arch != 1 && arch != 3) return SLAM_EINVAL;  // 2 is not a family
+  if (arch != 0 && arch != 1 && arch != 3 && arch != 4) return SLAM_EINVAL;  // 2 is not a family
   if (flags & ~SLAM_MODEL_UNTIED_HEAD) return SLAM_EINVAL;
   const bool untied = (flags & SLAM_MODEL_UNTIED_HEAD) != 0;
   if (untied && arch == 1) return SLAM_EINVAL;
   if ((d.head_dim != 64 && d.head_dim != 128) || d.n_heads <= 0 || d.n_kv_heads <= 0 || d.n_heads % d.n_kv_heads) return SLAM_EINVAL;
-  if (d.hidden % 8 || d.hidden > (arch == 1 ? 2048 : 4096) || d.vocab <= 0) return SLAM_EINVAL;  // the row-norm kernels' limits
+  const bool ln = arch == 1 || arch == 4;
+  if (d.hidden % 8 || d.hidden > (ln ? 2048 : 4096) || d.vocab <= 0) return SLAM_EINVAL;  // the row-norm kernels' limits
   if (d.n_layers <= 0) return SLAM_EINVAL;
-  if (arch != 1 && d.intermediate % GU_BLK) return SLAM_EINVAL;
+  if (!ln && d.intermediate % GU_BLK) return SLAM_EINVAL;
   if (arch == 3 && (d.intermediate <= 0 || d.n_heads / d.n_kv_heads > 8)) return SLAM_EINVAL;  // the decode kernels' group limit
   // OPT: multi-head attention (kv = q heads), head_dim 64, a position table of n_positions + 2 rows
   if (arch == 1 && (d.n_kv_heads != d.n_heads || d.head_dim != 64 || d.intermediate <= 0 || d.intermediate % 8 || n_positions <= 0))
     return SLAM_EINVAL;
+  // GPT-NeoX: multi-head attention, n_positions = the rotary width (a multiple of 8 in [8, head_dim]), no position table
+  if (arch == 4 && (d.n_kv_heads != d.n_heads || d.hidden % 64 || d.intermediate <= 0 || d.intermediate % 64 || n_positions < 8 ||
+                    n_positions % 8 || n_positions > d.head_dim))
+    return SLAM_EINVAL;
   SlamEngine* e = new SlamEngine();
   e->d = d;
   e->arch = arch;
+  e->rot = arch == 4 ? n_positions : 0;
   e->untied = untied;
   e->npos = arch == 1 ? n_positions + 2 : 0;
   e->QKV = (d.n_heads + 2 * d.n_kv_heads) * d.head_dim;
   e->vpad = d.vocab <= VPAD_SMALL ? VPAD_SMALL : ((d.vocab + 255) / 256) * 256;  // 256: the LM-head GEMM can take the 256 x 256 kernel
-  e->fuse_swiglu = arch != 1 && (d.hidden % 64 == 0) && ((2 * d.intermediate) % 128 == 0);
+  e->fuse_swiglu = !ln && (d.hidden % 64 == 0) && ((2 * d.intermediate) % 128 == 0);
   int64_t off = 0;
   e->off_embed = off;
   add_tensor(e, "embed", off, e->vpad, d.hidden);
@@ -548,7 +592,20 @@ int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_pos
     std::string p = "layers." + std::to_string(l) + ".";
     LayerOff& o = e->lo[l];
     const size_t t0 = e->tensors.size();
-    if (arch == 1) {
+    if (arch == 4) {  // both norms first: they read the same row
+      o.ln1 = off;   add_tensor(e, p + "ln1", off, d.hidden, 1);
+      o.ln1_b = off; add_tensor(e, p + "ln1_b", off, d.hidden, 1);
+      o.ln2 = off;   add_tensor(e, p + "ln2", off, d.hidden, 1);
+      o.ln2_b = off; add_tensor(e, p + "ln2_b", off, d.hidden, 1);
+      o.wqkv = off;  add_tensor(e, p + "wqkv", off, e->QKV, d.hidden);
+      o.bqkv = off;  add_tensor(e, p + "bqkv", off, e->QKV, 1);
+      o.wo = off;    add_tensor(e, p + "wo", off, d.hidden, d.n_heads * d.head_dim);
+      o.bo = off;    add_tensor(e, p + "bo", off, d.hidden, 1);
+      o.wgu = off;   add_tensor(e, p + "w1", off, d.intermediate, d.hidden);
+      o.b1 = off;    add_tensor(e, p + "b1", off, d.intermediate, 1);
+      o.wd = off;    add_tensor(e, p + "w2", off, d.hidden, d.intermediate);
+      o.b2 = off;    add_tensor(e, p + "b2", off, d.hidden, 1);
+    } else if (arch == 1) {
       o.ln1 = off;   add_tensor(e, p + "ln1", off, d.hidden, 1);
       o.ln1_b = off; add_tensor(e, p + "ln1_b", off, d.hidden, 1);
       o.wqkv = off;  add_tensor(e, p + "wqkv", off, e->QKV, d.hidden);
@@ -586,7 +643,7 @@ int slam_engine_create_ex(const SlamModelDesc* desc, int32_t arch, int32_t n_pos
   e->layer_stride = d.n_layers > 1 ? e->lo[1].ln1 - e->lo[0].ln1 : (off - e->lo[0].ln1);
   e->off_norm = off;
   add_tensor(e, "norm", off, d.hidden, 1);
-  if (arch == 1) {
+  if (ln) {
     e->off_norm_b = off;
     add_tensor(e, "norm_b", off, d.hidden, 1);
   }
@@ -745,6 +802,13 @@ int slam_set_option(SlamEngine* h, const char* key, int64_t value) {
     if (h->neftune_alpha > 0.f) h->neftune_call_next = value;  // ignored while NEFTune is off
     return SLAM_OK;
   }
+  if (!strcmp(key, "neox_split_ln") && h) {
+    if (value < 0 || value > 1) return h->fail(SLAM_EINVAL, "value out of range for option neox_split_ln (0 or 1)");
+    if (h->arch != 4) return h->fail(SLAM_EINVAL, "neox_split_ln: the dual LayerNorm exists for the GPT-NeoX family only");
+    h->neox_split_ln = (int)value;
+    h->have_fwd = h->have_loss = false;  // a backward takes the form its forward took
+    return SLAM_OK;
+  }
   if (!strcmp(key, "fuse_swiglu") && h) { h->fuse_swiglu = value != 0; return SLAM_OK; }
   if (!strcmp(key, "fuse_dswiglu") && h) { h->fuse_dswiglu = value != 0; return SLAM_OK; }
   if (!strcmp(key, "fuse_adamw_t") && h) { h->fuse_adamw_t = value != 0; return SLAM_OK; }
@@ -893,10 +957,10 @@ struct Backward {
   const int M = h->B * h->T, H = d.hidden, I = d.intermediate, L = d.n_layers;
   const bf16_t *const P = h->params, *const Pt = h->params_t;  // Pt: the transposed weight images (nullable)
   float* const G = h->grads;
-  const bool opt = h->arch == 1, q3 = h->arch == 3;
+  const bool opt = h->ln(), q3 = h->arch == 3, neox = h->arch == 4;  // opt: the LayerNorm families' common ground
   const bool two = h->wgrad_stream != 0, aux = two && h->aux_side != 0;  // bwd_wgrad_stream, bwd_aux_side
   const int rc = h->recompute;
-  const bool slot_edges = rc && two && L > RC_SLOTS, drop = opt && h->fwd_drop;
+  const bool slot_edges = rc && two && L > RC_SLOTS, drop = h->arch == 1 && h->fwd_drop;
   const int qnb = q3 ? qn_blocks(h, M) : 0;  // Qwen3: blocks of the q / k norm backward
   hipStream_t ws = st;     // the weight gradients' stream: h->wside with bwd_wgrad_stream (begin)
   int acc = 1, fin = 0;    // 0: this backward stores gradients, 1: it adds to them; "grad_final_next" of this call
@@ -1054,8 +1118,59 @@ struct Backward {
     }
     return SLAM_OK;
   }
+  // GPT-NeoX's parallel residual: hs[l + 1] = hs[l] + attn(ln1(hs[l])) + mlp(ln2(hs[l])), so dh reaches both branches and the
+  // residual unchanged. The same steps as layer() below in the same order - MLP, attention, norms - with one norm backward for
+  // both norms at the end: dx2 (through w1) waits in h->dx, dx1 (through wqkv) in the dead hs[l + 1] buffer.
+  int layer_neox(int l) {
+    const int nH = d.n_heads, HD = nH * d.head_dim, hd = d.head_dim;
+    const LayerOff& o = h->lo[l];
+    LayerAct& a = h->la[l];
+    bf16_t* dx1 = h->hs[l + 1];
+    bf16_t* dqkv = l + 1 < L ? h->la[l + 1].qkv : h->dqkv;
+    const size_t MH = (size_t)M * H;
+    if (rc) CK(rebuild(l));
+    CK(proj_wgrad(F_WD_WGRAD, dh, a.act, o.wd, H, I, h->b2_part + (size_t)l * h->hb_ps));
+    {
+      const int slot = fam_begin(h, F_DOWN_DGRAD, st);
+      if (Pt) CK(gemm_nt_dgelu(dh, Pt + o.wd, a.gu, a.gu, M, I, H, st));  // the GELU backward in the dgrad epilogue: gu -> d(pre)
+      else {
+        CK(dgrad(dh, o.wd, h->dact, H, I));
+        CK(gelu_bwd(a.gu, h->dact, (size_t)M * I, st));
+      }
+      fam_end(h, slot, st);
+    }
+    CK(proj_wgrad(F_WGU_WGRAD, a.gu, a.x2, o.wgu, I, H, h->b1_part + (size_t)l * h->ib_ps));
+    TK(F_GATEUP_DGRAD, st, dgrad(a.gu, o.wgu, h->dx, I, H));
+    CK(proj_wgrad(F_WO_WGRAD, dh, a.o, o.wo, H, HD, h->bo_part + (size_t)l * h->hb_ps));
+    TK(F_O_DGRAD, st, dgrad(dh, o.wo, h->d_o, H, HD));
+    {
+      const int slot = fam_begin(h, F_ATTN_BWD, st);
+      CK(attn_bwd(a.qkv, a.o, h->d_o, a.lse, h->dsum, h->nlse, dqkv, h->dkv_part, h->cur_seg_s, h->cur_seg_e, h->attn_plan_buf, h->attn_tune,
+                  h->cosb, h->sinb, M, nH, nH, hd, st));
+      if (h->rot != hd) CK(rope_partial(dqkv, h->QKV, M, 2 * nH, hd, h->rot, h->cosq, h->sinq, 1, st));
+      fam_end(h, slot, st);
+    }
+    CK(proj_wgrad(F_WQKV_WGRAD, dqkv, a.x1, o.wqkv, h->QKV, H, h->bias_part + (size_t)l * h->bias_ps));
+    CK(slot_done(l));
+    TK(F_QKV_DGRAD, st, dgrad(dqkv, o.wqkv, dx1, h->QKV, H));
+    bf16_t* out = a.hmid;  // grad wrt hs[l]: nothing in this backward reads hmid[l]
+    float *pw1 = h->ln_part + (size_t)(2 * l) * h->ln_ps, *pb1 = h->lnb_part + (size_t)(2 * l) * h->ln_ps;
+    float *pw2 = pw1 + h->ln_ps, *pb2 = pb1 + h->ln_ps;
+    const int slot = fam_begin(h, F_NORM_BWD, st);
+    if (!h->neox_split_ln) {
+      CK(layernorm_dual_bwd(dx1, h->dx, h->hs[l], P + o.ln1, P + o.ln2, a.mu1, a.rstd1, dh, out, pw1, pb1, pw2, pb2, M, H, st));
+    } else {
+      CK(layernorm_bwd_term(dx1, h->hs[l], P + o.ln1, a.mu1, a.rstd1, h->ln_t, pw1, pb1, M, H, st));
+      CK(layernorm_bwd_term(h->dx, h->hs[l], P + o.ln2, a.mu1, a.rstd1, h->ln_t + MH, pw2, pb2, M, H, st));
+      CK(dual_add(dh, h->ln_t, h->ln_t + MH, out, MH, st));
+    }
+    fam_end(h, slot, st);
+    dh = out;
+    return SLAM_OK;
+  }
   // One decoder layer, for every family: dh (wrt hs[l + 1]) -> dh (wrt hs[l]), the layer's weight gradients and its partial slabs
   int layer(int l) {
+    if (neox) return layer_neox(l);
     const int nH = d.n_heads, nKV = d.n_kv_heads, HD = nH * d.head_dim, GU = opt ? I : 2 * I;  // GU: columns of gate|up / fc1
     const LayerOff& o = h->lo[l];
     LayerAct& a = h->la[l];
@@ -1163,7 +1278,7 @@ struct Backward {
       CK(embed_bwd(h->last_ids, dh, G + h->off_embed, M, H, VP, d.vocab, d.pad_token_id, h->embed_ws, ws));
       CK(finish_scattered(h->off_embed, (size_t)VP * H));
     }
-    if (opt) {  // learned positions: deterministic token-ordered scatter by position row (no padding_idx), zeroed first when storing
+    if (h->arch == 1) {  // learned positions: deterministic token-ordered scatter by position row (no padding_idx), zeroed first when storing
       const size_t ne = (size_t)h->npos * H;
       if (!acc) CK((int)hipMemsetAsync(G + h->off_pos, 0, ne * sizeof(float), ws));
       CK(embed_bwd(h->prow, dh, G + h->off_pos, M, H, h->npos, h->npos, -1, h->embed_ws, ws));

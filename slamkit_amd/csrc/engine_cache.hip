@@ -45,6 +45,7 @@ static std::vector<W8Shape> w8_matrix_list(const SlamEngine* h, bool include_hea
 // why the FP8 decode copy cannot exist for this engine (nullptr: it can)
 static const char* w8_refusal(const SlamEngine* h) {
   if (h->arch == 1) return "FP8 decode weights: the OPT family has no decode path";
+  if (h->arch == 4) return "FP8 decode weights: the GPT-NeoX family has no decode path";
   const SlamModelDesc& d = h->d;
   if (d.hidden % W8_K_GRAIN || d.intermediate % W8_K_GRAIN || (d.n_heads * d.head_dim) % W8_K_GRAIN)
     return "FP8 decode weights need hidden, intermediate and n_heads * head_dim to be multiples of 64";
@@ -110,6 +111,7 @@ int extend_common(SlamEngine* h, const int64_t* ids, const int32_t* new_lens, in
   if (!h || !ids || !new_lens || !lens || !logits_out || B <= 0 || T <= 0 || (score && !lp_out)) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
+  if (h->arch == 4) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only (this engine is GPT-NeoX)");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   // shared mode: the two scoring calls run (two-region chunk attention); a sequence continues with slam_decode_step
   if (h->kv_shared && mode == EXT_LAST) return h->fail(SLAM_ESTATE, "slam_extend* in the shared-prompt mode: prefill again to leave it");
@@ -217,13 +219,14 @@ size_t slam_kv_cache_bytes_ex(SlamEngine* h, int32_t max_batch, int32_t capacity
   const SlamModelDesc& d = h->d;
   const size_t vectors = (size_t)d.n_layers * 2 * max_batch * d.n_kv_heads * capacity;
   if (dtype == SLAM_KV_BF16) return vectors * d.head_dim * sizeof(bf16_t);
-  return h->arch == 1 ? 0 : vectors * (d.head_dim + 1);  // codes, then one exponent byte per vector
+  return h->no_cache() ? 0 : vectors * (d.head_dim + 1);  // codes, then one exponent byte per vector
 }
 int slam_bind_kv_cache_ex(SlamEngine* h, void* cache, size_t bytes, int32_t max_batch, int32_t capacity, int32_t dtype) {
   if (!h || !cache || max_batch <= 0 || capacity <= 0) return SLAM_EINVAL;
   if (dtype != SLAM_KV_BF16 && dtype != SLAM_KV_FP8_E4M3)
     return h->fail(SLAM_EINVAL, "KV cache dtype must be SLAM_KV_BF16 (0) or SLAM_KV_FP8_E4M3 (1)");
   if (dtype == SLAM_KV_FP8_E4M3 && h->arch == 1) return h->fail(SLAM_EINVAL, "FP8 KV cache: the OPT family has no KV cache");
+  if (dtype == SLAM_KV_FP8_E4M3 && h->arch == 4) return h->fail(SLAM_EINVAL, "FP8 KV cache: the GPT-NeoX family has no KV cache");
   if (((uintptr_t)cache) & 255) return h->fail(SLAM_EINVAL, "KV cache must be 256-byte aligned");
   if (bytes < slam_kv_cache_bytes_ex(h, max_batch, capacity, dtype)) return h->fail(SLAM_ENOMEM, "KV cache too small");
   h->kv = (bf16_t*)cache;
@@ -296,6 +299,7 @@ static int prefill_common(SlamEngine* h, const int64_t* ids, const int32_t* lens
   if (!h || !ids || !lens || !logits_out || B <= 0 || T <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
+  if (h->arch == 4) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only (this engine is GPT-NeoX)");
   if (prefix) {
     if (!h->kvp) return h->fail(SLAM_ESTATE, "bind a prompt store first (slam_bind_kv_prefix)");
     if (B > h->kvp_pmax || T > h->kvp_cap) return h->fail(SLAM_EINVAL, "prefill batch exceeds the bound prompt store");
@@ -347,7 +351,7 @@ int slam_prefill(SlamEngine* h, const int64_t* ids, const int32_t* lens, int32_t
 }
 
 size_t slam_kv_prefix_bytes(SlamEngine* h, int32_t max_prompts, int32_t prefix_capacity) {
-  if (!h || max_prompts <= 0 || prefix_capacity <= 0 || h->arch == 1) return 0;
+  if (!h || max_prompts <= 0 || prefix_capacity <= 0 || h->no_cache()) return 0;
   const SlamModelDesc& d = h->d;
   return (size_t)d.n_layers * 2 * max_prompts * d.n_kv_heads * prefix_capacity * d.head_dim * sizeof(bf16_t) +
          (size_t)max_prompts * sizeof(int32_t);
@@ -362,6 +366,7 @@ int slam_bind_kv_prefix(SlamEngine* h, void* buf, size_t bytes, int32_t max_prom
   if (!buf) return SLAM_OK;
   if (max_prompts <= 0 || prefix_capacity <= 0) return SLAM_EINVAL;
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "prompt store: the OPT family has no KV cache");
+  if (h->arch == 4) return h->fail(SLAM_EINVAL, "prompt store: the GPT-NeoX family has no KV cache");
   if (((uintptr_t)buf) & 255) return h->fail(SLAM_EINVAL, "prompt store must be 256-byte aligned");
   const size_t need = slam_kv_prefix_bytes(h, max_prompts, prefix_capacity);
   if (bytes < need) return h->fail(SLAM_ENOMEM, "prompt store too small");
@@ -399,6 +404,7 @@ int slam_decode_step(SlamEngine* h, const int64_t* ids, int32_t* lens, int32_t B
   if (!h || !ids || !lens || !logits_out || B <= 0) return SLAM_EINVAL;
   if (!h->params || !h->ws) return h->fail(SLAM_ESTATE, "bind params and workspace first");
   if (h->arch == 1) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only");
+  if (h->arch == 4) return h->fail(SLAM_EINVAL, "KV-cached generation is implemented for the Qwen2 family only (this engine is GPT-NeoX)");
   if (!h->kv) return h->fail(SLAM_ESTATE, "bind a KV cache first");
   if (!h->kv_ready) return h->fail(SLAM_ESTATE, "slam_decode_step needs a slam_prefill into the bound cache first");
   if (B != h->kv_B) return h->fail(SLAM_EINVAL, "decode batch differs from the prefill batch");

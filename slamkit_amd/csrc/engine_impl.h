@@ -23,7 +23,7 @@ constexpr int VPAD_SMALL = 512;  // vocabularies up to 512 (the speech-unit LMs)
 constexpr int GU_BLK = 32;  // Wgu rows / gate|up columns come in blocks of 32 gate + 32 up
 constexpr int RC_SLOTS = 3;  // "recompute": shared activation slots (layer l uses slot l mod 3; DESIGN.md has the hazard table)
 
-// OPT (arch 1) keeps fc1 in `wgu` and fc2 in `wd`; ln1_b, bo, ln2_b, b1, b2 are OPT's alone. Qwen3 (arch 3) has no bqkv (-1);
+// OPT (arch 1) and GPT-NeoX (arch 4) keep fc1 in `wgu` and fc2 in `wd`; ln1_b, bo, ln2_b, b1, b2 are theirs alone. Qwen3 (arch 3) has no bqkv (-1);
 // q_norm, k_norm are Qwen3's alone
 struct LayerOff {
   int64_t ln1, wqkv, bqkv, wo, ln2, wgu, wd;
@@ -32,6 +32,7 @@ struct LayerOff {
 };
 
 // OPT: gu is [M][I] (the layer's d(act) in backward), act the post-ReLU fc1 output; mu1 / mu2 the LayerNorm means
+// GPT-NeoX: gu is the fc1 pre-activation [M][I] (d(pre) in backward), act = gelu(gu); both LayerNorms read hs[l]: mu1 / rstd1 only
 struct LayerAct {
   bf16_t *hmid, *x1, *x2, *qkv, *o, *gu, *act;
   float *rstd1, *rstd2, *lse;
@@ -47,7 +48,13 @@ using namespace slam_impl;
 
 struct SlamEngine {
   SlamModelDesc d;
-  int arch = 0;  // 0 Qwen2, 1 OPT, 3 Qwen3 (slam_engine_create_arch)
+  int arch = 0;  // 0 Qwen2, 1 OPT, 3 Qwen3, 4 GPT-NeoX (slam_engine_create_arch)
+  bool ln() const { return arch == 1 || arch == 4; }        // LayerNorm with bias, biases on every projection, one [M][I] MLP buffer
+  bool no_cache() const { return arch == 1 || arch == 4; }  // families without KV-cached generation
+  // GPT-NeoX: rotary width (the first `rot` dims of a head rotate, dim i with i + rot / 2; rot == head_dim is the Qwen2 path);
+  // "neox_split_ln" = 1 runs the layer's two LayerNorms as two single launches (+ an add in backward): the dual kernels' cross-check
+  int rot = 0, neox_split_ln = 0;
+  float* ln_t = nullptr;  // GPT-NeoX, split form: the two fp32 backward terms, 2 x [M][H]
   int npos = 0;  // OPT: rows of the learned position table (n_positions + 2, HF's offset)
   int QKV;  // (nH + 2 nKV) * hd
   int vpad = VPAD_SMALL;  // embedding / logits rows: 512, or vocab rounded up to 256 beyond that
@@ -352,7 +359,7 @@ int for_each_param_group(SlamEngine* h, int chunk, F&& fn) {
   if (!r && chunk >= 1 && chunk <= L) r = for_each_layer_tensor(h, chunk - 1, 1, fn);
   if (!r && (chunk < 0 || chunk == L + 1)) {
     r = fn(h->off_norm, H, 1, 1);
-    if (!r && h->arch == 1) r = fn(h->off_norm_b, H, 1, 1);
+    if (!r && h->ln()) r = fn(h->off_norm_b, H, 1, 1);
     if (!r && h->untied) r = fn(h->off_head, h->vpad, H, 1);
   }
   return r;

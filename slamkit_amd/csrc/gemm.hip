@@ -113,7 +113,25 @@ struct GemmArgs {
   // the 4-column one) have them: the persistent and 256 x 224 launches are not chosen when either is set.
   int relu;
   const bf16_t* relu_mask;
+  // GPT-NeoX's GELU FFN on the same epilogues. gelu_act [R][ldc] (forward, with bias): C keeps the pre-activation
+  // pre = bf16(acc + bias) and gelu_act = bf16(gelu(float(pre))), exact erf form on the ROUNDED pre - what a later pass can rebuild
+  // from C alone. gelu_mask = 1 (backward): relu_mask holds pre and C = acc * gelu'(float(pre)) instead of the ReLU mask.
+  bf16_t* gelu_act;
+  int gelu_mask;
 };
+
+// exact (erf) GELU and its derivative in fp32: gelu(x) = x Phi(x), gelu'(x) = Phi(x) + x phi(x)
+SLAM_DEVICE float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+SLAM_DEVICE float dgelu_erf(float x) {
+  return 0.5f * (1.f + erff(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
+}
+SLAM_DEVICE uint4 gelu_bf16x8(const uint4& pre) {
+  float t[8];
+  unpack_bf16x8(pre, t);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) t[e] = gelu_erf(t[e]);
+  return pack_bf16x8(t);
+}
 
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
 SLAM_DEVICE void st_out(bf16_t* ptr, const uint4& v, int nt) {
@@ -284,13 +302,13 @@ SLAM_DEVICE void epilogue8(const GemmArgs& p_, const f32x4_t (&acc)[4][4], int r
     void* C; bf16_t* act; bf16_t* gu; int R, Cn, ldc, nt_store;
     const bf16_t* bias; const bf16_t* resid; const float* rope_cos; const float* rope_sin; int rope_heads;
     const float* rope_cos_q; const float* rope_sin_q; int rope_q_heads;
-    int relu; const bf16_t* relu_mask;
+    int relu; const bf16_t* relu_mask; bf16_t* gelu_act; int gelu_mask;
   };
   const Fields p = {p_.C, p_.act, p_.gu, p_.R, p_.Cn, p_.ldc, p_.nt_store,
                   LEAN ? nullptr : p_.bias, LEAN ? nullptr : p_.resid, LEAN ? nullptr : p_.rope_cos,
                   LEAN ? nullptr : p_.rope_sin, LEAN ? 0 : p_.rope_heads,
                   LEAN ? nullptr : p_.rope_cos_q, LEAN ? nullptr : p_.rope_sin_q, LEAN ? 0 : p_.rope_q_heads,
-                  LEAN ? 0 : p_.relu, LEAN ? nullptr : p_.relu_mask};
+                  LEAN ? 0 : p_.relu, LEAN ? nullptr : p_.relu_mask, LEAN ? nullptr : p_.gelu_act, LEAN ? 0 : p_.gelu_mask};
   // lane holds C[m][cq(q) .. +7] for q = 0, 1 in fragments (2q, 2q+1): 16-byte accesses throughout
   const int cw = col0 + wn * 64 + g * 8;  // + 32 q
   uint4 bb4[2];
@@ -368,8 +386,13 @@ SLAM_DEVICE void epilogue8(const GemmArgs& p_, const f32x4_t (&acc)[4][4], int r
       if (p.relu_mask) {
         float a[8];
         unpack_bf16x8(mm4[q], a);
+        if (p.gelu_mask) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[q][e] = a[e] > 0.f ? v[q][e] : 0.f;
+          for (int e = 0; e < 8; ++e) v[q][e] *= dgelu_erf(a[e]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[q][e] = a[e] > 0.f ? v[q][e] : 0.f;
+        }
       }
     }
     // fused RoPE: the wave's 64 columns are one head; q = 0 / 1 hold d and d + 32 of the same lane
@@ -389,8 +412,11 @@ SLAM_DEVICE void epilogue8(const GemmArgs& p_, const f32x4_t (&acc)[4][4], int r
     }
     if (mok) {
 #pragma unroll
-      for (int q = 0; q < 2; ++q)
-        st_out(reinterpret_cast<bf16_t*>(p.C) + rowoff + cw + 32 * q, pack_bf16x8(v[q]), p.nt_store);
+      for (int q = 0; q < 2; ++q) {
+        const uint4 o = pack_bf16x8(v[q]);
+        st_out(reinterpret_cast<bf16_t*>(p.C) + rowoff + cw + 32 * q, o, p.nt_store);
+        if (p.gelu_act) st_out(p.gelu_act + rowoff + cw + 32 * q, gelu_bf16x8(o), p.nt_store);
+      }
       // fused SwiGLU: this wave's 64 columns are [32 gate | 32 up] = (q 0 | q 1) of the same lane
       if (p.act) {
         float a8[8];
@@ -583,13 +609,13 @@ SLAM_DEVICE void epilogue32(const GemmArgs& p_, const f32x16_t (&acc)[2][2], int
     void* C; bf16_t* act; bf16_t* gu; int R, Cn, ldc, nt_store;
     const bf16_t* bias; const bf16_t* resid; const float* rope_cos; const float* rope_sin; int rope_heads;
     const float* rope_cos_q; const float* rope_sin_q; int rope_q_heads;
-    int relu; const bf16_t* relu_mask;
+    int relu; const bf16_t* relu_mask; bf16_t* gelu_act; int gelu_mask;
   };
   const Fields p = {p_.C, p_.act, p_.gu, p_.R, p_.Cn, p_.ldc, p_.nt_store,
                   LEAN ? nullptr : p_.bias, LEAN ? nullptr : p_.resid, LEAN ? nullptr : p_.rope_cos,
                   LEAN ? nullptr : p_.rope_sin, LEAN ? 0 : p_.rope_heads,
                   LEAN ? nullptr : p_.rope_cos_q, LEAN ? nullptr : p_.rope_sin_q, LEAN ? 0 : p_.rope_q_heads,
-                  LEAN ? 0 : p_.relu, LEAN ? nullptr : p_.relu_mask};
+                  LEAN ? 0 : p_.relu, LEAN ? nullptr : p_.relu_mask, LEAN ? nullptr : p_.gelu_act, LEAN ? 0 : p_.gelu_mask};
   const int cl = cbase + 16 * h;  // + 32 nb
   uint4 bb4[2][2];
   if (p.bias) {
@@ -686,8 +712,13 @@ SLAM_DEVICE void epilogue32(const GemmArgs& p_, const f32x16_t (&acc)[2][2], int
         for (int u = 0; u < 2; ++u) {
           float a[8];
           unpack_bf16x8(mm4[nb][u], a);
+          if (p.gelu_mask) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[nb][8 * u + e] = a[e] > 0.f ? v[nb][8 * u + e] : 0.f;
+            for (int e = 0; e < 8; ++e) v[nb][8 * u + e] *= dgelu_erf(a[e]);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[nb][8 * u + e] = a[e] > 0.f ? v[nb][8 * u + e] : 0.f;
+          }
         }
       }
     }
@@ -712,8 +743,11 @@ SLAM_DEVICE void epilogue32(const GemmArgs& p_, const f32x16_t (&acc)[2][2], int
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-        for (int u = 0; u < 2; ++u)
-          st_out(reinterpret_cast<bf16_t*>(p.C) + rowoff + cl + 32 * nb + 8 * u, pack_bf16x8(v[nb] + 8 * u), p.nt_store);
+        for (int u = 0; u < 2; ++u) {
+          const uint4 o = pack_bf16x8(v[nb] + 8 * u);
+          st_out(reinterpret_cast<bf16_t*>(p.C) + rowoff + cl + 32 * nb + 8 * u, o, p.nt_store);
+          if (p.gelu_act) st_out(p.gelu_act + rowoff + cl + 32 * nb + 8 * u, gelu_bf16x8(o), p.nt_store);
+        }
       if (p.act) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -1049,7 +1083,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
           const float a[4] = {__uint_as_float(mm[fn].x << 16), __uint_as_float(mm[fn].x & 0xffff0000u),
                               __uint_as_float(mm[fn].y << 16), __uint_as_float(mm[fn].y & 0xffff0000u)};
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[fn][r] = a[r] > 0.f ? v[fn][r] : 0.f;
+          for (int r = 0; r < 4; ++r) v[fn][r] = p.gelu_mask ? v[fn][r] * dgelu_erf(a[r]) : (a[r] > 0.f ? v[fn][r] : 0.f);
         }
       }
       if constexpr (NF == 4) {
@@ -1079,6 +1113,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
         o.x = pack_bf16x2(v[fn][0], v[fn][1]);
         o.y = pack_bf16x2(v[fn][2], v[fn][3]);
         if (mok && n < p.Cn) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.C) + rowoff + n) = o;
+        if (p.gelu_act && mok && n < p.Cn) {
+          uint2 ga;
+          ga.x = pack_bf16x2(gelu_erf(__uint_as_float(o.x << 16)), gelu_erf(__uint_as_float(o.x & 0xffff0000u)));
+          ga.y = pack_bf16x2(gelu_erf(__uint_as_float(o.y << 16)), gelu_erf(__uint_as_float(o.y & 0xffff0000u)));
+          *reinterpret_cast<uint2*>(p.gelu_act + rowoff + n) = ga;
+        }
       }
       if constexpr (NF == 4) {
         // fused SwiGLU: this wave's 64 columns are [32 gate | 32 up]; fragments fn and fn+2 of a lane
@@ -2393,7 +2433,7 @@ static int launch_256(GemmArgs a, hipStream_t st) {
   const int cus_all = cus_dev;
   const int want = T().g256_persist_cus > 0 ? (T().g256_persist_cus & ~7) : cus_all;
   const int cus = want >= 8 && want < cus_all ? want : cus_all;
-  const bool persist = T().g256_persist && tiles > cus && !a.bias && !a.resid && !a.rope_cos && !a.relu && !a.relu_mask;
+  const bool persist = T().g256_persist && tiles > cus && !a.bias && !a.resid && !a.rope_cos && !a.relu && !a.relu_mask && !a.gelu_act;
   if (T().mf32 && T().g256_w4 && persist) {  // four waves of 128 x 128, persistent
     static bool attr4 = false;
     if (!attr4) {
@@ -2421,7 +2461,7 @@ static int launch_256(GemmArgs a, hipStream_t st) {
 // nt224_min_k: long contractions only (gate|up dgrad, K = 9728): interleaved A/B x3 on the Slam-358M step 311.5-312.0k vs 310.3-310.6k tok/s; with the K = 896 / 1152 dgrads as well: no gain  (field of GemmTune, kernels.h)
 static bool use_nt224(const GemmArgs& a) {
   if (!T().nt224 || (a.R % 256) || (a.Cn % 224) || (a.Kc % BK) || a.Kc < 2 * BK) return false;
-  if (a.bias || a.act || a.gu || a.rope_cos || a.relu || a.relu_mask) return false;
+  if (a.bias || a.act || a.gu || a.rope_cos || a.relu || a.relu_mask || a.gelu_act) return false;
   if (T().nt224 == 2) return true;
   return T().shared && a.Kc >= T().nt224_min_k && (a.R / 256) * (a.Cn / 224) >= 64;
 }
@@ -2481,6 +2521,27 @@ int gemm_nt_drelu(const bf16_t* dY, const bf16_t* Wt, bf16_t* dact, const bf16_t
   GemmArgs a{dY, Wt, dact, nullptr, nullptr, nullptr, nullptr, M, N, K, K, K, N, ((K + BK - 1) / BK) * BK, (M + BM - 1) / BM,
              (N + BN - 1) / BN};
   a.relu_mask = act;
+  if ((K % BK == 0) && (N % BN == 0) && T().glds) return launch_nt_dma(a, st);
+  return launch<false, false, false, false>(a, 1, st);
+}
+
+// GPT-NeoX dense_h_to_4h: pre[M,N] = bf16(X W^T + bias), act[M,N] = bf16(gelu(float(pre))), both from the accumulator tile
+int gemm_nt_gelu(const bf16_t* X, const bf16_t* W, bf16_t* pre, bf16_t* act, const bf16_t* bias, int M, int N, int K, hipStream_t st) {
+  if (check_dims(M, N, K, K, K, N) || (K & 7) || !bias || !act) return -1;
+  GemmArgs a{X, W, pre, bias, nullptr, nullptr, nullptr, M, N, K, K, K, N, ((K + BK - 1) / BK) * BK, (M + BM - 1) / BM,
+             (N + BN - 1) / BN};
+  a.gelu_act = act;
+  if ((K % BK == 0) && (N % BN == 0) && T().glds) return launch_nt_dma(a, st);
+  return launch<false, false, false, false>(a, 1, st);
+}
+// GPT-NeoX dense_4h_to_h dgrad with the GELU backward in the epilogue: d(pre)[M,N] = (dY[M,K] Wt[N,K]^T) * gelu'(float(pre));
+// dpre may be pre itself (every element is read and written by the same lane)
+int gemm_nt_dgelu(const bf16_t* dY, const bf16_t* Wt, bf16_t* dpre, const bf16_t* pre, int M, int N, int K, hipStream_t st) {
+  if (check_dims(M, N, K, K, K, N) || (K & 7)) return -1;
+  GemmArgs a{dY, Wt, dpre, nullptr, nullptr, nullptr, nullptr, M, N, K, K, K, N, ((K + BK - 1) / BK) * BK, (M + BM - 1) / BM,
+             (N + BN - 1) / BN};
+  a.relu_mask = pre;
+  a.gelu_mask = 1;
   if ((K % BK == 0) && (N % BN == 0) && T().glds) return launch_nt_dma(a, st);
   return launch<false, false, false, false>(a, 1, st);
 }

@@ -63,6 +63,11 @@ int gemm_nt_dswiglu(const bf16_t* dY, const bf16_t* Wt, bf16_t* gu, int M, int N
 // fused into the epilogue: dact = (dY Wt^T) * [act > 0]
 int gemm_nt_relu(const bf16_t* X, const bf16_t* W, bf16_t* act, const bf16_t* bias, int M, int N, int K, hipStream_t st);
 int gemm_nt_drelu(const bf16_t* dY, const bf16_t* Wt, bf16_t* dact, const bf16_t* act, int M, int N, int K, hipStream_t st);
+// GPT-NeoX's GELU FFN (exact erf form): dense_h_to_4h keeps pre = bf16(X W^T + bias) AND act = bf16(gelu(float(pre))) - the
+// backward needs the pre-activation, and act can be rebuilt from it; the dense_4h_to_h dgrad multiplies by gelu'(float(pre)) in
+// the epilogue (dpre may alias pre)
+int gemm_nt_gelu(const bf16_t* X, const bf16_t* W, bf16_t* pre, bf16_t* act, const bf16_t* bias, int M, int N, int K, hipStream_t st);
+int gemm_nt_dgelu(const bf16_t* dY, const bf16_t* Wt, bf16_t* dpre, const bf16_t* pre, int M, int N, int K, hipStream_t st);
 int gemm_nn(const bf16_t* dY, const bf16_t* W, bf16_t* dX, const bf16_t* resid, int M, int N, int K,
             hipStream_t st);
 int gemm_tn_splits(int M, int N, int K);
@@ -117,6 +122,17 @@ int layernorm_fwd(const bf16_t* x, const bf16_t* w, const bf16_t* b, bf16_t* y, 
 // dx (+ dres) and per-block partial slabs of dw and db ([rmsnorm_bwd_blocks(M)][H] each; colsum_finish_many finishes them)
 int layernorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* mean, const float* rstd, const bf16_t* dres,
                   bf16_t* dx, float* dw_part, float* db_part, int M, int H, hipStream_t st);
+// GPT-NeoX's parallel residual: the two LayerNorms of a layer read the same row. Forward: one pass, one mean / rstd, each output
+// the bits of layernorm_fwd. Backward: dx = bf16((d + t1) + t2) with t_k the fp32 LayerNorm-backward term of (dy_k, w_k), and the four
+// partial slabs of layernorm_bwd. layernorm_bwd_term + dual_add are the same result from layernorm_bwd's own kernel, twice.
+int layernorm_dual_fwd(const bf16_t* x, const bf16_t* w1, const bf16_t* b1, const bf16_t* w2, const bf16_t* b2, bf16_t* y1, bf16_t* y2,
+                       float* mean, float* rstd, int M, int H, float eps, hipStream_t st);
+int layernorm_dual_bwd(const bf16_t* dy1, const bf16_t* dy2, const bf16_t* x, const bf16_t* w1, const bf16_t* w2, const float* mean,
+                       const float* rstd, const bf16_t* d, bf16_t* dx, float* dw1_part, float* db1_part, float* dw2_part,
+                       float* db2_part, int M, int H, hipStream_t st);
+int layernorm_bwd_term(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* mean, const float* rstd, float* t,
+                       float* dw_part, float* db_part, int M, int H, hipStream_t st);
+int dual_add(const bf16_t* d, const float* t1, const float* t2, bf16_t* dx, size_t n, hipStream_t st);
 int rmsnorm_bwd_blocks(int M);
 int rmsnorm_bwd(const bf16_t* dy, const bf16_t* x, const bf16_t* w, const float* rstd, const bf16_t* dres,
                 bf16_t* dx, float* dw, int accumulate, float* part, int M, int H, hipStream_t st, bf16_t* dw_img = nullptr,
@@ -129,6 +145,11 @@ int rope_table(const int64_t* pos, int M, int T, int head_dim, float theta, floa
                float qscale, hipStream_t st);
 int rope_apply(bf16_t* qkv, int ld, int M, int nrot_heads, int head_dim, const float* cs, const float* sn, int backward,
                hipStream_t st, int q_heads = 0, float q_scale = 1.f);
+// GPT-NeoX: rotate-half over the first `rot` dims of the first nrot_heads heads (dim i with i + rot/2; tables [M][rot/2]); rot a
+// multiple of 8 in [8, head_dim]. Forward scales ALL dims of the q_heads query heads by q_scale; backward (q_heads = 0) is the
+// transpose rotation alone.
+int rope_partial(bf16_t* qkv, int ld, int M, int nrot_heads, int head_dim, int rot, const float* cs, const float* sn, int backward,
+                 hipStream_t st, int q_heads = 0, float q_scale = 1.f);
 // Qwen3: RMSNorm over head_dim (64 or 128) of every q and k head of qkv [M][ld] with the weights wq / wk [head_dim], then
 // rotate-half RoPE (csq / snq for the nH query heads), fp32 throughout, one rounding at the in-place store; the v columns are
 // not touched. raw_save (bf16 [M][(nH + nKV) head_dim]: the input bits) and rstd_save (fp32 [M][nH + nKV]) are nullable.
@@ -160,6 +181,9 @@ int embed_noise_fwd(const int64_t* ids, const int64_t* pos, const bf16_t* E, con
                     int V, int T, int NP, const NeftSite& n, hipStream_t st);
 // d *= [act > 0] (n a multiple of 8): the ReLU backward without the fused fc2 dgrad epilogue
 int relu_bwd(bf16_t* d, const bf16_t* act, size_t n, hipStream_t st);
+// exact GELU outside a GEMM (n a multiple of 8): act = bf16(gelu(float(pre))); pre = bf16(float(d) gelu'(float(pre))) in place
+int gelu_fwd(const bf16_t* pre, bf16_t* act, size_t n, hipStream_t st);
+int gelu_bwd(bf16_t* pre, const bf16_t* d, size_t n, hipStream_t st);
 // Residual dropout (OPT): the mask of element (m, n) of a site is a function of (seed, call, site, index0 + m H + n) alone
 // (include/slam_engine.h, "dropout_thr16"); thr16 = round(p * 65536), an element is dropped iff its 16 random bits are below it.
 // H and index0 multiples of 8.

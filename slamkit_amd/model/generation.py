@@ -404,6 +404,8 @@ def _resolve(model, gc, extra: dict, a: dict) -> _Request:
         raise ValueError(f"prefill_chunk must be None or an int >= 1 (got {prefill_chunk!r})")
     if model.config.is_opt:
         raise ValueError("generate is not implemented for OPT models (the engine's KV-cached decode covers Qwen2 only)")
+    if getattr(model.config, "is_neox", False):
+        raise ValueError("generate is not implemented for GPT-NeoX models (the engine's KV-cached decode covers Qwen2 only)")
 
     def pick(name, default):
         v = a[name] if name in a else extra.pop(name, None)
@@ -669,8 +671,8 @@ class _DraftProposer:
             raise ValueError(f"assistant_model must be a UnitLM (got {type(draft).__name__})")
         if draft is model:
             raise ValueError("assistant_model must be another model than the target (it needs a KV cache of its own)")
-        if draft.config.is_opt:
-            raise ValueError("assistant_model must not be an OPT model (the engine's KV-cached decode covers Qwen2 only)")
+        if draft.config.is_opt or getattr(draft.config, "is_neox", False):
+            raise ValueError("assistant_model must not be an OPT or GPT-NeoX model (the engine's KV-cached decode covers Qwen2 only)")
         if torch.device(draft.device) != torch.device(model.device):
             raise ValueError(f"assistant_model is on {draft.device}, the target on {model.device}")
         if draft.config.vocab_size != model.config.vocab_size:
@@ -938,6 +940,8 @@ def score_continuations(model, input_ids, attention_mask, continuations, continu
         raise ValueError(f"continuation_lengths must have shape [{BN}], got {list(continuation_lengths.shape)}")
     if model.config.is_opt:
         raise ValueError("score_continuations is not implemented for OPT models (the engine's KV cache covers Qwen2 only)")
+    if getattr(model.config, "is_neox", False):
+        raise ValueError("score_continuations is not implemented for GPT-NeoX models (the engine's KV cache covers Qwen2 only)")
     dev = model.device
     seq_in = input_ids.to(dev, torch.int64)
     cont = continuations.to(dev, torch.int64)

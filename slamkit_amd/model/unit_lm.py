@@ -29,6 +29,8 @@ from .token_lm import TokenLM
 # Qwen2.5-0.5B body (config/model/slam.yaml:7 base_model_name) - the hub is unreachable from a
 # training box, so the dims the reference pulls via AutoConfig.from_pretrained (unit_lm.py:64)
 # are carried here.
+_PYTHIA = dict(rotary_pct=0.25, rotary_emb_base=10000.0, layer_norm_eps=1e-5, hidden_act="gelu", use_parallel_residual=True,
+               attention_bias=True, tie_word_embeddings=False, initializer_range=0.02)
 KNOWN_BASE_CONFIGS = {
     "Qwen/Qwen2.5-0.5B": dict(num_hidden_layers=24, hidden_size=896, num_attention_heads=14, num_key_value_heads=2,
                               head_dim=64, intermediate_size=4864, rms_norm_eps=1e-6, rope_theta=1000000.0,
@@ -59,10 +61,25 @@ KNOWN_BASE_CONFIGS = {
                               max_position_embeddings=2048, init_std=0.02, tie_word_embeddings=True),
     "facebook/opt-1.3b": dict(model_type="opt", num_hidden_layers=24, hidden_size=2048, num_attention_heads=32, ffn_dim=8192,
                               max_position_embeddings=2048, init_std=0.02, tie_word_embeddings=True),
+    # GPT-NeoX (Pythia): the family of the reference's interleaved scale-up recipe (config/train_inter_scale.yaml). The published
+    # configs restated, as for Qwen3 above: a local HuggingFace directory is the authoritative route
+    "EleutherAI/pythia-70m": dict(model_type="gpt_neox", num_hidden_layers=6, hidden_size=512, num_attention_heads=8,
+                                  intermediate_size=2048, **_PYTHIA),
+    "EleutherAI/pythia-160m": dict(model_type="gpt_neox", num_hidden_layers=12, hidden_size=768, num_attention_heads=12,
+                                   intermediate_size=3072, **_PYTHIA),
+    "EleutherAI/pythia-410m": dict(model_type="gpt_neox", num_hidden_layers=24, hidden_size=1024, num_attention_heads=16,
+                                   intermediate_size=4096, **_PYTHIA),
+    "EleutherAI/pythia-1.4b": dict(model_type="gpt_neox", num_hidden_layers=24, hidden_size=2048, num_attention_heads=16,
+                                   intermediate_size=8192, **_PYTHIA),
 }
+# the Pythia checkpoints outside the engine's GPT-NeoX limits, and why
+PYTHIA_REFUSED = {"EleutherAI/pythia-14m": "head_dim 32", "EleutherAI/pythia-31m": "head_dim 32", "EleutherAI/pythia-1b": "head_dim 256",
+                  "EleutherAI/pythia-2.8b": "hidden_size above 2048", "EleutherAI/pythia-6.9b": "hidden_size above 2048",
+                  "EleutherAI/pythia-12b": "hidden_size above 2048"}
 
 ARCH_QWEN2, ARCH_OPT = 0, 1
 ARCH_QWEN3 = 3  # 2 is not a family (the engine refuses it)
+ARCH_NEOX = 4
 
 
 _HF_DIM_KEYS = ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "head_dim",
@@ -87,7 +104,8 @@ def hf_name_is_decayed(name: str, is_opt: bool) -> bool:
     return not (is_opt and "layer_norm." in name)
 
 
-MUON_PROJECTIONS = ("q_proj", "k_proj", "v_proj", "o_proj", "out_proj", "gate_proj", "up_proj", "down_proj", "fc1", "fc2")
+MUON_PROJECTIONS = ("q_proj", "k_proj", "v_proj", "o_proj", "out_proj", "gate_proj", "up_proj", "down_proj", "fc1", "fc2",
+                    "query_key_value", "dense", "dense_h_to_4h", "dense_4h_to_h")
 
 
 def hf_name_is_muon(name: str) -> bool:
@@ -160,6 +178,57 @@ def _opt_base_config(c: dict) -> dict:
                 dropout=p)
 
 
+def _neox_base_config(c: dict) -> dict:
+    """Engine-side `base_config` of a HuggingFace GPTNeoXConfig dict (or of an already converted one: idempotent). The engine
+    runs the parallel-residual form with exact GELU, biases everywhere and plain rotary embedding over the first
+    head_dim * rotary_pct dims; everything else is refused by the name of its field."""
+    missing = [k for k in ("num_hidden_layers", "hidden_size", "num_attention_heads", "intermediate_size") if c.get(k) is None]
+    if missing:
+        raise ValueError(f"GPT-NeoX config without {missing}")
+    H, nH = int(c["hidden_size"]), int(c["num_attention_heads"])
+    if not c.get("use_parallel_residual", True):
+        raise ValueError("GPT-NeoX with use_parallel_residual=False is not supported")
+    if c.get("hidden_act", "gelu") != "gelu":
+        raise ValueError(f"unsupported GPT-NeoX hidden_act {c.get('hidden_act')!r} (gelu, the exact erf form, only)")
+    if not c.get("attention_bias", True):
+        raise ValueError("GPT-NeoX with attention_bias=False is not supported")
+    rp = c.get("rope_parameters") or {}
+    scaling = c.get("rope_scaling") or (rp if rp.get("rope_type", rp.get("type", "default")) not in ("default", None) else None)
+    if scaling:
+        raise ValueError(f"GPT-NeoX with rope_scaling={scaling} is not supported")
+    for k in ("attention_dropout", "hidden_dropout"):
+        if float(c.get(k, 0.0) or 0.0) != 0.0:
+            raise ValueError(f"GPT-NeoX with {k}={c[k]} is not supported (no dropout in this family)")
+    if H % nH or H // nH not in (64, 128):
+        raise ValueError(f"GPT-NeoX head_dim {H / nH:g} is not supported (64 or 128)")
+    if H > 2048:
+        raise ValueError(f"GPT-NeoX hidden_size {H} > 2048 is not supported")
+    hd = H // nH
+    pct = float(c.get("rotary_pct", rp.get("partial_rotary_factor", 0.25)))
+    rot = int(c["rotary_ndims"]) if "rotary_ndims" in c else int(hd * pct)
+    if rot < 8 or rot % 8 or rot > hd:
+        raise ValueError(f"GPT-NeoX rotary_pct {pct:g} gives a rotary width of {rot}: it must be a multiple of 8 in [8, head_dim]")
+    I = int(c["intermediate_size"])
+    if H % 64 or I % 64:
+        raise ValueError(f"GPT-NeoX hidden_size {H} / intermediate_size {I} must be multiples of 64")
+    theta = c.get("rotary_emb_base", c.get("rope_theta", rp.get("rope_theta", 10000.0)))
+    return dict(model_type="gpt_neox", num_hidden_layers=int(c["num_hidden_layers"]), hidden_size=H, num_attention_heads=nH,
+                num_key_value_heads=nH, head_dim=hd, intermediate_size=I, rotary_pct=pct, rotary_ndims=rot,
+                rope_theta=float(theta), layer_norm_eps=float(c.get("layer_norm_eps", 1e-5)),
+                initializer_range=float(c.get("initializer_range", 0.02)),
+                tie_word_embeddings=bool(c.get("tie_word_embeddings", False)))
+
+
+def qkv_hf_to_engine(t: torch.Tensor, n_heads: int, head_dim: int) -> torch.Tensor:
+    """GPT-NeoX's fused query_key_value (weight [3 H][H] or bias [3 H]): HF rows are [n_heads][3][head_dim], the engine's q | k | v."""
+    return t.reshape(n_heads, 3, head_dim, -1).transpose(0, 1).reshape(t.shape)
+
+
+def qkv_engine_to_hf(t: torch.Tensor, n_heads: int, head_dim: int) -> torch.Tensor:
+    """The inverse of qkv_hf_to_engine."""
+    return t.reshape(3, n_heads, head_dim, -1).transpose(0, 1).reshape(t.shape)
+
+
 def base_config_from_hf(c: dict) -> dict:
     """Engine-side `base_config` from a HuggingFace Qwen2, Qwen3 or OPT config dict (a text-LM `config.json`, or the
     `base_config` object the reference's UnitLMConfig serialises, unit_lm.py:63-73). transformers 4.x stores `rope_theta` at
@@ -169,8 +238,10 @@ def base_config_from_hf(c: dict) -> dict:
     mt = c.get("model_type", "qwen2")
     if mt == "opt":
         return _opt_base_config(c)
+    if mt == "gpt_neox":
+        return _neox_base_config(c)
     if mt not in ("qwen2", "qwen3"):
-        raise ValueError(f"the engine implements the Qwen2 and OPT decoder families, and Qwen3, only (model_type={mt!r})")
+        raise ValueError(f"the engine implements the Qwen2 and OPT decoder families, Qwen3 and GPT-NeoX, only (model_type={mt!r})")
     if c.get("hidden_act", "silu") != "silu":
         raise ValueError(f"unsupported hidden_act {c.get('hidden_act')!r}")
     if c.get("use_sliding_window"):
@@ -242,8 +313,10 @@ class UnitLMConfig:
                     base_config = base_config_from_hf(json.load(f))
             elif base_model_name in KNOWN_BASE_CONFIGS:
                 base_config = dict(KNOWN_BASE_CONFIGS[base_model_name])
-                if base_config.get("model_type") == "opt":
+                if base_config.get("model_type") in ("opt", "gpt_neox"):
                     base_config = base_config_from_hf(base_config)
+            elif base_model_name in PYTHIA_REFUSED:
+                raise ValueError(f"{base_model_name} is outside the engine's GPT-NeoX limits: {PYTHIA_REFUSED[base_model_name]}")
             else:
                 raise ValueError(f"unknown base model {base_model_name!r}: pass a local HuggingFace directory or "
                                  f"base_config=dict(...) (no hub access); known: {sorted(KNOWN_BASE_CONFIGS)}")
@@ -262,6 +335,8 @@ class UnitLMConfig:
             base_config["dropout"] = p_drop
         elif p_drop != 0.0:
             raise ValueError(f"dropout={p_drop}: the Qwen2 family has no residual dropout (OPT only)")
+        if base_config.get("model_type") == "gpt_neox":
+            base_config.setdefault("tie_word_embeddings", False)  # GPTNeoXConfig's default: embed_out is a tensor of its own
         base_config.setdefault("head_dim", base_config["hidden_size"] // base_config["num_attention_heads"])
         base_config.setdefault("rms_norm_eps", 1e-6)
         base_config.setdefault("rope_theta", 10000.0)
@@ -302,10 +377,16 @@ class UnitLMConfig:
     def is_qwen3(self) -> bool:
         return self.base_config.get("model_type") == "qwen3"
 
+    @property
+    def is_neox(self) -> bool:
+        return self.base_config.get("model_type") == "gpt_neox"
+
     def engine_arch(self) -> Tuple[int, int]:
         """(arch, n_positions) of slam_engine_create_arch: Qwen2 = (0, 0), OPT = (1, max_position_embeddings), Qwen3 = (3, 0)."""
         if self.is_opt:
             return ARCH_OPT, int(self.base_config["max_position_embeddings"])
+        if self.is_neox:  # the argument carries the rotary width
+            return ARCH_NEOX, int(self.base_config["rotary_ndims"])
         return (ARCH_QWEN3 if self.is_qwen3 else ARCH_QWEN2), 0
 
     @property
@@ -319,7 +400,7 @@ class UnitLMConfig:
 
     def engine_desc(self) -> E.SlamModelDesc:
         b = self.base_config
-        eps = b["layer_norm_eps"] if self.is_opt else b["rms_norm_eps"]  # OPT: the LayerNorm eps travels in rms_eps
+        eps = b["layer_norm_eps"] if self.is_opt or self.is_neox else b["rms_norm_eps"]  # the LayerNorm eps travels in rms_eps
         return E.SlamModelDesc(b["num_hidden_layers"], b["hidden_size"], b["num_attention_heads"],
                                b["num_key_value_heads"], b["head_dim"], b["intermediate_size"], self.vocab_size,
                                self.pad_token_id if self.pad_token_id is not None else -1,
@@ -445,6 +526,8 @@ class UnitLM(TokenLM):
     def _build_key_map(self):
         if self.config.is_opt:
             return self._build_key_map_opt()
+        if self.config.is_neox:
+            return self._build_key_map_neox()
         b, t = self.config.base_config, self.engine.tensors
         nH, nKV, hd, I = b["num_attention_heads"], b["num_key_value_heads"], b["head_dim"], b["intermediate_size"]
         H = b["hidden_size"]
@@ -509,6 +592,40 @@ class UnitLM(TokenLM):
             km[p + "final_layer_norm.bias"] = (t[q + "ln2_b"].offset, (H,))
         self.key_map = km
 
+    def _build_key_map_neox(self):
+        """HF GPTNeoXForCausalLM names under the reference UnitLM's `lm.` prefix. query_key_value carries a third entry
+        ("qkv", n_heads, head_dim): HF's rows are [n_heads][3][head_dim], the engine's q | k | v, and `_view` is the permuted
+        window. Optimizers that reduce per HF tensor see the fused tensor in the engine's row order (hf_param_segments): a
+        row permutation changes neither Adafactor's factors and clip nor Muon's orthogonalisation, beyond the rows' places."""
+        b, t = self.config.base_config, self.engine.tensors
+        H, I, L = b["hidden_size"], b["intermediate_size"], b["num_hidden_layers"]
+        qkv = ("qkv", b["num_attention_heads"], b["head_dim"])
+        d = "lm.gpt_neox."
+        km: Dict[str, tuple] = {}
+        self._embed_key = d + "embed_in.weight"
+        km[self._embed_key] = (t["embed"].offset, (self.config.vocab_size, H))
+        for l in range(L):
+            p, q = f"{d}layers.{l}.", f"layers.{l}."
+            km[p + "input_layernorm.weight"] = (t[q + "ln1"].offset, (H,))
+            km[p + "input_layernorm.bias"] = (t[q + "ln1_b"].offset, (H,))
+            km[p + "post_attention_layernorm.weight"] = (t[q + "ln2"].offset, (H,))
+            km[p + "post_attention_layernorm.bias"] = (t[q + "ln2_b"].offset, (H,))
+            km[p + "attention.query_key_value.weight"] = (t[q + "wqkv"].offset, (3 * H, H), qkv)
+            km[p + "attention.query_key_value.bias"] = (t[q + "bqkv"].offset, (3 * H,), qkv)
+            km[p + "attention.dense.weight"] = (t[q + "wo"].offset, (H, H))
+            km[p + "attention.dense.bias"] = (t[q + "bo"].offset, (H,))
+            km[p + "mlp.dense_h_to_4h.weight"] = (t[q + "w1"].offset, (I, H))
+            km[p + "mlp.dense_h_to_4h.bias"] = (t[q + "b1"].offset, (I,))
+            km[p + "mlp.dense_4h_to_h.weight"] = (t[q + "w2"].offset, (H, I))
+            km[p + "mlp.dense_4h_to_h.bias"] = (t[q + "b2"].offset, (H,))
+        km[d + "final_layer_norm.weight"] = (t["norm"].offset, (H,))
+        km[d + "final_layer_norm.bias"] = (t["norm_b"].offset, (H,))
+        self._head_key = None
+        if not self.config.tie_word_embeddings:
+            self._head_key = "lm.lm_head.weight"  # transformers 5 names GPT-NeoX's head lm_head; `embed_out` (4.x, the published
+            km[self._head_key] = (t["lm_head"].offset, (self.config.vocab_size, H))  # Pythia files) is read as the same tensor
+        self.key_map = km
+
     def hf_decay_flags(self) -> List[bool]:
         """HF Trainer's weight-decay rule per engine tensor, in `engine.tensors` order: True = decayed. Restated from
         transformers `Trainer.get_decay_parameter_names`: every parameter except those of an nn.LayerNorm and those whose name
@@ -542,7 +659,8 @@ class UnitLM(TokenLM):
                 out.append(HFParamSegment(key, shp, off, 1, shp[0], False, 0))
             else:
                 assert len(shp) == 2, f"{key}: no HF decoder parameter here has more than two dimensions"
-                out.append(HFParamSegment(key, shp, off, shp[0], shp[1], True, 1 + int(ent[2]) if len(ent) == 3 else 0))
+                gate_up = len(ent) == 3 and not isinstance(ent[2], tuple)  # a ("qkv", ..) entry is contiguous rows, permuted
+                out.append(HFParamSegment(key, shp, off, shp[0], shp[1], True, 1 + int(ent[2]) if gate_up else 0))
         return out
 
     def hf_muon_segments(self) -> List[HFParamSegment]:
@@ -558,6 +676,11 @@ class UnitLM(TokenLM):
         an [I, H] copy."""
         ent = self.key_map[key]
         off, shp = ent[0], ent[1]
+        if len(ent) == 3 and isinstance(ent[2], tuple):  # GPT-NeoX query_key_value: engine [3][nH][hd][..] seen as HF's [nH][3][hd][..]
+            _, nH, hd = ent[2]
+            n = 3 * nH * hd * (shp[1] if len(shp) == 2 else 1)
+            v = flat[off:off + n].view(3, nH, hd, -1).transpose(0, 1)
+            return v if writable else v.reshape(*shp)
         if len(ent) == 3:
             I, H = shp
             v = flat[off:off + 2 * I * H].view(I // 32, 2, 32, H)[:, ent[2]]
@@ -670,8 +793,8 @@ class UnitLM(TokenLM):
         afterwards is an ordinary bf16 checkpoint of the quantised model). With a tied head and `include_head` the embedding
         table is quantised, being the same tensor. Any later write of the parameters (load_state_dict, an optimizer step) drops
         the codes silently; decode goes on in bf16. Returns the relative RMS error per matrix kind and the byte counts."""
-        if self.config.is_opt:
-            raise ValueError("quantize_decode_weights: the OPT family has no KV-cached decode path")
+        if self.config.is_opt or getattr(self.config, "is_neox", False):
+            raise ValueError("quantize_decode_weights: the OPT and GPT-NeoX families have no KV-cached decode path")
         if dtype != "fp8_e4m3":
             raise ValueError(f"quantize_decode_weights: unknown dtype {dtype!r} (only 'fp8_e4m3')")
         eng = self.engine
@@ -760,11 +883,13 @@ class UnitLM(TokenLM):
     def _canonical_keys(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """Key layouts accepted: the UnitLM layout `lm.model.*` (reference and engine checkpoints) and a raw
         HuggingFace causal LM's `model.*` / `lm_head.weight` (text-LM weights for TWIST initialisation)."""
+        if any(k.startswith(("lm.embed_out.", "embed_out.")) for k in sd):  # GPT-NeoX checkpoints of transformers 4.x
+            sd = {k.replace("embed_out.", "lm_head.", 1) if k.startswith(("lm.embed_out.", "embed_out.")) else k: v for k, v in sd.items()}
         if any(k.startswith("lm.") for k in sd):
             return dict(sd)
         if any(k.startswith("decoder.") for k in sd):  # a bare OPTModel (HF's base_model_prefix is "model")
             return {("lm.model." + k if k.startswith("decoder.") else k): v for k, v in sd.items()}
-        return {("lm." + k if k.startswith(("model.", "lm_head.")) else k): v for k, v in sd.items()}
+        return {("lm." + k if k.startswith(("model.", "lm_head.", "gpt_neox.")) else k): v for k, v in sd.items()}
 
     @torch.no_grad()
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
@@ -777,7 +902,8 @@ class UnitLM(TokenLM):
         self.engine.join()
         sd = self._canonical_keys(sd)
         missing = [k for k in self.key_map if k not in sd]
-        extra = [k for k in sd if k not in self.key_map and not (self._head_key is None and k.endswith("lm_head.weight"))]
+        extra = [k for k in sd if k not in self.key_map and not (self._head_key is None and k.endswith("lm_head.weight"))
+                 and not k.endswith((".attention.bias", ".attention.masked_bias", ".rotary_emb.inv_freq"))]  # old GPT-NeoX buffers
         if strict and (missing or extra):
             raise KeyError(f"state_dict mismatch: {len(missing)} missing (first: {missing[:4]}), "
                            f"{len(extra)} unexpected (first: {extra[:4]})")
@@ -810,6 +936,8 @@ class UnitLM(TokenLM):
             raise ValueError(f"text LM model_type {c.get('model_type')!r} does not match the model's")
         keys = ("num_hidden_layers", "hidden_size", "num_attention_heads", "num_key_value_heads", "intermediate_size",
                 "max_position_embeddings")
+        if self.config.is_neox:
+            keys = keys[:-1] + ("rotary_ndims",)  # no position table; the rotary width is part of the model
         if self.config.is_qwen3:
             keys += ("head_dim",)  # a field of its own there
         for k in keys:
@@ -1302,7 +1430,7 @@ class UnitLM(TokenLM):
         if "base_config" in c:
             base = c["base_config"]
             name = c.get("base_model_name", "local")
-        elif c.get("model_type") in ("qwen2", "qwen3") or (c.get("model_type") == "opt" and all(
+        elif c.get("model_type") in ("qwen2", "qwen3", "gpt_neox") or (c.get("model_type") == "opt" and all(
                 k in c for k in ("num_hidden_layers", "hidden_size", "num_attention_heads", "ffn_dim", "max_position_embeddings"))):
             base, name = c, path
         else:
